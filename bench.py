@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the qgemm hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one `flute.qgemm` launch (M=1, W4G64 NF4 table, fp16, K=N=4096 -
 BASELINE.json configs[1], the shape the metric's target is quoted on) over one
@@ -147,6 +147,7 @@ def flush_l3(device):
 
 
 LAST_TIMING = {}        # of the latest time_graph call: the HIP-event time of the same replay, the clock used
+LAST_OUTPUT = {}        # of the latest time_graph(keep_output=True) call: the last step's output, copied to the host
 
 
 def _timestamp(ts, slot):
@@ -159,7 +160,7 @@ def _timestamp(ts, slot):
         raise RuntimeError(f"flute_debug_timestamp: {rc}")
 
 
-def time_graph(layer, steps, warmup, sync, cold=True, replays=1):
+def time_graph(layer, steps, warmup, sync, cold=True, replays=1, keep_output=False):
     """Capture `steps` launches in one hipGraph, bracketed INSIDE the graph by two device-clock stamps (one-lane kernels
     writing the chip-wide 100 MHz clock: the first runs when everything before it has finished, the second when the last
     step has), replay once.  Returns (ms between the stamps, host wall ms around sync()).  HIP events around the same replay
@@ -168,7 +169,8 @@ def time_graph(layer, steps, warmup, sync, cold=True, replays=1):
     183.0 for 40, 8190 for 2000 - slope 4.09 us per step at every length), i.e. +0.8 us per step at 20 steps and nothing
     at 2000; the stamps see the launches themselves.  cold: flush the caches (untimed) before the timed replay.
     replays > 1: that many timed replays of the same K steps, each behind its own flush and barrier; the MEDIAN replay is returned,
-    every replay's time is kept in LAST_TIMING (median + min)."""
+    every replay's time is kept in LAST_TIMING (median + min).  keep_output: after the timed replays, the
+    output of the last captured step (what its caller receives) is copied to the host into LAST_OUTPUT["y"] (untimed)."""
     for i in range(warmup):
         layer.step(i)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -180,7 +182,7 @@ def time_graph(layer, steps, warmup, sync, cold=True, replays=1):
     with torch.cuda.graph(graph):
         _timestamp(ts, 0)
         for i in range(steps):
-            layer.step(warmup + i)
+            y = layer.step(warmup + i)
         _timestamp(ts, 1)
     # untimed: the first replay pays the upload; then ~30 ms of replays so that the chip is at its sustained clocks
     # when the timed replay starts (a 20-step replay lasts 90 us - far shorter than a clock ramp; measured: 5.9 us
@@ -219,6 +221,9 @@ def time_graph(layer, steps, warmup, sync, cold=True, replays=1):
     LAST_TIMING.update({"events_ms": ev_ms, "device_clock_ms": dev_ms, "replays_ms": [round(r[0], 6) for r in runs],
                         "min_ms": runs[0][0], "median_ms": best})
     LAST_TIMING["clock"] = "device clock stamps inside the graph" if ok else "hip events (device stamps implausible)"
+    LAST_OUTPUT.clear()
+    if keep_output:
+        LAST_OUTPUT["y"] = y.detach().cpu()
     return best, wall_ms
 
 
@@ -410,6 +415,9 @@ def main():
     ap.add_argument("--template-id", type=int, default=-1,
                     help="skip the tuner and use this template id (profiling runs: keeps the tuner's "
                          "candidate launches out of the kernel trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline qgemm returned in its last timed step to "
+                         "DIR/qgemm_out.npy (float32; rank 0). Inputs are seeded: the same arguments give the same inputs")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -454,8 +462,10 @@ def main():
         tid = layer.template_id = args.template_id
     else:
         tid = layer.tune()
-    ev_ms, wall_ms = time_graph(layer, args.steps, args.warmup, sync, replays=5)      # five timed replays of the K steps: the median is the line's figure
+    ev_ms, wall_ms = time_graph(layer, args.steps, args.warmup, sync, replays=5,      # five timed replays of the K steps: the median is the line's figure
+                                keep_output=args.dump_outputs is not None)
     headline_timing = dict(LAST_TIMING)
+    headline_output = LAST_OUTPUT.get("y")
     eager_ms = time_eager(layer, min(args.steps, 500), 10)
     t = torch.tensor([ev_ms, wall_ms, headline_timing["events_ms"], headline_timing["min_ms"]], device=device, dtype=torch.float64)
     ranks_counted = 1
@@ -705,6 +715,11 @@ def main():
             out["tp_mlp_pair"] = tp_pair
         if dist is None and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(N, K, bits, g)
+        if args.dump_outputs is not None:
+            # the [M, N] output of the headline's last timed step (weight copy (warmup + steps - 1) % copies), exact in float32
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "qgemm_out.npy"), headline_output.float().numpy())
         if saved_stdout is not None:
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)

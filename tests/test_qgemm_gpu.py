@@ -1140,3 +1140,35 @@ def test_random_launch_plan_fuzz_sweep(env):
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_fuzz.py"), "600", "5"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(env, tmp_path):
+    """bench.py --dump-outputs DIR writes what the headline qgemm returned in its last timed step (float32).  The inputs
+    are seeded: a second run (the first run's template id given explicitly) dumps the same array, and an eager launch of
+    that step on inputs rebuilt here returns it too.  The result line reports the steps asked for and ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from flute_amd.nf_utils import NF4_VALUES
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 2
+    lines, dumps = [], []
+    for i in range(2):
+        extra = ["--template-id", str(lines[0]["config"]["template_id"])] if i else []
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", str(warmup), "--no-extras", "--no-cpu", "--dump-outputs", str(out)] + extra,
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append(np.load(out / "qgemm_out.npy"))
+    for line in lines:
+        assert line["steps"] == steps and line["ms_per_step"] > 0, line
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1, 4096)
+    assert np.array_equal(dumps[0], dumps[1])
+    M, N, K, bits, g = 1, 4096, 4096, 4, 64
+    layer = bench.Layer(M, N, K, bits, g, torch.float16, env.dev, bench.copies_for(N, K, bits), NF4_VALUES, seed=0)
+    layer.template_id = lines[0]["config"]["template_id"]
+    y = layer.step(warmup + steps - 1).float().cpu().numpy()
+    assert np.array_equal(y, dumps[0])
