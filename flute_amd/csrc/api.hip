@@ -348,6 +348,8 @@ int plan_persistm(int bits, int lg, int M, int N, int K, int num_sms, int ng_ovr
         }
     }
     if (ng_ovr >= 1 && ng_ovr <= 3) ng = ng_ovr;
+    // an override of the sets per workgroup that would need more workgroups than CUs cannot apply: refused, not replaced
+    if (visits_ovr >= 1 && ceil_div(ceil_div(N / 16, ng), visits_ovr) > num_sms) return FLUTE_ERR_SHAPE;
     (void)persistm_model_us(M, N, K, num_sms, ng, &grid, &visits, visits_ovr);
     memset(p, 0, sizeof(*p));
     p->family = kFamilyPersistM;

@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import exact_cases as XC
+
 pytestmark = pytest.mark.gpu
 
 FP16_TOL = 1e-3          # north_star
@@ -130,6 +132,7 @@ def check_shape_case(e, N, K, bits, g, dtype, uniform, Ms, seed, tile_p=32, tune
         assert torch.equal(out, What_rows[:M]), ("one-hot", N, K, bits, g, dtype, M, tid_of(M))
     del E
     What = (table[W.long()] * Sx).float()                                        # [K, N] checker, fp32 copy
+    W_exact = table.double()[W.long()] * Sx.double()                             # lut * s before any rounding (componentwise bound)
     del W, Sx
     for M in Ms:
         X = (torch.randn(M, K, device=d) / 100).to(dtype)
@@ -137,7 +140,8 @@ def check_shape_case(e, N, K, bits, g, dtype, uniform, Ms, seed, tile_p=32, tune
         ref = X.float() @ What
         err = ((out.float() - ref).norm() / ref.norm()).item()
         assert err < tol_of(dtype), (N, K, bits, g, dtype, uniform, M, tid_of(M), err)
-    del What
+        XC.assert_componentwise(out, X, W_exact, K, dtype, what=(N, K, bits, g, dtype, uniform, M, tid_of(M)))
+    del What, W_exact
     torch.cuda.empty_cache()
 
 

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import exact_cases as XC
+
 pytestmark = pytest.mark.gpu
 
 FP16_TOL = 1e-3
@@ -113,6 +115,7 @@ def test_random_vs_oracle_all_M(env, bits, tile_p, dtype):
     K, N, g = 1024, 1024, 64
     W, Q, S, table, table2 = make_case(env, bits, tile_p, g, dtype, K, N, seed=bits * 10 + tile_p)
     What = env.O.dequantize(Q.numpy(), S, table2, bits, g, tile_p).float()
+    W_exact = table.double()[W.long()] * torch.repeat_interleave(S.double(), g, dim=1).T        # lut * s before any rounding
     tids = template_ids_for(env.fa, bits, tile_p)
     for i, M in enumerate(M_VALUES):
         X = (torch.randn(M, K) / 100).to(dtype)
@@ -122,6 +125,7 @@ def test_random_vs_oracle_all_M(env, bits, tile_p, dtype):
         assert D.shape == (M, N) and D.dtype == dtype
         err = rel_err(D, ref)
         assert err < tol_of(dtype), (bits, tile_p, dtype, M, tid, err)
+        XC.assert_componentwise(D, X, W_exact, K, dtype, what=(bits, tile_p, dtype, M, tid))
 
 
 @pytest.mark.parametrize("bits,tile_p", LAYOUTS)
