@@ -2,8 +2,8 @@
 // and dispatch.  Mirrors the role of flute/csrc/qgemm.cpp:39-83 (qgemm_raw) +
 // qgemm_kernel_raw_generated.cu:15-768 (_qgemm_raw's template switch) +
 // qgemm_kernel.hpp:824-939 (qgemm_host), re-thought for gfx950: instead of one
-// Stream-K kernel with 36/144 tile variants there are two kernel families
-// (streaming decode for M <= 2 - on small layers M <= 4 -, MFMA above, block-tiled MFMA for prefill) whose launch geometry is derived
+// Stream-K kernel with 36/144 tile variants there are several kernel families (flute_plan::family: decode kernels for a few
+// rows, per-wave / skinny / split-K / block-tiled MFMA kernels above) whose launch geometry is derived
 // from the template's knobs and the problem shape.  Nothing here is process-global mutable state
 // except the per-device "large LDS granted" cache (mutex-guarded): plan overrides travel with the call.
 #include <hip/hip_runtime.h>
@@ -40,6 +40,7 @@ Ovr ovr_of(const flute_overrides* o) {
 }
 
 constexpr int kMaxLds = 160 * 1024;
+constexpr size_t kTileInLaunchMax = 4 << 20;    // bytes of slabs up to which the per-wave kernel's K slices meet inside the launch (plan_tile)
 constexpr int kFamilyBlock = 3;                 // block-tiled prefill kernel (qgemm_block.h)
 constexpr int kFamilySkinny = 5;                // registers-only MFMA kernel for 3 <= M <= 32 (qgemm_skinny.h)
 constexpr int kFamilySplitK = 6;                // 128 / 64 x 128 / 64 tiles, K split over workgroups, combined in the launch (qgemm_splitk.h)
@@ -48,11 +49,6 @@ constexpr int kFamilyPersistM = 8;              // persistent MFMA decode kernel
 // Workspace layout (every kernel): [0, kXwgFlagBytes) tile state words of the in-launch reductions (xwg.h; zero between
 // calls), fp32 slabs behind them.  A planner sees the room behind the state words only.
 size_t slab_room(size_t workspace_bytes) { return workspace_bytes > kXwgFlagBytes ? workspace_bytes - kXwgFlagBytes : 0; }
-// development A/B (tools/time_cases.py): FLUTE_AMD_B3_TWO_LAUNCH=1 keeps the 3-bit blocks' K slices on fp32 slabs + the reduce launch
-bool block3_two_launch() {
-    static const bool v = [] { const char* e = getenv("FLUTE_AMD_B3_TWO_LAUNCH"); return e && e[0] == '1'; }();
-    return v;
-}
 
 int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 int floor_pow2(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
@@ -645,499 +641,574 @@ int plan_stream(int dtype, int bits, int lg, int M, int N, int K, int num_sms, c
     return FLUTE_OK;
 }
 
-// Per-wave MFMA kernel (2 / 4 bits), TFLOP/s by batch size, 128 <= M < 512 (end of round 6, profiles/r06/planner_regret_bits_4_2_m128_to_512_end_of_round.json:
-// measured 295 / 345 at M = 160 / 192 on 11008 x 4096, 426 / 493 at M = 320 / 384 on 4096^2 - the "520 at M = 256, 465 below" it replaces kept the per-wave
-// kernel at M = 160 / 192 / 320 on 11008 x 4096, 14336 x 4096, 14336 x 3584, 3584 x 14336, 3584 x 8192 where split-K tiles run 30 - 70 % faster)
-double wave_tf_mid(int M, int bits, bool bf) { return (300.0 + 0.75 * (M - 128)) * (bf ? 0.8 : 1.0) * (bits == 2 ? 0.65 : 1.0); }
+// ---- the planner ------------------------------------------------------------------------------------------
 
+// What every entry point checks of a layer - bits, group size (0: none, flute_unpack), template id, then N and K alignment -
+// in the order of its error codes.  *l describes the layer that passes.
+struct Layer { int bits, lg, J, units; flute_template_info t; };
+int check_layer(int bits, int group, int template_id, int N, int K, int k_align, Layer* l) {
+    if (bits != 2 && bits != 3 && bits != 4) return FLUTE_ERR_NUM_BITS;
+    if (group && group != 32 && group != 64 && group != 128 && group != 256) return FLUTE_ERR_GROUP_SIZE;
+    if (!decode_template(bits, template_id, &l->t)) return FLUTE_ERR_TEMPLATE_ID;
+    if (bits == 3 && l->t.tile_p != 32) return FLUTE_ERR_TEMPLATE_ID;   // utils.py:137-139
+    l->bits = bits;
+    l->J = (bits == 3) ? 16 : 16 / bits;
+    l->lg = group ? ilog2(group) : 0;
+    if (N < 1 || K < 1 || N % (l->J * l->t.tile_p) || K % k_align) return FLUTE_ERR_SHAPE;
+    l->units = N / l->J;
+    return FLUTE_OK;
+}
+
+// One planner call: the layer, the shape, the CU count, the workspace and the overrides.
+struct Call : Layer { int dtype, M, N, K, template_id, num_sms; size_t workspace_bytes; Ovr ov; };
+// A plan and the launch arguments the decode kernels take beside it.
+struct Planned { flute_plan p; OneArgs oa; StreamArgs sa; };
+
+int lds_fits(const flute_plan& p) { return p.lds_bytes > (size_t)kMaxLds ? FLUTE_ERR_SHAPE : FLUTE_OK; }
+// workspace of a grid K split whose fp32 slabs are [splitk][M][N] behind the state words
+size_t split_slabs(int splitk, int M, int N) { return splitk > 1 ? (size_t)splitk * M * N * 4 + kXwgFlagBytes : 0; }
+
+// The per-wave kernel's overrides (m_tiles, waves, kw, splitk, slabs, m_block) by their largest value: < 0 none given at all,
+// <= 0 none that asks for anything (0 reads as automatic in the per-wave planner)
+int wave_ovr_max(const Ovr& o) { return std::max({o.m_tiles, o.waves, o.kw, o.splitk, o.slabs, o.m_block}); }
 // ids whose last digit leaves the kernel choice to the planner: 4-bit QuantMapMode digit 0, every 2- / 3-bit id
 bool auto_digit_sk(int bits, int template_id) { return bits != 4 || (template_id % 4) == 0; }
+// ... and, for the 4-bit lean and MFMA decode kernels, SMs_Multiple 1 besides
+bool auto_lean_id(const Call& c) { return c.bits == 4 && (c.template_id % 4) == 0 && c.t.sms_multiple == 1; }
 
+// Streaming decode kernel: M <= 2; its four-row variant (2- / 4-bit) only on request (override family 0, which
+// flute_qgemm_hadamard sets for small layers so that the rotation stays fused): measured at M = 3, 4 the MFMA
+// kernel is as fast on 4096^2 (7.6 vs 7.75 us) and 15-25 % faster on every larger layer (8192x28672: 38.6 vs 48.9).
+// (3-bit layers up to 24 M weights also take it by themselves: their MFMA plans are 256 columns wide per wave -
+// 4096^2 M = 4: 9.9 against 13.7 us; larger 3-bit layers are faster on the MFMA kernel.)
+// round 4: 2- / 4-bit layers up to 16 M weights take the four-row one-shot kernel at M = 3, 4 too (4096^2 M = 4: 6.3 us
+// against 7.1 on the MFMA kernel, profiles/r04_planner_regret_before_fixes.json - the one-shot kernel of round 3 was not
+// there when the MFMA kernel was measured level with the ring kernel)
+// (only ids whose last digit leaves the choice to the planner: a 4-bit id with QuantMapMode digit 3 keeps the skinny MFMA kernel it was
+// tuned on - "a tuned id keeps the kernel it was timed on", tests/test_abi.py)
+bool decode_auto(const Call& c) {
+    if (c.M <= 2) return true;
+    if (c.M > 4) return false;
+    const size_t weights = (size_t)c.N * c.K;
+    if (c.bits == 3) return weights <= ((size_t)24 << 20);
+    return weights <= ((size_t)16 << 20) && auto_digit_sk(c.bits, c.template_id);
+}
+
+// Persistent MFMA decode kernel (qgemm_persistm.h, round 6): by override (family 8), or automatically - under the ids that leave the choice
+// to the planner, as the lean MFMA decode kernel - for 3 <= M <= 16 rows of a 4-bit layer with K >= 6144 (group size 64 / 128).  Measured (profiles/r06/call31_persistm_xr.log,
+// us, table's plan -> this): M = 4: 8192 x 28672 [N x K] 34.6 -> 29.4, 10240 x 8192 20.6 -> 14.3, 4096 x 11008 14.7 -> 9.2, 3584 x 14336 14.6 -> 10.0,
+// 4096 x 14336 14.7 -> 10.5, 8192^2 12.9 -> 11.7, 28672 x 8192 33.0 -> 31.1; M = 16: 10240 x 8192 22.2 -> 17.4, 4096 x 11008 14.9 -> 11.9,
+// 8192^2 15.8 -> 13.9; not taken: K = 4096 (14336 x 4096: 11.1 against 11.5 .. 12.4; the lean MFMA decode kernel's and the skinny kernel's
+// layers)
+// (second sweep, profiles/r06/planner_regret_persistm*.json: also K >= 3584 at M <= 4 - 14336 x 3584 13.2 -> 10.3, 11008 x 4096 11.1 -> 9.6,
+// 6144 x 4096 8.3 -> 7.6 - and at every M <= 16 where K is neither 2048 nor 4096, the lean MFMA decode / skinny kernels' depths -
+// 14336 x 3584 M = 8 13.2 -> 11.9; and no limit on the activations at M > 8: equal at M = 16 on the 28672-wide / -deep layers, 7 - 15 % faster at M = 11)
+// (third step, profiles/r06/call37_persistm_resident_activations.log: with the activations RESIDENT in LDS - K * ceil(M / 4) rows within 64 KB - also
+// K = 4096 at M <= 8: 4096^2 M = 8 5.9 -> 5.5, 11008 x 4096 10.9 -> 9.3, 14336 x 4096 11.4 -> 11.3)
+// 2-bit member (profiles/r06/call38_persistm_2bit.log, us, table's plan -> this): every 2-bit id leaves the choice to the planner and no lean kernel
+// competes - from K = 3584 and 16 M weights at every 3 <= M <= 16: 4096^2 M = 4 / 16 8.4 / 8.6 -> 5.0 / 6.1, 4096 x 11008 14.1 -> 8.1, 10240 x 8192 18.3 -> 13.8,
+// 8192 x 28672 30.7 -> 25.8; above M = 8 not where the busiest workgroup pulls more than 28672 k of sixteen-row activations (28672 x 8192: 33.4 against 31.5)
+bool persistm_auto(const Call& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    const bool pm_k = K >= 6144 || (K >= 3584 && (M <= 8 || (K != 4096 && K != 2048)));
+    const bool pm4 = auto_lean_id(c) && pm_k && (size_t)N * K + (M >= 5 ? 1 : 0) > ((size_t)16 << 20);
+    const bool pm2 = c.bits == 2 && K >= 3584 && (size_t)N * K >= ((size_t)16 << 20);
+    return (pm4 || pm2) && M >= 3 && M <= 16 && (c.lg == 6 || c.lg == 7) &&
+           (long)(N / 16) * 2 >= (long)c.num_sms &&      // (smaller layers: the decode kernels / too few sets for the chip; 4-bit 4096^2 itself from M = 5)
+           wave_ovr_max(c.ov) < 0 && c.ov.one_shot < 0 && c.ov.depth <= 0;
+}
+bool persistm_taken(const Call& c, const flute_plan& p) { return c.bits == 4 || c.M <= 8 || (long)p.visits * c.K <= 28672; }
+
+// Lean MFMA decode kernel (qgemm_fastm.h, round 5): by override (family 7), or automatically for 5 <= M <= 16 rows of a 4-bit layer
+// with K = 2048 / 4096 that ONE round of its workgroups (4 unit rows each) covers, under the ids whose last digit leaves the
+// choice to the planner (QuantMapMode digit 0, SMs_Multiple 1).  Measured (tools/time_cases.py, us, automatic plan of round 4 ->
+// this kernel; profiles/r05/time_cases_fastm*.jsonl): 4096^2 M = 5 / 8 / 16 7.13 / 7.13 / 7.18 -> 5.9 / 5.9 / 6.1, 4096 x 2048
+// 5.7 / 5.7 / 5.8 -> 4.3 / 4.3 / 4.5, 2048 x 4096 7.6 / 7.6 / 7.7 -> 5.4 / 5.4 / 5.6; not taken: more than one round (8192 x 4096:
+// 10.2 .. 10.8 against the skinny kernel's 8.9 .. 9.6: every workgroup pulls all of X through its CU), M <= 4 (the dot-product
+// lean kernel: 5.05 against 5.9)
+// Round 6: two / three column groups per workgroup on ONE staged activation set make wider layers one round of workgroups
+// (profiles/r06/call18_fastm_column_groups.log, M = 16, us, table's plan -> this): 8192 x 4096 10.1 -> 8.9 (2 groups, 256 workgroups),
+// 11008 12.6 -> 11.4 (3 groups, 230), 6144 9.4 -> 8.4, 5120 9.2 -> 8.0, 8192 x 2048 6.9 -> 6.2; M = 8 on 11008 11.6 -> 11.0; not taken:
+// more than one round even at three groups (14336: 16.0 against 13.1; 28672: 30 against 23)
+bool fastm_auto(const Call& c) {
+    const long groups = c.N / 16, ns = c.num_sms;
+    const long wgs = groups <= ns ? groups : (groups <= 2 * ns ? (groups + 1) / 2 : (groups + 2) / 3);
+    return auto_lean_id(c) && c.M >= 5 && c.M <= 16 && (c.K == 4096 || c.K == 2048) && wgs <= ns && wgs * 2 >= ns &&
+           wave_ovr_max(c.ov) < 0;
+}
+
+// Skinny MFMA kernel (qgemm_skinny.h): by override (family 5), by template (4-bit QuantMapMode digit 3 at M <= 16, where
+// the digit's other meaning - two slabs per wave - does not exist; digit 2: never), or automatically (digit 0) for
+// 3 <= M <= 16 on layers whose slabs (64 columns) fill 55 .. 100 % of the CUs in ONE round - a workgroup pulls its slab's
+// weights AND all of X through one CU, so fewer slabs leave CUs idle; wider layers take the per-wave kernel with two
+// slabs per wave (4096 x 28672: 21.1 us against 23.3 here).  Measured (profiles/r03/skinny_lab.jsonl, M = 16, us, per-wave kernel -> skinny):
+// 4096 x 11008 17.9 -> 12.0, 4096 x 14336 18.3 -> 12.6 (M = 4: 17.6 -> 11.8), 4096 x 28672 26.6 -> 23.3, 4096 x 6144
+// 13.1 -> 11.7, 2048 x 8192 7.6 -> 7.0; 4096 x 8192 10.0 -> 11.8 and 4096^2 7.6 -> 11.6 (not taken).
+bool skinny_auto(const Call& c) {
+    const long slabs = c.units / 16;
+    const bool fills = slabs * 20 >= 11L * c.num_sms && slabs <= c.num_sms;
+    const int q4 = c.template_id % 4;
+    return c.bits == 4 && c.M >= 3 && c.M <= 16 && ((q4 == 0 && c.K >= 4096 && fills) || q4 == 3);
+}
+// Round 4: narrower layers through a grid-level K split (the slices of a slab meet inside the launch, xwg.h: 1.5 - 1.7 us
+// of seam, profiles/r04/xwg_seam_price.json) - the smallest power-of-two split that fills 55 % of the CUs, while a
+// slice keeps >= 2048 k.  Measured (profiles/r04_planner_regret_before_fixes.json, us, per-wave kernel -> split skinny):
+// M = 4: 3584 x 8192 10.1 -> 8.7, 8192^2 14.6 -> 13.0, 6144 x 4096 9.2 -> 8.5; M = 16: 3584 x 8192 10.2 -> 9.6; not
+// taken: 4096^2 (four slices of 1024 k: 7.6 against 7.2).  Returns the split, 0: none.
+int skinny_split_auto(const Call& c) {
+    const long slabs = c.units / 16;
+    const int q4 = c.template_id % 4;
+    if (c.ov.splitk >= 0 || c.bits != 4 || c.M < 3 || c.M > 16 || (q4 != 0 && q4 != 3) || c.K < 4096 || slabs * 20 >= 11L * c.num_sms)
+        return 0;
+    int sk = 2;
+    while (sk < 16 && slabs * sk * 20 < 11L * c.num_sms) sk *= 2;
+    return (slabs * sk <= c.num_sms && c.K / sk >= 2048) ? sk : 0;
+}
+
+// Split-K block kernel (qgemm_splitk.h): by override (family 6); by template - Stages 5 of the automatic digit at
+// M >= 128 (SMs_Multiple 1 / 2 / 4: the cost model's best / second / third K split; those ids' old meaning, a quarter of
+// the per-wave kernel's in-workgroup K split, is still reachable through digits 1 .. 3); automatically below, when
+// its modelled time beats what the other MFMA kernels are modelled at
+// (round 4, late: 4-bit layers from M = 33, 2-bit layers from M = 65 - 64-row tiles x K slices against the per-wave kernel:
+// M = 64 x 8192^2 24.7 -> 20.0 us, M = 33 23.7 -> 19.5, M = 96 x 14336 x 4096 41.2 -> 24.6, M = 96 x 8192^2 45.3 -> 28.6;
+// 2 bits M = 96: 8192^2 43.3 -> 29.0, 14336 x 4096 40.5 -> 25.4; 2 bits at M = 64 gain 3 .. 9 % only: left alone)
+// (2 bits: from M = 65 until round 6 - with 64 x 64 tiles M = 48 / 64 gain 25 - 43 %: profiles/r06/planner_regret_before_fixes.json)
+// (overrides of the per-wave kernel - m_tiles, waves, kw, splitk, slabs - mean something else in plan_splitk: a call that sets
+// any of them without family = 6 keeps the per-wave / block kernels)
+bool splitk_regime(const Call& c) {
+    return wave_ovr_max(c.ov) <= 0 && c.bits != 3 && c.M >= 33 && auto_digit_sk(c.bits, c.template_id);
+}
+// (M <= 64: the table's Stages-5 ids of that bucket were tuned on the per-wave kernel's K split)
+bool splitk_stages5(const Call& c) { return splitk_regime(c) && c.t.stages == 5 && c.M > 64; }
+
+// Per-wave MFMA kernel (family 2), 2 / 4 bits: TFLOP/s by batch size (what the block and split-K kernels are priced against)
+double wave_tflops(const Call& c) {
+    const int M = c.M;
+    const bool bf = c.dtype == FLUTE_BF16;
+    // (2-bit layers: twice the lookups per byte - the per-wave kernel ran M = 384 on 4096^2 at 316 TFLOP/s where the 4-bit layer runs 503:
+    // profiles/r06_planner_regret_between_final.json)
+    // (the 2-bit factor holds below M = 128 too - it was once applied above that branch only: 2-bit M = 48 on 4096^2 kept the per-wave kernel
+    // x 4 K slices, 15.0 us, where 64 x 64 tiles x 4 slices run 11.1: profiles/r06_planner_regret_final_tree_between.json)
+    const double b2 = c.bits == 2 ? 0.65 : 1.0;
+    // below M = 128 (measured fp16, tools/time_cases.py): 220 .. 280 TFLOP/s at M = 48, 270 .. 350 at M = 64 .. 96 on layers up to
+    // 14336 columns; 490 .. 570 on 28672 columns (two slabs per wave, every CU busy)
+    if (M < 128) return std::min(300.0, 5.5 * M) * (bf ? 0.8 : 1.0) * (c.N >= 16384 ? 1.8 : 1.0) * b2;
+    // 128 <= M < 512 (end of round 6, profiles/r06/planner_regret_bits_4_2_m128_to_512_end_of_round.json: measured 295 / 345 at M = 160 / 192
+    // on 11008 x 4096, 426 / 493 at M = 320 / 384 on 4096^2 - the "520 at M = 256, 465 below" it replaces kept the per-wave kernel at M = 160 /
+    // 192 / 320 on 11008 x 4096, 14336 x 4096, 14336 x 3584, 3584 x 14336, 3584 x 8192 where split-K tiles run 30 - 70 % faster)
+    if (M < 512) return (300.0 + 0.75 * (M - 128)) * (bf ? 0.8 : 1.0) * b2;
+    // from M = 512: 520 (bf16 400) TFLOP/s at M = 256, + 55 per doubling of M, up to 730 (560)
+    int dbl = 0;
+    for (int m = M; m >= 512; m >>= 1) ++dbl;
+    return (bf ? std::min(560.0, 400.0 + 55.0 * dbl) : std::min(730.0, 520.0 + 55.0 * dbl)) * b2;
+}
+double flop_us(const Call& c, double tflops) { return 2.0 * c.M * (double)c.N * c.K / (tflops * 1e6); }
+
+// Block-tiled prefill kernels (qgemm_block2.h: 256 x 256 or 128 x 256 blocks, a wave owns all rows and 32
+// columns, 4- and 2-bit layers; qgemm_block3.h: the same for 3 bits, 128-row blocks); scale rows in
+// whole 16-B granules.  No K split for 2 / 4 bits (qgemm_splitk.h serves that regime; 3 bits: priced below), so what decides is
+// how many blocks the output has.  Cost model fitted to tools/block_lab.py (MI355X, K = 4096; us per block,
+// running alone / with the whole chip busy - the chip clocks down under a full MFMA load):
+//   256-row block fp16 100 / 126, bf16 104 / 129;  128-row block fp16 72 / 81, bf16 80 / 89 (round 2);
+//   round 4 (2- / 4-bit blocks: whole-line activation pieces, one whole-line weight request per step):
+//   256-row 97 / 120, bf16 101 / 124;  128-row 62 / 74, bf16 70 / 78 (profiles/r04/splitk_lab_run7*.jsonl);
+//   per-wave MFMA kernel (family 2): wave_tflops.
+// The choice: block configuration (flute_plan::m_block of family 3, -1: none), the grid K split the cost model chose with it
+// (3 bits, 0: none), and the modelled time of the best other MFMA kernel (-1: not priced).
+struct BlockChoice { int cfg, sk; double alt_us; };
+BlockChoice choose_block(const Call& c) {
+    const int bits = c.bits, M = c.M, N = c.N, K = c.K, lg = c.lg, units = c.units, num_sms = c.num_sms;
+    const Ovr& ov = c.ov;
+    BlockChoice b{-1, 0, -1.0};
+    const int blk_units = 256 / c.J;                  // units of a 256-column block (4-bit: 64, 2-bit: 32, 3-bit: 16)
+    const bool b3_ok = bits != 3 || (size_t)3 * (N >> 4) * K * 2 < (size_t)0xfffffff0u;   // one descriptor over Q
+    const bool x32_ok = (size_t)(M + 256) * K * 2 < (size_t)0xfffffff0u;       // activation byte offsets are 32-bit voffsets
+    if (!b3_ok || !x32_ok || (K >> lg) % 8 || units % blk_units) return b;
+    const long tiles256 = (long)ceil_div(M, 256) * (units / blk_units), tiles128 = (long)ceil_div(M, 128) * (units / blk_units);
+    if (ov.family == kFamilyBlock) {
+        b.cfg = (ov.m_tiles == 4) ? 5 : 4;               // 128- / 256-row blocks of qgemm_block2.h
+        if (bits == 3 && ov.m_tiles != 8) b.cfg = 5;     // 3-bit layers: 128-row blocks of qgemm_block3.h unless 256 rows are asked for ...
+        if (bits == 3 && (ov.m_block == 1 || ov.m_block == 2 || ov.m_block == 4))
+            b.cfg = 8 + ov.m_block;                      // ... or its skinny blocks of m_block row tiles
+    } else if (bits == 3 && M > 32 && M <= 64 && (size_t)N * K >= ((size_t)56 << 20) &&
+               (M > 48 || skinny3_fills(M, units / blk_units, K, lg, num_sms))) {    // (14336 x 3584, 51 M weights: 29.5 against 26.4 us on the per-wave kernel)
+        // 3-bit skinny blocks (64 rows, grid K split): measured against the per-wave kernel at M = 64 - 8192^2 31.6 vs
+        // 38.5 us, 28672x8192 86.9 vs 105.7, 4096x14336 31.8 vs 35.4; slower below M = 33 and on 4096^2 (fixed
+        // costs of ~8 us per call: prologue, fp32 slabs, reduce launch)
+        b.cfg = 12;
+    } else if (M >= 256 || (bits == 3 && M > 64) || (bits != 3 && M > 128)) {          // (3 bits from M = 65: the K-split candidates below; 2 / 4 bits from M = 129: 128-row blocks on the
+        // widest layers - 2-bit 28672 x 8192 at M = 192 ran 210 us on the per-wave kernel, 125 on 128-row blocks, profiles/r06/planner_regret_bits_4_2_m96_to_768_unswept_batch_sizes.json)
+        const bool bf = c.dtype == FLUTE_BF16;
+        auto block_us = [&](long tiles, double alone, double busy) {
+            const long whole = tiles / num_sms, rest = tiles % num_sms;       // full rounds + a last partial one
+            const double last = rest == 0 ? 0.0 : (rest * 4 >= (long)num_sms * 3 ? busy : alone);
+            return ((double)whole * busy + last) * (double)K / 4096.0 + 3.0;
+        };
+        // 3-bit layers (qgemm_block3.h): 128-row blocks 78 / 85 us alone, 85 / 90 busy; 256-row blocks (round 3) 108 / 118
+        // alone, 124 / 128 busy (profiles/r03/block_lab_w3_256_row_blocks.jsonl); the per-wave kernel runs them at
+        // 330-380 TFLOP/s
+        const double t256 = (bits == 3) ? block_us(tiles256, bf ? 118.0 : 108.0, bf ? 128.0 : 124.0)
+                                        : block_us(tiles256, bf ? 101.0 : 97.0, bf ? 124.0 : 120.0);
+        const double t128 = (bits == 3) ? block_us(tiles128, bf ? 85.0 : 78.0, bf ? 90.0 : 85.0)
+                                        : block_us(tiles128, bf ? 70.0 : 62.0, bf ? 78.0 : 74.0);
+        // (3 bits, round 4: 14336 x 3584 M = 256 runs at 305, modelled 370 kept it off the 128-row blocks: 86.4 against 70.3 us; round 5's
+        // regret sweep, fp16: 3584 x 8192 M = 256 293, 14336 x 3584 M = 128 276, 8192^2 M = 96 253 - fewer rows, fewer MFMAs per lookup)
+        const double wave_tf = (bits == 3) ? (bf ? 290.0 : 300.0) * (M >= 256 ? 1.0 : 0.6 + 0.4 * M / 256.0) : wave_tflops(c);
+        const double wave_us = flop_us(c, wave_tf);
+        if (t256 <= t128 && t256 < wave_us) b.cfg = 4;
+        else if (t128 < t256 && t128 < wave_us) b.cfg = 5;
+        b.alt_us = std::min(wave_us, std::min(t256, t128));
+        if (bits == 3) {
+            // 3-bit layers have no split-K block kernel of their own (qgemm_splitk.h: 2 / 4 bits): where whole blocks leave
+            // CUs idle, 128- or 64-row blocks of qgemm_block3.h with a grid K split (fp32 slabs + the reduce pass) fill
+            // them.  One round of workgroups; a block costs ~4 us + its K share of (128 rows: 78 / 85 us alone, 85 / 90 busy;
+            // 64 rows: 66 / 72 - the lookups of a block's 256 columns dominate, the rows are nearly free), the slabs 0.25 us
+            // per MB + the reduce launch.  Measured (bf16, profiles/r04/w3_mid_m_forced_plans.jsonl; before -> after):
+            // M = 1024 x 4096^2 84.9 -> 56.4 us, M = 512 x 8192^2 160.5 -> 95.6, M = 512 x 4096^2 54.5 -> 45.4
+            const double base = b.cfg == 4 ? t256 : (b.cfg == 5 ? t128 : wave_us);
+            double best = 0.95 * base;                      // a K-split plan has to beat the unsplit best by 5 %; among themselves: the cheapest
+            const int align_k = std::max(64, 8 << lg);
+            for (int rows = 128; rows >= 64; rows >>= 1) {
+                const long tiles = (long)ceil_div(M, rows) * (units / blk_units);
+                const double alone = rows == 128 ? (bf ? 85.0 : 78.0) : (bf ? 72.0 : 66.0);
+                const double busy = rows == 128 ? (bf ? 90.0 : 85.0) : (bf ? 72.0 : 70.0);
+                for (int sk = (rows == 128 ? 2 : 1); sk <= 4; sk *= 2) {
+                    const long wgs = tiles * sk;
+                    // slices of kps k, the last one shorter where K is no multiple (K = 3584: 2048 + 1536, or 3 x 1024 + 512 - round 5:
+                    // 14336 x 3584 M = 128 47.6 -> 33.9 us, M = 256 61.7 -> 49.3; until then only equal slices were priced)
+                    const int kps = round_up(ceil_div(K, sk), align_k);
+                    if (sk > 1 && (wgs > (long)num_sms || ceil_div(K, kps) != sk || kps < 1024 ||
+                                   (size_t)sk * tiles * rows * 1024 > slab_room(c.workspace_bytes))) continue;
+                    double us;
+                    if (sk == 1) us = block_us(tiles, alone, busy);
+                    else us = 4.0 + ((wgs * 4 >= (long)num_sms * 3 ? busy : alone) - 4.0) * (double)kps / 4096.0 +
+                              (rows == 128 ? 2.0 : 5.0) +              // (128-row blocks: combined in the launch, round 5; else the reduce launch)
+                              0.25 * (double)sk * M * N * 4.0 / 1e6;
+                    if (us < best) { best = us; b.cfg = rows == 128 ? 5 : 12; b.sk = sk; }
+                }
+            }
+            b.alt_us = std::min(b.alt_us, b.sk > 0 ? best : base);
+        }
+    }
+    return b;
+}
+
+// Split-K block kernel, automatic (the template's default Stages and SMs_Multiple): taken when its modelled time is
+// 8 % under the best of the per-wave kernel and the block kernels (alt_us; the per-wave kernel alone where the block cost model did not run).
+// Measured (tools/splitk_lab.py, us, automatic plan of round 3 -> this kernel): M = 256 x 4096 x 11008 44.5 -> 38.1,
+// 4096 x 14336 47.2 -> 40.2, 8192^2 49.0 -> 44.2; M = 1024 x 4096^2 49.6 -> 41.8 (torch.mm 46.9), M = 512 29.0 -> 27.4;
+// not taken: M = 256 x 4096^2 (24.9 against 20.1: the seam of four slices), M = 128 x 4096^2, K = 14336.
+bool splitk_auto(const Call& c) { return splitk_regime(c) && c.t.stages == 2 && c.t.sms_multiple == 1; }
+bool splitk_auto_taken(const Call& c, const flute_plan& q, double sk_us, double alt_us) {
+    // (one round of workgroups only: multi-round launches are left to the tuner's Stages-5 ids until measured)
+    // (round 6: 64 x 64 tiles - four K parts per workgroup - that fill at least half the chip are priced against the per-wave kernel
+    // WITH its fixed part, which the TFLOP/s model lacks: measured - modelled 3.2 .. 5.7 us on 4096-wide layers, 10 on
+    // 2048 x 8192; profiles/r06/call17_automatic_plan_vs_forced.log: M = 128 on 4096^2 13.1 against 14.9 us, M = 192 15.1 / 18.8, M = 512 on
+    // 2048 x 4096 15.8 / 19.9, M = 256 on 2048 x 8192 18.0 / 26.6, M = 48 on 3584 x 14336 16.7 / 21.6, M = 33 on 8192^2 17.7 / 26.1)
+    // (2-bit layers up to M = 64: also two rounds - 28672 x 8192 M = 33 / 48 / 64: 448 workgroups of 64 x 128 tiles x 2 slices 46.6 / 47.8 / 49.3 us
+    // against the per-wave kernel's 61.3 / 61.5 / 62.3, profiles/r06/planner_regret_b2_m33_96_after_2bit_rate_fix.json)
+    return sk_us < ((q.kw == 4 && (long)q.grid * 2 >= (long)c.num_sms) ? alt_us + 4.0 : 0.92 * alt_us) &&
+           (long)q.grid <= (c.bits == 2 && c.M <= 64 ? 2L : 1L) * (long)c.num_sms && q.lds_bytes <= (size_t)kMaxLds;
+}
+
+// Decode kernels (family 0).  Three of them: the one-shot kernel (qgemm_oneshot.h: non-persistent workgroups, every request up
+// front) and the persistent ring kernel (qgemm_stream.h).  Forced by override (one_shot 1 / 0; an explicit
+// ring depth or grid K split means the ring kernel) or by the template (4-bit QuantMapMode digit 1, 2:
+// one-shot with 4 / 8 pieces per wave, 3: ring; 2- / 3-bit SMs_Multiple 4: one-shot, 2: ring); automatic:
+// one-shot for layers up to 64 M weights that give at least half the CUs a workgroup; one or two rows on larger layers:
+// the persistent one-shot kernel (qgemm_persist.h; override one_shot = 3, as flute_plan reports it, or 2).
+// Tried in order: lean one-row kernel -> persistent one-shot -> one-shot -> ring.
+int plan_decode(const Call& c, Planned* out) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K, num_sms = c.num_sms, template_id = c.template_id;
+    const flute_template_info& t = c.t;
+    const Ovr& ov = c.ov;
+    // a fused Hadamard rotation prefers 8-wave workgroups (4096x3584 M = 1: 5.5 us with 8 waves, 6.5 with
+    // the 4-wave shape the plain product takes)
+    Ovr ovd = ov;
+    if (ov.had8 && ovd.waves < 0 && ovd.kw < 0 && ovd.one_shot != 0) ovd.waves = 8;
+    int want = ov.one_shot == 3 ? 2 : ov.one_shot;       // 3 = flute_plan's code for the persistent kernel (2 kept from ABI v4)
+    if (want < 0 && (ov.depth > 0 || ov.splitk > 1)) want = 0;
+    if (want < 0 && bits == 4) { const int q = template_id % 4; want = (q == 3) ? 0 : ((q == 1 || q == 2) ? 1 : -1); }
+    if (want < 0 && bits != 4) want = (t.sms_multiple == 2) ? 0 : (t.sms_multiple == 4 ? 1 : -1);
+    // lean one-row kernel (qgemm_fast.h): by override (one_shot = 4), or automatically for the ids whose last digit leaves the choice
+    // to the planner and whose Stages digit asks for the planner's first or second shape (4-bit QuantMapMode digit 0, Stages 2 / 3,
+    // SMs_Multiple 1: ids 0 / 4 - TileP 64 - and 16 / 20 - TileP 32), on K = 2048 / 4096 layers up to 48 M weights that give at
+    // least half the CUs a workgroup - measured against the persistent and the round-4 one-shot kernel (us, persistent / lean /
+    // one-shot): 4096^2 4.42 / 4.05 / 4.14, 5120 4.96 / 4.90 / 5.88, 8192 5.51 / 5.46 / 5.91, 11008 7.54 / 6.86 / 8.04; not taken:
+    // 14336 7.85 / 8.27 / 8.43, 28672 13.6 / 13.9 / 14.6, more than three workgroups per CU (16384 x 2048: 5.97 against 5.49 on the
+    // one-shot kernel; 8192 x 2048 3.77 / 4.05 is taken), K = 8192 (8192^2 8.42 against 10.42, 4096 x 8192 5.71 / 5.97: by
+    // override only).  Two to four rows (dot products per row on the same lookups): while ONE round of workgroups covers the layer
+    // (4096^2: M = 2 5.04 -> 4.29 us, M = 3, 4 6.25 -> 5.03; 4096 x 2048: 3.87 -> 3.25, 4.65 -> 3.71; beyond, the persistent kernel
+    // (M = 2) and the skinny MFMA kernel (M = 3, 4) win: 8192 x 4096 5.79 against 7.12, 8.69 against 8.98).  Never for a call that
+    // fuses the Hadamard rotation.  K = 8192 (shape (8, 2, 8)), round 5's last call series: one row a tie with the one-shot kernel
+    // (3584 x 8192: 5.33 / 5.40 us, 4096 x 8192: 5.57 / 5.51), TWO rows on layers that give >= 80 % of the CUs a workgroup 6.11 against
+    // 6.78 and 6.33 against 6.82 - taken; narrower layers (2048, 1024 columns: 128 / 64 workgroups) lose 13 - 17 % and are not.
+    // K = 2048, two rows: up to two rounds (6144 x 2048 4.34 -> 3.79 us, 8192 x 2048 4.38 -> 4.01; four rows lose there: 5.14 / 5.76)
+    if ((want == 4 || (want < 0 && auto_lean_id(c) && t.stages <= 3 && ov.waves < 0)) && !ov.had8 && ov.kw < 0) {
+        Planned q{};
+        if (plan_fast(bits, lg, M, N, K, num_sms, std::max(0, t.stages - 2), want == 4 ? ov.waves : -1, &q.p, &q.oa) == FLUTE_OK &&
+            (want == 4 || ((K != 8192 || (M == 2 && (long)q.p.grid * 5 >= (long)num_sms * 4)) &&
+                           (size_t)N * K <= ((size_t)48 << 20) && (long)q.p.grid * 2 >= (long)num_sms &&
+                           (long)q.p.grid <= (M == 1 ? 3L : (M == 2 && K == 2048 ? 2L : 1L)) * num_sms))) {
+            *out = q;
+            return lds_fits(out->p);
+        }
+    }
+    if (want == 4) want = -1;
+    // persistent one-shot kernel: by override, or automatically (one or two rows; four rows measured 1.7x the one-row
+    // time - no faster than the MFMA kernel, profiles/r03/decode_lab_persist_rows.jsonl) on layers of >= 40 M weights that give
+    // every CU six whole unit rows (below that the in-workgroup K split of the other two kernels wins:
+    // profiles/r03/persist_lab.txt; round 4: from 40 M weights / 6 unit rows per CU - 6144 x 4096 M = 2 6.8 -> 6.0 us, 2-bit
+    // 10240 x 8192 M = 1 10.8 -> 9.8)
+    const bool auto_digit = (bits == 4) ? (template_id % 4) == 0 : t.sms_multiple == 1;
+    const bool persist_auto = want < 0 && ov.one_shot < 0 && ov.depth <= 0 && ov.splitk <= 1 && auto_digit &&
+                              (size_t)N * K >= ((size_t)24 << 20) && (long)c.units >= 4L * num_sms;
+    if (want == 2 || persist_auto) {
+        Planned q{};
+        if (plan_persist(bits, lg, M, N, K, num_sms, t, ovd, &q.p, &q.oa) == FLUTE_OK) { *out = q; return lds_fits(out->p); }
+        if (want == 2) want = 0;
+    }
+    if (want != 0) {
+        Planned q{};
+        if (plan_oneshot(bits, lg, M, N, K, num_sms, t, template_id, ovd, &q.p, &q.oa) == FLUTE_OK &&
+            (want == 1 || ((size_t)N * K <= ((size_t)64 << 20) && (long)q.p.grid * 2 >= (long)num_sms))) {
+            *out = q;
+            return lds_fits(out->p);
+        }
+    }
+    Planned q{};
+    const int rc = plan_stream(c.dtype, bits, lg, M, N, K, num_sms, t, ovd, slab_room(c.workspace_bytes), &q.p, &q.sa);
+    if (rc) return rc;
+    q.p.workspace_needed = split_slabs(q.p.splitk, M, N);
+    *out = q;
+    return lds_fits(out->p);
+}
+
+// Block kernels (family 3) in configuration b.cfg, K split b.sk (0: the planner's own).
+int plan_block(const Call& c, const BlockChoice& b, Planned* out) {
+    const int bits = c.bits, M = c.M, N = c.N, K = c.K, lg = c.lg;
+    const Ovr& ov = c.ov;
+    const int bm = block_rows(b.cfg), tm = bm / 32;
+    const int tiles_m = ceil_div(M, bm), tiles_n = c.units / (256 / c.J);
+    const int align_k = std::max(64, 8 << lg);
+    int splitk = (ov.splitk > 0) ? ov.splitk : (b.sk > 0 ? b.sk : 1);
+    if (b.cfg >= 8 && ov.splitk <= 0 && b.sk == 0)   // skinny blocks: the K split fills the chip
+        while ((long)tiles_m * tiles_n * splitk * 2 <= (long)c.num_sms && K / (splitk * 2) >= std::max(256, align_k)) splitk *= 2;
+    int kps = round_up(ceil_div(K, splitk), align_k);
+    splitk = ceil_div(K, kps);
+    while (splitk > 1 && (size_t)splitk * M * N * 4 > slab_room(c.workspace_bytes)) {
+        splitk >>= 1;
+        kps = round_up(ceil_div(K, splitk), align_k);
+        splitk = ceil_div(K, kps);
+    }
+    if (splitk == 1) kps = K;
+    Planned q{};
+    flute_plan& p = q.p;
+    p.family = kFamilyBlock;
+    p.m_block = b.cfg; p.m_tiles = tm; p.slabs_per_wave = 1; p.waves = 8; p.kw = 1;
+    p.splitk = splitk; p.k_per_split = kps;
+    p.grid = (unsigned)((long)tiles_m * tiles_n * splitk);
+    p.block = 512;
+    p.workspace_needed = split_slabs(splitk, M, N);
+    // 3-bit 128-row blocks x 2 / 4 K slices (round 5): the slices of a block meet inside the launch (xwg.h, E form; slabs in
+    // fragment order, whole blocks: tiles x 128 x 256 x 4 B per slice) - no reduce launch.  Measured against the reduce launch
+    // (bf16, us, profiles/r05/call24_w3_inlaunch_and_line_planes.log): M = 1024 x 4096^2 56.3 -> 53.0 (fp16 53.4 -> 50.1),
+    // M = 256 x 8192^2 56.0 -> 54.4, M = 512 x 8192^2 95.3 -> 92.7, M = 96 x 28672 x 8192 92.1 -> 89.0, M = 512 x 4096^2 a tie; NOT for
+    // the skinny blocks (64 rows x 4 slices 46.7 -> 47.8; 8 slices, L form - the last arriver reads seven partials - 30.5 -> 32.6)
+    if (bits == 3 && (splitk == 2 || splitk == 4) && bm == 128 && (long)tiles_m * tiles_n <= (long)kXwgMaxTiles) {
+        const size_t slabs = (size_t)splitk * tiles_m * tiles_n * bm * 1024;
+        if (slabs <= slab_room(c.workspace_bytes) && slabs < ((size_t)1 << 31)) { p.splitk_mode = 1; p.workspace_needed = slabs + kXwgFlagBytes; }
+    }
+    // pair table + three activation stages + per wave: two scale blocks and a sink
+    // (3-bit 256-row blocks: + 18 KB, the second / third plane pieces of waves 6 and 7)
+    p.lds_bytes = (size_t)((128 << (2 * bits)) + 3 * (bm / 16) * 2 * 1024 + 8 * 3 * 1024 + ((bits == 3 && bm == 256) ? 18 * 1024 : 0));
+    p.lut_copies = 32;
+    *out = q;
+    return lds_fits(out->p);
+}
+
+// Per-wave MFMA kernel (qgemm_tile.h; families 1 / 2).  MT 16-row tiles per wave (1 for M <= 16),
+// R lanes share a unit: pick the smallest R whose slab x row-tile count fills the chip; the
+// rest of the parallelism is the in-workgroup K split, a grid-level split only for very
+// narrow layers.
+int plan_tile(const Call& c, Planned* out) {
+    const int bits = c.bits, J = c.J, M = c.M, N = c.N, K = c.K, units = c.units, num_sms = c.num_sms, template_id = c.template_id;
+    const flute_template_info& t = c.t;
+    const Ovr& ov = c.ov;
+    int mt = (M <= 16) ? 1 : (M <= 32 ? 2 : 4);
+    const int mt_cap = (bits == 3) ? 2 : 4;
+    if (mt > mt_cap) mt = mt_cap;
+    if (t.tile_m / 16 < mt && M > 16) mt = t.tile_m / 16 >= 2 ? t.tile_m / 16 : mt;
+    // SMs_Multiple = "more, smaller workgroups": halves / quarters the row tiles per wave (and,
+    // below, raises the slab count the choice of R aims for)
+    for (int m2 = t.sms_multiple; m2 > 1 && mt > 1; m2 >>= 1) mt >>= 1;
+    if (ov.m_tiles == 1 || ov.m_tiles == 2 || ov.m_tiles == 4) mt = ov.m_tiles;
+    if (mt > mt_cap) mt = mt_cap;
+    // instantiated (R, MT): (J/R)*MT <= 16 accumulator tiles, R in {1,2,4}, MT > 1 needs R <= 2
+    auto combo_ok = [&](int r, int m) {
+        if (bits == 3) return r == 1 && m == 1;
+        return (J / r) * m <= 16 && r <= 4 && (m == 1 || r <= 2);
+    };
+    while (mt > 1 && !combo_ok(1, mt) && !combo_ok(2, mt)) mt >>= 1;
+    const int mtiles = ceil_div(M, mt * 16);
+    int R = 1;
+    while (!combo_ok(R, mt)) R *= 2;
+    // Every workgroup pulls its rows of X through one CU, so lane sharing (R-fold more, narrower slabs) multiplies the
+    // activation traffic: it pays only while the workgroups leave more than ~45 % of the CUs idle (round 3,
+    // profiles/r03/tile_lab_sw2_m16.jsonl, tile_lab_sw2_m32_m128.jsonl: 10240 x 8192 M = 16, 160 slabs: R = 1 22.2 us,
+    // R = 2 26.8; M = 64: 36.7 / 49.9; 4096 x 11008 M = 64: 21.4 / 29.1; but 8192^2 M = 32, 128 slabs: R = 2 16.2, R = 1 19.3)
+    auto fills = [&](long wgs) { return wgs * 20 >= 11L * num_sms * t.sms_multiple; };
+    // ... and not at all where the grid K split can fill the chip instead (round 5's regret sweep, the in-launch seam of xwg.h being
+    // cheap now): deep layers - K >= 10240: two slices, K >= 12288: four - stop sharing lanes as soon as that split fills.
+    // 4096 x 11008 (N x K) M = 4: four lanes per unit 16.6 us, two lanes x 2 slices 14.8 (2 bits: 14.2 -> 12.5), M = 16 16.9 -> 15.4;
+    // 3584 x 14336 M = 48: two lanes x 2 slices 26.4, no sharing x 4 slices 21.6 (profiles/r05_planner_regret_*.json)
+    const long deep_split = (bits != 3 && (bits != 4 || (template_id % 4) == 0) && ov.splitk < 0) ? (K >= 12288 ? 4 : (K >= 10240 ? 2 : 1)) : 1;
+    while (combo_ok(R * 2, mt) && !fills((long)units * R / 16 * mtiles) &&
+           !(deep_split > 1 && fills((long)units * R / 16 * mtiles * deep_split))) R *= 2;
+    // QuantMapMode digit 1 (4-bit ids): no lane sharing above M = 16 - the chip is filled by the grid K split
+    // instead (8192^2 M = 64: R = 1, MT = 4, split 2 26.2 us against R = 2, MT = 2 30.3; 4096^2 prefers R = 2:
+    // the tuner decides)
+    if (bits == 4 && (template_id % 4) == 1 && combo_ok(1, mt)) R = 1;       // (M <= 16: with two slabs per wave, below)
+    // QuantMapMode digit 3 above M = 16 (round 5): no lane sharing AND two slabs per wave, the chip filled by the grid K split - the
+    // plan round 4's regret sweep wanted on 8192 x 28672 and could not reach through an id (M = 64: 72.6 -> 55.3 us, M = 48 65.0 ->
+    // 52.8, M = 32 52.4 -> 45.2).  The automatic digit takes it by itself on layers that deep (K >= 16384: a slice keeps >= 4096 k) whose halved slab count x four slices fills the chip
+    const bool deep_sw2 = bits == 4 && M > 16 && combo_ok(1, mt) && (c.dtype == 0 || mt <= 2) && (units / 16) % 2 == 0 && ov.m_block <= 0 &&
+                          ((template_id % 4) == 3 || ((template_id % 4) == 0 && K >= 16384 && !fills((long)(units / 16) * mtiles) && fills((long)(units / 32) * mtiles * 4)));
+    if (deep_sw2) R = 1;
+    if (ov.m_block > 0 && combo_ok(ov.m_block, mt)) R = ov.m_block;
+    // SW = 2 slabs per wave (4-bit, no lane sharing, fp16 up to MT = 4 / bf16 up to MT = 2: the bf16 path
+    // keeps a second accumulator set): every activation fragment then serves 8 column tiles and the
+    // texture-path traffic per MFMA drops by 40 %.  Worth it once halving the slab count still leaves a
+    // workgroup for every CU; QuantMapMode (the last template digit) lets the tuner force either.
+    const bool sw_ok = bits == 4 && R == 1 && (c.dtype == 0 || mt <= 2) && (units / 16) % 2 == 0;
+    int sw = 1;
+    // ... as soon as the halved slab count still fills 55 % of the CUs (28672 x 8192 M = 16: 448 workgroups 43.4 us, 224
+    // workgroups 37.1; M = 64: 73.4 -> 54.2; 4096 x 14336 M = 128: 38.2 -> 28.2) - or, at M <= 16, on the tuner's request (digit 1)
+    if (sw_ok && (fills((long)(units / 32) * mtiles) || (mt == 1 && M <= 16 && (template_id % 4) == 1))) sw = 2;
+    if (sw_ok && bits == 4 && ((template_id % 4) == 3 || deep_sw2)) sw = 2;
+    if (bits == 4 && (template_id % 4) == 2) sw = 1;
+    if (sw_ok && ov.slabs == 2) sw = 2;
+    if (ov.slabs == 1) sw = 1;
+    const int slabs = units * R / 16 / sw;                    // wave-sized column groups
+    int nw = (t.threads >= 1024) ? 8 : 4;                     // Threads 1024 / 512 templates
+    if (ov.waves > 0 && ov.waves <= 8) nw = floor_pow2(ov.waves);
+    while (nw > 1 && tile_geom(bits, R, mt, sw, nw, kMaxLds).depth < 2) nw >>= 1;   // ring of >= 2 slots per wave
+    int kw = nw;
+    while (kw > 1 && K / kw < 256) kw >>= 1;
+    // enough workgroups already: keep more of K per wave (fewer partial tiles to reduce)
+    while (kw > 1 && (long)slabs * mtiles / (nw / kw) >= 2L * num_sms * t.sms_multiple && K / kw < 1024) kw >>= 1;
+    if (t.stages == 3 && kw > 1) kw >>= 1;                    // the tuner's handle on the K split
+    if (t.stages == 4 && kw < nw) kw <<= 1;
+    if (t.stages == 5 && kw > 2) kw >>= 2;
+    if (ov.kw > 0 && ov.kw <= nw) kw = floor_pow2(ov.kw);
+    while (nw % kw) kw >>= 1;
+    while (slabs % (nw / kw)) kw <<= 1;
+    const long wgs = (long)slabs / (nw / kw) * mtiles;
+    int splitk = 1;
+    // 3-bit layers have no lane-sharing variants (a wave = 16 units x 16 fields = 256 columns): the grid-level K
+    // split is their only way to fill the chip, down to 64 k per wave (4096^2 M = 16: 20.5 -> 14.5 us,
+    // 4096x14336: 30.8 -> 20.2 us)
+    const int k_min = (bits == 3) ? 64 : 256;
+    while (wgs * splitk * 2 <= (long)num_sms && K / (splitk * 2 * kw) >= k_min) splitk *= 2;
+    if (ov.splitk > 0) splitk = ov.splitk;
+    int kps = round_up(ceil_div(K, splitk), 32 * kw);
+    splitk = ceil_div(K, kps);
+    while (splitk > 1 && (size_t)splitk * M * N * 4 > slab_room(c.workspace_bytes)) {
+        splitk >>= 1;
+        kps = round_up(ceil_div(K, splitk), 32 * kw);
+        splitk = ceil_div(K, kps);
+    }
+    if (splitk == 1) kps = K;
+    Planned q{};
+    flute_plan& p = q.p;
+    p.family = 2;
+    p.m_block = R; p.m_tiles = mt; p.slabs_per_wave = sw; p.waves = nw; p.kw = kw; p.splitk = splitk;
+    p.k_per_split = kps;
+    // round 4: the K slices of a (slab group, row tile) meet inside the launch (xwg.h, L form) while the slabs are small -
+    // the reduce launch it replaces costs >= 2 us; beyond kTileInLaunchMax (4 MB) of slabs the all-CU reduce pass reads them
+    // faster than the last arrivers would
+    if (splitk > 1 && wgs <= kXwgMaxTiles && (size_t)splitk * M * N * 4 <= kTileInLaunchMax) p.splitk_mode = 1;
+    p.grid = (unsigned)(wgs * splitk);
+    p.block = (unsigned)(nw * 64);
+    p.lds_bytes = (size_t)tile_geom(bits, R, mt, sw, nw, kMaxLds).total;
+    p.lut_copies = 32;
+    p.workspace_needed = split_slabs(splitk, M, N);
+    *out = q;
+    return lds_fits(out->p);
+}
+
+// The planner: validate, route a forced family to its planner, else try the automatic candidates in their order.
 int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int template_id, int num_sms,
-              size_t workspace_bytes, const Ovr& ov, flute_plan* p, flute_template_info* tinfo,
-              StreamArgs* sa, OneArgs* oa) {
+                       size_t workspace_bytes, const Ovr& ov, Planned* out, flute_template_info* tinfo) {
     if (dtype != 0 && dtype != 1) return FLUTE_ERR_DTYPE;
     // override families: -1 automatic, 0 decode, 1 / 2 per-wave MFMA kernel, 3 block kernels, 5 skinny MFMA kernel,
     // 6 split-K block kernel, 7 lean MFMA decode kernel, 8 persistent MFMA decode kernel; anything else is a caller error (round 1's family 4 is gone)
     if (ov.family < -1 || ov.family == 4 || ov.family > 8) return FLUTE_ERR_SHAPE;
-    if (bits != 2 && bits != 3 && bits != 4) return FLUTE_ERR_NUM_BITS;
-    if (group != 32 && group != 64 && group != 128 && group != 256) return FLUTE_ERR_GROUP_SIZE;
-    flute_template_info t;
-    if (!decode_template(bits, template_id, &t)) return FLUTE_ERR_TEMPLATE_ID;
-    if (bits == 3 && t.tile_p != 32) return FLUTE_ERR_TEMPLATE_ID;   // utils.py:137-139
-    if (tinfo) *tinfo = t;
-    const int J = (bits == 3) ? 16 : 16 / bits;
-    if (M < 1 || N < 1 || K < 1) return FLUTE_ERR_SHAPE;
-    if (N % (J * t.tile_p) || K % 64 || K % group) return FLUTE_ERR_SHAPE;
-    if (num_sms < 1) num_sms = 256;
-    const int lg = ilog2(group);
-    const int units = N / J;
+    Call c;
+    const int lrc = check_layer(bits, group, template_id, N, K, std::max(64, group), &c);
+    if (lrc) return lrc;
+    if (M < 1) return FLUTE_ERR_SHAPE;
+    *tinfo = c.t;
+    c.dtype = dtype; c.M = M; c.N = N; c.K = K; c.template_id = template_id;
+    c.num_sms = num_sms < 1 ? 256 : num_sms; c.workspace_bytes = workspace_bytes; c.ov = ov;
+    const int fam = ov.family;
 
-    memset(p, 0, sizeof(*p));
+    // forced: the family's planner; families 6 and 8 refuse a call they do not fit, the others fall back to the per-wave
+    // kernel (family 0: above M = 4)
+    if (fam == kFamilyPersistM)
+        return plan_persistm(bits, c.lg, M, N, K, c.num_sms, ov.slabs, ov.m_tiles, ov.one_shot, &out->p, &out->oa);
+    if (fam == kFamilySplitK) {
+        const int rc = plan_splitk(bits, c.lg, M, N, K, c.num_sms, ov, workspace_bytes, &out->p);
+        return rc ? rc : lds_fits(out->p);
+    }
+    if (fam == kFamilyFastM) {
+        Planned q{};
+        if (plan_fastm(bits, c.lg, M, N, K, c.num_sms, ov.slabs, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+    }
+    if (fam == kFamilySkinny) {
+        Planned q{};
+        if (plan_skinny(bits, c.lg, M, N, K, ov, workspace_bytes, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+    }
+    if (fam == 0 && M <= 4) return plan_decode(c, out);
+    if (fam == kFamilyBlock) {
+        const BlockChoice b = choose_block(c);
+        if (b.cfg >= 0) return plan_block(c, b, out);
+    }
+    if (fam >= 0) return plan_tile(c, out);
 
-    // Streaming decode kernel: M <= 2; its four-row variant (2- / 4-bit) only on request (override family 0, which
-    // flute_qgemm_hadamard sets for small layers so that the rotation stays fused): measured at M = 3, 4 the MFMA
-    // kernel is as fast on 4096^2 (7.6 vs 7.75 us) and 15-25 % faster on every larger layer (8192x28672: 38.6 vs 48.9).
-    // (3-bit layers up to 24 M weights also take it by themselves: their MFMA plans are 256 columns wide per wave -
-    // 4096^2 M = 4: 9.9 against 13.7 us; larger 3-bit layers are faster on the MFMA kernel.)
-    const int dec_max = 4;
-    const bool small_b3 = bits == 3 && ov.family < 0 && (size_t)N * K <= ((size_t)24 << 20);
-    // round 4: 2- / 4-bit layers up to 16 M weights take the four-row one-shot kernel at M = 3, 4 too (4096^2 M = 4: 6.3 us
-    // against 7.1 on the MFMA kernel, profiles/r04_planner_regret_before_fixes.json - the one-shot kernel of round 3 was not
-    // there when the MFMA kernel was measured level with the ring kernel)
-    // (only ids whose last digit leaves the choice to the planner: a 4-bit id with QuantMapMode digit 3 keeps the skinny MFMA kernel it was
-    // tuned on - "a tuned id keeps the kernel it was timed on", tests/test_abi.py)
-    const bool small_b24 = bits != 3 && ov.family < 0 && M >= 3 && (size_t)N * K <= ((size_t)16 << 20) && auto_digit_sk(bits, template_id);
-    const bool auto_digit = (bits == 4) ? (template_id % 4) == 0 : t.sms_multiple == 1;
-    // decode planners: a fused Hadamard rotation prefers 8-wave workgroups (4096x3584 M = 1: 5.5 us with 8 waves, 6.5 with
-    // the 4-wave shape the plain product takes)
-    Ovr ovd = ov;
-    if (ov.had8 && ovd.waves < 0 && ovd.kw < 0 && ovd.one_shot != 0) ovd.waves = 8;
-    auto persist_auto_ok = [&](int rows) {
-        if (ov.one_shot >= 0 || ov.depth > 0 || ov.splitk > 1 || !auto_digit) return false;
-        if ((size_t)N * K < ((size_t)24 << 20) || (long)units < 4L * num_sms) return false;     // (round 4: from 40 M weights / 6 unit rows per CU - 6144 x 4096 M = 2 6.8 -> 6.0 us, 2-bit 10240 x 8192 M = 1 10.8 -> 9.8)
-        flute_plan tmp;
-        memset(&tmp, 0, sizeof(tmp));
-        return plan_persist(bits, lg, rows, N, K, num_sms, t, ovd, &tmp, nullptr) == FLUTE_OK;
-    };
-    int family = (M <= 2 || (M <= dec_max && (ov.family == 0 || small_b3 || small_b24))) ? 0 : 2;
-    if (ov.family >= 1) family = 2;               // any M may be forced through the MFMA kernel
-    // Skinny MFMA kernel (qgemm_skinny.h): by override (family 5), by template (4-bit QuantMapMode digit 3 at M <= 16, where
-    // the digit's other meaning - two slabs per wave - does not exist; digit 2: never), or automatically (digit 0) for
-    // 3 <= M <= 16 on layers whose slabs (64 columns) fill 55 .. 100 % of the CUs in ONE round - a workgroup pulls its slab's
-    // weights AND all of X through one CU, so fewer slabs leave CUs idle; wider layers take the per-wave kernel with two
-    // slabs per wave (4096 x 28672: 21.1 us against 23.3 here).  Measured (profiles/r03/skinny_lab.jsonl, M = 16, us, per-wave kernel -> skinny):
-    // 4096 x 11008 17.9 -> 12.0, 4096 x 14336 18.3 -> 12.6 (M = 4: 17.6 -> 11.8), 4096 x 28672 26.6 -> 23.3, 4096 x 6144
-    // 13.1 -> 11.7, 2048 x 8192 7.6 -> 7.0; 4096 x 8192 10.0 -> 11.8 and 4096^2 7.6 -> 11.6 (not taken).
-    // Lean MFMA decode kernel (qgemm_fastm.h, round 5): by override (family 7), or automatically for 5 <= M <= 16 rows of a 4-bit layer
-    // with K = 2048 / 4096 that ONE round of its workgroups (4 unit rows each) covers, under the ids whose last digit leaves the
-    // choice to the planner (QuantMapMode digit 0, SMs_Multiple 1).  Measured (tools/time_cases.py, us, automatic plan of round 4 ->
-    // this kernel; profiles/r05/time_cases_fastm*.jsonl): 4096^2 M = 5 / 8 / 16 7.13 / 7.13 / 7.18 -> 5.9 / 5.9 / 6.1, 4096 x 2048
-    // 5.7 / 5.7 / 5.8 -> 4.3 / 4.3 / 4.5, 2048 x 4096 7.6 / 7.6 / 7.7 -> 5.4 / 5.4 / 5.6; not taken: more than one round (8192 x 4096:
-    // 10.2 .. 10.8 against the skinny kernel's 8.9 .. 9.6: every workgroup pulls all of X through its CU), M <= 4 (the dot-product
-    // lean kernel: 5.05 against 5.9)
-    // Round 6: two / three column groups per workgroup on ONE staged activation set make wider layers one round of workgroups
-    // (profiles/r06/call18_fastm_column_groups.log, M = 16, us, table's plan -> this): 8192 x 4096 10.1 -> 8.9 (2 groups, 256 workgroups),
-    // 11008 12.6 -> 11.4 (3 groups, 230), 6144 9.4 -> 8.4, 5120 9.2 -> 8.0, 8192 x 2048 6.9 -> 6.2; M = 8 on 11008 11.6 -> 11.0; not taken:
-    // more than one round even at three groups (14336: 16.0 against 13.1; 28672: 30 against 23)
-    const long fm_groups = N / 16;
-    const long fm_wgs = fm_groups <= (long)num_sms ? fm_groups : (fm_groups <= 2L * num_sms ? (fm_groups + 1) / 2 : (fm_groups + 2) / 3);
-    const bool fastm_auto = ov.family < 0 && bits == 4 && M >= 5 && M <= 16 && (template_id % 4) == 0 && t.sms_multiple == 1 &&
-                            (K == 4096 || K == 2048) && fm_wgs <= (long)num_sms && fm_wgs * 2 >= (long)num_sms &&
-                            ov.m_tiles < 0 && ov.waves < 0 && ov.kw < 0 && ov.splitk < 0 && ov.slabs < 0 && ov.m_block < 0;
-    // Persistent MFMA decode kernel (qgemm_persistm.h, round 6): by override (family 8), or automatically - under the ids that leave the choice
-    // to the planner, as the lean MFMA decode kernel - for 3 <= M <= 16 rows of a 4-bit layer with K >= 6144 (group size 64 / 128).  Measured (profiles/r06/call31_persistm_xr.log,
-    // us, table's plan -> this): M = 4: 8192 x 28672 [N x K] 34.6 -> 29.4, 10240 x 8192 20.6 -> 14.3, 4096 x 11008 14.7 -> 9.2, 3584 x 14336 14.6 -> 10.0,
-    // 4096 x 14336 14.7 -> 10.5, 8192^2 12.9 -> 11.7, 28672 x 8192 33.0 -> 31.1; M = 16: 10240 x 8192 22.2 -> 17.4, 4096 x 11008 14.9 -> 11.9,
-    // 8192^2 15.8 -> 13.9; not taken: K = 4096 (14336 x 4096: 11.1 against 11.5 .. 12.4; the lean MFMA decode kernel's and the skinny kernel's
-    // layers)
-    if (ov.family == kFamilyPersistM) return plan_persistm(bits, lg, M, N, K, num_sms, ov.slabs, ov.m_tiles, ov.one_shot, p, oa);
-    // (second sweep, profiles/r06/planner_regret_persistm*.json: also K >= 3584 at M <= 4 - 14336 x 3584 13.2 -> 10.3, 11008 x 4096 11.1 -> 9.6,
-    // 6144 x 4096 8.3 -> 7.6 - and at every M <= 16 where K is neither 2048 nor 4096, the lean MFMA decode / skinny kernels' depths -
-    // 14336 x 3584 M = 8 13.2 -> 11.9; and no limit on the activations at M > 8: equal at M = 16 on the 28672-wide / -deep layers, 7 - 15 % faster at M = 11)
-    // (third step, profiles/r06/call37_persistm_resident_activations.log: with the activations RESIDENT in LDS - K * ceil(M / 4) rows within 64 KB - also
-    // K = 4096 at M <= 8: 4096^2 M = 8 5.9 -> 5.5, 11008 x 4096 10.9 -> 9.3, 14336 x 4096 11.4 -> 11.3)
-    const bool pm_k = K >= 6144 || (K >= 3584 && (M <= 8 || (K != 4096 && K != 2048)));
-    // 2-bit member (profiles/r06/call38_persistm_2bit.log, us, table's plan -> this): every 2-bit id leaves the choice to the planner and no lean kernel
-    // competes - from K = 3584 and 16 M weights at every 3 <= M <= 16: 4096^2 M = 4 / 16 8.4 / 8.6 -> 5.0 / 6.1, 4096 x 11008 14.1 -> 8.1, 10240 x 8192 18.3 -> 13.8,
-    // 8192 x 28672 30.7 -> 25.8; above M = 8 not where the busiest workgroup pulls more than 28672 k of sixteen-row activations (28672 x 8192: 33.4 against 31.5)
-    const bool pm4 = bits == 4 && (template_id % 4) == 0 && t.sms_multiple == 1 && pm_k && (size_t)N * K + (M >= 5 ? 1 : 0) > ((size_t)16 << 20);
-    const bool pm2 = bits == 2 && K >= 3584 && (size_t)N * K >= ((size_t)16 << 20);
-    if (ov.family < 0 && (pm4 || pm2) && M >= 3 && M <= 16 && (lg == 6 || lg == 7) &&
-        (long)(N / 16) * 2 >= (long)num_sms &&      // (smaller layers: the decode kernels / too few sets for the chip; 4-bit 4096^2 itself from M = 5)
-        ov.m_tiles < 0 && ov.waves < 0 && ov.kw < 0 && ov.splitk < 0 && ov.slabs < 0 && ov.m_block < 0 && ov.one_shot < 0 && ov.depth <= 0) {
-        flute_plan pm;
-        OneArgs pm_oa;
-        if (plan_persistm(bits, lg, M, N, K, num_sms, -1, -1, -1, &pm, &pm_oa) == FLUTE_OK && (bits == 4 || M <= 8 || (long)pm.visits * K <= 28672)) {
-            *p = pm;
-            if (oa) *oa = pm_oa;
-            return FLUTE_OK;
-        }
+    // automatic: persistent MFMA decode -> lean MFMA decode -> decode kernels -> skinny (split) -> split-K Stages 5 ->
+    // split-K priced against the block / per-wave cost models -> block -> per-wave
+    if (persistm_auto(c)) {
+        Planned q{};
+        if (plan_persistm(bits, c.lg, M, N, K, c.num_sms, -1, -1, -1, &q.p, &q.oa) == FLUTE_OK && persistm_taken(c, q.p)) { *out = q; return FLUTE_OK; }
     }
-    if (ov.family == kFamilyFastM || fastm_auto) {
-        if (plan_fastm(bits, lg, M, N, K, num_sms, ov.family == kFamilyFastM ? ov.slabs : -1, p, oa) == FLUTE_OK) return FLUTE_OK;
-        memset(p, 0, sizeof(*p));
+    if (fastm_auto(c)) {
+        Planned q{};
+        if (plan_fastm(bits, c.lg, M, N, K, c.num_sms, -1, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
-    {
-        const int q4 = (bits == 4) ? template_id % 4 : -1;
-        const long slabs5 = units / 16;
-        const bool fill5 = slabs5 * 20 >= 11L * num_sms && slabs5 <= num_sms;
-        const bool auto5 = ov.family < 0 && family == 2 && bits == 4 && M >= 3 && M <= 16 &&
-                           ((q4 == 0 && K >= 4096 && fill5) || q4 == 3);
-        // Round 4: narrower layers through a grid-level K split (the slices of a slab meet inside the launch, xwg.h: 1.5 - 1.7 us
-        // of seam, profiles/r04/xwg_seam_price.json) - the smallest power-of-two split that fills 55 % of the CUs, while a
-        // slice keeps >= 2048 k.  Measured (profiles/r04_planner_regret_before_fixes.json, us, per-wave kernel -> split skinny):
-        // M = 4: 3584 x 8192 10.1 -> 8.7, 8192^2 14.6 -> 13.0, 6144 x 4096 9.2 -> 8.5; M = 16: 3584 x 8192 10.2 -> 9.6; not
-        // taken: 4096^2 (four slices of 1024 k: 7.6 against 7.2).
-        int sk5 = 0;
-        if (ov.family < 0 && ov.splitk < 0 && family == 2 && bits == 4 && M >= 3 && M <= 16 && (q4 == 0 || q4 == 3) && K >= 4096 && !fill5 &&
-            slabs5 * 20 < 11L * num_sms) {
-            int sk = 2;
-            while (sk < 16 && slabs5 * sk * 20 < 11L * num_sms) sk *= 2;
-            if (slabs5 * sk <= num_sms && K / sk >= 2048) sk5 = sk;
-        }
-        if (ov.family == kFamilySkinny || auto5 || sk5) {
-            Ovr o5 = ov;
-            if (sk5) o5.splitk = sk5;
-            if (plan_skinny(bits, lg, M, N, K, o5, workspace_bytes, p, oa) == FLUTE_OK) return FLUTE_OK;
-            memset(p, 0, sizeof(*p));
-        }
+    if (decode_auto(c)) return plan_decode(c, out);
+    if (const int sk5 = skinny_split_auto(c); sk5 || skinny_auto(c)) {
+        Ovr o5 = ov;
+        if (sk5) o5.splitk = sk5;
+        Planned q{};
+        if (plan_skinny(bits, c.lg, M, N, K, o5, workspace_bytes, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
-    // Split-K block kernel (qgemm_splitk.h): by override (family 6); by template - Stages 5 of the automatic digit at
-    // M >= 128 (SMs_Multiple 1 / 2 / 4: the cost model's best / second / third K split; those ids' old meaning, a quarter of
-    // the per-wave kernel's in-workgroup K split, is still reachable through digits 1 .. 3); automatically below, when
-    // its modelled time beats what the other MFMA kernels are modelled at
-    if (ov.family == kFamilySplitK) {
-        const int src = plan_splitk(bits, lg, M, N, K, num_sms, ov, workspace_bytes, p);
-        if (src == FLUTE_OK && p->lds_bytes > (size_t)kMaxLds) return FLUTE_ERR_SHAPE;
-        return src;
+    if (splitk_stages5(c)) {
+        Planned q{};
+        const int rank = c.t.sms_multiple == 1 ? 0 : (c.t.sms_multiple == 2 ? 1 : 2);
+        if (plan_splitk(bits, c.lg, M, N, K, c.num_sms, ov, workspace_bytes, &q.p, rank) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
-    // (round 4, late: 4-bit layers from M = 33, 2-bit layers from M = 65 - 64-row tiles x K slices against the per-wave kernel:
-    // M = 64 x 8192^2 24.7 -> 20.0 us, M = 33 23.7 -> 19.5, M = 96 x 14336 x 4096 41.2 -> 24.6, M = 96 x 8192^2 45.3 -> 28.6;
-    // 2 bits M = 96: 8192^2 43.3 -> 29.0, 14336 x 4096 40.5 -> 25.4; 2 bits at M = 64 gain 3 .. 9 % only: left alone)
-    // (overrides of the per-wave kernel - m_tiles, waves, kw, splitk, slabs - mean something else in plan_splitk: a call that sets
-    // any of them without family = 6 keeps the per-wave / block kernels)
-    const bool wave_ovr = ov.m_tiles > 0 || ov.waves > 0 || ov.kw > 0 || ov.splitk > 0 || ov.slabs > 0 || ov.m_block > 0;
-    const bool sk_regime = ov.family < 0 && !wave_ovr && family == 2 && bits != 3 && (M >= 128 || M >= 33) && auto_digit_sk(bits, template_id);      // (2 bits: from M = 65 until round 6 - with 64 x 64 tiles M = 48 / 64 gain 25 - 43 %: profiles/r06/planner_regret_before_fixes.json)
-    if (sk_regime && t.stages == 5 && M > 64) {       // (M <= 64: the table's Stages-5 ids of that bucket were tuned on the per-wave kernel's K split)
-        if (plan_splitk(bits, lg, M, N, K, num_sms, ov, workspace_bytes, p, t.sms_multiple == 1 ? 0 : (t.sms_multiple == 2 ? 1 : 2)) == FLUTE_OK)
-            return FLUTE_OK;
-        memset(p, 0, sizeof(*p));
-    }
-    // Block-tiled prefill kernels (qgemm_block2.h: 256 x 256 or 128 x 256 blocks, a wave owns all rows and 32
-    // columns, 4- and 2-bit layers; qgemm_block3.h: the same for 3 bits, 128-row blocks); scale rows in
-    // whole 16-B granules.  No K split for 2 / 4 bits (qgemm_splitk.h serves that regime; 3 bits: priced below), so what decides is
-    // how many blocks the output has.  Cost model fitted to tools/block_lab.py (MI355X, K = 4096; us per block,
-    // running alone / with the whole chip busy - the chip clocks down under a full MFMA load):
-    //   256-row block fp16 100 / 126, bf16 104 / 129;  128-row block fp16 72 / 81, bf16 80 / 89 (round 2);
-    //   round 4 (2- / 4-bit blocks: whole-line activation pieces, one whole-line weight request per step):
-    //   256-row 97 / 120, bf16 101 / 124;  128-row 62 / 74, bf16 70 / 78 (profiles/r04/splitk_lab_run7*.jsonl);
-    //   per-wave MFMA kernel (family 2): 520 ... 730 TFLOP/s fp16, 400 ... 560 bf16 for M = 256 ... 4096.
-    int blk_cfg = -1, blk_sk = 0;                     // blk_sk: grid K split the cost model chose with the block shape (3 bits)
-    size_t blk_slabs = 0;                             // bytes of fragment-order slabs when a 3-bit block plan combines its K slices in the launch
-    double alt_us = -1.0;                             // modelled time of the best other MFMA kernel (set by the block cost model)
-    const int blk_units = 256 / J;                    // units of a 256-column block (4-bit: 64, 2-bit: 32, 3-bit: 16)
-    const bool b3_ok = bits != 3 || (size_t)3 * (N >> 4) * K * 2 < (size_t)0xfffffff0u;   // one descriptor over Q
-    const bool x32_ok = (size_t)(M + 256) * K * 2 < (size_t)0xfffffff0u;       // activation byte offsets are 32-bit voffsets
-    if (b3_ok && x32_ok && (K >> lg) % 8 == 0 && units % blk_units == 0 && K % 64 == 0 &&
-        (family == 2 || ov.family == kFamilyBlock) && (ov.family < 0 || ov.family == kFamilyBlock)) {
-        const long tiles256 = (long)ceil_div(M, 256) * (units / blk_units), tiles128 = (long)ceil_div(M, 128) * (units / blk_units);
-        if (ov.family == kFamilyBlock) {
-            blk_cfg = (ov.m_tiles == 4) ? 5 : 4;             // 128- / 256-row blocks of qgemm_block2.h
-            if (bits == 3 && ov.m_tiles != 8) blk_cfg = 5;   // 3-bit layers: 128-row blocks of qgemm_block3.h unless 256 rows are asked for ...
-            if (bits == 3 && (ov.m_block == 1 || ov.m_block == 2 || ov.m_block == 4))
-                blk_cfg = 8 + ov.m_block;                    // ... or its skinny blocks of m_block row tiles
-        } else if (bits == 3 && M > 32 && M <= 64 && (size_t)N * K >= ((size_t)56 << 20) &&
-                   (M > 48 || skinny3_fills(M, units / blk_units, K, lg, num_sms))) {    // (14336 x 3584, 51 M weights: 29.5 against 26.4 us on the per-wave kernel)
-            // 3-bit skinny blocks (64 rows, grid K split): measured against the per-wave kernel at M = 64 - 8192^2 31.6 vs
-            // 38.5 us, 28672x8192 86.9 vs 105.7, 4096x14336 31.8 vs 35.4; slower below M = 33 and on 4096^2 (fixed
-            // costs of ~8 us per call: prologue, fp32 slabs, reduce launch)
-            blk_cfg = 12;
-        } else if (M >= 256 || (bits == 3 && M > 64) || (bits != 3 && M > 128)) {          // (3 bits from M = 65: the K-split candidates below; 2 / 4 bits from M = 129: 128-row blocks on the
-            // widest layers - 2-bit 28672 x 8192 at M = 192 ran 210 us on the per-wave kernel, 125 on 128-row blocks, profiles/r06/planner_regret_bits_4_2_m96_to_768_unswept_batch_sizes.json)
-            const bool bf = dtype == FLUTE_BF16;
-            auto block_us = [&](long tiles, double alone, double busy) {
-                const long whole = tiles / num_sms, rest = tiles % num_sms;       // full rounds + a last partial one
-                const double last = rest == 0 ? 0.0 : (rest * 4 >= (long)num_sms * 3 ? busy : alone);
-                return ((double)whole * busy + last) * (double)K / 4096.0 + 3.0;
-            };
-            // 3-bit layers (qgemm_block3.h): 128-row blocks 78 / 85 us alone, 85 / 90 busy; 256-row blocks (round 3) 108 / 118
-            // alone, 124 / 128 busy (profiles/r03/block_lab_w3_256_row_blocks.jsonl); the per-wave kernel runs them at
-            // 330-380 TFLOP/s
-            const double t256 = (bits == 3) ? block_us(tiles256, bf ? 118.0 : 108.0, bf ? 128.0 : 124.0)
-                                            : block_us(tiles256, bf ? 101.0 : 97.0, bf ? 124.0 : 120.0);
-            const double t128 = (bits == 3) ? block_us(tiles128, bf ? 85.0 : 78.0, bf ? 90.0 : 85.0)
-                                            : block_us(tiles128, bf ? 70.0 : 62.0, bf ? 78.0 : 74.0);
-            // per-wave kernel: 520 (bf16 400) TFLOP/s at M = 256, + 55 per doubling of M, up to 730 (560)
-            int dbl = 0;
-            for (int m = M; m >= 512; m >>= 1) ++dbl;
-            // (3 bits, round 4: 14336 x 3584 M = 256 runs at 305, modelled 370 kept it off the 128-row blocks: 86.4 against 70.3 us; round 5's
-            // regret sweep, fp16: 3584 x 8192 M = 256 293, 14336 x 3584 M = 128 276, 8192^2 M = 96 253 - fewer rows, fewer MFMAs per lookup)
-            const double wave_tf = (bits == 3) ? (bf ? 290.0 : 300.0) * (M >= 256 ? 1.0 : 0.6 + 0.4 * M / 256.0)
-                                   : (M < 512 ? wave_tf_mid(M, bits, bf)
-                                              : (bf ? std::min(560.0, 400.0 + 55.0 * dbl) : std::min(730.0, 520.0 + 55.0 * dbl)) * (bits == 2 ? 0.65 : 1.0));   // (2 bits: see below)
-            const double wave_us = 2.0 * M * (double)N * K / (wave_tf * 1e6);
-            if (t256 <= t128 && t256 < wave_us) blk_cfg = 4;
-            else if (t128 < t256 && t128 < wave_us) blk_cfg = 5;
-            alt_us = std::min(wave_us, std::min(t256, t128));
-            if (bits == 3) {
-                // 3-bit layers have no split-K block kernel of their own (qgemm_splitk.h: 2 / 4 bits): where whole blocks leave
-                // CUs idle, 128- or 64-row blocks of qgemm_block3.h with a grid K split (fp32 slabs + the reduce pass) fill
-                // them.  One round of workgroups; a block costs ~4 us + its K share of (128 rows: 78 / 85 us alone, 85 / 90 busy;
-                // 64 rows: 66 / 72 - the lookups of a block's 256 columns dominate, the rows are nearly free), the slabs 0.25 us
-                // per MB + the reduce launch.  Measured (bf16, profiles/r04/w3_mid_m_forced_plans.jsonl; before -> after):
-                // M = 1024 x 4096^2 84.9 -> 56.4 us, M = 512 x 8192^2 160.5 -> 95.6, M = 512 x 4096^2 54.5 -> 45.4
-                const double base = blk_cfg == 4 ? t256 : (blk_cfg == 5 ? t128 : wave_us);
-                double best = 0.95 * base;                      // a K-split plan has to beat the unsplit best by 5 %; among themselves: the cheapest
-                const int align_k = std::max(64, 8 << lg);
-                for (int rows = 128; rows >= 64; rows >>= 1) {
-                    const long tiles = (long)ceil_div(M, rows) * (units / blk_units);
-                    const double alone = rows == 128 ? (bf ? 85.0 : 78.0) : (bf ? 72.0 : 66.0);
-                    const double busy = rows == 128 ? (bf ? 90.0 : 85.0) : (bf ? 72.0 : 70.0);
-                    for (int sk = (rows == 128 ? 2 : 1); sk <= 4; sk *= 2) {
-                        const long wgs = tiles * sk;
-                        // slices of kps k, the last one shorter where K is no multiple (K = 3584: 2048 + 1536, or 3 x 1024 + 512 - round 5:
-                        // 14336 x 3584 M = 128 47.6 -> 33.9 us, M = 256 61.7 -> 49.3; until then only equal slices were priced)
-                        const int kps = round_up(ceil_div(K, sk), align_k);
-                        if (sk > 1 && (wgs > (long)num_sms || ceil_div(K, kps) != sk || kps < 1024 ||
-                                       (size_t)sk * tiles * rows * 1024 > slab_room(workspace_bytes))) continue;
-                        double us;
-                        if (sk == 1) us = block_us(tiles, alone, busy);
-                        else us = 4.0 + ((wgs * 4 >= (long)num_sms * 3 ? busy : alone) - 4.0) * (double)kps / 4096.0 +
-                                  (rows == 128 ? 2.0 : 5.0) +              // (128-row blocks: combined in the launch, round 5; else the reduce launch)
-                                  0.25 * (double)sk * M * N * 4.0 / 1e6;
-                        if (us < best) { best = us; blk_cfg = rows == 128 ? 5 : 12; blk_sk = sk; }
-                    }
-                }
-                alt_us = std::min(alt_us, blk_sk > 0 ? best : base);
-            }
-        }
-        if (blk_cfg >= 0) family = kFamilyBlock;
-    }
-    // Split-K block kernel, automatic (the template's default Stages and SMs_Multiple): taken when its modelled time is
-    // 8 % under the best of the per-wave kernel (520 TFLOP/s at M = 256, - 55 at 128, + 55 per doubling) and the block kernels.
-    // Measured (tools/splitk_lab.py, us, automatic plan of round 3 -> this kernel): M = 256 x 4096 x 11008 44.5 -> 38.1,
-    // 4096 x 14336 47.2 -> 40.2, 8192^2 49.0 -> 44.2; M = 1024 x 4096^2 49.6 -> 41.8 (torch.mm 46.9), M = 512 29.0 -> 27.4;
-    // not taken: M = 256 x 4096^2 (24.9 against 20.1: the seam of four slices), M = 128 x 4096^2, K = 14336.
-    if (sk_regime && t.stages == 2 && t.sms_multiple == 1 && (blk_cfg < 0 || blk_cfg == 4 || blk_cfg == 5)) {
-        if (alt_us < 0.0) {
-            const bool bf = dtype == FLUTE_BF16;
-            int dbl = M < 256 ? -1 : 0;
-            for (int m = M; m >= 512; m >>= 1) ++dbl;
-            double wave_tf = bf ? std::min(560.0, 400.0 + 55.0 * dbl) : std::min(730.0, 520.0 + 55.0 * dbl);
-            // (2-bit layers: twice the lookups per byte - the per-wave kernel ran M = 384 on 4096^2 at 316 TFLOP/s where the 4-bit layer runs 503:
-            // profiles/r06_planner_regret_between_final.json)
-            if (bits == 2) wave_tf *= 0.65;
-            if (M >= 128 && M < 512) wave_tf = wave_tf_mid(M, bits, bf);
-            if (M < 128) {
-                // per-wave kernel below M = 128 (measured fp16, tools/time_cases.py): 220 .. 280 TFLOP/s at M = 48, 270 .. 350 at
-                // M = 64 .. 96 on layers up to 14336 columns; 490 .. 570 on 28672 columns (two slabs per wave, every CU busy)
-                wave_tf = std::min(300.0, 5.5 * M) * (bf ? 0.8 : 1.0);
-                if (N >= 16384) wave_tf *= 1.8;
-                // (the 2-bit factor holds here too - it was applied above the branch only: 2-bit M = 48 on 4096^2 kept the per-wave kernel x 4 K slices,
-                // 15.0 us, where 64 x 64 tiles x 4 slices run 11.1: profiles/r06_planner_regret_final_tree_between.json)
-                if (bits == 2) wave_tf *= 0.65;
-            }
-            alt_us = 2.0 * M * (double)N * K / (wave_tf * 1e6);
-        }
-        flute_plan q;
+    const BlockChoice b = choose_block(c);
+    if (splitk_auto(c)) {
+        const double alt_us = b.alt_us >= 0.0 ? b.alt_us : flop_us(c, wave_tflops(c));
         double sk_us = 0.0;
-        // (one round of workgroups only: multi-round launches are left to the tuner's Stages-5 ids until measured)
-        // (round 6: 64 x 64 tiles - four K parts per workgroup - that fill at least half the chip are priced against the per-wave kernel
-        // WITH its fixed part, which the TFLOP/s model above lacks: measured - modelled 3.2 .. 5.7 us on 4096-wide layers, 10 on
-        // 2048 x 8192; profiles/r06/call17_automatic_plan_vs_forced.log: M = 128 on 4096^2 13.1 against 14.9 us, M = 192 15.1 / 18.8, M = 512 on
-        // 2048 x 4096 15.8 / 19.9, M = 256 on 2048 x 8192 18.0 / 26.6, M = 48 on 3584 x 14336 16.7 / 21.6, M = 33 on 8192^2 17.7 / 26.1)
-        if (plan_splitk(bits, lg, M, N, K, num_sms, ov, workspace_bytes, &q, 0, &sk_us) == FLUTE_OK &&
-            sk_us < ((q.kw == 4 && (long)q.grid * 2 >= (long)num_sms) ? alt_us + 4.0 : 0.92 * alt_us) &&
-            (long)q.grid <= (bits == 2 && M <= 64 ? 2L : 1L) * (long)num_sms && q.lds_bytes <= (size_t)kMaxLds) {
-            // (2-bit layers up to M = 64: also two rounds - 28672 x 8192 M = 33 / 48 / 64: 448 workgroups of 64 x 128 tiles x 2 slices 46.6 / 47.8 / 49.3 us
-            // against the per-wave kernel's 61.3 / 61.5 / 62.3, profiles/r06/planner_regret_b2_m33_96_after_2bit_rate_fix.json)
-            *p = q;
+        Planned q{};
+        if (plan_splitk(bits, c.lg, M, N, K, c.num_sms, ov, workspace_bytes, &q.p, 0, &sk_us) == FLUTE_OK && splitk_auto_taken(c, q.p, sk_us, alt_us)) {
+            *out = q;
             return FLUTE_OK;
         }
     }
-    p->family = family;
-
-    int rc = FLUTE_OK;
-    if (family == 0) {
-        // Three decode kernels: the one-shot kernel (qgemm_oneshot.h: non-persistent workgroups, every request up
-        // front) and the persistent ring kernel (qgemm_stream.h).  Forced by override (one_shot 1 / 0; an explicit
-        // ring depth or grid K split means the ring kernel) or by the template (4-bit QuantMapMode digit 1, 2:
-        // one-shot with 4 / 8 pieces per wave, 3: ring; 2- / 3-bit SMs_Multiple 4: one-shot, 2: ring); automatic:
-        // one-shot for layers up to 64 M weights that give at least half the CUs a workgroup; one or two rows on larger layers:
-        // the persistent one-shot kernel (qgemm_persist.h; override one_shot = 3, as flute_plan reports it, or 2).
-        int want = ov.one_shot == 3 ? 2 : ov.one_shot;       // 3 = flute_plan's code for the persistent kernel (2 kept from ABI v4)
-        if (want < 0 && (ov.depth > 0 || ov.splitk > 1)) want = 0;
-        if (want < 0 && bits == 4) { const int q = template_id % 4; want = (q == 3) ? 0 : ((q == 1 || q == 2) ? 1 : -1); }
-        if (want < 0 && bits != 4) want = (t.sms_multiple == 2) ? 0 : (t.sms_multiple == 4 ? 1 : -1);
-        bool taken = false;
-        // lean one-row kernel (qgemm_fast.h): by override (one_shot = 4), or automatically for the ids whose last digit leaves the choice
-        // to the planner and whose Stages digit asks for the planner's first or second shape (4-bit QuantMapMode digit 0, Stages 2 / 3,
-        // SMs_Multiple 1: ids 0 / 4 - TileP 64 - and 16 / 20 - TileP 32), on K = 2048 / 4096 layers up to 48 M weights that give at
-        // least half the CUs a workgroup - measured against the persistent and the round-4 one-shot kernel (us, persistent / lean /
-        // one-shot): 4096^2 4.42 / 4.05 / 4.14, 5120 4.96 / 4.90 / 5.88, 8192 5.51 / 5.46 / 5.91, 11008 7.54 / 6.86 / 8.04; not taken:
-        // 14336 7.85 / 8.27 / 8.43, 28672 13.6 / 13.9 / 14.6, more than three workgroups per CU (16384 x 2048: 5.97 against 5.49 on the
-        // one-shot kernel; 8192 x 2048 3.77 / 4.05 is taken), K = 8192 (8192^2 8.42 against 10.42, 4096 x 8192 5.71 / 5.97: by
-        // override only).  Two to four rows (dot products per row on the same lookups): while ONE round of workgroups covers the layer
-        // (4096^2: M = 2 5.04 -> 4.29 us, M = 3, 4 6.25 -> 5.03; 4096 x 2048: 3.87 -> 3.25, 4.65 -> 3.71; beyond, the persistent kernel
-        // (M = 2) and the skinny MFMA kernel (M = 3, 4) win: 8192 x 4096 5.79 against 7.12, 8.69 against 8.98).  Never for a call that
-        // fuses the Hadamard rotation.  K = 8192 (shape (8, 2, 8)), round 5's last call series: one row a tie with the one-shot kernel
-        // (3584 x 8192: 5.33 / 5.40 us, 4096 x 8192: 5.57 / 5.51), TWO rows on layers that give >= 80 % of the CUs a workgroup 6.11 against
-        // 6.78 and 6.33 against 6.82 - taken; narrower layers (2048, 1024 columns: 128 / 64 workgroups) lose 13 - 17 % and are not.
-        // K = 2048, two rows: up to two rounds (6144 x 2048 4.34 -> 3.79 us, 8192 x 2048 4.38 -> 4.01; four rows lose there: 5.14 / 5.76)
-        if ((want == 4 || (want < 0 && bits == 4 && (template_id % 4) == 0 && t.stages <= 3 && t.sms_multiple == 1 && ov.waves < 0)) &&
-            !ov.had8 && ov.kw < 0) {
-            flute_plan q;
-            memset(&q, 0, sizeof(q));
-            if (plan_fast(bits, lg, M, N, K, num_sms, std::max(0, t.stages - 2), want == 4 ? ov.waves : -1, &q, oa) == FLUTE_OK &&
-                (want == 4 || ((K != 8192 || (M == 2 && (long)q.grid * 5 >= (long)num_sms * 4)) &&
-                               (size_t)N * K <= ((size_t)48 << 20) && (long)q.grid * 2 >= (long)num_sms &&
-                               (long)q.grid <= (M == 1 ? 3L : (M == 2 && K == 2048 ? 2L : 1L)) * num_sms))) {
-                *p = q;
-                taken = true;
-            }
-        }
-        if (want == 4 && !taken) want = -1;
-        // persistent one-shot kernel: by override, or automatically (one or two rows; four rows measured 1.7x the one-row
-        // time - no faster than the MFMA kernel, profiles/r03/decode_lab_persist_rows.jsonl) on layers of >= 40 M weights that give
-        // every CU six whole unit rows (below that the in-workgroup K split of the other two kernels wins:
-        // profiles/r03/persist_lab.txt)
-        const bool persist_auto = !taken && want < 0 && persist_auto_ok(M);
-        if (!taken && (want == 2 || persist_auto)) {
-            flute_plan q;
-            memset(&q, 0, sizeof(q));
-            if (plan_persist(bits, lg, M, N, K, num_sms, t, ovd, &q, oa) == FLUTE_OK) { *p = q; taken = true; }
-            else if (want == 2) want = 0;
-        }
-        if (!taken && want != 0) {
-            flute_plan q;
-            memset(&q, 0, sizeof(q));
-            if (plan_oneshot(bits, lg, M, N, K, num_sms, t, template_id, ovd, &q, oa) == FLUTE_OK &&
-                (want == 1 || ((size_t)N * K <= ((size_t)64 << 20) && (long)q.grid * 2 >= (long)num_sms))) {
-                *p = q;
-                taken = true;
-            }
-        }
-        if (!taken) rc = plan_stream(dtype, bits, lg, M, N, K, num_sms, t, ovd, slab_room(workspace_bytes), p, sa);
-    } else if (family == kFamilyBlock) {
-        const int bm = block_rows(blk_cfg), tm = bm / 32;
-        const int tiles_m = ceil_div(M, bm), tiles_n = units / (256 / J);
-        const int align_k = std::max(64, 8 << lg);
-        int splitk = (ov.splitk > 0) ? ov.splitk : (blk_sk > 0 ? blk_sk : 1);
-        if (blk_cfg >= 8 && ov.splitk <= 0 && blk_sk == 0)   // skinny blocks: the K split fills the chip
-            while ((long)tiles_m * tiles_n * splitk * 2 <= (long)num_sms && K / (splitk * 2) >= std::max(256, align_k)) splitk *= 2;
-        int kps = round_up(ceil_div(K, splitk), align_k);
-        splitk = ceil_div(K, kps);
-        while (splitk > 1 && (size_t)splitk * M * N * 4 > slab_room(workspace_bytes)) {
-            splitk >>= 1;
-            kps = round_up(ceil_div(K, splitk), align_k);
-            splitk = ceil_div(K, kps);
-        }
-        if (splitk == 1) kps = K;
-        p->m_block = blk_cfg; p->m_tiles = tm; p->slabs_per_wave = 1; p->waves = 8; p->kw = 1;
-        p->splitk = splitk; p->k_per_split = kps;
-        p->grid = (unsigned)((long)tiles_m * tiles_n * splitk);
-        p->block = 512;
-        // 3-bit 128-row blocks x 2 / 4 K slices (round 5): the slices of a block meet inside the launch (xwg.h, E form; slabs in
-        // fragment order, whole blocks: tiles x 128 x 256 x 4 B per slice) - no reduce launch.  Measured against the reduce launch
-        // (bf16, us, profiles/r05/call24_w3_inlaunch_and_line_planes.log): M = 1024 x 4096^2 56.3 -> 53.0 (fp16 53.4 -> 50.1),
-        // M = 256 x 8192^2 56.0 -> 54.4, M = 512 x 8192^2 95.3 -> 92.7, M = 96 x 28672 x 8192 92.1 -> 89.0, M = 512 x 4096^2 a tie; NOT for
-        // the skinny blocks (64 rows x 4 slices 46.7 -> 47.8; 8 slices, L form - the last arriver reads seven partials - 30.5 -> 32.6)
-        if (bits == 3 && (splitk == 2 || splitk == 4) && bm == 128 && (long)tiles_m * tiles_n <= (long)kXwgMaxTiles && !block3_two_launch()) {
-            const size_t slabs = (size_t)splitk * tiles_m * tiles_n * bm * 1024;
-            if (slabs <= slab_room(workspace_bytes) && slabs < ((size_t)1 << 31)) { p->splitk_mode = 1; blk_slabs = slabs; }
-        }
-        // pair table + three activation stages + per wave: two scale blocks and a sink
-        // (3-bit 256-row blocks: + 18 KB, the second / third plane pieces of waves 6 and 7)
-        p->lds_bytes = (size_t)((128 << (2 * bits)) + 3 * (bm / 16) * 2 * 1024 + 8 * 3 * 1024 + ((bits == 3 && bm == 256) ? 18 * 1024 : 0));
-        p->lut_copies = 32;
-    } else {
-        // M > decode range: MFMA kernel (qgemm_tile.h).  MT 16-row tiles per wave (1 for M <= 16),
-        // R lanes share a unit: pick the smallest R whose slab x row-tile count fills the chip; the
-        // rest of the parallelism is the in-workgroup K split, a grid-level split only for very
-        // narrow layers.
-        int mt = (M <= 16) ? 1 : (M <= 32 ? 2 : 4);
-        const int mt_cap = (bits == 3) ? 2 : 4;
-        if (mt > mt_cap) mt = mt_cap;
-        if (t.tile_m / 16 < mt && M > 16) mt = t.tile_m / 16 >= 2 ? t.tile_m / 16 : mt;
-        // SMs_Multiple = "more, smaller workgroups": halves / quarters the row tiles per wave (and,
-        // below, raises the slab count the choice of R aims for)
-        for (int m2 = t.sms_multiple; m2 > 1 && mt > 1; m2 >>= 1) mt >>= 1;
-        if (ov.m_tiles == 1 || ov.m_tiles == 2 || ov.m_tiles == 4) mt = ov.m_tiles;
-        if (mt > mt_cap) mt = mt_cap;
-        // instantiated (R, MT): (J/R)*MT <= 16 accumulator tiles, R in {1,2,4}, MT > 1 needs R <= 2
-        auto combo_ok = [&](int r, int m) {
-            if (bits == 3) return r == 1 && m == 1;
-            return (J / r) * m <= 16 && r <= 4 && (m == 1 || r <= 2);
-        };
-        while (mt > 1 && !combo_ok(1, mt) && !combo_ok(2, mt)) mt >>= 1;
-        const int mtiles = ceil_div(M, mt * 16);
-        int R = 1;
-        while (!combo_ok(R, mt)) R *= 2;
-        // Every workgroup pulls its rows of X through one CU, so lane sharing (R-fold more, narrower slabs) multiplies the
-        // activation traffic: it pays only while the workgroups leave more than ~45 % of the CUs idle (round 3,
-        // profiles/r03/tile_lab_sw2_m16.jsonl, tile_lab_sw2_m32_m128.jsonl: 10240 x 8192 M = 16, 160 slabs: R = 1 22.2 us,
-        // R = 2 26.8; M = 64: 36.7 / 49.9; 4096 x 11008 M = 64: 21.4 / 29.1; but 8192^2 M = 32, 128 slabs: R = 2 16.2, R = 1 19.3)
-        auto fills = [&](long wgs) { return wgs * 20 >= 11L * num_sms * t.sms_multiple; };
-        // ... and not at all where the grid K split can fill the chip instead (round 5's regret sweep, the in-launch seam of xwg.h being
-        // cheap now): deep layers - K >= 10240: two slices, K >= 12288: four - stop sharing lanes as soon as that split fills.
-        // 4096 x 11008 (N x K) M = 4: four lanes per unit 16.6 us, two lanes x 2 slices 14.8 (2 bits: 14.2 -> 12.5), M = 16 16.9 -> 15.4;
-        // 3584 x 14336 M = 48: two lanes x 2 slices 26.4, no sharing x 4 slices 21.6 (profiles/r05_planner_regret_*.json)
-        const long deep_split = (bits != 3 && (bits != 4 || (template_id % 4) == 0) && ov.splitk < 0) ? (K >= 12288 ? 4 : (K >= 10240 ? 2 : 1)) : 1;
-        while (combo_ok(R * 2, mt) && !fills((long)units * R / 16 * mtiles) &&
-               !(deep_split > 1 && fills((long)units * R / 16 * mtiles * deep_split))) R *= 2;
-        // QuantMapMode digit 1 (4-bit ids): no lane sharing above M = 16 - the chip is filled by the grid K split
-        // instead (8192^2 M = 64: R = 1, MT = 4, split 2 26.2 us against R = 2, MT = 2 30.3; 4096^2 prefers R = 2:
-        // the tuner decides)
-        if (bits == 4 && (template_id % 4) == 1 && combo_ok(1, mt)) R = 1;       // (M <= 16: with two slabs per wave, below)
-        // QuantMapMode digit 3 above M = 16 (round 5): no lane sharing AND two slabs per wave, the chip filled by the grid K split - the
-        // plan round 4's regret sweep wanted on 8192 x 28672 and could not reach through an id (M = 64: 72.6 -> 55.3 us, M = 48 65.0 ->
-        // 52.8, M = 32 52.4 -> 45.2).  The automatic digit takes it by itself on layers that deep (K >= 16384: a slice keeps >= 4096 k) whose halved slab count x four slices fills the chip
-        const bool deep_sw2 = bits == 4 && M > 16 && combo_ok(1, mt) && (dtype == 0 || mt <= 2) && (units / 16) % 2 == 0 && ov.m_block <= 0 &&
-                              ((template_id % 4) == 3 || ((template_id % 4) == 0 && K >= 16384 && !fills((long)(units / 16) * mtiles) && fills((long)(units / 32) * mtiles * 4)));
-        if (deep_sw2) R = 1;
-        if (ov.m_block > 0 && combo_ok(ov.m_block, mt)) R = ov.m_block;
-        // SW = 2 slabs per wave (4-bit, no lane sharing, fp16 up to MT = 4 / bf16 up to MT = 2: the bf16 path
-        // keeps a second accumulator set): every activation fragment then serves 8 column tiles and the
-        // texture-path traffic per MFMA drops by 40 %.  Worth it once halving the slab count still leaves a
-        // workgroup for every CU; QuantMapMode (the last template digit) lets the tuner force either.
-        const bool sw_ok = bits == 4 && R == 1 && (dtype == 0 || mt <= 2) && (units / 16) % 2 == 0;
-        int sw = 1;
-        // ... as soon as the halved slab count still fills 55 % of the CUs (28672 x 8192 M = 16: 448 workgroups 43.4 us, 224
-        // workgroups 37.1; M = 64: 73.4 -> 54.2; 4096 x 14336 M = 128: 38.2 -> 28.2) - or, at M <= 16, on the tuner's request (digit 1)
-        if (sw_ok && (fills((long)(units / 32) * mtiles) || (mt == 1 && M <= 16 && (template_id % 4) == 1))) sw = 2;
-        if (sw_ok && bits == 4 && ((template_id % 4) == 3 || deep_sw2)) sw = 2;
-        if (bits == 4 && (template_id % 4) == 2) sw = 1;
-        if (sw_ok && ov.slabs == 2) sw = 2;
-        if (ov.slabs == 1) sw = 1;
-        const int slabs = units * R / 16 / sw;                    // wave-sized column groups
-        int nw = (t.threads >= 1024) ? 8 : 4;                     // Threads 1024 / 512 templates
-        if (ov.waves > 0 && ov.waves <= 8) nw = floor_pow2(ov.waves);
-        while (nw > 1 && tile_geom(bits, R, mt, sw, nw, kMaxLds).depth < 2) nw >>= 1;   // ring of >= 2 slots per wave
-        int kw = nw;
-        while (kw > 1 && K / kw < 256) kw >>= 1;
-        // enough workgroups already: keep more of K per wave (fewer partial tiles to reduce)
-        while (kw > 1 && (long)slabs * mtiles / (nw / kw) >= 2L * num_sms * t.sms_multiple && K / kw < 1024) kw >>= 1;
-        if (t.stages == 3 && kw > 1) kw >>= 1;                    // the tuner's handle on the K split
-        if (t.stages == 4 && kw < nw) kw <<= 1;
-        if (t.stages == 5 && kw > 2) kw >>= 2;
-        if (ov.kw > 0 && ov.kw <= nw) kw = floor_pow2(ov.kw);
-        while (nw % kw) kw >>= 1;
-        while (slabs % (nw / kw)) kw <<= 1;
-        const long wgs = (long)slabs / (nw / kw) * mtiles;
-        int splitk = 1;
-        // 3-bit layers have no lane-sharing variants (a wave = 16 units x 16 fields = 256 columns): the grid-level K
-        // split is their only way to fill the chip, down to 64 k per wave (4096^2 M = 16: 20.5 -> 14.5 us,
-        // 4096x14336: 30.8 -> 20.2 us)
-        const int k_min = (bits == 3) ? 64 : 256;
-        while (wgs * splitk * 2 <= (long)num_sms && K / (splitk * 2 * kw) >= k_min) splitk *= 2;
-        if (ov.splitk > 0) splitk = ov.splitk;
-        int kps = round_up(ceil_div(K, splitk), 32 * kw);
-        splitk = ceil_div(K, kps);
-        while (splitk > 1 && (size_t)splitk * M * N * 4 > slab_room(workspace_bytes)) {
-            splitk >>= 1;
-            kps = round_up(ceil_div(K, splitk), 32 * kw);
-            splitk = ceil_div(K, kps);
-        }
-        if (splitk == 1) kps = K;
-        p->m_block = R; p->m_tiles = mt; p->slabs_per_wave = sw; p->waves = nw; p->kw = kw; p->splitk = splitk;
-        p->k_per_split = kps;
-        // round 4: the K slices of a (slab group, row tile) meet inside the launch (xwg.h, L form) while the slabs are small -
-        // the reduce launch it replaces costs >= 2 us; beyond 4 MB of slabs the all-CU reduce pass reads them faster than the
-        // last arrivers would
-#ifndef FLUTE_TILE_INLAUNCH_MAX
-#define FLUTE_TILE_INLAUNCH_MAX (4 << 20)     // bytes of slabs; development builds set 0 to time the two-launch form
-#endif
-        if (splitk > 1 && wgs <= kXwgMaxTiles && (size_t)splitk * M * N * 4 <= (size_t)FLUTE_TILE_INLAUNCH_MAX) p->splitk_mode = 1;
-        p->grid = (unsigned)(wgs * splitk);
-        p->block = (unsigned)(nw * 64);
-        p->lds_bytes = (size_t)tile_geom(bits, R, mt, sw, nw, kMaxLds).total;
-        p->lut_copies = 32;
-    }
-    if (rc) return rc;
-    p->workspace_needed = p->splitk > 1 ? (blk_slabs ? blk_slabs : (size_t)p->splitk * M * N * 4) + kXwgFlagBytes : 0;
-    if (p->lds_bytes > (size_t)kMaxLds) return FLUTE_ERR_SHAPE;
-    return FLUTE_OK;
+    return b.cfg >= 0 ? plan_block(c, b, out) : plan_tile(c, out);
 }
 
 // make_plan is a pure function of its arguments and runs on every call of the operator (ranking the decode
@@ -1149,11 +1220,10 @@ struct PlanKey {
     Ovr ov;
     bool operator==(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) == 0; }
 };
-struct PlanEntry { PlanKey key; int rc; flute_plan plan; flute_template_info tinfo; StreamArgs sa; OneArgs oa; bool valid; };
+struct PlanEntry { PlanKey key; int rc; Planned plan; flute_template_info tinfo; bool valid; };
 
 int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_id, int num_sms,
-              size_t workspace_bytes, const Ovr& ov, flute_plan* p, flute_template_info* tinfo,
-              StreamArgs* sa, OneArgs* oa) {
+              size_t workspace_bytes, const Ovr& ov, Planned* out, flute_template_info* tinfo = nullptr) {
     constexpr int kEntries = 32;
     thread_local PlanEntry cache[kEntries] = {};
     thread_local int next = 0;
@@ -1164,7 +1234,7 @@ int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_
     for (int i = 0; i < kEntries; ++i) {
         const PlanEntry& e = cache[i];
         if (e.valid && e.key == key) {
-            if (e.rc == FLUTE_OK) { *p = e.plan; if (tinfo) *tinfo = e.tinfo; if (sa) *sa = e.sa; if (oa) *oa = e.oa; }
+            if (e.rc == FLUTE_OK) { *out = e.plan; if (tinfo) *tinfo = e.tinfo; }
             return e.rc;
         }
     }
@@ -1172,23 +1242,41 @@ int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_
     next = (next + 1) % kEntries;
     e.valid = false;
     e.key = key;
-    memset(&e.plan, 0, sizeof(e.plan));
-    memset(&e.sa, 0, sizeof(e.sa));
-    memset(&e.oa, 0, sizeof(e.oa));
-    e.rc = make_plan_uncached(dtype, bits, group, M, N, K, template_id, num_sms, workspace_bytes, ov, &e.plan, &e.tinfo,
-                              &e.sa, &e.oa);
+    e.plan = Planned{};
+    e.rc = make_plan_uncached(dtype, bits, group, M, N, K, template_id, num_sms, workspace_bytes, ov, &e.plan, &e.tinfo);
     e.valid = true;
-    if (e.rc == FLUTE_OK) { *p = e.plan; if (tinfo) *tinfo = e.tinfo; if (sa) *sa = e.sa; if (oa) *oa = e.oa; }
+    if (e.rc == FLUTE_OK) { *out = e.plan; if (tinfo) *tinfo = e.tinfo; }
     return e.rc;
 }
 
-StreamKernel pick_stream_kernel(int bits, int dtype, int tile_p, int mb, int depth, int one_shot) {
-    if (bits == 4) return stream_kernel_b4(dtype, tile_p, mb, depth, one_shot);
-    if (bits == 3) return stream_kernel_b3(dtype, tile_p, mb, depth, one_shot);
-    return stream_kernel_b2(dtype, tile_p, mb, depth, one_shot);
-}
+// ---- launching a plan ---------------------------------------------------------------------------------------
 
-QGemmKernel pick_kernel(int family, int bits, int dtype, int tile_p, int mblk, int mtiles, int sw) {
+// each family's kernel for a bit width and dtype (nullptr: not instantiated)
+StreamKernel stream_kernel(int bits, int dtype, int tile_p, int mb, int depth) {
+    if (bits == 4) return stream_kernel_b4(dtype, tile_p, mb, depth, 0);
+    if (bits == 3) return stream_kernel_b3(dtype, tile_p, mb, depth, 0);
+    return stream_kernel_b2(dtype, tile_p, mb, depth, 0);
+}
+OneKernel oneshot_kernel(int bits, int dtype, int tile_p, int mb, int depth, int had, int pipe) {
+    if (bits == 4) return dtype == 0 ? oneshot_kernel_b4_f16(tile_p, mb, depth, had, pipe) : oneshot_kernel_b4_bf16(tile_p, mb, depth, had, pipe);
+    if (bits == 2) return dtype == 0 ? oneshot_kernel_b2_f16(tile_p, mb, depth, had, pipe) : oneshot_kernel_b2_bf16(tile_p, mb, depth, had, pipe);
+    return oneshot_kernel_b3(dtype, tile_p, mb, depth, had, pipe);
+}
+PersistKernel persist_kernel(int bits, int dtype, int tile_p, int mb, int depth, int nsets, int had) {
+    if (bits == 4) return persist_kernel_b4(dtype, tile_p, mb, depth, nsets, had);
+    if (bits == 2) return persist_kernel_b2(dtype, tile_p, mb, depth, nsets, had);
+    return persist_kernel_b3(dtype, tile_p, mb, depth, nsets, had);
+}
+PersistMKernel persistm_kernel(int bits, int dtype, int tile_p, int lg, int ng, int xr, int waves, int xres) {
+    if (bits == 4) return dtype == 0 ? persistm_kernel_b4_f16(tile_p, lg, ng, xr, waves, xres) : persistm_kernel_b4_bf16(tile_p, lg, ng, xr, waves, xres);
+    return dtype == 0 ? persistm_kernel_b2_f16(tile_p, lg, ng, xr, waves, xres) : persistm_kernel_b2_bf16(tile_p, lg, ng, xr, waves, xres);
+}
+BlockKernel block_kernel(int bits, int dtype, int tile_p, int cfg) {
+    if (bits == 4) return block_kernel_b4(dtype, tile_p, cfg);
+    if (bits == 3) return block_kernel_b3(dtype, tile_p, cfg);
+    return block_kernel_b2(dtype, tile_p, cfg);
+}
+QGemmKernel tile_kernel(int bits, int dtype, int tile_p, int mblk, int mtiles, int sw) {
     if (bits == 4) return tile_kernel_b4(dtype, tile_p, mblk, mtiles, sw);
     if (bits == 3) return tile_kernel_b3(dtype, tile_p, mblk, mtiles);
     return tile_kernel_b2(dtype, tile_p, mblk, mtiles);
@@ -1214,6 +1302,31 @@ int ensure_lds(const void* fn, size_t bytes) {
     }
     if (g_big_lds_n < 512) g_big_lds[g_big_lds_n++] = BigLds{dev, fn};
     return 0;
+}
+
+// One kernel launch of a plan: its grid, block and dynamic LDS (granted first where it exceeds 64 KB).  A kernel that is
+// not instantiated is FLUTE_ERR_TEMPLATE_ID.
+template <class Kernel>
+int launch(Kernel fn, const flute_plan& p, void** kargs, hipStream_t st) {
+    const void* f = reinterpret_cast<const void*>(fn);
+    if (!f) return FLUTE_ERR_TEMPLATE_ID;
+    if (ensure_lds(f, p.lds_bytes)) return FLUTE_ERR_LAUNCH;
+    if (hipLaunchKernel(f, dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return FLUTE_ERR_LAUNCH;
+    }
+    return FLUTE_OK;
+}
+
+// FLUTE_STAMPS builds: per-wave phase timestamps (128 B a wave) at byte `offset` of the workspace, where they fit; else none.
+// Bytes [0, kXwgFlagBytes) hold the xwg state words, which must stay zero between calls.
+uint64_t* stamps_at(void* workspace, size_t workspace_bytes, size_t offset, const flute_plan& p) {
+#ifdef FLUTE_STAMPS
+    if (workspace && workspace_bytes >= offset + (size_t)p.grid * p.waves * 128)
+        return reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + offset);
+#endif
+    (void)workspace; (void)workspace_bytes; (void)offset; (void)p;
+    return nullptr;
 }
 
 // The decode kernels can rotate the activations while staging them - every workgroup rotates ALL rows for itself, so the
@@ -1263,8 +1376,10 @@ int flute_get_template_info(int num_bits, int template_id, flute_template_info* 
 int flute_qgemm_plan_ex(int dtype, int num_bits, int group_size, int M, int N, int K, int template_id,
                         int num_sms, size_t workspace_bytes, const flute_overrides* ovr, flute_plan* out) {
     if (!out) return FLUTE_ERR_NULL;
-    return make_plan(dtype, num_bits, group_size, M, N, K, template_id, num_sms, workspace_bytes,
-                     ovr_of(ovr), out, nullptr, nullptr, nullptr);
+    Planned pl;
+    const int rc = make_plan(dtype, num_bits, group_size, M, N, K, template_id, num_sms, workspace_bytes, ovr_of(ovr), &pl);
+    if (rc == FLUTE_OK) *out = pl.p;
+    return rc;
 }
 
 int flute_qgemm_plan(int dtype, int num_bits, int group_size, int M, int N, int K,
@@ -1283,21 +1398,20 @@ int flute_qgemm(int dtype, int num_bits, int group_size, int M, int N, int K, in
 
 // Calls that will fuse the rotation prefer 8-wave workgroups: the rotation is done by the workgroup's waves, 512 k each - 8 waves
 // rotate a 4096-k row in one pass (4096x3584 M = 1: 5.5 us with 8 waves, 6.5 with the 4-wave shape the plain product prefers).
-// (Applied inside the decode branch of the planner only: make_plan_uncached.  Round 3 also forced the four-row decode
+// (Applied inside the decode planner only: plan_decode.  Round 3 also forced the four-row decode
 // kernel at M = 3, 4 to keep the rotation fused: measured again in round 4, the fused form loses there - above.)
-static Ovr hadamard_ovr(Ovr o, int hadamard_size, int bits, int M, int N, int K) {
-    (void)bits; (void)N;
+static Ovr hadamard_ovr(Ovr o, int hadamard_size, int M, int K) {
     if (hadamard_size > 1 && hadamard_size <= 512 && M <= 4 && hadamard_worth_fusing(M, K, o.family == 0)) o.had8 = 1;
     return o;
 }
 
 int flute_qgemm_hadamard_fused(int dtype, int num_bits, int group_size, int hadamard_size, int M,
                                int N, int K, int template_id, int num_sms, size_t workspace_bytes) {
-    flute_plan p;
+    Planned pl;
     if (make_plan(dtype, num_bits, group_size, M, N, K, template_id, num_sms, workspace_bytes,
-                  hadamard_ovr(ovr_of(nullptr), hadamard_size, num_bits, M, N, K), &p, nullptr, nullptr, nullptr))
+                  hadamard_ovr(ovr_of(nullptr), hadamard_size, M, K), &pl))
         return 0;
-    return hadamard_fusable(p, hadamard_size, M, K, false) ? 1 : 0;
+    return hadamard_fusable(pl.p, hadamard_size, M, K, false) ? 1 : 0;
 }
 
 int flute_qgemm_hadamard(int dtype, int num_bits, int group_size, int hadamard_size, int M, int N,
@@ -1316,16 +1430,16 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
     if (M == 0) return FLUTE_OK;
     if (hadamard_size > 1 && (hadamard_size & (hadamard_size - 1))) return FLUTE_ERR_HADAMARD_SIZE;
     // everything is validated before anything is enqueued
-    flute_plan p;
+    Planned pl;
     flute_template_info t;
-    StreamArgs sa;
-    OneArgs oa;
     if (!workspace) workspace_bytes = 0;
     const int rc = make_plan(dtype, num_bits, group_size, M, N, K, template_id, num_sms, workspace_bytes,
-                             hadamard_ovr(ovr_of(ovr), hadamard_size, num_bits, M, N, K), &p, &t, &sa, &oa);
+                             hadamard_ovr(ovr_of(ovr), hadamard_size, M, K), &pl, &t);
     if (rc) return rc;
     if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
     if (!A || !Q || !D || !S || !QM2) return FLUTE_ERR_NULL;
+    const flute_plan& p = pl.p;
+    const OneArgs& oa = pl.oa;
     if (p.splitk > 1 && (!workspace || p.workspace_needed > workspace_bytes)) return FLUTE_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
@@ -1341,164 +1455,71 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
             A = x_scratch;
         }
     }
-    const float had_scale = 1.0f / sqrtf((float)(1 << had_log));     // as flute_hadamard: bit-identical results
+    float had_scale = 1.0f / sqrtf((float)(1 << had_log));     // as flute_hadamard: bit-identical results
+    int had = had_log > 0 ? 1 : 0;
 
-    if (p.family == kFamilySkinny) {
-        SkinnyKernel fn = skinny_kernel_b4(dtype, t.tile_p, oa.depth);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
-        uint32_t geo = SkinnyGeo::pack(oa.lg, oa.lkw, oa.ipw, p.splitk);
-        uint64_t* stamps = nullptr;
-        float* partial = workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes) : nullptr;
-        uint32_t* state = reinterpret_cast<uint32_t*>(workspace);
-#ifdef FLUTE_STAMPS   // behind the state words and the slabs
-        if (workspace && workspace_bytes >= p.workspace_needed + kXwgFlagBytes + (size_t)p.grid * p.waves * 128)
-            stamps = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + (p.workspace_needed ? p.workspace_needed : kXwgFlagBytes));
-#endif
-        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &stamps, &partial, &state};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
-    }
+    const int tp = t.tile_p;
+    const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
+    const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
+    // workspace: the xwg state words, the fp32 slabs behind them
+    uint32_t* state = reinterpret_cast<uint32_t*>(workspace);
+    float* partial = workspace ? reinterpret_cast<float*>(static_cast<char*>(workspace) + kXwgFlagBytes) : nullptr;
+    // slabs a launch left for the reduce pass (grid K split not combined inside the launch)
+    auto then_reduce = [&](int lrc) {
+        if (lrc || p.splitk == 1 || p.splitk_mode == 1) return lrc;
+        return splitk_reduce_dispatch(dtype, partial, D, (size_t)M * N, p.splitk, st);
+    };
 
-    if (p.family == 0 && p.one_shot == 3) {
-        const int had = had_log > 0 ? 1 : 0;
-        PersistKernel fn = num_bits == 4 ? persist_kernel_b4(dtype, t.tile_p, p.m_block, oa.depth, oa.nsets, had)
-                           : (num_bits == 2 ? persist_kernel_b2(dtype, t.tile_p, p.m_block, oa.depth, oa.nsets, had)
-                                            : persist_kernel_b3(dtype, t.tile_p, p.m_block, oa.depth, oa.nsets, had));
+    if (p.family == 0 && p.one_shot == 3) {              // persistent one-shot kernel
+        PersistKernel fn = persist_kernel(num_bits, dtype, tp, p.m_block, oa.depth, oa.nsets, had);
         if (!fn) return FLUTE_ERR_SHAPE;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
         uint32_t geo = PersistGeo::pack(oa.lg, p.waves, oa.nch, oa.ipw, had_log, oneshot_x_in_holes(num_bits, p.m_block, K) ? 1 : 0, M);
-        float hs = had_scale;
         int nvis = oa.nvis, nwg = oa.nwg;
-        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &nvis, &D, &hs, &nwg};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
+        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &nvis, &D, &had_scale, &nwg};
+        return launch(fn, p, kargs, st);
     }
-
+    if (p.family == 0 && p.one_shot == 4) {              // lean one-row kernel
+        int lg = oa.lg;
+        uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
+        void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &lg, &M, &stamps};
+        return launch(fast_kernel_b4(dtype, tp, p.waves, p.kw, p.ring_depth, p.m_block), p, kargs, st);
+    }
+    if (p.family == 0 && p.one_shot) {                   // one-shot kernel
+        uint32_t geo = OneGeo::pack(oa.lg, oa.lkw, oa.upw, oa.pk, oa.ipw, had_log, oneshot_x_in_holes(num_bits, p.m_block, K) ? 1 : 0);
+        uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
+        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &had_scale, &stamps};
+        return launch(oneshot_kernel(num_bits, dtype, tp, p.m_block, oa.depth, had, oa.pipe), p, kargs, st);
+    }
+    if (p.family == 0) {                                 // ring kernel
+        StreamArgs sa = pl.sa;
+        sa.A = A; sa.Q = q32; sa.D = D; sa.S = S; sa.QM2 = qm2;
+        sa.partial = partial;
+        sa.had_log = had_log; sa.had_scale = had_scale; sa.m0 = 0;
+        void* kargs[] = {&sa};
+        return then_reduce(launch(stream_kernel(num_bits, dtype, tp, p.m_block, p.ring_depth), p, kargs, st));
+    }
+    if (p.family == kFamilySkinny) {
+        uint32_t geo = SkinnyGeo::pack(oa.lg, oa.lkw, oa.ipw, p.splitk);
+        uint64_t* stamps = stamps_at(workspace, workspace_bytes, p.workspace_needed ? p.workspace_needed : kXwgFlagBytes, p);   // behind the slabs
+        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &stamps, &partial, &state};
+        return launch(skinny_kernel_b4(dtype, tp, oa.depth), p, kargs, st);
+    }
+    if (p.family == kFamilyFastM) {
+        uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
+        void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &M, &stamps};
+        return launch(fastm_kernel_b4(dtype, tp, p.waves, p.ring_depth, oa.lg, p.slabs_per_wave), p, kargs, st);
+    }
     if (p.family == kFamilyPersistM) {
-        PersistMKernel fn = num_bits == 4 ? (dtype == 0 ? persistm_kernel_b4_f16(t.tile_p, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot)
-                                                        : persistm_kernel_b4_bf16(t.tile_p, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot))
-                                          : (dtype == 0 ? persistm_kernel_b2_f16(t.tile_p, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot)
-                                                        : persistm_kernel_b2_bf16(t.tile_p, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot));
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
         int nsets = ceil_div(N / 16, p.slabs_per_wave);
         void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &K, &M, &nsets};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
+        return launch(persistm_kernel(num_bits, dtype, tp, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot), p, kargs, st);
     }
-
-    if (p.family == kFamilyFastM) {
-        FastMKernel fn = fastm_kernel_b4(dtype, t.tile_p, p.waves, p.ring_depth, oa.lg, p.slabs_per_wave);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
-        uint64_t* stamps = nullptr;
-#ifdef FLUTE_STAMPS
-        if (workspace && workspace_bytes >= kXwgFlagBytes + (size_t)p.grid * p.waves * 128)
-            stamps = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes);
-#endif
-        void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &M, &stamps};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
-    }
-
-    if (p.family == 0 && p.one_shot == 4) {
-        FastKernel fn = fast_kernel_b4(dtype, t.tile_p, p.waves, p.kw, p.ring_depth, p.m_block);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
-        int lg = oa.lg;
-        uint64_t* stamps = nullptr;
-#ifdef FLUTE_STAMPS
-        if (workspace && workspace_bytes >= kXwgFlagBytes + (size_t)p.grid * p.waves * 128)
-            stamps = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes);
-#endif
-        void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &lg, &M, &stamps};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
-    }
-
-    if (p.family == 0 && p.one_shot) {
-        OneKernel fn = nullptr;
-        const int had = had_log > 0 ? 1 : 0;
-        if (num_bits == 4) fn = dtype == 0 ? oneshot_kernel_b4_f16(t.tile_p, p.m_block, oa.depth, had, oa.pipe)
-                                           : oneshot_kernel_b4_bf16(t.tile_p, p.m_block, oa.depth, had, oa.pipe);
-        else if (num_bits == 2) fn = dtype == 0 ? oneshot_kernel_b2_f16(t.tile_p, p.m_block, oa.depth, had, oa.pipe)
-                                                : oneshot_kernel_b2_bf16(t.tile_p, p.m_block, oa.depth, had, oa.pipe);
-        else fn = oneshot_kernel_b3(dtype, t.tile_p, p.m_block, oa.depth, had, oa.pipe);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
-        const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
-        uint32_t geo = OneGeo::pack(oa.lg, oa.lkw, oa.upw, oa.pk, oa.ipw, had_log, oneshot_x_in_holes(num_bits, p.m_block, K) ? 1 : 0);
-        float hs = had_scale;
-        uint64_t* stamps = nullptr;
-#ifdef FLUTE_STAMPS
-        // behind the xwg state words (bytes [0, 64 KB) must stay zero between calls)
-        if (workspace && workspace_bytes >= kXwgFlagBytes + (size_t)p.grid * p.waves * 128)
-            stamps = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes);
-#endif
-        void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &hs, &stamps};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
-    }
-
-    if (p.family == 0) {
-        sa.A = A; sa.Q = reinterpret_cast<const uint32_t*>(Q); sa.D = D; sa.S = S;
-        sa.QM2 = reinterpret_cast<const uint32_t*>(QM2);
-        sa.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes);
-        sa.had_log = had_log; sa.had_scale = had_scale; sa.m0 = 0;
-        StreamKernel fn = pick_stream_kernel(num_bits, dtype, t.tile_p, p.m_block, p.ring_depth, 0);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-        void* kargs[] = {&sa};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs,
-                            p.lds_bytes, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        if (p.splitk > 1)
-            return splitk_reduce_dispatch(dtype, sa.partial, D, (size_t)M * N, p.splitk, st);
-        return FLUTE_OK;
-    }
-
     if (p.family == kFamilySplitK) {
         SplitKArgs b;
         memset(&b, 0, sizeof(b));
-        b.A = A; b.Q = reinterpret_cast<const uint32_t*>(Q); b.D = D; b.S = S;
-        b.QM2 = reinterpret_cast<const uint32_t*>(QM2);
-        b.state = reinterpret_cast<uint32_t*>(workspace);
-        b.partial = workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes) : nullptr;
+        b.A = A; b.Q = q32; b.D = D; b.S = S; b.QM2 = qm2;
+        b.state = state;
+        b.partial = partial;
         b.M = M; b.N = N; b.K = K; b.G = K / group_size; b.lg = ilog2(group_size);
         b.tiles_m = ceil_div(M, p.m_tiles * 16);
         b.splitk = p.splitk; b.k_per_split = p.k_per_split;
@@ -1511,24 +1532,14 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
             b.pair_lg = ilog2(b.tiles_m / E);
             b.pair_c8 = ((b.tiles_m / E) * (N / tile_cols)) & ~7;
         }
-        SplitKKernel fn = splitk_kernel(num_bits, dtype, t.tile_p, p.m_tiles, p.kw);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
         void* kargs[] = {&b};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        return FLUTE_OK;
+        return launch(splitk_kernel(num_bits, dtype, tp, p.m_tiles, p.kw), p, kargs, st);
     }
-
     if (p.family == kFamilyBlock) {
         BlockArgs b;
         memset(&b, 0, sizeof(b));
-        b.A = A; b.Q = reinterpret_cast<const uint32_t*>(Q); b.D = D; b.S = S;
-        b.QM2 = reinterpret_cast<const uint32_t*>(QM2);
-        b.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes);
+        b.A = A; b.Q = q32; b.D = D; b.S = S; b.QM2 = qm2;
+        b.partial = partial;
         b.M = M; b.N = N; b.K = K; b.G = K / group_size; b.lg = ilog2(group_size);
         const int bm = block_rows(p.m_block);
         b.tiles_m = ceil_div(M, bm); b.tiles_n = N / 256;
@@ -1536,25 +1547,14 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         // XCD x (block id % 8) owns a contiguous range of row blocks (their activations then stay in its L2
         // while the weights stream through), else of column blocks
         b.order = (b.tiles_m % 8 == 0) ? 1 : ((b.tiles_n % 8 == 0) ? 2 : 0);
-        b.state = (p.splitk > 1 && p.splitk_mode == 1) ? reinterpret_cast<uint32_t*>(workspace) : nullptr;
-        BlockKernel fn = (num_bits == 2) ? block_kernel_b2(dtype, t.tile_p, p.m_block)
-                         : (num_bits == 3) ? block_kernel_b3(dtype, t.tile_p, p.m_block) : block_kernel_b4(dtype, t.tile_p, p.m_block);
-        if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-        if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
+        b.state = (p.splitk > 1 && p.splitk_mode == 1) ? state : nullptr;
         void* kargs[] = {&b};
-        if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            return FLUTE_ERR_LAUNCH;
-        }
-        if (p.splitk > 1 && p.splitk_mode == 0) return splitk_reduce_dispatch(dtype, b.partial, D, (size_t)M * N, p.splitk, st);
-        return FLUTE_OK;
+        return then_reduce(launch(block_kernel(num_bits, dtype, tp, p.m_block), p, kargs, st));
     }
 
-    QGemmArgs a;
-    a.A = A; a.Q = reinterpret_cast<const uint32_t*>(Q); a.D = D; a.S = S;
-    a.QM2 = reinterpret_cast<const uint32_t*>(QM2);
-    a.partial = workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kXwgFlagBytes) : nullptr;
+    QGemmArgs a;                                         // per-wave MFMA kernel
+    a.A = A; a.Q = q32; a.D = D; a.S = S; a.QM2 = qm2;
+    a.partial = partial;
     a.M = M; a.N = N; a.K = K; a.G = K / group_size;
     a.lg = ilog2(group_size);
     a.units = N / ((num_bits == 3) ? 16 : 16 / num_bits);
@@ -1562,7 +1562,7 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
     a.lut_shift = 0;
     a.lds_budget = kMaxLds;
     a.lkw = ilog2(p.kw);
-    a.state = (p.splitk > 1 && p.splitk_mode == 1) ? reinterpret_cast<uint32_t*>(workspace) : nullptr;
+    a.state = (p.splitk > 1 && p.splitk_mode == 1) ? state : nullptr;
     a.had_log = had_log;
     a.had_scale = had_scale;
     for (int i = 0; i < 10; ++i) a.geo[i] = 0;
@@ -1574,20 +1574,8 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         // as the activations (which every XCD then reads in full) are the smaller operand
         a.geo[5] = (((int)p.grid / p.splitk / a.geo[4]) % 8 == 0 && (long)M * 32 <= (long)num_bits * N) ? 1 : 0;
     }
-
-    QGemmKernel fn = pick_kernel(p.family, num_bits, dtype, t.tile_p, p.m_block, p.m_tiles, p.slabs_per_wave);
-    if (!fn) return FLUTE_ERR_TEMPLATE_ID;
-    if (ensure_lds(reinterpret_cast<const void*>(fn), p.lds_bytes)) return FLUTE_ERR_LAUNCH;
-
     void* kargs[] = {&a};
-    if (hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), kargs,
-                        p.lds_bytes, st) != hipSuccess) {
-        (void)hipGetLastError();
-        return FLUTE_ERR_LAUNCH;
-    }
-    if (p.splitk > 1 && p.splitk_mode == 0)
-        return splitk_reduce_dispatch(dtype, a.partial, D, (size_t)M * N, p.splitk, st);
-    return FLUTE_OK;
+    return then_reduce(launch(tile_kernel(num_bits, dtype, tp, p.m_block, p.m_tiles, p.slabs_per_wave), p, kargs, st));
 }
 
 int flute_hadamard(int dtype, const void* in, void* out, size_t numel, uint32_t had_size,
@@ -1598,14 +1586,11 @@ int flute_hadamard(int dtype, const void* in, void* out, size_t numel, uint32_t 
 
 int flute_unpack(int num_bits, int template_id, int N, int K, const void* Q, void* W,
                  void* stream) {
-    flute_template_info t;
-    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return FLUTE_ERR_NUM_BITS;
-    if (!decode_template(num_bits, template_id, &t)) return FLUTE_ERR_TEMPLATE_ID;
-    if (num_bits == 3 && t.tile_p != 32) return FLUTE_ERR_TEMPLATE_ID;
-    const int J = (num_bits == 3) ? 16 : 16 / num_bits;
-    if (N < 1 || K < 2 || N % (J * t.tile_p) || K % 2) return FLUTE_ERR_SHAPE;
+    Layer l;
+    const int rc = check_layer(num_bits, 0, template_id, N, K, 2, &l);
+    if (rc) return rc;
     if (!Q || !W) return FLUTE_ERR_NULL;
-    return unpack_dispatch(num_bits, t.tile_p, N, K, Q, W, reinterpret_cast<hipStream_t>(stream));
+    return unpack_dispatch(num_bits, l.t.tile_p, N, K, Q, W, reinterpret_cast<hipStream_t>(stream));
 }
 
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
