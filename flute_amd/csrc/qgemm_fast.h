@@ -6,7 +6,7 @@
 // life, and a launch of back-to-back dependent kernels lasts boundary + dispatch ramp (1.9 us for an empty kernel) +
 // the life of the workgroups that start last (profiles/r05/fast_lab_run*_stamps.jsonl).  This kernel is the same
 // algorithm - table image in LDS (256-B entry stride, 32 copies), wave-private scale image, every request in the
-// prologue, pipelined_pieces() as the decode loop - with the instruction count cut to ~760:
+// prologue, a software-pipelined decode loop - with the instruction count cut to ~760:
 //   * K = 512 * D * KW is a COMPILE-TIME constant (D pieces per wave, KW waves share a unit row), so are the waves
 //     per workgroup W, the rows MB and TileP: no geometry word, no ragged rows, no dead units, no bounds selects - every
 //     wave of the grid holds exactly D whole pieces and every unit is live (host contract below); 145 instructions
@@ -20,7 +20,9 @@
 //   * transpose-reduce epilogue: the 4 x MB partial sums of a wave are reduced TOGETHER - lanes of a quad keep one
 //     column each, the DPP rows keep one activation row each (v_permlane16/32_swap), 22 instructions at MB = 1
 //     instead of 4 x 11 - and the outputs of a unit leave in ONE store instruction;
-//   * K split across waves (KW > 1): partial sums and arrival tick leave back to back (two LDS round trips, not three).
+//   * K split across waves (KW > 1): partial sums and arrival tick leave back to back (two LDS round trips, not three);
+//   * round 7: the decode loop is the kernel's own (fast_pieces): activations and scales of all D pieces in registers first,
+//     then a ring of three groups of 8 lookups in flight (round 5 kept one behind the group being consumed).
 // Measured and dropped: helper waves that take the set-up loads off the compute waves (a CU's memory pipeline is
 // first-in first-out ACROSS its waves: the helpers' small loads queued behind the weight requests the compute waves
 // had already issued - table word after 3000 cycles instead of 650, profiles/r05/fast_lab_run2_stamps.jsonl).
@@ -42,8 +44,120 @@ __host__ __device__ constexpr size_t fast_lds_bytes(int W, int KW, int D, int lg
     return (size_t)65536 + (size_t)mb * 512 * D * KW * 2 + (size_t)W * 4 * D * (512 >> lg) * 2 + 128 + (size_t)W * 64;
 }
 
-// OPT bits (lab): 1 = default-policy weight loads (nt otherwise), 2 = lookups ablated (timing floor), 32 = hipcc's own
-// order of table addresses / lookups and zeroed partial sums (pipelined_pieces BA = 0)
+// The decode loop's lookup ring: R groups of GS lookups in flight.  A piece is 16 lookups per lane (k-pair words 0 .. 3 x columns
+// 0 .. 3); the loop numbers the wave's 16 * D lookups L = 16 * piece + 4 * word + column and cuts them into groups of GS
+// consecutive lookups (the last one may be short; a group may straddle two pieces).  OPT bits 64 .. 448 (lab) pick another
+// ring; 0 is the shipped one.
+struct FastRing { int R, GS; };
+__host__ __device__ constexpr FastRing fast_ring_of(int opt) {
+    constexpr FastRing rings[] = {{3, 8}, {2, 8}, {3, 8}, {4, 4}, {5, 4}, {3, 6}, {4, 5}};
+    return rings[(opt >> 6) & 7];
+}
+
+// The lean kernel's decode loop.  Every activation word and every scale pair of the wave's D pieces is read into registers
+// first (MB x D ds_read_b128 and D ds_read_b64, issued before any lookup: the first group's wait releases them), so the
+// LDS queue of the loop holds lookups only.  Then group g + R - 1 is issued before group g is waited for and multiplied:
+// R - 1 groups stay in flight behind the one being consumed, which hides one LDS round trip under a single wave per SIMD
+// (round 5's loop kept ONE group in flight: ~174 cycles per group of 8, one round trip).  LDS returns in
+// order, so "at most YOUNGER operations outstanding" releases group g; lgkmcnt encodes at most 15, and the rings allowed
+// here keep at most 16 younger lookups: the wait may release at most one read more than it needs.
+// Arithmetic and its order are pipelined_pieces' (qgemm_oneshot.h, BA = 1): per lane, column and row, the piece's 8-k partial
+// sum starts with v_dot2 against a zero constant for k-pair word 0 and accumulates words 1, 2, 3 in order; then the fp32 group
+// scale: acc = fma(partial, scale, acc), pieces in order.
+template <typename T, int MB, int D, int R, int GS>
+__device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane, uint32_t x_row, uint32_t s_lane, uint32_t s_piece,
+                                            uint32_t lane_off, float (&acc)[4][MB]) {
+    using NT = Num<T>;
+    constexpr int NL = 16 * D;                                  // lookups of the wave
+    constexpr int NGR = (NL + GS - 1) / GS;                     // groups
+    static_assert(R >= 2 && GS >= 1 && GS <= 16, "lookup ring");
+    // lookups issued behind group g when it is waited for
+    auto younger = [](int g) constexpr {
+        const int last = (g + R - 1 < NGR - 1) ? g + R - 1 : NGR - 1;
+        const int end = ((last + 1) * GS < NL) ? (last + 1) * GS : NL;
+        return end - (g + 1) * GS > 0 ? end - (g + 1) * GS : 0;
+    };
+    static_assert((R - 1) * GS <= 16, "at most one read of over-wait: lgkmcnt encodes 0 .. 15");
+    ring16_t xq[D][MB];                                         // activation words of every piece and row
+    u32x2_t sq[D];                                              // the 4 scales of every piece
+    uint32_t lv[NL];                                            // lookup results
+    float al[4][MB];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int m = 0; m < MB; ++m) xq[i][m] = lds_hidden128(x_lane + ((uint32_t)i << 10) + (uint32_t)m * x_row);
+#pragma unroll
+    for (int i = 0; i < D; ++i) sq[i] = lds_hidden64(s_lane + (uint32_t)i * s_piece);
+
+    auto issue_group = [&](auto g_tag) {
+        constexpr int g = decltype(g_tag)::value;
+        constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
+        // the weights of every piece the group starts (each piece released by its own counted vmcnt)
+        static_for<L1 - L0>([&](auto n_tag) {
+            constexpr int L = L0 + decltype(n_tag)::value;
+            if constexpr (L % 16 == 0) vm_wait_regs<D - 1 - L / 16>(q[L / 16][0]);
+        });
+        // every table address of the group before its first lookup (hipcc otherwise alternates v_perm / ds_read through one
+        // register); the empty asm statements are ordered before the lookups, each holds one address
+        uint32_t ad[GS];
+#pragma unroll
+        for (int n = 0; n < L1 - L0; ++n) {
+            const int L = L0 + n;
+            ad[n] = __builtin_amdgcn_perm(q[L / 16][0][(L % 16) / 4], lane_off, 0x0c0c0400u | ((4u + (uint32_t)(L % 4)) << 8));
+        }
+#pragma unroll
+        for (int n = 0; n < L1 - L0; ++n) { uint32_t& r = ad[n]; asm volatile("" : "+v"(r)); }
+#pragma unroll
+        for (int n = 0; n < L1 - L0; ++n) lv[L0 + n] = lds_lookup32(ad[n]);
+    };
+    // group g: released by its counted wait, its registers tied to the wait (ordered behind it) before their first use
+    auto wait_group = [&](auto g_tag) {
+        constexpr int g = decltype(g_tag)::value;
+        constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
+        constexpr int YOUNGER = younger(g);
+        static_assert(YOUNGER <= 16, "over-wait");
+        // (YOUNGER = 16: lgkmcnt(15) also waits for the oldest lookup of group g + 1)
+        asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(YOUNGER < 15 ? YOUNGER : 15) : "memory");
+#pragma unroll
+        for (int n = L0; n < L1; ++n) { uint32_t& r = lv[n]; asm volatile("" : "+v"(r) : : "memory"); }
+        if constexpr (g == 0) {                                 // the activation / scale reads are older than every lookup
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+#pragma unroll
+                for (int m = 0; m < MB; ++m) { ring16_t& r = xq[i][m]; asm volatile("" : "+v"(r) : : "memory"); }
+                u32x2_t& s2 = sq[i];
+                asm volatile("" : "+v"(s2) : : "memory");
+            }
+        }
+    };
+
+    static_for<(R - 1 < NGR ? R - 1 : NGR)>([&](auto g_tag) { issue_group(g_tag); });
+    static_for<NGR>([&](auto g_tag) {
+        constexpr int g = decltype(g_tag)::value;
+        constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
+        if constexpr (g + R - 1 < NGR) issue_group(std::integral_constant<int, g + R - 1>{});
+        wait_group(g_tag);
+#pragma unroll
+        for (int L = L0; L < L1; ++L) {
+            const int I = L / 16, ww = (L % 16) / 4, j = L % 4;
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                // (a piece's first products start its partial sums - no register zeroed first)
+                if (ww == 0) al[j][m] = NT::dot2z(lv[L], xq[I][m][ww]);
+                else al[j][m] = NT::dot2(lv[L], xq[I][m][ww], al[j][m]);
+            }
+            if (ww == 3) {                                      // column j of piece I is summed: its group scale
+                const uint32_t w = sq[I][j / 2];
+                const float sf = scale_to_float<T>((j & 1) ? (w >> 16) : (w & 0xffffu));
+#pragma unroll
+                for (int m = 0; m < MB; ++m) acc[j][m] = __builtin_fmaf(al[j][m], sf, acc[j][m]);
+            }
+        }
+    });
+}
+
+// OPT bits (lab): 1 = default-policy weight loads (nt otherwise), 2 = lookups ablated (timing floor), 64 .. 448 = another
+// lookup ring of the decode loop (fast_ring_of)
 // (The fused Hadamard pre-rotation of flute.qgemm_hadamard stays with the round-4 one-shot kernel: this kernel's four waves rotate
 // a row of K = 3584 / 4096 in two rounds - measured with the rotation as a template flag, 4.69 / 4.62 us against 4.81 / 4.61 for one
 // row on 4096 x 3584 / 4096 x 4096 and 6.28 against 5.99 for two: profiles/r05/call20_hadamard.log - and the flag was removed.)
@@ -194,7 +308,8 @@ __global__ __launch_bounds__(W * 64) void qgemv_fast_kernel(
             for (int ww = 0; ww < 4; ++ww) acc[ww][0] += __builtin_bit_cast(float, q[i][0][ww]);
         });
     } else {
-        pipelined_pieces<T, 4, MB, D, 0, (OPT & 32) ? 0 : 1>(q, x_lane, 10u, (uint32_t)K * 2u, s_lane, (uint32_t)(gpp * 4) * 2u, lane_off, acc);
+        constexpr FastRing ring = fast_ring_of(OPT);
+        fast_pieces<T, MB, D, ring.R, ring.GS>(q, x_lane, (uint32_t)K * 2u, s_lane, (uint32_t)(gpp * 4) * 2u, lane_off, acc);
     }
     FLUTE_FSTAMP(9);
 

@@ -19,7 +19,14 @@ Round 5 added a second rule, on every instruction of the unit: a VGPR written by
 instruction (or by a v_dot* as its A / B operand) only three wait states later (gfx90a+).  hipcc's hazard recognizer keeps that for
 the instructions it schedules but does not look into asm statements: a per-word bf16 scale multiply written as v_dot2_f32_bf16 asm
 statements with the conversion right behind them computed wrong values (tests/test_qgemm_gpu.py caught it; common.h mul_scale4 is the
-form that keeps the distance by construction)."""
+form that keeps the distance by construction).
+
+The lean decode kernel (qgemm_fast.h, qgemv_fast_kernel) keeps up to three groups of hidden table lookups in flight and releases
+each group with a counted lgkmcnt, so for it the replay also reports (third rule) a scalar-memory load issued while hidden LDS reads
+are outstanding: scalar loads share lgkmcnt and return out of order, and the count would no longer prove that a lookup landed.
+The first rule already covers its lookups (any read of a ds_read destination before the lgkmcnt that covers it is flagged).  The
+summary lists, per instantiation of that kernel, the decode loop's VALU / DS / s_waitcnt instruction counts (from its first
+lookup to its last group-scale fma: v_fma_mix_f32 for fp16 scales, v_fma(c)_f32 for bf16)."""
 import os
 import re
 import subprocess
@@ -261,6 +268,9 @@ def audit(path):
                     findings.append((kernel, ln, text, sorted(src & busy)))
                 ds_set.append((ln, dst))
                 continue
+        if not in_asm and kernel and "qgemv_fast_kernel" in kernel and re.match(r"(s_load_|s_buffer_load_)", text) \
+                and any(r for _, r in ds_set):
+            findings.append((kernel, ln, text + "   [scalar load while hidden LDS reads are counted]", []))
         if not in_asm and re.match(r"(ds_|s_load_|s_buffer_load_)", text):
             ds_set.append((ln, set()))                         # compiler-managed LGKM operation: a slot in the queue only
         busy = set()
@@ -273,6 +283,50 @@ def audit(path):
         if hit and not _dead_readfirstlane(all_lines, ln - 1, text):
             findings.append((kernel, ln, text, sorted(hit)))
     return findings
+
+
+def fast_loop_stats(path):
+    """{kernel: (VALU, DS, s_waitcnt)} of the decode loop of every qgemv_fast_kernel instantiation in one assembly file: the
+    instructions from the first hidden ds_read_b32 (a table lookup) to the last fp32 fma (a group scale), in layout order."""
+    out = {}
+    kernel, body, in_asm = None, [], False
+
+    def close():
+        if kernel and "qgemv_fast_kernel" in kernel:
+            first = next((i for i, (t, a) in enumerate(body) if a and t.startswith("ds_read_b32")), None)
+            last = max((i for i, (t, _) in enumerate(body) if re.match(r"v_fma(c|_mix)?_f32", t)), default=None)
+            if first is not None and last is not None and last > first:
+                lp = [t for t, _ in body[first:last + 1]]
+                out[kernel] = (sum(t.startswith("v_") for t in lp), sum(t.startswith("ds_") for t in lp),
+                               sum(t.startswith("s_waitcnt") for t in lp))
+    for raw in open(path):
+        st = raw.strip()
+        if st.startswith(";;#ASMSTART"):
+            in_asm = True
+            continue
+        if st.startswith(";;#ASMEND"):
+            in_asm = False
+            continue
+        m = re.match(r"^(_Z\w+):", raw)
+        if m:
+            close()
+            kernel, body = m.group(1), []
+            continue
+        if re.match(r"^\.Lfunc_end", raw):
+            close()
+            kernel, body = None, []
+            continue
+        text = raw.split(";")[0].strip()
+        if kernel and text and not text.startswith(".") and not text.endswith(":"):
+            body.append((text, in_asm))
+    close()
+    return out
+
+
+def _short_fast_name(k):
+    """qgemv_fast_kernel<T, TileP, W, KW, D, MB, OPT> of a mangled name."""
+    m = re.search(r"qgemv_fast_kernelINS_\d*(F16|BF16)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", k)
+    return "<%s, %s, %s, %s, %s, %s, %s>" % m.groups() if m else k
 
 
 def compile_unit(src, outdir):
@@ -308,6 +362,8 @@ def main(argv):
         for (k, ln, text, hit) in fs[:40]:
             print(f"{os.path.basename(f)}:{ln}: {k}: `{text}` touches in-flight v{hit}")
         print(f"{os.path.basename(f)}: {len(fs)} finding(s)")
+        for k, (nv, nd, nw) in fast_loop_stats(f).items():
+            print(f"    decode loop of qgemv_fast_kernel{_short_fast_name(k)}: {nv} VALU, {nd} DS, {nw} s_waitcnt")
     return 1 if total else 0
 
 

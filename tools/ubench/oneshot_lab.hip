@@ -250,7 +250,12 @@ int main(int argc, char** argv) {
 #define FV_(name, W_, KW_, D_, H_, OPT_) FV{name, (FastKernel)qgemv_fast_kernel<F16, 32, W_, KW_, D_, 1, OPT_>, W_, KW_, D_, 0, false}
         const FV fvs[] = {
             FV_("fast_w4_kw1_d8", 4, 1, 8, 0, 0), FV_("fast_w8_kw2_d4", 8, 2, 4, 0, 0), FV_("fast_w4_kw2_d4", 4, 2, 4, 0, 0),
-            FV_("fast_w4_kw1_d8_hipcc_order", 4, 1, 8, 0, 32), FV_("fast_w4_kw1_d8_nolookup", 4, 1, 8, 0, 2),
+            FV_("fast_w4_kw1_d8_nolookup", 4, 1, 8, 0, 2),
+            // the decode loop's lookup ring (qgemm_fast.h fast_ring_of): R groups x GS lookups in flight
+            FV_("fast_w4_kw1_d8_ring2x8", 4, 1, 8, 0, 64), FV_("fast_w4_kw1_d8_ring3x8", 4, 1, 8, 0, 128),
+            FV_("fast_w4_kw1_d8_ring4x4", 4, 1, 8, 0, 192), FV_("fast_w4_kw1_d8_ring5x4", 4, 1, 8, 0, 256),
+            FV_("fast_w4_kw1_d8_ring3x6", 4, 1, 8, 0, 320), FV_("fast_w4_kw1_d8_ring4x5", 4, 1, 8, 0, 384),
+            FV_("fast_w4_kw1_d7_ring2x8", 4, 1, 7, 0, 64), FV_("fast_w4_kw1_d7", 4, 1, 7, 0, 0),
             FV_("fast_w8_kw2_d8", 8, 2, 8, 0, 0), FV_("fast_w16_kw4_d4", 16, 4, 4, 0, 0),
             FV_("fast_w4_kw1_d4", 4, 1, 4, 0, 0), FV_("fast_w8_kw2_d2", 8, 2, 2, 0, 0),
         };
