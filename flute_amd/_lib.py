@@ -57,6 +57,7 @@ SYMBOLS = {
     "flute_qgemm_hadamard_fused": (c_int, [c_int] * 9 + [c_size_t]),
     "flute_hadamard": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]),
     "flute_unpack": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "flute_dequantize": (c_int, [c_int] * 8 + [c_void_p] * 4 + [c_int, c_void_p]),
     "flute_debug_stream_read": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "flute_debug_timestamp": (c_int, [c_void_p, c_void_p]),
 }
@@ -77,7 +78,7 @@ def get() -> ctypes.CDLL:
             fn = getattr(lib, name)   # AttributeError if the ABI is incomplete
             fn.restype = res
             fn.argtypes = args
-        if lib.flute_abi_version() != 8:
+        if lib.flute_abi_version() != 9:
             raise ImportError("flute_amd: ABI version mismatch, rebuild libflute_amd.so")
         _lib = lib
     return _lib

@@ -1593,6 +1593,20 @@ int flute_unpack(int num_bits, int template_id, int N, int K, const void* Q, voi
     return unpack_dispatch(num_bits, l.t.tile_p, N, K, Q, W, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int P, int k_begin, int k_count,
+                     const void* Q, const void* S, const void* QM2, void* W, int template_id, void* stream) {
+    if (!Q || !S || !QM2 || !W) return FLUTE_ERR_NULL;
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
+    if (k_begin < 0 || k_count < 0 || k_begin % 64 || k_count % 64 || k_count > K - k_begin) return FLUTE_ERR_SHAPE;
+    if (k_count == 0) return FLUTE_OK;
+    return dequant_dispatch(dtype, num_bits, l.t.tile_p, N, K, l.lg, k_begin, k_count, Q, S, QM2, W,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -60,6 +60,9 @@ int hadamard_dispatch(int dtype, const void* in, void* out, size_t numel, uint32
                       hipStream_t stream);
 int unpack_dispatch(int num_bits, int tile_p, int N, int K, const void* Q, void* W,
                     hipStream_t stream);
+// dense dequantized weight [N, k_count] (dequant.hip); lg = log2(group size)
+int dequant_dispatch(int dtype, int num_bits, int tile_p, int N, int K, int lg, int k_begin, int k_count,
+                     const void* Q, const void* S, const void* QM2, void* W, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

@@ -1,10 +1,14 @@
-"""torch operator surface: `flute::qgemm_raw_simple[_hadamard]`.
+"""torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
 PyTorch-ROCm, as qgemm.cpp:257-260 does for CUDA) by a compiled C++ binding and
 forwards to the C ABI.  The fake (meta) implementations restate flute/ops.py:4-83
 so that torch.compile / opcheck see the same validation.  No CPU kernel is registered.
+
+The binding also registers Autograd kernels for both `flute::` ops (input gradient
+only: dX = dY @ dequantize(...), computed in bounded K chunks) and this project's
+own `flute_amd::dequantize` (the dense [N, K] weight, a native HIP kernel).
 """
 import os
 
@@ -88,3 +92,26 @@ def _qgemm_raw_simple_hadamard_abstract(input, weight, scales, table, table2, wo
                                         num_sms):
     return _qgemm_raw_simple_abstract(input, weight, scales, table, table2, workspace,
                                       num_bits, group_size, template_id, num_sms)
+
+
+def _validate_dequantize(weight, scales, table2, num_bits, group_size):
+    if not all([weight.ndim == 2, scales.ndim == 2, table2.ndim == 3]):
+        raise ValueError
+    if scales.dtype not in _DTYPE_ID:
+        raise TypeError
+    if weight.dtype != torch.int16 or table2.dtype != torch.float32:
+        raise TypeError
+    if not all([
+        weight.shape[1] == scales.shape[1] * group_size,
+        weight.shape[0] == int(num_bits * (scales.shape[0] / 16)),
+        table2.shape[0] == 2 ** num_bits,
+        table2.shape[1] == 2 ** num_bits,
+        table2.shape[2] == 1,
+    ]):
+        raise ValueError
+
+
+@torch.library.register_fake("flute_amd::dequantize")
+def _dequantize_abstract(weight, scales, table2, num_bits, group_size, template_id):
+    _validate_dequantize(weight, scales, table2, num_bits, group_size)
+    return torch.empty((scales.shape[0], weight.shape[1]), dtype=scales.dtype, device=scales.device)

@@ -23,12 +23,13 @@
 extern "C" {
 #endif
 
-/* 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
+/* 9: flute_dequantize
+ * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
  *    of family 7 = column groups per workgroup (1 .. 3), and the overrides of the same names select them; family 6 refuses waves = 8
  * 6 (round 5): flute_plan.one_shot / flute_overrides.one_shot value 4 (lean decode kernel, qgemm_fast.h), flute_debug_timestamp */
-#define FLUTE_AMD_ABI_VERSION 8
+#define FLUTE_AMD_ABI_VERSION 9
 
 enum flute_dtype { FLUTE_F16 = 0, FLUTE_BF16 = 1 };
 
@@ -206,6 +207,15 @@ int flute_hadamard(int dtype, const void* in, void* out, size_t numel, uint32_t 
  * (flute/utils.py:347-407). */
 int flute_unpack(int num_bits, int template_id, int N, int K, const void* Q, void* W,
                  void* stream);
+
+/* The dense dequantized weight W[N, k_count] (row-major T, the nn.Linear weight layout) of columns
+ * [k_begin, k_begin + k_count) of K: W[n, k - k_begin] = round_T(QM2-pair-lookup(Q)[k, n] * S[n, k / group_size]),
+ * the lookup and the one rounding of the qgemm kernels, so W equals qgemm(identity) element by element.  QM is not
+ * read (HIGGS pair codebooks dequantize as they multiply).  k_begin and k_count are multiples of 64 and group_size
+ * divides K; k_count == 0 is a no-op.  Same layer checks as flute_qgemm; FLUTE_ERR_SHAPE also for a bad k range or
+ * P != num_bits * N / 16.  Null pointers are refused (FLUTE_ERR_NULL) before anything else. */
+int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int P, int k_begin, int k_count,
+                     const void* Q, const void* S, const void* QM2, void* W, int template_id, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */
