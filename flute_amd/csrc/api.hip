@@ -676,6 +676,11 @@ bool auto_digit_sk(int bits, int template_id) { return bits != 4 || (template_id
 // ... and, for the 4-bit lean and MFMA decode kernels, SMs_Multiple 1 besides
 bool auto_lean_id(const Call& c) { return c.bits == 4 && (c.template_id % 4) == 0 && c.t.sms_multiple == 1; }
 
+// Every decode kernel reads the scales through one descriptor with 32-bit byte offsets (qgemm_stream.h:271,302, qgemm_oneshot.h:400,411,
+// qgemm_persist.h:96,114, qgemm_fast.h:225): a layer whose scales reach that range takes the per-wave kernel (64-bit pointers), forced
+// family 0 as well.
+bool decode_fits(const Call& c) { return (size_t)c.N * (size_t)(c.K >> c.lg) * 2 < (size_t)0xfffffff0u; }
+
 // Streaming decode kernel: M <= 2; its four-row variant (2- / 4-bit) only on request (override family 0, which
 // flute_qgemm_hadamard sets for small layers so that the rotation stays fused): measured at M = 3, 4 the MFMA
 // kernel is as fast on 4096^2 (7.6 vs 7.75 us) and 15-25 % faster on every larger layer (8192x28672: 38.6 vs 48.9).
@@ -687,6 +692,7 @@ bool auto_lean_id(const Call& c) { return c.bits == 4 && (c.template_id % 4) == 
 // (only ids whose last digit leaves the choice to the planner: a 4-bit id with QuantMapMode digit 3 keeps the skinny MFMA kernel it was
 // tuned on - "a tuned id keeps the kernel it was timed on", tests/test_abi.py)
 bool decode_auto(const Call& c) {
+    if (!decode_fits(c)) return false;
     if (c.M <= 2) return true;
     if (c.M > 4) return false;
     const size_t weights = (size_t)c.N * c.K;
@@ -823,7 +829,8 @@ BlockChoice choose_block(const Call& c) {
     const int blk_units = 256 / c.J;                  // units of a 256-column block (4-bit: 64, 2-bit: 32, 3-bit: 16)
     const bool b3_ok = bits != 3 || (size_t)3 * (N >> 4) * K * 2 < (size_t)0xfffffff0u;   // one descriptor over Q
     const bool x32_ok = (size_t)(M + 256) * K * 2 < (size_t)0xfffffff0u;       // activation byte offsets are 32-bit voffsets
-    if (!b3_ok || !x32_ok || (K >> lg) % 8 || units % blk_units) return b;
+    const bool s32_ok = (size_t)N * (K >> lg) * 2 < (size_t)0xfffffff0u;       // ... and so are the scale offsets (one descriptor over S)
+    if (!b3_ok || !x32_ok || !s32_ok || (K >> lg) % 8 || units % blk_units) return b;
     const long tiles256 = (long)ceil_div(M, 256) * (units / blk_units), tiles128 = (long)ceil_div(M, 128) * (units / blk_units);
     if (ov.family == kFamilyBlock) {
         b.cfg = (ov.m_tiles == 4) ? 5 : 4;               // 128- / 256-row blocks of qgemm_block2.h
@@ -1154,7 +1161,7 @@ int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int 
     const int fam = ov.family;
 
     // forced: the family's planner; families 6 and 8 refuse a call they do not fit, the others fall back to the per-wave
-    // kernel (family 0: above M = 4)
+    // kernel (family 0: above M = 4, and where the scales outgrow the decode kernels' descriptor)
     if (fam == kFamilyPersistM)
         return plan_persistm(bits, c.lg, M, N, K, c.num_sms, ov.slabs, ov.m_tiles, ov.one_shot, &out->p, &out->oa);
     if (fam == kFamilySplitK) {
@@ -1169,7 +1176,7 @@ int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int 
         Planned q{};
         if (plan_skinny(bits, c.lg, M, N, K, ov, workspace_bytes, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
-    if (fam == 0 && M <= 4) return plan_decode(c, out);
+    if (fam == 0 && M <= 4 && decode_fits(c)) return plan_decode(c, out);
     if (fam == kFamilyBlock) {
         const BlockChoice b = choose_block(c);
         if (b.cfg >= 0) return plan_block(c, b, out);
