@@ -20,6 +20,8 @@ _lib.get()   # fail at import time, not at first call, when the HIP library is m
 qgemm = cast(Callable[..., torch.Tensor], torch.ops.flute.qgemm_raw_simple.default)
 qgemm_hadamard = cast(Callable[..., torch.Tensor], torch.ops.flute.qgemm_raw_simple_hadamard.default)
 hadamard_transform = ops.hadamard_transform
+# the gradient of a packed layer's scales [N, K / g] (a plain function over the C ABI, not a torch op)
+qgemm_scale_grad = ops.qgemm_scale_grad
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

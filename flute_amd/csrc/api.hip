@@ -1614,6 +1614,22 @@ int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int 
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
+                           const void* dY, const void* X, const void* Q, const void* QM2, void* dS,
+                           void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
+    if (!dY || !X || !Q || !QM2 || !dS) return FLUTE_ERR_NULL;
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
+    if (M < 1) return FLUTE_ERR_SHAPE;
+    return scale_grad_dispatch(dtype, num_bits, l.t.tile_p, l.lg, M, N, K, dY, X, Q, QM2, dS,
+                               scratch_bytes ? scratch : nullptr, scratch ? scratch_bytes : 0, num_sms,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -63,6 +63,10 @@ int unpack_dispatch(int num_bits, int tile_p, int N, int K, const void* Q, void*
 // dense dequantized weight [N, k_count] (dequant.hip); lg = log2(group size)
 int dequant_dispatch(int dtype, int num_bits, int tile_p, int N, int K, int lg, int k_begin, int k_count,
                      const void* Q, const void* S, const void* QM2, void* W, hipStream_t stream);
+// scale gradient dS [N, K / g] (scale_grad.hip): M split over workgroups through the scratch when the blocks do not fill the chip
+int scale_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
+                        const void* X, const void* Q, const void* QM2, void* dS, void* scratch, size_t scratch_bytes,
+                        int num_sms, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

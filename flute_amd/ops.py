@@ -1,4 +1,5 @@
-"""torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`.
+"""torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
+plus two plain functions over the C ABI: `hadamard_transform` and `qgemm_scale_grad`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -115,3 +116,68 @@ def _validate_dequantize(weight, scales, table2, num_bits, group_size):
 def _dequantize_abstract(weight, scales, table2, num_bits, group_size, template_id):
     _validate_dequantize(weight, scales, table2, num_bits, group_size)
     return torch.empty((scales.shape[0], weight.shape[1]), dtype=scales.dtype, device=scales.device)
+
+
+def _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_size):
+    if not all([input.ndim >= 2, grad_output.ndim == input.ndim, weight.ndim == 2, table2.ndim == 3]):
+        raise ValueError
+    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype:
+        raise TypeError
+    if weight.dtype != torch.int16 or table2.dtype != torch.float32:
+        raise TypeError
+    K, N = input.shape[-1], grad_output.shape[-1]
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    if not all([
+        grad_output.shape[:-1] == input.shape[:-1],
+        weight.shape[1] == K,
+        K > 0 and K % max(64, group_size) == 0,
+        N > 0 and N % 16 == 0 and weight.shape[0] == num_bits * (N // 16),
+        table2.shape[0] == 2 ** num_bits,
+        table2.shape[1] == 2 ** num_bits,
+        table2.shape[2] == 1,
+    ]):
+        raise ValueError
+
+
+def _scale_grad_scratch_bytes(N, K, group_size, num_sms):
+    # the most the launch can split M into (scale_grad.hip: 256 x 128 blocks of (k, n), two workgroups per CU)
+    blocks = (N // 128) * -(-K // 256)
+    target = 2 * (num_sms if num_sms >= 1 else 256)
+    if blocks == 0 or blocks >= target:
+        return 0
+    return -(-target // blocks) * N * (K // group_size) * 4
+
+
+def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: torch.Tensor,
+                     table2: torch.Tensor, num_bits: int, group_size: int, template_id: int,
+                     num_sms=None) -> torch.Tensor:
+    """Gradient of the scales of `Y = qgemm(input, weight, scales, ...)` for the upstream gradient `grad_output`:
+    dS[n, j] = round_T(sum_m sum_{k in group j} dY[m, n] * X[m, k] * L[k, n]), L the table2 pair lookup of the
+    packed codes (what the forward multiplies by the scale).  Leading dimensions are flattened; returns [N, K / g]
+    in input.dtype.  For a Hadamard layer pass the rotated input, `hadamard_transform(input, hadamard_size)`.
+    A native HIP kernel on the current stream (scale_grad.hip); the same arguments give the same bits."""
+    _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_size)
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in (grad_output, input, weight, table2)):
+        raise RuntimeError("flute_amd.qgemm_scale_grad: all tensors must live on the same GPU")
+    K, N = input.shape[-1], grad_output.shape[-1]
+    x = input.reshape(-1, K).contiguous()
+    dy = grad_output.reshape(-1, N).contiguous()
+    M = x.shape[0]
+    if M >= 2 ** 31:
+        raise ValueError
+    out = torch.empty((N, K // group_size), dtype=input.dtype, device=dev)
+    if M == 0:
+        return out.zero_()
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    scratch = torch.empty(_scale_grad_scratch_bytes(N, K, group_size, num_sms), dtype=torch.uint8, device=dev)
+    w = weight.contiguous()
+    t2 = table2.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_scale_grad(
+            _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
+            dy.data_ptr(), x.data_ptr(), w.data_ptr(), t2.data_ptr(), out.data_ptr(),
+            scratch.data_ptr() if scratch.numel() else None, scratch.numel(), num_sms, _stream_ptr(dev)))
+    return out

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* 9: flute_dequantize
+/* 9: flute_dequantize; flute_qgemm_scale_grad (additive: no existing entry point changed)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -216,6 +216,19 @@ int flute_unpack(int num_bits, int template_id, int N, int K, const void* Q, voi
  * P != num_bits * N / 16.  Null pointers are refused (FLUTE_ERR_NULL) before anything else. */
 int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int P, int k_begin, int k_count,
                      const void* Q, const void* S, const void* QM2, void* W, int template_id, void* stream);
+
+/* The gradient of a layer's scales, dS[n, j] = round_T(sum_{m < M} sum_{j*g <= k < (j+1)*g} dY[m, n] * X[m, k] * L[k, n]),
+ * L[k, n] the value the qgemm kernels multiply by the scale (the QM2 pair lookup of Q, as flute_dequantize; QM is not
+ * read).  dY [M, N] and X [M, K] row-major T, dS [N, K / group_size] T: fp32 products and sums, one rounding to T.  X is
+ * the activation the weight multiplies (for a Hadamard layer the rotated input).  M >= 1; group_size in {32, 64, 128,
+ * 256}; same layer checks as flute_dequantize, in its order (FLUTE_ERR_NULL for a null dY / X / Q / QM2 / dS first).
+ * `scratch` (scratch_bytes, may be null / 0) lets small layers split M across workgroups: fp32 partials
+ * [splits][N][K / group_size] summed in split order by a second launch.  The number of splits follows from M, N, K,
+ * num_sms (< 1: 256) and scratch_bytes alone, so equal arguments give equal bits; too little scratch only means fewer
+ * splits, never an error.  Do not pass the qgemm workspace (its leading state words must stay zero). */
+int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
+                           const void* dY, const void* X, const void* Q, const void* QM2, void* dS,
+                           void* scratch, size_t scratch_bytes, int num_sms, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */
