@@ -22,6 +22,10 @@ qgemm_hadamard = cast(Callable[..., torch.Tensor], torch.ops.flute.qgemm_raw_sim
 hadamard_transform = ops.hadamard_transform
 # the gradient of a packed layer's scales [N, K / g] (a plain function over the C ABI, not a torch op)
 qgemm_scale_grad = ops.qgemm_scale_grad
+# the gradient of a packed layer's pair codebook [2^b, 2^b, 2] fp32 (optionally with the scale gradient, one launch),
+# and its fold onto a scalar table [2^b]
+qgemm_table_grad = ops.qgemm_table_grad
+pair_grad_to_table_grad = ops.pair_grad_to_table_grad
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

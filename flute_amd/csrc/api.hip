@@ -1630,6 +1630,31 @@ int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_qgemm_table_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
+                           const void* dY, const void* X, const void* Q, const void* S, const void* QM2, float* dT2,
+                           void* dS, void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
+    if (!dY || !X || !Q || !S || !dT2 || !scratch || (dS && !QM2)) return FLUTE_ERR_NULL;
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
+    if (M < 1) return FLUTE_ERR_SHAPE;
+    if (scratch_bytes < table_grad_scratch_bytes(num_bits, l.lg, M, N, K, dS != nullptr, num_sms))
+        return FLUTE_ERR_WORKSPACE;
+    return table_grad_dispatch(dtype, num_bits, l.t.tile_p, l.lg, M, N, K, dY, X, Q, S, QM2, dT2, dS, scratch,
+                               num_sms, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M, int N, int K, int want_dS,
+                                            int num_sms) {
+    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return 0;
+    if (group_size != 32 && group_size != 64 && group_size != 128 && group_size != 256) return 0;
+    if (M < 1 || N < 1 || K < 1 || N % 128 || K % std::max(64, group_size)) return 0;
+    return table_grad_scratch_bytes(num_bits, ilog2(group_size), M, N, K, want_dS != 0, num_sms);
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -1,0 +1,191 @@
+// G = X^T dY reduced over M, the GEMM both parameter gradients of a packed layer share (scale_grad.hip, table_grad.hip),
+// and the scale gradient's epilogue on it.
+//
+// A workgroup of 8 waves owns a 256 (k) x 128 (n) block - whole groups up to g = 256 - and walks its M range in steps
+// of 32 rows: both operand tiles are copied row-major into LDS (16 B per lane, coalesced; rows past the range and
+// columns past K are written as zeros, never masked) and read back with ds_read_b64_tr_b16, which delivers the MFMA
+// fragments k- / n-major.  Every wave keeps G for its 64 x 64 sub-block in fp32 accumulators (v_mfma_f32_16x16x32: rows
+// k, columns n).  The MFMA's reduction index is the step's row m in a fixed permutation shared by both operands:
+// element e of lane group h is row 4h + e (e < 4) or 16 + 4h + e - 4, so that each 32-lane half of a transposed read
+// covers 8 consecutive rows, which an LDS pitch of 8 dwords mod 64 spreads over all 64 banks.
+#pragma once
+#include "common.h"
+#include "mfma.h"
+
+namespace flute_amd {
+
+constexpr int kSgThreads = 512;                     // 8 waves: 4 along k x 2 along n
+constexpr int kSgBK = 256;                          // k per workgroup
+constexpr int kSgBN = 128;                          // n per workgroup (every legal N is a multiple)
+constexpr int kSgBM = 32;                           // rows per step: one MFMA reduction depth
+constexpr int kSgXPitch = kSgBK * 2 + 32;           // bytes per LDS row; 136 dwords = 8 mod 64
+constexpr int kSgYPitch = kSgBN * 2 + 32;           // 72 dwords = 8 mod 64
+constexpr int kSgXBytes = kSgBM * kSgXPitch;
+constexpr int kSgYBytes = kSgBM * kSgYPitch;
+constexpr int kSgLut = 2 * (kSgXBytes + kSgYBytes); // pair table behind the two operand buffers
+constexpr int kSgLds = kSgLut + 4 * 256;
+constexpr int kSgMinSteps = 4;                      // fewest 32-row steps a split of M gets
+
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint2 lds_tr16(uint32_t addr) {
+    const s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)addr);
+    return __builtin_bit_cast(uint2, v);
+}
+
+// acc[kt][nt][r] = G[k][n] over rows [m_begin, m_end) for the block at (kb, nb): n = nb + wn * 64 + nt * 16 + (lane & 15),
+// k = kb + wk * 64 + kt * 16 + 4 (lane >> 4) + r.  Ends behind a barrier: the operand buffers are free on return.
+template <typename T>
+__device__ __forceinline__ void grad_gemm_mainloop(char* smem, const uint16_t* __restrict__ dY,
+                                                   const uint16_t* __restrict__ X, int N, int K, int nb, int kb,
+                                                   int m_begin, int m_end, f32x4_t (&acc)[4][4]) {
+    const uint32_t base = lds_base_of(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wk = wave & 3, wn = wave >> 2;          // the wave's 64 k and 64 n inside the block
+    const int nsteps = (m_end - m_begin + kSgBM - 1) / kSgBM;
+
+    // loaders: X two 16-B chunks (rows xr, xr + 16), dY one (row yr)
+    const int xc = tid & 31, xr = tid >> 5, yc = tid & 15, yr = tid >> 4;
+    const bool x_in = kb + 8 * xc < K;                // K % 64 == 0: a chunk is all in or all out
+    const uint16_t* xp = X + (size_t)(kb + 8 * xc);
+    const uint16_t* yp = dY + (size_t)(nb + 8 * yc);
+    uint4 xv[2], yv;
+    auto load = [&](int m0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int m = m0 + xr + 16 * h;
+            xv[h] = (x_in && m < m_end) ? *reinterpret_cast<const uint4*>(xp + (size_t)m * K) : make_uint4(0, 0, 0, 0);
+        }
+        const int m = m0 + yr;
+        yv = m < m_end ? *reinterpret_cast<const uint4*>(yp + (size_t)m * N) : make_uint4(0, 0, 0, 0);
+    };
+    auto store = [&](int buf) {
+        char* xs = smem + buf * kSgXBytes + xc * 16;
+        *reinterpret_cast<uint4*>(xs + xr * kSgXPitch) = xv[0];
+        *reinterpret_cast<uint4*>(xs + (xr + 16) * kSgXPitch) = xv[1];
+        *reinterpret_cast<uint4*>(smem + 2 * kSgXBytes + buf * kSgYBytes + yr * kSgYPitch + yc * 16) = yv;
+    };
+
+    // transposed reads: lane 4q + p of 16-lane group h supplies row 4h + q (+ 16 for elements 4..7), columns 4p .. 4p + 3
+    const int h = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const uint32_t xa = base + (4 * h + q) * kSgXPitch + (wk * 64 + 4 * p) * 2;
+    const uint32_t ya = base + 2 * kSgXBytes + (4 * h + q) * kSgYPitch + (wn * 64 + 4 * p) * 2;
+
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    if (nsteps > 0) { load(m_begin); store(0); }
+    __syncthreads();
+    for (int s = 0; s < nsteps; ++s) {
+        const bool more = s + 1 < nsteps;
+        if (more) load(m_begin + (s + 1) * kSgBM);
+        const uint32_t xb = xa + (s & 1) * kSgXBytes, yb = ya + (s & 1) * kSgYBytes;
+        u32x4_t af[4], bf[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const uint2 a0 = lds_tr16(xb + t * 32), a1 = lds_tr16(xb + 16 * kSgXPitch + t * 32);
+            const uint2 b0 = lds_tr16(yb + t * 32), b1 = lds_tr16(yb + 16 * kSgYPitch + t * 32);
+            af[t] = u32x4_t{a0.x, a0.y, a1.x, a1.y};
+            bf[t] = u32x4_t{b0.x, b0.y, b1.x, b1.y};
+        }
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[kt][nt] = Mfma<T>::run(af[kt], bf[nt], acc[kt][nt]);
+        if (more) store((s + 1) & 1);
+        __syncthreads();
+    }
+}
+
+// The packed words behind a lane's accumulators acc[kt][nt]: 4 consecutive k = 2 pair words (x: k0, k0 + 1; y: k0 + 2,
+// k0 + 3) of column n's unit, one per plane.
+template <int BITS, int TILEP>
+struct GradColumn {
+    using L = Layout<BITS>;
+    static constexpr int NP = L::NPLANES;
+    int j, u;                                         // column n is column j of unit u
+    __device__ __forceinline__ explicit GradColumn(int n) {
+        constexpr int JT = L::J * TILEP;
+        const int nblk = n / JT, rem = n - nblk * JT;
+        j = rem / TILEP;
+        u = nblk * TILEP + (rem - j * TILEP);
+    }
+    __device__ __forceinline__ void words(const uint32_t* __restrict__ Q, int N, int K2, int k0, uint2 (&w2)[NP]) const {
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl)
+            w2[pl] = *reinterpret_cast<const uint2*>(Q + (size_t)unit_row<BITS, TILEP>(u, pl, N) * K2 + (k0 >> 1));
+    }
+    // pair index code(k0 + 2e) << b | code(k0 + 2e + 1)
+    __device__ __forceinline__ uint32_t index(const uint2 (&w2)[NP], int e) const {
+        uint32_t w[NP];
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) w[pl] = e ? w2[pl].y : w2[pl].x;
+        return field<BITS>(w, j);
+    }
+};
+
+// The scale gradient from the accumulators: a lane's accumulators are decoded as dequant_kernel does (Layout / unit_row
+// / unit_col0 / field, table2 in LDS at `lut`), multiplied and summed per 32-k chunk; lanes and then waves (through LDS:
+// the first 4 KB of smem) sum the chunks of a group in a fixed order.  Writes T to dS, or fp32 to pout when given.
+template <typename T, int BITS, int TILEP>
+__device__ __forceinline__ void scale_grad_epilogue(char* smem, const uint32_t* lut, const f32x4_t (&acc)[4][4],
+                                                    const uint32_t* __restrict__ Q, uint16_t* __restrict__ dS,
+                                                    float* __restrict__ pout, int N, int K, int lg, int nb, int kb) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wk = wave & 3, wn = wave >> 2, h = lane >> 4;
+    const int K2 = K >> 1;
+    float* red = reinterpret_cast<float*>(smem);      // [8 chunks of 32 k][128 n]; the operand buffers are free now
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int nl = wn * 64 + nt * 16 + (lane & 15);
+        const GradColumn<BITS, TILEP> col(nb + nl);
+        float c[2] = {0.f, 0.f};
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            const int k0 = kb + wk * 64 + kt * 16 + 4 * h;
+            if (k0 < K) {                             // columns past K hold zeros; their codes are not read
+                uint2 w2[GradColumn<BITS, TILEP>::NP];
+                col.words(Q, N, K2, k0, w2);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const uint32_t pr = lut[col.index(w2, e)];    // low half k = 2 kappa, high half 2 kappa + 1
+                    c[kt >> 1] += acc[kt][nt][2 * e] * Num<T>::to_float((uint16_t)(pr & 0xffffu));
+                    c[kt >> 1] += acc[kt][nt][2 * e + 1] * Num<T>::to_float((uint16_t)(pr >> 16));
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            c[i] += __shfl_xor(c[i], 16, 64);
+            c[i] += __shfl_xor(c[i], 32, 64);
+        }
+        if (lane < 16) {
+            red[(wk * 2 + 0) * kSgBN + nl] = c[0];
+            red[(wk * 2 + 1) * kSgBN + nl] = c[1];
+        }
+    }
+    __syncthreads();
+
+    // one output per (n, group of the block): the group's 32-k chunks in order
+    const int G = K >> lg;
+    const int lgb = 8 - lg;                           // log2(groups per block)
+    const int cpg = 1 << (lg - 5);                    // chunks per group
+    for (int it = tid; it < (kSgBN << lgb); it += kSgThreads) {
+        const int nl = it >> lgb, jg = it & ((1 << lgb) - 1);
+        if (kb + (jg << lg) >= K) continue;
+        float v = 0.f;
+        for (int ch = jg * cpg; ch < (jg + 1) * cpg; ++ch) v += red[ch * kSgBN + nl];
+        const size_t o = (size_t)(nb + nl) * G + (kb >> lg) + jg;
+        if (pout) pout[o] = v;
+        else dS[o] = Num<T>::from_float(v);
+    }
+}
+
+// splits of M for a launch (scale_grad.hip): 1 when the blocks fill the chip (two workgroups per CU) or the scratch holds no split
+int scale_grad_splits(int M, int N, int K, int lg, int num_sms, size_t scratch_bytes);
+// the scratch with which scale_grad_splits is bounded by the shape alone: the most splits any M takes x [N][K / g] fp32
+size_t scale_grad_full_scratch(int N, int K, int lg, int num_sms);
+
+}  // namespace flute_amd

@@ -67,6 +67,12 @@ int dequant_dispatch(int dtype, int num_bits, int tile_p, int N, int K, int lg, 
 int scale_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
                         const void* X, const void* Q, const void* QM2, void* dS, void* scratch, size_t scratch_bytes,
                         int num_sms, hipStream_t stream);
+// table gradient dT2 [4^b][2] fp32 (table_grad.hip), with dS non-null also the scale gradient in the same launch; the scratch holds
+// table_grad_scratch_bytes (the only place its size is computed)
+size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int want_dS, int num_sms);
+int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
+                        const void* X, const void* Q, const void* S, const void* QM2, float* dT2, void* dS,
+                        void* scratch, int num_sms, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

@@ -1,4 +1,4 @@
-"""Learnable scales on packed layers: the codes stay packed and fixed, only the scales train.
+"""Learnable scales and lookup tables on packed layers: the codes stay packed and fixed, the float parameters train.
 
 The reference learns scales on a dense copy (flute/integrations/learnable.py keeps the bf16 weight and rebuilds the
 fake-quantized weight every forward).  Here only the 4-bit weight is resident: the forward is `flute.qgemm` itself,
@@ -10,9 +10,17 @@ kernel).  With the codes fixed this is exactly the reference's `absmax` gradient
     ...
     freeze_scales(model)                      # back to plain FluteLinear with the learned scales
 
+The lookup table trains the same way (`make_learnable` / `freeze`): an fp32 master codebook - the scalar table
+[2^b] or the pair codebook [2^b, 2^b, 2] the kernels read - is rounded to the layer's type every forward, and its
+gradient comes from `flute_amd.qgemm_table_grad`, in one launch with the scale gradient when both train.
+
+    params = make_learnable(model, scales=True, table="scalar")   # FluteLinear -> LearnableFluteLinear, in place
+    ...
+    freeze(model)                             # plain FluteLinear: learned scales, tables and tables2, in the layer's type
+
 Not registered by `install_as_flute()`: the reference's `flute.integrations.learnable` is its dense layer.
 """
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -141,3 +149,152 @@ def freeze_scales(module: torch.nn.Module) -> None:
     if isinstance(module, LearnableScalesFluteLinear):
         raise ValueError("freeze_scales swaps the layers below a module: pass the module that holds it")
     _swap(module, lambda m: _frozen(m) if isinstance(m, LearnableScalesFluteLinear) else m)
+
+
+def _codebook_tables(codebook: torch.Tensor, num_bits: int, dtype: torch.dtype):
+    """(table [2^b] T, table2 [2^b, 2^b, 1] fp32 words of T pairs) of an fp32 master codebook, rounded to T."""
+    n = 2 ** num_bits
+    if codebook.dtype != torch.float32:
+        raise TypeError("qgemm_learnable: the codebook is an fp32 master parameter")
+    if tuple(codebook.shape) == (n,):
+        table = codebook.detach().to(dtype)
+        return table, flute_amd.utils.make_qmap2_from_qmap(table)
+    if tuple(codebook.shape) == (n, n, 2):
+        pairs = codebook.detach().to(dtype).contiguous()
+        return pairs[:, 0, 0].contiguous(), pairs.view(torch.float32)      # `table` is not read by the kernels
+    raise ValueError(f"qgemm_learnable: codebook of shape {tuple(codebook.shape)}, expected ({n},) or ({n}, {n}, 2)")
+
+
+class _Learnable(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, scales, codebook, weight, workspace, num_bits, group_size, template_id, num_sms,
+                hadamard_size):
+        table, table2 = _codebook_tables(codebook, num_bits, input.dtype)
+        with torch.enable_grad():
+            x = input.detach().requires_grad_(input.requires_grad)
+            if hadamard_size:
+                y = flute_amd.qgemm_hadamard(x, weight, scales.detach(), table, table2, workspace, num_bits,
+                                             group_size, hadamard_size, template_id, num_sms)
+            else:
+                y = flute_amd.qgemm(x, weight, scales.detach(), table, table2, workspace, num_bits, group_size,
+                                    template_id, num_sms)
+        ctx.inner = (x, y)
+        ctx.save_for_backward(input, scales, weight, table2)
+        ctx.cfg = (num_bits, group_size, template_id, num_sms, hadamard_size, codebook.ndim == 1)
+        return y.detach()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, scales, weight, table2 = ctx.saved_tensors
+        num_bits, group_size, template_id, num_sms, hadamard_size, scalar = ctx.cfg
+        x, y = ctx.inner
+        grad_input = grad_scales = grad_codebook = None
+        if ctx.needs_input_grad[0]:
+            (grad_input,) = torch.autograd.grad(y, x, grad_output)
+        want_s, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if want_s or want_t:
+            xs = flute_amd.hadamard_transform(input, hadamard_size) if hadamard_size else input
+            if want_t:
+                out = flute_amd.qgemm_table_grad(grad_output, xs, weight, scales.detach(), num_bits, group_size,
+                                                 template_id, num_sms, table2=table2, with_scale_grad=want_s)
+                grad_codebook, grad_scales = out if want_s else (out, None)
+                if scalar:
+                    grad_codebook = flute_amd.pair_grad_to_table_grad(grad_codebook)
+            else:
+                grad_scales = flute_amd.qgemm_scale_grad(grad_output, xs, weight, table2, num_bits, group_size,
+                                                         template_id, num_sms)
+        return grad_input, grad_scales, grad_codebook, None, None, None, None, None, None, None
+
+
+def qgemm_learnable(input: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor, codebook: torch.Tensor,
+                    workspace: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms: int,
+                    hadamard_size: int = 0) -> torch.Tensor:
+    """`flute.qgemm` (or `flute.qgemm_hadamard` when hadamard_size > 0), differentiable with respect to `input`,
+    `scales` and `codebook`.  `codebook` is the fp32 master of the lookup table: [2^b] for a scalar table
+    (table2 = make_qmap2_from_qmap) or [2^b, 2^b, 2] for a pair codebook.  The forward rounds it to input.dtype and
+    runs the unchanged op; the gradient passes straight through that rounding, as it does for the scales."""
+    return _Learnable.apply(input, scales, codebook, weight, workspace, num_bits, group_size, template_id, num_sms,
+                            hadamard_size)
+
+
+class LearnableFluteLinear(FluteLinear):
+    """A `FluteLinear` whose scales and / or lookup table train.  `scales=True` makes `scales` an `nn.Parameter` (a
+    copy, in the layer's type); `table="scalar"` / `"pair"` adds the fp32 parameter `codebook` ([2^b] from `tables` /
+    [2^b, 2^b, 2] from `tables2`), `None` keeps the table fixed (no `codebook`: the forward reads the layer's
+    own `tables` / `tables2`).  `weight`, `tables`, `tables2` and `bias` are the source layer's tensors.  With a
+    trained table the state dict carries `codebook` next to `tables` / `tables2`, and those two are stale - the values
+    before training - until `freeze` writes the rounded codebook into them.  Like `FluteLinear` the layer passes no
+    Hadamard size: a layer whose input is rotated first trains through `qgemm_learnable(..., hadamard_size)`."""
+
+    def __init__(self, layer: FluteLinear, scales: bool = True, table: Optional[str] = "scalar") -> None:
+        if not isinstance(layer, FluteLinear):
+            raise TypeError("LearnableFluteLinear wraps a FluteLinear")
+        if table not in ("scalar", "pair", None):
+            raise ValueError("table is 'scalar', 'pair' or None")
+        torch.nn.Module.__init__(self)
+        _share(self, layer, torch.nn.Parameter(layer.scales.detach().clone()) if scales else layer.scales)
+        self.table_mode = table
+        if table is None:
+            return                                    # the fixed table: the layer's own `tables` / `tables2`
+        n = 2 ** layer.num_bits
+        dtype = layer.scales.dtype
+        if table == "scalar":
+            if not torch.equal(flute_amd.utils.make_qmap2_from_qmap(layer.tables.to(dtype)), layer.tables2):
+                raise ValueError("table='scalar': the layer's tables2 is not the pair table of its tables "
+                                 "(a pair codebook trains with table='pair')")
+            codebook = layer.tables.detach().float()
+        else:
+            codebook = layer.tables2.detach().contiguous().view(dtype).view(n, n, 2).float()
+        self.codebook = torch.nn.Parameter(codebook)
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        if self.workspace_lazy_init:
+            num_sms = flute_amd.utils.get_device_num_sms(inputs.device)
+            workspace = flute_amd.utils.get_workspace_streamk(inputs.device)
+        else:
+            num_sms, workspace = self.num_sms, self.workspace
+        if self.table_mode is None:
+            output = qgemm_learnable_scales(inputs, self.weight, self.scales, self.tables, self.tables2, workspace,
+                                            self.num_bits, self.group_size, self.template_id, num_sms)
+        else:
+            output = qgemm_learnable(inputs, self.weight, self.scales, self.codebook, workspace, self.num_bits,
+                                     self.group_size, self.template_id, num_sms)
+        if self.bias is not None:
+            output.add_(self.bias)
+        return output
+
+
+def make_learnable(module: torch.nn.Module, scales: bool = True,
+                   table: Optional[str] = "scalar") -> List[torch.nn.Parameter]:
+    """Replace every `FluteLinear` below `module` by a `LearnableFluteLinear(layer, scales, table)`, in place; returns
+    the parameters this makes trainable (scales, then codebook, per layer in module order)."""
+    if type(module) is FluteLinear:
+        raise ValueError("make_learnable swaps the layers below a module: pass the module that holds it")
+    _swap(module, lambda m: LearnableFluteLinear(m, scales, table) if type(m) is FluteLinear else m)
+    params = []
+    for m in module.modules():
+        if isinstance(m, LearnableFluteLinear):
+            params += [p for p in (m.scales, getattr(m, "codebook", None)) if isinstance(p, torch.nn.Parameter)]
+    return params
+
+
+def _frozen_learnable(layer: LearnableFluteLinear) -> FluteLinear:
+    new = FluteLinear.__new__(FluteLinear)
+    torch.nn.Module.__init__(new)
+    _share(new, layer, layer.scales.detach())
+    if layer.table_mode is not None:
+        table, table2 = _codebook_tables(layer.codebook, layer.num_bits, layer.scales.dtype)
+        if layer.table_mode == "scalar":
+            new.tables = table                        # a pair codebook keeps the source's `tables`: nothing reads it
+        new.tables2 = table2
+    return new
+
+
+def freeze(module: torch.nn.Module) -> None:
+    """Replace every `LearnableFluteLinear` below `module` by a plain `FluteLinear` whose `scales`, `tables` and
+    `tables2` buffers carry the learned values, rounded to the layer's type as every forward rounded them, in place:
+    the model runs the unchanged `flute.qgemm` path again, with `FluteLinear`'s state-dict keys."""
+    if isinstance(module, LearnableFluteLinear):
+        raise ValueError("freeze swaps the layers below a module: pass the module that holds it")
+    _swap(module, lambda m: _frozen_learnable(m) if isinstance(m, LearnableFluteLinear) else m)

@@ -1,5 +1,5 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
-plus two plain functions over the C ABI: `hadamard_transform` and `qgemm_scale_grad`.
+plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad` and `qgemm_table_grad`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -181,3 +181,87 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
             dy.data_ptr(), x.data_ptr(), w.data_ptr(), t2.data_ptr(), out.data_ptr(),
             scratch.data_ptr() if scratch.numel() else None, scratch.numel(), num_sms, _stream_ptr(dev)))
     return out
+
+
+def _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, group_size, with_scale_grad):
+    if not all([input.ndim >= 2, grad_output.ndim == input.ndim, weight.ndim == 2, scales.ndim == 2]):
+        raise ValueError
+    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype or scales.dtype != input.dtype:
+        raise TypeError
+    if weight.dtype != torch.int16:
+        raise TypeError
+    K, N = input.shape[-1], grad_output.shape[-1]
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    if not all([
+        grad_output.shape[:-1] == input.shape[:-1],
+        weight.shape[1] == K,
+        K > 0 and K % max(64, group_size) == 0,
+        N > 0 and N % 16 == 0 and weight.shape[0] == num_bits * (N // 16),
+        tuple(scales.shape) == (N, K // group_size),
+    ]):
+        raise ValueError
+    if with_scale_grad and table2 is None:
+        raise ValueError("qgemm_table_grad: with_scale_grad needs table2 (the scale gradient reads the table)")
+    if table2 is not None:
+        if table2.ndim != 3:
+            raise ValueError
+        if table2.dtype != torch.float32:
+            raise TypeError
+        if tuple(table2.shape) != (2 ** num_bits, 2 ** num_bits, 1):
+            raise ValueError
+
+
+def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                     num_bits: int, group_size: int, template_id: int, num_sms=None, *, table2=None,
+                     with_scale_grad: bool = False):
+    """Gradient of the pair codebook of `Y = qgemm(input, weight, scales, ...)` with the codes fixed, for the upstream
+    gradient `grad_output`: dT2[i, j, e] = sum over the pairs (kappa, n) with codes (i, j) at rows (2 kappa,
+    2 kappa + 1) of sum_m dY[m, n] * X[m, 2 kappa + e] * S[n, 2 kappa / g], as [2^b, 2^b, 2] fp32 (element e of
+    entry (i, j) of `table2` seen as pairs of T).  `pair_grad_to_table_grad` folds it for a scalar table.  The table
+    itself is not read.  With `with_scale_grad` (needs `table2`) the same launch also computes the scale gradient
+    and (dT2, dS) is returned, dS bit for bit `qgemm_scale_grad`'s.  Leading dimensions are flattened; for a
+    Hadamard layer pass the rotated input.  Native HIP kernels on the current stream (table_grad.hip); the same
+    arguments give the same bits."""
+    _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, group_size, with_scale_grad)
+    dev = input.device
+    tensors = (grad_output, input, weight, scales) + ((table2,) if table2 is not None else ())
+    if not all(t.is_cuda and t.device == dev for t in tensors):
+        raise RuntimeError("flute_amd.qgemm_table_grad: all tensors must live on the same GPU")
+    K, N = input.shape[-1], grad_output.shape[-1]
+    x = input.reshape(-1, K).contiguous()
+    dy = grad_output.reshape(-1, N).contiguous()
+    M = x.shape[0]
+    if M >= 2 ** 31:
+        raise ValueError
+    n = 2 ** num_bits
+    dT2 = torch.empty((n, n, 2), dtype=torch.float32, device=dev)
+    dS = torch.empty((N, K // group_size), dtype=input.dtype, device=dev) if with_scale_grad else None
+    if M == 0:
+        dT2.zero_()
+        return (dT2, dS.zero_()) if with_scale_grad else dT2
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    lib = _lib.get()
+    nbytes = lib.flute_qgemm_table_grad_scratch_bytes(num_bits, group_size, M, N, K, int(with_scale_grad), num_sms)
+    if nbytes == 0:
+        raise ValueError(f"flute_amd.qgemm_table_grad: no kernel for N = {N}, K = {K}, group size {group_size}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    w = weight.contiguous()
+    s = scales.contiguous()
+    t2 = table2.contiguous() if with_scale_grad else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.flute_qgemm_table_grad(
+            _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
+            dy.data_ptr(), x.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr() if t2 is not None else None,
+            dT2.data_ptr(), dS.data_ptr() if dS is not None else None, scratch.data_ptr(), nbytes, num_sms,
+            _stream_ptr(dev)))
+    return (dT2, dS) if with_scale_grad else dT2
+
+
+def pair_grad_to_table_grad(dT2: torch.Tensor) -> torch.Tensor:
+    """The adjoint of `utils.make_qmap2_from_qmap` (table2[i, j] = (table[i], table[j])): the gradient [2^b] of a
+    scalar table from the pair-codebook gradient [2^b, 2^b, 2], dtable[i] = sum_j dT2[i, j, 0] + sum_j dT2[j, i, 1]."""
+    if dT2.ndim != 3 or dT2.shape[0] != dT2.shape[1] or dT2.shape[2] != 2:
+        raise ValueError
+    return dT2[:, :, 0].sum(dim=1) + dT2[:, :, 1].sum(dim=0)

@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-/* 9: flute_dequantize; flute_qgemm_scale_grad (additive: no existing entry point changed)
+/* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query (additive: no existing entry point
+ *    changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -81,9 +82,9 @@ typedef struct flute_plan {
                             6 = split-K block kernel (qgemm_splitk.h: 2- / 4-bit, m_tiles x 16 rows (128 or 64) x 256 / kw columns
                             (128; 64 with kw = 4 K parts per workgroup, 64-row tiles only - round 6) output tiles x splitk K slices,
                             one workgroup of 8 compute + 4 loader waves each, partial tiles combined inside the launch; automatic
-                            from M = 33 (4 bits) / 65 (2 bits) where its modelled time is 8 % under the other MFMA kernels' (64-column
+                            from M = 33 (2 and 4 bits) where its modelled time is 8 % under the other MFMA kernels' (64-column
                             tiles that fill half the chip: under the per-wave kernel's time + 4 us) and one round of workgroups
-                            covers the output),
+                            covers the output (2-bit layers up to M = 64: two rounds),
                             7 = lean MFMA decode kernel (qgemm_fastm.h, round 5: 4 bits, 5 <= M <= 16, K in {2048, 4096}, a
                             workgroup = 4 unit rows x all of K, N / 16 workgroups of 8 waves between half a round and one
                             round of the CUs, 32 KB + 32 copies x 4 KB of LDS = 160 KB; what it cannot take falls back),
@@ -229,6 +230,27 @@ int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int 
 int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
                            const void* dY, const void* X, const void* Q, const void* QM2, void* dS,
                            void* scratch, size_t scratch_bytes, int num_sms, void* stream);
+
+/* The gradient of a layer's lookup table with the codes fixed, for the pair codebook the kernels read:
+ *   dT2[c][e] = sum over (kappa, n) whose pair index code(2 kappa) << b | code(2 kappa + 1) is c of
+ *               G[2 kappa + e][n] * S[n][2 kappa / group_size],   G[k][n] = sum_{m < M} X[m][k] * dY[m][n],
+ * dT2 [4^b][2] fp32 (e = 0: the low half of the 32-bit pair word), written whole.  For a scalar table the caller folds
+ * it: dtable[i] = sum_j dT2[i 2^b + j][0] + sum_j dT2[j 2^b + i][1].  dY, X, Q as flute_qgemm_scale_grad; S [N, K /
+ * group_size] T.  The table is not read.  With dS non-null the same launch also writes the scale gradient, bit for bit
+ * what flute_qgemm_scale_grad returns for the same layer and M given its full scratch (what
+ * flute_amd.qgemm_scale_grad passes); QM2 is needed then and only then.  fp32 products and sums inside a workgroup, fp64
+ * across workgroups, one rounding to fp32; no atomics on global memory: equal arguments give equal bits.
+ * Refusals in flute_qgemm_scale_grad's order: FLUTE_ERR_NULL first (dY / X / Q / S / dT2 / scratch, QM2 with a dS),
+ * then dtype, the layer checks, P and M.  `scratch` must hold flute_qgemm_table_grad_scratch_bytes(...) bytes for the
+ * same num_bits, group_size, M, N, K, num_sms and want_dS = (dS != NULL): less is FLUTE_ERR_WORKSPACE (more changes
+ * nothing).  The query takes no template_id: it is 0 for a num_bits / group_size / shape no template accepts (N % 128,
+ * K % max(64, group_size), M < 1) and may be non-zero for arguments one template's own checks still refuse.  Everything
+ * is refused before anything is enqueued. */
+int flute_qgemm_table_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
+                           const void* dY, const void* X, const void* Q, const void* S, const void* QM2, float* dT2,
+                           void* dS, void* scratch, size_t scratch_bytes, int num_sms, void* stream);
+size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M, int N, int K, int want_dS,
+                                            int num_sms);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */
