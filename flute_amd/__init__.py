@@ -26,6 +26,9 @@ qgemm_scale_grad = ops.qgemm_scale_grad
 # and its fold onto a scalar table [2^b]
 qgemm_table_grad = ops.qgemm_table_grad
 pair_grad_to_table_grad = ops.pair_grad_to_table_grad
+# qgemm for the E stacked experts of a mixture-of-experts layer over rows sorted by expert, one launch (the row offsets
+# stay on the device); modules on top of it: flute_amd.integrations.moe
+qgemm_grouped = ops.qgemm_grouped
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

@@ -1655,6 +1655,21 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
     return table_grad_scratch_bytes(num_bits, ilog2(group_size), M, N, K, want_dS != 0, num_sms);
 }
 
+int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                        const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
+                        int num_sms, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (N / 16) || E < 0 || T < 0) return FLUTE_ERR_SHAPE;
+    if (E == 0 || T == 0) return FLUTE_OK;
+    if (!X || !offsets || !Q || !S || !QM2 || !Y) return FLUTE_ERR_NULL;
+    return qgemm_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, Y, num_sms,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

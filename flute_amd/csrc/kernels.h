@@ -73,6 +73,10 @@ size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int w
 int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
                         const void* X, const void* Q, const void* S, const void* QM2, float* dT2, void* dS,
                         void* scratch, int num_sms, hipStream_t stream);
+// grouped qgemm of E stacked layers over rows sorted by expert (qgemm_grouped.hip); offsets [E + 1] int32 is read on the device only
+int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
+                           const void* offsets, const void* Q, const void* S, const void* QM2, void* Y, int num_sms,
+                           hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

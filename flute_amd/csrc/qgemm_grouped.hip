@@ -1,0 +1,282 @@
+// Grouped qgemm for mixture-of-experts layers: Y[r, :] = X[r, :] @ W_e^T for the rows r in [offsets[e], offsets[e + 1]) of
+// every expert e < E, ONE launch whose grid does not depend on how the rows are spread.  X [T, K] holds the rows sorted by
+// expert, offsets [E + 1] int32 lives in device memory and is read by the kernel only (never by the host: the launch is
+// hipGraph-capturable and a replay honours whatever the table then holds), Q [E, P, K] / S [E, N, K / g] / QM2 [E, 4^b] are E
+// layers packed exactly as one FluteLinear's buffers (layout: common.h), all of one num_bits / group size / TileP.
+//
+// Arithmetic (include/flute_amd.h, as dequant.hip and the MFMA kernels): w^ = round_T(lut * s) by Num<T>::mul_scale4, fp32
+// accumulation in the matrix core, one rounding of the output to T.  K is split over the waves of ONE workgroup only and
+// the partial tiles are summed through LDS in wave order; no atomics, no split across workgroups: equal arguments give
+// equal bits.
+//
+// Geometry (qgemm_skinny.h's, for every bit width through Layout / unit_row / unit_col0 / field).  v_mfma_f32_16x16x32 with
+// the weights as the A operand: lane (u = l % 16, q = l / 16) loads, per plane, the 16 B of unit row u that hold k-pairs
+// 4 q .. 4 q + 3 of a 32-k step; field j of each dword is looked up in the expert's pair table (LDS, 32 copies: lane l reads
+// copy l % 32, so the 32 lanes of a ds_read_b32 group never share a bank) and multiplied by the scale of column
+// unit_col0(u) + j TileP: one A fragment per column tile j < J.  The activations are the B operand: lane (r, q) loads its
+// 16 B of row row0 + 16 t + r.  One weight request feeds J x (row tiles of the pass) MFMAs.  D[u][r] lands in lane (q, r) as
+// units 4 q .. 4 q + 3 - four consecutive output columns, one 8-byte store per tile.
+//
+// Work split.  A workgroup is (expert, a run of `spw` 16-unit slabs); its 8 waves split K in blocks of U k-steps (U = 4,
+// 128 k; 2 bits below group size 128: 2; 3 bits: 1), wave w taking blocks w, w + 8, ..: at any moment the waves of a
+// workgroup read one contiguous 0.5 - 2 KB piece of each of the 16 unit rows.  A wave holds the next block's weights and
+// activations in registers while it decodes the current one (plain loads: the compiler counts the waits).  The scales go
+// through LDS: per K chunk the workgroup stages the slab's panel [16 J columns][groups of the chunk] with requests that run
+// along a scale row (64 groups = one cache line per request; read per lane from global memory they were 2-byte requests
+// touching 16 lines each, 9 - 21 % of the time at Mixtral shapes), in the 32 KB the reduction uses after the K loop; the
+// row stride in dwords is odd, so the 16 units of a ds_read_u16 hit 16 banks.  A chunk is the largest multiple of 8 blocks
+// whose groups fit (all of K up to 16 K at 4 bits and group size 64).  The expert index is the slow one of blockIdx
+// (e = blockIdx / runs): consecutive blocks go to different XCDs, so the slabs of ONE busy expert spread over all eight
+// dies - with the expert as the fast index a decode step that routes to two experts would run on two dies.
+// The host picks spw in {1, 2, 4} as the largest that still leaves eight workgroups per CU; it and the grid follow from
+// (E, N, num_bits, num_sms) alone, as include/flute_amd.h says.
+//
+// Rows.  rb = clamp(offsets[e]), re = clamp(offsets[e + 1]) to [0, T]; a workgroup with re <= rb returns before it requests
+// a weight, scale or table word.  The expert's rows are taken in passes of RT 16-row tiles (RT = 2; 3 bits: 1 - the
+// accumulators, J x RT x 4 fp32, and two blocks of operands stay in registers, no scratch), the weights streamed once per
+// pass; a tile of a pass that holds no row issues neither loads nor MFMAs (the K loop is compiled per tile count), rows
+// past `re` inside a tile are fed as zeros and never stored.  Every row index the kernel forms is < re <= T, so a
+// malformed table cannot reach outside X / Y; rows no expert covers are left unwritten.
+//
+// Address arithmetic: the expert bases into Q / S / QM2 and the row bases into X / Y are 64-bit (stacked 8192 x 8192 4-bit
+// experts pass 2 GiB of codes at E = 64).
+#include "kernels.h"
+#include "mfma.h"
+#include <type_traits>
+#include "../../include/flute_amd.h"
+
+namespace flute_amd {
+
+constexpr int kGroupedWaves = 8;
+constexpr int kGroupedThreads = kGroupedWaves * 64;
+constexpr int kGroupedRedTiles = 4;          // output tiles per round of the LDS reduction (8 waves x 4 KB = 32 KB)
+
+// Sized so that the accumulators (J x RT x 4 fp32) and two blocks of operands fit in 256 registers without scratch.
+// LGC (2 bits only; 7 otherwise): 5 / 6 = log2(group size), 7 = group size >= 128
+template <int BITS, int LGC> struct GroupedShape {
+    static constexpr int RT = (BITS == 3) ? 1 : 2;                                           // 16-row tiles per pass
+    static constexpr int U = (BITS == 3) ? 1 : (BITS == 2 && LGC < 7) ? 2 : 4;               // k-steps per block
+};
+
+template <typename T, int BITS, int TILEP, int LGC>
+__global__ __launch_bounds__(kGroupedThreads) void qgemm_grouped_kernel(
+    const uint16_t* __restrict__ X, const int* __restrict__ offsets, const uint32_t* __restrict__ Q,
+    const uint16_t* __restrict__ S, const uint32_t* __restrict__ QM2, uint16_t* __restrict__ Y, int T_rows, int N,
+    int K, int P, int lg, int runs, int spw) {
+    using L = Layout<BITS>;
+    using NT = Num<T>;
+    constexpr int J = L::J;
+    constexpr int NP = L::NPLANES;
+    constexpr int RT = GroupedShape<BITS, LGC>::RT;
+    constexpr int U = GroupedShape<BITS, LGC>::U;
+    constexpr int NI = J * RT;                                     // 16 x 16 output tiles per wave
+    constexpr int KW = kGroupedWaves;
+    constexpr int TR = kGroupedRedTiles;
+    constexpr int NC = 16 * J;                                     // columns of a slab
+    // scale panel of a K chunk: [NC][ST] T in the reduction's LDS; ST / 2 is odd, so the 16 units a ds_read_u16 serves hit 16 banks
+    constexpr int ST = (int)(KW * TR * 64 * sizeof(float4) / 2) / NC - 2;
+    static_assert(NI % TR == 0 && (ST / 2) % 2 == 1 && ST >= 16, "reduction / panel shape");
+
+    __shared__ uint32_t lut[L::LUT_N * 32];
+    __shared__ float4 red[KW * TR * 64];
+
+    const int e = (int)blockIdx.x / runs;
+    const int run = (int)blockIdx.x - e * runs;
+    const int rb = min(max(offsets[e], 0), T_rows);
+    const int re = min(max(offsets[e + 1], 0), T_rows);
+    if (re <= rb) return;                                          // no rows: nothing of this expert is requested
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int u = lane & 15, q = lane >> 4;
+    const int K2 = K >> 1;
+    const int G = K >> lg;
+    const int NS = K >> 5;                                         // k-steps
+    const int NB = (NS + U - 1) / U;                               // blocks (the last one may be short: K % 64 == 0 only)
+    const int slabs = (N / J) >> 4;
+
+    const uint32_t* __restrict__ Qe = Q + (size_t)e * (size_t)P * (size_t)K2;
+    const uint16_t* __restrict__ Se = S + (size_t)e * (size_t)N * (size_t)G;
+    const uint32_t* __restrict__ Te = QM2 + (size_t)e * L::LUT_N;
+
+    // table image: entry i of copy c at word i * 32 + c
+    for (int i = tid; i < L::LUT_N * 32; i += kGroupedThreads) lut[i] = Te[i >> 5];
+    __syncthreads();
+    const uint32_t* lut_lane = lut + (lane & 31);
+    uint16_t* panel = reinterpret_cast<uint16_t*>(red);
+    // blocks per chunk: a multiple of KW whose groups (+ 2 for ragged ends) fit ST
+    const int bpc = ((((ST - 2) << lg) / (U * 32)) / KW) * KW;
+
+    for (int sl = 0; sl < spw; ++sl) {
+        const int slab = run * spw + sl;
+        if (slab >= slabs) break;
+        const int unit = slab * 16 + u;
+        const uint32_t* wrow[NP];
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) wrow[pl] = Qe + (size_t)unit_row<BITS, TILEP>(unit, pl, N) * K2 + q * 4;
+
+        for (int row0 = rb; row0 < re; row0 += 16 * RT) {
+            const int nt = min(RT, (re - row0 + 15) >> 4);         // row tiles of this pass that hold a row
+            const uint16_t* xrow[RT];
+            bool xok[RT];
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+                const int row = row0 + 16 * t + u;
+                xok[t] = row < re;
+                xrow[t] = X + (size_t)(xok[t] ? row : rb) * K + q * 8;
+            }
+
+            f32x4_t acc[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+            // the K loop of a pass with NTC row tiles (a compile-time count: the accumulators of the tiles without rows are
+            // never touched, and no MFMA sits behind a branch)
+            auto k_loop = [&](auto nt_tag) {
+                constexpr int NTC = decltype(nt_tag)::value;
+                struct Block {
+                    u32x4_t w[U][NP];
+                    u32x4_t x[U][NTC];
+                };
+                // block b of this wave: k-steps b U .. b U + U - 1 (those < NS) while b lies in the chunk
+                auto load_block = [&](Block& blk, int b, int cend) {
+#pragma unroll
+                    for (int i = 0; i < U; ++i) {
+                        const int ks = b * U + i;
+                        const bool in = b < cend && ks < NS;
+#pragma unroll
+                        for (int pl = 0; pl < NP; ++pl)
+                            blk.w[i][pl] = in ? *reinterpret_cast<const u32x4_t*>(wrow[pl] + ks * 16) : u32x4_t{0, 0, 0, 0};
+#pragma unroll
+                        for (int t = 0; t < NTC; ++t)
+                            blk.x[i][t] = (in && xok[t]) ? *reinterpret_cast<const u32x4_t*>(xrow[t] + ks * 32)
+                                                         : u32x4_t{0, 0, 0, 0};
+                    }
+                };
+                // K in chunks of `bpc` blocks whose scale panel fits the LDS it shares with the reduction
+                for (int cb = 0; cb < NB; cb += bpc) {
+                    const int cend = min(NB, cb + bpc);
+                    const int g_lo = (cb * U * 32) >> lg;
+                    const int gc = min(G, ((cend * U * 32 - 1) >> lg) + 1) - g_lo;      // <= (bpc U 32 >> lg) + 2 <= ST
+                    __syncthreads();                               // the panel's (or the reduction's) last readers are done
+                    // panel[column tile j][unit u][group]: a wave stages whole scale rows, 64 consecutive groups per request
+                    for (int ci = wave; ci < NC; ci += KW) {
+                        const int col = unit_col0<BITS, TILEP>(slab * 16 + (ci & 15)) + (ci >> 4) * TILEP;
+                        const uint16_t* src = Se + (size_t)col * G + g_lo;
+                        for (int gg = lane; gg < gc; gg += 64) panel[ci * ST + gg] = src[gg];
+                    }
+                    __syncthreads();
+                    const uint16_t* prow = panel + u * ST - g_lo;
+                    Block cur;
+                    load_block(cur, cb + wave, cend);
+                    for (int b = cb + wave; b < cend; b += KW) {
+                        Block nxt;
+                        load_block(nxt, b + KW, cend);             // past the chunk: no request, zeros
+#pragma unroll
+                        for (int i = 0; i < U; ++i) {
+                            const int ks = b * U + i;
+                            if (ks < NS) {
+                                const uint16_t* ps = prow + ((ks * 32) >> lg);
+#pragma unroll
+                                for (int j = 0; j < J; ++j) {
+                                    uint32_t v[4], a[4];
+#pragma unroll
+                                    for (int d = 0; d < 4; ++d) {
+                                        uint32_t w[NP];
+#pragma unroll
+                                        for (int pl = 0; pl < NP; ++pl) w[pl] = cur.w[i][pl][d];
+                                        v[d] = lut_lane[field<BITS>(w, j) << 5];
+                                    }
+                                    NT::mul_scale4(v, (uint32_t)ps[j * 16 * ST], a);
+                                    const u32x4_t af = {a[0], a[1], a[2], a[3]};
+#pragma unroll
+                                    for (int t = 0; t < NTC; ++t) acc[j * RT + t] = Mfma<T>::run(af, cur.x[i][t], acc[j * RT + t]);
+                                }
+                            }
+                        }
+                        cur = nxt;
+                    }
+                }
+            };
+            if constexpr (RT == 1) {
+                k_loop(std::integral_constant<int, 1>{});
+            } else {
+                if (nt == 1) k_loop(std::integral_constant<int, 1>{});
+                else k_loop(std::integral_constant<int, 2>{});
+            }
+
+            // K reduction inside the workgroup, TR tiles per round: tile i of a round is summed by wave i, in wave order
+#pragma unroll
+            for (int t0 = 0; t0 < NI; t0 += TR) {
+                __syncthreads();                                   // the previous round's readers are done
+#pragma unroll
+                for (int i = 0; i < TR; ++i)
+                    red[(wave * TR + i) * 64 + lane] = make_float4(acc[t0 + i][0], acc[t0 + i][1], acc[t0 + i][2], acc[t0 + i][3]);
+                __syncthreads();
+                if (wave < TR) {
+                    const int tile = t0 + wave;
+                    const int j = tile / RT, t = tile % RT;
+                    float4 s = red[wave * 64 + lane];
+                    for (int ww = 1; ww < KW; ++ww) {
+                        const float4 p = red[(ww * TR + wave) * 64 + lane];
+                        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+                    }
+                    // lane (q, r = u): X row row0 + 16 t + r, units 4 q .. 4 q + 3 of the slab = four consecutive columns
+                    const int row = row0 + 16 * t + u;
+                    if (row < re) {
+                        const int col = unit_col0<BITS, TILEP>(slab * 16 + 4 * q) + j * TILEP;
+                        ushort4 o;
+                        o.x = NT::from_float(s.x); o.y = NT::from_float(s.y); o.z = NT::from_float(s.z); o.w = NT::from_float(s.w);
+                        *reinterpret_cast<ushort4*>(Y + (size_t)row * N + col) = o;
+                    }
+                }
+            }
+        }
+    }
+}
+
+int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
+                           const void* offsets, const void* Q, const void* S, const void* QM2, void* Y, int num_sms,
+                           hipStream_t stream) {
+    const int J = (num_bits == 3) ? 16 : 16 / num_bits;
+    const int slabs = N / J / 16;
+    const long long sms = num_sms >= 1 ? num_sms : 256;
+    int spw = 1;
+    while (spw < 4 && (long long)E * ((slabs + 2 * spw - 1) / (2 * spw)) >= 8 * sms) spw *= 2;
+    const int runs = (slabs + spw - 1) / spw;
+    if ((long long)E * runs > 0x7fffffffLL) return FLUTE_ERR_SHAPE;
+    const unsigned grid = (unsigned)((long long)E * runs);
+    const uint16_t* x = reinterpret_cast<const uint16_t*>(X);
+    const int* off = reinterpret_cast<const int*>(offsets);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(Q);
+    const uint16_t* s = reinterpret_cast<const uint16_t*>(S);
+    const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
+    uint16_t* y = reinterpret_cast<uint16_t*>(Y);
+#define FLUTE_GRP(TY, B, TP, LGC)                                                                                       \
+    hipLaunchKernelGGL((qgemm_grouped_kernel<TY, B, TP, LGC>), dim3(grid), dim3(kGroupedThreads), 0, stream, x, off, q, \
+                       s, qm2, y, T, N, K, P, lg, runs, spw)
+#define FLUTE_GRP_L(TY, B, TP)                 \
+    if (lg == 5) FLUTE_GRP(TY, B, TP, 5);      \
+    else if (lg == 6) FLUTE_GRP(TY, B, TP, 6); \
+    else FLUTE_GRP(TY, B, TP, 7)
+#define FLUTE_GRP_T(B, TP)                            \
+    if (dtype == FLUTE_F16) { FLUTE_GRP_L(F16, B, TP); } \
+    else { FLUTE_GRP_L(BF16, B, TP); }
+#define FLUTE_GRP_7(B, TP)                                \
+    if (dtype == FLUTE_F16) { FLUTE_GRP(F16, B, TP, 7); } \
+    else { FLUTE_GRP(BF16, B, TP, 7); }
+    if (num_bits == 4 && tile_p == 32) { FLUTE_GRP_7(4, 32) }
+    else if (num_bits == 4 && tile_p == 64) { FLUTE_GRP_7(4, 64) }
+    else if (num_bits == 2 && tile_p == 32) { FLUTE_GRP_T(2, 32) }
+    else if (num_bits == 2 && tile_p == 64) { FLUTE_GRP_T(2, 64) }
+    else if (num_bits == 3 && tile_p == 32) { FLUTE_GRP_7(3, 32) }
+    else return FLUTE_ERR_TEMPLATE_ID;
+#undef FLUTE_GRP_7
+#undef FLUTE_GRP_T
+#undef FLUTE_GRP_L
+#undef FLUTE_GRP
+    return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+}
+
+}  // namespace flute_amd

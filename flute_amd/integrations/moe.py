@@ -1,0 +1,119 @@
+"""Mixture-of-experts layers on packed weights: all experts of a projection in one launch.
+
+`GroupedFluteLinear` stacks E `FluteLinear`s of one shape and serves rows sorted by expert through
+`flute_amd.qgemm_grouped` (qgemm_grouped.hip); the per-expert row counts never leave the device (`sort_by_expert`
+uses ops of fixed output shape only), so a decode step with changing routing can sit in one captured graph.
+`FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them.
+
+    experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
+    out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
+
+Not registered by `install_as_flute()`: the reference has no grouped form.
+"""
+from typing import Sequence, Tuple
+
+import torch
+
+import flute_amd
+import flute_amd.utils
+from .base import FluteLinear
+
+
+def sort_by_expert(topk_ids: torch.Tensor, num_experts: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The grouping `qgemm_grouped` takes, from the router's choice topk_ids [T, k]: `perm` [T k] lists the flattened
+    (token, slot) pairs by expert, pairs of one expert in their original order (a stable sort), and `offsets`
+    [E + 1] int32 are the experts' row ranges in that order.  Token of sorted row i: perm[i] // k.  Ids outside
+    [0, E) sort behind every expert, past offsets[E]: no expert serves those rows.
+    Ops of fixed output shape on the ids' device only (the counts are a comparison against arange(E) summed over the
+    pairs, not `bincount`, whose output length depends on the data and is read back to the host): no host
+    synchronise, capturable in a graph."""
+    flat = topk_ids.reshape(-1)
+    experts = torch.arange(num_experts, device=flat.device, dtype=flat.dtype)
+    hit = flat[:, None] == experts                              # [T k, E]
+    perm = torch.argsort(torch.where(hit.any(dim=1), flat, num_experts), stable=True)
+    offsets = torch.zeros(num_experts + 1, dtype=torch.int32, device=flat.device)
+    offsets[1:] = torch.cumsum(hit.sum(dim=0), 0)
+    return perm, offsets
+
+
+class GroupedFluteLinear(torch.nn.Module):
+    """E packed layers [N, K] of one num_bits / group_size / template_id / dtype, stacked along a leading expert axis."""
+
+    def __init__(self, num_experts: int, in_features: int, out_features: int, num_bits: int, group_size: int,
+                 template_id: int, device: torch.device, dtype: torch.dtype) -> None:
+        if dtype not in [torch.float16, torch.bfloat16]:
+            raise NotImplementedError
+        super().__init__()
+        E, K, N = num_experts, in_features, out_features
+        n = 2 ** num_bits
+        self.num_experts, self.in_features, self.out_features = E, K, N
+        self.num_bits, self.group_size, self.template_id = num_bits, group_size, template_id
+        self.num_sms = flute_amd.utils.get_device_num_sms(device) if device.type == "cuda" else None
+        tables = torch.arange(n, dtype=dtype, device=device)
+        self.register_buffer("weight", torch.empty((E, N // 16 * num_bits, K), dtype=torch.int16, device=device))
+        self.register_buffer("scales", torch.ones((E, N, K // group_size), dtype=dtype, device=device))
+        self.register_buffer("tables", tables.repeat(E, 1))
+        self.register_buffer("tables2", flute_amd.utils.make_qmap2_from_qmap(tables).repeat(E, 1, 1, 1))
+
+    @classmethod
+    def from_linears(cls, layers: Sequence[FluteLinear]) -> "GroupedFluteLinear":
+        if len(layers) == 0:
+            raise ValueError("GroupedFluteLinear.from_linears: no layers")
+        first = layers[0]
+        key = lambda m: (m.in_features, m.out_features, m.num_bits, m.group_size, m.template_id, m.scales.dtype,
+                         m.scales.device)
+        for i, m in enumerate(layers):
+            if not isinstance(m, FluteLinear):
+                raise TypeError(f"expert {i}: not a FluteLinear")
+            if m.bias is not None:
+                raise ValueError(f"expert {i}: a bias is not supported")
+            if key(m) != key(first):
+                raise ValueError(f"expert {i}: {key(m)} differs from expert 0's {key(first)}")
+        new = cls(len(layers), first.in_features, first.out_features, first.num_bits, first.group_size,
+                  first.template_id, device=first.scales.device, dtype=first.scales.dtype)
+        new.weight.copy_(torch.stack([m.weight for m in layers]))
+        new.scales.copy_(torch.stack([m.scales for m in layers]))
+        new.tables.copy_(torch.stack([m.tables for m in layers]))
+        new.tables2.copy_(torch.stack([m.tables2 for m in layers]))
+        return new
+
+    def forward(self, x_sorted: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        num_sms = self.num_sms if self.num_sms is not None else flute_amd.utils.get_device_num_sms(x_sorted.device)
+        return flute_amd.qgemm_grouped(x_sorted, offsets, self.weight, self.scales, self.tables2, self.num_bits,
+                                       self.group_size, self.template_id, num_sms)
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, "
+                f"num_bits={self.num_bits}, group_size={self.group_size}")
+
+
+class FluteExperts(torch.nn.Module):
+    """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token."""
+
+    def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear) -> None:
+        super().__init__()
+        if not (gate.num_experts == up.num_experts == down.num_experts):
+            raise ValueError("FluteExperts: gate, up and down differ in their number of experts")
+        if (gate.in_features, gate.out_features) != (up.in_features, up.out_features) or \
+                (down.in_features, down.out_features) != (gate.out_features, gate.in_features):
+            raise ValueError("FluteExperts: gate / up must be [K -> F] and down [F -> K]")
+        self.gate, self.up, self.down = gate, up, down
+        self.num_experts = gate.num_experts
+
+    @classmethod
+    def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
+                     downs: Sequence[FluteLinear]) -> "FluteExperts":
+        return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
+                   GroupedFluteLinear.from_linears(downs))
+
+    def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
+        k = topk_ids.shape[1]
+        perm, offsets = sort_by_expert(topk_ids, self.num_experts)
+        token = perm // k
+        x = hidden[token]
+        h = torch.nn.functional.silu(self.gate(x, offsets)) * self.up(x, offsets)
+        y = self.down(h, offsets) * topk_weights.reshape(-1)[perm].to(hidden.dtype)[:, None]
+        # rows past offsets[E] (ids outside [0, E)) were written by no expert: they contribute nothing
+        served = torch.arange(y.shape[0], device=y.device) < offsets[-1]
+        y = torch.where(served[:, None], y, torch.zeros_like(y))
+        return torch.zeros_like(hidden).index_add_(0, token, y)

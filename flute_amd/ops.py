@@ -1,5 +1,5 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
-plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad` and `qgemm_table_grad`.
+plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad` and `qgemm_grouped`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -265,3 +265,60 @@ def pair_grad_to_table_grad(dT2: torch.Tensor) -> torch.Tensor:
     if dT2.ndim != 3 or dT2.shape[0] != dT2.shape[1] or dT2.shape[2] != 2:
         raise ValueError
     return dT2[:, :, 0].sum(dim=1) + dT2[:, :, 1].sum(dim=0)
+
+
+def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size):
+    if not all([input.ndim == 2, offsets.ndim == 1, weight.ndim == 3, scales.ndim == 3, table2.ndim == 4]):
+        raise ValueError
+    if input.dtype not in _DTYPE_ID or scales.dtype != input.dtype:
+        raise TypeError
+    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
+        raise TypeError
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    K = input.shape[1]
+    E, N = scales.shape[0], scales.shape[1]
+    if not all([
+        weight.shape[0] == E,
+        weight.shape[2] == K,
+        K > 0 and K % max(64, group_size) == 0,
+        scales.shape[2] * group_size == K,
+        N > 0 and N % 16 == 0 and weight.shape[1] == num_bits * (N // 16),
+        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
+        offsets.shape[0] == E + 1,
+    ]):
+        raise ValueError
+
+
+def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                  table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+    """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
+    r in [offsets[e], offsets[e + 1]).  `input` [T, K] holds the rows sorted by expert, `offsets` is an int32 CUDA tensor
+    of E + 1 elements (0, non-decreasing, T last), `weight` [E, P, K], `scales` [E, N, K / g] and `table2`
+    [E, 2^b, 2^b, 1] are E layers packed as `FluteLinear`'s buffers with one num_bits, group_size and template_id.
+    Returns [T, N] in input.dtype; rows no expert covers are left unwritten, and a table that decreases or whose
+    ranges overlap is memory-safe (every index is clamped to T) but leaves the contents of the rows it names twice unspecified.  The host never reads `offsets` (no
+    synchronise: the call can be captured in a graph and replayed on other row counts of the same T).  A native HIP
+    kernel on the current stream (qgemm_grouped.hip); the same arguments give the same bits."""
+    _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in (input, offsets, weight, scales, table2)):
+        raise RuntimeError("flute_amd.qgemm_grouped: all tensors must live on the same GPU")
+    T, K = input.shape
+    E, N = scales.shape[0], scales.shape[1]
+    if T >= 2 ** 31:
+        raise ValueError
+    x = input.contiguous()
+    off = offsets.contiguous()
+    w = weight.contiguous()
+    s = scales.contiguous()
+    t2 = table2.contiguous()
+    out = torch.empty((T, N), dtype=input.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_grouped(
+            _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
+            x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), out.data_ptr(), num_sms,
+            _stream_ptr(dev)))
+    return out

@@ -23,8 +23,8 @@
 extern "C" {
 #endif
 
-/* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query (additive: no existing entry point
- *    changed, so the number stays)
+/* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped (additive: no
+ *    existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -251,6 +251,27 @@ int flute_qgemm_table_grad(int dtype, int num_bits, int group_size, int M, int N
                            void* dS, void* scratch, size_t scratch_bytes, int num_sms, void* stream);
 size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M, int N, int K, int want_dS,
                                             int num_sms);
+
+/* Grouped qgemm for mixture-of-experts layers: Y[r, :] = X[r, :] @ W_e^T for every row r in [offsets[e], offsets[e + 1]),
+ * e = 0 .. E - 1, in ONE launch.  X [T, K] T holds the rows sorted by expert; offsets [E + 1] int32 in DEVICE memory,
+ * offsets[0] = 0, non-decreasing, offsets[E] = T; Q [E, P, K] int16, S [E, N, K / group_size] T and QM2 [E, 2^b, 2^b] pair
+ * words are E layers packed exactly as flute_qgemm takes one (one num_bits, group_size and template_id for all); Y [T, N] T.
+ * Arithmetic as flute_dequantize and the MFMA kernels: w^ = round_T(QM2-pair-lookup * scale), fp32 accumulation in the
+ * matrix core, one rounding of the output.  K is split among the waves of one workgroup only and combined through LDS
+ * in a fixed order (no atomics, no split across workgroups): equal arguments give equal bits.
+ * The host never reads `offsets`: the grid follows from (E, N, num_bits, num_sms) alone, so
+ * the launch can be captured in a hipGraph and a replay serves whatever the table then holds.  A workgroup whose expert
+ * has no rows requests nothing.  Every row index is clamped to [0, T]: a malformed table cannot read or write outside
+ * X / Y; rows no expert covers are left unwritten, rows that overlapping ranges name twice have unspecified contents.
+ * Experts with many rows stream their weights once per pass of 32 rows (3 bits: 16): correct for any count, fast for
+ * decode-sized ones.
+ * Refusals, before anything is enqueued: FLUTE_ERR_DTYPE, then the layer checks of flute_dequantize (num_bits 2 / 3 / 4,
+ * group_size 32 / 64 / 128 / 256, the template id - 3 bits: TileP 32 only -, N a multiple of the template's column block,
+ * K % max(64, group_size) == 0), FLUTE_ERR_SHAPE for P != num_bits * N / 16 or a negative E / T; E == 0 or T == 0 returns
+ * FLUTE_OK without a launch; then FLUTE_ERR_NULL for a null pointer.  num_sms < 1: 256. */
+int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                        const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                        void* Y, int num_sms, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */
