@@ -29,6 +29,8 @@ pair_grad_to_table_grad = ops.pair_grad_to_table_grad
 # qgemm for the E stacked experts of a mixture-of-experts layer over rows sorted by expert, one launch (the row offsets
 # stay on the device); modules on top of it: flute_amd.integrations.moe
 qgemm_grouped = ops.qgemm_grouped
+qgemm_grouped_glu = ops.qgemm_grouped_glu
+qgemm_grouped_weighted = ops.qgemm_grouped_weighted
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

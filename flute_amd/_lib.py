@@ -62,6 +62,8 @@ SYMBOLS = {
     "flute_qgemm_table_grad": (c_int, [c_int] * 8 + [c_void_p] * 8 + [c_size_t, c_int, c_void_p]),
     "flute_qgemm_table_grad_scratch_bytes": (c_size_t, [c_int] * 7),
     "flute_qgemm_grouped": (c_int, [c_int] * 9 + [c_void_p] * 6 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_glu": (c_int, [c_int] * 10 + [c_void_p] * 10 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_weighted": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
     "flute_debug_stream_read": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "flute_debug_timestamp": (c_int, [c_void_p, c_void_p]),
 }

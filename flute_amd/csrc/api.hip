@@ -1670,6 +1670,38 @@ int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, i
                                   reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                            int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                            const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                            void* H, int num_sms, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, F, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (F / 16) || E < 0 || R < 0 || Tsrc < 0) return FLUTE_ERR_SHAPE;
+    if (rows ? (R > 0 && Tsrc < 1) : Tsrc != R) return FLUTE_ERR_SHAPE;
+    if (E == 0 || R == 0) return FLUTE_OK;
+    if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
+    return qgemm_grouped_glu_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, Tsrc, F, K, P, Xsrc, rows, offsets, Qgate,
+                                      Sgate, QM2gate, Qup, Sup, QM2up, H, num_sms, reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                 int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                 const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    Layer l;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (N / 16) || E < 0 || T < 0) return FLUTE_ERR_SHAPE;
+    if (E == 0 || T == 0) return FLUTE_OK;
+    if (!X || !offsets || !Q || !S || !QM2 || !row_weight || !Y) return FLUTE_ERR_NULL;
+    return qgemm_grouped_weighted_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2,
+                                           row_weight, Y, num_sms, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

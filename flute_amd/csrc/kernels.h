@@ -77,6 +77,15 @@ int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int 
 int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
                            const void* offsets, const void* Q, const void* S, const void* QM2, void* Y, int num_sms,
                            hipStream_t stream);
+// its fused forms for a mixture-of-experts MLP (qgemm_grouped_fused.h): H = silu32(gate) * up over rows read through an optional
+// index, and Y = row_weight * (X @ W^T) with the rows past offsets[E] written as zeros
+int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int Tsrc, int N, int K, int P,
+                               const void* Xsrc, const void* rows, const void* offsets, const void* Qg, const void* Sg,
+                               const void* QM2g, const void* Qu, const void* Su, const void* QM2u, void* H, int num_sms,
+                               hipStream_t stream);
+int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
+                                    const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                                    const void* row_weight, void* Y, int num_sms, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

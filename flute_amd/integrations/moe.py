@@ -3,10 +3,12 @@
 `GroupedFluteLinear` stacks E `FluteLinear`s of one shape and serves rows sorted by expert through
 `flute_amd.qgemm_grouped` (qgemm_grouped.hip); the per-expert row counts never leave the device (`sort_by_expert`
 uses ops of fixed output shape only), so a decode step with changing routing can sit in one captured graph.
-`FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them.
+`FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
+its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
+    fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
@@ -90,30 +92,51 @@ class GroupedFluteLinear(torch.nn.Module):
 class FluteExperts(torch.nn.Module):
     """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token."""
 
-    def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear) -> None:
+    def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
+                 fused: bool = False) -> None:
         super().__init__()
         if not (gate.num_experts == up.num_experts == down.num_experts):
             raise ValueError("FluteExperts: gate, up and down differ in their number of experts")
         if (gate.in_features, gate.out_features) != (up.in_features, up.out_features) or \
                 (down.in_features, down.out_features) != (gate.out_features, gate.in_features):
             raise ValueError("FluteExperts: gate / up must be [K -> F] and down [F -> K]")
+        if fused and (gate.num_bits, gate.group_size, gate.template_id, gate.scales.dtype) != \
+                (up.num_bits, up.group_size, up.template_id, up.scales.dtype):
+            raise ValueError("FluteExperts: the fused forward needs gate and up of one num_bits / group_size / template_id / dtype")
         self.gate, self.up, self.down = gate, up, down
         self.num_experts = gate.num_experts
+        self.fused = bool(fused)
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
-                     downs: Sequence[FluteLinear]) -> "FluteExperts":
+                     downs: Sequence[FluteLinear], fused: bool = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
-                   GroupedFluteLinear.from_linears(downs))
+                   GroupedFluteLinear.from_linears(downs), fused=fused)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         k = topk_ids.shape[1]
         perm, offsets = sort_by_expert(topk_ids, self.num_experts)
         token = perm // k
+        if self.fused:
+            return self._forward_fused(hidden, topk_weights, perm, offsets, token)
         x = hidden[token]
         h = torch.nn.functional.silu(self.gate(x, offsets)) * self.up(x, offsets)
         y = self.down(h, offsets) * topk_weights.reshape(-1)[perm].to(hidden.dtype)[:, None]
         # rows past offsets[E] (ids outside [0, E)) were written by no expert: they contribute nothing
         served = torch.arange(y.shape[0], device=y.device) < offsets[-1]
         y = torch.where(served[:, None], y, torch.zeros_like(y))
+        return torch.zeros_like(hidden).index_add_(0, token, y)
+
+    def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
+        """Two launches (qgemm_grouped_fused.h): silu(gate(x)) * up(x) with the rows of `hidden` read through the
+        routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
+        the rows past offsets[E] (ids outside [0, E)) as zeros: no silu, no where, no gathered copy of `hidden`."""
+        gate, up, down = self.gate, self.up, self.down
+        num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
+        h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight, up.scales,
+                                        up.tables2, gate.num_bits, gate.group_size, gate.template_id, num_sms,
+                                        rows=token.to(torch.int32))
+        y = flute_amd.qgemm_grouped_weighted(h, offsets, down.weight, down.scales, down.tables2,
+                                             topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
+                                             down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)

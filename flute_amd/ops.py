@@ -1,5 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
-plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad` and `qgemm_grouped`.
+plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu` and
+`qgemm_grouped_weighted`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -321,4 +322,89 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
             _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
             x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), out.data_ptr(), num_sms,
             _stream_ptr(dev)))
+    return out
+
+
+def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                          num_bits, group_size, rows):
+    _validate_grouped(input, offsets, gate_weight, gate_scales, gate_table2, num_bits, group_size)
+    _validate_grouped(input, offsets, up_weight, up_scales, up_table2, num_bits, group_size)
+    if tuple(up_scales.shape) != tuple(gate_scales.shape):          # (weight and table2 follow from the scales' shape)
+        raise ValueError
+    if rows is not None:
+        if rows.dtype != torch.int32:
+            raise TypeError
+        if rows.ndim != 1:
+            raise ValueError
+
+
+def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
+                      gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
+                      up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                      rows=None) -> torch.Tensor:
+    """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
+    the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
+    clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
+    one, of one shape, num_bits, group_size and template_id.  Both products stay in fp32 until the one rounding of the
+    result (include/flute_amd.h, flute_qgemm_grouped_glu); nothing intermediate is written.  Returns [R, F] in
+    input.dtype, rows no expert covers left unwritten.  The host reads neither `offsets` nor `rows` (no synchronise,
+    capturable); a native HIP kernel on the current stream (qgemm_grouped_fused.h); equal arguments give equal bits."""
+    _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                          num_bits, group_size, rows)
+    dev = input.device
+    tensors = (input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2) + \
+        (() if rows is None else (rows,))
+    if not all(t.is_cuda and t.device == dev for t in tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_glu: all tensors must live on the same GPU")
+    Tsrc, K = input.shape
+    E, F = gate_scales.shape[0], gate_scales.shape[1]
+    R = Tsrc if rows is None else rows.shape[0]
+    if max(R, Tsrc) >= 2 ** 31:
+        raise ValueError
+    x, off = input.contiguous(), offsets.contiguous()
+    ops = [t.contiguous() for t in (gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2)]
+    idx = None if rows is None else rows.contiguous()
+    out = torch.empty((R, F), dtype=input.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_grouped_glu(
+            _DTYPE_ID[x.dtype], num_bits, group_size, E, R, Tsrc, F, K, ops[0].shape[1], template_id,
+            x.data_ptr(), None if idx is None else idx.data_ptr(), off.data_ptr(), *[t.data_ptr() for t in ops],
+            out.data_ptr(), num_sms, _stream_ptr(dev)))
+    return out
+
+
+def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size):
+    _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    if row_weight.dtype != torch.float32:
+        raise TypeError
+    if row_weight.ndim != 1 or row_weight.shape[0] != input.shape[0]:
+        raise ValueError
+
+
+def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                           table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
+                           template_id: int, num_sms=None) -> torch.Tensor:
+    """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
+    product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
+    offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
+    HIP kernel on the current stream (qgemm_grouped_fused.h); equal arguments give equal bits."""
+    _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in (input, offsets, weight, scales, table2, row_weight)):
+        raise RuntimeError("flute_amd.qgemm_grouped_weighted: all tensors must live on the same GPU")
+    T, K = input.shape
+    E, N = scales.shape[0], scales.shape[1]
+    if T >= 2 ** 31:
+        raise ValueError
+    x, off, w, s, t2, rw = (t.contiguous() for t in (input, offsets, weight, scales, table2, row_weight))
+    out = torch.empty((T, N), dtype=input.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_grouped_weighted(
+            _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
+            x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), rw.data_ptr(), out.data_ptr(),
+            num_sms, _stream_ptr(dev)))
     return out

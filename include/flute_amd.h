@@ -23,8 +23,8 @@
 extern "C" {
 #endif
 
-/* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped (additive: no
- *    existing entry point changed, so the number stays)
+/* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
+ *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -272,6 +272,43 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
 int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
                         const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
                         void* Y, int num_sms, void* stream);
+
+/* The gated half of a mixture-of-experts MLP in ONE launch, on flute_qgemm_grouped's kernel geometry:
+ *   H[r, :] = round_T( silu32(g) * u ),   g = Xsrc[rows[r], :] @ Wgate_e^T,   u = Xsrc[rows[r], :] @ Wup_e^T
+ * for every row r in [offsets[e], offsets[e + 1]), e = 0 .. E - 1.  g and u are the fp32 sums of the matrix core after the
+ * K reduction inside the workgroup (w^ = round_T(QM2-pair-lookup * scale) exactly as flute_qgemm_grouped), the product is
+ * formed in fp32 and there is ONE rounding to T, at the store; nothing intermediate reaches global memory.
+ *   silu32(g) = g / (1 + exp(-g)), evaluated in fp32 as written: expf (within 1 ulp = 2^-23 relative), one correctly
+ *   rounded addition and one correctly rounded division (2^-24 each).  An error of the exponential enters the sum 1 + t
+ *   scaled by t / (1 + t) < 1, so silu32 is within 2^-23 + 2 * 2^-24 = 2^-22 (to first order) of g / (1 + e^-g) for
+ *   every |g| <= 88 (e^88 is finite in fp32; e^-88 vanishes against the 1); with the fp32 product by u (2^-24):
+ *   eps_s = 2^-21 bounds the relative error of silu32(g) * u before the store, well below the rounding to T.
+ * Xsrc [Tsrc, K] T; rows [R] int32 in DEVICE memory or null.  Null: row r of Xsrc is r, and Tsrc must equal R.  Otherwise
+ * each entry is clamped to [0, Tsrc) before it forms an address (Tsrc >= 1 then), and the activation load is the only use
+ * of it: no gathered copy of Xsrc is needed.  offsets [E + 1] as flute_qgemm_grouped, clamped to [0, R].  Gate and up are
+ * two stacks Q [E, P, K] / S [E, F, K / group_size] / QM2 [E, 2^b, 2^b] of one shape, num_bits, group_size and
+ * template_id, each with its own tables and scales; H [R, F] T.  A workgroup serves the same column slab of both stacks
+ * for the same rows: no atomics, no split across workgroups, equal arguments give equal bits.  The host reads neither
+ * offsets nor rows; the grid follows from (E, F, num_bits, num_sms) alone (hipGraph-capturable, a replay serves what
+ * the arrays then hold); an expert without rows requests nothing; rows no expert covers are left unwritten.
+ * Refusals as flute_qgemm_grouped, in its order, before anything is enqueued: dtype, the layer checks, FLUTE_ERR_SHAPE
+ * (P, a negative E / R / Tsrc, Tsrc != R without rows, Tsrc == 0 with rows and R > 0); E == 0 or R == 0 returns FLUTE_OK
+ * without a launch; then FLUTE_ERR_NULL for a null pointer other than rows.  num_sms < 1: 256. */
+int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                            int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                            const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                            void* H, int num_sms, void* stream);
+
+/* flute_qgemm_grouped with a per-row weight in the epilogue, for the down projection of a mixture-of-experts MLP:
+ *   Y[r, :] = round_T( row_weight[r] * acc32 ),   acc32 = the fp32 sum of X[r, :] @ W_e^T,
+ * for every row r in [offsets[e], offsets[e + 1]): the product in fp32, ONE rounding.  row_weight [T] fp32 in device memory.
+ * The rows [clamp(offsets[E]), T) - rows no expert serves - are written as zeros by the same launch, whichever experts
+ * have rows (none included); rows >= T are never touched.  Everything else - operands, arithmetic of w^, determinism, the
+ * grid, clamping, the refusals and their order, E == 0 or T == 0, num_sms - is flute_qgemm_grouped's; row_weight is one
+ * of the pointers FLUTE_ERR_NULL covers. */
+int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                 int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                 const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */

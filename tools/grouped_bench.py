@@ -1,6 +1,7 @@
 """Grouped qgemm against the per-expert loop on Mixtral-8x7B-shaped experts, timed the way bench.py times the headline.
 
     python tools/grouped_bench.py [--steps 20] [--warmup 5] [--replays 5] [--out profiles/grouped_moe.json]
+    python tools/grouped_bench.py --mode mlp [--out profiles/grouped_moe_fused.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -14,6 +15,15 @@ every timed replay, warm-up, the median of `replays` replays), alternately in th
 
 Per shape: microseconds per step of both, their ratio, the bytes the algorithm needs (packed weights and scales of the
 routed experts, X and Y), the GB/s and the share of 8 TB/s that follow, and the spread of the replays.
+
+--mode mlp times a whole expert MLP step at the same shapes, token counts and routing, from the gather of the hidden
+states through the down projection's weighted output (everything of FluteExperts.forward between sort_by_expert and
+index_add_), by the same method, both forms alternating in one process:
+
+  unfused   hidden[token], three qgemm_grouped launches, silu, the product, the weight gather and cast, the scaling and
+            where(served): FluteExperts.forward as it is without `fused`
+  fused     qgemm_grouped_glu reading hidden through the routing index, then qgemm_grouped_weighted: two launches
+            (and the cast of the index and the gather of the weights, which the fused forward also runs)
 """
 import argparse
 import json
@@ -91,6 +101,91 @@ class Experts:
         return routed * per_expert + sum(self.counts) * (self.K + self.N) * 2
 
 
+class Mlp:
+    """`copies` sets of gate / up [F, K] and down [K, F] stacks; step(i) runs one MLP step of all routed rows on set i."""
+
+    def __init__(self, counts, tokens, copies, device, fused):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.fused, self.counts = flute_amd, fused, counts
+        self.num_sms = utils.get_device_num_sms(device)
+        K, F = 4096, 14336
+        self.K, self.F = K, F
+        gen = torch.Generator(device=device).manual_seed(1)
+
+        def stack(N, Kin):
+            Q = torch.randint(-2 ** 15, 2 ** 15, (copies, E, BITS * N // 16, Kin), dtype=torch.int16, device=device, generator=gen)
+            S = (torch.rand(copies, E, N, Kin // G, device=device, generator=gen) * 0.02 + 0.005).to(DTYPE)
+            return Q, S
+        self.gate, self.up, self.down = stack(F, K), stack(F, K), stack(K, F)
+        table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
+        self.tables2 = utils.make_qmap2_from_qmap(table).repeat(E, 1, 1, 1)
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+        T = sum(counts)
+        self.hidden = torch.randn(tokens, K, device=device, generator=gen).to(DTYPE)
+        # what sort_by_expert hands the forward: the token of every sorted row, the sorted rows' weights' places, the offsets
+        self.token = torch.randint(0, tokens, (T,), device=device, generator=gen)
+        self.perm = torch.randperm(T, device=device, generator=gen)
+        self.topk_weights = torch.rand(T, device=device, generator=gen).to(DTYPE)
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + c)
+        self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
+
+    def step(self, i):
+        c = i % self.gate[0].shape[0]
+        fa, off, t2, a = self.fa, self.offsets, self.tables2, (BITS, G, self.tid, self.num_sms)
+        (Qg, Sg), (Qu, Su), (Qd, Sd) = self.gate, self.up, self.down
+        if self.fused:
+            h = fa.qgemm_grouped_glu(self.hidden, off, Qg[c], Sg[c], t2, Qu[c], Su[c], t2, *a, rows=self.token.to(torch.int32))
+            return fa.qgemm_grouped_weighted(h, off, Qd[c], Sd[c], t2, self.topk_weights[self.perm].float(), *a)
+        x = self.hidden[self.token]
+        h = torch.nn.functional.silu(fa.qgemm_grouped(x, off, Qg[c], Sg[c], t2, *a)) * fa.qgemm_grouped(x, off, Qu[c], Su[c], t2, *a)
+        y = fa.qgemm_grouped(h, off, Qd[c], Sd[c], t2, *a) * self.topk_weights[self.perm].to(DTYPE)[:, None]
+        served = torch.arange(y.shape[0], device=y.device) < off[-1]
+        return torch.where(served[:, None], y, torch.zeros_like(y))
+
+    def bytes(self):
+        routed = sum(1 for c in self.counts if c)
+        per_expert = 3 * ((BITS * self.F // 16) * self.K * 2 + self.F * (self.K // G) * 2)
+        return routed * per_expert + sum(self.counts) * 2 * self.K * 2
+
+
+def main_mlp(args, device):
+    rows = []
+    per_copy = 3 * E * ((BITS * 14336 // 16) * 4096 * 2 + 14336 * (4096 // G) * 2)
+    copies = max(2, bench.L3_BYTES // per_copy + 2)
+    for tokens in args.tokens:
+        counts = routing(tokens, seed=tokens)
+        unfused = Mlp(counts, tokens, copies, device, fused=False)
+        fused = Mlp(counts, tokens, copies, device, fused=True)
+        a, b = unfused.step(0).float(), fused.step(0).float()
+        torch.cuda.synchronize()
+        # two passes of each, alternating; the figure is the mean of each form's two medians
+        m = [measure(layer, args) for layer in (unfused, fused, unfused, fused)]
+        u_us, f_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+        nbytes = fused.bytes()
+        row = {"tokens": tokens, "rows": sum(counts), "counts": counts, "weight_copies": copies,
+               "unfused_us": round(u_us, 3), "fused_us": round(f_us, 3), "fused_over_unfused": round(f_us / u_us, 4),
+               "bytes": nbytes, "fused_GBps": round(nbytes / f_us * 1e-3, 1), "unfused_GBps": round(nbytes / u_us * 1e-3, 1),
+               "max_abs_diff_fused_vs_unfused": float((a - b).abs().max()), "max_abs_unfused": float(a.abs().max()),
+               "passes": m}
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
+        del unfused, fused
+        torch.cuda.empty_cache()
+    out = {"what": "expert MLP step (gather .. weighted down-projection output): three grouped launches + torch ops vs the two "
+                   "fused launches, hipGraph replays, device-clock stamps, cold caches",
+           "config": {"bits": BITS, "group_size": G, "experts": E, "top_k": TOPK, "dtype": "float16", "K": 4096, "F": 14336,
+                      "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                      "device": torch.cuda.get_device_name(device)},
+           "rows": rows}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def measure(layer, args):
     us, _ = bench.time_graph(layer, args.steps, args.warmup, torch.cuda.synchronize, cold=True, replays=args.replays)
     t = dict(bench.LAST_TIMING)
@@ -105,10 +200,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grouped_moe.json"))
+    ap.add_argument("--mode", choices=["projection", "mlp"], default="projection")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "grouped_moe.json" if args.mode == "projection" else "grouped_moe_fused.json")
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
+    if args.mode == "mlp":
+        return main_mlp(args, device)
     rows = []
     for name, N, K in (("gate_up", 14336, 4096), ("down", 4096, 14336)):
         per_copy = E * ((BITS * N // 16) * K * 2 + N * (K // G) * 2)
