@@ -31,6 +31,10 @@ pair_grad_to_table_grad = ops.pair_grad_to_table_grad
 qgemm_grouped = ops.qgemm_grouped
 qgemm_grouped_glu = ops.qgemm_grouped_glu
 qgemm_grouped_weighted = ops.qgemm_grouped_weighted
+# the routing around them, one launch each: the router's choice [T, k] -> offsets, rows, row_weight, pos, perm (a stable
+# counting sort on the device), and the sorted rows of the down projection summed per token in fp32 with one rounding
+moe_route = ops.moe_route
+moe_combine = ops.moe_combine
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

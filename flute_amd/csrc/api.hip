@@ -1702,6 +1702,30 @@ int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E,
                                            row_weight, Y, num_sms, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
+                    int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
+    if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;
+    if (weight_dtype != FLUTE_F16 && weight_dtype != FLUTE_BF16 && weight_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
+    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
+    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    const int P = T * k;
+    if (P == 0 && !offsets) return FLUTE_OK;                    // no pair and nowhere to write the E + 1 zeros
+    if (P > 0 && (!ids || !perm || !rows || !pos || (weights && !row_weight))) return FLUTE_ERR_NULL;
+    if (!offsets) return FLUTE_ERR_NULL;
+    return moe_route_dispatch(id_dtype, weight_dtype, P, k, E, ids, weights, offsets, perm, rows, row_weight, pos,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
+                      void* out, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    if (T < 0 || k < 0 || E < 0 || N < 0 || N % 8) return FLUTE_ERR_SHAPE;
+    if ((long long)T * k > 0x7fffffffLL || (T > 0 && N > 0 && moe_combine_grid(T, N) == 0)) return FLUTE_ERR_SHAPE;
+    if (T == 0 || N == 0) return FLUTE_OK;
+    if (!offsets || !out || (k > 0 && (!Y || !pos))) return FLUTE_ERR_NULL;
+    return moe_combine_dispatch(dtype, T, k, E, N, Y, pos, offsets, out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -86,6 +86,15 @@ int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int 
 int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
                                     const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
                                     const void* row_weight, void* Y, int num_sms, hipStream_t stream);
+// the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
+// workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
+int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,
+                       int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
+// its end (moe_combine.hip): out[t] = round_T(fp32 sum over the slots of Y[pos[t, j]]), positions outside [0, clamp(offsets[E])) skipped;
+// the grid is tokens x chunks of 1024 columns (0: it does not fit)
+unsigned moe_combine_grid(int T, int N);
+int moe_combine_dispatch(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
+                         void* out, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

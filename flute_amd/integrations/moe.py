@@ -4,11 +4,15 @@
 `flute_amd.qgemm_grouped` (qgemm_grouped.hip); the per-expert row counts never leave the device (`sort_by_expert`
 uses ops of fixed output shape only), so a decode step with changing routing can sit in one captured graph.
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
-its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops.
+its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
+`native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`
+after - become two more launches (`moe_route`, `moe_combine`): four launches and no torch arithmetic, the same bits
+for equal arguments at every top-k, one rounding in the sum over a token's experts.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
     fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
+    four = FluteExperts.from_linears(gates, ups, downs, fused=True, native_routing=True)   # moe_route -> glu -> weighted -> moe_combine
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
@@ -93,7 +97,7 @@ class FluteExperts(torch.nn.Module):
     """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token."""
 
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
-                 fused: bool = False) -> None:
+                 fused: bool = False, native_routing: bool = False) -> None:
         super().__init__()
         if not (gate.num_experts == up.num_experts == down.num_experts):
             raise ValueError("FluteExperts: gate, up and down differ in their number of experts")
@@ -106,14 +110,17 @@ class FluteExperts(torch.nn.Module):
         self.gate, self.up, self.down = gate, up, down
         self.num_experts = gate.num_experts
         self.fused = bool(fused)
+        self.native_routing = bool(native_routing)
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
-                     downs: Sequence[FluteLinear], fused: bool = False) -> "FluteExperts":
+                     downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
-                   GroupedFluteLinear.from_linears(downs), fused=fused)
+                   GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
+        if self.native_routing:
+            return self._forward_native(hidden, topk_ids, topk_weights)
         k = topk_ids.shape[1]
         perm, offsets = sort_by_expert(topk_ids, self.num_experts)
         token = perm // k
@@ -140,3 +147,22 @@ class FluteExperts(torch.nn.Module):
                                              topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
                                              down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)
+
+    def _forward_native(self, hidden, topk_ids, topk_weights):
+        """`moe_route` (moe_route.hip) in place of sort_by_expert and its glue, `moe_combine` (moe_combine.hip) in place
+        of zeros_like + index_add_: the sum over a token's experts is taken in fp32 in slot order and rounded once, and
+        rows no expert served are never read.  Fused: four launches, nothing else."""
+        gate, up, down = self.gate, self.up, self.down
+        offsets, rows, row_weight, pos, _ = flute_amd.moe_route(topk_ids, topk_weights, self.num_experts)
+        if self.fused:
+            num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
+            h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
+                                            up.scales, up.tables2, gate.num_bits, gate.group_size, gate.template_id,
+                                            num_sms, rows=rows)
+            y = flute_amd.qgemm_grouped_weighted(h, offsets, down.weight, down.scales, down.tables2, row_weight,
+                                                 down.num_bits, down.group_size, down.template_id, num_sms)
+        else:
+            x = hidden[rows]
+            h = torch.nn.functional.silu(gate(x, offsets)) * up(x, offsets)
+            y = down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
+        return flute_amd.moe_combine(y, pos, offsets)

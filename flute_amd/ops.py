@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
-plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu` and
-`qgemm_grouped_weighted`.
+plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
+`qgemm_grouped_weighted`, `moe_route` and `moe_combine`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -407,4 +407,90 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
             _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
             x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), rw.data_ptr(), out.data_ptr(),
             num_sms, _stream_ptr(dev)))
+    return out
+
+
+_INDEX_DTYPE_ID = {torch.int32: 0, torch.int64: 1}
+_ROUTE_WEIGHT_DTYPE_ID = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
+MOE_ROUTE_MAX_EXPERTS = 1024            # include/flute_amd.h FLUTE_MOE_ROUTE_MAX_EXPERTS
+MOE_ROUTE_MAX_PAIRS = 1 << 27           # FLUTE_MOE_ROUTE_MAX_PAIRS
+
+
+def _validate_moe_route(topk_ids, topk_weights, num_experts):
+    if topk_ids.ndim != 2:
+        raise ValueError
+    if topk_ids.dtype not in _INDEX_DTYPE_ID:
+        raise TypeError
+    if topk_weights is not None:
+        if topk_weights.dtype not in _ROUTE_WEIGHT_DTYPE_ID:
+            raise TypeError
+        if tuple(topk_weights.shape) != tuple(topk_ids.shape):
+            raise ValueError
+    if not 0 <= num_experts <= MOE_ROUTE_MAX_EXPERTS:
+        raise ValueError
+    if topk_ids.shape[0] * topk_ids.shape[1] >= MOE_ROUTE_MAX_PAIRS:
+        raise ValueError
+
+
+def moe_route(topk_ids: torch.Tensor, topk_weights, num_experts: int):
+    """The routing of a mixture-of-experts step in one launch: from the router's choice `topk_ids` [T, k] (int32 or
+    int64, as `torch.topk` returns them) and `topk_weights` [T, k] (fp16 / bf16 / fp32, or None) to
+    (offsets [E + 1] int32, rows [T k] int32, row_weight [T k] fp32 or None, pos [T, k] int32, perm [T k] int32):
+    `offsets` and `perm` are `integrations.moe.sort_by_expert`'s (a stable sort by expert; ids outside [0, E) behind
+    every expert, past offsets[E]), rows = perm // k is the token of each sorted row (`qgemm_grouped_glu`'s `rows`),
+    row_weight = topk_weights.flatten()[perm].float() (`qgemm_grouped_weighted`'s), pos.flatten()[perm] = arange(T k)
+    (`moe_combine`'s).  E <= 1024, T k < 2^27; a counting sort in one workgroup, meant for decode-sized T k.  The host
+    reads nothing (no synchronise, capturable); a native HIP kernel on the current stream (moe_route.hip); equal
+    arguments give equal bits."""
+    _validate_moe_route(topk_ids, topk_weights, num_experts)
+    dev = topk_ids.device
+    if not all(t.is_cuda and t.device == dev for t in (topk_ids,) + (() if topk_weights is None else (topk_weights,))):
+        raise RuntimeError("flute_amd.moe_route: all tensors must live on the same GPU")
+    T, k = topk_ids.shape
+    P, E = T * k, int(num_experts)
+    ids = topk_ids.contiguous()
+    w = None if topk_weights is None else topk_weights.contiguous()
+    offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    perm = torch.empty(P, dtype=torch.int32, device=dev)
+    rows = torch.empty(P, dtype=torch.int32, device=dev)
+    pos = torch.empty((T, k), dtype=torch.int32, device=dev)
+    row_weight = None if w is None else torch.empty(P, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_moe_route(
+            _INDEX_DTYPE_ID[ids.dtype], 0 if w is None else _ROUTE_WEIGHT_DTYPE_ID[w.dtype], T, k, E, ids.data_ptr(),
+            None if w is None else w.data_ptr(), offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
+            None if row_weight is None else row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
+    return offsets, rows, row_weight, pos, perm
+
+
+def _validate_moe_combine(y, pos, offsets):
+    if not all([y.ndim == 2, pos.ndim == 2, offsets.ndim == 1]):
+        raise ValueError
+    if y.dtype not in _DTYPE_ID or pos.dtype != torch.int32 or offsets.dtype != torch.int32:
+        raise TypeError
+    if y.shape[0] != pos.shape[0] * pos.shape[1] or offsets.shape[0] < 1 or y.shape[1] % 8 != 0:
+        raise ValueError
+    if y.shape[0] >= 2 ** 31:
+        raise ValueError
+
+
+def moe_combine(y: torch.Tensor, pos: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """The end of a mixture-of-experts step in one launch: out[t] = sum over the slots j, ascending, of y[pos[t, j]], in
+    fp32 with one rounding to y.dtype.  `y` [T k, N] are the down projection's rows in sorted order (N % 8 == 0), `pos`
+    [T, k] int32 and `offsets` [E + 1] int32 are `moe_route`'s.  A slot whose position is outside [0, offsets[E]) - an id
+    no expert serves - adds nothing and its row is never read; every element of the [T, N] result is written (a token
+    with no served slot is zeros).  No atomics: equal arguments give equal bits for every k.  No host synchronise; a
+    native HIP kernel on the current stream (moe_combine.hip)."""
+    _validate_moe_combine(y, pos, offsets)
+    dev = y.device
+    if not all(t.is_cuda and t.device == dev for t in (y, pos, offsets)):
+        raise RuntimeError("flute_amd.moe_combine: all tensors must live on the same GPU")
+    T, k = pos.shape
+    N = y.shape[1]
+    yc, p, off = y.contiguous(), pos.contiguous(), offsets.contiguous()
+    out = torch.empty((T, N), dtype=y.dtype, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_moe_combine(
+            _DTYPE_ID[yc.dtype], T, k, off.shape[0] - 1, N, yc.data_ptr(), p.data_ptr(), off.data_ptr(), out.data_ptr(),
+            _stream_ptr(dev)))
     return out

@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 /* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
- *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted (additive: no existing entry point changed, so the number stays)
+ *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype
+ *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -32,7 +33,10 @@ extern "C" {
  * 6 (round 5): flute_plan.one_shot / flute_overrides.one_shot value 4 (lean decode kernel, qgemm_fast.h), flute_debug_timestamp */
 #define FLUTE_AMD_ABI_VERSION 9
 
-enum flute_dtype { FLUTE_F16 = 0, FLUTE_BF16 = 1 };
+/* FLUTE_F32: the routing weights of flute_moe_route only; every other entry point refuses it (FLUTE_ERR_DTYPE) */
+enum flute_dtype { FLUTE_F16 = 0, FLUTE_BF16 = 1, FLUTE_F32 = 2 };
+/* the width of flute_moe_route's expert ids */
+enum flute_index_dtype { FLUTE_I32 = 0, FLUTE_I64 = 1 };
 
 enum flute_status {
     FLUTE_OK = 0,
@@ -309,6 +313,51 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream);
+
+/* The routing of a mixture-of-experts step in ONE launch: from the router's choice to every array the grouped launches
+ * and flute_moe_combine read.  ids [T, k] int32 or int64 (id_dtype: flute_index_dtype; torch.topk returns int64), weights
+ * [T, k] fp16 / bf16 / fp32 (weight_dtype: flute_dtype) or null, E experts.  With P = T k and the pairs (token, slot)
+ * numbered p = token k + slot, all outputs have a fixed shape:
+ *   offsets    [E + 1] int32   offsets[e] = the number of pairs whose id is in [0, e): expert e's rows are
+ *                              [offsets[e], offsets[e + 1]), offsets[E] = the pairs some expert serves
+ *   perm       [P] int32       the pair of sorted row i; a STABLE sort by expert: pairs of one expert in ascending p
+ *   rows       [P] int32       perm[i] / k, the token of sorted row i (flute_qgemm_grouped_glu's `rows`)
+ *   row_weight [P] fp32        (float) weights[perm[i]], exact (flute_qgemm_grouped_weighted's `row_weight`); not written
+ *                              and not looked at when weights is null
+ *   pos        [T, k] int32    the inverse: pos[perm[i]] = i
+ * An id outside [0, E) sorts behind every expert, from offsets[E] on, in ascending p among its like, and still gets its
+ * perm / rows / row_weight / pos entries.  The comparison is made at the ids' own width: an int64 id of 2^32 + 1 is
+ * outside, not expert 1.  offsets, perm are integrations/moe.py sort_by_expert's, value for value.
+ * Integer counting only: a counting sort inside one workgroup of 16 waves (moe_route.hip), each wave on one contiguous
+ * range of the pairs, no atomics on global memory, nothing that depends on scheduling: equal arguments give equal bits.
+ * The host reads neither ids nor weights; the grid is one workgroup whatever (P, E) (hipGraph-capturable, a replay serves
+ * what the arrays then hold).  Correct for every P below FLUTE_MOE_ROUTE_MAX_PAIRS, fast for decode-sized ones: there is
+ * no multi-workgroup form for prefill-sized P.
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE (id_dtype, then weight_dtype - checked with null
+ * weights too); FLUTE_ERR_SHAPE (a negative T / k / E, E > FLUTE_MOE_ROUTE_MAX_EXPERTS, T k >=
+ * FLUTE_MOE_ROUTE_MAX_PAIRS); P == 0 (T == 0 or k == 0) with a null offsets returns FLUTE_OK without a launch; then
+ * FLUTE_ERR_NULL (offsets; with P > 0 also ids, perm, rows, pos, and row_weight when weights is given).  P == 0 with
+ * offsets given is served by the same launch, which then reads no other pointer and writes the E + 1 zeros. */
+#define FLUTE_MOE_ROUTE_MAX_EXPERTS 1024
+#define FLUTE_MOE_ROUTE_MAX_PAIRS (1 << 27) /* 2^31 / 16: a wave's range end, rounded up to 64, stays an int */
+int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
+                    int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream);
+
+/* The end of a mixture-of-experts step: the sorted rows Y [P, N] T of the down projection (flute_qgemm_grouped_weighted's
+ * output), summed per token through pos [T, k] int32 (flute_moe_route's), into out [T, N] T.  Per element:
+ *   served = clamp(offsets[E], 0, P)
+ *   acc = +0.0f;  for j = 0 .. k - 1, ascending:  p = pos[t, j];  if (0 <= p < served) acc += (float) Y[p, n]
+ *   out[t, n] = round_T(acc)
+ * fp32 additions in slot order, ONE rounding.  Every element of out is written - a token with no served slot is zeros -
+ * so out needs no zero fill.  Rows of Y at or past `served` and positions outside [0, P) are never read: the result does
+ * not depend on what the rows no expert served hold.  No atomics: equal arguments give equal bits for every k.  Of
+ * offsets [E + 1] int32 only offsets[E] is read, on the device; the host reads neither it nor pos, and the grid follows
+ * from (T, N) alone (hipGraph-capturable).  A pure stream, 16 bytes per lane (moe_combine.hip).
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE; FLUTE_ERR_SHAPE (a negative T / k / E / N,
+ * N % 8, T k or T * ceil(N / 1024) above 2^31 - 1); T == 0 or N == 0 returns FLUTE_OK without a launch; then
+ * FLUTE_ERR_NULL (offsets, out; Y and pos unless k == 0 - with k == 0 the launch writes out as zeros). */
+int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
+                      void* out, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */

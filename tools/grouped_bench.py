@@ -2,6 +2,7 @@
 
     python tools/grouped_bench.py [--steps 20] [--warmup 5] [--replays 5] [--out profiles/grouped_moe.json]
     python tools/grouped_bench.py --mode mlp [--out profiles/grouped_moe_fused.json]
+    python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -24,11 +25,19 @@ index_add_), by the same method, both forms alternating in one process:
             where(served): FluteExperts.forward as it is without `fused`
   fused     qgemm_grouped_glu reading hidden through the routing index, then qgemm_grouped_weighted: two launches
             (and the cast of the index and the gather of the weights, which the fused forward also runs)
+
+--mode step times the WHOLE FluteExperts(fused=True).forward - routing, the two fused launches, the sum per token - at the
+same shapes and token counts, with `native_routing` off (sort_by_expert and its glue, zeros_like + index_add_: the default
+forward) and on (moe_route, moe_combine), by the same method, the two forms alternating twice in one process, in
+`--processes` fresh processes one after the other.  One more pair of rows leaves the GEMMs out: moe_route + moe_combine
+against sort_by_expert, perm // k, the cast, the weight gather and zeros_like + index_add_ at E = 64, top-8, N = 2048.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
+import tempfile
 
 import torch
 
@@ -186,6 +195,146 @@ def main_mlp(args, device):
     print("wrote", args.out)
 
 
+class Step:
+    """`copies` FluteExperts(fused=True) on random stacks of the --mode mlp shapes; step(i) is one whole forward on set i."""
+
+    def __init__(self, stacks, tokens, device, native):
+        from flute_amd.integrations import moe
+        self.experts = [moe.FluteExperts(g, u, d, fused=True, native_routing=native) for g, u, d in stacks]
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+        self.ids = torch.rand(tokens, E, generator=torch.Generator().manual_seed(tokens)).topk(TOPK, dim=1).indices.to(device)
+        w = torch.rand(tokens, TOPK, device=device, generator=gen)
+        self.weights = (w / w.sum(1, keepdim=True)).to(DTYPE)
+
+    def step(self, i):
+        return self.experts[i % len(self.experts)](self.hidden, self.ids, self.weights)
+
+
+def step_stacks(copies, device):
+    """`copies` sets of gate / up [F, K] and down [K, F] GroupedFluteLinear with random packed bits, shared by both forms."""
+    import flute_amd
+    from flute_amd import utils
+    from flute_amd.integrations import moe
+    K, F = 4096, 14336
+    gen = torch.Generator(device=device).manual_seed(1)
+    tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+    table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
+    t2 = utils.make_qmap2_from_qmap(table).repeat(E, 1, 1, 1)
+
+    def grouped(Kin, N):
+        m = moe.GroupedFluteLinear(E, Kin, N, BITS, G, tid, device, DTYPE)
+        m.weight.copy_(torch.randint(-2 ** 15, 2 ** 15, tuple(m.weight.shape), dtype=torch.int16, device=device, generator=gen))
+        m.scales.copy_((torch.rand(tuple(m.scales.shape), device=device, generator=gen) * 0.02 + 0.005).to(DTYPE))
+        m.tables.copy_(table.repeat(E, 1))
+        m.tables2.copy_(t2)
+        return m
+    return [(grouped(K, F), grouped(K, F), grouped(F, K)) for _ in range(copies)]
+
+
+R_E, R_TOPK, R_N = 64, 8, 2048          # the routing-only rows
+
+
+class RoutingOnly:
+    """The routing around the launches without them: Y [T k, N] stands for the down projection's output."""
+
+    def __init__(self, tokens, device, native):
+        import flute_amd
+        from flute_amd.integrations import moe
+        self.fa, self.moe, self.native = flute_amd, moe, native
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        self.ids = torch.rand(tokens, R_E, generator=torch.Generator().manual_seed(tokens)).topk(R_TOPK, dim=1).indices.to(device)
+        w = torch.rand(tokens, R_TOPK, device=device, generator=gen)
+        self.weights = (w / w.sum(1, keepdim=True)).to(DTYPE)
+        self.hidden = torch.randn(tokens, R_N, device=device, generator=gen).to(DTYPE)
+        self.y = torch.randn(tokens * R_TOPK, R_N, device=device, generator=gen).to(DTYPE)
+
+    def step(self, i):
+        if self.native:
+            offsets, rows, row_weight, pos, _ = self.fa.moe_route(self.ids, self.weights, R_E)
+            return self.fa.moe_combine(self.y, pos, offsets)
+        # FluteExperts.forward / _forward_fused around the two launches, as it is by default
+        perm, offsets = self.moe.sort_by_expert(self.ids, R_E)
+        token = perm // R_TOPK
+        rows, row_weight = token.to(torch.int32), self.weights.reshape(-1)[perm].float()
+        return torch.zeros_like(self.hidden).index_add_(0, token, self.y)
+
+
+def step_row(off, on, args, **head):
+    a, b = off.step(0).float(), on.step(0).float()
+    torch.cuda.synchronize()
+    # two passes of each, alternating; the figure is the mean of each form's two medians
+    m = [measure(layer, args) for layer in (off, on, off, on)]
+    off_us, on_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+    row = dict(head, torch_routing_us=round(off_us, 3), native_routing_us=round(on_us, 3),
+               native_over_torch=round(on_us / off_us, 4), spread=max(p["spread"] for p in m),
+               max_abs_diff_native_vs_torch=float((a - b).abs().max()), max_abs_torch=float(a.abs().max()), passes=m)
+    print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
+    return row
+
+
+def child_step(args, device):
+    """One process's rows, written to args.out."""
+    rows = []
+    per_copy = 3 * E * ((BITS * 14336 // 16) * 4096 * 2 + 14336 * (4096 // G) * 2)
+    copies = max(2, bench.L3_BYTES // per_copy + 2)
+    stacks = step_stacks(copies, device)
+    for tokens in args.tokens:
+        off, on = Step(stacks, tokens, device, native=False), Step(stacks, tokens, device, native=True)
+        rows.append(step_row(off, on, args, what="forward", tokens=tokens, rows=tokens * TOPK, experts=E, top_k=TOPK,
+                             weight_copies=copies))
+    del stacks, off, on
+    torch.cuda.empty_cache()
+    for tokens in args.routing_tokens:
+        off, on = RoutingOnly(tokens, device, native=False), RoutingOnly(tokens, device, native=True)
+        rows.append(step_row(off, on, args, what="routing only", tokens=tokens, rows=tokens * R_TOPK, experts=R_E,
+                             top_k=R_TOPK, N=R_N))
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
+
+
+def main_step(args):
+    """`--processes` fresh child processes one after the other; per row the median of the processes' figures, and the
+    spread: the largest (max - min) / median among the replays of any pass of the row, in any process."""
+    runs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i in range(args.processes):
+            path = os.path.join(tmp, "p%d.json" % i)
+            cmd = [sys.executable, os.path.abspath(__file__), "--mode", "step", "--child", "--out", path, "--steps", str(args.steps),
+                   "--warmup", str(args.warmup), "--replays", str(args.replays), "--tokens", *map(str, args.tokens),
+                   "--routing-tokens", *map(str, args.routing_tokens)]
+            subprocess.run(cmd, check=True)
+            with open(path) as f:
+                runs.append(json.load(f))
+    median = lambda v: sorted(v)[len(v) // 2]
+    rows = []
+    for i, first in enumerate(runs[0]["rows"]):
+        per = [r["rows"][i] for r in runs]
+        off_us, on_us = median([p["torch_routing_us"] for p in per]), median([p["native_routing_us"] for p in per])
+        spread = max(p["spread"] for p in per)
+        row = {k: first[k] for k in first if k in ("what", "tokens", "rows", "experts", "top_k", "N", "weight_copies")}
+        row.update(torch_routing_us=off_us, native_routing_us=on_us, saved_us=round(off_us - on_us, 3),
+                   native_over_torch=round(on_us / off_us, 4), spread=spread,
+                   faster_by_more_than_spread=bool(1 - on_us / off_us > spread),
+                   per_process_torch_us=[p["torch_routing_us"] for p in per],
+                   per_process_native_us=[p["native_routing_us"] for p in per],
+                   max_abs_diff_native_vs_torch=max(p["max_abs_diff_native_vs_torch"] for p in per),
+                   max_abs_torch=first["max_abs_torch"],
+                   replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+    out = {"what": "FluteExperts(fused=True).forward, native_routing off (sort_by_expert + torch glue + zeros_like + index_add_) vs on "
+                   "(moe_route + moe_combine); and the routing alone without the GEMMs; hipGraph replays, device-clock stamps, cold "
+                   "caches; passes per process: off, on, off, on",
+           "config": {"bits": BITS, "group_size": G, "dtype": "float16", "K": 4096, "F": 14336, "steps": args.steps,
+                      "warmup": args.warmup, "replays": args.replays, "processes": args.processes, "device": runs[0]["device"]},
+           "rows": rows}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def measure(layer, args):
     us, _ = bench.time_graph(layer, args.steps, args.warmup, torch.cuda.synchronize, cold=True, replays=args.replays)
     t = dict(bench.LAST_TIMING)
@@ -200,13 +349,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
-    ap.add_argument("--mode", choices=["projection", "mlp"], default="projection")
+    ap.add_argument("--mode", choices=["projection", "mlp", "step"], default="projection")
+    ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step: the routing-only rows")
+    ap.add_argument("--processes", type=int, default=3, help="--mode step: fresh processes, one after the other")
+    ap.add_argument("--child", action="store_true", help="--mode step: one of those processes (internal)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "grouped_moe.json" if args.mode == "projection" else "grouped_moe_fused.json")
+        args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
+                                                   "step": "grouped_moe_routing.json"}[args.mode])
+    if args.mode == "step" and not args.child:
+        return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
+    if args.mode == "step":
+        return child_step(args, device)
     if args.mode == "mlp":
         return main_mlp(args, device)
     rows = []
