@@ -35,6 +35,10 @@ qgemm_grouped_weighted = ops.qgemm_grouped_weighted
 # counting sort on the device), and the sorted rows of the down projection summed per token in fp32 with one rounding
 moe_route = ops.moe_route
 moe_combine = ops.moe_combine
+# the gating in front of them: router logits [T, E] -> (ids, weights) with a defined tie order, one launch; and the same launch
+# carried on through moe_route's sort: from logits to every routing array
+moe_gate = ops.moe_gate
+moe_gate_route = ops.moe_gate_route
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

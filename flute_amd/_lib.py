@@ -6,7 +6,7 @@ the first symbol, loudly, with the build command.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_int, c_size_t, c_uint32, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FLUTE_AMD_LIB: development builds of the same ABI (e.g. the phase-timestamp build)
@@ -66,6 +66,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_weighted": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
     "flute_moe_route": (c_int, [c_int] * 5 + [c_void_p] * 7 + [c_void_p]),
     "flute_moe_combine": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
+    "flute_moe_gate": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 4 + [c_void_p]),
+    "flute_moe_gate_route": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 9 + [c_void_p]),
     "flute_debug_stream_read": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "flute_debug_timestamp": (c_int, [c_void_p, c_void_p]),
 }

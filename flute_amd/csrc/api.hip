@@ -1716,6 +1716,37 @@ int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const v
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+// the refusals flute_moe_gate and flute_moe_gate_route share, in their order: dtype and scoring, then shape
+static int check_moe_gate(int logit_dtype, int T, int E, int k, int scoring) {
+    if (logit_dtype != FLUTE_F16 && logit_dtype != FLUTE_BF16 && logit_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
+    if (scoring != FLUTE_GATE_SOFTMAX && scoring != FLUTE_GATE_SIGMOID) return FLUTE_ERR_DTYPE;
+    if (T < 0 || k < 1 || k > E || k > FLUTE_MOE_GATE_MAX_TOPK || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
+    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    return FLUTE_OK;
+}
+
+int flute_moe_gate(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                   const float* bias, int32_t* ids, float* weights, void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, scoring);
+    if (rc) return rc;
+    if (T == 0) return FLUTE_OK;
+    if (!logits || !ids || !weights) return FLUTE_ERR_NULL;
+    return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_moe_gate_route(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale,
+                         const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets,
+                         int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, scoring);
+    if (rc) return rc;
+    if (T == 0 && !offsets) return FLUTE_OK;                    // no token and nowhere to write the E + 1 zeros
+    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
+    if (!offsets) return FLUTE_ERR_NULL;
+    return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
+                             rows, row_weight, pos, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
                       void* out, void* stream) {
     if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;

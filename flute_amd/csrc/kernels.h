@@ -90,6 +90,11 @@ int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg,
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,
                        int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
+// the gating in front of it (moe_gate.hip): logits [T, E] -> ids [T, k] int32, weights [T, k] fp32, one wave per token; with offsets non-null
+// the routed form: one workgroup of 16 waves gates every token and then runs moe_route's counting sort on what it wrote
+int moe_gate_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                      const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows,
+                      float* row_weight, int32_t* pos, hipStream_t stream);
 // its end (moe_combine.hip): out[t] = round_T(fp32 sum over the slots of Y[pos[t, j]]), positions outside [0, clamp(offsets[E])) skipped;
 // the grid is tokens x chunks of 1024 columns (0: it does not fit)
 unsigned moe_combine_grid(int T, int N);

@@ -1,0 +1,270 @@
+// The gating of a mixture-of-experts step: from the router's logits [T, E] to the k experts of every token, ids [T, k] int32,
+// and their weights [T, k] fp32 (include/flute_amd.h, flute_moe_gate), and in a second form straight on to every array
+// moe_route writes (flute_moe_gate_route): one launch from logits to offsets / perm / rows / row_weight / pos.
+//
+// One wave = one token.  Lane l holds experts l, l + 64, ... in registers: NV = ceil(E / 64) values, a compile-time count per
+// class (1, 2, 4, 8, 16), so the arrays are never indexed by a run-time value and nothing spills.
+//   score   the max and the sum over all experts are wave reductions; every lane ends with the same bits.
+//   key     each expert's key becomes a 32-bit integer whose unsigned order is the order of the floats (NaN as -infinity, -0
+//           as +0); 0 is below every key and marks "no expert here" and "already taken".
+//   choice  k rounds: the wave's maximum key, then the lowest expert that holds it - one ballot per register, the first
+//           register with a hit and the lowest lane in it, which is scalar work: the tie rule is that comparison of indices,
+//           not an accident of the reduction.  The winning lane clears its key.  The winner's score reaches every lane
+//           through a v_readlane, and lane j keeps round j's expert and score: the stores are coalesced.
+//   weight  the sum of the chosen scores is a compensated (Kahan) sum in slot order, made by every lane alike: at k = 64 a plain
+//           running sum would carry up to 63 roundings into every weight of the row.
+// A wave reduction is six exchange steps without LDS: DPP quad_perm (lanes ^ 1, ^ 2), row_half_mirror, row_mirror inside a
+// row of 16, then v_permlane16_swap and v_permlane32_swap across rows.  Every step combines the same two values in both
+// partners, so all 64 lanes hold the same bits afterwards and the order of the additions is fixed.
+// The per-token work is ONE device function, gate_token, which both kernels call: their equal bits rest on it (it is compiled
+// with floating-point contraction off, so the two inlined copies cannot differ by a fused multiply-add).
+//   moe_gate_kernel        4 waves per workgroup, wave w of block b takes token 4 b + w; the grid covers T.
+//   moe_gate_route_kernel  one workgroup of 16 waves (moe_route_kernel's design point): wave w takes tokens w, w + 16, ...,
+//                          then a barrier, then the count / scan / place phases of moe_route_sort.h on the ids and
+//                          weights just written (same CU, workgroup-scope fence before the barrier).
+// No atomics on global memory, plain vector stores, nothing read on the host.
+#include "kernels.h"
+#include "moe_route_sort.h"
+#include "../../include/flute_amd.h"
+
+#include <math.h>
+
+namespace flute_amd {
+
+constexpr int kGateWaves = 4;                   // waves per workgroup of the standalone form
+constexpr int kGateThreads = 64 * kGateWaves;
+
+template <typename L> struct GateLogit;
+template <> struct GateLogit<F16> {
+    typedef uint16_t type;
+    static __device__ __forceinline__ float to_float(uint16_t u) { return Num<F16>::to_float(u); }
+};
+template <> struct GateLogit<BF16> {
+    typedef uint16_t type;
+    static __device__ __forceinline__ float to_float(uint16_t u) { return Num<BF16>::to_float(u); }
+};
+template <> struct GateLogit<float> {
+    typedef float type;
+    static __device__ __forceinline__ float to_float(float f) { return f; }
+};
+
+// ---- the exchange steps of a wave reduction ---------------------------------------------------------------------------------
+// STEP 0 .. 3: the value of the partner lane inside a row of 16 (every lane active: callers keep the wave whole)
+template <int STEP>
+static __device__ __forceinline__ uint32_t row_partner(uint32_t v) {
+    constexpr int ctrl = STEP == 0 ? 0xB1      // quad_perm [1, 0, 3, 2]
+                         : STEP == 1 ? 0x4E    // quad_perm [2, 3, 0, 1]
+                         : STEP == 2 ? 0x141   // row_half_mirror: quads agree by now, so this pairs the two quads of a half
+                                     : 0x140;  // row_mirror: halves agree, this pairs the two halves of the row
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, ctrl, 0xF, 0xF, true);
+}
+
+struct OpMaxF {
+    static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a, b); }
+};
+struct OpAddF {
+    static __device__ __forceinline__ float apply(float a, float b) { return a + b; }
+};
+struct OpMaxU {
+    static __device__ __forceinline__ uint32_t apply(uint32_t a, uint32_t b) { return a > b ? a : b; }
+};
+
+template <typename Op>
+static __device__ __forceinline__ uint32_t wave_reduce_bits(uint32_t v, auto from, auto to) {
+    v = to(Op::apply(from(v), from(row_partner<0>(v))));
+    v = to(Op::apply(from(v), from(row_partner<1>(v))));
+    v = to(Op::apply(from(v), from(row_partner<2>(v))));
+    v = to(Op::apply(from(v), from(row_partner<3>(v))));
+    // rows agree inside themselves; with both operands the same register the swap returns (the even row's, the odd row's) value
+    // of each pair of rows in every lane of the pair, then (the lower half's, the upper half's) in every lane
+    auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    v = to(Op::apply(from(r[0]), from(r[1])));
+    r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return to(Op::apply(from(r[0]), from(r[1])));
+}
+
+template <typename Op>
+static __device__ __forceinline__ float wave_reduce(float v) {
+    return __uint_as_float(wave_reduce_bits<Op>(__float_as_uint(v), [](uint32_t u) { return __uint_as_float(u); },
+                                                [](float f) { return __float_as_uint(f); }));
+}
+
+static __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    return wave_reduce_bits<OpMaxU>(v, [](uint32_t u) { return u; }, [](uint32_t u) { return u; });
+}
+
+// a float as an integer of the same (unsigned) order; NaN ranks as -infinity, -0 as +0; the smallest result is 0x007fffff
+static __device__ __forceinline__ uint32_t ordered_key(float f) {
+    if (!(f == f)) f = -INFINITY;
+    if (f == 0.0f) f = 0.0f;
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// ---- one token, one wave ----------------------------------------------------------------------------------------------------
+// Every lane of the wave calls it with the same arguments (the exchanges need the whole wave).  Writes ids[0 .. k), weights[0 .. k).
+template <typename L, int NV>
+static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::type* __restrict__ logits,
+                                                  const float* __restrict__ bias, int E, int k, int scoring, int renormalize,
+                                                  float scale, int lane, int32_t* ids, float* weights) {
+#pragma clang fp contract(off)
+    float x[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = lane + 64 * i;
+        x[i] = e < E ? GateLogit<L>::to_float(logits[e]) : -INFINITY;
+    }
+
+    // v: what a chosen expert contributes to the weights - u for a renormalised softmax without bias, else the score s
+    float v[NV];
+    if (scoring == FLUTE_GATE_SOFTMAX) {
+        float m = x[0];
+#pragma unroll
+        for (int i = 1; i < NV; ++i) m = fmaxf(m, x[i]);
+        m = wave_reduce<OpMaxF>(m);
+        float part = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            v[i] = lane + 64 * i < E ? expf(x[i] - m) : 0.0f;
+            part += v[i];
+        }
+        if (!renormalize || bias) {
+            const float total = wave_reduce<OpAddF>(part);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[i] = v[i] / total;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) v[i] = 1.0f / (1.0f + expf(-x[i]));
+    }
+
+    uint32_t key[NV];                            // 0: no expert in this slot, or taken
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = lane + 64 * i;
+        const float kf = bias ? v[i] + (e < E ? bias[e] : 0.0f) : x[i];
+        key[i] = e < E ? ordered_key(kf) : 0u;
+    }
+
+    int my_id = 0;
+    float my_v = 0.0f, chosen = 0.0f, lost = 0.0f;      // chosen: the compensated (Kahan) sum of the winners' scores, in slot order
+    for (int j = 0; j < k; ++j) {
+        uint32_t best = key[0];
+#pragma unroll
+        for (int i = 1; i < NV; ++i) best = OpMaxU::apply(best, key[i]);
+        best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(best));   // k <= E: some expert is left, best > 0
+        // the lowest index that holds it: the first register with a hit (its experts come before the next register's), the
+        // lowest lane in it - scalar work on one ballot per register
+        int e = 0;
+#pragma unroll
+        for (int i = NV - 1; i >= 0; --i) {
+            const uint64_t hit = __builtin_amdgcn_ballot_w64(key[i] == best);
+            if (hit) e = 64 * i + (int)__builtin_ctzll(hit);
+        }
+        float mine = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            if (lane + 64 * i == e) {
+                mine = v[i];
+                key[i] = 0u;
+            }
+        }
+        const float won = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(mine), e & 63));
+        const float term = won - lost;
+        const float next = chosen + term;
+        lost = (next - chosen) - term;
+        chosen = next;
+        if (lane == j) {
+            my_id = e;
+            my_v = won;
+        }
+    }
+    if (lane < k) {
+        float w = renormalize ? my_v / chosen : my_v;
+        w = w * scale;
+        ids[lane] = my_id;
+        weights[lane] = w;
+    }
+}
+
+template <typename L, int NV>
+__global__ __launch_bounds__(kGateThreads) void moe_gate_kernel(const typename GateLogit<L>::type* __restrict__ logits,
+                                                                const float* __restrict__ bias, int T, int E, int k,
+                                                                int scoring, int renormalize, float scale,
+                                                                int32_t* __restrict__ ids, float* __restrict__ weights) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = blockIdx.x * kGateWaves + w;          // T k < 2^27, k >= 1: the grid is below 2^25 and t fits an int
+    if (t >= T) return;                                 // the whole wave leaves
+    gate_token<L, NV>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, lane, ids + (size_t)t * k,
+                      weights + (size_t)t * k);
+}
+
+template <typename L, int NV>
+__global__ __launch_bounds__(kRouteThreads) void moe_gate_route_kernel(const typename GateLogit<L>::type* __restrict__ logits,
+                                                                       const float* __restrict__ bias, int T, int E, int k,
+                                                                       int scoring, int renormalize, float scale, int nbits,
+                                                                       int32_t* ids, float* weights,
+                                                                       int32_t* __restrict__ offsets, int32_t* __restrict__ perm,
+                                                                       int32_t* __restrict__ rows, float* __restrict__ row_weight,
+                                                                       int32_t* __restrict__ pos) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int t = w; t < T; t += kRouteWaves)
+        gate_token<L, NV>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, lane, ids + (size_t)t * k,
+                          weights + (size_t)t * k);
+    __threadfence_block();
+    __syncthreads();                                    // every wave's ids and weights are written and visible in the workgroup
+    route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
+}
+
+template <typename L, int NV>
+static int gate_launch(int T, int E, int k, int scoring, int renormalize, float scale, const void* logits, const float* bias,
+                       int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight,
+                       int32_t* pos, hipStream_t stream) {
+    const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(logits);
+    if (!offsets) {
+        const unsigned grid = (unsigned)((T + kGateWaves - 1) / kGateWaves);
+        hipLaunchKernelGGL((moe_gate_kernel<L, NV>), dim3(grid), dim3(kGateThreads), 0, stream, x, bias, T, E, k, scoring,
+                           renormalize, scale, ids, weights);
+    } else {
+        auto kern = moe_gate_route_kernel<L, NV>;
+        const size_t lds = route_lds_bytes(E);
+        if (lds > 65536 &&
+            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return FLUTE_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(kRouteThreads), lds, stream, x, bias, T, E, k, scoring, renormalize, scale,
+                           route_bucket_bits(E), ids, weights, offsets, perm, rows, row_weight, pos);
+    }
+    return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+}
+
+template <typename L>
+static int gate_by_class(int T, int E, int k, int scoring, int renormalize, float scale, const void* logits, const float* bias,
+                         int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight,
+                         int32_t* pos, hipStream_t stream) {
+#define FLUTE_GATE(NV) \
+    return gate_launch<L, NV>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows, row_weight, pos, stream)
+    if (E <= 64) FLUTE_GATE(1);
+    if (E <= 128) FLUTE_GATE(2);
+    if (E <= 256) FLUTE_GATE(4);
+    if (E <= 512) FLUTE_GATE(8);
+    FLUTE_GATE(16);
+#undef FLUTE_GATE
+}
+
+int moe_gate_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                      const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows,
+                      float* row_weight, int32_t* pos, hipStream_t stream) {
+    renormalize = renormalize != 0;
+    if (logit_dtype == FLUTE_F16)
+        return gate_by_class<F16>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
+                                  row_weight, pos, stream);
+    if (logit_dtype == FLUTE_BF16)
+        return gate_by_class<BF16>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
+                                   row_weight, pos, stream);
+    return gate_by_class<float>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
+                                row_weight, pos, stream);
+}
+
+}  // namespace flute_amd

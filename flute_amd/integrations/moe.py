@@ -8,11 +8,18 @@ its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) inst
 `native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`
 after - become two more launches (`moe_route`, `moe_combine`): four launches and no torch arithmetic, the same bits
 for equal arguments at every top-k, one rounding in the sum over a token's experts.
+`FluteExperts.forward_logits` takes what a router produces - logits [T, E] - instead of (topk_ids, topk_weights): the
+softmax / sigmoid, the optional correction bias, the top-k with a defined tie order, the renormalisation and the scale
+are `moe_gate` (moe_gate.hip), and with `native_routing=True` gating and routing are one launch (`moe_gate_route`), four
+launches from logits.  `FluteSparseMoeBlock` is the whole sparse-MoE block: the router's dense GEMM (a torch op) and
+`forward_logits`.  DeepSeek's group-limited selection (n_group, topk_group) is not covered: the choice is over all experts.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
     fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
     four = FluteExperts.from_linears(gates, ups, downs, fused=True, native_routing=True)   # moe_route -> glu -> weighted -> moe_combine
+    out = four.forward_logits(hidden, router_logits, top_k=2, renormalize=True)            # moe_gate_route -> glu -> weighted -> moe_combine
+    block = FluteSparseMoeBlock(router_weight, four, top_k=2, renormalize=True)             # [E, K] router, out = block(hidden)
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
@@ -134,6 +141,23 @@ class FluteExperts(torch.nn.Module):
         y = torch.where(served[:, None], y, torch.zeros_like(y))
         return torch.zeros_like(hidden).index_add_(0, token, y)
 
+    def forward_logits(self, hidden: torch.Tensor, router_logits: torch.Tensor, top_k: int, scoring: str = "softmax",
+                       renormalize: bool = False, bias=None, scale: float = 1.0) -> torch.Tensor:
+        """The forward from the router's logits [T, E] (fp16 / bf16 / fp32); the gating is `flute_amd.moe_gate`'s contract
+        (scoring "softmax" / "sigmoid", the optional selection `bias` [E] fp32, ties to the lower expert, `renormalize`,
+        `scale`).  With `native_routing` gating and routing are one launch, `moe_gate_route`, and the forward is
+        moe_gate_route -> glu -> weighted -> moe_combine (fused): four launches from logits.  Without it `moe_gate` feeds
+        the existing forward.  Either way the result is bit for bit `forward(hidden, *moe_gate(...))`.  Group-limited
+        selection (n_group, topk_group) is not covered."""
+        if router_logits.shape[1] != self.num_experts:
+            raise ValueError("FluteExperts.forward_logits: router_logits must be [T, num_experts]")
+        if not self.native_routing:
+            ids, weights = flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale)
+            return self.forward(hidden, ids, weights)
+        _, _, offsets, rows, row_weight, pos, _ = flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring,
+                                                                           renormalize, bias, scale)
+        return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
         """Two launches (qgemm_grouped_fused.h): silu(gate(x)) * up(x) with the rows of `hidden` read through the
         routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
@@ -152,8 +176,12 @@ class FluteExperts(torch.nn.Module):
         """`moe_route` (moe_route.hip) in place of sort_by_expert and its glue, `moe_combine` (moe_combine.hip) in place
         of zeros_like + index_add_: the sum over a token's experts is taken in fp32 in slot order and rounded once, and
         rows no expert served are never read.  Fused: four launches, nothing else."""
-        gate, up, down = self.gate, self.up, self.down
         offsets, rows, row_weight, pos, _ = flute_amd.moe_route(topk_ids, topk_weights, self.num_experts)
+        return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+
+    def _forward_routed(self, hidden, offsets, rows, row_weight, pos):
+        """The launches behind the routing arrays, whichever kernel wrote them (`moe_route` or `moe_gate_route`)."""
+        gate, up, down = self.gate, self.up, self.down
         if self.fused:
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
             h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
@@ -166,3 +194,38 @@ class FluteExperts(torch.nn.Module):
             h = torch.nn.functional.silu(gate(x, offsets)) * up(x, offsets)
             y = down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
         return flute_amd.moe_combine(y, pos, offsets)
+
+
+class FluteSparseMoeBlock(torch.nn.Module):
+    """A whole sparse-MoE block: router, gating, experts.  forward(hidden [T, K]) is
+    `experts.forward_logits(F.linear(hidden, router_weight), top_k, ...)`, bit for bit.  `router_weight` [E, K] is the
+    router's dense matrix; its GEMM stays a dense torch op (E is 8 .. 256 columns: nothing to quantise or fuse), and
+    everything behind it is the module's own kernels - with `FluteExperts(fused=True, native_routing=True)` four
+    launches.  `scoring`, `renormalize`, `bias` (the selection bias [E] fp32, kept as a buffer) and `scale` are
+    `flute_amd.moe_gate`'s.  Group-limited selection (DeepSeek's n_group / topk_group) is not covered."""
+
+    def __init__(self, router_weight: torch.Tensor, experts: FluteExperts, top_k: int, scoring: str = "softmax",
+                 renormalize: bool = False, bias=None, scale: float = 1.0) -> None:
+        super().__init__()
+        if router_weight.ndim != 2 or router_weight.shape[0] != experts.num_experts or \
+                router_weight.shape[1] != experts.gate.in_features:
+            raise ValueError("FluteSparseMoeBlock: router_weight must be [num_experts, in_features]")
+        if scoring not in ("softmax", "sigmoid"):
+            raise ValueError("FluteSparseMoeBlock: scoring is 'softmax' or 'sigmoid'")
+        if not 1 <= top_k <= min(experts.num_experts, flute_amd.ops.MOE_GATE_MAX_TOPK):
+            raise ValueError("FluteSparseMoeBlock: 1 <= top_k <= min(num_experts, 64)")
+        if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (experts.num_experts,)):
+            raise ValueError("FluteSparseMoeBlock: bias must be [num_experts] fp32")
+        self.experts = experts
+        self.register_buffer("router_weight", router_weight)
+        self.register_buffer("bias", bias)
+        self.top_k, self.scoring, self.renormalize, self.scale = int(top_k), scoring, bool(renormalize), float(scale)
+
+    def forward(self, hidden: torch.Tensor) -> torch.Tensor:
+        logits = torch.nn.functional.linear(hidden, self.router_weight)
+        return self.experts.forward_logits(hidden, logits, self.top_k, self.scoring, self.renormalize, self.bias,
+                                           self.scale)
+
+    def extra_repr(self) -> str:
+        return (f"top_k={self.top_k}, scoring={self.scoring}, renormalize={self.renormalize}, scale={self.scale}, "
+                f"bias={self.bias is not None}")

@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `moe_route` and `moe_combine`.
+`qgemm_grouped_weighted`, `moe_route`, `moe_combine`, `moe_gate` and `moe_gate_route`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -461,6 +461,83 @@ def moe_route(topk_ids: torch.Tensor, topk_weights, num_experts: int):
             None if w is None else w.data_ptr(), offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
             None if row_weight is None else row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
     return offsets, rows, row_weight, pos, perm
+
+
+_GATE_SCORING_ID = {"softmax": 0, "sigmoid": 1}     # include/flute_amd.h flute_gate_scoring
+MOE_GATE_MAX_TOPK = 64                              # FLUTE_MOE_GATE_MAX_TOPK
+
+
+def _validate_moe_gate(logits, k, scoring, bias, num_experts=None):
+    if logits.ndim != 2:
+        raise ValueError
+    if logits.dtype not in _ROUTE_WEIGHT_DTYPE_ID:
+        raise TypeError
+    if scoring not in _GATE_SCORING_ID:
+        raise ValueError
+    T, E = logits.shape
+    if num_experts is not None and num_experts != E:
+        raise ValueError
+    if bias is not None:
+        if bias.dtype != torch.float32:
+            raise TypeError
+        if tuple(bias.shape) != (E,):
+            raise ValueError
+    if not 1 <= k <= min(E, MOE_GATE_MAX_TOPK) or E > MOE_ROUTE_MAX_EXPERTS:
+        raise ValueError
+    if T * k >= MOE_ROUTE_MAX_PAIRS:
+        raise ValueError
+
+
+def _moe_gate_call(name, logits, k, scoring, renormalize, bias, scale, routed):
+    dev = logits.device
+    if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
+        raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
+    T, E = logits.shape
+    k = int(k)
+    x = logits.contiguous()
+    b = None if bias is None else bias.contiguous()
+    ids = torch.empty((T, k), dtype=torch.int32, device=dev)
+    weights = torch.empty((T, k), dtype=torch.float32, device=dev)
+    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale),
+            x.data_ptr(), None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
+    with torch.cuda.device(dev):
+        if not routed:
+            _lib.check(_lib.get().flute_moe_gate(*head, _stream_ptr(dev)))
+            return ids, weights
+        P = T * k
+        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        perm = torch.empty(P, dtype=torch.int32, device=dev)
+        rows = torch.empty(P, dtype=torch.int32, device=dev)
+        row_weight = torch.empty(P, dtype=torch.float32, device=dev)
+        pos = torch.empty((T, k), dtype=torch.int32, device=dev)
+        _lib.check(_lib.get().flute_moe_gate_route(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
+                                                   row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
+    return ids, weights, offsets, rows, row_weight, pos, perm
+
+
+def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
+             scale: float = 1.0):
+    """The gating of a mixture-of-experts step in one launch: from the router's `logits` [T, E] (fp16 / bf16 / fp32) to
+    (ids [T, k] int32, weights [T, k] fp32) - what `moe_route` takes.  In fp32: the score s of an expert is the softmax
+    over all E logits (`scoring="softmax"`) or 1 / (1 + exp(-x)) (`"sigmoid"`); slot j holds the expert with the j-th
+    largest key, equal keys in ascending expert index (a total order: unlike `torch.topk`, ties are defined), where the
+    key is the logit itself or, with `bias` [E] fp32 (DeepSeek-V3's correction bias), s + bias - the bias decides the
+    choice only; the weight is s, with `renormalize` divided by the sum of the k chosen scores, then times `scale`.
+    1 <= k <= min(E, 64), E <= 1024, T k < 2^27.  DeepSeek's group-limited selection (n_group, topk_group) is not
+    covered.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
+    stream (moe_gate.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
+    _validate_moe_gate(logits, k, scoring, bias)
+    return _moe_gate_call("moe_gate", logits, k, scoring, renormalize, bias, scale, routed=False)
+
+
+def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str = "softmax", renormalize: bool = False,
+                   bias=None, scale: float = 1.0):
+    """`moe_gate` and `moe_route` in one launch: (ids, weights, offsets, rows, row_weight, pos, perm), the first two
+    bit for bit `moe_gate(logits, k, ...)`'s and the other five bit for bit `moe_route(ids, weights, E)`'s.
+    `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves gates the tokens and sorts the
+    pairs: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
+    _validate_moe_gate(logits, k, scoring, bias, num_experts)
+    return _moe_gate_call("moe_gate_route", logits, k, scoring, renormalize, bias, scale, routed=True)
 
 
 def _validate_moe_combine(y, pos, offsets):

@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 /* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
- *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype
+ *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
+ *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring
  *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -33,10 +34,13 @@ extern "C" {
  * 6 (round 5): flute_plan.one_shot / flute_overrides.one_shot value 4 (lean decode kernel, qgemm_fast.h), flute_debug_timestamp */
 #define FLUTE_AMD_ABI_VERSION 9
 
-/* FLUTE_F32: the routing weights of flute_moe_route only; every other entry point refuses it (FLUTE_ERR_DTYPE) */
+/* FLUTE_F32: the routing weights of flute_moe_route and the router logits of flute_moe_gate / flute_moe_gate_route only; every
+ * other entry point refuses it (FLUTE_ERR_DTYPE) */
 enum flute_dtype { FLUTE_F16 = 0, FLUTE_BF16 = 1, FLUTE_F32 = 2 };
 /* the width of flute_moe_route's expert ids */
 enum flute_index_dtype { FLUTE_I32 = 0, FLUTE_I64 = 1 };
+/* how flute_moe_gate / flute_moe_gate_route turn a router logit into a score */
+enum flute_gate_scoring { FLUTE_GATE_SOFTMAX = 0, FLUTE_GATE_SIGMOID = 1 };
 
 enum flute_status {
     FLUTE_OK = 0,
@@ -342,6 +346,48 @@ int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E,
 #define FLUTE_MOE_ROUTE_MAX_PAIRS (1 << 27) /* 2^31 / 16: a wave's range end, rounded up to 64, stays an int */
 int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
                     int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream);
+
+/* The gating of a mixture-of-experts step in ONE launch: from the router's logits [T, E] fp16 / bf16 / fp32 (logit_dtype:
+ * flute_dtype, FLUTE_F32 included) to the k experts each token goes to, ids [T, k] int32, and their weights [T, k] fp32 -
+ * exactly what flute_moe_route accepts (FLUTE_I32, FLUTE_F32).  bias [E] fp32 or null.  Everything is computed in fp32.
+ *   score      x_e = (float) logits[t, e].  FLUTE_GATE_SOFTMAX: m = max_e x_e, u_e = exp(x_e - m), s_e = u_e / sum over ALL e of u_e.
+ *              FLUTE_GATE_SIGMOID: s_e = 1 / (1 + exp(-x_e)).
+ *   key        without bias the key of expert e is x_e itself (both scorings increase with x, so no rounding of a probability can
+ *              make or break a tie); with bias it is s_e + bias[e] in fp32 (the "correction bias" of DeepSeek-V3 / GLM: it decides
+ *              the choice only and never enters a weight).  A NaN key compares as -infinity (and -0 as +0).
+ *   choice     slot j holds the expert with the j-th largest key, equal keys in ascending expert index: a total order, so ids is
+ *              defined value for value and never holds an expert twice.
+ *   weight     w_j = s_{ids[j]}; with renormalize (any nonzero value) w_j = s_{ids[j]} / (s_{ids[0]} + ... + s_{ids[k-1]}), a
+ *              compensated sum taken in slot order - for a softmax without bias as u_{ids[j]} / (the same sum of u): the sum
+ *              over all E is then not formed.  Then w_j = w_j * scale (one more rounding; scale = 1 changes nothing).  A row in
+ *              which every chosen score is 0 or not finite gets whatever this arithmetic gives (a division by zero, NaN); only
+ *              its ids are defined.
+ * Limits: 1 <= k <= min(E, FLUTE_MOE_GATE_MAX_TOPK), E <= FLUTE_MOE_ROUTE_MAX_EXPERTS, T k < FLUTE_MOE_ROUTE_MAX_PAIRS.
+ * DeepSeek's group-limited selection (n_group, topk_group) is out of scope: the choice is over all E experts.
+ * One wave per token, lane l holding experts l, l + 64, ... in registers; the max, the sum and the k rounds of "largest key,
+ * lowest index" are wave reductions in a fixed order and ballots, without LDS (moe_gate.hip).  The host reads nothing, the grid follows from T
+ * alone (hipGraph-capturable), no atomics, plain vector stores: equal arguments give equal bits, and a token's ids and weights
+ * depend neither on T nor on the row it sits in.
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE (logit_dtype, then scoring); FLUTE_ERR_SHAPE (a negative
+ * T, k < 1, k > E, k > FLUTE_MOE_GATE_MAX_TOPK, E > FLUTE_MOE_ROUTE_MAX_EXPERTS, T k >= FLUTE_MOE_ROUTE_MAX_PAIRS); T == 0 returns
+ * FLUTE_OK without a launch; then FLUTE_ERR_NULL (logits, ids, weights; bias is optional). */
+#define FLUTE_MOE_GATE_MAX_TOPK 64
+int flute_moe_gate(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                   const float* bias, int32_t* ids, float* weights, void* stream);
+
+/* flute_moe_gate and flute_moe_route in ONE launch: a decode step goes from the router's logits to every routing array.  It
+ * writes ids and weights exactly as flute_moe_gate does, and offsets, perm, rows, row_weight, pos exactly as
+ * flute_moe_route(FLUTE_I32, FLUTE_F32, T, k, E, ids, weights, ...) then writes on them: bit for bit the two-call sequence (both
+ * forms run the same per-token device function and the same counting sort).  One workgroup of 16 waves, flute_moe_route's design
+ * point: its waves loop over the tokens, and after a barrier the count / scan / place phases run on what they wrote.  Correct for
+ * every T the limits admit, fast for decode-sized ones.  Everything else - the arithmetic, the limits, the properties - is
+ * flute_moe_gate's.
+ * Refusals in the same order: FLUTE_ERR_DTYPE; FLUTE_ERR_SHAPE; T == 0 with a null offsets returns FLUTE_OK without a launch;
+ * then FLUTE_ERR_NULL (offsets; with T > 0 also logits, ids, weights, perm, rows, row_weight, pos).  T == 0 with offsets given is
+ * served by the same launch, which then reads no other pointer and writes the E + 1 zeros, as flute_moe_route does. */
+int flute_moe_gate_route(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale,
+                         const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets,
+                         int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream);
 
 /* The end of a mixture-of-experts step: the sorted rows Y [P, N] T of the down projection (flute_qgemm_grouped_weighted's
  * output), summed per token through pos [T, k] int32 (flute_moe_route's), into out [T, N] T.  Per element:

@@ -3,6 +3,7 @@
     python tools/grouped_bench.py [--steps 20] [--warmup 5] [--replays 5] [--out profiles/grouped_moe.json]
     python tools/grouped_bench.py --mode mlp [--out profiles/grouped_moe_fused.json]
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
+    python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -31,6 +32,12 @@ same shapes and token counts, with `native_routing` off (sort_by_expert and its 
 forward) and on (moe_route, moe_combine), by the same method, the two forms alternating twice in one process, in
 `--processes` fresh processes one after the other.  One more pair of rows leaves the GEMMs out: moe_route + moe_combine
 against sort_by_expert, perm // k, the cast, the weight gather and zeros_like + index_add_ at E = 64, top-8, N = 2048.
+
+--mode gate times the step from the router's logits, by --mode step's method.  Gating alone: the torch chain models run
+today (Mixtral's softmax -> topk -> renormalise at E = 8, top-2 and E = 64, top-8; DeepSeek-V3's sigmoid -> + bias -> topk ->
+gather -> renormalise -> scale at E = 256, top-8) followed by moe_route - the best the code before moe_gate offers - against
+one moe_gate_route launch, fp16 logits.  The whole block: the router GEMM, that chain and
+FluteExperts(fused=True, native_routing=True).forward against FluteSparseMoeBlock on the same experts, at --mode step's shape.
 """
 import argparse
 import json
@@ -300,7 +307,7 @@ def main_step(args):
     with tempfile.TemporaryDirectory() as tmp:
         for i in range(args.processes):
             path = os.path.join(tmp, "p%d.json" % i)
-            cmd = [sys.executable, os.path.abspath(__file__), "--mode", "step", "--child", "--out", path, "--steps", str(args.steps),
+            cmd = [sys.executable, os.path.abspath(__file__), "--mode", args.mode, "--child", "--out", path, "--steps", str(args.steps),
                    "--warmup", str(args.warmup), "--replays", str(args.replays), "--tokens", *map(str, args.tokens),
                    "--routing-tokens", *map(str, args.routing_tokens)]
             subprocess.run(cmd, check=True)
@@ -312,7 +319,8 @@ def main_step(args):
         per = [r["rows"][i] for r in runs]
         off_us, on_us = median([p["torch_routing_us"] for p in per]), median([p["native_routing_us"] for p in per])
         spread = max(p["spread"] for p in per)
-        row = {k: first[k] for k in first if k in ("what", "tokens", "rows", "experts", "top_k", "N", "weight_copies")}
+        row = {k: first[k] for k in first if k in ("what", "tokens", "rows", "experts", "top_k", "N", "weight_copies", "scoring",
+                                                   "bias")}
         row.update(torch_routing_us=off_us, native_routing_us=on_us, saved_us=round(off_us - on_us, 3),
                    native_over_torch=round(on_us / off_us, 4), spread=spread,
                    faster_by_more_than_spread=bool(1 - on_us / off_us > spread),
@@ -323,9 +331,14 @@ def main_step(args):
                    replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
         rows.append(row)
         print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
-    out = {"what": "FluteExperts(fused=True).forward, native_routing off (sort_by_expert + torch glue + zeros_like + index_add_) vs on "
-                   "(moe_route + moe_combine); and the routing alone without the GEMMs; hipGraph replays, device-clock stamps, cold "
-                   "caches; passes per process: off, on, off, on",
+    what = {"step": "FluteExperts(fused=True).forward, native_routing off (sort_by_expert + torch glue + zeros_like + index_add_) vs on "
+                    "(moe_route + moe_combine); and the routing alone without the GEMMs; hipGraph replays, device-clock stamps, cold "
+                    "caches; passes per process: off, on, off, on",
+            "gate": "from router logits: 'torch' = the models' torch gating chain (softmax / sigmoid, topk, renormalise) + moe_route, "
+                    "'native' = one moe_gate_route launch; and the whole block (router GEMM, gating, "
+                    "FluteExperts(fused=True, native_routing=True)) with the chain vs FluteSparseMoeBlock; hipGraph replays, "
+                    "device-clock stamps, cold caches; passes per process: torch, native, torch, native"}[args.mode]
+    out = {"what": what,
            "config": {"bits": BITS, "group_size": G, "dtype": "float16", "K": 4096, "F": 14336, "steps": args.steps,
                       "warmup": args.warmup, "replays": args.replays, "processes": args.processes, "device": runs[0]["device"]},
            "rows": rows}
@@ -333,6 +346,80 @@ def main_step(args):
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", args.out)
+
+
+GATE_SHAPES = [(8, 2, "softmax", False, 1.0), (64, 8, "softmax", False, 1.0), (256, 8, "sigmoid", True, 2.5)]
+
+
+def torch_gate(logits, k, scoring, bias, scale):
+    """The gating chain of the models' own code, with renormalisation: softmax (Mixtral, Qwen-MoE) or sigmoid with the
+    selection bias (DeepSeek-V3)."""
+    if scoring == "softmax":
+        w, ids = torch.topk(torch.softmax(logits, dim=1, dtype=torch.float32), k, dim=1)
+    else:
+        s = torch.sigmoid(logits.float())
+        ids = torch.topk(s if bias is None else s + bias, k, dim=1).indices
+        w = s.gather(1, ids)
+    w = w / w.sum(dim=1, keepdim=True)
+    return ids, (w if scale == 1.0 else w * scale)
+
+
+class GateOnly:
+    """From logits [T, E] fp16 to the routing arrays; step(i) returns `offsets`."""
+
+    def __init__(self, tokens, shape, device, native):
+        import flute_amd
+        self.fa, self.native = flute_amd, native
+        self.E, self.k, self.scoring, with_bias, self.scale = shape
+        gen = torch.Generator(device=device).manual_seed(tokens + self.E)
+        self.logits = (torch.randn(tokens, self.E, device=device, generator=gen) * 2).to(DTYPE)
+        self.bias = torch.randn(self.E, device=device, generator=gen) * 0.1 if with_bias else None
+
+    def step(self, i):
+        if self.native:
+            return self.fa.moe_gate_route(self.logits, self.k, self.E, self.scoring, True, self.bias, self.scale)[2]
+        ids, w = torch_gate(self.logits, self.k, self.scoring, self.bias, self.scale)
+        return self.fa.moe_route(ids, w, self.E)[0]
+
+
+class Block:
+    """The whole sparse-MoE block on `copies` FluteExperts(fused=True, native_routing=True): router GEMM, gating, experts."""
+
+    def __init__(self, stacks, tokens, device, native):
+        from flute_amd.integrations import moe
+        self.native = native
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+        self.router = (torch.randn(E, 4096, device=device, generator=gen) * 0.02).to(DTYPE)
+        self.experts = [moe.FluteExperts(g, u, d, fused=True, native_routing=True) for g, u, d in stacks]
+        self.blocks = [moe.FluteSparseMoeBlock(self.router, x, TOPK, renormalize=True) for x in self.experts]
+
+    def step(self, i):
+        c = i % len(self.experts)
+        if self.native:
+            return self.blocks[c](self.hidden)
+        logits = torch.nn.functional.linear(self.hidden, self.router)
+        ids, w = torch_gate(logits, TOPK, "softmax", None, 1.0)
+        return self.experts[c](self.hidden, ids, w)
+
+
+def child_gate(args, device):
+    """One process's rows, written to args.out."""
+    rows = []
+    for shape in GATE_SHAPES:
+        for tokens in args.routing_tokens:
+            off, on = GateOnly(tokens, shape, device, native=False), GateOnly(tokens, shape, device, native=True)
+            rows.append(step_row(off, on, args, what="gating + routing", tokens=tokens, rows=tokens * shape[1], experts=shape[0],
+                                 top_k=shape[1], scoring=shape[2], bias=shape[3]))
+    per_copy = 3 * E * ((BITS * 14336 // 16) * 4096 * 2 + 14336 * (4096 // G) * 2)
+    copies = max(2, bench.L3_BYTES // per_copy + 2)
+    stacks = step_stacks(copies, device)
+    for tokens in args.tokens:
+        off, on = Block(stacks, tokens, device, native=False), Block(stacks, tokens, device, native=True)
+        rows.append(step_row(off, on, args, what="block", tokens=tokens, rows=tokens * TOPK, experts=E, top_k=TOPK,
+                             scoring="softmax", bias=False, weight_copies=copies))
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
 def measure(layer, args):
@@ -349,21 +436,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
-    ap.add_argument("--mode", choices=["projection", "mlp", "step"], default="projection")
-    ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step: the routing-only rows")
-    ap.add_argument("--processes", type=int, default=3, help="--mode step: fresh processes, one after the other")
-    ap.add_argument("--child", action="store_true", help="--mode step: one of those processes (internal)")
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate"], default="projection")
+    ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
+    ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
+    ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
-                                                   "step": "grouped_moe_routing.json"}[args.mode])
-    if args.mode == "step" and not args.child:
+                                                   "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json"}[args.mode])
+    if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     if args.mode == "step":
         return child_step(args, device)
+    if args.mode == "gate":
+        return child_gate(args, device)
     if args.mode == "mlp":
         return main_mlp(args, device)
     rows = []
