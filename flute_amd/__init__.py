@@ -39,6 +39,8 @@ moe_combine = ops.moe_combine
 # carried on through moe_route's sort: from logits to every routing array
 moe_gate = ops.moe_gate
 moe_gate_route = ops.moe_gate_route
+moe_gate_limited = ops.moe_gate_limited
+moe_gate_route_limited = ops.moe_gate_route_limited
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

@@ -22,6 +22,16 @@
 //   moe_gate_route_kernel  one workgroup of 16 waves (moe_route_kernel's design point): wave w takes tokens w, w + 16, ...,
 //                          then a barrier, then the count / scan / place phases of moe_route_sort.h on the ids and
 //                          weights just written (same CU, workgroup-scope fence before the barrier).
+// Group-limited selection (flute_moe_gate_limited / flute_moe_gate_route_limited) is the same device function with one more stage
+// between key and choice, compiled in by its LIMITED parameter (the unlimited kernels instantiate it without: their code is what
+// it was):
+//   groups  a wave-uniform loop over the n_group groups.  Group g is experts g gs .. (g + 1) gs - 1, a run of lanes that may
+//           straddle registers, so each pass is a wave maximum of the keys under the mask lo <= e < hi.  For the top-2 sum a
+//           second maximum follows with the lowest holder of the first left out; the two come back from key to float order and
+//           are added once.  Lane g keeps group g's key.
+//   pick    topk_group rounds of "largest group key, lowest lane by ballot"; each winner's experts are marked allowed, and
+//           afterwards the key of every expert not allowed becomes 0, "no expert here": the k rounds run unchanged.
+//   moe_gate_limited_kernel / moe_gate_route_limited_kernel are the two kernels above with these arguments.
 // No atomics on global memory, plain vector stores, nothing read on the host.
 #include "kernels.h"
 #include "moe_route_sort.h"
@@ -101,12 +111,77 @@ static __device__ __forceinline__ uint32_t ordered_key(float f) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// the float an ordered key stands for (a NaN comes back as -infinity, -0 as +0)
+static __device__ __forceinline__ float key_value(uint32_t key) {
+    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+// The group stage of the group-limited selection: bit i of the result says that this lane's expert lane + 64 i belongs to one of the
+// topk_group best groups.  key: the experts' keys (0 past E); c: what FLUTE_GATE_GROUP_TOP2SUM adds up, s (+ bias).  Every lane calls
+// it with the same n_group, gs, topk_group, group_score.
+template <int NV>
+static __device__ __forceinline__ uint32_t allowed_by_group(const uint32_t (&key)[NV], const float (&c)[NV], int n_group, int gs,
+                                                            int topk_group, int group_score, int lane) {
+#pragma clang fp contract(off)
+    uint32_t ckey[NV];                           // what a group is ranked by, per expert, in key order
+#pragma unroll
+    for (int i = 0; i < NV; ++i) ckey[i] = group_score == FLUTE_GATE_GROUP_TOP2SUM ? ordered_key(c[i]) : key[i];
+
+    uint32_t gkey = 0u;                          // lane g: group g's key; 0: no group here, or taken (a group key is >= 0x007fffff)
+    for (int g = 0; g < n_group; ++g) {
+        const int lo = g * gs, hi = lo + gs;     // hi <= E: every expert of a group exists
+        uint32_t best = 0u;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = lane + 64 * i;
+            if (e >= lo && e < hi) best = OpMaxU::apply(best, ckey[i]);
+        }
+        best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(best));
+        uint32_t gk = best;
+        if (group_score == FLUTE_GATE_GROUP_TOP2SUM) {
+            // the lowest expert that holds the maximum is left out of the second maximum (an equal value elsewhere stays in)
+            int first = 0;
+#pragma unroll
+            for (int i = NV - 1; i >= 0; --i) {
+                const int e = lane + 64 * i;
+                const uint64_t hit = __builtin_amdgcn_ballot_w64(e >= lo && e < hi && ckey[i] == best);
+                if (hit) first = 64 * i + (int)__builtin_ctzll(hit);
+            }
+            uint32_t second = 0u;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int e = lane + 64 * i;
+                if (e >= lo && e < hi && e != first) second = OpMaxU::apply(second, ckey[i]);
+            }
+            second = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(second));      // gs >= 2: an expert is left
+            gk = ordered_key(key_value(best) + key_value(second));
+        }
+        if (lane == g) gkey = gk;
+    }
+
+    uint32_t allowed = 0u;
+    for (int j = 0; j < topk_group; ++j) {
+        const uint32_t best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(gkey));   // topk_group <= n_group: a group is left
+        const int g = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(gkey == best));
+        if (lane == g) gkey = 0u;
+        const int lo = g * gs, hi = lo + gs;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = lane + 64 * i;
+            if (e >= lo && e < hi) allowed |= 1u << i;
+        }
+    }
+    return allowed;
+}
+
 // ---- one token, one wave ----------------------------------------------------------------------------------------------------
 // Every lane of the wave calls it with the same arguments (the exchanges need the whole wave).  Writes ids[0 .. k), weights[0 .. k).
-template <typename L, int NV>
+// LIMITED: the group stage is compiled in and n_group, gs = E / n_group, topk_group, group_score are read; without it they are not.
+template <typename L, int NV, bool LIMITED>
 static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::type* __restrict__ logits,
                                                   const float* __restrict__ bias, int E, int k, int scoring, int renormalize,
-                                                  float scale, int lane, int32_t* ids, float* weights) {
+                                                  float scale, int n_group, int gs, int topk_group, int group_score, int lane,
+                                                  int32_t* ids, float* weights) {
 #pragma clang fp contract(off)
     float x[NV];
 #pragma unroll
@@ -128,7 +203,8 @@ static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::t
             v[i] = lane + 64 * i < E ? expf(x[i] - m) : 0.0f;
             part += v[i];
         }
-        if (!renormalize || bias) {
+        // (the top-2 sum of a group is a sum of normalised scores: that form always divides)
+        if (!renormalize || bias || (LIMITED && group_score == FLUTE_GATE_GROUP_TOP2SUM)) {
             const float total = wave_reduce<OpAddF>(part);
 #pragma unroll
             for (int i = 0; i < NV; ++i) v[i] = v[i] / total;
@@ -146,13 +222,26 @@ static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::t
         key[i] = e < E ? ordered_key(kf) : 0u;
     }
 
+    if constexpr (LIMITED) {
+        float c[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = lane + 64 * i;
+            c[i] = bias ? v[i] + (e < E ? bias[e] : 0.0f) : v[i];
+        }
+        const uint32_t allowed = allowed_by_group<NV>(key, c, n_group, gs, topk_group, group_score, lane);
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (!((allowed >> i) & 1u)) key[i] = 0u;
+    }
+
     int my_id = 0;
     float my_v = 0.0f, chosen = 0.0f, lost = 0.0f;      // chosen: the compensated (Kahan) sum of the winners' scores, in slot order
     for (int j = 0; j < k; ++j) {
         uint32_t best = key[0];
 #pragma unroll
         for (int i = 1; i < NV; ++i) best = OpMaxU::apply(best, key[i]);
-        best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(best));   // k <= E: some expert is left, best > 0
+        best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(best));   // k <= E (LIMITED: k <= topk_group gs): some expert is left, best > 0
         // the lowest index that holds it: the first register with a hit (its experts come before the next register's), the
         // lowest lane in it - scalar work on one ballot per register
         int e = 0;
@@ -196,8 +285,8 @@ __global__ __launch_bounds__(kGateThreads) void moe_gate_kernel(const typename G
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = blockIdx.x * kGateWaves + w;          // T k < 2^27, k >= 1: the grid is below 2^25 and t fits an int
     if (t >= T) return;                                 // the whole wave leaves
-    gate_token<L, NV>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, lane, ids + (size_t)t * k,
-                      weights + (size_t)t * k);
+    gate_token<L, NV, false>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, 0, 0, 0, 0, lane,
+                             ids + (size_t)t * k, weights + (size_t)t * k);
 }
 
 template <typename L, int NV>
@@ -211,11 +300,81 @@ __global__ __launch_bounds__(kRouteThreads) void moe_gate_route_kernel(const typ
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int t = w; t < T; t += kRouteWaves)
-        gate_token<L, NV>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, lane, ids + (size_t)t * k,
-                          weights + (size_t)t * k);
+        gate_token<L, NV, false>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, 0, 0, 0, 0, lane,
+                                 ids + (size_t)t * k, weights + (size_t)t * k);
     __threadfence_block();
     __syncthreads();                                    // every wave's ids and weights are written and visible in the workgroup
     route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
+}
+
+// ---- the group-limited forms: the two kernels above, with the group stage ---------------------------------------------------
+template <typename L, int NV>
+__global__ __launch_bounds__(kGateThreads) void moe_gate_limited_kernel(const typename GateLogit<L>::type* __restrict__ logits,
+                                                                        const float* __restrict__ bias, int T, int E, int k,
+                                                                        int scoring, int renormalize, float scale, int n_group,
+                                                                        int topk_group, int group_score,
+                                                                        int32_t* __restrict__ ids, float* __restrict__ weights) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = blockIdx.x * kGateWaves + w;
+    if (t >= T) return;                                 // the whole wave leaves
+    gate_token<L, NV, true>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, n_group, E / n_group, topk_group,
+                            group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
+}
+
+template <typename L, int NV>
+__global__ __launch_bounds__(kRouteThreads) void moe_gate_route_limited_kernel(
+    const typename GateLogit<L>::type* __restrict__ logits, const float* __restrict__ bias, int T, int E, int k, int scoring,
+    int renormalize, float scale, int n_group, int topk_group, int group_score, int nbits, int32_t* ids, float* weights,
+    int32_t* __restrict__ offsets, int32_t* __restrict__ perm, int32_t* __restrict__ rows, float* __restrict__ row_weight,
+    int32_t* __restrict__ pos) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gs = E / n_group;
+    for (int t = w; t < T; t += kRouteWaves)
+        gate_token<L, NV, true>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, n_group, gs, topk_group,
+                                group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
+    __threadfence_block();
+    __syncthreads();                                    // every wave's ids and weights are written and visible in the workgroup
+    route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
+}
+
+template <typename L, int NV>
+static int gate_limited_launch(int T, int E, int k, int n_group, int topk_group, int group_score, int scoring, int renormalize,
+                               float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                               int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
+                               hipStream_t stream) {
+    const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(logits);
+    if (!offsets) {
+        const unsigned grid = (unsigned)((T + kGateWaves - 1) / kGateWaves);
+        hipLaunchKernelGGL((moe_gate_limited_kernel<L, NV>), dim3(grid), dim3(kGateThreads), 0, stream, x, bias, T, E, k, scoring,
+                           renormalize, scale, n_group, topk_group, group_score, ids, weights);
+    } else {
+        auto kern = moe_gate_route_limited_kernel<L, NV>;
+        const size_t lds = route_lds_bytes(E);
+        if (lds > 65536 &&
+            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return FLUTE_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(kRouteThreads), lds, stream, x, bias, T, E, k, scoring, renormalize, scale, n_group,
+                           topk_group, group_score, route_bucket_bits(E), ids, weights, offsets, perm, rows, row_weight, pos);
+    }
+    return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+}
+
+template <typename L>
+static int gate_limited_by_class(int T, int E, int k, int n_group, int topk_group, int group_score, int scoring, int renormalize,
+                                 float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                                 int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
+                                 hipStream_t stream) {
+#define FLUTE_GATE(NV)                                                                                                          \
+    return gate_limited_launch<L, NV>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias, ids, \
+                                      weights, offsets, perm, rows, row_weight, pos, stream)
+    if (E <= 64) FLUTE_GATE(1);
+    if (E <= 128) FLUTE_GATE(2);
+    if (E <= 256) FLUTE_GATE(4);
+    if (E <= 512) FLUTE_GATE(8);
+    FLUTE_GATE(16);
+#undef FLUTE_GATE
 }
 
 template <typename L, int NV>
@@ -265,6 +424,25 @@ int moe_gate_dispatch(int logit_dtype, int T, int E, int k, int scoring, int ren
                                    row_weight, pos, stream);
     return gate_by_class<float>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
                                 row_weight, pos, stream);
+}
+
+int moe_gate_limited_dispatch(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
+                              int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                              int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream) {
+    // every group allowed: every expert is, and the unlimited kernels serve the call - bit for bit by construction.  T == 0 (the
+    // routed form's E + 1 zeros) gates nothing and goes the same way.
+    if (topk_group == n_group || T == 0)
+        return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
+                                 rows, row_weight, pos, stream);
+    renormalize = renormalize != 0;
+    if (logit_dtype == FLUTE_F16)
+        return gate_limited_by_class<F16>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
+                                          ids, weights, offsets, perm, rows, row_weight, pos, stream);
+    if (logit_dtype == FLUTE_BF16)
+        return gate_limited_by_class<BF16>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
+                                           ids, weights, offsets, perm, rows, row_weight, pos, stream);
+    return gate_limited_by_class<float>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
+                                        ids, weights, offsets, perm, rows, row_weight, pos, stream);
 }
 
 }  // namespace flute_amd

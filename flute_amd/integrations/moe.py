@@ -12,7 +12,9 @@ for equal arguments at every top-k, one rounding in the sum over a token's exper
 softmax / sigmoid, the optional correction bias, the top-k with a defined tie order, the renormalisation and the scale
 are `moe_gate` (moe_gate.hip), and with `native_routing=True` gating and routing are one launch (`moe_gate_route`), four
 launches from logits.  `FluteSparseMoeBlock` is the whole sparse-MoE block: the router's dense GEMM (a torch op) and
-`forward_logits`.  DeepSeek's group-limited selection (n_group, topk_group) is not covered: the choice is over all experts.
+`forward_logits`.  DeepSeek's group-limited selection (n_group groups of experts, the topk_group best of them allowed:
+DeepSeek-V2 / V3 / R1) is `forward_logits_limited` on `moe_gate_limited` / `moe_gate_route_limited`, the same launch
+count, and the block's `n_group`, `topk_group`, `group_score` arguments.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
@@ -20,6 +22,8 @@ launches from logits.  `FluteSparseMoeBlock` is the whole sparse-MoE block: the 
     four = FluteExperts.from_linears(gates, ups, downs, fused=True, native_routing=True)   # moe_route -> glu -> weighted -> moe_combine
     out = four.forward_logits(hidden, router_logits, top_k=2, renormalize=True)            # moe_gate_route -> glu -> weighted -> moe_combine
     block = FluteSparseMoeBlock(router_weight, four, top_k=2, renormalize=True)             # [E, K] router, out = block(hidden)
+    v3 = FluteSparseMoeBlock(router_weight, four, top_k=8, scoring="sigmoid", renormalize=True, bias=correction_bias,
+                             scale=2.5, n_group=8, topk_group=4, group_score="top2sum")    # DeepSeek-V3's gating, 256 experts
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
@@ -147,8 +151,8 @@ class FluteExperts(torch.nn.Module):
         (scoring "softmax" / "sigmoid", the optional selection `bias` [E] fp32, ties to the lower expert, `renormalize`,
         `scale`).  With `native_routing` gating and routing are one launch, `moe_gate_route`, and the forward is
         moe_gate_route -> glu -> weighted -> moe_combine (fused): four launches from logits.  Without it `moe_gate` feeds
-        the existing forward.  Either way the result is bit for bit `forward(hidden, *moe_gate(...))`.  Group-limited
-        selection (n_group, topk_group) is not covered."""
+        the existing forward.  Either way the result is bit for bit `forward(hidden, *moe_gate(...))`.  The choice is over
+        all experts; group-limited selection (n_group, topk_group) is `forward_logits_limited`."""
         if router_logits.shape[1] != self.num_experts:
             raise ValueError("FluteExperts.forward_logits: router_logits must be [T, num_experts]")
         if not self.native_routing:
@@ -156,6 +160,24 @@ class FluteExperts(torch.nn.Module):
             return self.forward(hidden, ids, weights)
         _, _, offsets, rows, row_weight, pos, _ = flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring,
                                                                            renormalize, bias, scale)
+        return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+
+    def forward_logits_limited(self, hidden: torch.Tensor, router_logits: torch.Tensor, top_k: int, n_group: int,
+                               topk_group: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
+                               scale: float = 1.0, group_score: str = "max") -> torch.Tensor:
+        """`forward_logits` with DeepSeek's group-limited selection: the gating is `flute_amd.moe_gate_limited`'s contract
+        (the `topk_group` best of `n_group` contiguous groups of experts by `group_score` "max" / "top2sum", then the top-k
+        among their experts only).  With `native_routing` the forward is moe_gate_route_limited -> glu -> weighted ->
+        moe_combine (fused): still four launches from logits.  Without it `moe_gate_limited` feeds the existing forward.
+        Either way the result is bit for bit `forward(hidden, *moe_gate_limited(...))`."""
+        if router_logits.shape[1] != self.num_experts:
+            raise ValueError("FluteExperts.forward_logits_limited: router_logits must be [T, num_experts]")
+        if not self.native_routing:
+            ids, weights = flute_amd.moe_gate_limited(router_logits, top_k, n_group, topk_group, scoring, renormalize, bias,
+                                                      scale, group_score)
+            return self.forward(hidden, ids, weights)
+        _, _, offsets, rows, row_weight, pos, _ = flute_amd.moe_gate_route_limited(
+            router_logits, top_k, n_group, topk_group, self.num_experts, scoring, renormalize, bias, scale, group_score)
         return self._forward_routed(hidden, offsets, rows, row_weight, pos)
 
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
@@ -180,7 +202,7 @@ class FluteExperts(torch.nn.Module):
         return self._forward_routed(hidden, offsets, rows, row_weight, pos)
 
     def _forward_routed(self, hidden, offsets, rows, row_weight, pos):
-        """The launches behind the routing arrays, whichever kernel wrote them (`moe_route` or `moe_gate_route`)."""
+        """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`)."""
         gate, up, down = self.gate, self.up, self.down
         if self.fused:
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
@@ -202,10 +224,13 @@ class FluteSparseMoeBlock(torch.nn.Module):
     router's dense matrix; its GEMM stays a dense torch op (E is 8 .. 256 columns: nothing to quantise or fuse), and
     everything behind it is the module's own kernels - with `FluteExperts(fused=True, native_routing=True)` four
     launches.  `scoring`, `renormalize`, `bias` (the selection bias [E] fp32, kept as a buffer) and `scale` are
-    `flute_amd.moe_gate`'s.  Group-limited selection (DeepSeek's n_group / topk_group) is not covered."""
+    `flute_amd.moe_gate`'s.  With `n_group` > 1 the selection is DeepSeek's group-limited one (`flute_amd.moe_gate_limited`:
+    the `topk_group` best of `n_group` groups of experts by `group_score` "max" / "top2sum") and forward is
+    `experts.forward_logits_limited(...)`, the same number of launches; with n_group == 1 it is exactly the path above."""
 
     def __init__(self, router_weight: torch.Tensor, experts: FluteExperts, top_k: int, scoring: str = "softmax",
-                 renormalize: bool = False, bias=None, scale: float = 1.0) -> None:
+                 renormalize: bool = False, bias=None, scale: float = 1.0, n_group: int = 1, topk_group: int = 1,
+                 group_score: str = "max") -> None:
         super().__init__()
         if router_weight.ndim != 2 or router_weight.shape[0] != experts.num_experts or \
                 router_weight.shape[1] != experts.gate.in_features:
@@ -216,16 +241,33 @@ class FluteSparseMoeBlock(torch.nn.Module):
             raise ValueError("FluteSparseMoeBlock: 1 <= top_k <= min(num_experts, 64)")
         if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (experts.num_experts,)):
             raise ValueError("FluteSparseMoeBlock: bias must be [num_experts] fp32")
+        if group_score not in ("max", "top2sum"):
+            raise ValueError("FluteSparseMoeBlock: group_score is 'max' or 'top2sum'")
+        if not 1 <= n_group <= flute_amd.ops.MOE_GATE_MAX_GROUPS or experts.num_experts % n_group != 0:
+            raise ValueError("FluteSparseMoeBlock: 1 <= n_group <= 64 must divide num_experts")
+        if not 1 <= topk_group <= n_group:
+            raise ValueError("FluteSparseMoeBlock: 1 <= topk_group <= n_group")
+        group_size = experts.num_experts // n_group
+        if top_k > topk_group * group_size:
+            raise ValueError("FluteSparseMoeBlock: top_k <= topk_group * (num_experts / n_group)")
+        if n_group > 1 and group_score == "top2sum" and group_size < 2:
+            raise ValueError("FluteSparseMoeBlock: group_score 'top2sum' needs groups of two experts or more")
         self.experts = experts
         self.register_buffer("router_weight", router_weight)
         self.register_buffer("bias", bias)
         self.top_k, self.scoring, self.renormalize, self.scale = int(top_k), scoring, bool(renormalize), float(scale)
+        self.n_group, self.topk_group, self.group_score = int(n_group), int(topk_group), group_score
 
     def forward(self, hidden: torch.Tensor) -> torch.Tensor:
         logits = torch.nn.functional.linear(hidden, self.router_weight)
+        if self.n_group > 1:
+            return self.experts.forward_logits_limited(hidden, logits, self.top_k, self.n_group, self.topk_group,
+                                                       self.scoring, self.renormalize, self.bias, self.scale,
+                                                       self.group_score)
         return self.experts.forward_logits(hidden, logits, self.top_k, self.scoring, self.renormalize, self.bias,
                                            self.scale)
 
     def extra_repr(self) -> str:
         return (f"top_k={self.top_k}, scoring={self.scoring}, renormalize={self.renormalize}, scale={self.scale}, "
-                f"bias={self.bias is not None}")
+                f"bias={self.bias is not None}, n_group={self.n_group}, topk_group={self.topk_group}, "
+                f"group_score={self.group_score}")

@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `moe_route`, `moe_combine`, `moe_gate` and `moe_gate_route`.
+`qgemm_grouped_weighted`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and `moe_gate_route_limited`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -523,8 +523,8 @@ def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize
     largest key, equal keys in ascending expert index (a total order: unlike `torch.topk`, ties are defined), where the
     key is the logit itself or, with `bias` [E] fp32 (DeepSeek-V3's correction bias), s + bias - the bias decides the
     choice only; the weight is s, with `renormalize` divided by the sum of the k chosen scores, then times `scale`.
-    1 <= k <= min(E, 64), E <= 1024, T k < 2^27.  DeepSeek's group-limited selection (n_group, topk_group) is not
-    covered.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
+    1 <= k <= min(E, 64), E <= 1024, T k < 2^27.  The choice is over all E experts; DeepSeek's group-limited
+    selection (n_group, topk_group) is `moe_gate_limited`.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
     stream (moe_gate.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
     _validate_moe_gate(logits, k, scoring, bias)
     return _moe_gate_call("moe_gate", logits, k, scoring, renormalize, bias, scale, routed=False)
@@ -538,6 +538,84 @@ def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str 
     pairs: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     _validate_moe_gate(logits, k, scoring, bias, num_experts)
     return _moe_gate_call("moe_gate_route", logits, k, scoring, renormalize, bias, scale, routed=True)
+
+
+_GATE_GROUP_SCORE_ID = {"max": 0, "top2sum": 1}     # include/flute_amd.h flute_gate_group_score
+MOE_GATE_MAX_GROUPS = 64                            # FLUTE_MOE_GATE_MAX_GROUPS
+
+
+def _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score, num_experts=None):
+    if group_score not in _GATE_GROUP_SCORE_ID:
+        raise ValueError
+    _validate_moe_gate(logits, k, scoring, bias, num_experts)
+    E = logits.shape[1]
+    if not 1 <= n_group <= MOE_GATE_MAX_GROUPS or E % n_group != 0:
+        raise ValueError
+    if not 1 <= topk_group <= n_group:
+        raise ValueError
+    gs = E // n_group
+    if k > topk_group * gs:
+        raise ValueError
+    if group_score == "top2sum" and gs < 2:
+        raise ValueError
+
+
+def _moe_gate_limited_call(name, logits, k, n_group, topk_group, group_score, scoring, renormalize, bias, scale, routed):
+    dev = logits.device
+    if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
+        raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
+    T, E = logits.shape
+    k = int(k)
+    x = logits.contiguous()
+    b = None if bias is None else bias.contiguous()
+    ids = torch.empty((T, k), dtype=torch.int32, device=dev)
+    weights = torch.empty((T, k), dtype=torch.float32, device=dev)
+    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, int(n_group), int(topk_group), _GATE_GROUP_SCORE_ID[group_score],
+            _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale), x.data_ptr(),
+            None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
+    with torch.cuda.device(dev):
+        if not routed:
+            _lib.check(_lib.get().flute_moe_gate_limited(*head, _stream_ptr(dev)))
+            return ids, weights
+        P = T * k
+        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        perm = torch.empty(P, dtype=torch.int32, device=dev)
+        rows = torch.empty(P, dtype=torch.int32, device=dev)
+        row_weight = torch.empty(P, dtype=torch.float32, device=dev)
+        pos = torch.empty((T, k), dtype=torch.int32, device=dev)
+        _lib.check(_lib.get().flute_moe_gate_route_limited(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
+                                                           row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
+    return ids, weights, offsets, rows, row_weight, pos, perm
+
+
+def moe_gate_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int, scoring: str = "softmax",
+                     renormalize: bool = False, bias=None, scale: float = 1.0, group_score: str = "max"):
+    """`moe_gate` with DeepSeek's group-limited selection, in one launch: the E experts are `n_group` contiguous groups of
+    gs = E / n_group, the `topk_group` best groups are chosen (equal group keys to the lower group), and the k experts
+    are `moe_gate`'s choice among the experts of those groups only - an expert of another group is never chosen,
+    whatever its key (vLLM's -inf mask, not the HF code's 0.0 fill).  A group's key is, with `group_score="max"`
+    (DeepSeek-V2), its largest expert key (the logit, or s + bias), with `"top2sum"` (DeepSeek-V3) the fp32 sum of its
+    two largest s (+ bias), which needs gs >= 2; there a softmax is always normalised over all E, also under
+    `renormalize` without a bias.  Scores, keys, tie order, weights, `renormalize` and `scale` are `moe_gate`'s.
+    1 <= n_group <= 64, E % n_group == 0, 1 <= topk_group <= n_group, k <= topk_group gs, and `moe_gate`'s limits.
+    With topk_group == n_group the result is bit for bit `moe_gate`'s.  Returns (ids [T, k] int32, weights [T, k]
+    fp32); no host synchronise (capturable), a native HIP kernel on the current stream (moe_gate.hip), equal arguments
+    give equal bits."""
+    _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score)
+    return _moe_gate_limited_call("moe_gate_limited", logits, k, n_group, topk_group, group_score, scoring, renormalize,
+                                  bias, scale, routed=False)
+
+
+def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int, num_experts=None,
+                           scoring: str = "softmax", renormalize: bool = False, bias=None, scale: float = 1.0,
+                           group_score: str = "max"):
+    """`moe_gate_limited` and `moe_route` in one launch: (ids, weights, offsets, rows, row_weight, pos, perm), the first
+    two bit for bit `moe_gate_limited(logits, k, n_group, topk_group, ...)`'s and the other five bit for bit
+    `moe_route(ids, weights, E)`'s.  `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves, as
+    `moe_gate_route`: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
+    _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score, num_experts)
+    return _moe_gate_limited_call("moe_gate_route_limited", logits, k, n_group, topk_group, group_score, scoring,
+                                  renormalize, bias, scale, routed=True)
 
 
 def _validate_moe_combine(y, pos, offsets):

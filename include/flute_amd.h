@@ -25,7 +25,8 @@ extern "C" {
 
 /* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
  *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
- *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring
+ *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring; flute_moe_gate_limited and flute_moe_gate_route_limited with
+ *    flute_gate_group_score
  *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -41,6 +42,9 @@ enum flute_dtype { FLUTE_F16 = 0, FLUTE_BF16 = 1, FLUTE_F32 = 2 };
 enum flute_index_dtype { FLUTE_I32 = 0, FLUTE_I64 = 1 };
 /* how flute_moe_gate / flute_moe_gate_route turn a router logit into a score */
 enum flute_gate_scoring { FLUTE_GATE_SOFTMAX = 0, FLUTE_GATE_SIGMOID = 1 };
+/* how flute_moe_gate_limited / flute_moe_gate_route_limited rank a group of experts: by its largest key (DeepSeek-V2), or by the sum
+ * of its two largest biased scores (DeepSeek-V3) */
+enum flute_gate_group_score { FLUTE_GATE_GROUP_MAX = 0, FLUTE_GATE_GROUP_TOP2SUM = 1 };
 
 enum flute_status {
     FLUTE_OK = 0,
@@ -363,7 +367,8 @@ int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const v
  *              which every chosen score is 0 or not finite gets whatever this arithmetic gives (a division by zero, NaN); only
  *              its ids are defined.
  * Limits: 1 <= k <= min(E, FLUTE_MOE_GATE_MAX_TOPK), E <= FLUTE_MOE_ROUTE_MAX_EXPERTS, T k < FLUTE_MOE_ROUTE_MAX_PAIRS.
- * DeepSeek's group-limited selection (n_group, topk_group) is out of scope: the choice is over all E experts.
+ * The choice here is over all E experts; DeepSeek's group-limited selection (n_group, topk_group) is flute_moe_gate_limited /
+ * flute_moe_gate_route_limited below.
  * One wave per token, lane l holding experts l, l + 64, ... in registers; the max, the sum and the k rounds of "largest key,
  * lowest index" are wave reductions in a fixed order and ballots, without LDS (moe_gate.hip).  The host reads nothing, the grid follows from T
  * alone (hipGraph-capturable), no atomics, plain vector stores: equal arguments give equal bits, and a token's ids and weights
@@ -388,6 +393,47 @@ int flute_moe_gate(int logit_dtype, int T, int E, int k, int scoring, int renorm
 int flute_moe_gate_route(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale,
                          const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets,
                          int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream);
+
+/* flute_moe_gate with DeepSeek's group-limited selection: the E experts form n_group contiguous groups of gs = E / n_group
+ * (group g is experts g gs .. (g + 1) gs - 1), the topk_group best groups are chosen first, and the k experts are then chosen
+ * among the experts of those groups only.  Score, key and weight are flute_moe_gate's; one stage sits between key and choice:
+ *   group key     group_score (flute_gate_group_score) FLUTE_GATE_GROUP_MAX (DeepSeek-V2): the largest expert key of the group - the
+ *                 keys are flute_moe_gate's, the logit itself without a bias (nothing is rounded), s_e + bias[e] with one.
+ *                 FLUTE_GATE_GROUP_TOP2SUM (DeepSeek-V3): the sum, ONE fp32 addition, of the two largest c_e = s_e (+ bias[e]) of
+ *                 the group, a NaN c_e counting as -infinity; needs gs >= 2.  s_e is the normalised score: with
+ *                 FLUTE_GATE_SOFTMAX this form always divides by the sum over all E, under renormalize and without a bias too,
+ *                 where flute_moe_gate renormalises the u_e directly - the weights are then s_j / (the compensated sum of the
+ *                 chosen s), equal in value and not always in bits.  A NaN group key compares as -infinity (and -0 as +0).
+ *   group choice  the topk_group groups with the largest group keys, equal keys to the lower group index: a total order.
+ *   choice        flute_moe_gate's k rounds over the experts of the chosen groups.  An expert of another group is never chosen,
+ *                 whatever its key (the -infinity mask of vLLM's grouped_topk; the HF modelling code fills with 0.0 instead, which
+ *                 lets a masked expert beat an allowed one with a negative key - that is not reproduced).  Hence k <= topk_group gs.
+ * With topk_group == n_group (n_group == 1 included) every expert is allowed, whatever group_score is: the call is served by
+ * flute_moe_gate's own kernel and the result is bit for bit flute_moe_gate's.
+ * Limits: flute_moe_gate's, and 1 <= n_group <= FLUTE_MOE_GATE_MAX_GROUPS, E % n_group == 0, 1 <= topk_group <= n_group,
+ * k <= topk_group gs.  The same wave-per-token kernel with the group stage compiled in (moe_gate.hip): a wave-uniform loop over the
+ * groups (a masked wave maximum each, two for the sum), topk_group rounds of "largest group key, lowest group" on lane g's group key,
+ * and the keys of the experts outside the chosen groups cleared; no LDS, no atomics, plain vector stores; every property of
+ * flute_moe_gate holds (capturable, equal bits for equal arguments, a token's result independent of T and of its row).
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE (logit_dtype, then scoring, then group_score);
+ * FLUTE_ERR_SHAPE (flute_moe_gate's conditions; then n_group < 1 or > FLUTE_MOE_GATE_MAX_GROUPS; E % n_group; topk_group < 1 or
+ * > n_group; k > topk_group gs; FLUTE_GATE_GROUP_TOP2SUM with gs < 2); T == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL
+ * (logits, ids, weights; bias is optional). */
+#define FLUTE_MOE_GATE_MAX_GROUPS 64
+int flute_moe_gate_limited(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
+                           int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                           void* stream);
+
+/* flute_moe_gate_limited and flute_moe_route in ONE launch, as flute_moe_gate_route is for flute_moe_gate: ids and weights bit for bit
+ * flute_moe_gate_limited's, the five routing arrays bit for bit what flute_moe_route then writes on them.  One workgroup of 16 waves.
+ * With topk_group == n_group it is served by flute_moe_gate_route's kernel, bit for bit in all seven arrays.
+ * Refusals: flute_moe_gate_limited's FLUTE_ERR_DTYPE and FLUTE_ERR_SHAPE; T == 0 with a null offsets returns FLUTE_OK without a
+ * launch; then FLUTE_ERR_NULL (offsets; with T > 0 also logits, ids, weights, perm, rows, row_weight, pos).  T == 0 with offsets
+ * given writes the E + 1 zeros. */
+int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
+                                 int renormalize, float scale, const void* logits, const float* bias, int32_t* ids,
+                                 float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
+                                 void* stream);
 
 /* The end of a mixture-of-experts step: the sorted rows Y [P, N] T of the down projection (flute_qgemm_grouped_weighted's
  * output), summed per token through pos [T, k] int32 (flute_moe_route's), into out [T, N] T.  Per element:

@@ -4,6 +4,7 @@
     python tools/grouped_bench.py --mode mlp [--out profiles/grouped_moe_fused.json]
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
+    python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -38,6 +39,11 @@ today (Mixtral's softmax -> topk -> renormalise at E = 8, top-2 and E = 64, top-
 gather -> renormalise -> scale at E = 256, top-8) followed by moe_route - the best the code before moe_gate offers - against
 one moe_gate_route launch, fp16 logits.  The whole block: the router GEMM, that chain and
 FluteExperts(fused=True, native_routing=True).forward against FluteSparseMoeBlock on the same experts, at --mode step's shape.
+
+--mode gate_limited times the group-limited gating alone at DeepSeek-V3's shape (E = 256, top-8, 8 groups, the best 4 by the
+top-2 sum, sigmoid + bias, renormalised, scale 2.5, fp16 logits) by --mode gate's method, in one process: moe_gate_limited,
+moe_gate at the same (E, k) - the difference is the cost of the group stage - and the torch-op chain for the same selection
+(view / topk / sum / topk / scatter / masked_fill / topk / gather / sum / div).
 """
 import argparse
 import json
@@ -422,6 +428,78 @@ def child_gate(args, device):
         json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
+LIMITED_SHAPE = dict(E=256, k=8, n_group=8, topk_group=4, scoring="sigmoid", scale=2.5, group_score="top2sum")
+
+
+def torch_gate_limited(logits, bias, E, k, n_group, topk_group, scale):
+    """DeepSeek-V3's group-limited gating as a torch-op chain, with the -infinity mask."""
+    T = logits.shape[0]
+    s = torch.sigmoid(logits.float())
+    c = s + bias
+    group_scores = c.view(T, n_group, E // n_group).topk(2, dim=-1).values.sum(dim=-1)
+    group_idx = torch.topk(group_scores, topk_group, dim=-1).indices
+    group_mask = torch.zeros_like(group_scores).scatter_(1, group_idx, 1.0)
+    score_mask = group_mask.unsqueeze(-1).expand(T, n_group, E // n_group).reshape(T, E)
+    ids = torch.topk(c.masked_fill(score_mask == 0, float("-inf")), k, dim=-1).indices
+    w = s.gather(1, ids)
+    w = w / w.sum(dim=-1, keepdim=True)
+    return ids, w * scale
+
+
+class GateLimited:
+    """From logits [T, 256] fp16 to (ids, weights); step(i) returns the weights.  form: "limited", "unlimited" or "torch"."""
+
+    def __init__(self, tokens, device, form):
+        import flute_amd
+        self.fa, self.form = flute_amd, form
+        gen = torch.Generator(device=device).manual_seed(tokens + LIMITED_SHAPE["E"])
+        self.logits = (torch.randn(tokens, LIMITED_SHAPE["E"], device=device, generator=gen) * 2).to(DTYPE)
+        self.bias = torch.randn(LIMITED_SHAPE["E"], device=device, generator=gen) * 0.1
+
+    def step(self, i):
+        c = LIMITED_SHAPE
+        if self.form == "limited":
+            return self.fa.moe_gate_limited(self.logits, c["k"], c["n_group"], c["topk_group"], c["scoring"], True, self.bias,
+                                            c["scale"], c["group_score"])[1]
+        if self.form == "unlimited":
+            return self.fa.moe_gate(self.logits, c["k"], c["scoring"], True, self.bias, c["scale"])[1]
+        return torch_gate_limited(self.logits, self.bias, c["E"], c["k"], c["n_group"], c["topk_group"], c["scale"])[1]
+
+
+def main_gate_limited(args, device):
+    rows = []
+    for tokens in args.tokens:
+        forms = {f: GateLimited(tokens, device, f) for f in ("limited", "unlimited", "torch")}
+        ids = forms["limited"].fa.moe_gate_limited(forms["limited"].logits, 8, 8, 4, "sigmoid", True, forms["limited"].bias, 2.5,
+                                                   "top2sum")[0]
+        want = torch_gate_limited(forms["torch"].logits, forms["torch"].bias, 256, 8, 8, 4, 2.5)[0]
+        diff = float((forms["limited"].step(0) - forms["torch"].step(0)).abs().max())
+        torch.cuda.synchronize()
+        # two passes of each, alternating; the figure is the mean of each form's two medians
+        order = ("limited", "unlimited", "torch") * 2
+        m = [measure(forms[f], args) for f in order]
+        us = {f: (m[i]["us"] + m[i + 3]["us"]) / 2 for i, f in enumerate(order[:3])}
+        row = dict(LIMITED_SHAPE, tokens=tokens, bias=True, renormalize=True, moe_gate_limited_us=round(us["limited"], 3),
+                   moe_gate_us=round(us["unlimited"], 3), torch_chain_us=round(us["torch"], 3),
+                   group_stage_us=round(us["limited"] - us["unlimited"], 3),
+                   limited_over_torch=round(us["limited"] / us["torch"], 4), spread=max(p["spread"] for p in m),
+                   ids_equal_torch_chain=bool(torch.equal(ids.long(), want)), max_abs_weight_diff_vs_torch=diff,
+                   replays_us={f: [m[i]["replays_us"], m[i + 3]["replays_us"]] for i, f in enumerate(order[:3])})
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        rows.append(row)
+    out = {"what": "group-limited gating alone at DeepSeek-V3's shape, fp16 logits [T, 256] -> (ids, weights): one moe_gate_limited "
+                   "launch; one moe_gate launch at the same (E, k) (no group stage); the torch-op chain for the same selection. "
+                   "hipGraph replays of `steps` calls between device-clock stamps, cold caches, median of `replays`; passes: "
+                   "limited, unlimited, torch, twice",
+           "config": {"steps": args.steps, "warmup": args.warmup, "replays": args.replays, "dtype": "float16",
+                      "device": torch.cuda.get_device_name(device)},
+           "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def measure(layer, args):
     us, _ = bench.time_graph(layer, args.steps, args.warmup, torch.cuda.synchronize, cold=True, replays=args.replays)
     t = dict(bench.LAST_TIMING)
@@ -436,7 +514,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
-    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate"], default="projection")
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited"], default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
@@ -444,7 +522,8 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
-                                                   "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json"}[args.mode])
+                                                   "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json",
+                                                   "gate_limited": "grouped_moe_gate_limited.json"}[args.mode])
     if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
@@ -453,6 +532,8 @@ def main():
         return child_step(args, device)
     if args.mode == "gate":
         return child_gate(args, device)
+    if args.mode == "gate_limited":
+        return main_gate_limited(args, device)
     if args.mode == "mlp":
         return main_mlp(args, device)
     rows = []
