@@ -1655,15 +1655,24 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
     return table_grad_scratch_bytes(num_bits, ilog2(group_size), M, N, K, want_dS != 0, num_sms);
 }
 
+// the refusals flute_qgemm_grouped, _glu and _weighted share, in their order: dtype, the layer, the zero group size, then P and the
+// negative counts (N: the stack's output columns, rows: T or R)
+static int check_grouped(int dtype, int num_bits, int group_size, int template_id, int E, int rows, int N, int K, int P,
+                         Layer* l) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), l);
+    if (rc) return rc;
+    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
+    if (P != num_bits * (N / 16) || E < 0 || rows < 0) return FLUTE_ERR_SHAPE;
+    return FLUTE_OK;
+}
+
 int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
                         const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
                         int num_sms, void* stream) {
-    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
     Layer l;
-    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
     if (rc) return rc;
-    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
-    if (P != num_bits * (N / 16) || E < 0 || T < 0) return FLUTE_ERR_SHAPE;
     if (E == 0 || T == 0) return FLUTE_OK;
     if (!X || !offsets || !Q || !S || !QM2 || !Y) return FLUTE_ERR_NULL;
     return qgemm_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, Y, num_sms,
@@ -1674,12 +1683,10 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
                             int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
                             const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
                             void* H, int num_sms, void* stream) {
-    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
     Layer l;
-    const int rc = check_layer(num_bits, group_size, template_id, F, K, std::max(64, group_size), &l);
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, P, &l);
     if (rc) return rc;
-    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
-    if (P != num_bits * (F / 16) || E < 0 || R < 0 || Tsrc < 0) return FLUTE_ERR_SHAPE;
+    if (Tsrc < 0) return FLUTE_ERR_SHAPE;
     if (rows ? (R > 0 && Tsrc < 1) : Tsrc != R) return FLUTE_ERR_SHAPE;
     if (E == 0 || R == 0) return FLUTE_OK;
     if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
@@ -1690,12 +1697,9 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream) {
-    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
     Layer l;
-    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
     if (rc) return rc;
-    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
-    if (P != num_bits * (N / 16) || E < 0 || T < 0) return FLUTE_ERR_SHAPE;
     if (E == 0 || T == 0) return FLUTE_OK;
     if (!X || !offsets || !Q || !S || !QM2 || !row_weight || !Y) return FLUTE_ERR_NULL;
     return qgemm_grouped_weighted_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2,

@@ -73,11 +73,12 @@ size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int w
 int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
                         const void* X, const void* Q, const void* S, const void* QM2, float* dT2, void* dS,
                         void* scratch, int num_sms, hipStream_t stream);
-// grouped qgemm of E stacked layers over rows sorted by expert (qgemm_grouped.hip); offsets [E + 1] int32 is read on the device only
+// grouped qgemm of E stacked layers over rows sorted by expert (qgemm_grouped.h, one kernel template; inst_grouped_plain.hip); offsets [E + 1]
+// int32 is read on the device only
 int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
                            const void* offsets, const void* Q, const void* S, const void* QM2, void* Y, int num_sms,
                            hipStream_t stream);
-// its fused forms for a mixture-of-experts MLP (qgemm_grouped_fused.h): H = silu32(gate) * up over rows read through an optional
+// the template's fused modes for a mixture-of-experts MLP (inst_grouped_glu.hip, inst_grouped_weighted.hip): H = silu32(gate) * up over rows read through an optional
 // index, and Y = row_weight * (X @ W^T) with the rows past offsets[E] written as zeros
 int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int Tsrc, int N, int K, int P,
                                const void* Xsrc, const void* rows, const void* offsets, const void* Qg, const void* Sg,

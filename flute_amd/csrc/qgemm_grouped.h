@@ -1,26 +1,64 @@
-// The fused forms of the grouped qgemm (qgemm_grouped.hip) for a mixture-of-experts MLP, on that kernel's geometry:
+// Grouped qgemm for mixture-of-experts layers: Y[r, :] = X[r, :] @ W_e^T for the rows r in [offsets[e], offsets[e + 1]) of
+// every expert e < E, ONE launch whose grid does not depend on how the rows are spread.  X [T, K] holds the rows sorted by
+// expert, offsets [E + 1] int32 lives in device memory and is read by the kernel only (never by the host: the launch is
+// hipGraph-capturable and a replay honours whatever the table then holds), Q [E, P, K] / S [E, N, K / g] / QM2 [E, 4^b] are E
+// layers packed exactly as one FluteLinear's buffers (layout: common.h), all of one num_bits / group size / TileP.
 //
-//   GLU       H[r, :] = round_T( silu32(g) * u ),  g = Xsrc[rows[r]] @ Wgate_e^T,  u = Xsrc[rows[r]] @ Wup_e^T
-//             for the rows r in [offsets[e], offsets[e + 1]) of every expert e: one launch instead of two grouped
-//             launches, a gather, silu and a multiply.  g, u are the fp32 sums after the in-workgroup K reduction,
-//             silu32(g) = g / (1 + exp(-g)) in fp32 (silu32() below), one rounding to T at the store.
-//   weighted  Y[r, :] = round_T( row_weight[r] * acc32 ), one rounding, and the rows [clamp(offsets[E]), T) - rows no
+// One kernel template, three epilogues (GroupedMode):
+//
+//   Plain     Y[r, :] = round_T( acc32 ); rows no expert covers are left unwritten.
+//   Glu       H[r, :] = round_T( silu32(g) * u ),  g = Xsrc[rows[r]] @ Wgate_e^T,  u = Xsrc[rows[r]] @ Wup_e^T: one launch
+//             instead of two grouped launches, a gather, silu and a multiply.  g, u are the fp32 sums after the
+//             in-workgroup K reduction, silu32(g) = g / (1 + exp(-g)) in fp32 (silu32() below), one rounding to T at the store.
+//   Weighted  Y[r, :] = round_T( row_weight[r] * acc32 ), one rounding, and the rows [clamp(offsets[E]), T) - rows no
 //             expert serves - written as zeros by the same launch whichever experts have rows.
 //
-// This is a translation unit of its own on purpose: qgemm_grouped.hip is not touched, so every
-// qgemm_grouped_kernel instantiation keeps its code and its bits.  What is shared is restated, not changed: Layout /
-// unit_row / unit_col0 / field, the 8 waves that split K in interleaved blocks of U k-steps, the next block's
-// operands held in registers, the scale panel staged per K chunk in the reduction's LDS, the pair table as 32 LDS
-// copies, row passes of RT 16-row tiles with the K loop compiled per tile count, the reduction through LDS in wave
-// order (no atomics, no split across workgroups: equal arguments give equal bits), 64-bit bases, the grid from
-// (E, N, num_bits, num_sms) alone, and a workgroup whose expert has no rows requesting nothing.
+// What a mode adds sits under `if constexpr`; everything else is one program text, so Plain is Weighted without the zero
+// fill and without the multiply.
 //
-// GLU.  A workgroup serves slab s of the gate stack and slab s of the up stack for the same rows: the K loop and the
+// Arithmetic (include/flute_amd.h, as dequant.hip and the MFMA kernels): w^ = round_T(lut * s) by Num<T>::mul_scale4, fp32
+// accumulation in the matrix core, one rounding of the output to T.  K is split over the waves of ONE workgroup only and
+// the partial tiles are summed through LDS in wave order; no atomics, no split across workgroups: equal arguments give
+// equal bits.
+//
+// Geometry (qgemm_skinny.h's, for every bit width through Layout / unit_row / unit_col0 / field).  v_mfma_f32_16x16x32 with
+// the weights as the A operand: lane (u = l % 16, q = l / 16) loads, per plane, the 16 B of unit row u that hold k-pairs
+// 4 q .. 4 q + 3 of a 32-k step; field j of each dword is looked up in the expert's pair table (LDS, 32 copies: lane l reads
+// copy l % 32, so the 32 lanes of a ds_read_b32 group never share a bank) and multiplied by the scale of column
+// unit_col0(u) + j TileP: one A fragment per column tile j < J.  The activations are the B operand: lane (r, q) loads its
+// 16 B of row row0 + 16 t + r.  One weight request feeds J x (row tiles of the pass) MFMAs.  D[u][r] lands in lane (q, r) as
+// units 4 q .. 4 q + 3 - four consecutive output columns, one 8-byte store per tile.
+//
+// Work split.  A workgroup is (expert, a run of `spw` 16-unit slabs); its 8 waves split K in blocks of U k-steps (U = 4,
+// 128 k; 2 bits below group size 128: 2; 3 bits: 1), wave w taking blocks w, w + 8, ..: at any moment the waves of a
+// workgroup read one contiguous 0.5 - 2 KB piece of each of the 16 unit rows.  A wave holds the next block's weights and
+// activations in registers while it decodes the current one (plain loads: the compiler counts the waits).  The scales go
+// through LDS: per K chunk the workgroup stages the slab's panel [16 J columns][groups of the chunk] with requests that run
+// along a scale row (64 groups = one cache line per request; read per lane from global memory they were 2-byte requests
+// touching 16 lines each, 9 - 21 % of the time at Mixtral shapes), in the 32 KB the reduction uses after the K loop; the
+// row stride in dwords is odd, so the 16 units of a ds_read_u16 hit 16 banks.  A chunk is the largest multiple of 8 blocks
+// whose groups fit (all of K up to 16 K at 4 bits and group size 64).  The expert index is the slow one of blockIdx
+// (e = blockIdx / runs): consecutive blocks go to different XCDs, so the slabs of ONE busy expert spread over all eight
+// dies - with the expert as the fast index a decode step that routes to two experts would run on two dies.
+// The host picks spw in {1, 2, 4} as the largest that still leaves eight workgroups per CU; it and the grid follow from
+// (E, N, num_bits, num_sms) alone, as include/flute_amd.h says (grouped_grid() below, the only place they are computed).
+//
+// Rows.  rb = clamp(offsets[e]), re = clamp(offsets[e + 1]) to [0, R]; a workgroup with re <= rb returns before it requests
+// a weight, scale or table word.  The expert's rows are taken in passes of RT 16-row tiles (RT = 2; 3 bits: 1 - the
+// accumulators, J x RT x 4 fp32, and two blocks of operands stay in registers, no scratch), the weights streamed once per
+// pass; a tile of a pass that holds no row issues neither loads nor MFMAs (the K loop is compiled per tile count), rows
+// past `re` inside a tile are fed as zeros and never stored.  Every row index the kernel forms is < re <= R, so a
+// malformed table cannot reach outside X / Y.
+//
+// Glu.  A workgroup serves slab s of the gate stack and slab s of the up stack for the same rows: the K loop and the
 // reduction run for the gate slab, waves 0 .. TR - 1 keep their reduced tiles in registers (NI / TR float4 per lane: 2 at
 // 4 bits, 4 at 2 and 3 bits), the K loop and the reduction run again for the up slab, and the same lanes combine and
 // store.  Both pair tables sit in LDS (4 bits: 2 x 32 KB beside the 32 KB of the reduction).  The activation rows are
 // read through `rows` (int32, each entry clamped to [0, Tsrc) before it forms an address; null: row r is r) - the only
 // place the index is used.
+//
+// Address arithmetic: the expert bases into Q / S / QM2 and the row bases into X / Y are 64-bit (stacked 8192 x 8192 4-bit
+// experts pass 2 GiB of codes at E = 64).
 #pragma once
 #include "kernels.h"
 #include "mfma.h"
@@ -29,12 +67,15 @@
 
 namespace flute_amd {
 
-constexpr int kFusedWaves = 8;
-constexpr int kFusedThreads = kFusedWaves * 64;
-constexpr int kFusedRedTiles = 4;            // output tiles per round of the LDS reduction (8 waves x 4 KB = 32 KB)
+enum class GroupedMode { Plain, Glu, Weighted };
 
-// qgemm_grouped.hip's GroupedShape: the accumulators (J x RT x 4 fp32) and two blocks of operands fit 256 registers
-template <int BITS, int LGC> struct FusedShape {
+constexpr int kGroupedWaves = 8;
+constexpr int kGroupedThreads = kGroupedWaves * 64;
+constexpr int kGroupedRedTiles = 4;          // output tiles per round of the LDS reduction (8 waves x 4 KB = 32 KB)
+
+// Sized so that the accumulators (J x RT x 4 fp32) and two blocks of operands fit in 256 registers without scratch.
+// LGC (2 bits only; 7 otherwise): 5 / 6 = log2(group size), 7 = group size >= 128
+template <int BITS, int LGC> struct GroupedShape {
     static constexpr int RT = (BITS == 3) ? 1 : 2;                                           // 16-row tiles per pass
     static constexpr int U = (BITS == 3) ? 1 : (BITS == 2 && LGC < 7) ? 2 : 4;               // k-steps per block
 };
@@ -45,29 +86,48 @@ template <int BITS, int LGC> struct FusedShape {
 // exp(-88) underflows against the 1).  With the fp32 product by u (2^-24) behind it: eps_s = 2^-21 covers both.
 __device__ __forceinline__ float silu32(float g) { return g / (1.0f + expf(-g)); }
 
-struct GroupedFusedArgs {
+struct GroupedArgs {
     const uint16_t* X;          // [Tsrc, K] T
-    const int* rows;            // [R] or null (GLU only)
+    const int* rows;            // [R] or null (Glu only)
     const int* offsets;         // [E + 1]
-    const uint32_t* Q[2];       // [E, P, K / 2]: the stack (GLU: gate, up)
+    const uint32_t* Q[2];       // [E, P, K / 2]: the stack (Glu: gate, up)
     const uint16_t* S[2];       // [E, N, K / g]
     const uint32_t* QM2[2];     // [E, 4^b]
-    const float* row_weight;    // [R] (weighted only)
+    const float* row_weight;    // [R] (Weighted only)
     uint16_t* Y;                // [R, N]
     int R, Tsrc, N, K, P, lg, runs, spw, E;
 };
 
-template <typename T, int BITS, int TILEP, int LGC, bool GLU>
-__global__ __launch_bounds__(kFusedThreads) void qgemm_grouped_fused_kernel(const GroupedFusedArgs a) {
+// The arguments of a launch from the untyped pointers of the *_dispatch functions; one stack fills both slots, runs / spw
+// are the launch's to set.
+inline GroupedArgs grouped_args(const void* X, const void* rows, const void* offsets, const void* Q0, const void* S0,
+                                const void* QM20, const void* Q1, const void* S1, const void* QM21, const void* row_weight,
+                                void* Y, int R, int Tsrc, int N, int K, int P, int lg, int E) {
+    GroupedArgs a{};
+    a.X = reinterpret_cast<const uint16_t*>(X);
+    a.rows = reinterpret_cast<const int*>(rows);
+    a.offsets = reinterpret_cast<const int*>(offsets);
+    a.Q[0] = reinterpret_cast<const uint32_t*>(Q0); a.Q[1] = reinterpret_cast<const uint32_t*>(Q1);
+    a.S[0] = reinterpret_cast<const uint16_t*>(S0); a.S[1] = reinterpret_cast<const uint16_t*>(S1);
+    a.QM2[0] = reinterpret_cast<const uint32_t*>(QM20); a.QM2[1] = reinterpret_cast<const uint32_t*>(QM21);
+    a.row_weight = reinterpret_cast<const float*>(row_weight);
+    a.Y = reinterpret_cast<uint16_t*>(Y);
+    a.R = R; a.Tsrc = Tsrc; a.N = N; a.K = K; a.P = P; a.lg = lg; a.E = E;
+    return a;
+}
+
+template <typename T, int BITS, int TILEP, int LGC, GroupedMode MODE>
+__global__ __launch_bounds__(kGroupedThreads) void qgemm_grouped_kernel(const GroupedArgs a) {
     using L = Layout<BITS>;
     using NT = Num<T>;
+    constexpr bool GLU = MODE == GroupedMode::Glu;
     constexpr int J = L::J;
     constexpr int NP = L::NPLANES;
-    constexpr int RT = FusedShape<BITS, LGC>::RT;
-    constexpr int U = FusedShape<BITS, LGC>::U;
+    constexpr int RT = GroupedShape<BITS, LGC>::RT;
+    constexpr int U = GroupedShape<BITS, LGC>::U;
     constexpr int NI = J * RT;                                     // 16 x 16 output tiles per wave
-    constexpr int KW = kFusedWaves;
-    constexpr int TR = kFusedRedTiles;
+    constexpr int KW = kGroupedWaves;
+    constexpr int TR = kGroupedRedTiles;
     constexpr int NC = 16 * J;                                     // columns of a slab
     constexpr int NSTK = GLU ? 2 : 1;                              // weight stacks
     // scale panel of a K chunk: [NC][ST] T in the reduction's LDS; ST / 2 is odd, so the 16 units of a ds_read_u16 hit 16 banks
@@ -81,12 +141,12 @@ __global__ __launch_bounds__(kFusedThreads) void qgemm_grouped_fused_kernel(cons
     const int R = a.R, N = a.N, K = a.K, lg = a.lg;
     uint16_t* __restrict__ Y = a.Y;
 
-    if constexpr (!GLU) {
+    if constexpr (MODE == GroupedMode::Weighted) {
         // rows no expert serves, [clamp(offsets[E]), R): zeros, 8 bytes per lane, spread over the whole grid
         const int zb = min(max(a.offsets[a.E], 0), R);
         const size_t n4 = (size_t)(R - zb) * (size_t)(N >> 2);
         ushort4* z = reinterpret_cast<ushort4*>(Y + (size_t)zb * N);
-        for (size_t i = (size_t)blockIdx.x * kFusedThreads + tid; i < n4; i += (size_t)gridDim.x * kFusedThreads)
+        for (size_t i = (size_t)blockIdx.x * kGroupedThreads + tid; i < n4; i += (size_t)gridDim.x * kGroupedThreads)
             z[i] = ushort4{0, 0, 0, 0};
     }
 
@@ -111,7 +171,7 @@ __global__ __launch_bounds__(kFusedThreads) void qgemm_grouped_fused_kernel(cons
 #pragma unroll
     for (int s = 0; s < NSTK; ++s) {
         const uint32_t* __restrict__ Te = a.QM2[s] + (size_t)e * L::LUT_N;
-        for (int i = tid; i < L::LUT_N * 32; i += kFusedThreads) lut[s][i] = Te[i >> 5];
+        for (int i = tid; i < L::LUT_N * 32; i += kGroupedThreads) lut[s][i] = Te[i >> 5];
     }
     __syncthreads();
     uint16_t* panel = reinterpret_cast<uint16_t*>(red);
@@ -251,7 +311,7 @@ __global__ __launch_bounds__(kFusedThreads) void qgemm_grouped_fused_kernel(cons
                 const int j = tile / RT, t = tile % RT;
                 const int row = row0 + 16 * t + u;
                 if (row < re) {
-                    if constexpr (!GLU) {
+                    if constexpr (MODE == GroupedMode::Weighted) {
                         const float w = a.row_weight[row];
                         s.x *= w; s.y *= w; s.z *= w; s.w *= w;
                     }
@@ -279,40 +339,51 @@ __global__ __launch_bounds__(kFusedThreads) void qgemm_grouped_fused_kernel(cons
     }
 }
 
-// The launch of either form: spw and the grid exactly as qgemm_grouped_dispatch picks them, from (E, N, num_bits, num_sms).
-template <bool GLU>
-int qgemm_grouped_fused_launch(int dtype, int num_bits, int tile_p, int lg, GroupedFusedArgs a, int num_sms, hipStream_t stream) {
+// spw, runs and the grid of a launch, from (E, N, num_bits, num_sms) alone: spw in {1, 2, 4} is the largest that still
+// leaves eight workgroups per CU.  False: the grid does not fit 31 bits.
+inline bool grouped_grid(int E, int N, int num_bits, int num_sms, int* spw_out, int* runs_out, unsigned* grid_out) {
     const int J = (num_bits == 3) ? 16 : 16 / num_bits;
-    const int slabs = a.N / J / 16;
+    const int slabs = N / J / 16;
     const long long sms = num_sms >= 1 ? num_sms : 256;
     int spw = 1;
-    while (spw < 4 && (long long)a.E * ((slabs + 2 * spw - 1) / (2 * spw)) >= 8 * sms) spw *= 2;
-    a.spw = spw;
-    a.runs = (slabs + spw - 1) / spw;
-    if ((long long)a.E * a.runs > 0x7fffffffLL) return FLUTE_ERR_SHAPE;
-    const unsigned grid = (unsigned)((long long)a.E * a.runs);
-#define FLUTE_GRPF(TY, B, TP, LGC) \
-    hipLaunchKernelGGL((qgemm_grouped_fused_kernel<TY, B, TP, LGC, GLU>), dim3(grid), dim3(kFusedThreads), 0, stream, a)
-#define FLUTE_GRPF_L(TY, B, TP)                 \
-    if (lg == 5) FLUTE_GRPF(TY, B, TP, 5);      \
-    else if (lg == 6) FLUTE_GRPF(TY, B, TP, 6); \
-    else FLUTE_GRPF(TY, B, TP, 7)
-#define FLUTE_GRPF_T(B, TP)                               \
-    if (dtype == FLUTE_F16) { FLUTE_GRPF_L(F16, B, TP); } \
-    else { FLUTE_GRPF_L(BF16, B, TP); }
-#define FLUTE_GRPF_7(B, TP)                                \
-    if (dtype == FLUTE_F16) { FLUTE_GRPF(F16, B, TP, 7); } \
-    else { FLUTE_GRPF(BF16, B, TP, 7); }
-    if (num_bits == 4 && tile_p == 32) { FLUTE_GRPF_7(4, 32) }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_GRPF_7(4, 64) }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_GRPF_T(2, 32) }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_GRPF_T(2, 64) }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_GRPF_7(3, 32) }
+    while (spw < 4 && (long long)E * ((slabs + 2 * spw - 1) / (2 * spw)) >= 8 * sms) spw *= 2;
+    const int runs = (slabs + spw - 1) / spw;
+    if ((long long)E * runs > 0x7fffffffLL) return false;
+    *spw_out = spw;
+    *runs_out = runs;
+    *grid_out = (unsigned)((long long)E * runs);
+    return true;
+}
+
+// The launch of every form: the 18 instantiations of a mode (4 bits: TileP 32 / 64; 2 bits: TileP 32 / 64 x group size
+// 32 / 64 / >= 128; 3 bits: TileP 32; each in f16 and bf16).
+template <GroupedMode MODE>
+int qgemm_grouped_launch(int dtype, int num_bits, int tile_p, GroupedArgs a, int num_sms, hipStream_t stream) {
+    unsigned grid;
+    if (!grouped_grid(a.E, a.N, num_bits, num_sms, &a.spw, &a.runs, &grid)) return FLUTE_ERR_SHAPE;
+    const int lg = a.lg;
+#define FLUTE_GRP(TY, B, TP, LGC) \
+    hipLaunchKernelGGL((qgemm_grouped_kernel<TY, B, TP, LGC, MODE>), dim3(grid), dim3(kGroupedThreads), 0, stream, a)
+#define FLUTE_GRP_L(TY, B, TP)                 \
+    if (lg == 5) FLUTE_GRP(TY, B, TP, 5);      \
+    else if (lg == 6) FLUTE_GRP(TY, B, TP, 6); \
+    else FLUTE_GRP(TY, B, TP, 7)
+#define FLUTE_GRP_T(B, TP)                               \
+    if (dtype == FLUTE_F16) { FLUTE_GRP_L(F16, B, TP); } \
+    else { FLUTE_GRP_L(BF16, B, TP); }
+#define FLUTE_GRP_7(B, TP)                                \
+    if (dtype == FLUTE_F16) { FLUTE_GRP(F16, B, TP, 7); } \
+    else { FLUTE_GRP(BF16, B, TP, 7); }
+    if (num_bits == 4 && tile_p == 32) { FLUTE_GRP_7(4, 32) }
+    else if (num_bits == 4 && tile_p == 64) { FLUTE_GRP_7(4, 64) }
+    else if (num_bits == 2 && tile_p == 32) { FLUTE_GRP_T(2, 32) }
+    else if (num_bits == 2 && tile_p == 64) { FLUTE_GRP_T(2, 64) }
+    else if (num_bits == 3 && tile_p == 32) { FLUTE_GRP_7(3, 32) }
     else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_GRPF_7
-#undef FLUTE_GRPF_T
-#undef FLUTE_GRPF_L
-#undef FLUTE_GRPF
+#undef FLUTE_GRP_7
+#undef FLUTE_GRP_T
+#undef FLUTE_GRP_L
+#undef FLUTE_GRP
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 

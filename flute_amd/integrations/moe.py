@@ -1,7 +1,7 @@
 """Mixture-of-experts layers on packed weights: all experts of a projection in one launch.
 
 `GroupedFluteLinear` stacks E `FluteLinear`s of one shape and serves rows sorted by expert through
-`flute_amd.qgemm_grouped` (qgemm_grouped.hip); the per-expert row counts never leave the device (`sort_by_expert`
+`flute_amd.qgemm_grouped` (qgemm_grouped.h); the per-expert row counts never leave the device (`sort_by_expert`
 uses ops of fixed output shape only), so a decode step with changing routing can sit in one captured graph.
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
 its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
@@ -181,7 +181,7 @@ class FluteExperts(torch.nn.Module):
         return self._forward_routed(hidden, offsets, rows, row_weight, pos)
 
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
-        """Two launches (qgemm_grouped_fused.h): silu(gate(x)) * up(x) with the rows of `hidden` read through the
+        """Two launches (qgemm_grouped.h, GLU and weighted modes): silu(gate(x)) * up(x) with the rows of `hidden` read through the
         routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
         the rows past offsets[E] (ids outside [0, E)) as zeros: no silu, no where, no gathered copy of `hidden`."""
         gate, up, down = self.gate, self.up, self.down

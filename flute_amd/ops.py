@@ -291,6 +291,27 @@ def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_si
         raise ValueError
 
 
+def _launch_grouped(name, rows, weight, N, tensors, num_bits, group_size, template_id, num_sms):
+    """The tail of the three validated grouped ops: flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P,
+    template_id, *pointers, out, num_sms, stream) with `tensors` as the pointers in the ABI's order (input first; None: a
+    null pointer), `rows` the ABI's row counts (the result's first) and `weight` [E, P, K] one of the stacks."""
+    input = tensors[0]
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
+        raise RuntimeError(f"flute_amd.{name}: all tensors must live on the same GPU")
+    if max(rows) >= 2 ** 31:
+        raise ValueError
+    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    out = torch.empty((rows[0], N), dtype=input.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.get(), "flute_" + name)(
+            _DTYPE_ID[input.dtype], num_bits, group_size, weight.shape[0], *rows, N, input.shape[1], weight.shape[1],
+            template_id, *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
+    return out
+
+
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                   table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
     """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
@@ -300,29 +321,10 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     Returns [T, N] in input.dtype; rows no expert covers are left unwritten, and a table that decreases or whose
     ranges overlap is memory-safe (every index is clamped to T) but leaves the contents of the rows it names twice unspecified.  The host never reads `offsets` (no
     synchronise: the call can be captured in a graph and replayed on other row counts of the same T).  A native HIP
-    kernel on the current stream (qgemm_grouped.hip); the same arguments give the same bits."""
+    kernel on the current stream (qgemm_grouped.h); the same arguments give the same bits."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in (input, offsets, weight, scales, table2)):
-        raise RuntimeError("flute_amd.qgemm_grouped: all tensors must live on the same GPU")
-    T, K = input.shape
-    E, N = scales.shape[0], scales.shape[1]
-    if T >= 2 ** 31:
-        raise ValueError
-    x = input.contiguous()
-    off = offsets.contiguous()
-    w = weight.contiguous()
-    s = scales.contiguous()
-    t2 = table2.contiguous()
-    out = torch.empty((T, N), dtype=input.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_grouped(
-            _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
-            x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), out.data_ptr(), num_sms,
-            _stream_ptr(dev)))
-    return out
+    return _launch_grouped("qgemm_grouped", (input.shape[0],), weight, scales.shape[1],
+                           (input, offsets, weight, scales, table2), num_bits, group_size, template_id, num_sms)
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -348,31 +350,14 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     one, of one shape, num_bits, group_size and template_id.  Both products stay in fp32 until the one rounding of the
     result (include/flute_amd.h, flute_qgemm_grouped_glu); nothing intermediate is written.  Returns [R, F] in
     input.dtype, rows no expert covers left unwritten.  The host reads neither `offsets` nor `rows` (no synchronise,
-    capturable); a native HIP kernel on the current stream (qgemm_grouped_fused.h); equal arguments give equal bits."""
+    capturable); a native HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
-    dev = input.device
-    tensors = (input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2) + \
-        (() if rows is None else (rows,))
-    if not all(t.is_cuda and t.device == dev for t in tensors):
-        raise RuntimeError("flute_amd.qgemm_grouped_glu: all tensors must live on the same GPU")
-    Tsrc, K = input.shape
-    E, F = gate_scales.shape[0], gate_scales.shape[1]
+    Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
-    if max(R, Tsrc) >= 2 ** 31:
-        raise ValueError
-    x, off = input.contiguous(), offsets.contiguous()
-    ops = [t.contiguous() for t in (gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2)]
-    idx = None if rows is None else rows.contiguous()
-    out = torch.empty((R, F), dtype=input.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_grouped_glu(
-            _DTYPE_ID[x.dtype], num_bits, group_size, E, R, Tsrc, F, K, ops[0].shape[1], template_id,
-            x.data_ptr(), None if idx is None else idx.data_ptr(), off.data_ptr(), *[t.data_ptr() for t in ops],
-            out.data_ptr(), num_sms, _stream_ptr(dev)))
-    return out
+    return _launch_grouped("qgemm_grouped_glu", (R, Tsrc), gate_weight, gate_scales.shape[1],
+                           (input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2),
+                           num_bits, group_size, template_id, num_sms)
 
 
 def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size):
@@ -389,25 +374,10 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
-    HIP kernel on the current stream (qgemm_grouped_fused.h); equal arguments give equal bits."""
+    HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in (input, offsets, weight, scales, table2, row_weight)):
-        raise RuntimeError("flute_amd.qgemm_grouped_weighted: all tensors must live on the same GPU")
-    T, K = input.shape
-    E, N = scales.shape[0], scales.shape[1]
-    if T >= 2 ** 31:
-        raise ValueError
-    x, off, w, s, t2, rw = (t.contiguous() for t in (input, offsets, weight, scales, table2, row_weight))
-    out = torch.empty((T, N), dtype=input.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_grouped_weighted(
-            _DTYPE_ID[x.dtype], num_bits, group_size, E, T, N, K, w.shape[1], template_id,
-            x.data_ptr(), off.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr(), rw.data_ptr(), out.data_ptr(),
-            num_sms, _stream_ptr(dev)))
-    return out
+    return _launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, scales.shape[1],
+                           (input, offsets, weight, scales, table2, row_weight), num_bits, group_size, template_id, num_sms)
 
 
 _INDEX_DTYPE_ID = {torch.int32: 0, torch.int64: 1}

@@ -1,4 +1,4 @@
-"""flute_amd.qgemm_grouped_glu / qgemm_grouped_weighted (qgemm_grouped_fused.h) and FluteExperts(fused=True) on the GPU.
+"""flute_amd.qgemm_grouped_glu / qgemm_grouped_weighted (qgemm_grouped.h) and FluteExperts(fused=True) on the GPU.
 
 GLU.  Gate and up are exact stacks (tests/exact_cases) with different seeds and X = make_x(...) * 2^-p, still exact in T, so
 g = x @ Wgate^T and u = x @ Wup^T are exact in fp32 whatever the summation order.  With E = g / (1 + e^-g) * u in fp64 the
@@ -19,7 +19,7 @@ import torch
 
 from tests import exact_cases as XC
 from tests.test_grouped_gpu import (COUNTS, K_CHUNK_CASES, bits16, env, exact_layers, exact_matrix, exact_seed,  # noqa: F401
-                                    experts_case, offsets_of, stack_exact)
+                                    experts_case, first_template, offsets_of, random_stack, stack_exact)
 
 pytestmark = pytest.mark.gpu
 
@@ -313,6 +313,24 @@ def test_weighted_zero_fill_all_offsets_zero(env, weighted_small):
     """No expert has a row: the launch still writes every row of [0, T) as zeros and nothing else."""
     Y = weighted_abi(env, weighted_small, torch.zeros(len(COUNTS) + 1, dtype=torch.int32))
     assert torch.all(Y == 0)
+
+
+@pytest.mark.parametrize("bits,tile_p,g,dtype", [(4, 32, 64, F16), (2, 64, 64, BF16), (3, 32, 32, BF16)])
+def test_weighted_by_one_is_the_plain_form(env, bits, tile_p, g, dtype):
+    """row_weight = 1 and offsets[E] = T: the fp32 product by 1.0 is exact, so the weighted form is the plain form bit for bit on
+    every row (one kernel template, qgemm_grouped.h).  K = 1088: each of the eight waves gets a block and the last block is
+    short; N: the smallest the template takes, two slabs or more.  Then offsets[E] lowered by 17: equal below it, zeros from it on."""
+    K, N, E, T = 1088, XC.cols_per_block(bits, tile_p), len(COUNTS), sum(COUNTS)
+    Q, S, t2, _ = random_stack(env, bits, tile_p, g, dtype, K, N, E, seed=8800 + bits)
+    X = torch.randn(T, K, generator=torch.Generator().manual_seed(8801)).to(dtype).to(env.dev)
+    off, ones = offsets_of(COUNTS, env.dev), torch.ones(T, device=env.dev)
+    tid = first_template(env.fa, bits, tile_p)
+    plain = bits16(env.fa.qgemm_grouped(X, off, Q, S, t2, bits, g, tid, env.num_sms))
+    assert torch.equal(bits16(env.fa.qgemm_grouped_weighted(X, off, Q, S, t2, ones, bits, g, tid, env.num_sms)), plain)
+    cut = T - 17
+    off[E] = cut
+    short = bits16(env.fa.qgemm_grouped_weighted(X, off, Q, S, t2, ones, bits, g, tid, env.num_sms))
+    assert torch.equal(short[:cut], plain[:cut]) and torch.all(short[cut:] == 0)
 
 
 # ---- the module --------------------------------------------------------------------------------------------------------

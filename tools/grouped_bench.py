@@ -1,6 +1,6 @@
 """Grouped qgemm against the per-expert loop on Mixtral-8x7B-shaped experts, timed the way bench.py times the headline.
 
-    python tools/grouped_bench.py [--steps 20] [--warmup 5] [--replays 5] [--out profiles/grouped_moe.json]
+    python tools/grouped_bench.py [--bits 4] [--steps 20] [--warmup 5] [--replays 5] [--out profiles/grouped_moe.json]
     python tools/grouped_bench.py --mode mlp [--out profiles/grouped_moe_fused.json]
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
@@ -17,7 +17,9 @@ every timed replay, warm-up, the median of `replays` replays), alternately in th
             best case (eager it also needs the counts on the host, i.e. a device synchronise per step)
 
 Per shape: microseconds per step of both, their ratio, the bytes the algorithm needs (packed weights and scales of the
-routed experts, X and Y), the GB/s and the share of 8 TB/s that follow, and the spread of the replays.
+routed experts, X and Y), the GB/s and the share of 8 TB/s that follow, and the spread of the replays.  --bits 2 / 3 times
+the projection at that bit width (same group size and dtype); where the shipped table holds no template for one of the
+loop's (row count, shape) pairs at that width, the grouped form is timed alone and the row says so.
 
 --mode mlp times a whole expert MLP step at the same shapes, token counts and routing, from the gather of the hidden
 states through the down projection's weighted output (everything of FluteExperts.forward between sort_by_expert and
@@ -73,18 +75,18 @@ def routing(tokens, seed):
 class Experts:
     """`copies` stacks of E packed layers [N, K]; step(i) runs one projection of all routed rows on copy i."""
 
-    def __init__(self, N, K, counts, copies, device, grouped):
+    def __init__(self, N, K, counts, copies, device, grouped, bits=BITS):
         import flute_amd
         from flute_amd import tune, utils
-        self.fa, self.N, self.K, self.counts, self.grouped = flute_amd, N, K, counts, grouped
+        self.fa, self.N, self.K, self.counts, self.grouped, self.bits = flute_amd, N, K, counts, grouped, bits
         self.num_sms = utils.get_device_num_sms(device)
         self.ws = utils.get_workspace_streamk(device)
         T = sum(counts)
         gen = torch.Generator(device=device).manual_seed(1)
-        P = BITS * N // 16
+        P = bits * N // 16
         self.Q = torch.randint(-2 ** 15, 2 ** 15, (copies, E, P, K), dtype=torch.int16, device=device, generator=gen)
         self.S = torch.randn(copies, E, N, K // G, device=device, generator=gen).to(DTYPE)
-        self.table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
+        self.table = torch.randn(2 ** bits, device=device, generator=gen).sort().values.to(DTYPE)
         self.table2 = utils.make_qmap2_from_qmap(self.table)
         self.tables2 = self.table2.repeat(E, 1, 1, 1)
         self.X = (torch.randn(T, K, device=device, generator=gen) / 100).to(DTYPE)
@@ -93,20 +95,20 @@ class Experts:
             off.append(off[-1] + c)
         self.off_host = off
         self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
-        self.tid_grouped = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+        self.tid_grouped = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == 32)
         # the loop's template per row count: the shipped table's (random bits are a valid packed matrix in either layout);
-        # a shape the table does not hold is an error here, not an on-device tuning run
+        # a shape the table does not hold is no on-device tuning run: LookupError, and the caller times the grouped form alone
         self.tid_loop = {}
-        for m in sorted(set(c for c in counts if c)):
-            tid = tune.lookup_tuned(m, N, K, BITS, G, self.num_sms, DTYPE)
+        for m in (() if grouped else sorted(set(c for c in counts if c))):
+            tid = tune.lookup_tuned(m, N, K, bits, G, self.num_sms, DTYPE)
             if tid is None:
-                raise RuntimeError(f"no shipped template for M={m} N={N} K={K} W{BITS}G{G} on {self.num_sms} CUs")
+                raise LookupError(f"no shipped template for M={m} N={N} K={K} W{bits}G{G} on {self.num_sms} CUs")
             self.tid_loop[m] = tid
 
     def step(self, i):
         c = i % self.Q.shape[0]
         if self.grouped:
-            return self.fa.qgemm_grouped(self.X, self.offsets, self.Q[c], self.S[c], self.tables2, BITS, G,
+            return self.fa.qgemm_grouped(self.X, self.offsets, self.Q[c], self.S[c], self.tables2, self.bits, G,
                                          self.tid_grouped, self.num_sms)
         # the per-expert outputs are kept as they come: no copy into one [T, N] tensor (the grouped form has none either)
         ys = []
@@ -114,12 +116,12 @@ class Experts:
             if m:
                 r0, r1 = self.off_host[e], self.off_host[e + 1]
                 ys.append(self.fa.qgemm(self.X[r0:r1], self.Q[c, e], self.S[c, e], self.table, self.table2, self.ws,
-                                        BITS, G, self.tid_loop[m], self.num_sms))
+                                        self.bits, G, self.tid_loop[m], self.num_sms))
         return ys
 
     def bytes(self):
         routed = sum(1 for c in self.counts if c)
-        per_expert = (BITS * self.N // 16) * self.K * 2 + self.N * (self.K // G) * 2
+        per_expert = (self.bits * self.N // 16) * self.K * 2 + self.N * (self.K // G) * 2
         return routed * per_expert + sum(self.counts) * (self.K + self.N) * 2
 
 
@@ -514,6 +516,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
+    ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
     ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited"], default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -537,35 +540,50 @@ def main():
     if args.mode == "mlp":
         return main_mlp(args, device)
     rows = []
+    bits = args.bits
     for name, N, K in (("gate_up", 14336, 4096), ("down", 4096, 14336)):
-        per_copy = E * ((BITS * N // 16) * K * 2 + N * (K // G) * 2)
+        per_copy = E * ((bits * N // 16) * K * 2 + N * (K // G) * 2)
         copies = max(2, bench.L3_BYTES // per_copy + 2)
         for tokens in args.tokens:
             counts = routing(tokens, seed=tokens)
-            grouped = Experts(N, K, counts, copies, device, grouped=True)
-            loop = Experts(N, K, counts, copies, device, grouped=False)
-            a = torch.cat([grouped.step(0)[grouped.off_host[e]:grouped.off_host[e + 1]] for e in range(E)])
-            b = torch.cat(loop.step(0))
-            torch.cuda.synchronize()
-            # two passes of each, alternating; the figure is the mean of each form's two medians
-            m = [measure(layer, args) for layer in (grouped, loop, grouped, loop)]
-            g_us, l_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+            grouped = Experts(N, K, counts, copies, device, grouped=True, bits=bits)
+            try:
+                loop, no_loop = Experts(N, K, counts, copies, device, grouped=False, bits=bits), None
+            except LookupError as err:
+                loop, no_loop = None, str(err)
             nbytes = grouped.bytes()
-            row = {"projection": name, "N": N, "K": K, "tokens": tokens, "rows": sum(counts), "counts": counts,
-                   "weight_copies": copies, "grouped_us": round(g_us, 3), "loop_us": round(l_us, 3),
-                   "grouped_over_loop": round(g_us / l_us, 4), "bytes": nbytes,
-                   "grouped_GBps": round(nbytes / g_us * 1e-3, 1), "loop_GBps": round(nbytes / l_us * 1e-3, 1),
-                   "grouped_share_of_8TBps": round(nbytes / (g_us * 1e-6) / PEAK, 4),
-                   "loop_share_of_8TBps": round(nbytes / (l_us * 1e-6) / PEAK, 4),
-                   "loop_launches": sum(1 for c in counts if c), "loop_templates": loop.tid_loop,
-                   "max_abs_diff_grouped_vs_loop": float((a.float() - b.float()).abs().max()),
-                   "passes": m}
+            row = {"projection": name, "bits": bits, "N": N, "K": K, "tokens": tokens, "rows": sum(counts), "counts": counts,
+                   "weight_copies": copies}
+            if loop is None:
+                # the grouped form alone, the same two passes
+                grouped.step(0)
+                torch.cuda.synchronize()
+                m = [measure(grouped, args) for _ in range(2)]
+                g_us = (m[0]["us"] + m[1]["us"]) / 2
+                row.update({"grouped_us": round(g_us, 3), "loop_us": None, "loop_not_timed": no_loop, "bytes": nbytes,
+                            "grouped_GBps": round(nbytes / g_us * 1e-3, 1),
+                            "grouped_share_of_8TBps": round(nbytes / (g_us * 1e-6) / PEAK, 4), "passes": m})
+            else:
+                a = torch.cat([grouped.step(0)[grouped.off_host[e]:grouped.off_host[e + 1]] for e in range(E)])
+                b = torch.cat(loop.step(0))
+                torch.cuda.synchronize()
+                # two passes of each, alternating; the figure is the mean of each form's two medians
+                m = [measure(layer, args) for layer in (grouped, loop, grouped, loop)]
+                g_us, l_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+                row.update({"grouped_us": round(g_us, 3), "loop_us": round(l_us, 3),
+                            "grouped_over_loop": round(g_us / l_us, 4), "bytes": nbytes,
+                            "grouped_GBps": round(nbytes / g_us * 1e-3, 1), "loop_GBps": round(nbytes / l_us * 1e-3, 1),
+                            "grouped_share_of_8TBps": round(nbytes / (g_us * 1e-6) / PEAK, 4),
+                            "loop_share_of_8TBps": round(nbytes / (l_us * 1e-6) / PEAK, 4),
+                            "loop_launches": sum(1 for c in counts if c), "loop_templates": loop.tid_loop,
+                            "max_abs_diff_grouped_vs_loop": float((a.float() - b.float()).abs().max()),
+                            "passes": m})
             rows.append(row)
             print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
             del grouped, loop
             torch.cuda.empty_cache()
     out = {"what": "grouped qgemm vs per-expert qgemm loop, hipGraph replays, device-clock stamps, cold caches",
-           "config": {"bits": BITS, "group_size": G, "experts": E, "top_k": TOPK, "dtype": "float16",
+           "config": {"bits": bits, "group_size": G, "experts": E, "top_k": TOPK, "dtype": "float16",
                       "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
                       "device": torch.cuda.get_device_name(device)},
            "rows": rows}
