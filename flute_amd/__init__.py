@@ -31,6 +31,9 @@ pair_grad_to_table_grad = ops.pair_grad_to_table_grad
 qgemm_grouped = ops.qgemm_grouped
 qgemm_grouped_glu = ops.qgemm_grouped_glu
 qgemm_grouped_weighted = ops.qgemm_grouped_weighted
+# their input gradient, one launch over the packed stacks (contracts over N); the grouped and mixture-of-experts functions
+# here backpropagate through it to activations, routing weights and router logits
+qgemm_grouped_input_grad = ops.qgemm_grouped_input_grad
 # the routing around them, one launch each: the router's choice [T, k] -> offsets, rows, row_weight, pos, perm (a stable
 # counting sort on the device), and the sorted rows of the down projection summed per token in fp32 with one rounding
 moe_route = ops.moe_route

@@ -1706,6 +1706,32 @@ int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E,
                                            row_weight, Y, num_sms, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_qgemm_grouped_input_grad_row_block(void) { return FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK; }
+
+int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                   const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                   const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
+    if (rc) return rc;
+    const bool pair = dY2 || Q2 || S2 || QM22;
+    if (pair && row_weight) return FLUTE_ERR_SHAPE;               // the pair form takes no row weight
+    if (R == 0) return FLUTE_OK;
+    if (!dX) return FLUTE_ERR_NULL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (E == 0)                                                    // no expert serves any row: zeros, as the kernel writes them
+        return hipMemsetAsync(dX, 0, (size_t)R * (size_t)K * 2, st) == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+    if (!dY || !offsets || !Q || !S || !QM2 || (pair && (!dY2 || !Q2 || !S2 || !QM22))) return FLUTE_ERR_NULL;
+    (void)num_sms;                                                 // the grid is E x ceil(K / 128): from the shapes alone
+    const int tp = l.t.tile_p, lg = l.lg;
+    if (num_bits == 4)
+        return qgemm_grouped_input_grad_dispatch_b4(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+    if (num_bits == 3)
+        return qgemm_grouped_input_grad_dispatch_b3(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+    return qgemm_grouped_input_grad_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+}
+
 int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
                     int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
     if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;

@@ -87,6 +87,17 @@ int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int 
 int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
                                     const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
                                     const void* row_weight, void* Y, int num_sms, hipStream_t stream);
+// the input gradient of the grouped qgemm (qgemm_grouped_input_grad.h; inst_grouped_input_grad_b*.hip, one unit per bit width): dX [R, K] from
+// dY [R, N], with dY2 / Q2 / S2 / QM22 non-null the pair form (both products summed in fp32); rows past offsets[E] written as zeros
+#define FLUTE_IG_DISPATCH(B)                                                                                                   \
+    int qgemm_grouped_input_grad_dispatch_b##B(int dtype, int tile_p, int lg, int E, int R, int N, int K, int P, const void* dY, \
+                                               const void* offsets, const void* Q, const void* S, const void* QM2,             \
+                                               const void* row_weight, const void* dY2, const void* Q2, const void* S2,        \
+                                               const void* QM22, void* dX, hipStream_t stream)
+FLUTE_IG_DISPATCH(4);
+FLUTE_IG_DISPATCH(3);
+FLUTE_IG_DISPATCH(2);
+#undef FLUTE_IG_DISPATCH
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

@@ -16,6 +16,15 @@ launches from logits.  `FluteSparseMoeBlock` is the whole sparse-MoE block: the 
 DeepSeek-V2 / V3 / R1) is `forward_logits_limited` on `moe_gate_limited` / `moe_gate_route_limited`, the same launch
 count, and the block's `n_group`, `topk_group`, `group_score` arguments.
 
+Every path here backpropagates: when `hidden`, `topk_weights` or the router's logits require grad, the launches record
+their backward (`flute_amd.ops`): the input gradients of the three projections are `qgemm_grouped_input_grad` launches
+(the fused GLU recomputes gate and up with two plain grouped launches and takes both gradients in one pair-form launch),
+the gradient of the gather is `moe_combine` under native routing (equal bits at every top-k) and `index_add_` otherwise,
+`moe_combine`'s own gradient is a gather, and the gating ops differentiate their formula in fp32 with the chosen ids
+held fixed - so layers in front of the block (LoRA on attention, a trainable router) get their gradients.  The packed
+stacks themselves are frozen: scales or tables that require grad raise.  With grad mode off, or nothing requiring grad,
+the forward is exactly the inference path above and stays capturable.
+
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
     fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
@@ -208,7 +217,7 @@ class FluteExperts(torch.nn.Module):
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
             h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
                                             up.scales, up.tables2, gate.num_bits, gate.group_size, gate.template_id,
-                                            num_sms, rows=rows)
+                                            num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
             y = flute_amd.qgemm_grouped_weighted(h, offsets, down.weight, down.scales, down.tables2, row_weight,
                                                  down.num_bits, down.group_size, down.template_id, num_sms)
         else:

@@ -1,6 +1,10 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and `moe_gate_route_limited`.
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
+`moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
+routing weights and router logits (not the packed stacks): when grad mode is on and such an input requires grad they run
+through a `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`,
+`moe_combine` and a few torch ops; otherwise they take exactly the path they always took.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -268,6 +272,26 @@ def pair_grad_to_table_grad(dT2: torch.Tensor) -> torch.Tensor:
     return dT2[:, :, 0].sum(dim=1) + dT2[:, :, 1].sum(dim=0)
 
 
+def _records_grad(*tensors):
+    """Whether a call on these inputs must record a graph: grad mode is on and a floating-point one requires grad."""
+    return torch.is_grad_enabled() and any(t is not None and t.is_floating_point() and t.requires_grad for t in tensors)
+
+
+def _refuse_stack_grads(name, *tensors):
+    if any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(
+            f"flute_amd.{name}: gradients with respect to scales, table or table2 are not supported "
+            "(only the input gradient is); detach them or set requires_grad=False")
+
+
+def _zero_unserved_(out, offsets):
+    """Rows from offsets[E] on - rows no expert serves, which the launch left unwritten - as zeros, on the device: under
+    autograd an unwritten row must not hold a NaN that a zero gradient could meet."""
+    R = out.shape[0]
+    unserved = torch.arange(R, device=out.device) >= offsets[-1].clamp(0, R)
+    return out.masked_fill_(unserved[:, None], 0)
+
+
 def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size):
     if not all([input.ndim == 2, offsets.ndim == 1, weight.ndim == 3, scales.ndim == 3, table2.ndim == 4]):
         raise ValueError
@@ -323,8 +347,28 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     synchronise: the call can be captured in a graph and replayed on other row counts of the same T).  A native HIP
     kernel on the current stream (qgemm_grouped.h); the same arguments give the same bits."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    if _records_grad(input, scales, table2):
+        _refuse_stack_grads("qgemm_grouped", scales, table2)
+        return _GroupedFunction.apply(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
     return _launch_grouped("qgemm_grouped", (input.shape[0],), weight, scales.shape[1],
                            (input, offsets, weight, scales, table2), num_bits, group_size, template_id, num_sms)
+
+
+class _GroupedFunction(torch.autograd.Function):
+    """`qgemm_grouped` under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)."""
+
+    @staticmethod
+    def forward(ctx, input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms):
+        out = _launch_grouped("qgemm_grouped", (input.shape[0],), weight, scales.shape[1],
+                              (input, offsets, weight, scales, table2), num_bits, group_size, template_id, num_sms)
+        ctx.save_for_backward(offsets, weight, scales, table2)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return _zero_unserved_(out, offsets)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        return (qgemm_grouped_input_grad(grad_output, *ctx.saved_tensors, *ctx.layer),) + (None,) * 8
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -343,21 +387,71 @@ def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2,
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                      rows=None) -> torch.Tensor:
+                      rows=None, pos=None) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
     one, of one shape, num_bits, group_size and template_id.  Both products stay in fp32 until the one rounding of the
     result (include/flute_amd.h, flute_qgemm_grouped_glu); nothing intermediate is written.  Returns [R, F] in
     input.dtype, rows no expert covers left unwritten.  The host reads neither `offsets` nor `rows` (no synchronise,
-    capturable); a native HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
+    capturable); a native HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits.
+    `pos` (`moe_route`'s [Tsrc, k] int32, the inverse of `rows`) is read by the backward only: with it the gradient of the
+    gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
+    if pos is not None:
+        if rows is None or pos.dtype != torch.int32:
+            raise TypeError
+        if pos.ndim != 2 or pos.shape[0] != Tsrc or pos.shape[0] * pos.shape[1] != R:
+            raise ValueError
+    if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
+        _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
+        return _GroupedGluFunction.apply(input, rows, pos, offsets, gate_weight, gate_scales, gate_table2, up_weight,
+                                         up_scales, up_table2, num_bits, group_size, template_id, num_sms)
     return _launch_grouped("qgemm_grouped_glu", (R, Tsrc), gate_weight, gate_scales.shape[1],
                            (input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2),
                            num_bits, group_size, template_id, num_sms)
+
+
+class _GroupedGluFunction(torch.autograd.Function):
+    """`qgemm_grouped_glu` under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
+    g and u with two plain grouped launches on the gathered rows, forms dg = dh u sigma(g) (1 + g (1 - sigma(g))) and
+    du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel."""
+
+    @staticmethod
+    def forward(ctx, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, num_bits, group_size, template_id, num_sms):
+        Tsrc = input.shape[0]
+        R = Tsrc if rows is None else rows.shape[0]
+        out = _launch_grouped("qgemm_grouped_glu", (R, Tsrc), gw, gs.shape[1],
+                              (input, rows, offsets, gw, gs, gt, uw, us, ut), num_bits, group_size, template_id, num_sms)
+        ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
+        ctx.has = (rows is not None, pos is not None)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return _zero_unserved_(out, offsets)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, offsets, gw, gs, gt, uw, us, ut, *index = ctx.saved_tensors
+        rows = index[0] if ctx.has[0] else None
+        pos = index[1] if ctx.has[1] else None
+        Tsrc = input.shape[0]
+        x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
+        launch = lambda w, sc, t2: _launch_grouped("qgemm_grouped", (x.shape[0],), w, sc.shape[1], (x, offsets, w, sc, t2),
+                                                   *ctx.layer)
+        g, u, dh = launch(gw, gs, gt).float(), launch(uw, us, ut).float(), grad_output.float()
+        sig = torch.sigmoid(g)
+        dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
+        du = (dh * (g * sig)).to(input.dtype)
+        dx = qgemm_grouped_input_grad(dg, offsets, gw, gs, gt, *ctx.layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
+        if rows is not None:
+            if pos is not None:
+                dx = moe_combine(dx, pos, offsets)
+            else:
+                dx = torch.zeros_like(input).index_add_(0, rows.clamp(0, Tsrc - 1).long(), dx)
+        return (dx,) + (None,) * 13
 
 
 def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size):
@@ -376,8 +470,125 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
     HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    if _records_grad(input, row_weight, scales, table2):
+        _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
+        return _GroupedWeightedFunction.apply(input, row_weight, offsets, weight, scales, table2, num_bits, group_size,
+                                              template_id, num_sms)
     return _launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, scales.shape[1],
                            (input, offsets, weight, scales, table2, row_weight), num_bits, group_size, template_id, num_sms)
+
+
+class _GroupedWeightedFunction(torch.autograd.Function):
+    """`qgemm_grouped_weighted` under autograd.  A row weight that needs no gradient rides in the input-gradient kernel's
+    epilogue (one launch); one that does takes dH' = input_grad(dY), d row_weight[r] = sum_k dH'[r, k] h[r, k] in fp32
+    (zero from offsets[E] on) and dH = round_T(row_weight dH')."""
+
+    @staticmethod
+    def forward(ctx, input, row_weight, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms):
+        out = _launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, scales.shape[1],
+                              (input, offsets, weight, scales, table2, row_weight), num_bits, group_size, template_id, num_sms)
+        ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
+        stack = (offsets, weight, scales, table2)
+        if not ctx.needs_input_grad[1]:
+            return (qgemm_grouped_input_grad(grad_output, *stack, *ctx.layer, row_weight=row_weight),) + (None,) * 9
+        R = input.shape[0]
+        dh = qgemm_grouped_input_grad(grad_output, *stack, *ctx.layer).float()
+        served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
+        # (a row no expert serves may hold anything in `input`: its dH' is zero, and the where keeps 0 x NaN out)
+        d_weight = torch.where(served, (dh * input.float()).sum(dim=1), torch.zeros((), device=input.device))
+        d_input = (row_weight[:, None] * dh).to(input.dtype) if ctx.needs_input_grad[0] else None
+        return (d_input, d_weight) + (None,) * 8
+
+
+def _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
+                                 grad_output2, weight2, scales2, table22):
+    if not all([grad_output.ndim == 2, offsets.ndim == 1, weight.ndim == 3, scales.ndim == 3, table2.ndim == 4]):
+        raise ValueError
+    if grad_output.dtype not in _DTYPE_ID or scales.dtype != grad_output.dtype:
+        raise TypeError
+    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
+        raise TypeError
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    E, N, K = scales.shape[0], scales.shape[1], weight.shape[2]
+    if not all([
+        grad_output.shape[1] == N,
+        weight.shape[0] == E,
+        K > 0 and K % max(64, group_size) == 0,
+        scales.shape[2] * group_size == K,
+        N > 0 and N % 16 == 0 and weight.shape[1] == num_bits * (N // 16),
+        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
+        offsets.shape[0] == E + 1,
+    ]):
+        raise ValueError
+    second = (grad_output2, weight2, scales2, table22)
+    if any(t is not None for t in second):
+        if any(t is None for t in second):
+            raise ValueError("qgemm_grouped_input_grad: the pair form needs grad_output2, weight2, scales2 and table22")
+        if row_weight is not None:
+            raise ValueError("qgemm_grouped_input_grad: the pair form takes no row_weight")
+        if grad_output2.dtype != grad_output.dtype or scales2.dtype != scales.dtype or weight2.dtype != torch.int16 or \
+                table22.dtype != torch.float32:
+            raise TypeError
+        if not all([tuple(grad_output2.shape) == tuple(grad_output.shape), tuple(weight2.shape) == tuple(weight.shape),
+                    tuple(scales2.shape) == tuple(scales.shape), tuple(table22.shape) == tuple(table2.shape)]):
+            raise ValueError
+    if row_weight is not None:
+        if row_weight.dtype != torch.float32:
+            raise TypeError
+        if row_weight.ndim != 1 or row_weight.shape[0] != grad_output.shape[0]:
+            raise ValueError
+
+
+def _grouped_input_grad_row_block():
+    return _lib.get().flute_qgemm_grouped_input_grad_row_block()
+
+
+GROUPED_INPUT_GRAD_ROW_BLOCK = _grouped_input_grad_row_block()      # include/flute_amd.h FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK
+
+
+def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                             table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                             row_weight=None, grad_output2=None, weight2=None, scales2=None, table22=None) -> torch.Tensor:
+    """The input gradient of `qgemm_grouped` in one launch: dX[r] = row_weight[r] * (grad_output[r] @ W_e) for the rows r in
+    [offsets[e], offsets[e + 1]), W_e [N, K] the dequantized weight of expert e (`flute_amd.dequantize`'s), the sum over
+    N in fp32 in the matrix core and one rounding to grad_output.dtype.  `grad_output` [R, N] holds the rows sorted by
+    expert; `offsets`, `weight` [E, P, K], `scales` [E, N, K / g], `table2` as `qgemm_grouped` takes them; `row_weight`
+    [R] fp32 or None (no multiply).  With `grad_output2`, `weight2`, `scales2`, `table22` - a second stack of the same
+    shape - the pair form: dX[r] = grad_output[r] @ W_e + grad_output2[r] @ W2_e, both sums added in fp32 before the one
+    rounding (the gradient of a row that fed `qgemm_grouped_glu`'s gate and up); it takes no `row_weight`.  Returns
+    [R, K]; the rows from offsets[E] on - rows no expert serves - are zeros, so every element is written.  A workgroup
+    walks an expert's rows in blocks of GROUPED_INPUT_GRAD_ROW_BLOCK.  The host never reads `offsets` (no synchronise,
+    capturable); a native HIP kernel on the current stream (qgemm_grouped_input_grad.h); equal arguments give equal
+    bits.  Not differentiable itself: it raises when grad mode is on and an argument requires grad."""
+    _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
+                                 grad_output2, weight2, scales2, table22)
+    tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
+    if _records_grad(*tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_input_grad: the backward is once-differentiable (no double backward)")
+    dev = grad_output.device
+    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
+        raise RuntimeError("flute_amd.qgemm_grouped_input_grad: all tensors must live on the same GPU")
+    R, N = grad_output.shape
+    E, P, K = weight.shape
+    if R >= 2 ** 31:
+        raise ValueError
+    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    out = torch.empty((R, K), dtype=grad_output.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_grouped_input_grad(
+            _DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P, template_id,
+            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
+    return out
 
 
 _INDEX_DTYPE_ID = {torch.int32: 0, torch.int64: 1}
@@ -413,6 +624,30 @@ def moe_route(topk_ids: torch.Tensor, topk_weights, num_experts: int):
     reads nothing (no synchronise, capturable); a native HIP kernel on the current stream (moe_route.hip); equal
     arguments give equal bits."""
     _validate_moe_route(topk_ids, topk_weights, num_experts)
+    if _records_grad(topk_weights):
+        return _MoeRouteFunction.apply(topk_ids, topk_weights, num_experts)
+    return _moe_route_call(topk_ids, topk_weights, num_experts)
+
+
+class _MoeRouteFunction(torch.autograd.Function):
+    """`moe_route` under autograd: row_weight is a permutation of topk_weights, so d topk_weights = d row_weight[pos]."""
+
+    @staticmethod
+    def forward(ctx, topk_ids, topk_weights, num_experts):
+        offsets, rows, row_weight, pos, perm = _moe_route_call(topk_ids, topk_weights, num_experts)
+        ctx.save_for_backward(pos)
+        ctx.dtype = topk_weights.dtype
+        ctx.mark_non_differentiable(offsets, rows, pos, perm)
+        return offsets, rows, row_weight, pos, perm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_offsets, d_rows, d_row_weight, d_pos, d_perm):
+        (pos,) = ctx.saved_tensors
+        return None, d_row_weight.index_select(0, pos.reshape(-1).long()).view(pos.shape).to(ctx.dtype), None
+
+
+def _moe_route_call(topk_ids, topk_weights, num_experts):
     dev = topk_ids.device
     if not all(t.is_cuda and t.device == dev for t in (topk_ids,) + (() if topk_weights is None else (topk_weights,))):
         raise RuntimeError("flute_amd.moe_route: all tensors must live on the same GPU")
@@ -485,6 +720,45 @@ def _moe_gate_call(name, logits, k, scoring, renormalize, bias, scale, routed):
     return ids, weights, offsets, rows, row_weight, pos, perm
 
 
+class _MoeGateFunction(torch.autograd.Function):
+    """The gating ops under autograd: `ids` (and the routing arrays) stay non-differentiable, `weights` - and `row_weight`,
+    a permutation of it - get a gradient to `logits`.  The backward differentiates the documented formula in fp32 with
+    the kernel's ids held fixed: softmax over all E (or the sigmoid), the gather of the chosen, the optional division by
+    their sum, times `scale`; the bias enters the choice only."""
+
+    @staticmethod
+    def forward(ctx, logits, run, scoring, renormalize, scale):
+        outs = run()
+        routed = len(outs) > 2
+        ctx.save_for_backward(logits, outs[0], *((outs[5],) if routed else ()))
+        ctx.formula = (scoring, bool(renormalize), float(scale))
+        ctx.mark_non_differentiable(*[o for o in outs if not o.is_floating_point()])
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        logits, ids, *rest = ctx.saved_tensors
+        scoring, renormalize, scale = ctx.formula
+        d_weights = grads[1]
+        if rest:                                                # row_weight[i] = weights.flatten()[perm[i]], pos the inverse of perm
+            d_weights = d_weights + grads[4].index_select(0, rest[0].reshape(-1).long()).view_as(d_weights)
+        with torch.enable_grad():
+            x = logits.detach().float().requires_grad_(True)
+            s = torch.softmax(x, dim=1) if scoring == "softmax" else torch.sigmoid(x)
+            w = s.gather(1, ids.long())
+            if renormalize:
+                w = w / w.sum(dim=1, keepdim=True)
+            (dx,) = torch.autograd.grad(w * scale, x, d_weights)
+        return dx.to(logits.dtype), None, None, None, None
+
+
+def _moe_gate_op(logits, run, scoring, renormalize, scale):
+    if _records_grad(logits):
+        return _MoeGateFunction.apply(logits, run, scoring, renormalize, scale)
+    return run()
+
+
 def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
              scale: float = 1.0):
     """The gating of a mixture-of-experts step in one launch: from the router's `logits` [T, E] (fp16 / bf16 / fp32) to
@@ -497,7 +771,8 @@ def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize
     selection (n_group, topk_group) is `moe_gate_limited`.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
     stream (moe_gate.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
     _validate_moe_gate(logits, k, scoring, bias)
-    return _moe_gate_call("moe_gate", logits, k, scoring, renormalize, bias, scale, routed=False)
+    return _moe_gate_op(logits, lambda: _moe_gate_call("moe_gate", logits, k, scoring, renormalize, bias, scale, routed=False),
+                        scoring, renormalize, scale)
 
 
 def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str = "softmax", renormalize: bool = False,
@@ -507,7 +782,8 @@ def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str 
     `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves gates the tokens and sorts the
     pairs: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     _validate_moe_gate(logits, k, scoring, bias, num_experts)
-    return _moe_gate_call("moe_gate_route", logits, k, scoring, renormalize, bias, scale, routed=True)
+    return _moe_gate_op(logits, lambda: _moe_gate_call("moe_gate_route", logits, k, scoring, renormalize, bias, scale,
+                                                       routed=True), scoring, renormalize, scale)
 
 
 _GATE_GROUP_SCORE_ID = {"max": 0, "top2sum": 1}     # include/flute_amd.h flute_gate_group_score
@@ -572,8 +848,9 @@ def moe_gate_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int
     fp32); no host synchronise (capturable), a native HIP kernel on the current stream (moe_gate.hip), equal arguments
     give equal bits."""
     _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score)
-    return _moe_gate_limited_call("moe_gate_limited", logits, k, n_group, topk_group, group_score, scoring, renormalize,
-                                  bias, scale, routed=False)
+    return _moe_gate_op(logits, lambda: _moe_gate_limited_call("moe_gate_limited", logits, k, n_group, topk_group, group_score,
+                                                               scoring, renormalize, bias, scale, routed=False),
+                        scoring, renormalize, scale)
 
 
 def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int, num_experts=None,
@@ -584,8 +861,9 @@ def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_grou
     `moe_route(ids, weights, E)`'s.  `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves, as
     `moe_gate_route`: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score, num_experts)
-    return _moe_gate_limited_call("moe_gate_route_limited", logits, k, n_group, topk_group, group_score, scoring,
-                                  renormalize, bias, scale, routed=True)
+    return _moe_gate_op(logits, lambda: _moe_gate_limited_call("moe_gate_route_limited", logits, k, n_group, topk_group,
+                                                               group_score, scoring, renormalize, bias, scale, routed=True),
+                        scoring, renormalize, scale)
 
 
 def _validate_moe_combine(y, pos, offsets):
@@ -607,6 +885,38 @@ def moe_combine(y: torch.Tensor, pos: torch.Tensor, offsets: torch.Tensor) -> to
     with no served slot is zeros).  No atomics: equal arguments give equal bits for every k.  No host synchronise; a
     native HIP kernel on the current stream (moe_combine.hip)."""
     _validate_moe_combine(y, pos, offsets)
+    if _records_grad(y):
+        return _MoeCombineFunction.apply(y, pos, offsets)
+    return _moe_combine_call(y, pos, offsets)
+
+
+class _MoeCombineFunction(torch.autograd.Function):
+    """`moe_combine` under autograd: a gather, dY[r] = dOut[token of sorted row r] for the rows below offsets[E], zero from
+    there on (the forward never reads those)."""
+
+    @staticmethod
+    def forward(ctx, y, pos, offsets):
+        ctx.save_for_backward(pos, offsets)
+        return _moe_combine_call(y, pos, offsets)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        pos, offsets = ctx.saved_tensors
+        T, k = pos.shape
+        R = T * k
+        dev = pos.device
+        p = pos.reshape(-1).long()
+        inside = (p >= 0) & (p < R)
+        token = torch.arange(T, device=dev).repeat_interleave(k)
+        # the token of every sorted row (pos is a permutation of the rows; an entry outside [0, R) names no row)
+        rows = torch.full((R + 1,), T, dtype=torch.long, device=dev).scatter_(0, torch.where(inside, p, R), token)[:R]
+        named = (rows < T) & (torch.arange(R, device=dev) < offsets[-1].clamp(0, R))
+        dy = grad_output.index_select(0, rows.clamp(max=T - 1))
+        return dy.masked_fill_(~named[:, None], 0), None, None
+
+
+def _moe_combine_call(y, pos, offsets):
     dev = y.device
     if not all(t.is_cuda and t.device == dev for t in (y, pos, offsets)):
         raise RuntimeError("flute_amd.moe_combine: all tensors must live on the same GPU")

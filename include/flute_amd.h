@@ -26,7 +26,7 @@ extern "C" {
 /* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
  *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
  *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring; flute_moe_gate_limited and flute_moe_gate_route_limited with
- *    flute_gate_group_score
+ *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block
  *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -321,6 +321,40 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream);
+
+/* The input gradient of flute_qgemm_grouped and of the fused forms built on it, in ONE launch: a grouped GEMM over the
+ * packed stacks that contracts over N where the forward contracts over K.
+ *   dX[r, :] = round_T( w_r * sum_n dY[r, n] * w^_e[n, :] )   for every row r in [offsets[e], offsets[e + 1]), e < E,
+ * w^ = round_T(QM2-pair-lookup * scale) exactly as flute_dequantize and every MFMA kernel form it, products and sums in
+ * fp32 in the matrix core, ONE rounding to T; w_r = row_weight[r] (fp32, device memory), or no multiply when row_weight
+ * is null.  dY [R, N] T holds the rows sorted by expert; offsets [E + 1] int32 in DEVICE memory; Q [E, P, K] / S [E, N,
+ * K / group_size] / QM2 [E, 2^b, 2^b] as flute_qgemm_grouped takes them; dX [R, K] T.
+ * Pair form (dY2, Q2, S2, QM22 all non-null; a second stack of the same shape, num_bits, group_size and template_id):
+ *   dX[r, :] = round_T( sum_n dY[r, n] * w^(1)_e[n, :] + sum_n dY2[r, n] * w^(2)_e[n, :] ),
+ * both sums added in fp32 (one accumulator: the first stack's columns, then the second's) before the one rounding - the
+ * gradient of a row that fed both the gate and the up projection of flute_qgemm_grouped_glu.  It takes no row_weight.
+ * The rows [clamp(offsets[E]), R) - rows no expert serves - are written as zeros by the same launch whatever the routing:
+ * every element of dX is written whenever offsets is a proper table (0 first, non-decreasing, at most R).  Every row
+ * index formed is clamped to [0, R]: a malformed table is memory-safe and leaves only the rows it names twice or skips
+ * unspecified.  Expert and row bases are 64-bit.
+ * A workgroup is (expert, 128 k); it walks the expert's rows in blocks of FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK rows and all
+ * of N per block in a fixed order: no atomics, no split of the N reduction across workgroups, equal arguments give equal
+ * bits.  The host never reads offsets: the grid is E x ceil(K / 128), from the shapes alone (num_sms is accepted for
+ * symmetry and not used), so the launch is hipGraph-capturable and a replay serves what the table then holds.  A
+ * workgroup whose expert has no rows requests no weight, scale or table word.
+ * Supported layers are flute_qgemm_grouped's: 4 / 3 / 2 bits, TileP 32 / 64 (3 bits: 32), group sizes 32 / 64 / 128 / 256,
+ * fp16 / bf16, K % max(64, group_size) == 0, N a multiple of the template's column block.
+ * Refusals, before anything is enqueued and in this order: flute_qgemm_grouped's (dtype, the layer checks, FLUTE_ERR_SHAPE
+ * for P or a negative E / R), FLUTE_ERR_SHAPE for a row_weight together with any pointer of the pair form; R == 0 returns
+ * FLUTE_OK and enqueues nothing; then FLUTE_ERR_NULL for a null dX, and - with E > 0 - for a null dY / offsets / Q / S /
+ * QM2 or a pair form given in part.  E == 0 with R > 0 writes dX as zeros (a memset node). */
+#define FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK 128
+int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                   const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                   const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
+/* FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK of the library that is loaded */
+int flute_qgemm_grouped_input_grad_row_block(void);
 
 /* The routing of a mixture-of-experts step in ONE launch: from the router's choice to every array the grouped launches
  * and flute_moe_combine read.  ids [T, k] int32 or int64 (id_dtype: flute_index_dtype; torch.topk returns int64), weights

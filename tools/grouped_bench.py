@@ -5,6 +5,7 @@
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
+    python tools/grouped_bench.py --mode input_grad [--processes 3] [--out profiles/grouped_moe_input_grad.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -46,6 +47,16 @@ FluteExperts(fused=True, native_routing=True).forward against FluteSparseMoeBloc
 top-2 sum, sigmoid + bias, renormalised, scale 2.5, fp16 logits) by --mode gate's method, in one process: moe_gate_limited,
 moe_gate at the same (E, k) - the difference is the cost of the group stage - and the torch-op chain for the same selection
 (view / topk / sum / topk / scatter / masked_fill / topk / gather / sum / div).
+
+--mode input_grad times the grouped input-gradient kernel (qgemm_grouped_input_grad.h), dX = dY @ W_e per expert in one launch,
+at training-sized row counts: W4G64 fp16 at Mixtral's two projections (E = 8, K = 4096, F = 14336) with 512 and 4096 routed
+rows and at a many-expert shape (E = 64, K = 2048, F = 1408, 4096 rows), against the only alternative there was: a per-expert
+loop of flute_amd.dequantize + torch.mm with the row counts known on the host (its best case).  Same method: a hipGraph of
+steps between device-clock stamps, rotating copies of the stacks, cold caches, the median of five replays, two alternating
+passes of each form, three fresh processes.  Reported: both times, the ratio, the achieved FLOP/s against 2.5 PFLOP/s, the
+spread.  A last row splits one whole backward step of FluteExperts(fused=True, native_routing=True) at 512 tokens into its
+launches (down's input gradient with the routing weight in its epilogue, the recompute of gate and up through the grouped
+forward, the fp32 elementwise dg / du, the pair-form input gradient, moe_combine).
 """
 import argparse
 import json
@@ -502,6 +513,197 @@ def main_gate_limited(args, device):
     print("wrote", args.out)
 
 
+# ---- --mode input_grad ------------------------------------------------------------------------------------------------
+PEAK_FLOPS = 2.5e15
+IG_SHAPES = [("mixtral gate_up", 8, 14336, 4096, 512), ("mixtral gate_up", 8, 14336, 4096, 4096),
+             ("mixtral down", 8, 4096, 14336, 512), ("mixtral down", 8, 4096, 14336, 4096),
+             ("many-expert gate_up", 64, 1408, 2048, 4096), ("many-expert down", 64, 2048, 1408, 4096)]
+
+
+def ig_counts(rows, experts, seed):
+    """Row counts of `rows` routed rows over `experts` experts, drawn as a top-2 router would spread them."""
+    gen = torch.Generator().manual_seed(seed)
+    ids = torch.rand(rows // 2, experts, generator=gen).topk(2, dim=1).indices
+    return torch.bincount(ids.reshape(-1), minlength=experts).tolist()
+
+
+class InputGrad:
+    """`copies` stacks of `experts` packed layers [N, K]; step(i) is dX [R, K] = dY [R, N] @ W_e on copy i: one grouped launch, or
+    the per-expert loop of dequantize + mm on row ranges the host knows."""
+
+    def __init__(self, experts, N, K, counts, copies, device, grouped):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.N, self.K, self.counts, self.grouped = flute_amd, N, K, counts, grouped
+        self.num_sms = utils.get_device_num_sms(device)
+        gen = torch.Generator(device=device).manual_seed(1)
+        self.Q = torch.randint(-2 ** 15, 2 ** 15, (copies, experts, BITS * N // 16, K), dtype=torch.int16, device=device, generator=gen)
+        self.S = (torch.rand(copies, experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(DTYPE)
+        table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
+        self.table2 = utils.make_qmap2_from_qmap(table)
+        self.tables2 = self.table2.repeat(experts, 1, 1, 1)
+        self.dY = torch.randn(sum(counts), N, device=device, generator=gen).to(DTYPE)
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + c)
+        self.off_host = off
+        self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+
+    def step(self, i):
+        c = i % self.Q.shape[0]
+        if self.grouped:
+            return self.fa.qgemm_grouped_input_grad(self.dY, self.offsets, self.Q[c], self.S[c], self.tables2, BITS, G, self.tid,
+                                                    self.num_sms)
+        out = []
+        for e, m in enumerate(self.counts):
+            if m:
+                W = self.fa.dequantize(self.Q[c, e], self.S[c, e], self.table2, BITS, G, self.tid)         # [N, K]
+                out.append(torch.mm(self.dY[self.off_host[e]:self.off_host[e + 1]], W))
+        return out
+
+    def flops(self):
+        return 2.0 * sum(self.counts) * self.N * self.K
+
+
+class BackwardStep:
+    """The launches of one backward step of FluteExperts(fused=True, native_routing=True) at `tokens` tokens (top-2, Mixtral's
+    shapes), by hand, so that each can be timed alone: `part` selects one, None runs them in the backward's order."""
+    PARTS = ("down_input_grad", "recompute_gate_up", "elementwise_dg_du", "pair_input_grad", "moe_combine")
+
+    def __init__(self, stacks, tokens, device, part=None):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.part = flute_amd, part
+        self.stacks = stacks                                       # step_stacks: (gate, up, down) GroupedFluteLinear per copy
+        self.num_sms = utils.get_device_num_sms(device)
+        K, F = 4096, 14336
+        gen = torch.Generator(device=device).manual_seed(2)
+        ids = torch.rand(tokens, E, device=device, generator=gen).topk(TOPK, dim=1).indices
+        weights = torch.rand(tokens, TOPK, device=device, generator=gen)
+        self.offsets, self.rows, self.row_weight, self.pos, _ = flute_amd.moe_route(ids, weights, E)
+        R = tokens * TOPK
+        self.hidden = torch.randn(tokens, K, device=device, generator=gen).to(DTYPE)
+        self.x = self.hidden[self.rows.long()]
+        self.dY = torch.randn(R, K, device=device, generator=gen).to(DTYPE)
+        self.dH = torch.randn(R, F, device=device, generator=gen).to(DTYPE)
+        self.g = torch.randn(R, F, device=device, generator=gen).to(DTYPE)
+        self.u = torch.randn(R, F, device=device, generator=gen).to(DTYPE)
+        self.dx = torch.randn(R, K, device=device, generator=gen).to(DTYPE)
+
+    def step(self, i):
+        gate, up, down = self.stacks[i % len(self.stacks)]
+        fa, off, t2, a = self.fa, self.offsets, gate.tables2, (BITS, G, gate.template_id, self.num_sms)
+        (Qg, Sg), (Qu, Su), (Qd, Sd) = (gate.weight, gate.scales), (up.weight, up.scales), (down.weight, down.scales)
+        run = lambda name: self.part in (None, name)
+        dH, g, u, dx = self.dH, self.g, self.u, self.dx
+        if run("down_input_grad"):
+            dH = fa.qgemm_grouped_input_grad(self.dY, off, Qd, Sd, t2, *a, row_weight=self.row_weight)
+        if run("recompute_gate_up"):
+            x = self.hidden[self.rows.long()] if self.part is None else self.x
+            g, u = fa.qgemm_grouped(x, off, Qg, Sg, t2, *a), fa.qgemm_grouped(x, off, Qu, Su, t2, *a)
+        if run("elementwise_dg_du"):
+            gf, uf, dh = g.float(), u.float(), dH.float()
+            sig = torch.sigmoid(gf)
+            dg, du = (dh * uf * sig * (1 + gf * (1 - sig))).to(DTYPE), (dh * (gf * sig)).to(DTYPE)
+        else:
+            dg, du = self.g, self.u
+        if run("pair_input_grad"):
+            dx = fa.qgemm_grouped_input_grad(dg, off, Qg, Sg, t2, *a, grad_output2=du, weight2=Qu, scales2=Su, table22=t2)
+        if run("moe_combine"):
+            dx = fa.moe_combine(dx, self.pos, off)
+        return dx
+
+
+def child_input_grad(args, device):
+    rows = []
+    for name, experts, N, K, nrows in IG_SHAPES:
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        per_copy = experts * ((BITS * N // 16) * K * 2 + N * (K // G) * 2)
+        copies = max(2, bench.L3_BYTES // per_copy + 2)
+        grouped = InputGrad(experts, N, K, counts, copies, device, grouped=True)
+        loop = InputGrad(experts, N, K, counts, copies, device, grouped=False)
+        a = grouped.step(0)
+        b = torch.cat(loop.step(0))
+        torch.cuda.synchronize()
+        diff, ref = float((a.float() - b.float()).abs().max()), float(b.float().abs().max())
+        m = [measure(layer, args) for layer in (grouped, loop, grouped, loop)]
+        g_us, l_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+        row = {"what": "input_grad", "shape": name, "experts": experts, "N": N, "K": K, "rows": sum(counts), "counts_min_max":
+               [min(counts), max(counts)], "weight_copies": copies, "grouped_us": round(g_us, 3), "loop_us": round(l_us, 3),
+               "grouped_over_loop": round(g_us / l_us, 4), "flop": grouped.flops(),
+               "grouped_share_of_2.5PFLOPs": round(grouped.flops() / (g_us * 1e-6) / PEAK_FLOPS, 4),
+               "loop_share_of_2.5PFLOPs": round(grouped.flops() / (l_us * 1e-6) / PEAK_FLOPS, 4),
+               "spread": max(p["spread"] for p in m), "max_abs_diff_grouped_vs_loop": diff, "max_abs_loop": ref, "passes": m}
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
+        del grouped, loop, a, b
+        torch.cuda.empty_cache()
+    per_copy = 3 * E * ((BITS * 14336 // 16) * 4096 * 2 + 14336 * (4096 // G) * 2)
+    copies = max(2, bench.L3_BYTES // per_copy + 2)
+    stacks = step_stacks(copies, device)
+    parts = {}
+    for part in (None,) + BackwardStep.PARTS:
+        layer = BackwardStep(stacks, 512, device, part)
+        layer.step(0)
+        torch.cuda.synchronize()
+        m = [measure(layer, args) for _ in range(2)]
+        parts["whole" if part is None else part] = {"us": round((m[0]["us"] + m[1]["us"]) / 2, 3),
+                                                    "spread": max(p["spread"] for p in m), "passes": m}
+    row = {"what": "backward step", "tokens": 512, "rows": 512 * TOPK, "experts": E, "top_k": TOPK, "weight_copies": copies,
+           "parts": parts}
+    rows.append(row)
+    print(json.dumps({"what": row["what"], "tokens": 512, "us": {k: v["us"] for k, v in parts.items()}}), flush=True)
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
+
+
+def main_input_grad(args):
+    """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
+    spread of any pass in any process."""
+    runs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i in range(args.processes):
+            path = os.path.join(tmp, "p%d.json" % i)
+            cmd = [sys.executable, os.path.abspath(__file__), "--mode", "input_grad", "--child", "--out", path, "--steps",
+                   str(args.steps), "--warmup", str(args.warmup), "--replays", str(args.replays)]
+            subprocess.run(cmd, check=True)
+            with open(path) as f:
+                runs.append(json.load(f))
+    median = lambda v: sorted(v)[len(v) // 2]
+    rows = []
+    for i, first in enumerate(runs[0]["rows"]):
+        per = [r["rows"][i] for r in runs]
+        if first["what"] == "input_grad":
+            g_us, l_us = median([p["grouped_us"] for p in per]), median([p["loop_us"] for p in per])
+            row = {k: first[k] for k in ("what", "shape", "experts", "N", "K", "rows", "counts_min_max", "weight_copies", "flop")}
+            row.update(grouped_us=g_us, loop_us=l_us, grouped_over_loop=round(g_us / l_us, 4),
+                       grouped_TFLOPs=round(first["flop"] / g_us * 1e-6, 1), loop_TFLOPs=round(first["flop"] / l_us * 1e-6, 1),
+                       grouped_share_of_2_5_PFLOPs=round(first["flop"] / (g_us * 1e-6) / PEAK_FLOPS, 4),
+                       loop_share_of_2_5_PFLOPs=round(first["flop"] / (l_us * 1e-6) / PEAK_FLOPS, 4),
+                       spread=max(p["spread"] for p in per), per_process_grouped_us=[p["grouped_us"] for p in per],
+                       per_process_loop_us=[p["loop_us"] for p in per],
+                       max_abs_diff_grouped_vs_loop=max(p["max_abs_diff_grouped_vs_loop"] for p in per),
+                       max_abs_loop=first["max_abs_loop"], replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
+        else:
+            row = {k: first[k] for k in ("what", "tokens", "rows", "experts", "top_k", "weight_copies")}
+            row["parts_us"] = {k: median([p["parts"][k]["us"] for p in per]) for k in first["parts"]}
+            row["parts_spread"] = {k: max(p["parts"][k]["spread"] for p in per) for k in first["parts"]}
+            row["per_process_parts_us"] = [{k: v["us"] for k, v in p["parts"].items()} for p in per]
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+    out = {"what": "grouped input gradient (one launch) vs a per-expert loop of dequantize + mm with host-known row counts; and one "
+                   "backward step of FluteExperts(fused=True, native_routing=True) split into its launches; hipGraph replays, "
+                   "device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
+           "config": {"bits": BITS, "group_size": G, "dtype": "float16", "steps": args.steps, "warmup": args.warmup,
+                      "replays": args.replays, "processes": args.processes, "device": runs[0]["device"]},
+           "rows": rows}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def measure(layer, args):
     us, _ = bench.time_graph(layer, args.steps, args.warmup, torch.cuda.synchronize, cold=True, replays=args.replays)
     t = dict(bench.LAST_TIMING)
@@ -517,7 +719,7 @@ def main():
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
-    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited"], default="projection")
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad"], default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
@@ -526,7 +728,14 @@ def main():
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
                                                    "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json",
-                                                   "gate_limited": "grouped_moe_gate_limited.json"}[args.mode])
+                                                   "gate_limited": "grouped_moe_gate_limited.json",
+                                                   "input_grad": "grouped_moe_input_grad.json"}[args.mode])
+    if args.mode == "input_grad":
+        if not args.child:
+            return main_input_grad(args)             # the parent never opens the GPU
+        device = torch.device("cuda", 0)
+        torch.cuda.set_device(device)
+        return child_input_grad(args, device)
     if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
