@@ -1746,78 +1746,74 @@ int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const v
                               reinterpret_cast<hipStream_t>(stream));
 }
 
-// the refusals flute_moe_gate and flute_moe_gate_route share, in their order: dtype and scoring, then shape
-static int check_moe_gate(int logit_dtype, int T, int E, int k, int scoring) {
+// the refusals the four gating entry points share, in their order: dtype, scoring and (g non-null: the group-limited forms) group_score,
+// then the shapes, then the groups'
+static int check_moe_gate(int logit_dtype, int T, int E, int k, const GateGroups* g, int scoring) {
     if (logit_dtype != FLUTE_F16 && logit_dtype != FLUTE_BF16 && logit_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
     if (scoring != FLUTE_GATE_SOFTMAX && scoring != FLUTE_GATE_SIGMOID) return FLUTE_ERR_DTYPE;
+    if (g && g->group_score != FLUTE_GATE_GROUP_MAX && g->group_score != FLUTE_GATE_GROUP_TOP2SUM) return FLUTE_ERR_DTYPE;
     if (T < 0 || k < 1 || k > E || k > FLUTE_MOE_GATE_MAX_TOPK || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
     if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    if (!g) return FLUTE_OK;
+    if (g->n_group < 1 || g->n_group > FLUTE_MOE_GATE_MAX_GROUPS) return FLUTE_ERR_SHAPE;
+    if (E % g->n_group) return FLUTE_ERR_SHAPE;
+    if (g->topk_group < 1 || g->topk_group > g->n_group) return FLUTE_ERR_SHAPE;
+    const int gs = E / g->n_group;
+    if (k > g->topk_group * gs) return FLUTE_ERR_SHAPE;         // topk_group gs <= E <= 1024
+    if (g->group_score == FLUTE_GATE_GROUP_TOP2SUM && gs < 2) return FLUTE_ERR_SHAPE;
     return FLUTE_OK;
+}
+
+// the standalone form behind flute_moe_gate (g null) and flute_moe_gate_limited
+static int moe_gate_alone(int logit_dtype, int T, int E, int k, const GateGroups* g, int scoring, int renormalize, float scale,
+                          const void* logits, const float* bias, int32_t* ids, float* weights, void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, g, scoring);
+    if (rc) return rc;
+    if (T == 0) return FLUTE_OK;
+    if (!logits || !ids || !weights) return FLUTE_ERR_NULL;
+    return moe_gate_dispatch(logit_dtype, T, E, k, g, scoring, renormalize, scale, logits, bias, ids, weights, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the routed form behind flute_moe_gate_route (g null) and flute_moe_gate_route_limited
+static int moe_gate_routed(int logit_dtype, int T, int E, int k, const GateGroups* g, int scoring, int renormalize, float scale,
+                           const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
+                           int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, g, scoring);
+    if (rc) return rc;
+    if (T == 0 && !offsets) return FLUTE_OK;                    // no token and nowhere to write the E + 1 zeros
+    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
+    if (!offsets) return FLUTE_ERR_NULL;
+    return moe_gate_dispatch(logit_dtype, T, E, k, g, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
+                             rows, row_weight, pos, reinterpret_cast<hipStream_t>(stream));
 }
 
 int flute_moe_gate(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
                    const float* bias, int32_t* ids, float* weights, void* stream) {
-    const int rc = check_moe_gate(logit_dtype, T, E, k, scoring);
-    if (rc) return rc;
-    if (T == 0) return FLUTE_OK;
-    if (!logits || !ids || !weights) return FLUTE_ERR_NULL;
-    return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+    return moe_gate_alone(logit_dtype, T, E, k, nullptr, scoring, renormalize, scale, logits, bias, ids, weights, stream);
 }
 
 int flute_moe_gate_route(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale,
                          const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets,
                          int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
-    const int rc = check_moe_gate(logit_dtype, T, E, k, scoring);
-    if (rc) return rc;
-    if (T == 0 && !offsets) return FLUTE_OK;                    // no token and nowhere to write the E + 1 zeros
-    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
-    if (!offsets) return FLUTE_ERR_NULL;
-    return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
-                             rows, row_weight, pos, reinterpret_cast<hipStream_t>(stream));
-}
-
-// the refusals of the group-limited forms, in their order: dtype, scoring and group_score, then flute_moe_gate's shapes, then the groups'
-static int check_moe_gate_limited(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score,
-                                  int scoring) {
-    if (logit_dtype != FLUTE_F16 && logit_dtype != FLUTE_BF16 && logit_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
-    if (scoring != FLUTE_GATE_SOFTMAX && scoring != FLUTE_GATE_SIGMOID) return FLUTE_ERR_DTYPE;
-    if (group_score != FLUTE_GATE_GROUP_MAX && group_score != FLUTE_GATE_GROUP_TOP2SUM) return FLUTE_ERR_DTYPE;
-    const int rc = check_moe_gate(logit_dtype, T, E, k, scoring);
-    if (rc) return rc;
-    if (n_group < 1 || n_group > FLUTE_MOE_GATE_MAX_GROUPS) return FLUTE_ERR_SHAPE;
-    if (E % n_group) return FLUTE_ERR_SHAPE;
-    if (topk_group < 1 || topk_group > n_group) return FLUTE_ERR_SHAPE;
-    const int gs = E / n_group;
-    if (k > topk_group * gs) return FLUTE_ERR_SHAPE;            // topk_group gs <= E <= 1024
-    if (group_score == FLUTE_GATE_GROUP_TOP2SUM && gs < 2) return FLUTE_ERR_SHAPE;
-    return FLUTE_OK;
+    return moe_gate_routed(logit_dtype, T, E, k, nullptr, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
+                           rows, row_weight, pos, stream);
 }
 
 int flute_moe_gate_limited(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
                            int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
                            void* stream) {
-    const int rc = check_moe_gate_limited(logit_dtype, T, E, k, n_group, topk_group, group_score, scoring);
-    if (rc) return rc;
-    if (T == 0) return FLUTE_OK;
-    if (!logits || !ids || !weights) return FLUTE_ERR_NULL;
-    return moe_gate_limited_dispatch(logit_dtype, T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits,
-                                     bias, ids, weights, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     reinterpret_cast<hipStream_t>(stream));
+    const GateGroups g = {n_group, topk_group, group_score};
+    return moe_gate_alone(logit_dtype, T, E, k, &g, scoring, renormalize, scale, logits, bias, ids, weights, stream);
 }
 
 int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
                                  int renormalize, float scale, const void* logits, const float* bias, int32_t* ids,
                                  float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
                                  void* stream) {
-    const int rc = check_moe_gate_limited(logit_dtype, T, E, k, n_group, topk_group, group_score, scoring);
-    if (rc) return rc;
-    if (T == 0 && !offsets) return FLUTE_OK;                    // no token and nowhere to write the E + 1 zeros
-    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
-    if (!offsets) return FLUTE_ERR_NULL;
-    return moe_gate_limited_dispatch(logit_dtype, T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits,
-                                     bias, ids, weights, offsets, perm, rows, row_weight, pos,
-                                     reinterpret_cast<hipStream_t>(stream));
+    const GateGroups g = {n_group, topk_group, group_score};
+    return moe_gate_routed(logit_dtype, T, E, k, &g, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
+                           row_weight, pos, stream);
 }
 
 int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,

@@ -103,15 +103,15 @@ FLUTE_IG_DISPATCH(2);
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,
                        int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
 // the gating in front of it (moe_gate.hip): logits [T, E] -> ids [T, k] int32, weights [T, k] fp32, one wave per token; with offsets non-null
-// the routed form: one workgroup of 16 waves gates every token and then runs moe_route's counting sort on what it wrote
-int moe_gate_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
-                      const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows,
-                      float* row_weight, int32_t* pos, hipStream_t stream);
-// the same with group-limited selection (n_group groups of E / n_group experts, the topk_group best by group_score allowed); the caller has
-// checked the shapes; topk_group == n_group is served by moe_gate_dispatch's kernels
-int moe_gate_limited_dispatch(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
-                              int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
-                              int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
+// the routed form: one workgroup of 16 waves gates every token and then runs moe_route's counting sort on what it wrote.  groups non-null:
+// group-limited selection (n_group groups of E / n_group experts, the topk_group best by group_score allowed); the caller has checked the
+// shapes; topk_group == n_group is served by the kernels without the group stage, as groups == null is
+struct GateGroups {
+    int n_group, topk_group, group_score;
+};
+int moe_gate_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
+                      const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
+                      int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
 // its end (moe_combine.hip): out[t] = round_T(fp32 sum over the slots of Y[pos[t, j]]), positions outside [0, clamp(offsets[E])) skipped;
 // the grid is tokens x chunks of 1024 columns (0: it does not fit)
 unsigned moe_combine_grid(int T, int N);

@@ -22,16 +22,16 @@
 //   moe_gate_route_kernel  one workgroup of 16 waves (moe_route_kernel's design point): wave w takes tokens w, w + 16, ...,
 //                          then a barrier, then the count / scan / place phases of moe_route_sort.h on the ids and
 //                          weights just written (same CU, workgroup-scope fence before the barrier).
-// Group-limited selection (flute_moe_gate_limited / flute_moe_gate_route_limited) is the same device function with one more stage
-// between key and choice, compiled in by its LIMITED parameter (the unlimited kernels instantiate it without: their code is what
-// it was):
+// Group-limited selection (flute_moe_gate_limited / flute_moe_gate_route_limited) is the same two kernels with their LIMITED
+// parameter set: gate_token then has one more stage between key and choice (without LIMITED it is not compiled in, and the
+// kernels' group arguments, the last of their list, are not read):
 //   groups  a wave-uniform loop over the n_group groups.  Group g is experts g gs .. (g + 1) gs - 1, a run of lanes that may
 //           straddle registers, so each pass is a wave maximum of the keys under the mask lo <= e < hi.  For the top-2 sum a
 //           second maximum follows with the lowest holder of the first left out; the two come back from key to float order and
 //           are added once.  Lane g keeps group g's key.
 //   pick    topk_group rounds of "largest group key, lowest lane by ballot"; each winner's experts are marked allowed, and
 //           afterwards the key of every expert not allowed becomes 0, "no expert here": the k rounds run unchanged.
-//   moe_gate_limited_kernel / moe_gate_route_limited_kernel are the two kernels above with these arguments.
+// One host path serves the four entry points (moe_gate_dispatch): LIMITED, the class NV and the logit type are its three choices.
 // No atomics on global memory, plain vector stores, nothing read on the host.
 #include "kernels.h"
 #include "moe_route_sort.h"
@@ -276,173 +276,103 @@ static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::t
     }
 }
 
-template <typename L, int NV>
+// ---- the two kernels ----------------------------------------------------------------------------------------------------------
+// LIMITED picks gate_token's instantiation.  The group arguments come last: every other argument sits where it sits without them,
+// and an instantiation without LIMITED does not read them.
+template <typename L, int NV, bool LIMITED>
 __global__ __launch_bounds__(kGateThreads) void moe_gate_kernel(const typename GateLogit<L>::type* __restrict__ logits,
                                                                 const float* __restrict__ bias, int T, int E, int k,
                                                                 int scoring, int renormalize, float scale,
-                                                                int32_t* __restrict__ ids, float* __restrict__ weights) {
+                                                                int32_t* __restrict__ ids, float* __restrict__ weights,
+                                                                GateGroups g) {
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = blockIdx.x * kGateWaves + w;          // T k < 2^27, k >= 1: the grid is below 2^25 and t fits an int
     if (t >= T) return;                                 // the whole wave leaves
-    gate_token<L, NV, false>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, 0, 0, 0, 0, lane,
-                             ids + (size_t)t * k, weights + (size_t)t * k);
+    gate_token<L, NV, LIMITED>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, g.n_group,
+                               LIMITED ? E / g.n_group : 0, g.topk_group, g.group_score, lane, ids + (size_t)t * k,
+                               weights + (size_t)t * k);
 }
 
-template <typename L, int NV>
+template <typename L, int NV, bool LIMITED>
 __global__ __launch_bounds__(kRouteThreads) void moe_gate_route_kernel(const typename GateLogit<L>::type* __restrict__ logits,
                                                                        const float* __restrict__ bias, int T, int E, int k,
                                                                        int scoring, int renormalize, float scale, int nbits,
                                                                        int32_t* ids, float* weights,
                                                                        int32_t* __restrict__ offsets, int32_t* __restrict__ perm,
                                                                        int32_t* __restrict__ rows, float* __restrict__ row_weight,
-                                                                       int32_t* __restrict__ pos) {
+                                                                       int32_t* __restrict__ pos, GateGroups g) {
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gs = LIMITED ? E / g.n_group : 0;
     for (int t = w; t < T; t += kRouteWaves)
-        gate_token<L, NV, false>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, 0, 0, 0, 0, lane,
-                                 ids + (size_t)t * k, weights + (size_t)t * k);
+        gate_token<L, NV, LIMITED>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, g.n_group, gs, g.topk_group,
+                                   g.group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
     __threadfence_block();
     __syncthreads();                                    // every wave's ids and weights are written and visible in the workgroup
     route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
 }
 
-// ---- the group-limited forms: the two kernels above, with the group stage ---------------------------------------------------
-template <typename L, int NV>
-__global__ __launch_bounds__(kGateThreads) void moe_gate_limited_kernel(const typename GateLogit<L>::type* __restrict__ logits,
-                                                                        const float* __restrict__ bias, int T, int E, int k,
-                                                                        int scoring, int renormalize, float scale, int n_group,
-                                                                        int topk_group, int group_score,
-                                                                        int32_t* __restrict__ ids, float* __restrict__ weights) {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int t = blockIdx.x * kGateWaves + w;
-    if (t >= T) return;                                 // the whole wave leaves
-    gate_token<L, NV, true>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, n_group, E / n_group, topk_group,
-                            group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
-}
+// ---- the host side: one call, one launch, the ladder of classes and the ladder of logit types ---------------------------------
+struct GateCall {
+    int T, E, k, scoring, renormalize;
+    float scale;
+    GateGroups groups;
+    const void* logits;
+    const float* bias;
+    int32_t* ids;
+    float* weights;
+    int32_t *offsets, *perm, *rows;                     // offsets null: the standalone form, and the four after it are not used
+    float* row_weight;
+    int32_t* pos;
+    hipStream_t stream;
+};
 
-template <typename L, int NV>
-__global__ __launch_bounds__(kRouteThreads) void moe_gate_route_limited_kernel(
-    const typename GateLogit<L>::type* __restrict__ logits, const float* __restrict__ bias, int T, int E, int k, int scoring,
-    int renormalize, float scale, int n_group, int topk_group, int group_score, int nbits, int32_t* ids, float* weights,
-    int32_t* __restrict__ offsets, int32_t* __restrict__ perm, int32_t* __restrict__ rows, float* __restrict__ row_weight,
-    int32_t* __restrict__ pos) {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gs = E / n_group;
-    for (int t = w; t < T; t += kRouteWaves)
-        gate_token<L, NV, true>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, n_group, gs, topk_group,
-                                group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
-    __threadfence_block();
-    __syncthreads();                                    // every wave's ids and weights are written and visible in the workgroup
-    route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
-}
-
-template <typename L, int NV>
-static int gate_limited_launch(int T, int E, int k, int n_group, int topk_group, int group_score, int scoring, int renormalize,
-                               float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
-                               int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
-                               hipStream_t stream) {
-    const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(logits);
-    if (!offsets) {
-        const unsigned grid = (unsigned)((T + kGateWaves - 1) / kGateWaves);
-        hipLaunchKernelGGL((moe_gate_limited_kernel<L, NV>), dim3(grid), dim3(kGateThreads), 0, stream, x, bias, T, E, k, scoring,
-                           renormalize, scale, n_group, topk_group, group_score, ids, weights);
+template <typename L, int NV, bool LIMITED>
+static int gate_launch(const GateCall& c) {
+    const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(c.logits);
+    if (!c.offsets) {
+        const unsigned grid = (unsigned)((c.T + kGateWaves - 1) / kGateWaves);
+        hipLaunchKernelGGL((moe_gate_kernel<L, NV, LIMITED>), dim3(grid), dim3(kGateThreads), 0, c.stream, x, c.bias, c.T, c.E, c.k,
+                           c.scoring, c.renormalize, c.scale, c.ids, c.weights, c.groups);
     } else {
-        auto kern = moe_gate_route_limited_kernel<L, NV>;
-        const size_t lds = route_lds_bytes(E);
+        auto kern = moe_gate_route_kernel<L, NV, LIMITED>;
+        const size_t lds = route_lds_bytes(c.E);
         if (lds > 65536 &&
             hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return FLUTE_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(kRouteThreads), lds, stream, x, bias, T, E, k, scoring, renormalize, scale, n_group,
-                           topk_group, group_score, route_bucket_bits(E), ids, weights, offsets, perm, rows, row_weight, pos);
+        hipLaunchKernelGGL(kern, dim3(1), dim3(kRouteThreads), lds, c.stream, x, c.bias, c.T, c.E, c.k, c.scoring, c.renormalize,
+                           c.scale, route_bucket_bits(c.E), c.ids, c.weights, c.offsets, c.perm, c.rows, c.row_weight, c.pos,
+                           c.groups);
     }
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 
-template <typename L>
-static int gate_limited_by_class(int T, int E, int k, int n_group, int topk_group, int group_score, int scoring, int renormalize,
-                                 float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
-                                 int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
-                                 hipStream_t stream) {
-#define FLUTE_GATE(NV)                                                                                                          \
-    return gate_limited_launch<L, NV>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias, ids, \
-                                      weights, offsets, perm, rows, row_weight, pos, stream)
-    if (E <= 64) FLUTE_GATE(1);
-    if (E <= 128) FLUTE_GATE(2);
-    if (E <= 256) FLUTE_GATE(4);
-    if (E <= 512) FLUTE_GATE(8);
-    FLUTE_GATE(16);
-#undef FLUTE_GATE
+template <typename L, bool LIMITED>
+static int gate_by_class(const GateCall& c) {
+    if (c.E <= 64) return gate_launch<L, 1, LIMITED>(c);
+    if (c.E <= 128) return gate_launch<L, 2, LIMITED>(c);
+    if (c.E <= 256) return gate_launch<L, 4, LIMITED>(c);
+    if (c.E <= 512) return gate_launch<L, 8, LIMITED>(c);
+    return gate_launch<L, 16, LIMITED>(c);
 }
 
-template <typename L, int NV>
-static int gate_launch(int T, int E, int k, int scoring, int renormalize, float scale, const void* logits, const float* bias,
-                       int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight,
-                       int32_t* pos, hipStream_t stream) {
-    const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(logits);
-    if (!offsets) {
-        const unsigned grid = (unsigned)((T + kGateWaves - 1) / kGateWaves);
-        hipLaunchKernelGGL((moe_gate_kernel<L, NV>), dim3(grid), dim3(kGateThreads), 0, stream, x, bias, T, E, k, scoring,
-                           renormalize, scale, ids, weights);
-    } else {
-        auto kern = moe_gate_route_kernel<L, NV>;
-        const size_t lds = route_lds_bytes(E);
-        if (lds > 65536 &&
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return FLUTE_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(kRouteThreads), lds, stream, x, bias, T, E, k, scoring, renormalize, scale,
-                           route_bucket_bits(E), ids, weights, offsets, perm, rows, row_weight, pos);
-    }
-    return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+template <bool LIMITED>
+static int gate_by_type(int logit_dtype, const GateCall& c) {
+    if (logit_dtype == FLUTE_F16) return gate_by_class<F16, LIMITED>(c);
+    if (logit_dtype == FLUTE_BF16) return gate_by_class<BF16, LIMITED>(c);
+    return gate_by_class<float, LIMITED>(c);
 }
 
-template <typename L>
-static int gate_by_class(int T, int E, int k, int scoring, int renormalize, float scale, const void* logits, const float* bias,
-                         int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight,
-                         int32_t* pos, hipStream_t stream) {
-#define FLUTE_GATE(NV) \
-    return gate_launch<L, NV>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows, row_weight, pos, stream)
-    if (E <= 64) FLUTE_GATE(1);
-    if (E <= 128) FLUTE_GATE(2);
-    if (E <= 256) FLUTE_GATE(4);
-    if (E <= 512) FLUTE_GATE(8);
-    FLUTE_GATE(16);
-#undef FLUTE_GATE
-}
-
-int moe_gate_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
-                      const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm, int32_t* rows,
-                      float* row_weight, int32_t* pos, hipStream_t stream) {
-    renormalize = renormalize != 0;
-    if (logit_dtype == FLUTE_F16)
-        return gate_by_class<F16>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
-                                  row_weight, pos, stream);
-    if (logit_dtype == FLUTE_BF16)
-        return gate_by_class<BF16>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
-                                   row_weight, pos, stream);
-    return gate_by_class<float>(T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
-                                row_weight, pos, stream);
-}
-
-int moe_gate_limited_dispatch(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
-                              int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
-                              int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream) {
+int moe_gate_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
+                      const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
+                      int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream) {
     // every group allowed: every expert is, and the unlimited kernels serve the call - bit for bit by construction.  T == 0 (the
     // routed form's E + 1 zeros) gates nothing and goes the same way.
-    if (topk_group == n_group || T == 0)
-        return moe_gate_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
-                                 rows, row_weight, pos, stream);
-    renormalize = renormalize != 0;
-    if (logit_dtype == FLUTE_F16)
-        return gate_limited_by_class<F16>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
-                                          ids, weights, offsets, perm, rows, row_weight, pos, stream);
-    if (logit_dtype == FLUTE_BF16)
-        return gate_limited_by_class<BF16>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
-                                           ids, weights, offsets, perm, rows, row_weight, pos, stream);
-    return gate_limited_by_class<float>(T, E, k, n_group, topk_group, group_score, scoring, renormalize, scale, logits, bias,
-                                        ids, weights, offsets, perm, rows, row_weight, pos, stream);
+    const bool limited = groups && groups->topk_group != groups->n_group && T != 0;
+    const GateCall c = {T, E, k, scoring, renormalize != 0, scale, limited ? *groups : GateGroups{}, logits, bias, ids,
+                        weights, offsets, perm, rows, row_weight, pos, stream};
+    return limited ? gate_by_type<true>(logit_dtype, c) : gate_by_type<false>(logit_dtype, c);
 }
 
 }  // namespace flute_amd

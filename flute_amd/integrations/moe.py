@@ -162,14 +162,10 @@ class FluteExperts(torch.nn.Module):
         moe_gate_route -> glu -> weighted -> moe_combine (fused): four launches from logits.  Without it `moe_gate` feeds
         the existing forward.  Either way the result is bit for bit `forward(hidden, *moe_gate(...))`.  The choice is over
         all experts; group-limited selection (n_group, topk_group) is `forward_logits_limited`."""
-        if router_logits.shape[1] != self.num_experts:
-            raise ValueError("FluteExperts.forward_logits: router_logits must be [T, num_experts]")
-        if not self.native_routing:
-            ids, weights = flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale)
-            return self.forward(hidden, ids, weights)
-        _, _, offsets, rows, row_weight, pos, _ = flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring,
-                                                                           renormalize, bias, scale)
-        return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+        return self._forward_gated(
+            "forward_logits", hidden, router_logits,
+            lambda: flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale),
+            lambda: flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale))
 
     def forward_logits_limited(self, hidden: torch.Tensor, router_logits: torch.Tensor, top_k: int, n_group: int,
                                topk_group: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
@@ -179,14 +175,21 @@ class FluteExperts(torch.nn.Module):
         among their experts only).  With `native_routing` the forward is moe_gate_route_limited -> glu -> weighted ->
         moe_combine (fused): still four launches from logits.  Without it `moe_gate_limited` feeds the existing forward.
         Either way the result is bit for bit `forward(hidden, *moe_gate_limited(...))`."""
+        return self._forward_gated(
+            "forward_logits_limited", hidden, router_logits,
+            lambda: flute_amd.moe_gate_limited(router_logits, top_k, n_group, topk_group, scoring, renormalize, bias, scale,
+                                               group_score),
+            lambda: flute_amd.moe_gate_route_limited(router_logits, top_k, n_group, topk_group, self.num_experts, scoring,
+                                                     renormalize, bias, scale, group_score))
+
+    def _forward_gated(self, name, hidden, router_logits, gate, gate_route):
+        """The tail `forward_logits` and `forward_logits_limited` share: `gate()` feeds the existing forward, with
+        `native_routing` `gate_route()`'s routing arrays feed the launches behind them."""
         if router_logits.shape[1] != self.num_experts:
-            raise ValueError("FluteExperts.forward_logits_limited: router_logits must be [T, num_experts]")
+            raise ValueError("FluteExperts.%s: router_logits must be [T, num_experts]" % name)
         if not self.native_routing:
-            ids, weights = flute_amd.moe_gate_limited(router_logits, top_k, n_group, topk_group, scoring, renormalize, bias,
-                                                      scale, group_score)
-            return self.forward(hidden, ids, weights)
-        _, _, offsets, rows, row_weight, pos, _ = flute_amd.moe_gate_route_limited(
-            router_logits, top_k, n_group, topk_group, self.num_experts, scoring, renormalize, bias, scale, group_score)
+            return self.forward(hidden, *gate())
+        _, _, offsets, rows, row_weight, pos, _ = gate_route()
         return self._forward_routed(hidden, offsets, rows, row_weight, pos)
 
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):

@@ -693,7 +693,9 @@ def _validate_moe_gate(logits, k, scoring, bias, num_experts=None):
         raise ValueError
 
 
-def _moe_gate_call(name, logits, k, scoring, renormalize, bias, scale, routed):
+def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=None):
+    """One gating launch: flute_moe_gate, with `routed` _route, with `groups` = (n_group, topk_group, group_score) _limited."""
+    name = "moe_gate" + ("_route" if routed else "") + ("" if groups is None else "_limited")
     dev = logits.device
     if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
         raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
@@ -703,11 +705,13 @@ def _moe_gate_call(name, logits, k, scoring, renormalize, bias, scale, routed):
     b = None if bias is None else bias.contiguous()
     ids = torch.empty((T, k), dtype=torch.int32, device=dev)
     weights = torch.empty((T, k), dtype=torch.float32, device=dev)
-    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale),
-            x.data_ptr(), None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
+    group_args = () if groups is None else (int(groups[0]), int(groups[1]), _GATE_GROUP_SCORE_ID[groups[2]])
+    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, *group_args, _GATE_SCORING_ID[scoring], int(bool(renormalize)),
+            float(scale), x.data_ptr(), None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
+    fn = getattr(_lib.get(), "flute_" + name)
     with torch.cuda.device(dev):
         if not routed:
-            _lib.check(_lib.get().flute_moe_gate(*head, _stream_ptr(dev)))
+            _lib.check(fn(*head, _stream_ptr(dev)))
             return ids, weights
         P = T * k
         offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
@@ -715,8 +719,8 @@ def _moe_gate_call(name, logits, k, scoring, renormalize, bias, scale, routed):
         rows = torch.empty(P, dtype=torch.int32, device=dev)
         row_weight = torch.empty(P, dtype=torch.float32, device=dev)
         pos = torch.empty((T, k), dtype=torch.int32, device=dev)
-        _lib.check(_lib.get().flute_moe_gate_route(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
-                                                   row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
+        _lib.check(fn(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(), row_weight.data_ptr(), pos.data_ptr(),
+                      _stream_ptr(dev)))
     return ids, weights, offsets, rows, row_weight, pos, perm
 
 
@@ -771,7 +775,7 @@ def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize
     selection (n_group, topk_group) is `moe_gate_limited`.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
     stream (moe_gate.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
     _validate_moe_gate(logits, k, scoring, bias)
-    return _moe_gate_op(logits, lambda: _moe_gate_call("moe_gate", logits, k, scoring, renormalize, bias, scale, routed=False),
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=False),
                         scoring, renormalize, scale)
 
 
@@ -782,8 +786,8 @@ def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str 
     `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves gates the tokens and sorts the
     pairs: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     _validate_moe_gate(logits, k, scoring, bias, num_experts)
-    return _moe_gate_op(logits, lambda: _moe_gate_call("moe_gate_route", logits, k, scoring, renormalize, bias, scale,
-                                                       routed=True), scoring, renormalize, scale)
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=True),
+                        scoring, renormalize, scale)
 
 
 _GATE_GROUP_SCORE_ID = {"max": 0, "top2sum": 1}     # include/flute_amd.h flute_gate_group_score
@@ -806,34 +810,6 @@ def _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, gr
         raise ValueError
 
 
-def _moe_gate_limited_call(name, logits, k, n_group, topk_group, group_score, scoring, renormalize, bias, scale, routed):
-    dev = logits.device
-    if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
-        raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
-    T, E = logits.shape
-    k = int(k)
-    x = logits.contiguous()
-    b = None if bias is None else bias.contiguous()
-    ids = torch.empty((T, k), dtype=torch.int32, device=dev)
-    weights = torch.empty((T, k), dtype=torch.float32, device=dev)
-    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, int(n_group), int(topk_group), _GATE_GROUP_SCORE_ID[group_score],
-            _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale), x.data_ptr(),
-            None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
-    with torch.cuda.device(dev):
-        if not routed:
-            _lib.check(_lib.get().flute_moe_gate_limited(*head, _stream_ptr(dev)))
-            return ids, weights
-        P = T * k
-        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
-        perm = torch.empty(P, dtype=torch.int32, device=dev)
-        rows = torch.empty(P, dtype=torch.int32, device=dev)
-        row_weight = torch.empty(P, dtype=torch.float32, device=dev)
-        pos = torch.empty((T, k), dtype=torch.int32, device=dev)
-        _lib.check(_lib.get().flute_moe_gate_route_limited(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
-                                                           row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
-    return ids, weights, offsets, rows, row_weight, pos, perm
-
-
 def moe_gate_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int, scoring: str = "softmax",
                      renormalize: bool = False, bias=None, scale: float = 1.0, group_score: str = "max"):
     """`moe_gate` with DeepSeek's group-limited selection, in one launch: the E experts are `n_group` contiguous groups of
@@ -848,8 +824,8 @@ def moe_gate_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int
     fp32); no host synchronise (capturable), a native HIP kernel on the current stream (moe_gate.hip), equal arguments
     give equal bits."""
     _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score)
-    return _moe_gate_op(logits, lambda: _moe_gate_limited_call("moe_gate_limited", logits, k, n_group, topk_group, group_score,
-                                                               scoring, renormalize, bias, scale, routed=False),
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=False,
+                                                       groups=(n_group, topk_group, group_score)),
                         scoring, renormalize, scale)
 
 
@@ -861,8 +837,8 @@ def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_grou
     `moe_route(ids, weights, E)`'s.  `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves, as
     `moe_gate_route`: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score, num_experts)
-    return _moe_gate_op(logits, lambda: _moe_gate_limited_call("moe_gate_route_limited", logits, k, n_group, topk_group,
-                                                               group_score, scoring, renormalize, bias, scale, routed=True),
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=True,
+                                                       groups=(n_group, topk_group, group_score)),
                         scoring, renormalize, scale)
 
 

@@ -365,8 +365,11 @@ def test_weights_against_fp64(env, weight_cases):
                                                                   ("sigmoid", True, True, "top2sum"), ("sigmoid", False, False, "max")])
 def test_equal_bits(env, scoring, renorm, with_bias, group_score):
     d = env.dev
+    # (5, 60, ...): E no multiple of 64, k = 4 <= 2 groups of 10; (3, 160, ...): groups of 20 straddle registers - with them the routed
+    # entry point's group arguments are checked against moe_gate_limited + moe_route at topk_group < n_group for every form below
     for (T, E, k, n_group, topk_group), dtype in (((37, 64, 8, 4, 2), F16), ((37, 160, 6, 8, 3), F32), ((1030, 8, 2, 4, 2), BF16),
-                                                  ((3, 1000, 16, 8, 2), F32), ((18, 256, 8, 8, 4), BF16)):
+                                                  ((3, 1000, 16, 8, 2), F32), ((18, 256, 8, 8, 4), BF16), ((5, 60, 4, 6, 2), F16),
+                                                  ((3, 160, 6, 8, 3), F16)):
         x = draw_logits(T, E, dtype, T + E).to(d)
         bias = draw_bias(E, 3).to(d) if with_bias else None
         args = (k, n_group, topk_group, scoring, renorm, bias, 1.5, group_score)
