@@ -1732,6 +1732,27 @@ int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int 
     return qgemm_grouped_input_grad_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
 }
 
+int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
+                                   const void* QM2, const float* row_weight, void* dS, int num_sms, void* stream) {
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
+    if (rc) return rc;
+    if (l.t.tile_p != 32 && l.t.tile_p != 64) return FLUTE_ERR_TEMPLATE_ID;
+    // the workgroup's block is 128 n; the grid's z is the expert; a row index plus one 32-row step stays an int
+    if (N % 128 || E > 65535 || R > 0x7fffffff - 64) return FLUTE_ERR_SHAPE;
+    if (E == 0) return FLUTE_OK;                                   // dS has no element
+    if (!dS) return FLUTE_ERR_NULL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (R == 0)                                                    // no expert has a row: zeros, as the kernel writes them
+        return hipMemsetAsync(dS, 0, (size_t)E * (size_t)N * (size_t)(K >> l.lg) * 2, st) == hipSuccess ? FLUTE_OK
+                                                                                                         : FLUTE_ERR_LAUNCH;
+    if (!dY || !X || !offsets || !Q || !QM2) return FLUTE_ERR_NULL;
+    (void)num_sms;                                                 // the grid is (N / 128, ceil(K / 256), E): from the shapes alone
+    return scale_grad_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, N, K, P, dY, X, offsets, Q, QM2, row_weight,
+                                       dS, st);
+}
+
 int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
                     int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
     if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;

@@ -35,10 +35,12 @@ __device__ __forceinline__ uint2 lds_tr16(uint32_t addr) {
 
 // acc[kt][nt][r] = G[k][n] over rows [m_begin, m_end) for the block at (kb, nb): n = nb + wn * 64 + nt * 16 + (lane & 15),
 // k = kb + wk * 64 + kt * 16 + 4 (lane >> 4) + r.  Ends behind a barrier: the operand buffers are free on return.
-template <typename T>
+// ROW_WEIGHT (scale_grad_grouped.hip): the dY tile is staged as round_T(row_weight[m] * dY[m, n]), the product in fp32.
+template <typename T, bool ROW_WEIGHT = false>
 __device__ __forceinline__ void grad_gemm_mainloop(char* smem, const uint16_t* __restrict__ dY,
                                                    const uint16_t* __restrict__ X, int N, int K, int nb, int kb,
-                                                   int m_begin, int m_end, f32x4_t (&acc)[4][4]) {
+                                                   int m_begin, int m_end, f32x4_t (&acc)[4][4],
+                                                   const float* __restrict__ row_weight = nullptr) {
     const uint32_t base = lds_base_of(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wk = wave & 3, wn = wave >> 2;          // the wave's 64 k and 64 n inside the block
@@ -50,6 +52,7 @@ __device__ __forceinline__ void grad_gemm_mainloop(char* smem, const uint16_t* _
     const uint16_t* xp = X + (size_t)(kb + 8 * xc);
     const uint16_t* yp = dY + (size_t)(nb + 8 * yc);
     uint4 xv[2], yv;
+    float yw = 0.f;
     auto load = [&](int m0) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -58,8 +61,15 @@ __device__ __forceinline__ void grad_gemm_mainloop(char* smem, const uint16_t* _
         }
         const int m = m0 + yr;
         yv = m < m_end ? *reinterpret_cast<const uint4*>(yp + (size_t)m * N) : make_uint4(0, 0, 0, 0);
+        if constexpr (ROW_WEIGHT) yw = m < m_end ? row_weight[m] : 0.f;
+    };
+    auto weigh = [&](uint32_t v) {                    // two T: each times yw in fp32, one rounding
+        const uint32_t lo = Num<T>::from_float(Num<T>::to_float((uint16_t)(v & 0xffffu)) * yw);
+        const uint32_t hi = Num<T>::from_float(Num<T>::to_float((uint16_t)(v >> 16)) * yw);
+        return lo | (hi << 16);
     };
     auto store = [&](int buf) {
+        if constexpr (ROW_WEIGHT) yv = make_uint4(weigh(yv.x), weigh(yv.y), weigh(yv.z), weigh(yv.w));
         char* xs = smem + buf * kSgXBytes + xc * 16;
         *reinterpret_cast<uint4*>(xs + xr * kSgXPitch) = xv[0];
         *reinterpret_cast<uint4*>(xs + (xr + 16) * kSgXPitch) = xv[1];

@@ -98,6 +98,11 @@ FLUTE_IG_DISPATCH(4);
 FLUTE_IG_DISPATCH(3);
 FLUTE_IG_DISPATCH(2);
 #undef FLUTE_IG_DISPATCH
+// the gradient of the stacks' scales dS [E, N, K / g] (scale_grad_grouped.hip): scale_grad.hip's mainloop and epilogue per expert over the row
+// range the kernel reads from offsets; row_weight [R] fp32 or null; the grid is (N / 128, ceil(K / 256), E), no scratch
+int scale_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int N, int K, int P,
+                                const void* dY, const void* X, const void* offsets, const void* Q, const void* QM2,
+                                const void* row_weight, void* dS, hipStream_t stream);
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

@@ -18,6 +18,11 @@ gradient comes from `flute_amd.qgemm_table_grad`, in one launch with the scale g
     ...
     freeze(model)                             # plain FluteLinear: learned scales, tables and tables2, in the layer's type
 
+The experts of a mixture-of-experts layer train their scales the same way: `qgemm_grouped_learnable_scales`,
+`qgemm_grouped_glu_learnable_scales` and `qgemm_grouped_weighted_learnable_scales` are the three grouped ops with a
+gradient to the stacks' scales from `flute_amd.qgemm_grouped_scale_grad` (one launch per stack, the row counts stay on the
+device); the modules on them are `integrations.moe.make_experts_learnable` / `freeze_experts`.
+
 Not registered by `install_as_flute()`: the reference's `flute.integrations.learnable` is its dense layer.
 """
 from typing import List, Optional
@@ -25,6 +30,7 @@ from typing import List, Optional
 import torch
 
 import flute_amd
+from flute_amd import ops as _ops
 from .base import FluteLinear
 
 
@@ -298,3 +304,141 @@ def freeze(module: torch.nn.Module) -> None:
     if isinstance(module, LearnableFluteLinear):
         raise ValueError("freeze swaps the layers below a module: pass the module that holds it")
     _swap(module, lambda m: _frozen_learnable(m) if isinstance(m, LearnableFluteLinear) else m)
+
+
+# ---- the experts' scales: the three grouped ops with a gradient to the stacks' scales
+
+def _refuse_table_grad(name, *tables):
+    if any(t.requires_grad for t in tables):
+        raise RuntimeError(f"{name}: no gradient for table2 (only input, row_weight and scales train)")
+
+
+class _GroupedLearnableScales(torch.autograd.Function):
+    """`qgemm_grouped` with dS: the op's launch on detached scales (rows no expert serves zeroed, as the op does under
+    autograd), dX = qgemm_grouped_input_grad(dY), dS = qgemm_grouped_scale_grad(dY, x)."""
+
+    @staticmethod
+    def forward(ctx, input, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms):
+        s = scales.detach()
+        out = _ops._launch_grouped("qgemm_grouped", (input.shape[0],), weight, s.shape[1],
+                                   (input, offsets, weight, s, table2), num_bits, group_size, template_id, num_sms)
+        ctx.save_for_backward(input, offsets, weight, s, table2)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return _ops._zero_unserved_(out, offsets)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, offsets, weight, scales, table2 = ctx.saved_tensors
+        d_input = d_scales = None
+        if ctx.needs_input_grad[0]:
+            d_input = flute_amd.qgemm_grouped_input_grad(grad_output, offsets, weight, scales, table2, *ctx.layer)
+        if ctx.needs_input_grad[1]:
+            d_scales = flute_amd.qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer)
+        return (d_input, d_scales) + (None,) * 7
+
+
+def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                                   table2: torch.Tensor, num_bits: int, group_size: int, template_id: int,
+                                   num_sms=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped`, differentiable with respect to `input` and `scales` [E, N, K / g].  The forward is the
+    op's launch (the same bits); the backward adds dS = `qgemm_grouped_scale_grad(dY, input, ...)`.  With grad mode off, or
+    nothing requiring grad, it is the plain op.  `table2` requiring grad is refused."""
+    _ops._validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    _refuse_table_grad("qgemm_grouped_learnable_scales", table2)
+    if not _ops._records_grad(input, scales):
+        return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
+    return _GroupedLearnableScales.apply(input, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms)
+
+
+class _GroupedWeightedLearnableScales(torch.autograd.Function):
+    """`qgemm_grouped_weighted` with dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight
+    multiplies dY where the kernel stages it."""
+
+    @staticmethod
+    def forward(ctx, input, row_weight, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms):
+        s = scales.detach()
+        out = _ops._launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, s.shape[1],
+                                   (input, offsets, weight, s, table2, row_weight), num_bits, group_size, template_id,
+                                   num_sms)
+        ctx.save_for_backward(input, row_weight, offsets, weight, s, table2)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
+        d_input = d_weight = d_scales = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            d_input, d_weight = _ops._grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer,
+                                                                ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if ctx.needs_input_grad[2]:
+            d_scales = flute_amd.qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer,
+                                                          row_weight=row_weight)
+        return (d_input, d_weight, d_scales) + (None,) * 7
+
+
+def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                                            scales: torch.Tensor, table2: torch.Tensor, row_weight: torch.Tensor,
+                                            num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped_weighted`, differentiable with respect to `input`, `row_weight` and `scales`.  The
+    forward is the op's launch; the gradients of `input` and `row_weight` are the op's own, and
+    dS = `qgemm_grouped_scale_grad(dY, input, ..., row_weight=row_weight)`.  `table2` requiring grad is refused."""
+    _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    _refuse_table_grad("qgemm_grouped_weighted_learnable_scales", table2)
+    if not _ops._records_grad(input, row_weight, scales):
+        return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
+                                                template_id, num_sms)
+    return _GroupedWeightedLearnableScales.apply(input, row_weight, scales, offsets, weight, table2, num_bits, group_size,
+                                                 template_id, num_sms)
+
+
+class _GroupedGluLearnableScales(torch.autograd.Function):
+    """`qgemm_grouped_glu` with dS_gate = qgemm_grouped_scale_grad(dg, x_sorted) and dS_up = (du, x_sorted): x_sorted, dg
+    and du are the tensors the op's backward forms (`ops._grouped_glu_backward`)."""
+
+    @staticmethod
+    def forward(ctx, input, gs, us, rows, pos, offsets, gw, gt, uw, ut, num_bits, group_size, template_id, num_sms):
+        gs, us = gs.detach(), us.detach()
+        Tsrc = input.shape[0]
+        R = Tsrc if rows is None else rows.shape[0]
+        out = _ops._launch_grouped("qgemm_grouped_glu", (R, Tsrc), gw, gs.shape[1],
+                                   (input, rows, offsets, gw, gs, gt, uw, us, ut), num_bits, group_size, template_id, num_sms)
+        ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
+        ctx.has = (rows is not None, pos is not None)
+        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        return _ops._zero_unserved_(out, offsets)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, offsets, gw, gs, gt, uw, us, ut, *index = ctx.saved_tensors
+        rows = index[0] if ctx.has[0] else None
+        pos = index[1] if ctx.has[1] else None
+        dx, x, dg, du = _ops._grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
+                                                   want_input_grad=ctx.needs_input_grad[0])
+        d_gs = d_us = None
+        if ctx.needs_input_grad[1]:
+            d_gs = flute_amd.qgemm_grouped_scale_grad(dg, x, offsets, gw, gt, *ctx.layer)
+        if ctx.needs_input_grad[2]:
+            d_us = flute_amd.qgemm_grouped_scale_grad(du, x, offsets, uw, ut, *ctx.layer)
+        return (dx, d_gs, d_us) + (None,) * 11
+
+
+def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
+                                       gate_scales: torch.Tensor, gate_table2: torch.Tensor, up_weight: torch.Tensor,
+                                       up_scales: torch.Tensor, up_table2: torch.Tensor, num_bits: int, group_size: int,
+                                       template_id: int, num_sms=None, rows=None, pos=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped_glu`, differentiable with respect to `input`, `gate_scales` and `up_scales`.  The forward is
+    the op's launch; the backward is the op's own (gate and up recomputed, dg and du in fp32, the pair-form input gradient)
+    plus one `qgemm_grouped_scale_grad` launch per stack on the gathered rows.  The tables requiring grad are refused."""
+    _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                               num_bits, group_size, rows)
+    _refuse_table_grad("qgemm_grouped_glu_learnable_scales", gate_table2, up_table2)
+    if not _ops._records_grad(input, gate_scales, up_scales):
+        return flute_amd.qgemm_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
+                                           up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
+    _ops._validate_grouped_glu_pos(input, rows, pos)
+    return _GroupedGluLearnableScales.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
+                                            up_weight, up_table2, num_bits, group_size, template_id, num_sms)

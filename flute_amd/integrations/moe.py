@@ -21,14 +21,21 @@ their backward (`flute_amd.ops`): the input gradients of the three projections a
 (the fused GLU recomputes gate and up with two plain grouped launches and takes both gradients in one pair-form launch),
 the gradient of the gather is `moe_combine` under native routing (equal bits at every top-k) and `index_add_` otherwise,
 `moe_combine`'s own gradient is a gather, and the gating ops differentiate their formula in fp32 with the chosen ids
-held fixed - so layers in front of the block (LoRA on attention, a trainable router) get their gradients.  The packed
-stacks themselves are frozen: scales or tables that require grad raise.  With grad mode off, or nothing requiring grad,
-the forward is exactly the inference path above and stays capturable.
+held fixed - so layers in front of the block (LoRA on attention, a trainable router) get their gradients.  With grad mode
+off, or nothing requiring grad, the forward is exactly the inference path above and stays capturable.
+
+The experts' scales train: `make_experts_learnable(model)` swaps every `GroupedFluteLinear` for a
+`LearnableGroupedFluteLinear` (its `scales` an `nn.Parameter`, the packed codes and tables shared) and `FluteExperts` then
+runs its three projections through `integrations.learnable.qgemm_grouped*_learnable_scales`, whose backward adds one
+`flute_amd.qgemm_grouped_scale_grad` launch per stack - the row counts stay on the device there too; `freeze_experts(model)`
+swaps back to plain stacks holding the learned scales.  The tables stay fixed, and the public `flute_amd.qgemm_grouped*`
+ops still raise on scales or tables that require grad.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
     fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
     four = FluteExperts.from_linears(gates, ups, downs, fused=True, native_routing=True)   # moe_route -> glu -> weighted -> moe_combine
+    params = make_experts_learnable(four); ...; freeze_experts(four)                        # train the experts' scales
     out = four.forward_logits(hidden, router_logits, top_k=2, renormalize=True)            # moe_gate_route -> glu -> weighted -> moe_combine
     block = FluteSparseMoeBlock(router_weight, four, top_k=2, renormalize=True)             # [E, K] router, out = block(hidden)
     v3 = FluteSparseMoeBlock(router_weight, four, top_k=8, scoring="sigmoid", renormalize=True, bias=correction_bias,
@@ -36,13 +43,15 @@ the forward is exactly the inference path above and stays capturable.
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
-from typing import Sequence, Tuple
+from typing import List, Sequence, Tuple
 
 import torch
 
 import flute_amd
 import flute_amd.utils
 from .base import FluteLinear
+from .learnable import (_swap, qgemm_grouped_glu_learnable_scales, qgemm_grouped_learnable_scales,
+                        qgemm_grouped_weighted_learnable_scales)
 
 
 def sort_by_expert(topk_ids: torch.Tensor, num_experts: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -111,6 +120,64 @@ class GroupedFluteLinear(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, "
                 f"num_bits={self.num_bits}, group_size={self.group_size}")
+
+
+_GROUPED_ATTRS = ("num_experts", "in_features", "out_features", "num_bits", "group_size", "template_id", "num_sms")
+
+
+def _share_grouped(new: torch.nn.Module, stack: GroupedFluteLinear, scales: torch.Tensor) -> None:
+    # `new` takes the stack's configuration and its weight / tables / tables2 tensors; nothing is copied
+    for name in _GROUPED_ATTRS:
+        setattr(new, name, getattr(stack, name))
+    new.register_buffer("weight", stack.weight)
+    if isinstance(scales, torch.nn.Parameter):
+        new.scales = scales
+    else:
+        new.register_buffer("scales", scales)
+    new.register_buffer("tables", stack.tables)
+    new.register_buffer("tables2", stack.tables2)
+    new.train(stack.training)
+
+
+class LearnableGroupedFluteLinear(GroupedFluteLinear):
+    """A `GroupedFluteLinear` whose `scales` [E, N, K / g] is an `nn.Parameter` (a copy); `weight`, `tables` and `tables2`
+    are the source stack's tensors, the state-dict keys are `GroupedFluteLinear`'s.  The forward is
+    `qgemm_grouped_learnable_scales`: the same launch, with a gradient to the scales from `qgemm_grouped_scale_grad`."""
+
+    def __init__(self, stack: GroupedFluteLinear) -> None:
+        if not isinstance(stack, GroupedFluteLinear):
+            raise TypeError("LearnableGroupedFluteLinear wraps a GroupedFluteLinear")
+        torch.nn.Module.__init__(self)
+        _share_grouped(self, stack, torch.nn.Parameter(stack.scales.detach().clone()))
+
+    def forward(self, x_sorted: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        num_sms = self.num_sms if self.num_sms is not None else flute_amd.utils.get_device_num_sms(x_sorted.device)
+        return qgemm_grouped_learnable_scales(x_sorted, offsets, self.weight, self.scales, self.tables2, self.num_bits,
+                                              self.group_size, self.template_id, num_sms)
+
+
+def make_experts_learnable(module: torch.nn.Module) -> List[torch.nn.Parameter]:
+    """Replace every `GroupedFluteLinear` below `module` by a `LearnableGroupedFluteLinear`, in place; returns the scale
+    parameters of all learnable stacks below `module`, in module order."""
+    if type(module) is GroupedFluteLinear:
+        raise ValueError("make_experts_learnable swaps the stacks below a module: pass the module that holds it")
+    _swap(module, lambda m: LearnableGroupedFluteLinear(m) if type(m) is GroupedFluteLinear else m)
+    return [m.scales for m in module.modules() if isinstance(m, LearnableGroupedFluteLinear)]
+
+
+def _frozen_grouped(stack: LearnableGroupedFluteLinear) -> GroupedFluteLinear:
+    new = GroupedFluteLinear.__new__(GroupedFluteLinear)
+    torch.nn.Module.__init__(new)
+    _share_grouped(new, stack, stack.scales.detach())
+    return new
+
+
+def freeze_experts(module: torch.nn.Module) -> None:
+    """Replace every `LearnableGroupedFluteLinear` below `module` by a plain `GroupedFluteLinear` holding the learned
+    scales as its buffer, in place: the experts run the unchanged inference launches again."""
+    if isinstance(module, LearnableGroupedFluteLinear):
+        raise ValueError("freeze_experts swaps the stacks below a module: pass the module that holds it")
+    _swap(module, lambda m: _frozen_grouped(m) if isinstance(m, LearnableGroupedFluteLinear) else m)
 
 
 class FluteExperts(torch.nn.Module):
@@ -197,14 +264,22 @@ class FluteExperts(torch.nn.Module):
         routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
         the rows past offsets[E] (ids outside [0, E)) as zeros: no silu, no where, no gathered copy of `hidden`."""
         gate, up, down = self.gate, self.up, self.down
+        glu, weighted = self._fused_ops()
         num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-        h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight, up.scales,
-                                        up.tables2, gate.num_bits, gate.group_size, gate.template_id, num_sms,
-                                        rows=token.to(torch.int32))
-        y = flute_amd.qgemm_grouped_weighted(h, offsets, down.weight, down.scales, down.tables2,
-                                             topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
-                                             down.template_id, num_sms)
+        h = glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight, up.scales,
+                up.tables2, gate.num_bits, gate.group_size, gate.template_id, num_sms,
+                rows=token.to(torch.int32))
+        y = weighted(h, offsets, down.weight, down.scales, down.tables2,
+                     topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
+                     down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)
+
+    def _fused_ops(self):
+        """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
+        scales their gradient (with grad mode off those are the public ops)."""
+        if any(isinstance(m, LearnableGroupedFluteLinear) for m in (self.gate, self.up, self.down)):
+            return qgemm_grouped_glu_learnable_scales, qgemm_grouped_weighted_learnable_scales
+        return flute_amd.qgemm_grouped_glu, flute_amd.qgemm_grouped_weighted
 
     def _forward_native(self, hidden, topk_ids, topk_weights):
         """`moe_route` (moe_route.hip) in place of sort_by_expert and its glue, `moe_combine` (moe_combine.hip) in place
@@ -217,12 +292,13 @@ class FluteExperts(torch.nn.Module):
         """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`)."""
         gate, up, down = self.gate, self.up, self.down
         if self.fused:
+            glu, weighted = self._fused_ops()
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-            h = flute_amd.qgemm_grouped_glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
-                                            up.scales, up.tables2, gate.num_bits, gate.group_size, gate.template_id,
-                                            num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
-            y = flute_amd.qgemm_grouped_weighted(h, offsets, down.weight, down.scales, down.tables2, row_weight,
-                                                 down.num_bits, down.group_size, down.template_id, num_sms)
+            h = glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
+                    up.scales, up.tables2, gate.num_bits, gate.group_size, gate.template_id,
+                    num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
+            y = weighted(h, offsets, down.weight, down.scales, down.tables2, row_weight,
+                         down.num_bits, down.group_size, down.template_id, num_sms)
         else:
             x = hidden[rows]
             h = torch.nn.functional.silu(gate(x, offsets)) * up(x, offsets)

@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
 `moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
 routing weights and router logits (not the packed stacks): when grad mode is on and such an input requires grad they run
 through a `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`,
@@ -384,6 +384,16 @@ def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2,
             raise ValueError
 
 
+def _validate_grouped_glu_pos(input, rows, pos):
+    """`pos` [Tsrc, k] int32, the inverse of `rows` [Tsrc k] (which it needs); None passes."""
+    if pos is None:
+        return
+    if rows is None or pos.dtype != torch.int32:
+        raise TypeError
+    if pos.ndim != 2 or pos.shape[0] != input.shape[0] or pos.shape[0] * pos.shape[1] != rows.shape[0]:
+        raise ValueError
+
+
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
@@ -401,11 +411,7 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
                           num_bits, group_size, rows)
     Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
-    if pos is not None:
-        if rows is None or pos.dtype != torch.int32:
-            raise TypeError
-        if pos.ndim != 2 or pos.shape[0] != Tsrc or pos.shape[0] * pos.shape[1] != R:
-            raise ValueError
+    _validate_grouped_glu_pos(input, rows, pos)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, rows, pos, offsets, gate_weight, gate_scales, gate_table2, up_weight,
@@ -437,21 +443,31 @@ class _GroupedGluFunction(torch.autograd.Function):
         input, offsets, gw, gs, gt, uw, us, ut, *index = ctx.saved_tensors
         rows = index[0] if ctx.has[0] else None
         pos = index[1] if ctx.has[1] else None
-        Tsrc = input.shape[0]
-        x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
-        launch = lambda w, sc, t2: _launch_grouped("qgemm_grouped", (x.shape[0],), w, sc.shape[1], (x, offsets, w, sc, t2),
-                                                   *ctx.layer)
-        g, u, dh = launch(gw, gs, gt).float(), launch(uw, us, ut).float(), grad_output.float()
-        sig = torch.sigmoid(g)
-        dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
-        du = (dh * (g * sig)).to(input.dtype)
-        dx = qgemm_grouped_input_grad(dg, offsets, gw, gs, gt, *ctx.layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
-        if rows is not None:
-            if pos is not None:
-                dx = moe_combine(dx, pos, offsets)
-            else:
-                dx = torch.zeros_like(input).index_add_(0, rows.clamp(0, Tsrc - 1).long(), dx)
+        dx, _, _, _ = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer)
         return (dx,) + (None,) * 13
+
+
+def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad=True):
+    """The backward of the fused GLU launch, shared with `integrations.learnable`: (d input, x_sorted, dg, du) - the
+    gathered rows and the two gradients in T that the pair-form launch reads, which the scale gradients read too.
+    `want_input_grad` false skips the pair-form launch and the sum over a token's slots (d input: None)."""
+    Tsrc = input.shape[0]
+    x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
+    launch = lambda w, sc, t2: _launch_grouped("qgemm_grouped", (x.shape[0],), w, sc.shape[1], (x, offsets, w, sc, t2),
+                                               *layer)
+    g, u, dh = launch(gw, gs, gt).float(), launch(uw, us, ut).float(), grad_output.float()
+    sig = torch.sigmoid(g)
+    dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
+    du = (dh * (g * sig)).to(input.dtype)
+    if not want_input_grad:
+        return None, x, dg, du
+    dx = qgemm_grouped_input_grad(dg, offsets, gw, gs, gt, *layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
+    if rows is not None:
+        if pos is not None:
+            dx = moe_combine(dx, pos, offsets)
+        else:
+            dx = torch.zeros_like(input).index_add_(0, rows.clamp(0, Tsrc - 1).long(), dx)
+    return dx, x, dg, du
 
 
 def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size):
@@ -494,17 +510,23 @@ class _GroupedWeightedFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
-        stack = (offsets, weight, scales, table2)
-        if not ctx.needs_input_grad[1]:
-            return (qgemm_grouped_input_grad(grad_output, *stack, *ctx.layer, row_weight=row_weight),) + (None,) * 9
-        R = input.shape[0]
-        dh = qgemm_grouped_input_grad(grad_output, *stack, *ctx.layer).float()
-        served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
-        # (a row no expert serves may hold anything in `input`: its dH' is zero, and the where keeps 0 x NaN out)
-        d_weight = torch.where(served, (dh * input.float()).sum(dim=1), torch.zeros((), device=input.device))
-        d_input = (row_weight[:, None] * dh).to(input.dtype) if ctx.needs_input_grad[0] else None
-        return (d_input, d_weight) + (None,) * 8
+        return _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, ctx.needs_input_grad[0],
+                                          ctx.needs_input_grad[1]) + (None,) * 8
+
+
+def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
+                               want_weight):
+    """(d input, d row_weight) of the weighted launch, shared with `integrations.learnable`."""
+    stack = (offsets, weight, scales, table2)
+    if not want_weight:
+        return qgemm_grouped_input_grad(grad_output, *stack, *layer, row_weight=row_weight), None
+    R = input.shape[0]
+    dh = qgemm_grouped_input_grad(grad_output, *stack, *layer).float()
+    served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
+    # (a row no expert serves may hold anything in `input`: its dH' is zero, and the where keeps 0 x NaN out)
+    d_weight = torch.where(served, (dh * input.float()).sum(dim=1), torch.zeros((), device=input.device))
+    d_input = (row_weight[:, None] * dh).to(input.dtype) if want_input else None
+    return d_input, d_weight
 
 
 def _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
@@ -587,6 +609,70 @@ def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, w
     with torch.cuda.device(dev):
         _lib.check(_lib.get().flute_qgemm_grouped_input_grad(
             _DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P, template_id,
+            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
+    return out
+
+
+def _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight):
+    if not all([grad_output.ndim == 2, input.ndim == 2, offsets.ndim == 1, weight.ndim == 3, table2.ndim == 4]):
+        raise ValueError
+    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype:
+        raise TypeError
+    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
+        raise TypeError
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    E, K, N = weight.shape[0], input.shape[1], grad_output.shape[1]
+    if not all([
+        grad_output.shape[0] == input.shape[0],
+        weight.shape[2] == K,
+        K > 0 and K % max(64, group_size) == 0,
+        N > 0 and N % 128 == 0 and weight.shape[1] == num_bits * (N // 16),
+        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
+        offsets.shape[0] == E + 1,
+    ]):
+        raise ValueError
+    if row_weight is not None:
+        if row_weight.dtype != torch.float32:
+            raise TypeError
+        if row_weight.ndim != 1 or row_weight.shape[0] != input.shape[0]:
+            raise ValueError
+
+
+def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                             table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                             row_weight=None) -> torch.Tensor:
+    """The gradient of the scales of `qgemm_grouped`'s stack in one launch: `qgemm_scale_grad` for every expert over the
+    rows the device-side table gives it, dS[e, n, j] = round_T(sum_{r in [offsets[e], offsets[e + 1])} sum_{k in group j}
+    dYw[r, n] * input[r, k] * L_e[k, n]), L_e the `table2[e]` pair lookup of expert e's codes.  `grad_output` [R, N] and
+    `input` [R, K] hold the rows sorted by expert; `offsets`, `weight` [E, P, K] and `table2` as `qgemm_grouped` takes them.
+    dYw is `grad_output`, or with `row_weight` [R] fp32 round_T(row_weight[r] * grad_output[r, n]) (the product in fp32) -
+    the gradient that reaches `qgemm_grouped_weighted`'s product.  Returns [E, N, K / g] in input.dtype, every element
+    written: an expert without rows gets zeros and its codes and table are not read; rows from offsets[E] on are never
+    read; offsets are clamped to [0, R].  Sums in fp32 in `qgemm_scale_grad`'s order with one rounding: an expert's slice
+    has that op's bits on the expert's rows wherever it does not split M.  The host never reads `offsets` (no
+    synchronise, capturable); no scratch, no atomics, equal arguments give equal bits; a native HIP kernel on the current
+    stream (scale_grad_grouped.hip).  Not differentiable itself: it raises when grad mode is on and an argument requires
+    grad."""
+    _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight)
+    tensors = (grad_output, input, offsets, weight, table2, row_weight)
+    if _records_grad(*tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_scale_grad: the backward is once-differentiable (no double backward)")
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
+        raise RuntimeError("flute_amd.qgemm_grouped_scale_grad: all tensors must live on the same GPU")
+    R, K = input.shape
+    N = grad_output.shape[1]
+    E, P = weight.shape[0], weight.shape[1]
+    if R >= 2 ** 31 - 64:
+        raise ValueError
+    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    out = torch.empty((E, N, K // group_size), dtype=input.dtype, device=dev)
+    if num_sms is None:
+        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_qgemm_grouped_scale_grad(
+            _DTYPE_ID[input.dtype], num_bits, group_size, E, R, N, K, P, template_id,
             *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
     return out
 

@@ -26,7 +26,8 @@ extern "C" {
 /* 9: flute_dequantize; flute_qgemm_scale_grad; flute_qgemm_table_grad and its scratch query; flute_qgemm_grouped;
  *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
  *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring; flute_moe_gate_limited and flute_moe_gate_route_limited with
- *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block
+ *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block;
+ *    flute_qgemm_grouped_scale_grad
  *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -355,6 +356,33 @@ int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int 
                                    const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
 /* FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK of the library that is loaded */
 int flute_qgemm_grouped_input_grad_row_block(void);
+
+/* The gradient of the scales of a stack flute_qgemm_grouped multiplies by, in ONE launch: flute_qgemm_scale_grad for every
+ * expert over the rows the device-side table gives it.  With b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):
+ *   dS[e, n, j] = round_T( sum_{r in [b_e, e_e)} sum_{k in group j} dYw[r, n] * X[r, k] * L_e[k, n] ),
+ * L_e the pair lookup of expert e's codes in expert e's QM2 (flute_qgemm_scale_grad's L), dYw = dY when row_weight is null and
+ * dYw[r, n] = round_T(row_weight[r] * dY[r, n]) otherwise - the product in fp32, one round-to-nearest-even to T, formed where
+ * the dY tile is staged - which is the gradient that reaches flute_qgemm_grouped_weighted's product.  Products and sums in
+ * fp32 in flute_qgemm_scale_grad's order, one rounding of the result: wherever that launch does not split M (always without
+ * scratch) an expert's dS has its bits.
+ * dY [R, N] and X [R, K] row-major T, rows sorted by expert; offsets [E + 1] int32 in DEVICE memory; Q [E, P, K] int16;
+ * QM2 [E, 2^b, 2^b] fp32 words; row_weight [R] fp32 in device memory or null; dS [E, N, K / group_size] T.
+ * The host never reads offsets: the grid is (N / 128, ceil(K / 256), E), from the shapes alone (num_sms is accepted for
+ * symmetry and not used).  One workgroup walks all rows of its expert: no split of the row reduction, no scratch, no
+ * atomics, equal arguments give equal bits, and the launch is hipGraph-capturable (a replay serves what the table then
+ * holds).  Every element of dS is written.  An expert with e_e <= b_e gets zeros and none of its codes or table words is
+ * read (a table of inf / NaN there stays out of the result).  Rows from clamp(offsets[E]) on are never read, and every row
+ * index formed lies inside [0, R): a malformed table (decreasing, past R) is memory-safe.  Expert bases into Q / QM2 / dS
+ * and row bases into dY / X are 64-bit.
+ * Supported layers are flute_qgemm_scale_grad's: 4 / 2 bits with TileP 32 / 64, 3 bits with TileP 32, fp16 / bf16, group
+ * sizes 32 / 64 / 128 / 256, N % 128 == 0, K % max(64, group_size) == 0.
+ * Refusals, before anything is enqueued and in this order: flute_qgemm_grouped's (dtype, the layer checks, FLUTE_ERR_SHAPE
+ * for P or a negative E / R), FLUTE_ERR_SHAPE for E > 65535; E == 0 returns FLUTE_OK (dS is empty); then FLUTE_ERR_NULL for
+ * a null dS; R == 0 writes dS as zeros (a memset node) and returns; then FLUTE_ERR_NULL for a null dY / X / offsets / Q /
+ * QM2.  No pointer is dereferenced by the host. */
+int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
+                                   const void* QM2, const float* row_weight, void* dS, int num_sms, void* stream);
 
 /* The routing of a mixture-of-experts step in ONE launch: from the router's choice to every array the grouped launches
  * and flute_moe_combine read.  ids [T, k] int32 or int64 (id_dtype: flute_index_dtype; torch.topk returns int64), weights

@@ -6,6 +6,7 @@
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
     python tools/grouped_bench.py --mode input_grad [--processes 3] [--out profiles/grouped_moe_input_grad.json]
+    python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -57,6 +58,10 @@ passes of each form, three fresh processes.  Reported: both times, the ratio, th
 spread.  A last row splits one whole backward step of FluteExperts(fused=True, native_routing=True) at 512 tokens into its
 launches (down's input gradient with the routing weight in its epilogue, the recompute of gate and up through the grouped
 forward, the fp32 elementwise dg / du, the pair-form input gradient, moe_combine).
+
+--mode scale_grad times the grouped scale-gradient kernel (scale_grad_grouped.hip), dS [E, N, K / g] of a stack in one launch,
+by --mode input_grad's method at its six shape / row-count lines, against a per-expert loop of flute_amd.qgemm_scale_grad on
+row ranges the host knows - the loop's best case: inside FluteExperts the counts are not on the host.  FLOP = 2 rows N K.
 """
 import argparse
 import json
@@ -658,6 +663,72 @@ def child_input_grad(args, device):
         json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
+class ScaleGrad:
+    """`copies` stacks of `experts` packed layers [N, K]; step(i) is dS [E, N, K / g] from dY [R, N] and X [R, K] on copy i: one
+    grouped launch, or the per-expert loop of the dense qgemm_scale_grad on row ranges the host knows."""
+
+    def __init__(self, experts, N, K, counts, copies, device, grouped):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.N, self.K, self.counts, self.grouped = flute_amd, N, K, counts, grouped
+        self.num_sms = utils.get_device_num_sms(device)
+        gen = torch.Generator(device=device).manual_seed(1)
+        self.Q = torch.randint(-2 ** 15, 2 ** 15, (copies, experts, BITS * N // 16, K), dtype=torch.int16, device=device, generator=gen)
+        table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
+        self.table2 = utils.make_qmap2_from_qmap(table)
+        self.tables2 = self.table2.repeat(experts, 1, 1, 1)
+        self.dY = (torch.randn(sum(counts), N, device=device, generator=gen) / 16).to(DTYPE)
+        self.X = (torch.randn(sum(counts), K, device=device, generator=gen) / 16).to(DTYPE)
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + c)
+        self.off_host = off
+        self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+
+    def step(self, i):
+        c = i % self.Q.shape[0]
+        if self.grouped:
+            return self.fa.qgemm_grouped_scale_grad(self.dY, self.X, self.offsets, self.Q[c], self.tables2, BITS, G, self.tid,
+                                                    self.num_sms)
+        out = []
+        for e, m in enumerate(self.counts):
+            if m:
+                r0, r1 = self.off_host[e], self.off_host[e + 1]
+                out.append(self.fa.qgemm_scale_grad(self.dY[r0:r1], self.X[r0:r1], self.Q[c, e], self.table2, BITS, G, self.tid,
+                                                    self.num_sms))
+        return out
+
+    def flops(self):
+        return 2.0 * sum(self.counts) * self.N * self.K
+
+
+def child_scale_grad(args, device):
+    rows = []
+    for name, experts, N, K, nrows in IG_SHAPES:
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        per_copy = experts * (BITS * N // 16) * K * 2
+        copies = max(2, bench.L3_BYTES // per_copy + 2)
+        grouped = ScaleGrad(experts, N, K, counts, copies, device, grouped=True)
+        loop = ScaleGrad(experts, N, K, counts, copies, device, grouped=False)
+        a = torch.stack([grouped.step(0)[e] for e, m in enumerate(counts) if m])
+        b = torch.stack(loop.step(0))
+        torch.cuda.synchronize()
+        diff, ref = float((a.float() - b.float()).abs().max()), float(b.float().abs().max())
+        m = [measure(layer, args) for layer in (grouped, loop, grouped, loop)]
+        g_us, l_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
+        row = {"what": "scale_grad", "shape": name, "experts": experts, "N": N, "K": K, "rows": sum(counts), "counts_min_max":
+               [min(counts), max(counts)], "weight_copies": copies, "grouped_us": round(g_us, 3), "loop_us": round(l_us, 3),
+               "grouped_over_loop": round(g_us / l_us, 4), "flop": grouped.flops(),
+               "spread": max(p["spread"] for p in m), "max_abs_diff_grouped_vs_loop": diff, "max_abs_loop": ref, "passes": m}
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
+        del grouped, loop, a, b
+        torch.cuda.empty_cache()
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -665,7 +736,7 @@ def main_input_grad(args):
     with tempfile.TemporaryDirectory() as tmp:
         for i in range(args.processes):
             path = os.path.join(tmp, "p%d.json" % i)
-            cmd = [sys.executable, os.path.abspath(__file__), "--mode", "input_grad", "--child", "--out", path, "--steps",
+            cmd = [sys.executable, os.path.abspath(__file__), "--mode", args.mode, "--child", "--out", path, "--steps",
                    str(args.steps), "--warmup", str(args.warmup), "--replays", str(args.replays)]
             subprocess.run(cmd, check=True)
             with open(path) as f:
@@ -674,7 +745,7 @@ def main_input_grad(args):
     rows = []
     for i, first in enumerate(runs[0]["rows"]):
         per = [r["rows"][i] for r in runs]
-        if first["what"] == "input_grad":
+        if first["what"] in ("input_grad", "scale_grad"):
             g_us, l_us = median([p["grouped_us"] for p in per]), median([p["loop_us"] for p in per])
             row = {k: first[k] for k in ("what", "shape", "experts", "N", "K", "rows", "counts_min_max", "weight_copies", "flop")}
             row.update(grouped_us=g_us, loop_us=l_us, grouped_over_loop=round(g_us / l_us, 4),
@@ -692,9 +763,12 @@ def main_input_grad(args):
             row["per_process_parts_us"] = [{k: v["us"] for k, v in p["parts"].items()} for p in per]
         rows.append(row)
         print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
-    out = {"what": "grouped input gradient (one launch) vs a per-expert loop of dequantize + mm with host-known row counts; and one "
-                   "backward step of FluteExperts(fused=True, native_routing=True) split into its launches; hipGraph replays, "
-                   "device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
+    what = {"input_grad": "grouped input gradient (one launch) vs a per-expert loop of dequantize + mm with host-known row counts; and one "
+                          "backward step of FluteExperts(fused=True, native_routing=True) split into its launches; hipGraph replays, "
+                          "device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
+            "scale_grad": "grouped scale gradient (one launch) vs a per-expert loop of the dense qgemm_scale_grad with host-known row "
+                          "counts; hipGraph replays, device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop"}
+    out = {"what": what[args.mode],
            "config": {"bits": BITS, "group_size": G, "dtype": "float16", "steps": args.steps, "warmup": args.warmup,
                       "replays": args.replays, "processes": args.processes, "device": runs[0]["device"]},
            "rows": rows}
@@ -719,7 +793,8 @@ def main():
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
-    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad"], default="projection")
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad"],
+                    default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
@@ -729,13 +804,14 @@ def main():
         args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
                                                    "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json",
                                                    "gate_limited": "grouped_moe_gate_limited.json",
-                                                   "input_grad": "grouped_moe_input_grad.json"}[args.mode])
-    if args.mode == "input_grad":
+                                                   "input_grad": "grouped_moe_input_grad.json",
+                                                   "scale_grad": "grouped_moe_scale_grad.json"}[args.mode])
+    if args.mode in ("input_grad", "scale_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
         device = torch.device("cuda", 0)
         torch.cuda.set_device(device)
-        return child_input_grad(args, device)
+        return child_scale_grad(args, device) if args.mode == "scale_grad" else child_input_grad(args, device)
     if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
