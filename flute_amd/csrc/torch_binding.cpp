@@ -13,6 +13,8 @@
 #include <torch/autograd.h>
 #include <torch/library.h>
 
+#include <cstdint>
+
 #include "../../include/flute_amd.h"
 
 namespace {
@@ -22,6 +24,15 @@ int dtype_id(const at::Tensor& t) {
     if (t.scalar_type() == at::kBFloat16) return FLUTE_BF16;
     TORCH_CHECK_TYPE(false, "Only fp16 and bf16 supported currently");
     return -1;
+}
+
+// A tensor as the C ABI takes it (include/flute_amd.h: contiguous, 16-B aligned): borrowed when it already is - no
+// allocation, no operator call - otherwise a fresh contiguous copy, which the allocator aligns.  A contiguous view such
+// as buf[1:1 + n] is not aligned, and the kernels address their operands with 16-B loads and buffer descriptors.
+c10::MaybeOwned<at::Tensor> abi_tensor(const at::Tensor& t) {
+    if (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0)
+        return c10::MaybeOwned<at::Tensor>::borrowed(t);
+    return c10::MaybeOwned<at::Tensor>::owned(t.clone(at::MemoryFormat::Contiguous));
 }
 
 // flute/ops.py:17-49 (the reference validates in its fake impl only and trusts raw pointers in the real one,
@@ -57,8 +68,12 @@ at::Tensor qgemm_impl(const at::Tensor& input, const at::Tensor& weight, const a
                 "flute::qgemm_raw_simple: all tensors must be on the input's device");
     const int64_t K = input.size(-1), N = scales.size(0);
     const bool flat = input.dim() == 2 && input.is_contiguous();          // the decode-loop case: no view objects at all
-    at::Tensor x2d = flat ? input : input.reshape({-1, K});
-    if (!x2d.is_contiguous()) x2d = x2d.contiguous();
+    at::Tensor reshaped;
+    if (!flat) reshaped = input.reshape({-1, K});
+    const c10::MaybeOwned<at::Tensor> x2d_ = abi_tensor(*(flat ? &input : &reshaped));
+    const c10::MaybeOwned<at::Tensor> weight_ = abi_tensor(weight), scales_ = abi_tensor(scales),
+                                      table_ = abi_tensor(table), table2_ = abi_tensor(table2);
+    const at::Tensor& x2d = *x2d_;
     const int64_t M = x2d.size(0);
     at::Tensor out = at::empty({M, N}, input.options());
     if (M > 0) {
@@ -83,8 +98,8 @@ at::Tensor qgemm_impl(const at::Tensor& input, const at::Tensor& weight, const a
         }
         const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();   // qgemm.cpp:105
         const int rc = flute_qgemm_hadamard(dt, (int)num_bits, (int)group_size, (int)hadamard_size, (int)M, (int)N,
-                                            (int)K, (int)weight.size(0), x2d.data_ptr(), weight.data_ptr(),
-                                            out.data_ptr(), scales.data_ptr(), table.data_ptr(), table2.data_ptr(),
+                                            (int)K, (int)weight.size(0), x2d.data_ptr(), weight_->data_ptr(),
+                                            out.data_ptr(), scales_->data_ptr(), table_->data_ptr(), table2_->data_ptr(),
                                             scratch_ptr, workspace.data_ptr(), (size_t)workspace.numel(),
                                             (int)template_id, (int)num_sms, stream);
         TORCH_CHECK(rc == FLUTE_OK, flute_strerror(rc));      // RuntimeError with the reference's message prefixes
@@ -132,7 +147,8 @@ int64_t check_dequant_args(const at::Tensor& weight, const at::Tensor& scales, c
     return N;
 }
 
-// columns [k0, k0 + W.size(1)) of the dense weight into W ([N, k_count] contiguous, scales' dtype)
+// columns [k0, k0 + W.size(1)) of the dense weight into W ([N, k_count] contiguous, scales' dtype); weight, scales and table2
+// as abi_tensor returns them (the callers realign once, not per chunk)
 void dequantize_into(const at::Tensor& weight, const at::Tensor& scales, const at::Tensor& table2, int64_t num_bits,
                      int64_t group_size, int64_t template_id, int64_t k0, at::Tensor& W) {
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(scales.device());
@@ -148,7 +164,7 @@ at::Tensor dequantize(const at::Tensor& weight, const at::Tensor& scales, const 
                       int64_t group_size, int64_t template_id) {
     const int64_t N = check_dequant_args(weight, scales, table2, num_bits, group_size);
     at::Tensor W = at::empty({N, weight.size(1)}, scales.options());
-    dequantize_into(weight, scales, table2, num_bits, group_size, template_id, 0, W);
+    dequantize_into(*abi_tensor(weight), *abi_tensor(scales), *abi_tensor(table2), num_bits, group_size, template_id, 0, W);
     return W;
 }
 
@@ -174,10 +190,11 @@ at::Tensor qgemm_input_grad(const at::Tensor& dY, const at::Tensor& weight, cons
         int64_t kc = 64;
         while (kc * 2 * N * 2 <= kBackwardScratchBytes) kc *= 2;
         at::Tensor W = at::empty({N, std::min(kc, K)}, scales.options());
+        const c10::MaybeOwned<at::Tensor> weight_ = abi_tensor(weight), scales_ = abi_tensor(scales), table2_ = abi_tensor(table2);
         for (int64_t k0 = 0; k0 < K; k0 += kc) {
             const int64_t kn = std::min(kc, K - k0);
             at::Tensor Wc = kn == W.size(1) ? W : W.narrow(1, 0, kn).contiguous();
-            dequantize_into(weight, scales, table2, num_bits, group_size, template_id, k0, Wc);
+            dequantize_into(*weight_, *scales_, *table2_, num_bits, group_size, template_id, k0, Wc);
             if (kn == K) {
                 at::mm_out(dx, dy, Wc);
             } else {

@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .ops import _DTYPE_ID, _stream_ptr, _validate
+from .ops import _DTYPE_ID, _abi_tensor, _stream_ptr, _validate
 
 Overrides = _lib.Overrides
 
@@ -21,7 +21,8 @@ def qgemm_planned(input: torch.Tensor, weight: torch.Tensor, scales: torch.Tenso
     _validate(input, weight, scales, table, table2, workspace, num_bits, group_size)
     K = input.shape[-1]
     N = scales.shape[0]
-    x2d = input.reshape(-1, K).contiguous()
+    x2d = _abi_tensor(input.reshape(-1, K))
+    weight, scales, table, table2 = (_abi_tensor(t) for t in (weight, scales, table, table2))
     M = x2d.shape[0]
     out = torch.empty((M, N), dtype=input.dtype, device=input.device)
     if M == 0:

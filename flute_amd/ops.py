@@ -66,6 +66,15 @@ def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _abi_tensor(t):
+    """`t` as the C ABI takes it (include/flute_amd.h: contiguous, 16-B aligned): `t` itself when it already is - no
+    allocation, no torch op - otherwise a fresh contiguous copy, which the allocator aligns.  A contiguous view such as
+    buf[1:1 + n] is not aligned, and the kernels address their operands with 16-B loads and buffer descriptors."""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def hadamard_transform(input: torch.Tensor, hadamard_size: int) -> torch.Tensor:
     """apply_hadamard (qgemm.cpp:201-211): out-of-place FWHT over
     input.reshape(-1, hadamard_size), orthonormal."""
@@ -75,7 +84,7 @@ def hadamard_transform(input: torch.Tensor, hadamard_size: int) -> torch.Tensor:
         raise RuntimeError("flute_amd.hadamard_transform: tensor must live on the GPU")
     if input.shape[-1] % hadamard_size and input.numel() % hadamard_size:
         raise RuntimeError(f"shape {tuple(input.shape)} is invalid for hadamard_size {hadamard_size}")
-    x = input.contiguous()
+    x = _abi_tensor(input)
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):
         _lib.check(_lib.get().flute_hadamard(
@@ -167,8 +176,8 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if not all(t.is_cuda and t.device == dev for t in (grad_output, input, weight, table2)):
         raise RuntimeError("flute_amd.qgemm_scale_grad: all tensors must live on the same GPU")
     K, N = input.shape[-1], grad_output.shape[-1]
-    x = input.reshape(-1, K).contiguous()
-    dy = grad_output.reshape(-1, N).contiguous()
+    x = _abi_tensor(input.reshape(-1, K))
+    dy = _abi_tensor(grad_output.reshape(-1, N))
     M = x.shape[0]
     if M >= 2 ** 31:
         raise ValueError
@@ -178,8 +187,8 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if num_sms is None:
         num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
     scratch = torch.empty(_scale_grad_scratch_bytes(N, K, group_size, num_sms), dtype=torch.uint8, device=dev)
-    w = weight.contiguous()
-    t2 = table2.contiguous()
+    w = _abi_tensor(weight)
+    t2 = _abi_tensor(table2)
     with torch.cuda.device(dev):
         _lib.check(_lib.get().flute_qgemm_scale_grad(
             _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
@@ -234,8 +243,8 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if not all(t.is_cuda and t.device == dev for t in tensors):
         raise RuntimeError("flute_amd.qgemm_table_grad: all tensors must live on the same GPU")
     K, N = input.shape[-1], grad_output.shape[-1]
-    x = input.reshape(-1, K).contiguous()
-    dy = grad_output.reshape(-1, N).contiguous()
+    x = _abi_tensor(input.reshape(-1, K))
+    dy = _abi_tensor(grad_output.reshape(-1, N))
     M = x.shape[0]
     if M >= 2 ** 31:
         raise ValueError
@@ -252,9 +261,9 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if nbytes == 0:
         raise ValueError(f"flute_amd.qgemm_table_grad: no kernel for N = {N}, K = {K}, group size {group_size}")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    w = weight.contiguous()
-    s = scales.contiguous()
-    t2 = table2.contiguous() if with_scale_grad else None
+    w = _abi_tensor(weight)
+    s = _abi_tensor(scales)
+    t2 = _abi_tensor(table2) if with_scale_grad else None
     with torch.cuda.device(dev):
         _lib.check(lib.flute_qgemm_table_grad(
             _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
@@ -325,7 +334,7 @@ def _launch_grouped(name, rows, weight, N, tensors, num_bits, group_size, templa
         raise RuntimeError(f"flute_amd.{name}: all tensors must live on the same GPU")
     if max(rows) >= 2 ** 31:
         raise ValueError
-    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
     out = torch.empty((rows[0], N), dtype=input.dtype, device=dev)
     if num_sms is None:
         num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -602,7 +611,7 @@ def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, w
     E, P, K = weight.shape
     if R >= 2 ** 31:
         raise ValueError
-    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
     out = torch.empty((R, K), dtype=grad_output.dtype, device=dev)
     if num_sms is None:
         num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -666,7 +675,7 @@ def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     E, P = weight.shape[0], weight.shape[1]
     if R >= 2 ** 31 - 64:
         raise ValueError
-    ptrs = [None if t is None else t.contiguous() for t in tensors]
+    ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
     out = torch.empty((E, N, K // group_size), dtype=input.dtype, device=dev)
     if num_sms is None:
         num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -739,8 +748,8 @@ def _moe_route_call(topk_ids, topk_weights, num_experts):
         raise RuntimeError("flute_amd.moe_route: all tensors must live on the same GPU")
     T, k = topk_ids.shape
     P, E = T * k, int(num_experts)
-    ids = topk_ids.contiguous()
-    w = None if topk_weights is None else topk_weights.contiguous()
+    ids = _abi_tensor(topk_ids)
+    w = None if topk_weights is None else _abi_tensor(topk_weights)
     offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(P, dtype=torch.int32, device=dev)
     rows = torch.empty(P, dtype=torch.int32, device=dev)
@@ -787,8 +796,8 @@ def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=
         raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
     T, E = logits.shape
     k = int(k)
-    x = logits.contiguous()
-    b = None if bias is None else bias.contiguous()
+    x = _abi_tensor(logits)
+    b = None if bias is None else _abi_tensor(bias)
     ids = torch.empty((T, k), dtype=torch.int32, device=dev)
     weights = torch.empty((T, k), dtype=torch.float32, device=dev)
     group_args = () if groups is None else (int(groups[0]), int(groups[1]), _GATE_GROUP_SCORE_ID[groups[2]])
@@ -984,7 +993,7 @@ def _moe_combine_call(y, pos, offsets):
         raise RuntimeError("flute_amd.moe_combine: all tensors must live on the same GPU")
     T, k = pos.shape
     N = y.shape[1]
-    yc, p, off = y.contiguous(), pos.contiguous(), offsets.contiguous()
+    yc, p, off = _abi_tensor(y), _abi_tensor(pos), _abi_tensor(offsets)
     out = torch.empty((T, N), dtype=y.dtype, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.get().flute_moe_combine(

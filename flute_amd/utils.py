@@ -214,7 +214,8 @@ def unpack_codes(weight: torch.Tensor, num_bits: int, template_id: int) -> torch
         raise TypeError
     if not weight.is_cuda:
         raise RuntimeError("flute_amd.utils.unpack_codes needs a GPU tensor (native HIP unpacker)")
-    weight = weight.contiguous()
+    from .ops import _abi_tensor
+    weight = _abi_tensor(weight)
     P, K = weight.shape
     N = P * 16 // num_bits
     W = torch.empty((K, N), dtype=torch.uint8, device=weight.device)

@@ -8,7 +8,10 @@
  * (the reference's tuner string-matches those, flute/tune.py:160-167).
  *
  * Device pointers must be valid on the current HIP device, contiguous and 16-B
- * aligned (torch allocations are).  Nothing here allocates, synchronises or
+ * aligned (torch allocations are).  A contiguous torch VIEW need not be (buf[1:1 + n]
+ * is 2 bytes off): the Python entry points (flute_amd/ops.py) and the torch binding
+ * (csrc/torch_binding.cpp) realign such views - a fresh copy - before they pass a
+ * pointer; a caller of this C ABI does that itself.  Nothing here allocates, synchronises or
  * touches the host after enqueue: every call is stream-ordered on `stream`
  * (a hipStream_t) and hipGraph-capturable, like the reference's launch on
  * at::cuda::getCurrentCUDAStream() (flute/csrc/qgemm.cpp:101-105).
@@ -173,7 +176,15 @@ typedef struct flute_overrides {
  *   S  [N,K/group_size] T         QM [2^b] T (unused by the kernel, as in the reference)
  *   QM2 [2^b,2^b] pairs of T in one 32-bit word (flute/utils.py:15-33)
  *   workspace: caller-owned scratch, used for split-K slabs; may be NULL when
- *   the plan has splitk == 1 (flute/utils.py:36-56 over-allocates it). */
+ *   the plan has splitk == 1 (flute/utils.py:36-56 over-allocates it).
+ * Arithmetic, every family: w^ = round_T(lut * s) or the scale applied in fp32 to an fp32 partial sum; fp32
+ * accumulation; one IEEE round-to-nearest-even of the output.  No exception at the edges of T (measured on gfx950,
+ * tests/test_value_edges_gpu.py): fp16 subnormal weights and activations are multiplied as they are (neither the packed
+ * dot instructions nor the matrix unit flush them), a result beyond the largest finite T is +-inf (no saturation), a
+ * subnormal result is rounded correctly.  A NaN or Inf in A propagates through its own row only, by IEEE rules (Inf
+ * times a zero weight is NaN).  Nothing outside an operand's extent reaches a result, whatever lies next to it in
+ * memory.  QM2 (and QM) must hold finite values: a table entry of Inf or NaN is not a supported input (the bf16
+ * block kernels form lo * s + hi * 0 per packed table word). */
 int flute_qgemm(int dtype, int num_bits, int group_size, int M, int N, int K, int P,
                 const void* A, const void* Q, void* D, const void* S, const void* QM,
                 const void* QM2, void* workspace, size_t workspace_bytes, int template_id,

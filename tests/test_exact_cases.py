@@ -159,3 +159,114 @@ def test_persistm_sets_override_that_cannot_apply_is_refused():
     assert p["family"] == 8 and p["visits"] == 4 and p["grid"] <= NUM_SMS, p
     p = dev.get_plan(4, 28672, 8192, 4, 64, tid, NUM_SMS, torch.float16, dev.Overrides(family=8))
     assert p["family"] == 8 and p["grid"] <= NUM_SMS, p
+
+
+# ---------------------------------------------------------------------------
+# the fp16 range edges and non-finite rows (exact_cases.edge_cases, tests/test_value_edges_gpu.py)
+# ---------------------------------------------------------------------------
+
+FAMILIES = (0, 2, 3, 5, 6, 7, 8)
+
+
+def _edge_layers(kind):
+    seen = {}
+    for fam in FAMILIES:
+        for kw, M, ovr, exp in E.edge_cases(fam, kind):
+            seen.setdefault(E.layer_key(kw), (kw, set()))[1].add(M)
+    return list(seen.values())
+
+
+def test_edge_premises_hold():
+    """Every layer of the three fp16 kinds, with the seeds the GPU test uses: operands representable, sums exact in fp32, at least
+    half the weights and some outputs subnormal ("subw"), every activation subnormal ("subx"), +inf, -inf and a finite
+    output above 2^15 ("overflow").  Wide layers: their first 1024 columns (the overflow rows are built from the first 256)."""
+    for kind in ("subw", "subx", "overflow"):
+        layers = _edge_layers(kind)
+        assert layers
+        for kw, Ms in layers:
+            lay = E.make_layer(kw, E.seed_of(E.layer_key(kw)))
+            for M in sorted(Ms):
+                X = E.edge_x(kind, M, lay, E.seed_of(kind, M))
+                full = lay.N
+                lay.N = min(full, 1024)
+                R, A = E.exact_product(X, lay, abs_too=True)
+                lay.N = full
+                E.premise_edge(kind, X, lay, R, A)
+                if kind == "overflow":                      # the old premise but for the output range it leaves on purpose
+                    assert kw["K"] * 64 < E.EXACT_SUM_LIMIT
+                    assert float(R.abs().max()) > E.FP16_MAX
+
+
+def test_edge_cases_plan_to_their_variants():
+    """Host planner only: every edge case plans to the family and variant it asks for, and within a family every bit width
+    and every way of combining K is there."""
+    from flute_amd import dev
+    for fam in FAMILIES:
+        for kind in E.EDGE_KINDS:
+            cases = E.edge_cases(fam, kind)
+            assert cases, (fam, kind)
+            ways = set()
+            for kw, M, ovr, exp in cases:
+                try:
+                    plan = dev.get_plan(M, kw["N"], kw["K"], kw["bits"], kw["g"], first_template(kw["bits"], kw["tile_p"]), NUM_SMS,
+                                        kw["dtype"], dev.Overrides(**ovr))
+                except RuntimeError:
+                    assert exp.get("may_refuse"), (fam, kind, kw, M, ovr)
+                    continue
+                for k, v in exp.items():
+                    if k == "may_refuse":
+                        continue
+                    assert plan[k] in (v if isinstance(v, tuple) else (v,)), (kind, kw, M, ovr, k, v, plan)
+                ways.add(E.edge_way(fam, kw["bits"], plan))
+            E.assert_edge_coverage(fam, kind, cases, ways)
+
+
+def test_edge_checks_reject_wrong_kernels():
+    """Three wrong kernels, simulated in torch on the CPU, that the suite's operating region let through: one that reads fp16
+    subnormal weights and activations as zero, one that saturates at 65504 where IEEE rounds to infinity, one that reads a
+    NaN-carrying padded row of the weight (past K) and masks it by multiplying with a zero activation."""
+    T = torch.float16
+    kw = dict(bits=4, K=4096, N=512, g=64, dtype=T, tile_p=32, pair=False)
+    for kind in ("subw", "subx"):
+        lay = E.make_layer(dict(kw, **(E.SUBW if kind == "subw" else {})), 21)
+        X = E.edge_x(kind, 5, lay, 22)
+        R, A = E.exact_product(X, lay, abs_too=True)
+        E.premise_edge(kind, X, lay, R, A)
+        assert E.exact_equal(R.to(T), R, T)
+        flushed = E.flush_subnormal_f16(X.double()) @ E.flush_subnormal_f16(lay.w_exact())
+        assert not E.exact_equal(flushed.to(T), R, T), kind
+        assert E.exact_equal(flushed.to(T), E.exact_product(X, lay, flush_w=True, flush_x=True), T)
+    lay = E.make_layer(dict(kw, **E.OVERFLOW), 23)
+    X = E.edge_x("overflow", 5, lay, 24)
+    R, A = E.exact_product(X, lay, abs_too=True)
+    E.premise_edge("overflow", X, lay, R, A)
+    assert E.exact_equal(R.to(T), R, T)
+    assert not E.exact_equal(R.clamp(-E.FP16_MAX, E.FP16_MAX).to(T), R, T)
+    # the weight padded to the next multiple of 1024 rows with a neighbour's NaN, the activations padded with zeros
+    lay = E.make_layer(dict(kw, K=3584), 25)
+    X = E.make_x(5, lay.K, 26, T)
+    R = E.exact_product(X, lay)
+    Wp = torch.cat([lay.w_exact(), torch.full((512, lay.N), float("nan"), dtype=torch.float64)])
+    Xp = torch.cat([X.double(), torch.zeros(5, 512, dtype=torch.float64)], 1)
+    masked = (Xp[:, :, None] * Wp[None, :, :64]).sum(1)              # x * w term by term: 0 * NaN = NaN
+    assert torch.isnan(masked).all() and not E.exact_equal(masked.to(T), R[:, :64], T)
+    selected = (Xp[:, :lay.K, None] * Wp[None, :lay.K, :64]).sum(1)  # a predicate on k < K instead
+    assert E.exact_equal(selected.to(T), R[:, :64], T)
+
+
+def test_nonfinite_rule():
+    """nonfinite_expected against IEEE arithmetic term by term on a small layer, and nonfinite_equal's NaN handling."""
+    for T in (torch.float16, torch.bfloat16):
+        lay = E.Layer(4, 256, 128, 64, T, 31, pair=True)
+        X = E.make_x(4, 256, 32, T)
+        clean = E.exact_product(X, lay).to(T)
+        k_inf = next(k for k in range(256) if (lay.w_exact()[k] == 0).any() and (lay.w_exact()[k] > 0).any() and (lay.w_exact()[k] < 0).any())
+        Xp = E.poison_x(X, 1, 2, 7, k_inf)
+        ieee = (Xp.double()[:, :, None] * lay.w_exact()[None]).sum(1).to(T)
+        exp = E.nonfinite_expected(clean, lay, 1, 2, k_inf)
+        assert E.nonfinite_equal(ieee, exp)
+        assert torch.isnan(exp[1]).all() and torch.isnan(exp[2]).any() and (exp[2] == float("inf")).any() and (exp[2] == -float("inf")).any()
+        assert not E.nonfinite_equal(clean, exp)
+        bad = exp.clone()
+        bad[2] = float("nan")
+        assert not E.nonfinite_equal(bad, exp)

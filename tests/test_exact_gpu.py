@@ -2,13 +2,14 @@
 
 With integer activations, integer lookup tables and power-of-two scales every partial sum is exact in fp32, so the
 documented arithmetic (fp32 accumulation, one rounding of the output) allows one answer only: round_T(X @ W_exact).
-Each launch writes into the middle of a NaN-filled buffer; afterwards the guard bands are untouched, no output
-element is left unwritten, the inputs are unchanged and the in-launch reduction state words are zero again.  Before
+Each launch writes into the middle of a NaN-filled buffer, and every operand it reads (X, Q, S, table, table2) sits in
+the middle of a poisoned buffer of its own - NaN around the floating operands, a non-zero code pattern around Q - so a
+read past an operand's end that is only masked by a multiply with zero reaches the result; afterwards the guard bands
+are untouched, no output element is left unwritten, the inputs are unchanged and the in-launch reduction state words
+are zero again.  Before
 each launch the plan is checked to be the family and variant the case asks for (overrides can fall back or clamp).
 Where exactness is impossible (random NF4 data, the 1 / sqrt(512) rotation) a proven per-element bound is checked.
 """
-import zlib
-
 import pytest
 import torch
 
@@ -16,7 +17,32 @@ from tests import exact_cases as E
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096            # elements on each side of D: 8 KB, D stays 16-B aligned
+GUARD = 4096            # elements on each side of D and of every operand: a multiple of 16 B, the middle stays 16-B aligned
+Q_GUARD_BITS = 0x5A5A   # the code pattern around the packed weight
+_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32}
+
+
+def guard_bits(t, T):
+    """What surrounds operand `t` of a layer in T: NaN in T (both halves of a table2 pair word), a code pattern for Q."""
+    if t.dtype == torch.int16:
+        return Q_GUARD_BITS
+    nan = E.NAN_BITS[T]
+    return nan << 16 | nan if t.element_size() == 4 else nan
+
+
+class Carved:
+    """A copy of `t` on the device in the middle of a larger buffer filled with `fill` bits, contiguous and 16-B aligned."""
+
+    def __init__(self, t, dev, fill):
+        n = t.numel()
+        self.fill, self.n = fill, n
+        self.buf = torch.full((GUARD + n + GUARD,), fill, dtype=_INT[t.element_size()], device=dev)
+        self.buf[GUARD:GUARD + n] = t.contiguous().view(self.buf.dtype).reshape(-1).to(dev)
+        self.t = self.buf[GUARD:GUARD + n].view(t.dtype).view(t.shape)
+        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0 and self.t.shape == t.shape
+
+    def intact(self):
+        return bool(torch.all(self.buf[:GUARD] == self.fill) and torch.all(self.buf[GUARD + self.n:] == self.fill))
 
 
 @pytest.fixture(scope="module")
@@ -43,8 +69,7 @@ def first_template(fa, bits, tile_p):
     return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
-def seed_of(*key):
-    return zlib.crc32(repr(key).encode()) & 0x7FFFFFFF
+seed_of = E.seed_of
 
 
 class DevLayer:
@@ -54,17 +79,24 @@ class DevLayer:
         self.lay = lay
         self.tid = first_template(env.fa, lay.bits, lay.tile_p)
         d = env.dev
-        self.Q = env.utils.pack(lay.W.to(d), lay.bits, [self.tid], env.num_sms)
-        self.S, self.table, self.table2 = lay.S.to(d), lay.table.to(d), lay.table2.to(d)
+        self.set_operands(d, env.utils.pack(lay.W.to(d), lay.bits, [self.tid], env.num_sms), lay.S, lay.table, lay.table2)
         self.witnessed = False
+
+    def set_operands(self, d, Q, S, table, table2):
+        T = S.dtype
+        self.carved = [Carved(t, d, guard_bits(t, T)) for t in (Q, S, table, table2)]
+        self.Q, self.S, self.table, self.table2 = (c.t for c in self.carved)
+
+    def guards_intact(self):
+        return all(c.intact() for c in self.carved)
 
 
 def get_layer(env, kw):
-    key = tuple(sorted((k, str(v)) for k, v in kw.items()))
+    key = E.layer_key(kw)
     if key not in env.layers:
         env.layers.clear()                       # one layer at a time on the device (the matrix is grouped by layer)
         torch.cuda.empty_cache()
-        lay = E.Layer(kw["bits"], kw["K"], kw["N"], kw["g"], kw["dtype"], seed_of(key), kw["tile_p"], kw["pair"])
+        lay = E.make_layer(kw, seed_of(key))
         env.layers[key] = DevLayer(env, lay)
     return env.layers[key]
 
@@ -77,12 +109,14 @@ def state_words_clean(env):
     return int(env.ws[:65536].view(torch.int32).abs().sum().item()) == 0
 
 
-def guarded_qgemm(env, dl, X, ovr=None, hadamard_size=0):
-    """flute_qgemm_ex with D in the middle of a NaN-filled buffer; checks guards, coverage, inputs, state words."""
+def guarded_qgemm(env, dl, X, ovr=None, hadamard_size=0, nan_expected=False):
+    """flute_qgemm_ex with D and every operand in the middle of poisoned buffers; checks guards, coverage, inputs, state
+    words.  nan_expected: X itself holds a NaN or an Inf (the coverage check then belongs to the clean launch)."""
     lay = dl.lay
     T = lay.dtype
     M, K, N = X.shape[0], lay.K, lay.N
-    X = X.to(env.dev).contiguous()
+    Xc = Carved(X, env.dev, guard_bits(X, T))
+    X = Xc.t
     buf = torch.full((GUARD + M * N + GUARD,), E.NAN_BITS[T], dtype=torch.int16, device=env.dev)
     D = buf[GUARD:GUARD + M * N].view(T)
     assert D.data_ptr() % 16 == 0
@@ -98,9 +132,10 @@ def guarded_qgemm(env, dl, X, ovr=None, hadamard_size=0):
     env.check(rc)
     torch.cuda.synchronize()
     assert torch.all(buf[:GUARD] == E.NAN_BITS[T]) and torch.all(buf[GUARD + M * N:] == E.NAN_BITS[T]), "write outside D"
-    assert not torch.isnan(D).any(), "output element left unwritten"
+    assert nan_expected or not torch.isnan(D).any(), "output element left unwritten"
     after = [_bits(t) for t in (X, dl.Q, dl.S, dl.table, dl.table2)]
     assert all(torch.equal(a, b) for a, b in zip(before, after)), "an input was modified"
+    assert Xc.intact() and dl.guards_intact(), "an operand's guard band was modified"
     assert state_words_clean(env), "state words left set"
     return D.view(M, N).clone()
 
@@ -164,9 +199,10 @@ def test_automatic_plans_exact(env):
         X = E.make_x(M, lay.K, seed_of("auto", M), lay.dtype)
         R, A = E.exact_product(X, lay, env.dev, abs_too=True)
         E.premise(X, lay, R.cpu(), A.cpu(), witness=False)
-        d = env.dev
-        D = env.fa.qgemm(X.to(d), dl.Q, dl.S, dl.table, dl.table2, env.ws, lay.bits, lay.g, dl.tid, env.num_sms)
+        Xc = Carved(X, env.dev, guard_bits(X, lay.dtype))
+        D = env.fa.qgemm(Xc.t, dl.Q, dl.S, dl.table, dl.table2, env.ws, lay.bits, lay.g, dl.tid, env.num_sms)
         assert E.exact_equal(D, R, lay.dtype), (lay, M, plan["family"])
+        assert Xc.intact() and dl.guards_intact(), "an operand's guard band was modified"
         assert state_words_clean(env)
         reached.setdefault(plan["family"], []).append((lay.N, lay.K, M))
     print("automatic plans reached:", {f: len(v) for f, v in sorted(reached.items())})
@@ -263,7 +299,7 @@ def test_componentwise_random_nf4(env):
         ndl = DevLayer.__new__(DevLayer)
         ndl.__dict__.update(dl.__dict__)
         ndl.lay = nf
-        ndl.S, ndl.table, ndl.table2 = S.to(d), table.to(d), env.utils.make_qmap2_from_qmap(table).to(d)
+        ndl.set_operands(d, dl.Q, S, table, env.utils.make_qmap2_from_qmap(table))
         D = guarded_qgemm(env, ndl, X, ovr)
         R, A = E.exact_product(X, nf, d, abs_too=True)
         ex = E.componentwise_excess(D, R, A, lay.K, dtype)

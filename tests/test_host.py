@@ -270,3 +270,22 @@ def test_persistent_mfma_decode_kernel_activation_ring_layout():
                     addrs.add(r * 1024 + (16 * mm + 4 * (s ^ mm) + (kg ^ g(r))) * 16)
                 slots = {(a // 16) % 16 for a in addrs}
                 assert len(slots) == len(addrs) and (xr < 4 or len(addrs) == 16), (xr, s, grp)       # distinct addresses never share a slot
+
+
+def test_abi_tensor_realigns_views():
+    """ops._abi_tensor: the tensor itself when it is contiguous and 16-B aligned (no copy), otherwise an equal, aligned,
+    contiguous copy - a contiguous view one element into a buffer is 2 bytes off."""
+    import torch
+    from flute_amd.ops import _abi_tensor
+    buf = torch.arange(64 * 9 + 8, dtype=torch.float32).to(torch.float16)
+    assert buf.data_ptr() % 16 == 0 and _abi_tensor(buf) is buf
+    aligned = buf[8:8 + 64].view(8, 8)
+    assert _abi_tensor(aligned) is aligned
+    for off in (1, 4):
+        v = buf[off:off + 64 * 9].view(64, 9)
+        assert v.is_contiguous() and v.data_ptr() % 16 != 0
+        c = _abi_tensor(v)
+        assert c is not v and c.data_ptr() % 16 == 0 and c.is_contiguous() and torch.equal(c, v) and c.dtype == v.dtype
+    t = buf[:64].view(8, 8).t()                                  # aligned but not contiguous
+    c = _abi_tensor(t)
+    assert c.is_contiguous() and c.data_ptr() % 16 == 0 and torch.equal(c, t)
