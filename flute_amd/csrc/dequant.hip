@@ -10,7 +10,7 @@
 // per plane.  Every workgroup stages the pair table (<= 1 KB) in LDS; the 8 k of a lane share one scale (8 divides
 // every group size).
 #include "kernels.h"
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -74,20 +74,11 @@ int dequant_dispatch(int dtype, int num_bits, int tile_p, int N, int K, int lg, 
     const uint16_t* s = reinterpret_cast<const uint16_t*>(S);
     const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
     uint16_t* w = reinterpret_cast<uint16_t*>(W);
-#define FLUTE_DEQ(TY, B, TP)                                                                                       \
-    hipLaunchKernelGGL((dequant_kernel<TY, B, TP>), dim3(grid), dim3(kDequantThreads), 0, stream, q, s, qm2, w, N, K, \
-                       lg, k_begin, k_count)
-#define FLUTE_DEQ_T(B, TP)                 \
-    if (dtype == FLUTE_F16) FLUTE_DEQ(F16, B, TP); \
-    else FLUTE_DEQ(BF16, B, TP)
-    if (num_bits == 4 && tile_p == 32) { FLUTE_DEQ_T(4, 32); }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_DEQ_T(4, 64); }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_DEQ_T(2, 32); }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_DEQ_T(2, 64); }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_DEQ_T(3, 32); }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_DEQ_T
-#undef FLUTE_DEQ
+    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+        hipLaunchKernelGGL((dequant_kernel<decltype(t), bits(), tp()>), dim3(grid), dim3(kDequantThreads), 0, stream, q, s,
+                           qm2, w, N, K, lg, k_begin, k_count);
+    });
+    if (err != FLUTE_OK) return err;
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 

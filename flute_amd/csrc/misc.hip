@@ -1,6 +1,7 @@
 // Small kernels around the hot path: split-K second pass and the native unpacker.
 #include "kernels.h"
 #include "mfma.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -53,15 +54,11 @@ int unpack_dispatch(int num_bits, int tile_p, int N, int K, const void* Q, void*
     const unsigned grid = (unsigned)((total + 255) / 256);
     const uint32_t* q = reinterpret_cast<const uint32_t*>(Q);
     uint8_t* w = reinterpret_cast<uint8_t*>(W);
-#define FLUTE_UNPACK(B, TP) \
-    hipLaunchKernelGGL((unpack_kernel<B, TP>), dim3(grid), dim3(256), 0, stream, q, w, N, K)
-    if (num_bits == 4 && tile_p == 32) FLUTE_UNPACK(4, 32);
-    else if (num_bits == 4 && tile_p == 64) FLUTE_UNPACK(4, 64);
-    else if (num_bits == 2 && tile_p == 32) FLUTE_UNPACK(2, 32);
-    else if (num_bits == 2 && tile_p == 64) FLUTE_UNPACK(2, 64);
-    else if (num_bits == 3 && tile_p == 32) FLUTE_UNPACK(3, 32);
-    else return -3;
-#undef FLUTE_UNPACK
+    // (codes have no element type: both types reach the same instantiation)
+    const int err = dispatch_layout(FLUTE_F16, num_bits, tile_p, [&](auto, auto bits, auto tp) {
+        hipLaunchKernelGGL((unpack_kernel<bits(), tp()>), dim3(grid), dim3(256), 0, stream, q, w, N, K);
+    });
+    if (err != FLUTE_OK) return err;
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 

@@ -57,12 +57,6 @@ __device__ __forceinline__ int blk_swz(int row) { return (4 - (row >> 2)) & 3; }
 // lanes of every ds_read_b128 lane group then hit 16 different 16-B slots of the 256-B bank row (tests/test_splitk_layout.py)
 __host__ __device__ constexpr int blk_swz8(int row8, int rh) { return (row8 >> 1) | (rh << 2); }
 
-__host__ __device__ constexpr int block_lds_bytes(int bits, int tm, int wm, int wn) {
-    const int lut = (1 << (2 * bits)) * 128;
-    const int stage = wm * tm * 2 * 1024;                      // BM/16 row tiles x 2 half steps x 1 KB
-    return lut + BLK_STAGES * stage + wm * wn * 3 * 1024 * (bits == 2 ? 2 : 1);     // + per wave: two scale blocks + a sink
-}
-
 // LDS-DMA through a buffer descriptor: 16 B per lane from base + voff (per lane, range-checked) + soff
 // (wave-uniform) to LDS byte m0 + 16 * lane.  No VGPR destination: only the counted vmcnt orders it.
 __device__ __forceinline__ void dma16_buf(uint32_t voff, srd_t srd, uint32_t soff, uint32_t lds_addr) {

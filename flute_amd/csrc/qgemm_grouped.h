@@ -63,7 +63,7 @@
 #include "kernels.h"
 #include "mfma.h"
 #include <type_traits>
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -362,28 +362,21 @@ int qgemm_grouped_launch(int dtype, int num_bits, int tile_p, GroupedArgs a, int
     unsigned grid;
     if (!grouped_grid(a.E, a.N, num_bits, num_sms, &a.spw, &a.runs, &grid)) return FLUTE_ERR_SHAPE;
     const int lg = a.lg;
-#define FLUTE_GRP(TY, B, TP, LGC) \
-    hipLaunchKernelGGL((qgemm_grouped_kernel<TY, B, TP, LGC, MODE>), dim3(grid), dim3(kGroupedThreads), 0, stream, a)
-#define FLUTE_GRP_L(TY, B, TP)                 \
-    if (lg == 5) FLUTE_GRP(TY, B, TP, 5);      \
-    else if (lg == 6) FLUTE_GRP(TY, B, TP, 6); \
-    else FLUTE_GRP(TY, B, TP, 7)
-#define FLUTE_GRP_T(B, TP)                               \
-    if (dtype == FLUTE_F16) { FLUTE_GRP_L(F16, B, TP); } \
-    else { FLUTE_GRP_L(BF16, B, TP); }
-#define FLUTE_GRP_7(B, TP)                                \
-    if (dtype == FLUTE_F16) { FLUTE_GRP(F16, B, TP, 7); } \
-    else { FLUTE_GRP(BF16, B, TP, 7); }
-    if (num_bits == 4 && tile_p == 32) { FLUTE_GRP_7(4, 32) }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_GRP_7(4, 64) }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_GRP_T(2, 32) }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_GRP_T(2, 64) }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_GRP_7(3, 32) }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_GRP_7
-#undef FLUTE_GRP_T
-#undef FLUTE_GRP_L
-#undef FLUTE_GRP
+    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+        constexpr int B = decltype(bits)::value;
+        auto launch = [&](auto lgc) {
+            hipLaunchKernelGGL((qgemm_grouped_kernel<decltype(t), B, decltype(tp)::value, decltype(lgc)::value, MODE>),
+                               dim3(grid), dim3(kGroupedThreads), 0, stream, a);
+        };
+        if constexpr (B == 2) {                         // only the 2-bit kernels take the group size as a constant
+            if (lg == 5) launch(int_c<5>{});
+            else if (lg == 6) launch(int_c<6>{});
+            else launch(int_c<7>{});
+        } else {
+            launch(int_c<7>{});
+        }
+    });
+    if (err != FLUTE_OK) return err;
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 

@@ -44,7 +44,7 @@
 #include "kernels.h"
 #include "mfma.h"
 #include "grad_gemm.h"
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -316,22 +316,17 @@ int qgemm_grouped_input_grad_launch(int dtype, int tile_p, bool pair, GroupedIgA
     a.slabs = (a.K + kIgKS - 1) / kIgKS;
     if ((long long)a.E * a.slabs > 0x7fffffffLL) return FLUTE_ERR_SHAPE;
     const unsigned grid = (unsigned)((long long)a.E * a.slabs);
-#define FLUTE_IG(TY, TP, PR) \
-    hipLaunchKernelGGL((qgemm_grouped_input_grad_kernel<TY, BITS, TP, PR>), dim3(grid), dim3(kIgThreads), 0, stream, a)
-#define FLUTE_IG_P(TY, TP)              \
-    if (pair) FLUTE_IG(TY, TP, true);   \
-    else FLUTE_IG(TY, TP, false)
-#define FLUTE_IG_T(TP)                                  \
-    if (dtype == FLUTE_F16) { FLUTE_IG_P(F16, TP); }    \
-    else { FLUTE_IG_P(BF16, TP); }
-    if (tile_p == 32) { FLUTE_IG_T(32) }
-    else if (tile_p == 64 && BITS != 3) {
-        if constexpr (BITS != 3) { FLUTE_IG_T(64) }
-    }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_IG_T
-#undef FLUTE_IG_P
-#undef FLUTE_IG
+    const int err = dispatch_layout(dtype, BITS, tile_p, [&](auto t, auto bits, auto tp) {
+        if constexpr (decltype(bits)::value == BITS) {  // the other widths live in their own units
+            auto launch = [&](auto pr) {
+                hipLaunchKernelGGL((qgemm_grouped_input_grad_kernel<decltype(t), BITS, decltype(tp)::value, decltype(pr)::value>),
+                                   dim3(grid), dim3(kIgThreads), 0, stream, a);
+            };
+            if (pair) launch(std::true_type{});
+            else launch(std::false_type{});
+        }
+    });
+    if (err != FLUTE_OK) return err;
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 

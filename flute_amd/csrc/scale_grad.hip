@@ -10,7 +10,7 @@
 
 #include "kernels.h"
 #include "grad_gemm.h"
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -70,20 +70,11 @@ int scale_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int 
     const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
     uint16_t* ds = reinterpret_cast<uint16_t*>(dS);
     float* part = splits > 1 ? reinterpret_cast<float*>(scratch) : nullptr;
-#define FLUTE_SG(TY, B, TP)                                                                                          \
-    hipLaunchKernelGGL((scale_grad_kernel<TY, B, TP>), grid, dim3(kSgThreads), 0, stream, y, x, q, qm2, ds, part, M, \
-                       N, K, lg, sps)
-#define FLUTE_SG_T(B, TP)                         \
-    if (dtype == FLUTE_F16) FLUTE_SG(F16, B, TP); \
-    else FLUTE_SG(BF16, B, TP)
-    if (num_bits == 4 && tile_p == 32) { FLUTE_SG_T(4, 32); }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_SG_T(4, 64); }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_SG_T(2, 32); }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_SG_T(2, 64); }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_SG_T(3, 32); }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_SG_T
-#undef FLUTE_SG
+    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+        hipLaunchKernelGGL((scale_grad_kernel<decltype(t), bits(), tp()>), grid, dim3(kSgThreads), 0, stream, y, x, q, qm2,
+                           ds, part, M, N, K, lg, sps);
+    });
+    if (err != FLUTE_OK) return err;
     if (hipGetLastError() != hipSuccess) return FLUTE_ERR_LAUNCH;
     if (splits > 1) {
         const size_t mn = (size_t)N * (size_t)(K >> lg);  // a multiple of 16: N % 128 == 0

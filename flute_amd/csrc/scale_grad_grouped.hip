@@ -15,7 +15,7 @@
 // bases into Q / QM2 / dS and row bases into dY / X are 64-bit.
 #include "kernels.h"
 #include "grad_gemm.h"
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -66,24 +66,16 @@ int scale_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int
     const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
     const float* rw = reinterpret_cast<const float*>(row_weight);
     uint16_t* ds = reinterpret_cast<uint16_t*>(dS);
-#define FLUTE_SGG(TY, B, TP, W)                                                                                       \
-    hipLaunchKernelGGL((scale_grad_grouped_kernel<TY, B, TP, W>), grid, dim3(kSgThreads), 0, stream, y, x, off, q, qm2, \
-                       rw, ds, R, N, K, P, lg)
-#define FLUTE_SGG_W(TY, B, TP)              \
-    if (rw) FLUTE_SGG(TY, B, TP, true);     \
-    else FLUTE_SGG(TY, B, TP, false)
-#define FLUTE_SGG_T(B, TP)                                \
-    if (dtype == FLUTE_F16) { FLUTE_SGG_W(F16, B, TP); }  \
-    else { FLUTE_SGG_W(BF16, B, TP); }
-    if (num_bits == 4 && tile_p == 32) { FLUTE_SGG_T(4, 32) }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_SGG_T(4, 64) }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_SGG_T(2, 32) }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_SGG_T(2, 64) }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_SGG_T(3, 32) }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_SGG_T
-#undef FLUTE_SGG_W
-#undef FLUTE_SGG
+    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+        auto launch = [&](auto weighted) {
+            hipLaunchKernelGGL((scale_grad_grouped_kernel<decltype(t), decltype(bits)::value, decltype(tp)::value,
+                                                          decltype(weighted)::value>),
+                               grid, dim3(kSgThreads), 0, stream, y, x, off, q, qm2, rw, ds, R, N, K, P, lg);
+        };
+        if (rw) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
+    if (err != FLUTE_OK) return err;
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
 }
 

@@ -27,7 +27,7 @@
 
 #include "kernels.h"
 #include "grad_gemm.h"
-#include "../../include/flute_amd.h"
+#include "layout_dispatch.h"
 
 namespace flute_amd {
 
@@ -154,20 +154,11 @@ int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int 
     uint16_t* ds = reinterpret_cast<uint16_t*>(dS);
     float* ds_part = sh.ds_bytes ? reinterpret_cast<float*>(scratch) : nullptr;
     float* t_part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + sh.ds_bytes);
-#define FLUTE_TG(TY, B, TP)                                                                                          \
-    hipLaunchKernelGGL((table_grad_kernel<TY, B, TP>), grid, dim3(kSgThreads), 0, stream, y, x, q, s, qm2, ds,       \
-                       ds_part, t_part, M, N, K, lg, sps)
-#define FLUTE_TG_T(B, TP)                         \
-    if (dtype == FLUTE_F16) FLUTE_TG(F16, B, TP); \
-    else FLUTE_TG(BF16, B, TP)
-    if (num_bits == 4 && tile_p == 32) { FLUTE_TG_T(4, 32); }
-    else if (num_bits == 4 && tile_p == 64) { FLUTE_TG_T(4, 64); }
-    else if (num_bits == 2 && tile_p == 32) { FLUTE_TG_T(2, 32); }
-    else if (num_bits == 2 && tile_p == 64) { FLUTE_TG_T(2, 64); }
-    else if (num_bits == 3 && tile_p == 32) { FLUTE_TG_T(3, 32); }
-    else return FLUTE_ERR_TEMPLATE_ID;
-#undef FLUTE_TG_T
-#undef FLUTE_TG
+    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+        hipLaunchKernelGGL((table_grad_kernel<decltype(t), bits(), tp()>), grid, dim3(kSgThreads), 0, stream, y, x, q, s,
+                           qm2, ds, ds_part, t_part, M, N, K, lg, sps);
+    });
+    if (err != FLUTE_OK) return err;
     if (hipGetLastError() != hipSuccess) return FLUTE_ERR_LAUNCH;
     const int nbins = 2 << (2 * num_bits);
     const long wgs = (long)grid.x * grid.y * grid.z;

@@ -62,12 +62,14 @@ class FluteLinear(torch.nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+    def _launch_resources(self, device: torch.device):
+        """(num_sms, workspace) of a forward on `device`: the layer's own, or with `workspace_lazy_init` the device's."""
         if self.workspace_lazy_init:
-            num_sms = flute_amd.utils.get_device_num_sms(inputs.device)
-            workspace = flute_amd.utils.get_workspace_streamk(inputs.device)
-        else:
-            num_sms, workspace = self.num_sms, self.workspace
+            return flute_amd.utils.get_device_num_sms(device), flute_amd.utils.get_workspace_streamk(device)
+        return self.num_sms, self.workspace
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        num_sms, workspace = self._launch_resources(inputs.device)
         output = flute_amd.qgemm(inputs, self.weight, self.scales, self.tables, self.tables2,
                                  workspace, self.num_bits, self.group_size, self.template_id,
                                  num_sms)

@@ -34,40 +34,6 @@ from flute_amd import ops as _ops
 from .base import FluteLinear
 
 
-class _LearnableScales(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, input, scales, weight, table, table2, workspace, num_bits, group_size, template_id, num_sms,
-                hadamard_size):
-        # the op runs on a detached leaf with detached scales, so its own Autograd kernel gives dX unchanged
-        with torch.enable_grad():
-            x = input.detach().requires_grad_(input.requires_grad)
-            if hadamard_size:
-                y = flute_amd.qgemm_hadamard(x, weight, scales.detach(), table, table2, workspace, num_bits,
-                                             group_size, hadamard_size, template_id, num_sms)
-            else:
-                y = flute_amd.qgemm(x, weight, scales.detach(), table, table2, workspace, num_bits, group_size,
-                                    template_id, num_sms)
-        ctx.inner = (x, y)
-        ctx.save_for_backward(input, weight, table2)
-        ctx.cfg = (num_bits, group_size, template_id, num_sms, hadamard_size)
-        return y.detach()       # not a differentiable view: the caller may add a bias in place
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        input, weight, table2 = ctx.saved_tensors
-        num_bits, group_size, template_id, num_sms, hadamard_size = ctx.cfg
-        x, y = ctx.inner
-        grad_input = grad_scales = None
-        if ctx.needs_input_grad[0]:
-            (grad_input,) = torch.autograd.grad(y, x, grad_output)
-        if ctx.needs_input_grad[1]:
-            xs = flute_amd.hadamard_transform(input, hadamard_size) if hadamard_size else input
-            grad_scales = flute_amd.qgemm_scale_grad(grad_output, xs, weight, table2, num_bits, group_size,
-                                                     template_id, num_sms)
-        return grad_input, grad_scales, None, None, None, None, None, None, None, None, None
-
-
 def qgemm_learnable_scales(input: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor, table: torch.Tensor,
                            table2: torch.Tensor, workspace: torch.Tensor, num_bits: int, group_size: int,
                            template_id: int, num_sms: int, hadamard_size: int = 0) -> torch.Tensor:
@@ -75,8 +41,8 @@ def qgemm_learnable_scales(input: torch.Tensor, weight: torch.Tensor, scales: to
     `scales`.  Gradients for `table` / `table2` are not available and are refused."""
     if table.requires_grad or table2.requires_grad:
         raise RuntimeError("qgemm_learnable_scales: no gradient for table / table2 (only input and scales train)")
-    return _LearnableScales.apply(input, scales, weight, table, table2, workspace, num_bits, group_size,
-                                  template_id, num_sms, hadamard_size)
+    return _Learnable.apply(input, scales, None, weight, table, table2, workspace, num_bits, group_size, template_id,
+                            num_sms, hadamard_size)
 
 
 _ATTRS = ("in_features", "out_features", "num_bits", "group_size", "template_id", "num_sms", "workspace",
@@ -112,11 +78,7 @@ class LearnableScalesFluteLinear(FluteLinear):
         _share(self, layer, torch.nn.Parameter(layer.scales.detach().clone()))
 
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:
-        if self.workspace_lazy_init:
-            num_sms = flute_amd.utils.get_device_num_sms(inputs.device)
-            workspace = flute_amd.utils.get_workspace_streamk(inputs.device)
-        else:
-            num_sms, workspace = self.num_sms, self.workspace
+        num_sms, workspace = self._launch_resources(inputs.device)
         output = qgemm_learnable_scales(inputs, self.weight, self.scales, self.tables, self.tables2, workspace,
                                         self.num_bits, self.group_size, self.template_id, num_sms)
         if self.bias is not None:
@@ -172,10 +134,15 @@ def _codebook_tables(codebook: torch.Tensor, num_bits: int, dtype: torch.dtype):
 
 
 class _Learnable(torch.autograd.Function):
+    """`flute.qgemm` / `flute.qgemm_hadamard` with gradients to `scales` and to the fp32 master `codebook`; a codebook of
+    None means the caller's `table` / `table2` are used as given (and nothing but input and scales trains)."""
+
     @staticmethod
-    def forward(ctx, input, scales, codebook, weight, workspace, num_bits, group_size, template_id, num_sms,
-                hadamard_size):
-        table, table2 = _codebook_tables(codebook, num_bits, input.dtype)
+    def forward(ctx, input, scales, codebook, weight, table, table2, workspace, num_bits, group_size, template_id,
+                num_sms, hadamard_size):
+        if codebook is not None:
+            table, table2 = _codebook_tables(codebook, num_bits, input.dtype)
+        # the op runs on a detached leaf with detached scales, so its own Autograd kernel gives dX unchanged
         with torch.enable_grad():
             x = input.detach().requires_grad_(input.requires_grad)
             if hadamard_size:
@@ -185,14 +152,14 @@ class _Learnable(torch.autograd.Function):
                 y = flute_amd.qgemm(x, weight, scales.detach(), table, table2, workspace, num_bits, group_size,
                                     template_id, num_sms)
         ctx.inner = (x, y)
-        ctx.save_for_backward(input, scales, weight, table2)
-        ctx.cfg = (num_bits, group_size, template_id, num_sms, hadamard_size, codebook.ndim == 1)
-        return y.detach()
+        ctx.save_for_backward(input, weight, table2, *((scales,) if codebook is not None else ()))   # (scales: dT2 only)
+        ctx.cfg = (num_bits, group_size, template_id, num_sms, hadamard_size, codebook is not None and codebook.ndim == 1)
+        return y.detach()       # not a differentiable view: the caller may add a bias in place
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        input, scales, weight, table2 = ctx.saved_tensors
+        input, weight, table2, *scales = ctx.saved_tensors
         num_bits, group_size, template_id, num_sms, hadamard_size, scalar = ctx.cfg
         x, y = ctx.inner
         grad_input = grad_scales = grad_codebook = None
@@ -202,7 +169,7 @@ class _Learnable(torch.autograd.Function):
         if want_s or want_t:
             xs = flute_amd.hadamard_transform(input, hadamard_size) if hadamard_size else input
             if want_t:
-                out = flute_amd.qgemm_table_grad(grad_output, xs, weight, scales.detach(), num_bits, group_size,
+                out = flute_amd.qgemm_table_grad(grad_output, xs, weight, scales[0].detach(), num_bits, group_size,
                                                  template_id, num_sms, table2=table2, with_scale_grad=want_s)
                 grad_codebook, grad_scales = out if want_s else (out, None)
                 if scalar:
@@ -210,7 +177,7 @@ class _Learnable(torch.autograd.Function):
             else:
                 grad_scales = flute_amd.qgemm_scale_grad(grad_output, xs, weight, table2, num_bits, group_size,
                                                          template_id, num_sms)
-        return grad_input, grad_scales, grad_codebook, None, None, None, None, None, None, None
+        return (grad_input, grad_scales, grad_codebook) + (None,) * 9
 
 
 def qgemm_learnable(input: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor, codebook: torch.Tensor,
@@ -220,8 +187,8 @@ def qgemm_learnable(input: torch.Tensor, weight: torch.Tensor, scales: torch.Ten
     `scales` and `codebook`.  `codebook` is the fp32 master of the lookup table: [2^b] for a scalar table
     (table2 = make_qmap2_from_qmap) or [2^b, 2^b, 2] for a pair codebook.  The forward rounds it to input.dtype and
     runs the unchanged op; the gradient passes straight through that rounding, as it does for the scales."""
-    return _Learnable.apply(input, scales, codebook, weight, workspace, num_bits, group_size, template_id, num_sms,
-                            hadamard_size)
+    return _Learnable.apply(input, scales, codebook, weight, None, None, workspace, num_bits, group_size, template_id,
+                            num_sms, hadamard_size)
 
 
 class LearnableFluteLinear(FluteLinear):
@@ -255,11 +222,7 @@ class LearnableFluteLinear(FluteLinear):
         self.codebook = torch.nn.Parameter(codebook)
 
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:
-        if self.workspace_lazy_init:
-            num_sms = flute_amd.utils.get_device_num_sms(inputs.device)
-            workspace = flute_amd.utils.get_workspace_streamk(inputs.device)
-        else:
-            num_sms, workspace = self.num_sms, self.workspace
+        num_sms, workspace = self._launch_resources(inputs.device)
         if self.table_mode is None:
             output = qgemm_learnable_scales(inputs, self.weight, self.scales, self.tables, self.tables2, workspace,
                                             self.num_bits, self.group_size, self.template_id, num_sms)
@@ -306,36 +269,12 @@ def freeze(module: torch.nn.Module) -> None:
     _swap(module, lambda m: _frozen_learnable(m) if isinstance(m, LearnableFluteLinear) else m)
 
 
-# ---- the experts' scales: the three grouped ops with a gradient to the stacks' scales
+# ---- the experts' scales: the three grouped ops with a gradient to the stacks' scales - the ops' own autograd functions
+# (flute_amd/ops.py), whose scale slot only these entry points open
 
 def _refuse_table_grad(name, *tables):
     if any(t.requires_grad for t in tables):
         raise RuntimeError(f"{name}: no gradient for table2 (only input, row_weight and scales train)")
-
-
-class _GroupedLearnableScales(torch.autograd.Function):
-    """`qgemm_grouped` with dS: the op's launch on detached scales (rows no expert serves zeroed, as the op does under
-    autograd), dX = qgemm_grouped_input_grad(dY), dS = qgemm_grouped_scale_grad(dY, x)."""
-
-    @staticmethod
-    def forward(ctx, input, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms):
-        s = scales.detach()
-        out = _ops._launch_grouped("qgemm_grouped", (input.shape[0],), weight, s.shape[1],
-                                   (input, offsets, weight, s, table2), num_bits, group_size, template_id, num_sms)
-        ctx.save_for_backward(input, offsets, weight, s, table2)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
-        return _ops._zero_unserved_(out, offsets)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        input, offsets, weight, scales, table2 = ctx.saved_tensors
-        d_input = d_scales = None
-        if ctx.needs_input_grad[0]:
-            d_input = flute_amd.qgemm_grouped_input_grad(grad_output, offsets, weight, scales, table2, *ctx.layer)
-        if ctx.needs_input_grad[1]:
-            d_scales = flute_amd.qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer)
-        return (d_input, d_scales) + (None,) * 7
 
 
 def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
@@ -348,35 +287,7 @@ def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, w
     _refuse_table_grad("qgemm_grouped_learnable_scales", table2)
     if not _ops._records_grad(input, scales):
         return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
-    return _GroupedLearnableScales.apply(input, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms)
-
-
-class _GroupedWeightedLearnableScales(torch.autograd.Function):
-    """`qgemm_grouped_weighted` with dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight
-    multiplies dY where the kernel stages it."""
-
-    @staticmethod
-    def forward(ctx, input, row_weight, scales, offsets, weight, table2, num_bits, group_size, template_id, num_sms):
-        s = scales.detach()
-        out = _ops._launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, s.shape[1],
-                                   (input, offsets, weight, s, table2, row_weight), num_bits, group_size, template_id,
-                                   num_sms)
-        ctx.save_for_backward(input, row_weight, offsets, weight, s, table2)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
-        d_input = d_weight = d_scales = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            d_input, d_weight = _ops._grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer,
-                                                                ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        if ctx.needs_input_grad[2]:
-            d_scales = flute_amd.qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer,
-                                                          row_weight=row_weight)
-        return (d_input, d_weight, d_scales) + (None,) * 7
+    return _ops._GroupedFunction.apply(input, scales, offsets, weight, table2, (num_bits, group_size, template_id, num_sms))
 
 
 def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
@@ -390,40 +301,8 @@ def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.
     if not _ops._records_grad(input, row_weight, scales):
         return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
                                                 template_id, num_sms)
-    return _GroupedWeightedLearnableScales.apply(input, row_weight, scales, offsets, weight, table2, num_bits, group_size,
-                                                 template_id, num_sms)
-
-
-class _GroupedGluLearnableScales(torch.autograd.Function):
-    """`qgemm_grouped_glu` with dS_gate = qgemm_grouped_scale_grad(dg, x_sorted) and dS_up = (du, x_sorted): x_sorted, dg
-    and du are the tensors the op's backward forms (`ops._grouped_glu_backward`)."""
-
-    @staticmethod
-    def forward(ctx, input, gs, us, rows, pos, offsets, gw, gt, uw, ut, num_bits, group_size, template_id, num_sms):
-        gs, us = gs.detach(), us.detach()
-        Tsrc = input.shape[0]
-        R = Tsrc if rows is None else rows.shape[0]
-        out = _ops._launch_grouped("qgemm_grouped_glu", (R, Tsrc), gw, gs.shape[1],
-                                   (input, rows, offsets, gw, gs, gt, uw, us, ut), num_bits, group_size, template_id, num_sms)
-        ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
-        ctx.has = (rows is not None, pos is not None)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
-        return _ops._zero_unserved_(out, offsets)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_output):
-        input, offsets, gw, gs, gt, uw, us, ut, *index = ctx.saved_tensors
-        rows = index[0] if ctx.has[0] else None
-        pos = index[1] if ctx.has[1] else None
-        dx, x, dg, du = _ops._grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
-                                                   want_input_grad=ctx.needs_input_grad[0])
-        d_gs = d_us = None
-        if ctx.needs_input_grad[1]:
-            d_gs = flute_amd.qgemm_grouped_scale_grad(dg, x, offsets, gw, gt, *ctx.layer)
-        if ctx.needs_input_grad[2]:
-            d_us = flute_amd.qgemm_grouped_scale_grad(du, x, offsets, uw, ut, *ctx.layer)
-        return (dx, d_gs, d_us) + (None,) * 11
+    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, offsets, weight, table2,
+                                               (num_bits, group_size, template_id, num_sms))
 
 
 def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
@@ -440,5 +319,5 @@ def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tenso
         return flute_amd.qgemm_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
                                            up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
     _ops._validate_grouped_glu_pos(input, rows, pos)
-    return _GroupedGluLearnableScales.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
-                                            up_weight, up_table2, num_bits, group_size, template_id, num_sms)
+    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
+                                          up_weight, up_table2, (num_bits, group_size, template_id, num_sms))

@@ -2,9 +2,13 @@
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
 `qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
 `moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
-routing weights and router logits (not the packed stacks): when grad mode is on and such an input requires grad they run
-through a `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`,
-`moe_combine` and a few torch ops; otherwise they take exactly the path they always took.
+routing weights and router logits: when grad mode is on and such an input requires grad they run through a
+`torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`, `moe_combine`
+and a few torch ops; otherwise they take exactly the path they always took.  Each of the three grouped ops has ONE such
+function, which also carries the gradient of the stacks' scales (`qgemm_grouped_scale_grad`): the ops themselves refuse
+packed stacks that require grad, `integrations.learnable` opens that slot.  Every validator of a packed layer or stack is
+three calls into one set of checks (`_check_ranks`, `_check_dtypes`, `_check_packed`), and every grouped launch -
+forward, input gradient, scale gradient - ends in `_launch_grouped`.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -75,6 +79,11 @@ def _abi_tensor(t):
     return t.clone(memory_format=torch.contiguous_format)
 
 
+def _num_sms(num_sms, device):
+    """`num_sms` as the C ABI takes it: the caller's, or with None the device's CU count."""
+    return torch.cuda.get_device_properties(device).multi_processor_count if num_sms is None else num_sms
+
+
 def hadamard_transform(input: torch.Tensor, hadamard_size: int) -> torch.Tensor:
     """apply_hadamard (qgemm.cpp:201-211): out-of-place FWHT over
     input.reshape(-1, hadamard_size), orthonormal."""
@@ -109,19 +118,60 @@ def _qgemm_raw_simple_hadamard_abstract(input, weight, scales, table, table2, wo
                                       num_bits, group_size, template_id, num_sms)
 
 
-def _validate_dequantize(weight, scales, table2, num_bits, group_size):
-    if not all([weight.ndim == 2, scales.ndim == 2, table2.ndim == 3]):
+# ---- what every validator of a packed layer or stack checks, in three phases that each raise one class: ranks
+# (ValueError), then dtypes (TypeError), then values and shapes (ValueError)
+
+def _check_ranks(*tensor_ndim):
+    """(tensor, ndim) pairs; "at least 2" is (t, max(t.ndim, 2))."""
+    if not all(t.ndim == ndim for t, ndim in tensor_ndim):
         raise ValueError
-    if scales.dtype not in _DTYPE_ID:
+
+
+def _check_dtypes(dtype, like=(), int16=(), fp32=(), int32=()):
+    """`dtype` - the activations' - is fp16 or bf16, the `like` tensors have it and the others their fixed type."""
+    if dtype not in _DTYPE_ID or not all(t.dtype == dtype for t in like):
         raise TypeError
-    if weight.dtype != torch.int16 or table2.dtype != torch.float32:
+    if not all(t.dtype == want for ts, want in ((int16, torch.int16), (fp32, torch.float32), (int32, torch.int32))
+               for t in ts):
         raise TypeError
+
+
+def _pair_table_shape(num_bits, lead=()):
+    return lead + (2 ** num_bits, 2 ** num_bits, 1)
+
+
+def _check_packed(weight, num_bits, group_size, N, K, lead=(), table2=None, offsets=None, n_multiple=16):
+    """The values of a packed layer - or with lead = (E,) a stack of E - of N outputs and K inputs: num_bits and
+    group_size legal, K % max(64, g) == 0, N % n_multiple == 0, `weight` lead + [num_bits N / 16, K], and where given
+    `table2` lead + [2^b, 2^b, 1] and `offsets` of E + 1."""
+    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
+        raise ValueError
+    if not all([
+        K > 0 and K % max(64, group_size) == 0,
+        N > 0 and N % n_multiple == 0,
+        tuple(weight.shape) == lead + (num_bits * (N // 16), K),
+        table2 is None or tuple(table2.shape) == _pair_table_shape(num_bits, lead),
+        offsets is None or offsets.shape[0] == lead[0] + 1,
+    ]):
+        raise ValueError
+
+
+def _check_row_weight(row_weight, R):
+    """`row_weight` [R] fp32."""
+    if row_weight.dtype != torch.float32:
+        raise TypeError
+    if row_weight.ndim != 1 or row_weight.shape[0] != R:
+        raise ValueError
+
+
+def _validate_dequantize(weight, scales, table2, num_bits, group_size):
+    _check_ranks((weight, 2), (scales, 2), (table2, 3))
+    _check_dtypes(scales.dtype, int16=(weight,), fp32=(table2,))
+    # (the reference's relations, flute/ops.py:40-49: which num_bits and group_size are legal is the C ABI's to say)
     if not all([
         weight.shape[1] == scales.shape[1] * group_size,
         weight.shape[0] == int(num_bits * (scales.shape[0] / 16)),
-        table2.shape[0] == 2 ** num_bits,
-        table2.shape[1] == 2 ** num_bits,
-        table2.shape[2] == 1,
+        tuple(table2.shape) == _pair_table_shape(num_bits),
     ]):
         raise ValueError
 
@@ -133,24 +183,10 @@ def _dequantize_abstract(weight, scales, table2, num_bits, group_size, template_
 
 
 def _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_size):
-    if not all([input.ndim >= 2, grad_output.ndim == input.ndim, weight.ndim == 2, table2.ndim == 3]):
-        raise ValueError
-    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype:
-        raise TypeError
-    if weight.dtype != torch.int16 or table2.dtype != torch.float32:
-        raise TypeError
-    K, N = input.shape[-1], grad_output.shape[-1]
-    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
-        raise ValueError
-    if not all([
-        grad_output.shape[:-1] == input.shape[:-1],
-        weight.shape[1] == K,
-        K > 0 and K % max(64, group_size) == 0,
-        N > 0 and N % 16 == 0 and weight.shape[0] == num_bits * (N // 16),
-        table2.shape[0] == 2 ** num_bits,
-        table2.shape[1] == 2 ** num_bits,
-        table2.shape[2] == 1,
-    ]):
+    _check_ranks((input, max(input.ndim, 2)), (grad_output, input.ndim), (weight, 2), (table2, 3))
+    _check_dtypes(input.dtype, like=(grad_output,), int16=(weight,), fp32=(table2,))
+    _check_packed(weight, num_bits, group_size, grad_output.shape[-1], input.shape[-1], table2=table2)
+    if grad_output.shape[:-1] != input.shape[:-1]:
         raise ValueError
 
 
@@ -184,8 +220,7 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     out = torch.empty((N, K // group_size), dtype=input.dtype, device=dev)
     if M == 0:
         return out.zero_()
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    num_sms = _num_sms(num_sms, dev)
     scratch = torch.empty(_scale_grad_scratch_bytes(N, K, group_size, num_sms), dtype=torch.uint8, device=dev)
     w = _abi_tensor(weight)
     t2 = _abi_tensor(table2)
@@ -198,22 +233,11 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
 
 
 def _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, group_size, with_scale_grad):
-    if not all([input.ndim >= 2, grad_output.ndim == input.ndim, weight.ndim == 2, scales.ndim == 2]):
-        raise ValueError
-    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype or scales.dtype != input.dtype:
-        raise TypeError
-    if weight.dtype != torch.int16:
-        raise TypeError
+    _check_ranks((input, max(input.ndim, 2)), (grad_output, input.ndim), (weight, 2), (scales, 2))
+    _check_dtypes(input.dtype, like=(grad_output, scales), int16=(weight,))
     K, N = input.shape[-1], grad_output.shape[-1]
-    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
-        raise ValueError
-    if not all([
-        grad_output.shape[:-1] == input.shape[:-1],
-        weight.shape[1] == K,
-        K > 0 and K % max(64, group_size) == 0,
-        N > 0 and N % 16 == 0 and weight.shape[0] == num_bits * (N // 16),
-        tuple(scales.shape) == (N, K // group_size),
-    ]):
+    _check_packed(weight, num_bits, group_size, N, K)
+    if grad_output.shape[:-1] != input.shape[:-1] or tuple(scales.shape) != (N, K // group_size):
         raise ValueError
     if with_scale_grad and table2 is None:
         raise ValueError("qgemm_table_grad: with_scale_grad needs table2 (the scale gradient reads the table)")
@@ -222,7 +246,7 @@ def _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, g
             raise ValueError
         if table2.dtype != torch.float32:
             raise TypeError
-        if tuple(table2.shape) != (2 ** num_bits, 2 ** num_bits, 1):
+        if tuple(table2.shape) != _pair_table_shape(num_bits):
             raise ValueError
 
 
@@ -254,8 +278,7 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if M == 0:
         dT2.zero_()
         return (dT2, dS.zero_()) if with_scale_grad else dT2
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    num_sms = _num_sms(num_sms, dev)
     lib = _lib.get()
     nbytes = lib.flute_qgemm_table_grad_scratch_bytes(num_bits, group_size, M, N, K, int(with_scale_grad), num_sms)
     if nbytes == 0:
@@ -302,47 +325,52 @@ def _zero_unserved_(out, offsets):
 
 
 def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size):
-    if not all([input.ndim == 2, offsets.ndim == 1, weight.ndim == 3, scales.ndim == 3, table2.ndim == 4]):
-        raise ValueError
-    if input.dtype not in _DTYPE_ID or scales.dtype != input.dtype:
-        raise TypeError
-    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
-        raise TypeError
-    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
-        raise ValueError
-    K = input.shape[1]
-    E, N = scales.shape[0], scales.shape[1]
-    if not all([
-        weight.shape[0] == E,
-        weight.shape[2] == K,
-        K > 0 and K % max(64, group_size) == 0,
-        scales.shape[2] * group_size == K,
-        N > 0 and N % 16 == 0 and weight.shape[1] == num_bits * (N // 16),
-        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
-        offsets.shape[0] == E + 1,
-    ]):
+    _check_ranks((input, 2), (offsets, 1), (weight, 3), (scales, 3), (table2, 4))
+    _check_dtypes(input.dtype, like=(scales,), int16=(weight,), fp32=(table2,), int32=(offsets,))
+    E, N, K = scales.shape[0], scales.shape[1], input.shape[1]
+    _check_packed(weight, num_bits, group_size, N, K, lead=(E,), table2=table2, offsets=offsets)
+    if scales.shape[2] * group_size != K:
         raise ValueError
 
 
-def _launch_grouped(name, rows, weight, N, tensors, num_bits, group_size, template_id, num_sms):
-    """The tail of the three validated grouped ops: flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P,
-    template_id, *pointers, out, num_sms, stream) with `tensors` as the pointers in the ABI's order (input first; None: a
-    null pointer), `rows` the ABI's row counts (the result's first) and `weight` [E, P, K] one of the stacks."""
-    input = tensors[0]
-    dev = input.device
+def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=2 ** 31):
+    """The tail of every validated grouped op: flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P, template_id,
+    *pointers, out, num_sms, stream) with `tensors` as the pointers in the ABI's order (None: a null pointer; the first
+    gives the result's type and device), `rows` the ABI's row counts, each below `row_limit`, `weight` [E, P, K] one of
+    the stacks and `layer` = (num_bits, group_size, template_id, num_sms).  Returns the result, `out_shape`."""
+    num_bits, group_size, template_id, num_sms = layer
+    first = tensors[0]
+    dev = first.device
     if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
         raise RuntimeError(f"flute_amd.{name}: all tensors must live on the same GPU")
-    if max(rows) >= 2 ** 31:
+    if max(rows) >= row_limit:
         raise ValueError
     ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
-    out = torch.empty((rows[0], N), dtype=input.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
+    out = torch.empty(out_shape, dtype=first.dtype, device=dev)
+    num_sms = _num_sms(num_sms, dev)
+    E, P, K = weight.shape
     with torch.cuda.device(dev):
         _lib.check(getattr(_lib.get(), "flute_" + name)(
-            _DTYPE_ID[input.dtype], num_bits, group_size, weight.shape[0], *rows, N, input.shape[1], weight.shape[1],
-            template_id, *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
+            _DTYPE_ID[first.dtype], num_bits, group_size, E, *rows, N, K, P, template_id,
+            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
     return out
+
+
+def _launch_plain(input, offsets, weight, scales, table2, layer):
+    return _launch_grouped("qgemm_grouped", (input, offsets, weight, scales, table2), weight, (input.shape[0],),
+                           scales.shape[1], (input.shape[0], scales.shape[1]), layer)
+
+
+def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer):
+    Tsrc = input.shape[0]
+    R = Tsrc if rows is None else rows.shape[0]
+    return _launch_grouped("qgemm_grouped_glu", (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
+                           gs.shape[1], (R, gs.shape[1]), layer)
+
+
+def _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer):
+    return _launch_grouped("qgemm_grouped_weighted", (input, offsets, weight, scales, table2, row_weight), weight,
+                           (input.shape[0],), scales.shape[1], (input.shape[0], scales.shape[1]), layer)
 
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
@@ -356,28 +384,35 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     synchronise: the call can be captured in a graph and replayed on other row counts of the same T).  A native HIP
     kernel on the current stream (qgemm_grouped.h); the same arguments give the same bits."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
-    return _launch_grouped("qgemm_grouped", (input.shape[0],), weight, scales.shape[1],
-                           (input, offsets, weight, scales, table2), num_bits, group_size, template_id, num_sms)
+        return _GroupedFunction.apply(input, scales, offsets, weight, table2, layer)
+    return _launch_plain(input, offsets, weight, scales, table2, layer)
 
 
 class _GroupedFunction(torch.autograd.Function):
-    """`qgemm_grouped` under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)."""
+    """`qgemm_grouped` under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)
+    and - for `integrations.learnable`; the op itself refuses scales that require grad -
+    dS = qgemm_grouped_scale_grad(dY, x), the only reader of the saved `input`."""
 
     @staticmethod
-    def forward(ctx, input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms):
-        out = _launch_grouped("qgemm_grouped", (input.shape[0],), weight, scales.shape[1],
-                              (input, offsets, weight, scales, table2), num_bits, group_size, template_id, num_sms)
-        ctx.save_for_backward(offsets, weight, scales, table2)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
+    def forward(ctx, input, scales, offsets, weight, table2, layer):
+        out = _launch_plain(input, offsets, weight, scales, table2, layer)
+        ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if ctx.needs_input_grad[1] else ()))
+        ctx.layer = layer
         return _zero_unserved_(out, offsets)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        return (qgemm_grouped_input_grad(grad_output, *ctx.saved_tensors, *ctx.layer),) + (None,) * 8
+        offsets, weight, scales, table2, *saved_input = ctx.saved_tensors
+        d_input = d_scales = None
+        if ctx.needs_input_grad[0]:
+            d_input = qgemm_grouped_input_grad(grad_output, offsets, weight, scales, table2, *ctx.layer)
+        if ctx.needs_input_grad[1]:
+            d_scales = qgemm_grouped_scale_grad(grad_output, saved_input[0], offsets, weight, table2, *ctx.layer)
+        return (d_input, d_scales) + (None,) * 4
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -418,32 +453,28 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
-    Tsrc = input.shape[0]
-    R = Tsrc if rows is None else rows.shape[0]
     _validate_grouped_glu_pos(input, rows, pos)
+    layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
-        return _GroupedGluFunction.apply(input, rows, pos, offsets, gate_weight, gate_scales, gate_table2, up_weight,
-                                         up_scales, up_table2, num_bits, group_size, template_id, num_sms)
-    return _launch_grouped("qgemm_grouped_glu", (R, Tsrc), gate_weight, gate_scales.shape[1],
-                           (input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2),
-                           num_bits, group_size, template_id, num_sms)
+        return _GroupedGluFunction.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
+                                         up_weight, up_table2, layer)
+    return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer)
 
 
 class _GroupedGluFunction(torch.autograd.Function):
     """`qgemm_grouped_glu` under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
     g and u with two plain grouped launches on the gathered rows, forms dg = dh u sigma(g) (1 + g (1 - sigma(g))) and
-    du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel."""
+    du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel.  For
+    `integrations.learnable` (the op itself refuses scales that require grad) dS_gate = qgemm_grouped_scale_grad(dg,
+    x_sorted) and dS_up = (du, x_sorted), one launch per stack on the tensors the backward has formed."""
 
     @staticmethod
-    def forward(ctx, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, num_bits, group_size, template_id, num_sms):
-        Tsrc = input.shape[0]
-        R = Tsrc if rows is None else rows.shape[0]
-        out = _launch_grouped("qgemm_grouped_glu", (R, Tsrc), gw, gs.shape[1],
-                              (input, rows, offsets, gw, gs, gt, uw, us, ut), num_bits, group_size, template_id, num_sms)
+    def forward(ctx, input, gs, us, rows, pos, offsets, gw, gt, uw, ut, layer):
+        out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer)
         ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
         ctx.has = (rows is not None, pos is not None)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
+        ctx.layer = layer
         return _zero_unserved_(out, offsets)
 
     @staticmethod
@@ -452,19 +483,25 @@ class _GroupedGluFunction(torch.autograd.Function):
         input, offsets, gw, gs, gt, uw, us, ut, *index = ctx.saved_tensors
         rows = index[0] if ctx.has[0] else None
         pos = index[1] if ctx.has[1] else None
-        dx, _, _, _ = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer)
-        return (dx,) + (None,) * 13
+        dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
+                                              want_input_grad=ctx.needs_input_grad[0])
+        d_gs = d_us = None
+        if ctx.needs_input_grad[1]:
+            d_gs = qgemm_grouped_scale_grad(dg, x, offsets, gw, gt, *ctx.layer)
+        if ctx.needs_input_grad[2]:
+            d_us = qgemm_grouped_scale_grad(du, x, offsets, uw, ut, *ctx.layer)
+        return (dx, d_gs, d_us) + (None,) * 8
 
 
-def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad=True):
-    """The backward of the fused GLU launch, shared with `integrations.learnable`: (d input, x_sorted, dg, du) - the
-    gathered rows and the two gradients in T that the pair-form launch reads, which the scale gradients read too.
-    `want_input_grad` false skips the pair-form launch and the sum over a token's slots (d input: None)."""
+def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad):
+    """The backward of the fused GLU launch: (d input, x_sorted, dg, du) - the gathered rows and the two gradients in T
+    that the pair-form launch reads, which the scale gradients read too.  `want_input_grad` false skips the pair-form
+    launch and the sum over a token's slots (d input: None)."""
     Tsrc = input.shape[0]
     x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
-    launch = lambda w, sc, t2: _launch_grouped("qgemm_grouped", (x.shape[0],), w, sc.shape[1], (x, offsets, w, sc, t2),
-                                               *layer)
-    g, u, dh = launch(gw, gs, gt).float(), launch(uw, us, ut).float(), grad_output.float()
+    g = _launch_plain(x, offsets, gw, gs, gt, layer).float()
+    u = _launch_plain(x, offsets, uw, us, ut, layer).float()
+    dh = grad_output.float()
     sig = torch.sigmoid(g)
     dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
     du = (dh * (g * sig)).to(input.dtype)
@@ -481,10 +518,7 @@ def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw
 
 def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size):
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
-    if row_weight.dtype != torch.float32:
-        raise TypeError
-    if row_weight.ndim != 1 or row_weight.shape[0] != input.shape[0]:
-        raise ValueError
+    _check_row_weight(row_weight, input.shape[0])
 
 
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
@@ -495,37 +529,44 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
     HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
-        return _GroupedWeightedFunction.apply(input, row_weight, offsets, weight, scales, table2, num_bits, group_size,
-                                              template_id, num_sms)
-    return _launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, scales.shape[1],
-                           (input, offsets, weight, scales, table2, row_weight), num_bits, group_size, template_id, num_sms)
+        return _GroupedWeightedFunction.apply(input, row_weight, scales, offsets, weight, table2, layer)
+    return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
 
 
 class _GroupedWeightedFunction(torch.autograd.Function):
     """`qgemm_grouped_weighted` under autograd.  A row weight that needs no gradient rides in the input-gradient kernel's
     epilogue (one launch); one that does takes dH' = input_grad(dY), d row_weight[r] = sum_k dH'[r, k] h[r, k] in fp32
-    (zero from offsets[E] on) and dH = round_T(row_weight dH')."""
+    (zero from offsets[E] on) and dH = round_T(row_weight dH').  For `integrations.learnable` (the op itself refuses
+    scales that require grad) dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight multiplies
+    dY where the kernel stages it."""
 
     @staticmethod
-    def forward(ctx, input, row_weight, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms):
-        out = _launch_grouped("qgemm_grouped_weighted", (input.shape[0],), weight, scales.shape[1],
-                              (input, offsets, weight, scales, table2, row_weight), num_bits, group_size, template_id, num_sms)
+    def forward(ctx, input, row_weight, scales, offsets, weight, table2, layer):
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
-        ctx.layer = (num_bits, group_size, template_id, num_sms)
-        return out
+        ctx.layer = layer
+        return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        return _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, ctx.needs_input_grad[0],
-                                          ctx.needs_input_grad[1]) + (None,) * 8
+        input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
+        want_input, want_weight, want_scales = ctx.needs_input_grad[:3]
+        d_input = d_weight = d_scales = None
+        if want_input or want_weight:
+            d_input, d_weight = _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, want_input,
+                                                           want_weight)
+        if want_scales:
+            d_scales = qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer,
+                                                row_weight=row_weight)
+        return (d_input, d_weight, d_scales) + (None,) * 4
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
                                want_weight):
-    """(d input, d row_weight) of the weighted launch, shared with `integrations.learnable`."""
+    """(d input, d row_weight) of the weighted launch."""
     stack = (offsets, weight, scales, table2)
     if not want_weight:
         return qgemm_grouped_input_grad(grad_output, *stack, *layer, row_weight=row_weight), None
@@ -540,24 +581,11 @@ def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, 
 
 def _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
                                  grad_output2, weight2, scales2, table22):
-    if not all([grad_output.ndim == 2, offsets.ndim == 1, weight.ndim == 3, scales.ndim == 3, table2.ndim == 4]):
-        raise ValueError
-    if grad_output.dtype not in _DTYPE_ID or scales.dtype != grad_output.dtype:
-        raise TypeError
-    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
-        raise TypeError
-    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
-        raise ValueError
+    _check_ranks((grad_output, 2), (offsets, 1), (weight, 3), (scales, 3), (table2, 4))
+    _check_dtypes(grad_output.dtype, like=(scales,), int16=(weight,), fp32=(table2,), int32=(offsets,))
     E, N, K = scales.shape[0], scales.shape[1], weight.shape[2]
-    if not all([
-        grad_output.shape[1] == N,
-        weight.shape[0] == E,
-        K > 0 and K % max(64, group_size) == 0,
-        scales.shape[2] * group_size == K,
-        N > 0 and N % 16 == 0 and weight.shape[1] == num_bits * (N // 16),
-        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
-        offsets.shape[0] == E + 1,
-    ]):
+    _check_packed(weight, num_bits, group_size, N, K, lead=(E,), table2=table2, offsets=offsets)
+    if grad_output.shape[1] != N or scales.shape[2] * group_size != K:
         raise ValueError
     second = (grad_output2, weight2, scales2, table22)
     if any(t is not None for t in second):
@@ -568,14 +596,10 @@ def _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, n
         if grad_output2.dtype != grad_output.dtype or scales2.dtype != scales.dtype or weight2.dtype != torch.int16 or \
                 table22.dtype != torch.float32:
             raise TypeError
-        if not all([tuple(grad_output2.shape) == tuple(grad_output.shape), tuple(weight2.shape) == tuple(weight.shape),
-                    tuple(scales2.shape) == tuple(scales.shape), tuple(table22.shape) == tuple(table2.shape)]):
+        if not all(tuple(t2.shape) == tuple(t.shape) for t2, t in zip(second, (grad_output, weight, scales, table2))):
             raise ValueError
     if row_weight is not None:
-        if row_weight.dtype != torch.float32:
-            raise TypeError
-        if row_weight.ndim != 1 or row_weight.shape[0] != grad_output.shape[0]:
-            raise ValueError
+        _check_row_weight(row_weight, grad_output.shape[0])
 
 
 def _grouped_input_grad_row_block():
@@ -604,48 +628,20 @@ def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, w
     tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
     if _records_grad(*tensors):
         raise RuntimeError("flute_amd.qgemm_grouped_input_grad: the backward is once-differentiable (no double backward)")
-    dev = grad_output.device
-    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
-        raise RuntimeError("flute_amd.qgemm_grouped_input_grad: all tensors must live on the same GPU")
     R, N = grad_output.shape
-    E, P, K = weight.shape
-    if R >= 2 ** 31:
-        raise ValueError
-    ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
-    out = torch.empty((R, K), dtype=grad_output.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_grouped_input_grad(
-            _DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P, template_id,
-            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
-    return out
+    return _launch_grouped("qgemm_grouped_input_grad", tensors, weight, (R,), N, (R, weight.shape[2]),
+                           (num_bits, group_size, template_id, num_sms))
 
 
 def _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight):
-    if not all([grad_output.ndim == 2, input.ndim == 2, offsets.ndim == 1, weight.ndim == 3, table2.ndim == 4]):
-        raise ValueError
-    if input.dtype not in _DTYPE_ID or grad_output.dtype != input.dtype:
-        raise TypeError
-    if weight.dtype != torch.int16 or table2.dtype != torch.float32 or offsets.dtype != torch.int32:
-        raise TypeError
-    if num_bits not in (2, 3, 4) or group_size not in (32, 64, 128, 256):
-        raise ValueError
-    E, K, N = weight.shape[0], input.shape[1], grad_output.shape[1]
-    if not all([
-        grad_output.shape[0] == input.shape[0],
-        weight.shape[2] == K,
-        K > 0 and K % max(64, group_size) == 0,
-        N > 0 and N % 128 == 0 and weight.shape[1] == num_bits * (N // 16),
-        tuple(table2.shape) == (E, 2 ** num_bits, 2 ** num_bits, 1),
-        offsets.shape[0] == E + 1,
-    ]):
+    _check_ranks((grad_output, 2), (input, 2), (offsets, 1), (weight, 3), (table2, 4))
+    _check_dtypes(input.dtype, like=(grad_output,), int16=(weight,), fp32=(table2,), int32=(offsets,))
+    _check_packed(weight, num_bits, group_size, grad_output.shape[1], input.shape[1], lead=(weight.shape[0],),
+                  table2=table2, offsets=offsets, n_multiple=128)
+    if grad_output.shape[0] != input.shape[0]:
         raise ValueError
     if row_weight is not None:
-        if row_weight.dtype != torch.float32:
-            raise TypeError
-        if row_weight.ndim != 1 or row_weight.shape[0] != input.shape[0]:
-            raise ValueError
+        _check_row_weight(row_weight, input.shape[0])
 
 
 def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
@@ -667,23 +663,10 @@ def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     tensors = (grad_output, input, offsets, weight, table2, row_weight)
     if _records_grad(*tensors):
         raise RuntimeError("flute_amd.qgemm_grouped_scale_grad: the backward is once-differentiable (no double backward)")
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
-        raise RuntimeError("flute_amd.qgemm_grouped_scale_grad: all tensors must live on the same GPU")
     R, K = input.shape
-    N = grad_output.shape[1]
-    E, P = weight.shape[0], weight.shape[1]
-    if R >= 2 ** 31 - 64:
-        raise ValueError
-    ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
-    out = torch.empty((E, N, K // group_size), dtype=input.dtype, device=dev)
-    if num_sms is None:
-        num_sms = torch.cuda.get_device_properties(dev).multi_processor_count
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_grouped_scale_grad(
-            _DTYPE_ID[input.dtype], num_bits, group_size, E, R, N, K, P, template_id,
-            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
-    return out
+    E, N = weight.shape[0], grad_output.shape[1]
+    return _launch_grouped("qgemm_grouped_scale_grad", tensors, weight, (R,), N, (E, N, K // group_size),
+                           (num_bits, group_size, template_id, num_sms), row_limit=2 ** 31 - 64)
 
 
 _INDEX_DTYPE_ID = {torch.int32: 0, torch.int64: 1}

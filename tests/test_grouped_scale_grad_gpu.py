@@ -448,6 +448,94 @@ def test_autograd_grouped_glu_learnable_scales(env, op_case, native):
 
 
 # ---------------------------------------------------------------------------
+# one autograd function per grouped op, shared by the op and its learnable entry
+# ---------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def tiny(env):
+    """The smallest legal stacks (4 bits, TileP 32, g = 64, K = 64, N = 128; gate and up) over five rows of three
+    experts, the middle one empty: offsets [0, 3, 3, 5], from moe_route at top-1."""
+    d, dtype, bits, tile_p, g, K, N, E = env.dev, F16, 4, 32, 64, 64, 128, 3
+    gen = torch.Generator().manual_seed(4100)
+
+    def stack(seed):
+        parts = [random_layer(env, bits, tile_p, dtype, K, N, seed + e, pair=(e == 1)) for e in range(E)]
+        S = (torch.randn(E, N, K // g, generator=gen) / 8).to(dtype).to(d)
+        return torch.stack([p[0] for p in parts]), S, torch.stack([p[1] for p in parts])
+
+    ids = torch.tensor([[2], [0], [0], [2], [0]], dtype=torch.int32, device=d)
+    offsets, rows, _, pos, _ = env.fa.moe_route(ids, None, E)
+    assert offsets.tolist() == [0, 3, 3, 5]
+    tokens = (torch.randn(5, K, generator=gen) / 4).to(dtype).to(d)
+    return dict(gate=stack(4110), up=stack(4120), off=offsets, rows=rows, pos=pos, tokens=tokens,
+                x_sorted=tokens.index_select(0, rows.long()), rw=(torch.rand(5, generator=gen) + 0.5).to(d),
+                dY=torch.randn(5, N, generator=gen).to(dtype).to(d),
+                args=(bits, g, first_template(env.fa, bits, tile_p), env.num_sms))
+
+
+def through_autograd(env, c, form, learnable, scales_grad):
+    """One forward and backward of a grouped op (`learnable`: through its *_learnable_scales entry) with the input - and the
+    row weight - requiring grad: (out, dX, d row_weight or None, [dS_gate, dS_up] or None, whether the graph saved the input)."""
+    (Qg, Sg, tg), (Qu, Su, tu) = c["gate"], c["up"]
+    if scales_grad:
+        Sg, Su = torch.nn.Parameter(Sg.clone()), torch.nn.Parameter(Su.clone())
+    op = lambda name: getattr(env.ln, name + "_learnable_scales") if learnable else getattr(env.fa, name)
+    rw = None
+    if form == "plain":
+        x = c["x_sorted"].clone().requires_grad_()
+        y = op("qgemm_grouped")(x, c["off"], Qg, Sg, tg, *c["args"])
+    elif form == "weighted":
+        x, rw = c["x_sorted"].clone().requires_grad_(), c["rw"].clone().requires_grad_()
+        y = op("qgemm_grouped_weighted")(x, c["off"], Qg, Sg, tg, rw, *c["args"])
+    else:
+        rows, pos = c["rows"] if "rows" in form else None, c["pos"] if "pos" in form else None
+        x = (c["x_sorted"] if rows is None else c["tokens"]).clone().requires_grad_()
+        y = op("qgemm_grouped_glu")(x, c["off"], Qg, Sg, tg, Qu, Su, tu, *c["args"], rows=rows, pos=pos)
+    saves_input = any(t.data_ptr() == x.data_ptr() for t in y.grad_fn.saved_tensors)
+    y.backward(c["dY"])
+    return y.detach(), x.grad, None if rw is None else rw.grad, [Sg.grad, Su.grad] if scales_grad else None, saves_input
+
+
+@pytest.mark.parametrize("form", ["plain", "weighted", "glu", "glu_rows", "glu_rows_pos"])
+def test_op_and_learnable_entry_are_one_function(env, tiny, form):
+    """The op and its learnable entry run one autograd function: equal bits for the output, dX and d row_weight whether or
+    not the scales train, dS the direct scale-gradient call on the tensors the backward forms, and `input` saved only for dS."""
+    c, fa = tiny, env.fa
+    (Qg, Sg, tg), (Qu, Su, tu) = c["gate"], c["up"]
+    y0, dx0, drw0, _, saves_input = through_autograd(env, c, form, learnable=False, scales_grad=False)
+    assert torch.isfinite(dx0).all() and float(dx0.abs().max()) > 0 and float(y0.abs().max()) > 0
+    assert (drw0 is not None) == (form == "weighted")
+    for scales_grad in (False, True):
+        y, dx, drw, dS, _ = through_autograd(env, c, form, learnable=True, scales_grad=scales_grad)
+        assert torch.equal(bits16(y), bits16(y0)) and torch.equal(bits16(dx), bits16(dx0))
+        if form == "weighted":
+            assert torch.equal(drw.view(torch.int32), drw0.view(torch.int32)) and float(drw0.abs().max()) > 0
+        else:
+            assert drw is None
+    x, dY = c["x_sorted"], c["dY"]
+    if form == "plain":
+        want = [fa.qgemm_grouped_scale_grad(dY, x, c["off"], Qg, tg, *c["args"]), None]
+        assert not saves_input                                       # only the input requires grad: dS alone reads it
+    elif form == "weighted":
+        want = [fa.qgemm_grouped_scale_grad(dY, x, c["off"], Qg, tg, *c["args"], row_weight=c["rw"]), None]
+    else:
+        g = fa.qgemm_grouped(x, c["off"], Qg, Sg, tg, *c["args"]).float()
+        u = fa.qgemm_grouped(x, c["off"], Qu, Su, tu, *c["args"]).float()
+        sig = torch.sigmoid(g)
+        dg = (dY.float() * u * sig * (1 + g * (1 - sig))).to(x.dtype)
+        du = (dY.float() * (g * sig)).to(x.dtype)
+        want = [fa.qgemm_grouped_scale_grad(dg, x, c["off"], Qg, tg, *c["args"]),
+                fa.qgemm_grouped_scale_grad(du, x, c["off"], Qu, tu, *c["args"])]
+    for got, w in zip(dS, want):
+        if w is None:
+            assert got is None                                       # (the up stack plays no part in this form)
+        else:
+            assert got.shape == Sg.shape and torch.equal(bits16(got), bits16(w))
+            assert torch.isfinite(w).all() and float(w[0].abs().max()) > 0 and float(w[2].abs().max()) > 0
+            assert not w[1].any()                                    # the empty expert: zeros
+
+
+# ---------------------------------------------------------------------------
 # module level
 # ---------------------------------------------------------------------------
 
