@@ -237,7 +237,8 @@ int flute_unpack(int num_bits, int template_id, int N, int K, const void* Q, voi
  * [k_begin, k_begin + k_count) of K: W[n, k - k_begin] = round_T(QM2-pair-lookup(Q)[k, n] * S[n, k / group_size]),
  * the lookup and the one rounding of the qgemm kernels, so W equals qgemm(identity) element by element.  QM is not
  * read (HIGGS pair codebooks dequantize as they multiply).  k_begin and k_count are multiples of 64 and group_size
- * divides K; k_count == 0 is a no-op.  Same layer checks as flute_qgemm; FLUTE_ERR_SHAPE also for a bad k range or
+ * divides K; k_count == 0 is a no-op.  The product is rounded as IEEE rounds it: an fp16 subnormal lut * s is kept (no
+ * flush) and a product beyond the largest finite T is +-inf, not 65504 (tests/test_grad_edges_gpu.py).  Same layer checks as flute_qgemm; FLUTE_ERR_SHAPE also for a bad k range or
  * P != num_bits * N / 16.  Null pointers are refused (FLUTE_ERR_NULL) before anything else. */
 int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int P, int k_begin, int k_count,
                      const void* Q, const void* S, const void* QM2, void* W, int template_id, void* stream);
@@ -245,7 +246,11 @@ int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int 
 /* The gradient of a layer's scales, dS[n, j] = round_T(sum_{m < M} sum_{j*g <= k < (j+1)*g} dY[m, n] * X[m, k] * L[k, n]),
  * L[k, n] the value the qgemm kernels multiply by the scale (the QM2 pair lookup of Q, as flute_dequantize; QM is not
  * read).  dY [M, N] and X [M, K] row-major T, dS [N, K / group_size] T: fp32 products and sums, one rounding to T.  X is
- * the activation the weight multiplies (for a Hadamard layer the rotated input).  M >= 1; group_size in {32, 64, 128,
+ * the activation the weight multiplies (for a Hadamard layer the rotated input).  Non-finite inputs propagate by IEEE
+ * rules to exactly the outputs the formula connects them to: a NaN or Inf at X[m, k] reaches dS[:, k / group_size] only, one
+ * at dY[m, n] reaches dS[n, :] only (Inf: +-inf by the signs of the factors it meets, NaN where one is zero or both signs
+ * meet), split or unsplit; rows past M are not loaded, never multiplied by zero.  Subnormal dY and X are multiplied as
+ * they are and dS rounds to +-inf, not to 65504 (tests/test_grad_edges_gpu.py).  M >= 1; group_size in {32, 64, 128,
  * 256}; same layer checks as flute_dequantize, in its order (FLUTE_ERR_NULL for a null dY / X / Q / QM2 / dS first).
  * `scratch` (scratch_bytes, may be null / 0) lets small layers split M across workgroups: fp32 partials
  * [splits][N][K / group_size] summed in split order by a second launch.  The number of splits follows from M, N, K,
@@ -264,6 +269,9 @@ int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N
  * what flute_qgemm_scale_grad returns for the same layer and M given its full scratch (what
  * flute_amd.qgemm_scale_grad passes); QM2 is needed then and only then.  fp32 products and sums inside a workgroup, fp64
  * across workgroups, one rounding to fp32; no atomics on global memory: equal arguments give equal bits.
+ * Non-finite inputs propagate by IEEE rules to exactly the bins the formula connects them to: a NaN or Inf at X[m, k]
+ * reaches the bins (c, e = k & 1) whose pair index occurs at pair row k >> 1, one at dY[m, n] the bins of column n's pairs;
+ * every other bin keeps its bits.  dS follows flute_qgemm_scale_grad's rule and rounds to +-inf, not to 65504.
  * Refusals in flute_qgemm_scale_grad's order: FLUTE_ERR_NULL first (dY / X / Q / S / dT2 / scratch, QM2 with a dS),
  * then dtype, the layer checks, P and M.  `scratch` must hold flute_qgemm_table_grad_scratch_bytes(...) bytes for the
  * same num_bits, group_size, M, N, K, num_sms and want_dS = (dS != NULL): less is FLUTE_ERR_WORKSPACE (more changes
@@ -283,6 +291,10 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
  * Arithmetic as flute_dequantize and the MFMA kernels: w^ = round_T(QM2-pair-lookup * scale), fp32 accumulation in the
  * matrix core, one rounding of the output.  K is split among the waves of one workgroup only and combined through LDS
  * in a fixed order (no atomics, no split across workgroups): equal arguments give equal bits.
+ * Non-finite inputs propagate by IEEE rules to exactly the outputs the formula connects them to: a NaN or Inf in row r of X
+ * reaches row r of Y only (Inf: +-inf by the sign of the weight it meets, NaN at a zero weight), whichever expert's rows
+ * share its 16-row tile - rows outside an expert's range are not loaded, never multiplied by zero.  fp16 subnormal
+ * weights and activations are multiplied as they are, and Y rounds to +-inf, not to 65504 (tests/test_grouped_edges_gpu.py).
  * The host never reads `offsets`: the grid follows from (E, N, num_bits, num_sms) alone, so
  * the launch can be captured in a hipGraph and a replay serves whatever the table then holds.  A workgroup whose expert
  * has no rows requests nothing.  Every row index is clamped to [0, T]: a malformed table cannot read or write outside
@@ -307,6 +319,11 @@ int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, i
  *   scaled by t / (1 + t) < 1, so silu32 is within 2^-23 + 2 * 2^-24 = 2^-22 (to first order) of g / (1 + e^-g) for
  *   every |g| <= 88 (e^88 is finite in fp32; e^-88 vanishes against the 1); with the fp32 product by u (2^-24):
  *   eps_s = 2^-21 bounds the relative error of silu32(g) * u before the store, well below the rounding to T.
+ *   Outside that range the form saturates as written: for g >= 18 the sum 1 + exp(-g) is 1 in fp32 and silu32(g) = g
+ *   exactly; for g <= -90 exp(-g) is +inf and silu32(g) = -0; neither branch yields a NaN (g e^g / (1 + e^g) would).
+ *   Non-finite inputs propagate by IEEE rules to exactly the rows the formula connects them to - every sorted row whose
+ *   source row holds the NaN or Inf, in whichever expert: g = +inf gives +inf times u, g = -inf gives -inf / inf = NaN.
+ *   H rounds to +-inf, not to 65504.
  * Xsrc [Tsrc, K] T; rows [R] int32 in DEVICE memory or null.  Null: row r of Xsrc is r, and Tsrc must equal R.  Otherwise
  * each entry is clamped to [0, Tsrc) before it forms an address (Tsrc >= 1 then), and the activation load is the only use
  * of it: no gathered copy of Xsrc is needed.  offsets [E + 1] as flute_qgemm_grouped, clamped to [0, R].  Gate and up are
@@ -326,6 +343,8 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
 /* flute_qgemm_grouped with a per-row weight in the epilogue, for the down projection of a mixture-of-experts MLP:
  *   Y[r, :] = round_T( row_weight[r] * acc32 ),   acc32 = the fp32 sum of X[r, :] @ W_e^T,
  * for every row r in [offsets[e], offsets[e + 1]): the product in fp32, ONE rounding.  row_weight [T] fp32 in device memory.
+ * Non-finite inputs propagate as in flute_qgemm_grouped, through the fp32 product: a row weight of 0 on a row holding an
+ * Inf gives NaN (0 x inf), on a finite row zeros.  Y rounds to +-inf, not to 65504, also where only the weight takes it there.
  * The rows [clamp(offsets[E]), T) - rows no expert serves - are written as zeros by the same launch, whichever experts
  * have rows (none included); rows >= T are never touched.  Everything else - operands, arithmetic of w^, determinism, the
  * grid, clamping, the refusals and their order, E == 0 or T == 0, num_sms - is flute_qgemm_grouped's; row_weight is one
@@ -345,6 +364,10 @@ int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E,
  *   dX[r, :] = round_T( sum_n dY[r, n] * w^(1)_e[n, :] + sum_n dY2[r, n] * w^(2)_e[n, :] ),
  * both sums added in fp32 (one accumulator: the first stack's columns, then the second's) before the one rounding - the
  * gradient of a row that fed both the gate and the up projection of flute_qgemm_grouped_glu.  It takes no row_weight.
+ * Two halves that would each overflow T alone and cancel give 0, not inf - inf: nothing is rounded before the sum is whole.
+ * Non-finite inputs propagate by IEEE rules to exactly the outputs the formula connects them to: a NaN or Inf in row r of
+ * dY (or dY2) reaches row r of dX only (Inf: +-inf by the sign of w^[n, :], NaN at a zero weight or a zero row weight).
+ * fp16 subnormal weights and dY are multiplied as they are, and dX rounds to +-inf, not to 65504 (tests/test_grouped_edges_gpu.py).
  * The rows [clamp(offsets[E]), R) - rows no expert serves - are written as zeros by the same launch whatever the routing:
  * every element of dX is written whenever offsets is a proper table (0 first, non-decreasing, at most R).  Every row
  * index formed is clamped to [0, R]: a malformed table is memory-safe and leaves only the rows it names twice or skips
@@ -375,7 +398,9 @@ int flute_qgemm_grouped_input_grad_row_block(void);
  * dYw[r, n] = round_T(row_weight[r] * dY[r, n]) otherwise - the product in fp32, one round-to-nearest-even to T, formed where
  * the dY tile is staged - which is the gradient that reaches flute_qgemm_grouped_weighted's product.  Products and sums in
  * fp32 in flute_qgemm_scale_grad's order, one rounding of the result: wherever that launch does not split M (always without
- * scratch) an expert's dS has its bits.
+ * scratch) an expert's dS has its bits.  Non-finite inputs propagate by IEEE rules to exactly the outputs the formula connects
+ * them to - flute_qgemm_scale_grad's rule inside the expert that owns the row, and no other expert's dS: rows outside an
+ * expert's range are not loaded, never multiplied by zero.  dYw and dS round to +-inf, not to 65504, and a subnormal dYw is kept.
  * dY [R, N] and X [R, K] row-major T, rows sorted by expert; offsets [E + 1] int32 in DEVICE memory; Q [E, P, K] int16;
  * QM2 [E, 2^b, 2^b] fp32 words; row_weight [R] fp32 in device memory or null; dS [E, N, K / group_size] T.
  * The host never reads offsets: the grid is (N / 128, ceil(K / 256), E), from the shapes alone (num_sms is accepted for
@@ -513,7 +538,9 @@ int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_gro
  *   served = clamp(offsets[E], 0, P)
  *   acc = +0.0f;  for j = 0 .. k - 1, ascending:  p = pos[t, j];  if (0 <= p < served) acc += (float) Y[p, n]
  *   out[t, n] = round_T(acc)
- * fp32 additions in slot order, ONE rounding.  Every element of out is written - a token with no served slot is zeros -
+ * fp32 additions in slot order, ONE rounding (to +-inf, not to 65504).  Non-finite inputs propagate by IEEE rules to
+ * exactly the outputs the formula connects them to: a NaN in a served row reaches its token's row in that column, +inf
+ * and -inf in two slots of one token give NaN there.  Every element of out is written - a token with no served slot is zeros -
  * so out needs no zero fill.  Rows of Y at or past `served` and positions outside [0, P) are never read: the result does
  * not depend on what the rows no expert served hold.  No atomics: equal arguments give equal bits for every k.  Of
  * offsets [E + 1] int32 only offsets[E] is read, on the device; the host reads neither it nor pos, and the grid follows

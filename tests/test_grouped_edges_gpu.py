@@ -1,0 +1,245 @@
+"""The grouped forward (Plain, Weighted, Glu) and the grouped input gradient (single, pair, row-weighted) on hostile
+operands (tests/op_edge_cases.py): fp16-subnormal weights, a subnormal row operand, results that overflow fp16 in both
+directions, the GLU outside |g| <= 88, and one NaN and one +Inf on the two sides of a seam between two experts.
+
+Range edges have one allowed answer, round_T of the fp64 result by value, infinities included.  Non-finite launches follow
+by rule from the bits of the same launch on the unpoisoned operands: the NaN row is NaN, the Inf row is +-inf by the sign
+of the weight it meets, every other row - the neighbour across the seam, in the same 16-row tile, included - is untouched.
+These kernels mask out-of-range rows by not loading them; a mask by multiplication would leak exactly here.
+
+Every launch goes through the C ABI with the output and every row operand (X / dY / dY2 / row_weight / rows / offsets) in
+the middle of poisoned buffers: afterwards the guards are intact, the inputs unmodified and (clean launches) no canary is
+left in the rows the op promises to write."""
+import pytest
+import torch
+
+from tests import exact_cases as XC
+from tests import op_edge_cases as OE
+from tests import test_exact_gpu as G
+from tests.test_grouped_glu_gpu import assert_glu
+from tests.test_grouped_gpu import stack_exact
+
+pytestmark = pytest.mark.gpu
+
+F16, BF16 = torch.float16, torch.bfloat16
+GUARD = G.GUARD
+FILL32 = {torch.int32: 0x5A5A5A5A, torch.float32: 0x7FC00000}      # around offsets / rows: a huge index; around row_weight: NaN
+
+
+@pytest.fixture(scope="module")
+def env():
+    import flute_amd
+    from flute_amd import _lib, utils
+
+    class Env:
+        pass
+
+    e = Env()
+    e.fa, e.lib, e.utils = flute_amd, _lib.get(), utils
+    e.dev = torch.device("cuda:0")
+    e.num_sms = utils.get_device_num_sms(e.dev)
+    e.ws = utils.get_workspace_streamk(e.dev)
+    e.stacks = {}
+    assert flute_amd.ops.GROUPED_INPUT_GRAD_ROW_BLOCK == OE.ROW_BLOCK
+    return e
+
+
+def carve(env, t, T):
+    """A row operand in the middle of a poisoned buffer: NaN of T around floating data, a huge index around int32."""
+    fill = FILL32[t.dtype] if t.element_size() == 4 else XC.NAN_BITS[T]
+    return G.Carved(t, env.dev, fill)
+
+
+class Out:
+    """An output of `shape` in the middle of a canary-filled buffer (NaN bits of its type)."""
+
+    def __init__(self, env, shape, dtype):
+        n = 1
+        for s in shape:
+            n *= s
+        wide = dtype == torch.float32
+        self.fill = FILL32[torch.float32] if wide else XC.NAN_BITS[dtype]
+        self.buf = torch.full((GUARD + n + GUARD,), self.fill, dtype=torch.int32 if wide else torch.int16, device=env.dev)
+        self.mid = self.buf[GUARD:GUARD + n]
+        self.t = self.mid.view(dtype).view(shape)
+        assert self.t.data_ptr() % 16 == 0
+
+    def intact(self):
+        return bool(torch.all(self.buf[:GUARD] == self.fill) and torch.all(self.buf[GUARD + self.mid.numel():] == self.fill))
+
+    def canaries(self):
+        return int((self.mid == self.fill).sum())
+
+
+def guarded(env, fn, args, carved, outs, nan_expected=False):
+    """fn(*args) with the checks every launch gets.  carved: the Carved row operands; outs: the Out buffers."""
+    before = [G._bits(c.t) for c in carved]
+    with torch.cuda.device(env.dev):
+        rc = fn(*args)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert all(o.intact() for o in outs), "write outside the output"
+    assert all(torch.equal(b, G._bits(c.t)) for b, c in zip(before, carved)), "an input was modified"
+    assert all(c.intact() for c in carved), "an operand's guard band was modified"
+    if not nan_expected:
+        assert all(o.canaries() == 0 for o in outs), "an element the op promises to write was left unwritten"
+    return [o.t.clone() for o in outs]
+
+
+class DevStack:
+    def __init__(self, env, layers):
+        self.Q, self.S, self.t2, self.tid = stack_exact(env, layers)
+        self.bits, self.g, self.dtype = layers[0].bits, layers[0].g, layers[0].dtype
+
+
+def dev_stack(env, layers):
+    """The packed stack of a case's layers, built once per module (op_edge_cases.stack hands out one list per stack)."""
+    if id(layers) not in env.stacks:
+        env.stacks[id(layers)] = (layers, DevStack(env, layers))
+    return env.stacks[id(layers)][1]
+
+
+def grouped_call(env, name, st, rows, N, operands, out_shape, nan_expected=False):
+    """flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P, template_id, *operands, out, num_sms, stream): host tensors
+    among the operands are row operands and get carved, device tensors are the stack's, None is a null pointer."""
+    T = st.dtype
+    E, P, K = st.Q.shape
+    carved = [carve(env, t, T) if (t is not None and not t.is_cuda) else None for t in operands]
+    ptrs = [None if t is None else (c.t if c is not None else t).data_ptr() for t, c in zip(operands, carved)]
+    out = Out(env, out_shape, T)
+    args = (0 if T == F16 else 1, st.bits, st.g, E, *rows, N, K, P, st.tid, *ptrs, out.t.data_ptr(), env.num_sms,
+            torch.cuda.current_stream(env.dev).cuda_stream)
+    return guarded(env, getattr(env.lib, "flute_" + name), args, [c for c in carved if c is not None], [out], nan_expected)[0]
+
+
+def offsets_tensor(counts):
+    return torch.tensor(OE.offsets_list(counts), dtype=torch.int32)
+
+
+def run_forward(env, c, X, nan_expected=False):
+    st = dev_stack(env, c.layers)
+    off = offsets_tensor(c.counts)
+    R = int(off[-1])
+    if c.op == "glu":
+        up = dev_stack(env, c.up)
+        rows = None if c.rows is None else c.rows.int()
+        return grouped_call(env, "qgemm_grouped_glu", st, (R, X.shape[0]), c.N,
+                            (X, rows, off, st.Q, st.S, st.t2, up.Q, up.S, up.t2), (R, c.N), nan_expected)
+    if c.op == "weighted":
+        return grouped_call(env, "qgemm_grouped_weighted", st, (R,), c.N, (X, off, st.Q, st.S, st.t2, c.rw), (R, c.N), nan_expected)
+    return grouped_call(env, "qgemm_grouped", st, (R,), c.N, (X, off, st.Q, st.S, st.t2), (R, c.N), nan_expected)
+
+
+def run_grad(env, c, dY, dY2, nan_expected=False):
+    st = dev_stack(env, c.layers)
+    off = offsets_tensor(c.counts)
+    R = int(off[-1])
+    second = (None,) * 4
+    if dY2 is not None:
+        s2 = dev_stack(env, c.layers2)
+        second = (dY2, s2.Q, s2.S, s2.t2)
+    return grouped_call(env, "qgemm_grouped_input_grad", st, (R,), c.N, (dY, off, st.Q, st.S, st.t2, c.rw, *second), (R, c.K),
+                        nan_expected)
+
+
+def diagnose(D, dtype, alternatives):
+    """Which other result D equals, for the failure message: an operand's subnormals flushed, or saturation at 65504."""
+    out = [name for name, R in alternatives if XC.exact_equal(D, R, dtype)]
+    out.append("%d NaN, %d inf in D" % (int(torch.isnan(D).sum()), int(torch.isinf(D).sum())))
+    return out
+
+
+def differing(D, R, dtype):
+    return int((D.double().cpu() != R.to(dtype).double()).sum())
+
+
+def check_rule(D, exp, what):
+    if not XC.nonfinite_equal(D, exp):
+        D = D.cpu()
+        rows = [r for r in range(D.shape[0]) if not XC.nonfinite_equal(D[r], exp[r])]
+        raise AssertionError((what, "rows that differ", rows[:20], len(rows)))
+
+
+# ---- the grouped forward -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("op,kind,bits,tile_p,g", OE.forward_range_params())
+def test_forward_range_edges(env, op, kind, bits, tile_p, g):
+    c = OE.forward_range_case(op, kind, bits, tile_p, g)
+    D = run_forward(env, c, c.X)
+    if not XC.exact_equal(D, c.R, c.dtype):
+        w = 1 if c.rw is None else c.rw.double()[:, None]
+        alt = [("subnormal %s flushed" % n, OE.forward_exact(c.layers, c.counts, c.X, flush_w=fw, flush_x=fx)[0] * w)
+               for n, fw, fx in (("w", True, False), ("x", False, True), ("w+x", True, True))]
+        alt.append(("saturates at 65504", c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX)))
+        raise AssertionError((op, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, alt)))
+
+
+@pytest.mark.parametrize("bits,tile_p", OE.pushed_params())
+def test_weighted_row_weight_alone_overflows(env, bits, tile_p):
+    """The unweighted result is finite: the power-of-two row weight pushes row a to +inf and, negated, row b to -inf."""
+    c = OE.weighted_pushed_case(bits, tile_p)
+    D = run_forward(env, c, c.X).cpu()
+    assert XC.exact_equal(D, c.R, c.dtype), (differing(D, c.R, c.dtype),
+                                             diagnose(D, c.dtype, [("saturates at 65504", c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX))]))
+    assert (D[c.a] == OE.INF).any() and torch.equal(D[c.b].double(), -D[c.a].double())
+
+
+@pytest.mark.parametrize("bits,tile_p,g,dtype,use_rows", OE.glu_saturation_params())
+def test_glu_saturation(env, bits, tile_p, g, dtype, use_rows):
+    """silu32(g) = g / (1 + expf(-g)) outside |g| <= 88.  g >= 18: 1 + expf(-g) is 1 in fp32 (e^-18 < 2^-25), so
+    H = round_T(g u) exactly (the product is exact in fp32: op_edge_cases asserts |g u| < 2^18 in multiples of 2^-6).
+    g <= -90: expf(-g) is +inf, H is zero by value.  -88 <= g < 18: test_grouped_glu_gpu.assert_glu's bound.  -90 < g < -88
+    (expf near its overflow) is left out: a condition on g, at most 2 % of the case."""
+    c = OE.glu_saturation_case(bits, tile_p, g, dtype, use_rows)
+    H = run_forward(env, c, c.X, nan_expected=True).double().cpu()      # (nothing non-finite goes in: a NaN is a failure below)
+    want_hi = c.P.to(dtype).double()
+    bad_hi = int((H[c.hi] != want_hi[c.hi]).sum())
+    bad_lo = int((H[c.lo] != 0).sum())
+    print("glu saturation %s: %d elements g >= 18 (%d of them +-inf in T), %d with g <= -90, %d mid, sign_k %d; wrong: %d, %d; NaN %d"
+          % ((bits, tile_p, g, dtype, use_rows), int(c.hi.sum()), int(torch.isinf(want_hi[c.hi]).sum()), int(c.lo.sum()),
+             int(c.mid.sum()), c.sign_k, bad_hi, bad_lo, int(torch.isnan(H).sum())))
+    assert bad_hi == 0, ("g >= 18: H != round_T(g u)", bad_hi, int(torch.isnan(H[c.hi]).sum()))
+    assert bad_lo == 0, ("g <= -90: H != 0", bad_lo)
+    assert_glu(H[c.mid], c.Eref[c.mid], dtype, ("mid range", bits, tile_p, g))
+
+
+@pytest.mark.parametrize("op,bits,tile_p,g,dtype,use_rows", OE.forward_nonfinite_params())
+def test_forward_nonfinite(env, op, bits, tile_p, g, dtype, use_rows):
+    c = OE.forward_nonfinite_case(op, bits, tile_p, g, dtype, use_rows)
+    clean = run_forward(env, c, c.X)
+    assert torch.isfinite(clean).all()
+    if op != "glu":
+        R = OE.forward_exact(c.layers, c.counts, c.X)[0]
+        assert XC.exact_equal(clean, R if c.rw is None else R * c.rw.double()[:, None], dtype)
+    for la in c.launches:
+        D = run_forward(env, c, la.X, nan_expected=True)
+        check_rule(D, OE.rowwise_expected(clean, la.poisons), (op, bits, tile_p, g, dtype, use_rows, la.name))
+
+
+# ---- the grouped input gradient ------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("form,kind,bits,tile_p,g", OE.grad_range_params())
+def test_input_grad_range_edges(env, form, kind, bits, tile_p, g):
+    c = OE.grad_range_case(form, kind, bits, tile_p, g)
+    D = run_grad(env, c, c.dY, c.dY2)
+    if not XC.exact_equal(D, c.R, c.dtype):
+        alt = [("saturates at 65504", c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX))]
+        for n, fw, fy in (("w", True, False), ("dY", False, True), ("w+dY", True, True)):
+            R = OE.grad_exact(c.layers, c.counts, c.dY, flush_w=fw, flush_y=fy)[0]
+            if c.dY2 is not None:
+                R = R + OE.grad_exact(c.layers2, c.counts, c.dY2, flush_w=fw, flush_y=fy)[0]
+            alt.append(("subnormal %s flushed" % n, R if c.rw is None else R * c.rw.double()[:, None]))
+        raise AssertionError((form, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, alt)))
+
+
+@pytest.mark.parametrize("form,bits,tile_p,g,dtype", OE.grad_nonfinite_params())
+def test_input_grad_nonfinite(env, form, bits, tile_p, g, dtype):
+    c = OE.grad_nonfinite_case(form, bits, tile_p, g, dtype)
+    clean = run_grad(env, c, c.dY, c.dY2)
+    R = OE.grad_exact(c.layers, c.counts, c.dY)[0]
+    if c.dY2 is not None:
+        R = R + OE.grad_exact(c.layers2, c.counts, c.dY2)[0]
+    assert XC.exact_equal(clean, R if c.rw is None else R * c.rw.double()[:, None], dtype)
+    for la in c.launches:
+        D = run_grad(env, c, la.dY, la.dY2, nan_expected=True)
+        check_rule(D, OE.rowwise_expected(clean, la.poisons), (form, bits, tile_p, g, dtype, la.name))
