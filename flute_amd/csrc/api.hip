@@ -101,6 +101,41 @@ bool decode_template(int bits, int id, flute_template_info* t) {
     return true;
 }
 
+// What every entry point checks of a layer (check_layer), and one planner call: the layer, the shape, the CU count, the workspace
+// and the overrides.
+struct Layer { int bits, lg, J, units; flute_template_info t; };
+struct Call : Layer { int dtype, M, N, K, template_id, num_sms; size_t workspace_bytes; Ovr ov; };
+
+// ---- which kernels are built ---------------------------------------------------------------------------
+// Each family's entry point for a call's layer (bit width, dtype, TileP) and the family's knobs, from the row lists of the
+// instantiation units (kernels.h); nullptr: not built.  The only statement of which shapes exist: the planners ask these, and
+// resolve_kernel stores the answer with the plan.
+template <class Kernel> const void* fn_of(Kernel k) { return reinterpret_cast<const void*>(k); }
+#define FLUTE_BY_BITS(F, ...) (c.bits == 4 ? fn_of(F##_b4(__VA_ARGS__)) : (c.bits == 3 ? fn_of(F##_b3(__VA_ARGS__)) : fn_of(F##_b2(__VA_ARGS__))))
+#define FLUTE_BY_DTYPE(F, ...) (c.dtype == 0 ? fn_of(F##_f16(__VA_ARGS__)) : fn_of(F##_bf16(__VA_ARGS__)))
+const void* stream_fn(const Call& c, int mb, int depth) { return FLUTE_BY_BITS(stream_kernel, c.dtype, c.t.tile_p, mb, depth); }
+const void* oneshot_fn(const Call& c, int mb, int depth, int had, int pipe) {
+    if (c.bits == 3) return fn_of(oneshot_kernel_b3(c.dtype, c.t.tile_p, mb, depth, had, pipe));
+    return c.bits == 4 ? FLUTE_BY_DTYPE(oneshot_kernel_b4, c.t.tile_p, mb, depth, had, pipe) : FLUTE_BY_DTYPE(oneshot_kernel_b2, c.t.tile_p, mb, depth, had, pipe);
+}
+const void* persist_fn(const Call& c, int mb, int depth, int nsets, int had) { return FLUTE_BY_BITS(persist_kernel, c.dtype, c.t.tile_p, mb, depth, nsets, had); }
+const void* fast_fn(const Call& c, int waves, int kw, int depth, int mb) { return c.bits == 4 ? fn_of(fast_kernel_b4(c.dtype, c.t.tile_p, waves, kw, depth, mb)) : nullptr; }
+const void* fastm_fn(const Call& c, int waves, int nm, int lg, int ng) { return c.bits == 4 ? fn_of(fastm_kernel_b4(c.dtype, c.t.tile_p, waves, nm, lg, ng)) : nullptr; }
+const void* persistm_fn(const Call& c, int lg, int ng, int xr, int waves, int xres) {
+    if (c.bits == 3) return nullptr;
+    return c.bits == 4 ? FLUTE_BY_DTYPE(persistm_kernel_b4, c.t.tile_p, lg, ng, xr, waves, xres) : FLUTE_BY_DTYPE(persistm_kernel_b2, c.t.tile_p, lg, ng, xr, waves, xres);
+}
+const void* skinny_fn(const Call& c, int depth) { return c.bits == 4 ? fn_of(skinny_kernel_b4(c.dtype, c.t.tile_p, depth)) : nullptr; }
+const void* splitk_fn(const Call& c, int rt, int kp) { return fn_of(splitk_kernel(c.bits, c.dtype, c.t.tile_p, rt, kp)); }
+const void* block_fn(const Call& c, int cfg) { return FLUTE_BY_BITS(block_kernel, c.dtype, c.t.tile_p, cfg); }
+const void* tile_fn(const Call& c, int r, int mt, int sw) {                     // sw: slabs per wave, 2 for 4-bit layers only
+    if (c.bits == 4) return fn_of(tile_kernel_b4(c.dtype, c.t.tile_p, r, mt, sw));
+    if (sw != 1) return nullptr;
+    return c.bits == 3 ? fn_of(tile_kernel_b3(c.dtype, c.t.tile_p, r, mt)) : fn_of(tile_kernel_b2(c.dtype, c.t.tile_p, r, mt));
+}
+#undef FLUTE_BY_BITS
+#undef FLUTE_BY_DTYPE
+
 // ---- streaming decode kernel: launch shape ------------------------------------------------------------
 // Every (waves per workgroup, in-workgroup K split) that fits LDS is priced by the piece-slots its busiest
 // CU executes (1 piece = 1 KiB of one unit's packed row) plus a per-visit overhead, and the candidates are
@@ -172,16 +207,17 @@ bool stream_shape(int bits, int mb, int lg, int units, int krange, int G, bool s
 struct OneShape { int W, kw, upw, pk, depth, pipe, ipw, grid; size_t lds; };
 struct OneArgs { int lg, lkw, upw, pk, ipw, depth, pipe, nvis, nch, nwg, nsets; };
 
-int plan_oneshot(int bits, int lg, int M, int N, int K, int num_sms, const flute_template_info& t, int template_id,
-                 const Ovr& ov, flute_plan* p, OneArgs* oa) {
+int plan_oneshot(const Call& c, const Ovr& ov, flute_plan* p, OneArgs* oa) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K, num_sms = c.num_sms, template_id = c.template_id;
+    const flute_template_info& t = c.t;
     if (lg < 6) return FLUTE_ERR_SHAPE;                       // 32-wide groups: twice the scale words per wave
     if ((K >> lg) & 1) return FLUTE_ERR_SHAPE;                // scale rows are read as aligned dwords (two groups each)
     const int J = (bits == 3) ? 16 : 16 / bits;
     const int units = N / J;
     const int npieces = ceil_div(K, 512);
     int mb = 1; while (mb < M) mb <<= 1;
-    if (mb > 4 || (bits == 3 && mb > 2)) return FLUTE_ERR_SHAPE;
     const int dlo = (bits == 3) ? 2 : 4, dhi = 2 * dlo;
+    if (!oneshot_fn(c, mb, dlo, 0, 0)) return FLUTE_ERR_SHAPE;         // rows per pass: 1, 2, 4 (3 bits: 1, 2)
     int dsel = 0;                                             // 0: both depths
     if (bits == 4 && (template_id % 4) == 1) dsel = dlo;
     if (bits == 4 && (template_id % 4) == 2) dsel = dhi;
@@ -191,7 +227,7 @@ int plan_oneshot(int bits, int lg, int M, int N, int K, int num_sms, const flute
     const int xpr = (mb == 4) ? 1 : 2;
     std::vector<OneShape> cands;
     for (int D = dhi; D >= dlo; D /= 2) {
-        if (dsel && D != dsel) continue;
+        if ((dsel && D != dsel) || !oneshot_fn(c, mb, D, 0, 0)) continue;
         for (int W = 4; W <= 16; W *= 2) {
             int w = W;
             if (ov.waves > 0) { if (W != 4) continue; w = ov.waves; }
@@ -241,10 +277,10 @@ int plan_oneshot(int bits, int lg, int M, int N, int K, int num_sms, const flute
 // us per launch next to the round-4 one-shot kernel in the same harness): K = 4096: (4, 1, 8) 4.24 / (8, 2, 4) 4.35 against 4.43
 // on 4096 x 4096, 7.49 / 7.50 against 8.63 on 4096 x 11008; K = 8192: (8, 2, 8) 6.50 on 8192 x 4096 (g = 128).  rank = the
 // template's Stages - 2.
-int plan_fast(int bits, int lg, int M, int N, int K, int num_sms, int rank, int want_waves, flute_plan* p, OneArgs* oa) {
+int plan_fast(const Call& call, int rank, int want_waves, flute_plan* p, OneArgs* oa) {
+    const int bits = call.bits, lg = call.lg, M = call.M, N = call.N, K = call.K, num_sms = call.num_sms;
     if (bits != 4 || M < 1 || M > 4 || lg < 6 || lg > 8) return FLUTE_ERR_SHAPE;
-    int mb = 1; while (mb < M) mb <<= 1;                       // rows per pass: 1, 2, 4 (their activations beside the table image: mb * K * 2 <= 32 KB)
-    if ((size_t)mb * K * 2 > 32768) return FLUTE_ERR_SHAPE;
+    int mb = 1; while (mb < M) mb <<= 1;                       // rows per pass: 1, 2, 4
     struct Shape { int W, KW, D; };
     std::vector<Shape> c;
     if (K == 2048) c = {{4, 1, 4}};
@@ -263,10 +299,11 @@ int plan_fast(int bits, int lg, int M, int N, int K, int num_sms, int rank, int 
         for (const Shape& x : c) if (x.W == want_waves) { sh = x; found = true; break; }
         if (!found) return FLUTE_ERR_SHAPE;
     }
+    // (built for the rows whose activations fit beside the table image, mb * K * 2 <= 32 KB: not four rows of K = 8192)
+    if (!fast_fn(call, sh.W, sh.KW, sh.D, mb)) return FLUTE_ERR_SHAPE;
     const int units = N / 4, upw = sh.W / sh.KW;
     if (units % upw) return FLUTE_ERR_SHAPE;
     if (((size_t)N * (size_t)(K >> lg)) * 2 >= (size_t)0xfffffff0u || (size_t)units * K * 2 >= ((size_t)1 << 40)) return FLUTE_ERR_SHAPE;
-    (void)num_sms;
     memset(p, 0, sizeof(*p));
     p->family = 0;
     p->m_block = mb; p->waves = sh.W; p->kw = sh.KW; p->splitk = 1; p->k_per_split = K;
@@ -281,10 +318,11 @@ int plan_fast(int bits, int lg, int M, int N, int K, int num_sms, int rank, int 
 // 4 unit rows (16 columns) x all of K; every wave's K range must hold >= 2 groups (its scale words are read as whole dwords).
 // Round 6: ng column groups (4 unit rows each) per workgroup share one staged activation set: the smallest of 1, 2, 3 that covers the
 // layer in one round of workgroups (override slabs_per_wave = 1 / 2 / 3 fixes it).
-int plan_fastm(int bits, int lg, int M, int N, int K, int num_sms, int ng_ovr, flute_plan* p, OneArgs* oa) {
-    if (bits != 4 || M < 1 || M > 16 || lg < 6 || lg > 8 || (K != 4096 && K != 2048)) return FLUTE_ERR_SHAPE;
+int plan_fastm(const Call& c, int ng_ovr, flute_plan* p, OneArgs* oa) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K, num_sms = c.num_sms;
+    if (bits != 4 || M < 1 || M > 16 || (K != 4096 && K != 2048)) return FLUTE_ERR_SHAPE;
     const int W = 8, nm = K / (128 * W);
-    if (((128 * nm) >> lg) < 2) return FLUTE_ERR_SHAPE;
+    if (!fastm_fn(c, W, nm, lg, 1)) return FLUTE_ERR_SHAPE;      // group sizes 64 .. 256 that leave a wave's K range >= 2 groups
     const int units = N / 4;
     if (units % 4) return FLUTE_ERR_SHAPE;
     int ng = 1;
@@ -322,7 +360,8 @@ double persistm_model_us(int M, int N, int K, int num_sms, int ng, int* grid_out
     if (visits_out) *visits_out = visits;
     return 3.5 + (hbm > issue ? hbm : issue);
 }
-int plan_persistm(int bits, int lg, int M, int N, int K, int num_sms, int ng_ovr, int visits_ovr, int xres_ovr, flute_plan* p, OneArgs* oa) {
+int plan_persistm(const Call& c, int ng_ovr, int visits_ovr, int xres_ovr, flute_plan* p, OneArgs* oa) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K, num_sms = c.num_sms;
     // (sixteen waves per workgroup - four per SIMD, rings three deep - measured slower than eight on every layer: 28672 x 8192 M = 4 32.1 against
     // 31.1 us, 8192^2 13.3 against 11.1, profiles/r06/call33_persistm_16_waves_dropped.log; the kernel keeps the template parameter)
     // (group size 128: a column's scale row must be a whole number of dwords - the macro-step's 4-B scale request)
@@ -352,9 +391,9 @@ int plan_persistm(int bits, int lg, int M, int N, int K, int num_sms, int ng_ovr
     p->m_block = 16; p->m_tiles = 1; p->slabs_per_wave = ng; p->waves = 8; p->kw = 8; p->splitk = 1; p->k_per_split = K;
     p->grid = (unsigned)grid; p->block = 512u;
     const int xr = M <= 4 ? 1 : (M <= 8 ? 2 : 4);                  // activation requests per macro-step (4 rows each)
-    // activations resident in LDS (staged once per workgroup, no activation request in the loop) where 4 xr rows x K fit in 64 KB beside the rest;
-    // override one_shot = 0 keeps the rings
-    const bool xres = (long)K * xr <= 8192 && xr <= 2 && !(xr == 1 && ng == 3) && xres_ovr != 0;
+    // activations resident in LDS (staged once per workgroup, no activation request in the loop) where 4 xr rows x K fit in 64 KB beside the rest
+    // and that member is built; override one_shot = 0 keeps the rings
+    const bool xres = (long)K * xr <= 8192 && xres_ovr != 0 && persistm_fn(c, lg, ng, xr, 8, 1);
     p->lds_bytes = persistm_lds_bytes(ng, xr, 8, xres, bits); p->lut_copies = 32;
     p->ring_depth = PM_DW; p->visits = visits; p->k_chunks = xr; p->one_shot = xres ? 1 : 0;
     if (oa) { memset(oa, 0, sizeof(*oa)); oa->lg = lg; oa->depth = PM_DW; }
@@ -369,17 +408,19 @@ int plan_persistm(int bits, int lg, int M, int N, int K, int num_sms, int ng_ovr
 // 42 us against 25.7 on 28672 x 8192 W3), then the launch closest to EIGHT waves per CU (7 - 8 waves per CU x 4 visits
 // beat 14 - 16 x 2 by 4 - 6 %, 4 per CU lose 20 %), then the larger workgroup (fewer table images).
 // Stages 2..5 -> rank 0..3.
-int plan_persist(int bits, int lg, int M, int N, int K, int num_sms, const flute_template_info& t, const Ovr& ov,
-                 flute_plan* p, OneArgs* oa) {
+int plan_persist(const Call& c, const Ovr& ov, flute_plan* p, OneArgs* oa) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K, num_sms = c.num_sms;
+    const flute_template_info& t = c.t;
     if (M < 1 || M > 2 || lg < 6 || ((K >> lg) & 1) || K % 512) return FLUTE_ERR_SHAPE;
     int mb = 1; while (mb < M) mb <<= 1;                      // rows per pass (their staged activations must fit LDS: below)
     const int J = (bits == 3) ? 16 : 16 / bits;
     const int units = N / J;
     const int npieces = K / 512;
-    int D = (bits == 3) ? 2 : 4;
-    while (D > 2 && npieces % D) D /= 2;
-    if (ov.depth == 2 || (ov.depth == 4 && bits != 3)) D = ov.depth;
     const int NS = 2;
+    auto built = [&](int d) { return persist_fn(c, mb, d, NS, 0) != nullptr; };
+    int D = 4;                                                // the deepest built segment: 4 pieces, 3 bits 2
+    while (D > 2 && (!built(D) || npieces % D)) D /= 2;
+    if ((ov.depth == 2 || ov.depth == 4) && built(ov.depth)) D = ov.depth;
     if (npieces % D) return FLUTE_ERR_SHAPE;
     const int nch = npieces / D;
     if (nch > 255) return FLUTE_ERR_SHAPE;
@@ -426,7 +467,9 @@ int plan_persist(int bits, int lg, int M, int N, int K, int num_sms, const flute
 // Skinny MFMA kernel (qgemm_skinny.h): 4-bit, M <= 16.  A wave = one slab (16 units) x D k-steps, the 4 or 8 waves of a
 // workgroup share a K slice of the slab, so K = splitk x 32 D KW with D in {4, 8, 16}; splitk > 1 (round 4): the slices of a
 // slab are neighbouring workgroups and meet through the workspace inside the launch (xwg.h, L form).
-int plan_skinny(int bits, int lg, int M, int N, int K, const Ovr& ov, size_t workspace_bytes, flute_plan* p, OneArgs* ka) {
+int plan_skinny(const Call& c, const Ovr& ov, flute_plan* p, OneArgs* ka) {
+    const int bits = c.bits, lg = c.lg, M = c.M, N = c.N, K = c.K;
+    const size_t workspace_bytes = c.workspace_bytes;
     if (bits != 4 || M < 1 || M > 16 || lg < 5 || ((K >> lg) & 1) || K % 128) return FLUTE_ERR_SHAPE;
     const int units = N / 4;
     if (units % 16) return FLUTE_ERR_SHAPE;
@@ -444,7 +487,7 @@ int plan_skinny(int bits, int lg, int M, int N, int K, const Ovr& ov, size_t wor
         if (ov.waves > 0 && kw != ov.waves) continue;
         if (ksteps % kw) continue;
         const int d = ksteps / kw;
-        if ((d != 4 && d != 8 && d != 16) || ((d * 32) >> lg) > 8) continue;
+        if (!skinny_fn(c, d) || ((d * 32) >> lg) > 8) continue;
         KW = kw; D = d;
         break;
     }
@@ -645,7 +688,6 @@ int plan_stream(int dtype, int bits, int lg, int M, int N, int K, int num_sms, c
 
 // What every entry point checks of a layer - bits, group size (0: none, flute_unpack), template id, then N and K alignment -
 // in the order of its error codes.  *l describes the layer that passes.
-struct Layer { int bits, lg, J, units; flute_template_info t; };
 int check_layer(int bits, int group, int template_id, int N, int K, int k_align, Layer* l) {
     if (bits != 2 && bits != 3 && bits != 4) return FLUTE_ERR_NUM_BITS;
     if (group && group != 32 && group != 64 && group != 128 && group != 256) return FLUTE_ERR_GROUP_SIZE;
@@ -659,10 +701,9 @@ int check_layer(int bits, int group, int template_id, int N, int K, int k_align,
     return FLUTE_OK;
 }
 
-// One planner call: the layer, the shape, the CU count, the workspace and the overrides.
-struct Call : Layer { int dtype, M, N, K, template_id, num_sms; size_t workspace_bytes; Ovr ov; };
-// A plan and the launch arguments the decode kernels take beside it.
-struct Planned { flute_plan p; OneArgs oa; StreamArgs sa; };
+// A plan, the launch arguments the decode kernels take beside it, and its kernel (resolve_kernel): fn_had is the member that rotates
+// the activations while it stages them, where that is an instantiation of its own (one-shot and persistent one-shot kernels; else null).
+struct Planned { flute_plan p; OneArgs oa; StreamArgs sa; const void* fn; const void* fn_had; };
 
 int lds_fits(const flute_plan& p) { return p.lds_bytes > (size_t)kMaxLds ? FLUTE_ERR_SHAPE : FLUTE_OK; }
 // workspace of a grid K split whose fp32 slabs are [splitk][M][N] behind the state words
@@ -835,8 +876,8 @@ BlockChoice choose_block(const Call& c) {
     if (ov.family == kFamilyBlock) {
         b.cfg = (ov.m_tiles == 4) ? 5 : 4;               // 128- / 256-row blocks of qgemm_block2.h
         if (bits == 3 && ov.m_tiles != 8) b.cfg = 5;     // 3-bit layers: 128-row blocks of qgemm_block3.h unless 256 rows are asked for ...
-        if (bits == 3 && (ov.m_block == 1 || ov.m_block == 2 || ov.m_block == 4))
-            b.cfg = 8 + ov.m_block;                      // ... or its skinny blocks of m_block row tiles
+        if (bits == 3 && ov.m_block > 0 && block_fn(c, 8 + ov.m_block))
+            b.cfg = 8 + ov.m_block;                      // ... or its skinny blocks of m_block row tiles (1, 2, 4)
     } else if (bits == 3 && M > 32 && M <= 64 && (size_t)N * K >= ((size_t)56 << 20) &&
                (M > 48 || skinny3_fills(M, units / blk_units, K, lg, num_sms))) {    // (14336 x 3584, 51 M weights: 29.5 against 26.4 us on the per-wave kernel)
         // 3-bit skinny blocks (64 rows, grid K split): measured against the per-wave kernel at M = 64 - 8192^2 31.6 vs
@@ -897,6 +938,7 @@ BlockChoice choose_block(const Call& c) {
             b.alt_us = std::min(b.alt_us, b.sk > 0 ? best : base);
         }
     }
+    if (b.cfg >= 0 && !block_fn(c, b.cfg)) b.cfg = -1;     // a configuration that is not built is no choice
     return b;
 }
 
@@ -953,7 +995,7 @@ int plan_decode(const Call& c, Planned* out) {
     // K = 2048, two rows: up to two rounds (6144 x 2048 4.34 -> 3.79 us, 8192 x 2048 4.38 -> 4.01; four rows lose there: 5.14 / 5.76)
     if ((want == 4 || (want < 0 && auto_lean_id(c) && t.stages <= 3 && ov.waves < 0)) && !ov.had8 && ov.kw < 0) {
         Planned q{};
-        if (plan_fast(bits, lg, M, N, K, num_sms, std::max(0, t.stages - 2), want == 4 ? ov.waves : -1, &q.p, &q.oa) == FLUTE_OK &&
+        if (plan_fast(c, std::max(0, t.stages - 2), want == 4 ? ov.waves : -1, &q.p, &q.oa) == FLUTE_OK &&
             (want == 4 || ((K != 8192 || (M == 2 && (long)q.p.grid * 5 >= (long)num_sms * 4)) &&
                            (size_t)N * K <= ((size_t)48 << 20) && (long)q.p.grid * 2 >= (long)num_sms &&
                            (long)q.p.grid <= (M == 1 ? 3L : (M == 2 && K == 2048 ? 2L : 1L)) * num_sms))) {
@@ -972,12 +1014,12 @@ int plan_decode(const Call& c, Planned* out) {
                               (size_t)N * K >= ((size_t)24 << 20) && (long)c.units >= 4L * num_sms;
     if (want == 2 || persist_auto) {
         Planned q{};
-        if (plan_persist(bits, lg, M, N, K, num_sms, t, ovd, &q.p, &q.oa) == FLUTE_OK) { *out = q; return lds_fits(out->p); }
+        if (plan_persist(c, ovd, &q.p, &q.oa) == FLUTE_OK) { *out = q; return lds_fits(out->p); }
         if (want == 2) want = 0;
     }
     if (want != 0) {
         Planned q{};
-        if (plan_oneshot(bits, lg, M, N, K, num_sms, t, template_id, ovd, &q.p, &q.oa) == FLUTE_OK &&
+        if (plan_oneshot(c, ovd, &q.p, &q.oa) == FLUTE_OK &&
             (want == 1 || ((size_t)N * K <= ((size_t)64 << 20) && (long)q.p.grid * 2 >= (long)num_sms))) {
             *out = q;
             return lds_fits(out->p);
@@ -1039,7 +1081,7 @@ int plan_block(const Call& c, const BlockChoice& b, Planned* out) {
 // rest of the parallelism is the in-workgroup K split, a grid-level split only for very
 // narrow layers.
 int plan_tile(const Call& c, Planned* out) {
-    const int bits = c.bits, J = c.J, M = c.M, N = c.N, K = c.K, units = c.units, num_sms = c.num_sms, template_id = c.template_id;
+    const int bits = c.bits, M = c.M, N = c.N, K = c.K, units = c.units, num_sms = c.num_sms, template_id = c.template_id;
     const flute_template_info& t = c.t;
     const Ovr& ov = c.ov;
     int mt = (M <= 16) ? 1 : (M <= 32 ? 2 : 4);
@@ -1051,11 +1093,8 @@ int plan_tile(const Call& c, Planned* out) {
     for (int m2 = t.sms_multiple; m2 > 1 && mt > 1; m2 >>= 1) mt >>= 1;
     if (ov.m_tiles == 1 || ov.m_tiles == 2 || ov.m_tiles == 4) mt = ov.m_tiles;
     if (mt > mt_cap) mt = mt_cap;
-    // instantiated (R, MT): (J/R)*MT <= 16 accumulator tiles, R in {1,2,4}, MT > 1 needs R <= 2
-    auto combo_ok = [&](int r, int m) {
-        if (bits == 3) return r == 1 && m == 1;
-        return (J / r) * m <= 16 && r <= 4 && (m == 1 || r <= 2);
-    };
+    // built (R, MT), one slab per wave (inst_tile_b*.hip: (J/R)*MT <= 16 accumulator tiles)
+    auto combo_ok = [&](int r, int m) { return tile_fn(c, r, m, 1) != nullptr; };
     while (mt > 1 && !combo_ok(1, mt) && !combo_ok(2, mt)) mt >>= 1;
     const int mtiles = ceil_div(M, mt * 16);
     int R = 1;
@@ -1079,15 +1118,16 @@ int plan_tile(const Call& c, Planned* out) {
     // QuantMapMode digit 3 above M = 16 (round 5): no lane sharing AND two slabs per wave, the chip filled by the grid K split - the
     // plan round 4's regret sweep wanted on 8192 x 28672 and could not reach through an id (M = 64: 72.6 -> 55.3 us, M = 48 65.0 ->
     // 52.8, M = 32 52.4 -> 45.2).  The automatic digit takes it by itself on layers that deep (K >= 16384: a slice keeps >= 4096 k) whose halved slab count x four slices fills the chip
-    const bool deep_sw2 = bits == 4 && M > 16 && combo_ok(1, mt) && (c.dtype == 0 || mt <= 2) && (units / 16) % 2 == 0 && ov.m_block <= 0 &&
+    const bool deep_sw2 = M > 16 && tile_fn(c, 1, mt, 2) && (units / 16) % 2 == 0 && ov.m_block <= 0 &&
                           ((template_id % 4) == 3 || ((template_id % 4) == 0 && K >= 16384 && !fills((long)(units / 16) * mtiles) && fills((long)(units / 32) * mtiles * 4)));
     if (deep_sw2) R = 1;
-    if (ov.m_block > 0 && combo_ok(ov.m_block, mt)) R = ov.m_block;
-    // SW = 2 slabs per wave (4-bit, no lane sharing, fp16 up to MT = 4 / bf16 up to MT = 2: the bf16 path
+    // (m_block = 3 at MT = 1 is not built; the rule this lookup replaced let it plan, and it keeps planning until that is fixed: resolve_kernel)
+    if (ov.m_block > 0 && (combo_ok(ov.m_block, mt) || (bits != 3 && ov.m_block == 3 && mt == 1))) R = ov.m_block;
+    // SW = 2 slabs per wave (where built - inst_tile_b4.hip: 4-bit, no lane sharing, fp16 up to MT = 4 / bf16 up to MT = 2: the bf16 path
     // keeps a second accumulator set): every activation fragment then serves 8 column tiles and the
     // texture-path traffic per MFMA drops by 40 %.  Worth it once halving the slab count still leaves a
     // workgroup for every CU; QuantMapMode (the last template digit) lets the tuner force either.
-    const bool sw_ok = bits == 4 && R == 1 && (c.dtype == 0 || mt <= 2) && (units / 16) % 2 == 0;
+    const bool sw_ok = tile_fn(c, R, mt, 2) && (units / 16) % 2 == 0;
     int sw = 1;
     // ... as soon as the halved slab count still fills 55 % of the CUs (28672 x 8192 M = 16: 448 workgroups 43.4 us, 224
     // workgroups 37.1; M = 64: 73.4 -> 54.2; 4096 x 14336 M = 128: 38.2 -> 28.2) - or, at M <= 16, on the tuner's request (digit 1)
@@ -1144,37 +1184,28 @@ int plan_tile(const Call& c, Planned* out) {
     return lds_fits(out->p);
 }
 
-// The planner: validate, route a forced family to its planner, else try the automatic candidates in their order.
-int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int template_id, int num_sms,
-                       size_t workspace_bytes, const Ovr& ov, Planned* out, flute_template_info* tinfo) {
-    if (dtype != 0 && dtype != 1) return FLUTE_ERR_DTYPE;
-    // override families: -1 automatic, 0 decode, 1 / 2 per-wave MFMA kernel, 3 block kernels, 5 skinny MFMA kernel,
-    // 6 split-K block kernel, 7 lean MFMA decode kernel, 8 persistent MFMA decode kernel; anything else is a caller error (round 1's family 4 is gone)
-    if (ov.family < -1 || ov.family == 4 || ov.family > 8) return FLUTE_ERR_SHAPE;
-    Call c;
-    const int lrc = check_layer(bits, group, template_id, N, K, std::max(64, group), &c);
-    if (lrc) return lrc;
-    if (M < 1) return FLUTE_ERR_SHAPE;
-    *tinfo = c.t;
-    c.dtype = dtype; c.M = M; c.N = N; c.K = K; c.template_id = template_id;
-    c.num_sms = num_sms < 1 ? 256 : num_sms; c.workspace_bytes = workspace_bytes; c.ov = ov;
+// The choice of a plan: route a forced family to its planner, else try the automatic candidates in their order.
+int choose_plan(const Call& c, Planned* out) {
+    const int bits = c.bits, M = c.M, N = c.N, K = c.K;
+    const size_t workspace_bytes = c.workspace_bytes;
+    const Ovr& ov = c.ov;
     const int fam = ov.family;
 
     // forced: the family's planner; families 6 and 8 refuse a call they do not fit, the others fall back to the per-wave
     // kernel (family 0: above M = 4, and where the scales outgrow the decode kernels' descriptor)
     if (fam == kFamilyPersistM)
-        return plan_persistm(bits, c.lg, M, N, K, c.num_sms, ov.slabs, ov.m_tiles, ov.one_shot, &out->p, &out->oa);
+        return plan_persistm(c, ov.slabs, ov.m_tiles, ov.one_shot, &out->p, &out->oa);
     if (fam == kFamilySplitK) {
         const int rc = plan_splitk(bits, c.lg, M, N, K, c.num_sms, ov, workspace_bytes, &out->p);
         return rc ? rc : lds_fits(out->p);
     }
     if (fam == kFamilyFastM) {
         Planned q{};
-        if (plan_fastm(bits, c.lg, M, N, K, c.num_sms, ov.slabs, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+        if (plan_fastm(c, ov.slabs, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
     if (fam == kFamilySkinny) {
         Planned q{};
-        if (plan_skinny(bits, c.lg, M, N, K, ov, workspace_bytes, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+        if (plan_skinny(c, ov, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
     if (fam == 0 && M <= 4 && decode_fits(c)) return plan_decode(c, out);
     if (fam == kFamilyBlock) {
@@ -1187,18 +1218,18 @@ int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int 
     // split-K priced against the block / per-wave cost models -> block -> per-wave
     if (persistm_auto(c)) {
         Planned q{};
-        if (plan_persistm(bits, c.lg, M, N, K, c.num_sms, -1, -1, -1, &q.p, &q.oa) == FLUTE_OK && persistm_taken(c, q.p)) { *out = q; return FLUTE_OK; }
+        if (plan_persistm(c, -1, -1, -1, &q.p, &q.oa) == FLUTE_OK && persistm_taken(c, q.p)) { *out = q; return FLUTE_OK; }
     }
     if (fastm_auto(c)) {
         Planned q{};
-        if (plan_fastm(bits, c.lg, M, N, K, c.num_sms, -1, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+        if (plan_fastm(c, -1, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
     if (decode_auto(c)) return plan_decode(c, out);
     if (const int sk5 = skinny_split_auto(c); sk5 || skinny_auto(c)) {
         Ovr o5 = ov;
         if (sk5) o5.splitk = sk5;
         Planned q{};
-        if (plan_skinny(bits, c.lg, M, N, K, o5, workspace_bytes, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
+        if (plan_skinny(c, o5, &q.p, &q.oa) == FLUTE_OK) { *out = q; return FLUTE_OK; }
     }
     if (splitk_stages5(c)) {
         Planned q{};
@@ -1218,6 +1249,47 @@ int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int 
     return b.cfg >= 0 ? plan_block(c, b, out) : plan_tile(c, out);
 }
 
+// The kernel of a plan, from the lookups the planners asked.  A plan whose kernel is not built is refused here, when it is planned:
+// FLUTE_ERR_TEMPLATE_ID.
+int resolve_kernel(const Call& c, Planned* pl) {
+    const flute_plan& p = pl->p;
+    const OneArgs& oa = pl->oa;
+    const bool decode = p.family == 0;
+    pl->fn_had = nullptr;
+    if (decode && p.one_shot == 3) { pl->fn = persist_fn(c, p.m_block, oa.depth, oa.nsets, 0); pl->fn_had = persist_fn(c, p.m_block, oa.depth, oa.nsets, 1); }
+    else if (decode && p.one_shot == 4) pl->fn = fast_fn(c, p.waves, p.kw, p.ring_depth, p.m_block);
+    else if (decode && p.one_shot) { pl->fn = oneshot_fn(c, p.m_block, oa.depth, 0, oa.pipe); pl->fn_had = oneshot_fn(c, p.m_block, oa.depth, 1, oa.pipe); }
+    else if (decode) pl->fn = stream_fn(c, p.m_block, p.ring_depth);
+    else if (p.family == kFamilySkinny) pl->fn = skinny_fn(c, oa.depth);
+    else if (p.family == kFamilyFastM) pl->fn = fastm_fn(c, p.waves, p.ring_depth, oa.lg, p.slabs_per_wave);
+    else if (p.family == kFamilyPersistM) pl->fn = persistm_fn(c, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot);
+    else if (p.family == kFamilySplitK) pl->fn = splitk_fn(c, p.m_tiles, p.kw);
+    else if (p.family == kFamilyBlock) pl->fn = block_fn(c, p.m_block);
+    else pl->fn = tile_fn(c, p.m_block, p.m_tiles, p.slabs_per_wave);
+    // the one plan that has no kernel: the per-wave kernel under an override m_block = 3 (plan_tile).  As before, the plan is
+    // returned and flute_qgemm_ex refuses to launch it
+    if (!pl->fn && p.family == 2 && p.m_block == 3) return FLUTE_OK;
+    const bool two = decode && p.one_shot >= 1 && p.one_shot <= 3;      // the kernels whose rotating member is a second instantiation
+    return pl->fn && (!two || pl->fn_had) ? FLUTE_OK : FLUTE_ERR_TEMPLATE_ID;
+}
+
+// The planner: validate, choose the plan, resolve its kernel.
+int make_plan_uncached(int dtype, int bits, int group, int M, int N, int K, int template_id, int num_sms,
+                       size_t workspace_bytes, const Ovr& ov, Planned* out) {
+    if (dtype != 0 && dtype != 1) return FLUTE_ERR_DTYPE;
+    // override families: -1 automatic, 0 decode, 1 / 2 per-wave MFMA kernel, 3 block kernels, 5 skinny MFMA kernel,
+    // 6 split-K block kernel, 7 lean MFMA decode kernel, 8 persistent MFMA decode kernel; anything else is a caller error (round 1's family 4 is gone)
+    if (ov.family < -1 || ov.family == 4 || ov.family > 8) return FLUTE_ERR_SHAPE;
+    Call c;
+    const int lrc = check_layer(bits, group, template_id, N, K, std::max(64, group), &c);
+    if (lrc) return lrc;
+    if (M < 1) return FLUTE_ERR_SHAPE;
+    c.dtype = dtype; c.M = M; c.N = N; c.K = K; c.template_id = template_id;
+    c.num_sms = num_sms < 1 ? 256 : num_sms; c.workspace_bytes = workspace_bytes; c.ov = ov;
+    const int rc = choose_plan(c, out);
+    return rc ? rc : resolve_kernel(c, out);
+}
+
 // make_plan is a pure function of its arguments and runs on every call of the operator (ranking the decode
 // shapes costs a few microseconds of host time - as much as the kernel it plans): memoise the last results
 // per host thread.  thread_local, so there is still no shared mutable state.
@@ -1227,10 +1299,10 @@ struct PlanKey {
     Ovr ov;
     bool operator==(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) == 0; }
 };
-struct PlanEntry { PlanKey key; int rc; Planned plan; flute_template_info tinfo; bool valid; };
+struct PlanEntry { PlanKey key; int rc; Planned plan; bool valid; };     // the plan with its kernel pointers
 
 int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_id, int num_sms,
-              size_t workspace_bytes, const Ovr& ov, Planned* out, flute_template_info* tinfo = nullptr) {
+              size_t workspace_bytes, const Ovr& ov, Planned* out) {
     constexpr int kEntries = 32;
     thread_local PlanEntry cache[kEntries] = {};
     thread_local int next = 0;
@@ -1241,7 +1313,7 @@ int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_
     for (int i = 0; i < kEntries; ++i) {
         const PlanEntry& e = cache[i];
         if (e.valid && e.key == key) {
-            if (e.rc == FLUTE_OK) { *out = e.plan; if (tinfo) *tinfo = e.tinfo; }
+            if (e.rc == FLUTE_OK) *out = e.plan;
             return e.rc;
         }
     }
@@ -1250,44 +1322,13 @@ int make_plan(int dtype, int bits, int group, int M, int N, int K, int template_
     e.valid = false;
     e.key = key;
     e.plan = Planned{};
-    e.rc = make_plan_uncached(dtype, bits, group, M, N, K, template_id, num_sms, workspace_bytes, ov, &e.plan, &e.tinfo);
+    e.rc = make_plan_uncached(dtype, bits, group, M, N, K, template_id, num_sms, workspace_bytes, ov, &e.plan);
     e.valid = true;
-    if (e.rc == FLUTE_OK) { *out = e.plan; if (tinfo) *tinfo = e.tinfo; }
+    if (e.rc == FLUTE_OK) *out = e.plan;
     return e.rc;
 }
 
 // ---- launching a plan ---------------------------------------------------------------------------------------
-
-// each family's kernel for a bit width and dtype (nullptr: not instantiated)
-StreamKernel stream_kernel(int bits, int dtype, int tile_p, int mb, int depth) {
-    if (bits == 4) return stream_kernel_b4(dtype, tile_p, mb, depth, 0);
-    if (bits == 3) return stream_kernel_b3(dtype, tile_p, mb, depth, 0);
-    return stream_kernel_b2(dtype, tile_p, mb, depth, 0);
-}
-OneKernel oneshot_kernel(int bits, int dtype, int tile_p, int mb, int depth, int had, int pipe) {
-    if (bits == 4) return dtype == 0 ? oneshot_kernel_b4_f16(tile_p, mb, depth, had, pipe) : oneshot_kernel_b4_bf16(tile_p, mb, depth, had, pipe);
-    if (bits == 2) return dtype == 0 ? oneshot_kernel_b2_f16(tile_p, mb, depth, had, pipe) : oneshot_kernel_b2_bf16(tile_p, mb, depth, had, pipe);
-    return oneshot_kernel_b3(dtype, tile_p, mb, depth, had, pipe);
-}
-PersistKernel persist_kernel(int bits, int dtype, int tile_p, int mb, int depth, int nsets, int had) {
-    if (bits == 4) return persist_kernel_b4(dtype, tile_p, mb, depth, nsets, had);
-    if (bits == 2) return persist_kernel_b2(dtype, tile_p, mb, depth, nsets, had);
-    return persist_kernel_b3(dtype, tile_p, mb, depth, nsets, had);
-}
-PersistMKernel persistm_kernel(int bits, int dtype, int tile_p, int lg, int ng, int xr, int waves, int xres) {
-    if (bits == 4) return dtype == 0 ? persistm_kernel_b4_f16(tile_p, lg, ng, xr, waves, xres) : persistm_kernel_b4_bf16(tile_p, lg, ng, xr, waves, xres);
-    return dtype == 0 ? persistm_kernel_b2_f16(tile_p, lg, ng, xr, waves, xres) : persistm_kernel_b2_bf16(tile_p, lg, ng, xr, waves, xres);
-}
-BlockKernel block_kernel(int bits, int dtype, int tile_p, int cfg) {
-    if (bits == 4) return block_kernel_b4(dtype, tile_p, cfg);
-    if (bits == 3) return block_kernel_b3(dtype, tile_p, cfg);
-    return block_kernel_b2(dtype, tile_p, cfg);
-}
-QGemmKernel tile_kernel(int bits, int dtype, int tile_p, int mblk, int mtiles, int sw) {
-    if (bits == 4) return tile_kernel_b4(dtype, tile_p, mblk, mtiles, sw);
-    if (bits == 3) return tile_kernel_b3(dtype, tile_p, mblk, mtiles);
-    return tile_kernel_b2(dtype, tile_p, mblk, mtiles);
-}
 
 // (device, kernel) pairs already granted > 64 KB of dynamic LDS: the attribute is per device, and one
 // process may drive several GPUs (accelerate-style sharded inference)
@@ -1311,12 +1352,9 @@ int ensure_lds(const void* fn, size_t bytes) {
     return 0;
 }
 
-// One kernel launch of a plan: its grid, block and dynamic LDS (granted first where it exceeds 64 KB).  A kernel that is
-// not instantiated is FLUTE_ERR_TEMPLATE_ID.
-template <class Kernel>
-int launch(Kernel fn, const flute_plan& p, void** kargs, hipStream_t st) {
-    const void* f = reinterpret_cast<const void*>(fn);
-    if (!f) return FLUTE_ERR_TEMPLATE_ID;
+// One launch of a plan's kernel (resolve_kernel; the one plan without a kernel does not come this far): its grid, block and
+// dynamic LDS (granted first where it exceeds 64 KB).
+int launch(const void* f, const flute_plan& p, void** kargs, hipStream_t st) {
     if (ensure_lds(f, p.lds_bytes)) return FLUTE_ERR_LAUNCH;
     if (hipLaunchKernel(f, dim3(p.grid), dim3(p.block), kargs, p.lds_bytes, st) != hipSuccess) {
         (void)hipGetLastError();
@@ -1438,10 +1476,9 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
     if (hadamard_size > 1 && (hadamard_size & (hadamard_size - 1))) return FLUTE_ERR_HADAMARD_SIZE;
     // everything is validated before anything is enqueued
     Planned pl;
-    flute_template_info t;
     if (!workspace) workspace_bytes = 0;
     const int rc = make_plan(dtype, num_bits, group_size, M, N, K, template_id, num_sms, workspace_bytes,
-                             hadamard_ovr(ovr_of(ovr), hadamard_size, M, K), &pl, &t);
+                             hadamard_ovr(ovr_of(ovr), hadamard_size, M, K), &pl);
     if (rc) return rc;
     if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
     if (!A || !Q || !D || !S || !QM2) return FLUTE_ERR_NULL;
@@ -1463,9 +1500,8 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         }
     }
     float had_scale = 1.0f / sqrtf((float)(1 << had_log));     // as flute_hadamard: bit-identical results
-    int had = had_log > 0 ? 1 : 0;
+    const void* fn = had_log > 0 && pl.fn_had ? pl.fn_had : pl.fn;      // the plan's kernel; what follows packs its arguments
 
-    const int tp = t.tile_p;
     const uint32_t* q32 = reinterpret_cast<const uint32_t*>(Q);
     const uint32_t* qm2 = reinterpret_cast<const uint32_t*>(QM2);
     // workspace: the xwg state words, the fp32 slabs behind them
@@ -1478,8 +1514,6 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
     };
 
     if (p.family == 0 && p.one_shot == 3) {              // persistent one-shot kernel
-        PersistKernel fn = persist_kernel(num_bits, dtype, tp, p.m_block, oa.depth, oa.nsets, had);
-        if (!fn) return FLUTE_ERR_SHAPE;
         uint32_t geo = PersistGeo::pack(oa.lg, p.waves, oa.nch, oa.ipw, had_log, oneshot_x_in_holes(num_bits, p.m_block, K) ? 1 : 0, M);
         int nvis = oa.nvis, nwg = oa.nwg;
         void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &nvis, &D, &had_scale, &nwg};
@@ -1489,13 +1523,13 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         int lg = oa.lg;
         uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
         void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &lg, &M, &stamps};
-        return launch(fast_kernel_b4(dtype, tp, p.waves, p.kw, p.ring_depth, p.m_block), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == 0 && p.one_shot) {                   // one-shot kernel
         uint32_t geo = OneGeo::pack(oa.lg, oa.lkw, oa.upw, oa.pk, oa.ipw, had_log, oneshot_x_in_holes(num_bits, p.m_block, K) ? 1 : 0);
         uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
         void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &had_scale, &stamps};
-        return launch(oneshot_kernel(num_bits, dtype, tp, p.m_block, oa.depth, had, oa.pipe), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == 0) {                                 // ring kernel
         StreamArgs sa = pl.sa;
@@ -1503,23 +1537,23 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         sa.partial = partial;
         sa.had_log = had_log; sa.had_scale = had_scale; sa.m0 = 0;
         void* kargs[] = {&sa};
-        return then_reduce(launch(stream_kernel(num_bits, dtype, tp, p.m_block, p.ring_depth), p, kargs, st));
+        return then_reduce(launch(fn, p, kargs, st));
     }
     if (p.family == kFamilySkinny) {
         uint32_t geo = SkinnyGeo::pack(oa.lg, oa.lkw, oa.ipw, p.splitk);
         uint64_t* stamps = stamps_at(workspace, workspace_bytes, p.workspace_needed ? p.workspace_needed : kXwgFlagBytes, p);   // behind the slabs
         void* kargs[] = {&q32, &S, &A, &qm2, &K, &N, &geo, &M, &D, &stamps, &partial, &state};
-        return launch(skinny_kernel_b4(dtype, tp, oa.depth), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == kFamilyFastM) {
         uint64_t* stamps = stamps_at(workspace, workspace_bytes, kXwgFlagBytes, p);
         void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &M, &stamps};
-        return launch(fastm_kernel_b4(dtype, tp, p.waves, p.ring_depth, oa.lg, p.slabs_per_wave), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == kFamilyPersistM) {
         int nsets = ceil_div(N / 16, p.slabs_per_wave);
         void* kargs[] = {&q32, &S, &A, &qm2, &D, &N, &K, &M, &nsets};
-        return launch(persistm_kernel(num_bits, dtype, tp, oa.lg, p.slabs_per_wave, p.k_chunks, p.waves, p.one_shot), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == kFamilySplitK) {
         SplitKArgs b;
@@ -1540,7 +1574,7 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
             b.pair_c8 = ((b.tiles_m / E) * (N / tile_cols)) & ~7;
         }
         void* kargs[] = {&b};
-        return launch(splitk_kernel(num_bits, dtype, tp, p.m_tiles, p.kw), p, kargs, st);
+        return launch(fn, p, kargs, st);
     }
     if (p.family == kFamilyBlock) {
         BlockArgs b;
@@ -1556,7 +1590,7 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         b.order = (b.tiles_m % 8 == 0) ? 1 : ((b.tiles_n % 8 == 0) ? 2 : 0);
         b.state = (p.splitk > 1 && p.splitk_mode == 1) ? state : nullptr;
         void* kargs[] = {&b};
-        return then_reduce(launch(block_kernel(num_bits, dtype, tp, p.m_block), p, kargs, st));
+        return then_reduce(launch(fn, p, kargs, st));
     }
 
     QGemmArgs a;                                         // per-wave MFMA kernel
@@ -1582,7 +1616,8 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
         a.geo[5] = (((int)p.grid / p.splitk / a.geo[4]) % 8 == 0 && (long)M * 32 <= (long)num_bits * N) ? 1 : 0;
     }
     void* kargs[] = {&a};
-    return then_reduce(launch(tile_kernel(num_bits, dtype, tp, p.m_block, p.m_tiles, p.slabs_per_wave), p, kargs, st));
+    if (!fn) return FLUTE_ERR_TEMPLATE_ID;               // override m_block = 3 (resolve_kernel)
+    return then_reduce(launch(fn, p, kargs, st));
 }
 
 int flute_hadamard(int dtype, const void* in, void* out, size_t numel, uint32_t had_size,

@@ -1,4 +1,6 @@
-// Kernel lookup tables filled by the per-bit-width instantiation units.
+// Kernel lookups defined by the instantiation units (inst_*.hip), one row list per family and unit: the entry point of a
+// shape, nullptr where that shape is not built.  api.hip asks them while it plans (which shapes exist) and once more when
+// the plan is made (resolve_kernel: a plan without a built kernel is refused there, FLUTE_ERR_TEMPLATE_ID); a launch looks nothing up.
 #pragma once
 #include "common.h"
 
@@ -6,12 +8,12 @@ namespace flute_amd {
 
 typedef void (*QGemmKernel)(const QGemmArgs);
 
-// streaming decode kernel (qgemm_stream.h): mb rows per pass (1/2/4; b=3: 1/2), depth = ring slots (2/4), one_shot = the no-refill variant (b=2/4: depth 4, b=3: depth 2)
+// streaming decode kernel (qgemm_stream.h): mb rows per pass (1/2/4), depth = ring slots (2/4; b=3: 2)
 struct StreamArgs;
 typedef void (*StreamKernel)(const StreamArgs);
-StreamKernel stream_kernel_b4(int dtype, int tile_p, int mb, int depth, int one_shot);
-StreamKernel stream_kernel_b3(int dtype, int tile_p, int mb, int depth, int one_shot);
-StreamKernel stream_kernel_b2(int dtype, int tile_p, int mb, int depth, int one_shot);
+StreamKernel stream_kernel_b4(int dtype, int tile_p, int mb, int depth);
+StreamKernel stream_kernel_b3(int dtype, int tile_p, int mb, int depth);
+StreamKernel stream_kernel_b2(int dtype, int tile_p, int mb, int depth);
 // one-shot decode kernel (qgemm_oneshot.h): mb rows per pass (1/2/4; b=3: 1/2), depth = pieces per wave (4/8; b=3: 2/4), had = fused
 // Hadamard pre-rotation, pipe = software-pipelined lookup groups (every wave of the launch holds `depth` whole pieces)
 typedef void (*OneKernel)(const uint32_t*, const void*, const void*, const uint32_t*, int, int, uint32_t, int, void*, float, uint64_t*);

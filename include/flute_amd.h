@@ -213,7 +213,10 @@ int flute_qgemm_ex(int dtype, int num_bits, int group_size, int hadamard_size, i
                    const void* QM2, void* x_scratch, void* workspace, size_t workspace_bytes,
                    int template_id, int num_sms, const flute_overrides* ovr, void* stream);
 
-/* The plan flute_qgemm would use (exposed for tests and the offline tuner). */
+/* The plan flute_qgemm would use (exposed for tests and the offline tuner).  A plan is resolved to its kernel when it is made:
+ * FLUTE_OK here (and 1 from flute_qgemm_hadamard_fused) means a kernel that is built, and a shape no kernel is instantiated for
+ * is FLUTE_ERR_TEMPLATE_ID here as in flute_qgemm - no GPU needed.  (One exception, kept as it was: the override m_block = 3 of
+ * the per-wave MFMA kernel plans, and the launch refuses it with FLUTE_ERR_TEMPLATE_ID.) */
 int flute_qgemm_plan(int dtype, int num_bits, int group_size, int M, int N, int K,
                      int template_id, int num_sms, size_t workspace_bytes, flute_plan* out);
 int flute_qgemm_plan_ex(int dtype, int num_bits, int group_size, int M, int N, int K,

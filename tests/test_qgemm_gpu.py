@@ -1018,6 +1018,66 @@ def test_qgemm_hadamard_fused_equals_two_launches(env):
         assert torch.equal(out, two), (M, h)
 
 
+def test_cached_plan_entries_keep_their_kernel(env):
+    """A plan is cached with its kernel's entry point (32 entries per host thread, replaced in turn): more than three times as
+    many distinct calls, so that every entry is evicted and reused, each checked against the oracle - and in a second pass, in
+    another order, every call returns the bits of its first.  Small layers (N = 512, K = 512 / 1024, group 64), 2 / 3 / 4 bits
+    under an id that leaves the kernel to the planner, both dtypes, M = 1 .. 64; at M = 1 the plain call is followed by the
+    fused rotation (Hadamard 512) and, where 1024 divides K, the two-launch rotation (Hadamard 1024) of the same layer.  On
+    layers this small the automatic ids reach the decode and the per-wave kernels only (families 0 and 2, whatever the CU
+    count), so the 4-bit K = 1024 layers are also called at M = 5, 16 under the id that asks for the skinny MFMA kernel
+    (QuantMapMode digit 3, family 5)."""
+    d = env.dev
+    lib = env.fa._lib.get()
+    N, g, tile_p = 512, 64, 32
+    calls, families, fused_seen = [], set(), set()
+    for bits in (4, 3, 2):
+        auto_id = template_ids_for(env.fa, bits, tile_p)[0]
+        for K in (512, 1024):
+            for dtype in (torch.float16, torch.bfloat16):
+                dt = 0 if dtype == torch.float16 else 1
+                W, Q, S, table, table2 = make_case(env, bits, tile_p, g, dtype, K, N, seed=bits * 100 + K // 512 + dt)
+                layer = dict(dev=[t.to(d) for t in (Q, S, table, table2)], bits=bits, dtype=dtype,
+                             What=env.O.dequantize(Q.numpy(), S, table2, bits, g, tile_p).float())
+                shapes = [(M, auto_id, 0) for M in (1, 2, 3, 5, 16, 17, 33, 64)]
+                shapes[1:1] = [(1, auto_id, h) for h in (512, 1024) if K % h == 0]
+                if bits == 4 and K == 1024:
+                    shapes += [(M, auto_id + 3, 0) for M in (5, 16)]
+                for M, tid, h in shapes:
+                    calls.append((layer, M, tid, h, (torch.randn(M, K) / 10).to(dtype)))
+                    if h:
+                        fused_seen.add(lib.flute_qgemm_hadamard_fused(dt, bits, g, h, M, N, K, tid, env.num_sms, env.ws.numel()))
+                    else:
+                        p = env.fa._lib.Plan()
+                        assert lib.flute_qgemm_plan(dt, bits, g, M, N, K, tid, env.num_sms, env.ws.numel(), p) == 0
+                        families.add(p.family)
+    assert len(calls) > 3 * 32
+    assert {0, 2} <= families and families & {5, 6, 7, 8}, families
+    assert fused_seen == {0, 1}, fused_seen
+
+    def run(call):
+        layer, M, tid, h, X = call
+        Qd, Sd, td, t2d = layer["dev"]
+        if h:
+            return env.fa.qgemm_hadamard(X.to(d), Qd, Sd, td, t2d, env.ws, layer["bits"], g, h, tid, env.num_sms).cpu()
+        return env.fa.qgemm(X.to(d), Qd, Sd, td, t2d, env.ws, layer["bits"], g, tid, env.num_sms).cpu()
+
+    first = []
+    for call in calls:
+        layer, M, tid, h, X = call
+        out = run(call)
+        Xr = env.O.hadamard_transform(X, h) if h else X
+        ref = (Xr.float() @ layer["What"]).to(layer["dtype"])
+        err = rel_err(out, ref)
+        assert err < tol_of(layer["dtype"]), (layer["bits"], layer["dtype"], M, tid, h, err)
+        first.append(out)
+    order = torch.randperm(len(calls), generator=torch.Generator().manual_seed(7)).tolist()
+    assert order != list(range(len(calls)))
+    for i in order:
+        layer, M, tid, h, X = calls[i]
+        assert torch.equal(run(calls[i]), first[i]), (layer["bits"], layer["dtype"], M, tid, h)
+
+
 # ---------------------------------------------------------------------------
 # boundary behaviour
 # ---------------------------------------------------------------------------
