@@ -37,6 +37,8 @@ qgemm_grouped_input_grad = ops.qgemm_grouped_input_grad
 # the gradient of a stack's scales [E, N, K / g], one launch over the same device-side row table; the entry points that train
 # the experts' scales through it: flute_amd.integrations.learnable.qgemm_grouped*_learnable_scales, make_experts_learnable
 qgemm_grouped_scale_grad = ops.qgemm_grouped_scale_grad
+qgemm_grouped_table_grad = ops.qgemm_grouped_table_grad
+grouped_pair_grad_to_table_grad = ops.grouped_pair_grad_to_table_grad
 # the routing around them, one launch each: the router's choice [T, k] -> offsets, rows, row_weight, pos, perm (a stable
 # counting sort on the device), and the sorted rows of the down projection summed per token in fp32 with one rounding
 moe_route = ops.moe_route

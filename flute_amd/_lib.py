@@ -67,6 +67,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_input_grad": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p]),
     "flute_qgemm_grouped_input_grad_row_block": (c_int, []),
     "flute_qgemm_grouped_scale_grad": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_table_grad": (c_int, [c_int] * 9 + [c_void_p] * 10 + [c_size_t, c_int, c_void_p]),
+    "flute_qgemm_grouped_table_grad_scratch_bytes": (c_size_t, [c_int] * 5),
     "flute_moe_route": (c_int, [c_int] * 5 + [c_void_p] * 7 + [c_void_p]),
     "flute_moe_combine": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
     "flute_moe_gate": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 4 + [c_void_p]),

@@ -1788,6 +1788,40 @@ int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int 
                                        dS, st);
 }
 
+int flute_qgemm_grouped_table_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
+                                   const void* S, const void* QM2, const float* row_weight, float* dT2, void* dS,
+                                   void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
+    if (rc) return rc;
+    if (l.t.tile_p != 32 && l.t.tile_p != 64) return FLUTE_ERR_TEMPLATE_ID;
+    // flute_qgemm_grouped_scale_grad's limits: the block is 128 n, the grid's z (the reduce's y) is the expert, a row index plus one step is an int
+    if (N % 128 || E > 65535 || R > 0x7fffffff - 64) return FLUTE_ERR_SHAPE;
+    if (E == 0) return FLUTE_OK;                                   // dT2 and dS have no element
+    if (!dT2 || !scratch || (dS && !QM2)) return FLUTE_ERR_NULL;
+    if (scratch_bytes < table_grad_grouped_scratch_bytes(num_bits, E, N, K)) return FLUTE_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (R == 0) {                                                  // no expert has a row: zeros, as the kernels write them
+        const size_t t_bytes = (size_t)E * ((size_t)2 << (2 * num_bits)) * 4;
+        if (hipMemsetAsync(dT2, 0, t_bytes, st) != hipSuccess) return FLUTE_ERR_LAUNCH;
+        if (dS && hipMemsetAsync(dS, 0, (size_t)E * (size_t)N * (size_t)(K >> l.lg) * 2, st) != hipSuccess)
+            return FLUTE_ERR_LAUNCH;
+        return FLUTE_OK;
+    }
+    if (!dY || !X || !offsets || !Q || !S) return FLUTE_ERR_NULL;
+    (void)num_sms;                                                 // the grid is (N / 128, ceil(K / 256), E): from the shapes alone
+    return table_grad_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, N, K, P, dY, X, offsets, Q, S, QM2,
+                                       row_weight, dT2, dS, scratch, st);
+}
+
+size_t flute_qgemm_grouped_table_grad_scratch_bytes(int num_bits, int group_size, int E, int N, int K) {
+    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return 0;
+    if (group_size != 32 && group_size != 64 && group_size != 128 && group_size != 256) return 0;
+    if (E < 1 || E > 65535 || N < 1 || K < 1 || N % 128 || K % std::max(64, group_size)) return 0;
+    return table_grad_grouped_scratch_bytes(num_bits, E, N, K);
+}
+
 int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
                     int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
     if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;

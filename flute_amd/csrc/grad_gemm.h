@@ -1,5 +1,5 @@
-// G = X^T dY reduced over M, the GEMM both parameter gradients of a packed layer share (scale_grad.hip, table_grad.hip),
-// and the scale gradient's epilogue on it.
+// G = X^T dY reduced over M, the GEMM both parameter gradients of a packed layer share (scale_grad.hip, table_grad.hip
+// and their grouped forms), and the scale gradient's and the table gradient's epilogues on it.
 //
 // A workgroup of 8 waves owns a 256 (k) x 128 (n) block - whole groups up to g = 256 - and walks its M range in steps
 // of 32 rows: both operand tiles are copied row-major into LDS (16 B per lane, coalesced; rows past the range and
@@ -25,6 +25,8 @@ constexpr int kSgYBytes = kSgBM * kSgYPitch;
 constexpr int kSgLut = 2 * (kSgXBytes + kSgYBytes); // pair table behind the two operand buffers
 constexpr int kSgLds = kSgLut + 4 * 256;
 constexpr int kSgMinSteps = 4;                      // fewest 32-row steps a split of M gets
+constexpr int kTgBinsAt = 4096;                     // the table gradient's wave bins: behind the scale epilogue's 4 KB of chunk sums
+static_assert(kTgBinsAt + 8 * 2 * 256 * 4 <= kSgLut, "wave bins fit in the operand buffers");
 
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
@@ -190,6 +192,71 @@ __device__ __forceinline__ void scale_grad_epilogue(char* smem, const uint32_t* 
         const size_t o = (size_t)(nb + nl) * G + (kb >> lg) + jg;
         if (pout) pout[o] = v;
         else dS[o] = Num<T>::from_float(v);
+    }
+}
+
+// The block's groups below K of a scale gradient as zeros: what a workgroup of the grouped kernels writes for an expert
+// without rows, in scale_grad_epilogue's place.
+__device__ __forceinline__ void scale_grad_zero_block(uint16_t* __restrict__ dS, int N, int K, int lg, int nb, int kb) {
+    const int G = K >> lg;
+    const int lgb = 8 - lg;
+    for (int it = threadIdx.x; it < (kSgBN << lgb); it += kSgThreads) {
+        const int nl = it >> lgb, jg = it & ((1 << lgb) - 1);
+        if (kb + (jg << lg) >= K) continue;
+        dS[(size_t)(nb + nl) * G + (kb >> lg) + jg] = 0;
+    }
+}
+
+// The table gradient from the accumulators (table_grad.hip describes it): every wave zeroes its 4^b x 2 fp32 bins at
+// smem + kTgBinsAt, decodes the pair index behind each accumulator pair, multiplies both accumulators by the group's
+// scale S[n, k / g] in fp32 and adds them into its bins with ds_add_f32; after a barrier the 8 waves' bins are summed in
+// wave order into t_out [4^b][2], the workgroup's partial.  With dS non-null (uniform) the scale gradient is written in
+// between, by scale_grad_epilogue with `lut`, dS and pout: its chunk sums lie below the bins.
+template <typename T, int BITS, int TILEP>
+__device__ __forceinline__ void table_grad_epilogue(char* smem, const uint32_t* lut, const f32x4_t (&acc)[4][4],
+                                                    const uint32_t* __restrict__ Q, const uint16_t* __restrict__ S,
+                                                    uint16_t* __restrict__ dS, float* __restrict__ pout,
+                                                    float* __restrict__ t_out, int N, int K, int lg, int nb, int kb) {
+    using L = Layout<BITS>;
+    constexpr int NB = 2 * L::LUT_N;                  // bins
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));                     // opaque: what the epilogue derives from it is computed here, not kept across the mainloop
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wk = wave & 3, wn = wave >> 2, h = lane >> 4;
+    float* all_bins = reinterpret_cast<float*>(smem + kTgBinsAt);
+    float* bins = all_bins + wave * NB;               // this wave's alone until the barrier
+    for (int i = lane; i < NB; i += 64) bins[i] = 0.f;
+
+    const int K2 = K >> 1, G = K >> lg;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int n = nb + wn * 64 + nt * 16 + (lane & 15);
+        const GradColumn<BITS, TILEP> col(n);
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            const int k0 = kb + wk * 64 + kt * 16 + 4 * h;
+            if (k0 < K) {                             // columns past K hold zeros; their codes are not read
+                uint2 w2[GradColumn<BITS, TILEP>::NP];
+                col.words(Q, N, K2, k0, w2);
+                const float s = Num<T>::to_float(S[(size_t)n * G + (k0 >> lg)]);   // 4 k of one group: g >= 32
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    float* bin = bins + 2 * col.index(w2, e);
+                    __hip_atomic_fetch_add(bin, acc[kt][nt][2 * e] * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(bin + 1, acc[kt][nt][2 * e + 1] * s, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+
+    if (dS) scale_grad_epilogue<T, BITS, TILEP>(smem, lut, acc, Q, dS, pout, N, K, lg, nb, kb);   // uniform: it holds a barrier
+    __syncthreads();
+    for (int i = tid; i < NB; i += kSgThreads) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) v += all_bins[w * NB + i];
+        t_out[i] = v;
     }
 }
 

@@ -105,6 +105,14 @@ FLUTE_IG_DISPATCH(2);
 int scale_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int N, int K, int P,
                                 const void* dY, const void* X, const void* offsets, const void* Q, const void* QM2,
                                 const void* row_weight, void* dS, hipStream_t stream);
+// the gradient of the stacks' lookup tables dT2 [E, 4^b, 2] fp32 (table_grad_grouped.hip): table_grad.hip's mainloop and epilogue per expert
+// over the row range the kernel reads from offsets, then a per-expert fp64 reduce of the workgroups' partials in the scratch, which holds
+// table_grad_grouped_scratch_bytes (the only place its size is computed); with dS non-null also the scale gradient, as scale_grad_grouped_dispatch's
+size_t table_grad_grouped_scratch_bytes(int num_bits, int E, int N, int K);
+int table_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int N, int K, int P,
+                                const void* dY, const void* X, const void* offsets, const void* Q, const void* S,
+                                const void* QM2, const void* row_weight, float* dT2, void* dS, void* scratch,
+                                hipStream_t stream);
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

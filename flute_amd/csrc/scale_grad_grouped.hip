@@ -36,12 +36,7 @@ __global__ __launch_bounds__(kSgThreads, 4) void scale_grad_grouped_kernel(
     uint16_t* __restrict__ dSe = dS + (size_t)e * (size_t)N * (size_t)G;
 
     if (re <= rb) {                                   // no rows: the block's groups below K as zeros, nothing of the expert read
-        const int lgb = 8 - lg;
-        for (int it = tid; it < (kSgBN << lgb); it += kSgThreads) {
-            const int nl = it >> lgb, jg = it & ((1 << lgb) - 1);
-            if (kb + (jg << lg) >= K) continue;
-            dSe[(size_t)(nb + nl) * G + (kb >> lg) + jg] = 0;
-        }
+        scale_grad_zero_block(dSe, N, K, lg, nb, kb);
         return;
     }
 

@@ -5,7 +5,8 @@
 // The table itself is not read.  With dS given the same launch also writes the scale gradient (scale_grad.hip) with
 // that kernel's own epilogue and split of M: bit for bit what flute_qgemm_scale_grad returns given its full scratch.
 //
-// The mainloop is grad_gemm.h's.  Epilogue: every wave owns 4^b x 2 fp32 bins in LDS (8 x 2 KB at 4 bits, in the
+// The mainloop and the epilogue (table_grad_epilogue, which table_grad_grouped.hip shares) are grad_gemm.h's.
+// Epilogue: every wave owns 4^b x 2 fp32 bins in LDS (8 x 2 KB at 4 bits, in the
 // operand buffers, free by then).  A lane decodes the pair index behind each accumulator pair, multiplies both
 // accumulators by the group's scale in fp32 and adds them into its wave's bins with ds_add_f32.  Only lanes of ONE wave
 // ever meet on a bin, inside one instruction, and a wave's LDS instructions complete in program order: nothing depends
@@ -31,9 +32,7 @@
 
 namespace flute_amd {
 
-constexpr int kTgBinsAt = 4096;                     // behind the scale epilogue's 4 KB of chunk sums
 constexpr int kTgRedBins = 32, kTgRedSlots = 32;    // the reduce pass: bins x workgroup slots per workgroup
-static_assert(kTgBinsAt + 8 * 2 * 256 * 4 <= kSgLut, "wave bins fit in the operand buffers");
 
 // (4 waves per SIMD = two workgroups per CU, as scale_grad_kernel reaches by itself: at most 128 VGPRs)
 template <typename T, int BITS, int TILEP>
@@ -48,8 +47,7 @@ __global__ __launch_bounds__(kSgThreads, 4) void table_grad_kernel(const uint16_
     using L = Layout<BITS>;
     constexpr int NB = 2 * L::LUT_N;                  // bins
     __shared__ __attribute__((aligned(16))) char smem[kSgLds];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wk = wave & 3, wn = wave >> 2, h = lane >> 4;
+    const int tid = threadIdx.x;
     const int nb = blockIdx.x * kSgBN, kb = blockIdx.y * kSgBK;
 
     uint32_t* lut = reinterpret_cast<uint32_t*>(smem + kSgLut);
@@ -61,45 +59,9 @@ __global__ __launch_bounds__(kSgThreads, 4) void table_grad_kernel(const uint16_
     f32x4_t acc[4][4];
     grad_gemm_mainloop<T>(smem, dY, X, N, K, nb, kb, m_begin, m_end, acc);
 
-    float* all_bins = reinterpret_cast<float*>(smem + kTgBinsAt);
-    float* bins = all_bins + wave * NB;               // this wave's alone until the barrier
-    for (int i = lane; i < NB; i += 64) bins[i] = 0.f;
-
-    const int K2 = K >> 1, G = K >> lg;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int n = nb + wn * 64 + nt * 16 + (lane & 15);
-        const GradColumn<BITS, TILEP> col(n);
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            const int k0 = kb + wk * 64 + kt * 16 + 4 * h;
-            if (k0 < K) {                             // columns past K hold zeros; their codes are not read
-                uint2 w2[GradColumn<BITS, TILEP>::NP];
-                col.words(Q, N, K2, k0, w2);
-                const float s = Num<T>::to_float(S[(size_t)n * G + (k0 >> lg)]);   // 4 k of one group: g >= 32
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    float* bin = bins + 2 * col.index(w2, e);
-                    __hip_atomic_fetch_add(bin, acc[kt][nt][2 * e] * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(bin + 1, acc[kt][nt][2 * e + 1] * s, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
-        }
-    }
-
-    if (dS) {                                         // uniform: the epilogue holds a barrier
-        float* pout = ds_part ? ds_part + (size_t)blockIdx.z * N * G : nullptr;
-        scale_grad_epilogue<T, BITS, TILEP>(smem, lut, acc, Q, dS, pout, N, K, lg, nb, kb);
-    }
-    __syncthreads();
+    float* pout = ds_part ? ds_part + (size_t)blockIdx.z * N * (K >> lg) : nullptr;   // (null without a dS)
     const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    for (int i = tid; i < NB; i += kSgThreads) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) v += all_bins[w * NB + i];
-        t_part[wg * NB + i] = v;
-    }
+    table_grad_epilogue<T, BITS, TILEP>(smem, lut, acc, Q, S, dS, pout, t_part + wg * NB, N, K, lg, nb, kb);
 }
 
 // dT2[bin] = sum over workgroups of part[wg][bin], in fp64 in a fixed order

@@ -21,7 +21,10 @@ gradient comes from `flute_amd.qgemm_table_grad`, in one launch with the scale g
 The experts of a mixture-of-experts layer train their scales the same way: `qgemm_grouped_learnable_scales`,
 `qgemm_grouped_glu_learnable_scales` and `qgemm_grouped_weighted_learnable_scales` are the three grouped ops with a
 gradient to the stacks' scales from `flute_amd.qgemm_grouped_scale_grad` (one launch per stack, the row counts stay on the
-device); the modules on them are `integrations.moe.make_experts_learnable` / `freeze_experts`.
+device).  Their lookup tables train too: `qgemm_grouped_learnable`, `qgemm_grouped_glu_learnable` and
+`qgemm_grouped_weighted_learnable` take a stack's fp32 master `codebook` ([E, 2^b] or [E, 2^b, 2^b, 2]) in `table2`'s
+place, and their backward adds one `flute_amd.qgemm_grouped_table_grad` launch per stack, which also carries the scale
+gradient when both train.  The modules on them are `integrations.moe.make_experts_learnable` / `freeze_experts`.
 
 Not registered by `install_as_flute()`: the reference's `flute.integrations.learnable` is its dense layer.
 """
@@ -287,7 +290,8 @@ def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, w
     _refuse_table_grad("qgemm_grouped_learnable_scales", table2)
     if not _ops._records_grad(input, scales):
         return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
-    return _ops._GroupedFunction.apply(input, scales, offsets, weight, table2, (num_bits, group_size, template_id, num_sms))
+    return _ops._GroupedFunction.apply(input, scales, None, offsets, weight, table2,
+                                       (num_bits, group_size, template_id, num_sms))
 
 
 def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
@@ -301,7 +305,7 @@ def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.
     if not _ops._records_grad(input, row_weight, scales):
         return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
                                                 template_id, num_sms)
-    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, offsets, weight, table2,
+    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2,
                                                (num_bits, group_size, template_id, num_sms))
 
 
@@ -319,5 +323,71 @@ def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tenso
         return flute_amd.qgemm_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
                                            up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
     _ops._validate_grouped_glu_pos(input, rows, pos)
-    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
-                                          up_weight, up_table2, (num_bits, group_size, template_id, num_sms))
+    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
+                                          gate_table2, up_weight, up_table2, (num_bits, group_size, template_id, num_sms))
+
+
+# ---- the experts' lookup tables: the same three functions with the codebook slot open.  `codebook` is a stack's fp32
+# master, [E, 2^b] (scalar tables: table2[e] = make_qmap2_from_qmap) or [E, 2^b, 2^b, 2] (pair codebooks); the entry point
+# rounds it to input.dtype, builds table2 and runs the unchanged launch - the public op's bits for that table2 - and the
+# gradient passes straight through the rounding, as in `_Learnable`.
+
+def _codebook_stack(name, codebook, num_bits, dtype, scales):
+    """The built table2 of a stack's codebook, validated: [E, ...] with the scales' E."""
+    try:
+        table2 = _ops._grouped_codebook_table2(codebook, num_bits, dtype)
+    except TypeError:
+        raise TypeError(f"{name}: the codebook is an fp32 master parameter") from None
+    if scales.ndim != 3 or table2.shape[0] != scales.shape[0]:
+        raise ValueError(f"{name}: the codebook's leading dimension is the stack's number of experts")
+    return table2
+
+
+def qgemm_grouped_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                            codebook: torch.Tensor, num_bits: int, group_size: int, template_id: int,
+                            num_sms=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped`, differentiable with respect to `input`, `scales` and the stack's fp32 master `codebook`.
+    The forward has the op's bits for the table2 built from the rounded codebook; the backward adds ONE
+    `qgemm_grouped_table_grad(dY, input, ...)` launch (with the scale gradient in it when the scales train too; a stack
+    that trains only scales keeps `qgemm_grouped_scale_grad`), folded per expert for the scalar form."""
+    table2 = _codebook_stack("qgemm_grouped_learnable", codebook, num_bits, input.dtype, scales)
+    _ops._validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    if not _ops._records_grad(input, scales, codebook):
+        return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
+    return _ops._GroupedFunction.apply(input, scales, codebook, offsets, weight, table2,
+                                       (num_bits, group_size, template_id, num_sms))
+
+
+def qgemm_grouped_weighted_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                                     scales: torch.Tensor, codebook: torch.Tensor, row_weight: torch.Tensor,
+                                     num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped_weighted`, differentiable with respect to `input`, `row_weight`, `scales` and the stack's
+    fp32 master `codebook`: `qgemm_grouped_weighted_learnable_scales` with the table gradient from
+    `qgemm_grouped_table_grad(dY, input, ..., row_weight=row_weight)`."""
+    table2 = _codebook_stack("qgemm_grouped_weighted_learnable", codebook, num_bits, input.dtype, scales)
+    _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    if not _ops._records_grad(input, row_weight, scales, codebook):
+        return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
+                                                template_id, num_sms)
+    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, codebook, offsets, weight, table2,
+                                               (num_bits, group_size, template_id, num_sms))
+
+
+def qgemm_grouped_glu_learnable(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
+                                gate_scales: torch.Tensor, gate_codebook: torch.Tensor, up_weight: torch.Tensor,
+                                up_scales: torch.Tensor, up_codebook: torch.Tensor, num_bits: int, group_size: int,
+                                template_id: int, num_sms=None, rows=None, pos=None) -> torch.Tensor:
+    """`flute_amd.qgemm_grouped_glu`, differentiable with respect to `input`, both stacks' scales and both stacks' fp32
+    master codebooks: `qgemm_grouped_glu_learnable_scales` with the table gradients from
+    `qgemm_grouped_table_grad(dg, x_sorted, ...)` for gate and `(du, x_sorted, ...)` for up, one launch per stack."""
+    gate_table2 = _codebook_stack("qgemm_grouped_glu_learnable", gate_codebook, num_bits, input.dtype, gate_scales)
+    up_table2 = _codebook_stack("qgemm_grouped_glu_learnable", up_codebook, num_bits, input.dtype, up_scales)
+    _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                               num_bits, group_size, rows)
+    if not _ops._records_grad(input, gate_scales, up_scales, gate_codebook, up_codebook):
+        return flute_amd.qgemm_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
+                                           up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
+    _ops._validate_grouped_glu_pos(input, rows, pos)
+    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, gate_codebook, up_codebook, rows, pos, offsets,
+                                          gate_weight, gate_table2, up_weight, up_table2,
+                                          (num_bits, group_size, template_id, num_sms))

@@ -28,14 +28,19 @@ The experts' scales train: `make_experts_learnable(model)` swaps every `GroupedF
 `LearnableGroupedFluteLinear` (its `scales` an `nn.Parameter`, the packed codes and tables shared) and `FluteExperts` then
 runs its three projections through `integrations.learnable.qgemm_grouped*_learnable_scales`, whose backward adds one
 `flute_amd.qgemm_grouped_scale_grad` launch per stack - the row counts stay on the device there too; `freeze_experts(model)`
-swaps back to plain stacks holding the learned scales.  The tables stay fixed, and the public `flute_amd.qgemm_grouped*`
-ops still raise on scales or tables that require grad.
+swaps back to plain stacks holding the learned scales.  Their lookup tables train too:
+`make_experts_learnable(model, scales=True, table="scalar" | "pair")` gives every stack an fp32 master `codebook`
+([E, 2^b] / [E, 2^b, 2^b, 2]) and the projections run through `qgemm_grouped*_learnable`, whose backward is one
+`flute_amd.qgemm_grouped_table_grad` launch per stack - scale gradient included - and `freeze_experts` writes the rounded
+codebooks into the plain stacks' `tables` / `tables2`.  The public `flute_amd.qgemm_grouped*` ops still raise on scales or
+tables that require grad.
 
     experts = FluteExperts.from_linears(gates, ups, downs)          # lists of E FluteLinear each
     out = experts(hidden, topk_ids, topk_weights)                   # [T, K], [T, k], [T, k] -> [T, K]
     fast = FluteExperts.from_linears(gates, ups, downs, fused=True) # the same MLP through the fused launches
     four = FluteExperts.from_linears(gates, ups, downs, fused=True, native_routing=True)   # moe_route -> glu -> weighted -> moe_combine
     params = make_experts_learnable(four); ...; freeze_experts(four)                        # train the experts' scales
+    params = make_experts_learnable(four, scales=True, table="scalar")                      # ... and their lookup tables
     out = four.forward_logits(hidden, router_logits, top_k=2, renormalize=True)            # moe_gate_route -> glu -> weighted -> moe_combine
     block = FluteSparseMoeBlock(router_weight, four, top_k=2, renormalize=True)             # [E, K] router, out = block(hidden)
     v3 = FluteSparseMoeBlock(router_weight, four, top_k=8, scoring="sigmoid", renormalize=True, bias=correction_bias,
@@ -43,14 +48,15 @@ ops still raise on scales or tables that require grad.
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 import flute_amd
 import flute_amd.utils
 from .base import FluteLinear
-from .learnable import (_swap, qgemm_grouped_glu_learnable_scales, qgemm_grouped_learnable_scales,
+from .learnable import (_swap, qgemm_grouped_glu_learnable, qgemm_grouped_glu_learnable_scales, qgemm_grouped_learnable,
+                        qgemm_grouped_learnable_scales, qgemm_grouped_weighted_learnable,
                         qgemm_grouped_weighted_learnable_scales)
 
 
@@ -140,44 +146,95 @@ def _share_grouped(new: torch.nn.Module, stack: GroupedFluteLinear, scales: torc
 
 
 class LearnableGroupedFluteLinear(GroupedFluteLinear):
-    """A `GroupedFluteLinear` whose `scales` [E, N, K / g] is an `nn.Parameter` (a copy); `weight`, `tables` and `tables2`
-    are the source stack's tensors, the state-dict keys are `GroupedFluteLinear`'s.  The forward is
-    `qgemm_grouped_learnable_scales`: the same launch, with a gradient to the scales from `qgemm_grouped_scale_grad`."""
+    """A `GroupedFluteLinear` whose scales and / or lookup tables train.  `scales=True` makes `scales` [E, N, K / g] an
+    `nn.Parameter` (a copy); `table="scalar"` / `"pair"` adds the fp32 parameter `codebook` ([E, 2^b] from `tables` /
+    [E, 2^b, 2^b, 2] from `tables2`), `None` keeps the tables fixed (no `codebook`).  `weight`, `tables` and `tables2` are
+    the source stack's tensors; without a codebook the state-dict keys are `GroupedFluteLinear`'s, with one `codebook`
+    comes next to `tables` / `tables2`, which are stale until `freeze_experts` writes the rounded codebook into new ones.
+    The forward is `qgemm_grouped_learnable_scales` / `qgemm_grouped_learnable`: the same launch, with the parameter
+    gradients from `qgemm_grouped_scale_grad` / `qgemm_grouped_table_grad`."""
 
-    def __init__(self, stack: GroupedFluteLinear) -> None:
+    def __init__(self, stack: GroupedFluteLinear, scales: bool = True, table: Optional[str] = None) -> None:
         if not isinstance(stack, GroupedFluteLinear):
             raise TypeError("LearnableGroupedFluteLinear wraps a GroupedFluteLinear")
+        if table not in ("scalar", "pair", None):
+            raise ValueError("table is 'scalar', 'pair' or None")
         torch.nn.Module.__init__(self)
-        _share_grouped(self, stack, torch.nn.Parameter(stack.scales.detach().clone()))
+        _share_grouped(self, stack, torch.nn.Parameter(stack.scales.detach().clone()) if scales else stack.scales)
+        self.table_mode = table
+        if table is None:
+            return                                    # the fixed tables: the stack's own `tables2`
+        n = 2 ** stack.num_bits
+        dtype = stack.scales.dtype
+        if table == "scalar":
+            if not torch.equal(flute_amd.ops._grouped_codebook_table2(stack.tables.float(), stack.num_bits, dtype),
+                               stack.tables2):
+                raise ValueError("table='scalar': an expert's tables2 is not the pair table of its tables "
+                                 "(pair codebooks train with table='pair')")
+            codebook = stack.tables.detach().float()
+        else:
+            codebook = stack.tables2.detach().contiguous().view(dtype).view(stack.num_experts, n, n, 2).float()
+        self.codebook = torch.nn.Parameter(codebook)
 
     def forward(self, x_sorted: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
         num_sms = self.num_sms if self.num_sms is not None else flute_amd.utils.get_device_num_sms(x_sorted.device)
-        return qgemm_grouped_learnable_scales(x_sorted, offsets, self.weight, self.scales, self.tables2, self.num_bits,
-                                              self.group_size, self.template_id, num_sms)
+        if self.table_mode is None:
+            return qgemm_grouped_learnable_scales(x_sorted, offsets, self.weight, self.scales, self.tables2,
+                                                  self.num_bits, self.group_size, self.template_id, num_sms)
+        return qgemm_grouped_learnable(x_sorted, offsets, self.weight, self.scales, self.codebook, self.num_bits,
+                                       self.group_size, self.template_id, num_sms)
 
 
-def make_experts_learnable(module: torch.nn.Module) -> List[torch.nn.Parameter]:
-    """Replace every `GroupedFluteLinear` below `module` by a `LearnableGroupedFluteLinear`, in place; returns the scale
-    parameters of all learnable stacks below `module`, in module order."""
+def make_experts_learnable(module: torch.nn.Module, scales: bool = True,
+                           table: Optional[str] = None) -> List[torch.nn.Parameter]:
+    """Replace every `GroupedFluteLinear` below `module` by a `LearnableGroupedFluteLinear(stack, scales, table)`, in
+    place; returns the parameters of all learnable stacks below `module` (scales, then codebook, per stack in module
+    order - with the defaults the scale parameters).  A stack that is learnable already is kept as it is when it was
+    made so with these `scales` and `table`, and refused otherwise (`freeze_experts` first): nothing is changed then."""
     if type(module) is GroupedFluteLinear:
         raise ValueError("make_experts_learnable swaps the stacks below a module: pass the module that holds it")
-    _swap(module, lambda m: LearnableGroupedFluteLinear(m) if type(m) is GroupedFluteLinear else m)
-    return [m.scales for m in module.modules() if isinstance(m, LearnableGroupedFluteLinear)]
+    if table not in ("scalar", "pair", None):
+        raise ValueError("table is 'scalar', 'pair' or None")
+    for m in module.modules():
+        if isinstance(m, LearnableGroupedFluteLinear) and \
+                (isinstance(m.scales, torch.nn.Parameter), m.table_mode) != (bool(scales), table):
+            raise ValueError("make_experts_learnable: a stack below the module is learnable already with scales=%s, table=%r; "
+                             "freeze_experts(module) first" % (isinstance(m.scales, torch.nn.Parameter), m.table_mode))
+    _swap(module, lambda m: LearnableGroupedFluteLinear(m, scales, table) if type(m) is GroupedFluteLinear else m)
+    params = []
+    for m in module.modules():
+        if isinstance(m, LearnableGroupedFluteLinear):
+            params += [p for p in (m.scales, getattr(m, "codebook", None)) if isinstance(p, torch.nn.Parameter)]
+    return params
 
 
 def _frozen_grouped(stack: LearnableGroupedFluteLinear) -> GroupedFluteLinear:
     new = GroupedFluteLinear.__new__(GroupedFluteLinear)
     torch.nn.Module.__init__(new)
     _share_grouped(new, stack, stack.scales.detach())
+    if stack.table_mode is not None:                  # new tensors: the source stack's buffers are not written
+        if stack.table_mode == "scalar":
+            new.tables = stack.codebook.detach().to(stack.scales.dtype)   # (pair codebooks keep `tables`: nothing reads it)
+        new.tables2 = flute_amd.ops._grouped_codebook_table2(stack.codebook, stack.num_bits, stack.scales.dtype)
     return new
 
 
 def freeze_experts(module: torch.nn.Module) -> None:
     """Replace every `LearnableGroupedFluteLinear` below `module` by a plain `GroupedFluteLinear` holding the learned
-    scales as its buffer, in place: the experts run the unchanged inference launches again."""
+    scales - and, where the tables trained, the codebook rounded to the stack's type as every forward rounded it, in
+    `tables` / `tables2` - as its buffers, in place: the experts run the unchanged inference launches again."""
     if isinstance(module, LearnableGroupedFluteLinear):
         raise ValueError("freeze_experts swaps the stacks below a module: pass the module that holds it")
     _swap(module, lambda m: _frozen_grouped(m) if isinstance(m, LearnableGroupedFluteLinear) else m)
+
+
+def _has_codebook(stack) -> bool:
+    return getattr(stack, "table_mode", None) is not None
+
+
+def _table_of(stack):
+    """What a fused entry point takes in the table's place: the stack's codebook where it has one, else `tables2`."""
+    return stack.codebook if _has_codebook(stack) else stack.tables2
 
 
 class FluteExperts(torch.nn.Module):
@@ -266,20 +323,28 @@ class FluteExperts(torch.nn.Module):
         gate, up, down = self.gate, self.up, self.down
         glu, weighted = self._fused_ops()
         num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-        h = glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight, up.scales,
-                up.tables2, gate.num_bits, gate.group_size, gate.template_id, num_sms,
+        h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales,
+                _table_of(up), gate.num_bits, gate.group_size, gate.template_id, num_sms,
                 rows=token.to(torch.int32))
-        y = weighted(h, offsets, down.weight, down.scales, down.tables2,
+        y = weighted(h, offsets, down.weight, down.scales, _table_of(down),
                      topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
                      down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)
 
     def _fused_ops(self):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
-        scales their gradient (with grad mode off those are the public ops)."""
-        if any(isinstance(m, LearnableGroupedFluteLinear) for m in (self.gate, self.up, self.down)):
-            return qgemm_grouped_glu_learnable_scales, qgemm_grouped_weighted_learnable_scales
-        return flute_amd.qgemm_grouped_glu, flute_amd.qgemm_grouped_weighted
+        scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
+        `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops)."""
+        gate, up, down = self.gate, self.up, self.down
+        has = [_has_codebook(m) for m in (gate, up, down)]
+        if has[0] != has[1]:
+            raise ValueError("FluteExperts: the fused forward needs gate and up both with or both without a codebook")
+        learnable = any(isinstance(m, LearnableGroupedFluteLinear) for m in (gate, up, down))
+        glu = qgemm_grouped_glu_learnable if has[0] else \
+            qgemm_grouped_glu_learnable_scales if learnable else flute_amd.qgemm_grouped_glu
+        weighted = qgemm_grouped_weighted_learnable if has[2] else \
+            qgemm_grouped_weighted_learnable_scales if learnable else flute_amd.qgemm_grouped_weighted
+        return glu, weighted
 
     def _forward_native(self, hidden, topk_ids, topk_weights):
         """`moe_route` (moe_route.hip) in place of sort_by_expert and its glue, `moe_combine` (moe_combine.hip) in place
@@ -294,10 +359,10 @@ class FluteExperts(torch.nn.Module):
         if self.fused:
             glu, weighted = self._fused_ops()
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-            h = glu(hidden, offsets, gate.weight, gate.scales, gate.tables2, up.weight,
-                    up.scales, up.tables2, gate.num_bits, gate.group_size, gate.template_id,
+            h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight,
+                    up.scales, _table_of(up), gate.num_bits, gate.group_size, gate.template_id,
                     num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
-            y = weighted(h, offsets, down.weight, down.scales, down.tables2, row_weight,
+            y = weighted(h, offsets, down.weight, down.scales, _table_of(down), row_weight,
                          down.num_bits, down.group_size, down.template_id, num_sms)
         else:
             x = hidden[rows]

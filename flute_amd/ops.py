@@ -1,14 +1,16 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
 `moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
 routing weights and router logits: when grad mode is on and such an input requires grad they run through a
 `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`, `moe_combine`
 and a few torch ops; otherwise they take exactly the path they always took.  Each of the three grouped ops has ONE such
-function, which also carries the gradient of the stacks' scales (`qgemm_grouped_scale_grad`): the ops themselves refuse
-packed stacks that require grad, `integrations.learnable` opens that slot.  Every validator of a packed layer or stack is
+function, which also carries the gradients of the stacks' scales (`qgemm_grouped_scale_grad`) and of their fp32 master
+codebooks (`qgemm_grouped_table_grad`): the ops themselves refuse packed stacks that require grad, `integrations.learnable`
+opens those slots.  Every validator of a packed layer or stack is
 three calls into one set of checks (`_check_ranks`, `_check_dtypes`, `_check_packed`), and every grouped launch -
-forward, input gradient, scale gradient - ends in `_launch_grouped`.
+forward, input gradient, scale gradient - ends in `_launch_grouped`; the table gradient alone, with its two results and its
+scratch, makes its call itself.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -304,6 +306,47 @@ def pair_grad_to_table_grad(dT2: torch.Tensor) -> torch.Tensor:
     return dT2[:, :, 0].sum(dim=1) + dT2[:, :, 1].sum(dim=0)
 
 
+def grouped_pair_grad_to_table_grad(dT2: torch.Tensor) -> torch.Tensor:
+    """`pair_grad_to_table_grad` per expert: the gradients [E, 2^b] of E scalar tables from `qgemm_grouped_table_grad`'s
+    [E, 2^b, 2^b, 2], dtable[e, i] = sum_j dT2[e, i, j, 0] + sum_j dT2[e, j, i, 1]."""
+    if dT2.ndim != 4 or dT2.shape[1] != dT2.shape[2] or dT2.shape[3] != 2:
+        raise ValueError
+    return dT2[..., 0].sum(-1) + dT2[..., 1].sum(-2)
+
+
+def _grouped_codebook_table2(codebook, num_bits, dtype):
+    """`table2` [E, 2^b, 2^b, 1] fp32 words of T pairs from a stack's fp32 master codebook rounded to T, in a number of
+    torch ops that does not depend on E: [E, 2^b] scalar tables give torch.stack([make_qmap2_from_qmap(t_e)]) bit for bit,
+    [E, 2^b, 2^b, 2] pair codebooks the rounded pairs viewed as words."""
+    n = 2 ** num_bits
+    if codebook.dtype != torch.float32:
+        raise TypeError("the codebook is an fp32 master parameter")
+    if codebook.ndim == 2 and codebook.shape[1] == n:
+        table = codebook.detach().to(dtype)
+        E = table.shape[0]
+        pairs = torch.stack([table[:, :, None].expand(E, n, n), table[:, None, :].expand(E, n, n)], dim=-1)
+    elif codebook.ndim == 4 and tuple(codebook.shape[1:]) == (n, n, 2):
+        pairs = codebook.detach().to(dtype)
+    else:
+        raise ValueError(f"codebook of shape {tuple(codebook.shape)}, expected (E, {n}) or (E, {n}, {n}, 2)")
+    return pairs.contiguous().view(torch.float32)
+
+
+def _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, layer, want_scales, want_codebook, scalar,
+                         row_weight=None):
+    """(d scales, d codebook) of one stack in a grouped backward: one `qgemm_grouped_table_grad` launch when the codebook
+    trains - with the scale gradient in it when the scales train too - else today's `qgemm_grouped_scale_grad`; the scalar
+    form folds per expert.  The gradient passes straight through the codebook's rounding."""
+    if not want_codebook:
+        d_scales = qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *layer, row_weight=row_weight) \
+            if want_scales else None
+        return d_scales, None
+    out = qgemm_grouped_table_grad(grad_output, input, offsets, weight, scales.detach(), *layer, table2=table2,
+                                   with_scale_grad=want_scales, row_weight=row_weight)
+    d_codebook, d_scales = out if want_scales else (out, None)
+    return d_scales, grouped_pair_grad_to_table_grad(d_codebook) if scalar else d_codebook
+
+
 def _records_grad(*tensors):
     """Whether a call on these inputs must record a graph: grad mode is on and a floating-point one requires grad."""
     return torch.is_grad_enabled() and any(t is not None and t.is_floating_point() and t.requires_grad for t in tensors)
@@ -387,32 +430,36 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, scales, offsets, weight, table2, layer)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer)
     return _launch_plain(input, offsets, weight, scales, table2, layer)
 
 
 class _GroupedFunction(torch.autograd.Function):
     """`qgemm_grouped` under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)
     and - for `integrations.learnable`; the op itself refuses scales that require grad -
-    dS = qgemm_grouped_scale_grad(dY, x), the only reader of the saved `input`."""
+    dS = qgemm_grouped_scale_grad(dY, x), the only reader of the saved `input`.  With `codebook` - a stack's fp32 master,
+    which `integrations.learnable` passes next to the `table2` it built from it (`_grouped_codebook_table2`) - the
+    backward's parameter gradients are `_grouped_table_grads`: one qgemm_grouped_table_grad launch for both."""
 
     @staticmethod
-    def forward(ctx, input, scales, offsets, weight, table2, layer):
+    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer):
         out = _launch_plain(input, offsets, weight, scales, table2, layer)
-        ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if ctx.needs_input_grad[1] else ()))
+        ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if any(ctx.needs_input_grad[1:3]) else ()))
         ctx.layer = layer
+        ctx.scalar = codebook is not None and codebook.ndim == 2
         return _zero_unserved_(out, offsets)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         offsets, weight, scales, table2, *saved_input = ctx.saved_tensors
-        d_input = d_scales = None
+        d_input = d_scales = d_codebook = None
         if ctx.needs_input_grad[0]:
             d_input = qgemm_grouped_input_grad(grad_output, offsets, weight, scales, table2, *ctx.layer)
-        if ctx.needs_input_grad[1]:
-            d_scales = qgemm_grouped_scale_grad(grad_output, saved_input[0], offsets, weight, table2, *ctx.layer)
-        return (d_input, d_scales) + (None,) * 4
+        if any(ctx.needs_input_grad[1:3]):
+            d_scales, d_codebook = _grouped_table_grads(grad_output, saved_input[0], offsets, weight, scales, table2,
+                                                        ctx.layer, *ctx.needs_input_grad[1:3], ctx.scalar)
+        return (d_input, d_scales, d_codebook) + (None,) * 4
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -457,8 +504,8 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
-        return _GroupedGluFunction.apply(input, gate_scales, up_scales, rows, pos, offsets, gate_weight, gate_table2,
-                                         up_weight, up_table2, layer)
+        return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
+                                         gate_table2, up_weight, up_table2, layer)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer)
 
 
@@ -467,10 +514,13 @@ class _GroupedGluFunction(torch.autograd.Function):
     g and u with two plain grouped launches on the gathered rows, forms dg = dh u sigma(g) (1 + g (1 - sigma(g))) and
     du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel.  For
     `integrations.learnable` (the op itself refuses scales that require grad) dS_gate = qgemm_grouped_scale_grad(dg,
-    x_sorted) and dS_up = (du, x_sorted), one launch per stack on the tensors the backward has formed."""
+    x_sorted) and dS_up = (du, x_sorted), one launch per stack on the tensors the backward has formed.  With `gc` / `uc` -
+    the stacks' fp32 master codebooks, which `gt` / `ut` were built from - each stack's parameter gradients are
+    `_grouped_table_grads` on the same operands."""
 
     @staticmethod
-    def forward(ctx, input, gs, us, rows, pos, offsets, gw, gt, uw, ut, layer):
+    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer):
+        ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
         out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer)
         ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
         ctx.has = (rows is not None, pos is not None)
@@ -485,12 +535,10 @@ class _GroupedGluFunction(torch.autograd.Function):
         pos = index[1] if ctx.has[1] else None
         dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
                                               want_input_grad=ctx.needs_input_grad[0])
-        d_gs = d_us = None
-        if ctx.needs_input_grad[1]:
-            d_gs = qgemm_grouped_scale_grad(dg, x, offsets, gw, gt, *ctx.layer)
-        if ctx.needs_input_grad[2]:
-            d_us = qgemm_grouped_scale_grad(du, x, offsets, uw, ut, *ctx.layer)
-        return (dx, d_gs, d_us) + (None,) * 8
+        want = ctx.needs_input_grad
+        d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
+        d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
+        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 8
 
 
 def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad):
@@ -532,7 +580,7 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
-        return _GroupedWeightedFunction.apply(input, row_weight, scales, offsets, weight, table2, layer)
+        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
 
 
@@ -541,27 +589,28 @@ class _GroupedWeightedFunction(torch.autograd.Function):
     epilogue (one launch); one that does takes dH' = input_grad(dY), d row_weight[r] = sum_k dH'[r, k] h[r, k] in fp32
     (zero from offsets[E] on) and dH = round_T(row_weight dH').  For `integrations.learnable` (the op itself refuses
     scales that require grad) dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight multiplies
-    dY where the kernel stages it."""
+    dY where the kernel stages it.  With `codebook` - the stack's fp32 master, which `table2` was built from - the
+    parameter gradients are `_grouped_table_grads` with the same row weight."""
 
     @staticmethod
-    def forward(ctx, input, row_weight, scales, offsets, weight, table2, layer):
+    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer):
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
         ctx.layer = layer
+        ctx.scalar = codebook is not None and codebook.ndim == 2
         return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         input, row_weight, offsets, weight, scales, table2 = ctx.saved_tensors
-        want_input, want_weight, want_scales = ctx.needs_input_grad[:3]
-        d_input = d_weight = d_scales = None
+        want_input, want_weight, want_scales, want_codebook = ctx.needs_input_grad[:4]
+        d_input = d_weight = None
         if want_input or want_weight:
             d_input, d_weight = _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, want_input,
                                                            want_weight)
-        if want_scales:
-            d_scales = qgemm_grouped_scale_grad(grad_output, input, offsets, weight, table2, *ctx.layer,
-                                                row_weight=row_weight)
-        return (d_input, d_weight, d_scales) + (None,) * 4
+        d_scales, d_codebook = _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, ctx.layer,
+                                                    want_scales, want_codebook, ctx.scalar, row_weight=row_weight)
+        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 4
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
@@ -667,6 +716,72 @@ def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     E, N = weight.shape[0], grad_output.shape[1]
     return _launch_grouped("qgemm_grouped_scale_grad", tensors, weight, (R,), N, (E, N, K // group_size),
                            (num_bits, group_size, template_id, num_sms), row_limit=2 ** 31 - 64)
+
+
+def _validate_grouped_table_grad(grad_output, input, offsets, weight, scales, table2, num_bits, group_size,
+                                 with_scale_grad, row_weight):
+    _check_ranks((grad_output, 2), (input, 2), (offsets, 1), (weight, 3), (scales, 3),
+                 *(((table2, 4),) if table2 is not None else ()))
+    _check_dtypes(input.dtype, like=(grad_output, scales), int16=(weight,),
+                  fp32=(table2,) if table2 is not None else (), int32=(offsets,))
+    E, N, K = weight.shape[0], grad_output.shape[1], input.shape[1]
+    _check_packed(weight, num_bits, group_size, N, K, lead=(E,), table2=table2, offsets=offsets, n_multiple=128)
+    if grad_output.shape[0] != input.shape[0] or tuple(scales.shape) != (E, N, K // group_size):
+        raise ValueError
+    if with_scale_grad and table2 is None:
+        raise ValueError("qgemm_grouped_table_grad: with_scale_grad needs table2 (the scale gradient reads the tables)")
+    if row_weight is not None:
+        _check_row_weight(row_weight, input.shape[0])
+
+
+def qgemm_grouped_table_grad(grad_output: torch.Tensor, input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                             scales: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None, *,
+                             table2=None, with_scale_grad: bool = False, row_weight=None):
+    """The gradient of the pair codebooks of `qgemm_grouped`'s stack with the codes fixed: `qgemm_table_grad` for every
+    expert over the rows the device-side table gives it, dT2[e, i, j, h] = sum over the pairs (kappa, n) of expert e with
+    codes (i, j) at rows (2 kappa, 2 kappa + 1) of sum_{r in [offsets[e], offsets[e + 1])} dYw[r, n] * input[r, 2 kappa + h]
+    * scales[e, n, 2 kappa / g], as [E, 2^b, 2^b, 2] fp32; `grouped_pair_grad_to_table_grad` folds it for scalar tables.
+    `grad_output` [R, N] and `input` [R, K] hold the rows sorted by expert; `offsets`, `weight` [E, P, K] and `scales`
+    [E, N, K / g] as `qgemm_grouped` takes them; dYw is `grad_output`, or with `row_weight` [R] fp32
+    round_T(row_weight[r] * grad_output[r, n]) (the product in fp32).  The tables are not read.  With `with_scale_grad`
+    (needs `table2` [E, 2^b, 2^b, 1]) the same launch also computes the stack's scale gradient and (dT2, dS) is returned,
+    dS bit for bit `qgemm_grouped_scale_grad`'s.  Every element is written: an expert without rows gets zeros and nothing
+    of it is read; rows from offsets[E] on are never read; offsets are clamped to [0, R].  An expert's dT2 has
+    `qgemm_table_grad`'s bits on the expert's rows wherever that op does not split M.  The host never reads `offsets` (no
+    synchronise, capturable): the scratch - `flute_qgemm_grouped_table_grad_scratch_bytes`, one partial per (expert, block)
+    - is sized from the shapes alone.  No atomics on global memory, equal arguments give equal bits; native HIP kernels on
+    the current stream (table_grad_grouped.hip).  Not differentiable itself: it raises when grad mode is on and an argument
+    requires grad."""
+    _validate_grouped_table_grad(grad_output, input, offsets, weight, scales, table2, num_bits, group_size,
+                                 with_scale_grad, row_weight)
+    tensors = (grad_output, input, offsets, weight, scales, table2 if with_scale_grad else None, row_weight)
+    if _records_grad(*tensors, table2):
+        raise RuntimeError("flute_amd.qgemm_grouped_table_grad: the backward is once-differentiable (no double backward)")
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
+        raise RuntimeError("flute_amd.qgemm_grouped_table_grad: all tensors must live on the same GPU")
+    R, K = input.shape
+    E, P, N = weight.shape[0], weight.shape[1], grad_output.shape[1]
+    if R >= 2 ** 31 - 64:
+        raise ValueError
+    n = 2 ** num_bits
+    dT2 = torch.empty((E, n, n, 2), dtype=torch.float32, device=dev)
+    dS = torch.empty((E, N, K // group_size), dtype=input.dtype, device=dev) if with_scale_grad else None
+    if E > 0:
+        lib = _lib.get()
+        nbytes = lib.flute_qgemm_grouped_table_grad_scratch_bytes(num_bits, group_size, E, N, K)
+        if nbytes == 0:
+            raise ValueError(f"flute_amd.qgemm_grouped_table_grad: no kernel for E = {E}, N = {N}, K = {K}, "
+                             f"group size {group_size}")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
+        with torch.cuda.device(dev):
+            _lib.check(lib.flute_qgemm_grouped_table_grad(
+                _DTYPE_ID[input.dtype], num_bits, group_size, E, R, N, K, P, template_id,
+                *[None if t is None else t.data_ptr() for t in ptrs], dT2.data_ptr(),
+                dS.data_ptr() if dS is not None else None, scratch.data_ptr(), nbytes, _num_sms(num_sms, dev),
+                _stream_ptr(dev)))
+    return (dT2, dS) if with_scale_grad else dT2
 
 
 _INDEX_DTYPE_ID = {torch.int32: 0, torch.int64: 1}

@@ -30,7 +30,7 @@ extern "C" {
  *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
  *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring; flute_moe_gate_limited and flute_moe_gate_route_limited with
  *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block;
- *    flute_qgemm_grouped_scale_grad
+ *    flute_qgemm_grouped_scale_grad; flute_qgemm_grouped_table_grad and its scratch query
  *    (additive: no existing entry point changed, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -422,6 +422,46 @@ int flute_qgemm_grouped_input_grad_row_block(void);
 int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
                                    int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
                                    const void* QM2, const float* row_weight, void* dS, int num_sms, void* stream);
+
+/* The gradient of the lookup tables of a stack flute_qgemm_grouped multiplies by, with the codes fixed: flute_qgemm_table_grad
+ * for every expert over the rows the device-side table gives it, in one main launch and one small reduce launch.  With
+ * b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):
+ *   dT2[e, c, h] = sum over (kappa, n) whose pair index in expert e's codes is c of G_e[2 kappa + h, n] * S[e, n, 2 kappa / group_size],
+ *   G_e[k, n]    = sum_{r in [b_e, e_e)} X[r, k] * dYw[r, n],
+ * dYw as flute_qgemm_grouped_scale_grad forms it (dY, or round_T(row_weight[r] * dY[r, n]), the product in fp32), the pair index
+ * and the halves h as flute_qgemm_table_grad's c and e.  dT2 [E, 4^b, 2] fp32, written whole; the tables are not read.  dY [R, N]
+ * and X [R, K] row-major T, rows sorted by expert; offsets [E + 1] int32 in DEVICE memory; Q [E, P, K] int16; S [E, N, K /
+ * group_size] T; row_weight [R] fp32 in device memory or null.
+ * With dS non-null the same launch also writes the stack's scale gradient dS [E, N, K / group_size] T, bit for bit what
+ * flute_qgemm_grouped_scale_grad returns for the same arguments; QM2 [E, 2^b, 2^b] fp32 words is needed then and only then.
+ * The host never reads offsets: the main grid is (N / 128, ceil(K / 256), E), from the shapes alone (num_sms is accepted for
+ * symmetry and not used).  One workgroup walks all rows of its expert - no split of the row reduction - and writes one fp32
+ * partial to `scratch`; the reduce launch sums an expert's partials in fp64 in flute_qgemm_table_grad's order (32 slots, each
+ * every 32nd workgroup in the order k block * (N / 128) + n block, then a fixed binary tree) and rounds once to fp32.  So
+ * dT2[e] has flute_qgemm_table_grad's bits on the expert's rows wherever that launch does not split M.  No atomics on global
+ * memory, equal arguments give equal bits, and both launches are hipGraph-capturable (a replay serves what the table then holds).
+ * An expert with e_e <= b_e gets dT2[e] (and its dS) as zeros; none of its codes, scales or table words is read, and neither is
+ * its part of the scratch.  Rows from clamp(offsets[E]) on are never read - not multiplied by zero - and every row index formed
+ * lies inside [b_e, e_e) inside [0, R): a malformed table (decreasing, past R, negative) is memory-safe and gives the result of
+ * the clamped table.  Expert bases into Q / S / QM2 / dS / dT2 / scratch and row bases into dY / X are 64-bit.
+ * Non-finite inputs propagate by IEEE rules to exactly the bins of the expert that owns the row - flute_qgemm_table_grad's rule
+ * inside that expert - and reach no other expert's dT2 or dS.
+ * `scratch` must hold flute_qgemm_grouped_table_grad_scratch_bytes(num_bits, group_size, E, N, K) =
+ * E * (N / 128) * ceil(K / 256) * 2 * 4^b * 4 bytes: every (expert, block) has its slot whether or not the expert has rows,
+ * which is the price of not reading offsets on the host.  A large stack pays for it: E 256, N 2048, K 7168 at 4 bits needs
+ * 235 MB (the figure scales with 4^b: 15 MB at 2 bits).  Less is FLUTE_ERR_WORKSPACE (more changes nothing).  The query
+ * takes no template_id: it is 0 for a num_bits / group_size / shape no template accepts (N % 128, K % max(64, group_size),
+ * E < 1, E > 65535) and may be non-zero for arguments one template's own checks still refuse.
+ * Supported layers are flute_qgemm_grouped_scale_grad's.  Refusals, before anything is enqueued and in this order:
+ * flute_qgemm_grouped_scale_grad's (dtype, the layer checks, FLUTE_ERR_SHAPE for P or a negative E / R, FLUTE_ERR_SHAPE for
+ * E > 65535); E == 0 returns FLUTE_OK (dT2 is empty); then FLUTE_ERR_NULL for a null dT2 or scratch, or a null QM2 with a dS;
+ * FLUTE_ERR_WORKSPACE; R == 0 writes dT2 (and dS) as zeros (memset nodes) and returns; then FLUTE_ERR_NULL for a null dY / X /
+ * offsets / Q / S.  No pointer is dereferenced by the host. */
+int flute_qgemm_grouped_table_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
+                                   const void* S, const void* QM2, const float* row_weight, float* dT2, void* dS,
+                                   void* scratch, size_t scratch_bytes, int num_sms, void* stream);
+size_t flute_qgemm_grouped_table_grad_scratch_bytes(int num_bits, int group_size, int E, int N, int K);
 
 /* The routing of a mixture-of-experts step in ONE launch: from the router's choice to every array the grouped launches
  * and flute_moe_combine read.  ids [T, k] int32 or int64 (id_dtype: flute_index_dtype; torch.topk returns int64), weights

@@ -7,6 +7,7 @@
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
     python tools/grouped_bench.py --mode input_grad [--processes 3] [--out profiles/grouped_moe_input_grad.json]
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
+    python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -62,8 +63,14 @@ forward, the fp32 elementwise dg / du, the pair-form input gradient, moe_combine
 --mode scale_grad times the grouped scale-gradient kernel (scale_grad_grouped.hip), dS [E, N, K / g] of a stack in one launch,
 by --mode input_grad's method at its six shape / row-count lines, against a per-expert loop of flute_amd.qgemm_scale_grad on
 row ranges the host knows - the loop's best case: inside FluteExperts the counts are not on the host.  FLOP = 2 rows N K.
+
+--mode table_grad times the grouped table-gradient launch pair (table_grad_grouped.hip: the main launch and its reduce), by
+--mode scale_grad's method at the same six lines: dT2 alone, dT2 + dS in one launch pair ("fused"), `qgemm_grouped_scale_grad`
+followed by the dT2-only pair ("separate": what the fused form replaces), and a per-expert loop of the dense
+flute_amd.qgemm_table_grad (dT2 only) on row ranges the host knows.  Passes per process: table, fused, separate, loop, twice.
 """
 import argparse
+import copy
 import json
 import os
 import subprocess
@@ -729,6 +736,76 @@ def child_scale_grad(args, device):
         json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
+class TableGrad(ScaleGrad):
+    """`copies` stacks of `experts` packed layers [N, K]; step(i) on copy i is, by `form`: "table" dT2 [E, 2^b, 2^b, 2] from the
+    grouped launch pair; "fused" dT2 and dS from it; "separate" the grouped scale gradient and then "table"; "loop" the per-expert
+    loop of the dense qgemm_table_grad (dT2 only) on row ranges the host knows.  `as_form` gives another form on the same
+    tensors: the forms of a line share one set of weight copies."""
+
+    def __init__(self, experts, N, K, counts, copies, device, form):
+        super().__init__(experts, N, K, counts, copies, device, grouped=form != "loop")
+        self.form = form
+        gen = torch.Generator(device=device).manual_seed(3)
+        self.S = (torch.rand(experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(DTYPE)
+
+    def step(self, i):
+        c = i % self.Q.shape[0]
+        fa, a = self.fa, (BITS, G, self.tid, self.num_sms)
+        if self.form == "loop":
+            out = []
+            for e, m in enumerate(self.counts):
+                if m:
+                    r0, r1 = self.off_host[e], self.off_host[e + 1]
+                    out.append(fa.qgemm_table_grad(self.dY[r0:r1], self.X[r0:r1], self.Q[c, e], self.S[e], *a))
+            return out
+        if self.form == "fused":
+            return fa.qgemm_grouped_table_grad(self.dY, self.X, self.offsets, self.Q[c], self.S, *a, table2=self.tables2,
+                                               with_scale_grad=True)
+        dT2 = fa.qgemm_grouped_table_grad(self.dY, self.X, self.offsets, self.Q[c], self.S, *a)
+        if self.form == "separate":
+            return dT2, fa.qgemm_grouped_scale_grad(self.dY, self.X, self.offsets, self.Q[c], self.tables2, *a)
+        return dT2
+
+    def as_form(self, form):
+        other = copy.copy(self)
+        other.form = form
+        return other
+
+
+TG_FORMS = ("table", "fused", "separate", "loop")
+
+
+def child_table_grad(args, device):
+    rows = []
+    for name, experts, N, K, nrows in IG_SHAPES:
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        per_copy = experts * (BITS * N // 16) * K * 2
+        copies = max(2, bench.L3_BYTES // per_copy + 2)
+        base = TableGrad(experts, N, K, counts, copies, device, TG_FORMS[0])
+        layers = {f: base.as_form(f) for f in TG_FORMS}
+        a = torch.stack([layers["table"].step(0)[e] for e, m in enumerate(counts) if m])
+        b = torch.stack(layers["loop"].step(0))
+        fused = layers["fused"].step(0)
+        sep = layers["separate"].step(0)
+        torch.cuda.synchronize()
+        diff, ref = float((a - b).abs().max()), float(b.abs().max())
+        assert torch.equal(fused[0], sep[0]) and torch.equal(fused[1], sep[1])
+        m = [measure(layers[f], args) for f in TG_FORMS + TG_FORMS]
+        us = {f: (m[i]["us"] + m[i + len(TG_FORMS)]["us"]) / 2 for i, f in enumerate(TG_FORMS)}
+        row = {"what": "table_grad", "shape": name, "experts": experts, "N": N, "K": K, "rows": sum(counts), "counts_min_max":
+               [min(counts), max(counts)], "weight_copies": copies, "flop": layers["table"].flops(),
+               "scratch_bytes": experts * (N // 128) * -(-K // 256) * 2 * 4 ** BITS * 4}
+        row.update({f + "_us": round(us[f], 3) for f in TG_FORMS})
+        row.update(table_over_loop=round(us["table"] / us["loop"], 4), fused_over_separate=round(us["fused"] / us["separate"], 4),
+                   spread=max(p["spread"] for p in m), max_abs_diff_grouped_vs_loop=diff, max_abs_loop=ref, passes=m)
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
+        del base, layers, a, b, fused, sep
+        torch.cuda.empty_cache()
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -745,7 +822,20 @@ def main_input_grad(args):
     rows = []
     for i, first in enumerate(runs[0]["rows"]):
         per = [r["rows"][i] for r in runs]
-        if first["what"] in ("input_grad", "scale_grad"):
+        if first["what"] == "table_grad":
+            us = {f: median([p[f + "_us"] for p in per]) for f in TG_FORMS}
+            row = {k: first[k] for k in ("what", "shape", "experts", "N", "K", "rows", "counts_min_max", "weight_copies", "flop",
+                                         "scratch_bytes")}
+            row.update({f + "_us": us[f] for f in TG_FORMS})
+            row.update(table_over_loop=round(us["table"] / us["loop"], 4),
+                       fused_over_separate=round(us["fused"] / us["separate"], 4),
+                       fused_over_table=round(us["fused"] / us["table"], 4),
+                       table_TFLOPs=round(first["flop"] / us["table"] * 1e-6, 1), loop_TFLOPs=round(first["flop"] / us["loop"] * 1e-6, 1),
+                       spread=max(p["spread"] for p in per),
+                       per_process_us={f: [p[f + "_us"] for p in per] for f in TG_FORMS},
+                       max_abs_diff_grouped_vs_loop=max(p["max_abs_diff_grouped_vs_loop"] for p in per),
+                       max_abs_loop=first["max_abs_loop"], replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
+        elif first["what"] in ("input_grad", "scale_grad"):
             g_us, l_us = median([p["grouped_us"] for p in per]), median([p["loop_us"] for p in per])
             row = {k: first[k] for k in ("what", "shape", "experts", "N", "K", "rows", "counts_min_max", "weight_copies", "flop")}
             row.update(grouped_us=g_us, loop_us=l_us, grouped_over_loop=round(g_us / l_us, 4),
@@ -767,7 +857,11 @@ def main_input_grad(args):
                           "backward step of FluteExperts(fused=True, native_routing=True) split into its launches; hipGraph replays, "
                           "device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
             "scale_grad": "grouped scale gradient (one launch) vs a per-expert loop of the dense qgemm_scale_grad with host-known row "
-                          "counts; hipGraph replays, device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop"}
+                          "counts; hipGraph replays, device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
+            "table_grad": "grouped table gradient (main launch + reduce): dT2 alone (table), dT2 + dS in the same launch pair (fused), "
+                          "qgemm_grouped_scale_grad followed by the dT2-only pair (separate), and a per-expert loop of the dense "
+                          "qgemm_table_grad with host-known row counts (loop, dT2 only); hipGraph replays, device-clock stamps, cold "
+                          "caches; passes per process: table, fused, separate, loop, twice"}
     out = {"what": what[args.mode],
            "config": {"bits": BITS, "group_size": G, "dtype": "float16", "steps": args.steps, "warmup": args.warmup,
                       "replays": args.replays, "processes": args.processes, "device": runs[0]["device"]},
@@ -793,7 +887,7 @@ def main():
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
-    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad"],
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad"],
                     default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -805,13 +899,15 @@ def main():
                                                    "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json",
                                                    "gate_limited": "grouped_moe_gate_limited.json",
                                                    "input_grad": "grouped_moe_input_grad.json",
-                                                   "scale_grad": "grouped_moe_scale_grad.json"}[args.mode])
-    if args.mode in ("input_grad", "scale_grad"):
+                                                   "scale_grad": "grouped_moe_scale_grad.json",
+                                                   "table_grad": "grouped_moe_table_grad.json"}[args.mode])
+    if args.mode in ("input_grad", "scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
         device = torch.device("cuda", 0)
         torch.cuda.set_device(device)
-        return child_scale_grad(args, device) if args.mode == "scale_grad" else child_input_grad(args, device)
+        child = {"scale_grad": child_scale_grad, "table_grad": child_table_grad, "input_grad": child_input_grad}
+        return child[args.mode](args, device)
     if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
     device = torch.device("cuda", 0)
