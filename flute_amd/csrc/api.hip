@@ -1649,10 +1649,10 @@ int flute_dequantize(int dtype, int num_bits, int group_size, int N, int K, int 
                             reinterpret_cast<hipStream_t>(stream));
 }
 
-int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
-                           const void* dY, const void* X, const void* Q, const void* QM2, void* dS,
-                           void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
-    if (!dY || !X || !Q || !QM2 || !dS) return FLUTE_ERR_NULL;
+// flute_qgemm_scale_grad (dT2 null) and _table_grad behind their null-pointer checks: the refusals they share, in their order, and the launch
+static int dense_param_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id, const void* dY,
+                            const void* X, const void* Q, const void* S, const void* QM2, float* dT2, void* dS, void* scratch,
+                            size_t scratch_bytes, int num_sms, void* stream) {
     if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
     Layer l;
     const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
@@ -1660,33 +1660,38 @@ int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N
     if (!group_size) return FLUTE_ERR_GROUP_SIZE;
     if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
     if (M < 1) return FLUTE_ERR_SHAPE;
-    return scale_grad_dispatch(dtype, num_bits, l.t.tile_p, l.lg, M, N, K, dY, X, Q, QM2, dS,
-                               scratch_bytes ? scratch : nullptr, scratch ? scratch_bytes : 0, num_sms,
-                               reinterpret_cast<hipStream_t>(stream));
+    if (dT2 && scratch_bytes < table_grad_scratch_bytes(num_bits, l.lg, M, N, K, dS != nullptr, num_sms)) return FLUTE_ERR_WORKSPACE;
+    const ParamGrad a = {dtype, num_bits, l.t.tile_p, l.lg, 1, M, N, K, P, dY, X, nullptr, Q, S, QM2, nullptr, dT2, dS,
+                         scratch, scratch_bytes, num_sms};
+    return param_grad_dispatch(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_qgemm_scale_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
+                           const void* dY, const void* X, const void* Q, const void* QM2, void* dS,
+                           void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
+    if (!dY || !X || !Q || !QM2 || !dS) return FLUTE_ERR_NULL;
+    return dense_param_grad(dtype, num_bits, group_size, M, N, K, P, template_id, dY, X, Q, nullptr, QM2, nullptr, dS,
+                            scratch_bytes ? scratch : nullptr, scratch ? scratch_bytes : 0, num_sms, stream);
 }
 
 int flute_qgemm_table_grad(int dtype, int num_bits, int group_size, int M, int N, int K, int P, int template_id,
                            const void* dY, const void* X, const void* Q, const void* S, const void* QM2, float* dT2,
                            void* dS, void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
     if (!dY || !X || !Q || !S || !dT2 || !scratch || (dS && !QM2)) return FLUTE_ERR_NULL;
-    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
-    Layer l;
-    const int rc = check_layer(num_bits, group_size, template_id, N, K, std::max(64, group_size), &l);
-    if (rc) return rc;
-    if (!group_size) return FLUTE_ERR_GROUP_SIZE;
-    if (P != num_bits * (N / 16)) return FLUTE_ERR_SHAPE;
-    if (M < 1) return FLUTE_ERR_SHAPE;
-    if (scratch_bytes < table_grad_scratch_bytes(num_bits, l.lg, M, N, K, dS != nullptr, num_sms))
-        return FLUTE_ERR_WORKSPACE;
-    return table_grad_dispatch(dtype, num_bits, l.t.tile_p, l.lg, M, N, K, dY, X, Q, S, QM2, dT2, dS, scratch,
-                               num_sms, reinterpret_cast<hipStream_t>(stream));
+    return dense_param_grad(dtype, num_bits, group_size, M, N, K, P, template_id, dY, X, Q, S, QM2, dT2, dS, scratch,
+                            scratch_bytes, num_sms, stream);
+}
+
+// what both scratch queries refuse (0): the bit width, the group size and the block's shape
+static bool grad_scratch_args_ok(int num_bits, int group_size, int N, int K) {
+    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return false;
+    if (group_size != 32 && group_size != 64 && group_size != 128 && group_size != 256) return false;
+    return N >= 1 && K >= 1 && N % 128 == 0 && K % std::max(64, group_size) == 0;
 }
 
 size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M, int N, int K, int want_dS,
                                             int num_sms) {
-    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return 0;
-    if (group_size != 32 && group_size != 64 && group_size != 128 && group_size != 256) return 0;
-    if (M < 1 || N < 1 || K < 1 || N % 128 || K % std::max(64, group_size)) return 0;
+    if (!grad_scratch_args_ok(num_bits, group_size, N, K) || M < 1) return 0;
     return table_grad_scratch_bytes(num_bits, ilog2(group_size), M, N, K, want_dS != 0, num_sms);
 }
 
@@ -1767,58 +1772,50 @@ int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int 
     return qgemm_grouped_input_grad_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
 }
 
-int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
-                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
-                                   const void* QM2, const float* row_weight, void* dS, int num_sms, void* stream) {
+// flute_qgemm_grouped_scale_grad (table false: S, dT2 and the scratch null) and _table_grad behind their signatures.  The refusals after
+// check_grouped: the layout, and the kernel's limits - the workgroup's block is 128 n, the grid's z (the reduce's y) is the expert, a row
+// index plus one 32-row step stays an int.  (num_sms plays no part: the grid is (N / 128, ceil(K / 256), E), from the shapes alone.)
+static int grouped_param_grad(bool table, int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P, int template_id,
+                              const void* dY, const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                              const float* row_weight, float* dT2, void* dS, void* scratch, size_t scratch_bytes, int num_sms,
+                              void* stream) {
     Layer l;
     const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
     if (rc) return rc;
     if (l.t.tile_p != 32 && l.t.tile_p != 64) return FLUTE_ERR_TEMPLATE_ID;
-    // the workgroup's block is 128 n; the grid's z is the expert; a row index plus one 32-row step stays an int
     if (N % 128 || E > 65535 || R > 0x7fffffff - 64) return FLUTE_ERR_SHAPE;
-    if (E == 0) return FLUTE_OK;                                   // dS has no element
-    if (!dS) return FLUTE_ERR_NULL;
+    if (E == 0) return FLUTE_OK;                                   // dT2 and dS have no element
+    if (table ? (!dT2 || !scratch || (dS && !QM2)) : !dS) return FLUTE_ERR_NULL;
+    if (table && scratch_bytes < table_grad_grouped_scratch_bytes(num_bits, E, N, K)) return FLUTE_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (R == 0)                                                    // no expert has a row: zeros, as the kernel writes them
-        return hipMemsetAsync(dS, 0, (size_t)E * (size_t)N * (size_t)(K >> l.lg) * 2, st) == hipSuccess ? FLUTE_OK
-                                                                                                         : FLUTE_ERR_LAUNCH;
-    if (!dY || !X || !offsets || !Q || !QM2) return FLUTE_ERR_NULL;
-    (void)num_sms;                                                 // the grid is (N / 128, ceil(K / 256), E): from the shapes alone
-    return scale_grad_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, N, K, P, dY, X, offsets, Q, QM2, row_weight,
-                                       dS, st);
+    if (R == 0) {                                                  // no expert has a row: zeros, as the kernels write them
+        if (table && hipMemsetAsync(dT2, 0, (size_t)E * ((size_t)2 << (2 * num_bits)) * 4, st) != hipSuccess) return FLUTE_ERR_LAUNCH;
+        if (dS && hipMemsetAsync(dS, 0, (size_t)E * (size_t)N * (size_t)(K >> l.lg) * 2, st) != hipSuccess) return FLUTE_ERR_LAUNCH;
+        return FLUTE_OK;
+    }
+    if (!dY || !X || !offsets || !Q || (table ? !S : !QM2)) return FLUTE_ERR_NULL;
+    const ParamGrad a = {dtype, num_bits, l.t.tile_p, l.lg, E, R, N, K, P, dY, X, offsets, Q, S, QM2, row_weight, dT2, dS,
+                         scratch, scratch_bytes, num_sms};
+    return param_grad_dispatch(a, st);
+}
+
+int flute_qgemm_grouped_scale_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
+                                   const void* QM2, const float* row_weight, void* dS, int num_sms, void* stream) {
+    return grouped_param_grad(false, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, X, offsets, Q, nullptr, QM2,
+                              row_weight, nullptr, dS, nullptr, 0, num_sms, stream);
 }
 
 int flute_qgemm_grouped_table_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
                                    int template_id, const void* dY, const void* X, const void* offsets, const void* Q,
                                    const void* S, const void* QM2, const float* row_weight, float* dT2, void* dS,
                                    void* scratch, size_t scratch_bytes, int num_sms, void* stream) {
-    Layer l;
-    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
-    if (rc) return rc;
-    if (l.t.tile_p != 32 && l.t.tile_p != 64) return FLUTE_ERR_TEMPLATE_ID;
-    // flute_qgemm_grouped_scale_grad's limits: the block is 128 n, the grid's z (the reduce's y) is the expert, a row index plus one step is an int
-    if (N % 128 || E > 65535 || R > 0x7fffffff - 64) return FLUTE_ERR_SHAPE;
-    if (E == 0) return FLUTE_OK;                                   // dT2 and dS have no element
-    if (!dT2 || !scratch || (dS && !QM2)) return FLUTE_ERR_NULL;
-    if (scratch_bytes < table_grad_grouped_scratch_bytes(num_bits, E, N, K)) return FLUTE_ERR_WORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (R == 0) {                                                  // no expert has a row: zeros, as the kernels write them
-        const size_t t_bytes = (size_t)E * ((size_t)2 << (2 * num_bits)) * 4;
-        if (hipMemsetAsync(dT2, 0, t_bytes, st) != hipSuccess) return FLUTE_ERR_LAUNCH;
-        if (dS && hipMemsetAsync(dS, 0, (size_t)E * (size_t)N * (size_t)(K >> l.lg) * 2, st) != hipSuccess)
-            return FLUTE_ERR_LAUNCH;
-        return FLUTE_OK;
-    }
-    if (!dY || !X || !offsets || !Q || !S) return FLUTE_ERR_NULL;
-    (void)num_sms;                                                 // the grid is (N / 128, ceil(K / 256), E): from the shapes alone
-    return table_grad_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, N, K, P, dY, X, offsets, Q, S, QM2,
-                                       row_weight, dT2, dS, scratch, st);
+    return grouped_param_grad(true, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, X, offsets, Q, S, QM2, row_weight,
+                              dT2, dS, scratch, scratch_bytes, num_sms, stream);
 }
 
 size_t flute_qgemm_grouped_table_grad_scratch_bytes(int num_bits, int group_size, int E, int N, int K) {
-    if (num_bits != 2 && num_bits != 3 && num_bits != 4) return 0;
-    if (group_size != 32 && group_size != 64 && group_size != 128 && group_size != 256) return 0;
-    if (E < 1 || E > 65535 || N < 1 || K < 1 || N % 128 || K % std::max(64, group_size)) return 0;
+    if (!grad_scratch_args_ok(num_bits, group_size, N, K) || E < 1 || E > 65535) return 0;
     return table_grad_grouped_scratch_bytes(num_bits, E, N, K);
 }
 

@@ -1,5 +1,6 @@
-// G = X^T dY reduced over M, the GEMM both parameter gradients of a packed layer share (scale_grad.hip, table_grad.hip
-// and their grouped forms), and the scale gradient's and the table gradient's epilogues on it.
+// G = X^T dY reduced over M, the GEMM both parameter gradients of a packed layer share, the scale gradient's and the
+// table gradient's epilogues on it, and the one kernel template built from them (param_grad_kernel; param_grad.hip
+// states what it computes and launches it).
 //
 // A workgroup of 8 waves owns a 256 (k) x 128 (n) block - whole groups up to g = 256 - and walks its M range in steps
 // of 32 rows: both operand tiles are copied row-major into LDS (16 B per lane, coalesced; rows past the range and
@@ -37,7 +38,7 @@ __device__ __forceinline__ uint2 lds_tr16(uint32_t addr) {
 
 // acc[kt][nt][r] = G[k][n] over rows [m_begin, m_end) for the block at (kb, nb): n = nb + wn * 64 + nt * 16 + (lane & 15),
 // k = kb + wk * 64 + kt * 16 + 4 (lane >> 4) + r.  Ends behind a barrier: the operand buffers are free on return.
-// ROW_WEIGHT (scale_grad_grouped.hip): the dY tile is staged as round_T(row_weight[m] * dY[m, n]), the product in fp32.
+// ROW_WEIGHT: the dY tile is staged as round_T(row_weight[m] * dY[m, n]), the product in fp32.
 template <typename T, bool ROW_WEIGHT = false>
 __device__ __forceinline__ void grad_gemm_mainloop(char* smem, const uint16_t* __restrict__ dY,
                                                    const uint16_t* __restrict__ X, int N, int K, int nb, int kb,
@@ -207,7 +208,7 @@ __device__ __forceinline__ void scale_grad_zero_block(uint16_t* __restrict__ dS,
     }
 }
 
-// The table gradient from the accumulators (table_grad.hip describes it): every wave zeroes its 4^b x 2 fp32 bins at
+// The table gradient from the accumulators (param_grad.hip describes it): every wave zeroes its 4^b x 2 fp32 bins at
 // smem + kTgBinsAt, decodes the pair index behind each accumulator pair, multiplies both accumulators by the group's
 // scale S[n, k / g] in fp32 and adds them into its bins with ds_add_f32; after a barrier the 8 waves' bins are summed in
 // wave order into t_out [4^b][2], the workgroup's partial.  With dS non-null (uniform) the scale gradient is written in
@@ -260,9 +261,60 @@ __device__ __forceinline__ void table_grad_epilogue(char* smem, const uint32_t* 
     }
 }
 
-// splits of M for a launch (scale_grad.hip): 1 when the blocks fill the chip (two workgroups per CU) or the scratch holds no split
-int scale_grad_splits(int M, int N, int K, int lg, int num_sms, size_t scratch_bytes);
-// the scratch with which scale_grad_splits is bounded by the shape alone: the most splits any M takes x [N][K / g] fp32
-size_t scale_grad_full_scratch(int N, int K, int lg, int num_sms);
+// The parameter-gradient kernel in all its forms; the axes are compile-time, a workgroup is one (k, n) block of one z.
+//   GROUPED   the row range: rows [clamp(offsets[z]), clamp(offsets[z + 1])) of expert z, with the Q / S / QM2 / dS bases
+//             moved to that expert (64-bit) and a return before anything of an expert without rows is read (its block of
+//             dS written as zeros, no partial); dense: the z-th run of steps_per_split 32-row steps of [0, rows), with
+//             the scale gradient's fp32 partial at ds_part[z] when ds_part is given.
+//   TABLE     the epilogue: table_grad_epilogue into the workgroup's slot of t_part, at ((z, y), x), with the scale
+//             epilogue inside it when dS is given (uniform); else scale_grad_epilogue alone.
+//   WEIGHTED  the mainloop's ROW_WEIGHT.
+// QM2 is read when dS is written and only then.  Written for 4 waves per SIMD = two workgroups per CU: at most 128 VGPRs.
+template <typename T, int BITS, int TILEP, bool GROUPED, bool TABLE, bool WEIGHTED>
+__global__ __launch_bounds__(kSgThreads, 4) void param_grad_kernel(
+    const uint16_t* __restrict__ dY, const uint16_t* __restrict__ X, const int* __restrict__ offsets,
+    const uint32_t* __restrict__ Q, const uint16_t* __restrict__ S, const uint32_t* __restrict__ QM2,
+    const float* __restrict__ row_weight, uint16_t* __restrict__ dS, float* __restrict__ ds_part,
+    float* __restrict__ t_part, int rows, int N, int K, int P, int lg, int steps_per_split) {
+    using L = Layout<BITS>;
+    __shared__ __attribute__((aligned(16))) char smem[kSgLds];
+    const int tid = threadIdx.x;
+    const int nb = blockIdx.x * kSgBN, kb = blockIdx.y * kSgBK;
+    const int z = (int)blockIdx.z;
+    const int G = K >> lg;
+    int rb, re;
+    if constexpr (GROUPED) {
+        rb = min(max(offsets[z], 0), rows);
+        re = min(max(offsets[z + 1], 0), rows);
+        if (!TABLE || dS) dS += (size_t)z * (size_t)N * (size_t)G;
+        if (re <= rb) {
+            if (!TABLE || dS) scale_grad_zero_block(dS, N, K, lg, nb, kb);
+            return;
+        }
+        Q += (size_t)z * (size_t)P * (size_t)(K >> 1);
+        QM2 += (size_t)z * L::LUT_N;
+        if constexpr (TABLE) S += (size_t)z * (size_t)N * (size_t)G;
+    } else {
+        rb = z * steps_per_split * kSgBM;
+        re = (int)min((long)rows, (long)rb + (long)steps_per_split * kSgBM);
+    }
+
+    uint32_t* lut = reinterpret_cast<uint32_t*>(smem + kSgLut);
+    if (!TABLE || dS)
+        for (int i = tid; i < L::LUT_N; i += kSgThreads) lut[i] = QM2[i];
+
+    f32x4_t acc[4][4];
+    grad_gemm_mainloop<T, WEIGHTED>(smem, dY, X, N, K, nb, kb, rb, re, acc, row_weight);
+    float* pout = nullptr;                            // (a grouped launch has no split: the branch on it folds away)
+    if constexpr (!GROUPED)
+        if (ds_part) pout = ds_part + (size_t)blockIdx.z * N * G;
+    if constexpr (TABLE) {
+        const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        table_grad_epilogue<T, BITS, TILEP>(smem, lut, acc, Q, S, dS, pout, t_part + wg * (2 * L::LUT_N), N, K, lg,
+                                            nb, kb);
+    } else {
+        scale_grad_epilogue<T, BITS, TILEP>(smem, lut, acc, Q, dS, pout, N, K, lg, nb, kb);
+    }
+}
 
 }  // namespace flute_amd

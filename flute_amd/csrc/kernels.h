@@ -65,16 +65,25 @@ int unpack_dispatch(int num_bits, int tile_p, int N, int K, const void* Q, void*
 // dense dequantized weight [N, k_count] (dequant.hip); lg = log2(group size)
 int dequant_dispatch(int dtype, int num_bits, int tile_p, int N, int K, int lg, int k_begin, int k_count,
                      const void* Q, const void* S, const void* QM2, void* W, hipStream_t stream);
-// scale gradient dS [N, K / g] (scale_grad.hip): M split over workgroups through the scratch when the blocks do not fill the chip
-int scale_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
-                        const void* X, const void* Q, const void* QM2, void* dS, void* scratch, size_t scratch_bytes,
-                        int num_sms, hipStream_t stream);
-// table gradient dT2 [4^b][2] fp32 (table_grad.hip), with dS non-null also the scale gradient in the same launch; the scratch holds
-// table_grad_scratch_bytes (the only place its size is computed)
+// the parameter gradients of a packed layer or of a stack of E (param_grad.hip states what they compute): with dT2 the table gradient
+// [E][4^b][2] fp32, with dS the scale gradient [E][N, K / g] T, or both from one main launch.  offsets null: the dense form over
+// rows [0, rows), which splits the rows through the scratch when the blocks do not fill the chip (a scale-only call takes what
+// scratch it is given, a null one included).  offsets [E + 1] int32, read on the device only: expert e over the rows the table
+// gives it, row_weight [rows] fp32 or null, the grid from the shapes alone.  With dT2 the scratch holds table_grad_scratch_bytes or
+// table_grad_grouped_scratch_bytes, the only places its size is computed.  S is read with dT2, QM2 with dS.
+struct ParamGrad {
+    int dtype, num_bits, tile_p, lg;
+    int E, rows, N, K, P;                             // (E and P: the grouped form's)
+    const void *dY, *X, *offsets, *Q, *S, *QM2, *row_weight;
+    float* dT2;
+    void* dS;
+    void* scratch;
+    size_t scratch_bytes;                             // (read by the dense scale-only form)
+    int num_sms;
+};
+int param_grad_dispatch(const ParamGrad& a, hipStream_t stream);
 size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int want_dS, int num_sms);
-int table_grad_dispatch(int dtype, int num_bits, int tile_p, int lg, int M, int N, int K, const void* dY,
-                        const void* X, const void* Q, const void* S, const void* QM2, float* dT2, void* dS,
-                        void* scratch, int num_sms, hipStream_t stream);
+size_t table_grad_grouped_scratch_bytes(int num_bits, int E, int N, int K);
 // grouped qgemm of E stacked layers over rows sorted by expert (qgemm_grouped.h, one kernel template; inst_grouped_plain.hip); offsets [E + 1]
 // int32 is read on the device only
 int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
@@ -100,19 +109,6 @@ FLUTE_IG_DISPATCH(4);
 FLUTE_IG_DISPATCH(3);
 FLUTE_IG_DISPATCH(2);
 #undef FLUTE_IG_DISPATCH
-// the gradient of the stacks' scales dS [E, N, K / g] (scale_grad_grouped.hip): scale_grad.hip's mainloop and epilogue per expert over the row
-// range the kernel reads from offsets; row_weight [R] fp32 or null; the grid is (N / 128, ceil(K / 256), E), no scratch
-int scale_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int N, int K, int P,
-                                const void* dY, const void* X, const void* offsets, const void* Q, const void* QM2,
-                                const void* row_weight, void* dS, hipStream_t stream);
-// the gradient of the stacks' lookup tables dT2 [E, 4^b, 2] fp32 (table_grad_grouped.hip): table_grad.hip's mainloop and epilogue per expert
-// over the row range the kernel reads from offsets, then a per-expert fp64 reduce of the workgroups' partials in the scratch, which holds
-// table_grad_grouped_scratch_bytes (the only place its size is computed); with dS non-null also the scale gradient, as scale_grad_grouped_dispatch's
-size_t table_grad_grouped_scratch_bytes(int num_bits, int E, int N, int K);
-int table_grad_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int N, int K, int P,
-                                const void* dY, const void* X, const void* offsets, const void* Q, const void* S,
-                                const void* QM2, const void* row_weight, float* dT2, void* dS, void* scratch,
-                                hipStream_t stream);
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

@@ -193,7 +193,7 @@ def _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_siz
 
 
 def _scale_grad_scratch_bytes(N, K, group_size, num_sms):
-    # the most the launch can split M into (scale_grad.hip: 256 x 128 blocks of (k, n), two workgroups per CU)
+    # the most the launch can split M into (param_grad.hip: 256 x 128 blocks of (k, n), two workgroups per CU)
     blocks = (N // 128) * -(-K // 256)
     target = 2 * (num_sms if num_sms >= 1 else 256)
     if blocks == 0 or blocks >= target:
@@ -208,7 +208,7 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     dS[n, j] = round_T(sum_m sum_{k in group j} dY[m, n] * X[m, k] * L[k, n]), L the table2 pair lookup of the
     packed codes (what the forward multiplies by the scale).  Leading dimensions are flattened; returns [N, K / g]
     in input.dtype.  For a Hadamard layer pass the rotated input, `hadamard_transform(input, hadamard_size)`.
-    A native HIP kernel on the current stream (scale_grad.hip); the same arguments give the same bits."""
+    A native HIP kernel on the current stream (param_grad.hip); the same arguments give the same bits."""
     _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_size)
     dev = input.device
     if not all(t.is_cuda and t.device == dev for t in (grad_output, input, weight, table2)):
@@ -261,7 +261,7 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     entry (i, j) of `table2` seen as pairs of T).  `pair_grad_to_table_grad` folds it for a scalar table.  The table
     itself is not read.  With `with_scale_grad` (needs `table2`) the same launch also computes the scale gradient
     and (dT2, dS) is returned, dS bit for bit `qgemm_scale_grad`'s.  Leading dimensions are flattened; for a
-    Hadamard layer pass the rotated input.  Native HIP kernels on the current stream (table_grad.hip); the same
+    Hadamard layer pass the rotated input.  Native HIP kernels on the current stream (param_grad.hip); the same
     arguments give the same bits."""
     _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, group_size, with_scale_grad)
     dev = input.device
@@ -706,7 +706,7 @@ def qgemm_grouped_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     read; offsets are clamped to [0, R].  Sums in fp32 in `qgemm_scale_grad`'s order with one rounding: an expert's slice
     has that op's bits on the expert's rows wherever it does not split M.  The host never reads `offsets` (no
     synchronise, capturable); no scratch, no atomics, equal arguments give equal bits; a native HIP kernel on the current
-    stream (scale_grad_grouped.hip).  Not differentiable itself: it raises when grad mode is on and an argument requires
+    stream (param_grad.hip).  Not differentiable itself: it raises when grad mode is on and an argument requires
     grad."""
     _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight)
     tensors = (grad_output, input, offsets, weight, table2, row_weight)
@@ -750,7 +750,7 @@ def qgemm_grouped_table_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     `qgemm_table_grad`'s bits on the expert's rows wherever that op does not split M.  The host never reads `offsets` (no
     synchronise, capturable): the scratch - `flute_qgemm_grouped_table_grad_scratch_bytes`, one partial per (expert, block)
     - is sized from the shapes alone.  No atomics on global memory, equal arguments give equal bits; native HIP kernels on
-    the current stream (table_grad_grouped.hip).  Not differentiable itself: it raises when grad mode is on and an argument
+    the current stream (param_grad.hip).  Not differentiable itself: it raises when grad mode is on and an argument
     requires grad."""
     _validate_grouped_table_grad(grad_output, input, offsets, weight, scales, table2, num_bits, group_size,
                                  with_scale_grad, row_weight)

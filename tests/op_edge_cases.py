@@ -612,7 +612,7 @@ def sg_shape(bits):
 
 
 def sg_splits(M, N, K, g, num_sms, scratch_bytes):
-    """scale_grad.hip's split of M (include/flute_amd.h: it follows from M, N, K, num_sms and scratch_bytes alone)."""
+    """param_grad.hip's split of M (include/flute_amd.h: it follows from M, N, K, num_sms and scratch_bytes alone)."""
     blocks = (N // 128) * -(-K // 256)
     steps = -(-M // 32)
     target = 2 * (num_sms if num_sms >= 1 else 256)

@@ -36,7 +36,7 @@ def to_scalar(dT2, bits):
 
 
 def chain_depth(M):
-    """The most fp32 roundings one term passes through in table_grad.hip (derived in its header): the mainloop's 32
+    """The most fp32 roundings one term passes through in param_grad.hip (derived in its header): the mainloop's 32
     per 32-row step, the product with the scale, a wave's 2048 elements of one pair half, 8 waves, the rounding of
     the fp64 total over workgroups."""
     return 32 * -(-M // 32) + 1 + 2048 + 8 + 1

@@ -1,4 +1,4 @@
-"""The scale gradient of packed layers on the GPU: flute_amd.qgemm_scale_grad (scale_grad.hip) bit for bit on exactly
+"""The scale gradient of packed layers on the GPU: flute_amd.qgemm_scale_grad (param_grad.hip) bit for bit on exactly
 representable data, within the componentwise bound on random data, deterministic across M splits, repeated calls
 and graph replay, past 2^31 activation elements; qgemm_learnable_scales / LearnableScalesFluteLinear through
 autograd, against dense fake quantization and the reference's recorded absmax gradient, and a short training run."""

@@ -1,4 +1,4 @@
-"""The lookup-table gradient of packed layers on the GPU: flute_amd.qgemm_table_grad (table_grad.hip) bit for bit on
+"""The lookup-table gradient of packed layers on the GPU: flute_amd.qgemm_table_grad (param_grad.hip) bit for bit on
 exactly representable data, within the componentwise bound gamma(d) on random data, its fused scale gradient equal to
 qgemm_scale_grad's, reproducible over repeated calls and graph replay, past 2^31 activation elements;
 qgemm_learnable / LearnableFluteLinear through autograd against a dense fp64 model and the reference's recorded
@@ -157,7 +157,7 @@ RANDOM = [(4, 4096, 1024, 64, F16, 32, 600), (4, 2048, 2048, 128, BF16, 64, 77),
 @pytest.mark.parametrize("bits,K,N,g,dtype,tile_p,M", RANDOM)
 def test_random_within_componentwise_bound(env, bits, K, N, g, dtype, tile_p, M):
     """|dT2 - exact| <= gamma_fp32(d) sum |dY X S|, bin by bin: d = table_grad_ref.chain_depth(M) is the longest chain
-    of fp32 roundings one term passes through (table_grad.hip's header), well inside M + 2 + 32768.  The fused scale
+    of fp32 roundings one term passes through (param_grad.hip's header), well inside M + 2 + 32768.  The fused scale
     gradient equals qgemm_scale_grad's bit for bit on the same data."""
     d = env.dev
     codes, Q, S, table, table2, tid = random_layer(env, bits, K, N, g, dtype, tile_p, seed=K + N + M)

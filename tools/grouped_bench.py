@@ -60,11 +60,11 @@ spread.  A last row splits one whole backward step of FluteExperts(fused=True, n
 launches (down's input gradient with the routing weight in its epilogue, the recompute of gate and up through the grouped
 forward, the fp32 elementwise dg / du, the pair-form input gradient, moe_combine).
 
---mode scale_grad times the grouped scale-gradient kernel (scale_grad_grouped.hip), dS [E, N, K / g] of a stack in one launch,
+--mode scale_grad times the grouped scale-gradient kernel (param_grad.hip), dS [E, N, K / g] of a stack in one launch,
 by --mode input_grad's method at its six shape / row-count lines, against a per-expert loop of flute_amd.qgemm_scale_grad on
 row ranges the host knows - the loop's best case: inside FluteExperts the counts are not on the host.  FLOP = 2 rows N K.
 
---mode table_grad times the grouped table-gradient launch pair (table_grad_grouped.hip: the main launch and its reduce), by
+--mode table_grad times the grouped table-gradient launch pair (param_grad.hip: the main launch and its reduce), by
 --mode scale_grad's method at the same six lines: dT2 alone, dT2 + dS in one launch pair ("fused"), `qgemm_grouped_scale_grad`
 followed by the dT2-only pair ("separate": what the fused form replaces), and a per-expert loop of the dense
 flute_amd.qgemm_table_grad (dT2 only) on row ranges the host knows.  Passes per process: table, fused, separate, loop, twice.

@@ -1,4 +1,4 @@
-"""Time flute_amd.qgemm_scale_grad (scale_grad.hip) against hipBLASLt and against the unfused composition.
+"""Time flute_amd.qgemm_scale_grad (param_grad.hip) against hipBLASLt and against the unfused composition.
 
     python tools/time_scale_grad.py [--steps 3] [--out FILE.jsonl]
 

@@ -1,4 +1,4 @@
-"""Time flute_amd.qgemm_table_grad (table_grad.hip): the table gradient alone, fused with the scale gradient, and the
+"""Time flute_amd.qgemm_table_grad (param_grad.hip): the table gradient alone, fused with the scale gradient, and the
 two kernels it would otherwise take, against hipBLASLt.
 
     python tools/time_table_grad.py [--steps 3] [--out profiles/table_grad/time_table_grad.jsonl] [--only K,N]
@@ -8,7 +8,7 @@ replays of `steps` launches, read from the chip-wide clock stamped inside the gr
 one process:
   table_only_us  dT2 [2^b, 2^b, 2] of a K x N layer for dY [M, N] and X [M, K] (the main launch + the reduce pass);
   fused_us       the same launch also writing dS [N, K / 64];
-  scale_grad_us  flute_amd.qgemm_scale_grad alone (scale_grad.hip);
+  scale_grad_us  flute_amd.qgemm_scale_grad alone (param_grad.hip);
   mm_us          torch.mm(dY.t(), X) in the same dtype (hipBLASLt; the [N, K] product only).
 Fusing pays where fused_us < scale_grad_us + table_only_us; table_vs_scale = table_only_us / scale_grad_us shows what the
 binning epilogue costs over the scale epilogue, fused_vs_mm = fused_us / mm_us what both gradients cost over the bare GEMM."""
