@@ -1707,27 +1707,95 @@ static int check_grouped(int dtype, int num_bits, int group_size, int template_i
     return FLUTE_OK;
 }
 
-int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
-                        const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
-                        int num_sms, void* stream) {
+// The two forms of the grouped forward launches (include/flute_amd.h, flute_qgemm_grouped_form): rows = qgemm_grouped.h, blocks =
+// qgemm_grouped_blocks.h.  The automatic rule reads host-known quantities only, never `offsets`: the block form where it is
+// eligible (grouped_blocks_eligible) and the mean rows per expert, rows / E, reach a threshold - 32 where the experts' column
+// blocks alone, E * N / 256 workgroups, fill the chip, 64 where they do not.  Why two: the row form's time grows with the passes
+// of 32 rows, the block form's is flat until the 128-row blocks are full, and flat at a higher level where part of the chip idles.
+// Read from profiles/grouped_moe_prefill.json ("threshold sweep": W4G64 fp16, us of rows / blocks at even counts, rows / E = 16, 32,
+// 48, 64, 96): Mixtral gate / up (448 workgroups) 134 / 121, 177 / 124, 272 / 127, 311 / 131, 446 / 141; E 64 2048 x 2048 (512)
+// 116 / 65, 136 / 68, 209 / 72, 226 / 78, 318 / 88; Mixtral down (E 8, N 4096, K 14336: 128 workgroups) 96 / 197, 121 / 198,
+// 195 / 198, 221 / 200, 319 / 203 - the routed draws say the same.  On every line from 32 on the rule is within the line's spread
+// of the better form.  The crossovers lie lower - below 16 where the chip is full, near 48 where it is not -; the rule stays at
+// the lowest values of the sweep that every stack of its kind confirmed, and below them the launch is the row form's, grid included.
+static int grouped_blocks_min_mean_rows(int E, int N, int num_sms) {
+    const long long sms = num_sms >= 1 ? num_sms : 256;
+    return (long long)E * (N / 256) >= sms ? FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS : FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL;
+}
+static int grouped_form_auto(int mode, int num_bits, int lg, int E, int rows, int N, int K, int num_sms) {
+    if (!grouped_blocks_eligible(mode, num_bits, lg, E, rows, N, K)) return FLUTE_GROUPED_FORM_ROWS;
+    return (long long)rows >= (long long)grouped_blocks_min_mean_rows(E, N, num_sms) * E ? FLUTE_GROUPED_FORM_BLOCKS
+                                                                                        : FLUTE_GROUPED_FORM_ROWS;
+}
+// the form a launch takes (1 rows / 2 blocks) for the caller's `form`, or a negative refusal: an unknown form, or blocks forced
+// where the block form is not eligible (FLUTE_ERR_SHAPE; after the refusals of check_grouped, before the null pointers)
+static int resolve_grouped_form(int form, int mode, int num_bits, int lg, int E, int rows, int N, int K, int num_sms) {
+    if (form == FLUTE_GROUPED_FORM_AUTO) return grouped_form_auto(mode, num_bits, lg, E, rows, N, K, num_sms);
+    if (form == FLUTE_GROUPED_FORM_ROWS) return form;
+    if (form == FLUTE_GROUPED_FORM_BLOCKS && grouped_blocks_eligible(mode, num_bits, lg, E, rows, N, K)) return form;
+    return FLUTE_ERR_SHAPE;
+}
+static int grouped_blocks_dispatch(int weighted, int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
+                                   const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                                   const void* row_weight, void* Y, hipStream_t st) {
+    if (num_bits == 4)
+        return qgemm_grouped_blocks_dispatch_b4(weighted, dtype, tile_p, lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y, st);
+    return qgemm_grouped_blocks_dispatch_b2(weighted, dtype, tile_p, lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y, st);
+}
+
+int flute_qgemm_grouped_form(int mode, int dtype, int num_bits, int group_size, int E, int rows, int N, int K, int template_id,
+                             int num_sms) {
+    if (mode != FLUTE_GROUPED_PLAIN && mode != FLUTE_GROUPED_GLU && mode != FLUTE_GROUPED_WEIGHTED) return FLUTE_ERR_SHAPE;
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, rows, N, K, num_bits * (N / 16), &l);
+    if (rc) return rc;
+    return grouped_form_auto(mode, num_bits, l.lg, E, rows, N, K, num_sms);
+}
+
+int flute_qgemm_grouped_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                           const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
+                           int num_sms, void* stream, int form) {
     Layer l;
     const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
     if (rc) return rc;
+    const int f = resolve_grouped_form(form, FLUTE_GROUPED_PLAIN, num_bits, l.lg, E, T, N, K, num_sms);
+    if (f < 0) return f;
     if (E == 0 || T == 0) return FLUTE_OK;
     if (!X || !offsets || !Q || !S || !QM2 || !Y) return FLUTE_ERR_NULL;
+    if (f == FLUTE_GROUPED_FORM_BLOCKS)
+        return grouped_blocks_dispatch(0, dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, nullptr, Y,
+                                       reinterpret_cast<hipStream_t>(stream));
     return qgemm_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, Y, num_sms,
                                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                        const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
+                        int num_sms, void* stream) {
+    return flute_qgemm_grouped_ex(dtype, num_bits, group_size, E, T, N, K, P, template_id, X, offsets, Q, S, QM2, Y, num_sms,
+                                  stream, FLUTE_GROUPED_FORM_AUTO);
 }
 
 int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
                             int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
                             const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
                             void* H, int num_sms, void* stream) {
+    return flute_qgemm_grouped_glu_ex(dtype, num_bits, group_size, E, R, Tsrc, F, K, P, template_id, Xsrc, rows, offsets, Qgate,
+                                      Sgate, QM2gate, Qup, Sup, QM2up, H, num_sms, stream, FLUTE_GROUPED_FORM_AUTO);
+}
+
+// (no block form of this mode is built: automatic is the row form at every row count, and forcing blocks is refused)
+int flute_qgemm_grouped_glu_ex(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                               int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                               const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                               void* H, int num_sms, void* stream, int form) {
     Layer l;
     const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, P, &l);
     if (rc) return rc;
     if (Tsrc < 0) return FLUTE_ERR_SHAPE;
     if (rows ? (R > 0 && Tsrc < 1) : Tsrc != R) return FLUTE_ERR_SHAPE;
+    const int f = resolve_grouped_form(form, FLUTE_GROUPED_GLU, num_bits, l.lg, E, R, F, K, num_sms);
+    if (f < 0) return f;
     if (E == 0 || R == 0) return FLUTE_OK;
     if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
     return qgemm_grouped_glu_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, Tsrc, F, K, P, Xsrc, rows, offsets, Qgate,
@@ -1737,11 +1805,23 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream) {
+    return flute_qgemm_grouped_weighted_ex(dtype, num_bits, group_size, E, T, N, K, P, template_id, X, offsets, Q, S, QM2,
+                                           row_weight, Y, num_sms, stream, FLUTE_GROUPED_FORM_AUTO);
+}
+
+int flute_qgemm_grouped_weighted_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                    int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                    const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream, int form) {
     Layer l;
     const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
     if (rc) return rc;
+    const int f = resolve_grouped_form(form, FLUTE_GROUPED_WEIGHTED, num_bits, l.lg, E, T, N, K, num_sms);
+    if (f < 0) return f;
     if (E == 0 || T == 0) return FLUTE_OK;
     if (!X || !offsets || !Q || !S || !QM2 || !row_weight || !Y) return FLUTE_ERR_NULL;
+    if (f == FLUTE_GROUPED_FORM_BLOCKS)
+        return grouped_blocks_dispatch(1, dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y,
+                                       reinterpret_cast<hipStream_t>(stream));
     return qgemm_grouped_weighted_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2,
                                            row_weight, Y, num_sms, reinterpret_cast<hipStream_t>(stream));
 }

@@ -98,6 +98,15 @@ int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int 
 int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
                                     const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
                                     const void* row_weight, void* Y, int num_sms, hipStream_t stream);
+// the block form of the plain and weighted grouped qgemm for experts with many rows (qgemm_grouped_blocks.h; what it
+// serves: grouped_blocks_eligible, qgemm_block.h; inst_grouped_blocks_b*.hip, one unit per bit width); the grid follows from (E, T, N) alone
+#define FLUTE_GB_DISPATCH(B)                                                                                                   \
+    int qgemm_grouped_blocks_dispatch_b##B(int weighted, int dtype, int tile_p, int lg, int E, int T, int N, int K, int P,     \
+                                           const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,  \
+                                           const void* row_weight, void* Y, hipStream_t stream)
+FLUTE_GB_DISPATCH(4);
+FLUTE_GB_DISPATCH(2);
+#undef FLUTE_GB_DISPATCH
 // the input gradient of the grouped qgemm (qgemm_grouped_input_grad.h; inst_grouped_input_grad_b*.hip, one unit per bit width): dX [R, K] from
 // dY [R, N], with dY2 / Q2 / S2 / QM22 non-null the pair form (both products summed in fp32); rows past offsets[E] written as zeros
 #define FLUTE_IG_DISPATCH(B)                                                                                                   \

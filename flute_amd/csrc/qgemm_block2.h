@@ -19,6 +19,8 @@
 // touched 16 half lines each: 128-row blocks 72 -> 62.5 us per block at K = 4096, 256-row blocks 126.9 -> 123.0 us at
 // M = 4096 on 4096^2 (profiles/r04/splitk_lab_run7_block2_whole_line_requests.jsonl).
 #pragma once
+#include <type_traits>
+
 #include "qgemm_block.h"
 
 namespace flute_amd {
@@ -27,9 +29,26 @@ namespace flute_amd {
 // by the NEXT half step's fragment of the same row tile; smaller stages, for outputs with too few 256-row blocks).
 // BITS = 2: a word holds 8 four-bit pair fields, so the wave's 32 columns are 4 units x 8 fields (lane r16: unit r16 % 4,
 // field r16 / 4, + 4 for the second column tile) and the pair table has 16 entries; everything else is the same code.
-template <typename T, int TILEP, int RT = 16, int BITS = 4>
-__global__ __launch_bounds__(512) void qgemm_block2_kernel(const BlockArgs args) {
+//
+// GM != 0: the grouped front end for mixture-of-experts stacks with many rows per expert (GM = 1: plain, 2: weighted; the arithmetic and
+// the modes are qgemm_grouped.h's, which keeps the experts with few rows; 128-row blocks only).  The main loop is the one below, untouched:
+// what changes is where a workgroup's operands come from and which rows it stores.  A workgroup is (column block, row block b); b counts the
+// 128-row blocks of all experts in expert order, expert e owning ceil(max(re - rb, 0) / 128) of them with rb = clamp(offsets[e], 0, T) and
+// re = clamp(offsets[e + 1], 0, T).  Every wave finds (e, block j of e) for itself at the top of the kernel - 64 experts per round, one
+// per lane, an inclusive prefix sum over the lanes and a ballot; the answer is wave-uniform, so the eight waves agree without LDS and
+// without a barrier ahead of the first request.  The grid holds floor((T + 127 E) / 128) row blocks, the most a monotone table can own
+// (each expert wastes at most 127 rows of its last block), from T and E alone: the host never reads the table.  A workgroup whose b is
+// past the table's total returns before it requests a weight, scale or table word; an expert without rows owns no block.
+// (The order of b against the column block is the host's: GroupedBlockArgs::order, measured in qgemm_grouped_blocks.h.)
+// The activation descriptor starts at row rb and is (re - rb) rows long, so the rows of the block at or past re read as zero by the
+// same out-of-range idiom as the dense rows past M, and no row outside [rb, re) forms an address; the epilogue stores rows < re.
+// A malformed table (decreasing or overlapping ranges) stays inside X / Y because every bound is clamped; it may own more blocks
+// than the grid holds or the same row twice: rows are then left unwritten or hold either expert's result.
+template <typename T, int TILEP, int RT = 16, int BITS = 4, int GM = 0>
+__global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs> args) {
     using NT = Num<T>;
+    static_assert(GM == 0 || RT == 8, "the grouped front end is built for 128-row blocks");
+    static_assert(GM >= 0 && GM <= 2, "0: dense, 1: grouped plain, 2: grouped weighted");
     static_assert(BITS == 4 || BITS == 2, "3-bit layers use the per-wave MFMA kernel (qgemm_tile.h)");
     constexpr int J = 16 / BITS;                                   // fields per word
     constexpr int U = 32 / J;                                      // units per wave (32 columns)
@@ -52,7 +71,7 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const BlockArgs args)
     constexpr int dbg = 0;
 #endif
 
-    BlockArgs a = args;
+    auto a = args;
     {
 #define FLUTE_OPAQUE(x) asm volatile("" : "+s"(x))
         FLUTE_OPAQUE(a.A); FLUTE_OPAQUE(a.Q); FLUTE_OPAQUE(a.D); FLUTE_OPAQUE(a.S); FLUTE_OPAQUE(a.QM2);
@@ -75,7 +94,54 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const BlockArgs args)
     int bid = blockIdx.x, split = 0;
     if (a.splitk > 1) { split = bid % a.splitk; bid /= a.splitk; }
     int tm_idx, tn_idx;
-    if (a.order == 1) {
+    int row_lo = 0, row_hi = 0;                                    // grouped: the expert's rows [rb, re)
+    if constexpr (GM != 0) {
+        if constexpr (GM == 2) {
+            // rows no expert serves, [clamp(offsets[E]), T): zeros, 8 bytes per lane, spread over the whole grid
+            const int zb = min(max(a.offsets[a.E], 0), a.M);
+            const size_t n4 = (size_t)(a.M - zb) * (size_t)(a.N >> 2);
+            ushort4* z = reinterpret_cast<ushort4*>(reinterpret_cast<uint16_t*>(a.D) + (size_t)zb * a.N);
+            for (size_t i = (size_t)blockIdx.x * (NW * 64) + tid; i < n4; i += (size_t)gridDim.x * (NW * 64))
+                z[i] = ushort4{0, 0, 0, 0};
+        }
+        int b;
+        if (a.order == 1) { tn_idx = bid % a.tiles_n; b = bid / a.tiles_n; }
+        else { b = bid % a.tiles_m; tn_idx = bid / a.tiles_m; }
+        int e = -1, j = 0, base = 0;
+        for (int c0 = 0; c0 < a.E; c0 += 64) {
+            const int ee = c0 + lane;
+            int lo = 0, hi = 0;
+            if (ee < a.E) {
+                lo = min(max(a.offsets[ee], 0), a.M);
+                hi = min(max(a.offsets[ee + 1], 0), a.M);
+            }
+            const int nb = (max(hi - lo, 0) + BM - 1) / BM;        // blocks of expert ee
+            int incl = nb;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            const unsigned long long hit = __ballot(base + incl > b);
+            if (hit) {                                             // the first lane whose running total passes b: its nb > 0
+                const int src = __ffsll(hit) - 1;
+                e = c0 + src;
+                j = b - (base + __shfl(incl - nb, src));
+                row_lo = __shfl(lo, src);
+                row_hi = __shfl(hi, src);
+                break;
+            }
+            base += __shfl(incl, 63);
+        }
+        e = __builtin_amdgcn_readfirstlane(e);
+        if (e < 0) return;                                         // b is past the table's blocks: nothing is requested
+        tm_idx = __builtin_amdgcn_readfirstlane(j);
+        row_lo = __builtin_amdgcn_readfirstlane(row_lo);
+        row_hi = __builtin_amdgcn_readfirstlane(row_hi);
+        a.Q += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);
+        a.S = reinterpret_cast<const uint16_t*>(a.S) + (size_t)e * (size_t)a.N * (size_t)a.G;
+        a.QM2 += (size_t)e << (2 * BITS);
+    } else if (a.order == 1) {
         const int per = a.tiles_m >> 3, x = bid & 7, i = bid >> 3;
         tm_idx = x * per + i % per;
         tn_idx = i / per;
@@ -94,14 +160,17 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const BlockArgs args)
     const int nsteps = (kend - kbeg) >> 6;
     const uint32_t row_bytes = (uint32_t)a.K * 2u;
 
-    const srd_t x_srd = make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
+    const srd_t x_srd = GM != 0
+        ? make_srd(reinterpret_cast<const uint16_t*>(a.A) + (size_t)row_lo * a.K,
+                   (uint32_t)min((size_t)(row_hi - row_lo) * a.K * 2, (size_t)0xfffffff0u))
+        : make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
     const srd_t w_srd = make_srd(reinterpret_cast<const char*>(a.Q) + (size_t)unit0 * row_bytes, (uint32_t)U * row_bytes);
     const srd_t s_srd = make_srd(a.S, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
     // Activations (round 4: WHOLE cache lines - a request is priced per line it touches; before: 16 rows x 64 B): piece
     // p = 2 rt + rh of a stage = rows 16 rt + 8 rh .. + 7, 128 B (the 64 k of the step) each; lane L fetches the 16-B chunk
     // (L & 7) ^ blk_swz8(L >> 3, rh) of row L >> 3, written lane-linearly.  This wave's pieces: wave * PPW + i.  Rows past M
     // need no flag: their byte offset is past the descriptor's range (voffset is what the range check covers) and reads
-    // as zero; the K offset of a step travels in the scalar offset.
+    // as zero; the K offset of a step travels in the scalar offset.  (Grouped: rows count from the expert's first; the descriptor ends at its last.)
     constexpr int PH = PPW;
     const int p0 = wave * PPW;
     uint32_t x_vo[PPW];
@@ -338,13 +407,16 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const BlockArgs args)
     const int c_unit = unit0 + (4 * q4) % U;
 #pragma unroll
     for (int r = 0; r < RT; ++r) {
-        const int row = m0 + r * 16 + r16;
-        if (row < a.M) {
+        const int row = (GM != 0 ? row_lo : 0) + m0 + r * 16 + r16;
+        if (row < (GM != 0 ? row_hi : a.M)) {
+            float rw = 1.0f;
+            if constexpr (GM == 2) rw = a.row_weight[row];
 #pragma unroll
             for (int t = 0; t < NT2; ++t) {
                 const int col = unit_col0<BITS, TILEP>(c_unit) + ((4 * q4) / U + FPT * t) * TILEP;
-                const f32x4_t o4 = acc[r][t];
-                if (a.splitk == 1) {
+                f32x4_t o4 = acc[r][t];
+                if constexpr (GM == 2) { o4[0] *= rw; o4[1] *= rw; o4[2] *= rw; o4[3] *= rw; }
+                if (GM != 0 || a.splitk == 1) {
                     uint2 o;
                     o.x = (uint32_t)NT::from_float(o4[0]) | ((uint32_t)NT::from_float(o4[1]) << 16);
                     o.y = (uint32_t)NT::from_float(o4[2]) | ((uint32_t)NT::from_float(o4[3]) << 16);

@@ -49,6 +49,18 @@ def get_plan(M: int, N: int, K: int, num_bits: int, group_size: int, template_id
     return plan.as_dict()
 
 
+def grouped_form(mode: str, E: int, rows: int, N: int, K: int, num_bits: int, group_size: int, template_id: int,
+                 num_sms: int = 0, dtype: torch.dtype = torch.float16) -> str:
+    """The form - "rows" or "blocks" - the automatic rule takes for a grouped forward launch (`mode`: "plain", "glu",
+    "weighted") of `rows` rows over E experts with [N, K] layers; host only (flute_qgemm_grouped_form).  A shape the
+    launch itself refuses raises."""
+    rc = _lib.get().flute_qgemm_grouped_form({"plain": 0, "glu": 1, "weighted": 2}[mode], _DTYPE_ID[dtype], num_bits,
+                                             group_size, E, rows, N, K, template_id, num_sms)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "rows", 2: "blocks"}[rc]
+
+
 def overrides_from_tuple(t) -> Optional[Overrides]:
     """(family, m_block, waves, kw, splitk, m_tiles, slabs_per_wave[, ring_depth[, one_shot]]) -> Overrides; None
     when every field is -1 (automatic plan)."""

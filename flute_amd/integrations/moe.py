@@ -1,8 +1,13 @@
 """Mixture-of-experts layers on packed weights: all experts of a projection in one launch.
 
 `GroupedFluteLinear` stacks E `FluteLinear`s of one shape and serves rows sorted by expert through
-`flute_amd.qgemm_grouped` (qgemm_grouped.h); the per-expert row counts never leave the device (`sort_by_expert`
-uses ops of fixed output shape only), so a decode step with changing routing can sit in one captured graph.
+`flute_amd.qgemm_grouped`; the per-expert row counts never leave the device (`sort_by_expert`
+uses ops of fixed output shape only), so a step with changing routing can sit in one captured graph.  The launches serve
+decode, prefill and training row counts: the library picks the kernel from the shapes alone - the row form
+(qgemm_grouped.h) for decode-sized counts, the block form (qgemm_grouped_blocks.h: 128-row blocks of the dense prefill
+kernel) from a mean of 32 - 64 rows per expert on, for the plain and weighted launches of 4- and 2-bit stacks it is eligible
+for (`flute_amd.dev.grouped_form` tells which) - so the modules here need no switch: the down projection and the
+backward's recompute of gate and up take the block form by themselves; the fused GLU launch has no block form yet.
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
 its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
 `native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`

@@ -376,11 +376,23 @@ def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_si
         raise ValueError
 
 
-def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=2 ** 31):
+# the `form` of the three grouped forward ops -> flute_grouped_form_t
+_GROUPED_FORMS = {None: 0, "rows": 1, "blocks": 2}
+
+
+def _grouped_form_id(form):
+    if form not in _GROUPED_FORMS:
+        raise ValueError(f"form must be None, 'rows' or 'blocks', not {form!r}")
+    return _GROUPED_FORMS[form]
+
+
+def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=2 ** 31, form=()):
     """The tail of every validated grouped op: flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P, template_id,
     *pointers, out, num_sms, stream) with `tensors` as the pointers in the ABI's order (None: a null pointer; the first
     gives the result's type and device), `rows` the ABI's row counts, each below `row_limit`, `weight` [E, P, K] one of
-    the stacks and `layer` = (num_bits, group_size, template_id, num_sms).  Returns the result, `out_shape`."""
+    the stacks and `layer` = (num_bits, group_size, template_id, num_sms).  `form` (the three forward ops, whose `name` is
+    the `_ex` entry's): (None | "rows" | "blocks",), the ABI's trailing argument.  Returns the result, `out_shape`."""
+    form = tuple(_grouped_form_id(f) for f in form)
     num_bits, group_size, template_id, num_sms = layer
     first = tensors[0]
     dev = first.device
@@ -395,29 +407,30 @@ def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=
     with torch.cuda.device(dev):
         _lib.check(getattr(_lib.get(), "flute_" + name)(
             _DTYPE_ID[first.dtype], num_bits, group_size, E, *rows, N, K, P, template_id,
-            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev)))
+            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev), *form))
     return out
 
 
-def _launch_plain(input, offsets, weight, scales, table2, layer):
-    return _launch_grouped("qgemm_grouped", (input, offsets, weight, scales, table2), weight, (input.shape[0],),
-                           scales.shape[1], (input.shape[0], scales.shape[1]), layer)
+def _launch_plain(input, offsets, weight, scales, table2, layer, form=None):
+    return _launch_grouped("qgemm_grouped_ex", (input, offsets, weight, scales, table2), weight, (input.shape[0],),
+                           scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=(form,))
 
 
-def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer):
+def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form=None):
     Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
-    return _launch_grouped("qgemm_grouped_glu", (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
-                           gs.shape[1], (R, gs.shape[1]), layer)
+    return _launch_grouped("qgemm_grouped_glu_ex", (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
+                           gs.shape[1], (R, gs.shape[1]), layer, form=(form,))
 
 
-def _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer):
-    return _launch_grouped("qgemm_grouped_weighted", (input, offsets, weight, scales, table2, row_weight), weight,
-                           (input.shape[0],), scales.shape[1], (input.shape[0], scales.shape[1]), layer)
+def _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form=None):
+    return _launch_grouped("qgemm_grouped_weighted_ex", (input, offsets, weight, scales, table2, row_weight), weight,
+                           (input.shape[0],), scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=(form,))
 
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
-                  table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+                  table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                  form=None) -> torch.Tensor:
     """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
     r in [offsets[e], offsets[e + 1]).  `input` [T, K] holds the rows sorted by expert, `offsets` is an int32 CUDA tensor
     of E + 1 elements (0, non-decreasing, T last), `weight` [E, P, K], `scales` [E, N, K / g] and `table2`
@@ -425,13 +438,18 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     Returns [T, N] in input.dtype; rows no expert covers are left unwritten, and a table that decreases or whose
     ranges overlap is memory-safe (every index is clamped to T) but leaves the contents of the rows it names twice unspecified.  The host never reads `offsets` (no
     synchronise: the call can be captured in a graph and replayed on other row counts of the same T).  A native HIP
-    kernel on the current stream (qgemm_grouped.h); the same arguments give the same bits."""
+    kernel on the current stream; the same arguments give the same bits.
+    `form`: None - the library chooses from the shapes alone (`flute_amd.dev.grouped_form`): the row form (qgemm_grouped.h) for
+    decode-sized row counts, the block form (qgemm_grouped_blocks.h: 128-row blocks of the dense prefill kernel) from a mean of
+    32 rows per expert on (64 where the experts' column blocks do not fill the chip) where the layer is eligible for it;
+    "rows" / "blocks" force one (forcing blocks on a layer that is not eligible raises).  In the block form a malformed table may also leave rows it does name unwritten."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    _grouped_form_id(form)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer)
-    return _launch_plain(input, offsets, weight, scales, table2, layer)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form)
+    return _launch_plain(input, offsets, weight, scales, table2, layer, form)
 
 
 class _GroupedFunction(torch.autograd.Function):
@@ -442,8 +460,8 @@ class _GroupedFunction(torch.autograd.Function):
     backward's parameter gradients are `_grouped_table_grads`: one qgemm_grouped_table_grad launch for both."""
 
     @staticmethod
-    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer):
-        out = _launch_plain(input, offsets, weight, scales, table2, layer)
+    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer, form=None):
+        out = _launch_plain(input, offsets, weight, scales, table2, layer, form)
         ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if any(ctx.needs_input_grad[1:3]) else ()))
         ctx.layer = layer
         ctx.scalar = codebook is not None and codebook.ndim == 2
@@ -459,7 +477,7 @@ class _GroupedFunction(torch.autograd.Function):
         if any(ctx.needs_input_grad[1:3]):
             d_scales, d_codebook = _grouped_table_grads(grad_output, saved_input[0], offsets, weight, scales, table2,
                                                         ctx.layer, *ctx.needs_input_grad[1:3], ctx.scalar)
-        return (d_input, d_scales, d_codebook) + (None,) * 4
+        return (d_input, d_scales, d_codebook) + (None,) * 5
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -488,7 +506,7 @@ def _validate_grouped_glu_pos(input, rows, pos):
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                      rows=None, pos=None) -> torch.Tensor:
+                      rows=None, pos=None, form=None) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
@@ -497,16 +515,20 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     input.dtype, rows no expert covers left unwritten.  The host reads neither `offsets` nor `rows` (no synchronise,
     capturable); a native HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits.
     `pos` (`moe_route`'s [Tsrc, k] int32, the inverse of `rows`) is read by the backward only: with it the gradient of the
-    gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`."""
+    gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`.
+    `form` as `qgemm_grouped`'s; this op has no block form yet: None and "rows" are the row form at every row count, "blocks"
+    raises.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)"""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
+    _grouped_form_id(form)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer)
-    return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer)
+                                         gate_table2, up_weight, up_table2, layer, form)
+    return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
+                       form)
 
 
 class _GroupedGluFunction(torch.autograd.Function):
@@ -519,9 +541,9 @@ class _GroupedGluFunction(torch.autograd.Function):
     `_grouped_table_grads` on the same operands."""
 
     @staticmethod
-    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer):
+    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None):
         ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
-        out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer)
+        out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form)
         ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
         ctx.has = (rows is not None, pos is not None)
         ctx.layer = layer
@@ -538,7 +560,7 @@ class _GroupedGluFunction(torch.autograd.Function):
         want = ctx.needs_input_grad
         d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
         d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
-        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 8
+        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 9
 
 
 def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad):
@@ -571,17 +593,18 @@ def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weigh
 
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                            table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
-                           template_id: int, num_sms=None) -> torch.Tensor:
+                           template_id: int, num_sms=None, form=None) -> torch.Tensor:
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
-    HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits."""
+    HIP kernel on the current stream; equal arguments give equal bits.  `form` as `qgemm_grouped`'s."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    _grouped_form_id(form)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
-        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer)
-    return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
+        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form)
+    return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
 class _GroupedWeightedFunction(torch.autograd.Function):
@@ -593,11 +616,11 @@ class _GroupedWeightedFunction(torch.autograd.Function):
     parameter gradients are `_grouped_table_grads` with the same row weight."""
 
     @staticmethod
-    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer):
+    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None):
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
         ctx.layer = layer
         ctx.scalar = codebook is not None and codebook.ndim == 2
-        return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer)
+        return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -610,7 +633,7 @@ class _GroupedWeightedFunction(torch.autograd.Function):
                                                            want_weight)
         d_scales, d_codebook = _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, ctx.layer,
                                                     want_scales, want_codebook, ctx.scalar, row_weight=row_weight)
-        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 4
+        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 5
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,

@@ -30,8 +30,10 @@ extern "C" {
  *    flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted; flute_moe_route and flute_moe_combine with FLUTE_F32 / flute_index_dtype;
  *    flute_moe_gate and flute_moe_gate_route with flute_gate_scoring; flute_moe_gate_limited and flute_moe_gate_route_limited with
  *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block;
- *    flute_qgemm_grouped_scale_grad; flute_qgemm_grouped_table_grad and its scratch query
- *    (additive: no existing entry point changed, so the number stays)
+ *    flute_qgemm_grouped_scale_grad; flute_qgemm_grouped_table_grad and its scratch query;
+ *    the block form of the grouped forward launches: flute_qgemm_grouped_ex, flute_qgemm_grouped_glu_ex, flute_qgemm_grouped_weighted_ex
+ *    (the old entries with a trailing `form`), flute_qgemm_grouped_form, flute_grouped_form_t, flute_grouped_mode_t
+ *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
  * 7 (round 6): same structs; flute_plan.kw / m_block of family 6 = K parts per workgroup (2 / 4) / row tiles per XCD group, flute_plan.slabs_per_wave
@@ -302,8 +304,24 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
  * the launch can be captured in a hipGraph and a replay serves whatever the table then holds.  A workgroup whose expert
  * has no rows requests nothing.  Every row index is clamped to [0, T]: a malformed table cannot read or write outside
  * X / Y; rows no expert covers are left unwritten, rows that overlapping ranges name twice have unspecified contents.
- * Experts with many rows stream their weights once per pass of 32 rows (3 bits: 16): correct for any count, fast for
- * decode-sized ones.
+ * Two forms serve the launch (flute_qgemm_grouped_ex chooses; this entry is the automatic choice).  The ROW form is the one
+ * described so far: experts with many rows stream their weights once per pass of 32 rows (3 bits: 16) - correct for any
+ * count, the fast one for decode-sized counts.  The BLOCK form serves prefill and training counts: 128-row x 256-column
+ * blocks of the dense prefill kernel, a weight dequantised once per 128 rows, all of K in one fp32 accumulator of the
+ * matrix core (no K split at all), one rounding; equal arguments give equal bits.  Its bits may differ from the row form's,
+ * whose summation order differs, except on exactly representable inputs.  Its grid follows from (E, T, N, num_bits)
+ * alone - floor((T + 127 E) / 128) row blocks, the most a table over T rows can own, times N / 256 - never from
+ * `offsets`: capture and replay on another table of the same T hold as for the row form.  A block past the table's total
+ * requests nothing.  In the block form the rows of a block past its expert's end are read as zeros through the bounds of
+ * the activation descriptor (no address outside the expert's rows is formed) and are never stored, whatever the weights
+ * hold: a NaN or Inf in row r still reaches row r of Y only.  A malformed table stays memory-safe in both forms; in the
+ * block form a table whose clamped ranges own more blocks than the grid holds (decreasing entries can) leaves the rows of
+ * the blocks past the grid unwritten, and rows that overlapping ranges name twice have unspecified contents.
+ * The block form serves: num_bits 4 / 2, (K / group_size) % 8 == 0, N a multiple of 256, (T + 256) * K * 2 and one expert's
+ * scale bytes N * (K / group_size) * 2 below 2^32 - 16, the plain and weighted launches.  The automatic rule takes it where
+ * it is eligible and the mean rows per expert, T / E, is at least FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS - or
+ * FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms - (measured: csrc/api.hip);
+ * below that the launch is the row form's, grid included.  flute_qgemm_grouped_glu has no block form: it runs the row form at every count.
  * Refusals, before anything is enqueued: FLUTE_ERR_DTYPE, then the layer checks of flute_dequantize (num_bits 2 / 3 / 4,
  * group_size 32 / 64 / 128 / 256, the template id - 3 bits: TileP 32 only -, N a multiple of the template's column block,
  * K % max(64, group_size) == 0), FLUTE_ERR_SHAPE for P != num_bits * N / 16 or a negative E / T; E == 0 or T == 0 returns
@@ -311,6 +329,34 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
 int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
                         const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
                         void* Y, int num_sms, void* stream);
+
+/* The form of a grouped forward launch, and the three launches as flute_qgemm_grouped_form names them. */
+typedef enum { FLUTE_GROUPED_FORM_AUTO = 0, FLUTE_GROUPED_FORM_ROWS = 1, FLUTE_GROUPED_FORM_BLOCKS = 2 } flute_grouped_form_t;
+typedef enum { FLUTE_GROUPED_PLAIN = 0, FLUTE_GROUPED_GLU = 1, FLUTE_GROUPED_WEIGHTED = 2 } flute_grouped_mode_t;
+#define FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS 32            /* E * (N / 256) >= num_sms: the experts' column blocks fill the chip */
+#define FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL 64    /* fewer workgroups than compute units */
+
+/* flute_qgemm_grouped, flute_qgemm_grouped_glu and flute_qgemm_grouped_weighted with the form chosen by the caller
+ * (flute_grouped_form_t; the old entries pass FLUTE_GROUPED_FORM_AUTO).  Everything else is the old entry's.  One more
+ * refusal, after the old entry's shape refusals and before E == 0 / T == 0 and the null pointers, so before anything is
+ * enqueued or dereferenced: FLUTE_ERR_SHAPE for a form outside the enum, or FLUTE_GROUPED_FORM_BLOCKS where the block form is
+ * not eligible (the list above; the GLU launch always, E == 0 or T == 0 included). */
+int flute_qgemm_grouped_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                           const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                           void* Y, int num_sms, void* stream, int form);
+int flute_qgemm_grouped_glu_ex(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                               int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                               const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                               void* H, int num_sms, void* stream, int form);
+int flute_qgemm_grouped_weighted_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                    int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                    const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream, int form);
+
+/* The form the automatic rule takes for a launch: FLUTE_GROUPED_FORM_ROWS or FLUTE_GROUPED_FORM_BLOCKS, or the negative error
+ * the launch itself would refuse the shape with (mode outside flute_grouped_mode_t: FLUTE_ERR_SHAPE).  Host only: no pointers,
+ * nothing is enqueued.  rows is T (GLU: R), N the stack's output columns (GLU: F); P is taken as num_bits * N / 16. */
+int flute_qgemm_grouped_form(int mode, int dtype, int num_bits, int group_size, int E, int rows, int N, int K,
+                             int template_id, int num_sms);
 
 /* The gated half of a mixture-of-experts MLP in ONE launch, on flute_qgemm_grouped's kernel geometry:
  *   H[r, :] = round_T( silu32(g) * u ),   g = Xsrc[rows[r], :] @ Wgate_e^T,   u = Xsrc[rows[r], :] @ Wup_e^T

@@ -8,6 +8,7 @@
     python tools/grouped_bench.py --mode input_grad [--processes 3] [--out profiles/grouped_moe_input_grad.json]
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
+    python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -68,6 +69,17 @@ row ranges the host knows - the loop's best case: inside FluteExperts the counts
 --mode scale_grad's method at the same six lines: dT2 alone, dT2 + dS in one launch pair ("fused"), `qgemm_grouped_scale_grad`
 followed by the dT2-only pair ("separate": what the fused form replaces), and a per-expert loop of the dense
 flute_amd.qgemm_table_grad (dT2 only) on row ranges the host knows.  Passes per process: table, fused, separate, loop, twice.
+
+--mode prefill times the grouped FORWARD at prefill and training row counts, where the block form (qgemm_grouped_blocks.h) meets
+the row form (qgemm_grouped.h): W4G64 fp16 at Mixtral's two projections with 512, 4096 and 8192 routed rows (the counts of
+--mode projection at rows / 2 tokens, so its grouped figure from a build of the parent is the row form's here), the many-expert
+pair of --mode input_grad (which the block form does not serve: 1408 columns, 22 scale groups) and an E = 64 2048 x 2048 stack
+at 4096 rows, one bf16 and one 2-bit line, the weighted down projection, and the gate / up pair as the fused GLU launch (row form
+only) against two plain launches and the elementwise product.  Contenders, alternating in one process, each timed twice by the
+tool's method: form="rows", form="blocks", the automatic rule, and a per-expert loop of flute_amd.qgemm on row ranges the host
+knows (the stack's template; the planner picks each call's kernel).  Then the threshold sweep - rows / E in 16 .. 256 on two E = 8 stacks and
+an E = 64 stack, rows against blocks - and the backward step of --mode input_grad at 512 and 4096 tokens with the recompute of
+gate and up on the row form (the code before the block form) and on the automatic rule.
 """
 import argparse
 import copy
@@ -98,10 +110,11 @@ def routing(tokens, seed):
 class Experts:
     """`copies` stacks of E packed layers [N, K]; step(i) runs one projection of all routed rows on copy i."""
 
-    def __init__(self, N, K, counts, copies, device, grouped, bits=BITS):
+    def __init__(self, N, K, counts, copies, device, grouped, bits=BITS, form=None):
         import flute_amd
         from flute_amd import tune, utils
         self.fa, self.N, self.K, self.counts, self.grouped, self.bits = flute_amd, N, K, counts, grouped, bits
+        self.form = form
         self.num_sms = utils.get_device_num_sms(device)
         self.ws = utils.get_workspace_streamk(device)
         T = sum(counts)
@@ -132,7 +145,7 @@ class Experts:
         c = i % self.Q.shape[0]
         if self.grouped:
             return self.fa.qgemm_grouped(self.X, self.offsets, self.Q[c], self.S[c], self.tables2, self.bits, G,
-                                         self.tid_grouped, self.num_sms)
+                                         self.tid_grouped, self.num_sms, form=self.form)
         # the per-expert outputs are kept as they come: no copy into one [T, N] tensor (the grouped form has none either)
         ys = []
         for e, m in enumerate(self.counts):
@@ -583,10 +596,10 @@ class BackwardStep:
     shapes), by hand, so that each can be timed alone: `part` selects one, None runs them in the backward's order."""
     PARTS = ("down_input_grad", "recompute_gate_up", "elementwise_dg_du", "pair_input_grad", "moe_combine")
 
-    def __init__(self, stacks, tokens, device, part=None):
+    def __init__(self, stacks, tokens, device, part=None, form=None):
         import flute_amd
         from flute_amd import utils
-        self.fa, self.part = flute_amd, part
+        self.fa, self.part, self.form = flute_amd, part, form   # form: of the recompute's two plain launches (None: automatic)
         self.stacks = stacks                                       # step_stacks: (gate, up, down) GroupedFluteLinear per copy
         self.num_sms = utils.get_device_num_sms(device)
         K, F = 4096, 14336
@@ -613,7 +626,8 @@ class BackwardStep:
             dH = fa.qgemm_grouped_input_grad(self.dY, off, Qd, Sd, t2, *a, row_weight=self.row_weight)
         if run("recompute_gate_up"):
             x = self.hidden[self.rows.long()] if self.part is None else self.x
-            g, u = fa.qgemm_grouped(x, off, Qg, Sg, t2, *a), fa.qgemm_grouped(x, off, Qu, Su, t2, *a)
+            g, u = (fa.qgemm_grouped(x, off, Qg, Sg, t2, *a, form=self.form),
+                    fa.qgemm_grouped(x, off, Qu, Su, t2, *a, form=self.form))
         if run("elementwise_dg_du"):
             gf, uf, dh = g.float(), u.float(), dH.float()
             sig = torch.sigmoid(gf)
@@ -806,6 +820,183 @@ def child_table_grad(args, device):
         json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
+class Forward:
+    """`copies` stacks of `experts` packed layers [N, K]; step(i) is one forward over all routed rows on copy i, by `how`:
+    "rows" / "blocks" / "auto" - one grouped launch of that form (mode "plain" or "weighted") -, "loop" - flute_amd.qgemm per expert
+    on row ranges the host knows -, "glu" - the fused gate / up launch (N columns each) -, "two_plain" - what it fuses, as two
+    plain automatic launches, silu and the product."""
+
+    def __init__(self, experts, N, K, counts, copies, device, how, mode="plain", bits=BITS, dtype=DTYPE):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.N, self.K, self.counts, self.how, self.mode, self.bits = flute_amd, N, K, counts, how, mode, bits
+        self.num_sms = utils.get_device_num_sms(device)
+        self.ws = utils.get_workspace_streamk(device)
+        gen = torch.Generator(device=device).manual_seed(1)
+        nst = 2 if how in ("glu", "two_plain") else 1
+        self.Q = [torch.randint(-2 ** 15, 2 ** 15, (copies, experts, bits * N // 16, K), dtype=torch.int16, device=device,
+                                generator=gen) for _ in range(nst)]
+        self.S = [(torch.rand(copies, experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(dtype) for _ in range(nst)]
+        self.table = torch.randn(2 ** bits, device=device, generator=gen).sort().values.to(dtype)
+        self.table2 = utils.make_qmap2_from_qmap(self.table)
+        self.tables2 = self.table2.repeat(experts, 1, 1, 1)
+        self.X = torch.randn(sum(counts), K, device=device, generator=gen).to(dtype)
+        self.w = torch.rand(sum(counts), device=device, generator=gen)
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + c)
+        self.off_host = off
+        self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == 32)
+
+    def step(self, i):
+        c = i % self.Q[0].shape[0]
+        fa, a = self.fa, (self.bits, G, self.tid, self.num_sms)
+        Q, S, t2 = self.Q[0][c], self.S[0][c], self.tables2
+        if self.how == "loop":
+            ys = []
+            for e, m in enumerate(self.counts):
+                if m:
+                    r0, r1 = self.off_host[e], self.off_host[e + 1]
+                    ys.append(fa.qgemm(self.X[r0:r1], Q[e], S[e], self.table, self.table2, self.ws, *a))
+            return ys
+        if self.how == "glu":
+            return fa.qgemm_grouped_glu(self.X, self.offsets, Q, S, t2, self.Q[1][c], self.S[1][c], t2, *a)
+        if self.how == "two_plain":
+            g = fa.qgemm_grouped(self.X, self.offsets, Q, S, t2, *a)
+            return torch.nn.functional.silu(g) * fa.qgemm_grouped(self.X, self.offsets, self.Q[1][c], self.S[1][c], t2, *a)
+        form = None if self.how == "auto" else self.how
+        if self.mode == "weighted":
+            return fa.qgemm_grouped_weighted(self.X, self.offsets, Q, S, t2, self.w, *a, form=form)
+        return fa.qgemm_grouped(self.X, self.offsets, Q, S, t2, *a, form=form)
+
+    def flops(self):
+        return 2.0 * sum(self.counts) * self.N * self.K * len(self.Q)
+
+
+def even_counts(rows, experts):
+    """`rows` rows spread as evenly as they go."""
+    return [rows // experts + (e < rows % experts) for e in range(experts)]
+
+
+# (name, experts, N, K, routed rows, bits, dtype, mode); the first six are --mode projection's shapes and counts at rows / 2 tokens
+PREFILL_LINES = [("mixtral gate_up", 8, 14336, 4096, r, 4, "float16", "plain") for r in (512, 4096, 8192)] + \
+                [("mixtral down", 8, 4096, 14336, r, 4, "float16", "plain") for r in (512, 4096, 8192)] + \
+                [("many-expert gate_up", 64, 1408, 2048, 4096, 4, "float16", "plain"),
+                 ("many-expert down", 64, 2048, 1408, 4096, 4, "float16", "plain"),
+                 ("many-expert 2048 x 2048", 64, 2048, 2048, 4096, 4, "float16", "plain"),
+                 ("mixtral gate_up", 8, 14336, 4096, 4096, 4, "bfloat16", "plain"),
+                 ("mixtral gate_up", 8, 14336, 4096, 4096, 2, "float16", "plain"),
+                 ("mixtral down", 8, 4096, 14336, 4096, 4, "float16", "weighted"),
+                 ("mixtral down", 8, 4096, 14336, 8192, 4, "float16", "weighted")]
+SWEEP_MEANS = (16, 32, 48, 64, 96, 128, 192, 256)
+SWEEP_STACKS = [("mixtral gate_up", 8, 14336, 4096), ("mixtral down", 8, 4096, 14336), ("many-expert 2048 x 2048", 64, 2048, 2048)]
+
+
+def prefill_copies(experts, N, K, bits, stacks=1):
+    per_copy = stacks * experts * ((bits * N // 16) * K * 2 + N * (K // G) * 2)
+    return max(2, bench.L3_BYTES // per_copy + 2)
+
+
+def time_forms(layers, args):
+    """Two alternating passes over `layers` {name: layer}: {name: mean of its two medians}, the largest spread, the passes."""
+    for layer in layers.values():
+        layer.step(0)
+    torch.cuda.synchronize()
+    order = list(layers) * 2
+    m = [measure(layers[n], args) for n in order]
+    us = {n: round(sum(p["us"] for o, p in zip(order, m) if o == n) / 2, 3) for n in layers}
+    return us, max(p["spread"] for p in m), {n: [p["replays_us"] for o, p in zip(order, m) if o == n] for n in layers}
+
+
+def main_prefill(args, device):
+    from flute_amd import dev
+    rows = []
+    tid = None
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        with open(args.out, "w") as f:                # (rewritten after every line: a long run that is cut short keeps its lines)
+            json.dump({"what": "grouped forward at prefill / training row counts: row form, block form, the automatic rule and a "
+                               "per-expert loop of flute_amd.qgemm with host-known counts; hipGraph replays, device-clock stamps, "
+                               "cold caches, median of the replays, two alternating passes of each form in one process",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name, experts, N, K, nrows, bits, dt, mode in PREFILL_LINES:
+        dtype = getattr(torch, dt)
+        counts = routing(nrows // 2, seed=nrows // 2) if experts == E else ig_counts(nrows, experts, seed=nrows + experts)
+        copies = prefill_copies(experts, N, K, bits)
+        mk = lambda how: Forward(experts, N, K, counts, copies, device, how, mode, bits, dtype)
+        layers = {"rows": mk("rows"), "auto": mk("auto")}
+        auto_form = dev.grouped_form(mode, experts, sum(counts), N, K, bits, G, layers["rows"].tid, layers["rows"].num_sms, dtype)
+        try:
+            layers["blocks"] = mk("blocks")
+            layers["blocks"].step(0)
+        except RuntimeError:
+            layers.pop("blocks")                      # the block form does not serve this stack
+        if mode == "plain":
+            layers["loop"] = mk("loop")
+        us, spread, replays = time_forms(layers, args)
+        flop = layers["rows"].flops()
+        row = {"what": "forward", "shape": name, "mode": mode, "bits": bits, "dtype": dt, "experts": experts, "N": N, "K": K,
+               "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies, "auto_form": auto_form,
+               "us": us, "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()}, "spread": spread, "flop": flop}
+        if "blocks" in us:
+            nblk = sum(-(-c // 128) for c in counts) * (N // 256)
+            num_sms = layers["rows"].num_sms
+            row.update(blocks_over_rows=round(us["blocks"] / us["rows"], 4), row_blocks=sum(-(-c // 128) for c in counts),
+                       workgroups_with_rows=nblk, rounds_of_256_CUs=round(nblk / num_sms, 2),
+                       us_per_block_round_at_K4096=round(us["blocks"] / max(1.0, nblk / num_sms) * 4096 / K, 2))
+        row["replays_us"] = replays
+        emit(row)
+        del layers
+        torch.cuda.empty_cache()
+    # the fused GLU launch (row form at every count) against two plain automatic launches + silu and the product
+    for nrows in (512, 4096):
+        counts = routing(nrows // 2, seed=nrows // 2)
+        copies = prefill_copies(E, 14336, 4096, BITS, stacks=2)
+        layers = {how: Forward(E, 14336, 4096, counts, copies, device, how) for how in ("glu", "two_plain")}
+        us, spread, replays = time_forms(layers, args)
+        emit({"what": "glu", "shape": "mixtral gate_up pair", "experts": E, "N": 14336, "K": 4096, "rows": sum(counts),
+              "weight_copies": copies, "us": us, "glu_over_two_plain": round(us["glu"] / us["two_plain"], 4), "spread": spread,
+              "replays_us": replays})
+        del layers
+        torch.cuda.empty_cache()
+    # the threshold sweep: rows / E on both sides of the rule, rows against blocks, even counts and a routed draw
+    for name, experts, N, K in SWEEP_STACKS:
+        copies = prefill_copies(experts, N, K, BITS)
+        for mean in SWEEP_MEANS:
+            for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                        ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                layers = {how: Forward(experts, N, K, counts, copies, device, how) for how in ("rows", "blocks", "auto")}
+                us, spread, replays = time_forms(layers, args)
+                emit({"what": "threshold sweep", "shape": name, "experts": experts, "N": N, "K": K, "mean_rows_per_expert": mean,
+                      "counts": spread_name, "counts_min_max": [min(counts), max(counts)], "rows": sum(counts), "us": us,
+                      "blocks_over_rows": round(us["blocks"] / us["rows"], 4),
+                      "auto_over_best": round(us["auto"] / min(us["rows"], us["blocks"]), 4), "spread": spread,
+                      "auto_form": dev.grouped_form("plain", experts, sum(counts), N, K, BITS, G, layers["rows"].tid,
+                                                    layers["rows"].num_sms), "replays_us": replays})
+                del layers
+                torch.cuda.empty_cache()
+    # one backward step of FluteExperts(fused=True, native_routing=True): the recompute on the row form and on the automatic rule
+    copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
+    stacks = step_stacks(copies, device)
+    for tokens in (512, 4096):
+        layers = {}
+        for part in (None, "recompute_gate_up"):
+            for form in ("rows", None):
+                layers[("whole" if part is None else part) + (" rows" if form else " auto")] = BackwardStep(stacks, tokens, device, part, form)
+        us, spread, replays = time_forms(layers, args)
+        emit({"what": "backward step", "tokens": tokens, "rows": tokens * TOPK, "experts": E, "top_k": TOPK, "weight_copies": copies,
+              "us": us, "recompute_share_rows": round(us["recompute_gate_up rows"] / us["whole rows"], 4),
+              "recompute_share_auto": round(us["recompute_gate_up auto"] / us["whole auto"], 4), "spread": spread,
+              "replays_us": replays})
+    print("wrote", args.out)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -887,7 +1078,8 @@ def main():
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
-    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad"],
+    ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad",
+                                       "prefill"],
                     default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -900,7 +1092,8 @@ def main():
                                                    "gate_limited": "grouped_moe_gate_limited.json",
                                                    "input_grad": "grouped_moe_input_grad.json",
                                                    "scale_grad": "grouped_moe_scale_grad.json",
-                                                   "table_grad": "grouped_moe_table_grad.json"}[args.mode])
+                                                   "table_grad": "grouped_moe_table_grad.json",
+                                                   "prefill": "grouped_moe_prefill.json"}[args.mode])
     if args.mode in ("input_grad", "scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
@@ -920,6 +1113,8 @@ def main():
         return main_gate_limited(args, device)
     if args.mode == "mlp":
         return main_mlp(args, device)
+    if args.mode == "prefill":
+        return main_prefill(args, device)
     rows = []
     bits = args.bits
     for name, N, K in (("gate_up", 14336, 4096), ("down", 4096, 14336)):
