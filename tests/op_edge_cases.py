@@ -36,7 +36,7 @@ WEIGHTS = (0.5, 1.0, 2.0, -1.0, -0.25, 0.0)
 
 
 def grad_counts(rb=ROW_BLOCK):
-    """test_grouped_input_grad_gpu.counts_of"""
+    """grouped_cases.counts_of"""
     return [0, 1, rb - 1, rb, rb + 1, 0, 2 * rb + 3, 5]
 
 

@@ -6,55 +6,18 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
+from tests.grouped_cases import random_case
+from tests.support import bits16, env, first_template  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
 
 
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import _lib, utils
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.lib, e.utils, e.O = flute_amd, _lib, utils, O
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def first_template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
-def bits16(t):
-    return t.contiguous().view(torch.int16)
-
-
-def random_case(e, bits, tile_p, g, dtype, K, N, seed, pair):
-    """Random codes, randn scales, an NF-style table or a random pair codebook (HIGGS vector_size = 2)."""
-    gen = torch.Generator().manual_seed(seed)
-    n = 2 ** bits
-    W = torch.randint(0, n, (K, N), generator=gen, dtype=torch.uint8)
-    S = torch.randn(N, K // g, generator=gen).to(dtype)
-    if pair:
-        table2 = torch.randn(n * n, 2, generator=gen).to(dtype).view(n, n, 2).contiguous().view(torch.float32)
-    else:
-        table2 = e.O.make_qmap2_from_qmap(torch.randn(n, generator=gen).sort().values.to(dtype))
-    Q = torch.from_numpy(e.O.pack(W.numpy(), bits, tile_p))
-    return Q, S, table2
-
-
 def test_golden_fixtures(env, golden):
     """Every reference fixture (the HIGGS pair codebooks included): dequantize == qgemm(I) of the reference."""
     d = env.dev
-    tid = first_template(env.fa, golden.num_bits, golden.tile_p)
+    tid = first_template(golden.num_bits, golden.tile_p)
     out = env.fa.dequantize(torch.as_tensor(golden.Q).to(d), golden.S.to(d), golden.table2.to(d), golden.num_bits,
                             golden.group_size, tid).cpu()
     ref = golden.D_identity.T
@@ -83,7 +46,7 @@ def sweep_cases():
 def test_against_oracle(env, bits, tile_p, g, dtype, K, N, pair):
     d = env.dev
     Q, S, table2 = random_case(env, bits, tile_p, g, dtype, K, N, seed=K * 7 + N + g + bits, pair=pair)
-    out = env.fa.dequantize(Q.to(d), S.to(d), table2.to(d), bits, g, first_template(env.fa, bits, tile_p)).cpu()
+    out = env.fa.dequantize(Q.to(d), S.to(d), table2.to(d), bits, g, first_template(bits, tile_p)).cpu()
     ref = env.O.dequantize(Q.numpy(), S, table2, bits, g, tile_p).T
     assert torch.equal(bits16(out), bits16(ref))
 
@@ -95,7 +58,7 @@ def test_large_layers_exact(env, bits, K, N, tile_p, dtype, pair):
     """Full-size layers: against the exact weights of tests/exact_cases (lut * scale is exact in T there)."""
     d = env.dev
     lay = XC.Layer(bits, K, N, 64, dtype, seed=bits * 1000 + K + N, tile_p=tile_p, pair=pair)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(lay.W.to(d), bits, [tid], env.num_sms)
     out = env.fa.dequantize(Q, lay.S.to(d), lay.table2.to(d), bits, 64, tid)
     for n0 in range(0, N, 4096):
@@ -114,7 +77,7 @@ def test_against_reconstruct(env, bits, tile_p, g, dtype, K, N, pair):
     Q, S, table2 = random_case(env, bits, tile_p, g, dtype, K, N, seed=3 + K + N, pair=pair)
     n = 2 ** bits
     table = torch.zeros(n, dtype=dtype)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Qd, Sd, t2 = Q.to(d), S.to(d), table2.to(d)
     out = env.fa.dequantize(Qd, Sd, t2, bits, g, tid)
     rec = env.utils.reconstruct(Qd, Sd, table.to(d), t2, env.ws, bits, g, tid, env.num_sms)
@@ -125,7 +88,7 @@ def test_against_reconstruct(env, bits, tile_p, g, dtype, K, N, pair):
 
 
 def raw_call(env, dtype, bits, g, N, K, k_begin, k_count, Q, S, table2, Wptr, tid):
-    lib = env.lib.get()
+    lib = env.lib
     with torch.cuda.device(env.dev):
         return lib.flute_dequantize(0 if dtype == F16 else 1, bits, g, N, K, Q.shape[0], k_begin, k_count, Q.data_ptr(),
                                     S.data_ptr(), table2.data_ptr(), Wptr, tid, torch.cuda.current_stream(env.dev).cuda_stream)
@@ -137,7 +100,7 @@ def raw_call(env, dtype, bits, g, N, K, k_begin, k_count, Q, S, table2, Wptr, ti
 def test_k_chunks_concatenate(env, bits, tile_p, g, dtype, K, N, chunks):
     d = env.dev
     Q, S, table2 = random_case(env, bits, tile_p, g, dtype, K, N, seed=11 + K, pair=False)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Qd, Sd, t2 = Q.to(d), S.to(d), table2.to(d)
     whole = env.fa.dequantize(Qd, Sd, t2, bits, g, tid)
     parts = []
@@ -156,7 +119,7 @@ def test_direct_abi_writes_exactly_its_block(env, bits, tile_p, g, dtype, K, N, 
     left: the tables and scales are finite), the guard bands are untouched, and the block equals the oracle's."""
     d = env.dev
     Q, S, table2 = random_case(env, bits, tile_p, g, dtype, K, N, seed=5 + K + k0, pair=True)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Qd, Sd, t2 = Q.to(d), S.to(d), table2.to(d)
     guard = 32768
     buf = torch.full((guard + N * kc + guard,), XC.NAN_BITS[dtype], dtype=torch.int16, device=d)
@@ -176,4 +139,4 @@ def test_direct_abi_writes_exactly_its_block(env, bits, tile_p, g, dtype, K, N, 
 def test_opcheck(env):
     d = env.dev
     Q, S, table2 = random_case(env, 4, 32, 64, F16, 512, 256, seed=1, pair=False)
-    torch.library.opcheck(env.fa.dequantize, (Q.to(d), S.to(d), table2.to(d), 4, 64, first_template(env.fa, 4, 32)))
+    torch.library.opcheck(env.fa.dequantize, (Q.to(d), S.to(d), table2.to(d), 4, 64, first_template(4, 32)))

@@ -3,13 +3,10 @@ the componentwise bound reject the errors kernels make, the forced-plan matrix p
 import torch
 
 from tests import exact_cases as E
+from tests.qgemm_cases import FAMILIES
+from tests.support import first_template
 
 NUM_SMS = 256
-
-
-def first_template(bits, tile_p):
-    import flute_amd
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def _layers():
@@ -164,9 +161,6 @@ def test_persistm_sets_override_that_cannot_apply_is_refused():
 # ---------------------------------------------------------------------------
 # the fp16 range edges and non-finite rows (exact_cases.edge_cases, tests/test_value_edges_gpu.py)
 # ---------------------------------------------------------------------------
-
-FAMILIES = (0, 2, 3, 5, 6, 7, 8)
-
 
 def _edge_layers(kind):
     seen = {}

@@ -14,161 +14,11 @@ import pytest
 import torch
 
 from tests import exact_cases as E
+from tests.qgemm_cases import (FAMILIES, Carved, DevLayer, check_plan, get_layer, guard_bits, guarded_qgemm, onehot_x,
+                               run_exact, seed_of, state_words_clean)
+from tests.support import env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096            # elements on each side of D and of every operand: a multiple of 16 B, the middle stays 16-B aligned
-Q_GUARD_BITS = 0x5A5A   # the code pattern around the packed weight
-_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32}
-
-
-def guard_bits(t, T):
-    """What surrounds operand `t` of a layer in T: NaN in T (both halves of a table2 pair word), a code pattern for Q."""
-    if t.dtype == torch.int16:
-        return Q_GUARD_BITS
-    nan = E.NAN_BITS[T]
-    return nan << 16 | nan if t.element_size() == 4 else nan
-
-
-class Carved:
-    """A copy of `t` on the device in the middle of a larger buffer filled with `fill` bits, contiguous and 16-B aligned."""
-
-    def __init__(self, t, dev, fill):
-        n = t.numel()
-        self.fill, self.n = fill, n
-        self.buf = torch.full((GUARD + n + GUARD,), fill, dtype=_INT[t.element_size()], device=dev)
-        self.buf[GUARD:GUARD + n] = t.contiguous().view(self.buf.dtype).reshape(-1).to(dev)
-        self.t = self.buf[GUARD:GUARD + n].view(t.dtype).view(t.shape)
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0 and self.t.shape == t.shape
-
-    def intact(self):
-        return bool(torch.all(self.buf[:GUARD] == self.fill) and torch.all(self.buf[GUARD + self.n:] == self.fill))
-
-
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import _lib, dev, utils
-    from flute_amd.ops import _stream_ptr
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.lib, e.dev_mod, e.utils, e.O = flute_amd, _lib.get(), dev, utils, O
-    e.check, e.stream_ptr = _lib.check, _stream_ptr
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    e.layers = {}
-    return e
-
-
-def first_template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
-seed_of = E.seed_of
-
-
-class DevLayer:
-    """A Layer with its packed weight and tables on the device."""
-
-    def __init__(self, env, lay):
-        self.lay = lay
-        self.tid = first_template(env.fa, lay.bits, lay.tile_p)
-        d = env.dev
-        self.set_operands(d, env.utils.pack(lay.W.to(d), lay.bits, [self.tid], env.num_sms), lay.S, lay.table, lay.table2)
-        self.witnessed = False
-
-    def set_operands(self, d, Q, S, table, table2):
-        T = S.dtype
-        self.carved = [Carved(t, d, guard_bits(t, T)) for t in (Q, S, table, table2)]
-        self.Q, self.S, self.table, self.table2 = (c.t for c in self.carved)
-
-    def guards_intact(self):
-        return all(c.intact() for c in self.carved)
-
-
-def get_layer(env, kw):
-    key = E.layer_key(kw)
-    if key not in env.layers:
-        env.layers.clear()                       # one layer at a time on the device (the matrix is grouped by layer)
-        torch.cuda.empty_cache()
-        lay = E.make_layer(kw, seed_of(key))
-        env.layers[key] = DevLayer(env, lay)
-    return env.layers[key]
-
-
-def _bits(t):
-    return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32}[t.element_size()]).clone()
-
-
-def state_words_clean(env):
-    return int(env.ws[:65536].view(torch.int32).abs().sum().item()) == 0
-
-
-def guarded_qgemm(env, dl, X, ovr=None, hadamard_size=0, nan_expected=False):
-    """flute_qgemm_ex with D and every operand in the middle of poisoned buffers; checks guards, coverage, inputs, state
-    words.  nan_expected: X itself holds a NaN or an Inf (the coverage check then belongs to the clean launch)."""
-    lay = dl.lay
-    T = lay.dtype
-    M, K, N = X.shape[0], lay.K, lay.N
-    Xc = Carved(X, env.dev, guard_bits(X, T))
-    X = Xc.t
-    buf = torch.full((GUARD + M * N + GUARD,), E.NAN_BITS[T], dtype=torch.int16, device=env.dev)
-    D = buf[GUARD:GUARD + M * N].view(T)
-    assert D.data_ptr() % 16 == 0
-    before = [_bits(t) for t in (X, dl.Q, dl.S, dl.table, dl.table2)]
-    scratch = torch.empty_like(X) if hadamard_size else None
-    o = env.dev_mod.Overrides(**ovr) if ovr else None
-    with torch.cuda.device(env.dev):
-        rc = env.lib.flute_qgemm_ex(
-            0 if T == torch.float16 else 1, lay.bits, lay.g, hadamard_size, M, N, K, dl.Q.shape[0],
-            X.data_ptr(), dl.Q.data_ptr(), D.data_ptr(), dl.S.data_ptr(), dl.table.data_ptr(), dl.table2.data_ptr(),
-            scratch.data_ptr() if scratch is not None else None, env.ws.data_ptr(), env.ws.numel(), dl.tid, env.num_sms,
-            o, env.stream_ptr(env.dev))
-    env.check(rc)
-    torch.cuda.synchronize()
-    assert torch.all(buf[:GUARD] == E.NAN_BITS[T]) and torch.all(buf[GUARD + M * N:] == E.NAN_BITS[T]), "write outside D"
-    assert nan_expected or not torch.isnan(D).any(), "output element left unwritten"
-    after = [_bits(t) for t in (X, dl.Q, dl.S, dl.table, dl.table2)]
-    assert all(torch.equal(a, b) for a, b in zip(before, after)), "an input was modified"
-    assert Xc.intact() and dl.guards_intact(), "an operand's guard band was modified"
-    assert state_words_clean(env), "state words left set"
-    return D.view(M, N).clone()
-
-
-def check_plan(env, dl, M, ovr, exp):
-    lay = dl.lay
-    try:
-        plan = env.dev_mod.get_plan(M, lay.N, lay.K, lay.bits, lay.g, dl.tid, env.num_sms, lay.dtype, env.dev_mod.Overrides(**ovr))
-    except RuntimeError:
-        if exp.get("may_refuse"):
-            return None
-        raise
-    for k, v in exp.items():
-        if k != "may_refuse":
-            assert plan[k] in (v if isinstance(v, tuple) else (v,)), (lay, M, ovr, k, v, plan)
-    return plan
-
-
-def run_exact(env, dl, M, ovr, xseed, repeat=True):
-    lay = dl.lay
-    X = E.make_x(M, lay.K, xseed, lay.dtype)
-    R, A = E.exact_product(X, lay, env.dev, abs_too=True)
-    E.premise(X, lay, R.cpu(), A.cpu(), witness=not dl.witnessed)
-    dl.witnessed = True
-    D1 = guarded_qgemm(env, dl, X, ovr)
-    assert E.exact_equal(D1, R, lay.dtype), (lay, M, ovr, int((D1.double().cpu() != R.to(lay.dtype).double().cpu()).sum()))
-    if repeat:
-        D2 = guarded_qgemm(env, dl, X, ovr)
-        assert torch.equal(_bits(D1), _bits(D2)), ("repeat launch differs", lay, M, ovr)
-    return D1
-
-
-FAMILIES = (0, 2, 3, 5, 6, 7, 8)
 
 
 @pytest.mark.parametrize("family", FAMILIES)
@@ -208,17 +58,6 @@ def test_automatic_plans_exact(env):
     print("automatic plans reached:", {f: len(v) for f, v in sorted(reached.items())})
     if env.num_sms == 256:
         assert set(reached) == E.AUTO_FAMILIES, sorted(reached)
-
-
-def onehot_x(M, K, h, seed, dtype):
-    """Each h-block of every row: at most three one-hot vectors with integer coefficients in [-4, 4]."""
-    gen = torch.Generator().manual_seed(seed)
-    X = torch.zeros(M, K // h, h, dtype=torch.float64)
-    for _ in range(3):
-        pos = torch.randint(0, h, (M, K // h, 1), generator=gen)
-        c = torch.randint(-4, 5, (M, K // h, 1), generator=gen).double()
-        X.scatter_add_(2, pos, c)
-    return X.reshape(M, K).to(dtype)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

@@ -6,26 +6,22 @@ return round_T of the fp64 sum by value for subnormal dY, subnormal X and sums t
 with equal bits unsplit and through the fp32 scratch of a split M, and per expert the dense op's bits.  Non-finite: a NaN
 or an Inf in one row reaches exactly the elements the documented formula connects it to - one k group or one column of
 one expert's dS, the bins of dT2 its pair row feeds, one token of moe_combine - and everything else keeps the bits of
-the clean launch.  Every launch goes through the C ABI between poisoned guards (test_grouped_edges_gpu.guarded)."""
+the clean launch.  Every launch goes through the C ABI between poisoned guards (edge_runs.guarded)."""
 import pytest
 import torch
 
 from tests import exact_cases as XC
 from tests import op_edge_cases as OE
 from tests import scale_grad_ref as SR
-from tests import test_exact_gpu as G
-from tests.test_grouped_edges_gpu import (Out, carve, check_rule, dev_stack, diagnose, differing, env,  # noqa: F401
-                                          grouped_call, guarded, offsets_tensor)
-from tests.test_qgemm_grad_gpu import fp32_blas_reduction
+from tests.edge_runs import (Out, carve, check_rule, dev_stack, diagnose, differing, grouped_call, guarded,
+                             offsets_tensor)
+from tests.qgemm_cases import Carved, guard_bits
+from tests.support import bits16, env, fp32_blas_reduction  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
 SPLIT_SCRATCH, SPLIT_SMS = 1 << 24, 256             # test_scale_grad_gpu.test_split_and_unsplit_agree_and_repeat's
-
-
-def bits16(t):
-    return t.contiguous().view(torch.int16)
 
 
 def stream(env):
@@ -47,7 +43,7 @@ def dtype_id(T):
 def test_dequantize_range_edges(env, kind, bits, tile_p):
     c = OE.dequant_case(kind, bits, tile_p)
     lay, st = c.lay, dense_layer(env, c.lay)
-    S, t2 = (G.Carved(t, env.dev, G.guard_bits(t, F16)) for t in (lay.S, lay.table2))
+    S, t2 = (Carved(t, env.dev, guard_bits(t, F16)) for t in (lay.S, lay.table2))
     out = Out(env, (lay.N, lay.K), F16)
     args = (0, bits, lay.g, lay.N, lay.K, st.Q.shape[1], 0, lay.K, st.Q[0].data_ptr(), S.t.data_ptr(), t2.t.data_ptr(),
             out.t.data_ptr(), st.tid, stream(env))

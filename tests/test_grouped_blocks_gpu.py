@@ -9,12 +9,9 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
-from tests.test_dequant_gpu import first_template
-from tests.test_grouped_glu_gpu import draw_weights, weighted_expected
-from tests.test_grouped_input_grad_gpu import rel_err, restated_experts
-from tests.test_grouped_scale_grad_gpu import dense_project, scale_leaves
-from tests.test_grouped_gpu import (bits16, check_exact, env, exact_layers, offsets_of, random_stack,  # noqa: F401
-                                    stack_exact)
+from tests.grouped_cases import (check_exact, dense_project, draw_row_weights, exact_layers, random_stack, restated_experts,
+                                 scale_leaves, stack_exact, weighted_expected)
+from tests.support import bits16, env, first_template, max_rel_err, offsets_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +85,7 @@ def test_random_componentwise(env, bits, tile_p, g, dtype):
     Q, S, t2, Ws = random_stack(env, bits, tile_p, g, dtype, K, N, len(counts), seed=bits * 100 + 7)
     X = torch.randn(sum(counts), K, generator=torch.Generator().manual_seed(5)).to(dtype)
     off = offsets_of(counts)
-    Y = env.fa.qgemm_grouped(X.to(env.dev), off.to(env.dev), Q, S, t2, bits, g, first_template(env.fa, bits, tile_p),
+    Y = env.fa.qgemm_grouped(X.to(env.dev), off.to(env.dev), Q, S, t2, bits, g, first_template(bits, tile_p),
                              form="blocks").cpu()
     for e, W in enumerate(Ws):
         r0, r1 = int(off[e]), int(off[e + 1])
@@ -104,7 +101,7 @@ def weighted_case(env):
     layers = witnessed_layers(bits, tile_p, g, dtype, K, N, False, len(COUNTS), 9300)
     Q, S, t2, tid = stack_exact(env, layers)
     T = sum(COUNTS)
-    X, w = XC.make_x(T, K, 9301, dtype), draw_weights(T, 9302)       # multiples of 2^-2 below 2: w R is exact in fp32
+    X, w = XC.make_x(T, K, 9301, dtype), draw_row_weights(T, 9302)       # multiples of 2^-2 below 2: w R is exact in fp32
     return dict(bits=bits, g=g, dtype=dtype, K=K, N=N, layers=layers, Q=Q, S=S, t2=t2, tid=tid, X=X, w=w,
                 want=weighted_expected(layers, COUNTS, X, w))
 
@@ -126,9 +123,9 @@ def abi_call(env, c, off, weighted, E=None, form=2, xfill=3.0):
     with torch.cuda.device(d):
         if weighted:
             w = c["w"].to(d)
-            rc = env.lib.get().flute_qgemm_grouped_weighted_ex(*head, w.data_ptr(), *tail)
+            rc = env.lib.flute_qgemm_grouped_weighted_ex(*head, w.data_ptr(), *tail)
         else:
-            rc = env.lib.get().flute_qgemm_grouped_ex(*head, *tail)
+            rc = env.lib.flute_qgemm_grouped_ex(*head, *tail)
     assert rc == 0
     torch.cuda.synchronize()
     assert torch.all(ybuf[:guard] == canary), "front guard"
@@ -298,11 +295,11 @@ def test_non_finite_rows_stay_in_their_rows(env, weighted_case, weighted):
 def module_case(env):
     """E = 2 experts (4-bit, g = 32, K = 256, N_ff = 256, fp16), top-1, 300 tokens: a mean of 150 rows per expert, above the
     rule's threshold, so the weighted down projection and the backward's recompute of gate and up take the block form (the
-    fused GLU launch has none).  `lut`: every layer's lookups [N, K] in fp64 (test_grouped_scale_grad_gpu.make_experts_case)."""
+    fused GLU launch has none).  `lut`: every layer's lookups [N, K] in fp64 (test_grouped_scale_grad_gpu.py, make_experts_case)."""
     from flute_amd import dev
     d, dtype = env.dev, F16
     E, K, F, T, bits, g = 2, 256, 256, 300, 4, 32
-    tid = first_template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     gen = torch.Generator().manual_seed(51)
     nf4 = torch.tensor(env.O.NF4_VALUES).to(dtype)
 
@@ -372,7 +369,7 @@ def test_flute_experts_backward_on_the_block_form(env, module_case):
     got, yard = step(c["T"]), step(c["chunk"])
     for name, a, y, r in zip(("gate scales", "up scales", "down scales", "hidden"), got, yard, ref):
         assert a is not None and a.shape == r.shape and torch.isfinite(a).all()
-        err, yerr = rel_err(a, r), rel_err(y, r)
+        err, yerr = max_rel_err(a, r), max_rel_err(y, r)
         print("block-form step, %s.grad: %.3e (row-form chunks %.3e)" % (name, err, yerr))
         assert yerr > 0
         assert err <= 2 * yerr, (name, err, yerr)

@@ -9,6 +9,7 @@ import torch
 
 import flute_amd
 from flute_amd import _lib, dev
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 AUTO, ROWS, BLOCKS = 0, 1, 2
@@ -17,8 +18,11 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 FAKE = 0x1000            # a host address no refusal may look behind
 
 
-def template(bits, tile_p):
-    return min([t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p] or [0])
+def template_or_zero(bits, tile_p):
+    try:
+        return first_template(bits, tile_p)
+    except ValueError:       # no template has this bit width: the call is refused before the id is read
+        return 0
 
 
 def thresholds():
@@ -29,24 +33,24 @@ def thresholds():
 
 
 def query(mode=PLAIN, dtype=0, bits=4, g=64, E=8, rows=4096, N=1024, K=512, tid=None, num_sms=256):
-    tid = template(bits, 32) if tid is None else tid
+    tid = template_or_zero(bits, 32) if tid is None else tid
     return _lib.get().flute_qgemm_grouped_form(mode, dtype, bits, g, E, rows, N, K, tid, num_sms)
 
 
 def plain_ex(form, dtype=0, bits=4, g=64, E=8, T=4096, N=1024, K=512, P=None, tid=None, ptrs=(None,) * 6):
-    tid = template(bits, 32) if tid is None else tid
+    tid = template_or_zero(bits, 32) if tid is None else tid
     P = bits * N // 16 if P is None else P
     return _lib.get().flute_qgemm_grouped_ex(dtype, bits, g, E, T, N, K, P, tid, *ptrs, 256, None, form)
 
 
 def weighted_ex(form, dtype=0, bits=4, g=64, E=8, T=4096, N=1024, K=512, P=None, tid=None, ptrs=(None,) * 7):
-    tid = template(bits, 32) if tid is None else tid
+    tid = template_or_zero(bits, 32) if tid is None else tid
     P = bits * N // 16 if P is None else P
     return _lib.get().flute_qgemm_grouped_weighted_ex(dtype, bits, g, E, T, N, K, P, tid, *ptrs, 256, None, form)
 
 
 def glu_ex(form, dtype=0, bits=4, g=64, E=8, R=4096, Tsrc=4096, F=1024, K=512, tid=None, ptrs=(None,) * 10):
-    tid = template(bits, 32) if tid is None else tid
+    tid = template_or_zero(bits, 32) if tid is None else tid
     return _lib.get().flute_qgemm_grouped_glu_ex(dtype, bits, g, E, R, Tsrc, F, K, bits * F // 16, tid, *ptrs, 256, None, form)
 
 
@@ -67,7 +71,7 @@ def test_query_rows_where_not_eligible():
     assert query() == BLOCKS                                               # the eligible shape the cases below vary
     assert query(bits=3, N=1024, rows=8192) == ROWS
     assert query(N=1024 + 128) == ROWS                                     # N % 256
-    assert query(bits=2, N=1024 + 256) == BLOCKS and query(bits=2, N=1024 + 128, tid=template(2, 32)) == ERR_SHAPE
+    assert query(bits=2, N=1024 + 256) == BLOCKS and query(bits=2, N=1024 + 128, tid=template_or_zero(2, 32)) == ERR_SHAPE
     assert query(K=448, g=64) == ROWS                                      # (K / g) % 8 = 7
     assert query(K=256, g=64) == ROWS                                      # 4 groups
     assert query(K=256, g=32) == BLOCKS
@@ -93,17 +97,17 @@ def test_query_threshold_on_mean_rows_per_expert():
     assert query(E=8, N=8192 - 256, rows=partial * 8) == BLOCKS and query(E=8, N=8192 - 256, rows=partial * 8 - 1) == ROWS
     assert query(E=8, rows=partial * 8, num_sms=0) == query(E=8, rows=partial * 8, num_sms=256)      # num_sms < 1: 256
     assert query(E=0) == ROWS and query(rows=0) == ROWS
-    assert dev.grouped_form("plain", 8, partial * 8, 1024, 512, 4, 64, template(4, 32), 256) == "blocks"
-    assert dev.grouped_form("weighted", 8, partial * 8 - 1, 1024, 512, 4, 64, template(4, 32), 256) == "rows"
-    assert dev.grouped_form("glu", 8, 4096, 1024, 512, 4, 64, template(4, 32)) == "rows"
+    assert dev.grouped_form("plain", 8, partial * 8, 1024, 512, 4, 64, template_or_zero(4, 32), 256) == "blocks"
+    assert dev.grouped_form("weighted", 8, partial * 8 - 1, 1024, 512, 4, 64, template_or_zero(4, 32), 256) == "rows"
+    assert dev.grouped_form("glu", 8, 4096, 1024, 512, 4, 64, template_or_zero(4, 32)) == "rows"
     with pytest.raises(RuntimeError):
-        dev.grouped_form("plain", 8, 4096, 1000, 512, 4, 64, template(4, 32))
+        dev.grouped_form("plain", 8, 4096, 1000, 512, 4, 64, template_or_zero(4, 32))
 
 
 @pytest.mark.parametrize("call", [plain_ex, weighted_ex])
 def test_forcing_blocks_where_not_eligible_is_refused_first(call):
     """FLUTE_ERR_SHAPE with null pointers: the refusal comes before the pointers are looked at."""
-    assert call(BLOCKS, bits=3, tid=template(3, 32)) == ERR_SHAPE
+    assert call(BLOCKS, bits=3, tid=template_or_zero(3, 32)) == ERR_SHAPE
     assert call(BLOCKS, N=1024 + 128) == ERR_SHAPE
     assert call(BLOCKS, K=448) == ERR_SHAPE
     assert call(BLOCKS, T=2 ** 20, K=2048) == ERR_SHAPE
@@ -136,7 +140,7 @@ def test_old_entries_unchanged():
     """The old entry points are the `_ex` ones with the automatic form: the same refusals in the same order, on shapes on
     either side of the threshold."""
     lib = _lib.get()
-    tid = template(4, 32)
+    tid = template_or_zero(4, 32)
     for T in (8, 4096):
         for kw in (dict(), dict(dtype=2), dict(bits=5), dict(g=48), dict(N=1000), dict(K=480), dict(P=255), dict(E=-1),
                    dict(T=-1), dict(T=0), dict(E=0), dict(N=1024 + 128), dict(K=448)):
@@ -164,9 +168,9 @@ def test_python_form_keyword_is_validated():
             meta(E, 2 ** bits, 2 ** bits, 1, dtype=torch.float32))
     for op, extra in ((flute_amd.qgemm_grouped, ()), (flute_amd.qgemm_grouped_weighted, (meta(8, dtype=torch.float32),))):
         with pytest.raises(ValueError, match="form"):
-            op(*args, *extra, bits, g, template(bits, 32), form="block")
+            op(*args, *extra, bits, g, template_or_zero(bits, 32), form="block")
     with pytest.raises(ValueError, match="form"):
-        flute_amd.qgemm_grouped_glu(*args, *args[2:], bits, g, template(bits, 32), form=2)
+        flute_amd.qgemm_grouped_glu(*args, *args[2:], bits, g, template_or_zero(bits, 32), form=2)
 
 
 def row_blocks_bound(E, T):

@@ -18,15 +18,13 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
-from tests.test_grouped_gpu import (COUNTS, K_CHUNK_CASES, bits16, env, exact_layers, exact_matrix, exact_seed,  # noqa: F401
-                                    experts_case, first_template, offsets_of, random_stack, stack_exact)
+from tests.grouped_cases import (COUNTS, K_CHUNK_CASES, assert_glu, draw_row_weights, exact_layers, exact_matrix,  # noqa: F401
+                                 exact_seed, experts_case, random_stack, stack_exact, weighted_expected)
+from tests.support import bits16, env, first_template, offsets_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-EPS_S = 2.0 ** -21                                   # include/flute_amd.h: silu32 and the fp32 product by u
-ETA = {F16: 2.0 ** -24, BF16: 2.0 ** -126}
-assert EPS_S <= 2.0 ** -14
 TSRC = 40
 
 
@@ -77,16 +75,6 @@ def glu_reference(gate, up, counts, Xi, rows):
     if dtype == F16:
         assert float(E.abs().max()) < XC.FP16_MAX / 2, float(E.abs().max())
     return dict(p=p, X=X, E=E, share=share(p))
-
-
-def assert_glu(H, E, dtype, what):
-    u = XC.U_T[dtype]
-    H = H.double().cpu()
-    err = (H - E).abs()
-    bound = (u + EPS_S * (1 + u)) * E.abs() + ETA[dtype]
-    worst = float((err / bound).max())
-    print("glu %s: max |H - E| / bound = %.4f, max|E| = %.3e" % (what, worst, float(E.abs().max())))
-    assert torch.isfinite(H).all() and bool((err <= bound).all()), (what, worst)
 
 
 class GluCase:
@@ -209,7 +197,7 @@ def test_glu_direct_abi_clamps_and_writes_exactly_its_rows(env, glu_small):
     off_host[E] = R + 4
     off, rows_d = off_host.to(d), rows.int().to(d)
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_qgemm_grouped_glu(
+        rc = env.lib.flute_qgemm_grouped_glu(
             0, c.bits, c.g, E, R, TSRC, c.N, c.K, c.Qg.shape[1], c.tid, xbuf[guard:].data_ptr(), rows_d.data_ptr(),
             off.data_ptr(), *[t.data_ptr() for t in c.ops()], hbuf[guard:].data_ptr(), env.num_sms,
             torch.cuda.current_stream(d).cuda_stream)
@@ -224,28 +212,6 @@ def test_glu_direct_abi_clamps_and_writes_exactly_its_rows(env, glu_small):
 
 # ---- the weighted down projection ------------------------------------------------------------------------------------
 
-WEIGHTS = torch.tensor([0.25, 0.5, 0.75, 1.0, 1.5])
-
-
-def draw_weights(T, seed):
-    return WEIGHTS[torch.randint(0, len(WEIGHTS), (T,), generator=torch.Generator().manual_seed(seed))]
-
-
-def weighted_expected(layers, counts, X, w):
-    """round_T(w R) per row, R the exact product; premise: |R| < 2^19, so w R (w a multiple of 2^-2 below 2) is exact in fp32."""
-    off = offsets_of(counts).tolist()
-    out = torch.zeros(off[-1], layers[0].N, dtype=torch.float64)
-    for e, lay in enumerate(layers):
-        r0, r1 = off[e], off[e + 1]
-        if r1 == r0:
-            continue
-        R, A = XC.exact_product(X[r0:r1], lay, abs_too=True)
-        XC.premise(X[r0:r1], lay, R, A, witness=(r1 == off[-1]))
-        assert float(R.abs().max()) < 2.0 ** 19
-        out[r0:r1] = R * w[r0:r1].double()[:, None]
-    return out
-
-
 @pytest.mark.parametrize("bits,tile_p,g,dtype,K,nblk,pair", [(4, 32, 64, F16, 1088, 3, False), (4, 64, 256, F16, 4352, 1, False),
                                                              (2, 64, 128, BF16, 2048, 1, True), (2, 32, 32, BF16, 64, 1, False),
                                                              (3, 32, 64, F16, 1088, 3, False)])
@@ -254,7 +220,7 @@ def test_weighted_exact_products(env, bits, tile_p, g, dtype, K, nblk, pair):
     layers = exact_layers(bits, tile_p, g, dtype, K, N, pair, len(COUNTS), 6000 + bits + tile_p)
     Q, S, t2, tid = stack_exact(env, layers)
     T = sum(COUNTS)
-    X, w = XC.make_x(T, K, 6001, dtype), draw_weights(T, 6002)
+    X, w = XC.make_x(T, K, 6001, dtype), draw_row_weights(T, 6002)
     want = weighted_expected(layers, COUNTS, X, w)
     Y = env.fa.qgemm_grouped_weighted(X.to(env.dev), offsets_of(COUNTS, env.dev), Q, S, t2, w.to(env.dev), bits, g, tid,
                                       env.num_sms)
@@ -268,7 +234,7 @@ def weighted_small(env):
     layers = exact_layers(bits, tile_p, g, dtype, K, N, False, len(COUNTS), 9200)
     Q, S, t2, tid = stack_exact(env, layers)
     T = sum(COUNTS)
-    X, w = XC.make_x(T, K, 9201, dtype), draw_weights(T, 9202)
+    X, w = XC.make_x(T, K, 9201, dtype), draw_row_weights(T, 9202)
     return dict(bits=bits, g=g, dtype=dtype, K=K, N=N, layers=layers, Q=Q, S=S, t2=t2, tid=tid, X=X, w=w,
                 want=weighted_expected(layers, COUNTS, X, w))
 
@@ -283,7 +249,7 @@ def weighted_abi(env, c, off):
     xbuf[guard:guard + T] = c["X"].to(d)
     off, w = off.to(d), c["w"].to(d)
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_qgemm_grouped_weighted(
+        rc = env.lib.flute_qgemm_grouped_weighted(
             0 if dtype == F16 else 1, c["bits"], c["g"], E, T, N, K, c["Q"].shape[1], c["tid"], xbuf[guard:].data_ptr(),
             off.data_ptr(), c["Q"].data_ptr(), c["S"].data_ptr(), c["t2"].data_ptr(), w.data_ptr(), ybuf[guard:].data_ptr(),
             env.num_sms, torch.cuda.current_stream(d).cuda_stream)
@@ -324,7 +290,7 @@ def test_weighted_by_one_is_the_plain_form(env, bits, tile_p, g, dtype):
     Q, S, t2, _ = random_stack(env, bits, tile_p, g, dtype, K, N, E, seed=8800 + bits)
     X = torch.randn(T, K, generator=torch.Generator().manual_seed(8801)).to(dtype).to(env.dev)
     off, ones = offsets_of(COUNTS, env.dev), torch.ones(T, device=env.dev)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     plain = bits16(env.fa.qgemm_grouped(X, off, Q, S, t2, bits, g, tid, env.num_sms))
     assert torch.equal(bits16(env.fa.qgemm_grouped_weighted(X, off, Q, S, t2, ones, bits, g, tid, env.num_sms)), plain)
     cut = T - 17

@@ -10,14 +10,11 @@ import flute_amd
 from flute_amd import _lib
 from flute_amd.integrations.moe import FluteExperts, GroupedFluteLinear
 from flute_amd.ops import _validate_grouped_glu, _validate_grouped_weighted
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flute_amd.h")
 FAKE = 0x1000            # a host address no refusal may look behind
-
-
-def template(bits, tile_p):
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def glu(dtype=0, bits=4, g=64, E=4, R=8, Tsrc=8, F=1024, K=512, P=None, tid=0, ptrs=(None,) * 10, num_sms=256):
@@ -55,7 +52,7 @@ def test_layer_refusals_with_null_pointers(call):
         assert call(g=g) == ERR_GROUP_SIZE, g
     assert call(tid=10 ** 6) == ERR_TEMPLATE_ID
     width = "F" if call is glu else "N"
-    assert call(bits=3, tid=template(3, 64), **{width: 512}) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
+    assert call(bits=3, tid=first_template(3, 64), **{width: 512}) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
     assert call(dtype=2, bits=5) == ERR_DTYPE                                        # the order: dtype first
     assert call(bits=5, g=48, K=480, E=-1) == ERR_NUM_BITS
 
@@ -65,9 +62,9 @@ def test_shape_refusals_with_null_pointers(call):
     width = "F" if call is glu else "N"
     rows = "R" if call is glu else "T"
     assert call(**{width: 1000}) == ERR_SHAPE
-    assert call(tid=template(4, 32), **{width: 64}) == ERR_SHAPE
-    assert call(tid=template(4, 64), **{width: 128}) == ERR_SHAPE      # TileP 64: the column block is 256
-    assert call(bits=3, tid=template(3, 32), **{width: 256}) == ERR_SHAPE
+    assert call(tid=first_template(4, 32), **{width: 64}) == ERR_SHAPE
+    assert call(tid=first_template(4, 64), **{width: 128}) == ERR_SHAPE      # TileP 64: the column block is 256
+    assert call(bits=3, tid=first_template(3, 32), **{width: 256}) == ERR_SHAPE
     assert call(K=480) == ERR_SHAPE              # K % 64
     assert call(K=384, g=256) == ERR_SHAPE       # K % g
     assert call(K=0) == ERR_SHAPE

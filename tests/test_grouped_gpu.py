@@ -9,82 +9,13 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
-from tests.test_dequant_gpu import first_template, random_case
+from tests.grouped_cases import (COUNTS, K_CHUNK_CASES, check_exact, exact_layers, exact_matrix, exact_seed, experts_case,  # noqa: F401
+                                 random_stack, stack_exact)
+from tests.support import bits16, env, first_template, offsets_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-COUNTS = [0, 1, 15, 16, 17, 0, 33, 70]           # an empty first expert, one in the middle, both sides of a 16-row tile
-
-
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import _lib, utils
-    from flute_amd.integrations import moe
-    from flute_amd.integrations.base import FluteLinear
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.lib, e.utils, e.O, e.moe, e.FluteLinear = flute_amd, _lib, utils, O, moe, FluteLinear
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def offsets_of(counts, device=None):
-    off = torch.zeros(len(counts) + 1, dtype=torch.int32)
-    off[1:] = torch.cumsum(torch.tensor(counts), 0)
-    return off if device is None else off.to(device)
-
-
-def bits16(t):
-    return t.contiguous().view(torch.int16)
-
-
-def exact_layers(bits, tile_p, g, dtype, K, N, pair, E, seed0):
-    return [XC.Layer(bits, K, N, g, dtype, seed=seed0 + e, tile_p=tile_p, pair=pair) for e in range(E)]
-
-
-def stack_exact(env, layers):
-    """The grouped operands of E exact layers: Q [E, P, K], S [E, N, G], table2 [E, n, n, 1] on the device."""
-    lay = layers[0]
-    tid = first_template(env.fa, lay.bits, lay.tile_p)
-    Q = torch.stack([env.utils.pack(l.W.to(env.dev), l.bits, [tid], env.num_sms) for l in layers])
-    S = torch.stack([l.S for l in layers]).to(env.dev)
-    t2 = torch.stack([l.table2 for l in layers]).to(env.dev)
-    return Q, S, t2, tid
-
-
-def check_exact(env, layers, counts, X, Y):
-    off = offsets_of(counts).tolist()
-    T = off[-1]
-    for e, lay in enumerate(layers):
-        r0, r1 = off[e], off[e + 1]
-        if r1 == r0:
-            continue
-        rows = X[r0:r1]
-        R, A = XC.exact_product(rows, lay, abs_too=True)
-        XC.premise(rows, lay, R, A, witness=(r1 == T))           # the accumulator witness is the last row of X
-        assert XC.exact_equal(Y[r0:r1], R, lay.dtype), (e, lay)
-
-
-def exact_matrix():
-    rows = ((32, BF16, 64, 1, False), (64, F16, 1088, 3, False), (128, BF16, 2048, 1, True), (256, F16, 4352, 1, False))
-    out = []
-    for bits in (4, 3, 2):
-        for tile_p in ((32, 64) if bits != 3 else (32,)):
-            for g, dtype, K, nblk, pair in rows:
-                out.append((bits, tile_p, g, dtype, K, nblk * XC.cols_per_block(bits, tile_p), pair))
-    return out
-
-
-def exact_seed(bits, tile_p, g):
-    return 1000 * bits + 10 * tile_p + g
 
 
 @pytest.mark.parametrize("bits,tile_p,g,dtype,K,N,pair", exact_matrix())
@@ -109,11 +40,6 @@ def test_exact_several_row_passes(env):
     check_exact(env, layers, counts, X, Y.cpu())
 
 
-# the first K past one scale-panel chunk of the kernel (56 blocks: 7168 k at 4 bits, 3584 at 2 bits, 1792 at 3 bits, all at
-# group size 32) plus one 64-k step: the panel is staged a second time, for a ragged last chunk
-K_CHUNK_CASES = [(4, 32, 7168 + 64), (4, 64, 7168 + 64), (2, 32, 3584 + 64), (3, 32, 1792 + 64)]
-
-
 @pytest.mark.parametrize("bits,tile_p,K", K_CHUNK_CASES)
 def test_exact_across_k_chunks(env, bits, tile_p, K):
     counts = [0, 17, 3]
@@ -125,20 +51,6 @@ def test_exact_across_k_chunks(env, bits, tile_p, K):
     check_exact(env, layers, counts, X, Y.cpu())
 
 
-def random_stack(env, bits, tile_p, g, dtype, K, N, E, seed):
-    """E random layers (test_dequant_gpu.random_case: random codes, randn scales, an NF-style table or a pair codebook)
-    and their exact lut * s weights [K, N] in fp64."""
-    Qs, Ss, t2s, Ws = [], [], [], []
-    for e in range(E):
-        Q, S, table2 = random_case(env, bits, tile_p, g, dtype, K, N, seed + e, pair=(e % 2 == 1))
-        idx = torch.from_numpy(env.O.pair_index(Q.numpy(), bits, tile_p))                  # [K / 2, N]
-        w = env.O.table2_as_pairs(table2, dtype).double()[idx].permute(0, 2, 1).reshape(K, N)
-        Ws.append(w * torch.repeat_interleave(S.double(), g, dim=1).T)
-        Qs.append(Q), Ss.append(S), t2s.append(table2)
-    d = env.dev
-    return torch.stack(Qs).to(d), torch.stack(Ss).to(d), torch.stack(t2s).to(d), Ws
-
-
 @pytest.mark.parametrize("nblk", [1, 3])
 @pytest.mark.parametrize("bits,tile_p,g,dtype", [(4, 32, 64, F16), (3, 32, 32, BF16), (2, 64, 64, BF16)])
 def test_random_componentwise(env, bits, tile_p, g, dtype, nblk):
@@ -148,7 +60,7 @@ def test_random_componentwise(env, bits, tile_p, g, dtype, nblk):
     gen = torch.Generator().manual_seed(5)
     X = torch.randn(sum(counts), K, generator=gen).to(dtype)
     off = offsets_of(counts)
-    Y = env.fa.qgemm_grouped(X.to(env.dev), off.to(env.dev), Q, S, t2, bits, g, first_template(env.fa, bits, tile_p)).cpu()
+    Y = env.fa.qgemm_grouped(X.to(env.dev), off.to(env.dev), Q, S, t2, bits, g, first_template(bits, tile_p)).cpu()
     for e, W in enumerate(Ws):
         r0, r1 = int(off[e]), int(off[e + 1])
         if r1 > r0:
@@ -218,7 +130,7 @@ def test_direct_abi_writes_exactly_its_rows(env, small_exact):
     off[E] = T + 4
     off = off.to(d)
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_qgemm_grouped(
+        rc = env.lib.flute_qgemm_grouped(
             0 if dtype == F16 else 1, c["bits"], c["g"], E, T, N, K, c["Q"].shape[1], c["tid"],
             xbuf[guard:].data_ptr(), off.data_ptr(), c["Q"].data_ptr(), c["S"].data_ptr(), c["t2"].data_ptr(),
             ybuf[guard:].data_ptr(), env.num_sms, torch.cuda.current_stream(d).cuda_stream)
@@ -233,7 +145,7 @@ def test_direct_abi_writes_exactly_its_rows(env, small_exact):
     off2[E] = off2[E - 1]
     off2 = off2.to(d)
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_qgemm_grouped(
+        rc = env.lib.flute_qgemm_grouped(
             0 if dtype == F16 else 1, c["bits"], c["g"], E, T, N, K, c["Q"].shape[1], c["tid"],
             xbuf[guard:].data_ptr(), off2.data_ptr(), c["Q"].data_ptr(), c["S"].data_ptr(), c["t2"].data_ptr(),
             ybuf[guard:].data_ptr(), env.num_sms, torch.cuda.current_stream(d).cuda_stream)
@@ -252,7 +164,7 @@ def test_past_32_bit_limits(env):
     if free < 16 * 2 ** 30:
         pytest.skip("needs 16 GiB of free device memory, %.1f GiB free" % (free / 2 ** 30))
     bits, g, dtype, N, K, E = 4, 64, F16, 8192, 8192, 136
-    tid = first_template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     gen = torch.Generator(device=d).manual_seed(11)
     Q = torch.randint(-32768, 32767, (E, bits * N // 16, K), dtype=torch.int16, device=d, generator=gen)
     S = (torch.rand(E, N, K // g, device=d, generator=gen) * 0.02 + 0.005).to(dtype)
@@ -270,34 +182,6 @@ def test_past_32_bit_limits(env):
         del W
     del Q, S, Y
     torch.cuda.empty_cache()
-
-
-@pytest.fixture(scope="module")
-def experts_case(env):
-    """E = 4 experts from FluteLinear.from_codes (4-bit, g = 64, K = 256, N_ff = 512), T = 37 tokens, top-2 routing among
-    experts 0, 1, 3: expert 2 is never chosen."""
-    d, dtype = env.dev, F16
-    E, K, F, T, k, bits, g = 4, 256, 512, 37, 2, 4, 64
-    tid = first_template(env.fa, bits, 32)
-    gen = torch.Generator().manual_seed(21)
-    nf4 = torch.tensor(env.O.NF4_VALUES).to(dtype)
-
-    def linear(kk, nn):
-        codes = torch.randint(0, 16, (kk, nn), generator=gen, dtype=torch.uint8).to(d)
-        scales = (torch.rand(nn, kk // g, generator=gen) * 0.1 + 0.02).to(dtype).to(d)
-        return env.FluteLinear.from_codes(codes, scales, nf4.to(d), bits, g, tid)
-
-    c = dict(E=E, K=K, F=F, T=T, k=k, bits=bits, g=g, tid=tid, dtype=dtype)
-    c["gates"], c["ups"], c["downs"] = ([linear(K, F) for _ in range(E)], [linear(K, F) for _ in range(E)],
-                                        [linear(F, K) for _ in range(E)])
-    c["experts"] = env.moe.FluteExperts.from_linears(c["gates"], c["ups"], c["downs"])
-    c["hidden"] = torch.randn(T, K, generator=gen).to(dtype).to(d)
-    choice = torch.tensor([[0, 1], [1, 3], [3, 0], [0, 3], [3, 1], [1, 0]])
-    c["ids"] = choice[torch.randint(0, len(choice), (T,), generator=gen)].to(d)
-    c["ids2"] = choice[torch.randint(0, len(choice), (T,), generator=gen)].flip(0).to(d)
-    weights = torch.rand(T, k, generator=gen)
-    c["weights"] = (weights / weights.sum(1, keepdim=True)).to(dtype).to(d)
-    return c
 
 
 def test_flute_experts_against_loop_and_fp64(env, experts_case):

@@ -10,13 +10,10 @@ import flute_amd
 from flute_amd import _lib
 from flute_amd.integrations.moe import sort_by_expert
 from flute_amd.ops import _validate_grouped
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flute_amd.h")
-
-
-def template(bits, tile_p):
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def call(dtype=0, bits=4, g=64, E=4, T=8, N=1024, K=512, P=None, tid=0, ptrs=(None,) * 6, num_sms=256):
@@ -41,14 +38,14 @@ def test_layer_refusals_with_null_pointers():
     for g in (0, 16, 48, 512):
         assert call(g=g) == ERR_GROUP_SIZE, g
     assert call(tid=10 ** 6) == ERR_TEMPLATE_ID
-    assert call(bits=3, N=512, tid=template(3, 64)) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
+    assert call(bits=3, N=512, tid=first_template(3, 64)) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
 
 
 def test_shape_refusals_with_null_pointers():
     assert call(N=1000) == ERR_SHAPE             # N % (J * TileP)
-    assert call(N=64, tid=template(4, 32)) == ERR_SHAPE
-    assert call(N=128, tid=template(4, 64)) == ERR_SHAPE      # TileP 64: the column block is 256
-    assert call(bits=3, N=256, tid=template(3, 32)) == ERR_SHAPE
+    assert call(N=64, tid=first_template(4, 32)) == ERR_SHAPE
+    assert call(N=128, tid=first_template(4, 64)) == ERR_SHAPE      # TileP 64: the column block is 256
+    assert call(bits=3, N=256, tid=first_template(3, 32)) == ERR_SHAPE
     assert call(K=480) == ERR_SHAPE              # K % 64
     assert call(K=384, g=256) == ERR_SHAPE       # K % g
     assert call(K=0) == ERR_SHAPE

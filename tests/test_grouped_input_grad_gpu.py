@@ -11,36 +11,17 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
-from tests.test_dequant_gpu import first_template
-from tests.test_grouped_gpu import bits16, exact_layers, exact_matrix, exact_seed, offsets_of, random_stack, stack_exact
+from tests.grouped_cases import (counts_of, exact_layers, exact_matrix, exact_seed, gate_formula, random_stack,
+                                 restated_experts, stack_exact)
+from tests.support import bits16, env, first_template, max_rel_err, offsets_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
 
 
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import _lib, utils
-    from flute_amd.integrations import moe
-    from flute_amd.integrations.base import FluteLinear
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.lib, e.utils, e.O, e.moe, e.FluteLinear = flute_amd, _lib, utils, O, moe, FluteLinear
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.RB = flute_amd.ops.GROUPED_INPUT_GRAD_ROW_BLOCK
-    return e
-
-
-def counts_of(RB):
-    """An empty first expert, an empty one in the middle, counts on both sides of the kernel's row block."""
-    return [0, 1, RB - 1, RB, RB + 1, 0, 2 * RB + 3, 5]
+def row_block(env):
+    return env.fa.ops.GROUPED_INPUT_GRAD_ROW_BLOCK
 
 
 def exact_grad(dY, layer):
@@ -80,7 +61,7 @@ def check_exact_grad(layers, counts, dY, dX, dY2=None, layers2=None, row_weight=
 
 
 def grad_matrix():
-    """bits 4 / 3 / 2 x TileP 32 / 64 (3 bits: 32) x the four (g, dtype, pair) rows of test_grouped_gpu.exact_matrix; N = 3
+    """bits 4 / 3 / 2 x TileP 32 / 64 (3 bits: 32) x the four (g, dtype, pair) rows of grouped_cases.exact_matrix; N = 3
     column blocks (>= 6 chunks of the kernel's 64 columns), K = 5 max(64, g): the last 128-k slab is half for g <= 64."""
     out = []
     for bits, tile_p, g, dtype, _, _, pair in exact_matrix():
@@ -90,7 +71,7 @@ def grad_matrix():
 
 @pytest.mark.parametrize("bits,tile_p,g,dtype,K,N,pair", grad_matrix())
 def test_exact_per_expert(env, bits, tile_p, g, dtype, K, N, pair):
-    counts = counts_of(env.RB)
+    counts = counts_of(row_block(env))
     layers = exact_layers(bits, tile_p, g, dtype, K, N, pair, len(counts), exact_seed(bits, tile_p, g) + 300)
     Q, S, t2, tid = stack_exact(env, layers)
     R = sum(counts)
@@ -104,7 +85,7 @@ def test_exact_per_expert(env, bits, tile_p, g, dtype, K, N, pair):
 def small_exact(env):
     """Two exact 4-bit stacks and two integer dY shared by the pair, row-weight, ABI, determinism and graph tests."""
     bits, tile_p, g, dtype, K, N = 4, 32, 64, F16, 320, 3 * 128
-    counts = counts_of(env.RB)
+    counts = counts_of(row_block(env))
     layers = exact_layers(bits, tile_p, g, dtype, K, N, False, len(counts), 9100)
     layers2 = exact_layers(bits, tile_p, g, dtype, K, N, False, len(counts), 9200)
     Q, S, t2, tid = stack_exact(env, layers)
@@ -147,7 +128,7 @@ def abi_call(env, c, off, ybuf, xbuf, guard, pair=False, row_weight=None):
         Q2, S2, t22 = c["stack2"]
         second = (c["dY2_dev"].data_ptr(), Q2.data_ptr(), S2.data_ptr(), t22.data_ptr())
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_qgemm_grouped_input_grad(
+        rc = env.lib.flute_qgemm_grouped_input_grad(
             0 if c["dtype"] == F16 else 1, c["bits"], c["g"], len(c["counts"]), c["R"], c["N"], c["K"], Q.shape[1], c["tid"],
             ybuf[guard:].data_ptr(), off.data_ptr(), Q.data_ptr(), S.data_ptr(), t2.data_ptr(),
             None if row_weight is None else row_weight.data_ptr(), *second, xbuf[guard:].data_ptr(), env.num_sms,
@@ -208,14 +189,14 @@ def test_random_componentwise(env, bits, tile_p, g, dtype):
     """Random codes, scales and tables against the fp64 product with the exact lut * s weight: the gamma bound of an fp32
     sum of N terms over weights rounded once to T, plus the one rounding of the output (XC.assert_componentwise with
     contraction length N)."""
-    counts = [7, 0, env.RB + 12]
+    counts = [7, 0, row_block(env) + 12]
     K, N = 448, 3 * XC.cols_per_block(bits, tile_p)
     Q, S, t2, Ws = random_stack(env, bits, tile_p, g, dtype, K, N, len(counts), seed=bits * 100 + 31)
     gen = torch.Generator().manual_seed(6)
     dY = torch.randn(sum(counts), N, generator=gen).to(dtype)
     off = offsets_of(counts)
     dX = env.fa.qgemm_grouped_input_grad(dY.to(env.dev), off.to(env.dev), Q, S, t2, bits, g,
-                                         first_template(env.fa, bits, tile_p)).cpu()
+                                         first_template(bits, tile_p)).cpu()
     for e, W in enumerate(Ws):                                    # W [K, N]
         r0, r1 = int(off[e]), int(off[e + 1])
         if r1 > r0:
@@ -227,7 +208,7 @@ def test_equal_bits_over_two_calls_and_in_a_graph(env, small_exact):
     contents, bit for bit what an eager call on them returns."""
     c = small_exact
     R, E = c["R"], len(c["counts"])
-    counts2 = [40, 0, 3, 0, R - 40 - 3 - 2 * env.RB - 1, env.RB, 1, env.RB]
+    counts2 = [40, 0, 3, 0, R - 40 - 3 - 2 * row_block(env) - 1, row_block(env), 1, row_block(env)]
     assert sum(counts2) == R and len(counts2) == E and min(counts2) >= 0
     dY2 = XC.make_x(R, c["N"], 9102, c["dtype"], witness=False).to(env.dev)
     off2 = offsets_of(counts2, env.dev)
@@ -390,7 +371,7 @@ def experts_case(env):
     token 0 is routed only to ids outside [0, E), token 5 has one such slot."""
     d, dtype = env.dev, F16
     E, K, F, T, bits, g = 4, 256, 512, 37, 4, 64
-    tid = first_template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     gen = torch.Generator().manual_seed(41)
     nf4 = torch.tensor(env.O.NF4_VALUES).to(dtype)
 
@@ -418,20 +399,6 @@ def experts_case(env):
     return c
 
 
-def restated_experts(c, hidden, ids, weights, project):
-    """The block restated with torch ops: a loop over the experts on rows selected on the host, `project(e, which, x)` the
-    projection `which` (0 gate, 1 up, 2 down) of expert e, silu, the routing weight and index_add_."""
-    out = torch.zeros_like(hidden)
-    for e in range(c["E"]):
-        tok, slot = (ids == e).nonzero(as_tuple=True)
-        if tok.numel() == 0:
-            continue
-        x = hidden[tok]
-        h = torch.nn.functional.silu(project(e, 0, x)) * project(e, 1, x)
-        out = out.index_add(0, tok, project(e, 2, h) * weights[tok, slot][:, None])
-    return out
-
-
 def reference_grads(c, k):
     """(fp64 gradients, the yardstick's gradients in T) of hidden and topk_weights for dOut, computed once per k."""
     if k not in c["refs"]:
@@ -443,10 +410,6 @@ def reference_grads(c, k):
         restated_experts(c, hT, ids, wT, lambda e, which, x: layers[which][e](x)).backward(c["dOut"])
         c["refs"][k] = (h64.grad, w64.grad, hT.grad, wT.grad)
     return c["refs"][k]
-
-
-def rel_err(a, ref):
-    return float((a.double() - ref).abs().max() / ref.abs().max())
 
 
 @pytest.mark.parametrize("k", [2, 3])
@@ -474,8 +437,8 @@ def test_flute_experts_backward(env, experts_case, fused, native, k):
     if native or k == 2:                                           # (index_add_ at top-3: the order of a token's addends is free)
         assert torch.equal(bits16(out), bits16(plain))             # recording a graph does not change the forward
     assert gh is not None and gw is not None and torch.isfinite(gh).all() and torch.isfinite(gw).all()
-    err_h, err_w = rel_err(gh, gh64), rel_err(gw, gw64)
-    yard_h, yard_w = rel_err(ghT, gh64), rel_err(gwT, gw64)
+    err_h, err_w = max_rel_err(gh, gh64), max_rel_err(gw, gw64)
+    yard_h, yard_w = max_rel_err(ghT, gh64), max_rel_err(gwT, gw64)
     print("FluteExperts backward fused=%d native=%d k=%d: hidden.grad %.3e (yardstick %.3e), topk_weights.grad %.3e "
           "(yardstick %.3e)" % (fused, native, k, err_h, yard_h, err_w, yard_w))
     assert yard_h > 0 and yard_w > 0
@@ -492,14 +455,6 @@ def test_flute_experts_backward(env, experts_case, fused, native, k):
 # ---------------------------------------------------------------------------
 # block level
 # ---------------------------------------------------------------------------
-
-def gate_formula(logits, ids, scoring, renormalize, scale):
-    s = torch.softmax(logits, dim=1) if scoring == "softmax" else torch.sigmoid(logits)
-    w = s.gather(1, ids.long())
-    if renormalize:
-        w = w / w.sum(dim=1, keepdim=True)
-    return w * scale
-
 
 BLOCK_CASES = [dict(top_k=2, scoring="softmax", renormalize=False, scale=1.0),
                dict(top_k=2, scoring="sigmoid", renormalize=True, scale=2.5, n_group=2, topk_group=1, bias=True)]
@@ -580,8 +535,8 @@ def test_sparse_moe_block_backward(env, experts_case, case):
     restated_experts(c, hT, ids, wT, lambda e, which, x: layers[which][e](x)).backward(c["dOut"])
     for name, g, g64, g32, dense, gT in (("hidden.grad", gh, gh64.double(), gh32, hd.grad, hT.grad),
                                          ("router_weight.grad", gr, gr64.double(), gr32, rd.grad, rT.grad)):
-        err, yard = rel_err(g, g64), rel_err(g32, g64)
-        err_dense, yard_dense = rel_err(g, dense), rel_err(gT, dense)
+        err, yard = max_rel_err(g, g64), max_rel_err(g32, g64)
+        err_dense, yard_dense = max_rel_err(g, dense), max_rel_err(gT, dense)
         print("FluteSparseMoeBlock %s %s: %.3e against the fp64 formula, the fp32 formula %.3e (ratio %s); %.3e against the "
               "dense fp64 block, the block in T %.3e" % (case["scoring"], name, err, yard, "%.2f" % (err / yard) if yard else "-",
                                                          err_dense, yard_dense))

@@ -9,14 +9,11 @@ import torch
 import flute_amd
 from flute_amd import _lib
 from flute_amd.ops import _validate_grouped_input_grad
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flute_amd.h")
 FAKE = 0x1000            # a host address no refusal may look behind
-
-
-def template(bits, tile_p):
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def igrad(dtype=0, bits=4, g=64, E=4, R=8, N=1024, K=512, P=None, tid=0, ptrs=(None,) * 11, num_sms=256):
@@ -47,10 +44,10 @@ def test_layer_and_shape_refusals_with_null_pointers():
     for g in (0, 16, 48, 512):
         assert igrad(g=g) == ERR_GROUP_SIZE, g
     assert igrad(tid=10 ** 6) == ERR_TEMPLATE_ID
-    assert igrad(bits=3, tid=template(3, 64), N=512) == ERR_TEMPLATE_ID       # 3 bits: TileP 32 only
+    assert igrad(bits=3, tid=first_template(3, 64), N=512) == ERR_TEMPLATE_ID       # 3 bits: TileP 32 only
     assert igrad(dtype=2, bits=5) == ERR_DTYPE                                # the order: dtype first
     assert igrad(N=1000) == ERR_SHAPE
-    assert igrad(tid=template(4, 64), N=128) == ERR_SHAPE                     # TileP 64: the column block is 256
+    assert igrad(tid=first_template(4, 64), N=128) == ERR_SHAPE                     # TileP 64: the column block is 256
     assert igrad(K=480) == ERR_SHAPE
     assert igrad(K=384, g=256) == ERR_SHAPE
     assert igrad(P=255) == ERR_SHAPE

@@ -2,7 +2,7 @@
 lookup tables built on it: dT2[e] = the dense table gradient of expert e over the rows a device-side table gives it, one
 main launch and one reduce launch.
 
-Kernel level, on test_grouped_scale_grad_gpu's case matrix: every non-empty expert's slice is bit for bit
+Kernel level, on the gradient tests' case matrix (grouped_cases.matrix): every non-empty expert's slice is bit for bit
 `qgemm_table_grad` on its rows (the dense launch never splits M at these counts), empty experts are zeros, NaN rows past
 offsets[E] stay out, the fused scale gradient is `qgemm_grouped_scale_grad`'s; the row weight is bit for bit a
 pre-multiplied dY; random data stays within the componentwise bound of the documented chain depth; exact layers equal
@@ -17,29 +17,23 @@ import torch
 from tests import exact_cases as XC
 from tests import scale_grad_ref as SR
 from tests import table_grad_ref as TR
-from tests.test_dequant_gpu import first_template
-from tests.test_grouped_gpu import bits16, exact_layers, exact_seed, offsets_of, stack_exact
-from tests.test_grouped_input_grad_gpu import gate_formula, rel_err, restated_experts
-from tests.test_grouped_scale_grad_gpu import (BF16, COUNTS, F16, HALF_SUB, MIN_NORMAL, PAD, env, matrix,  # noqa: F401
-                                               padded, tiny)
-from tests.test_table_grad_gpu import exact_inputs, exact_premise, exact_scales
+from tests.grouped_cases import (BF16, F16, GRAD_COUNTS, HALF_SUB, MIN_NORMAL, PAD, exact_inputs, exact_layers,  # noqa: F401
+                                 exact_premise, exact_scales, exact_seed, gate_formula, matrix, nan_padded, restated_experts,
+                                 stack_exact, tiny)
+from tests.support import bits16, bits32, env, first_template, max_rel_err, offsets_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-def bits32(t):
-    return t.contiguous().view(torch.int32)
-
-
 def random_case_of(env, bits, tile_p, g, dtype, pair, K, N):
-    """A random stack (codes, random scales as test_table_grad_gpu.random_layer's, an NF-style table or a pair codebook
-    per expert), random dY and X with NaN rows past offsets[E], a row weight, and the launches every test of the case
-    reads - computed once."""
+    """A random stack (codes, random scales as the random_layer of test_table_grad_gpu.py draws them, an NF-style table
+    or a pair codebook per expert), random dY and X with NaN rows past offsets[E], a row weight, and the launches every
+    test of the case reads - computed once."""
     key = ("table_grad", bits, tile_p, g, dtype, pair, K, N)
     if key not in env.cache:
-        d, E, Rs, n = env.dev, len(COUNTS), sum(COUNTS), 2 ** bits
-        assert max(COUNTS) <= 224                                    # the dense launch splits M from 8 steps of 32 rows on
-        tid = first_template(env.fa, bits, tile_p)
+        d, E, Rs, n = env.dev, len(GRAD_COUNTS), sum(GRAD_COUNTS), 2 ** bits
+        assert max(GRAD_COUNTS) <= 224                                    # the dense launch splits M from 8 steps of 32 rows on
+        tid = first_template(bits, tile_p)
         gen = torch.Generator().manual_seed(exact_seed(bits, tile_p, g) + 11)
         W = torch.randint(0, n, (E, K, N), generator=gen, dtype=torch.uint8).to(d)
         S = (torch.randn(E, N, K // g, generator=gen) / 8).to(dtype).to(d)
@@ -49,10 +43,10 @@ def random_case_of(env, bits, tile_p, g, dtype, pair, K, N):
             t2 = torch.stack([env.O.make_qmap2_from_qmap(torch.randn(n, generator=gen).sort().values.to(dtype))
                               for _ in range(E)])
         Q = torch.stack([env.utils.pack(W[e], bits, [tid], env.num_sms) for e in range(E)])
-        dY = padded(torch.randn(Rs, N, generator=gen).to(dtype)).to(d)
-        X = padded(torch.randn(Rs, K, generator=gen).to(dtype)).to(d)
+        dY = nan_padded(torch.randn(Rs, N, generator=gen).to(dtype)).to(d)
+        X = nan_padded(torch.randn(Rs, K, generator=gen).to(dtype)).to(d)
         rw = torch.cat([torch.rand(Rs, generator=gen) * 1.5 + 0.25, torch.full((PAD,), float("nan"))]).to(d)
-        c = dict(W=W, Q=Q, S=S, t2=t2.to(d), dY=dY, X=X, rw=rw, off=offsets_of(COUNTS, d), tid=tid, R=Rs + PAD,
+        c = dict(W=W, Q=Q, S=S, t2=t2.to(d), dY=dY, X=X, rw=rw, off=offsets_of(GRAD_COUNTS, d), tid=tid, R=Rs + PAD,
                  bits=bits, g=g, dtype=dtype, K=K, N=N)
         f = env.fa.qgemm_grouped_table_grad
         c["dT"] = f(dY, X, c["off"], Q, S, bits, g, tid)
@@ -66,12 +60,12 @@ def random_case_of(env, bits, tile_p, g, dtype, pair, K, N):
 @pytest.mark.parametrize("bits,tile_p,g,dtype,pair,K,N", matrix())
 def test_bit_equal_with_dense_op(env, bits, tile_p, g, dtype, pair, K, N):
     c = random_case_of(env, bits, tile_p, g, dtype, pair, K, N)
-    n, E = 2 ** bits, len(COUNTS)
+    n, E = 2 ** bits, len(GRAD_COUNTS)
     dT = c["dT"]
     assert dT.shape == (E, n, n, 2) and dT.dtype == torch.float32
     assert torch.isfinite(dT).all()                                  # the NaN rows past offsets[E] were not read
-    off = offsets_of(COUNTS).tolist()
-    for e, m in enumerate(COUNTS):
+    off = offsets_of(GRAD_COUNTS).tolist()
+    for e, m in enumerate(GRAD_COUNTS):
         if m == 0:
             assert torch.all(bits32(dT[e]) == 0), e
             continue
@@ -109,9 +103,9 @@ def test_random_within_componentwise_bound(env, bits, tile_p, g, dtype, pair, K,
     MIN_NORMAL (in bf16 there are none).  The result is fp32 and of order one: it has no rounding or underflow term."""
     c = random_case_of(env, bits, tile_p, g, dtype, pair, K, N)
     u, sub, tiny_ = XC.U_T[dtype], HALF_SUB[dtype], MIN_NORMAL[dtype]
-    off = offsets_of(COUNTS).tolist()
+    off = offsets_of(GRAD_COUNTS).tolist()
     worst = 0.0
-    for e, m in enumerate(COUNTS):
+    for e, m in enumerate(GRAD_COUNTS):
         if m == 0:
             continue
         r0, r1 = off[e], off[e + 1]
@@ -134,17 +128,17 @@ def test_random_within_componentwise_bound(env, bits, tile_p, g, dtype, pair, K,
 @pytest.mark.parametrize("bits,tile_p,g,dtype,pair,K,N", matrix())
 def test_exact_layers(env, bits, tile_p, g, dtype, pair, K, N):
     """X and dY multiples of 1/4, scales +-2^e, exact tables: every term is a multiple of 2^-5 and every bin's sum of |terms|
-    stays below 2^24 quanta (test_table_grad_gpu.exact_premise asserts it), so every partial sum in any order is exact in
+    stays below 2^24 quanta (grouped_cases.exact_premise asserts it), so every partial sum in any order is exact in
     fp32 and the fp64 sum is the only allowed answer - for dT2 by value, for the fused dS after its one rounding."""
-    d, E = env.dev, len(COUNTS)
+    d, E = env.dev, len(GRAD_COUNTS)
     layers = exact_layers(bits, tile_p, g, dtype, K, N, pair, E, exact_seed(bits, tile_p, g) + 700)
     Q, _, t2, tid = stack_exact(env, layers)
     S = torch.stack([exact_scales(N, K // g, dtype, seed=701 + g + e) for e in range(E)]).to(d)
-    parts = [exact_inputs(m, K, N, dtype, seed=702 + g + e) for e, m in enumerate(COUNTS)]
-    X, dY = (padded(torch.cat([p[i] for p in parts])).to(d) for i in range(2))
-    dT, dS = env.fa.qgemm_grouped_table_grad(dY, X, offsets_of(COUNTS, d), Q, S, bits, g, tid, table2=t2,
+    parts = [exact_inputs(m, K, N, dtype, seed=702 + g + e) for e, m in enumerate(GRAD_COUNTS)]
+    X, dY = (nan_padded(torch.cat([p[i] for p in parts])).to(d) for i in range(2))
+    dT, dS = env.fa.qgemm_grouped_table_grad(dY, X, offsets_of(GRAD_COUNTS, d), Q, S, bits, g, tid, table2=t2,
                                              with_scale_grad=True)
-    off = offsets_of(COUNTS).tolist()
+    off = offsets_of(GRAD_COUNTS).tolist()
     for e, lay in enumerate(layers):
         r0, r1 = off[e], off[e + 1]
         if r1 == r0:
@@ -170,22 +164,22 @@ def test_direct_abi_writes_exactly_dT2_and_dS(env, small):
     are written, finite, the wrapper's bits.  Malformed tables (negative entries, entries above R, a decreasing pair) give
     the clamped table's result with the guards intact."""
     c = small
-    d, dtype, K, N, g, bits, E = env.dev, c["dtype"], c["K"], c["N"], c["g"], c["bits"], len(COUNTS)
+    d, dtype, K, N, g, bits, E = env.dev, c["dtype"], c["K"], c["N"], c["g"], c["bits"], len(GRAD_COUNTS)
     G, nb = K // g, 2 * 4 ** bits
     guard, n_t, n_s = 4096, E * nb, E * N * G
     nan32, nan16 = 0x7FC00000, XC.NAN_BITS[dtype]
-    nbytes = env.lib.get().flute_qgemm_grouped_table_grad_scratch_bytes(bits, g, E, N, K)
+    nbytes = env.lib.flute_qgemm_grouped_table_grad_scratch_bytes(bits, g, E, N, K)
     assert nbytes == E * (N // 128) * -(-K // 256) * nb * 4
     tbuf = torch.empty(guard + n_t + guard, dtype=torch.int32, device=d)
     sbuf = torch.empty(guard + n_s + guard, dtype=torch.int16, device=d)
     scratch = torch.empty(nbytes // 4 + guard, dtype=torch.int32, device=d)
-    full = offsets_of(COUNTS)
+    full = offsets_of(GRAD_COUNTS)
 
     def run(off, with_ds=True, row_weight=None, R=None, E_=None, scratch_bytes=nbytes):
         tbuf.fill_(nan32), sbuf.fill_(nan16), scratch.fill_(nan32)
         off = off.to(d)
         with torch.cuda.device(d):
-            rc = env.lib.get().flute_qgemm_grouped_table_grad(
+            rc = env.lib.flute_qgemm_grouped_table_grad(
                 0 if dtype == F16 else 1, bits, g, E if E_ is None else E_, c["R"] if R is None else R, N, K,
                 c["Q"].shape[1], c["tid"], c["dY"].data_ptr(), c["X"].data_ptr(), off.data_ptr(), c["Q"].data_ptr(),
                 c["S"].data_ptr(), c["t2"].data_ptr() if with_ds else None,
@@ -229,7 +223,7 @@ def test_direct_abi_writes_exactly_dT2_and_dS(env, small):
     assert torch.equal(bits32(t), bits32(c["bothw"][0].view(E, -1))) and torch.equal(bits16(s), bits16(c["bothw"][1]))
     rc, t, s = run(full, with_ds=False)                             # table only: dS stays untouched
     assert rc == 0 and torch.equal(bits32(t), bits32(c["dT"].view(E, -1))) and torch.all(bits16(s) == nan16)
-    Rs = sum(COUNTS)
+    Rs = sum(GRAD_COUNTS)
     check(full.clamp(max=2 * Rs // 3))                              # a proper table that ends early
     neg = full.clone()
     neg[:3] = torch.tensor([-5, -1, -70])
@@ -243,7 +237,7 @@ def test_direct_abi_writes_exactly_dT2_and_dS(env, small):
     # `full` itself is then a table that runs past R (expert 6 loses its last 5 rows, expert 7 all of them: zeros), and in
     # `past` expert 5's end is R + 1 (it gets the rows [97, R) expert 6 had) and experts 6 and 7 start at or past R: zeros
     Rc = Rs - 10
-    assert full[6] < Rc < full[7] and COUNTS[5] == 0
+    assert full[6] < Rc < full[7] and GRAD_COUNTS[5] == 0
     past = full.clone()
     past[-3:] = torch.tensor([Rc + 1, Rc + 1000, 2 ** 31 - 1])
     for off in (full, past):
@@ -273,12 +267,12 @@ def test_equal_bits_over_calls_and_graph_replays(env):
     graph: the same bits every time.  The host reads nothing: a replay after `offsets`, dY and X were overwritten in
     place serves the new contents, bit for bit what an eager call on them returns."""
     c = random_case_of(env, 2, 32, 64, F16, False, 320, 256)
-    d, E = env.dev, len(COUNTS)
-    counts2 = [40, 0, 3, 0, 60, 33, 1, sum(COUNTS) - 137]
-    assert sum(counts2) == sum(COUNTS) and len(counts2) == E and min(counts2) >= 0
+    d, E = env.dev, len(GRAD_COUNTS)
+    counts2 = [40, 0, 3, 0, 60, 33, 1, sum(GRAD_COUNTS) - 137]
+    assert sum(counts2) == sum(GRAD_COUNTS) and len(counts2) == E and min(counts2) >= 0
     gen = torch.Generator().manual_seed(78)
-    dY2 = padded(torch.randn(sum(COUNTS), c["N"], generator=gen).to(c["dtype"])).to(d)
-    X2 = padded(torch.randn(sum(COUNTS), c["K"], generator=gen).to(c["dtype"])).to(d)
+    dY2 = nan_padded(torch.randn(sum(GRAD_COUNTS), c["N"], generator=gen).to(c["dtype"])).to(d)
+    X2 = nan_padded(torch.randn(sum(GRAD_COUNTS), c["K"], generator=gen).to(c["dtype"])).to(d)
     off2 = offsets_of(counts2, d)
     dy, x, off = c["dY"].clone(), c["X"].clone(), c["off"].clone()
     run = lambda a, b, o: env.fa.qgemm_grouped_table_grad(a, b, o, c["Q"], c["S"], c["bits"], c["g"], c["tid"], env.num_sms,
@@ -310,9 +304,9 @@ def test_nan_stays_in_the_bins_the_formula_names(env, small):
     of pair row 130): dT2[6] is NaN in exactly the bins (c, 1) whose pair index c occurs at pair row 130 of expert 6's
     codes, and every other bin of every expert - and every other expert's dS - keeps the clean run's bits."""
     c = small
-    bits, g, E = c["bits"], c["g"], len(COUNTS)
+    bits, g, E = c["bits"], c["g"], len(GRAD_COUNTS)
     e, k = 6, 261
-    off = offsets_of(COUNTS).tolist()
+    off = offsets_of(GRAD_COUNTS).tolist()
     X = c["X"].clone()
     X[off[e] + 40, k] = float("nan")
     dT, dS = env.fa.qgemm_grouped_table_grad(c["dY"], X, c["off"], c["Q"], c["S"], bits, g, c["tid"], table2=c["t2"],
@@ -439,12 +433,12 @@ NAMES = ("gate", "up", "down")
 
 
 def make_experts_case(env, dtype):
-    """test_grouped_scale_grad_gpu.make_experts_case with the codes kept: E = 4 experts from FluteLinear.from_codes (4-bit,
-    g = 64, K = 256, F = 512) with a table of their own each, 37 tokens; expert 2 is never chosen, token 0 is routed only
-    to ids outside [0, E), token 5 has one such slot."""
+    """The make_experts_case of test_grouped_scale_grad_gpu.py with the codes kept: E = 4 experts from
+    FluteLinear.from_codes (4-bit, g = 64, K = 256, F = 512) with a table of their own each, 37 tokens; expert 2 is never
+    chosen, token 0 is routed only to ids outside [0, E), token 5 has one such slot."""
     d = env.dev
     E, K, F, T, bits, g = 4, 256, 512, 37, 4, 64
-    tid = first_template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     gen = torch.Generator().manual_seed(43)
     nf4 = torch.tensor(env.O.NF4_VALUES)
     c = dict(E=E, K=K, F=F, T=T, bits=bits, g=g, tid=tid, dtype=dtype, codes=[[], [], []], layers=([], [], []))
@@ -545,7 +539,7 @@ def test_flute_experts_codebook_grads(env, experts_case, fused, native, k, table
     for name, p, s, r, y in zip(NAMES, params[1::2], params[0::2], ref, yard):
         assert p.grad is not None and p.grad.shape == p.shape and p.grad.dtype == torch.float32
         assert torch.isfinite(p.grad).all() and s.grad is not None
-        err, yerr = rel_err(p.grad, r), rel_err(y, r)
+        err, yerr = max_rel_err(p.grad, r), max_rel_err(y, r)
         print("FluteExperts codebook.grad %s fused=%d native=%d k=%d %s: %.3e (yardstick %.3e)"
               % (table, fused, native, k, name, err, yerr))
         assert yerr > 0
@@ -591,7 +585,7 @@ def test_sparse_moe_block_codebook_grads(env, experts_case, table):
     wT = gate_formula(torch.nn.functional.linear(c["hidden"], router).float(), ids, scoring, renorm, scale).to(dtype)
     restated_experts(c, c["hidden"], ids, wT, lambda e, which, x: loop[which][e](x)).backward(c["dOut"])
     for name, p, leaf, y in zip(NAMES, params[1::2], C64, loop_grads(loop)):
-        err, yerr = rel_err(p.grad, leaf.grad), rel_err(y, leaf.grad)
+        err, yerr = max_rel_err(p.grad, leaf.grad), max_rel_err(y, leaf.grad)
         print("FluteSparseMoeBlock codebook.grad %s %s: %.3e (yardstick %.3e)" % (table, name, err, yerr))
         assert yerr > 0
         assert err <= 2 * yerr, (name, err, yerr)

@@ -10,6 +10,7 @@ import torch
 
 import flute_amd
 from flute_amd import _lib
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flute_amd.h")
@@ -26,10 +27,6 @@ def header_value(name):
 
 
 ERR_WORKSPACE = header_value("FLUTE_ERR_WORKSPACE")
-
-
-def template(bits, tile_p):
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def query(bits=4, g=64, E=4, N=1024, K=512):
@@ -67,11 +64,11 @@ def test_layer_and_shape_refusals_with_null_and_host_pointers():
         for g in (0, 16, 48, 512):
             assert tgrad(g=g, **kw) == ERR_GROUP_SIZE, g
         assert tgrad(tid=10 ** 6, **kw) == ERR_TEMPLATE_ID
-        assert tgrad(bits=3, tid=template(3, 64), N=512, **kw) == ERR_TEMPLATE_ID   # 3 bits: TileP 32 only
+        assert tgrad(bits=3, tid=first_template(3, 64), N=512, **kw) == ERR_TEMPLATE_ID   # 3 bits: TileP 32 only
         assert tgrad(dtype=2, bits=5, **kw) == ERR_DTYPE                          # the order: dtype first
         assert tgrad(N=1000, **kw) == ERR_SHAPE
         assert tgrad(N=64, **kw) == ERR_SHAPE                                      # N % 128
-        assert tgrad(tid=template(4, 64), N=128, **kw) == ERR_SHAPE                # TileP 64: the column block is 256
+        assert tgrad(tid=first_template(4, 64), N=128, **kw) == ERR_SHAPE                # TileP 64: the column block is 256
         assert tgrad(K=480, **kw) == ERR_SHAPE                                     # K % 64
         assert tgrad(K=384, g=256, **kw) == ERR_SHAPE                              # K % g
         assert tgrad(K=96, g=32, **kw) == ERR_SHAPE                                # K % max(64, g)

@@ -26,7 +26,8 @@ import pytest
 import torch
 
 from tests import exact_cases as E
-from tests.test_exact_gpu import DevLayer, _bits, seed_of, state_words_clean
+from tests.qgemm_cases import DevLayer, seed_of, state_words_clean
+from tests.support import bits_by_size, make_env
 
 pytestmark = pytest.mark.gpu
 
@@ -43,19 +44,7 @@ GIB = 1 << 30
 
 @pytest.fixture(scope="module")
 def env():
-    import flute_amd
-    from flute_amd import _lib, dev, utils
-    from flute_amd.ops import _stream_ptr
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.lib, e.dev_mod, e.utils = flute_amd, _lib.get(), dev, utils
-    e.check, e.stream_ptr = _lib.check, _stream_ptr
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
+    e = make_env()
     torch.cuda.reset_peak_memory_stats(e.dev)
     yield e
     print("peak device memory: %.2f GiB" % (torch.cuda.max_memory_allocated(e.dev) / GIB))
@@ -158,7 +147,7 @@ def guarded_launch(env, ex, X, M, ovr, family, R, cfg=None):
     assert plan["family"] in family and cfg in (None, plan["m_block"]), (M, ovr, plan)
     buf = torch.full((GUARD + M * N + GUARD,), E.NAN_BITS[T], dtype=torch.int16, device=env.dev)
     D = buf[GUARD:GUARD + M * N].view(T)
-    before = [_bits(t) for t in (Xm, dl.Q, dl.S, dl.table, dl.table2)]
+    before = [bits_by_size(t) for t in (Xm, dl.Q, dl.S, dl.table, dl.table2)]
     with torch.cuda.device(env.dev):
         rc = env.lib.flute_qgemm_ex(
             0 if T == torch.float16 else 1, lay.bits, lay.g, 0, M, N, K, dl.Q.shape[0],
@@ -170,7 +159,7 @@ def guarded_launch(env, ex, X, M, ovr, family, R, cfg=None):
     D = D.view(M, N)
     for r0 in range(0, M, ROWS):
         assert not torch.isnan(D[r0:r0 + ROWS]).any(), ("output element left unwritten", r0)
-    after = [_bits(t) for t in (Xm, dl.Q, dl.S, dl.table, dl.table2)]
+    after = [bits_by_size(t) for t in (Xm, dl.Q, dl.S, dl.table, dl.table2)]
     assert all(torch.equal(a, b) for a, b in zip(before, after)), "an input was modified"
     del before, after
     assert state_words_clean(env), "state words left set"
@@ -214,7 +203,7 @@ def test_x32_edge_and_past_4gib_deep_layers(env):
                 D2 = env.fa.qgemm(X[:M_REF], dl.Q, dl.S, dl.table, dl.table2, env.ws, 4, 64, dl.tid, env.num_sms)
                 D3 = env.fa.qgemm(X3, dl.Q, dl.S, dl.table, dl.table2, env.ws, 4, 64, dl.tid, env.num_sms)
                 assert D3.shape == (3, M_REF // 3, ex.lay.N)
-                assert torch.equal(_bits(D3.reshape(M_REF, -1)), _bits(D2)), "3-D call differs from the 2-D call"
+                assert torch.equal(bits_by_size(D3.reshape(M_REF, -1)), bits_by_size(D2)), "3-D call differs from the 2-D call"
                 assert_equal_rows(D2, R[:M_REF], "operator")
                 del D2, D3
             if kw["bits"] == 3:                                                   # 3-bit blocks, 2 GiB < X < 4 GiB
@@ -297,10 +286,10 @@ def test_hadamard_two_launch_past_4gib(env, h):
     assert env.lib.flute_qgemm_hadamard_fused(0, 4, 64, h, M, lay.N, K, dl.tid, env.num_sms, env.ws.numel()) == 0
     fam = env.dev_mod.get_plan(M, lay.N, K, 4, 64, dl.tid, env.num_sms, dtype)["family"]
     assert fam == 2, fam                                          # past x32_ok: the per-wave kernel
-    before = _bits(X)
+    before = bits_by_size(X)
     D = env.fa.qgemm_hadamard(X, dl.Q, dl.S, dl.table, dl.table2, env.ws, 4, 64, h, dl.tid, env.num_sms)
     torch.cuda.synchronize()
-    assert torch.equal(before, _bits(X)), "the activations were modified"
+    assert torch.equal(before, bits_by_size(X)), "the activations were modified"
     del before
     assert state_words_clean(env)
     assert_equal_rows(D, R, ("hadamard", h))

@@ -22,15 +22,14 @@ import pytest
 import torch
 
 from tests import moe_gate_ref as R
-from tests.test_grouped_gpu import bits16, env  # noqa: F401
-from tests.test_moe_route_gpu import CANARY, host_route, intact, native, padded, top3_case  # noqa: F401
+from tests.moe_cases import (CANARY, canary_padded, draw_bias, draw_logits, gate_abi, host_route, intact, native, same_bits,  # noqa: F401
+                             top3_case)
+from tests.support import bits16, env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
 I32 = torch.int32
-DTYPE_CODE = {F16: 0, BF16: 1, F32: 2}
-SCORING_CODE = {"softmax": 0, "sigmoid": 1}
 GAP = 2.0 ** -16
 
 SHAPES = [
@@ -47,10 +46,6 @@ SHAPES = [
 
 # ---- inputs and calls --------------------------------------------------------------------------------------------------------
 
-def draw_logits(T, E, dtype, seed, spread=2.0):
-    return (torch.randn(T, E, generator=torch.Generator().manual_seed(seed)) * spread).to(dtype)
-
-
 def draw_separated(T, E, k, dtype, scoring, bias, seed, key_of=None):
     """Logits whose fp64 keys (score + bias, or `key_of`) satisfy the 2^-16 condition in every token: tokens that fail are
     drawn again with the next seed."""
@@ -62,45 +57,6 @@ def draw_separated(T, E, k, dtype, scoring, bias, seed, key_of=None):
             return x
         x[bad] = draw_logits(T, E, dtype, seed + 7919 * attempt)[bad]
     raise AssertionError("no separated draw for %s" % ((T, E, k, dtype, scoring),))
-
-
-def draw_bias(E, seed):
-    return torch.randn(E, generator=torch.Generator().manual_seed(seed))
-
-
-def gate_abi(env, logits, k, scoring="softmax", renormalize=False, bias=None, scale=1.0, routed=False):
-    """The direct call with every output in the middle of a larger buffer: (ids, weights) or, routed, also (offsets, rows,
-    row_weight, pos, perm)."""
-    d = env.dev
-    T, E = logits.shape
-    P = T * k
-    sizes = dict(ids=P, weights=P)
-    if routed:
-        sizes.update(offsets=E + 1, perm=P, rows=P, row_weight=P, pos=P)
-    bufs = {n: padded(s, F32 if n in ("weights", "row_weight") else I32, d) for n, s in sizes.items()}
-    head = (DTYPE_CODE[logits.dtype], T, E, k, SCORING_CODE[scoring], int(renormalize), float(scale), logits.data_ptr(),
-            None if bias is None else bias.data_ptr(), bufs["ids"][1].data_ptr(), bufs["weights"][1].data_ptr())
-    lib = env.lib.get()
-    with torch.cuda.device(d):
-        stream = torch.cuda.current_stream(d).cuda_stream
-        if routed:
-            rc = lib.flute_moe_gate_route(*head, *(bufs[n][1].data_ptr() for n in ("offsets", "perm", "rows", "row_weight", "pos")),
-                                          stream)
-        else:
-            rc = lib.flute_moe_gate(*head, stream)
-    assert rc == 0
-    torch.cuda.synchronize()
-    for n, s in sizes.items():
-        assert intact(bufs[n][0], s), "canary around " + n
-    out = {n: bufs[n][1] for n in sizes}
-    ids, weights = out["ids"].view(T, k), out["weights"].view(T, k)
-    if not routed:
-        return ids, weights
-    return ids, weights, out["offsets"], out["rows"], out["row_weight"], out["pos"].view(T, k), out["perm"]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(I32), b.contiguous().view(I32))
 
 
 # ---- 1. the choice, value for value ------------------------------------------------------------------------------------------

@@ -20,16 +20,14 @@ import torch
 
 from tests import moe_gate_limited_ref as L
 from tests import moe_gate_ref as R
-from tests.test_grouped_gpu import bits16, env  # noqa: F401
-from tests.test_moe_gate_gpu import draw_bias, draw_logits, gate_abi, same_bits
-from tests.test_moe_route_gpu import host_route, intact, native, padded, top3_case  # noqa: F401
+from tests.moe_cases import (DTYPE_CODE, SCORING_CODE, canary_padded, draw_bias, draw_logits, gate_abi, host_route, intact,  # noqa: F401
+                             native, same_bits, top3_case)
+from tests.support import bits16, env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
 I32 = torch.int32
-DTYPE_CODE = {F16: 0, BF16: 1, F32: 2}
-SCORING_CODE = {"softmax": 0, "sigmoid": 1}
 GROUP_SCORE_CODE = {"max": 0, "top2sum": 1}
 GAP = 2.0 ** -16
 
@@ -75,11 +73,11 @@ def limited_abi(env, logits, k, n_group, topk_group, scoring="softmax", renormal
     sizes = dict(ids=P, weights=P)
     if routed:
         sizes.update(offsets=E + 1, perm=P, rows=P, row_weight=P, pos=P)
-    bufs = {n: padded(s, F32 if n in ("weights", "row_weight") else I32, d) for n, s in sizes.items()}
+    bufs = {n: canary_padded(s, F32 if n in ("weights", "row_weight") else I32, d) for n, s in sizes.items()}
     head = (DTYPE_CODE[logits.dtype], T, E, k, n_group, topk_group, GROUP_SCORE_CODE[group_score], SCORING_CODE[scoring],
             int(renormalize), float(scale), logits.data_ptr(), None if bias is None else bias.data_ptr(),
             bufs["ids"][1].data_ptr(), bufs["weights"][1].data_ptr())
-    lib = env.lib.get()
+    lib = env.lib
     with torch.cuda.device(d):
         stream = torch.cuda.current_stream(d).cuda_stream
         if routed:

@@ -10,7 +10,7 @@ slot order from +0, skipped slots adding +0, one rounding.  At k = 8 also elemen
     |out - S| <= u_T |S| + (k - 1) 2^-24 sum_j |y_j| + eta_T,
 
 the bound of k - 1 fp32 additions (each partial sum is at most sum |y_j| in magnitude, each addition within 2^-24
-relative) and one rounding to T (eta_T: T's smallest subnormal step, as in tests/test_grouped_glu_gpu.py).
+relative) and one rounding to T (eta_T: T's smallest subnormal step, as in tests/grouped_cases.py).
 
 Module.  FluteExperts(native_routing=True) bit for bit what the same launches give when sort_by_expert drives them and
 the torch restatement combines them; top-3 against fp64 within twice the per-expert loop's own error; in a graph; ids
@@ -19,8 +19,9 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
-from tests.test_dequant_gpu import first_template
-from tests.test_grouped_gpu import bits16, env, experts_case  # noqa: F401
+from tests.grouped_cases import experts_case  # noqa: F401
+from tests.moe_cases import CANARY, GUARD, canary_padded, host_route, intact, native, top3_case  # noqa: F401
+from tests.support import bits16, env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -29,38 +30,9 @@ I32, I64 = torch.int32, torch.int64
 ETA = {F16: 2.0 ** -24, BF16: 2.0 ** -126}
 ID_CODE = {I32: 0, I64: 1}
 WEIGHT_CODE = {F16: 0, BF16: 1, F32: 2}
-CANARY = -0x5A5A5A5B
-GUARD = 32
 
 
 # ---- route ---------------------------------------------------------------------------------------------------------------
-
-def host_route(ids, k, E):
-    """The contract as a naive loop over the flattened ids (Python ints): offsets, perm, rows, pos."""
-    P = len(ids)
-    bucket = [v if 0 <= v < E else E for v in ids]
-    perm = []
-    offsets = []
-    for b in range(E + 1):
-        offsets.append(len(perm))
-        for p in range(P):
-            if bucket[p] == b:
-                perm.append(p)
-    assert len(perm) == P
-    pos = [0] * P
-    for i, p in enumerate(perm):
-        pos[p] = i
-    return offsets, perm, [p // k for p in perm], pos
-
-
-def padded(n, dtype, dev):
-    buf = torch.full((GUARD + n + GUARD,), CANARY, dtype=torch.int32, device=dev)
-    return buf, buf[GUARD:GUARD + n].view(dtype)
-
-
-def intact(buf, n):
-    return bool(torch.all(buf[:GUARD] == CANARY)) and bool(torch.all(buf[GUARD + n:] == CANARY))
-
 
 def route_abi(env, ids, weights, E):
     """The direct call with every output in the middle of a larger buffer: (offsets, rows, row_weight, pos, perm)."""
@@ -68,10 +40,10 @@ def route_abi(env, ids, weights, E):
     T, k = ids.shape
     P = T * k
     sizes = dict(offsets=E + 1, perm=P, rows=P, row_weight=P, pos=P)
-    bufs = {n: padded(s, F32 if n == "row_weight" else I32, d) for n, s in sizes.items()}
+    bufs = {n: canary_padded(s, F32 if n == "row_weight" else I32, d) for n, s in sizes.items()}
     ptr = lambda n: bufs[n][1].data_ptr() if sizes[n] else None
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_moe_route(
+        rc = env.lib.flute_moe_route(
             ID_CODE[ids.dtype], 0 if weights is None else WEIGHT_CODE[weights.dtype], T, k, E, ids.data_ptr() or None,
             None if weights is None else weights.data_ptr(), bufs["offsets"][1].data_ptr(), ptr("perm"), ptr("rows"),
             None if weights is None else ptr("row_weight"), ptr("pos"), torch.cuda.current_stream(d).cuda_stream)
@@ -200,7 +172,7 @@ def combine_abi(env, Y, pos, offsets):
     canary = XC.NAN_BITS[Y.dtype]
     buf = torch.full((GUARD + T * N + GUARD,), canary, dtype=torch.int16, device=d)
     with torch.cuda.device(d):
-        rc = env.lib.get().flute_moe_combine(
+        rc = env.lib.flute_moe_combine(
             0 if Y.dtype == F16 else 1, T, k, offsets.shape[0] - 1, N, Y.data_ptr() or None, pos.data_ptr() or None,
             offsets.data_ptr(), buf[GUARD:].data_ptr(), torch.cuda.current_stream(d).cuda_stream)
     assert rc == 0
@@ -298,10 +270,6 @@ def reference_forward(env, c, experts, hidden, ids, weights, fused):
     return combine_reference(y, pos.reshape(ids.shape), offsets)
 
 
-def native(env, c, fused):
-    return env.moe.FluteExperts.from_linears(c["gates"], c["ups"], c["downs"], fused=fused, native_routing=True)
-
-
 @pytest.fixture(scope="module")
 def native_fused(env, experts_case):
     return native(env, experts_case, True)
@@ -318,30 +286,6 @@ def test_native_top2_equals_the_launches_on_sort_by_expert(env, experts_case, na
         want = reference_forward(env, c, experts, c["hidden"], ids, c["weights"], fused)
         assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
         assert torch.equal(bits16(Y), bits16(want)), fused
-
-
-@pytest.fixture(scope="module")
-def top3_case(env):
-    """E = 4 experts (4-bit, g = 64, K = 256, N_ff = 512), T = 37 tokens, three of the four experts per token."""
-    d, dtype = env.dev, F16
-    E, K, F, T, k, bits, g = 4, 256, 512, 37, 3, 4, 64
-    tid = first_template(env.fa, bits, 32)
-    gen = torch.Generator().manual_seed(33)
-    nf4 = torch.tensor(env.O.NF4_VALUES).to(dtype)
-
-    def linear(kk, nn):
-        codes = torch.randint(0, 16, (kk, nn), generator=gen, dtype=torch.uint8).to(d)
-        scales = (torch.rand(nn, kk // g, generator=gen) * 0.1 + 0.02).to(dtype).to(d)
-        return env.FluteLinear.from_codes(codes, scales, nf4.to(d), bits, g, tid)
-
-    c = dict(E=E, K=K, F=F, T=T, k=k, bits=bits, g=g, tid=tid, dtype=dtype)
-    c["gates"], c["ups"], c["downs"] = ([linear(K, F) for _ in range(E)], [linear(K, F) for _ in range(E)],
-                                        [linear(F, K) for _ in range(E)])
-    c["hidden"] = torch.randn(T, K, generator=gen).to(dtype).to(d)
-    c["ids"] = torch.rand(T, E, generator=gen).topk(k, dim=1).indices.to(d)
-    weights = torch.rand(T, k, generator=gen)
-    c["weights"] = (weights / weights.sum(1, keepdim=True)).to(dtype).to(d)
-    return c
 
 
 @pytest.mark.parametrize("fused", [True, False])

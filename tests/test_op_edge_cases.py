@@ -9,6 +9,7 @@ from tests import exact_cases as XC
 from tests import op_edge_cases as OE
 from tests import scale_grad_ref as SR
 from tests import table_grad_ref as TR
+from tests.grouped_cases import counts_of
 
 F16, BF16 = torch.float16, torch.bfloat16
 
@@ -18,7 +19,6 @@ def test_shapes_cross_the_kernels_boundaries():
     assert OE.FWD_COUNTS[0] == 0 and 0 in OE.FWD_COUNTS[1:-1]
     assert any(0 < o % 16 for o in off[1:-1]) and max(OE.FWD_COUNTS) > 32        # seams inside a tile, a second row pass
     assert OE.K_EDGE % 64 == 0 and OE.K_EDGE % 256 != 0
-    from tests.test_grouped_input_grad_gpu import counts_of
     assert OE.grad_counts() == counts_of(OE.ROW_BLOCK)
     for bits, g in OE.SG_CASES:
         K, N = OE.sg_shape(bits)

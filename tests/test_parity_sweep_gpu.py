@@ -24,28 +24,13 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
+from tests.qgemm_cases import GEMMA2_9B, SUPPORTED_SHAPES
+from tests.support import env, first_template, norm_rel_err  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FP16_TOL = 1e-3          # north_star
 BF16_TOL = 4e-3          # what tests/test_oracle.py grants the oracle; the reference accepts 1.1e-2 (tests/kernel.py:13)
-
-# the reference's tests/shapes.py:1-96, (N, K)
-LLAMA3_8B = [(1024, 4096), (4096, 4096), (4096, 14336), (6144, 4096), (14336, 4096)]
-LLAMA3_70B = [(1024, 8192), (8192, 8192), (8192, 28672), (10240, 8192), (28672, 8192)]
-LLAMA3_70B_TP2 = [(5120, 8192), (8192, 4096), (8192, 14336), (14336, 8192)]
-LLAMA3_70B_TP4 = [(2560, 8192), (7168, 8192), (8192, 2048), (8192, 7168)]
-LLAMA3_405B = [(2048, 16384), (2560, 16384), (5120, 16384), (16384, 2048), (16384, 4096), (16384, 6656),
-               (16384, 16384), (16384, 53248), (16384, 13312), (53248, 16384), (20480, 16384),
-               (26624, 16384), (13312, 16384), (106496, 16384)]
-LLAMA3_EXTRA_VLLM = [(28672, 4096), (57344, 8192)]
-GEMMA2_9B = [(2048, 3584), (3584, 4096), (3584, 14336), (4096, 3584), (14336, 3584), (8192, 3584),
-             (28672, 3584)]
-GEMMA2_27B = [(2048, 4608), (4096, 4608), (4608, 4096), (4608, 36864), (36864, 4608), (8192, 4608),
-              (73728, 4608), (4608, 2048), (4608, 18432), (4608, 1024), (4608, 9216), (18432, 4608)]
-SUPPORTED_SHAPES = (LLAMA3_8B + LLAMA3_70B + LLAMA3_70B_TP2 + LLAMA3_70B_TP4 + LLAMA3_405B +
-                    LLAMA3_EXTRA_VLLM + GEMMA2_9B + GEMMA2_27B)
-assert len(SUPPORTED_SHAPES) == len(set(SUPPORTED_SHAPES)) == 53
 
 COMBOS = [c + (32,) for c in itertools.product([4, 3, 2], [64, 128, 256], [torch.float16, torch.bfloat16], [True, False])] + \
          [c + (64,) for c in itertools.product([4, 2], [64, 128, 256], [torch.float16, torch.bfloat16], [True, False])]
@@ -62,34 +47,8 @@ def tol_of(dtype):
     return FP16_TOL if dtype == torch.float16 else BF16_TOL
 
 
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import utils
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.utils, e.O = flute_amd, utils, O
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def first_template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
 def packable(N, bits, tile_p):
     return N % (tile_p * (16 if bits == 3 else 16 // bits)) == 0
-
-
-def rel(out, ref):
-    out, ref = out.float(), ref.float()
-    return ((out - ref).norm() / ref.norm()).item()
 
 
 def served_template(e, M, N, K, bits, g, dtype, tile_p):
@@ -102,7 +61,7 @@ def served_template(e, M, N, K, bits, g, dtype, tile_p):
     if tid is not None and e.fa.TEMPLATE_CONFIGS[(bits, tid)]["TileP"] == tile_p and \
             e.utils.is_template_supported(M, N, K, bits, tid, e.num_sms, g, dtype):
         return tid
-    return first_template(e.fa, bits, tile_p)
+    return first_template(bits, tile_p)
 
 
 def check_shape_case(e, N, K, bits, g, dtype, uniform, Ms, seed, tile_p=32, tuned=False):
@@ -117,7 +76,7 @@ def check_shape_case(e, N, K, bits, g, dtype, uniform, Ms, seed, tile_p=32, tune
     S = torch.randn(N, K // g, device=d).to(dtype)
     table = (torch.arange(2 ** bits, device=d) if uniform else torch.randn(2 ** bits, device=d)).to(dtype)
     table2 = e.utils.make_qmap2_from_qmap(table)
-    tid0 = first_template(e.fa, bits, tile_p)
+    tid0 = first_template(bits, tile_p)
     tid_of = (lambda M: served_template(e, M, N, K, bits, g, dtype, tile_p)) if tuned else (lambda M: tid0)
     Q = e.utils.pack(W, bits, [tid0], e.num_sms)                                # (the layout depends on TileP only)
     Sx = torch.repeat_interleave(S, g, dim=1).T                                 # [K, N]
@@ -221,7 +180,7 @@ def test_higgs_pair_codebook_hadamard_gemma2(env, N, K):
         ref = env.O.qgemm_hadamard(X, Q.cpu().numpy(), S.cpu(), tables.cpu(), tables2.cpu(), bits, g, h, tile_p)
         out = env.fa.qgemm_hadamard(X.to(d), Q, S, tables, tables2, env.ws, bits, g, h, meta.template_id,
                                     meta.num_sms).cpu()
-        assert rel(out, ref) < 3e-3, (N, K, rel(out, ref))
+        assert norm_rel_err(out, ref) < 3e-3, (N, K, norm_rel_err(out, ref))
 
 
 @pytest.mark.parametrize("bits,tile_p", [(4, 32), (4, 64), (2, 32), (2, 64), (3, 32)])
@@ -233,7 +192,7 @@ def test_product_packer_equals_oracle_on_row_slices(env, bits, tile_p):
     K, N = 4096, 4096
     torch.manual_seed(bits * 100 + tile_p)
     W = torch.randint(0, 2 ** bits, (K, N), dtype=torch.uint8, device=d)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(W, bits, [tid], env.num_sms).cpu().numpy()
     blk = tile_p * (16 if bits == 3 else 16 // bits)
     Wc = W.cpu().numpy()

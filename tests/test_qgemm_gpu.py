@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import exact_cases as XC
+from tests.support import env, norm_rel_err  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +24,6 @@ BF16_TOL = 4e-3
 
 def tol_of(dtype):
     return FP16_TOL if dtype == torch.float16 else BF16_TOL
-
-
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import utils
-    from oracle import flute_oracle as O
-    dev = torch.device("cuda:0")
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.utils, e.O, e.dev = flute_amd, utils, O, dev
-    e.num_sms = utils.get_device_num_sms(dev)
-    e.ws = utils.get_workspace_streamk(dev)
-    return e
 
 
 def template_ids_for(fa, bits, tile_p, limit=None):
@@ -55,11 +39,6 @@ def run_qgemm(e, X, Q, S, table, table2, bits, g, tid, ovr=None):
                                  e.ws, bits, g, tid, e.num_sms, dev.Overrides(**ovr)).cpu()
     return e.fa.qgemm(X.to(d), torch.as_tensor(Q).to(d), S.to(d), table.to(d), table2.to(d),
                       e.ws, bits, g, tid, e.num_sms).cpu()
-
-
-def rel_err(out, ref):
-    out, ref = out.float(), ref.float()
-    return ((out - ref).norm() / ref.norm()).item()
 
 
 # ---------------------------------------------------------------------------
@@ -85,7 +64,7 @@ def test_golden_random(env, golden):
     tid = template_ids_for(env.fa, golden.num_bits, golden.tile_p)[0]
     D = run_qgemm(env, golden.A, golden.Q, golden.S, golden.table, golden.table2,
                   golden.num_bits, golden.group_size, tid)
-    assert rel_err(D, golden.D) < tol_of(golden.dtype), golden.name
+    assert norm_rel_err(D, golden.D) < tol_of(golden.dtype), golden.name
 
 
 # ---------------------------------------------------------------------------
@@ -123,7 +102,7 @@ def test_random_vs_oracle_all_M(env, bits, tile_p, dtype):
         tid = tids[(i * 7) % len(tids)]
         D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid)
         assert D.shape == (M, N) and D.dtype == dtype
-        err = rel_err(D, ref)
+        err = norm_rel_err(D, ref)
         assert err < tol_of(dtype), (bits, tile_p, dtype, M, tid, err)
         XC.assert_componentwise(D, X, W_exact, K, dtype, what=(bits, tile_p, dtype, M, tid))
 
@@ -141,7 +120,7 @@ def test_group_sizes_identity_and_random(env, bits, tile_p, g):
     for M in (1, 4, 24):
         X = (torch.randn(M, K) / 100).to(dtype)
         D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid)
-        assert rel_err(D, (X.float() @ What.float())) < FP16_TOL
+        assert norm_rel_err(D, (X.float() @ What.float())) < FP16_TOL
 
 
 @pytest.mark.parametrize("bits,tile_p", LAYOUTS)
@@ -157,7 +136,7 @@ def test_ragged_k_and_odd_shapes(env, bits, tile_p):
         for M in (1, 3, 8, 20):
             X = (torch.randn(M, K) / 100).to(dtype)
             D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid)
-            err = rel_err(D, X.float() @ What)
+            err = norm_rel_err(D, X.float() @ What)
             assert err < FP16_TOL, (bits, tile_p, K, N, M, err)
 
 
@@ -180,12 +159,12 @@ def test_forced_splitk_and_kw_variants(env):
                         continue
                     ovr = dict(kw=kw, splitk=splitk, waves=waves, ring_depth=depth)
                     D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, ovr)
-                    err = rel_err(D, ref)
+                    err = norm_rel_err(D, ref)
                     assert err < FP16_TOL, (M, ovr, err)
         if M <= 4:                                   # both decode kernels, forced
             for one in (0, 1):
                 D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, dict(family=0, one_shot=one))
-                assert rel_err(D, ref) < FP16_TOL, (M, "one_shot", one)
+                assert norm_rel_err(D, ref) < FP16_TOL, (M, "one_shot", one)
     # the per-wave MFMA kernel's grid split is combined inside the launch while the slabs are small (round 4: csrc/xwg.h, L
     # form) and by the reduce pass beyond; both forms, every in-workgroup split, one-hot rows exact, repeat-identical, the
     # state words left clean
@@ -206,7 +185,7 @@ def test_forced_splitk_and_kw_variants(env):
                 o = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
                 o1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
                 o2 = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
-                assert rel_err(o.cpu(), X.float() @ What) < FP16_TOL, (M, kw, splitk)
+                assert norm_rel_err(o.cpu(), X.float() @ What) < FP16_TOL, (M, kw, splitk)
                 assert torch.equal(o1.cpu(), ref1) and torch.equal(o, o2), (M, kw, splitk)
                 assert int(env.ws[:65536].view(torch.int32).abs().sum().item()) == 0, (M, kw, splitk)
 
@@ -247,7 +226,7 @@ def test_decode_plan_shapes(env):
                     ovr = dev.Overrides(family=0, **shp)           # (M = 3, 4 take the MFMA kernel unless asked)
                     assert dev.get_plan(M, N, K, bits, g, tid, num_sms, dtype, ovr)["family"] == 0
                     out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, num_sms, ovr).cpu()
-                    err = rel_err(out, ref)
+                    err = norm_rel_err(out, ref)
                     assert err < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, shp, num_sms, err)
                     out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, num_sms, ovr).cpu()
                     assert torch.equal(out1, ref1), (bits, tile_p, g, dtype, K, N, M, shp, num_sms)
@@ -290,7 +269,7 @@ def test_persistent_oneshot_kernel(env):
                     assert plan["m_block"] >= M and plan["k_chunks"] * plan["ring_depth"] * 512 == K
                     assert plan["grid"] * plan["waves"] * plan["visits"] >= N // (16 if bits == 3 else 16 // bits)
                     out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, num_sms, ovr)
-                    assert rel_err(out.cpu(), ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, shp, num_sms)
+                    assert norm_rel_err(out.cpu(), ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, shp, num_sms)
                     out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, num_sms, ovr).cpu()
                     assert torch.equal(out1, ref1), (bits, tile_p, g, dtype, K, N, M, shp, num_sms)
         for h in (512, 64):                              # fused rotation == rotate, then multiply
@@ -351,7 +330,7 @@ def test_lean_decode_kernel(env):
                 X = (torch.randn(M, K) / 100).to(dtype)
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2.to(d), env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert out.shape == (M, N)
-                assert rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, rank, M, pair_codebook)
+                assert norm_rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, rank, M, pair_codebook)
                 ks = torch.randint(0, K, (M,))
                 ks[0] = (0, K - 1)[M % 2]
                 E = torch.zeros(M, K, dtype=dtype)
@@ -382,7 +361,7 @@ def test_lean_decode_kernel(env):
             auto = env.fa.qgemm_hadamard(X, Qd, Sd, td, t2d, env.ws, 4, g, h, tid, env.num_sms)
             two = env.fa.qgemm(env.fa.hadamard_transform(X, h), Qd, Sd, td, t2d, env.ws, 4, g, tid, env.num_sms)
             tol = 2e-3 if dtype == torch.float16 else 4e-3
-            assert rel_err(auto, two) < tol, (dtype, K, N, h)               # different kernels: the same products, summed in another order
+            assert norm_rel_err(auto, two) < tol, (dtype, K, N, h)               # different kernels: the same products, summed in another order
     # not taken: five rows, 2 / 3 bits, 32-wide groups, K that is not 2048 / 3584 / 4096 / 8192
     for (M, K, bits, g) in ((5, 4096, 4, 64), (1, 4096, 2, 64), (1, 4096, 3, 64), (1, 4096, 4, 32), (1, 3072, 4, 64), (1, 14336, 4, 64)):
         plan = dev.get_plan(M, 4096, K, bits, g, template_ids_for(env.fa, bits, 32)[0], env.num_sms, torch.float16, dev.Overrides(family=0, one_shot=4) if M <= 4 else dev.Overrides(one_shot=4))
@@ -422,7 +401,7 @@ def test_lean_mfma_decode_kernel(env):
                 X = (torch.randn(M, K) / 100).to(dtype)
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2.to(d), env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert out.shape == (M, N)
-                assert rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, M, ng, pair_codebook, rel_err(out, X.float() @ What))
+                assert norm_rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, M, ng, pair_codebook, norm_rel_err(out, X.float() @ What))
                 ks = torch.randint(0, K, (M,))
                 ks[0] = (0, K - 1)[M % 2]
                 E = torch.zeros(M, K, dtype=dtype)
@@ -473,7 +452,7 @@ def test_persistent_mfma_decode_kernel(env):
                 X = (torch.randn(M, K) / 100).to(dtype)
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2.to(d), env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert out.shape == (M, N)
-                assert rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, M, ng, vis, pair_codebook, rel_err(out, X.float() @ What))
+                assert norm_rel_err(out, X.float() @ What) < tol_of(dtype), (tile_p, g, dtype, K, N, M, ng, vis, pair_codebook, norm_rel_err(out, X.float() @ What))
                 ks = torch.randint(0, K, (M,))
                 ks[0] = (0, K - 1)[M % 2]
                 E = torch.zeros(M, K, dtype=dtype)
@@ -530,7 +509,7 @@ def test_skinny_mfma_kernel(env):
                 ran += 1
                 assert plan["ring_depth"] * plan["waves"] * 32 == K and plan["grid"] == N // 64 and plan["splitk"] == 1
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
-                assert rel_err(out, ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, waves)
+                assert norm_rel_err(out, ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, waves)
                 out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert torch.equal(out1, ref1), (bits, tile_p, g, dtype, K, N, M, waves)
             assert ran, (K, g)
@@ -544,7 +523,7 @@ def test_skinny_mfma_kernel(env):
     assert dev.get_plan(16, 11008, K, bits, g, tid, env.num_sms, dtype)["family"] == 7
     a = run_qgemm(env, X, Q, S, table, table2, bits, g, tid)
     b = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, dict(family=2))
-    assert rel_err(a, b.float()) < 5e-4
+    assert norm_rel_err(a, b.float()) < 5e-4
 
 
 def test_decode_chunked_activations(env):
@@ -564,7 +543,7 @@ def test_decode_chunked_activations(env):
         for shp in (dict(splitk=1), dict(waves=8, kw=8, splitk=1), dict(waves=6, kw=1, splitk=1), dict()):
             out = dev.qgemm_planned(X.to(d), Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, tid,
                                     env.num_sms, dev.Overrides(family=0, **shp)).cpu()
-            err = rel_err(out, X.float() @ What)
+            err = norm_rel_err(out, X.float() @ What)
             assert err < tol_of(dtype), (bits, g, dtype, K, M, shp, err)
 
 
@@ -579,7 +558,7 @@ def test_mfma_family_for_small_M(env):
         for M in (1, 7):
             X = (torch.randn(M, K) / 100).to(dtype)
             D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, dict(family=2))
-            assert rel_err(D, X.float() @ What) < tol_of(dtype)
+            assert norm_rel_err(D, X.float() @ What) < tol_of(dtype)
 
 
 def test_mfma_scale_block_and_ring_paths(env):
@@ -611,7 +590,7 @@ def test_mfma_scale_block_and_ring_paths(env):
         tid = template_ids_for(env.fa, bits, tile_p)[0]
         X = (torch.randn(M, K) / 100).to(dtype)
         D = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, ovr)
-        err = rel_err(D, X.float() @ What)
+        err = norm_rel_err(D, X.float() @ What)
         assert err < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, ovr, err)
         # one-hot rows: bit-exact (each output element is one rounded product)
         ks = torch.randint(0, K, (M,))
@@ -655,7 +634,7 @@ def test_block_prefill_kernel(env):
                 if "splitk" in shp:      # 3-bit blocks of up to 128 rows combine their K slices inside the launch (round 5), the others by a reduce launch
                     assert plan["splitk_mode"] == (1 if bits == 3 and shp["m_tiles"] == 4 else 0), plan
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
-                err = rel_err(out, X.float() @ What)
+                err = norm_rel_err(out, X.float() @ What)
                 assert err < tol_of(dtype), (tile_p, g, dtype, K, N, M, shp, err)
                 out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert torch.equal(out1, ref1), (tile_p, g, dtype, K, N, M, shp)
@@ -676,7 +655,7 @@ def test_block_prefill_kernel(env):
                 ovr = dev.Overrides(family=3, m_block=rt, splitk=sk)
                 assert dev.get_plan(M, N, K, bits, g, tid, env.num_sms, dtype, ovr)["m_block"] == 8 + rt
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
-                assert rel_err(out, X.float() @ What) < tol_of(dtype), (M, rt, sk)
+                assert norm_rel_err(out, X.float() @ What) < tol_of(dtype), (M, rt, sk)
                 out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr).cpu()
                 assert torch.equal(out1, ref1), (M, rt, sk)
     assert int(env.ws[:65536].view(torch.int32).abs().sum().item()) == 0        # the tile state words are zero again (xwg.h)
@@ -741,7 +720,7 @@ def test_splitk_block_kernel(env):
                 out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
                 out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
                 out2 = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms, ovr)
-                assert rel_err(out.cpu(), ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, sk, rt, kp)
+                assert norm_rel_err(out.cpu(), ref) < tol_of(dtype), (bits, tile_p, g, dtype, K, N, M, sk, rt, kp)
                 assert torch.equal(out1.cpu(), ref1), (bits, tile_p, g, dtype, K, N, M, sk, rt, kp)
                 assert torch.equal(out, out2), (bits, tile_p, g, dtype, K, N, M, sk, rt, kp)
                 assert _state_words_clean(env), (bits, tile_p, g, dtype, K, N, M, sk, rt, kp)
@@ -767,7 +746,7 @@ def test_splitk_block_kernel(env):
     X = (torch.randn(256, K) / 100).to(dtype)
     a = run_qgemm(env, X, Q, S, table, table2, bits, g, tid)
     b = run_qgemm(env, X, Q, S, table, table2, bits, g, tid, dict(family=2))
-    assert torch.equal(a, b) or rel_err(a, b.float()) < 2e-4         # same arithmetic contract, different summation order
+    assert torch.equal(a, b) or norm_rel_err(a, b.float()) < 2e-4         # same arithmetic contract, different summation order
 
 
 def test_splitk_seam_under_load(env):
@@ -838,11 +817,11 @@ def test_skinny_grid_split(env):
                     out = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, 4, g, tid, env.num_sms, ovr)
                     out1 = dev.qgemm_planned(E.to(d), Qd, Sd, td, t2d, env.ws, 4, g, tid, env.num_sms, ovr)
                     out2 = dev.qgemm_planned(X.to(d), Qd, Sd, td, t2d, env.ws, 4, g, tid, env.num_sms, ovr)
-                    assert rel_err(out.cpu(), ref) < tol_of(dtype), (tile_p, g, dtype, K, N, M, sk, waves)
+                    assert norm_rel_err(out.cpu(), ref) < tol_of(dtype), (tile_p, g, dtype, K, N, M, sk, waves)
                     if dtype == torch.float16:
                         assert torch.equal(out1.cpu(), ref1), (tile_p, g, dtype, K, N, M, sk, waves)
                     else:                                            # bf16: the scale is applied to the fp32 sum of a group run
-                        assert rel_err(out1.cpu(), ref1.float()) < tol_of(dtype)
+                        assert norm_rel_err(out1.cpu(), ref1.float()) < tol_of(dtype)
                     assert torch.equal(out, out2) and _state_words_clean(env), (tile_p, g, dtype, K, N, M, sk, waves)
             assert ran, (K, g, M)
 
@@ -950,12 +929,12 @@ def test_hadamard_vs_definition(env, dtype, h):
     y = env.fa.hadamard_transform(x.to(env.dev), h).cpu()
     ref = env.O.hadamard_transform(x, h)
     tol = 2e-3 if dtype == torch.float16 else 1.2e-2      # ~1 ulp of T rel. to the row norm
-    assert rel_err(y, ref) < tol, (h, rel_err(y, ref))
+    assert norm_rel_err(y, ref) < tol, (h, norm_rel_err(y, ref))
     # several blocks per row
     if h <= 512:
         x2 = torch.randn(5, 4 * h).to(dtype)
         y2 = env.fa.hadamard_transform(x2.to(env.dev), h).cpu()
-        assert rel_err(y2, env.O.hadamard_transform(x2, h)) < tol
+        assert norm_rel_err(y2, env.O.hadamard_transform(x2, h)) < tol
 
 
 def test_qgemm_hadamard(env):
@@ -968,7 +947,7 @@ def test_qgemm_hadamard(env):
         ref = env.O.qgemm_hadamard(X, Q.numpy(), S, table, table2, bits, g, h, tile_p)
         out = env.fa.qgemm_hadamard(X.to(d), Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws,
                                     bits, g, h, tid, env.num_sms).cpu()
-        assert rel_err(out, ref) < 3e-3, (M, rel_err(out, ref))
+        assert norm_rel_err(out, ref) < 3e-3, (M, norm_rel_err(out, ref))
 
 
 def test_qgemm_hadamard_fused_equals_two_launches(env):
@@ -1003,7 +982,7 @@ def test_qgemm_hadamard_fused_equals_two_launches(env):
                 assert torch.equal(fused, two), (bits, dtype, K, h, M)
                 auto = env.fa.qgemm_hadamard(X, Qd, Sd, td, t2d, env.ws, bits, g, h, tid, env.num_sms)
                 plain = env.fa.qgemm(env.fa.hadamard_transform(X, h), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms)
-                assert torch.equal(auto, plain) or rel_err(auto.cpu(), plain.float().cpu()) < 5e-4, (bits, dtype, K, h, M)
+                assert torch.equal(auto, plain) or norm_rel_err(auto.cpu(), plain.float().cpu()) < 5e-4, (bits, dtype, K, h, M)
     # plans that cannot fuse (MFMA kernel, blocks larger than 512) take the scratch path
     bits, tile_p, g, dtype, K, N = 4, 32, 64, torch.float16, 2048, 512
     W, Q, S, table, table2 = make_case(env, bits, tile_p, g, dtype, K, N, seed=2)
@@ -1068,7 +1047,7 @@ def test_cached_plan_entries_keep_their_kernel(env):
         out = run(call)
         Xr = env.O.hadamard_transform(X, h) if h else X
         ref = (Xr.float() @ layer["What"]).to(layer["dtype"])
-        err = rel_err(out, ref)
+        err = norm_rel_err(out, ref)
         assert err < tol_of(layer["dtype"]), (layer["bits"], layer["dtype"], M, tid, h, err)
         first.append(out)
     order = torch.randperm(len(calls), generator=torch.Generator().manual_seed(7)).tolist()
@@ -1094,7 +1073,7 @@ def test_batch_dims_errors_and_graph(env):
     X = (torch.randn(2, 3, K) / 100).to(dtype)
     out = env.fa.qgemm(X.to(d), Qd, Sd, td, t2d, env.ws, bits, g, tid, env.num_sms)
     assert out.shape == (2, 3, N)
-    assert rel_err(out.cpu().reshape(6, N), X.reshape(6, K).float() @ What) < FP16_TOL
+    assert norm_rel_err(out.cpu().reshape(6, N), X.reshape(6, K).float() @ What) < FP16_TOL
     # keyword calling convention of qgemm_v2 (tune.py:508-531)
     out2 = env.fa.qgemm(input=X.to(d), weight=Qd, scales=Sd, table=td, table2=t2d,
                         workspace=env.ws, num_bits=bits, group_size=g, template_id=tid,
@@ -1118,7 +1097,7 @@ def test_batch_dims_errors_and_graph(env):
     xg.copy_((torch.randn(1, K) / 100).to(dtype))
     graph.replay()
     torch.cuda.synchronize()
-    assert rel_err(static_out.cpu(), xg.cpu().float() @ What) < FP16_TOL
+    assert norm_rel_err(static_out.cpu(), xg.cpu().float() @ What) < FP16_TOL
 
 
 def test_prepare_model_flute_matches_fake_quantized_model(env):
@@ -1151,7 +1130,7 @@ def test_prepare_model_flute_matches_fake_quantized_model(env):
             x = torch.randn(M, dim, device=d, dtype=dtype)
             with torch.no_grad():                         # inference only: the op has no autograd formula (as the reference)
                 y, y_ref = model(x), fake(x)
-            assert rel_err(y.cpu(), y_ref.cpu()) < tol, (dtype, M, rel_err(y.cpu(), y_ref.cpu()))
+            assert norm_rel_err(y.cpu(), y_ref.cpu()) < tol, (dtype, M, norm_rel_err(y.cpu(), y_ref.cpu()))
     cpu_model = torch.nn.Sequential(torch.nn.Linear(64, 64)).half()
     with pytest.raises(ValueError):
         prepare_model_flute("m", cpu_model, 4, 64, 1)            # no CPU path
@@ -1172,7 +1151,7 @@ def test_flute_linear_and_repack(env):
     tile_p = env.fa.TEMPLATE_CONFIGS[(bits, 0)]["TileP"]
     What = env.O.dequantize(layer.weight.cpu().numpy(), S.cpu(), layer.tables2.cpu(), bits, g, tile_p)
     ref = x.cpu().float() @ What.float() + bias.cpu().float()
-    assert rel_err(layer(x).cpu(), ref) < 2e-3
+    assert norm_rel_err(layer(x).cpu(), ref) < 2e-3
     sd = layer.state_dict()
     assert set(k for k in sd if not k.startswith("_")) >= {"weight", "scales", "tables", "tables2", "bias"}
     # a checkpoint "packed on another GPU" (num_sms 108, reference id 132, TileP 32)

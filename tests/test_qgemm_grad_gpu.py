@@ -1,12 +1,11 @@
 """Backpropagation through flute::qgemm_raw_simple[_hadamard]: the input gradient dX = dY @ dequantize(...) (then the
 rotation), exact on exactly representable data, within the forward's tolerances on random data, through stacked
 FluteLinear layers with LoRA adapters, with the forward unchanged and scale gradients refused."""
-import contextlib
-
 import pytest
 import torch
 
 from tests import exact_cases as XC
+from tests.support import env, first_template, fp32_blas_reduction  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,41 +13,7 @@ F16, BF16 = torch.float16, torch.bfloat16
 TOL = {F16: 1e-3, BF16: 4e-3}
 
 
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    from flute_amd import utils
-    from oracle import flute_oracle as O
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.utils, e.O = flute_amd, utils, O
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def first_template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
-@contextlib.contextmanager
-def fp32_blas_reduction():
-    """hipBLASLt may reduce fp16 / bf16 GEMMs in reduced precision by default; the exact cases need fp32 partial sums."""
-    m = torch.backends.cuda.matmul
-    old = (m.allow_fp16_reduced_precision_reduction, m.allow_bf16_reduced_precision_reduction)
-    m.allow_fp16_reduced_precision_reduction = False
-    m.allow_bf16_reduced_precision_reduction = False
-    try:
-        yield
-    finally:
-        m.allow_fp16_reduced_precision_reduction, m.allow_bf16_reduced_precision_reduction = old
-
-
-def rel_err(a, b):
+def norm_rel_err64(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).norm() / b.norm())
 
@@ -67,7 +32,7 @@ def test_exact_input_grad(env, bits, K, N, g, dtype, tile_p, pair, shape):
     """Integer dY in [-4, 4] against exact weights: x.grad must be round_T(dY @ W_exact^T) bit for bit."""
     d = env.dev
     lay = XC.Layer(bits, K, N, g, dtype, seed=bits * 7919 + K + N + g, tile_p=tile_p, pair=pair)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(lay.W.to(d), bits, [tid], env.num_sms)
     S, table, table2 = lay.S.to(d), lay.table.to(d), lay.table2.to(d)
     M = 1
@@ -120,13 +85,13 @@ def random_layer(env, bits, K, N, g, dtype, tile_p, seed):
 def test_random_input_grad(env, bits, K, N, g, dtype, tile_p, M):
     d = env.dev
     Q, S, table, table2, What = random_layer(env, bits, K, N, g, dtype, tile_p, seed=K + N + M)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     x = torch.randn(M, K, dtype=dtype, device=d).requires_grad_()
     dY = torch.randn(M, N, dtype=dtype)
     y = env.fa.qgemm(x, Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, tid, env.num_sms)
     y.backward(dY.to(d))
     ref = dY.double() @ What.double().T
-    assert rel_err(x.grad, ref) < TOL[dtype]
+    assert norm_rel_err64(x.grad, ref) < TOL[dtype]
 
 
 @pytest.mark.parametrize("h", [64, 128, 512])
@@ -135,7 +100,7 @@ def test_random_input_grad_hadamard(env, h, dtype):
     d = env.dev
     bits, K, N, g, tile_p = 4, 2048, 1024, 64, 32
     Q, S, table, table2, What = random_layer(env, bits, K, N, g, dtype, tile_p, seed=h)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     for shape in ((1,), (6,), (2, 70)):
         x = torch.randn(*shape, K, dtype=dtype, device=d).requires_grad_()
         dY = torch.randn(*shape, N, dtype=dtype)
@@ -143,23 +108,23 @@ def test_random_input_grad_hadamard(env, h, dtype):
         y.backward(dY.to(d))
         ref = env.O.hadamard_transform((dY.double().reshape(-1, N) @ What.double().T), h).reshape(*shape, K)
         assert x.grad.shape == x.shape
-        assert rel_err(x.grad, ref) < TOL[dtype], (shape, rel_err(x.grad, ref))
+        assert norm_rel_err64(x.grad, ref) < TOL[dtype], (shape, norm_rel_err64(x.grad, ref))
 
 
 def test_non_contiguous_grad_output(env):
     d = env.dev
     bits, K, N, g, dtype, tile_p = 4, 1024, 512, 64, F16, 32
     Q, S, table, table2, What = random_layer(env, bits, K, N, g, dtype, tile_p, seed=4)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     x = torch.randn(5, K, dtype=dtype, device=d).requires_grad_()
     y = env.fa.qgemm(x, Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, tid, env.num_sms)
     dY = torch.randn(N, 5, dtype=dtype, device=d).T               # transposed: non-contiguous
     y.backward(dY)
-    assert rel_err(x.grad, dY.cpu().double() @ What.double().T) < TOL[dtype]
+    assert norm_rel_err64(x.grad, dY.cpu().double() @ What.double().T) < TOL[dtype]
     x.grad = None
     y = env.fa.qgemm(x, Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, tid, env.num_sms)
     y.sum().backward()                                            # an expanded (stride 0) gradient
-    assert rel_err(x.grad, torch.ones(5, N).double() @ What.double().T) < TOL[dtype]
+    assert norm_rel_err64(x.grad, torch.ones(5, N).double() @ What.double().T) < TOL[dtype]
 
 
 def test_lora_adapters_on_stacked_flute_linear(env):
@@ -200,7 +165,7 @@ def test_lora_adapters_on_stacked_flute_linear(env):
 
     got, ref = run(bases), run(denses)
     for i, (a, b) in enumerate(zip(got, ref)):
-        assert a is not None and rel_err(a, b) < 1e-2, (i, rel_err(a, b))
+        assert a is not None and norm_rel_err64(a, b) < 1e-2, (i, norm_rel_err64(a, b))
 
 
 @pytest.mark.parametrize("M", [1, 4, 33, 600])
@@ -208,7 +173,7 @@ def test_forward_unchanged_by_requires_grad(env, M):
     d = env.dev
     bits, K, N, g, dtype, tile_p = 4, 2048, 2048, 64, BF16, 32
     Q, S, table, table2, _ = random_layer(env, bits, K, N, g, dtype, tile_p, seed=M)
-    args = (Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, first_template(env.fa, bits, tile_p), env.num_sms)
+    args = (Q.to(d), S.to(d), table.to(d), table2.to(d), env.ws, bits, g, first_template(bits, tile_p), env.num_sms)
     x = torch.randn(M, K, dtype=dtype, device=d)
     with torch.no_grad():
         y0 = env.fa.qgemm(x, *args)
@@ -225,7 +190,7 @@ def test_scale_and_table_gradients_refused(env):
     d = env.dev
     bits, K, N, g, dtype, tile_p = 4, 1024, 512, 64, F16, 32
     Q, S, table, table2, _ = random_layer(env, bits, K, N, g, dtype, tile_p, seed=9)
-    tid = first_template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Sd = S.to(d).requires_grad_()
     x = torch.randn(3, K, dtype=dtype, device=d)
     y = env.fa.qgemm(x, Q.to(d), Sd, table.to(d), table2.to(d), env.ws, bits, g, tid, env.num_sms)

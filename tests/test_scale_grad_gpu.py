@@ -11,6 +11,7 @@ import torch
 
 from tests import exact_cases as XC
 from tests import scale_grad_ref as SR
+from tests.support import env, first_template, ints  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,36 +20,8 @@ TOL = {F16: 1e-3, BF16: 4e-3}
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "scale_grad", "manual_nf4_absmax_grad.npz")
 
 
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    import flute_amd.integrations.base  # noqa: F401
-    import flute_amd.nf_utils  # noqa: F401
-    from flute_amd import utils
-    from flute_amd.integrations import learnable
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.utils, e.ln = flute_amd, utils, learnable
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
-def ints(M, K, amp, seed, dtype):
-    gen = torch.Generator().manual_seed(seed)
-    return torch.randint(-amp, amp + 1, (M, K), generator=gen).to(dtype)
-
-
 def exact_layer(env, lay):
-    tid = template(env.fa, lay.bits, lay.tile_p)
+    tid = first_template(lay.bits, lay.tile_p)
     Q = env.utils.pack(lay.W.to(env.dev), lay.bits, [tid], env.num_sms)
     return Q, lay.table2.to(env.dev), tid, SR.lut_of_codes(lay.W.to(env.dev), lay.pairs, lay.bits)
 
@@ -111,7 +84,7 @@ def test_random_within_componentwise_bound(env, bits, K, N, g, dtype, tile_p, M)
     table = table[:: 16 // 2 ** bits][: 2 ** bits]
     n = 2 ** bits
     pairs = torch.stack([table[:, None].expand(n, n), table[None, :].expand(n, n)], -1).reshape(n * n, 2).double()
-    tid = template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(codes.to(d), bits, [tid], env.num_sms)
     table2 = env.utils.make_qmap2_from_qmap(table).to(d)
     L = SR.lut_of_codes(codes.to(d), pairs, bits)
@@ -154,7 +127,7 @@ def test_random_repeat_and_graph_replay(env):
     bits, K, N, g, dtype = 4, 1024, 512, 64, BF16
     gen = torch.Generator().manual_seed(3)
     codes = torch.randint(0, 16, (K, N), generator=gen, dtype=torch.uint8)
-    tid = template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     Q = env.utils.pack(codes.to(d), bits, [tid], env.num_sms)
     table2 = env.utils.make_qmap2_from_qmap(torch.tensor(env.fa.nf_utils.NF4_VALUES, dtype=dtype)).to(d)
     dY = torch.randn(2, 300, N, generator=gen).to(dtype).to(d)
@@ -206,7 +179,7 @@ def nf4_layer(env, bits, K, N, g, dtype, tile_p, seed):
     codes = torch.randint(0, 2 ** bits, (K, N), generator=gen, dtype=torch.uint8)
     table = torch.tensor(env.fa.nf_utils.NF4_VALUES, dtype=dtype)[:: 16 // 2 ** bits][: 2 ** bits]
     S = (torch.randn(N, K // g, generator=gen) / 8).to(dtype)
-    tid = template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(codes.to(d), bits, [tid], env.num_sms)
     return Q, S.to(d), table.to(d), env.utils.make_qmap2_from_qmap(table).to(d), tid
 
@@ -256,7 +229,7 @@ def test_matches_dense_fake_quantization(env, dtype):
     S = absmax.reshape(N, K // g).to(dtype)
     table = values.to(dtype)
     codes = idx.reshape(N, K).T.contiguous().to(torch.uint8)
-    tid = template(env.fa, bits, 32)
+    tid = first_template(bits, 32)
     Q = env.utils.pack(codes.to(d), bits, [tid], env.num_sms)
     X = torch.randn(M, K, generator=gen).to(dtype)
     dY = torch.randn(M, N, generator=gen).to(dtype)
@@ -285,7 +258,7 @@ def test_reproduces_reference_absmax_grad(env, dtype):
     table = values.to(dtype)
     X, dY = torch.from_numpy(z["X"]), torch.from_numpy(z["dY"])
     assert torch.equal(X.to(dtype).double(), X) and torch.equal(dY.to(dtype).double(), dY)
-    tid = template(env.fa, 4, 32)
+    tid = first_template(4, 32)
     Q = env.utils.pack(codes.to(d), 4, [tid], env.num_sms)
     table2 = env.utils.make_qmap2_from_qmap(table).to(d)
     got = env.fa.qgemm_scale_grad(dY.to(dtype).to(d), X.to(dtype).to(d), Q, table2, 4, g, tid).double().cpu()

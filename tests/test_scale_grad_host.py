@@ -11,14 +11,11 @@ import torch
 import flute_amd
 from flute_amd import _lib
 from tests import scale_grad_ref as SR
+from tests.support import first_template
 
 OK, ERR_NUM_BITS, ERR_GROUP_SIZE, ERR_TEMPLATE_ID, ERR_SHAPE, ERR_DTYPE, ERR_NULL = 0, -1, -2, -3, -4, -7, -9
 FAKE = ctypes.c_void_p(0x1000)      # never dereferenced: every call below is refused before a launch
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "scale_grad", "manual_nf4_absmax_grad.npz")
-
-
-def template(bits, tile_p):
-    return min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
 
 
 def call(dtype=0, bits=4, g=64, M=8, N=1024, K=512, P=None, tid=0, ptrs=(FAKE,) * 5, scratch=None, nbytes=0,
@@ -49,13 +46,13 @@ def test_layer_refusals():
     for g in (0, 16, 48, 512):
         assert call(g=g) == ERR_GROUP_SIZE, g
     assert call(tid=10 ** 6) == ERR_TEMPLATE_ID
-    assert call(bits=3, N=512, tid=template(3, 64)) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
+    assert call(bits=3, N=512, tid=first_template(3, 64)) == ERR_TEMPLATE_ID      # 3 bits: TileP 32 only
 
 
 def test_shape_refusals():
     assert call(N=1000) == ERR_SHAPE             # N % (J * TileP)
     assert call(N=0) == ERR_SHAPE
-    assert call(bits=3, N=256, tid=template(3, 32)) == ERR_SHAPE      # 3 bits: N % 512
+    assert call(bits=3, N=256, tid=first_template(3, 32)) == ERR_SHAPE      # 3 bits: N % 512
     assert call(K=480) == ERR_SHAPE              # K % 64
     assert call(K=384, g=256) == ERR_SHAPE       # K % g
     assert call(K=0) == ERR_SHAPE

@@ -17,7 +17,7 @@ from collections import namedtuple
 import pytest
 
 from flute_amd import TEMPLATE_CONFIGS, _lib
-from tests.test_parity_sweep_gpu import SUPPORTED_SHAPES
+from tests.qgemm_cases import SUPPORTED_SHAPES
 
 LIMIT = 0xFFFFFFF0              # the largest byte range the kernels give a descriptor
 SLAB_LIMIT = 1 << 31            # in-launch split-K slabs (xwg.h: xwg_rsrc)

@@ -13,37 +13,13 @@ import torch
 from tests import exact_cases as XC
 from tests import scale_grad_ref as SR
 from tests import table_grad_ref as TR
+from tests.grouped_cases import exact_inputs, exact_premise, exact_scales
+from tests.support import env, first_template  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "table_grad", "manual_nf4_values_grad.npz")
-QUANTUM = 2.0 ** -5          # x, dy multiples of 1/4, |s| in {1/2, 1, 2}: every term x dy s is a multiple
-
-
-@pytest.fixture(scope="module")
-def env():
-    import flute_amd
-    import flute_amd.integrations.base  # noqa: F401
-    import flute_amd.nf_utils  # noqa: F401
-    from flute_amd import utils
-    from flute_amd.integrations import learnable
-
-    class Env:
-        pass
-
-    e = Env()
-    e.fa, e.utils, e.ln = flute_amd, utils, learnable
-    e.dev = torch.device("cuda:0")
-    e.num_sms = utils.get_device_num_sms(e.dev)
-    e.ws = utils.get_workspace_streamk(e.dev)
-    return e
-
-
-def template(fa, bits, tile_p):
-    return min(t for (b, t), c in fa.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == tile_p)
-
-
 # ---------------------------------------------------------------------------
 # exactly representable data
 # ---------------------------------------------------------------------------
@@ -58,41 +34,6 @@ def exact_shape(bits, g, tile_p):
     K = {32: 448, 64: 3584 if bits != 2 else 320, 128: 1152, 256: 768}[g]
     N = XC.cols_per_block(bits, tile_p) * (3 if bits == 4 and tile_p == 32 else 1)
     return K, N
-
-
-def exact_inputs(M, K, N, dtype, seed):
-    """X and dY multiples of 1/4 in [-1, 1] (from 64 rows on: in [-1/4, 1/4], so that the larger sums stay exact)."""
-    gen = torch.Generator().manual_seed(seed)
-    amp = 4 if M < 64 else 1
-    X = (torch.randint(-amp, amp + 1, (M, K), generator=gen).double() / 4).to(dtype)
-    dY = (torch.randint(-amp, amp + 1, (M, N), generator=gen).double() / 4).to(dtype)
-    return X, dY
-
-
-def exact_scales(N, G, dtype, seed):
-    """S = +-2^e, e in {-1, 0, 1}."""
-    gen = torch.Generator().manual_seed(seed)
-    e = torch.randint(-1, 2, (N, G), generator=gen).double()
-    sign = torch.randint(0, 2, (N, G), generator=gen).double() * 2 - 1
-    return (sign * torch.pow(2.0, e)).to(dtype)
-
-
-def exact_premise(X, dY, S, codes, L, bits, g, dtype):
-    """What makes the fp64 sums the only allowed answers: every term x dy s is a multiple of QUANTUM and every bin's
-    sum of |terms| stays below 2^24 quanta, so each partial sum, in any order, is exact in fp32 (and G itself, whose
-    terms are multiples of 1/16); the same for the scale gradient's sum of |dY X L| (integers / 16) before its one
-    rounding to T.  Returns the references (dT2 [4^b, 2], dS [N, K / g]) in fp64."""
-    for t in (X, dY):
-        assert torch.equal(t.double() * 4, (t.double() * 4).round()) and t.abs().max() <= 1
-    assert torch.equal(S.double().abs().log2(), S.double().abs().log2().round()) and S.abs().max() <= 2 and S.abs().min() >= 0.5
-    A = TR.table_grad(dY, X, codes, S, bits, g, absolute=True)
-    assert float(A.max()) / QUANTUM < 2.0 ** 24, ("a bin's sum of |terms| reaches 2^24 quanta", float(A.max()))
-    As = SR.scale_grad(dY, X, L, g, absolute=True)
-    assert float(As.max()) * 16 < 2.0 ** 24
-    R = TR.table_grad(dY, X, codes, S, bits, g)
-    Rs = SR.scale_grad(dY, X, L, g)
-    assert torch.isfinite(Rs.to(dtype)).all()
-    return R, Rs
 
 
 EXACT = [(b, g, dt, tp, pair) for b, g, dt, tp, pair in
@@ -112,7 +53,7 @@ def test_exact(env, bits, g, dtype, tile_p, pair):
     d = env.dev
     lay, S = exact_case(bits, g, dtype, tile_p, pair)
     K, N = lay.K, lay.N
-    tid = template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     codes = lay.W.to(d)
     Q = env.utils.pack(codes, bits, [tid], env.num_sms)
     table2 = lay.table2.to(d)
@@ -145,7 +86,7 @@ def random_layer(env, bits, K, N, g, dtype, tile_p, seed):
     codes = torch.randint(0, 2 ** bits, (K, N), generator=gen, dtype=torch.uint8)
     table = torch.tensor(env.fa.nf_utils.NF4_VALUES, dtype=dtype)[:: 16 // 2 ** bits][: 2 ** bits]
     S = (torch.randn(N, K // g, generator=gen) / 8).to(dtype)
-    tid = template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     Q = env.utils.pack(codes.to(d), bits, [tid], env.num_sms)
     return codes.to(d), Q, S.to(d), table.to(d), env.utils.make_qmap2_from_qmap(table).to(d), tid
 
@@ -221,7 +162,7 @@ def test_activations_past_2_31_elements(env):
     bits, K, N, g, dtype, tile_p = 4, 32768, 128, 64, F16, 32
     M = 65600
     lay = XC.Layer(bits, K, N, g, dtype, seed=77, tile_p=tile_p)
-    tid = template(env.fa, bits, tile_p)
+    tid = first_template(bits, tile_p)
     codes = lay.W.to(d)
     Q = env.utils.pack(codes, bits, [tid], env.num_sms)
     L = SR.lut_of_codes(codes, lay.pairs, bits)
@@ -347,7 +288,7 @@ def test_reproduces_reference_values_grad(env, dtype):
     K, N = codes.shape
     X, dY, absmax = torch.from_numpy(z["X"]), torch.from_numpy(z["dY"]), torch.from_numpy(z["absmax"])
     assert torch.equal(X.to(dtype).double(), X) and torch.equal(dY.to(dtype).double(), dY)
-    tid = template(env.fa, 4, 32)
+    tid = first_template(4, 32)
     Q = env.utils.pack(codes.to(d), 4, [tid], env.num_sms)
     dT2 = env.fa.qgemm_table_grad(dY.to(dtype).to(d), X.to(dtype).to(d), Q, absmax.to(dtype).to(d), 4, g, tid)
     got = env.fa.pair_grad_to_table_grad(dT2).double().cpu()

@@ -5,18 +5,17 @@ family runs, per bit width and per way of combining K, exact cases whose weights
 are fp16 subnormals, and whose exact result overflows fp16 in both directions - each still with one allowed answer,
 round_T(X @ W_exact), infinities included - and cases with one NaN and one +Inf in X (fp16 and bf16), whose answer
 follows by rule: the NaN row is NaN, the Inf row is +-inf by the sign of the weight it meets (NaN where that weight is
-zero), every other row has the bits of the clean launch.  Every launch goes through test_exact_gpu.guarded_qgemm: all
+zero), every other row has the bits of the clean launch.  Every launch goes through qgemm_cases.guarded_qgemm: all
 operands and the output between poisoned guards.  Measured on gfx950: no family flushes an fp16 subnormal operand - the
 packed dot instructions and the matrix unit keep them - so the documented arithmetic holds without exception."""
 import pytest
 import torch
 
 from tests import exact_cases as E
-from tests import test_exact_gpu as G
+from tests import qgemm_cases as G
+from tests.support import env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-env = G.env
 
 
 def differing(D, R, T):
