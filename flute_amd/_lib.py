@@ -70,6 +70,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_form": (c_int, [c_int] * 10),
     "flute_qgemm_grouped_input_grad": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p]),
     "flute_qgemm_grouped_input_grad_row_block": (c_int, []),
+    "flute_qgemm_grouped_input_grad_ex": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p, c_int]),
+    "flute_qgemm_grouped_input_grad_form": (c_int, [c_int] * 10),
     "flute_qgemm_grouped_scale_grad": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
     "flute_qgemm_grouped_table_grad": (c_int, [c_int] * 9 + [c_void_p] * 10 + [c_size_t, c_int, c_void_p]),
     "flute_qgemm_grouped_table_grad_scratch_bytes": (c_size_t, [c_int] * 5),

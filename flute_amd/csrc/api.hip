@@ -1828,28 +1828,76 @@ int flute_qgemm_grouped_weighted_ex(int dtype, int num_bits, int group_size, int
 
 int flute_qgemm_grouped_input_grad_row_block(void) { return FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK; }
 
-int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
-                                   int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
-                                   const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
-                                   const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+// The two forms of the grouped input gradient (include/flute_amd.h): slabs = qgemm_grouped_input_grad.h, blocks =
+// qgemm_grouped_input_grad_blocks.h.  The automatic rule reads host-known quantities only, never `offsets`: the block form where
+// it is eligible (grouped_input_grad_blocks_eligible) and the mean rows per expert, R / E, reach a threshold - 32 where one row
+// block per expert, E * K / 256 workgroups, already fills the chip, 128 where it does not.  Why two: a block-form workgroup
+// walks all of N for 256 k, so with one block per expert the launch takes one workgroup's time however few rows the block
+// holds, and where those workgroups are fewer than the compute units the slab form's E * K / 128 fill the chip better until its
+// passes over N outnumber that.  Read from profiles/grouped_moe_input_grad_blocks.json ("threshold sweep": W4G64 fp16, us of
+// slabs / blocks at even counts, R / E = 16, 32, 48, 64, 96, 128): Mixtral down (E 8, N 4096, K 14336: 448 workgroups)
+// 141 / 158, 166 / 160, 206 / 162, 259 / 164, 369 / 201, 481 / 209; E 64 2048 x 2048 (512)
+// 76 / 84, 88 / 86, 107 / 88, 136 / 90, 191 / 109, 248 / 116; Mixtral gate / up (E 8, N 14336, K 4096: 128)
+// 191 / 262, 215 / 263, 241 / 265, 264 / 268, 322 / 330, 420 / 336 - the
+// routed draws say the same.  The constants are the lowest means of the sweep from which blocks is not slower on any stack of
+// its kind, on even and on routed counts.  The two forms give equal bits, so the rule decides the time of a launch and nothing else.
+static int grouped_input_grad_form_auto(int num_bits, int E, int R, int N, int K, int num_sms) {
+    if (!grouped_input_grad_blocks_eligible(num_bits, E, R, N, K)) return FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
+    const long long sms = num_sms >= 1 ? num_sms : 256;
+    const long long mean = (long long)E * (K / kGroupedIgBlockK) >= sms ? FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS
+                                                                        : FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS_PARTIAL;
+    return (long long)R >= mean * E ? FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS : FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
+}
+
+int flute_qgemm_grouped_input_grad_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
+                                        int template_id, int num_sms) {
+    (void)pair;                                                    // the pair form is eligible where the single form is
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, num_bits * (N / 16), &l);
+    if (rc) return rc;
+    return grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
+}
+
+int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                      int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                      const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                      const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form) {
     Layer l;
     const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
     if (rc) return rc;
     const bool pair = dY2 || Q2 || S2 || QM22;
     if (pair && row_weight) return FLUTE_ERR_SHAPE;               // the pair form takes no row weight
+    int f = form;
+    if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_AUTO) f = grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
+    else if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS ? !grouped_input_grad_blocks_eligible(num_bits, E, R, N, K)
+                                                       : f != FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS)
+        return FLUTE_ERR_SHAPE;                                    // an unknown form, or blocks forced where they do not serve
     if (R == 0) return FLUTE_OK;
     if (!dX) return FLUTE_ERR_NULL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (E == 0)                                                    // no expert serves any row: zeros, as the kernel writes them
         return hipMemsetAsync(dX, 0, (size_t)R * (size_t)K * 2, st) == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
     if (!dY || !offsets || !Q || !S || !QM2 || (pair && (!dY2 || !Q2 || !S2 || !QM22))) return FLUTE_ERR_NULL;
-    (void)num_sms;                                                 // the grid is E x ceil(K / 128): from the shapes alone
-    const int tp = l.t.tile_p, lg = l.lg;
+    const int tp = l.t.tile_p, lg = l.lg;                          // (either grid follows from the shapes alone)
+    if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS) {
+        if (num_bits == 4)
+            return qgemm_grouped_input_grad_blocks_dispatch_b4(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+        return qgemm_grouped_input_grad_blocks_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+    }
     if (num_bits == 4)
         return qgemm_grouped_input_grad_dispatch_b4(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
     if (num_bits == 3)
         return qgemm_grouped_input_grad_dispatch_b3(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
     return qgemm_grouped_input_grad_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+}
+
+int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                   int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                   const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                   const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+    return flute_qgemm_grouped_input_grad_ex(dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2,
+                                             row_weight, dY2, Q2, S2, QM22, dX, num_sms, stream,
+                                             FLUTE_GROUPED_INPUT_GRAD_FORM_AUTO);
 }
 
 // flute_qgemm_grouped_scale_grad (table false: S, dT2 and the scratch null) and _table_grad behind their signatures.  The refusals after

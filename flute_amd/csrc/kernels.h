@@ -118,6 +118,16 @@ FLUTE_IG_DISPATCH(4);
 FLUTE_IG_DISPATCH(3);
 FLUTE_IG_DISPATCH(2);
 #undef FLUTE_IG_DISPATCH
+// its block form for experts with many rows (qgemm_grouped_input_grad_blocks.h: one workgroup per 128-row block of an expert x 256 k; what it
+// serves: grouped_input_grad_blocks_eligible; inst_grouped_input_grad_blocks_b*.hip); same operands, same bits; the grid follows from (E, R, K) alone
+#define FLUTE_IGB_DISPATCH(B)                                                                                                  \
+    int qgemm_grouped_input_grad_blocks_dispatch_b##B(int dtype, int tile_p, int lg, int E, int R, int N, int K, int P,        \
+                                                      const void* dY, const void* offsets, const void* Q, const void* S,       \
+                                                      const void* QM2, const void* row_weight, const void* dY2, const void* Q2, \
+                                                      const void* S2, const void* QM22, void* dX, hipStream_t stream)
+FLUTE_IGB_DISPATCH(4);
+FLUTE_IGB_DISPATCH(2);
+#undef FLUTE_IGB_DISPATCH
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

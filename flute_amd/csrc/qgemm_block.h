@@ -76,6 +76,18 @@ inline bool grouped_blocks_eligible(int mode, int num_bits, int lg, int E, int T
     return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
 }
 
+// What the block form of the grouped input gradient serves (qgemm_grouped_input_grad_blocks.h; api.hip's form rule and refusal
+// read this, nothing else decides it): 4 / 2 bits, whole 256-k blocks, a row index plus a block that stays an int, and a 31-bit
+// grid.  (N, TileP and the group size are the slab form's, which the caller has checked with the layer; every base in the kernel
+// is 64-bit and it builds no descriptor, so no operand size is refused.)
+constexpr int kGroupedIgBlockK = 256;
+inline bool grouped_input_grad_blocks_eligible(int num_bits, int E, int R, int N, int K) {
+    if (num_bits != 4 && num_bits != 2) return false;
+    if (E < 1 || R < 1 || N < 64 || N % 64 || K < kGroupedIgBlockK || K % kGroupedIgBlockK) return false;
+    if (R > 0x7fffffff - 2 * kGroupedBlockRows) return false;
+    return grouped_blocks_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
+}
+
 constexpr int BLK_STAGES = 3;
 
 // 16-B chunk swizzle of a 16-row x 64-B activation piece (an involution applied to the DMA source address and

@@ -61,6 +61,18 @@ def grouped_form(mode: str, E: int, rows: int, N: int, K: int, num_bits: int, gr
     return {1: "rows", 2: "blocks"}[rc]
 
 
+def grouped_input_grad_form(E: int, rows: int, N: int, K: int, num_bits: int, group_size: int, template_id: int,
+                            num_sms: int = 0, dtype: torch.dtype = torch.float16, pair: bool = False) -> str:
+    """The form - "slabs" or "blocks" - the automatic rule takes for a grouped input-gradient launch of `rows` rows over
+    E experts with [N, K] layers (`pair`: the pair form); host only (flute_qgemm_grouped_input_grad_form).  A shape the
+    launch itself refuses raises."""
+    rc = _lib.get().flute_qgemm_grouped_input_grad_form(int(bool(pair)), _DTYPE_ID[dtype], num_bits, group_size, E, rows, N, K,
+                                                        template_id, num_sms)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "slabs", 2: "blocks"}[rc]
+
+
 def overrides_from_tuple(t) -> Optional[Overrides]:
     """(family, m_block, waves, kw, splitk, m_tiles, slabs_per_wave[, ring_depth[, one_shot]]) -> Overrides; None
     when every field is -1 (automatic plan)."""

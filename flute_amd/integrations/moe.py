@@ -7,7 +7,10 @@ decode, prefill and training row counts: the library picks the kernel from the s
 (qgemm_grouped.h) for decode-sized counts, the block form (qgemm_grouped_blocks.h: 128-row blocks of the dense prefill
 kernel) from a mean of 32 - 64 rows per expert on, for the plain and weighted launches of 4- and 2-bit stacks it is eligible
 for (`flute_amd.dev.grouped_form` tells which) - so the modules here need no switch: the down projection and the
-backward's recompute of gate and up take the block form by themselves; the fused GLU launch has no block form yet.
+backward's recompute of gate and up take the block form by themselves; the fused GLU launch has no block form yet.  The
+backward's two input-gradient launches have their own pair of forms - slabs and, for 4- / 2-bit stacks with K % 256 == 0 from a
+mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input_grad_blocks.h;
+`flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
 its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
 `native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`

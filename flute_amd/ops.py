@@ -378,6 +378,8 @@ def _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_si
 
 # the `form` of the three grouped forward ops -> flute_grouped_form_t
 _GROUPED_FORMS = {None: 0, "rows": 1, "blocks": 2}
+# the `form` of `qgemm_grouped_input_grad` -> flute_grouped_input_grad_form_t
+_GROUPED_INPUT_GRAD_FORMS = {None: 0, "slabs": 1, "blocks": 2}
 
 
 def _grouped_form_id(form):
@@ -386,13 +388,20 @@ def _grouped_form_id(form):
     return _GROUPED_FORMS[form]
 
 
-def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=2 ** 31, form=()):
+def _grouped_input_grad_form_id(form):
+    if form not in _GROUPED_INPUT_GRAD_FORMS:
+        raise ValueError(f"form must be None, 'slabs' or 'blocks', not {form!r}")
+    return _GROUPED_INPUT_GRAD_FORMS[form]
+
+
+def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=2 ** 31, form=(), form_id=_grouped_form_id):
     """The tail of every validated grouped op: flute_<name>(dtype, num_bits, group_size, E, *rows, N, K, P, template_id,
     *pointers, out, num_sms, stream) with `tensors` as the pointers in the ABI's order (None: a null pointer; the first
     gives the result's type and device), `rows` the ABI's row counts, each below `row_limit`, `weight` [E, P, K] one of
     the stacks and `layer` = (num_bits, group_size, template_id, num_sms).  `form` (the three forward ops, whose `name` is
-    the `_ex` entry's): (None | "rows" | "blocks",), the ABI's trailing argument.  Returns the result, `out_shape`."""
-    form = tuple(_grouped_form_id(f) for f in form)
+    the `_ex` entry's): (None | "rows" | "blocks",), the ABI's trailing argument, mapped by `form_id` (the input gradient's
+    `_ex` entry: its own names).  Returns the result, `out_shape`."""
+    form = tuple(form_id(f) for f in form)
     num_bits, group_size, template_id, num_sms = layer
     first = tensors[0]
     dev = first.device
@@ -683,7 +692,8 @@ GROUPED_INPUT_GRAD_ROW_BLOCK = _grouped_input_grad_row_block()      # include/fl
 
 def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                              table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                             row_weight=None, grad_output2=None, weight2=None, scales2=None, table22=None) -> torch.Tensor:
+                             row_weight=None, grad_output2=None, weight2=None, scales2=None, table22=None,
+                             form=None) -> torch.Tensor:
     """The input gradient of `qgemm_grouped` in one launch: dX[r] = row_weight[r] * (grad_output[r] @ W_e) for the rows r in
     [offsets[e], offsets[e + 1]), W_e [N, K] the dequantized weight of expert e (`flute_amd.dequantize`'s), the sum over
     N in fp32 in the matrix core and one rounding to grad_output.dtype.  `grad_output` [R, N] holds the rows sorted by
@@ -694,15 +704,22 @@ def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, w
     [R, K]; the rows from offsets[E] on - rows no expert serves - are zeros, so every element is written.  A workgroup
     walks an expert's rows in blocks of GROUPED_INPUT_GRAD_ROW_BLOCK.  The host never reads `offsets` (no synchronise,
     capturable); a native HIP kernel on the current stream (qgemm_grouped_input_grad.h); equal arguments give equal
-    bits.  Not differentiable itself: it raises when grad mode is on and an argument requires grad."""
+    bits.  Not differentiable itself: it raises when grad mode is on and an argument requires grad.
+
+    `form`: None - the library chooses from the shapes alone (`flute_amd.dev.grouped_input_grad_form`): the slab form
+    (a workgroup per expert and 128 k) for tens of rows per expert, the block form (qgemm_grouped_input_grad_blocks.h: a
+    workgroup per 128-row block of an expert and 256 k, for 4- / 2-bit layers with K % 256 == 0) from a mean row count per
+    expert on; "slabs" / "blocks" force one (forcing blocks on a layer that is not eligible raises).  Both forms give the
+    same bits; in the block form a malformed table may also leave rows it does name unwritten."""
+    _grouped_input_grad_form_id(form)
     _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
                                  grad_output2, weight2, scales2, table22)
     tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
     if _records_grad(*tensors):
         raise RuntimeError("flute_amd.qgemm_grouped_input_grad: the backward is once-differentiable (no double backward)")
     R, N = grad_output.shape
-    return _launch_grouped("qgemm_grouped_input_grad", tensors, weight, (R,), N, (R, weight.shape[2]),
-                           (num_bits, group_size, template_id, num_sms))
+    return _launch_grouped("qgemm_grouped_input_grad_ex", tensors, weight, (R,), N, (R, weight.shape[2]),
+                           (num_bits, group_size, template_id, num_sms), form=(form,), form_id=_grouped_input_grad_form_id)
 
 
 def _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight):

@@ -32,7 +32,9 @@ extern "C" {
  *    flute_gate_group_score; flute_qgemm_grouped_input_grad and flute_qgemm_grouped_input_grad_row_block;
  *    flute_qgemm_grouped_scale_grad; flute_qgemm_grouped_table_grad and its scratch query;
  *    the block form of the grouped forward launches: flute_qgemm_grouped_ex, flute_qgemm_grouped_glu_ex, flute_qgemm_grouped_weighted_ex
- *    (the old entries with a trailing `form`), flute_qgemm_grouped_form, flute_grouped_form_t, flute_grouped_mode_t
+ *    (the old entries with a trailing `form`), flute_qgemm_grouped_form, flute_grouped_form_t, flute_grouped_mode_t;
+ *    the block form of the grouped input gradient: flute_qgemm_grouped_input_grad_ex (the old entry with a trailing `form`),
+ *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -439,6 +441,38 @@ int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int 
                                    const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
 /* FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK of the library that is loaded */
 int flute_qgemm_grouped_input_grad_row_block(void);
+
+/* The two forms of the grouped input gradient.  Slabs (flute_grouped_input_grad_form_t 1) is the kernel described above.
+ * Blocks (2) is built for experts with hundreds of rows: a workgroup is one 128-row block of one expert x 256 k - the row
+ * blocks are found on the device from offsets as the forward's block form finds them, the grid is
+ * floor((R + 127 E) / 128) x K / 256, from (E, R, K) alone - and stages the block's dY once for all 256 k.  Operands,
+ * arithmetic, clamping, the zero rows from offsets[E] on, determinism and capture are the slab form's, and so is the order
+ * in which every output sums over N: the two forms give EQUAL BITS.  (The block form's one difference is the forward block
+ * form's: a malformed table that claims more 128-row blocks than a monotone one can own leaves the surplus unwritten.)
+ * The block form serves 4 / 2 bits and K % 256 == 0 (R <= 2^31 - 257, a 31-bit grid); 3 bits and other K stay on slabs.
+ * The automatic rule (0; flute_qgemm_grouped_input_grad is this) reads shapes only, never offsets: blocks where the shape
+ * is eligible and the mean rows per expert, R / E, reach FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS - where one row
+ * block per expert already fills the chip, E * (K / 256) >= num_sms - or FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS_PARTIAL
+ * where it does not (num_sms < 1: 256).  Both are the lowest means of the recorded sweep from which the block form is not
+ * slower on any stack of that kind.
+ * flute_qgemm_grouped_input_grad_ex is flute_qgemm_grouped_input_grad with the form chosen by the caller.  One more
+ * refusal, after the old entry's (the row_weight / pair refusal included) and before R == 0, E == 0 and the null pointers,
+ * so before anything is enqueued or dereferenced: FLUTE_ERR_SHAPE for a form outside the enum, or for blocks where the
+ * block form is not eligible (E == 0 or R == 0 included). */
+typedef enum {
+    FLUTE_GROUPED_INPUT_GRAD_FORM_AUTO = 0, FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS = 1, FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS = 2
+} flute_grouped_input_grad_form_t;
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS 32            /* E * (K / 256) >= num_sms: the experts' k blocks fill the chip */
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS_MIN_MEAN_ROWS_PARTIAL 128   /* fewer workgroups per row block than compute units */
+int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                      int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                      const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                      const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form);
+/* The form the automatic rule takes: FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS or _BLOCKS, or the negative error the launch
+ * itself would refuse the shape with.  Host only: no pointers, nothing is enqueued.  pair != 0: the pair form (the same
+ * rule); P is taken as num_bits * N / 16; num_sms < 1: 256. */
+int flute_qgemm_grouped_input_grad_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
+                                        int template_id, int num_sms);
 
 /* The gradient of the scales of a stack flute_qgemm_grouped multiplies by, in ONE launch: flute_qgemm_scale_grad for every
  * expert over the rows the device-side table gives it.  With b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):

@@ -5,7 +5,7 @@
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
-    python tools/grouped_bench.py --mode input_grad [--processes 3] [--out profiles/grouped_moe_input_grad.json]
+    python tools/grouped_bench.py --mode input_grad [--out profiles/grouped_moe_input_grad_blocks.json]
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
@@ -51,15 +51,18 @@ top-2 sum, sigmoid + bias, renormalised, scale 2.5, fp16 logits) by --mode gate'
 moe_gate at the same (E, k) - the difference is the cost of the group stage - and the torch-op chain for the same selection
 (view / topk / sum / topk / scatter / masked_fill / topk / gather / sum / div).
 
---mode input_grad times the grouped input-gradient kernel (qgemm_grouped_input_grad.h), dX = dY @ W_e per expert in one launch,
-at training-sized row counts: W4G64 fp16 at Mixtral's two projections (E = 8, K = 4096, F = 14336) with 512 and 4096 routed
-rows and at a many-expert shape (E = 64, K = 2048, F = 1408, 4096 rows), against the only alternative there was: a per-expert
-loop of flute_amd.dequantize + torch.mm with the row counts known on the host (its best case).  Same method: a hipGraph of
-steps between device-clock stamps, rotating copies of the stacks, cold caches, the median of five replays, two alternating
-passes of each form, three fresh processes.  Reported: both times, the ratio, the achieved FLOP/s against 2.5 PFLOP/s, the
-spread.  A last row splits one whole backward step of FluteExperts(fused=True, native_routing=True) at 512 tokens into its
-launches (down's input gradient with the routing weight in its epilogue, the recompute of gate and up through the grouped
-forward, the fp32 elementwise dg / du, the pair-form input gradient, moe_combine).
+--mode input_grad times the grouped input gradient, dX = dY @ W_e per expert in one launch, at training-sized row counts: its
+slab form (qgemm_grouped_input_grad.h), its block form (qgemm_grouped_input_grad_blocks.h), the automatic rule, and the only
+alternative there was: a per-expert loop of flute_amd.dequantize + torch.mm with the row counts known on the host (its best
+case).  W4G64 fp16 at Mixtral's two projections (E = 8, K = 4096, F = 14336) with 512, 4096 and 8192 routed rows and an E = 64
+2048 x 2048 stack at 4096 rows, one bf16, one 2-bit and two pair-form lines.  Same method: a hipGraph of steps between
+device-clock stamps, rotating copies of the stacks, cold caches, the median of five replays, two alternating passes of each
+contender, one process.  Reported: the times, blocks / slabs, blocks / loop, the achieved FLOP/s against 2.5 PFLOP/s, the
+spread.  Then the threshold sweep - rows / E in 16 .. 256 on two E = 8 stacks and an E = 64 stack, slabs against blocks, even
+counts and a routed draw - and one whole backward step of FluteExperts(fused=True, native_routing=True) at 512 and 4096 tokens
+with its two input-gradient launches (down's with the routing weight in its epilogue, the pair form over gate and up) on the
+slab form and on the automatic rule.  (profiles/grouped_moe_input_grad.json is the slab form's earlier record: three processes,
+grouped against loop, and the step split into its launches.)
 
 --mode scale_grad times the grouped scale-gradient kernel (param_grad.hip), dS [E, N, K / g] of a stack in one launch,
 by --mode input_grad's method at its six shape / row-count lines, against a per-expert loop of flute_amd.qgemm_scale_grad on
@@ -553,42 +556,56 @@ def ig_counts(rows, experts, seed):
 
 
 class InputGrad:
-    """`copies` stacks of `experts` packed layers [N, K]; step(i) is dX [R, K] = dY [R, N] @ W_e on copy i: one grouped launch, or
-    the per-expert loop of dequantize + mm on row ranges the host knows."""
+    """`copies` stacks of `experts` packed layers [N, K] (`pair`: two of them, and two dY); step(i) is dX [R, K] = dY [R, N] @ W_e on
+    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto" - or, "loop", the per-expert loop of dequantize + mm on row
+    ranges the host knows.  `weights`: another InputGrad of the same stack whose weight copies are shared."""
 
-    def __init__(self, experts, N, K, counts, copies, device, grouped):
+    def __init__(self, experts, N, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, pair=False, weights=None):
         import flute_amd
         from flute_amd import utils
-        self.fa, self.N, self.K, self.counts, self.grouped = flute_amd, N, K, counts, grouped
+        self.fa, self.N, self.K, self.counts, self.how, self.bits, self.pair = flute_amd, N, K, counts, how, bits, pair
         self.num_sms = utils.get_device_num_sms(device)
         gen = torch.Generator(device=device).manual_seed(1)
-        self.Q = torch.randint(-2 ** 15, 2 ** 15, (copies, experts, BITS * N // 16, K), dtype=torch.int16, device=device, generator=gen)
-        self.S = (torch.rand(copies, experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(DTYPE)
-        table = torch.randn(2 ** BITS, device=device, generator=gen).sort().values.to(DTYPE)
-        self.table2 = utils.make_qmap2_from_qmap(table)
-        self.tables2 = self.table2.repeat(experts, 1, 1, 1)
-        self.dY = torch.randn(sum(counts), N, device=device, generator=gen).to(DTYPE)
+        nst = 2 if pair else 1
+        if weights is None:
+            self.Q = [torch.randint(-2 ** 15, 2 ** 15, (copies, experts, bits * N // 16, K), dtype=torch.int16, device=device,
+                                    generator=gen) for _ in range(nst)]
+            self.S = [(torch.rand(copies, experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(dtype)
+                      for _ in range(nst)]
+            table = torch.randn(2 ** bits, device=device, generator=gen).sort().values.to(dtype)
+            self.table2 = utils.make_qmap2_from_qmap(table)
+            self.tables2 = self.table2.repeat(experts, 1, 1, 1)
+        else:
+            self.Q, self.S, self.table2, self.tables2 = weights.Q, weights.S, weights.table2, weights.tables2
+        gen_y = torch.Generator(device=device).manual_seed(2)    # (its own generator: contenders that share weights share dY too)
+        self.dY = [torch.randn(sum(counts), N, device=device, generator=gen_y).to(dtype) for _ in range(nst)]
         off = [0]
         for c in counts:
             off.append(off[-1] + c)
         self.off_host = off
         self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
-        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == BITS and c["TileP"] == 32)
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == 32)
 
     def step(self, i):
-        c = i % self.Q.shape[0]
-        if self.grouped:
-            return self.fa.qgemm_grouped_input_grad(self.dY, self.offsets, self.Q[c], self.S[c], self.tables2, BITS, G, self.tid,
-                                                    self.num_sms)
+        c = i % self.Q[0].shape[0]
+        if self.how != "loop":
+            second = dict(grad_output2=self.dY[1], weight2=self.Q[1][c], scales2=self.S[1][c], table22=self.tables2) if self.pair else {}
+            return self.fa.qgemm_grouped_input_grad(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G,
+                                                    self.tid, self.num_sms, form=None if self.how == "auto" else self.how, **second)
         out = []
         for e, m in enumerate(self.counts):
             if m:
-                W = self.fa.dequantize(self.Q[c, e], self.S[c, e], self.table2, BITS, G, self.tid)         # [N, K]
-                out.append(torch.mm(self.dY[self.off_host[e]:self.off_host[e + 1]], W))
+                r0, r1 = self.off_host[e], self.off_host[e + 1]
+                W = self.fa.dequantize(self.Q[0][c, e], self.S[0][c, e], self.table2, self.bits, G, self.tid)     # [N, K]
+                dx = torch.mm(self.dY[0][r0:r1], W)
+                if self.pair:
+                    W = self.fa.dequantize(self.Q[1][c, e], self.S[1][c, e], self.table2, self.bits, G, self.tid)
+                    dx = torch.addmm(dx, self.dY[1][r0:r1], W)
+                out.append(dx)
         return out
 
     def flops(self):
-        return 2.0 * sum(self.counts) * self.N * self.K
+        return 2.0 * sum(self.counts) * self.N * self.K * len(self.Q)
 
 
 class BackwardStep:
@@ -596,10 +613,11 @@ class BackwardStep:
     shapes), by hand, so that each can be timed alone: `part` selects one, None runs them in the backward's order."""
     PARTS = ("down_input_grad", "recompute_gate_up", "elementwise_dg_du", "pair_input_grad", "moe_combine")
 
-    def __init__(self, stacks, tokens, device, part=None, form=None):
+    def __init__(self, stacks, tokens, device, part=None, form=None, ig_form=None):
         import flute_amd
         from flute_amd import utils
         self.fa, self.part, self.form = flute_amd, part, form   # form: of the recompute's two plain launches (None: automatic)
+        self.ig_form = ig_form                                     # ... of the two input-gradient launches (None: automatic)
         self.stacks = stacks                                       # step_stacks: (gate, up, down) GroupedFluteLinear per copy
         self.num_sms = utils.get_device_num_sms(device)
         K, F = 4096, 14336
@@ -623,7 +641,7 @@ class BackwardStep:
         run = lambda name: self.part in (None, name)
         dH, g, u, dx = self.dH, self.g, self.u, self.dx
         if run("down_input_grad"):
-            dH = fa.qgemm_grouped_input_grad(self.dY, off, Qd, Sd, t2, *a, row_weight=self.row_weight)
+            dH = fa.qgemm_grouped_input_grad(self.dY, off, Qd, Sd, t2, *a, row_weight=self.row_weight, form=self.ig_form)
         if run("recompute_gate_up"):
             x = self.hidden[self.rows.long()] if self.part is None else self.x
             g, u = (fa.qgemm_grouped(x, off, Qg, Sg, t2, *a, form=self.form),
@@ -635,53 +653,11 @@ class BackwardStep:
         else:
             dg, du = self.g, self.u
         if run("pair_input_grad"):
-            dx = fa.qgemm_grouped_input_grad(dg, off, Qg, Sg, t2, *a, grad_output2=du, weight2=Qu, scales2=Su, table22=t2)
+            dx = fa.qgemm_grouped_input_grad(dg, off, Qg, Sg, t2, *a, grad_output2=du, weight2=Qu, scales2=Su, table22=t2,
+                                             form=self.ig_form)
         if run("moe_combine"):
             dx = fa.moe_combine(dx, self.pos, off)
         return dx
-
-
-def child_input_grad(args, device):
-    rows = []
-    for name, experts, N, K, nrows in IG_SHAPES:
-        counts = ig_counts(nrows, experts, seed=nrows + experts)
-        per_copy = experts * ((BITS * N // 16) * K * 2 + N * (K // G) * 2)
-        copies = max(2, bench.L3_BYTES // per_copy + 2)
-        grouped = InputGrad(experts, N, K, counts, copies, device, grouped=True)
-        loop = InputGrad(experts, N, K, counts, copies, device, grouped=False)
-        a = grouped.step(0)
-        b = torch.cat(loop.step(0))
-        torch.cuda.synchronize()
-        diff, ref = float((a.float() - b.float()).abs().max()), float(b.float().abs().max())
-        m = [measure(layer, args) for layer in (grouped, loop, grouped, loop)]
-        g_us, l_us = (m[0]["us"] + m[2]["us"]) / 2, (m[1]["us"] + m[3]["us"]) / 2
-        row = {"what": "input_grad", "shape": name, "experts": experts, "N": N, "K": K, "rows": sum(counts), "counts_min_max":
-               [min(counts), max(counts)], "weight_copies": copies, "grouped_us": round(g_us, 3), "loop_us": round(l_us, 3),
-               "grouped_over_loop": round(g_us / l_us, 4), "flop": grouped.flops(),
-               "grouped_share_of_2.5PFLOPs": round(grouped.flops() / (g_us * 1e-6) / PEAK_FLOPS, 4),
-               "loop_share_of_2.5PFLOPs": round(grouped.flops() / (l_us * 1e-6) / PEAK_FLOPS, 4),
-               "spread": max(p["spread"] for p in m), "max_abs_diff_grouped_vs_loop": diff, "max_abs_loop": ref, "passes": m}
-        rows.append(row)
-        print(json.dumps({k: v for k, v in row.items() if k != "passes"}), flush=True)
-        del grouped, loop, a, b
-        torch.cuda.empty_cache()
-    per_copy = 3 * E * ((BITS * 14336 // 16) * 4096 * 2 + 14336 * (4096 // G) * 2)
-    copies = max(2, bench.L3_BYTES // per_copy + 2)
-    stacks = step_stacks(copies, device)
-    parts = {}
-    for part in (None,) + BackwardStep.PARTS:
-        layer = BackwardStep(stacks, 512, device, part)
-        layer.step(0)
-        torch.cuda.synchronize()
-        m = [measure(layer, args) for _ in range(2)]
-        parts["whole" if part is None else part] = {"us": round((m[0]["us"] + m[1]["us"]) / 2, 3),
-                                                    "spread": max(p["spread"] for p in m), "passes": m}
-    row = {"what": "backward step", "tokens": 512, "rows": 512 * TOPK, "experts": E, "top_k": TOPK, "weight_copies": copies,
-           "parts": parts}
-    rows.append(row)
-    print(json.dumps({"what": row["what"], "tokens": 512, "us": {k: v["us"] for k, v in parts.items()}}), flush=True)
-    with open(args.out, "w") as f:
-        json.dump({"device": torch.cuda.get_device_name(device), "rows": rows}, f)
 
 
 class ScaleGrad:
@@ -997,6 +973,98 @@ def main_prefill(args, device):
     print("wrote", args.out)
 
 
+# (name, experts, N, K, routed rows, bits, dtype, pair): dX [rows, K] = dY [rows, N] @ W_e; the counts are --mode scale_grad's draws
+IG_LINES = [("mixtral gate_up", 8, 14336, 4096, r, 4, "float16", False) for r in (512, 4096, 8192)] + \
+           [("mixtral down", 8, 4096, 14336, r, 4, "float16", False) for r in (512, 4096, 8192)] + \
+           [("many-expert 2048 x 2048", 64, 2048, 2048, 4096, 4, "float16", False),
+            ("mixtral gate_up", 8, 14336, 4096, 4096, 4, "bfloat16", False),
+            ("mixtral gate_up", 8, 14336, 4096, 4096, 2, "float16", False),
+            ("mixtral gate_up pair", 8, 14336, 4096, 512, 4, "float16", True),
+            ("mixtral gate_up pair", 8, 14336, 4096, 4096, 4, "float16", True)]
+IG_FORMS = ("slabs", "blocks", "auto")
+
+
+def main_input_grad_forms(args, device):
+    """--mode input_grad: the two forms of the grouped input gradient, the automatic rule and the per-expert loop, in one process."""
+    from flute_amd import dev
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        with open(args.out, "w") as f:                # (rewritten after every line: a long run that is cut short keeps its lines)
+            json.dump({"what": "grouped input gradient at training row counts: slab form, block form, the automatic rule and a "
+                               "per-expert loop of flute_amd.dequantize + torch.mm with host-known counts; hipGraph replays, "
+                               "device-clock stamps, cold caches, median of the replays, two alternating passes of each contender "
+                               "in one process; then the threshold sweep and one backward step of FluteExperts(fused=True, "
+                               "native_routing=True) with its two input-gradient launches on the slab form and on the automatic rule",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name, experts, N, K, nrows, bits, dt, pair in IG_LINES:
+        dtype = getattr(torch, dt)
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        copies = prefill_copies(experts, N, K, bits, stacks=2 if pair else 1)
+        first = InputGrad(experts, N, K, counts, copies, device, "slabs", bits, dtype, pair)
+        layers = {"slabs": first}
+        for how in ("blocks", "auto", "loop"):
+            layers[how] = InputGrad(experts, N, K, counts, copies, device, how, bits, dtype, pair, weights=first)
+        a, b = layers["blocks"].step(0), torch.cat(layers["loop"].step(0))
+        torch.cuda.synchronize()
+        equal = bool(torch.equal(a.view(torch.int16), layers["slabs"].step(0).view(torch.int16)))
+        diff, ref = float((a.float() - b.float()).abs().max()), float(b.float().abs().max())
+        us, spread, replays = time_forms(layers, args)
+        flop = first.flops()
+        emit({"what": "input_grad", "shape": name, "bits": bits, "dtype": dt, "pair": pair, "experts": experts, "N": N, "K": K,
+              "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+              "auto_form": dev.grouped_input_grad_form(experts, sum(counts), N, K, bits, G, first.tid, first.num_sms, dtype, pair),
+              "us": us, "blocks_over_slabs": round(us["blocks"] / us["slabs"], 4), "blocks_over_loop": round(us["blocks"] / us["loop"], 4),
+              "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()},
+              "share_of_2.5PFLOPs": {n: round(flop / (v * 1e-6) / PEAK_FLOPS, 4) for n, v in us.items()},
+              "row_blocks": sum(-(-c // 128) for c in counts), "workgroups_with_rows": sum(-(-c // 128) for c in counts) * (K // 256),
+              "spread": spread, "flop": flop, "blocks_bits_equal_slabs": equal, "max_abs_diff_blocks_vs_loop": diff,
+              "max_abs_loop": ref, "replays_us": replays})
+        del layers, first, a, b
+        torch.cuda.empty_cache()
+    # the threshold sweep: rows / E on both sides of the rule, slabs against blocks, even counts and a routed draw
+    for name, experts, N, K in SWEEP_STACKS:
+        copies = prefill_copies(experts, N, K, BITS)
+        first = None
+        for mean in SWEEP_MEANS:
+            for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                        ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                layers = {}
+                for how in IG_FORMS:
+                    layers[how] = InputGrad(experts, N, K, counts, copies, device, how, weights=first)
+                    first = first or layers[how]
+                us, spread, replays = time_forms(layers, args)
+                emit({"what": "threshold sweep", "shape": name, "experts": experts, "N": N, "K": K, "mean_rows_per_expert": mean,
+                      "counts": spread_name, "counts_min_max": [min(counts), max(counts)], "rows": sum(counts), "us": us,
+                      "blocks_over_slabs": round(us["blocks"] / us["slabs"], 4),
+                      "auto_over_best": round(us["auto"] / min(us["slabs"], us["blocks"]), 4), "spread": spread,
+                      "auto_form": dev.grouped_input_grad_form(experts, sum(counts), N, K, BITS, G, first.tid, first.num_sms),
+                      "replays_us": replays})
+                del layers
+        del first
+        torch.cuda.empty_cache()
+    # one backward step of FluteExperts(fused=True, native_routing=True): the input gradients on the slab form (the code before
+    # the block form) and on the automatic rule
+    copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
+    stacks = step_stacks(copies, device)
+    for tokens in (512, 4096):
+        layers = {}
+        for part in (None, "down_input_grad", "pair_input_grad"):
+            for form in ("slabs", None):
+                layers[("whole" if part is None else part) + (" slabs" if form else " auto")] = \
+                    BackwardStep(stacks, tokens, device, part, ig_form=form)
+        us, spread, replays = time_forms(layers, args)
+        emit({"what": "backward step", "tokens": tokens, "rows": tokens * TOPK, "experts": E, "top_k": TOPK, "weight_copies": copies,
+              "us": us, "whole_auto_over_slabs": round(us["whole auto"] / us["whole slabs"], 4), "spread": spread,
+              "replays_us": replays})
+    print("wrote", args.out)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -1026,7 +1094,7 @@ def main_input_grad(args):
                        per_process_us={f: [p[f + "_us"] for p in per] for f in TG_FORMS},
                        max_abs_diff_grouped_vs_loop=max(p["max_abs_diff_grouped_vs_loop"] for p in per),
                        max_abs_loop=first["max_abs_loop"], replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
-        elif first["what"] in ("input_grad", "scale_grad"):
+        elif first["what"] == "scale_grad":
             g_us, l_us = median([p["grouped_us"] for p in per]), median([p["loop_us"] for p in per])
             row = {k: first[k] for k in ("what", "shape", "experts", "N", "K", "rows", "counts_min_max", "weight_copies", "flop")}
             row.update(grouped_us=g_us, loop_us=l_us, grouped_over_loop=round(g_us / l_us, 4),
@@ -1037,17 +1105,9 @@ def main_input_grad(args):
                        per_process_loop_us=[p["loop_us"] for p in per],
                        max_abs_diff_grouped_vs_loop=max(p["max_abs_diff_grouped_vs_loop"] for p in per),
                        max_abs_loop=first["max_abs_loop"], replays_us=[[q["replays_us"] for q in p["passes"]] for p in per])
-        else:
-            row = {k: first[k] for k in ("what", "tokens", "rows", "experts", "top_k", "weight_copies")}
-            row["parts_us"] = {k: median([p["parts"][k]["us"] for p in per]) for k in first["parts"]}
-            row["parts_spread"] = {k: max(p["parts"][k]["spread"] for p in per) for k in first["parts"]}
-            row["per_process_parts_us"] = [{k: v["us"] for k, v in p["parts"].items()} for p in per]
         rows.append(row)
         print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
-    what = {"input_grad": "grouped input gradient (one launch) vs a per-expert loop of dequantize + mm with host-known row counts; and one "
-                          "backward step of FluteExperts(fused=True, native_routing=True) split into its launches; hipGraph replays, "
-                          "device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
-            "scale_grad": "grouped scale gradient (one launch) vs a per-expert loop of the dense qgemm_scale_grad with host-known row "
+    what = {"scale_grad": "grouped scale gradient (one launch) vs a per-expert loop of the dense qgemm_scale_grad with host-known row "
                           "counts; hipGraph replays, device-clock stamps, cold caches; passes per process: grouped, loop, grouped, loop",
             "table_grad": "grouped table gradient (main launch + reduce): dT2 alone (table), dT2 + dS in the same launch pair (fused), "
                           "qgemm_grouped_scale_grad followed by the dT2-only pair (separate), and a per-expert loop of the dense "
@@ -1090,16 +1150,16 @@ def main():
         args.out = os.path.join(ROOT, "profiles", {"projection": "grouped_moe.json", "mlp": "grouped_moe_fused.json",
                                                    "step": "grouped_moe_routing.json", "gate": "grouped_moe_gate.json",
                                                    "gate_limited": "grouped_moe_gate_limited.json",
-                                                   "input_grad": "grouped_moe_input_grad.json",
+                                                   "input_grad": "grouped_moe_input_grad_blocks.json",
                                                    "scale_grad": "grouped_moe_scale_grad.json",
                                                    "table_grad": "grouped_moe_table_grad.json",
                                                    "prefill": "grouped_moe_prefill.json"}[args.mode])
-    if args.mode in ("input_grad", "scale_grad", "table_grad"):
+    if args.mode in ("scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
         device = torch.device("cuda", 0)
         torch.cuda.set_device(device)
-        child = {"scale_grad": child_scale_grad, "table_grad": child_table_grad, "input_grad": child_input_grad}
+        child = {"scale_grad": child_scale_grad, "table_grad": child_table_grad}
         return child[args.mode](args, device)
     if args.mode in ("step", "gate") and not args.child:
         return main_step(args)                       # the parent never opens the GPU
@@ -1115,6 +1175,8 @@ def main():
         return main_mlp(args, device)
     if args.mode == "prefill":
         return main_prefill(args, device)
+    if args.mode == "input_grad":
+        return main_input_grad_forms(args, device)
     rows = []
     bits = args.bits
     for name, N, K in (("gate_up", 14336, 4096), ("down", 4096, 14336)):
