@@ -1,8 +1,9 @@
 """Hostile operands for the MoE and training ops: the constructions and the by-rule expectations.
 
 A test helper module (not a conftest).  `tests/test_op_edge_cases.py` checks every construction and every rule on the CPU,
-`tests/test_grouped_edges_gpu.py` and `tests/test_grad_edges_gpu.py` run them against the kernels.  Each builder asserts
-the premises of its case while it builds it, so a premise holds wherever the case is used.
+`tests/test_grouped_edges_gpu.py`, `tests/test_block_edges_gpu.py` (the block variants) and `tests/test_grad_edges_gpu.py`
+run them against the kernels.  Each builder asserts the premises of its case while it builds it, so a premise holds
+wherever the case is used.
 
 Range edges (fp16): an exact case outside the exact tests' operating region - subnormal weights (`Layer(**SUBW)`),
 a subnormal row operand (j 2^-20), a result that overflows in both directions - still has ONE allowed answer, round_T of
@@ -33,6 +34,13 @@ GRAD_OVERFLOW_N, GRAD_OVERFLOW_K = 4096, 128
 SG_COUNTS = [0, 31, 33, 0, 64, 5]
 SG_M = 259                        # 9 steps of 32 rows: the dense scale gradient may split them in two (kSgMinSteps = 4)
 WEIGHTS = (0.5, 1.0, 2.0, -1.0, -0.25, 0.0)
+# The block forms (qgemm_grouped_blocks.h, qgemm_grouped_input_grad_blocks.h): 4 and 2 bits, 128-row blocks per expert.  Every
+# builder below takes `block`: the same construction at shapes the block forms serve - grad_counts() for the forward too, N a
+# multiple of 256, K = 8 groups in the forward, K = 512 (two k blocks of 256) in the gradient.
+BLOCK_CONFIGS = tuple(c for c in CONFIGS if c[0] != 3)
+BLOCK_G_CASES = tuple(c for c in G_CASES if c[0] != 3)
+BLOCK_K_GRAD = 512
+BLOCK_OVERFLOW_K_GRAD = 256
 
 
 def grad_counts(rb=ROW_BLOCK):
@@ -116,6 +124,46 @@ def has_both_infs(R, dtype):
     return bool((Rt == INF).any() and (Rt == -INF).any())
 
 
+def block_n(bits, tile_p):
+    return max(256, XC.cols_per_block(bits, tile_p))
+
+
+def largest(counts):
+    return counts.index(max(counts))
+
+
+def forward_blocks_eligible(bits, g, K, N):
+    """include/flute_amd.h, "The block form serves" (the byte limits are far away)."""
+    return bits in (4, 2) and K % g == 0 and (K // g) % 8 == 0 and N % 256 == 0
+
+
+def grad_blocks_eligible(bits, K):
+    return bits in (4, 2) and K % 256 == 0
+
+
+def _forward_shape(bits, tile_p, g, block, overflow=False):
+    """(counts, K, N) of a forward case."""
+    if block:
+        counts, K, N = grad_counts(), (XC.OVERFLOW_K if overflow else 8 * g), block_n(bits, tile_p)
+        assert forward_blocks_eligible(bits, g, K, N)
+        return counts, K, N
+    return FWD_COUNTS, (XC.OVERFLOW_K if overflow else K_EDGE), 3 * XC.cols_per_block(bits, tile_p)
+
+
+def _grad_shape(bits, tile_p, block, overflow=False):
+    """(K, N) of a gradient case."""
+    if block:
+        K, N = (BLOCK_OVERFLOW_K_GRAD, GRAD_OVERFLOW_N) if overflow else (BLOCK_K_GRAD, block_n(bits, tile_p))
+        assert grad_blocks_eligible(bits, K)
+        return K, N
+    return (GRAD_OVERFLOW_K, GRAD_OVERFLOW_N) if overflow else (K_EDGE, 3 * XC.cols_per_block(bits, tile_p))
+
+
+def _block_key(block):
+    """What a block variant adds to a seed's key: nothing for the cases that existed before it."""
+    return ("blocks",) if block else ()
+
+
 def _small_premise(kind, x, lay, A):
     """premise_edge's exactness conditions for an expert with fewer than three rows (no room for the edge rows)."""
     if kind == "subw":
@@ -143,12 +191,11 @@ def forward_exact(layers, counts, X, rows=None, flush_w=False, flush_x=False):
     return R, A
 
 
-def forward_range_case(op, kind, bits, tile_p, g=64):
+def forward_range_case(op, kind, bits, tile_p, g=64, block=False):
     """Plain / Weighted at a range edge: the expectation c.R is fp64, the allowed answer round_T(c.R) by value."""
-    dtype, counts = F16, FWD_COUNTS
-    N = 3 * XC.cols_per_block(bits, tile_p)
-    K = XC.OVERFLOW_K if kind == "overflow" else K_EDGE
-    seed = XC.seed_of("forward", kind, bits, tile_p, g)
+    dtype = F16
+    counts, K, N = _forward_shape(bits, tile_p, g, block, kind == "overflow")
+    seed = XC.seed_of("forward", kind, bits, tile_p, g, *_block_key(block))
     if kind == "overflow":
         layers = overflow_stack(bits, tile_p, g, dtype, K, N, counts, seed, 3,
                                 lambda lay: _reaches(lay.w_exact(0, min(N, 256)).abs().sum(0)))
@@ -173,25 +220,26 @@ def forward_range_case(op, kind, bits, tile_p, g=64):
     rw = None
     if op == "weighted":
         rw = draw_weights(T, seed + 3)                 # powers of two and zero: rw times an exact fp32 sum is exact
-        rw[off[5]:off[5] + 4] = torch.tensor([1.0, 1.0, 1.0, 0.0])  # the largest expert's edge rows keep their size; a zero
+        big = off[largest(counts)]
+        rw[big:big + 4] = torch.tensor([1.0, 1.0, 1.0, 0.0])  # the largest expert's edge rows keep their size; a zero
         R = R * rw.double()[:, None]
     if kind == "overflow":
         assert has_both_infs(R, dtype) and (torch.isfinite(R.to(dtype)) & (R.abs() >= 2.0 ** 15)).any()
     return types.SimpleNamespace(op=op, kind=kind, bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N, counts=counts,
-                                 layers=layers, X=X, rw=rw, R=R, rows=None)
+                                 layers=layers, X=X, rw=rw, R=R, rows=None, block=block)
 
 
-def weighted_pushed_case(bits, tile_p, g=64):
+def weighted_pushed_case(bits, tile_p, g=64, block=False):
     """The unweighted result is finite; a power-of-two row weight alone pushes row a past 65520 (+inf), and the same
     weight negated on a copy of the row, b, gives -inf at the same place."""
-    dtype, counts, K = F16, FWD_COUNTS, K_EDGE
-    N = 3 * XC.cols_per_block(bits, tile_p)
-    seed = XC.seed_of("pushed", bits, tile_p, g)
+    dtype = F16
+    counts, K, N = _forward_shape(bits, tile_p, g, block)
+    seed = XC.seed_of("pushed", bits, tile_p, g, *_block_key(block))
     layers = stack(bits, tile_p, g, dtype, K, N, len(counts), seed)
     off = offsets_list(counts)
     T = off[-1]
     X = XC.make_x(T, K, seed + 1, dtype)
-    a, b = off[5] + 1, off[5] + 2
+    a, b = off[largest(counts)] + 1, off[largest(counts)] + 2
     X[b] = X[a]
     R, A = forward_exact(layers, counts, X)
     for e, n in enumerate(counts):
@@ -212,7 +260,7 @@ def weighted_pushed_case(bits, tile_p, g=64):
     pos = Rt[a] == INF
     assert bool((Rt[b][pos] == -INF).all())
     return types.SimpleNamespace(op="weighted", kind="pushed", bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N,
-                                 counts=counts, layers=layers, X=X, rw=rw, R=R, rows=None, a=a, b=b)
+                                 counts=counts, layers=layers, X=X, rw=rw, R=R, rows=None, a=a, b=b, block=block)
 
 
 # --- Glu saturation -----------------------------------------------------------------------------------------------
@@ -306,29 +354,57 @@ def forward_inf_sign(c, r, k):
     return s
 
 
-def forward_nonfinite_case(op, bits, tile_p, g, dtype, use_rows=False):
+def block_places(first, last, later):
+    """[(name, NaN row, Inf row, (column of the NaN, column of the Inf), the pair form's second stack)] over grad_counts(): the
+    last valid row of a ragged 128-row block against the first row of the next expert, which follows it directly in memory;
+    across the empty expert; the second and the third row block of the largest expert; the first seam once more the other way
+    round - an Inf in the last valid row is what a tail masked by a multiplication would turn into NaN."""
+    return (("seam 127|128, first chunk", 127, 128, first, False), ("seam 384|385, last chunk", 384, 385, last, True),
+            ("later row blocks", 385 + 128 + 5, 642, later, False),
+            ("seam 127|128, Inf in the last row", 128, 127, first, False))
+
+
+BLOCK_ZERO_WEIGHT_ROW = 400       # a finite row of the largest expert whose row weight is zero
+BLOCK_INF_ROW_WEIGHTS = ((128, -2.0), (385, 0.0), (642, 0.5))      # Inf rows: a negative weight, zero (all NaN), a small one
+
+
+def _block_row_weights(rw):
+    for r, w in BLOCK_INF_ROW_WEIGHTS + ((BLOCK_ZERO_WEIGHT_ROW, 0.0),):
+        rw[r] = w
+    assert float(rw[127]) != 0                               # (the fourth place's Inf row keeps a drawn, non-zero weight)
+    return rw
+
+
+def forward_nonfinite_case(op, bits, tile_p, g, dtype, use_rows=False, block=False):
     """One NaN and one +Inf per launch, on both sides of a seam between two experts that have rows (c.launches); glu
     through `rows`: each poisoned token has two slots in two different experts."""
-    counts, K = FWD_COUNTS, K_EDGE
-    N = 3 * XC.cols_per_block(bits, tile_p)
-    seed = XC.seed_of("forward nonfinite", op, bits, tile_p, g, dtype, use_rows)
-    lseed = XC.seed_of("forward nonfinite layers", bits, tile_p, g, dtype)      # one stack for every op
+    assert not (block and (op == "glu" or use_rows)), "the GLU launch has no block form"
+    counts, K, N = _forward_shape(bits, tile_p, g, block)
+    seed = XC.seed_of("forward nonfinite", op, bits, tile_p, g, dtype, use_rows, *_block_key(block))
+    lseed = XC.seed_of("forward nonfinite layers", bits, tile_p, g, dtype, *_block_key(block))      # one stack for every op
     E = len(counts)
     layers = stack(bits, tile_p, g, dtype, K, N, E, lseed)
     up = stack(bits, tile_p, g, dtype, K, N, E, lseed + 500) if op == "glu" else None
     off = offsets_list(counts)
     R = off[-1]
-    assert off[3] == 16 and off[5] == 33 and counts[4] == 0
     c = types.SimpleNamespace(op=op, kind="nonfinite", bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N, counts=counts,
-                              layers=layers, up=up, rows=None, rw=None)
+                              layers=layers, up=up, rows=None, rw=None, block=block)
     first, last = (3, 6), (K - 2, K - 5)                    # (k of the NaN, k of the Inf): an even and an odd k each
-    # (NaN row, Inf row): the seam 15 | 16 inside a 16-row tile; 32 | 33 across the empty expert; the second row pass of the
-    # largest expert (row 33 + 32 at 32 rows a pass, rows 49 .. 64 at 16)
-    places = (("seam 15|16, first k-step", 15, 16, first), ("seam 32|33, last group", 32, 33, last),
-              ("second row pass", 65, 50, (K - 2, 6)))
+    if block:
+        assert off[3] == 128 and off[6] == 385 and counts[5] == 0 and counts[6] == 259
+        places = tuple(p[:4] for p in block_places(first, last, (K - 2, 6)))
+    else:
+        assert off[3] == 16 and off[5] == 33 and counts[4] == 0
+        # (NaN row, Inf row): the seam 15 | 16 inside a 16-row tile; 32 | 33 across the empty expert; the second row pass of the
+        # largest expert (row 33 + 32 at 32 rows a pass, rows 49 .. 64 at 16)
+        places = (("seam 15|16, first k-step", 15, 16, first), ("seam 32|33, last group", 32, 33, last),
+                  ("second row pass", 65, 50, (K - 2, 6)))
     if op == "weighted":
         rw = draw_weights(R, seed + 3, (0.5, 1.0, 2.0, -1.0))
-        rw[16], rw[33], rw[50], rw[40] = -2.0, 0.0, 0.5, 0.0       # Inf rows: a negative weight, zero (all NaN); a finite row: zero
+        if block:
+            _block_row_weights(rw)
+        else:
+            rw[16], rw[33], rw[50], rw[40] = -2.0, 0.0, 0.5, 0.0   # Inf rows: a negative weight, zero (all NaN); a finite row: zero
         c.rw = rw
     scale = 2.0 ** -6 if op == "glu" else 1.0               # glu: pre-activations of moderate size, a finite clean result
     if use_rows:
@@ -446,12 +522,12 @@ def grad_premise(kind, dY, lay, A):
         assert float(A.max()) < XC.EXACT_SUM_LIMIT, float(A.max())
 
 
-def grad_range_case(form, kind, bits, tile_p, g=64):
+def grad_range_case(form, kind, bits, tile_p, g=64, block=False):
     """single / pair / weighted at a range edge; c.R fp64, the allowed answer round_T(c.R) by value."""
     dtype, counts = F16, grad_counts()
-    K, N = (GRAD_OVERFLOW_K, GRAD_OVERFLOW_N) if kind == "overflow" else (K_EDGE, 3 * XC.cols_per_block(bits, tile_p))
-    seed = XC.seed_of("grad", form, kind, bits, tile_p, g)
-    lseed = XC.seed_of("grad layers", kind, bits, tile_p, g)                  # one stack for the three forms
+    K, N = _grad_shape(bits, tile_p, block, kind == "overflow")
+    seed = XC.seed_of("grad", form, kind, bits, tile_p, g, *_block_key(block))
+    lseed = XC.seed_of("grad layers", kind, bits, tile_p, g, *_block_key(block))      # one stack for the three forms
     E = len(counts)
     if kind == "overflow":
         layers = overflow_stack(bits, tile_p, g, dtype, K, N, counts, lseed, 5, lambda lay: _reaches(lay.w_exact().abs().sum(1)))
@@ -471,7 +547,7 @@ def grad_range_case(form, kind, bits, tile_p, g=64):
             dY[off[e] + 3:off[e] + 5] = edge[:2]
     R, A = grad_exact(layers, counts, dY)
     c = types.SimpleNamespace(form=form, kind=kind, bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N, counts=counts,
-                              layers=layers, layers2=None, dY=dY, dY2=None, rw=None)
+                              layers=layers, layers2=None, dY=dY, dY2=None, rw=None, block=block, big=big)
     if form == "pair":
         if kind == "overflow":
             # the same stack twice, dY2 = -dY on the two overflowing rows: two finite halves that would each overflow alone
@@ -518,31 +594,30 @@ def grad_inf_sign(c, r, n, second=False):
     return s * float(torch.sign(c.rw[r])) if c.rw is not None else s
 
 
-def grad_nonfinite_case(form, bits, tile_p, g, dtype):
-    counts, K = grad_counts(), K_EDGE
-    N = 3 * XC.cols_per_block(bits, tile_p)
-    seed = XC.seed_of("grad nonfinite", form, bits, tile_p, g, dtype)
-    lseed = XC.seed_of("grad nonfinite layers", bits, tile_p, g, dtype)
+def grad_nonfinite_case(form, bits, tile_p, g, dtype, block=False):
+    counts = grad_counts()
+    K, N = _grad_shape(bits, tile_p, block)
+    seed = XC.seed_of("grad nonfinite", form, bits, tile_p, g, dtype, *_block_key(block))
+    lseed = XC.seed_of("grad nonfinite layers", bits, tile_p, g, dtype, *_block_key(block))
     E = len(counts)
     off = offsets_list(counts)
     Rn = off[-1]
     assert off[3] == 128 and off[6] == 385 and counts[5] == 0 and counts[6] == 259
     c = types.SimpleNamespace(form=form, kind="nonfinite", bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N,
                               counts=counts, layers=stack(bits, tile_p, g, dtype, K, N, E, lseed), layers2=None,
-                              dY=XC.make_x(Rn, N, seed + 1, dtype, witness=False), dY2=None, rw=None)
+                              dY=XC.make_x(Rn, N, seed + 1, dtype, witness=False), dY2=None, rw=None, block=block)
     if form == "pair":
         c.layers2 = stack(bits, tile_p, g, dtype, K, N, E, lseed + 700)
         c.dY2 = XC.make_x(Rn, N, seed + 50, dtype, witness=False)
     if form == "weighted":
-        c.rw = draw_weights(Rn, seed + 3, (0.25, -0.25, 1.0, -1.0, 2.0))
-        c.rw[128], c.rw[385], c.rw[642], c.rw[400] = -2.0, 0.0, 0.5, 0.0
+        c.rw = _block_row_weights(draw_weights(Rn, seed + 3, (0.25, -0.25, 1.0, -1.0, 2.0)))
     first, last = (3, 6), (N - 2, N - 5)                    # the first and the last 64-column chunk of N
     # (NaN row, Inf row): the seam 127 | 128 inside a row block; 384 | 385 across the empty expert; the second and the third
-    # row block of the largest expert
-    places = (("seam 127|128, first chunk", 127, 128, first, False), ("seam 384|385, last chunk", 384, 385, last, form == "pair"),
-              ("later row blocks", 385 + 128 + 5, 642, (N - 2, 6), False))
+    # row block of the largest expert; the block variant adds the first seam the other way round
+    places = block_places(first, last, (N - 2, 6))
     c.launches = []
-    for name, r_nan, r_inf, (n_nan, n_inf), second in places:
+    for name, r_nan, r_inf, (n_nan, n_inf), second in places if block else places[:3]:
+        second = second and form == "pair"
         dY, dY2 = c.dY, c.dY2
         if second:
             dY2 = XC.poison_x(c.dY2, r_nan, r_inf, n_nan, n_inf)
@@ -627,13 +702,15 @@ def lut(lay):
     return SR.lut_of_codes(lay.W, lay.pairs, lay.bits)
 
 
-def sg_rows(kind, M, lay, seed):
-    """(dY [M, N], X [M, K]) of one expert / one dense launch and the fp64 reference, premises asserted."""
+def sg_rows(kind, M, lay, seed, amp=4):
+    """(dY [M, N], X [M, K]) of one expert / one dense launch and the fp64 reference, premises asserted.  amp: the size of
+    the integer operand that meets the subnormal one (the j of j 2^-20 stay in [-4, 4])."""
     K, N, g, T = lay.K, lay.N, lay.g, lay.dtype
     L = lut(lay)
     assert torch.equal(L, L.round()) and L.abs().max() <= 8
     ints = lambda m, n, amp, s: torch.randint(-amp, amp + 1, (m, n), generator=torch.Generator().manual_seed(s)).double()
-    dY, X = ints(M, N, 4, seed), ints(M, K, 4, seed + 1)
+    assert amp == 4 or kind in ("subdy", "subx")
+    dY, X = ints(M, N, amp if kind == "subx" else 4, seed), ints(M, K, amp if kind == "subdy" else 4, seed + 1)
     if kind == "subdy":
         dY = dY * 2.0 ** -20
     elif kind == "subx":
@@ -655,10 +732,10 @@ def sg_rows(kind, M, lay, seed):
     return dY, X, R
 
 
-def sg_dense_case(kind, bits, g):
+def sg_dense_case(kind, bits, g, tag="sg", amp=4):
     K, N = sg_shape(bits)
-    lay = XC.Layer(bits, K, N, g, F16, XC.seed_of("sg", kind, bits, g), tile_p=32)
-    dY, X, R = sg_rows(kind, SG_M, lay, lay.seed + 1)
+    lay = XC.Layer(bits, K, N, g, F16, XC.seed_of(tag, kind, bits, g), tile_p=32)
+    dY, X, R = sg_rows(kind, SG_M, lay, lay.seed + 1, amp)
     Rt = R.to(F16).double()
     if kind == "overflow":
         row = ((Rt == INF).any(1) & (Rt == -INF).any(1) & torch.isfinite(Rt).any(1))
@@ -669,17 +746,17 @@ def sg_dense_case(kind, bits, g):
     return types.SimpleNamespace(kind=kind, bits=bits, g=g, lay=lay, dY=dY, X=X, R=R, M=SG_M)
 
 
-def sg_grouped_case(kind, bits, g):
+def sg_grouped_case(kind, bits, g, tag="sg grouped", amp=4):
     counts = SG_COUNTS
     K, N = sg_shape(bits)
-    seed = XC.seed_of("sg grouped", kind, bits, g)
+    seed = XC.seed_of(tag, kind, bits, g)
     layers = stack(bits, 32, g, F16, K, N, len(counts), seed)
     off = offsets_list(counts)
     dY, X = torch.zeros(off[-1], N, dtype=F16), torch.zeros(off[-1], K, dtype=F16)
     R = torch.zeros(len(counts), N, K // g, dtype=torch.float64)
     for e, n in enumerate(counts):
         if n:
-            dY[off[e]:off[e + 1]], X[off[e]:off[e + 1]], R[e] = sg_rows(kind, n, layers[e], seed + 100 + e)
+            dY[off[e]:off[e + 1]], X[off[e]:off[e + 1]], R[e] = sg_rows(kind, n, layers[e], seed + 100 + e, amp)
     Rt = R.to(F16).double()
     assert has_both_infs(R, F16) if kind == "overflow" else XC.is_subnormal_f16(Rt).any()
     return types.SimpleNamespace(kind=kind, bits=bits, g=g, layers=layers, counts=counts, dY=dY, X=X, R=R)
@@ -841,15 +918,27 @@ def sg_nonfinite_dense_case(bits, g, dtype):
 
 def sg_nonfinite_grouped_case(bits, g, dtype, weighted):
     """NaN in the last row of expert 1, Inf in the first row of expert 2; experts 4 and 5 stay clean, 0 and 3 zeros."""
+    return _mreduce_nonfinite_grouped_case("sg grouped nonfinite", bits, g, dtype, weighted)
+
+
+def tg_nonfinite_grouped_case(bits, g, dtype, weighted):
+    """The same seam for flute_qgemm_grouped_table_grad.  Per expert e: dT2[e] = table_grad_expected(clean[e], premultiplied
+    dY, X, codes_e, S_e) and the by-product dS[e] = scale_grad_expected(...) on the expert's rows; experts without a
+    poisoned row keep the clean launch's bits, experts without rows are zeros."""
+    return _mreduce_nonfinite_grouped_case("tg grouped nonfinite", bits, g, dtype, weighted)
+
+
+def _mreduce_nonfinite_grouped_case(tag, bits, g, dtype, weighted):
     counts = SG_COUNTS
     K, N = sg_shape(bits)
-    seed = XC.seed_of("sg grouped nonfinite", bits, g, dtype, weighted)
+    seed = XC.seed_of(tag, bits, g, dtype, weighted)
     layers = stack(bits, 32, g, dtype, K, N, len(counts), seed)
     off = offsets_list(counts)
     Rn = off[-1]
     dY = XC.make_x(Rn, N, seed + 1, dtype, witness=False)
     X = XC.make_x(Rn, K, seed + 2, dtype, witness=False)
     r_nan, r_inf = off[2] - 1, off[2]
+    assert expert_of_row(counts, r_nan) == 1 and expert_of_row(counts, r_inf) == 2 and counts[0] == 0 and counts[3] == 0
     one_sign_rows(X, (r_inf,), lut(layers[2]), g, N - 2)
     one_sign_rows(X, (r_nan,), lut(layers[1]), g, N - 2)
     rw = draw_weights(Rn, seed + 3, (0.5, 1.0, -2.0)) if weighted else None
@@ -873,6 +962,55 @@ def tg_nonfinite_case(bits, g, dtype):
                                            ("on X, tail", [(M - 2, 2, NAN), (M - 1, K - 4, INF)], []),
                                            mreduce_launches(M - 2, M - 1, K, N, g, ", tail")[1]])
 # (a 2- or 3-bit table has 16 or 64 bins: one pair row over N columns reaches all of them, and a column of dY both halves)
+
+
+TG_RANGE_KINDS = ("subdy", "subx")
+TG_AMP = 1        # the integer operand of the table gradient's range cases: a bin sums thousands of (k, n) over all rows
+
+
+def tg_exact(dY, X, lay):
+    """The fp64 table gradient of one layer's rows and the premise that makes it the one allowed answer in fp32: every term
+    X dY S is a multiple of 2^-23 (j 2^-20, an integer, a scale 2^e with e >= -3) and every bin's sum of |terms| stays
+    below 2^24 of them, so every partial sum - in any order, over any split of the rows or workgroups - is exact in fp32
+    and so is the total."""
+    assert lay.scale_exp[0] >= -3 and lay.dtype == F16
+    sub = dY if XC.is_subnormal_f16(dY.double()).any() else X
+    assert XC.is_subnormal_f16(sub.double()).sum() == (sub != 0).sum(), "a kernel that flushes the operand returns zeros"
+    R = TR.table_grad(dY, X, lay.W, lay.S, lay.bits, lay.g)
+    A = TR.table_grad(dY, X, lay.W, lay.S, lay.bits, lay.g, absolute=True)
+    assert float(A.max()) < 2.0 ** -23 * 2.0 ** 24, float(A.max())
+    assert torch.equal(R.float().double(), R) and float(R.abs().max()) > 0
+    return R
+
+
+def tg_range_case(kind, bits, g, grouped):
+    """dY ("subdy") or X ("subx") is j 2^-20: dT2 in fp32 equals c.RT (fp64) by value; c.R is the by-product dS in fp64,
+    round_T by value.  Dense: c.lay and SG_M rows; grouped: c.layers over SG_COUNTS, c.RT [E, 4^b, 2]."""
+    assert kind in TG_RANGE_KINDS
+    if not grouped:
+        c = sg_dense_case(kind, bits, g, "tg", TG_AMP)
+        c.RT = tg_exact(c.dY, c.X, c.lay)
+        return c
+    c = sg_grouped_case(kind, bits, g, "tg grouped", TG_AMP)
+    off = offsets_list(c.counts)
+    c.RT = torch.zeros(len(c.counts), 4 ** bits, 2, dtype=torch.float64)
+    for e, n in enumerate(c.counts):
+        if n:
+            c.RT[e] = tg_exact(c.dY[off[e]:off[e + 1]], c.X[off[e]:off[e + 1]], c.layers[e])
+    return c
+
+
+def tg_row_weight_case(bits, g):
+    """sg_row_weight_case for the table gradient.  c.pre = round_T(rw dY) overflows on row c.r_big alone, in every column
+    whose |dY| is 2 or more; c.pre_finite is c.pre with those entries zero - the clean operand of the rules: a bin or a dS
+    entry that no infinite entry feeds does not depend on them."""
+    c = sg_row_weight_case(bits, g)
+    inf = torch.isinf(c.pre)
+    c.pre_finite = torch.where(inf, torch.zeros_like(c.pre), c.pre)
+    c.e_big = expert_of_row(c.counts, c.r_big)
+    assert inf[c.r_big].any() and torch.isfinite(c.pre[c.r_big]).any() and not inf[torch.arange(len(inf)) != c.r_big].any()
+    assert XC.is_subnormal_f16(c.pre_finite.double()).any() and not torch.isnan(c.pre).any()
+    return c
 
 
 # ---------------------------------------------------------------------------
@@ -971,3 +1109,31 @@ def sg_range_params():
 
 def sg_nonfinite_params():
     return [(b, g, dtype) for b, g in SG_CASES for dtype in (F16, BF16) if g == 64 or dtype == F16]
+
+
+def block_forward_range_params():
+    return [(op, kind, b, p, g) for op, kind, b, p, g in forward_range_params() if b != 3]
+
+
+def block_pushed_params():
+    return list(BLOCK_CONFIGS)
+
+
+def block_forward_nonfinite_params():
+    return [(op, b, p, g, dtype) for op, b, p, g, dtype, _ in forward_nonfinite_params() if b != 3 and op != "glu"]
+
+
+def block_grad_range_params():
+    return [p for p in grad_range_params() if p[2] != 3]
+
+
+def block_grad_nonfinite_params():
+    return [p for p in grad_nonfinite_params() if p[1] != 3]
+
+
+def tg_range_params():
+    return [(kind, b, g) for kind in TG_RANGE_KINDS for b, g in SG_CASES]
+
+
+def tg_nonfinite_grouped_params():
+    return [(b, g, dtype, weighted) for b, g, dtype in sg_nonfinite_params() for weighted in (False, True)]

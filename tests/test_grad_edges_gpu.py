@@ -6,17 +6,20 @@ return round_T of the fp64 sum by value for subnormal dY, subnormal X and sums t
 with equal bits unsplit and through the fp32 scratch of a split M, and per expert the dense op's bits.  Non-finite: a NaN
 or an Inf in one row reaches exactly the elements the documented formula connects it to - one k group or one column of
 one expert's dS, the bins of dT2 its pair row feeds, one token of moe_combine - and everything else keeps the bits of
-the clean launch.  Every launch goes through the C ABI between poisoned guards (edge_runs.guarded)."""
+the clean launch.  The table gradients, dense and grouped, return the fp64 sum by value in fp32 for fp16-subnormal dY and X;
+the grouped one keeps a NaN or an Inf on either side of a seam between two experts inside the expert that owns the row, by
+the dense rules on that expert's rows, and a row weight whose product with dY overflows T is a premultiplied dY.
+Every launch goes through the C ABI between poisoned guards (edge_runs.guarded)."""
 import pytest
 import torch
 
 from tests import exact_cases as XC
 from tests import op_edge_cases as OE
 from tests import scale_grad_ref as SR
-from tests.edge_runs import (Out, carve, check_rule, dev_stack, diagnose, differing, grouped_call, guarded,
-                             offsets_tensor)
+from tests.edge_runs import (Out, carve, check_rule, dev_stack, diagnose, differing, grouped_call, grouped_table_grad_call,
+                             guarded, offsets_tensor)
 from tests.qgemm_cases import Carved, guard_bits
-from tests.support import bits16, env, fp32_blas_reduction  # noqa: F401
+from tests.support import bits16, bits32, env, fp32_blas_reduction  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -204,6 +207,88 @@ def test_table_grad_nonfinite(env, bits, g, dtype):
         ref = env.fa.qgemm_scale_grad(dYp.to(env.dev), Xp.to(env.dev), st.Q[0], st.t2[0], bits, g, st.tid)
         assert XC.nonfinite_equal(dS, ref), name
         check_rule(dS, OE.scale_grad_expected(clean_dS, dYp, Xp, OE.lut(lay), g), (bits, g, dtype, name, "fused dS"))
+
+
+@pytest.mark.parametrize("kind,bits,g", OE.tg_range_params())
+def test_table_grad_range_edges(env, kind, bits, g):
+    """dY or X is j 2^-20, all of it fp16-subnormal: every partial sum of every bin is exact in fp32 (op_edge_cases.tg_exact),
+    so dT2 equals the fp64 sum by value, and the by-product dS round_T of its fp64 sum - dense over 259 rows and grouped over
+    counts [0, 31, 33, 0, 64, 5].  A kernel that flushes the subnormal operand returns zeros."""
+    c = OE.tg_range_case(kind, bits, g, grouped=False)
+    dT2, dS = table_grad_abi(env, c.lay, c.dY, c.X)
+    assert torch.equal(dT2.double().cpu(), c.RT), (kind, bits, g, int((dT2.double().cpu() != c.RT).sum()),
+                                                   "all zeros: the subnormal operand was flushed" if not dT2.any() else "")
+    assert XC.exact_equal(dS, c.R, F16), differing(dS, c.R, F16)
+    gc = OE.tg_range_case(kind, bits, g, grouped=True)
+    dT2, dS = grouped_table_grad(env, gc.layers, gc.counts, gc.dY, gc.X)
+    for e, n in enumerate(gc.counts):
+        if not n:
+            assert torch.all(bits32(dT2[e]) == 0) and torch.all(bits16(dS[e]) == 0), e
+            continue
+        assert torch.equal(dT2[e].double().cpu(), gc.RT[e]), (kind, bits, g, e, int((dT2[e].double().cpu() != gc.RT[e]).sum()),
+                                                              "all zeros: the subnormal operand was flushed" if not dT2[e].any() else "")
+        assert XC.exact_equal(dS[e], gc.R[e], F16), (e, differing(dS[e], gc.R[e], F16))
+
+
+def grouped_table_grad(env, layers, counts, dY, X, rw=None, nan_expected=False):
+    return grouped_table_grad_call(env, dev_stack(env, layers), counts, dY, X, rw, nan_expected)
+
+
+def check_expert_by_rule(c, e, dT2, dS, clean, clean_s, dYw, Xp, what):
+    """Expert e of a grouped table-gradient launch on (dYw, Xp) - dYw the premultiplied dY - by the dense rules on its rows."""
+    off = OE.offsets_list(c.counts)
+    sl, lay = slice(off[e], off[e + 1]), c.layers[e]
+    exp = OE.table_grad_expected(clean[e], dYw[sl], Xp[sl], lay.W, lay.S, lay.bits, lay.g)
+    assert not torch.isfinite(exp).all()
+    assert equal_with_nans(dT2[e], exp), (what, e, (~torch.isfinite(dT2[e].cpu())).nonzero().tolist()[:10],
+                                          (~torch.isfinite(exp)).nonzero().tolist()[:10])
+    exp_s = OE.scale_grad_expected(clean_s[e], dYw[sl], Xp[sl], OE.lut(lay), lay.g)
+    assert not torch.isfinite(exp_s).all()
+    check_rule(dS[e], exp_s, (what, e, "fused dS"))
+
+
+@pytest.mark.parametrize("bits,g,dtype,weighted", OE.tg_nonfinite_grouped_params())
+def test_table_grad_nonfinite_grouped(env, bits, g, dtype, weighted):
+    """NaN in the last row of expert 1, Inf in the first row of expert 2, then the other way round - the Inf in a last row
+    is what a tail masked by `clamp to the last row and multiply by zero` turns into NaN: the two experts' dT2 and dS by the
+    dense rules on their own rows, experts 4 and 5 bit for bit the clean launch, the empty experts zeros; the fused dS has
+    the bits of flute_qgemm_grouped_scale_grad on the same operands."""
+    c = OE.tg_nonfinite_grouped_case(bits, g, dtype, weighted)
+    clean, clean_s = grouped_table_grad(env, c.layers, c.counts, c.dY, c.X, rw=c.rw)
+    assert torch.isfinite(clean).all() and torch.isfinite(clean_s).all()
+    for name, xs, ys in c.launches:
+        dYp, Xp = OE.poison(c.dY, ys), OE.poison(c.X, xs)
+        dT2, dS = grouped_table_grad(env, c.layers, c.counts, dYp, Xp, rw=c.rw, nan_expected=True)
+        dYw = OE.premultiplied(dYp, c.rw)
+        for e, n in enumerate(c.counts):
+            if not n:
+                assert torch.all(bits32(dT2[e]) == 0) and torch.all(bits16(dS[e]) == 0), (name, e)
+            elif e in c.touched:
+                check_expert_by_rule(c, e, dT2, dS, clean, clean_s, dYw, Xp, (bits, g, dtype, weighted, name))
+            else:
+                assert torch.equal(bits32(dT2[e]), bits32(clean[e])) and torch.equal(bits16(dS[e]), bits16(clean_s[e])), (name, e)
+        alone = grouped_scale_grad(env, c.layers, c.counts, dYp, Xp, rw=c.rw, nan_expected=True)
+        assert XC.nonfinite_equal(dS, alone), name
+
+
+@pytest.mark.parametrize("bits,g", OE.SG_CASES)
+def test_grouped_table_grad_row_weight_range_edges(env, bits, g):
+    """round_T(row_weight dY) subnormal on some rows and +-inf on one: bit for bit the unweighted launch on the premultiplied
+    dY; the expert that owns the overflowing row by the rules on the premultiplied dY, from the clean bits of a launch on the
+    premultiplied dY with the infinite entries zero; every other expert that launch's bits."""
+    c = OE.tg_row_weight_case(bits, g)
+    weighted = grouped_table_grad(env, c.layers, c.counts, c.dY, c.X, rw=c.rw, nan_expected=True)
+    pre = grouped_table_grad(env, c.layers, c.counts, c.pre, c.X, nan_expected=True)
+    clean, clean_s = grouped_table_grad(env, c.layers, c.counts, c.pre_finite, c.X, nan_expected=True)
+    assert equal_with_nans(weighted[0], pre[0]) and XC.nonfinite_equal(weighted[1], pre[1])
+    assert torch.isfinite(clean).all() and not torch.isnan(clean_s).any()
+    dT2, dS = weighted
+    for e, n in enumerate(c.counts):
+        if e == c.e_big:
+            check_expert_by_rule(c, e, dT2, dS, clean, clean_s, c.pre, c.X, (bits, g, "row weight"))
+        else:
+            assert torch.equal(bits32(dT2[e]), bits32(clean[e])) and torch.equal(bits16(dS[e]), bits16(clean_s[e])), e
+            assert bool(dT2[e].any()) == (n > 0)
 
 
 # ---- moe_combine ---------------------------------------------------------------------------------------------------------

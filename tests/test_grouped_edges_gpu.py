@@ -15,39 +15,14 @@ import torch
 
 from tests import exact_cases as XC
 from tests import op_edge_cases as OE
-from tests.edge_runs import check_rule, dev_stack, diagnose, differing, grouped_call, offsets_tensor
+from tests.edge_runs import (check_rule, diagnose, differing, forward_alternatives, grad_alternatives, grad_reference,
+                             run_forward, run_grad)
 from tests.grouped_cases import assert_glu
 from tests.support import env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-
-
-def run_forward(env, c, X, nan_expected=False):
-    st = dev_stack(env, c.layers)
-    off = offsets_tensor(c.counts)
-    R = int(off[-1])
-    if c.op == "glu":
-        up = dev_stack(env, c.up)
-        rows = None if c.rows is None else c.rows.int()
-        return grouped_call(env, "qgemm_grouped_glu", st, (R, X.shape[0]), c.N,
-                            (X, rows, off, st.Q, st.S, st.t2, up.Q, up.S, up.t2), (R, c.N), nan_expected)
-    if c.op == "weighted":
-        return grouped_call(env, "qgemm_grouped_weighted", st, (R,), c.N, (X, off, st.Q, st.S, st.t2, c.rw), (R, c.N), nan_expected)
-    return grouped_call(env, "qgemm_grouped", st, (R,), c.N, (X, off, st.Q, st.S, st.t2), (R, c.N), nan_expected)
-
-
-def run_grad(env, c, dY, dY2, nan_expected=False):
-    st = dev_stack(env, c.layers)
-    off = offsets_tensor(c.counts)
-    R = int(off[-1])
-    second = (None,) * 4
-    if dY2 is not None:
-        s2 = dev_stack(env, c.layers2)
-        second = (dY2, s2.Q, s2.S, s2.t2)
-    return grouped_call(env, "qgemm_grouped_input_grad", st, (R,), c.N, (dY, off, st.Q, st.S, st.t2, c.rw, *second), (R, c.K),
-                        nan_expected)
 
 
 # ---- the grouped forward -----------------------------------------------------------------------------------------------
@@ -57,11 +32,7 @@ def test_forward_range_edges(env, op, kind, bits, tile_p, g):
     c = OE.forward_range_case(op, kind, bits, tile_p, g)
     D = run_forward(env, c, c.X)
     if not XC.exact_equal(D, c.R, c.dtype):
-        w = 1 if c.rw is None else c.rw.double()[:, None]
-        alt = [("subnormal %s flushed" % n, OE.forward_exact(c.layers, c.counts, c.X, flush_w=fw, flush_x=fx)[0] * w)
-               for n, fw, fx in (("w", True, False), ("x", False, True), ("w+x", True, True))]
-        alt.append(("saturates at 65504", c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX)))
-        raise AssertionError((op, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, alt)))
+        raise AssertionError((op, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, forward_alternatives(c))))
 
 
 @pytest.mark.parametrize("bits,tile_p", OE.pushed_params())
@@ -113,23 +84,14 @@ def test_input_grad_range_edges(env, form, kind, bits, tile_p, g):
     c = OE.grad_range_case(form, kind, bits, tile_p, g)
     D = run_grad(env, c, c.dY, c.dY2)
     if not XC.exact_equal(D, c.R, c.dtype):
-        alt = [("saturates at 65504", c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX))]
-        for n, fw, fy in (("w", True, False), ("dY", False, True), ("w+dY", True, True)):
-            R = OE.grad_exact(c.layers, c.counts, c.dY, flush_w=fw, flush_y=fy)[0]
-            if c.dY2 is not None:
-                R = R + OE.grad_exact(c.layers2, c.counts, c.dY2, flush_w=fw, flush_y=fy)[0]
-            alt.append(("subnormal %s flushed" % n, R if c.rw is None else R * c.rw.double()[:, None]))
-        raise AssertionError((form, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, alt)))
+        raise AssertionError((form, kind, bits, tile_p, g, differing(D, c.R, c.dtype), diagnose(D, c.dtype, grad_alternatives(c))))
 
 
 @pytest.mark.parametrize("form,bits,tile_p,g,dtype", OE.grad_nonfinite_params())
 def test_input_grad_nonfinite(env, form, bits, tile_p, g, dtype):
     c = OE.grad_nonfinite_case(form, bits, tile_p, g, dtype)
     clean = run_grad(env, c, c.dY, c.dY2)
-    R = OE.grad_exact(c.layers, c.counts, c.dY)[0]
-    if c.dY2 is not None:
-        R = R + OE.grad_exact(c.layers2, c.counts, c.dY2)[0]
-    assert XC.exact_equal(clean, R if c.rw is None else R * c.rw.double()[:, None], dtype)
+    assert XC.exact_equal(clean, grad_reference(c), dtype)
     for la in c.launches:
         D = run_grad(env, c, la.dY, la.dY2, nan_expected=True)
         check_rule(D, OE.rowwise_expected(clean, la.poisons), (form, bits, tile_p, g, dtype, la.name))
