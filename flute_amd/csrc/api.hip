@@ -25,6 +25,7 @@
 #include "mfma.h"
 #include "qgemm_tile.h"
 #include "qgemm_block.h"
+#include "grouped_rows.h"
 #include "qgemm_splitk.h"
 
 using namespace flute_amd;
@@ -1735,14 +1736,6 @@ static int resolve_grouped_form(int form, int mode, int num_bits, int lg, int E,
     if (form == FLUTE_GROUPED_FORM_BLOCKS && grouped_blocks_eligible(mode, num_bits, lg, E, rows, N, K)) return form;
     return FLUTE_ERR_SHAPE;
 }
-static int grouped_blocks_dispatch(int weighted, int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
-                                   const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
-                                   const void* row_weight, void* Y, hipStream_t st) {
-    if (num_bits == 4)
-        return qgemm_grouped_blocks_dispatch_b4(weighted, dtype, tile_p, lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y, st);
-    return qgemm_grouped_blocks_dispatch_b2(weighted, dtype, tile_p, lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y, st);
-}
-
 int flute_qgemm_grouped_form(int mode, int dtype, int num_bits, int group_size, int E, int rows, int N, int K, int template_id,
                              int num_sms) {
     if (mode != FLUTE_GROUPED_PLAIN && mode != FLUTE_GROUPED_GLU && mode != FLUTE_GROUPED_WEIGHTED) return FLUTE_ERR_SHAPE;
@@ -1752,21 +1745,39 @@ int flute_qgemm_grouped_form(int mode, int dtype, int num_bits, int group_size, 
     return grouped_form_auto(mode, num_bits, l.lg, E, rows, N, K, num_sms);
 }
 
+// flute_qgemm_grouped_ex, _glu_ex and _weighted_ex behind their signatures: the operands by name (a mode's own left null by the
+// others, one stack in both slots), and the one sequence - check_grouped, the GLU-only Tsrc / rows refusals, the form, the empty
+// launch, the null pointers, the dispatch.  (No block form of the GLU mode is built: automatic is the row form at every row count,
+// and forcing blocks is refused.)
+static int grouped_forward(GroupedForward g, int group_size, int template_id, int form, void* stream) {
+    const bool glu = g.mode == FLUTE_GROUPED_GLU;
+    Layer l;
+    const int rc = check_grouped(g.dtype, g.num_bits, group_size, template_id, g.E, g.R, g.N, g.K, g.P, &l);
+    if (rc) return rc;
+    if (glu) {
+        if (g.Tsrc < 0) return FLUTE_ERR_SHAPE;
+        if (g.rows ? (g.R > 0 && g.Tsrc < 1) : g.Tsrc != g.R) return FLUTE_ERR_SHAPE;
+    }
+    g.tile_p = l.t.tile_p;
+    g.lg = l.lg;
+    g.form = resolve_grouped_form(form, g.mode, g.num_bits, g.lg, g.E, g.R, g.N, g.K, g.num_sms);
+    if (g.form < 0) return g.form;
+    if (g.E == 0 || g.R == 0) return FLUTE_OK;
+    if (!g.X || !g.offsets || !g.Q[0] || !g.S[0] || !g.QM2[0] || !g.Y) return FLUTE_ERR_NULL;
+    if (glu && (!g.Q[1] || !g.S[1] || !g.QM2[1])) return FLUTE_ERR_NULL;
+    if (g.mode == FLUTE_GROUPED_WEIGHTED && !g.row_weight) return FLUTE_ERR_NULL;
+    return qgemm_grouped_dispatch(g, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_qgemm_grouped_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
                            const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
                            int num_sms, void* stream, int form) {
-    Layer l;
-    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
-    if (rc) return rc;
-    const int f = resolve_grouped_form(form, FLUTE_GROUPED_PLAIN, num_bits, l.lg, E, T, N, K, num_sms);
-    if (f < 0) return f;
-    if (E == 0 || T == 0) return FLUTE_OK;
-    if (!X || !offsets || !Q || !S || !QM2 || !Y) return FLUTE_ERR_NULL;
-    if (f == FLUTE_GROUPED_FORM_BLOCKS)
-        return grouped_blocks_dispatch(0, dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, nullptr, Y,
-                                       reinterpret_cast<hipStream_t>(stream));
-    return qgemm_grouped_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, Y, num_sms,
-                                  reinterpret_cast<hipStream_t>(stream));
+    GroupedForward g{};
+    g.mode = FLUTE_GROUPED_PLAIN; g.dtype = dtype; g.num_bits = num_bits;
+    g.E = E; g.R = T; g.Tsrc = T; g.N = N; g.K = K; g.P = P;
+    g.X = X; g.offsets = offsets; g.Y = Y; g.num_sms = num_sms;
+    g.Q[0] = g.Q[1] = Q; g.S[0] = g.S[1] = S; g.QM2[0] = g.QM2[1] = QM2;
+    return grouped_forward(g, group_size, template_id, form, stream);
 }
 
 int flute_qgemm_grouped(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
@@ -1784,22 +1795,17 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
                                       Sgate, QM2gate, Qup, Sup, QM2up, H, num_sms, stream, FLUTE_GROUPED_FORM_AUTO);
 }
 
-// (no block form of this mode is built: automatic is the row form at every row count, and forcing blocks is refused)
 int flute_qgemm_grouped_glu_ex(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
                                int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
                                const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
                                void* H, int num_sms, void* stream, int form) {
-    Layer l;
-    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, P, &l);
-    if (rc) return rc;
-    if (Tsrc < 0) return FLUTE_ERR_SHAPE;
-    if (rows ? (R > 0 && Tsrc < 1) : Tsrc != R) return FLUTE_ERR_SHAPE;
-    const int f = resolve_grouped_form(form, FLUTE_GROUPED_GLU, num_bits, l.lg, E, R, F, K, num_sms);
-    if (f < 0) return f;
-    if (E == 0 || R == 0) return FLUTE_OK;
-    if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
-    return qgemm_grouped_glu_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, R, Tsrc, F, K, P, Xsrc, rows, offsets, Qgate,
-                                      Sgate, QM2gate, Qup, Sup, QM2up, H, num_sms, reinterpret_cast<hipStream_t>(stream));
+    GroupedForward g{};
+    g.mode = FLUTE_GROUPED_GLU; g.dtype = dtype; g.num_bits = num_bits;
+    g.E = E; g.R = R; g.Tsrc = Tsrc; g.N = F; g.K = K; g.P = P;
+    g.X = Xsrc; g.rows = rows; g.offsets = offsets; g.Y = H; g.num_sms = num_sms;
+    g.Q[0] = Qgate; g.S[0] = Sgate; g.QM2[0] = QM2gate;
+    g.Q[1] = Qup; g.S[1] = Sup; g.QM2[1] = QM2up;
+    return grouped_forward(g, group_size, template_id, form, stream);
 }
 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
@@ -1812,18 +1818,12 @@ int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E,
 int flute_qgemm_grouped_weighted_ex(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                     int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                     const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream, int form) {
-    Layer l;
-    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
-    if (rc) return rc;
-    const int f = resolve_grouped_form(form, FLUTE_GROUPED_WEIGHTED, num_bits, l.lg, E, T, N, K, num_sms);
-    if (f < 0) return f;
-    if (E == 0 || T == 0) return FLUTE_OK;
-    if (!X || !offsets || !Q || !S || !QM2 || !row_weight || !Y) return FLUTE_ERR_NULL;
-    if (f == FLUTE_GROUPED_FORM_BLOCKS)
-        return grouped_blocks_dispatch(1, dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2, row_weight, Y,
-                                       reinterpret_cast<hipStream_t>(stream));
-    return qgemm_grouped_weighted_dispatch(dtype, num_bits, l.t.tile_p, l.lg, E, T, N, K, P, X, offsets, Q, S, QM2,
-                                           row_weight, Y, num_sms, reinterpret_cast<hipStream_t>(stream));
+    GroupedForward g{};
+    g.mode = FLUTE_GROUPED_WEIGHTED; g.dtype = dtype; g.num_bits = num_bits;
+    g.E = E; g.R = T; g.Tsrc = T; g.N = N; g.K = K; g.P = P;
+    g.X = X; g.offsets = offsets; g.row_weight = row_weight; g.Y = Y; g.num_sms = num_sms;
+    g.Q[0] = g.Q[1] = Q; g.S[0] = g.S[1] = S; g.QM2[0] = g.QM2[1] = QM2;
+    return grouped_forward(g, group_size, template_id, form, stream);
 }
 
 int flute_qgemm_grouped_input_grad_row_block(void) { return FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK; }
@@ -1878,17 +1878,13 @@ int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, i
     if (E == 0)                                                    // no expert serves any row: zeros, as the kernel writes them
         return hipMemsetAsync(dX, 0, (size_t)R * (size_t)K * 2, st) == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
     if (!dY || !offsets || !Q || !S || !QM2 || (pair && (!dY2 || !Q2 || !S2 || !QM22))) return FLUTE_ERR_NULL;
-    const int tp = l.t.tile_p, lg = l.lg;                          // (either grid follows from the shapes alone)
-    if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS) {
-        if (num_bits == 4)
-            return qgemm_grouped_input_grad_blocks_dispatch_b4(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
-        return qgemm_grouped_input_grad_blocks_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
-    }
-    if (num_bits == 4)
-        return qgemm_grouped_input_grad_dispatch_b4(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
-    if (num_bits == 3)
-        return qgemm_grouped_input_grad_dispatch_b3(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
-    return qgemm_grouped_input_grad_dispatch_b2(dtype, tp, lg, E, R, N, K, P, dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, st);
+    GroupedInputGrad g{};                                          // (either grid follows from the shapes alone)
+    g.form = f; g.dtype = dtype; g.num_bits = num_bits; g.tile_p = l.t.tile_p; g.lg = l.lg;
+    g.E = E; g.R = R; g.N = N; g.K = K; g.P = P; g.pair = pair;
+    g.dY[0] = dY; g.Q[0] = Q; g.S[0] = S; g.QM2[0] = QM2;
+    g.dY[1] = pair ? dY2 : dY; g.Q[1] = pair ? Q2 : Q; g.S[1] = pair ? S2 : S; g.QM2[1] = pair ? QM22 : QM2;
+    g.offsets = offsets; g.row_weight = row_weight; g.dX = dX;
+    return qgemm_grouped_input_grad_dispatch(g, st);
 }
 
 int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,

@@ -11,6 +11,7 @@
 // covers 8 consecutive rows, which an LDS pitch of 8 dwords mod 64 spreads over all 64 banks.
 #pragma once
 #include "common.h"
+#include "grouped_rows.h"
 #include "mfma.h"
 
 namespace flute_amd {
@@ -262,7 +263,7 @@ __device__ __forceinline__ void table_grad_epilogue(char* smem, const uint32_t* 
 }
 
 // The parameter-gradient kernel in all its forms; the axes are compile-time, a workgroup is one (k, n) block of one z.
-//   GROUPED   the row range: rows [clamp(offsets[z]), clamp(offsets[z + 1])) of expert z, with the Q / S / QM2 / dS bases
+//   GROUPED   the row range: the rows of expert z (grouped_rows.h), with the Q / S / QM2 / dS bases
 //             moved to that expert (64-bit) and a return before anything of an expert without rows is read (its block of
 //             dS written as zeros, no partial); dense: the z-th run of steps_per_split 32-row steps of [0, rows), with
 //             the scale gradient's fp32 partial at ds_part[z] when ds_part is given.
@@ -284,8 +285,9 @@ __global__ __launch_bounds__(kSgThreads, 4) void param_grad_kernel(
     const int G = K >> lg;
     int rb, re;
     if constexpr (GROUPED) {
-        rb = min(max(offsets[z], 0), rows);
-        re = min(max(offsets[z + 1], 0), rows);
+        // grouped_rows.h's range with its two clamps written out, deliberately (profiles/grouped_rows_ab.json)
+        rb = grouped_clamp(offsets[z], rows);
+        re = grouped_clamp(offsets[z + 1], rows);
         if (!TABLE || dS) dS += (size_t)z * (size_t)N * (size_t)G;
         if (re <= rb) {
             if (!TABLE || dS) scale_grad_zero_block(dS, N, K, lg, nb, kb);

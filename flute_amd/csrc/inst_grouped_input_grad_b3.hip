@@ -1,11 +1,7 @@
 // The grouped input gradient (qgemm_grouped_input_grad.h), 3 bits: 4 instantiations.
 #include "qgemm_grouped_input_grad.h"
 namespace flute_amd {
-int qgemm_grouped_input_grad_dispatch_b3(int dtype, int tile_p, int lg, int E, int R, int N, int K, int P, const void* dY,
-                                         const void* offsets, const void* Q, const void* S, const void* QM2,
-                                         const void* row_weight, const void* dY2, const void* Q2, const void* S2,
-                                         const void* QM22, void* dX, hipStream_t stream) {
-    const GroupedIgArgs a = grouped_ig_args(dY, offsets, Q, S, QM2, row_weight, dY2, Q2, S2, QM22, dX, R, N, K, P, lg, E);
-    return qgemm_grouped_input_grad_launch<3>(dtype, tile_p, dY2 != nullptr, a, stream);
+int qgemm_grouped_input_grad_unit_b3(const GroupedInputGrad& g, hipStream_t stream) {
+    return qgemm_grouped_input_grad_launch<3>(g, stream);
 }
 }  // namespace flute_amd

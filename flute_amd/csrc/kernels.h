@@ -3,6 +3,7 @@
 // the plan is made (resolve_kernel: a plan without a built kernel is refused there, FLUTE_ERR_TEMPLATE_ID); a launch looks nothing up.
 #pragma once
 #include "common.h"
+#include "../../include/flute_amd.h"
 
 namespace flute_amd {
 
@@ -84,50 +85,61 @@ struct ParamGrad {
 int param_grad_dispatch(const ParamGrad& a, hipStream_t stream);
 size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int want_dS, int num_sms);
 size_t table_grad_grouped_scratch_bytes(int num_bits, int E, int N, int K);
-// grouped qgemm of E stacked layers over rows sorted by expert (qgemm_grouped.h, one kernel template; inst_grouped_plain.hip); offsets [E + 1]
-// int32 is read on the device only
-int qgemm_grouped_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
-                           const void* offsets, const void* Q, const void* S, const void* QM2, void* Y, int num_sms,
-                           hipStream_t stream);
-// the template's fused modes for a mixture-of-experts MLP (inst_grouped_glu.hip, inst_grouped_weighted.hip): H = silu32(gate) * up over rows read through an optional
-// index, and Y = row_weight * (X @ W^T) with the rows past offsets[E] written as zeros
-int qgemm_grouped_glu_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int R, int Tsrc, int N, int K, int P,
-                               const void* Xsrc, const void* rows, const void* offsets, const void* Qg, const void* Sg,
-                               const void* QM2g, const void* Qu, const void* Su, const void* QM2u, void* H, int num_sms,
-                               hipStream_t stream);
-int qgemm_grouped_weighted_dispatch(int dtype, int num_bits, int tile_p, int lg, int E, int T, int N, int K, int P,
-                                    const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
-                                    const void* row_weight, void* Y, int num_sms, hipStream_t stream);
-// the block form of the plain and weighted grouped qgemm for experts with many rows (qgemm_grouped_blocks.h; what it
-// serves: grouped_blocks_eligible, qgemm_block.h; inst_grouped_blocks_b*.hip, one unit per bit width); the grid follows from (E, T, N) alone
-#define FLUTE_GB_DISPATCH(B)                                                                                                   \
-    int qgemm_grouped_blocks_dispatch_b##B(int weighted, int dtype, int tile_p, int lg, int E, int T, int N, int K, int P,     \
-                                           const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,  \
-                                           const void* row_weight, void* Y, hipStream_t stream)
-FLUTE_GB_DISPATCH(4);
-FLUTE_GB_DISPATCH(2);
-#undef FLUTE_GB_DISPATCH
-// the input gradient of the grouped qgemm (qgemm_grouped_input_grad.h; inst_grouped_input_grad_b*.hip, one unit per bit width): dX [R, K] from
-// dY [R, N], with dY2 / Q2 / S2 / QM22 non-null the pair form (both products summed in fp32); rows past offsets[E] written as zeros
-#define FLUTE_IG_DISPATCH(B)                                                                                                   \
-    int qgemm_grouped_input_grad_dispatch_b##B(int dtype, int tile_p, int lg, int E, int R, int N, int K, int P, const void* dY, \
-                                               const void* offsets, const void* Q, const void* S, const void* QM2,             \
-                                               const void* row_weight, const void* dY2, const void* Q2, const void* S2,        \
-                                               const void* QM22, void* dX, hipStream_t stream)
-FLUTE_IG_DISPATCH(4);
-FLUTE_IG_DISPATCH(3);
-FLUTE_IG_DISPATCH(2);
-#undef FLUTE_IG_DISPATCH
-// its block form for experts with many rows (qgemm_grouped_input_grad_blocks.h: one workgroup per 128-row block of an expert x 256 k; what it
-// serves: grouped_input_grad_blocks_eligible; inst_grouped_input_grad_blocks_b*.hip); same operands, same bits; the grid follows from (E, R, K) alone
-#define FLUTE_IGB_DISPATCH(B)                                                                                                  \
-    int qgemm_grouped_input_grad_blocks_dispatch_b##B(int dtype, int tile_p, int lg, int E, int R, int N, int K, int P,        \
-                                                      const void* dY, const void* offsets, const void* Q, const void* S,       \
-                                                      const void* QM2, const void* row_weight, const void* dY2, const void* Q2, \
-                                                      const void* S2, const void* QM22, void* dX, hipStream_t stream)
-FLUTE_IGB_DISPATCH(4);
-FLUTE_IGB_DISPATCH(2);
-#undef FLUTE_IGB_DISPATCH
+// One grouped forward launch over E stacked layers and rows sorted by expert (what every grouped kernel reads out of offsets [E + 1],
+// int32, device only: grouped_rows.h).  api.hip fills it by name; a unit fills its kernel's argument struct from it.
+struct GroupedForward {
+    int mode;                                         // FLUTE_GROUPED_PLAIN / _GLU / _WEIGHTED
+    int form;                                         // resolved: FLUTE_GROUPED_FORM_ROWS (qgemm_grouped.h) / _BLOCKS (qgemm_grouped_blocks.h)
+    int dtype, num_bits, tile_p, lg;
+    int E, R, Tsrc, N, K, P;                          // R sorted rows; Tsrc rows of X (Glu with `rows`; else R)
+    const void *X, *rows, *offsets;                   // rows [R] int32 or null: Glu only
+    const void *Q[2], *S[2], *QM2[2];                 // the stack (Glu: gate, up; else both slots hold the one stack)
+    const float* row_weight;                          // [R]: Weighted only
+    void* Y;                                          // [R, N]
+    int num_sms;
+};
+// the row form, one unit per mode (inst_grouped_plain.hip, _glu.hip, _weighted.hip: H = silu32(gate) * up over rows read through an
+// optional index; Y = row_weight * (X @ W^T) with the rows past offsets[E] written as zeros)
+int qgemm_grouped_plain_unit(const GroupedForward& g, hipStream_t stream);
+int qgemm_grouped_glu_unit(const GroupedForward& g, hipStream_t stream);
+int qgemm_grouped_weighted_unit(const GroupedForward& g, hipStream_t stream);
+// the block form of the plain and weighted modes for experts with many rows (what it serves: grouped_blocks_eligible, grouped_rows.h;
+// inst_grouped_blocks_b*.hip, one unit per bit width); the grid follows from (E, R, N) alone
+int qgemm_grouped_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);
+int qgemm_grouped_blocks_unit_b2(const GroupedForward& g, hipStream_t stream);
+// the unit of a launch: the one ladder over form, bit width and mode
+inline int qgemm_grouped_dispatch(const GroupedForward& g, hipStream_t stream) {
+    if (g.form == FLUTE_GROUPED_FORM_BLOCKS)
+        return g.num_bits == 4 ? qgemm_grouped_blocks_unit_b4(g, stream) : qgemm_grouped_blocks_unit_b2(g, stream);
+    if (g.mode == FLUTE_GROUPED_GLU) return qgemm_grouped_glu_unit(g, stream);
+    return g.mode == FLUTE_GROUPED_WEIGHTED ? qgemm_grouped_weighted_unit(g, stream) : qgemm_grouped_plain_unit(g, stream);
+}
+// One launch of the input gradient of the grouped qgemm: dX [R, K] from dY [R, N]; pair: both products summed in fp32 (the single form
+// fills both slots with its one stack); rows past offsets[E] written as zeros
+struct GroupedInputGrad {
+    int form;                                         // resolved: FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS (qgemm_grouped_input_grad.h) / _BLOCKS (.._blocks.h)
+    int dtype, num_bits, tile_p, lg;
+    int E, R, N, K, P;
+    bool pair;
+    const void *dY[2], *offsets;
+    const void *Q[2], *S[2], *QM2[2];
+    const float* row_weight;                          // [R] or null (single form only)
+    void* dX;
+};
+// the slab form (inst_grouped_input_grad_b*.hip, one unit per bit width) and the block form for experts with many rows (one workgroup
+// per 128-row block of an expert x 256 k; what it serves: grouped_input_grad_blocks_eligible; inst_grouped_input_grad_blocks_b*.hip):
+// same operands, same bits; either grid follows from the shapes alone
+int qgemm_grouped_input_grad_unit_b4(const GroupedInputGrad& g, hipStream_t stream);
+int qgemm_grouped_input_grad_unit_b3(const GroupedInputGrad& g, hipStream_t stream);
+int qgemm_grouped_input_grad_unit_b2(const GroupedInputGrad& g, hipStream_t stream);
+int qgemm_grouped_input_grad_blocks_unit_b4(const GroupedInputGrad& g, hipStream_t stream);
+int qgemm_grouped_input_grad_blocks_unit_b2(const GroupedInputGrad& g, hipStream_t stream);
+inline int qgemm_grouped_input_grad_dispatch(const GroupedInputGrad& g, hipStream_t stream) {
+    if (g.form == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS)
+        return g.num_bits == 4 ? qgemm_grouped_input_grad_blocks_unit_b4(g, stream) : qgemm_grouped_input_grad_blocks_unit_b2(g, stream);
+    if (g.num_bits == 4) return qgemm_grouped_input_grad_unit_b4(g, stream);
+    return g.num_bits == 3 ? qgemm_grouped_input_grad_unit_b3(g, stream) : qgemm_grouped_input_grad_unit_b2(g, stream);
+}
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

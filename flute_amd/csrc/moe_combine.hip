@@ -10,7 +10,7 @@
 // slots are taken four at a time so that four independent loads are in flight before the first addition; a slot that
 // is skipped adds +0, which leaves an accumulator that started at +0 unchanged bit for bit (it is never -0).
 #include "kernels.h"
-#include "../../include/flute_amd.h"
+#include "grouped_rows.h"
 
 namespace flute_amd {
 
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(kCombineThreads) void moe_combine_kernel(const uint
     const int t = blockIdx.x / col_blocks;
     const int col = 8 * ((blockIdx.x - t * col_blocks) * kCombineThreads + threadIdx.x);
     if (col >= N) return;
-    const int served = min(max(offsets[E], 0), P);
+    const int served = grouped_served(offsets, E, P);
     const int32_t* __restrict__ slot = pos + (size_t)t * k;
     float acc[8];
 #pragma unroll

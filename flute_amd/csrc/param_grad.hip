@@ -16,9 +16,8 @@
 // (scale_grad_splits, the same split with or without a dT2): each split writes its dS as fp32 partials [split][N][K / g]
 // to the scratch and splitk_reduce_kernel sums them in split order and rounds once.
 //
-// Grouped: Q, S, QM2, dS and dT2 carry a leading [E]; expert e's row range is [b_e, e_e), b_e = clamp(offsets[e], 0, R),
-// e_e = clamp(offsets[e + 1], 0, R), offsets [E + 1] int32 in device memory and read by the kernels only; row_weight [R]
-// fp32 or null.  The grid is (N / 128, ceil(K / 256), E), from the shapes alone: a workgroup walks ALL rows of its expert
+// Grouped: Q, S, QM2, dS and dT2 carry a leading [E]; expert e's row range is [b_e, e_e), clamped to [0, R] (grouped_rows.h:
+// offsets [E + 1] int32 in device memory and read by the kernels only); row_weight [R] fp32 or null.  The grid is (N / 128, ceil(K / 256), E), from the shapes alone: a workgroup walks ALL rows of its expert
 // in the dense kernel's order, so an expert's dS and dT2 have the dense launch's bits on its rows wherever that launch does
 // not split M.  Memory safety: every row index formed is in [b_e, e_e) inside [0, R) - a malformed table is safe, rows
 // from clamp(offsets[E]) on are never read - and nothing of an expert without rows is read: its workgroups write their
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(kTgRedBins* kTgRedSlots) void table_grad_reduce_ker
     const int bin = blockIdx.x * kTgRedBins + b;      // nbins is a multiple of 32
     const int e = (int)blockIdx.y;
     float* __restrict__ out = dT2 + (size_t)e * nbins;
-    if (offsets && min(max(offsets[e + 1], 0), R) <= min(max(offsets[e], 0), R)) {   // uniform over the workgroup
+    if (offsets && grouped_rows(offsets, e, R).empty()) {                            // uniform over the workgroup
         if (slot == 0) out[bin] = 0.f;
         return;
     }

@@ -27,6 +27,7 @@
 #include <utility>
 
 #include "common.h"
+#include "grouped_rows.h"
 #include "mfma.h"
 #include "qgemm_stream.h"      // srd_t, make_srd, buf_load16, hidden LDS lookups
 
@@ -46,47 +47,15 @@ struct BlockArgs {
     int order;              // 0: M tiles fastest; 1: XCD x owns a contiguous range of M tiles; 2: of N tiles
 };
 
-// The grouped front end of qgemm_block2.h (GM != 0; host side: qgemm_grouped_blocks.h): E stacked layers, the rows of expert e
-// are [offsets[e], offsets[e + 1]) of A / D.  M is the row count T the table is clamped to, Q / S / QM2 point at expert 0,
-// tiles_m is the host's bound on the row blocks, floor((T + 127 E) / 128); splitk = 1, k_per_split = K.
+// The grouped front end of qgemm_block2.h (GM != 0; host side: qgemm_grouped_blocks.h; the row map and its rules: grouped_rows.h):
+// E stacked layers over the rows of A / D.  M is the row count T the table is clamped to, Q / S / QM2 point at expert 0,
+// tiles_m is the host's bound on the row blocks, grouped_blocks_row_blocks(E, T); splitk = 1, k_per_split = K.
 // order 0: the row block is the fast index of blockIdx, 1: the column block.
 struct GroupedBlockArgs : BlockArgs {
     const int* offsets;         // [E + 1], device memory, read by the kernel only
     const float* row_weight;    // [T] (weighted mode)
     int E, P;                   // P: unit rows of one expert's Q
 };
-
-constexpr int kGroupedBlockRows = 128;
-
-// Row blocks of a launch: the most a monotone table over T rows and E experts can own, floor((T + 127 E) / 128) - an expert
-// with r rows owns ceil(r / 128) <= (r + 127) / 128 blocks, and the sum of integers is at most the floor of the sum.
-inline long long grouped_blocks_row_blocks(int E, int T) {
-    return ((long long)T + (long long)(kGroupedBlockRows - 1) * E) / kGroupedBlockRows;
-}
-
-// What the block form serves (api.hip's form rule and refusal read this, nothing else decides it): plain (0) and weighted (2),
-// 4 / 2 bits, scale rows in whole 8-group blocks, whole 256-column blocks, and the 32-bit descriptor limits of choose_block -
-// activation byte offsets (a block reaches up to 127 rows past its expert's end), one expert's scale bytes - and a 31-bit grid.
-inline bool grouped_blocks_eligible(int mode, int num_bits, int lg, int E, int T, int N, int K) {
-    if (mode != 0 && mode != 2) return false;
-    if (num_bits != 4 && num_bits != 2) return false;
-    if (E < 1 || T < 1 || N < 256 || N % 256 || K < 64 || (K >> lg) % 8) return false;
-    if ((size_t)(T + 256) * K * 2 >= (size_t)0xfffffff0u) return false;
-    if ((size_t)N * (K >> lg) * 2 >= (size_t)0xfffffff0u) return false;
-    return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
-}
-
-// What the block form of the grouped input gradient serves (qgemm_grouped_input_grad_blocks.h; api.hip's form rule and refusal
-// read this, nothing else decides it): 4 / 2 bits, whole 256-k blocks, a row index plus a block that stays an int, and a 31-bit
-// grid.  (N, TileP and the group size are the slab form's, which the caller has checked with the layer; every base in the kernel
-// is 64-bit and it builds no descriptor, so no operand size is refused.)
-constexpr int kGroupedIgBlockK = 256;
-inline bool grouped_input_grad_blocks_eligible(int num_bits, int E, int R, int N, int K) {
-    if (num_bits != 4 && num_bits != 2) return false;
-    if (E < 1 || R < 1 || N < 64 || N % 64 || K < kGroupedIgBlockK || K % kGroupedIgBlockK) return false;
-    if (R > 0x7fffffff - 2 * kGroupedBlockRows) return false;
-    return grouped_blocks_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
-}
 
 constexpr int BLK_STAGES = 3;
 

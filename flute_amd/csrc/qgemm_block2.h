@@ -32,18 +32,12 @@ namespace flute_amd {
 //
 // GM != 0: the grouped front end for mixture-of-experts stacks with many rows per expert (GM = 1: plain, 2: weighted; the arithmetic and
 // the modes are qgemm_grouped.h's, which keeps the experts with few rows; 128-row blocks only).  The main loop is the one below, untouched:
-// what changes is where a workgroup's operands come from and which rows it stores.  A workgroup is (column block, row block b); b counts the
-// 128-row blocks of all experts in expert order, expert e owning ceil(max(re - rb, 0) / 128) of them with rb = clamp(offsets[e], 0, T) and
-// re = clamp(offsets[e + 1], 0, T).  Every wave finds (e, block j of e) for itself at the top of the kernel - 64 experts per round, one
-// per lane, an inclusive prefix sum over the lanes and a ballot; the answer is wave-uniform, so the eight waves agree without LDS and
-// without a barrier ahead of the first request.  The grid holds floor((T + 127 E) / 128) row blocks, the most a monotone table can own
-// (each expert wastes at most 127 rows of its last block), from T and E alone: the host never reads the table.  A workgroup whose b is
-// past the table's total returns before it requests a weight, scale or table word; an expert without rows owns no block.
+// what changes is where a workgroup's operands come from and which rows it stores.  A workgroup is (column block, row block b) with b
+// mapped to (expert e, block of e, rows [rb, re)) by grouped_rows.h's block map, which also states what a malformed table can do; a
+// workgroup whose b is past the table's blocks returns before it requests a weight, scale or table word.
 // (The order of b against the column block is the host's: GroupedBlockArgs::order, measured in qgemm_grouped_blocks.h.)
 // The activation descriptor starts at row rb and is (re - rb) rows long, so the rows of the block at or past re read as zero by the
 // same out-of-range idiom as the dense rows past M, and no row outside [rb, re) forms an address; the epilogue stores rows < re.
-// A malformed table (decreasing or overlapping ranges) stays inside X / Y because every bound is clamped; it may own more blocks
-// than the grid holds or the same row twice: rows are then left unwritten or hold either expert's result.
 template <typename T, int TILEP, int RT = 16, int BITS = 4, int GM = 0>
 __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs> args) {
     using NT = Num<T>;
@@ -96,48 +90,17 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
     int tm_idx, tn_idx;
     int row_lo = 0, row_hi = 0;                                    // grouped: the expert's rows [rb, re)
     if constexpr (GM != 0) {
-        if constexpr (GM == 2) {
-            // rows no expert serves, [clamp(offsets[E]), T): zeros, 8 bytes per lane, spread over the whole grid
-            const int zb = min(max(a.offsets[a.E], 0), a.M);
-            const size_t n4 = (size_t)(a.M - zb) * (size_t)(a.N >> 2);
-            ushort4* z = reinterpret_cast<ushort4*>(reinterpret_cast<uint16_t*>(a.D) + (size_t)zb * a.N);
-            for (size_t i = (size_t)blockIdx.x * (NW * 64) + tid; i < n4; i += (size_t)gridDim.x * (NW * 64))
-                z[i] = ushort4{0, 0, 0, 0};
-        }
+        static_assert(BM == kGroupedBlockRows, "the host's grid counts these blocks");
+        if constexpr (GM == 2) grouped_zero_unserved<NW * 64>(reinterpret_cast<uint16_t*>(a.D), a.offsets, a.E, a.M, a.N);
         int b;
         if (a.order == 1) { tn_idx = bid % a.tiles_n; b = bid / a.tiles_n; }
         else { b = bid % a.tiles_m; tn_idx = bid / a.tiles_m; }
-        int e = -1, j = 0, base = 0;
-        for (int c0 = 0; c0 < a.E; c0 += 64) {
-            const int ee = c0 + lane;
-            int lo = 0, hi = 0;
-            if (ee < a.E) {
-                lo = min(max(a.offsets[ee], 0), a.M);
-                hi = min(max(a.offsets[ee + 1], 0), a.M);
-            }
-            const int nb = (max(hi - lo, 0) + BM - 1) / BM;        // blocks of expert ee
-            int incl = nb;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            const unsigned long long hit = __ballot(base + incl > b);
-            if (hit) {                                             // the first lane whose running total passes b: its nb > 0
-                const int src = __ffsll(hit) - 1;
-                e = c0 + src;
-                j = b - (base + __shfl(incl - nb, src));
-                row_lo = __shfl(lo, src);
-                row_hi = __shfl(hi, src);
-                break;
-            }
-            base += __shfl(incl, 63);
-        }
-        e = __builtin_amdgcn_readfirstlane(e);
+        const GroupedBlock gb = grouped_block_map<BM>(a.offsets, a.E, a.M, b);
+        const int e = gb.e;
         if (e < 0) return;                                         // b is past the table's blocks: nothing is requested
-        tm_idx = __builtin_amdgcn_readfirstlane(j);
-        row_lo = __builtin_amdgcn_readfirstlane(row_lo);
-        row_hi = __builtin_amdgcn_readfirstlane(row_hi);
+        tm_idx = gb.blk;
+        row_lo = gb.rb;
+        row_hi = gb.re;
         a.Q += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);
         a.S = reinterpret_cast<const uint16_t*>(a.S) + (size_t)e * (size_t)a.N * (size_t)a.G;
         a.QM2 += (size_t)e << (2 * BITS);

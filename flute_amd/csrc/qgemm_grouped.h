@@ -43,12 +43,10 @@
 // The host picks spw in {1, 2, 4} as the largest that still leaves eight workgroups per CU; it and the grid follow from
 // (E, N, num_bits, num_sms) alone, as include/flute_amd.h says (grouped_grid() below, the only place they are computed).
 //
-// Rows.  rb = clamp(offsets[e]), re = clamp(offsets[e + 1]) to [0, R]; a workgroup with re <= rb returns before it requests
-// a weight, scale or table word.  The expert's rows are taken in passes of RT 16-row tiles (RT = 2; 3 bits: 1 - the
-// accumulators, J x RT x 4 fp32, and two blocks of operands stay in registers, no scratch), the weights streamed once per
-// pass; a tile of a pass that holds no row issues neither loads nor MFMAs (the K loop is compiled per tile count), rows
-// past `re` inside a tile are fed as zeros and never stored.  Every row index the kernel forms is < re <= R, so a
-// malformed table cannot reach outside X / Y.
+// Rows.  [rb, re) of the expert and the contract on a malformed table: grouped_rows.h.  The expert's rows are taken in
+// passes of RT 16-row tiles (RT = 2; 3 bits: 1 - the accumulators, J x RT x 4 fp32, and two blocks of operands stay in
+// registers, no scratch), the weights streamed once per pass; a tile of a pass that holds no row issues neither loads nor
+// MFMAs (the K loop is compiled per tile count), rows past `re` inside a tile are fed as zeros and never stored.
 //
 // Glu.  A workgroup serves slab s of the gate stack and slab s of the up stack for the same rows: the K loop and the
 // reduction run for the gate slab, waves 0 .. TR - 1 keep their reduced tiles in registers (NI / TR float4 per lane: 2 at
@@ -61,6 +59,7 @@
 // experts pass 2 GiB of codes at E = 64).
 #pragma once
 #include "kernels.h"
+#include "grouped_rows.h"
 #include "mfma.h"
 #include <type_traits>
 #include "layout_dispatch.h"
@@ -98,21 +97,20 @@ struct GroupedArgs {
     int R, Tsrc, N, K, P, lg, runs, spw, E;
 };
 
-// The arguments of a launch from the untyped pointers of the *_dispatch functions; one stack fills both slots, runs / spw
-// are the launch's to set.
-inline GroupedArgs grouped_args(const void* X, const void* rows, const void* offsets, const void* Q0, const void* S0,
-                                const void* QM20, const void* Q1, const void* S1, const void* QM21, const void* row_weight,
-                                void* Y, int R, int Tsrc, int N, int K, int P, int lg, int E) {
+// The kernel's arguments from the launch's named operands; runs / spw are the launch's to set.
+inline GroupedArgs grouped_args(const GroupedForward& g) {
     GroupedArgs a{};
-    a.X = reinterpret_cast<const uint16_t*>(X);
-    a.rows = reinterpret_cast<const int*>(rows);
-    a.offsets = reinterpret_cast<const int*>(offsets);
-    a.Q[0] = reinterpret_cast<const uint32_t*>(Q0); a.Q[1] = reinterpret_cast<const uint32_t*>(Q1);
-    a.S[0] = reinterpret_cast<const uint16_t*>(S0); a.S[1] = reinterpret_cast<const uint16_t*>(S1);
-    a.QM2[0] = reinterpret_cast<const uint32_t*>(QM20); a.QM2[1] = reinterpret_cast<const uint32_t*>(QM21);
-    a.row_weight = reinterpret_cast<const float*>(row_weight);
-    a.Y = reinterpret_cast<uint16_t*>(Y);
-    a.R = R; a.Tsrc = Tsrc; a.N = N; a.K = K; a.P = P; a.lg = lg; a.E = E;
+    a.X = reinterpret_cast<const uint16_t*>(g.X);
+    a.rows = reinterpret_cast<const int*>(g.rows);
+    a.offsets = reinterpret_cast<const int*>(g.offsets);
+    for (int s = 0; s < 2; ++s) {
+        a.Q[s] = reinterpret_cast<const uint32_t*>(g.Q[s]);
+        a.S[s] = reinterpret_cast<const uint16_t*>(g.S[s]);
+        a.QM2[s] = reinterpret_cast<const uint32_t*>(g.QM2[s]);
+    }
+    a.row_weight = g.row_weight;
+    a.Y = reinterpret_cast<uint16_t*>(g.Y);
+    a.R = g.R; a.Tsrc = g.Tsrc; a.N = g.N; a.K = g.K; a.P = g.P; a.lg = g.lg; a.E = g.E;
     return a;
 }
 
@@ -141,20 +139,13 @@ __global__ __launch_bounds__(kGroupedThreads) void qgemm_grouped_kernel(const Gr
     const int R = a.R, N = a.N, K = a.K, lg = a.lg;
     uint16_t* __restrict__ Y = a.Y;
 
-    if constexpr (MODE == GroupedMode::Weighted) {
-        // rows no expert serves, [clamp(offsets[E]), R): zeros, 8 bytes per lane, spread over the whole grid
-        const int zb = min(max(a.offsets[a.E], 0), R);
-        const size_t n4 = (size_t)(R - zb) * (size_t)(N >> 2);
-        ushort4* z = reinterpret_cast<ushort4*>(Y + (size_t)zb * N);
-        for (size_t i = (size_t)blockIdx.x * kGroupedThreads + tid; i < n4; i += (size_t)gridDim.x * kGroupedThreads)
-            z[i] = ushort4{0, 0, 0, 0};
-    }
+    if constexpr (MODE == GroupedMode::Weighted) grouped_zero_unserved<kGroupedThreads>(Y, a.offsets, a.E, R, N);
 
     const int e = (int)blockIdx.x / a.runs;
     const int run = (int)blockIdx.x - e * a.runs;
-    const int rb = min(max(a.offsets[e], 0), R);
-    const int re = min(max(a.offsets[e + 1], 0), R);
-    if (re <= rb) return;                                          // no rows: nothing of this expert is requested
+    const GroupedRows er = grouped_rows(a.offsets, e, R);
+    if (er.empty()) return;                                        // no rows: nothing of this expert is requested
+    const int rb = er.rb, re = er.re;
 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -358,11 +349,12 @@ inline bool grouped_grid(int E, int N, int num_bits, int num_sms, int* spw_out, 
 // The launch of every form: the 18 instantiations of a mode (4 bits: TileP 32 / 64; 2 bits: TileP 32 / 64 x group size
 // 32 / 64 / >= 128; 3 bits: TileP 32; each in f16 and bf16).
 template <GroupedMode MODE>
-int qgemm_grouped_launch(int dtype, int num_bits, int tile_p, GroupedArgs a, int num_sms, hipStream_t stream) {
+int qgemm_grouped_launch(const GroupedForward& g, hipStream_t stream) {
+    GroupedArgs a = grouped_args(g);
     unsigned grid;
-    if (!grouped_grid(a.E, a.N, num_bits, num_sms, &a.spw, &a.runs, &grid)) return FLUTE_ERR_SHAPE;
+    if (!grouped_grid(a.E, a.N, g.num_bits, g.num_sms, &a.spw, &a.runs, &grid)) return FLUTE_ERR_SHAPE;
     const int lg = a.lg;
-    const int err = dispatch_layout(dtype, num_bits, tile_p, [&](auto t, auto bits, auto tp) {
+    const int err = dispatch_layout(g.dtype, g.num_bits, g.tile_p, [&](auto t, auto bits, auto tp) {
         constexpr int B = decltype(bits)::value;
         auto launch = [&](auto lgc) {
             hipLaunchKernelGGL((qgemm_grouped_kernel<decltype(t), B, decltype(tp)::value, decltype(lgc)::value, MODE>),

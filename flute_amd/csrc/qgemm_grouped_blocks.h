@@ -19,18 +19,18 @@ namespace flute_amd {
 
 // One launch: GM = 1 plain, 2 weighted.  The grid follows from (E, T, N) alone.
 template <int BITS, int GM>
-int qgemm_grouped_blocks_launch(int dtype, int tile_p, int lg, int E, int T, int N, int K, int P, const void* X,
-                                const void* offsets, const void* Q, const void* S, const void* QM2, const void* row_weight,
-                                void* Y, hipStream_t stream) {
+int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    const int dtype = g.dtype, tile_p = g.tile_p;
     GroupedBlockArgs a{};
-    a.A = X; a.Q = reinterpret_cast<const uint32_t*>(Q); a.D = Y; a.S = S; a.QM2 = reinterpret_cast<const uint32_t*>(QM2);
-    a.M = T; a.N = N; a.K = K; a.G = K >> lg; a.lg = lg;
-    a.tiles_m = (int)grouped_blocks_row_blocks(E, T); a.tiles_n = N / 256;
-    a.splitk = 1; a.k_per_split = K;
+    a.A = g.X; a.Q = reinterpret_cast<const uint32_t*>(g.Q[0]); a.D = g.Y; a.S = g.S[0];
+    a.QM2 = reinterpret_cast<const uint32_t*>(g.QM2[0]);
+    a.M = g.R; a.N = g.N; a.K = g.K; a.G = g.K >> g.lg; a.lg = g.lg;
+    a.tiles_m = (int)grouped_blocks_row_blocks(g.E, g.R); a.tiles_n = g.N / 256;
+    a.splitk = 1; a.k_per_split = g.K;
     a.order = FLUTE_GROUPED_BLOCKS_ORDER;
-    a.offsets = reinterpret_cast<const int*>(offsets);
-    a.row_weight = reinterpret_cast<const float*>(row_weight);
-    a.E = E; a.P = P;
+    a.offsets = reinterpret_cast<const int*>(g.offsets);
+    a.row_weight = GM == 2 ? g.row_weight : nullptr;
+    a.E = g.E; a.P = g.P;
     typedef void (*Kernel)(const GroupedBlockArgs);
     Kernel k = nullptr;
     if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, GM>;

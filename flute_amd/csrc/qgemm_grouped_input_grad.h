@@ -37,11 +37,11 @@
 // and a wave reaches the writes of chunk c + 1 only behind the barrier of chunk c, which every wave passes after its reads
 // of chunk c - 1.  The packed words, scales and dY of chunk c + 1 are requested before the MFMAs of chunk c.
 //
-// Rows.  rb = clamp(offsets[e]), re = clamp(offsets[e + 1]) to [0, R]; a workgroup with re <= rb returns before it
-// requests a weight, scale or table word.  Every row index formed is < re <= R: a malformed table cannot reach outside
-// dY / dX.  Expert bases into Q / S / QM2 and row bases into dY / dX are 64-bit.
+// Rows.  [rb, re) of the expert, the zero fill and the contract on a malformed table: grouped_rows.h.  Expert bases into
+// Q / S / QM2 and row bases into dY / dX are 64-bit.
 #pragma once
 #include "kernels.h"
+#include "grouped_rows.h"
 #include "mfma.h"
 #include "grad_gemm.h"
 #include "layout_dispatch.h"
@@ -86,15 +86,83 @@ __device__ __forceinline__ uint32_t field_rt(uint32_t w0, uint32_t w1, uint32_t 
     }
 }
 
+// ---- what the slab form below and the block form (qgemm_grouped_input_grad_blocks.h) share
+
+// copies of an expert's pair table in LDS, so that the lanes of a lookup spread over the banks: 8 / 32 / 32 at 4 / 3 / 2 bits
+template <int BITS>
+constexpr int kIgLutCopies = (kIgLutWords / Layout<BITS>::LUT_N) > 32 ? 32 : (kIgLutWords / Layout<BITS>::LUT_N);
+
+// The table images of expert e, by the whole workgroup: stack s at lut + s * stride, entry i of copy c at word i * C + c.
+template <int BITS, int NSTK>
+__device__ __forceinline__ void ig_load_tables(uint32_t* lut, int stride, const GroupedIgArgs& a, int e) {
+    using L = Layout<BITS>;
+    constexpr int C = kIgLutCopies<BITS>;
+#pragma unroll
+    for (int s = 0; s < NSTK; ++s) {
+        const uint32_t* __restrict__ Te = a.QM2[s] + (size_t)e * L::LUT_N;
+        for (int i = threadIdx.x; i < L::LUT_N * C; i += kIgThreads) lut[s * stride + i] = Te[i / C];
+    }
+    __syncthreads();
+}
+
+// The decode of one k-octet of unit ul of a chunk, fields 2 jp and 2 jp + 1: from the unit's plane words w (8 consecutive k)
+// and the two columns' scale words s, through the lane's copy lt of the stack's table image, 16 B to each of the tile rows
+// (2 jp + f) * UC + ul at dst (the octet's place in tile row 0).  `in` false: the octet lies past K and zeros are written.
+template <typename T, int BITS, int PITCH>
+__device__ __forceinline__ void ig_decode_octet(const u32x4_t (&w)[Layout<BITS>::NPLANES], const uint32_t (&s)[2],
+                                                const uint32_t* lt, int jp, int ul, bool in, char* dst) {
+    constexpr int NP = Layout<BITS>::NPLANES;
+    constexpr int UC = kIgNC / Layout<BITS>::J;
+    constexpr int C = kIgLutCopies<BITS>;
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+        const int j = 2 * jp + f;
+        uint32_t out[4] = {0, 0, 0, 0};
+        if (in) {
+            uint32_t v[4];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) v[d] = lt[field_rt<BITS>(w[0][d], w[NP > 1 ? 1 : 0][d], w[NP > 1 ? 2 : 0][d], j) * C];
+            Num<T>::mul_scale4(v, s[f], out);
+        }
+        *reinterpret_cast<uint4*>(dst + (j * UC + ul) * PITCH) = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+}
+
+// One A fragment: the two transposed reads of a 32-n step at byte `off` from the lane's addresses of step 0, k tile 0.
+__device__ __forceinline__ u32x4_t ig_a_fragment(const uint32_t (&a_addr)[2], uint32_t off) {
+    const uint2 a0 = lds_tr16(a_addr[0] + off);
+    const uint2 a1 = lds_tr16(a_addr[1] + off);
+    return u32x4_t{a0.x, a0.y, a1.x, a1.y};
+}
+
+// The epilogue of row tile t of a lane: its row `row` (< re) of dX at k0 + 16 kt .. + 3 for the four k tiles - the optional
+// row weight (single form), one rounding, one 8-byte store per k tile.
+template <typename T, bool PAIR, int RTILES>
+__device__ __forceinline__ void ig_store_row(const GroupedIgArgs& a, const f32x4_t (&acc)[4][RTILES], int t, int row, int k0) {
+    float w = 1.0f;
+    if constexpr (!PAIR) {
+        if (a.row_weight) w = a.row_weight[row];
+    }
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+        f32x4_t s = acc[kt][t];
+        if constexpr (!PAIR) {
+            if (a.row_weight) { s[0] *= w; s[1] *= w; s[2] *= w; s[3] *= w; }
+        }
+        ushort4 v;
+        v.x = Num<T>::from_float(s[0]); v.y = Num<T>::from_float(s[1]); v.z = Num<T>::from_float(s[2]); v.w = Num<T>::from_float(s[3]);
+        *reinterpret_cast<ushort4*>(a.dX + (size_t)row * a.K + k0 + kt * 16) = v;
+    }
+}
+
 template <typename T, int BITS, int TILEP, bool PAIR>
 __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(const GroupedIgArgs a) {
     using L = Layout<BITS>;
-    using NT = Num<T>;
     constexpr int J = L::J;
     constexpr int NP = L::NPLANES;
     constexpr int UC = kIgNC / J;                                  // units per chunk: 16 / 8 / 4
     constexpr int NSTK = PAIR ? 2 : 1;
-    constexpr int C = (kIgLutWords / L::LUT_N) > 32 ? 32 : (kIgLutWords / L::LUT_N);      // table copies: 8 / 32 / 32
+    constexpr int C = kIgLutCopies<BITS>;
     static_assert(UC >= 4 && UC % 4 == 0 && TILEP % UC == 0 && UC * 16 * (J / 2) == kIgThreads, "chunk shape");
 
     __shared__ __attribute__((aligned(16))) char tile[2 * kIgTile];
@@ -102,21 +170,14 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(co
 
     const int tid = threadIdx.x;
     const int R = a.R, N = a.N, K = a.K, lg = a.lg;
-    uint16_t* __restrict__ dX = a.dX;
 
-    {   // rows no expert serves, [clamp(offsets[E]), R): zeros, 8 bytes per lane, spread over the whole grid
-        const int zb = min(max(a.offsets[a.E], 0), R);
-        const size_t n4 = (size_t)(R - zb) * (size_t)(K >> 2);
-        ushort4* z = reinterpret_cast<ushort4*>(dX + (size_t)zb * K);
-        for (size_t i = (size_t)blockIdx.x * kIgThreads + tid; i < n4; i += (size_t)gridDim.x * kIgThreads)
-            z[i] = ushort4{0, 0, 0, 0};
-    }
+    grouped_zero_unserved<kIgThreads>(a.dX, a.offsets, a.E, R, K);
 
     const int e = (int)blockIdx.x / a.slabs;
     const int slab = (int)blockIdx.x - e * a.slabs;
-    const int rb = min(max(a.offsets[e], 0), R);
-    const int re = min(max(a.offsets[e + 1], 0), R);
-    if (re <= rb) return;                                          // no rows: nothing of this expert is requested
+    const GroupedRows er = grouped_rows(a.offsets, e, R);
+    if (er.empty()) return;                                        // no rows: nothing of this expert is requested
+    const int rb = er.rb, re = er.re;
 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -127,13 +188,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(co
     const size_t q_base = (size_t)e * (size_t)a.P * (size_t)K2;
     const size_t s_base = (size_t)e * (size_t)N * (size_t)G;
 
-    // table images: entry i of copy c at word i * C + c
-#pragma unroll
-    for (int s = 0; s < NSTK; ++s) {
-        const uint32_t* __restrict__ Te = a.QM2[s] + (size_t)e * L::LUT_N;
-        for (int i = tid; i < L::LUT_N * C; i += kIgThreads) lut[s][i] = Te[i / C];
-    }
-    __syncthreads();
+    ig_load_tables<BITS, NSTK>(&lut[0][0], L::LUT_N * C, a, e);
 
     // ---- the lane as a decoder: unit ul of the chunk, k-octet o of the slab, fields 2 jp and 2 jp + 1
     const int o = tid & 15;
@@ -162,22 +217,8 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(co
         for (int f = 0; f < 2; ++f) pk.s[f] = in ? (uint32_t)Ss[(size_t)(n0 + (2 * jp + f) * TILEP) * G] : 0u;
     };
     auto decode = [&](const Packed& pk, int cc) {
-        char* dst = tile + (cc & 1) * kIgTile + o * 16;
-        const uint32_t* lt = lut[PAIR ? (cc >= NCH) : 0] + lut_lane;
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            const int j = 2 * jp + f;
-            uint32_t out[4] = {0, 0, 0, 0};
-            if (k_in) {
-                uint32_t v[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    v[d] = lt[field_rt<BITS>(pk.w[0][d], pk.w[NP > 1 ? 1 : 0][d], pk.w[NP > 1 ? 2 : 0][d], j) * C];
-                }
-                NT::mul_scale4(v, pk.s[f], out);
-            }
-            *reinterpret_cast<uint4*>(dst + (j * UC + ul) * kIgPitch) = make_uint4(out[0], out[1], out[2], out[3]);
-        }
+        ig_decode_octet<T, BITS, kIgPitch>(pk.w, pk.s, lut[PAIR ? (cc >= NCH) : 0] + lut_lane, jp, ul, k_in,
+                                           tile + (cc & 1) * kIgTile + o * 16);
     };
 
     // ---- the lane in the MFMAs: rows 32 rg .. + 31 of the row block, k 64 kh .. + 63 of the slab
@@ -250,11 +291,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(co
                 for (int s = 0; s < 2; ++s) {
                     u32x4_t af[4];
 #pragma unroll
-                    for (int kt = 0; kt < 4; ++kt) {
-                        const uint2 a0 = lds_tr16(a_addr[0] + buf + s * 32 * kIgPitch + kt * 32);
-                        const uint2 a1 = lds_tr16(a_addr[1] + buf + s * 32 * kIgPitch + kt * 32);
-                        af[kt] = u32x4_t{a0.x, a0.y, a1.x, a1.y};
-                    }
+                    for (int kt = 0; kt < 4; ++kt) af[kt] = ig_a_fragment(a_addr, buf + s * 32 * kIgPitch + kt * 32);
 #pragma unroll
                     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -268,66 +305,65 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_kernel(co
         // lane (q = h, r = r16) of tile (kt, t): row row0 + 32 rg + 16 t + r, k = slab 128 + 64 kh + 16 kt + 4 q .. + 3
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const int row = row0 + 32 * rg + 16 * t + r16;
-            if (yok[t]) {
-                float w = 1.0f;
-                if constexpr (!PAIR) {
-                    if (a.row_weight) w = a.row_weight[row];
-                }
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    const int k = slab * kIgKS + kh * 64 + kt * 16 + 4 * h;       // < K: k_half_in and K % 64 == 0
-                    f32x4_t s = acc[kt][t];
-                    if constexpr (!PAIR) {
-                        if (a.row_weight) { s[0] *= w; s[1] *= w; s[2] *= w; s[3] *= w; }
-                    }
-                    ushort4 v;
-                    v.x = NT::from_float(s[0]); v.y = NT::from_float(s[1]); v.z = NT::from_float(s[2]); v.w = NT::from_float(s[3]);
-                    *reinterpret_cast<ushort4*>(dX + (size_t)row * K + k) = v;
-                }
-            }
+            // (k < K: k_half_in and K % 64 == 0)
+            if (yok[t]) ig_store_row<T, PAIR>(a, acc, t, row0 + 32 * rg + 16 * t + r16, slab * kIgKS + kh * 64 + 4 * h);
         }
         __syncthreads();                                           // the next row block's first chunk reuses buffer 0
     }
 }
 
-// The arguments of a launch from the untyped pointers of the *_dispatch functions; the single form fills both slots with
-// its one stack.
-inline GroupedIgArgs grouped_ig_args(const void* dY, const void* offsets, const void* Q, const void* S, const void* QM2,
-                                     const void* row_weight, const void* dY2, const void* Q2, const void* S2,
-                                     const void* QM22, void* dX, int R, int N, int K, int P, int lg, int E) {
-    const bool pair = dY2 != nullptr;
+// The kernel's arguments from the launch's named operands; slabs is the launch's to set.
+inline GroupedIgArgs grouped_ig_args(const GroupedInputGrad& g) {
     GroupedIgArgs a{};
-    a.dY[0] = reinterpret_cast<const uint16_t*>(dY); a.dY[1] = reinterpret_cast<const uint16_t*>(pair ? dY2 : dY);
-    a.offsets = reinterpret_cast<const int*>(offsets);
-    a.Q[0] = reinterpret_cast<const uint32_t*>(Q); a.Q[1] = reinterpret_cast<const uint32_t*>(pair ? Q2 : Q);
-    a.S[0] = reinterpret_cast<const uint16_t*>(S); a.S[1] = reinterpret_cast<const uint16_t*>(pair ? S2 : S);
-    a.QM2[0] = reinterpret_cast<const uint32_t*>(QM2); a.QM2[1] = reinterpret_cast<const uint32_t*>(pair ? QM22 : QM2);
-    a.row_weight = reinterpret_cast<const float*>(row_weight);
-    a.dX = reinterpret_cast<uint16_t*>(dX);
-    a.R = R; a.N = N; a.K = K; a.P = P; a.lg = lg; a.E = E;
+    for (int s = 0; s < 2; ++s) {
+        a.dY[s] = reinterpret_cast<const uint16_t*>(g.dY[s]);
+        a.Q[s] = reinterpret_cast<const uint32_t*>(g.Q[s]);
+        a.S[s] = reinterpret_cast<const uint16_t*>(g.S[s]);
+        a.QM2[s] = reinterpret_cast<const uint32_t*>(g.QM2[s]);
+    }
+    a.offsets = reinterpret_cast<const int*>(g.offsets);
+    a.row_weight = g.row_weight;
+    a.dX = reinterpret_cast<uint16_t*>(g.dX);
+    a.R = g.R; a.N = g.N; a.K = g.K; a.P = g.P; a.lg = g.lg; a.E = g.E;
     return a;
 }
 
-// The launch of one bit width (inst_grouped_input_grad_b*.hip): TileP 32 / 64 (3 bits: 32) x f16 / bf16 x single / pair.
-// The grid is E x ceil(K / 128), from the shapes alone.
-template <int BITS>
-int qgemm_grouped_input_grad_launch(int dtype, int tile_p, bool pair, GroupedIgArgs a, hipStream_t stream) {
-    a.slabs = (a.K + kIgKS - 1) / kIgKS;
-    if ((long long)a.E * a.slabs > 0x7fffffffLL) return FLUTE_ERR_SHAPE;
-    const unsigned grid = (unsigned)((long long)a.E * a.slabs);
-    const int err = dispatch_layout(dtype, BITS, tile_p, [&](auto t, auto bits, auto tp) {
+// The launch of either form for one bit width: kernel(T{}, int_c<TILEP>{}, pair as a type) names the instantiation - TileP
+// 32 / 64 (3 bits: 32) x f16 / bf16 x single / pair -, lds its dynamic LDS (0: none; above 64 KB it has to be asked for - the
+// attribute is per device and setting it is no stream operation: asked for at every launch, as moe_route.hip does).
+template <int BITS, typename Kernel>
+int grouped_ig_launch(const GroupedInputGrad& g, Kernel kernel, unsigned grid, int lds, const GroupedIgArgs& a, hipStream_t stream) {
+    int rc = FLUTE_OK;
+    const int err = dispatch_layout(g.dtype, BITS, g.tile_p, [&](auto t, auto bits, auto tp) {
         if constexpr (decltype(bits)::value == BITS) {  // the other widths live in their own units
             auto launch = [&](auto pr) {
-                hipLaunchKernelGGL((qgemm_grouped_input_grad_kernel<decltype(t), BITS, decltype(tp)::value, decltype(pr)::value>),
-                                   dim3(grid), dim3(kIgThreads), 0, stream, a);
+                auto k = kernel(t, tp, pr);
+                if (lds > 0 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+                    (void)hipGetLastError();
+                    rc = FLUTE_ERR_LAUNCH;
+                    return;
+                }
+                hipLaunchKernelGGL(k, dim3(grid), dim3(kIgThreads), lds, stream, a);
             };
-            if (pair) launch(std::true_type{});
+            if (g.pair) launch(std::true_type{});
             else launch(std::false_type{});
         }
     });
     if (err != FLUTE_OK) return err;
+    if (rc != FLUTE_OK) return rc;
     return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+}
+
+// The slab form (inst_grouped_input_grad_b*.hip).  The grid is E x ceil(K / 128), from the shapes alone.
+template <int BITS>
+int qgemm_grouped_input_grad_launch(const GroupedInputGrad& g, hipStream_t stream) {
+    GroupedIgArgs a = grouped_ig_args(g);
+    a.slabs = (a.K + kIgKS - 1) / kIgKS;
+    if ((long long)a.E * a.slabs > 0x7fffffffLL) return FLUTE_ERR_SHAPE;
+    auto kernel = [](auto t, auto tp, auto pr) {
+        return qgemm_grouped_input_grad_kernel<decltype(t), BITS, decltype(tp)::value, decltype(pr)::value>;
+    };
+    return grouped_ig_launch<BITS>(g, kernel, (unsigned)((long long)a.E * a.slabs), 0, a, stream);
 }
 
 }  // namespace flute_amd

@@ -5,11 +5,9 @@
 //
 // Work split.  A workgroup of 8 waves owns one 128-row block of one expert x one block of 256 k and walks all of N once, in
 // the slab form's chunks of 64 columns (pair form: the first stack, then the second, into the same fp32 accumulators).  The
-// row blocks are the forward block form's (qgemm_block2.h): b counts the 128-row blocks of all experts in expert order, every
-// wave finds (expert, block of it) from `offsets` in rounds of 64 experts - one per lane, a prefix sum and a ballot - and the
-// grid holds grouped_blocks_row_blocks(E, R) of them, the most a monotone table can own, times K / 256: from (E, R, K) alone.
-// The k block is the fast index of blockIdx, so the workgroups in flight share a row block's dY.  A workgroup whose b is
-// past the table's blocks returns before it requests a weight, scale or table word; an expert without rows owns no block.
+// row blocks are the forward block form's, found by grouped_rows.h's block map; the grid holds grouped_blocks_row_blocks(E, R)
+// of them times K / 256: from (E, R, K) alone.  The k block is the fast index of blockIdx, so the workgroups in flight share
+// a row block's dY.  A workgroup whose b is past the table's blocks returns before it requests a weight, scale or table word.
 //
 // Weights.  The slab form's decoder over twice the k: lane (unit ul < 64 / J, k-octet o < 16, field pair jp < J / 2) takes
 // the octets o and o + 16 of the block - one 16-B request per octet - and writes fields 2 jp and 2 jp + 1 of each as 16 B
@@ -37,12 +35,10 @@
 //
 // LDS (dynamic, above 64 KB: one workgroup per CU): 2 x 34 KB weight tiles, 2 x 18 KB dY tiles, 8 KB of table copies per stack.
 //
-// Rows.  rb / re are clamped to [0, R] before they form an address and every row index formed is < re: a malformed table
-// cannot reach outside dY / dX; it may claim more blocks than the grid holds (the surplus is dropped, as in the forward) or
-// a row twice.  Expert bases into Q / S / QM2 and row bases into dY / dX are 64-bit; there is no 32-bit descriptor.
+// Rows.  The contract on a malformed table is grouped_rows.h's.  Expert bases into Q / S / QM2 and row bases into dY / dX are
+// 64-bit; there is no 32-bit descriptor.
 #pragma once
 #include "qgemm_grouped_input_grad.h"
-#include "qgemm_block.h"
 
 namespace flute_amd {
 
@@ -58,17 +54,17 @@ static_assert(kIgbRB == 128 && kIgbKB == 256, "the wave layout below is 2 row gr
 
 constexpr int grouped_ig_blocks_lds(bool pair) { return kIgbLutAt + (pair ? 2 : 1) * kIgLutWords * 4; }
 
-static_assert(kIgbKB == kGroupedIgBlockK, "grouped_input_grad_blocks_eligible (qgemm_block.h) speaks of this k block");
+static_assert(kIgbKB == kGroupedIgBlockK, "grouped_input_grad_blocks_eligible (grouped_rows.h) speaks of this k block");
 
 template <typename T, int BITS, int TILEP, bool PAIR>
 __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_kernel(const GroupedIgArgs a) {
     using L = Layout<BITS>;
-    using NT = Num<T>;
     static_assert(BITS == 4 || BITS == 2, "3 bits stay on the slab form");
     constexpr int J = L::J;
+    constexpr int NP = L::NPLANES;                                 // 1
     constexpr int UC = kIgNC / J;                                  // units per chunk: 16 / 8
     constexpr int NSTK = PAIR ? 2 : 1;
-    constexpr int C = (kIgLutWords / L::LUT_N) > 32 ? 32 : (kIgLutWords / L::LUT_N);      // table copies: 8 / 32
+    constexpr int C = kIgLutCopies<BITS>;
     static_assert(UC % 8 == 0 && TILEP % UC == 0 && UC * 16 * (J / 2) == kIgThreads, "chunk shape");
 
     extern __shared__ __attribute__((aligned(16))) char igb_smem[];
@@ -78,55 +74,17 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int R = a.R, N = a.N, K = a.K, lg = a.lg;
-    uint16_t* __restrict__ dX = a.dX;
 
-    {   // rows no expert serves, [clamp(offsets[E]), R): zeros, 8 bytes per lane, spread over the whole grid
-        const int zb = min(max(a.offsets[a.E], 0), R);
-        const size_t n4 = (size_t)(R - zb) * (size_t)(K >> 2);
-        ushort4* z = reinterpret_cast<ushort4*>(dX + (size_t)zb * K);
-        for (size_t i = (size_t)blockIdx.x * kIgThreads + tid; i < n4; i += (size_t)gridDim.x * kIgThreads)
-            z[i] = ushort4{0, 0, 0, 0};
-    }
+    grouped_zero_unserved<kIgThreads>(a.dX, a.offsets, a.E, R, K);
 
-    // ---- the block map (qgemm_block2.h's): row block b -> (expert e, block jb of e, the expert's rows [rb, re))
+    // ---- row block b -> (expert e, block of e, the expert's rows [rb, re)); the k block is the fast index
     const int kblocks = a.slabs;                                   // K / 256
     const int b = (int)blockIdx.x / kblocks;
     const int kb = ((int)blockIdx.x - b * kblocks) * kIgbKB;
-    int e = -1, jb = 0, rb = 0, re = 0;
-    {
-        long long base = 0;                                        // (a malformed table may claim more blocks than an int counts)
-        for (int c0 = 0; c0 < a.E; c0 += 64) {
-            const int ee = c0 + lane;
-            int lo = 0, hi = 0;
-            if (ee < a.E) {
-                lo = min(max(a.offsets[ee], 0), R);
-                hi = min(max(a.offsets[ee + 1], 0), R);
-            }
-            const int nb = (max(hi - lo, 0) + kIgbRB - 1) / kIgbRB;        // blocks of expert ee; a round's sum is < 2^31
-            int incl = nb;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            const unsigned long long hit = __ballot(base + incl > (long long)b);
-            if (hit) {                                             // the first lane whose running total passes b: its nb > 0
-                const int src = __ffsll(hit) - 1;
-                e = c0 + src;
-                jb = (int)((long long)b - base) - __shfl(incl - nb, src);
-                rb = __shfl(lo, src);
-                re = __shfl(hi, src);
-                break;
-            }
-            base += __shfl(incl, 63);
-        }
-    }
-    e = __builtin_amdgcn_readfirstlane(e);
+    const GroupedBlock gb = grouped_block_map<kIgbRB>(a.offsets, a.E, R, b);
+    const int e = gb.e, rb = gb.rb, re = gb.re;
     if (e < 0) return;                                             // b is past the table's blocks: nothing is requested
-    jb = __builtin_amdgcn_readfirstlane(jb);
-    rb = __builtin_amdgcn_readfirstlane(rb);
-    re = __builtin_amdgcn_readfirstlane(re);
-    const int row0 = rb + jb * kIgbRB;                             // < re <= R
+    const int row0 = rb + gb.blk * kIgbRB;                         // < re <= R
 
     const int K2 = K >> 1;
     const int G = K >> lg;
@@ -135,13 +93,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
     const size_t q_base = (size_t)e * (size_t)a.P * (size_t)K2;
     const size_t s_base = (size_t)e * (size_t)N * (size_t)G;
 
-    // table images: entry i of copy c at word i * C + c
-#pragma unroll
-    for (int s = 0; s < NSTK; ++s) {
-        const uint32_t* __restrict__ Te = a.QM2[s] + (size_t)e * L::LUT_N;
-        for (int i = tid; i < L::LUT_N * C; i += kIgThreads) lut_all[s * kIgLutWords + i] = Te[i / C];
-    }
-    __syncthreads();
+    ig_load_tables<BITS, NSTK>(lut_all, kIgLutWords, a, e);
 
     // ---- the lane as a decoder: unit ul of the chunk, k-octets o and o + 16 of the block, fields 2 jp and 2 jp + 1
     const int o = tid & 15;
@@ -150,7 +102,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
     const int k0 = kb + 8 * o;                                     // the second octet: + 128; both < K (K % 256 == 0)
     const int lut_lane = lane % C;
     struct Packed {
-        u32x4_t w[2];
+        u32x4_t w[2][NP];                                          // [octet][plane]
         uint32_t s[2][2];                                          // [octet][field]
     };
     auto load_packed = [&](Packed& pk, int cc) {
@@ -162,7 +114,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
         const int n0 = unit_col0<BITS, TILEP>(u);
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
-            pk.w[hh] = in ? *reinterpret_cast<const u32x4_t*>(Qs + 64 * hh) : u32x4_t{0, 0, 0, 0};
+            pk.w[hh][0] = in ? *reinterpret_cast<const u32x4_t*>(Qs + 64 * hh) : u32x4_t{0, 0, 0, 0};
             const int gi = (k0 + 128 * hh) >> lg;
 #pragma unroll
             for (int f = 0; f < 2; ++f) pk.s[hh][f] = in ? (uint32_t)Ss[(size_t)(n0 + (2 * jp + f) * TILEP) * G + gi] : 0u;
@@ -172,16 +124,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
         char* dst = igb_smem + (cc & 1) * kIgbWTile + o * 16;
         const uint32_t* lt = lut_all + (PAIR ? (cc >= NCH) : 0) * kIgLutWords + lut_lane;
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                const int j = 2 * jp + f;
-                uint32_t v[4], out[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) v[d] = lt[field_rt<BITS>(pk.w[hh][d], pk.w[hh][d], pk.w[hh][d], j) * C];
-                NT::mul_scale4(v, pk.s[hh][f], out);
-                *reinterpret_cast<uint4*>(dst + (j * UC + ul) * kIgbWPitch + hh * 256) = make_uint4(out[0], out[1], out[2], out[3]);
-            }
+        for (int hh = 0; hh < 2; ++hh) ig_decode_octet<T, BITS, kIgbWPitch>(pk.w[hh], pk.s[hh], lt, jp, ul, true, dst + hh * 256);
     };
 
     // ---- the lane as a stager of dY: pieces (row yr + 64 t, tile rows 8 pc .. 8 pc + 7), t < 2
@@ -250,11 +193,7 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
             for (int s = 0; s < 2; ++s) {
                 u32x4_t af[4], bf[4];
 #pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    const uint2 a0 = lds_tr16(a_addr[0] + wbuf + s * 32 * kIgbWPitch + kt * 32);
-                    const uint2 a1 = lds_tr16(a_addr[1] + wbuf + s * 32 * kIgbWPitch + kt * 32);
-                    af[kt] = u32x4_t{a0.x, a0.y, a1.x, a1.y};
-                }
+                for (int kt = 0; kt < 4; ++kt) af[kt] = ig_a_fragment(a_addr, wbuf + s * 32 * kIgbWPitch + kt * 32);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const uint4 y = lds_ld128(y_addr + ybuf + t * 16 * kIgbYPitch + s * 64);
@@ -275,54 +214,21 @@ __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_ke
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int row = row0 + 64 * rg + 16 * t + r16;
-        if (row < re) {
-            float w = 1.0f;
-            if constexpr (!PAIR) {
-                if (a.row_weight) w = a.row_weight[row];
-            }
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {
-                const int k = kb + kq * 64 + kt * 16 + 4 * h;     // < K
-                f32x4_t s = acc[kt][t];
-                if constexpr (!PAIR) {
-                    if (a.row_weight) { s[0] *= w; s[1] *= w; s[2] *= w; s[3] *= w; }
-                }
-                ushort4 v;
-                v.x = NT::from_float(s[0]); v.y = NT::from_float(s[1]); v.z = NT::from_float(s[2]); v.w = NT::from_float(s[3]);
-                *reinterpret_cast<ushort4*>(dX + (size_t)row * K + k) = v;
-            }
-        }
+        if (row < re) ig_store_row<T, PAIR>(a, acc, t, row, kb + kq * 64 + 4 * h);       // k < K
     }
 }
 
-// The launch of one bit width (inst_grouped_input_grad_blocks_b*.hip): TileP 32 / 64 x f16 / bf16 x single / pair.  The grid
-// is grouped_blocks_row_blocks(E, R) x K / 256, from the shapes alone; the caller has checked grouped_input_grad_blocks_eligible.
+// The launch of one bit width (inst_grouped_input_grad_blocks_b*.hip).  The grid is grouped_blocks_row_blocks(E, R) x K / 256,
+// from the shapes alone; the caller has checked grouped_input_grad_blocks_eligible.
 template <int BITS>
-int qgemm_grouped_input_grad_blocks_launch(int dtype, int tile_p, bool pair, GroupedIgArgs a, hipStream_t stream) {
+int qgemm_grouped_input_grad_blocks_launch(const GroupedInputGrad& g, hipStream_t stream) {
+    GroupedIgArgs a = grouped_ig_args(g);
     a.slabs = a.K / kIgbKB;
-    const unsigned grid = (unsigned)(grouped_blocks_row_blocks(a.E, a.R) * a.slabs);
-    int rc = FLUTE_OK;
-    const int err = dispatch_layout(dtype, BITS, tile_p, [&](auto t, auto bits, auto tp) {
-        if constexpr (decltype(bits)::value == BITS) {  // the other widths live in their own units
-            auto launch = [&](auto pr) {
-                constexpr bool PR = decltype(pr)::value;
-                auto k = qgemm_grouped_input_grad_blocks_kernel<decltype(t), BITS, decltype(tp)::value, PR>;
-                const int lds = grouped_ig_blocks_lds(PR);
-                // (above 64 KB; the attribute is per device and setting it is no stream operation: asked for at every launch)
-                if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = FLUTE_ERR_LAUNCH;
-                    return;
-                }
-                hipLaunchKernelGGL(k, dim3(grid), dim3(kIgThreads), lds, stream, a);
-            };
-            if (pair) launch(std::true_type{});
-            else launch(std::false_type{});
-        }
-    });
-    if (err != FLUTE_OK) return err;
-    if (rc != FLUTE_OK) return rc;
-    return hipGetLastError() == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+    auto kernel = [](auto t, auto tp, auto pr) {
+        return qgemm_grouped_input_grad_blocks_kernel<decltype(t), BITS, decltype(tp)::value, decltype(pr)::value>;
+    };
+    return grouped_ig_launch<BITS>(g, kernel, (unsigned)(grouped_blocks_row_blocks(a.E, a.R) * a.slabs), grouped_ig_blocks_lds(g.pair),
+                                   a, stream);
 }
 
 }  // namespace flute_amd
