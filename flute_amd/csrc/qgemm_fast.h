@@ -6,7 +6,7 @@
 // life, and a launch of back-to-back dependent kernels lasts boundary + dispatch ramp (1.9 us for an empty kernel) +
 // the life of the workgroups that start last (profiles/r05/fast_lab_run*_stamps.jsonl).  This kernel is the same
 // algorithm - table image in LDS (256-B entry stride, 32 copies), wave-private scale image, every request in the
-// prologue, a software-pipelined decode loop - with the instruction count cut to ~760:
+// prologue, a software-pipelined decode loop - with the instruction count cut to ~760 (775 since round 8's finer lookup ring):
 //   * K = 512 * D * KW is a COMPILE-TIME constant (D pieces per wave, KW waves share a unit row), so are the waves
 //     per workgroup W, the rows MB and TileP: no geometry word, no ragged rows, no dead units, no bounds selects - every
 //     wave of the grid holds exactly D whole pieces and every unit is live (host contract below); 145 instructions
@@ -22,7 +22,11 @@
 //     instead of 4 x 11 - and the outputs of a unit leave in ONE store instruction;
 //   * K split across waves (KW > 1): partial sums and arrival tick leave back to back (two LDS round trips, not three);
 //   * round 7: the decode loop is the kernel's own (fast_pieces): activations and scales of all D pieces in registers first,
-//     then a ring of three groups of 8 lookups in flight (round 5 kept one behind the group being consumed).
+//     then a ring of three groups of 8 lookups in flight (round 5 kept one behind the group being consumed);
+//   * round 8: the wait for group g stands BETWEEN the table addresses and the lookups of the group issued behind it (it counts
+//     one group less and is exact for every ring), the ring is four groups of 4 lookups (a k-pair word x the 4 columns), and the
+//     upper half of a wave's pieces is requested behind the table word's wait instead of in front of it: 3.69 -> 3.53 us on the
+//     headline, more instructions than round 7's loop and faster ("Round 8").
 // Measured and dropped: helper waves that take the set-up loads off the compute waves (a CU's memory pipeline is
 // first-in first-out ACROSS its waves: the helpers' small loads queued behind the weight requests the compute waves
 // had already issued - table word after 3000 cycles instead of 650, profiles/r05/fast_lab_run2_stamps.jsonl).
@@ -50,21 +54,26 @@ __host__ __device__ constexpr size_t fast_lds_bytes(int W, int KW, int D, int lg
 // ring; 0 is the shipped one.
 struct FastRing { int R, GS; };
 __host__ __device__ constexpr FastRing fast_ring_of(int opt) {
-    constexpr FastRing rings[] = {{3, 8}, {2, 8}, {3, 8}, {4, 4}, {5, 4}, {3, 6}, {4, 5}};
+    constexpr FastRing rings[] = {{4, 4}, {2, 8}, {3, 8}, {4, 4}, {5, 4}, {3, 6}, {4, 5}, {5, 3}};
     return rings[(opt >> 6) & 7];
 }
 
 // The lean kernel's decode loop.  Every activation word and every scale pair of the wave's D pieces is read into registers
 // first (MB x D ds_read_b128 and D ds_read_b64, issued before any lookup: the first group's wait releases them), so the
-// LDS queue of the loop holds lookups only.  Then group g + R - 1 is issued before group g is waited for and multiplied:
-// R - 1 groups stay in flight behind the one being consumed, which hides one LDS round trip under a single wave per SIMD
-// (round 5's loop kept ONE group in flight: ~174 cycles per group of 8, one round trip).  LDS returns in
-// order, so "at most YOUNGER operations outstanding" releases group g; lgkmcnt encodes at most 15, and the rings allowed
-// here keep at most 16 younger lookups: the wait may release at most one read more than it needs.
+// LDS queue of the loop holds lookups only.  Then, for every group g: the table addresses of group g + R - 1, the wait for
+// group g, the lookups of group g + R - 1, the products of group g.  R - 2 groups are in flight behind the one being waited
+// for and R - 1 behind the one being multiplied, which hides one LDS round trip under a single wave per SIMD (round 5's
+// loop kept ONE group in flight: ~174 cycles per group of 8, one round trip).  The order is pinned
+// (sched_barrier: left alone, hipcc moves the addresses behind the wait and the products in front of the lookups).  Round 7
+// issued the lookups of group g + R - 1 BEFORE the wait for group g (OLD_ORDER, lab): with this order a ring of small groups
+// wins - the products of a group wait on the round trip of ITS lookups, and four return sooner than eight - which it did not
+// with round 7's ("Round 8": measured, both orders on six rings).  LDS returns in order, so "at most YOUNGER
+// operations outstanding" releases group g; lgkmcnt encodes at most 15, and the rings allowed here keep at most 16 younger
+// lookups: the wait may release at most one read more than it needs.
 // Arithmetic and its order are pipelined_pieces' (qgemm_oneshot.h, BA = 1): per lane, column and row, the piece's 8-k partial
 // sum starts with v_dot2 against a zero constant for k-pair word 0 and accumulates words 1, 2, 3 in order; then the fp32 group
 // scale: acc = fma(partial, scale, acc), pieces in order.
-template <typename T, int MB, int D, int R, int GS>
+template <typename T, int MB, int D, int R, int GS, bool OLD_ORDER = false>
 __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane, uint32_t x_row, uint32_t s_lane, uint32_t s_piece,
                                             uint32_t lane_off, float (&acc)[4][MB]) {
     using NT = Num<T>;
@@ -89,7 +98,8 @@ __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane
 #pragma unroll
     for (int i = 0; i < D; ++i) sq[i] = lds_hidden64(s_lane + (uint32_t)i * s_piece);
 
-    auto issue_group = [&](auto g_tag) {
+    uint32_t ad[GS];                                            // table addresses of the group being issued
+    auto addr_group = [&](auto g_tag) {
         constexpr int g = decltype(g_tag)::value;
         constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
         // the weights of every piece the group starts (each piece released by its own counted vmcnt)
@@ -99,7 +109,6 @@ __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane
         });
         // every table address of the group before its first lookup (hipcc otherwise alternates v_perm / ds_read through one
         // register); the empty asm statements are ordered before the lookups, each holds one address
-        uint32_t ad[GS];
 #pragma unroll
         for (int n = 0; n < L1 - L0; ++n) {
             const int L = L0 + n;
@@ -107,15 +116,22 @@ __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane
         }
 #pragma unroll
         for (int n = 0; n < L1 - L0; ++n) { uint32_t& r = ad[n]; asm volatile("" : "+v"(r)); }
+    };
+    auto read_group = [&](auto g_tag) {
+        constexpr int g = decltype(g_tag)::value;
+        constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
 #pragma unroll
         for (int n = 0; n < L1 - L0; ++n) lv[L0 + n] = lds_lookup32(ad[n]);
     };
+    auto issue_group = [&](auto g_tag) { addr_group(g_tag); read_group(g_tag); };
     // group g: released by its counted wait, its registers tied to the wait (ordered behind it) before their first use
     auto wait_group = [&](auto g_tag) {
         constexpr int g = decltype(g_tag)::value;
         constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
-        constexpr int YOUNGER = younger(g);
-        static_assert(YOUNGER <= 16, "over-wait");
+        // (group g + R - 1 is issued behind this wait, not in front of it: it does not count)
+        constexpr bool BEHIND = !OLD_ORDER && g + R - 1 < NGR;
+        constexpr int YOUNGER = younger(g) - (BEHIND ? ((g + R) * GS < NL ? GS : NL - (g + R - 1) * GS) : 0);
+        static_assert(YOUNGER >= 0 && YOUNGER <= 16, "over-wait");
         // (YOUNGER = 16: lgkmcnt(15) also waits for the oldest lookup of group g + 1)
         asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(YOUNGER < 15 ? YOUNGER : 15) : "memory");
 #pragma unroll
@@ -135,8 +151,16 @@ __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane
     static_for<NGR>([&](auto g_tag) {
         constexpr int g = decltype(g_tag)::value;
         constexpr int L0 = g * GS, L1 = (L0 + GS < NL) ? L0 + GS : NL;
-        if constexpr (g + R - 1 < NGR) issue_group(std::integral_constant<int, g + R - 1>{});
-        wait_group(g_tag);
+        if constexpr (OLD_ORDER) {
+            if constexpr (g + R - 1 < NGR) issue_group(std::integral_constant<int, g + R - 1>{});
+            wait_group(g_tag);
+        } else {
+            if constexpr (g + R - 1 < NGR) addr_group(std::integral_constant<int, g + R - 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+            wait_group(g_tag);
+            if constexpr (g + R - 1 < NGR) read_group(std::integral_constant<int, g + R - 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int L = L0; L < L1; ++L) {
             const int I = L / 16, ww = (L % 16) / 4, j = L % 4;
@@ -156,8 +180,9 @@ __device__ __forceinline__ void fast_pieces(ring16_t (&q)[D][1], uint32_t x_lane
     });
 }
 
-// OPT bits (lab): 1 = default-policy weight loads (nt otherwise), 2 = lookups ablated (timing floor), 64 .. 448 = another
-// lookup ring of the decode loop (fast_ring_of)
+// OPT bits (lab): 1 = default-policy weight loads (nt otherwise), 2 = lookups ablated (timing floor), 4 = round 7's loop order (the
+// lookups of group g + R - 1 in front of the wait for group g), 8 = every piece requested in front of the table word's wait
+// (round 7), 64 .. 448 = another lookup ring of the decode loop (fast_ring_of)
 // (The fused Hadamard pre-rotation of flute.qgemm_hadamard stays with the round-4 one-shot kernel: this kernel's four waves rotate
 // a row of K = 3584 / 4096 in two rounds - measured with the rotation as a template flag, 4.69 / 4.62 us against 4.81 / 4.61 for one
 // row on 4096 x 3584 / 4096 x 4096 and 6.28 against 5.99 for two: profiles/r05/call20_hadamard.log - and the flag was removed.)
@@ -235,18 +260,24 @@ __global__ __launch_bounds__(W * 64) void qgemv_fast_kernel(
     }
     const srd_t q_srd = make_srd(Qp + (size_t)unit * (K / 2), (uint32_t)K * 2u);
     ring16_t q[D][1];
-    static_for<D>([&](auto i_tag) {
+    // the lower half of the pieces here, the upper half behind the table word's wait: the wave has nothing else to issue while
+    // that word travels, and a piece of the upper half is not needed before the loop is half done (returns stay in request
+    // order, every counted wait below counts the pieces in the same order).  Measured: 0.01 - 0.08 us per launch by shape.
+    constexpr int DQ0 = (OPT & 8) ? D : (D + 1) / 2;
+    auto request_piece = [&](auto i_tag) {
         constexpr int i = decltype(i_tag)::value;
         const uint32_t vo = lane16 + (uint32_t)(kpart * D + i) * 1024u;
         if constexpr (OPT & 1) q[i][0] = buf_load16(vo, q_srd, 0);
         else q[i][0] = buf_load16_nt(vo, q_srd, 0);
-    });
+    };
+    static_for<DQ0>(request_piece);
     __builtin_amdgcn_sched_barrier(0);
     FLUTE_FSTAMP(2);
 
     // ---- table image: RUNS runs of 8 entries x 128 B; lane l writes 16 B (four copies) of entry l / 8 of the run ----
-    vm_wait_regs<XPR + NSL + D>(lut_v);
+    vm_wait_regs<XPR + NSL + DQ0>(lut_v);
     FLUTE_FSTAMP(3);
+    static_for<D - DQ0>([&](auto i_tag) { request_piece(std::integral_constant<int, DQ0 + decltype(i_tag)::value>{}); });
     {
         uint32_t te[RUNS];
 #pragma unroll
@@ -309,7 +340,7 @@ __global__ __launch_bounds__(W * 64) void qgemv_fast_kernel(
         });
     } else {
         constexpr FastRing ring = fast_ring_of(OPT);
-        fast_pieces<T, MB, D, ring.R, ring.GS>(q, x_lane, (uint32_t)K * 2u, s_lane, (uint32_t)(gpp * 4) * 2u, lane_off, acc);
+        fast_pieces<T, MB, D, ring.R, ring.GS, (OPT & 4) != 0>(q, x_lane, (uint32_t)K * 2u, s_lane, (uint32_t)(gpp * 4) * 2u, lane_off, acc);
     }
     FLUTE_FSTAMP(9);
 

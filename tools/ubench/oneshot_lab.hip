@@ -251,11 +251,16 @@ int main(int argc, char** argv) {
         const FV fvs[] = {
             FV_("fast_w4_kw1_d8", 4, 1, 8, 0, 0), FV_("fast_w8_kw2_d4", 8, 2, 4, 0, 0), FV_("fast_w4_kw2_d4", 4, 2, 4, 0, 0),
             FV_("fast_w4_kw1_d8_nolookup", 4, 1, 8, 0, 2),
-            // the decode loop's lookup ring (qgemm_fast.h fast_ring_of): R groups x GS lookups in flight
+            // the decode loop's lookup ring (qgemm_fast.h fast_ring_of): R groups x GS lookups in flight (OPT 0: 4 x 4)
             FV_("fast_w4_kw1_d8_ring2x8", 4, 1, 8, 0, 64), FV_("fast_w4_kw1_d8_ring3x8", 4, 1, 8, 0, 128),
-            FV_("fast_w4_kw1_d8_ring4x4", 4, 1, 8, 0, 192), FV_("fast_w4_kw1_d8_ring5x4", 4, 1, 8, 0, 256),
-            FV_("fast_w4_kw1_d8_ring3x6", 4, 1, 8, 0, 320), FV_("fast_w4_kw1_d8_ring4x5", 4, 1, 8, 0, 384),
-            FV_("fast_w4_kw1_d7_ring2x8", 4, 1, 7, 0, 64), FV_("fast_w4_kw1_d7", 4, 1, 7, 0, 0),
+            FV_("fast_w4_kw1_d8_ring5x4", 4, 1, 8, 0, 256), FV_("fast_w4_kw1_d8_ring3x6", 4, 1, 8, 0, 320),
+            FV_("fast_w4_kw1_d8_ring4x5", 4, 1, 8, 0, 384), FV_("fast_w4_kw1_d8_ring5x3", 4, 1, 8, 0, 448),
+            // round 7's loop order (4), every piece requested in front of the table word's wait (8), both on round 7's ring (140 =
+            // round 7's kernel)
+            FV_("fast_w4_kw1_d8_oldorder", 4, 1, 8, 0, 4), FV_("fast_w4_kw1_d8_upfront", 4, 1, 8, 0, 8),
+            FV_("fast_w4_kw1_d8_oldorder_upfront", 4, 1, 8, 0, 12), FV_("fast_w4_kw1_d8_r07", 4, 1, 8, 0, 140),
+            FV_("fast_w4_kw1_d7_r07", 4, 1, 7, 0, 140), FV_("fast_w4_kw1_d7", 4, 1, 7, 0, 0),
+            FV_("fast_w8_kw2_d4_r07", 8, 2, 4, 0, 140), FV_("fast_w4_kw1_d4_r07", 4, 1, 4, 0, 140),
             FV_("fast_w8_kw2_d8", 8, 2, 8, 0, 0), FV_("fast_w16_kw4_d4", 16, 4, 4, 0, 0),
             FV_("fast_w4_kw1_d4", 4, 1, 4, 0, 0), FV_("fast_w8_kw2_d2", 8, 2, 2, 0, 0),
         };
