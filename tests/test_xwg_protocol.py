@@ -5,7 +5,8 @@ Checked for every schedule: every share of the tile is combined exactly once, by
 of it; nobody reads a partial that was not published before the reader learnt of it through an atomic; the state words are
 zero when the launch ends; nothing waits for a workgroup that has not arrived.  The protocol below is xwg.h's, transcribed
 (publish -> drain -> arrive; poll / claim / abandon; last arriver: own share, sweep, reset).  The hardware run of the same
-paths: tests/test_qgemm_gpu.py::test_splitk_seam_under_load and profiles/r04/xwg_abandon_path_forced.json."""
+paths: tests/test_qgemm_gpu.py::test_splitk_seam_under_load (polls that succeed) and tests/test_xwg_giveup_gpu.py (polls
+that run out: the build's variant libraries with the poll limit 0 and 1)."""
 import random
 
 import pytest
