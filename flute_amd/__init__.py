@@ -30,6 +30,7 @@ pair_grad_to_table_grad = ops.pair_grad_to_table_grad
 # stay on the device); modules on top of it: flute_amd.integrations.moe
 qgemm_grouped = ops.qgemm_grouped
 qgemm_grouped_glu = ops.qgemm_grouped_glu
+qgemm_grouped_glu_blocks = ops.qgemm_grouped_glu_blocks     # the same launch on 128-row blocks, for prefill / training row counts
 qgemm_grouped_weighted = ops.qgemm_grouped_weighted
 # their input gradient, one launch over the packed stacks (contracts over N); the grouped and mixture-of-experts functions
 # here backpropagate through it to activations, routing weights and router logits

@@ -68,6 +68,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_glu_ex": (c_int, [c_int] * 10 + [c_void_p] * 10 + [c_int, c_void_p, c_int]),
     "flute_qgemm_grouped_weighted_ex": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p, c_int]),
     "flute_qgemm_grouped_form": (c_int, [c_int] * 10),
+    "flute_qgemm_grouped_glu_blocks": (c_int, [c_int] * 10 + [c_void_p] * 10 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_glu_blocks_form": (c_int, [c_int] * 10),
     "flute_qgemm_grouped_input_grad": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p]),
     "flute_qgemm_grouped_input_grad_row_block": (c_int, []),
     "flute_qgemm_grouped_input_grad_ex": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p, c_int]),

@@ -1745,18 +1745,25 @@ int flute_qgemm_grouped_form(int mode, int dtype, int num_bits, int group_size, 
     return grouped_form_auto(mode, num_bits, l.lg, E, rows, N, K, num_sms);
 }
 
+// the refusals of the GLU launches after check_grouped: Tsrc and its relation to `rows` (compared with null, never looked behind)
+static int check_glu_rows(int R, int Tsrc, bool has_rows) {
+    if (Tsrc < 0) return FLUTE_ERR_SHAPE;
+    if (has_rows ? (R > 0 && Tsrc < 1) : Tsrc != R) return FLUTE_ERR_SHAPE;
+    return FLUTE_OK;
+}
+
 // flute_qgemm_grouped_ex, _glu_ex and _weighted_ex behind their signatures: the operands by name (a mode's own left null by the
 // others, one stack in both slots), and the one sequence - check_grouped, the GLU-only Tsrc / rows refusals, the form, the empty
-// launch, the null pointers, the dispatch.  (No block form of the GLU mode is built: automatic is the row form at every row count,
-// and forcing blocks is refused.)
+// launch, the null pointers, the dispatch.  (Through these entries the GLU mode has no block form: automatic is the row form at
+// every row count, and forcing blocks is refused; its block form is an entry of its own, flute_qgemm_grouped_glu_blocks below.)
 static int grouped_forward(GroupedForward g, int group_size, int template_id, int form, void* stream) {
     const bool glu = g.mode == FLUTE_GROUPED_GLU;
     Layer l;
     const int rc = check_grouped(g.dtype, g.num_bits, group_size, template_id, g.E, g.R, g.N, g.K, g.P, &l);
     if (rc) return rc;
     if (glu) {
-        if (g.Tsrc < 0) return FLUTE_ERR_SHAPE;
-        if (g.rows ? (g.R > 0 && g.Tsrc < 1) : g.Tsrc != g.R) return FLUTE_ERR_SHAPE;
+        const int rows_rc = check_glu_rows(g.R, g.Tsrc, g.rows != nullptr);
+        if (rows_rc) return rows_rc;
     }
     g.tile_p = l.t.tile_p;
     g.lg = l.lg;
@@ -1806,6 +1813,57 @@ int flute_qgemm_grouped_glu_ex(int dtype, int num_bits, int group_size, int E, i
     g.Q[0] = Qgate; g.S[0] = Sgate; g.QM2[0] = QM2gate;
     g.Q[1] = Qup; g.S[1] = Sup; g.QM2[1] = QM2up;
     return grouped_forward(g, group_size, template_id, form, stream);
+}
+
+// The block form of the GLU launch behind its own entry (include/flute_amd.h; qgemm_block2.h GM = 3).  What it serves:
+// grouped_glu_blocks_eligible and nothing else, asked with an empty launch's E / R / Tsrc raised to 1 - the shape of the layer is
+// what is refused, and an empty launch of a served layer returns FLUTE_OK as everywhere.  The query's thresholds are the plain form's
+// rule (grouped_blocks_min_mean_rows' split by E * (F / 256) against num_sms) on constants of their own,
+// FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS / _PARTIAL = 16 / 48: each the smallest swept mean from which the block launch is not slower
+// on any swept stack of its kind (the policy of 3.3m / 3.3n).  The sweep (profiles/grouped_moe_glu_blocks.json, "glu threshold sweep":
+// W4G64 fp16, us of row form / block form at even counts, rows / E = 16, 32, 48, 64, 96, 128; the row form pays two K passes per 32
+// rows, so its crossover lies lower than the plain launch's): Mixtral gate / up pair (448 workgroups per row block) 254 / 245,
+// 329 / 253, 527 / 256, 600 / 266, 872 / 292, 1140 / 307; E 64 2048 x 2048 pair (512) 220 / 134, 255 / 140, 412 / 147, 440 / 153,
+// 622 / 169, 804 / 182; E 8 4096 x 4096 pair (128 workgroups: does not fill the chip) 77 / 119, 97 / 120, 154 / 122, 174 / 123,
+// 252 / 125, 329 / 128 - the routed draws say the same (at 32 on the last stack 121 / 121, a tie).
+static bool grouped_glu_blocks_serves(int num_bits, int lg, int E, int R, int Tsrc, int F, int K) {
+    return grouped_glu_blocks_eligible(num_bits, lg, std::max(E, 1), std::max(R, 1), std::max(Tsrc, 1), F, K);
+}
+
+int flute_qgemm_grouped_glu_blocks_form(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K,
+                                        int template_id, int num_sms) {
+    Layer l;
+    int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, num_bits * (F / 16), &l);
+    if (rc) return rc;
+    if (Tsrc < 0) return FLUTE_ERR_SHAPE;
+    if (E < 1 || R < 1 || !grouped_glu_blocks_eligible(num_bits, l.lg, E, R, Tsrc, F, K)) return FLUTE_GROUPED_FORM_ROWS;
+    const long long sms = num_sms >= 1 ? num_sms : 256;
+    const int thr = (long long)E * (F / 256) >= sms ? FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS
+                                                    : FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL;
+    return (long long)R >= (long long)thr * E ? FLUTE_GROUPED_FORM_BLOCKS : FLUTE_GROUPED_FORM_ROWS;
+}
+
+int flute_qgemm_grouped_glu_blocks(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                                   int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                                   const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                                   void* H, int num_sms, void* stream) {
+    Layer l;
+    int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, P, &l);
+    if (rc) return rc;
+    rc = check_glu_rows(R, Tsrc, rows != nullptr);
+    if (rc) return rc;
+    if (!grouped_glu_blocks_serves(num_bits, l.lg, E, R, Tsrc, F, K)) return FLUTE_ERR_SHAPE;
+    if (E == 0 || R == 0) return FLUTE_OK;
+    if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
+    GroupedForward g{};
+    g.mode = FLUTE_GROUPED_GLU; g.form = FLUTE_GROUPED_FORM_BLOCKS; g.dtype = dtype; g.num_bits = num_bits;
+    g.tile_p = l.t.tile_p; g.lg = l.lg;
+    g.E = E; g.R = R; g.Tsrc = Tsrc; g.N = F; g.K = K; g.P = P;
+    g.X = Xsrc; g.rows = rows; g.offsets = offsets; g.Y = H; g.num_sms = num_sms;
+    g.Q[0] = Qgate; g.S[0] = Sgate; g.QM2[0] = QM2gate;
+    g.Q[1] = Qup; g.S[1] = Sup; g.QM2[1] = QM2up;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return num_bits == 4 ? qgemm_grouped_glu_blocks_unit_b4(g, st) : qgemm_grouped_glu_blocks_unit_b2(g, st);
 }
 
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,

@@ -41,6 +41,19 @@ inline bool grouped_blocks_eligible(int mode, int num_bits, int lg, int E, int T
     return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
 }
 
+// What the block form of the fused SwiGLU launch serves (flute_qgemm_grouped_glu_blocks; api.hip's refusal and query read this,
+// nothing else decides it): the plain mode's conditions with F in N's place, but for the activations - the descriptor spans Xsrc
+// and no block reaches past its expert, so Tsrc * K * 2 is what must stay below 2^32 - 16 - and a sorted-row index plus a block
+// that stays an int (R is not bounded by Tsrc).
+inline bool grouped_glu_blocks_eligible(int num_bits, int lg, int E, int R, int Tsrc, int F, int K) {
+    if (num_bits != 4 && num_bits != 2) return false;
+    if (E < 1 || R < 1 || Tsrc < 1 || F < 256 || F % 256 || K < 64 || (K >> lg) % 8) return false;
+    if (R > 0x7fffffff - 2 * kGroupedBlockRows) return false;
+    if ((size_t)Tsrc * K * 2 >= (size_t)0xfffffff0u) return false;
+    if ((size_t)F * (K >> lg) * 2 >= (size_t)0xfffffff0u) return false;
+    return grouped_blocks_row_blocks(E, R) * (F / 256) <= 0x7fffffffLL;
+}
+
 // What the block form of the input gradient serves (qgemm_grouped_input_grad_blocks.h; api.hip's form rule and refusal read
 // this, nothing else decides it): 4 / 2 bits, whole 256-k blocks, a row index plus a block that stays an int, and a 31-bit
 // grid.  (N, TileP and the group size are the slab form's, which the caller has checked with the layer; every base in the kernel

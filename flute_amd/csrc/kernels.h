@@ -107,6 +107,10 @@ int qgemm_grouped_weighted_unit(const GroupedForward& g, hipStream_t stream);
 // inst_grouped_blocks_b*.hip, one unit per bit width); the grid follows from (E, R, N) alone
 int qgemm_grouped_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);
 int qgemm_grouped_blocks_unit_b2(const GroupedForward& g, hipStream_t stream);
+// the block form of the Glu mode (flute_qgemm_grouped_glu_blocks; what it serves: grouped_glu_blocks_eligible, grouped_rows.h;
+// inst_grouped_glu_blocks_b*.hip): the same grid from (E, R, F) alone.  Its own entry: qgemm_grouped_dispatch never takes it.
+int qgemm_grouped_glu_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);
+int qgemm_grouped_glu_blocks_unit_b2(const GroupedForward& g, hipStream_t stream);
 // the unit of a launch: the one ladder over form, bit width and mode
 inline int qgemm_grouped_dispatch(const GroupedForward& g, hipStream_t stream) {
     if (g.form == FLUTE_GROUPED_FORM_BLOCKS)

@@ -57,6 +57,16 @@ struct GroupedBlockArgs : BlockArgs {
     int E, P;                   // P: unit rows of one expert's Q
 };
 
+// The fused SwiGLU member of that front end (GM = 3): H = silu32(g) * u over two stacks.  Q / S / QM2 are the gate stack's, D is H,
+// N is F; A is Xsrc [Tsrc, K], read through rows [M] (null: row r is r).  Derived, so the arguments of GM = 0 / 1 / 2 do not move.
+struct GroupedGluBlockArgs : GroupedBlockArgs {
+    const uint32_t* Q_up;       // the up stack, expert 0
+    const void* S_up;
+    const uint32_t* QM2_up;
+    const int* rows;            // [M] int32 or null, device memory, read by the kernel only
+    int Tsrc;
+};
+
 constexpr int BLK_STAGES = 3;
 
 // 16-B chunk swizzle of a 16-row x 64-B activation piece (an involution applied to the DMA source address and

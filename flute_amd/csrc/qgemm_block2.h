@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "qgemm_block.h"
+#include "silu32.h"
 
 namespace flute_amd {
 
@@ -38,11 +39,19 @@ namespace flute_amd {
 // (The order of b against the column block is the host's: GroupedBlockArgs::order, measured in qgemm_grouped_blocks.h.)
 // The activation descriptor starts at row rb and is (re - rb) rows long, so the rows of the block at or past re read as zero by the
 // same out-of-range idiom as the dense rows past M, and no row outside [rb, re) forms an address; the epilogue stores rows < re.
+//
+// GM = 3: the fused SwiGLU member, H[r, :] = round_T(silu32(g) * u) (flute_qgemm_grouped_glu_blocks; the arithmetic is qgemm_grouped.h's
+// Glu mode).  The K pass below - prologue, main loop, drain: one program text, `k_pass` - runs twice over the same rows: for the gate
+// stack, whose 64 fp32 accumulators per lane are then set aside (the register budget of the dense RT = 16 form), and for the up stack
+// after a barrier, with the pair table restaged and the activations staged again (L2-hot); the epilogue combines and rounds once.  The
+// activation descriptor spans Xsrc and a lane's row is rows[r] (clamped to [0, Tsrc), read once per workgroup); a block row at or past
+// re reads no index and gets kRowOut, a voffset out of range for every descriptor the eligibility rule admits.
 template <typename T, int TILEP, int RT = 16, int BITS = 4, int GM = 0>
-__global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs> args) {
+__global__ __launch_bounds__(512) void qgemm_block2_kernel(
+    const std::conditional_t<GM == 3, GroupedGluBlockArgs, std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs>> args) {
     using NT = Num<T>;
     static_assert(GM == 0 || RT == 8, "the grouped front end is built for 128-row blocks");
-    static_assert(GM >= 0 && GM <= 2, "0: dense, 1: grouped plain, 2: grouped weighted");
+    static_assert(GM >= 0 && GM <= 3, "0: dense, 1: grouped plain, 2: grouped weighted, 3: grouped SwiGLU");
     static_assert(BITS == 4 || BITS == 2, "3-bit layers use the per-wave MFMA kernel (qgemm_tile.h)");
     constexpr int J = 16 / BITS;                                   // fields per word
     constexpr int U = 32 / J;                                      // units per wave (32 columns)
@@ -89,6 +98,9 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
     if (a.splitk > 1) { split = bid % a.splitk; bid /= a.splitk; }
     int tm_idx, tn_idx;
     int row_lo = 0, row_hi = 0;                                    // grouped: the expert's rows [rb, re)
+    const int* glu_rows = nullptr;                                 // GM = 3: the row index (or null) and the rows of Xsrc
+    int glu_tsrc = 0;
+    if constexpr (GM == 3) { glu_rows = a.rows; glu_tsrc = a.Tsrc; }
     if constexpr (GM != 0) {
         static_assert(BM == kGroupedBlockRows, "the host's grid counts these blocks");
         if constexpr (GM == 2) grouped_zero_unserved<NW * 64>(reinterpret_cast<uint16_t*>(a.D), a.offsets, a.E, a.M, a.N);
@@ -104,6 +116,11 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
         a.Q += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);
         a.S = reinterpret_cast<const uint16_t*>(a.S) + (size_t)e * (size_t)a.N * (size_t)a.G;
         a.QM2 += (size_t)e << (2 * BITS);
+        if constexpr (GM == 3) {
+            a.Q_up += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);
+            a.S_up = reinterpret_cast<const uint16_t*>(a.S_up) + (size_t)e * (size_t)a.N * (size_t)a.G;
+            a.QM2_up += (size_t)e << (2 * BITS);
+        }
     } else if (a.order == 1) {
         const int per = a.tiles_m >> 3, x = bid & 7, i = bid >> 3;
         tm_idx = x * per + i % per;
@@ -123,12 +140,13 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
     const int nsteps = (kend - kbeg) >> 6;
     const uint32_t row_bytes = (uint32_t)a.K * 2u;
 
-    const srd_t x_srd = GM != 0
+    srd_t x_srd = GM != 0
         ? make_srd(reinterpret_cast<const uint16_t*>(a.A) + (size_t)row_lo * a.K,
                    (uint32_t)min((size_t)(row_hi - row_lo) * a.K * 2, (size_t)0xfffffff0u))
         : make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
-    const srd_t w_srd = make_srd(reinterpret_cast<const char*>(a.Q) + (size_t)unit0 * row_bytes, (uint32_t)U * row_bytes);
-    const srd_t s_srd = make_srd(a.S, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
+    srd_t w_srd = make_srd(reinterpret_cast<const char*>(a.Q) + (size_t)unit0 * row_bytes, (uint32_t)U * row_bytes);
+    srd_t s_srd = make_srd(a.S, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
+    if constexpr (GM == 3) x_srd = make_srd(a.A, (uint32_t)min((size_t)glu_tsrc * a.K * 2, (size_t)0xfffffff0u));   // the whole of Xsrc
     // Activations (round 4: WHOLE cache lines - a request is priced per line it touches; before: 16 rows x 64 B): piece
     // p = 2 rt + rh of a stage = rows 16 rt + 8 rh .. + 7, 128 B (the 64 k of the step) each; lane L fetches the 16-B chunk
     // (L & 7) ^ blk_swz8(L >> 3, rh) of row L >> 3, written lane-linearly.  This wave's pieces: wave * PPW + i.  Rows past M
@@ -140,7 +158,20 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
         const int rt = (p0 + i) >> 1, rh = (p0 + i) & 1, row8 = lane >> 3;
-        x_vo[i] = (uint32_t)(((size_t)(m0 + rt * 16 + rh * 8 + row8) * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2);
+        if constexpr (GM == 3) {
+            // the lane's row through the index: r in [rb, re) reads rows[r] (null: r itself) clamped to [0, Tsrc); any other row of the
+            // block reads no index and forms no address.  kRowOut: Tsrc K 2 is a multiple of 128 below 2^32 - 16, so at most 2^32 - 128
+            // - out of range whether the check adds the 16 bytes of the request or not, and adding them does not wrap
+            constexpr uint32_t kRowOut = 0xffffffe0u;
+            const int r = row_lo + m0 + rt * 16 + rh * 8 + row8;
+            x_vo[i] = kRowOut;
+            if (r < row_hi) {
+                const int src = min(max(glu_rows ? glu_rows[r] : r, 0), glu_tsrc - 1);
+                x_vo[i] = (uint32_t)(((size_t)src * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2);
+            }
+        } else {
+            x_vo[i] = (uint32_t)(((size_t)(m0 + rt * 16 + rh * 8 + row8) * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2);
+        }
     }
     const uint32_t x_lds0 = (uint32_t)LUT_BYTES + (uint32_t)p0 * 1024u;
     // Weights (round 4): ONE request per wave and step - U unit rows x 128 B, whole lines: lane (r16, q4) fetches chunk
@@ -196,6 +227,12 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
         }
     };
 
+    // One K pass over the stack that a.QM2 / w_srd / s_srd name, from here to the drain below: all of K into acc.  GM = 3 comes
+    // back here once, for the up stack (after the drain; a jump, so that the pass stays one program text and the other members'
+    // code is what it was without it).
+    f32x4_t acc_gate[GM == 3 ? RT : 1][NT2];                       // GM = 3: g, set aside after the first pass
+    int pass = 0;
+k_pass: __attribute__((unused));
     issue_batch(std::integral_constant<int, 0>{}, 0);
     issue_batch(std::integral_constant<int, 1>{}, 1);
     {
@@ -364,6 +401,22 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
     }
     wait_lds();                                                    // the prefetch past the end
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]) : : "memory");
+    if constexpr (GM == 3) {
+        if (pass == 0) {
+            // g is whole: set it aside and run the same pass for the up stack (acc starts from zero again there).  The barrier: every
+            // wave has drained its requests and finished its lookups and fragment reads, so the pair table and the stages may be overwritten.
+            pass = 1;
+#pragma unroll
+            for (int r = 0; r < RT; ++r)
+#pragma unroll
+                for (int t = 0; t < NT2; ++t) acc_gate[r][t] = acc[r][t];
+            __builtin_amdgcn_s_barrier();
+            a.QM2 = a.QM2_up;
+            w_srd = make_srd(reinterpret_cast<const char*>(a.Q_up) + (size_t)unit0 * row_bytes, (uint32_t)U * row_bytes);
+            s_srd = make_srd(a.S_up, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
+            goto k_pass;
+        }
+    }
 
     // ---- epilogue: accumulator register i of lane (r16, q4) = weight row 4 q4 + i of the column tile = unit
     // (4 q4 + i) % 8, field q4 / 2 + 2 t: four consecutive columns; the lane's output row is r16 ----
@@ -378,6 +431,10 @@ __global__ __launch_bounds__(512) void qgemm_block2_kernel(const std::conditiona
             for (int t = 0; t < NT2; ++t) {
                 const int col = unit_col0<BITS, TILEP>(c_unit) + ((4 * q4) / U + FPT * t) * TILEP;
                 f32x4_t o4 = acc[r][t];
+                if constexpr (GM == 3) {
+                    const f32x4_t g4 = acc_gate[r][t];
+                    o4 = f32x4_t{silu32(g4[0]) * o4[0], silu32(g4[1]) * o4[1], silu32(g4[2]) * o4[2], silu32(g4[3]) * o4[3]};
+                }
                 if constexpr (GM == 2) { o4[0] *= rw; o4[1] *= rw; o4[2] *= rw; o4[3] *= rw; }
                 if (GM != 0 || a.splitk == 1) {
                     uint2 o;

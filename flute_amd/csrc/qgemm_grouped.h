@@ -61,6 +61,7 @@
 #include "kernels.h"
 #include "grouped_rows.h"
 #include "mfma.h"
+#include "silu32.h"
 #include <type_traits>
 #include "layout_dispatch.h"
 
@@ -79,11 +80,7 @@ template <int BITS, int LGC> struct GroupedShape {
     static constexpr int U = (BITS == 3) ? 1 : (BITS == 2 && LGC < 7) ? 2 : 4;               // k-steps per block
 };
 
-// silu32(g) = g / (1 + exp(-g)), fp32.  expf is within 1 ulp (2^-23 relative), the sum 1 + t and the quotient are
-// correctly rounded (2^-24 each; IEEE division is hipcc's default), and an error of t enters 1 + t scaled by
-// t / (1 + t) < 1: relative error <= 2^-23 + 2 * 2^-24 = 2^-22 to first order, for every |g| <= 88 (exp(88) is finite;
-// exp(-88) underflows against the 1).  With the fp32 product by u (2^-24) behind it: eps_s = 2^-21 covers both.
-__device__ __forceinline__ float silu32(float g) { return g / (1.0f + expf(-g)); }
+// (silu32() and its error account: silu32.h, shared with the block form of the Glu mode, qgemm_block2.h GM = 3)
 
 struct GroupedArgs {
     const uint16_t* X;          // [Tsrc, K] T

@@ -1,6 +1,7 @@
 // Host side of the block form of the grouped qgemm: qgemm_block2.h's 128-row blocks behind a grouped front end (the kernel text and
 // the block map are described there), for experts with many rows - prefill and training - where the row form of qgemm_grouped.h
-// streams an expert's weights once per 32 rows.  Plain and weighted modes, 4 and 2 bits; the SwiGLU mode and 3 bits stay on the row form.
+// streams an expert's weights once per 32 rows.  Plain and weighted modes (flute_qgemm_grouped_ex / _weighted_ex with the block form)
+// and the SwiGLU mode behind its own entry (flute_qgemm_grouped_glu_blocks), 4 and 2 bits; 3 bits stay on the row form.
 #pragma once
 #include "../../include/flute_amd.h"
 #include "kernels.h"
@@ -17,11 +18,15 @@
 
 namespace flute_amd {
 
-// One launch: GM = 1 plain, 2 weighted.  The grid follows from (E, T, N) alone.
-template <int BITS, int GM>
-int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
-    const int dtype = g.dtype, tile_p = g.tile_p;
-    GroupedBlockArgs a{};
+// The LDS of a grouped block launch, every mode: pair table + three activation stages + per wave: two scale blocks and a sink (as
+// plan_block sizes the dense launch).  The SwiGLU mode restages the one pair table between its two K passes and needs no more.
+template <int BITS>
+constexpr size_t grouped_blocks_lds_bytes() {
+    return (size_t)((128 << (2 * BITS)) + BLK_STAGES * (kGroupedBlockRows / 16) * 2 * 1024 + 8 * 3 * 1024);
+}
+
+// What every mode's argument struct shares, from the launch's named operands (GM = 3: Q / S / QM2 are the gate stack's, N is F).
+inline void grouped_block_args(GroupedBlockArgs& a, const GroupedForward& g) {
     a.A = g.X; a.Q = reinterpret_cast<const uint32_t*>(g.Q[0]); a.D = g.Y; a.S = g.S[0];
     a.QM2 = reinterpret_cast<const uint32_t*>(g.QM2[0]);
     a.M = g.R; a.N = g.N; a.K = g.K; a.G = g.K >> g.lg; a.lg = g.lg;
@@ -29,15 +34,15 @@ int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
     a.splitk = 1; a.k_per_split = g.K;
     a.order = FLUTE_GROUPED_BLOCKS_ORDER;
     a.offsets = reinterpret_cast<const int*>(g.offsets);
-    a.row_weight = GM == 2 ? g.row_weight : nullptr;
+    a.row_weight = nullptr;
     a.E = g.E; a.P = g.P;
-    typedef void (*Kernel)(const GroupedBlockArgs);
-    Kernel k = nullptr;
-    if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, GM>;
-    else if (tile_p == 64) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 64, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 64, 8, BITS, GM>;
+}
+
+// The launch of one resolved kernel: the grid follows from (E, R, N) alone.
+template <int BITS, typename Args>
+int grouped_blocks_enqueue(void (*k)(const Args), Args& a, hipStream_t stream) {
     if (!k) return FLUTE_ERR_SHAPE;
-    // pair table + three activation stages + per wave: two scale blocks and a sink (as plan_block sizes the dense launch)
-    const size_t lds = (size_t)((128 << (2 * BITS)) + 3 * (kGroupedBlockRows / 16) * 2 * 1024 + 8 * 3 * 1024);
+    const size_t lds = grouped_blocks_lds_bytes<BITS>();
     // (above 64 KB; the attribute is per device and setting it is no stream operation: asked for at every launch, as moe_route.hip does)
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
@@ -49,6 +54,37 @@ int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
         return FLUTE_ERR_LAUNCH;
     }
     return FLUTE_OK;
+}
+
+// One launch: GM = 1 plain, 2 weighted.
+template <int BITS, int GM>
+int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    const int dtype = g.dtype, tile_p = g.tile_p;
+    GroupedBlockArgs a{};
+    grouped_block_args(a, g);
+    a.row_weight = GM == 2 ? g.row_weight : nullptr;
+    typedef void (*Kernel)(const GroupedBlockArgs);
+    Kernel k = nullptr;
+    if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, GM>;
+    else if (tile_p == 64) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 64, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 64, 8, BITS, GM>;
+    return grouped_blocks_enqueue<BITS>(k, a, stream);
+}
+
+// The SwiGLU launch (GM = 3): both stacks, the row index and the rows of Xsrc beside the shared arguments; the same grid.
+template <int BITS>
+int qgemm_grouped_glu_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    const int dtype = g.dtype, tile_p = g.tile_p;
+    GroupedGluBlockArgs a{};
+    grouped_block_args(a, g);
+    a.Q_up = reinterpret_cast<const uint32_t*>(g.Q[1]); a.S_up = g.S[1];
+    a.QM2_up = reinterpret_cast<const uint32_t*>(g.QM2[1]);
+    a.rows = reinterpret_cast<const int*>(g.rows);
+    a.Tsrc = g.Tsrc;
+    typedef void (*Kernel)(const GroupedGluBlockArgs);
+    Kernel k = nullptr;
+    if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, 3> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, 3>;
+    else if (tile_p == 64) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 64, 8, BITS, 3> : (Kernel)qgemm_block2_kernel<BF16, 64, 8, BITS, 3>;
+    return grouped_blocks_enqueue<BITS>(k, a, stream);
 }
 
 }  // namespace flute_amd

@@ -61,6 +61,19 @@ def grouped_form(mode: str, E: int, rows: int, N: int, K: int, num_bits: int, gr
     return {1: "rows", 2: "blocks"}[rc]
 
 
+def grouped_glu_blocks_form(E: int, rows: int, Tsrc: int, F: int, K: int, num_bits: int, group_size: int, template_id: int,
+                            num_sms: int = 0, dtype: torch.dtype = torch.float16) -> str:
+    """Which fused SwiGLU launch to take for `rows` sorted rows read out of `Tsrc` source rows over E experts with [F, K]
+    gate / up layers: "blocks" - `flute_amd.qgemm_grouped_glu_blocks` - where the shape is eligible for it and rows / E
+    reaches the threshold, else "rows" - `flute_amd.qgemm_grouped_glu`; host only (flute_qgemm_grouped_glu_blocks_form).
+    A shape both launches refuse raises."""
+    rc = _lib.get().flute_qgemm_grouped_glu_blocks_form(_DTYPE_ID[dtype], num_bits, group_size, E, rows, Tsrc, F, K,
+                                                        template_id, num_sms)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "rows", 2: "blocks"}[rc]
+
+
 def grouped_input_grad_form(E: int, rows: int, N: int, K: int, num_bits: int, group_size: int, template_id: int,
                             num_sms: int = 0, dtype: torch.dtype = torch.float16, pair: bool = False) -> str:
     """The form - "slabs" or "blocks" - the automatic rule takes for a grouped input-gradient launch of `rows` rows over

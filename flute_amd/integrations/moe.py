@@ -7,7 +7,10 @@ decode, prefill and training row counts: the library picks the kernel from the s
 (qgemm_grouped.h) for decode-sized counts, the block form (qgemm_grouped_blocks.h: 128-row blocks of the dense prefill
 kernel) from a mean of 32 - 64 rows per expert on, for the plain and weighted launches of 4- and 2-bit stacks it is eligible
 for (`flute_amd.dev.grouped_form` tells which) - so the modules here need no switch: the down projection and the
-backward's recompute of gate and up take the block form by themselves; the fused GLU launch has no block form yet.  The
+backward's recompute of gate and up take the block form by themselves.  The fused GLU launch has its block form behind an
+entry of its own, `flute_amd.qgemm_grouped_glu_blocks`, and `FluteExperts(fused=True, glu_blocks=...)` opts in: `True` always
+(raises where the stacks are not eligible), `"auto"` where `flute_amd.dev.grouped_glu_blocks_form` says it pays for the step's
+T k rows (shapes only: no host synchronise), `False` - the default - never: the forward is then bit for bit what it was.  The
 backward's two input-gradient launches have their own pair of forms - slabs and, for 4- / 2-bit stacks with K % 256 == 0 from a
 mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input_grad_blocks.h;
 `flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.
@@ -56,11 +59,13 @@ tables that require grad.
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
-from typing import List, Optional, Sequence, Tuple
+import functools
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
 import flute_amd
+import flute_amd.dev
 import flute_amd.utils
 from .base import FluteLinear
 from .learnable import (_swap, qgemm_grouped_glu_learnable, qgemm_grouped_glu_learnable_scales, qgemm_grouped_learnable,
@@ -245,12 +250,23 @@ def _table_of(stack):
     return stack.codebook if _has_codebook(stack) else stack.tables2
 
 
+def _check_glu_blocks(glu_blocks, fused) -> None:
+    if not (glu_blocks is False or glu_blocks is True or (isinstance(glu_blocks, str) and glu_blocks == "auto")):
+        raise ValueError("FluteExperts: glu_blocks is False, True or 'auto', not %r" % (glu_blocks,))
+    if glu_blocks is not False and not fused:
+        raise ValueError("FluteExperts: glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
+
+
 class FluteExperts(torch.nn.Module):
-    """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token."""
+    """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token.
+    `glu_blocks` (with `fused=True`): which kernel runs the fused GLU launch - False: `qgemm_grouped_glu`'s row form at every
+    row count (the default, today's forward bit for bit); True: `qgemm_grouped_glu_blocks` (raises where the stacks are not
+    eligible); "auto": the block launch where `flute_amd.dev.grouped_glu_blocks_form` takes it for the step's T k rows."""
 
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
-                 fused: bool = False, native_routing: bool = False) -> None:
+                 fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False) -> None:
         super().__init__()
+        _check_glu_blocks(glu_blocks, fused)
         if not (gate.num_experts == up.num_experts == down.num_experts):
             raise ValueError("FluteExperts: gate, up and down differ in their number of experts")
         if (gate.in_features, gate.out_features) != (up.in_features, up.out_features) or \
@@ -263,12 +279,14 @@ class FluteExperts(torch.nn.Module):
         self.num_experts = gate.num_experts
         self.fused = bool(fused)
         self.native_routing = bool(native_routing)
+        self.glu_blocks = glu_blocks
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
-                     downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False) -> "FluteExperts":
+                     downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
+                     glu_blocks: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
-                   GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing)
+                   GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -329,8 +347,8 @@ class FluteExperts(torch.nn.Module):
         routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
         the rows past offsets[E] (ids outside [0, E)) as zeros: no silu, no where, no gathered copy of `hidden`."""
         gate, up, down = self.gate, self.up, self.down
-        glu, weighted = self._fused_ops()
         num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
+        glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, token.shape[0], num_sms))
         h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales,
                 _table_of(up), gate.num_bits, gate.group_size, gate.template_id, num_sms,
                 rows=token.to(torch.int32))
@@ -339,10 +357,20 @@ class FluteExperts(torch.nn.Module):
                      down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)
 
-    def _fused_ops(self):
+    def _takes_glu_blocks(self, hidden, rows: int, num_sms: int) -> bool:
+        """Whether this step's fused GLU launch is the block one: `glu_blocks`, "auto" resolved from the shapes alone."""
+        if self.glu_blocks != "auto":
+            return self.glu_blocks
+        gate = self.gate
+        return flute_amd.dev.grouped_glu_blocks_form(self.num_experts, rows, hidden.shape[0], gate.out_features,
+                                                     gate.in_features, gate.num_bits, gate.group_size, gate.template_id,
+                                                     num_sms, hidden.dtype) == "blocks"
+
+    def _fused_ops(self, glu_blocks: bool = False):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
         scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
-        `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops)."""
+        `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
+        `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`)."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
         if has[0] != has[1]:
@@ -350,6 +378,8 @@ class FluteExperts(torch.nn.Module):
         learnable = any(isinstance(m, LearnableGroupedFluteLinear) for m in (gate, up, down))
         glu = qgemm_grouped_glu_learnable if has[0] else \
             qgemm_grouped_glu_learnable_scales if learnable else flute_amd.qgemm_grouped_glu
+        if glu_blocks:
+            glu = flute_amd.qgemm_grouped_glu_blocks if glu is flute_amd.qgemm_grouped_glu else functools.partial(glu, blocks=True)
         weighted = qgemm_grouped_weighted_learnable if has[2] else \
             qgemm_grouped_weighted_learnable_scales if learnable else flute_amd.qgemm_grouped_weighted
         return glu, weighted
@@ -365,8 +395,8 @@ class FluteExperts(torch.nn.Module):
         """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`)."""
         gate, up, down = self.gate, self.up, self.down
         if self.fused:
-            glu, weighted = self._fused_ops()
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
+            glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms))
             h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight,
                     up.scales, _table_of(up), gate.num_bits, gate.group_size, gate.template_id,
                     num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
@@ -384,7 +414,8 @@ class FluteSparseMoeBlock(torch.nn.Module):
     `experts.forward_logits(F.linear(hidden, router_weight), top_k, ...)`, bit for bit.  `router_weight` [E, K] is the
     router's dense matrix; its GEMM stays a dense torch op (E is 8 .. 256 columns: nothing to quantise or fuse), and
     everything behind it is the module's own kernels - with `FluteExperts(fused=True, native_routing=True)` four
-    launches.  `scoring`, `renormalize`, `bias` (the selection bias [E] fp32, kept as a buffer) and `scale` are
+    launches; the experts' `glu_blocks` is honoured as they were built (the block calls their `forward_logits[_limited]`).
+    `scoring`, `renormalize`, `bias` (the selection bias [E] fp32, kept as a buffer) and `scale` are
     `flute_amd.moe_gate`'s.  With `n_group` > 1 the selection is DeepSeek's group-limited one (`flute_amd.moe_gate_limited`:
     the `topk_group` best of `n_group` groups of experts by `group_score` "max" / "top2sum") and forward is
     `experts.forward_logits_limited(...)`, the same number of launches; with n_group == 1 it is exactly the path above."""

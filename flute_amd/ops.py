@@ -425,11 +425,38 @@ def _launch_plain(input, offsets, weight, scales, table2, layer, form=None):
                            scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=(form,))
 
 
+# `_launch_glu`'s form for the block launch behind its own entry (flute_qgemm_grouped_glu_blocks): not one of `_GROUPED_FORMS`,
+# which keep their meaning on `qgemm_grouped_glu` ("blocks" raises there)
+_GLU_BLOCKS = "glu_blocks"
+_FLUTE_ERR_SHAPE, _FLUTE_ERR_NULL = -4, -9       # include/flute_amd.h
+
+
 def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form=None):
     Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
-    return _launch_grouped("qgemm_grouped_glu_ex", (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
-                           gs.shape[1], (R, gs.shape[1]), layer, form=(form,))
+    name, form = ("qgemm_grouped_glu_blocks", ()) if form == _GLU_BLOCKS else ("qgemm_grouped_glu_ex", (form,))
+    return _launch_grouped(name, (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
+                           gs.shape[1], (R, gs.shape[1]), layer, form=form)
+
+
+def _require_glu_blocks(name, input, rows, gate_weight, gate_scales, layer):
+    """Raise ValueError where flute_qgemm_grouped_glu_blocks does not serve the shape.  Host only, before anything is launched:
+    the entry refuses a shape before it looks at a pointer, so it is asked with null pointers (FLUTE_ERR_SHAPE: not served)."""
+    num_bits, group_size, template_id, _ = layer
+    Tsrc = input.shape[0]
+    R = Tsrc if rows is None else rows.shape[0]
+    E, P, K = gate_weight.shape
+    if max(R, Tsrc) >= 2 ** 31:
+        raise ValueError
+    rc = _lib.get().flute_qgemm_grouped_glu_blocks(
+        _DTYPE_ID[input.dtype], num_bits, group_size, E, R, Tsrc, gate_scales.shape[1], K, P, template_id,
+        None, None if rows is None else 1, *(None,) * 8, 0, None)          # (`rows` is compared with null only)
+    if rc == _FLUTE_ERR_SHAPE:
+        raise ValueError(f"flute_amd.{name}: the block form of the fused GLU launch is not eligible for this shape "
+                         "(include/flute_amd.h, flute_qgemm_grouped_glu_blocks: 4 / 2 bits, (K / group_size) % 8 == 0, "
+                         "F % 256 == 0, Tsrc * K * 2 below 2^32 - 16)")
+    if rc not in (0, _FLUTE_ERR_NULL):
+        _lib.check(rc)
 
 
 def _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form=None):
@@ -525,8 +552,8 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     capturable); a native HIP kernel on the current stream (qgemm_grouped.h); equal arguments give equal bits.
     `pos` (`moe_route`'s [Tsrc, k] int32, the inverse of `rows`) is read by the backward only: with it the gradient of the
     gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`.
-    `form` as `qgemm_grouped`'s; this op has no block form yet: None and "rows" are the row form at every row count, "blocks"
-    raises.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)"""
+    `form` as `qgemm_grouped`'s; on this op None and "rows" are the row form at every row count and "blocks" raises: the block
+    form of the launch is an op of its own, `qgemm_grouped_glu_blocks`.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)"""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
@@ -540,8 +567,32 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
                        form)
 
 
+def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
+                             gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
+                             up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                             rows=None, pos=None) -> torch.Tensor:
+    """`qgemm_grouped_glu` on the block form, for prefill and training row counts: the same operands, formula and rounding
+    (include/flute_amd.h, flute_qgemm_grouped_glu_blocks) on 128-row x 256-column blocks of the dense prefill kernel - all of K
+    for gate, then all of K for up, in two fp32 accumulators of the matrix core, a weight dequantised once per 128 rows
+    (qgemm_block2.h, GM = 3).  Same validation, same autograd (the backward recomputes gate and up and never depends on which
+    kernel ran the forward).  Equal arguments give equal bits; the bits equal `qgemm_grouped_glu`'s on exactly representable
+    inputs and may differ elsewhere (another summation order).  A shape the form does not serve raises ValueError before
+    anything is launched; `flute_amd.dev.grouped_glu_blocks_form` tells where the form pays."""
+    _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                          num_bits, group_size, rows)
+    _validate_grouped_glu_pos(input, rows, pos)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_glu_blocks("qgemm_grouped_glu_blocks", input, rows, gate_weight, gate_scales, layer)
+    if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
+        _refuse_stack_grads("qgemm_grouped_glu_blocks", gate_scales, gate_table2, up_scales, up_table2)
+        return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
+                                         gate_table2, up_weight, up_table2, layer, _GLU_BLOCKS)
+    return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
+                       _GLU_BLOCKS)
+
+
 class _GroupedGluFunction(torch.autograd.Function):
-    """`qgemm_grouped_glu` under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
+    """`qgemm_grouped_glu` (and, with form `_GLU_BLOCKS`, `qgemm_grouped_glu_blocks`) under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
     g and u with two plain grouped launches on the gathered rows, forms dg = dh u sigma(g) (1 + g (1 - sigma(g))) and
     du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel.  For
     `integrations.learnable` (the op itself refuses scales that require grad) dS_gate = qgemm_grouped_scale_grad(dg,

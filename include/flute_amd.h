@@ -34,7 +34,8 @@ extern "C" {
  *    the block form of the grouped forward launches: flute_qgemm_grouped_ex, flute_qgemm_grouped_glu_ex, flute_qgemm_grouped_weighted_ex
  *    (the old entries with a trailing `form`), flute_qgemm_grouped_form, flute_grouped_form_t, flute_grouped_mode_t;
  *    the block form of the grouped input gradient: flute_qgemm_grouped_input_grad_ex (the old entry with a trailing `form`),
- *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t
+ *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t;
+ *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -323,7 +324,8 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
  * scale bytes N * (K / group_size) * 2 below 2^32 - 16, the plain and weighted launches.  The automatic rule takes it where
  * it is eligible and the mean rows per expert, T / E, is at least FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS - or
  * FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms - (measured: csrc/api.hip);
- * below that the launch is the row form's, grid included.  flute_qgemm_grouped_glu has no block form: it runs the row form at every count.
+ * below that the launch is the row form's, grid included.  flute_qgemm_grouped_glu has no block form: it runs the row form at every count
+ * (the block form of that launch is an entry of its own, flute_qgemm_grouped_glu_blocks).
  * Refusals, before anything is enqueued: FLUTE_ERR_DTYPE, then the layer checks of flute_dequantize (num_bits 2 / 3 / 4,
  * group_size 32 / 64 / 128 / 256, the template id - 3 bits: TileP 32 only -, N a multiple of the template's column block,
  * K % max(64, group_size) == 0), FLUTE_ERR_SHAPE for P != num_bits * N / 16 or a negative E / T; E == 0 or T == 0 returns
@@ -390,6 +392,48 @@ int flute_qgemm_grouped_glu(int dtype, int num_bits, int group_size, int E, int 
                             int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
                             const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
                             void* H, int num_sms, void* stream);
+
+/* flute_qgemm_grouped_glu on the block form's geometry, for prefill and training row counts: the same operands, the same
+ * formula - H[r, :] = round_T( silu32(g) * u ), w^ = round_T(QM2-pair-lookup * scale), silu32 the one function above - on the
+ * 128-row x 256-column blocks of the dense prefill kernel: a workgroup runs all of K for the gate stack and then all of K
+ * for the up stack into two fp32 accumulators of the matrix core (no K split at all), forms the product in fp32 and rounds
+ * once, at the store; nothing intermediate reaches global memory, no gathered copy of Xsrc is made.  An entry of its own:
+ * flute_qgemm_grouped_glu, flute_qgemm_grouped_glu_ex and flute_qgemm_grouped_form keep their behaviour (the GLU launch
+ * there is the row form at every count and refuses FLUTE_GROUPED_FORM_BLOCKS); a caller opts in by calling this one.
+ * Equal arguments give equal bits.  Its bits may differ from flute_qgemm_grouped_glu's, whose summation order differs,
+ * except on exactly representable inputs (g and u exact in fp32), where they are equal.
+ * Grid: floor((R + 127 E) / 128) row blocks, the most a table over R rows can own, times F / 256 - from (E, R, F) alone.
+ * The host reads neither offsets nor rows: the launch can be captured in a hipGraph, and a replay serves whatever
+ * offsets, rows and Xsrc then hold (same R and Tsrc).  A block past the table's total requests nothing.
+ * offsets: every entry clamped to [0, R]; a malformed table (decreasing, overlapping, a last entry past R) cannot read
+ * or write outside Xsrc / H: rows it names twice have unspecified contents (one of the naming experts' results), a table
+ * whose clamped ranges own more blocks than the grid holds leaves the rows of the surplus blocks unwritten.  Rows no expert
+ * serves are left unwritten (no zero fill).  rows: each entry read only for a sorted row inside its expert's range and
+ * clamped to [0, Tsrc) before it forms an address - a negative or too large entry reads source row 0 or Tsrc - 1.  The rows
+ * of a block at or past its expert's end read no index and no activation (zeros through the bounds of the descriptor over
+ * Xsrc) and are never stored: a NaN or Inf in a source row reaches exactly the sorted rows that name it.
+ * It serves: num_bits 4 / 2, (K / group_size) % 8 == 0, F a multiple of 256, Tsrc * K * 2 and one expert's scale bytes
+ * F * (K / group_size) * 2 below 2^32 - 16, R at most 2^31 - 257, E >= 1, R >= 1.
+ * Refusals, before anything is enqueued or dereferenced, in this order: flute_qgemm_grouped_glu's (dtype, the layer checks,
+ * FLUTE_ERR_SHAPE for P, a negative E / R / Tsrc, Tsrc != R without rows, Tsrc == 0 with rows and R > 0 - the pointer `rows`
+ * is compared with null there and not looked behind); FLUTE_ERR_SHAPE for a shape outside the list above (E == 0 or R == 0
+ * are inside it); E == 0 or R == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL for a null pointer other than rows. */
+int flute_qgemm_grouped_glu_blocks(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                                   int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                                   const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                                   void* H, int num_sms, void* stream);
+
+/* Which of the two GLU launches a caller should take for R sorted rows read out of Tsrc source rows: FLUTE_GROUPED_FORM_BLOCKS
+ * (flute_qgemm_grouped_glu_blocks) where the shape is in its list and the mean rows per expert, R / E, is at least
+ * FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS - or FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (F / 256) is below
+ * num_sms (< 1: 256) -, else FLUTE_GROUPED_FORM_ROWS (flute_qgemm_grouped_glu; E == 0 and R == 0 included), or the negative
+ * error either launch would refuse the layer with.  Host only: no pointers, nothing is enqueued; P is taken as
+ * num_bits * F / 16.  The two constants are measured on the GLU launches (csrc/api.hip): each is the smallest
+ * swept mean from which the block launch is not slower on any swept stack of its kind. */
+#define FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS 16            /* E * (F / 256) >= num_sms: the experts' column blocks fill the chip */
+#define FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL 48    /* fewer workgroups than compute units */
+int flute_qgemm_grouped_glu_blocks_form(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K,
+                                        int template_id, int num_sms);
 
 /* flute_qgemm_grouped with a per-row weight in the epilogue, for the down projection of a mixture-of-experts MLP:
  *   Y[r, :] = round_T( row_weight[r] * acc32 ),   acc32 = the fp32 sum of X[r, :] @ W_e^T,

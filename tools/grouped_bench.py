@@ -77,8 +77,13 @@ flute_amd.qgemm_table_grad (dT2 only) on row ranges the host knows.  Passes per 
 the row form (qgemm_grouped.h): W4G64 fp16 at Mixtral's two projections with 512, 4096 and 8192 routed rows (the counts of
 --mode projection at rows / 2 tokens, so its grouped figure from a build of the parent is the row form's here), the many-expert
 pair of --mode input_grad (which the block form does not serve: 1408 columns, 22 scale groups) and an E = 64 2048 x 2048 stack
-at 4096 rows, one bf16 and one 2-bit line, the weighted down projection, and the gate / up pair as the fused GLU launch (row form
-only) against two plain launches and the elementwise product.  Contenders, alternating in one process, each timed twice by the
+at 4096 rows, one bf16 and one 2-bit line, the weighted down projection, and the gate / up pair read through the routing index as
+three GLU contenders - the fused launch on its row form (qgemm_grouped_glu), on its block form (qgemm_grouped_glu_blocks) and the
+unfused sequence: gather, two plain launches on the automatic form, silu and the product - at Mixtral's pair with 512, 4096 and
+8192 rows, an E = 64 2048 x 2048 pair, one bf16 and one 2-bit line; then the GLU threshold sweep (rows / E in 16 .. 128, row
+form against block form, on two pairs that fill the chip and one that does not) and one forward and one forward + backward
+step of FluteExperts(fused=True, native_routing=True) with glu_blocks False against "auto".  `--only` runs some of the sections
+(profiles/grouped_moe_glu_blocks.json: --only glu glu_sweep glu_module).  Contenders, alternating in one process, each timed twice by the
 tool's method: form="rows", form="blocks", the automatic rule, and a per-expert loop of flute_amd.qgemm on row ranges the host
 knows (the stack's template; the planner picks each call's kernel).  Then the threshold sweep - rows / E in 16 .. 256 on two E = 8 stacks and
 an E = 64 stack, rows against blocks - and the backward step of --mode input_grad at 512 and 4096 tokens with the recompute of
@@ -799,8 +804,7 @@ def child_table_grad(args, device):
 class Forward:
     """`copies` stacks of `experts` packed layers [N, K]; step(i) is one forward over all routed rows on copy i, by `how`:
     "rows" / "blocks" / "auto" - one grouped launch of that form (mode "plain" or "weighted") -, "loop" - flute_amd.qgemm per expert
-    on row ranges the host knows -, "glu" - the fused gate / up launch (N columns each) -, "two_plain" - what it fuses, as two
-    plain automatic launches, silu and the product."""
+    on row ranges the host knows.  (The GLU contenders: GluForward.)"""
 
     def __init__(self, experts, N, K, counts, copies, device, how, mode="plain", bits=BITS, dtype=DTYPE):
         import flute_amd
@@ -809,7 +813,7 @@ class Forward:
         self.num_sms = utils.get_device_num_sms(device)
         self.ws = utils.get_workspace_streamk(device)
         gen = torch.Generator(device=device).manual_seed(1)
-        nst = 2 if how in ("glu", "two_plain") else 1
+        nst = 1
         self.Q = [torch.randint(-2 ** 15, 2 ** 15, (copies, experts, bits * N // 16, K), dtype=torch.int16, device=device,
                                 generator=gen) for _ in range(nst)]
         self.S = [(torch.rand(copies, experts, N, K // G, device=device, generator=gen) * 0.02 + 0.005).to(dtype) for _ in range(nst)]
@@ -836,11 +840,6 @@ class Forward:
                     r0, r1 = self.off_host[e], self.off_host[e + 1]
                     ys.append(fa.qgemm(self.X[r0:r1], Q[e], S[e], self.table, self.table2, self.ws, *a))
             return ys
-        if self.how == "glu":
-            return fa.qgemm_grouped_glu(self.X, self.offsets, Q, S, t2, self.Q[1][c], self.S[1][c], t2, *a)
-        if self.how == "two_plain":
-            g = fa.qgemm_grouped(self.X, self.offsets, Q, S, t2, *a)
-            return torch.nn.functional.silu(g) * fa.qgemm_grouped(self.X, self.offsets, self.Q[1][c], self.S[1][c], t2, *a)
         form = None if self.how == "auto" else self.how
         if self.mode == "weighted":
             return fa.qgemm_grouped_weighted(self.X, self.offsets, Q, S, t2, self.w, *a, form=form)
@@ -848,6 +847,72 @@ class Forward:
 
     def flops(self):
         return 2.0 * sum(self.counts) * self.N * self.K * len(self.Q)
+
+
+class GluForward:
+    """`copies` pairs of gate / up stacks of `experts` packed layers [F, K] and `rows` sorted rows read out of rows / 2 source rows
+    through an index (top-2 routing); step(i) is silu(gate) * up on copy i, by `how`: "rows" - the fused launch, flute_amd.qgemm_grouped_glu
+    (the row form at every count) -, "blocks" - flute_amd.qgemm_grouped_glu_blocks -, "unfused" - the gather, two plain grouped
+    launches on the automatic form, silu and the product.  `weights`: another GluForward whose stacks and activations are shared."""
+
+    def __init__(self, experts, F, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, weights=None):
+        import flute_amd
+        from flute_amd import utils
+        self.fa, self.F, self.K, self.counts, self.how, self.bits, self.experts = flute_amd, F, K, counts, how, bits, experts
+        self.num_sms = utils.get_device_num_sms(device)
+        if weights is None:
+            gen = torch.Generator(device=device).manual_seed(1)
+            R = sum(counts)
+            self.Q = [torch.randint(-2 ** 15, 2 ** 15, (copies, experts, bits * F // 16, K), dtype=torch.int16, device=device,
+                                    generator=gen) for _ in range(2)]
+            self.S = [(torch.rand(copies, experts, F, K // G, device=device, generator=gen) * 0.02 + 0.005).to(dtype) for _ in range(2)]
+            table = torch.randn(2 ** bits, device=device, generator=gen).sort().values.to(dtype)
+            self.tables2 = utils.make_qmap2_from_qmap(table).repeat(experts, 1, 1, 1)
+            self.hidden = torch.randn(max(1, R // TOPK), K, device=device, generator=gen).to(dtype)
+            self.rows = torch.randint(0, self.hidden.shape[0], (R,), device=device, generator=gen).to(torch.int32)
+            off = [0]
+            for c in counts:
+                off.append(off[-1] + c)
+            self.offsets = torch.tensor(off, dtype=torch.int32, device=device)
+        else:
+            for name in ("Q", "S", "tables2", "hidden", "rows", "offsets"):
+                setattr(self, name, getattr(weights, name))
+        self.tid = min(t for (b, t), c in flute_amd.TEMPLATE_CONFIGS.items() if b == bits and c["TileP"] == 32)
+
+    def step(self, i):
+        c = i % self.Q[0].shape[0]
+        fa, a, t2, off = self.fa, (self.bits, G, self.tid, self.num_sms), self.tables2, self.offsets
+        if self.how == "unfused":
+            x = self.hidden[self.rows.long()]
+            return torch.nn.functional.silu(fa.qgemm_grouped(x, off, self.Q[0][c], self.S[0][c], t2, *a)) * \
+                fa.qgemm_grouped(x, off, self.Q[1][c], self.S[1][c], t2, *a)
+        op = fa.qgemm_grouped_glu_blocks if self.how == "blocks" else fa.qgemm_grouped_glu
+        return op(self.hidden, off, self.Q[0][c], self.S[0][c], t2, self.Q[1][c], self.S[1][c], t2, *a, rows=self.rows)
+
+    def flops(self):
+        return 2.0 * sum(self.counts) * self.F * self.K * 2
+
+
+class ModuleStep:
+    """One forward and one backward step of FluteExperts(fused=True, native_routing=True, glu_blocks=...) at `tokens` tokens (top-2)
+    on copy i of step_stacks: the gradient reaches the hidden states (the experts' parameters are frozen)."""
+
+    def __init__(self, stacks, tokens, device, glu_blocks, backward):
+        from flute_amd.integrations import moe
+        self.experts = [moe.FluteExperts(g, u, d, fused=True, native_routing=True, glu_blocks=glu_blocks) for g, u, d in stacks]
+        self.backward = backward
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE).requires_grad_(backward)
+        self.ids = torch.rand(tokens, E, generator=torch.Generator().manual_seed(tokens)).topk(TOPK, dim=1).indices.to(device)
+        w = torch.rand(tokens, TOPK, device=device, generator=gen)
+        self.weights = (w / w.sum(1, keepdim=True)).to(DTYPE)
+        self.dOut = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+
+    def step(self, i):
+        y = self.experts[i % len(self.experts)](self.hidden, self.ids, self.weights)
+        if not self.backward:
+            return y
+        return torch.autograd.grad(y, self.hidden, self.dOut)[0]
 
 
 def even_counts(rows, experts):
@@ -866,6 +931,15 @@ PREFILL_LINES = [("mixtral gate_up", 8, 14336, 4096, r, 4, "float16", "plain") f
                  ("mixtral down", 8, 4096, 14336, 4096, 4, "float16", "weighted"),
                  ("mixtral down", 8, 4096, 14336, 8192, 4, "float16", "weighted")]
 SWEEP_MEANS = (16, 32, 48, 64, 96, 128, 192, 256)
+# (name, experts, F, K, routed rows, bits, dtype): the fused GLU launch on its two forms against the unfused sequence
+GLU_LINES = [("mixtral gate_up pair", 8, 14336, 4096, r, 4, "float16") for r in (512, 4096, 8192)] + \
+            [("many-expert 2048 x 2048 pair", 64, 2048, 2048, 4096, 4, "float16"),
+             ("mixtral gate_up pair", 8, 14336, 4096, 4096, 4, "bfloat16"),
+             ("mixtral gate_up pair", 8, 14336, 4096, 4096, 2, "float16")]
+GLU_SWEEP_MEANS = (16, 32, 48, 64, 96, 128)
+GLU_SWEEP_STACKS = [("mixtral gate_up pair", 8, 14336, 4096), ("many-expert 2048 x 2048 pair", 64, 2048, 2048),   # fill the chip
+                    ("E 8 4096 x 4096 pair", 8, 4096, 4096)]                                                       # 128 workgroups: does not
+PREFILL_SECTIONS = ("forward", "glu", "sweep", "backward", "glu_sweep", "glu_module")
 SWEEP_STACKS = [("mixtral gate_up", 8, 14336, 4096), ("mixtral down", 8, 4096, 14336), ("many-expert 2048 x 2048", 64, 2048, 2048)]
 
 
@@ -901,7 +975,8 @@ def main_prefill(args, device):
                                   "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
 
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    for name, experts, N, K, nrows, bits, dt, mode in PREFILL_LINES:
+    want = lambda section: args.only is None or section in args.only
+    for name, experts, N, K, nrows, bits, dt, mode in (PREFILL_LINES if want("forward") else ()):
         dtype = getattr(torch, dt)
         counts = routing(nrows // 2, seed=nrows // 2) if experts == E else ig_counts(nrows, experts, seed=nrows + experts)
         copies = prefill_copies(experts, N, K, bits)
@@ -930,19 +1005,72 @@ def main_prefill(args, device):
         emit(row)
         del layers
         torch.cuda.empty_cache()
-    # the fused GLU launch (row form at every count) against two plain automatic launches + silu and the product
-    for nrows in (512, 4096):
-        counts = routing(nrows // 2, seed=nrows // 2)
-        copies = prefill_copies(E, 14336, 4096, BITS, stacks=2)
-        layers = {how: Forward(E, 14336, 4096, counts, copies, device, how) for how in ("glu", "two_plain")}
+    # the fused GLU launch through the routing index: its row form, its block form (flute_amd.qgemm_grouped_glu_blocks) and the
+    # unfused sequence - gather, two plain automatic launches, silu and the product
+    def glu_layers(experts, F, K, counts, bits=BITS, dtype=DTYPE):
+        copies = prefill_copies(experts, F, K, bits, stacks=2)
+        first = GluForward(experts, F, K, counts, copies, device, "rows", bits, dtype)
+        layers = {"rows": first}
+        for how in ("blocks", "unfused"):
+            layers[how] = GluForward(experts, F, K, counts, copies, device, how, bits, dtype, weights=first)
+        return layers, copies
+
+    for name, experts, F, K, nrows, bits, dt in (GLU_LINES if want("glu") else ()):
+        dtype = getattr(torch, dt)
+        counts = routing(nrows // 2, seed=nrows // 2) if experts == E else ig_counts(nrows, experts, seed=nrows + experts)
+        layers, copies = glu_layers(experts, F, K, counts, bits, dtype)
+        first = layers["rows"]
+        a, b = layers["blocks"].step(0).float(), first.step(0).float()
+        diff, ref = float((a - b).abs().max()), float(b.abs().max())
         us, spread, replays = time_forms(layers, args)
-        emit({"what": "glu", "shape": "mixtral gate_up pair", "experts": E, "N": 14336, "K": 4096, "rows": sum(counts),
-              "weight_copies": copies, "us": us, "glu_over_two_plain": round(us["glu"] / us["two_plain"], 4), "spread": spread,
-              "replays_us": replays})
-        del layers
+        flop = first.flops()
+        emit({"what": "glu", "shape": name, "bits": bits, "dtype": dt, "experts": experts, "F": F, "K": K, "rows": sum(counts),
+              "source_rows": first.hidden.shape[0], "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+              "auto_form": dev.grouped_glu_blocks_form(experts, sum(counts), first.hidden.shape[0], F, K, bits, G, first.tid,
+                                                       first.num_sms, dtype),
+              "us": us, "blocks_over_rows": round(us["blocks"] / us["rows"], 4),
+              "blocks_over_unfused": round(us["blocks"] / us["unfused"], 4),
+              "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()}, "spread": spread, "flop": flop,
+              "max_abs_diff_blocks_vs_rows": diff, "max_abs_rows": ref, "replays_us": replays})
+        del layers, first, a, b
+        torch.cuda.empty_cache()
+    # the GLU threshold sweep: rows / E on both sides of the rule, the row form against the block form, even counts and a routed draw
+    for name, experts, F, K in (GLU_SWEEP_STACKS if want("glu_sweep") else ()):
+        for mean in GLU_SWEEP_MEANS:
+            for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                        ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                layers, copies = glu_layers(experts, F, K, counts)
+                layers.pop("unfused")
+                first = layers["rows"]
+                us, spread, replays = time_forms(layers, args)
+                emit({"what": "glu threshold sweep", "shape": name, "experts": experts, "F": F, "K": K, "mean_rows_per_expert": mean,
+                      "counts": spread_name, "counts_min_max": [min(counts), max(counts)], "rows": sum(counts), "us": us,
+                      "fills_the_chip": bool(experts * (F // 256) >= first.num_sms),
+                      "blocks_over_rows": round(us["blocks"] / us["rows"], 4), "spread": spread,
+                      "auto_form": dev.grouped_glu_blocks_form(experts, sum(counts), first.hidden.shape[0], F, K, BITS, G, first.tid,
+                                                               first.num_sms), "replays_us": replays})
+                del layers, first
+                torch.cuda.empty_cache()
+    # one forward and one forward + backward step of FluteExperts(fused=True, native_routing=True): glu_blocks False against "auto"
+    if want("glu_module"):
+        copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
+        stacks = step_stacks(copies, device)
+        for tokens in (512, 4096):
+            layers = {}
+            for backward in (False, True):
+                for glu_blocks in (False, "auto"):
+                    layers[("forward+backward" if backward else "forward") + (" auto" if glu_blocks else " rows")] = \
+                        ModuleStep(stacks, tokens, device, glu_blocks, backward)
+            us, spread, replays = time_forms(layers, args)
+            emit({"what": "glu module step", "tokens": tokens, "rows": tokens * TOPK, "experts": E, "top_k": TOPK,
+                  "weight_copies": copies, "us": us, "forward_auto_over_rows": round(us["forward auto"] / us["forward rows"], 4),
+                  "step_auto_over_rows": round(us["forward+backward auto"] / us["forward+backward rows"], 4), "spread": spread,
+                  "replays_us": replays})
+            del layers
+        del stacks
         torch.cuda.empty_cache()
     # the threshold sweep: rows / E on both sides of the rule, rows against blocks, even counts and a routed draw
-    for name, experts, N, K in SWEEP_STACKS:
+    for name, experts, N, K in (SWEEP_STACKS if want("sweep") else ()):
         copies = prefill_copies(experts, N, K, BITS)
         for mean in SWEEP_MEANS:
             for spread_name, counts in (("even", even_counts(mean * experts, experts)),
@@ -958,6 +1086,9 @@ def main_prefill(args, device):
                 del layers
                 torch.cuda.empty_cache()
     # one backward step of FluteExperts(fused=True, native_routing=True): the recompute on the row form and on the automatic rule
+    if not want("backward"):
+        print("wrote", args.out)
+        return
     copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
     stacks = step_stacks(copies, device)
     for tokens in (512, 4096):
@@ -1144,6 +1275,8 @@ def main():
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
+    ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS, default=None,
+                    help="--mode prefill: the sections to run (default: all) - " + ", ".join(PREFILL_SECTIONS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
