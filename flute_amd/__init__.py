@@ -44,6 +44,10 @@ grouped_pair_grad_to_table_grad = ops.grouped_pair_grad_to_table_grad
 # counting sort on the device), and the sorted rows of the down projection summed per token in fp32 with one rounding
 moe_route = ops.moe_route
 moe_combine = ops.moe_combine
+# the two streams of the fused GLU launch's backward that are not GEMMs, one launch each (the ops' `native_glu_grad=True` runs them):
+# the row gather, moe_combine's transpose, and (dg, du) from g, u and the gradient of silu(g) u
+moe_gather = ops.moe_gather
+swiglu_grad = ops.swiglu_grad
 # the gating in front of them: router logits [T, E] -> (ids, weights) with a defined tie order, one launch; and the same launch
 # carried on through moe_route's sort: from logits to every routing array
 moe_gate = ops.moe_gate

@@ -79,6 +79,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_table_grad_scratch_bytes": (c_size_t, [c_int] * 5),
     "flute_moe_route": (c_int, [c_int] * 5 + [c_void_p] * 7 + [c_void_p]),
     "flute_moe_combine": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
+    "flute_swiglu_grad": (c_int, [c_int] * 4 + [c_void_p] * 6 + [c_void_p]),
+    "flute_moe_gather": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
     "flute_moe_gate": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 4 + [c_void_p]),
     "flute_moe_gate_route": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 9 + [c_void_p]),
     "flute_moe_gate_limited": (c_int, [c_int] * 9 + [c_float] + [c_void_p] * 4 + [c_void_p]),

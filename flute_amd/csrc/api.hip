@@ -2095,6 +2095,26 @@ int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, cons
     return moe_combine_dispatch(dtype, T, k, E, N, Y, pos, offsets, out, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_swiglu_grad(int dtype, int R, int F, int E, const void* g, const void* u, const void* dh, const int32_t* offsets,
+                      void* dg, void* du, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    if (R < 0 || F < 0 || F % 8 || (offsets && E < 0)) return FLUTE_ERR_SHAPE;
+    if (R > 0 && F > 0 && row_stream_grid(R, F) == 0) return FLUTE_ERR_SHAPE;
+    if (R == 0 || F == 0) return FLUTE_OK;
+    if (!g || !u || !dh || !dg || !du) return FLUTE_ERR_NULL;
+    return swiglu_grad_dispatch(dtype, R, F, E, g, u, dh, offsets, dg, du, reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_moe_gather(int dtype, int R, int Tsrc, int K, int E, const void* X, const int32_t* rows, const int32_t* offsets,
+                     void* out, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    if (R < 0 || Tsrc < 0 || K < 0 || K % 8 || (offsets && E < 0)) return FLUTE_ERR_SHAPE;
+    if (R > 0 && K > 0 && (Tsrc == 0 || row_stream_grid(R, K) == 0)) return FLUTE_ERR_SHAPE;
+    if (R == 0 || K == 0) return FLUTE_OK;
+    if (!X || !rows || !out) return FLUTE_ERR_NULL;
+    return moe_gather_dispatch(R, Tsrc, K, E, X, rows, offsets, out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -163,6 +163,14 @@ int moe_gate_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* gr
 unsigned moe_combine_grid(int T, int N);
 int moe_combine_dispatch(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
                          void* out, hipStream_t stream);
+// the two streams of the fused SwiGLU launch's backward (swiglu_grad.hip): dg, du [R, F] from g, u, dh in fp32 (flute_swiglu_grad's
+// formula) and out[r] = X[clamp(rows[r])], a copy; offsets null: every row served, else the rows from clamp(offsets[E]) on are zeros
+// and nothing of theirs is read.  One grid rule for both: rows x chunks of 1024 columns (0: it does not fit)
+unsigned row_stream_grid(int R, int width);
+int swiglu_grad_dispatch(int dtype, int R, int F, int E, const void* g, const void* u, const void* dh, const int32_t* offsets,
+                         void* dg, void* du, hipStream_t stream);
+int moe_gather_dispatch(int R, int Tsrc, int K, int E, const void* X, const int32_t* rows, const int32_t* offsets, void* out,
+                        hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

@@ -325,24 +325,26 @@ def _glu_form(blocks, name, input, rows, gate_weight, gate_scales, layer):
 def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
                                        gate_scales: torch.Tensor, gate_table2: torch.Tensor, up_weight: torch.Tensor,
                                        up_scales: torch.Tensor, up_table2: torch.Tensor, num_bits: int, group_size: int,
-                                       template_id: int, num_sms=None, rows=None, pos=None, blocks=False) -> torch.Tensor:
+                                       template_id: int, num_sms=None, rows=None, pos=None, blocks=False,
+                                       native_glu_grad: bool = False) -> torch.Tensor:
     """`flute_amd.qgemm_grouped_glu`, differentiable with respect to `input`, `gate_scales` and `up_scales`.  The forward is
     the op's launch; the backward is the op's own (gate and up recomputed, dg and du in fp32, the pair-form input gradient)
     plus one `qgemm_grouped_scale_grad` launch per stack on the gathered rows.  The tables requiring grad are refused.
     `blocks=True`: the forward is `flute_amd.qgemm_grouped_glu_blocks`' launch (a shape it does not serve raises); the
-    backward is the same."""
+    backward is the same.  `native_glu_grad` as the op's: the backward's gather and dg, du from `moe_gather` and `swiglu_grad`."""
     _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                                num_bits, group_size, rows)
     _refuse_table_grad("qgemm_grouped_glu_learnable_scales", gate_table2, up_table2)
     if not _ops._records_grad(input, gate_scales, up_scales):
         return _glu_op(blocks)(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
-                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
+                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos,
+                               native_glu_grad=native_glu_grad)
     _ops._validate_grouped_glu_pos(input, rows, pos)
     layer = (num_bits, group_size, template_id, num_sms)
     return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
                                           gate_table2, up_weight, up_table2, layer,
                                           _glu_form(blocks, "qgemm_grouped_glu_learnable_scales", input, rows, gate_weight,
-                                                    gate_scales, layer))
+                                                    gate_scales, layer), bool(native_glu_grad))
 
 
 # ---- the experts' lookup tables: the same three functions with the codebook slot open.  `codebook` is a stack's fp32
@@ -394,21 +396,23 @@ def qgemm_grouped_weighted_learnable(input: torch.Tensor, offsets: torch.Tensor,
 def qgemm_grouped_glu_learnable(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
                                 gate_scales: torch.Tensor, gate_codebook: torch.Tensor, up_weight: torch.Tensor,
                                 up_scales: torch.Tensor, up_codebook: torch.Tensor, num_bits: int, group_size: int,
-                                template_id: int, num_sms=None, rows=None, pos=None, blocks=False) -> torch.Tensor:
+                                template_id: int, num_sms=None, rows=None, pos=None, blocks=False,
+                                native_glu_grad: bool = False) -> torch.Tensor:
     """`flute_amd.qgemm_grouped_glu`, differentiable with respect to `input`, both stacks' scales and both stacks' fp32
     master codebooks: `qgemm_grouped_glu_learnable_scales` with the table gradients from
     `qgemm_grouped_table_grad(dg, x_sorted, ...)` for gate and `(du, x_sorted, ...)` for up, one launch per stack.
-    `blocks` as there."""
+    `blocks` and `native_glu_grad` as there."""
     gate_table2 = _codebook_stack("qgemm_grouped_glu_learnable", gate_codebook, num_bits, input.dtype, gate_scales)
     up_table2 = _codebook_stack("qgemm_grouped_glu_learnable", up_codebook, num_bits, input.dtype, up_scales)
     _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                                num_bits, group_size, rows)
     if not _ops._records_grad(input, gate_scales, up_scales, gate_codebook, up_codebook):
         return _glu_op(blocks)(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
-                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos)
+                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos,
+                               native_glu_grad=native_glu_grad)
     _ops._validate_grouped_glu_pos(input, rows, pos)
     layer = (num_bits, group_size, template_id, num_sms)
     return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, gate_codebook, up_codebook, rows, pos, offsets,
                                           gate_weight, gate_table2, up_weight, up_table2, layer,
                                           _glu_form(blocks, "qgemm_grouped_glu_learnable", input, rows, gate_weight,
-                                                    gate_scales, layer))
+                                                    gate_scales, layer), bool(native_glu_grad))

@@ -261,12 +261,18 @@ class FluteExperts(torch.nn.Module):
     """down(silu(gate(x)) * up(x)) over the experts each token was routed to, weighted and summed per token.
     `glu_blocks` (with `fused=True`): which kernel runs the fused GLU launch - False: `qgemm_grouped_glu`'s row form at every
     row count (the default, today's forward bit for bit); True: `qgemm_grouped_glu_blocks` (raises where the stacks are not
-    eligible); "auto": the block launch where `flute_amd.dev.grouped_glu_blocks_form` takes it for the step's T k rows."""
+    eligible); "auto": the block launch where `flute_amd.dev.grouped_glu_blocks_form` takes it for the step's T k rows.
+    `native_glu_grad` (with `fused=True`): the ops' keyword of that name - the backward of the fused GLU launch gathers its rows
+    with `moe_gather` and forms dg, du with `swiglu_grad` (two HIP launches) where the default runs torch ops; the forward's bits
+    are the same either way, the backward's differ within `flute_swiglu_grad`'s error account."""
 
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
-                 fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False) -> None:
+                 fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
+                 native_glu_grad: bool = False) -> None:
         super().__init__()
         _check_glu_blocks(glu_blocks, fused)
+        if native_glu_grad and not fused:
+            raise ValueError("FluteExperts: native_glu_grad selects the backward of the fused GLU launch and needs fused=True")
         if not (gate.num_experts == up.num_experts == down.num_experts):
             raise ValueError("FluteExperts: gate, up and down differ in their number of experts")
         if (gate.in_features, gate.out_features) != (up.in_features, up.out_features) or \
@@ -280,13 +286,15 @@ class FluteExperts(torch.nn.Module):
         self.fused = bool(fused)
         self.native_routing = bool(native_routing)
         self.glu_blocks = glu_blocks
+        self.native_glu_grad = bool(native_glu_grad)
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
-                     glu_blocks: Union[bool, str] = False) -> "FluteExperts":
+                     glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
-                   GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks)
+                   GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
+                   native_glu_grad=native_glu_grad)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -370,7 +378,8 @@ class FluteExperts(torch.nn.Module):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
         scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
         `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
-        `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`)."""
+        `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`).
+        The module's `native_glu_grad` rides on whichever GLU entry that is."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
         if has[0] != has[1]:
@@ -380,6 +389,8 @@ class FluteExperts(torch.nn.Module):
             qgemm_grouped_glu_learnable_scales if learnable else flute_amd.qgemm_grouped_glu
         if glu_blocks:
             glu = flute_amd.qgemm_grouped_glu_blocks if glu is flute_amd.qgemm_grouped_glu else functools.partial(glu, blocks=True)
+        if self.native_glu_grad:
+            glu = functools.partial(glu, native_glu_grad=True)
         weighted = qgemm_grouped_weighted_learnable if has[2] else \
             qgemm_grouped_weighted_learnable_scales if learnable else flute_amd.qgemm_grouped_weighted
         return glu, weighted

@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gather`, `swiglu_grad`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
 `moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
 routing weights and router logits: when grad mode is on and such an input requires grad they run through a
 `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`, `moe_combine`
@@ -542,7 +542,7 @@ def _validate_grouped_glu_pos(input, rows, pos):
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                      rows=None, pos=None, form=None) -> torch.Tensor:
+                      rows=None, pos=None, form=None, native_glu_grad: bool = False) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
@@ -553,7 +553,10 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     `pos` (`moe_route`'s [Tsrc, k] int32, the inverse of `rows`) is read by the backward only: with it the gradient of the
     gather is `moe_combine(dx_sorted, pos, offsets)` - fp32, one rounding, equal bits at every k - without it `index_add_`.
     `form` as `qgemm_grouped`'s; on this op None and "rows" are the row form at every row count and "blocks" raises: the block
-    form of the launch is an op of its own, `qgemm_grouped_glu_blocks`.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)"""
+    form of the launch is an op of its own, `qgemm_grouped_glu_blocks`.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)
+    `native_glu_grad` is read by the backward only: False (the default) forms the gather and dg, du with torch ops, bit for bit
+    as before; True runs `moe_gather` and `swiglu_grad` in their place (two launches, g and u never widened to fp32 tensors),
+    whose bits differ from the torch chain's within `flute_swiglu_grad`'s error account.  The forward's bits do not depend on it."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
@@ -562,7 +565,7 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer, form)
+                                         gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad))
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        form)
 
@@ -570,14 +573,14 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
 def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                              gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                              up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                             rows=None, pos=None) -> torch.Tensor:
+                             rows=None, pos=None, native_glu_grad: bool = False) -> torch.Tensor:
     """`qgemm_grouped_glu` on the block form, for prefill and training row counts: the same operands, formula and rounding
     (include/flute_amd.h, flute_qgemm_grouped_glu_blocks) on 128-row x 256-column blocks of the dense prefill kernel - all of K
     for gate, then all of K for up, in two fp32 accumulators of the matrix core, a weight dequantised once per 128 rows
     (qgemm_block2.h, GM = 3).  Same validation, same autograd (the backward recomputes gate and up and never depends on which
     kernel ran the forward).  Equal arguments give equal bits; the bits equal `qgemm_grouped_glu`'s on exactly representable
     inputs and may differ elsewhere (another summation order).  A shape the form does not serve raises ValueError before
-    anything is launched; `flute_amd.dev.grouped_glu_blocks_form` tells where the form pays."""
+    anything is launched; `flute_amd.dev.grouped_glu_blocks_form` tells where the form pays.  `native_glu_grad` as there."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
@@ -586,7 +589,7 @@ def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_we
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu_blocks", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer, _GLU_BLOCKS)
+                                         gate_table2, up_weight, up_table2, layer, _GLU_BLOCKS, bool(native_glu_grad))
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        _GLU_BLOCKS)
 
@@ -601,8 +604,9 @@ class _GroupedGluFunction(torch.autograd.Function):
     `_grouped_table_grads` on the same operands."""
 
     @staticmethod
-    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None):
+    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None, native=False):
         ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
+        ctx.native = native
         out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form)
         ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
         ctx.has = (rows is not None, pos is not None)
@@ -616,25 +620,34 @@ class _GroupedGluFunction(torch.autograd.Function):
         rows = index[0] if ctx.has[0] else None
         pos = index[1] if ctx.has[1] else None
         dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
-                                              want_input_grad=ctx.needs_input_grad[0])
+                                              want_input_grad=ctx.needs_input_grad[0], native=ctx.native)
         want = ctx.needs_input_grad
         d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
         d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
-        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 9
+        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 10
 
 
-def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad):
+def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad,
+                          native=False):
     """The backward of the fused GLU launch: (d input, x_sorted, dg, du) - the gathered rows and the two gradients in T
     that the pair-form launch reads, which the scale gradients read too.  `want_input_grad` false skips the pair-form
-    launch and the sum over a token's slots (d input: None)."""
+    launch and the sum over a token's slots (d input: None).  `native` (the ops' `native_glu_grad`): the gather is
+    `moe_gather` and dg, du are `swiglu_grad` on g and u as the plain launches wrote them, in T - two launches in place of
+    the torch chains, whose bits (torch's sigmoid) they do not promise; rows no expert serves are zeros in x, dg and du."""
     Tsrc = input.shape[0]
-    x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
-    g = _launch_plain(x, offsets, gw, gs, gt, layer).float()
-    u = _launch_plain(x, offsets, uw, us, ut, layer).float()
-    dh = grad_output.float()
-    sig = torch.sigmoid(g)
-    dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
-    du = (dh * (g * sig)).to(input.dtype)
+    if native:
+        x = input if rows is None else moe_gather(input, rows, offsets)
+        g = _launch_plain(x, offsets, gw, gs, gt, layer)
+        u = _launch_plain(x, offsets, uw, us, ut, layer)
+        dg, du = swiglu_grad(g, u, grad_output, offsets)
+    else:
+        x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
+        g = _launch_plain(x, offsets, gw, gs, gt, layer).float()
+        u = _launch_plain(x, offsets, uw, us, ut, layer).float()
+        dh = grad_output.float()
+        sig = torch.sigmoid(g)
+        dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)
+        du = (dh * (g * sig)).to(input.dtype)
     if not want_input_grad:
         return None, x, dg, du
     dx = qgemm_grouped_input_grad(dg, offsets, gw, gs, gt, *layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
@@ -1188,4 +1201,94 @@ def _moe_combine_call(y, pos, offsets):
         _lib.check(_lib.get().flute_moe_combine(
             _DTYPE_ID[yc.dtype], T, k, off.shape[0] - 1, N, yc.data_ptr(), p.data_ptr(), off.data_ptr(), out.data_ptr(),
             _stream_ptr(dev)))
+    return out
+
+
+def _validate_row_stream_offsets(offsets):
+    if offsets is None:
+        return
+    if offsets.ndim != 1:
+        raise ValueError
+    if offsets.dtype != torch.int32:
+        raise TypeError
+    if offsets.shape[0] < 1:
+        raise ValueError
+
+
+def _refuse_grad(name, *tensors):
+    if _records_grad(*tensors):
+        raise RuntimeError(f"flute_amd.{name} is not differentiable: it is a piece of a backward (call it on detached tensors "
+                           "or under torch.no_grad())")
+
+
+def _validate_swiglu_grad(g, u, grad_output, offsets):
+    if not all([g.ndim == 2, u.ndim == 2, grad_output.ndim == 2]):
+        raise ValueError
+    if g.dtype not in _DTYPE_ID or u.dtype != g.dtype or grad_output.dtype != g.dtype:
+        raise TypeError
+    _validate_row_stream_offsets(offsets)
+    if tuple(u.shape) != tuple(g.shape) or tuple(grad_output.shape) != tuple(g.shape) or g.shape[1] % 8 != 0:
+        raise ValueError
+    if g.shape[0] >= 2 ** 31:
+        raise ValueError
+
+
+def swiglu_grad(g: torch.Tensor, u: torch.Tensor, grad_output: torch.Tensor, offsets=None):
+    """The SwiGLU derivative of the fused GLU launch's backward in one launch: (dg, du) with dg = grad_output u ds(g),
+    ds(g) = sigma(g) (1 + g (1 - sigma(g))), and du = grad_output silu(g) - in fp32, in the order include/flute_amd.h states at
+    flute_swiglu_grad, one rounding per output.  `g`, `u`, `grad_output` [R, F] of one 16-bit type, F % 8 == 0.  `offsets`
+    (an int32 CUDA tensor of E + 1 entries, `moe_route`'s) or None: the rows from offsets[E] on are written as zeros and
+    never read; None serves every row.  Every element of both results is written.  Not differentiable (it is a piece of a
+    backward: an argument that requires grad, with grad mode on, raises RuntimeError).  No host synchronise (capturable); a
+    native HIP kernel on the current stream (swiglu_grad.hip); equal arguments give equal bits."""
+    _validate_swiglu_grad(g, u, grad_output, offsets)
+    _refuse_grad("swiglu_grad", g, u, grad_output)
+    dev = g.device
+    if not all(t.is_cuda and t.device == dev for t in (g, u, grad_output, offsets) if t is not None):
+        raise RuntimeError("flute_amd.swiglu_grad: all tensors must live on the same GPU")
+    R, F = g.shape
+    gc, uc, dh = _abi_tensor(g), _abi_tensor(u), _abi_tensor(grad_output)
+    off = None if offsets is None else _abi_tensor(offsets)
+    dg = torch.empty((R, F), dtype=g.dtype, device=dev)
+    du = torch.empty((R, F), dtype=g.dtype, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_swiglu_grad(
+            _DTYPE_ID[g.dtype], R, F, 0 if off is None else off.shape[0] - 1, gc.data_ptr(), uc.data_ptr(), dh.data_ptr(),
+            None if off is None else off.data_ptr(), dg.data_ptr(), du.data_ptr(), _stream_ptr(dev)))
+    return dg, du
+
+
+def _validate_moe_gather(input, rows, offsets):
+    if input.ndim != 2 or rows.ndim != 1:
+        raise ValueError
+    if input.dtype not in _DTYPE_ID or rows.dtype != torch.int32:
+        raise TypeError
+    _validate_row_stream_offsets(offsets)
+    if input.shape[1] % 8 != 0 or (input.shape[0] == 0 and rows.shape[0] > 0):
+        raise ValueError
+    if max(input.shape[0], rows.shape[0]) >= 2 ** 31:
+        raise ValueError
+
+
+def moe_gather(input: torch.Tensor, rows: torch.Tensor, offsets=None) -> torch.Tensor:
+    """The row gather of a mixture-of-experts step in one launch, the transpose of `moe_combine`:
+    out[r] = input[clamp(rows[r], 0, Tsrc - 1)].  `input` [Tsrc, K] of a 16-bit type, K % 8 == 0, `rows` an int32 CUDA
+    tensor of R entries (`moe_route`'s); `offsets` as `swiglu_grad`'s: the rows from offsets[E] on are zeros and their
+    `rows[r]` is never read.  A copy: a served row is bit for bit `input.index_select`'s.  Not differentiable (an `input`
+    that requires grad, with grad mode on, raises RuntimeError).  No host synchronise (capturable); a native HIP kernel
+    on the current stream (swiglu_grad.hip)."""
+    _validate_moe_gather(input, rows, offsets)
+    _refuse_grad("moe_gather", input)
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in (input, rows, offsets) if t is not None):
+        raise RuntimeError("flute_amd.moe_gather: all tensors must live on the same GPU")
+    Tsrc, K = input.shape
+    R = rows.shape[0]
+    x, rw = _abi_tensor(input), _abi_tensor(rows)
+    off = None if offsets is None else _abi_tensor(offsets)
+    out = torch.empty((R, K), dtype=input.dtype, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_moe_gather(
+            _DTYPE_ID[input.dtype], R, Tsrc, K, 0 if off is None else off.shape[0] - 1, x.data_ptr(), rw.data_ptr(),
+            None if off is None else off.data_ptr(), out.data_ptr(), _stream_ptr(dev)))
     return out

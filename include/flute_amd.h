@@ -36,6 +36,7 @@ extern "C" {
  *    the block form of the grouped input gradient: flute_qgemm_grouped_input_grad_ex (the old entry with a trailing `form`),
  *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t;
  *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
+ *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -717,6 +718,57 @@ int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_gro
  * FLUTE_ERR_NULL (offsets, out; Y and pos unless k == 0 - with k == 0 the launch writes out as zeros). */
 int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
                       void* out, void* stream);
+
+/* The SwiGLU derivative of the fused GLU launch's backward: from g, u (the recomputed gate and up products) and dh (the gradient
+ * of h = silu(g) u), all [R, F] T, contiguous, F % 8 == 0, the gradients dg, du [R, F] T.  Per element, in fp32, every operation
+ * rounded once, in this order (no contraction into an fma), ONE rounding to T per output (to +-inf, not to 65504):
+ *   d   = 1 + expf(-g)
+ *   sl  = g / d                          (silu32, csrc/silu32.h: the forward's function, the same bits from the same g)
+ *   sig = 1 / d
+ *   ds  = sig * (1 + g * (1 - sig))
+ *   dg  = round_T((dh * u) * ds)
+ *   du  = round_T(dh * sl)
+ * The contract is the formula: no selects, no special cases.  Every finite g of either type gives finite ds and sl - where expf(-g)
+ * overflows (g <= -89; g = -65504, g = -3.39e38) d = inf, sig = +0, sl = -0 and ds = +0 * (1 + g) = -0; where it vanishes against
+ * the 1 (g >= 18; g = +65504, g = +3.39e38) d = 1, sig = 1, 1 - sig = 0, sl = g and ds = 1.  A non-finite g, u or dh gives what IEEE
+ * arithmetic gives for that element and touches no other element.
+ * offsets [E + 1] int32 (device memory) or NULL.  NULL: every row is served and E is ignored.  Otherwise
+ * served = clamp(offsets[E], 0, R), read on the device, and the rows at or past `served` are written as +0 in both outputs while
+ * their g, u and dh are never read (the plain launches leave those rows unwritten).  Every element of dg and du is written in
+ * either case.  The host reads no operand; the grid follows from (R, F) alone (hipGraph-capturable).  A pure stream, one lane per
+ * 8 columns of one row: 10 bytes per element (csrc/swiglu_grad.hip).  Equal arguments give equal bits.
+ *
+ * Error account, against the formula in exact arithmetic on the same 16-bit inputs, to first order.  eps = 2^-24 is fp32's unit
+ * roundoff and u_T the unit roundoff of T (2^-11 fp16, 2^-8 bf16); expf is within 1 ulp (2 eps relative); |g| <= 88 (silu32.h's
+ * range), no fp32 intermediate subnormal and the result normal in T.
+ *   sl: silu32.h's count, 2 eps + eps + eps = 4 eps = 2^-22.  du adds the fp32 product (eps) and the rounding to T:
+ *       |du - du_ref| <= (u_T + eps_s) |du_ref|,  eps_s = 2^-21 (silu32.h's constant, which covers 5 eps).
+ *   ds: sig = 1 / d carries 4 eps relative (expf 2, the sum 1, the quotient 1).  1 - sig then carries 4 eps sig + eps (1 - sig)
+ *       absolute, g (1 - sig) that times |g| plus its own eps, the sum with 1 one more eps of its value, and the product with sig
+ *       sig's 4 eps and one more.  With sig <= 1, sig + (1 - sig) = 1 and |ds_ref| <= 1.1:
+ *       |ds - ds_ref| <= eps (4 |g| + 6 |ds_ref|) <= 6.6 eps (1 + |g|).
+ *   dg: dh * u (eps; exact for fp16) and the product with ds (eps) add 2 eps |ds_ref| <= 2.2 eps: 8.8 eps (1 + |g|) |dh u| = 4.4 * 2^-23
+ *       (1 + |g|) |dh u| before the rounding to T, which adds u_T of the value.  With the constant rounded up for the second-order terms
+ *       |dg - dg_ref| <= u_T |dg_ref| + c * 2^-23 * (1 + |g|) * |dh * u|,  c = 5.
+ *       (ds_ref passes through zero at g = -1.278..: a bound relative to dg_ref alone does not exist.  Outside |g| <= 88 ds and ds_ref
+ *       are both within 2^-120 of 0 or both of 1, so the bound holds there too.)
+ * Refusals in this order, before anything is enqueued and before a required pointer is looked at: FLUTE_ERR_DTYPE; FLUTE_ERR_SHAPE
+ * (a negative R or F, a negative E with offsets given, F % 8, R * ceil(F / 1024) above 2^31 - 1); R == 0 or F == 0 returns FLUTE_OK
+ * without a launch; then FLUTE_ERR_NULL (g, u, dh, dg, du). */
+int flute_swiglu_grad(int dtype, int R, int F, int E, const void* g, const void* u, const void* dh, const int32_t* offsets,
+                      void* dg, void* du, void* stream);
+
+/* The row gather in front of the backward's recompute, the transpose of flute_moe_combine: X [Tsrc, K] T, rows [R] int32
+ * (flute_moe_route's), K % 8 == 0, out [R, K] T with
+ *   out[r, :] = X[clamp(rows[r], 0, Tsrc - 1), :]   for r < served;   +0 for r >= served, whose rows[r] is never read
+ * served as flute_swiglu_grad's (offsets NULL: R, and E is ignored).  A copy of 16-bit patterns: a served row is bit for bit the row
+ * it names, NaN payloads included.  Every element of out is written.  The host reads neither rows nor offsets; the grid follows
+ * from (R, K) alone (hipGraph-capturable).  One lane per 16 bytes (csrc/swiglu_grad.hip).
+ * Refusals in this order: FLUTE_ERR_DTYPE; FLUTE_ERR_SHAPE (a negative R, Tsrc or K, a negative E with offsets given, K % 8,
+ * Tsrc == 0 with R > 0 and K > 0, R * ceil(K / 1024) above 2^31 - 1); R == 0 or K == 0 returns FLUTE_OK without a launch; then
+ * FLUTE_ERR_NULL (X, rows, out). */
+int flute_moe_gather(int dtype, int R, int Tsrc, int K, int E, const void* X, const int32_t* rows, const int32_t* offsets,
+                     void* out, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */

@@ -5,7 +5,7 @@
     python tools/grouped_bench.py --mode step [--processes 3] [--out profiles/grouped_moe_routing.json]
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
-    python tools/grouped_bench.py --mode input_grad [--out profiles/grouped_moe_input_grad_blocks.json]
+    python tools/grouped_bench.py --mode input_grad [--only-swiglu-grad] [--out profiles/grouped_moe_input_grad_blocks.json]
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
@@ -62,7 +62,11 @@ spread.  Then the threshold sweep - rows / E in 16 .. 256 on two E = 8 stacks an
 counts and a routed draw - and one whole backward step of FluteExperts(fused=True, native_routing=True) at 512 and 4096 tokens
 with its two input-gradient launches (down's with the routing weight in its epilogue, the pair form over gate and up) on the
 slab form and on the automatic rule.  (profiles/grouped_moe_input_grad.json is the slab form's earlier record: three processes,
-grouped against loop, and the step split into its launches.)
+grouped against loop, and the step split into its launches.)  Its last section, which `--only-swiglu-grad` runs alone, is the
+same step with `native_glu_grad` off and on (BackwardStep(native=...)): the gather in front of the recompute and the part
+`elementwise_dg_du` as torch op chains - the default backward's arithmetic - against flute_amd.moe_gather and flute_amd.swiglu_grad,
+per part and for the whole step at 512 and 4096 tokens, next to one yardstick of the same run: a `copy_` of a 16-bit tensor of
+2.5 R F elements, the 10 bytes per element of [R, F] that swiglu_grad moves.  It goes to profiles/grouped_moe_swiglu_grad.json.
 
 --mode scale_grad times the grouped scale-gradient kernel (param_grad.hip), dS [E, N, K / g] of a stack in one launch,
 by --mode input_grad's method at its six shape / row-count lines, against a per-expert loop of flute_amd.qgemm_scale_grad on
@@ -618,10 +622,11 @@ class BackwardStep:
     shapes), by hand, so that each can be timed alone: `part` selects one, None runs them in the backward's order."""
     PARTS = ("down_input_grad", "recompute_gate_up", "elementwise_dg_du", "pair_input_grad", "moe_combine")
 
-    def __init__(self, stacks, tokens, device, part=None, form=None, ig_form=None):
+    def __init__(self, stacks, tokens, device, part=None, form=None, ig_form=None, native=False):
         import flute_amd
         from flute_amd import utils
         self.fa, self.part, self.form = flute_amd, part, form   # form: of the recompute's two plain launches (None: automatic)
+        self.native = native                                       # the ops' native_glu_grad: moe_gather and swiglu_grad for the torch chains
         self.ig_form = ig_form                                     # ... of the two input-gradient launches (None: automatic)
         self.stacks = stacks                                       # step_stacks: (gate, up, down) GroupedFluteLinear per copy
         self.num_sms = utils.get_device_num_sms(device)
@@ -648,10 +653,17 @@ class BackwardStep:
         if run("down_input_grad"):
             dH = fa.qgemm_grouped_input_grad(self.dY, off, Qd, Sd, t2, *a, row_weight=self.row_weight, form=self.ig_form)
         if run("recompute_gate_up"):
-            x = self.hidden[self.rows.long()] if self.part is None else self.x
+            if self.part is not None:
+                x = self.x
+            elif self.native:
+                x = fa.moe_gather(self.hidden, self.rows, off)
+            else:
+                x = self.hidden[self.rows.long()]
             g, u = (fa.qgemm_grouped(x, off, Qg, Sg, t2, *a, form=self.form),
                     fa.qgemm_grouped(x, off, Qu, Su, t2, *a, form=self.form))
-        if run("elementwise_dg_du"):
+        if run("elementwise_dg_du") and self.native:
+            dg, du = fa.swiglu_grad(g, u, dH, off)
+        elif run("elementwise_dg_du"):
             gf, uf, dh = g.float(), u.float(), dH.float()
             sig = torch.sigmoid(gf)
             dg, du = (dh * uf * sig * (1 + gf * (1 - sig))).to(DTYPE), (dh * (gf * sig)).to(DTYPE)
@@ -1194,6 +1206,78 @@ def main_input_grad_forms(args, device):
               "us": us, "whole_auto_over_slabs": round(us["whole auto"] / us["whole slabs"], 4), "spread": spread,
               "replays_us": replays})
     print("wrote", args.out)
+    main_swiglu_grad(args, device, stacks, copies)
+
+
+class CopyYardstick:
+    """`copy_` of a 16-bit tensor of 2.5 R F elements: 5 R F bytes read and 5 R F written, the 10 bytes per element of [R, F]
+    that swiglu_grad moves (g, u, dh in; dg, du out)."""
+
+    def __init__(self, R, F, device):
+        n = 5 * R * F // 2
+        self.src = torch.randn(n, device=device, dtype=torch.float32).to(DTYPE)
+        self.dst = torch.empty_like(self.src)
+
+    def step(self, i):
+        return self.dst.copy_(self.src)
+
+
+class Gather:
+    """The gather in front of the recompute alone: the default backward's index_select on the clamped int64 index, or moe_gather."""
+
+    def __init__(self, step, native):
+        self.fa, self.hidden, self.rows, self.offsets, self.native = step.fa, step.hidden, step.rows, step.offsets, native
+
+    def step(self, i):
+        if self.native:
+            return self.fa.moe_gather(self.hidden, self.rows, self.offsets)
+        return self.hidden.index_select(0, self.rows.clamp(0, self.hidden.shape[0] - 1).long())
+
+
+def main_swiglu_grad(args, device, stacks=None, copies=None):
+    """The backward step with native_glu_grad off and on - the gather and `elementwise_dg_du` alone, and the whole step - and the
+    copy_ yardstick, all in one run."""
+    out = os.path.join(ROOT, "profiles", "grouped_moe_swiglu_grad.json")
+    F = 14336
+    if stacks is None:
+        copies = prefill_copies(E, F, 4096, BITS, stacks=3)
+        stacks = step_stacks(copies, device)
+    rows = []
+    for tokens in (512, 4096):
+        layers = {}
+        for part in (None, "elementwise_dg_du"):
+            for native in (False, True):
+                layers[("whole" if part is None else part) + (" native" if native else " torch")] = \
+                    BackwardStep(stacks, tokens, device, part, native=native)
+        layers["gather torch"], layers["gather native"] = Gather(layers["whole torch"], False), Gather(layers["whole torch"], True)
+        layers["copy_ yardstick"] = CopyYardstick(tokens * TOPK, F, device)
+        us, spread, replays = time_forms(layers, args)
+        part = "elementwise_dg_du"
+        rows.append({"what": "backward step, native_glu_grad off / on", "tokens": tokens, "rows": tokens * TOPK, "F": F, "experts": E,
+                     "top_k": TOPK, "weight_copies": copies, "us": us,
+                     "elementwise_torch_over_native": round(us[part + " torch"] / us[part + " native"], 3),
+                     "elementwise_native_over_copy": round(us[part + " native"] / us["copy_ yardstick"], 3),
+                     "elementwise_native_TBps": round(10.0 * tokens * TOPK * F / us[part + " native"] * 1e-6, 3),
+                     "copy_TBps": round(10.0 * tokens * TOPK * F / us["copy_ yardstick"] * 1e-6, 3),
+                     "gather_torch_over_native": round(us["gather torch"] / us["gather native"], 3),
+                     "whole_native_over_torch": round(us["whole native"] / us["whole torch"], 4),
+                     "whole_torch_minus_native_us": round(us["whole torch"] - us["whole native"], 3),
+                     "whole_replay_range_us": {n: [round(min(min(p) for p in replays[n]), 3), round(max(max(p) for p in replays[n]), 3)]
+                                               for n in ("whole torch", "whole native")},
+                     "spread": spread, "replays_us": replays})
+        print(json.dumps({k: v for k, v in rows[-1].items() if k != "replays_us"}), flush=True)
+        del layers
+        torch.cuda.empty_cache()
+        with open(out, "w") as f:
+            json.dump({"what": "one backward step of FluteExperts(fused=True, native_routing=True) at Mixtral's shapes (E = 8, top-2, K = 4096, "
+                               "F = 14336, W4G64 fp16) by hand, with the gather and the SwiGLU derivative as torch op chains (the default "
+                               "backward's arithmetic) and as flute_amd.moe_gather + flute_amd.swiglu_grad (native_glu_grad=True): the two "
+                               "parts alone and the whole step, and a copy_ of 2.5 R F 16-bit elements as the yardstick of the same "
+                               "traffic; hipGraph replays, device-clock stamps, cold caches, median of the replays, two alternating "
+                               "passes of every contender in one process",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+    print("wrote", out)
 
 
 def main_input_grad(args):
@@ -1277,6 +1361,8 @@ def main():
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
     ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS, default=None,
                     help="--mode prefill: the sections to run (default: all) - " + ", ".join(PREFILL_SECTIONS))
+    ap.add_argument("--only-swiglu-grad", action="store_true",
+                    help="--mode input_grad: its last section alone, the backward step with native_glu_grad off and on")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
@@ -1309,7 +1395,7 @@ def main():
     if args.mode == "prefill":
         return main_prefill(args, device)
     if args.mode == "input_grad":
-        return main_input_grad_forms(args, device)
+        return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
     bits = args.bits
     for name, N, K in (("gate_up", 14336, 4096), ("down", 4096, 14336)):
