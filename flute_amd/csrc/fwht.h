@@ -26,7 +26,8 @@ __device__ __forceinline__ void reg_stages(float (&v)[8], int nbits) {
 // Butterflies over `nbits` lane bits (lane bit s pairs lanes l and l ^ (1 << s)), without a trip through the LDS crossbar.
 // Rounds 1 - 4 fetched the partner's value with __shfl_xor (ds_bpermute_b32): six dependent LDS round trips per transform,
 // 1.4 us of a 5.3-us launch for the fused pre-rotation of ONE 3584-element row.  Round 5 (same fp32 operations on the same
-// operands in the same order: results are bit-identical, tests/test_hadamard_gpu.py):
+// operands in the same order: results are bit-identical; tests/test_hadamard_gpu.py compares both users of these stages with the
+// plain butterflies element for element, -0 == +0, on integer inputs whose sums are exact in fp32, at every h):
 //   lane bits 0 - 3: ONE instruction per value and stage, v_fmac_f32_dpp v, v(partner), c with c = -1 in the lanes whose bit s
 //     is set: those lanes hold v - p = -(p - v), the NEGATIVE of the butterfly's result; the pending sign is the same in both
 //     lanes of every later pair (they differ in a higher bit only), so it commutes with the later stages and is applied once

@@ -6,8 +6,9 @@ stage with c = -1 in the lanes whose bit is set - those lanes then hold the NEGA
 equal in both lanes of every later pair and is applied once (parity of the lane's low bits); the partner of bit 2 is reached by a quad
 reverse followed by `row_half_mirror`; lane bits 4 and 5 are register stages between two lane swaps (`v_permlane16_swap` /
 `v_permlane32_swap`).  The model below restates exactly that data movement with numpy float32 arithmetic and checks it, bit for bit,
-against the textbook butterflies - the property `tests/test_qgemm_gpu.py::test_hadamard_*` then checks on the hardware against the
-definition (reference: flute/csrc/hadamard/hadamard_transform_cuda.cu:141-154, the staged butterflies of the CUDA kernel)."""
+against the textbook butterflies - the property `tests/test_hadamard_gpu.py` then checks on the hardware, element for element at
+every h = 2 .. 32768, against the exact integer transform (`tests/test_qgemm_gpu.py::test_hadamard_*` against the definition within
+a norm tolerance; reference: flute/csrc/hadamard/hadamard_transform_cuda.cu:141-154, the staged butterflies of the CUDA kernel)."""
 import numpy as np
 
 L = np.arange(64)
