@@ -48,6 +48,10 @@ moe_combine = ops.moe_combine
 # the row gather, moe_combine's transpose, and (dg, du) from g, u and the gradient of silu(g) u
 moe_gather = ops.moe_gather
 swiglu_grad = ops.swiglu_grad
+# the router's backward, one launch each (the ops' `native_router_grad=True` runs them): d row_weight and the weighted input gradient
+# from the unweighted one, and d logits of the four gating ops from the gradients of their weights / row_weight
+moe_weight_grad = ops.moe_weight_grad
+moe_gate_grad = ops.moe_gate_grad
 # the gating in front of them: router logits [T, E] -> (ids, weights) with a defined tie order, one launch; and the same launch
 # carried on through moe_route's sort: from logits to every routing array
 moe_gate = ops.moe_gate

@@ -81,6 +81,8 @@ SYMBOLS = {
     "flute_moe_combine": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
     "flute_swiglu_grad": (c_int, [c_int] * 4 + [c_void_p] * 6 + [c_void_p]),
     "flute_moe_gather": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_void_p]),
+    "flute_moe_weight_grad": (c_int, [c_int] * 4 + [c_void_p] * 6 + [c_void_p]),
+    "flute_moe_gate_grad": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 6 + [c_void_p]),
     "flute_moe_gate": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 4 + [c_void_p]),
     "flute_moe_gate_route": (c_int, [c_int] * 6 + [c_float] + [c_void_p] * 9 + [c_void_p]),
     "flute_moe_gate_limited": (c_int, [c_int] * 9 + [c_float] + [c_void_p] * 4 + [c_void_p]),

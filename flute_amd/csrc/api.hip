@@ -2115,6 +2115,28 @@ int flute_moe_gather(int dtype, int R, int Tsrc, int K, int E, const void* X, co
     return moe_gather_dispatch(R, Tsrc, K, E, X, rows, offsets, out, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flute_moe_weight_grad(int dtype, int R, int K, int E, const void* dHp, const void* H, const float* row_weight,
+                          const int32_t* offsets, float* d_row_weight, void* dH, void* stream) {
+    if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;
+    if (R < 0 || K < 0 || K % 8 || (offsets && E < 0)) return FLUTE_ERR_SHAPE;
+    if (R == 0 || K == 0) return FLUTE_OK;
+    if (!dHp || !H || !d_row_weight || (row_weight != nullptr) != (dH != nullptr)) return FLUTE_ERR_NULL;
+    return moe_weight_grad_dispatch(dtype, R, K, E, dHp, H, row_weight, offsets, d_row_weight, dH,
+                                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_moe_gate_grad(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                        const int32_t* ids, const float* d_weights, const float* d_row_weight, const int32_t* pos, void* d_logits,
+                        void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, nullptr, scoring);
+    if (rc) return rc;
+    if (T == 0) return FLUTE_OK;
+    if (!logits || !ids || !d_logits) return FLUTE_ERR_NULL;
+    if ((!d_weights && !d_row_weight && !pos) || (d_row_weight != nullptr) != (pos != nullptr)) return FLUTE_ERR_NULL;
+    return moe_gate_grad_dispatch(logit_dtype, T, E, k, scoring, renormalize, scale, logits, ids, d_weights, d_row_weight, pos,
+                                  d_logits, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

@@ -171,6 +171,14 @@ int swiglu_grad_dispatch(int dtype, int R, int F, int E, const void* g, const vo
                          void* dg, void* du, hipStream_t stream);
 int moe_gather_dispatch(int R, int Tsrc, int K, int E, const void* X, const int32_t* rows, const int32_t* offsets, void* out,
                         hipStream_t stream);
+// the router's backward (router_grad.hip): d_row_weight [R] fp32 = the row sums of dHp * H and dH = round_T(row_weight dHp) in one
+// launch, one workgroup of 256 lanes per row (dH and row_weight null together: the sums only; offsets as swiglu_grad's); and the
+// gate's backward, d_logits [T, E] from the gradients of its weights [T, k] and / or of row_weight through pos, one wave per token
+int moe_weight_grad_dispatch(int dtype, int R, int K, int E, const void* dHp, const void* H, const float* row_weight,
+                             const int32_t* offsets, float* d_row_weight, void* dH, hipStream_t stream);
+int moe_gate_grad_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                           const int32_t* ids, const float* d_weights, const float* d_row_weight, const int32_t* pos,
+                           void* d_logits, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

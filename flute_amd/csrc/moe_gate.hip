@@ -15,7 +15,8 @@
 //           running sum would carry up to 63 roundings into every weight of the row.
 // A wave reduction is six exchange steps without LDS: DPP quad_perm (lanes ^ 1, ^ 2), row_half_mirror, row_mirror inside a
 // row of 16, then v_permlane16_swap and v_permlane32_swap across rows.  Every step combines the same two values in both
-// partners, so all 64 lanes hold the same bits afterwards and the order of the additions is fixed.
+// partners, so all 64 lanes hold the same bits afterwards and the order of the additions is fixed.  The exchange steps and the
+// score stage (gate_scores) live in moe_gate_score.h, which the gate's backward (router_grad.hip) shares.
 // The per-token work is ONE device function, gate_token, which both kernels call: their equal bits rest on it (it is compiled
 // with floating-point contraction off, so the two inlined copies cannot differ by a fused multiply-add).
 //   moe_gate_kernel        4 waves per workgroup, wave w of block b takes token 4 b + w; the grid covers T.
@@ -34,74 +35,13 @@
 // One host path serves the four entry points (moe_gate_dispatch): LIMITED, the class NV and the logit type are its three choices.
 // No atomics on global memory, plain vector stores, nothing read on the host.
 #include "kernels.h"
+#include "moe_gate_score.h"
 #include "moe_route_sort.h"
-#include "../../include/flute_amd.h"
-
-#include <math.h>
 
 namespace flute_amd {
 
 constexpr int kGateWaves = 4;                   // waves per workgroup of the standalone form
 constexpr int kGateThreads = 64 * kGateWaves;
-
-template <typename L> struct GateLogit;
-template <> struct GateLogit<F16> {
-    typedef uint16_t type;
-    static __device__ __forceinline__ float to_float(uint16_t u) { return Num<F16>::to_float(u); }
-};
-template <> struct GateLogit<BF16> {
-    typedef uint16_t type;
-    static __device__ __forceinline__ float to_float(uint16_t u) { return Num<BF16>::to_float(u); }
-};
-template <> struct GateLogit<float> {
-    typedef float type;
-    static __device__ __forceinline__ float to_float(float f) { return f; }
-};
-
-// ---- the exchange steps of a wave reduction ---------------------------------------------------------------------------------
-// STEP 0 .. 3: the value of the partner lane inside a row of 16 (every lane active: callers keep the wave whole)
-template <int STEP>
-static __device__ __forceinline__ uint32_t row_partner(uint32_t v) {
-    constexpr int ctrl = STEP == 0 ? 0xB1      // quad_perm [1, 0, 3, 2]
-                         : STEP == 1 ? 0x4E    // quad_perm [2, 3, 0, 1]
-                         : STEP == 2 ? 0x141   // row_half_mirror: quads agree by now, so this pairs the two quads of a half
-                                     : 0x140;  // row_mirror: halves agree, this pairs the two halves of the row
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, ctrl, 0xF, 0xF, true);
-}
-
-struct OpMaxF {
-    static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a, b); }
-};
-struct OpAddF {
-    static __device__ __forceinline__ float apply(float a, float b) { return a + b; }
-};
-struct OpMaxU {
-    static __device__ __forceinline__ uint32_t apply(uint32_t a, uint32_t b) { return a > b ? a : b; }
-};
-
-template <typename Op>
-static __device__ __forceinline__ uint32_t wave_reduce_bits(uint32_t v, auto from, auto to) {
-    v = to(Op::apply(from(v), from(row_partner<0>(v))));
-    v = to(Op::apply(from(v), from(row_partner<1>(v))));
-    v = to(Op::apply(from(v), from(row_partner<2>(v))));
-    v = to(Op::apply(from(v), from(row_partner<3>(v))));
-    // rows agree inside themselves; with both operands the same register the swap returns (the even row's, the odd row's) value
-    // of each pair of rows in every lane of the pair, then (the lower half's, the upper half's) in every lane
-    auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    v = to(Op::apply(from(r[0]), from(r[1])));
-    r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return to(Op::apply(from(r[0]), from(r[1])));
-}
-
-template <typename Op>
-static __device__ __forceinline__ float wave_reduce(float v) {
-    return __uint_as_float(wave_reduce_bits<Op>(__float_as_uint(v), [](uint32_t u) { return __uint_as_float(u); },
-                                                [](float f) { return __float_as_uint(f); }));
-}
-
-static __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    return wave_reduce_bits<OpMaxU>(v, [](uint32_t u) { return u; }, [](uint32_t u) { return u; });
-}
 
 // a float as an integer of the same (unsigned) order; NaN ranks as -infinity, -0 as +0; the smallest result is 0x007fffff
 static __device__ __forceinline__ uint32_t ordered_key(float f) {
@@ -183,36 +123,10 @@ static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::t
                                                   float scale, int n_group, int gs, int topk_group, int group_score, int lane,
                                                   int32_t* ids, float* weights) {
 #pragma clang fp contract(off)
-    float x[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int e = lane + 64 * i;
-        x[i] = e < E ? GateLogit<L>::to_float(logits[e]) : -INFINITY;
-    }
-
     // v: what a chosen expert contributes to the weights - u for a renormalised softmax without bias, else the score s
-    float v[NV];
-    if (scoring == FLUTE_GATE_SOFTMAX) {
-        float m = x[0];
-#pragma unroll
-        for (int i = 1; i < NV; ++i) m = fmaxf(m, x[i]);
-        m = wave_reduce<OpMaxF>(m);
-        float part = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            v[i] = lane + 64 * i < E ? expf(x[i] - m) : 0.0f;
-            part += v[i];
-        }
-        // (the top-2 sum of a group is a sum of normalised scores: that form always divides)
-        if (!renormalize || bias || (LIMITED && group_score == FLUTE_GATE_GROUP_TOP2SUM)) {
-            const float total = wave_reduce<OpAddF>(part);
-#pragma unroll
-            for (int i = 0; i < NV; ++i) v[i] = v[i] / total;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = 1.0f / (1.0f + expf(-x[i]));
-    }
+    // (the top-2 sum of a group is a sum of normalised scores: that form always divides)
+    float x[NV], v[NV];
+    gate_scores<L, NV>(logits, E, scoring, !renormalize || bias || (LIMITED && group_score == FLUTE_GATE_GROUP_TOP2SUM), lane, x, v);
 
     uint32_t key[NV];                            // 0: no expert in this slot, or taken
 #pragma unroll

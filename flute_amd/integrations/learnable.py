@@ -296,9 +296,11 @@ def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, w
 
 def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
                                             scales: torch.Tensor, table2: torch.Tensor, row_weight: torch.Tensor,
-                                            num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+                                            num_bits: int, group_size: int, template_id: int, num_sms=None,
+                                            native_router_grad: bool = False) -> torch.Tensor:
     """`flute_amd.qgemm_grouped_weighted`, differentiable with respect to `input`, `row_weight` and `scales`.  The
-    forward is the op's launch; the gradients of `input` and `row_weight` are the op's own, and
+    forward is the op's launch; the gradients of `input` and `row_weight` are the op's own (`native_router_grad` as the
+    op's: one `moe_weight_grad` launch for the two when `row_weight` trains), and
     dS = `qgemm_grouped_scale_grad(dY, input, ..., row_weight=row_weight)`.  `table2` requiring grad is refused."""
     _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     _refuse_table_grad("qgemm_grouped_weighted_learnable_scales", table2)
@@ -306,7 +308,7 @@ def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.
         return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
                                                 template_id, num_sms)
     return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2,
-                                               (num_bits, group_size, template_id, num_sms))
+                                               (num_bits, group_size, template_id, num_sms), None, bool(native_router_grad))
 
 
 def _glu_op(blocks):
@@ -380,17 +382,18 @@ def qgemm_grouped_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: 
 
 def qgemm_grouped_weighted_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
                                      scales: torch.Tensor, codebook: torch.Tensor, row_weight: torch.Tensor,
-                                     num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+                                     num_bits: int, group_size: int, template_id: int, num_sms=None,
+                                     native_router_grad: bool = False) -> torch.Tensor:
     """`flute_amd.qgemm_grouped_weighted`, differentiable with respect to `input`, `row_weight`, `scales` and the stack's
     fp32 master `codebook`: `qgemm_grouped_weighted_learnable_scales` with the table gradient from
-    `qgemm_grouped_table_grad(dY, input, ..., row_weight=row_weight)`."""
+    `qgemm_grouped_table_grad(dY, input, ..., row_weight=row_weight)`.  `native_router_grad` as there."""
     table2 = _codebook_stack("qgemm_grouped_weighted_learnable", codebook, num_bits, input.dtype, scales)
     _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     if not _ops._records_grad(input, row_weight, scales, codebook):
         return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
                                                 template_id, num_sms)
     return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, codebook, offsets, weight, table2,
-                                               (num_bits, group_size, template_id, num_sms))
+                                               (num_bits, group_size, template_id, num_sms), None, bool(native_router_grad))
 
 
 def qgemm_grouped_glu_learnable(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,

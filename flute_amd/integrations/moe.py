@@ -33,7 +33,9 @@ their backward (`flute_amd.ops`): the input gradients of the three projections a
 the gradient of the gather is `moe_combine` under native routing (equal bits at every top-k) and `index_add_` otherwise,
 `moe_combine`'s own gradient is a gather, and the gating ops differentiate their formula in fp32 with the chosen ids
 held fixed - so layers in front of the block (LoRA on attention, a trainable router) get their gradients.  With grad mode
-off, or nothing requiring grad, the forward is exactly the inference path above and stays capturable.
+off, or nothing requiring grad, the forward is exactly the inference path above and stays capturable.  With a trainable router,
+`FluteExperts(fused=True, native_routing=True, native_router_grad=True)` runs the torch parts of that backward - d row_weight and the
+weighted input gradient, the gate's derivative, `moe_combine`'s gather - as one HIP launch each (router_grad.hip, `moe_gather`).
 
 The experts' scales train: `make_experts_learnable(model)` swaps every `GroupedFluteLinear` for a
 `LearnableGroupedFluteLinear` (its `scales` an `nn.Parameter`, the packed codes and tables shared) and `FluteExperts` then
@@ -264,13 +266,20 @@ class FluteExperts(torch.nn.Module):
     eligible); "auto": the block launch where `flute_amd.dev.grouped_glu_blocks_form` takes it for the step's T k rows.
     `native_glu_grad` (with `fused=True`): the ops' keyword of that name - the backward of the fused GLU launch gathers its rows
     with `moe_gather` and forms dg, du with `swiglu_grad` (two HIP launches) where the default runs torch ops; the forward's bits
-    are the same either way, the backward's differ within `flute_swiglu_grad`'s error account."""
+    are the same either way, the backward's differ within `flute_swiglu_grad`'s error account.
+    `native_router_grad` (with `fused=True` and `native_routing=True`): the ops' keyword of that name - when the router trains,
+    the weighted launch's backward forms d row_weight and d h in one `moe_weight_grad` launch, the gate-route launch's
+    backward is one `moe_gate_grad` launch, and `moe_combine` gets `rows`, so its backward is one `moe_gather` launch; the
+    default runs torch ops in all three places.  The forward's bits are the same either way."""
 
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
                  fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
-                 native_glu_grad: bool = False) -> None:
+                 native_glu_grad: bool = False, native_router_grad: bool = False) -> None:
         super().__init__()
         _check_glu_blocks(glu_blocks, fused)
+        if native_router_grad and not (fused and native_routing):
+            raise ValueError("FluteExperts: native_router_grad selects the backward of the weighted, gate-route and combine "
+                             "launches and needs fused=True and native_routing=True")
         if native_glu_grad and not fused:
             raise ValueError("FluteExperts: native_glu_grad selects the backward of the fused GLU launch and needs fused=True")
         if not (gate.num_experts == up.num_experts == down.num_experts):
@@ -287,14 +296,16 @@ class FluteExperts(torch.nn.Module):
         self.native_routing = bool(native_routing)
         self.glu_blocks = glu_blocks
         self.native_glu_grad = bool(native_glu_grad)
+        self.native_router_grad = bool(native_router_grad)
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
-                     glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False) -> "FluteExperts":
+                     glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
+                     native_router_grad: bool = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
-                   native_glu_grad=native_glu_grad)
+                   native_glu_grad=native_glu_grad, native_router_grad=native_router_grad)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -323,7 +334,7 @@ class FluteExperts(torch.nn.Module):
         return self._forward_gated(
             "forward_logits", hidden, router_logits,
             lambda: flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale),
-            lambda: flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale))
+            lambda: self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale))
 
     def forward_logits_limited(self, hidden: torch.Tensor, router_logits: torch.Tensor, top_k: int, n_group: int,
                                topk_group: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
@@ -337,8 +348,18 @@ class FluteExperts(torch.nn.Module):
             "forward_logits_limited", hidden, router_logits,
             lambda: flute_amd.moe_gate_limited(router_logits, top_k, n_group, topk_group, scoring, renormalize, bias, scale,
                                                group_score),
-            lambda: flute_amd.moe_gate_route_limited(router_logits, top_k, n_group, topk_group, self.num_experts, scoring,
-                                                     renormalize, bias, scale, group_score))
+            lambda: self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale, (n_group, topk_group, group_score)))
+
+    def _gate_route(self, router_logits, top_k, scoring, renormalize, bias, scale, groups=None):
+        """`moe_gate_route` / `moe_gate_route_limited` (`groups` = (n_group, topk_group, group_score)); with the module's
+        `native_router_grad` the same launch through the ops' shared entry, which carries the keyword to its backward."""
+        if self.native_router_grad:
+            return flute_amd.ops._moe_gate_entry(router_logits, top_k, scoring, renormalize, bias, scale, routed=True,
+                                                 num_experts=self.num_experts, groups=groups, native_router_grad=True)
+        if groups is None:
+            return flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale)
+        return flute_amd.moe_gate_route_limited(router_logits, top_k, groups[0], groups[1], self.num_experts, scoring,
+                                                renormalize, bias, scale, groups[2])
 
     def _forward_gated(self, name, hidden, router_logits, gate, gate_route):
         """The tail `forward_logits` and `forward_logits_limited` share: `gate()` feeds the existing forward, with
@@ -379,7 +400,7 @@ class FluteExperts(torch.nn.Module):
         scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
         `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
         `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`).
-        The module's `native_glu_grad` rides on whichever GLU entry that is."""
+        The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
         if has[0] != has[1]:
@@ -393,6 +414,8 @@ class FluteExperts(torch.nn.Module):
             glu = functools.partial(glu, native_glu_grad=True)
         weighted = qgemm_grouped_weighted_learnable if has[2] else \
             qgemm_grouped_weighted_learnable_scales if learnable else flute_amd.qgemm_grouped_weighted
+        if self.native_router_grad:
+            weighted = functools.partial(weighted, native_router_grad=True)
         return glu, weighted
 
     def _forward_native(self, hidden, topk_ids, topk_weights):
@@ -417,7 +440,7 @@ class FluteExperts(torch.nn.Module):
             x = hidden[rows]
             h = torch.nn.functional.silu(gate(x, offsets)) * up(x, offsets)
             y = down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
-        return flute_amd.moe_combine(y, pos, offsets)
+        return flute_amd.moe_combine(y, pos, offsets, rows if self.native_router_grad else None)
 
 
 class FluteSparseMoeBlock(torch.nn.Module):

@@ -1,6 +1,6 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gather`, `swiglu_grad`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gather`, `swiglu_grad`, `moe_weight_grad`, `moe_gate_grad`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
 `moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
 routing weights and router logits: when grad mode is on and such an input requires grad they run through a
 `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`, `moe_combine`
@@ -666,17 +666,23 @@ def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weigh
 
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                            table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
-                           template_id: int, num_sms=None, form=None) -> torch.Tensor:
+                           template_id: int, num_sms=None, form=None, native_router_grad: bool = False) -> torch.Tensor:
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
-    HIP kernel on the current stream; equal arguments give equal bits.  `form` as `qgemm_grouped`'s."""
+    HIP kernel on the current stream; equal arguments give equal bits.  `form` as `qgemm_grouped`'s.
+
+    `native_router_grad` is read by the backward only, and only when `row_weight` requires grad: False (the default) forms
+    d row_weight and d input from the unweighted input gradient with torch ops, bit for bit as before; True runs one
+    `moe_weight_grad` launch in their place - d input has the same bits, d row_weight is summed in `flute_moe_weight_grad`'s
+    fixed order, not torch's.  The forward's bits do not depend on it."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     _grouped_form_id(form)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
-        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form)
+        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form,
+                                              bool(native_router_grad))
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
@@ -686,12 +692,14 @@ class _GroupedWeightedFunction(torch.autograd.Function):
     (zero from offsets[E] on) and dH = round_T(row_weight dH').  For `integrations.learnable` (the op itself refuses
     scales that require grad) dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight multiplies
     dY where the kernel stages it.  With `codebook` - the stack's fp32 master, which `table2` was built from - the
-    parameter gradients are `_grouped_table_grads` with the same row weight."""
+    parameter gradients are `_grouped_table_grads` with the same row weight.  `native` (the ops' `native_router_grad`):
+    the two results of a row weight that needs a gradient come from one `moe_weight_grad` launch."""
 
     @staticmethod
-    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None):
+    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None, native=False):
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
         ctx.layer = layer
+        ctx.native = native
         ctx.scalar = codebook is not None and codebook.ndim == 2
         return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
@@ -703,18 +711,23 @@ class _GroupedWeightedFunction(torch.autograd.Function):
         d_input = d_weight = None
         if want_input or want_weight:
             d_input, d_weight = _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, want_input,
-                                                           want_weight)
+                                                           want_weight, native=ctx.native)
         d_scales, d_codebook = _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, ctx.layer,
                                                     want_scales, want_codebook, ctx.scalar, row_weight=row_weight)
-        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 5
+        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 6
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
-                               want_weight):
-    """(d input, d row_weight) of the weighted launch."""
+                               want_weight, native=False):
+    """(d input, d row_weight) of the weighted launch.  `native` (the ops' `native_router_grad`): with `want_weight` the
+    unweighted input-gradient launch is followed by one `moe_weight_grad` launch in place of the torch lines below."""
     stack = (offsets, weight, scales, table2)
     if not want_weight:
         return qgemm_grouped_input_grad(grad_output, *stack, *layer, row_weight=row_weight), None
+    if native:
+        d_weight, d_input = moe_weight_grad(qgemm_grouped_input_grad(grad_output, *stack, *layer), input, row_weight, offsets,
+                                            want_input_grad=want_input)
+        return d_input, d_weight
     R = input.shape[0]
     dh = qgemm_grouped_input_grad(grad_output, *stack, *layer).float()
     served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
@@ -1025,14 +1038,16 @@ class _MoeGateFunction(torch.autograd.Function):
     """The gating ops under autograd: `ids` (and the routing arrays) stay non-differentiable, `weights` - and `row_weight`,
     a permutation of it - get a gradient to `logits`.  The backward differentiates the documented formula in fp32 with
     the kernel's ids held fixed: softmax over all E (or the sigmoid), the gather of the chosen, the optional division by
-    their sum, times `scale`; the bias enters the choice only."""
+    their sum, times `scale`; the bias enters the choice only.  `native` (the ops' `native_router_grad`): the same
+    derivative from one `moe_gate_grad` launch, which also folds d row_weight back through `pos`; `_moe_gate_entry` carries it."""
 
     @staticmethod
-    def forward(ctx, logits, run, scoring, renormalize, scale):
+    def forward(ctx, logits, run, scoring, renormalize, scale, native=False):
         outs = run()
         routed = len(outs) > 2
         ctx.save_for_backward(logits, outs[0], *((outs[5],) if routed else ()))
         ctx.formula = (scoring, bool(renormalize), float(scale))
+        ctx.native = native
         ctx.mark_non_differentiable(*[o for o in outs if not o.is_floating_point()])
         return tuple(outs)
 
@@ -1041,6 +1056,10 @@ class _MoeGateFunction(torch.autograd.Function):
     def backward(ctx, *grads):
         logits, ids, *rest = ctx.saved_tensors
         scoring, renormalize, scale = ctx.formula
+        if ctx.native:                                          # one launch: the fold through pos is the kernel's
+            dx = moe_gate_grad(logits, ids, grads[1], scoring, renormalize, scale,
+                               grad_row_weight=grads[4] if rest else None, pos=rest[0] if rest else None)
+            return dx, None, None, None, None, None
         d_weights = grads[1]
         if rest:                                                # row_weight[i] = weights.flatten()[perm[i]], pos the inverse of perm
             d_weights = d_weights + grads[4].index_select(0, rest[0].reshape(-1).long()).view_as(d_weights)
@@ -1051,13 +1070,27 @@ class _MoeGateFunction(torch.autograd.Function):
             if renormalize:
                 w = w / w.sum(dim=1, keepdim=True)
             (dx,) = torch.autograd.grad(w * scale, x, d_weights)
-        return dx.to(logits.dtype), None, None, None, None
+        return dx.to(logits.dtype), None, None, None, None, None
 
 
-def _moe_gate_op(logits, run, scoring, renormalize, scale):
+def _moe_gate_op(logits, run, scoring, renormalize, scale, native=False):
     if _records_grad(logits):
-        return _MoeGateFunction.apply(logits, run, scoring, renormalize, scale)
+        return _MoeGateFunction.apply(logits, run, scoring, renormalize, scale, bool(native))
     return run()
+
+
+def _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed, num_experts=None, groups=None,
+                    native_router_grad=False):
+    """What the four gating ops share: the validation, the launch and, when `logits` records a gradient, `_MoeGateFunction`.
+    `groups` = (n_group, topk_group, group_score) or None.  `native_router_grad` is read by the backward only: False (the four
+    ops' own) differentiates the formula with torch ops; True - `FluteExperts(native_router_grad=True)` passes it - runs one
+    `moe_gate_grad` launch (router_grad.hip) in their place.  The forward's bits do not depend on it."""
+    if groups is None:
+        _validate_moe_gate(logits, k, scoring, bias, num_experts)
+    else:
+        _validate_moe_gate_limited(logits, k, groups[0], groups[1], scoring, bias, groups[2], num_experts)
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=routed, groups=groups),
+                        scoring, renormalize, scale, native_router_grad)
 
 
 def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
@@ -1071,9 +1104,7 @@ def moe_gate(logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize
     1 <= k <= min(E, 64), E <= 1024, T k < 2^27.  The choice is over all E experts; DeepSeek's group-limited
     selection (n_group, topk_group) is `moe_gate_limited`.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
     stream (moe_gate.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
-    _validate_moe_gate(logits, k, scoring, bias)
-    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=False),
-                        scoring, renormalize, scale)
+    return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=False)
 
 
 def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str = "softmax", renormalize: bool = False,
@@ -1082,9 +1113,7 @@ def moe_gate_route(logits: torch.Tensor, k: int, num_experts=None, scoring: str 
     bit for bit `moe_gate(logits, k, ...)`'s and the other five bit for bit `moe_route(ids, weights, E)`'s.
     `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves gates the tokens and sorts the
     pairs: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
-    _validate_moe_gate(logits, k, scoring, bias, num_experts)
-    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=True),
-                        scoring, renormalize, scale)
+    return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=True, num_experts=num_experts)
 
 
 _GATE_GROUP_SCORE_ID = {"max": 0, "top2sum": 1}     # include/flute_amd.h flute_gate_group_score
@@ -1120,10 +1149,7 @@ def moe_gate_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int
     With topk_group == n_group the result is bit for bit `moe_gate`'s.  Returns (ids [T, k] int32, weights [T, k]
     fp32); no host synchronise (capturable), a native HIP kernel on the current stream (moe_gate.hip), equal arguments
     give equal bits."""
-    _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score)
-    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=False,
-                                                       groups=(n_group, topk_group, group_score)),
-                        scoring, renormalize, scale)
+    return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=False, groups=(n_group, topk_group, group_score))
 
 
 def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_group: int, num_experts=None,
@@ -1133,49 +1159,61 @@ def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_grou
     two bit for bit `moe_gate_limited(logits, k, n_group, topk_group, ...)`'s and the other five bit for bit
     `moe_route(ids, weights, E)`'s.  `num_experts`, when given, must be logits.shape[1].  One workgroup of 16 waves, as
     `moe_gate_route`: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
-    _validate_moe_gate_limited(logits, k, n_group, topk_group, scoring, bias, group_score, num_experts)
-    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=True,
-                                                       groups=(n_group, topk_group, group_score)),
-                        scoring, renormalize, scale)
+    return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=True, num_experts=num_experts,
+                           groups=(n_group, topk_group, group_score))
 
 
-def _validate_moe_combine(y, pos, offsets):
+def _validate_moe_combine(y, pos, offsets, rows=None):
     if not all([y.ndim == 2, pos.ndim == 2, offsets.ndim == 1]):
         raise ValueError
     if y.dtype not in _DTYPE_ID or pos.dtype != torch.int32 or offsets.dtype != torch.int32:
         raise TypeError
+    if rows is not None:
+        if rows.dtype != torch.int32:
+            raise TypeError
+        if rows.ndim != 1 or rows.shape[0] != y.shape[0]:
+            raise ValueError
     if y.shape[0] != pos.shape[0] * pos.shape[1] or offsets.shape[0] < 1 or y.shape[1] % 8 != 0:
         raise ValueError
     if y.shape[0] >= 2 ** 31:
         raise ValueError
 
 
-def moe_combine(y: torch.Tensor, pos: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+def moe_combine(y: torch.Tensor, pos: torch.Tensor, offsets: torch.Tensor, rows=None) -> torch.Tensor:
     """The end of a mixture-of-experts step in one launch: out[t] = sum over the slots j, ascending, of y[pos[t, j]], in
     fp32 with one rounding to y.dtype.  `y` [T k, N] are the down projection's rows in sorted order (N % 8 == 0), `pos`
     [T, k] int32 and `offsets` [E + 1] int32 are `moe_route`'s.  A slot whose position is outside [0, offsets[E]) - an id
     no expert serves - adds nothing and its row is never read; every element of the [T, N] result is written (a token
     with no served slot is zeros).  No atomics: equal arguments give equal bits for every k.  No host synchronise; a
-    native HIP kernel on the current stream (moe_combine.hip)."""
-    _validate_moe_combine(y, pos, offsets)
+    native HIP kernel on the current stream (moe_combine.hip).
+
+    `rows` (`moe_route`'s [T k] int32 tensor, or None) is read by the backward only: with it the gradient of `y` is
+    `moe_gather(grad_output, rows, offsets)`, one launch, where the default derives the token of every sorted row from `pos`
+    with torch ops.  The two have the same bits when `rows`, `pos` and `offsets` are what one routing kernel wrote
+    (`moe_route`, `moe_gate_route[_limited]`): then every row below offsets[E] is named by one entry of `pos` and `rows`
+    holds its token.  Arrays that do not belong together give the gather of the `rows` handed in."""
+    _validate_moe_combine(y, pos, offsets, rows)
     if _records_grad(y):
-        return _MoeCombineFunction.apply(y, pos, offsets)
+        return _MoeCombineFunction.apply(y, pos, offsets, rows)
     return _moe_combine_call(y, pos, offsets)
 
 
 class _MoeCombineFunction(torch.autograd.Function):
     """`moe_combine` under autograd: a gather, dY[r] = dOut[token of sorted row r] for the rows below offsets[E], zero from
-    there on (the forward never reads those)."""
+    there on (the forward never reads those).  With `rows` (the routing kernel's own token of every sorted row) that is one
+    `moe_gather` launch."""
 
     @staticmethod
-    def forward(ctx, y, pos, offsets):
-        ctx.save_for_backward(pos, offsets)
+    def forward(ctx, y, pos, offsets, rows=None):
+        ctx.save_for_backward(pos, offsets, *(() if rows is None else (rows,)))
         return _moe_combine_call(y, pos, offsets)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        pos, offsets = ctx.saved_tensors
+        pos, offsets, *rows = ctx.saved_tensors
+        if rows:
+            return moe_gather(grad_output, rows[0], offsets), None, None, None
         T, k = pos.shape
         R = T * k
         dev = pos.device
@@ -1186,7 +1224,7 @@ class _MoeCombineFunction(torch.autograd.Function):
         rows = torch.full((R + 1,), T, dtype=torch.long, device=dev).scatter_(0, torch.where(inside, p, R), token)[:R]
         named = (rows < T) & (torch.arange(R, device=dev) < offsets[-1].clamp(0, R))
         dy = grad_output.index_select(0, rows.clamp(max=T - 1))
-        return dy.masked_fill_(~named[:, None], 0), None, None
+        return dy.masked_fill_(~named[:, None], 0), None, None, None
 
 
 def _moe_combine_call(y, pos, offsets):
@@ -1291,4 +1329,108 @@ def moe_gather(input: torch.Tensor, rows: torch.Tensor, offsets=None) -> torch.T
         _lib.check(_lib.get().flute_moe_gather(
             _DTYPE_ID[input.dtype], R, Tsrc, K, 0 if off is None else off.shape[0] - 1, x.data_ptr(), rw.data_ptr(),
             None if off is None else off.data_ptr(), out.data_ptr(), _stream_ptr(dev)))
+    return out
+
+
+def _validate_moe_weight_grad(grad_unweighted, input, row_weight, offsets, want_input_grad):
+    if grad_unweighted.ndim != 2 or input.ndim != 2:
+        raise ValueError
+    if grad_unweighted.dtype not in _DTYPE_ID or input.dtype != grad_unweighted.dtype:
+        raise TypeError
+    _validate_row_stream_offsets(offsets)
+    if tuple(input.shape) != tuple(grad_unweighted.shape) or input.shape[1] % 8 != 0:
+        raise ValueError
+    if input.shape[0] >= 2 ** 31:
+        raise ValueError
+    if row_weight is None:
+        if want_input_grad:
+            raise ValueError("moe_weight_grad: the input gradient needs row_weight")
+    else:
+        _check_row_weight(row_weight, input.shape[0])
+
+
+def moe_weight_grad(grad_unweighted: torch.Tensor, input: torch.Tensor, row_weight, offsets=None,
+                    want_input_grad: bool = True):
+    """The routing weight's share of the weighted launch's backward in one launch: from dH' = `grad_unweighted` [R, K] (the
+    unweighted input gradient, `qgemm_grouped_input_grad` without `row_weight`) and h = `input` [R, K] (the weighted launch's
+    input), of one 16-bit type, K % 8 == 0, and `row_weight` [R] fp32:
+    (d_row_weight [R] fp32 = sum_k dH'[r, k] h[r, k], d_input [R, K] = round_T(row_weight[r] dH'[r, k]) or None).
+    The products are exact in fp32 and the sum is taken in the fixed order include/flute_amd.h states at flute_moe_weight_grad (no
+    atomics: a row's results depend neither on R nor on its position).  `offsets` as `swiglu_grad`'s: the rows from offsets[E]
+    on are +0 in both results and nothing of theirs is read; None serves every row.  `want_input_grad=False` forms the sums
+    only (`row_weight` may then be None).  Not differentiable (a piece of a backward).  No host synchronise (capturable); a
+    native HIP kernel on the current stream (router_grad.hip); equal arguments give equal bits."""
+    _validate_moe_weight_grad(grad_unweighted, input, row_weight, offsets, want_input_grad)
+    _refuse_grad("moe_weight_grad", grad_unweighted, input, row_weight)
+    dev = input.device
+    if not all(t.is_cuda and t.device == dev for t in (grad_unweighted, input, row_weight, offsets) if t is not None):
+        raise RuntimeError("flute_amd.moe_weight_grad: all tensors must live on the same GPU")
+    R, K = input.shape
+    dhp, h = _abi_tensor(grad_unweighted), _abi_tensor(input)
+    rw = _abi_tensor(row_weight) if want_input_grad else None
+    off = None if offsets is None else _abi_tensor(offsets)
+    d_weight = torch.empty((R,), dtype=torch.float32, device=dev)
+    d_input = torch.empty((R, K), dtype=input.dtype, device=dev) if want_input_grad else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_moe_weight_grad(
+            _DTYPE_ID[input.dtype], R, K, 0 if off is None else off.shape[0] - 1, dhp.data_ptr(), h.data_ptr(),
+            None if rw is None else rw.data_ptr(), None if off is None else off.data_ptr(), d_weight.data_ptr(),
+            None if d_input is None else d_input.data_ptr(), _stream_ptr(dev)))
+    return d_weight, d_input
+
+
+def _validate_moe_gate_grad(logits, ids, grad_weights, scoring, grad_row_weight, pos):
+    if logits.ndim != 2 or ids.ndim != 2:
+        raise ValueError
+    if logits.dtype not in _ROUTE_WEIGHT_DTYPE_ID or ids.dtype != torch.int32:
+        raise TypeError
+    if scoring not in _GATE_SCORING_ID:
+        raise ValueError
+    (T, E), k = logits.shape, ids.shape[1]
+    if ids.shape[0] != T or not 1 <= k <= min(E, MOE_GATE_MAX_TOPK) or E > MOE_ROUTE_MAX_EXPERTS or \
+            T * k >= MOE_ROUTE_MAX_PAIRS:
+        raise ValueError
+    if (grad_row_weight is None) != (pos is None):
+        raise ValueError("moe_gate_grad: grad_row_weight and pos are given together")
+    if grad_weights is None and pos is None:
+        raise ValueError("moe_gate_grad: no incoming gradient (grad_weights, or grad_row_weight with pos)")
+    if grad_weights is not None:
+        if grad_weights.dtype != torch.float32:
+            raise TypeError
+        if tuple(grad_weights.shape) != (T, k):
+            raise ValueError
+    if pos is not None:
+        if grad_row_weight.dtype != torch.float32 or pos.dtype != torch.int32:
+            raise TypeError
+        if tuple(grad_row_weight.shape) != (T * k,) or tuple(pos.shape) != (T, k):
+            raise ValueError
+
+
+def moe_gate_grad(logits: torch.Tensor, ids: torch.Tensor, grad_weights, scoring: str = "softmax",
+                  renormalize: bool = False, scale: float = 1.0, grad_row_weight=None, pos=None) -> torch.Tensor:
+    """The backward of the four gating ops in one launch: d_logits [T, E] in logits.dtype from `logits` [T, E] (fp16 / bf16 /
+    fp32), the forward's `ids` [T, k] int32 held fixed, and the incoming gradient of slot (t, j): `grad_weights`[t, j]
+    ([T, k] fp32, or None: 0) plus, with `grad_row_weight` [T k] fp32 and `pos` [T, k] int32 (the routed forms' arrays, given
+    together), grad_row_weight[pos[t, j]] where pos[t, j] is in [0, T k).  The scores are recomputed by the forward's device
+    function (softmax over all E, or the sigmoid), and the derivative of gather / renormalise / scale is include/flute_amd.h's
+    formula at flute_moe_gate_grad, in fp32 in slot order; the bias enters the choice only, so there is none here.  A slot whose
+    id is outside [0, E) is skipped; slots that name one expert add.  Every element of the result is written.  Not
+    differentiable.  One wave per token, no atomics, no host synchronise (capturable); a native HIP kernel on the current
+    stream (router_grad.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
+    _validate_moe_gate_grad(logits, ids, grad_weights, scoring, grad_row_weight, pos)
+    _refuse_grad("moe_gate_grad", logits, grad_weights, grad_row_weight)
+    dev = logits.device
+    if not all(t.is_cuda and t.device == dev for t in (logits, ids, grad_weights, grad_row_weight, pos) if t is not None):
+        raise RuntimeError("flute_amd.moe_gate_grad: all tensors must live on the same GPU")
+    T, E = logits.shape
+    k = ids.shape[1]
+    x, i = _abi_tensor(logits), _abi_tensor(ids)
+    q = None if grad_weights is None else _abi_tensor(grad_weights)
+    drw, p = (None, None) if pos is None else (_abi_tensor(grad_row_weight), _abi_tensor(pos))
+    out = torch.empty((T, E), dtype=logits.dtype, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get().flute_moe_gate_grad(
+            _ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale),
+            x.data_ptr(), i.data_ptr(), None if q is None else q.data_ptr(), None if drw is None else drw.data_ptr(),
+            None if p is None else p.data_ptr(), out.data_ptr(), _stream_ptr(dev)))
     return out

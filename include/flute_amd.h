@@ -37,6 +37,7 @@ extern "C" {
  *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t;
  *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
+ *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -769,6 +770,67 @@ int flute_swiglu_grad(int dtype, int R, int F, int E, const void* g, const void*
  * FLUTE_ERR_NULL (X, rows, out). */
 int flute_moe_gather(int dtype, int R, int Tsrc, int K, int E, const void* X, const int32_t* rows, const int32_t* offsets,
                      void* out, void* stream);
+
+/* The routing weight's share of the weighted launch's backward, in ONE launch.  dHp [R, K] T is the unweighted input gradient, as
+ * flute_qgemm_grouped_input_grad writes it without a row weight; H [R, K] T is the weighted launch's input; row_weight [R] fp32;
+ * contiguous, K % 8 == 0.  Per row r < served:
+ *   d_row_weight[r] = sum over k of (float) dHp[r, k] * (float) H[r, k]          fp32
+ *   dH[r, k]        = round_T(row_weight[r] * (float) dHp[r, k])                 ONE fp32 product, ONE rounding (to +-inf, not to 65504)
+ * offsets [E + 1] int32 (device memory) or NULL with flute_swiglu_grad's meaning: NULL serves every row and E is ignored; otherwise
+ * served = clamp(offsets[E], 0, R), read on the device, and the rows at or past `served` are written as +0 in both outputs while
+ * nothing of theirs is read - not dHp, not H (which may hold NaN there), not row_weight[r].  dH may be NULL: then only d_row_weight
+ * is formed; row_weight is NULL exactly when dH is.  Every element of every non-null output is written.
+ * Summation order.  The product of two fp16 or two bf16 values is exact in fp32 (22 / 16 significant bits; bf16 products beyond
+ * fp32's range excepted), so only the order of the additions is free, and it is fixed: one workgroup of 256 lanes takes one row;
+ * lane l takes the columns 2048 i + 8 l .. + 7 of step i = 0, 1, ... and adds its products to one fp32 accumulator (from +0) in
+ * ascending column order, step after step, one rounding per addition (no fma).  The 64 lanes of a wave then combine in the exchange
+ * tree of csrc/moe_gate_score.h - lanes ^ 1, lanes ^ 2, the two quads of a half row, the two halves of a row of 16, the two rows of
+ * a pair, the two pairs of a half wave, the two halves - every step adding the same two values in both partners; the four waves
+ * combine in wave order through LDS, ((w0 + w1) + w2) + w3.  No atomics: a row's two results depend neither on R nor on the row it
+ * sits in, and equal arguments give equal bits.
+ * Error account for d_row_weight against the exact sum of the exact products: any order of n - 1 fp32 additions of n terms gives
+ *   |d_row_weight[r] - ref| <= gamma_(K-1) * sum over k of |dHp[r, k] * H[r, k]|,   gamma_n = n 2^-24 / (1 - n 2^-24);
+ * this order's depth is 8 ceil(K / 2048) + 8, so gamma of that depth holds as well.  dH carries the one rounding to T.
+ * Non-finite operands propagate by IEEE rules: a NaN in a served row reaches that row's d_row_weight and the dH elements it
+ * multiplies, and no other row.  The host reads no operand; the grid is R workgroups (hipGraph-capturable); 64-bit element
+ * offsets; 16-byte loads and stores (csrc/router_grad.hip).
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE; FLUTE_ERR_SHAPE (a negative R or K, a negative E with
+ * offsets given, K % 8); R == 0 or K == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL (dHp, H, d_row_weight; row_weight
+ * without dH or dH without row_weight). */
+int flute_moe_weight_grad(int dtype, int R, int K, int E, const void* dHp, const void* H, const float* row_weight,
+                          const int32_t* offsets, float* d_row_weight, void* dH, void* stream);
+
+/* The backward of the four gating entries (flute_moe_gate, _route, _limited, _route_limited) in ONE launch: d_logits [T, E] in the
+ * logits' type from logits [T, E], the forward's ids [T, k] int32 held fixed, and the gradients that reach the weights.  The bias
+ * and the groups enter the choice only, so neither is an argument.  The incoming gradient of slot (t, j) is
+ *   q_j = (d_weights ? d_weights[t, j] : 0)  +  (pos && 0 <= pos[t, j] < T k ? d_row_weight[pos[t, j]] : nothing)
+ * d_weights [T, k] fp32 or NULL; d_row_weight [T k] fp32 and pos [T, k] int32 (flute_moe_route's: row_weight is a permutation of the
+ * weights) both given or both NULL; at least one source is given.  The scores s_e are recomputed from the logits by the forward's
+ * own device function (csrc/moe_gate_score.h, gate_scores): the softmax over all E - also where the forward renormalised the u_e
+ * directly - or the sigmoid.  Everything in fp32, every operation rounded once, no fma.  With s_j = s_(ids[t, j]); a slot whose id
+ * is outside [0, E) is skipped in every sum, and nothing outside the token's rows is read:
+ *   not renormalize:  ds_j = scale * q_j
+ *   renormalize:      S = sum_j s_j;  w_j = s_j / S;  B = sum_j q_j * w_j;  ds_j = (scale * (q_j - B)) / S      plain running sums
+ *                                                                                                              from +0 in slot order
+ *   ds_e = sum over the slots j with ids[t, j] == e, in slot order, of ds_j      (+0 for an expert no slot names; equal ids add)
+ *   FLUTE_GATE_SIGMOID:  dx_e = (ds_e * s_e) * (1 - s_e)
+ *   FLUTE_GATE_SOFTMAX:  dx_e = s_e * (ds_e - D),  D = sum_e ds_e * s_e: lane l adds its experts l, l + 64, ... in ascending order
+ *                        from +0, the lanes combine in the exchange tree
+ *   d_logits[t, e] = round to the logits' type (dx_e)      for every e < E: every element is written
+ * Error account, against the formula in exact arithmetic on the same inputs, to first order, eps = 2^-24: s_e carries the forward's
+ * error (expf within 2 eps, the sum over E, one quotient: (4 + log2-depth of the sum) eps relative); S and B are running sums of
+ * k terms, (k - 1) eps of their absolute sums; ds_j adds three roundings, dx_e three more.  There is no bound relative to |dx_e|
+ * alone - q_j - B and ds_e - D cancel - so the tests measure the error relative to max |d_logits| against the torch fp32 backward's.
+ * Limits: flute_moe_gate's.  One wave per token, lane l holding experts l, l + 64, ...; the sums over the slots are wave-uniform
+ * loops on values fetched by v_readlane; no LDS, no atomics, plain vector stores.  A non-finite row gives what the arithmetic gives
+ * and touches no other token.  The host reads nothing, the grid follows from T alone (hipGraph-capturable); equal arguments give
+ * equal bits, and a token's result depends neither on T nor on the row it sits in.
+ * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE (logit_dtype, then scoring); FLUTE_ERR_SHAPE (flute_moe_gate's
+ * conditions); T == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL (logits, ids, d_logits; neither gradient source given;
+ * one of d_row_weight / pos without the other). */
+int flute_moe_gate_grad(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
+                        const int32_t* ids, const float* d_weights, const float* d_row_weight, const int32_t* pos, void* d_logits,
+                        void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */

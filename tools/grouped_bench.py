@@ -9,6 +9,7 @@
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
+    python tools/grouped_bench.py --mode router_grad [--out profiles/grouped_moe_router_grad.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -76,6 +77,12 @@ row ranges the host knows - the loop's best case: inside FluteExperts the counts
 --mode scale_grad's method at the same six lines: dT2 alone, dT2 + dS in one launch pair ("fused"), `qgemm_grouped_scale_grad`
 followed by the dT2-only pair ("separate": what the fused form replaces), and a per-expert loop of the dense
 flute_amd.qgemm_table_grad (dT2 only) on row ranges the host knows.  Passes per process: table, fused, separate, loop, twice.
+
+--mode router_grad times the router's backward at Mixtral's shapes, 512 and 4096 tokens, top-2, by --mode input_grad's method in one
+process: the weighted launch's chain behind the unweighted input gradient (torch ops against flute_amd.moe_weight_grad, with a copy_
+of 1.5 R K 16-bit elements as the yardstick of the same traffic), the gate's backward (torch ops against flute_amd.moe_gate_grad) for
+an E = 8 top-2 softmax router and an E = 256 top-8 group-limited sigmoid router, moe_combine's backward (the torch chain against
+flute_amd.moe_gather), and one whole backward step of FluteSparseMoeBlock with the router training, native_router_grad off and on.
 
 --mode prefill times the grouped FORWARD at prefill and training row counts, where the block form (qgemm_grouped_blocks.h) meets
 the row form (qgemm_grouped.h): W4G64 fp16 at Mixtral's two projections with 512, 4096 and 8192 routed rows (the counts of
@@ -1280,6 +1287,175 @@ def main_swiglu_grad(args, device, stacks=None, copies=None):
     print("wrote", out)
 
 
+# ---- --mode router_grad -----------------------------------------------------------------------------------------------
+
+class WeightChain:
+    """What follows the unweighted input gradient when row_weight trains: `_grouped_weighted_backward`'s torch lines, or one
+    moe_weight_grad launch.  dHp and h [R, K] stand for the input gradient and the weighted launch's input."""
+
+    def __init__(self, R, K, device, native):
+        import flute_amd
+        self.fa, self.native, self.R = flute_amd, native, R
+        gen = torch.Generator(device=device).manual_seed(R)
+        self.dhp = (torch.randn(R, K, device=device, generator=gen) / 4).to(DTYPE)
+        self.h = torch.randn(R, K, device=device, generator=gen).to(DTYPE)
+        self.rw = torch.rand(R, device=device, generator=gen)
+        ends = torch.tensor(even_counts(R - 3, E)).cumsum(0)               # three rows no expert serves
+        self.offsets = torch.cat([torch.zeros(1, dtype=ends.dtype), ends]).int().to(device)
+
+    def step(self, i):
+        if self.native:
+            return self.fa.moe_weight_grad(self.dhp, self.h, self.rw, self.offsets)
+        R, dev = self.R, self.h.device
+        dh = self.dhp.float()
+        served = torch.arange(R, device=dev) < self.offsets[-1].clamp(0, R)
+        d_weight = torch.where(served, (dh * self.h.float()).sum(dim=1), torch.zeros((), device=dev))
+        return d_weight, (self.rw[:, None] * dh).to(self.h.dtype)
+
+
+class Copy16:
+    """`copy_` of `n` 16-bit elements: 2 n bytes read and 2 n written."""
+
+    def __init__(self, n, device):
+        self.src = torch.randn(n, device=device, dtype=torch.float32).to(DTYPE)
+        self.dst = torch.empty_like(self.src)
+
+    def step(self, i):
+        return self.dst.copy_(self.src)
+
+
+class GateBackward:
+    """The backward of a gate-route launch on fp16 logits: `_MoeGateFunction.backward`'s torch lines, or one moe_gate_grad launch."""
+
+    def __init__(self, tokens, shape, device, native):
+        import flute_amd
+        self.fa, self.native = flute_amd, native
+        self.E, self.k, self.scoring, self.renorm, self.scale, groups = shape
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        self.logits = torch.randn(tokens, self.E, device=device, generator=gen).to(DTYPE)
+        if groups is None:
+            outs = flute_amd.moe_gate_route(self.logits, self.k, self.E, self.scoring, self.renorm, None, self.scale)
+        else:
+            outs = flute_amd.moe_gate_route_limited(self.logits, self.k, *groups, self.E, self.scoring, self.renorm, None, self.scale)
+        self.ids, self.pos = outs[0], outs[5]
+        self.d_weights = torch.zeros(tokens, self.k, device=device)            # (autograd hands zeros for the unused `weights`)
+        self.d_row_weight = torch.randn(tokens * self.k, device=device, generator=gen)
+
+    def step(self, i):
+        if self.native:
+            return self.fa.moe_gate_grad(self.logits, self.ids, self.d_weights, self.scoring, self.renorm, self.scale,
+                                         grad_row_weight=self.d_row_weight, pos=self.pos)
+        d_weights = self.d_weights + self.d_row_weight.index_select(0, self.pos.reshape(-1).long()).view_as(self.d_weights)
+        with torch.enable_grad():
+            x = self.logits.detach().float().requires_grad_(True)
+            s = torch.softmax(x, dim=1) if self.scoring == "softmax" else torch.sigmoid(x)
+            w = s.gather(1, self.ids.long())
+            if self.renorm:
+                w = w / w.sum(dim=1, keepdim=True)
+            (dx,) = torch.autograd.grad(w * self.scale, x, d_weights)
+        return dx.to(self.logits.dtype)
+
+
+class CombineBackward:
+    """moe_combine's backward on dOut [T, N]: `_MoeCombineFunction.backward`'s torch lines, or one moe_gather launch on `rows`."""
+
+    def __init__(self, tokens, N, device, native):
+        import flute_amd
+        self.fa, self.native = flute_amd, native
+        ids = torch.rand(tokens, E, generator=torch.Generator().manual_seed(tokens)).topk(TOPK, dim=1).indices.to(device)
+        self.offsets, self.rows, _, self.pos, _ = flute_amd.moe_route(ids, None, E)
+        self.dOut = torch.randn(tokens, N, device=device, generator=torch.Generator(device=device).manual_seed(tokens)).to(DTYPE)
+
+    def step(self, i):
+        if self.native:
+            return self.fa.moe_gather(self.dOut, self.rows, self.offsets)
+        pos, offsets = self.pos, self.offsets
+        T, k = pos.shape
+        R, dev = T * k, pos.device
+        p = pos.reshape(-1).long()
+        inside = (p >= 0) & (p < R)
+        token = torch.arange(T, device=dev).repeat_interleave(k)
+        rows = torch.full((R + 1,), T, dtype=torch.long, device=dev).scatter_(0, torch.where(inside, p, R), token)[:R]
+        named = (rows < T) & (torch.arange(R, device=dev) < offsets[-1].clamp(0, R))
+        return self.dOut.index_select(0, rows.clamp(max=T - 1)).masked_fill_(~named[:, None], 0)
+
+
+class BlockBackward:
+    """One forward and backward step of FluteSparseMoeBlock (softmax top-2, renormalised) on copy i of step_stacks with the router
+    training: the gradient reaches the hidden states and the router's weight."""
+
+    def __init__(self, stacks, tokens, device, native):
+        from flute_amd.integrations import moe
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        router = (torch.randn(E, 4096, device=device, generator=gen) * 0.02).to(DTYPE)
+        self.blocks = [moe.FluteSparseMoeBlock(router.clone(), moe.FluteExperts(g, u, d, fused=True, native_routing=True,
+                                                                                native_router_grad=native), TOPK, renormalize=True)
+                       for g, u, d in stacks]
+        for b in self.blocks:
+            b.router_weight.requires_grad_()
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE).requires_grad_()
+        self.dOut = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+
+    def step(self, i):
+        block = self.blocks[i % len(self.blocks)]
+        return torch.autograd.grad(block(self.hidden), (self.hidden, block.router_weight), self.dOut)
+
+
+ROUTERS = {"E8 top2 softmax": (8, 2, "softmax", False, 1.0, None),
+           "E256 top8 sigmoid n_group8 topk_group4": (256, 8, "sigmoid", True, 2.5, (8, 4))}
+
+
+def main_router_grad(args, device):
+    K, F = 4096, 14336
+    copies = prefill_copies(E, F, K, BITS, stacks=3)
+    stacks = step_stacks(copies, device)
+    rows = []
+    for tokens in (512, 4096):
+        R = tokens * TOPK
+        layers = {"weight chain torch": WeightChain(R, F, device, False), "weight chain native": WeightChain(R, F, device, True),
+                  "copy_ yardstick": Copy16(3 * R * F // 2, device),
+                  "combine backward torch": CombineBackward(tokens, K, device, False),
+                  "combine backward native": CombineBackward(tokens, K, device, True),
+                  "block backward off": BlockBackward(stacks, tokens, device, False),
+                  "block backward on": BlockBackward(stacks, tokens, device, True)}
+        for name, shape in ROUTERS.items():
+            layers["gate backward torch, " + name] = GateBackward(tokens, shape, device, False)
+            layers["gate backward native, " + name] = GateBackward(tokens, shape, device, True)
+        us, spread, replays = time_forms(layers, args)
+        row = {"what": "router backward, native_router_grad off / on", "tokens": tokens, "rows": R, "K": K, "F": F, "experts": E,
+               "top_k": TOPK, "weight_copies": copies, "us": us,
+               "weight_chain_torch_over_native": round(us["weight chain torch"] / us["weight chain native"], 3),
+               "weight_chain_native_over_copy": round(us["weight chain native"] / us["copy_ yardstick"], 3),
+               "weight_chain_native_TBps": round(6.0 * R * F / us["weight chain native"] * 1e-6, 3),
+               "copy_TBps": round(6.0 * R * F / us["copy_ yardstick"] * 1e-6, 3),
+               "combine_backward_torch_over_native": round(us["combine backward torch"] / us["combine backward native"], 3),
+               "block_on_over_off": round(us["block backward on"] / us["block backward off"], 4),
+               "block_off_minus_on_us": round(us["block backward off"] - us["block backward on"], 3),
+               "block_replay_range_us": {n: [round(min(min(p) for p in replays[n]), 3), round(max(max(p) for p in replays[n]), 3)]
+                                         for n in ("block backward off", "block backward on")},
+               "spread": spread, "replays_us": replays}
+        for name in ROUTERS:
+            row["gate_backward_torch_over_native, " + name] = round(us["gate backward torch, " + name] /
+                                                                    us["gate backward native, " + name], 3)
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        del layers
+        torch.cuda.empty_cache()
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"what": "the router's backward at Mixtral's shapes (E = 8, top-2, K = 4096, F = 14336, W4G64 fp16): the weighted "
+                               "launch's chain behind the unweighted input gradient as torch ops and as flute_amd.moe_weight_grad, with "
+                               "a copy_ of 1.5 R F 16-bit elements as the yardstick of the same traffic; the gate's backward as torch "
+                               "ops and as flute_amd.moe_gate_grad for two routers; moe_combine's backward as its torch chain and as "
+                               "flute_amd.moe_gather; one whole forward + backward step of FluteSparseMoeBlock(fused=True, "
+                               "native_routing=True) with the router training, native_router_grad off and on; hipGraph replays, "
+                               "device-clock stamps, cold caches, median of the replays, two alternating passes of every contender in "
+                               "one process",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+    print("wrote", args.out)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -1354,7 +1530,7 @@ def main():
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
     ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad",
-                                       "prefill"],
+                                       "prefill", "router_grad"],
                     default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -1372,7 +1548,8 @@ def main():
                                                    "input_grad": "grouped_moe_input_grad_blocks.json",
                                                    "scale_grad": "grouped_moe_scale_grad.json",
                                                    "table_grad": "grouped_moe_table_grad.json",
-                                                   "prefill": "grouped_moe_prefill.json"}[args.mode])
+                                                   "prefill": "grouped_moe_prefill.json",
+                                                   "router_grad": "grouped_moe_router_grad.json"}[args.mode])
     if args.mode in ("scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
@@ -1394,6 +1571,8 @@ def main():
         return main_mlp(args, device)
     if args.mode == "prefill":
         return main_prefill(args, device)
+    if args.mode == "router_grad":
+        return main_router_grad(args, device)
     if args.mode == "input_grad":
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
