@@ -58,6 +58,9 @@ moe_gate = ops.moe_gate
 moe_gate_route = ops.moe_gate_route
 moe_gate_limited = ops.moe_gate_limited
 moe_gate_route_limited = ops.moe_gate_route_limited
+# the routing over many workgroups, for prefill and training token counts: the same arrays bit for bit, three launches
+moe_route_wide = ops.moe_route_wide
+moe_gate_route_wide = ops.moe_gate_route_wide
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

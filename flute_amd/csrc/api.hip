@@ -2085,6 +2085,84 @@ int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_gro
                            row_weight, pos, stream);
 }
 
+// ---- the routing over many workgroups (moe_route_wide.hip) ----------------------------------------------------------------------
+// the automatic chunk, a function of (gated, T, k) alone: gated one token per wave and round, ungated about FLUTE_MOE_ROUTE_WIDE_PAIRS
+// pairs; either grows to keep C <= FLUTE_MOE_ROUTE_MAX_CHUNKS
+static int route_wide_auto_chunk(bool gated, int T, int k) {
+    const int want = gated ? FLUTE_MOE_GATE_ROUTE_WIDE_TOKENS : (FLUTE_MOE_ROUTE_WIDE_PAIRS + (k > 0 ? k : 1) - 1) / (k > 0 ? k : 1);
+    const int cap = (T + FLUTE_MOE_ROUTE_MAX_CHUNKS - 1) / FLUTE_MOE_ROUTE_MAX_CHUNKS;
+    return want > cap ? want : cap;
+}
+// C for a checked shape, 0 for a chunk_tokens the entries refuse; chunk_tokens 0 is resolved in place.  No pair: one chunk.
+static int route_wide_chunks(bool gated, int T, int k, int* chunk_tokens) {
+    if (*chunk_tokens < 0) return 0;
+    if (*chunk_tokens == 0) *chunk_tokens = route_wide_auto_chunk(gated, T, k);
+    if (T == 0 || k == 0) return 1;
+    const int C = (int)(((long long)T + *chunk_tokens - 1) / *chunk_tokens);
+    return C <= FLUTE_MOE_ROUTE_MAX_CHUNKS ? C : 0;
+}
+static size_t route_wide_bytes(int C, int E) { return (size_t)(C + 1) * (size_t)(E + 1) * sizeof(int32_t); }
+
+size_t flute_moe_route_wide_workspace(int T, int k, int E, int chunk_tokens) {
+    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS || (long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return 0;
+    int ct = chunk_tokens, ctg = chunk_tokens;                     // automatic: enough for either entry's own chunk
+    const int Cu = route_wide_chunks(false, T, k, &ct), Cg = route_wide_chunks(true, T, k, &ctg);
+    const int C = Cg > Cu ? Cg : Cu;
+    return C ? route_wide_bytes(C, E) : 0;
+}
+
+int flute_moe_route_wide(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
+                         int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
+                         size_t workspace_bytes, int chunk_tokens, void* stream) {
+    if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;
+    if (weight_dtype != FLUTE_F16 && weight_dtype != FLUTE_BF16 && weight_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
+    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
+    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    const int C = route_wide_chunks(false, T, k, &chunk_tokens);
+    if (C == 0) return FLUTE_ERR_SHAPE;
+    const int P = T * k;
+    if (P == 0 && !offsets) return FLUTE_OK;
+    if (P > 0 && (!ids || !perm || !rows || !pos || (weights && !row_weight))) return FLUTE_ERR_NULL;
+    if (!offsets || (C > 1 && !workspace)) return FLUTE_ERR_NULL;
+    if (C > 1 && workspace_bytes < route_wide_bytes(C, E)) return FLUTE_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (C == 1) return moe_route_dispatch(id_dtype, weight_dtype, P, k, E, ids, weights, offsets, perm, rows, row_weight, pos, st);
+    return moe_route_wide_dispatch(id_dtype, weight_dtype, T, k, E, chunk_tokens, ids, weights, offsets, perm, rows, row_weight, pos,
+                                   workspace, st);
+}
+
+int flute_moe_gate_route_wide(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
+                              int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                              int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
+                              size_t workspace_bytes, int chunk_tokens, void* stream) {
+    const GateGroups g = {n_group, topk_group, group_score};
+    const int rc = check_moe_gate(logit_dtype, T, E, k, &g, scoring);
+    if (rc) return rc;
+    const int C = route_wide_chunks(true, T, k, &chunk_tokens);
+    if (C == 0) return FLUTE_ERR_SHAPE;
+    if (T == 0 && !offsets) return FLUTE_OK;
+    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
+    if (!offsets || (C > 1 && !workspace)) return FLUTE_ERR_NULL;
+    if (C > 1 && workspace_bytes < route_wide_bytes(C, E)) return FLUTE_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (C == 1)
+        return moe_gate_dispatch(logit_dtype, T, E, k, &g, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm, rows,
+                                 row_weight, pos, st);
+    return moe_gate_route_wide_dispatch(logit_dtype, T, E, k, &g, scoring, renormalize, scale, chunk_tokens, logits, bias, ids, weights,
+                                        offsets, perm, rows, row_weight, pos, workspace, st);
+}
+
+int flute_moe_route_form(int gated, int T, int k, int E, int num_sms) {
+    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
+    if (gated && (k < 1 || k > E || k > FLUTE_MOE_GATE_MAX_TOPK)) return FLUTE_ERR_SHAPE;
+    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    (void)num_sms;                                                 // the crossovers were measured on a whole part; see the header
+    int ct = 0;
+    return (long long)T * k >= FLUTE_MOE_ROUTE_WIDE_MIN_PAIRS && route_wide_chunks(gated != 0, T, k, &ct) > 1
+               ? FLUTE_MOE_ROUTE_FORM_WIDE
+               : FLUTE_MOE_ROUTE_FORM_ONE;
+}
+
 int flute_moe_combine(int dtype, int T, int k, int E, int N, const void* Y, const int32_t* pos, const int32_t* offsets,
                       void* out, void* stream) {
     if (dtype != FLUTE_F16 && dtype != FLUTE_BF16) return FLUTE_ERR_DTYPE;

@@ -158,6 +158,19 @@ struct GateGroups {
 int moe_gate_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
                       const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
                       int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream);
+// the same routing over many workgroups (moe_route_wide.hip): chunks of chunk_tokens tokens, C = ceil(T / chunk_tokens) > 1 of them, in
+// three launches - count (gated: moe_gate_count_dispatch, moe_gate.hip, which gates each chunk's tokens first), scan, place; workspace:
+// (C + 1) (E + 1) int32, every word the later launches read written by the earlier ones.  The caller has checked shapes and sizes.
+int moe_route_wide_dispatch(int id_dtype, int weight_dtype, int T, int k, int E, int chunk_tokens, const void* ids,
+                            const void* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
+                            void* workspace, hipStream_t stream);
+int moe_gate_route_wide_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize,
+                                 float scale, int chunk_tokens, const void* logits, const float* bias, int32_t* ids, float* weights,
+                                 int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
+                                 hipStream_t stream);
+int moe_gate_count_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
+                            int chunk_tokens, const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* hist,
+                            hipStream_t stream);
 // its end (moe_combine.hip): out[t] = round_T(fp32 sum over the slots of Y[pos[t, j]]), positions outside [0, clamp(offsets[E])) skipped;
 // the grid is tokens x chunks of 1024 columns (0: it does not fit)
 unsigned moe_combine_grid(int T, int N);

@@ -23,6 +23,9 @@
 //   moe_gate_route_kernel  one workgroup of 16 waves (moe_route_kernel's design point): wave w takes tokens w, w + 16, ...,
 //                          then a barrier, then the count / scan / place phases of moe_route_sort.h on the ids and
 //                          weights just written (same CU, workgroup-scope fence before the barrier).
+//   moe_gate_count_kernel  the first launch of the multi-workgroup routing (moe_route_wide.hip), grid = its chunks: workgroup c's wave
+//                          w takes the chunk's tokens w, w + 16, ..., then the same fence and barrier, then the count of the chunk's
+//                          pairs per expert into its row of the workspace - it reads back only what it wrote itself.
 // Group-limited selection (flute_moe_gate_limited / flute_moe_gate_route_limited) is the same two kernels with their LIMITED
 // parameter set: gate_token then has one more stage between key and choice (without LIMITED it is not compiled in, and the
 // kernels' group arguments, the last of their list, are not read):
@@ -190,7 +193,7 @@ static __device__ __forceinline__ void gate_token(const typename GateLogit<L>::t
     }
 }
 
-// ---- the two kernels ----------------------------------------------------------------------------------------------------------
+// ---- the kernels --------------------------------------------------------------------------------------------------------------
 // LIMITED picks gate_token's instantiation.  The group arguments come last: every other argument sits where it sits without them,
 // and an instantiation without LIMITED does not read them.
 template <typename L, int NV, bool LIMITED>
@@ -227,6 +230,25 @@ __global__ __launch_bounds__(kRouteThreads) void moe_gate_route_kernel(const typ
     route_sort_phases<int32_t, float>(ids, weights, T * k, k, E, nbits, offsets, perm, rows, row_weight, pos);
 }
 
+template <typename L, int NV, bool LIMITED>
+__global__ __launch_bounds__(kRouteThreads) void moe_gate_count_kernel(const typename GateLogit<L>::type* __restrict__ logits,
+                                                                       const float* __restrict__ bias, int T, int E, int k,
+                                                                       int scoring, int renormalize, float scale, int chunk_tokens,
+                                                                       int32_t* ids, float* weights, int32_t* __restrict__ hist,
+                                                                       GateGroups g) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gs = LIMITED ? E / g.n_group : 0;
+    int lo, hi;
+    route_chunk_pairs(blockIdx.x, chunk_tokens, T, k, &lo, &hi);
+    for (int t = lo / k + w; t < hi / k; t += kRouteWaves)      // lo, hi: multiples of k, the chunk's tokens
+        gate_token<L, NV, LIMITED>(logits + (size_t)t * E, bias, E, k, scoring, renormalize, scale, g.n_group, gs, g.topk_group,
+                                   g.group_score, lane, ids + (size_t)t * k, weights + (size_t)t * k);
+    __threadfence_block();
+    __syncthreads();                                    // the chunk's ids are written and visible in the workgroup
+    route_count_chunk<int32_t>(ids, lo, hi, E, hist + (size_t)blockIdx.x * (E + 1));
+}
+
 // ---- the host side: one call, one launch, the ladder of classes and the ladder of logit types ---------------------------------
 struct GateCall {
     int T, E, k, scoring, renormalize;
@@ -240,12 +262,23 @@ struct GateCall {
     float* row_weight;
     int32_t* pos;
     hipStream_t stream;
+    int chunk_tokens;                                   // hist non-null: the counting form, grid ceil(T / chunk_tokens), and of the
+    int32_t* hist;                                      // routing arrays none is used
 };
 
 template <typename L, int NV, bool LIMITED>
 static int gate_launch(const GateCall& c) {
     const typename GateLogit<L>::type* x = reinterpret_cast<const typename GateLogit<L>::type*>(c.logits);
-    if (!c.offsets) {
+    if (c.hist) {
+        auto kern = moe_gate_count_kernel<L, NV, LIMITED>;
+        const size_t lds = route_lds_bytes(c.E);
+        if (lds > 65536 &&
+            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return FLUTE_ERR_LAUNCH;
+        const unsigned grid = (unsigned)((c.T + c.chunk_tokens - 1) / c.chunk_tokens);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kRouteThreads), lds, c.stream, x, c.bias, c.T, c.E, c.k, c.scoring, c.renormalize,
+                           c.scale, c.chunk_tokens, c.ids, c.weights, c.hist, c.groups);
+    } else if (!c.offsets) {
         const unsigned grid = (unsigned)((c.T + kGateWaves - 1) / kGateWaves);
         hipLaunchKernelGGL((moe_gate_kernel<L, NV, LIMITED>), dim3(grid), dim3(kGateThreads), 0, c.stream, x, c.bias, c.T, c.E, c.k,
                            c.scoring, c.renormalize, c.scale, c.ids, c.weights, c.groups);
@@ -278,15 +311,26 @@ static int gate_by_type(int logit_dtype, const GateCall& c) {
     return gate_by_class<float, LIMITED>(c);
 }
 
+static int gate_dispatch(int logit_dtype, const GateGroups* groups, GateCall c) {
+    // every group allowed: every expert is, and the unlimited kernels serve the call - bit for bit by construction.  T == 0 (the
+    // routed form's E + 1 zeros) gates nothing and goes the same way.
+    const bool limited = groups && groups->topk_group != groups->n_group && c.T != 0;
+    c.groups = limited ? *groups : GateGroups{};
+    return limited ? gate_by_type<true>(logit_dtype, c) : gate_by_type<false>(logit_dtype, c);
+}
+
 int moe_gate_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
                       const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
                       int32_t* rows, float* row_weight, int32_t* pos, hipStream_t stream) {
-    // every group allowed: every expert is, and the unlimited kernels serve the call - bit for bit by construction.  T == 0 (the
-    // routed form's E + 1 zeros) gates nothing and goes the same way.
-    const bool limited = groups && groups->topk_group != groups->n_group && T != 0;
-    const GateCall c = {T, E, k, scoring, renormalize != 0, scale, limited ? *groups : GateGroups{}, logits, bias, ids,
-                        weights, offsets, perm, rows, row_weight, pos, stream};
-    return limited ? gate_by_type<true>(logit_dtype, c) : gate_by_type<false>(logit_dtype, c);
+    return gate_dispatch(logit_dtype, groups, {T, E, k, scoring, renormalize != 0, scale, GateGroups{}, logits, bias, ids, weights,
+                                               offsets, perm, rows, row_weight, pos, stream, 0, nullptr});
+}
+
+int moe_gate_count_dispatch(int logit_dtype, int T, int E, int k, const GateGroups* groups, int scoring, int renormalize, float scale,
+                            int chunk_tokens, const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* hist,
+                            hipStream_t stream) {
+    return gate_dispatch(logit_dtype, groups, {T, E, k, scoring, renormalize != 0, scale, GateGroups{}, logits, bias, ids, weights,
+                                               nullptr, nullptr, nullptr, nullptr, nullptr, stream, chunk_tokens, hist});
 }
 
 }  // namespace flute_amd

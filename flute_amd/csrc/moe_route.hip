@@ -17,8 +17,9 @@
 // are plain vector stores.  The ids are read twice from global memory except a wave's first 64, which stay in a
 // register (at decode sizes, P <= 1024, that is all of them and the load overlaps the clearing of the table).
 // One workgroup is the design point: decode-sized P.  It is correct for every P the ABI accepts (each wave loops over
-// its range), but a prefill-sized P is sorted by 1024 threads; a multi-workgroup form does not exist.
-// The device code of the sort is moe_route_sort.h (moe_gate.hip runs the same phases behind its gating).
+// its range), but a prefill-sized P is sorted by 1024 threads: the multi-workgroup form for those is moe_route_wide.hip.
+// The device code of the sort is moe_route_sort.h (moe_gate.hip runs the same phases behind its gating, moe_route_wide.hip
+// one chunk of the pairs per workgroup).
 #include "kernels.h"
 #include "moe_route_sort.h"
 #include "../../include/flute_amd.h"

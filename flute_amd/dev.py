@@ -86,6 +86,16 @@ def grouped_input_grad_form(E: int, rows: int, N: int, K: int, num_bits: int, gr
     return {1: "slabs", 2: "blocks"}[rc]
 
 
+def moe_route_form(T: int, k: int, E: int, gated: bool = True, num_sms: int = 0) -> str:
+    """The routing the automatic rule takes for T tokens, top-k, E experts - "one": `moe_gate_route[_limited]` (`gated`) or
+    `moe_route`, one workgroup; "wide": `moe_gate_route_wide` or `moe_route_wide`; host only, shapes alone, monotone in T
+    (flute_moe_route_form).  A shape the launch itself refuses raises."""
+    rc = _lib.get().flute_moe_route_form(int(bool(gated)), T, k, E, num_sms)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "one", 2: "wide"}[rc]
+
+
 def overrides_from_tuple(t) -> Optional[Overrides]:
     """(family, m_block, waves, kw, splitk, m_tiles, slabs_per_wave[, ring_depth[, one_shot]]) -> Overrides; None
     when every field is -1 (automatic plan)."""

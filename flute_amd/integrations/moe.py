@@ -270,13 +270,22 @@ class FluteExperts(torch.nn.Module):
     `native_router_grad` (with `fused=True` and `native_routing=True`): the ops' keyword of that name - when the router trains,
     the weighted launch's backward forms d row_weight and d h in one `moe_weight_grad` launch, the gate-route launch's
     backward is one `moe_gate_grad` launch, and `moe_combine` gets `rows`, so its backward is one `moe_gather` launch; the
-    default runs torch ops in all three places.  The forward's bits are the same either way."""
+    default runs torch ops in all three places.  The forward's bits are the same either way.
+    `wide_routing` (with `native_routing=True`): which routing launch runs - False: the one-workgroup `moe_route` /
+    `moe_gate_route[_limited]` at every token count (the default, today's forward line for line); True: the multi-workgroup
+    `moe_route_wide` / `moe_gate_route_wide`, three launches meant for prefill and training token counts; "auto": the wide form
+    where `flute_amd.dev.moe_route_form` takes it for the step's shapes.  Outputs and every gradient are bit for bit the same."""
 
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
                  fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
-                 native_glu_grad: bool = False, native_router_grad: bool = False) -> None:
+                 native_glu_grad: bool = False, native_router_grad: bool = False,
+                 wide_routing: Union[bool, str] = False) -> None:
         super().__init__()
         _check_glu_blocks(glu_blocks, fused)
+        if not (wide_routing is False or wide_routing is True or (isinstance(wide_routing, str) and wide_routing == "auto")):
+            raise ValueError("FluteExperts: wide_routing is False, True or 'auto', not %r" % (wide_routing,))
+        if wide_routing is not False and not native_routing:
+            raise ValueError("FluteExperts: wide_routing selects the kernels of the routing launch and needs native_routing=True")
         if native_router_grad and not (fused and native_routing):
             raise ValueError("FluteExperts: native_router_grad selects the backward of the weighted, gate-route and combine "
                              "launches and needs fused=True and native_routing=True")
@@ -297,15 +306,16 @@ class FluteExperts(torch.nn.Module):
         self.glu_blocks = glu_blocks
         self.native_glu_grad = bool(native_glu_grad)
         self.native_router_grad = bool(native_router_grad)
+        self.wide_routing = wide_routing
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
                      glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
-                     native_router_grad: bool = False) -> "FluteExperts":
+                     native_router_grad: bool = False, wide_routing: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
-                   native_glu_grad=native_glu_grad, native_router_grad=native_router_grad)
+                   native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -352,7 +362,16 @@ class FluteExperts(torch.nn.Module):
 
     def _gate_route(self, router_logits, top_k, scoring, renormalize, bias, scale, groups=None):
         """`moe_gate_route` / `moe_gate_route_limited` (`groups` = (n_group, topk_group, group_score)); with the module's
-        `native_router_grad` the same launch through the ops' shared entry, which carries the keyword to its backward."""
+        `native_router_grad` the same launch through the ops' shared entry, which carries the keyword to its backward.  With
+        `wide_routing` taken for these shapes: `moe_gate_route_wide`, the one op of both gatings."""
+        if self._takes_wide_routing(router_logits.shape[0], top_k, gated=True):
+            n_group, topk_group, group_score = (1, 1, "max") if groups is None else groups
+            if self.native_router_grad:
+                return flute_amd.ops._moe_gate_entry(router_logits, top_k, scoring, renormalize, bias, scale, routed=True,
+                                                     num_experts=self.num_experts, groups=(n_group, topk_group, group_score),
+                                                     native_router_grad=True, wide=0)
+            return flute_amd.moe_gate_route_wide(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale,
+                                                 n_group, topk_group, group_score)
         if self.native_router_grad:
             return flute_amd.ops._moe_gate_entry(router_logits, top_k, scoring, renormalize, bias, scale, routed=True,
                                                  num_experts=self.num_experts, groups=groups, native_router_grad=True)
@@ -385,6 +404,12 @@ class FluteExperts(torch.nn.Module):
                      topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
                      down.template_id, num_sms)
         return torch.zeros_like(hidden).index_add_(0, token, y)
+
+    def _takes_wide_routing(self, tokens: int, top_k: int, gated: bool) -> bool:
+        """Whether this step's routing is the multi-workgroup one: `wide_routing`, "auto" resolved from the shapes alone."""
+        if self.wide_routing != "auto":
+            return self.wide_routing
+        return flute_amd.dev.moe_route_form(tokens, top_k, self.num_experts, gated=gated) == "wide"
 
     def _takes_glu_blocks(self, hidden, rows: int, num_sms: int) -> bool:
         """Whether this step's fused GLU launch is the block one: `glu_blocks`, "auto" resolved from the shapes alone."""
@@ -422,11 +447,12 @@ class FluteExperts(torch.nn.Module):
         """`moe_route` (moe_route.hip) in place of sort_by_expert and its glue, `moe_combine` (moe_combine.hip) in place
         of zeros_like + index_add_: the sum over a token's experts is taken in fp32 in slot order and rounded once, and
         rows no expert served are never read.  Fused: four launches, nothing else."""
-        offsets, rows, row_weight, pos, _ = flute_amd.moe_route(topk_ids, topk_weights, self.num_experts)
+        route = flute_amd.moe_route_wide if self._takes_wide_routing(*topk_ids.shape, gated=False) else flute_amd.moe_route
+        offsets, rows, row_weight, pos, _ = route(topk_ids, topk_weights, self.num_experts)
         return self._forward_routed(hidden, offsets, rows, row_weight, pos)
 
     def _forward_routed(self, hidden, offsets, rows, row_weight, pos):
-        """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`)."""
+        """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`, their `_wide` forms)."""
         gate, up, down = self.gate, self.up, self.down
         if self.fused:
             num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)

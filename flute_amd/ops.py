@@ -935,16 +935,53 @@ def moe_route(topk_ids: torch.Tensor, topk_weights, num_experts: int):
     arguments give equal bits."""
     _validate_moe_route(topk_ids, topk_weights, num_experts)
     if _records_grad(topk_weights):
-        return _MoeRouteFunction.apply(topk_ids, topk_weights, num_experts)
+        return _MoeRouteFunction.apply(topk_ids, topk_weights, num_experts, None)
     return _moe_route_call(topk_ids, topk_weights, num_experts)
 
 
+MOE_ROUTE_MAX_CHUNKS = 8192             # FLUTE_MOE_ROUTE_MAX_CHUNKS
+
+
+def _validate_chunk_tokens(chunk_tokens, T):
+    """`chunk_tokens` of the wide routing ops: None (automatic) or an int >= 1 that leaves at most MOE_ROUTE_MAX_CHUNKS chunks;
+    returns the ABI's value, 0 for automatic."""
+    if chunk_tokens is None:
+        return 0
+    if isinstance(chunk_tokens, bool) or not isinstance(chunk_tokens, int):
+        raise TypeError
+    if chunk_tokens < 1 or -(-T // chunk_tokens) > MOE_ROUTE_MAX_CHUNKS:
+        raise ValueError
+    return chunk_tokens
+
+
+def _route_wide_workspace(T, k, E, chunk_tokens, dev):
+    """The wide launches' workspace: the queried size, from the caching allocator per call (capturable); the kernels write every
+    word they read, so it is not cleared."""
+    return torch.empty(_lib.get().flute_moe_route_wide_workspace(T, k, E, chunk_tokens), dtype=torch.uint8, device=dev)
+
+
+def moe_route_wide(topk_ids: torch.Tensor, topk_weights, num_experts: int, chunk_tokens=None):
+    """`moe_route` over many workgroups, for prefill and training token counts: the same five arrays (offsets, rows,
+    row_weight, pos, perm), bit for bit, from three launches - count, scan, place (moe_route_wide.hip) - in which chunk c
+    of `chunk_tokens` consecutive tokens is one workgroup's and no workgroup waits on another.  `chunk_tokens` None: the
+    automatic chunk, the tokens of 512 pairs; an int >= 1 (at most 8192 chunks) is for tests and sweeps.  One chunk (T <=
+    chunk_tokens) is served by `moe_route`'s own launch.  The workspace is allocated per call; the host reads nothing
+    (no synchronise, capturable); equal arguments give equal bits; autograd as `moe_route`.
+    `flute_amd.dev.moe_route_form(T, k, E, gated=False)` says where this form pays."""
+    _validate_moe_route(topk_ids, topk_weights, num_experts)
+    wide = _validate_chunk_tokens(chunk_tokens, topk_ids.shape[0])
+    if _records_grad(topk_weights):
+        return _MoeRouteFunction.apply(topk_ids, topk_weights, num_experts, wide)
+    return _moe_route_call(topk_ids, topk_weights, num_experts, wide)
+
+
 class _MoeRouteFunction(torch.autograd.Function):
-    """`moe_route` under autograd: row_weight is a permutation of topk_weights, so d topk_weights = d row_weight[pos]."""
+    """`moe_route` / `moe_route_wide` (`wide`: its chunk_tokens, None for the one-workgroup launch) under autograd: row_weight
+    is a permutation of topk_weights, so d topk_weights = d row_weight[pos]."""
 
     @staticmethod
-    def forward(ctx, topk_ids, topk_weights, num_experts):
-        offsets, rows, row_weight, pos, perm = _moe_route_call(topk_ids, topk_weights, num_experts)
+    def forward(ctx, topk_ids, topk_weights, num_experts, wide):
+        offsets, rows, row_weight, pos, perm = _moe_route_call(topk_ids, topk_weights, num_experts, wide)
         ctx.save_for_backward(pos)
         ctx.dtype = topk_weights.dtype
         ctx.mark_non_differentiable(offsets, rows, pos, perm)
@@ -954,10 +991,11 @@ class _MoeRouteFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_offsets, d_rows, d_row_weight, d_pos, d_perm):
         (pos,) = ctx.saved_tensors
-        return None, d_row_weight.index_select(0, pos.reshape(-1).long()).view(pos.shape).to(ctx.dtype), None
+        return None, d_row_weight.index_select(0, pos.reshape(-1).long()).view(pos.shape).to(ctx.dtype), None, None
 
 
-def _moe_route_call(topk_ids, topk_weights, num_experts):
+def _moe_route_call(topk_ids, topk_weights, num_experts, wide=None):
+    """One routing call: flute_moe_route, or with `wide` (the ABI's chunk_tokens, 0 automatic) flute_moe_route_wide."""
     dev = topk_ids.device
     if not all(t.is_cuda and t.device == dev for t in (topk_ids,) + (() if topk_weights is None else (topk_weights,))):
         raise RuntimeError("flute_amd.moe_route: all tensors must live on the same GPU")
@@ -970,11 +1008,15 @@ def _moe_route_call(topk_ids, topk_weights, num_experts):
     rows = torch.empty(P, dtype=torch.int32, device=dev)
     pos = torch.empty((T, k), dtype=torch.int32, device=dev)
     row_weight = None if w is None else torch.empty(P, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_moe_route(
-            _INDEX_DTYPE_ID[ids.dtype], 0 if w is None else _ROUTE_WEIGHT_DTYPE_ID[w.dtype], T, k, E, ids.data_ptr(),
+    head = (_INDEX_DTYPE_ID[ids.dtype], 0 if w is None else _ROUTE_WEIGHT_DTYPE_ID[w.dtype], T, k, E, ids.data_ptr(),
             None if w is None else w.data_ptr(), offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
-            None if row_weight is None else row_weight.data_ptr(), pos.data_ptr(), _stream_ptr(dev)))
+            None if row_weight is None else row_weight.data_ptr(), pos.data_ptr())
+    with torch.cuda.device(dev):
+        if wide is None:
+            _lib.check(_lib.get().flute_moe_route(*head, _stream_ptr(dev)))
+        else:
+            ws = _route_wide_workspace(T, k, E, wide, dev)
+            _lib.check(_lib.get().flute_moe_route_wide(*head, ws.data_ptr(), ws.numel(), wide, _stream_ptr(dev)))
     return offsets, rows, row_weight, pos, perm
 
 
@@ -1003,9 +1045,13 @@ def _validate_moe_gate(logits, k, scoring, bias, num_experts=None):
         raise ValueError
 
 
-def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=None):
-    """One gating launch: flute_moe_gate, with `routed` _route, with `groups` = (n_group, topk_group, group_score) _limited."""
-    name = "moe_gate" + ("_route" if routed else "") + ("" if groups is None else "_limited")
+def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=None, wide=None):
+    """One gating call: flute_moe_gate, with `routed` _route, with `groups` = (n_group, topk_group, group_score) _limited; with `wide`
+    (the ABI's chunk_tokens, 0 automatic; needs `routed`) flute_moe_gate_route_wide, the one entry of both gatings."""
+    if wide is not None and groups is None:
+        groups = (1, 1, "max")                                  # topk_group == n_group: the unlimited gating
+    name = "moe_gate_route_wide" if wide is not None else \
+        "moe_gate" + ("_route" if routed else "") + ("" if groups is None else "_limited")
     dev = logits.device
     if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
         raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
@@ -1029,8 +1075,12 @@ def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=
         rows = torch.empty(P, dtype=torch.int32, device=dev)
         row_weight = torch.empty(P, dtype=torch.float32, device=dev)
         pos = torch.empty((T, k), dtype=torch.int32, device=dev)
+        tail = ()
+        if wide is not None:
+            ws = _route_wide_workspace(T, k, E, wide, dev)
+            tail = (ws.data_ptr(), ws.numel(), wide)
         _lib.check(fn(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(), row_weight.data_ptr(), pos.data_ptr(),
-                      _stream_ptr(dev)))
+                      *tail, _stream_ptr(dev)))
     return ids, weights, offsets, rows, row_weight, pos, perm
 
 
@@ -1080,16 +1130,18 @@ def _moe_gate_op(logits, run, scoring, renormalize, scale, native=False):
 
 
 def _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed, num_experts=None, groups=None,
-                    native_router_grad=False):
+                    native_router_grad=False, wide=None):
     """What the four gating ops share: the validation, the launch and, when `logits` records a gradient, `_MoeGateFunction`.
     `groups` = (n_group, topk_group, group_score) or None.  `native_router_grad` is read by the backward only: False (the four
     ops' own) differentiates the formula with torch ops; True - `FluteExperts(native_router_grad=True)` passes it - runs one
-    `moe_gate_grad` launch (router_grad.hip) in their place.  The forward's bits do not depend on it."""
+    `moe_gate_grad` launch (router_grad.hip) in their place.  The forward's bits do not depend on it.  `wide` (with `routed`):
+    `moe_gate_route_wide`'s checked chunk_tokens, None for the one-workgroup launch; the backward is the same either way."""
     if groups is None:
         _validate_moe_gate(logits, k, scoring, bias, num_experts)
     else:
         _validate_moe_gate_limited(logits, k, groups[0], groups[1], scoring, bias, groups[2], num_experts)
-    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=routed, groups=groups),
+    return _moe_gate_op(logits, lambda: _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed=routed, groups=groups,
+                                                       wide=wide),
                         scoring, renormalize, scale, native_router_grad)
 
 
@@ -1161,6 +1213,22 @@ def moe_gate_route_limited(logits: torch.Tensor, k: int, n_group: int, topk_grou
     `moe_gate_route`: meant for decode-sized T, correct for every T the limits admit (moe_gate.hip)."""
     return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=True, num_experts=num_experts,
                            groups=(n_group, topk_group, group_score))
+
+
+def moe_gate_route_wide(logits: torch.Tensor, k: int, num_experts=None, scoring: str = "softmax", renormalize: bool = False,
+                        bias=None, scale: float = 1.0, n_group: int = 1, topk_group: int = 1, group_score: str = "max",
+                        chunk_tokens=None):
+    """`moe_gate_route` - with `n_group` > 1 `moe_gate_route_limited` - over many workgroups, for prefill and training
+    token counts: (ids, weights, offsets, rows, row_weight, pos, perm), all seven bit for bit the one-workgroup op's.
+    Three launches (moe_gate.hip, moe_route_wide.hip): workgroup c gates the `chunk_tokens` tokens of chunk c, one wave per
+    token, and counts their experts; a scan over the chunks; every workgroup places its chunk's pairs.  No workgroup
+    waits on another.  `chunk_tokens` None: automatic, 16 tokens; an int >= 1 (at most 8192 chunks) is for tests and
+    sweeps; one chunk is served by the one-workgroup launch.  topk_group == n_group is the unlimited gating.  The
+    workspace is allocated per call; no host synchronise (capturable); equal arguments give equal bits; autograd as
+    `moe_gate_route`.  `flute_amd.dev.moe_route_form(T, k, E)` says where this form pays."""
+    wide = _validate_chunk_tokens(chunk_tokens, logits.shape[0] if logits.ndim == 2 else 0)
+    return _moe_gate_entry(logits, k, scoring, renormalize, bias, scale, routed=True, num_experts=num_experts,
+                           groups=(n_group, topk_group, group_score), wide=wide)
 
 
 def _validate_moe_combine(y, pos, offsets, rows=None):

@@ -38,6 +38,7 @@ extern "C" {
  *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
+ *    the routing over many workgroups: flute_moe_route_wide, flute_moe_gate_route_wide, flute_moe_route_wide_workspace, flute_moe_route_form
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -606,8 +607,8 @@ size_t flute_qgemm_grouped_table_grad_scratch_bytes(int num_bits, int group_size
  * Integer counting only: a counting sort inside one workgroup of 16 waves (moe_route.hip), each wave on one contiguous
  * range of the pairs, no atomics on global memory, nothing that depends on scheduling: equal arguments give equal bits.
  * The host reads neither ids nor weights; the grid is one workgroup whatever (P, E) (hipGraph-capturable, a replay serves
- * what the arrays then hold).  Correct for every P below FLUTE_MOE_ROUTE_MAX_PAIRS, fast for decode-sized ones: there is
- * no multi-workgroup form for prefill-sized P.
+ * what the arrays then hold).  Correct for every P below FLUTE_MOE_ROUTE_MAX_PAIRS, fast for decode-sized ones: the
+ * multi-workgroup form for prefill-sized P is flute_moe_route_wide below.
  * Refusals in this order, before anything is enqueued: FLUTE_ERR_DTYPE (id_dtype, then weight_dtype - checked with null
  * weights too); FLUTE_ERR_SHAPE (a negative T / k / E, E > FLUTE_MOE_ROUTE_MAX_EXPERTS, T k >=
  * FLUTE_MOE_ROUTE_MAX_PAIRS); P == 0 (T == 0 or k == 0) with a null offsets returns FLUTE_OK without a launch; then
@@ -701,6 +702,78 @@ int flute_moe_gate_route_limited(int logit_dtype, int T, int E, int k, int n_gro
                                  int renormalize, float scale, const void* logits, const float* bias, int32_t* ids,
                                  float* weights, int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos,
                                  void* stream);
+
+/* The routing over MANY workgroups, for prefill and training token counts: flute_moe_route's contract in three plain launches
+ * (moe_route_wide.hip).  All five arrays are bit for bit what flute_moe_route writes for the same arguments - a stable sort by expert
+ * has one answer, and the device code of the count and the place is the one-workgroup kernel's.
+ *   chunks   chunk c owns the chunk_tokens consecutive tokens [c chunk_tokens, (c + 1) chunk_tokens) cut at T, one contiguous range
+ *            of pairs; C = ceil(T / chunk_tokens) chunks (C = 1 where T k == 0), one workgroup of 16 waves each.
+ *   count    grid C: each workgroup counts its chunk per bucket (E + 1 buckets, the last for ids outside [0, E)) into hist[c][.].
+ *   scan     grid ceil((E + 1) / 64): each bucket's column of hist becomes its exclusive prefix over the chunks; its total to total[.].
+ *   place    grid C: each workgroup scans total over the buckets (workgroup 0 stores offsets), counts its chunk per wave again and
+ *            places: row = (pairs of lower buckets) + (pairs of this bucket in earlier chunks, earlier waves) + rank in the wave's step.
+ * The kernel boundaries are the only ordering between workgroups: no workgroup waits on another inside a launch, there is no arrival
+ * counter and no atomic on global memory, so the launches need no co-residency and cannot hang.  The price is two more launches.
+ * workspace: flute_moe_route_wide_workspace(T, k, E, chunk_tokens) bytes, (C + 1) (E + 1) int32 - hist [C][E + 1], chunk-major (the
+ * two grid-C launches then touch contiguous rows; the scan reads 64 neighbouring buckets per wave, contiguous too), then total
+ * [E + 1].  Every word a launch reads was written by an earlier launch of the SAME call: the workspace may hold anything before, and
+ * holds nothing of use after.  The query returns 0 for a shape or chunk_tokens the launch refuses; with chunk_tokens 0 it covers the
+ * automatic chunk of either entry.  More bytes change nothing.
+ * chunk_tokens: 0 = automatic, a function of (T, k) only: the tokens of FLUTE_MOE_ROUTE_WIDE_PAIRS pairs here,
+ * FLUTE_MOE_GATE_ROUTE_WIDE_TOKENS tokens in the gated entry, either grown where C would pass FLUTE_MOE_ROUTE_MAX_CHUNKS (the
+ * workspace at E = 1024 then stays below 34 MB).  Both come from the sweep of DESIGN.md 3.3s: 512 pairs is the fastest or within
+ * 2 % of it at every swept shape of 8192 pairs and more (2048 pairs per chunk costs 12 - 22 % more, 4096 up to 55 %), and 16 tokens
+ * is the fastest gated chunk at E = 256 and at 1024 tokens of E = 8 and E = 64 (at E = 256 32 tokens costs 28 - 44 % more: a wave
+ * gates its tokens one after the other) and within 13 % of the fastest, 32, at 4096 tokens of E = 8 and E = 64.  An explicit value (>= 1, with C <= FLUTE_MOE_ROUTE_MAX_CHUNKS) is for tests and
+ * sweeps, the routing's counterpart of flute_overrides.
+ * C == 1 (T <= chunk_tokens; T k == 0 with offsets given, which writes the E + 1 zeros) is served by flute_moe_route's own
+ * one-workgroup launch, as topk_group == n_group is served by the unlimited gating kernel; the workspace is then not touched and
+ * may be null.
+ * Every property of flute_moe_route holds: the host reads nothing, the grids follow from (T, k, E, chunk_tokens) alone
+ * (hipGraph-capturable), equal arguments give equal bits.
+ * Refusals in this order, before anything is enqueued: flute_moe_route's FLUTE_ERR_DTYPE and FLUTE_ERR_SHAPE, in its order;
+ * FLUTE_ERR_SHAPE for chunk_tokens < 0 or C > FLUTE_MOE_ROUTE_MAX_CHUNKS; T k == 0 with a null offsets returns FLUTE_OK without a
+ * launch; FLUTE_ERR_NULL (flute_moe_route's pointers, and workspace when C > 1); FLUTE_ERR_WORKSPACE when C > 1 and workspace_bytes
+ * is below the query's figure for the same (T, k, E) and the chunk in use. */
+#define FLUTE_MOE_ROUTE_MAX_CHUNKS 8192
+#define FLUTE_MOE_ROUTE_WIDE_PAIRS 512
+#define FLUTE_MOE_GATE_ROUTE_WIDE_TOKENS 16
+size_t flute_moe_route_wide_workspace(int T, int k, int E, int chunk_tokens);
+int flute_moe_route_wide(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
+                         int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
+                         size_t workspace_bytes, int chunk_tokens, void* stream);
+
+/* flute_moe_gate_route and flute_moe_gate_route_limited over many workgroups, ONE entry for both gatings: topk_group == n_group
+ * (n_group == 1 included) is the unlimited gating, as in flute_moe_gate_route_limited.  ids, weights and the five routing arrays
+ * are bit for bit what flute_moe_gate_route[_limited] writes.  The first launch is the gated count (moe_gate.hip): workgroup c's
+ * wave w gates the chunk's tokens w, w + 16, ... with the per-token device function every gating kernel runs, then the workgroup
+ * counts the ids it wrote itself; scan and place are flute_moe_route_wide's launches on those ids and weights.  Workspace,
+ * chunk_tokens (automatic: FLUTE_MOE_GATE_ROUTE_WIDE_TOKENS tokens, one per wave and round) and C == 1 (served by the one-workgroup
+ * flute_moe_gate_route[_limited] launch) as above.
+ * Refusals in this order: flute_moe_gate_route_limited's FLUTE_ERR_DTYPE and FLUTE_ERR_SHAPE; FLUTE_ERR_SHAPE for chunk_tokens;
+ * T == 0 with a null offsets returns FLUTE_OK; FLUTE_ERR_NULL (its pointers, and workspace when C > 1); FLUTE_ERR_WORKSPACE. */
+int flute_moe_gate_route_wide(int logit_dtype, int T, int E, int k, int n_group, int topk_group, int group_score, int scoring,
+                              int renormalize, float scale, const void* logits, const float* bias, int32_t* ids, float* weights,
+                              int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
+                              size_t workspace_bytes, int chunk_tokens, void* stream);
+
+/* Which routing to take for T tokens, top-k, E experts - gated: flute_moe_gate_route[_limited] against flute_moe_gate_route_wide,
+ * else flute_moe_route against flute_moe_route_wide: FLUTE_MOE_ROUTE_FORM_ONE or FLUTE_MOE_ROUTE_FORM_WIDE, or (< 0) the launch's
+ * FLUTE_ERR_SHAPE.  Host only, shapes alone, monotone in T at fixed (k, E): wide from T k >= FLUTE_MOE_ROUTE_WIDE_MIN_PAIRS pairs on
+ * (where the automatic chunk gives more than one chunk, which it then does), gated or not.  The threshold is the measured crossover
+ * (profiles/grouped_moe_route_wide.json): against the better of the one-launch flute_moe_gate_route[_limited] and the
+ * two-call flute_moe_gate[_limited] + flute_moe_route the wide form loses at every measured row of 2048 pairs and below (1024 tokens
+ * top-2 at E = 8: 10.5 us against 7.9; 256 tokens top-8 at E = 64 and E = 256: 11.7 against 9.9, 21.1 against 16.8) and wins at
+ * every row of 8192 pairs and above (4096 tokens top-2: 14.5 us against 17.4; 1024 tokens top-8: 13.0 against 23.1, 22.6 against
+ * 30.5; 16384 tokens top-8 at E = 256: 78 us against 313, and against 11.6 ms of the one-launch form); ungated the same two rows
+ * (8192 pairs: 0.62 - 0.75 of flute_moe_route's time, 131072 pairs: 0.09).  Nothing between 2048 and 8192 pairs was measured: the
+ * rule says "one" there.  The one-launch gated form alone - what a caller of flute_moe_gate_route has today - is passed much
+ * earlier, at 64 - 256 tokens; a caller who has only that alternative may take the wide entry from there.  num_sms is accepted as
+ * in the other _form entries (< 1: a whole part) and does not enter the rule: the crossover was measured on a whole part only. */
+#define FLUTE_MOE_ROUTE_FORM_ONE 1
+#define FLUTE_MOE_ROUTE_FORM_WIDE 2
+#define FLUTE_MOE_ROUTE_WIDE_MIN_PAIRS 8192
+int flute_moe_route_form(int gated, int T, int k, int E, int num_sms);
 
 /* The end of a mixture-of-experts step: the sorted rows Y [P, N] T of the down projection (flute_qgemm_grouped_weighted's
  * output), summed per token through pos [T, k] int32 (flute_moe_route's), into out [T, N] T.  Per element:

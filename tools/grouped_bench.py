@@ -10,6 +10,7 @@
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
     python tools/grouped_bench.py --mode router_grad [--out profiles/grouped_moe_router_grad.json]
+    python tools/grouped_bench.py --mode route_wide [--out profiles/grouped_moe_route_wide.json]
 
 W4G64 fp16, E = 8, gate / up 4096 -> 14336 and down 14336 -> 4096, top-2 routing of 1, 4, 16 and 64 tokens; the expert of
 every (token, slot) is drawn once from a fixed seed.  Both forms are captured in a hipGraph of `steps` launches between
@@ -83,6 +84,15 @@ process: the weighted launch's chain behind the unweighted input gradient (torch
 of 1.5 R K 16-bit elements as the yardstick of the same traffic), the gate's backward (torch ops against flute_amd.moe_gate_grad) for
 an E = 8 top-2 softmax router and an E = 256 top-8 group-limited sigmoid router, moe_combine's backward (the torch chain against
 flute_amd.moe_gather), and one whole backward step of FluteSparseMoeBlock with the router training, native_router_grad off and on.
+
+--mode route_wide times the routing at prefill and training token counts - 16 .. 16384 tokens - for three routers (E = 8 top-2 softmax,
+E = 64 top-8 softmax, E = 256 top-8 sigmoid + bias with 8 groups / best 4 / top-2 sum, scale 2.5; fp16 logits, renormalised), by
+--mode gate_limited's method in one process, every contender timed twice, alternating: (a) moe_gate_route[_limited], one workgroup,
+what the modules run by default; (b) moe_gate[_limited] then moe_route, the two-call sequence; (c) moe_gate_route_wide on its
+automatic chunk; (d) ungated, moe_route against moe_route_wide on the ids and weights (a) wrote.  Then the chunk_tokens sweep at 1024
+and 4096 tokens - 16 .. 256 tokens for (c), the tokens of 512 .. 4096 pairs for (d) - and one forward of
+FluteSparseMoeBlock(fused=True, native_routing=True) at Mixtral's shapes, 512 and 4096 tokens, wide_routing off against "auto".
+Every row carries each contender's own spread over its ten replays.
 
 --mode prefill times the grouped FORWARD at prefill and training row counts, where the block form (qgemm_grouped_blocks.h) meets
 the row form (qgemm_grouped.h): W4G64 fp16 at Mixtral's two projections with 512, 4096 and 8192 routed rows (the counts of
@@ -1456,6 +1466,132 @@ def main_router_grad(args, device):
     print("wrote", args.out)
 
 
+# ---- --mode route_wide ------------------------------------------------------------------------------------------------
+WIDE_ROUTERS = {"E8 top2 softmax": dict(E=8, k=2, scoring="softmax", bias=False, scale=1.0, groups=None),
+                "E64 top8 softmax": dict(E=64, k=8, scoring="softmax", bias=False, scale=1.0, groups=None),
+                "E256 top8 sigmoid bias n_group8 topk_group4 top2sum": dict(E=256, k=8, scoring="sigmoid", bias=True, scale=2.5,
+                                                                            groups=(8, 4, "top2sum"))}
+WIDE_TOKENS = (16, 64, 256, 1024, 4096, 16384)
+WIDE_SWEEP_TOKENS = (1024, 4096)
+WIDE_GATED_CHUNKS = (16, 32, 64, 128, 256)
+WIDE_UNGATED_PAIRS = (512, 1024, 2048, 4096)
+
+
+class WideRouting:
+    """One routing of `tokens` tokens for a router of WIDE_ROUTERS; step(i) returns `pos`.  form: "one" (a), "two" (b), "wide" (c),
+    "route" / "route_wide" (d); chunk_tokens: the wide forms' (None: automatic)."""
+
+    def __init__(self, tokens, router, device, form, chunk_tokens=None):
+        import flute_amd
+        self.fa, self.r, self.form, self.chunk = flute_amd, router, form, chunk_tokens
+        gen = torch.Generator(device=device).manual_seed(tokens + router["E"])
+        self.logits = (torch.randn(tokens, router["E"], device=device, generator=gen) * 2).to(DTYPE)
+        self.bias = torch.randn(router["E"], device=device, generator=gen) * 0.1 if router["bias"] else None
+        if form in ("route", "route_wide"):
+            self.ids, self.weights = self.gate(routed=False)
+
+    def gate(self, routed, wide=False):
+        r, fa = self.r, self.fa
+        tail = (r["scoring"], True, self.bias, r["scale"])
+        if wide:
+            return fa.moe_gate_route_wide(self.logits, r["k"], r["E"], *tail, *(r["groups"] or (1, 1, "max")), chunk_tokens=self.chunk)
+        if r["groups"] is None:
+            return fa.moe_gate_route(self.logits, r["k"], r["E"], *tail) if routed else fa.moe_gate(self.logits, r["k"], *tail)
+        n_group, topk_group, group_score = r["groups"]
+        if routed:
+            return fa.moe_gate_route_limited(self.logits, r["k"], n_group, topk_group, r["E"], *tail, group_score)
+        return fa.moe_gate_limited(self.logits, r["k"], n_group, topk_group, *tail, group_score)
+
+    def step(self, i):
+        if self.form == "one":
+            return self.gate(routed=True)[5]
+        if self.form == "wide":
+            return self.gate(routed=True, wide=True)[5]
+        if self.form == "two":
+            return self.fa.moe_route(*self.gate(routed=False), self.r["E"])[3]
+        if self.form == "route":
+            return self.fa.moe_route(self.ids, self.weights, self.r["E"])[3]
+        return self.fa.moe_route_wide(self.ids, self.weights, self.r["E"], chunk_tokens=self.chunk)[3]
+
+
+class WideBlock:
+    """One forward of FluteSparseMoeBlock (softmax top-2, renormalised) on copy i of step_stacks."""
+
+    def __init__(self, stacks, tokens, device, wide_routing):
+        from flute_amd.integrations import moe
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        router = (torch.randn(E, 4096, device=device, generator=gen) * 0.02).to(DTYPE)
+        self.blocks = [moe.FluteSparseMoeBlock(router, moe.FluteExperts(g, u, d, fused=True, native_routing=True,
+                                                                        wide_routing=wide_routing), TOPK, renormalize=True)
+                       for g, u, d in stacks]
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+
+    def step(self, i):
+        with torch.no_grad():
+            return self.blocks[i % len(self.blocks)](self.hidden)
+
+
+def time_each(layers, args):
+    """time_forms with every contender's own spread: ({name: mean of its two medians}, {name: (max - min) / median over its ten
+    replays}, the passes)."""
+    us, _, replays = time_forms(layers, args)
+    spread = {}
+    for n, passes in replays.items():
+        flat = sorted(r for p in passes for r in p)
+        spread[n] = round((flat[-1] - flat[0]) / flat[len(flat) // 2], 4)
+    return us, spread, replays
+
+
+def main_route_wide(args, device):
+    from flute_amd import dev
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"what": "the MoE routing at prefill and training token counts, fp16 logits, renormalised: (a) one = "
+                               "moe_gate_route[_limited], one workgroup; (b) two = moe_gate[_limited] + moe_route; (c) wide = "
+                               "moe_gate_route_wide, automatic chunk; (d) route / route_wide = moe_route against moe_route_wide on "
+                               "given ids and weights; the chunk_tokens sweeps; one forward of FluteSparseMoeBlock(fused=True, "
+                               "native_routing=True) at Mixtral's shapes, wide_routing off against auto.  hipGraph replays of `steps` "
+                               "calls between device-clock stamps, cold caches, median of `replays`, every contender timed twice, "
+                               "alternating, one process; spread: (max - min) / median over a contender's replays",
+                       "config": {"steps": args.steps, "warmup": args.warmup, "replays": args.replays, "dtype": "float16",
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    for name, router in WIDE_ROUTERS.items():
+        for tokens in WIDE_TOKENS:
+            layers = {f: WideRouting(tokens, router, device, f) for f in ("one", "two", "wide", "route", "route_wide")}
+            same = all(torch.equal(a, b) for a, b in zip(layers["one"].gate(True), layers["wide"].gate(True, wide=True)))
+            us, spread, replays = time_each(layers, args)
+            best = min(us["one"], us["two"])
+            emit({"what": "routing", "router": name, "tokens": tokens, "pairs": tokens * router["k"], "us": us, "spread": spread,
+                  "wide_equals_one_bitwise": same, "wide_over_best_of_one_two": round(us["wide"] / best, 4),
+                  "route_wide_over_route": round(us["route_wide"] / us["route"], 4),
+                  "rule_gated": dev.moe_route_form(tokens, router["k"], router["E"], gated=True),
+                  "rule_ungated": dev.moe_route_form(tokens, router["k"], router["E"], gated=False), "replays_us": replays})
+    for name, router in WIDE_ROUTERS.items():
+        for tokens in WIDE_SWEEP_TOKENS:
+            layers = {"wide chunk %d" % c: WideRouting(tokens, router, device, "wide", c) for c in WIDE_GATED_CHUNKS}
+            layers.update({"route_wide pairs %d" % p: WideRouting(tokens, router, device, "route_wide", max(1, p // router["k"]))
+                           for p in WIDE_UNGATED_PAIRS})
+            us, spread, replays = time_each(layers, args)
+            emit({"what": "chunk sweep", "router": name, "tokens": tokens, "us": us, "spread": spread, "replays_us": replays})
+    copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
+    stacks = step_stacks(copies, device)
+    for tokens in (512, 4096):
+        layers = {"wide_routing off": WideBlock(stacks, tokens, device, False), "wide_routing auto": WideBlock(stacks, tokens, device, "auto")}
+        same = torch.equal(layers["wide_routing off"].step(0), layers["wide_routing auto"].step(0))
+        us, spread, replays = time_each(layers, args)
+        emit({"what": "FluteSparseMoeBlock forward, Mixtral shapes", "tokens": tokens, "experts": E, "top_k": TOPK, "us": us,
+              "spread": spread, "rule": dev.moe_route_form(tokens, TOPK, E, gated=True), "auto_equals_off_bitwise": same,
+              "auto_over_off": round(us["wide_routing auto"] / us["wide_routing off"], 4), "weight_copies": copies,
+              "replays_us": replays})
+    print("wrote", args.out)
+
+
 def main_input_grad(args):
     """`--processes` fresh child processes one after the other; per row the median of the processes' figures and the largest
     spread of any pass in any process."""
@@ -1530,7 +1666,7 @@ def main():
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
     ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad",
-                                       "prefill", "router_grad"],
+                                       "prefill", "router_grad", "route_wide"],
                     default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -1549,7 +1685,8 @@ def main():
                                                    "scale_grad": "grouped_moe_scale_grad.json",
                                                    "table_grad": "grouped_moe_table_grad.json",
                                                    "prefill": "grouped_moe_prefill.json",
-                                                   "router_grad": "grouped_moe_router_grad.json"}[args.mode])
+                                                   "router_grad": "grouped_moe_router_grad.json",
+                                                   "route_wide": "grouped_moe_route_wide.json"}[args.mode])
     if args.mode in ("scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
@@ -1573,6 +1710,8 @@ def main():
         return main_prefill(args, device)
     if args.mode == "router_grad":
         return main_router_grad(args, device)
+    if args.mode == "route_wide":
+        return main_route_wide(args, device)
     if args.mode == "input_grad":
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
