@@ -2001,12 +2001,21 @@ size_t flute_qgemm_grouped_table_grad_scratch_bytes(int num_bits, int group_size
     return table_grad_grouped_scratch_bytes(num_bits, E, N, K);
 }
 
-int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
-                    int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
+// the shapes every routing entry point serves (the workspace query asks nothing else)
+static bool moe_route_shape_ok(int T, int k, int E) {
+    return T >= 0 && k >= 0 && E >= 0 && E <= FLUTE_MOE_ROUTE_MAX_EXPERTS && (long long)T * k < FLUTE_MOE_ROUTE_MAX_PAIRS;
+}
+// the refusals flute_moe_route and flute_moe_route_wide share, in their order: the two dtypes, then the shapes
+static int check_moe_route(int id_dtype, int weight_dtype, int T, int k, int E) {
     if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;
     if (weight_dtype != FLUTE_F16 && weight_dtype != FLUTE_BF16 && weight_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
-    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
-    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    return moe_route_shape_ok(T, k, E) ? FLUTE_OK : FLUTE_ERR_SHAPE;
+}
+
+int flute_moe_route(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
+                    int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* stream) {
+    const int rc = check_moe_route(id_dtype, weight_dtype, T, k, E);
+    if (rc) return rc;
     const int P = T * k;
     if (P == 0 && !offsets) return FLUTE_OK;                    // no pair and nowhere to write the E + 1 zeros
     if (P > 0 && (!ids || !perm || !rows || !pos || (weights && !row_weight))) return FLUTE_ERR_NULL;
@@ -2044,6 +2053,12 @@ static int moe_gate_alone(int logit_dtype, int T, int E, int k, const GateGroups
                              nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
+// whether one of the pointers every routed gating entry reads or writes when there is a token is null (offsets: asked on its own)
+static bool routed_outputs_null(const void* logits, const int32_t* ids, const float* weights, const int32_t* perm,
+                                const int32_t* rows, const float* row_weight, const int32_t* pos) {
+    return !logits || !ids || !weights || !perm || !rows || !row_weight || !pos;
+}
+
 // the routed form behind flute_moe_gate_route (g null) and flute_moe_gate_route_limited
 static int moe_gate_routed(int logit_dtype, int T, int E, int k, const GateGroups* g, int scoring, int renormalize, float scale,
                            const void* logits, const float* bias, int32_t* ids, float* weights, int32_t* offsets, int32_t* perm,
@@ -2051,7 +2066,7 @@ static int moe_gate_routed(int logit_dtype, int T, int E, int k, const GateGroup
     const int rc = check_moe_gate(logit_dtype, T, E, k, g, scoring);
     if (rc) return rc;
     if (T == 0 && !offsets) return FLUTE_OK;                    // no token and nowhere to write the E + 1 zeros
-    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
+    if (T > 0 && routed_outputs_null(logits, ids, weights, perm, rows, row_weight, pos)) return FLUTE_ERR_NULL;
     if (!offsets) return FLUTE_ERR_NULL;
     return moe_gate_dispatch(logit_dtype, T, E, k, g, scoring, renormalize, scale, logits, bias, ids, weights, offsets, perm,
                              rows, row_weight, pos, reinterpret_cast<hipStream_t>(stream));
@@ -2104,7 +2119,7 @@ static int route_wide_chunks(bool gated, int T, int k, int* chunk_tokens) {
 static size_t route_wide_bytes(int C, int E) { return (size_t)(C + 1) * (size_t)(E + 1) * sizeof(int32_t); }
 
 size_t flute_moe_route_wide_workspace(int T, int k, int E, int chunk_tokens) {
-    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS || (long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return 0;
+    if (!moe_route_shape_ok(T, k, E)) return 0;
     int ct = chunk_tokens, ctg = chunk_tokens;                     // automatic: enough for either entry's own chunk
     const int Cu = route_wide_chunks(false, T, k, &ct), Cg = route_wide_chunks(true, T, k, &ctg);
     const int C = Cg > Cu ? Cg : Cu;
@@ -2114,10 +2129,8 @@ size_t flute_moe_route_wide_workspace(int T, int k, int E, int chunk_tokens) {
 int flute_moe_route_wide(int id_dtype, int weight_dtype, int T, int k, int E, const void* ids, const void* weights,
                          int32_t* offsets, int32_t* perm, int32_t* rows, float* row_weight, int32_t* pos, void* workspace,
                          size_t workspace_bytes, int chunk_tokens, void* stream) {
-    if (id_dtype != FLUTE_I32 && id_dtype != FLUTE_I64) return FLUTE_ERR_DTYPE;
-    if (weight_dtype != FLUTE_F16 && weight_dtype != FLUTE_BF16 && weight_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
-    if (T < 0 || k < 0 || E < 0 || E > FLUTE_MOE_ROUTE_MAX_EXPERTS) return FLUTE_ERR_SHAPE;
-    if ((long long)T * k >= FLUTE_MOE_ROUTE_MAX_PAIRS) return FLUTE_ERR_SHAPE;
+    const int rc = check_moe_route(id_dtype, weight_dtype, T, k, E);
+    if (rc) return rc;
     const int C = route_wide_chunks(false, T, k, &chunk_tokens);
     if (C == 0) return FLUTE_ERR_SHAPE;
     const int P = T * k;
@@ -2141,7 +2154,7 @@ int flute_moe_gate_route_wide(int logit_dtype, int T, int E, int k, int n_group,
     const int C = route_wide_chunks(true, T, k, &chunk_tokens);
     if (C == 0) return FLUTE_ERR_SHAPE;
     if (T == 0 && !offsets) return FLUTE_OK;
-    if (T > 0 && (!logits || !ids || !weights || !perm || !rows || !row_weight || !pos)) return FLUTE_ERR_NULL;
+    if (T > 0 && routed_outputs_null(logits, ids, weights, perm, rows, row_weight, pos)) return FLUTE_ERR_NULL;
     if (!offsets || (C > 1 && !workspace)) return FLUTE_ERR_NULL;
     if (C > 1 && workspace_bytes < route_wide_bytes(C, E)) return FLUTE_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -280,18 +280,62 @@ def _refuse_table_grad(name, *tables):
         raise RuntimeError(f"{name}: no gradient for table2 (only input, row_weight and scales train)")
 
 
+# The three bodies.  Each serves a pair of entry points, `name` the one that was called: `*_learnable_scales` hands in the
+# stack's `table2`, which must not require grad; `*_learnable` (below) hands in None there and the stack's fp32 master
+# `codebook`, from which `table2` is built (`_codebook_stack`) before anything is validated.  `layer` = (num_bits, group_size,
+# template_id, num_sms).
+
+def _grouped_learnable(name, input, offsets, weight, scales, table2, layer, codebook=None):
+    if codebook is not None:
+        table2 = _codebook_stack(name, codebook, layer[0], input.dtype, scales)
+    _ops._validate_grouped(input, offsets, weight, scales, table2, layer[0], layer[1])
+    if codebook is None:
+        _refuse_table_grad(name, table2)
+    if not _ops._records_grad(input, scales, codebook):
+        return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, *layer)
+    return _ops._GroupedFunction.apply(input, scales, codebook, offsets, weight, table2, layer)
+
+
+def _grouped_weighted_learnable(name, input, offsets, weight, scales, table2, row_weight, layer, native_router_grad,
+                                codebook=None):
+    if codebook is not None:
+        table2 = _codebook_stack(name, codebook, layer[0], input.dtype, scales)
+    _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, layer[0], layer[1])
+    if codebook is None:
+        _refuse_table_grad(name, table2)
+    if not _ops._records_grad(input, row_weight, scales, codebook):
+        return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, *layer)
+    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, codebook, offsets, weight, table2, layer, None,
+                                               bool(native_router_grad))
+
+
+def _grouped_glu_learnable(name, input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
+                           rows, pos, blocks, native_glu_grad, gate_codebook=None, up_codebook=None):
+    if gate_codebook is not None:
+        gate_table2 = _codebook_stack(name, gate_codebook, layer[0], input.dtype, gate_scales)
+        up_table2 = _codebook_stack(name, up_codebook, layer[0], input.dtype, up_scales)
+    _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                               layer[0], layer[1], rows)
+    if gate_codebook is None:
+        _refuse_table_grad(name, gate_table2, up_table2)
+    if not _ops._records_grad(input, gate_scales, up_scales, gate_codebook, up_codebook):
+        return _glu_op(blocks)(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, *layer,
+                               rows=rows, pos=pos, native_glu_grad=native_glu_grad)
+    _ops._validate_grouped_glu_pos(input, rows, pos)
+    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, gate_codebook, up_codebook, rows, pos, offsets,
+                                          gate_weight, gate_table2, up_weight, up_table2, layer,
+                                          _glu_form(blocks, name, input, rows, gate_weight, gate_scales, layer),
+                                          bool(native_glu_grad))
+
+
 def qgemm_grouped_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                                    table2: torch.Tensor, num_bits: int, group_size: int, template_id: int,
                                    num_sms=None) -> torch.Tensor:
     """`flute_amd.qgemm_grouped`, differentiable with respect to `input` and `scales` [E, N, K / g].  The forward is the
     op's launch (the same bits); the backward adds dS = `qgemm_grouped_scale_grad(dY, input, ...)`.  With grad mode off, or
     nothing requiring grad, it is the plain op.  `table2` requiring grad is refused."""
-    _ops._validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
-    _refuse_table_grad("qgemm_grouped_learnable_scales", table2)
-    if not _ops._records_grad(input, scales):
-        return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
-    return _ops._GroupedFunction.apply(input, scales, None, offsets, weight, table2,
-                                       (num_bits, group_size, template_id, num_sms))
+    return _grouped_learnable("qgemm_grouped_learnable_scales", input, offsets, weight, scales, table2,
+                              (num_bits, group_size, template_id, num_sms))
 
 
 def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
@@ -302,13 +346,8 @@ def qgemm_grouped_weighted_learnable_scales(input: torch.Tensor, offsets: torch.
     forward is the op's launch; the gradients of `input` and `row_weight` are the op's own (`native_router_grad` as the
     op's: one `moe_weight_grad` launch for the two when `row_weight` trains), and
     dS = `qgemm_grouped_scale_grad(dY, input, ..., row_weight=row_weight)`.  `table2` requiring grad is refused."""
-    _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
-    _refuse_table_grad("qgemm_grouped_weighted_learnable_scales", table2)
-    if not _ops._records_grad(input, row_weight, scales):
-        return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
-                                                template_id, num_sms)
-    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2,
-                                               (num_bits, group_size, template_id, num_sms), None, bool(native_router_grad))
+    return _grouped_weighted_learnable("qgemm_grouped_weighted_learnable_scales", input, offsets, weight, scales, table2,
+                                       row_weight, (num_bits, group_size, template_id, num_sms), native_router_grad)
 
 
 def _glu_op(blocks):
@@ -334,19 +373,9 @@ def qgemm_grouped_glu_learnable_scales(input: torch.Tensor, offsets: torch.Tenso
     plus one `qgemm_grouped_scale_grad` launch per stack on the gathered rows.  The tables requiring grad are refused.
     `blocks=True`: the forward is `flute_amd.qgemm_grouped_glu_blocks`' launch (a shape it does not serve raises); the
     backward is the same.  `native_glu_grad` as the op's: the backward's gather and dg, du from `moe_gather` and `swiglu_grad`."""
-    _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
-                               num_bits, group_size, rows)
-    _refuse_table_grad("qgemm_grouped_glu_learnable_scales", gate_table2, up_table2)
-    if not _ops._records_grad(input, gate_scales, up_scales):
-        return _glu_op(blocks)(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
-                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos,
-                               native_glu_grad=native_glu_grad)
-    _ops._validate_grouped_glu_pos(input, rows, pos)
-    layer = (num_bits, group_size, template_id, num_sms)
-    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                          gate_table2, up_weight, up_table2, layer,
-                                          _glu_form(blocks, "qgemm_grouped_glu_learnable_scales", input, rows, gate_weight,
-                                                    gate_scales, layer), bool(native_glu_grad))
+    return _grouped_glu_learnable("qgemm_grouped_glu_learnable_scales", input, offsets, gate_weight, gate_scales, gate_table2,
+                                  up_weight, up_scales, up_table2, (num_bits, group_size, template_id, num_sms), rows, pos,
+                                  blocks, native_glu_grad)
 
 
 # ---- the experts' lookup tables: the same three functions with the codebook slot open.  `codebook` is a stack's fp32
@@ -372,12 +401,8 @@ def qgemm_grouped_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: 
     The forward has the op's bits for the table2 built from the rounded codebook; the backward adds ONE
     `qgemm_grouped_table_grad(dY, input, ...)` launch (with the scale gradient in it when the scales train too; a stack
     that trains only scales keeps `qgemm_grouped_scale_grad`), folded per expert for the scalar form."""
-    table2 = _codebook_stack("qgemm_grouped_learnable", codebook, num_bits, input.dtype, scales)
-    _ops._validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
-    if not _ops._records_grad(input, scales, codebook):
-        return flute_amd.qgemm_grouped(input, offsets, weight, scales, table2, num_bits, group_size, template_id, num_sms)
-    return _ops._GroupedFunction.apply(input, scales, codebook, offsets, weight, table2,
-                                       (num_bits, group_size, template_id, num_sms))
+    return _grouped_learnable("qgemm_grouped_learnable", input, offsets, weight, scales, None,
+                              (num_bits, group_size, template_id, num_sms), codebook)
 
 
 def qgemm_grouped_weighted_learnable(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
@@ -387,13 +412,8 @@ def qgemm_grouped_weighted_learnable(input: torch.Tensor, offsets: torch.Tensor,
     """`flute_amd.qgemm_grouped_weighted`, differentiable with respect to `input`, `row_weight`, `scales` and the stack's
     fp32 master `codebook`: `qgemm_grouped_weighted_learnable_scales` with the table gradient from
     `qgemm_grouped_table_grad(dY, input, ..., row_weight=row_weight)`.  `native_router_grad` as there."""
-    table2 = _codebook_stack("qgemm_grouped_weighted_learnable", codebook, num_bits, input.dtype, scales)
-    _ops._validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
-    if not _ops._records_grad(input, row_weight, scales, codebook):
-        return flute_amd.qgemm_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size,
-                                                template_id, num_sms)
-    return _ops._GroupedWeightedFunction.apply(input, row_weight, scales, codebook, offsets, weight, table2,
-                                               (num_bits, group_size, template_id, num_sms), None, bool(native_router_grad))
+    return _grouped_weighted_learnable("qgemm_grouped_weighted_learnable", input, offsets, weight, scales, None, row_weight,
+                                       (num_bits, group_size, template_id, num_sms), native_router_grad, codebook)
 
 
 def qgemm_grouped_glu_learnable(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor,
@@ -405,17 +425,6 @@ def qgemm_grouped_glu_learnable(input: torch.Tensor, offsets: torch.Tensor, gate
     master codebooks: `qgemm_grouped_glu_learnable_scales` with the table gradients from
     `qgemm_grouped_table_grad(dg, x_sorted, ...)` for gate and `(du, x_sorted, ...)` for up, one launch per stack.
     `blocks` and `native_glu_grad` as there."""
-    gate_table2 = _codebook_stack("qgemm_grouped_glu_learnable", gate_codebook, num_bits, input.dtype, gate_scales)
-    up_table2 = _codebook_stack("qgemm_grouped_glu_learnable", up_codebook, num_bits, input.dtype, up_scales)
-    _ops._validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
-                               num_bits, group_size, rows)
-    if not _ops._records_grad(input, gate_scales, up_scales, gate_codebook, up_codebook):
-        return _glu_op(blocks)(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales,
-                               up_table2, num_bits, group_size, template_id, num_sms, rows=rows, pos=pos,
-                               native_glu_grad=native_glu_grad)
-    _ops._validate_grouped_glu_pos(input, rows, pos)
-    layer = (num_bits, group_size, template_id, num_sms)
-    return _ops._GroupedGluFunction.apply(input, gate_scales, up_scales, gate_codebook, up_codebook, rows, pos, offsets,
-                                          gate_weight, gate_table2, up_weight, up_table2, layer,
-                                          _glu_form(blocks, "qgemm_grouped_glu_learnable", input, rows, gate_weight,
-                                                    gate_scales, layer), bool(native_glu_grad))
+    return _grouped_glu_learnable("qgemm_grouped_glu_learnable", input, offsets, gate_weight, gate_scales, None, up_weight,
+                                  up_scales, None, (num_bits, group_size, template_id, num_sms), rows, pos, blocks,
+                                  native_glu_grad, gate_codebook, up_codebook)

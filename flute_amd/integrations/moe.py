@@ -75,6 +75,11 @@ from .learnable import (_swap, qgemm_grouped_glu_learnable, qgemm_grouped_glu_le
                         qgemm_grouped_weighted_learnable_scales)
 
 
+def _stack_num_sms(stack, device):
+    """The CU count a stack's launches are planned for: the one it recorded when it was built on a GPU, else `device`'s."""
+    return stack.num_sms if stack.num_sms is not None else flute_amd.utils.get_device_num_sms(device)
+
+
 def sort_by_expert(topk_ids: torch.Tensor, num_experts: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The grouping `qgemm_grouped` takes, from the router's choice topk_ids [T, k]: `perm` [T k] lists the flattened
     (token, slot) pairs by expert, pairs of one expert in their original order (a stable sort), and `offsets`
@@ -134,7 +139,7 @@ class GroupedFluteLinear(torch.nn.Module):
         return new
 
     def forward(self, x_sorted: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
-        num_sms = self.num_sms if self.num_sms is not None else flute_amd.utils.get_device_num_sms(x_sorted.device)
+        num_sms = _stack_num_sms(self, x_sorted.device)
         return flute_amd.qgemm_grouped(x_sorted, offsets, self.weight, self.scales, self.tables2, self.num_bits,
                                        self.group_size, self.template_id, num_sms)
 
@@ -192,7 +197,7 @@ class LearnableGroupedFluteLinear(GroupedFluteLinear):
         self.codebook = torch.nn.Parameter(codebook)
 
     def forward(self, x_sorted: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
-        num_sms = self.num_sms if self.num_sms is not None else flute_amd.utils.get_device_num_sms(x_sorted.device)
+        num_sms = _stack_num_sms(self, x_sorted.device)
         if self.table_mode is None:
             return qgemm_grouped_learnable_scales(x_sorted, offsets, self.weight, self.scales, self.tables2,
                                                   self.num_bits, self.group_size, self.template_id, num_sms)
@@ -252,11 +257,9 @@ def _table_of(stack):
     return stack.codebook if _has_codebook(stack) else stack.tables2
 
 
-def _check_glu_blocks(glu_blocks, fused) -> None:
-    if not (glu_blocks is False or glu_blocks is True or (isinstance(glu_blocks, str) and glu_blocks == "auto")):
-        raise ValueError("FluteExperts: glu_blocks is False, True or 'auto', not %r" % (glu_blocks,))
-    if glu_blocks is not False and not fused:
-        raise ValueError("FluteExperts: glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
+def _check_tristate(name, value) -> None:
+    if not (value is False or value is True or (isinstance(value, str) and value == "auto")):
+        raise ValueError("FluteExperts: %s is False, True or 'auto', not %r" % (name, value))
 
 
 class FluteExperts(torch.nn.Module):
@@ -281,9 +284,10 @@ class FluteExperts(torch.nn.Module):
                  native_glu_grad: bool = False, native_router_grad: bool = False,
                  wide_routing: Union[bool, str] = False) -> None:
         super().__init__()
-        _check_glu_blocks(glu_blocks, fused)
-        if not (wide_routing is False or wide_routing is True or (isinstance(wide_routing, str) and wide_routing == "auto")):
-            raise ValueError("FluteExperts: wide_routing is False, True or 'auto', not %r" % (wide_routing,))
+        _check_tristate("glu_blocks", glu_blocks)
+        if glu_blocks is not False and not fused:
+            raise ValueError("FluteExperts: glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
+        _check_tristate("wide_routing", wide_routing)
         if wide_routing is not False and not native_routing:
             raise ValueError("FluteExperts: wide_routing selects the kernels of the routing launch and needs native_routing=True")
         if native_router_grad and not (fused and native_routing):
@@ -341,10 +345,7 @@ class FluteExperts(torch.nn.Module):
         moe_gate_route -> glu -> weighted -> moe_combine (fused): four launches from logits.  Without it `moe_gate` feeds
         the existing forward.  Either way the result is bit for bit `forward(hidden, *moe_gate(...))`.  The choice is over
         all experts; group-limited selection (n_group, topk_group) is `forward_logits_limited`."""
-        return self._forward_gated(
-            "forward_logits", hidden, router_logits,
-            lambda: flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale),
-            lambda: self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale))
+        return self._forward_gated("forward_logits", hidden, router_logits, top_k, scoring, renormalize, bias, scale)
 
     def forward_logits_limited(self, hidden: torch.Tensor, router_logits: torch.Tensor, top_k: int, n_group: int,
                                topk_group: int, scoring: str = "softmax", renormalize: bool = False, bias=None,
@@ -354,56 +355,60 @@ class FluteExperts(torch.nn.Module):
         among their experts only).  With `native_routing` the forward is moe_gate_route_limited -> glu -> weighted ->
         moe_combine (fused): still four launches from logits.  Without it `moe_gate_limited` feeds the existing forward.
         Either way the result is bit for bit `forward(hidden, *moe_gate_limited(...))`."""
-        return self._forward_gated(
-            "forward_logits_limited", hidden, router_logits,
-            lambda: flute_amd.moe_gate_limited(router_logits, top_k, n_group, topk_group, scoring, renormalize, bias, scale,
-                                               group_score),
-            lambda: self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale, (n_group, topk_group, group_score)))
+        return self._forward_gated("forward_logits_limited", hidden, router_logits, top_k, scoring, renormalize, bias, scale,
+                                   (n_group, topk_group, group_score))
 
     def _gate_route(self, router_logits, top_k, scoring, renormalize, bias, scale, groups=None):
-        """`moe_gate_route` / `moe_gate_route_limited` (`groups` = (n_group, topk_group, group_score)); with the module's
-        `native_router_grad` the same launch through the ops' shared entry, which carries the keyword to its backward.  With
-        `wide_routing` taken for these shapes: `moe_gate_route_wide`, the one op of both gatings."""
-        if self._takes_wide_routing(router_logits.shape[0], top_k, gated=True):
-            n_group, topk_group, group_score = (1, 1, "max") if groups is None else groups
-            if self.native_router_grad:
-                return flute_amd.ops._moe_gate_entry(router_logits, top_k, scoring, renormalize, bias, scale, routed=True,
-                                                     num_experts=self.num_experts, groups=(n_group, topk_group, group_score),
-                                                     native_router_grad=True, wide=0)
-            return flute_amd.moe_gate_route_wide(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale,
-                                                 n_group, topk_group, group_score)
+        """The gate-route launch, `groups` = (n_group, topk_group, group_score) or None: `moe_gate_route` /
+        `moe_gate_route_limited`, or with `wide_routing` taken for these shapes `moe_gate_route_wide`, the one op of both gatings
+        - looked up in `flute_amd` when it runs.  With the module's `native_router_grad` the same launch through the ops' shared
+        entry, which carries the keyword to its backward."""
+        wide = self._takes_wide_routing(router_logits.shape[0], top_k, gated=True)
+        if wide and groups is None:
+            groups = (1, 1, "max")                              # topk_group == n_group: the unlimited gating
         if self.native_router_grad:
             return flute_amd.ops._moe_gate_entry(router_logits, top_k, scoring, renormalize, bias, scale, routed=True,
-                                                 num_experts=self.num_experts, groups=groups, native_router_grad=True)
+                                                 num_experts=self.num_experts, groups=groups, native_router_grad=True,
+                                                 wide=0 if wide else None)
+        if wide:
+            return flute_amd.moe_gate_route_wide(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale,
+                                                 *groups)
         if groups is None:
             return flute_amd.moe_gate_route(router_logits, top_k, self.num_experts, scoring, renormalize, bias, scale)
         return flute_amd.moe_gate_route_limited(router_logits, top_k, groups[0], groups[1], self.num_experts, scoring,
                                                 renormalize, bias, scale, groups[2])
 
-    def _forward_gated(self, name, hidden, router_logits, gate, gate_route):
-        """The tail `forward_logits` and `forward_logits_limited` share: `gate()` feeds the existing forward, with
-        `native_routing` `gate_route()`'s routing arrays feed the launches behind them."""
+    def _forward_gated(self, name, hidden, router_logits, top_k, scoring, renormalize, bias, scale, groups=None):
+        """The body of `forward_logits` (`groups` None) and `forward_logits_limited` (`groups` = (n_group, topk_group,
+        group_score)): `moe_gate[_limited]` feeds the existing forward, with `native_routing` `_gate_route`'s routing arrays feed
+        the launches behind them."""
         if router_logits.shape[1] != self.num_experts:
             raise ValueError("FluteExperts.%s: router_logits must be [T, num_experts]" % name)
-        if not self.native_routing:
-            return self.forward(hidden, *gate())
-        _, _, offsets, rows, row_weight, pos, _ = gate_route()
-        return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+        if self.native_routing:
+            _, _, offsets, rows, row_weight, pos, _ = self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale,
+                                                                       groups)
+            return self._forward_routed(hidden, offsets, rows, row_weight, pos)
+        if groups is None:
+            return self.forward(hidden, *flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale))
+        return self.forward(hidden, *flute_amd.moe_gate_limited(router_logits, top_k, groups[0], groups[1], scoring,
+                                                                renormalize, bias, scale, groups[2]))
 
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
-        """Two launches (qgemm_grouped.h, GLU and weighted modes): silu(gate(x)) * up(x) with the rows of `hidden` read through the
-        routing index, then the down projection with the routing weight (fp32) in its epilogue, which also writes
-        the rows past offsets[E] (ids outside [0, E)) as zeros: no silu, no where, no gathered copy of `hidden`."""
-        gate, up, down = self.gate, self.up, self.down
-        num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-        glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, token.shape[0], num_sms))
-        h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales,
-                _table_of(up), gate.num_bits, gate.group_size, gate.template_id, num_sms,
-                rows=token.to(torch.int32))
-        y = weighted(h, offsets, down.weight, down.scales, _table_of(down),
-                     topk_weights.reshape(-1)[perm].float(), down.num_bits, down.group_size,
-                     down.template_id, num_sms)
+        """`_fused_mlp` on torch's routing: no silu, no where, no gathered copy of `hidden`."""
+        y = self._fused_mlp(hidden, offsets, token.to(torch.int32), topk_weights.reshape(-1)[perm].float())
         return torch.zeros_like(hidden).index_add_(0, token, y)
+
+    def _fused_mlp(self, hidden, offsets, rows, row_weight, pos=None):
+        """Two launches (qgemm_grouped.h, GLU and weighted modes): silu(gate(x)) * up(x) with the rows of `hidden` read through the
+        routing index `rows`, then the down projection with the routing weight (fp32) in its epilogue, which also writes
+        the rows past offsets[E] (ids outside [0, E)) as zeros.  `pos` is read by the GLU launch's backward only."""
+        gate, up, down = self.gate, self.up, self.down
+        num_sms = _stack_num_sms(gate, hidden.device)
+        glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms))
+        h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales, _table_of(up),
+                gate.num_bits, gate.group_size, gate.template_id, num_sms, rows=rows, pos=pos)
+        return weighted(h, offsets, down.weight, down.scales, _table_of(down), row_weight, down.num_bits, down.group_size,
+                        down.template_id, num_sms)
 
     def _takes_wide_routing(self, tokens: int, top_k: int, gated: bool) -> bool:
         """Whether this step's routing is the multi-workgroup one: `wide_routing`, "auto" resolved from the shapes alone."""
@@ -453,19 +458,12 @@ class FluteExperts(torch.nn.Module):
 
     def _forward_routed(self, hidden, offsets, rows, row_weight, pos):
         """The launches behind the routing arrays, whichever kernel wrote them (`moe_route`, `moe_gate_route[_limited]`, their `_wide` forms)."""
-        gate, up, down = self.gate, self.up, self.down
         if self.fused:
-            num_sms = gate.num_sms if gate.num_sms is not None else flute_amd.utils.get_device_num_sms(hidden.device)
-            glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms))
-            h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight,
-                    up.scales, _table_of(up), gate.num_bits, gate.group_size, gate.template_id,
-                    num_sms, rows=rows, pos=pos)          # (pos: read by the backward only)
-            y = weighted(h, offsets, down.weight, down.scales, _table_of(down), row_weight,
-                         down.num_bits, down.group_size, down.template_id, num_sms)
+            y = self._fused_mlp(hidden, offsets, rows, row_weight, pos)
         else:
             x = hidden[rows]
-            h = torch.nn.functional.silu(gate(x, offsets)) * up(x, offsets)
-            y = down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
+            h = torch.nn.functional.silu(self.gate(x, offsets)) * self.up(x, offsets)
+            y = self.down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
         return flute_amd.moe_combine(y, pos, offsets, rows if self.native_router_grad else None)
 
 

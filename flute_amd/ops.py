@@ -8,9 +8,13 @@ and a few torch ops; otherwise they take exactly the path they always took.  Eac
 function, which also carries the gradients of the stacks' scales (`qgemm_grouped_scale_grad`) and of their fp32 master
 codebooks (`qgemm_grouped_table_grad`): the ops themselves refuse packed stacks that require grad, `integrations.learnable`
 opens those slots.  Every validator of a packed layer or stack is
-three calls into one set of checks (`_check_ranks`, `_check_dtypes`, `_check_packed`), and every grouped launch -
-forward, input gradient, scale gradient - ends in `_launch_grouped`; the table gradient alone, with its two results and its
-scratch, makes its call itself.
+three calls into one set of checks (`_check_ranks`, `_check_dtypes`, `_check_packed`); the validators of the routing,
+row-stream and router-gradient ops open with the first two and keep by hand only the checks whose order of exception classes
+those three phases cannot express.  Every grouped launch - forward, input gradient, scale gradient - ends in `_launch_grouped`,
+and every other call into the C ABI - the Hadamard transform, the dense and grouped parameter gradients, routing, gating,
+combine, gather and the router's gradients - ends in `_abi_call`: the same-GPU check (`_same_gpu`, the one place that words
+it), `_abi_tensor` on the inputs only, the device guard, the stream, the return code.  The five routing arrays and the wide
+launches' workspace are allocated in `_routing_arrays`, for `moe_route[_wide]` and the gating ops alike.
 
 Schemas are the reference's, verbatim (flute/csrc/qgemm.cpp:251-254); the
 implementation is registered for the `CUDA` dispatch key (HIP tensors use it on
@@ -69,6 +73,7 @@ def _validate(input, weight, scales, table, table2, workspace, num_bits, group_s
 
 
 def _stream_ptr(device):
+    """The current stream of `device` (a `torch.device` or its index) as the C ABI takes it."""
     return torch.cuda.current_stream(device).cuda_stream
 
 
@@ -86,6 +91,39 @@ def _num_sms(num_sms, device):
     return torch.cuda.get_device_properties(device).multi_processor_count if num_sms is None else num_sms
 
 
+def _same_gpu(name, tensors):
+    """The one GPU that `tensors` (None: absent) live on - the first one's - or RuntimeError in op `name`'s name."""
+    dev = tensors[0].device
+    for t in tensors:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise RuntimeError(f"flute_amd.{name}: all tensors must live on the same GPU")
+    return dev
+
+
+def _abi_call(name, fn, head, inputs, outputs, tail=(), dev=None):
+    """The tail of every validated op that is not a grouped launch: fn(*head, *pointers of `inputs`, *pointers of `outputs`,
+    *tail, stream) on the inputs' GPU, the return code checked.  `inputs` (None: a null pointer) are checked to share one GPU
+    (`_same_gpu`, in op `name`'s name; `dev`: the caller has asked already, before it allocated or because it may return
+    before it launches) and go through `_abi_tensor`, the copies alive across the call.  `outputs` - results and scratch the
+    caller allocated, None: a null pointer - are handed on as they are: a copy of one would lose the result, so nothing here
+    ever copies them.  One pass, one argument list; the guard and the stream are asked by device index, which spares torch
+    resolving a `torch.device` twice per call."""
+    if dev is None:
+        dev = _same_gpu(name, inputs)
+    args, kept = [*head], []
+    for t in inputs:
+        if t is not None:
+            t = _abi_tensor(t)
+            kept.append(t)
+            t = t.data_ptr()
+        args.append(t)
+    for t in outputs:
+        args.append(t if t is None else t.data_ptr())
+    index = dev.index
+    with torch.cuda.device(index):
+        _lib.check(fn(*args, *tail, _stream_ptr(index)))
+
+
 def hadamard_transform(input: torch.Tensor, hadamard_size: int) -> torch.Tensor:
     """apply_hadamard (qgemm.cpp:201-211): out-of-place FWHT over
     input.reshape(-1, hadamard_size), orthonormal."""
@@ -95,13 +133,10 @@ def hadamard_transform(input: torch.Tensor, hadamard_size: int) -> torch.Tensor:
         raise RuntimeError("flute_amd.hadamard_transform: tensor must live on the GPU")
     if input.shape[-1] % hadamard_size and input.numel() % hadamard_size:
         raise RuntimeError(f"shape {tuple(input.shape)} is invalid for hadamard_size {hadamard_size}")
-    x = _abi_tensor(input)
-    out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.get().flute_hadamard(
-            _DTYPE_ID[x.dtype], x.data_ptr(), out.data_ptr(), x.numel(), hadamard_size,
-            _stream_ptr(x.device)))
-    return out.view(input.shape)
+    out = torch.empty(input.shape, dtype=input.dtype, device=input.device)
+    _abi_call("hadamard_transform", _lib.get().flute_hadamard, (_DTYPE_ID[input.dtype],), (input,), (out,),
+              (input.numel(), hadamard_size))
+    return out
 
 
 @torch.library.register_fake("flute::qgemm_raw_simple")
@@ -125,17 +160,20 @@ def _qgemm_raw_simple_hadamard_abstract(input, weight, scales, table, table2, wo
 
 def _check_ranks(*tensor_ndim):
     """(tensor, ndim) pairs; "at least 2" is (t, max(t.ndim, 2))."""
-    if not all(t.ndim == ndim for t, ndim in tensor_ndim):
-        raise ValueError
+    for t, ndim in tensor_ndim:
+        if t.ndim != ndim:
+            raise ValueError
 
 
-def _check_dtypes(dtype, like=(), int16=(), fp32=(), int32=()):
-    """`dtype` - the activations' - is fp16 or bf16, the `like` tensors have it and the others their fixed type."""
-    if dtype not in _DTYPE_ID or not all(t.dtype == dtype for t in like):
+def _check_dtypes(dtype, like=(), int16=(), fp32=(), int32=(), allowed=_DTYPE_ID):
+    """`dtype` - the activations' - is fp16 or bf16 (one of `allowed`), the `like` tensors have it and the others their fixed
+    type."""
+    if dtype not in allowed:
         raise TypeError
-    if not all(t.dtype == want for ts, want in ((int16, torch.int16), (fp32, torch.float32), (int32, torch.int32))
-               for t in ts):
-        raise TypeError
+    for ts, want in ((like, dtype), (int16, torch.int16), (fp32, torch.float32), (int32, torch.int32)):
+        for t in ts:
+            if t.dtype != want:
+                raise TypeError
 
 
 def _pair_table_shape(num_bits, lead=()):
@@ -210,12 +248,9 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     in input.dtype.  For a Hadamard layer pass the rotated input, `hadamard_transform(input, hadamard_size)`.
     A native HIP kernel on the current stream (param_grad.hip); the same arguments give the same bits."""
     _validate_scale_grad(grad_output, input, weight, table2, num_bits, group_size)
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in (grad_output, input, weight, table2)):
-        raise RuntimeError("flute_amd.qgemm_scale_grad: all tensors must live on the same GPU")
+    dev = _same_gpu("qgemm_scale_grad", (input, grad_output, weight, table2))
     K, N = input.shape[-1], grad_output.shape[-1]
-    x = _abi_tensor(input.reshape(-1, K))
-    dy = _abi_tensor(grad_output.reshape(-1, N))
+    x, dy = input.reshape(-1, K), grad_output.reshape(-1, N)
     M = x.shape[0]
     if M >= 2 ** 31:
         raise ValueError
@@ -223,14 +258,11 @@ def qgemm_scale_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if M == 0:
         return out.zero_()
     num_sms = _num_sms(num_sms, dev)
-    scratch = torch.empty(_scale_grad_scratch_bytes(N, K, group_size, num_sms), dtype=torch.uint8, device=dev)
-    w = _abi_tensor(weight)
-    t2 = _abi_tensor(table2)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_qgemm_scale_grad(
-            _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
-            dy.data_ptr(), x.data_ptr(), w.data_ptr(), t2.data_ptr(), out.data_ptr(),
-            scratch.data_ptr() if scratch.numel() else None, scratch.numel(), num_sms, _stream_ptr(dev)))
+    nbytes = _scale_grad_scratch_bytes(N, K, group_size, num_sms)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _abi_call("qgemm_scale_grad", _lib.get().flute_qgemm_scale_grad,
+              (_DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, weight.shape[0], template_id),
+              (dy, x, weight, table2), (out, scratch if nbytes else None), (nbytes, num_sms), dev)
     return out
 
 
@@ -264,13 +296,9 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     Hadamard layer pass the rotated input.  Native HIP kernels on the current stream (param_grad.hip); the same
     arguments give the same bits."""
     _validate_table_grad(grad_output, input, weight, scales, table2, num_bits, group_size, with_scale_grad)
-    dev = input.device
-    tensors = (grad_output, input, weight, scales) + ((table2,) if table2 is not None else ())
-    if not all(t.is_cuda and t.device == dev for t in tensors):
-        raise RuntimeError("flute_amd.qgemm_table_grad: all tensors must live on the same GPU")
+    dev = _same_gpu("qgemm_table_grad", (input, grad_output, weight, scales, table2))
     K, N = input.shape[-1], grad_output.shape[-1]
-    x = _abi_tensor(input.reshape(-1, K))
-    dy = _abi_tensor(grad_output.reshape(-1, N))
+    x, dy = input.reshape(-1, K), grad_output.reshape(-1, N)
     M = x.shape[0]
     if M >= 2 ** 31:
         raise ValueError
@@ -286,15 +314,9 @@ def qgemm_table_grad(grad_output: torch.Tensor, input: torch.Tensor, weight: tor
     if nbytes == 0:
         raise ValueError(f"flute_amd.qgemm_table_grad: no kernel for N = {N}, K = {K}, group size {group_size}")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    w = _abi_tensor(weight)
-    s = _abi_tensor(scales)
-    t2 = _abi_tensor(table2) if with_scale_grad else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.flute_qgemm_table_grad(
-            _DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, w.shape[0], template_id,
-            dy.data_ptr(), x.data_ptr(), w.data_ptr(), s.data_ptr(), t2.data_ptr() if t2 is not None else None,
-            dT2.data_ptr(), dS.data_ptr() if dS is not None else None, scratch.data_ptr(), nbytes, num_sms,
-            _stream_ptr(dev)))
+    _abi_call("qgemm_table_grad", lib.flute_qgemm_table_grad,
+              (_DTYPE_ID[x.dtype], num_bits, group_size, M, N, K, weight.shape[0], template_id),
+              (dy, x, weight, scales, table2 if with_scale_grad else None), (dT2, dS, scratch), (nbytes, num_sms), dev)
     return (dT2, dS) if with_scale_grad else dT2
 
 
@@ -404,19 +426,18 @@ def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=
     form = tuple(form_id(f) for f in form)
     num_bits, group_size, template_id, num_sms = layer
     first = tensors[0]
-    dev = first.device
-    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
-        raise RuntimeError(f"flute_amd.{name}: all tensors must live on the same GPU")
+    dev = _same_gpu(name, tensors)
     if max(rows) >= row_limit:
         raise ValueError
     ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
     out = torch.empty(out_shape, dtype=first.dtype, device=dev)
     num_sms = _num_sms(num_sms, dev)
     E, P, K = weight.shape
-    with torch.cuda.device(dev):
+    index = dev.index                                           # (as `_abi_call`: torch resolves a `torch.device` slowly)
+    with torch.cuda.device(index):
         _lib.check(getattr(_lib.get(), "flute_" + name)(
             _DTYPE_ID[first.dtype], num_bits, group_size, E, *rows, N, K, P, template_id,
-            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(dev), *form))
+            *[None if t is None else t.data_ptr() for t in ptrs], out.data_ptr(), num_sms, _stream_ptr(index), *form))
     return out
 
 
@@ -874,9 +895,7 @@ def qgemm_grouped_table_grad(grad_output: torch.Tensor, input: torch.Tensor, off
     tensors = (grad_output, input, offsets, weight, scales, table2 if with_scale_grad else None, row_weight)
     if _records_grad(*tensors, table2):
         raise RuntimeError("flute_amd.qgemm_grouped_table_grad: the backward is once-differentiable (no double backward)")
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in tensors if t is not None):
-        raise RuntimeError("flute_amd.qgemm_grouped_table_grad: all tensors must live on the same GPU")
+    dev = _same_gpu("qgemm_grouped_table_grad", tensors)
     R, K = input.shape
     E, P, N = weight.shape[0], weight.shape[1], grad_output.shape[1]
     if R >= 2 ** 31 - 64:
@@ -891,13 +910,9 @@ def qgemm_grouped_table_grad(grad_output: torch.Tensor, input: torch.Tensor, off
             raise ValueError(f"flute_amd.qgemm_grouped_table_grad: no kernel for E = {E}, N = {N}, K = {K}, "
                              f"group size {group_size}")
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ptrs = [None if t is None else _abi_tensor(t) for t in tensors]
-        with torch.cuda.device(dev):
-            _lib.check(lib.flute_qgemm_grouped_table_grad(
-                _DTYPE_ID[input.dtype], num_bits, group_size, E, R, N, K, P, template_id,
-                *[None if t is None else t.data_ptr() for t in ptrs], dT2.data_ptr(),
-                dS.data_ptr() if dS is not None else None, scratch.data_ptr(), nbytes, _num_sms(num_sms, dev),
-                _stream_ptr(dev)))
+        _abi_call("qgemm_grouped_table_grad", lib.flute_qgemm_grouped_table_grad,
+                  (_DTYPE_ID[input.dtype], num_bits, group_size, E, R, N, K, P, template_id),
+                  tensors, (dT2, dS, scratch), (nbytes, _num_sms(num_sms, dev)), dev)
     return (dT2, dS) if with_scale_grad else dT2
 
 
@@ -954,12 +969,6 @@ def _validate_chunk_tokens(chunk_tokens, T):
     return chunk_tokens
 
 
-def _route_wide_workspace(T, k, E, chunk_tokens, dev):
-    """The wide launches' workspace: the queried size, from the caching allocator per call (capturable); the kernels write every
-    word they read, so it is not cleared."""
-    return torch.empty(_lib.get().flute_moe_route_wide_workspace(T, k, E, chunk_tokens), dtype=torch.uint8, device=dev)
-
-
 def moe_route_wide(topk_ids: torch.Tensor, topk_weights, num_experts: int, chunk_tokens=None):
     """`moe_route` over many workgroups, for prefill and training token counts: the same five arrays (offsets, rows,
     row_weight, pos, perm), bit for bit, from three launches - count, scan, place (moe_route_wide.hip) - in which chunk c
@@ -996,28 +1005,32 @@ class _MoeRouteFunction(torch.autograd.Function):
 
 def _moe_route_call(topk_ids, topk_weights, num_experts, wide=None):
     """One routing call: flute_moe_route, or with `wide` (the ABI's chunk_tokens, 0 automatic) flute_moe_route_wide."""
-    dev = topk_ids.device
-    if not all(t.is_cuda and t.device == dev for t in (topk_ids,) + (() if topk_weights is None else (topk_weights,))):
-        raise RuntimeError("flute_amd.moe_route: all tensors must live on the same GPU")
+    dev = _same_gpu("moe_route", (topk_ids, topk_weights))      # (refused before anything is allocated)
     T, k = topk_ids.shape
-    P, E = T * k, int(num_experts)
-    ids = _abi_tensor(topk_ids)
-    w = None if topk_weights is None else _abi_tensor(topk_weights)
+    E = int(num_experts)
+    outputs, tail = _routing_arrays(T, k, E, dev, topk_weights is not None, wide)
+    _abi_call("moe_route", _lib.get().flute_moe_route if wide is None else _lib.get().flute_moe_route_wide,
+              (_INDEX_DTYPE_ID[topk_ids.dtype], 0 if topk_weights is None else _ROUTE_WEIGHT_DTYPE_ID[topk_weights.dtype],
+               T, k, E), (topk_ids, topk_weights), outputs, tail, dev)
+    offsets, perm, rows, row_weight, pos = outputs[:5]
+    return offsets, rows, row_weight, pos, perm
+
+
+def _routing_arrays(T, k, E, dev, weighted, wide=None):
+    """What a routing launch writes, in the ABI's order, and the ABI's arguments behind them: (offsets [E + 1], perm [T k],
+    rows [T k], row_weight [T k] fp32 - None unless `weighted` -, pos [T, k]), (); with `wide` (the ABI's chunk_tokens, 0
+    automatic) the wide launches' workspace comes behind pos - the queried size, from the caching allocator per call
+    (capturable); the kernels write every word they read, so it is not cleared - and the tail is (its bytes, chunk_tokens)."""
+    P = T * k
     offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(P, dtype=torch.int32, device=dev)
     rows = torch.empty(P, dtype=torch.int32, device=dev)
     pos = torch.empty((T, k), dtype=torch.int32, device=dev)
-    row_weight = None if w is None else torch.empty(P, dtype=torch.float32, device=dev)
-    head = (_INDEX_DTYPE_ID[ids.dtype], 0 if w is None else _ROUTE_WEIGHT_DTYPE_ID[w.dtype], T, k, E, ids.data_ptr(),
-            None if w is None else w.data_ptr(), offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(),
-            None if row_weight is None else row_weight.data_ptr(), pos.data_ptr())
-    with torch.cuda.device(dev):
-        if wide is None:
-            _lib.check(_lib.get().flute_moe_route(*head, _stream_ptr(dev)))
-        else:
-            ws = _route_wide_workspace(T, k, E, wide, dev)
-            _lib.check(_lib.get().flute_moe_route_wide(*head, ws.data_ptr(), ws.numel(), wide, _stream_ptr(dev)))
-    return offsets, rows, row_weight, pos, perm
+    arrays = (offsets, perm, rows, torch.empty(P, dtype=torch.float32, device=dev) if weighted else None, pos)
+    if wide is None:
+        return arrays, ()
+    nbytes = _lib.get().flute_moe_route_wide_workspace(T, k, E, wide)
+    return arrays + (torch.empty(nbytes, dtype=torch.uint8, device=dev),), (nbytes, wide)
 
 
 _GATE_SCORING_ID = {"softmax": 0, "sigmoid": 1}     # include/flute_amd.h flute_gate_scoring
@@ -1052,35 +1065,19 @@ def _moe_gate_call(logits, k, scoring, renormalize, bias, scale, routed, groups=
         groups = (1, 1, "max")                                  # topk_group == n_group: the unlimited gating
     name = "moe_gate_route_wide" if wide is not None else \
         "moe_gate" + ("_route" if routed else "") + ("" if groups is None else "_limited")
-    dev = logits.device
-    if not all(t.is_cuda and t.device == dev for t in (logits,) + (() if bias is None else (bias,))):
-        raise RuntimeError("flute_amd.%s: all tensors must live on the same GPU" % name)
+    dev = _same_gpu(name, (logits, bias))                       # (refused before anything is allocated)
     T, E = logits.shape
     k = int(k)
-    x = _abi_tensor(logits)
-    b = None if bias is None else _abi_tensor(bias)
     ids = torch.empty((T, k), dtype=torch.int32, device=dev)
     weights = torch.empty((T, k), dtype=torch.float32, device=dev)
+    routing, tail = _routing_arrays(T, k, E, dev, True, wide) if routed else ((), ())
     group_args = () if groups is None else (int(groups[0]), int(groups[1]), _GATE_GROUP_SCORE_ID[groups[2]])
-    head = (_ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, *group_args, _GATE_SCORING_ID[scoring], int(bool(renormalize)),
-            float(scale), x.data_ptr(), None if b is None else b.data_ptr(), ids.data_ptr(), weights.data_ptr())
-    fn = getattr(_lib.get(), "flute_" + name)
-    with torch.cuda.device(dev):
-        if not routed:
-            _lib.check(fn(*head, _stream_ptr(dev)))
-            return ids, weights
-        P = T * k
-        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
-        perm = torch.empty(P, dtype=torch.int32, device=dev)
-        rows = torch.empty(P, dtype=torch.int32, device=dev)
-        row_weight = torch.empty(P, dtype=torch.float32, device=dev)
-        pos = torch.empty((T, k), dtype=torch.int32, device=dev)
-        tail = ()
-        if wide is not None:
-            ws = _route_wide_workspace(T, k, E, wide, dev)
-            tail = (ws.data_ptr(), ws.numel(), wide)
-        _lib.check(fn(*head, offsets.data_ptr(), perm.data_ptr(), rows.data_ptr(), row_weight.data_ptr(), pos.data_ptr(),
-                      *tail, _stream_ptr(dev)))
+    _abi_call(name, getattr(_lib.get(), "flute_" + name),
+              (_ROUTE_WEIGHT_DTYPE_ID[logits.dtype], T, E, k, *group_args, _GATE_SCORING_ID[scoring], int(bool(renormalize)),
+               float(scale)), (logits, bias), (ids, weights, *routing), tail, dev)
+    if not routed:
+        return ids, weights
+    offsets, perm, rows, row_weight, pos = routing[:5]
     return ids, weights, offsets, rows, row_weight, pos, perm
 
 
@@ -1232,18 +1229,11 @@ def moe_gate_route_wide(logits: torch.Tensor, k: int, num_experts=None, scoring:
 
 
 def _validate_moe_combine(y, pos, offsets, rows=None):
-    if not all([y.ndim == 2, pos.ndim == 2, offsets.ndim == 1]):
+    _check_ranks((y, 2), (pos, 2), (offsets, 1))
+    _check_dtypes(y.dtype, int32=(pos, offsets) if rows is None else (pos, offsets, rows))
+    if rows is not None and (rows.ndim != 1 or rows.shape[0] != y.shape[0]):
         raise ValueError
-    if y.dtype not in _DTYPE_ID or pos.dtype != torch.int32 or offsets.dtype != torch.int32:
-        raise TypeError
-    if rows is not None:
-        if rows.dtype != torch.int32:
-            raise TypeError
-        if rows.ndim != 1 or rows.shape[0] != y.shape[0]:
-            raise ValueError
-    if y.shape[0] != pos.shape[0] * pos.shape[1] or offsets.shape[0] < 1 or y.shape[1] % 8 != 0:
-        raise ValueError
-    if y.shape[0] >= 2 ** 31:
+    if y.shape[0] != pos.shape[0] * pos.shape[1] or offsets.shape[0] < 1 or y.shape[1] % 8 != 0 or y.shape[0] >= 2 ** 31:
         raise ValueError
 
 
@@ -1296,21 +1286,17 @@ class _MoeCombineFunction(torch.autograd.Function):
 
 
 def _moe_combine_call(y, pos, offsets):
-    dev = y.device
-    if not all(t.is_cuda and t.device == dev for t in (y, pos, offsets)):
-        raise RuntimeError("flute_amd.moe_combine: all tensors must live on the same GPU")
     T, k = pos.shape
     N = y.shape[1]
-    yc, p, off = _abi_tensor(y), _abi_tensor(pos), _abi_tensor(offsets)
-    out = torch.empty((T, N), dtype=y.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_moe_combine(
-            _DTYPE_ID[yc.dtype], T, k, off.shape[0] - 1, N, yc.data_ptr(), p.data_ptr(), off.data_ptr(), out.data_ptr(),
-            _stream_ptr(dev)))
+    out = torch.empty((T, N), dtype=y.dtype, device=y.device)
+    _abi_call("moe_combine", _lib.get().flute_moe_combine, (_DTYPE_ID[y.dtype], T, k, offsets.shape[0] - 1, N),
+              (y, pos, offsets), (out,))
     return out
 
 
 def _validate_row_stream_offsets(offsets):
+    """`offsets` of the row-stream ops: None, or int32 of E + 1 >= 1 entries - rank, type, length, in that order, a run of
+    ValueError, TypeError, ValueError that the callers' three phases cannot hold: written out."""
     if offsets is None:
         return
     if offsets.ndim != 1:
@@ -1328,14 +1314,10 @@ def _refuse_grad(name, *tensors):
 
 
 def _validate_swiglu_grad(g, u, grad_output, offsets):
-    if not all([g.ndim == 2, u.ndim == 2, grad_output.ndim == 2]):
-        raise ValueError
-    if g.dtype not in _DTYPE_ID or u.dtype != g.dtype or grad_output.dtype != g.dtype:
-        raise TypeError
+    _check_ranks((g, 2), (u, 2), (grad_output, 2))
+    _check_dtypes(g.dtype, like=(u, grad_output))
     _validate_row_stream_offsets(offsets)
-    if tuple(u.shape) != tuple(g.shape) or tuple(grad_output.shape) != tuple(g.shape) or g.shape[1] % 8 != 0:
-        raise ValueError
-    if g.shape[0] >= 2 ** 31:
+    if not u.shape == grad_output.shape == g.shape or g.shape[1] % 8 != 0 or g.shape[0] >= 2 ** 31:
         raise ValueError
 
 
@@ -1349,30 +1331,21 @@ def swiglu_grad(g: torch.Tensor, u: torch.Tensor, grad_output: torch.Tensor, off
     native HIP kernel on the current stream (swiglu_grad.hip); equal arguments give equal bits."""
     _validate_swiglu_grad(g, u, grad_output, offsets)
     _refuse_grad("swiglu_grad", g, u, grad_output)
-    dev = g.device
-    if not all(t.is_cuda and t.device == dev for t in (g, u, grad_output, offsets) if t is not None):
-        raise RuntimeError("flute_amd.swiglu_grad: all tensors must live on the same GPU")
     R, F = g.shape
-    gc, uc, dh = _abi_tensor(g), _abi_tensor(u), _abi_tensor(grad_output)
-    off = None if offsets is None else _abi_tensor(offsets)
-    dg = torch.empty((R, F), dtype=g.dtype, device=dev)
-    du = torch.empty((R, F), dtype=g.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_swiglu_grad(
-            _DTYPE_ID[g.dtype], R, F, 0 if off is None else off.shape[0] - 1, gc.data_ptr(), uc.data_ptr(), dh.data_ptr(),
-            None if off is None else off.data_ptr(), dg.data_ptr(), du.data_ptr(), _stream_ptr(dev)))
+    dg = torch.empty((R, F), dtype=g.dtype, device=g.device)
+    du = torch.empty((R, F), dtype=g.dtype, device=g.device)
+    _abi_call("swiglu_grad", _lib.get().flute_swiglu_grad,
+              (_DTYPE_ID[g.dtype], R, F, 0 if offsets is None else offsets.shape[0] - 1),
+              (g, u, grad_output, offsets), (dg, du))
     return dg, du
 
 
 def _validate_moe_gather(input, rows, offsets):
-    if input.ndim != 2 or rows.ndim != 1:
-        raise ValueError
-    if input.dtype not in _DTYPE_ID or rows.dtype != torch.int32:
-        raise TypeError
+    _check_ranks((input, 2), (rows, 1))
+    _check_dtypes(input.dtype, int32=(rows,))
     _validate_row_stream_offsets(offsets)
-    if input.shape[1] % 8 != 0 or (input.shape[0] == 0 and rows.shape[0] > 0):
-        raise ValueError
-    if max(input.shape[0], rows.shape[0]) >= 2 ** 31:
+    if input.shape[1] % 8 != 0 or (input.shape[0] == 0 and rows.shape[0] > 0) or \
+            max(input.shape[0], rows.shape[0]) >= 2 ** 31:
         raise ValueError
 
 
@@ -1385,30 +1358,20 @@ def moe_gather(input: torch.Tensor, rows: torch.Tensor, offsets=None) -> torch.T
     on the current stream (swiglu_grad.hip)."""
     _validate_moe_gather(input, rows, offsets)
     _refuse_grad("moe_gather", input)
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in (input, rows, offsets) if t is not None):
-        raise RuntimeError("flute_amd.moe_gather: all tensors must live on the same GPU")
     Tsrc, K = input.shape
     R = rows.shape[0]
-    x, rw = _abi_tensor(input), _abi_tensor(rows)
-    off = None if offsets is None else _abi_tensor(offsets)
-    out = torch.empty((R, K), dtype=input.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_moe_gather(
-            _DTYPE_ID[input.dtype], R, Tsrc, K, 0 if off is None else off.shape[0] - 1, x.data_ptr(), rw.data_ptr(),
-            None if off is None else off.data_ptr(), out.data_ptr(), _stream_ptr(dev)))
+    out = torch.empty((R, K), dtype=input.dtype, device=input.device)
+    _abi_call("moe_gather", _lib.get().flute_moe_gather,
+              (_DTYPE_ID[input.dtype], R, Tsrc, K, 0 if offsets is None else offsets.shape[0] - 1),
+              (input, rows, offsets), (out,))
     return out
 
 
 def _validate_moe_weight_grad(grad_unweighted, input, row_weight, offsets, want_input_grad):
-    if grad_unweighted.ndim != 2 or input.ndim != 2:
-        raise ValueError
-    if grad_unweighted.dtype not in _DTYPE_ID or input.dtype != grad_unweighted.dtype:
-        raise TypeError
+    _check_ranks((grad_unweighted, 2), (input, 2))
+    _check_dtypes(grad_unweighted.dtype, like=(input,))
     _validate_row_stream_offsets(offsets)
-    if tuple(input.shape) != tuple(grad_unweighted.shape) or input.shape[1] % 8 != 0:
-        raise ValueError
-    if input.shape[0] >= 2 ** 31:
+    if input.shape != grad_unweighted.shape or input.shape[1] % 8 != 0 or input.shape[0] >= 2 ** 31:
         raise ValueError
     if row_weight is None:
         if want_input_grad:
@@ -1430,28 +1393,20 @@ def moe_weight_grad(grad_unweighted: torch.Tensor, input: torch.Tensor, row_weig
     native HIP kernel on the current stream (router_grad.hip); equal arguments give equal bits."""
     _validate_moe_weight_grad(grad_unweighted, input, row_weight, offsets, want_input_grad)
     _refuse_grad("moe_weight_grad", grad_unweighted, input, row_weight)
-    dev = input.device
-    if not all(t.is_cuda and t.device == dev for t in (grad_unweighted, input, row_weight, offsets) if t is not None):
-        raise RuntimeError("flute_amd.moe_weight_grad: all tensors must live on the same GPU")
     R, K = input.shape
-    dhp, h = _abi_tensor(grad_unweighted), _abi_tensor(input)
-    rw = _abi_tensor(row_weight) if want_input_grad else None
-    off = None if offsets is None else _abi_tensor(offsets)
+    dev = _same_gpu("moe_weight_grad", (input, grad_unweighted, row_weight, offsets))
     d_weight = torch.empty((R,), dtype=torch.float32, device=dev)
     d_input = torch.empty((R, K), dtype=input.dtype, device=dev) if want_input_grad else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_moe_weight_grad(
-            _DTYPE_ID[input.dtype], R, K, 0 if off is None else off.shape[0] - 1, dhp.data_ptr(), h.data_ptr(),
-            None if rw is None else rw.data_ptr(), None if off is None else off.data_ptr(), d_weight.data_ptr(),
-            None if d_input is None else d_input.data_ptr(), _stream_ptr(dev)))
+    # (the sums alone read no `row_weight`: the ABI takes row_weight and d_input together or not at all)
+    _abi_call("moe_weight_grad", _lib.get().flute_moe_weight_grad,
+              (_DTYPE_ID[input.dtype], R, K, 0 if offsets is None else offsets.shape[0] - 1),
+              (grad_unweighted, input, row_weight if want_input_grad else None, offsets), (d_weight, d_input), dev=dev)
     return d_weight, d_input
 
 
 def _validate_moe_gate_grad(logits, ids, grad_weights, scoring, grad_row_weight, pos):
-    if logits.ndim != 2 or ids.ndim != 2:
-        raise ValueError
-    if logits.dtype not in _ROUTE_WEIGHT_DTYPE_ID or ids.dtype != torch.int32:
-        raise TypeError
+    _check_ranks((logits, 2), (ids, 2))
+    _check_dtypes(logits.dtype, int32=(ids,), allowed=_ROUTE_WEIGHT_DTYPE_ID)
     if scoring not in _GATE_SCORING_ID:
         raise ValueError
     (T, E), k = logits.shape, ids.shape[1]
@@ -1487,18 +1442,9 @@ def moe_gate_grad(logits: torch.Tensor, ids: torch.Tensor, grad_weights, scoring
     stream (router_grad.hip); equal arguments give equal bits, and a token's result does not depend on T or its row."""
     _validate_moe_gate_grad(logits, ids, grad_weights, scoring, grad_row_weight, pos)
     _refuse_grad("moe_gate_grad", logits, grad_weights, grad_row_weight)
-    dev = logits.device
-    if not all(t.is_cuda and t.device == dev for t in (logits, ids, grad_weights, grad_row_weight, pos) if t is not None):
-        raise RuntimeError("flute_amd.moe_gate_grad: all tensors must live on the same GPU")
     T, E = logits.shape
-    k = ids.shape[1]
-    x, i = _abi_tensor(logits), _abi_tensor(ids)
-    q = None if grad_weights is None else _abi_tensor(grad_weights)
-    drw, p = (None, None) if pos is None else (_abi_tensor(grad_row_weight), _abi_tensor(pos))
-    out = torch.empty((T, E), dtype=logits.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().flute_moe_gate_grad(
-            _ROUTE_WEIGHT_DTYPE_ID[x.dtype], T, E, k, _GATE_SCORING_ID[scoring], int(bool(renormalize)), float(scale),
-            x.data_ptr(), i.data_ptr(), None if q is None else q.data_ptr(), None if drw is None else drw.data_ptr(),
-            None if p is None else p.data_ptr(), out.data_ptr(), _stream_ptr(dev)))
+    out = torch.empty((T, E), dtype=logits.dtype, device=logits.device)
+    _abi_call("moe_gate_grad", _lib.get().flute_moe_gate_grad,
+              (_ROUTE_WEIGHT_DTYPE_ID[logits.dtype], T, E, ids.shape[1], _GATE_SCORING_ID[scoring], int(bool(renormalize)),
+               float(scale)), (logits, ids, grad_weights, grad_row_weight, pos), (out,))
     return out

@@ -291,3 +291,57 @@ def test_abi_tensor_realigns_views():
     t = buf[:64].view(8, 8).t()                                  # aligned but not contiguous
     c = _abi_tensor(t)
     assert c.is_contiguous() and c.data_ptr() % 16 == 0 and torch.equal(c, t)
+
+
+def test_abi_call_tail_on_stubbed_abi(monkeypatch):
+    """ops._abi_call, the tail of every op that is not a grouped launch, with a stub in the ctypes function's place: the inputs
+    must share one GPU (None skipped, the error names the op), each input goes through _abi_tensor - itself when aligned, a
+    copy that is alive and equal while the ABI runs otherwise - None is a null pointer, outputs are handed on as the
+    objects they are, never copied, and head, tail and the stream keep their places."""
+    import contextlib
+    import ctypes
+    import torch
+    from flute_amd import ops
+
+    class OnGpu(torch.Tensor):                                   # a CPU (or meta) tensor that says it lives on a GPU
+        is_cuda = True
+
+    gpu = lambda t: t.as_subclass(OnGpu)
+    buf = gpu(torch.arange(64 + 16, dtype=torch.float32).to(torch.float16))
+    aligned, unaligned, strided = buf[8:8 + 64].view(8, 8), buf[1:1 + 64].view(8, 8), buf[:64].view(8, 8).t()
+    assert aligned.data_ptr() % 16 == 0 and unaligned.is_contiguous() and unaligned.data_ptr() % 16 != 0
+    out = gpu(torch.empty(80, dtype=torch.float16))
+    out_view = out[1:65]                                         # an output is never realigned: a copy would lose the result
+    assert out_view.data_ptr() % 16 != 0
+
+    seen, passed = [], []
+    real = ops._abi_tensor
+    monkeypatch.setattr(ops, "_abi_tensor", lambda t: passed.append((t, real(t))) or passed[-1][1])
+    monkeypatch.setattr(ops, "_stream_ptr", lambda dev: 4242)
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+
+    def stub(*args):
+        seen.append(args)
+        for (t, c), ptr in zip(passed, args[2:2 + len(passed)]):  # the copies are alive and hold the values right now
+            now = (ctypes.c_uint16 * 64).from_address(ptr)
+            assert list(now) == (t.contiguous().view(torch.int16).reshape(-1).to(torch.int32) & 0xFFFF).tolist()
+        return 0
+
+    assert ops._abi_call("some_op", stub, (7, 8), (aligned, unaligned, strided, None), (out, None, out_view), (9,)) is None
+    (args,) = seen
+    (a_in, a_out), (u_in, u_out), (s_in, s_out) = passed         # outputs and None never reach _abi_tensor
+    assert a_in is aligned and a_out is aligned
+    assert u_in is unaligned and u_out is not unaligned and u_out.data_ptr() % 16 == 0 and torch.equal(u_out, unaligned)
+    assert s_in is strided and s_out.is_contiguous() and s_out.data_ptr() % 16 == 0 and torch.equal(s_out, strided)
+    assert args == (7, 8, aligned.data_ptr(), u_out.data_ptr(), s_out.data_ptr(), None, out.data_ptr(), None,
+                    out_view.data_ptr(), 9, 4242)
+
+    def refused(*a):
+        raise AssertionError("launched")
+    elsewhere = gpu(torch.empty(8, dtype=torch.float16, device="meta"))
+    for inputs in ((aligned, None, elsewhere), (aligned, torch.zeros(8))):      # another device; a tensor on no GPU at all
+        with pytest.raises(RuntimeError, match=r"flute_amd\.some_op: all tensors must live on the same GPU"):
+            ops._abi_call("some_op", refused, (), inputs, (out,))
+    with pytest.raises(RuntimeError) as refusal:                                # the return code is checked
+        ops._abi_call("some_op", lambda *a: -4, (), (aligned,), (out,))
+    assert "same GPU" not in str(refusal.value)
