@@ -61,6 +61,10 @@ moe_gate_route_limited = ops.moe_gate_route_limited
 # the routing over many workgroups, for prefill and training token counts: the same arrays bit for bit, three launches
 moe_route_wide = ops.moe_route_wide
 moe_gate_route_wide = ops.moe_gate_route_wide
+# the router's auxiliary losses: (balance, z, load, importance) from the logits and the gate's picks, two launches, and their
+# backward with respect to the logits, one launch
+moe_aux_loss = ops.moe_aux_loss
+moe_aux_loss_grad = ops.moe_aux_loss_grad
 # the dense dequantized weight [N, K] in scales.dtype (the nn.Linear layout), bit-identical to utils.reconstruct
 dequantize = cast(Callable[..., torch.Tensor], torch.ops.flute_amd.dequantize.default)
 

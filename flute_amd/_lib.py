@@ -91,6 +91,9 @@ SYMBOLS = {
     "flute_moe_route_wide": (c_int, [c_int] * 5 + [c_void_p] * 8 + [c_size_t, c_int, c_void_p]),
     "flute_moe_gate_route_wide": (c_int, [c_int] * 9 + [c_float] + [c_void_p] * 10 + [c_size_t, c_int, c_void_p]),
     "flute_moe_route_form": (c_int, [c_int] * 5),
+    "flute_moe_aux_loss_workspace": (c_size_t, [c_int] * 3),
+    "flute_moe_aux_loss": (c_int, [c_int] * 6 + [c_void_p] * 6 + [c_void_p]),
+    "flute_moe_aux_loss_grad": (c_int, [c_int] * 4 + [c_void_p] * 4 + [c_void_p]),
     "flute_debug_stream_read": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "flute_debug_timestamp": (c_int, [c_void_p, c_void_p]),
 }

@@ -2228,6 +2228,49 @@ int flute_moe_gate_grad(int logit_dtype, int T, int E, int k, int scoring, int r
                                   d_logits, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the router's auxiliary losses (moe_aux.hip) ----------------------------------------------------------------------------------
+// C for a checked T, 0 for a chunk_tokens the entries refuse; chunk_tokens 0 is resolved in place, from T alone
+static int aux_chunks(int T, int* chunk_tokens) {
+    if (*chunk_tokens < 0) return 0;
+    if (*chunk_tokens == 0) {
+        const int cap = (T + FLUTE_MOE_AUX_AUTO_CHUNKS - 1) / FLUTE_MOE_AUX_AUTO_CHUNKS;
+        *chunk_tokens = cap > FLUTE_MOE_AUX_CHUNK_TOKENS ? cap : FLUTE_MOE_AUX_CHUNK_TOKENS;
+    }
+    const long long C = ((long long)T + *chunk_tokens - 1) / *chunk_tokens;
+    return C <= FLUTE_MOE_ROUTE_MAX_CHUNKS ? (int)C : 0;
+}
+static bool aux_shape_ok(int T, int E) {
+    return T >= 1 && E >= 1 && E <= FLUTE_MOE_ROUTE_MAX_EXPERTS && T < FLUTE_MOE_ROUTE_MAX_PAIRS;
+}
+
+size_t flute_moe_aux_loss_workspace(int T, int E, int chunk_tokens) {
+    if (!aux_shape_ok(T, E)) return 0;
+    const int C = aux_chunks(T, &chunk_tokens);
+    return (size_t)C * (size_t)(2 * E + 1) * sizeof(int32_t);
+}
+
+int flute_moe_aux_loss(int logit_dtype, int T, int E, int k, int scoring, int chunk_tokens, const void* logits, const int32_t* ids,
+                       void* workspace, int32_t* load, float* importance, float* losses, void* stream) {
+    const int rc = check_moe_gate(logit_dtype, T, E, k, nullptr, scoring);
+    if (rc) return rc;
+    if (T < 1) return FLUTE_ERR_SHAPE;
+    const int C = aux_chunks(T, &chunk_tokens);
+    if (C == 0) return FLUTE_ERR_SHAPE;
+    if (!logits || !ids || !workspace || !load || !importance || !losses) return FLUTE_ERR_NULL;
+    return moe_aux_loss_dispatch(logit_dtype, T, E, k, scoring, chunk_tokens, logits, ids, workspace, load, importance, losses,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+int flute_moe_aux_loss_grad(int logit_dtype, int T, int E, int scoring, const void* logits, const int32_t* load, const float* grads,
+                            void* d_logits, void* stream) {
+    if (logit_dtype != FLUTE_F16 && logit_dtype != FLUTE_BF16 && logit_dtype != FLUTE_F32) return FLUTE_ERR_DTYPE;
+    if (scoring != FLUTE_GATE_SOFTMAX && scoring != FLUTE_GATE_SIGMOID) return FLUTE_ERR_DTYPE;
+    if (!aux_shape_ok(T, E)) return FLUTE_ERR_SHAPE;
+    if (!logits || !load || !grads || !d_logits) return FLUTE_ERR_NULL;
+    return moe_aux_loss_grad_dispatch(logit_dtype, T, E, scoring, logits, load, grads, d_logits,
+                                      reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_debug_stream_read(const void* src, void* sink, size_t bytes, int bytes_per_wave,
                             int grid, int block, void* stream) {
     if (!src || !sink || bytes_per_wave < 8192 || bytes_per_wave % 8192) return FLUTE_ERR_SHAPE;

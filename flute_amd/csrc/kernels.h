@@ -192,6 +192,14 @@ int moe_weight_grad_dispatch(int dtype, int R, int K, int E, const void* dHp, co
 int moe_gate_grad_dispatch(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
                            const int32_t* ids, const float* d_weights, const float* d_row_weight, const int32_t* pos,
                            void* d_logits, hipStream_t stream);
+// the router's auxiliary losses (moe_aux.hip): partials per chunk of chunk_tokens tokens into the workspace - psum [C][E] fp32, pcnt
+// [C][E] int32, pz [C] fp32, every word written - then one workgroup that sums the chunks in ascending order in fp64 into load [E],
+// importance [E] and losses [2] = (balance, z); and their backward, d_logits [T, E] from load and grads [2] on the device, one wave
+// per token.  The caller has checked shapes and sizes.
+int moe_aux_loss_dispatch(int logit_dtype, int T, int E, int k, int scoring, int chunk_tokens, const void* logits,
+                          const int32_t* ids, void* workspace, int32_t* load, float* importance, float* losses, hipStream_t stream);
+int moe_aux_loss_grad_dispatch(int logit_dtype, int T, int E, int scoring, const void* logits, const int32_t* load,
+                               const float* grads, void* d_logits, hipStream_t stream);
 int stream_read_dispatch(const void* src, void* sink, size_t bytes, int bytes_per_wave, int grid,
                          int block, hipStream_t stream);
 int timestamp_dispatch(void* dst, hipStream_t stream);

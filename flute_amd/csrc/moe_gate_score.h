@@ -1,6 +1,7 @@
-// The score stage of the gating, shared by its forward (moe_gate.hip: gate_token) and its backward (router_grad.hip:
-// moe_gate_grad_kernel): the logit types, the exchange steps of a wave reduction, and gate_scores, the device function that turns
-// one token's logits into the scores of its experts.  One wave = one token; lane l holds experts l, l + 64, ... in registers.
+// The score stage of the gating, shared by its forward (moe_gate.hip: gate_token), its backward (router_grad.hip:
+// moe_gate_grad_kernel) and the router's auxiliary losses (moe_aux.hip): the logit types, the exchange steps of a wave reduction,
+// gate_scores, the device function that turns one token's logits into the scores of its experts, and gate_score_sums, which returns
+// the max and the sums gate_scores keeps to itself.  One wave = one token; lane l holds experts l, l + 64, ... in registers.
 // A wave reduction is six exchange steps without LDS: DPP quad_perm (lanes ^ 1, ^ 2), row_half_mirror, row_mirror inside a row
 // of 16, then v_permlane16_swap and v_permlane32_swap across rows.  Every step combines the same two values in both partners, so
 // all 64 lanes hold the same bits afterwards and the order of the additions is fixed.
@@ -106,6 +107,42 @@ static __device__ __forceinline__ void gate_scores(const typename GateLogit<L>::
     } else {
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = 1.0f / (1.0f + expf(-x[i]));
+    }
+}
+
+// ---- what gate_scores does not return (moe_aux.hip: the auxiliary losses and their backward) ------------------------------------
+// Every lane calls it with the x and v of gate_scores(..., normalise = false, ...).  m: the max of the logits, by gate_scores' own
+// reduction (the same bits).  u: exp(x - m), 0 past E - FLUTE_GATE_SOFTMAX: v itself; FLUTE_GATE_SIGMOID: computed here.  S: the sum
+// of u over all E, lane l adding its experts in ascending order from +0, then the exchange tree - gate_scores' `total`, so u / S is
+// bit for bit its normalised score.  Z: the sum the score is normalised by - FLUTE_GATE_SOFTMAX: S; FLUTE_GATE_SIGMOID: the sum of
+// the sigmoids v over all E in the same order (past E the sigmoid of -infinity is +0).  gate_scores' own arithmetic is untouched.
+template <int NV>
+static __device__ __forceinline__ void gate_score_sums(const float (&x)[NV], const float (&v)[NV], int E, int scoring, int lane,
+                                                       float (&u)[NV], float& m, float& S, float& Z) {
+#pragma clang fp contract(off)
+    float mx = x[0];
+#pragma unroll
+    for (int i = 1; i < NV; ++i) mx = fmaxf(mx, x[i]);
+    m = wave_reduce<OpMaxF>(mx);
+    float part = 0.0f;
+    if (scoring == FLUTE_GATE_SOFTMAX) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            u[i] = v[i];
+            part += u[i];
+        }
+        S = wave_reduce<OpAddF>(part);
+        Z = S;
+    } else {
+        float zpart = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            u[i] = lane + 64 * i < E ? expf(x[i] - m) : 0.0f;
+            part += u[i];
+            zpart += v[i];
+        }
+        S = wave_reduce<OpAddF>(part);
+        Z = wave_reduce<OpAddF>(zpart);
     }
 }
 

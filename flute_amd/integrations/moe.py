@@ -61,6 +61,7 @@ tables that require grad.
 
 Not registered by `install_as_flute()`: the reference has no grouped form.
 """
+import collections
 import functools
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -378,20 +379,24 @@ class FluteExperts(torch.nn.Module):
         return flute_amd.moe_gate_route_limited(router_logits, top_k, groups[0], groups[1], self.num_experts, scoring,
                                                 renormalize, bias, scale, groups[2])
 
-    def _forward_gated(self, name, hidden, router_logits, top_k, scoring, renormalize, bias, scale, groups=None):
+    def _forward_gated(self, name, hidden, router_logits, top_k, scoring, renormalize, bias, scale, groups=None, want_ids=False):
         """The body of `forward_logits` (`groups` None) and `forward_logits_limited` (`groups` = (n_group, topk_group,
         group_score)): `moe_gate[_limited]` feeds the existing forward, with `native_routing` `_gate_route`'s routing arrays feed
-        the launches behind them."""
+        the launches behind them.  `want_ids` (`FluteSparseMoeBlock.aux_loss`): (the result, the gating's ids [T, k] int32)."""
         if router_logits.shape[1] != self.num_experts:
             raise ValueError("FluteExperts.%s: router_logits must be [T, num_experts]" % name)
         if self.native_routing:
-            _, _, offsets, rows, row_weight, pos, _ = self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale,
-                                                                       groups)
-            return self._forward_routed(hidden, offsets, rows, row_weight, pos)
-        if groups is None:
-            return self.forward(hidden, *flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale))
-        return self.forward(hidden, *flute_amd.moe_gate_limited(router_logits, top_k, groups[0], groups[1], scoring,
-                                                                renormalize, bias, scale, groups[2]))
+            ids, _, offsets, rows, row_weight, pos, _ = self._gate_route(router_logits, top_k, scoring, renormalize, bias, scale,
+                                                                         groups)
+            out = self._forward_routed(hidden, offsets, rows, row_weight, pos)
+        else:
+            if groups is None:
+                ids, weights = flute_amd.moe_gate(router_logits, top_k, scoring, renormalize, bias, scale)
+            else:
+                ids, weights = flute_amd.moe_gate_limited(router_logits, top_k, groups[0], groups[1], scoring, renormalize, bias,
+                                                          scale, groups[2])
+            out = self.forward(hidden, ids, weights)
+        return (out, ids) if want_ids else out
 
     def _forward_fused(self, hidden, topk_weights, perm, offsets, token):
         """`_fused_mlp` on torch's routing: no silu, no where, no gathered copy of `hidden`."""
@@ -467,6 +472,9 @@ class FluteExperts(torch.nn.Module):
         return flute_amd.moe_combine(y, pos, offsets, rows if self.native_router_grad else None)
 
 
+MoeAuxLosses = collections.namedtuple("MoeAuxLosses", ("balance", "z", "load", "importance"))     # FluteSparseMoeBlock.aux
+
+
 class FluteSparseMoeBlock(torch.nn.Module):
     """A whole sparse-MoE block: router, gating, experts.  forward(hidden [T, K]) is
     `experts.forward_logits(F.linear(hidden, router_weight), top_k, ...)`, bit for bit.  `router_weight` [E, K] is the
@@ -476,7 +484,18 @@ class FluteSparseMoeBlock(torch.nn.Module):
     `scoring`, `renormalize`, `bias` (the selection bias [E] fp32, kept as a buffer) and `scale` are
     `flute_amd.moe_gate`'s.  With `n_group` > 1 the selection is DeepSeek's group-limited one (`flute_amd.moe_gate_limited`:
     the `topk_group` best of `n_group` groups of experts by `group_score` "max" / "top2sum") and forward is
-    `experts.forward_logits_limited(...)`, the same number of launches; with n_group == 1 it is exactly the path above."""
+    `experts.forward_logits_limited(...)`, the same number of launches; with n_group == 1 it is exactly the path above.
+    `block.aux_loss = True` (a validated attribute, False by default; the constructor's parameters are as they were): forward
+    also calls `flute_amd.moe_aux_loss` on the logits it computed, with the ids its gating launch
+    picked and the block's own scoring, and leaves `block.aux = MoeAuxLosses(balance, z, load, importance)`: balance (the
+    load-balance loss; DeepSeek's is balance / top_k) and z (the router z-loss) are attached to the graph, so
+    `(loss + a * block.aux.balance + b * block.aux.z).backward()` reaches `router_weight` and `hidden` through torch's own
+    `F.linear`; load [E] int32 is what an aux-loss-free bias update reads (the rule itself is not part of this module).  The
+    block's output is bit for bit the one with `aux_loss` off.  Keep the router in fp32 or bf16 where the losses train: in fp16
+    their gradients, of order E / T^2, fall into the subnormal range.  Token masks and per-sequence losses are out of scope.
+    `block.aux` holds the autograd graph of the forward that wrote it, as a kept loss tensor does, until the next forward
+    replaces it: use it in that step's loss (or `del block.aux`) before a later step runs on another stream, a graph capture
+    for one.  With the default the forward is unchanged and the block has no `aux` attribute."""
 
     def __init__(self, router_weight: torch.Tensor, experts: FluteExperts, top_k: int, scoring: str = "softmax",
                  renormalize: bool = False, bias=None, scale: float = 1.0, n_group: int = 1, topk_group: int = 1,
@@ -508,8 +527,23 @@ class FluteSparseMoeBlock(torch.nn.Module):
         self.top_k, self.scoring, self.renormalize, self.scale = int(top_k), scoring, bool(renormalize), float(scale)
         self.n_group, self.topk_group, self.group_score = int(n_group), int(topk_group), group_score
 
+    _aux_loss = False
+
+    @property
+    def aux_loss(self) -> bool:
+        """Whether forward also computes the router's auxiliary losses into `self.aux` (the class docstring); False unless set."""
+        return self._aux_loss
+
+    @aux_loss.setter
+    def aux_loss(self, value: bool) -> None:
+        if not isinstance(value, bool):
+            raise TypeError("FluteSparseMoeBlock: aux_loss is a bool")
+        self._aux_loss = value
+
     def forward(self, hidden: torch.Tensor) -> torch.Tensor:
         logits = torch.nn.functional.linear(hidden, self.router_weight)
+        if self.aux_loss:
+            return self._forward_aux(hidden, logits)
         if self.n_group > 1:
             return self.experts.forward_logits_limited(hidden, logits, self.top_k, self.n_group, self.topk_group,
                                                        self.scoring, self.renormalize, self.bias, self.scale,
@@ -517,7 +551,16 @@ class FluteSparseMoeBlock(torch.nn.Module):
         return self.experts.forward_logits(hidden, logits, self.top_k, self.scoring, self.renormalize, self.bias,
                                            self.scale)
 
+    def _forward_aux(self, hidden, logits):
+        """The forward with `aux_loss`: the same launches, the gating's ids kept, and `moe_aux_loss` on them into `self.aux`."""
+        limited = self.n_group > 1
+        out, ids = self.experts._forward_gated(
+            "forward_logits_limited" if limited else "forward_logits", hidden, logits, self.top_k, self.scoring, self.renormalize,
+            self.bias, self.scale, (self.n_group, self.topk_group, self.group_score) if limited else None, want_ids=True)
+        self.aux = MoeAuxLosses(*flute_amd.moe_aux_loss(logits, ids, self.scoring))
+        return out
+
     def extra_repr(self) -> str:
         return (f"top_k={self.top_k}, scoring={self.scoring}, renormalize={self.renormalize}, scale={self.scale}, "
                 f"bias={self.bias is not None}, n_group={self.n_group}, topk_group={self.topk_group}, "
-                f"group_score={self.group_score}")
+                f"group_score={self.group_score}" + (", aux_loss=True" if self.aux_loss else ""))

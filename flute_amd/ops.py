@@ -1,7 +1,7 @@
 """torch operator surface: `flute::qgemm_raw_simple[_hadamard]` and `flute_amd::dequantize`,
 plus plain functions over the C ABI: `hadamard_transform`, `qgemm_scale_grad`, `qgemm_table_grad`, `qgemm_grouped`, `qgemm_grouped_glu`,
-`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gather`, `swiglu_grad`, `moe_weight_grad`, `moe_gate_grad`, `moe_gate`, `moe_gate_route`, `moe_gate_limited` and
-`moe_gate_route_limited`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
+`qgemm_grouped_weighted`, `qgemm_grouped_input_grad`, `qgemm_grouped_scale_grad`, `qgemm_grouped_table_grad`, `moe_route`, `moe_combine`, `moe_gather`, `swiglu_grad`, `moe_weight_grad`, `moe_gate_grad`, `moe_gate`, `moe_gate_route`, `moe_gate_limited`,
+`moe_gate_route_limited`, `moe_aux_loss` and `moe_aux_loss_grad`.  The grouped and mixture-of-experts functions are differentiable with respect to their activations,
 routing weights and router logits: when grad mode is on and such an input requires grad they run through a
 `torch.autograd.Function` whose forward is the same launch and whose backward is `qgemm_grouped_input_grad`, `moe_combine`
 and a few torch ops; otherwise they take exactly the path they always took.  Each of the three grouped ops has ONE such
@@ -1447,4 +1447,114 @@ def moe_gate_grad(logits: torch.Tensor, ids: torch.Tensor, grad_weights, scoring
     _abi_call("moe_gate_grad", _lib.get().flute_moe_gate_grad,
               (_ROUTE_WEIGHT_DTYPE_ID[logits.dtype], T, E, ids.shape[1], _GATE_SCORING_ID[scoring], int(bool(renormalize)),
                float(scale)), (logits, ids, grad_weights, grad_row_weight, pos), (out,))
+    return out
+
+
+def _validate_moe_aux_logits(logits, scoring):
+    """The values every auxiliary-loss op asks of `logits` [T, E] (ranks and types are checked): T >= 1, 1 <= E <= 1024, T < 2^27."""
+    if scoring not in _GATE_SCORING_ID:
+        raise ValueError
+    T, E = logits.shape
+    if T < 1 or not 1 <= E <= MOE_ROUTE_MAX_EXPERTS or T >= MOE_ROUTE_MAX_PAIRS:
+        raise ValueError
+
+
+def _validate_moe_aux_loss(logits, ids, scoring, chunk_tokens):
+    """Ranks, then types, then values; returns the ABI's chunk_tokens (0: automatic)."""
+    _check_ranks((logits, 2), (ids, 2))
+    _check_dtypes(logits.dtype, int32=(ids,), allowed=_ROUTE_WEIGHT_DTYPE_ID)
+    if chunk_tokens is not None and (isinstance(chunk_tokens, bool) or not isinstance(chunk_tokens, int)):
+        raise TypeError
+    _validate_moe_aux_logits(logits, scoring)
+    (T, E), k = logits.shape, ids.shape[1]
+    if ids.shape[0] != T or not 1 <= k <= min(E, MOE_GATE_MAX_TOPK) or T * k >= MOE_ROUTE_MAX_PAIRS:
+        raise ValueError
+    return _validate_chunk_tokens(chunk_tokens, T)
+
+
+def _validate_moe_aux_loss_grad(logits, load, grads, scoring):
+    _check_ranks((logits, 2), (load, 1), (grads, 1))
+    _check_dtypes(logits.dtype, fp32=(grads,), int32=(load,), allowed=_ROUTE_WEIGHT_DTYPE_ID)
+    _validate_moe_aux_logits(logits, scoring)
+    if load.shape[0] != logits.shape[1] or grads.shape[0] != 2:
+        raise ValueError
+
+
+def _moe_aux_loss_call(logits, ids, scoring, wide):
+    """One flute_moe_aux_loss call: (losses [2] fp32 = (balance, z), load [E] int32, importance [E] fp32); the workspace is the
+    queried size, from the caching allocator per call (capturable), and is not cleared: the kernels write every word they read."""
+    dev = _same_gpu("moe_aux_loss", (logits, ids))              # (refused before anything is allocated)
+    (T, E), k = logits.shape, ids.shape[1]
+    load = torch.empty(E, dtype=torch.int32, device=dev)
+    importance = torch.empty(E, dtype=torch.float32, device=dev)
+    losses = torch.empty(2, dtype=torch.float32, device=dev)
+    workspace = torch.empty(_lib.get().flute_moe_aux_loss_workspace(T, E, wide), dtype=torch.uint8, device=dev)
+    _abi_call("moe_aux_loss", _lib.get().flute_moe_aux_loss,
+              (_ROUTE_WEIGHT_DTYPE_ID[logits.dtype], T, E, k, _GATE_SCORING_ID[scoring], wide), (logits, ids),
+              (workspace, load, importance, losses), dev=dev)
+    return losses, load, importance
+
+
+class _MoeAuxLossFunction(torch.autograd.Function):
+    """`moe_aux_loss` under autograd: balance and z get a gradient to `logits` from one `moe_aux_loss_grad` launch; the two incoming
+    gradients are stacked on the device (a missing one is 0), so nothing synchronises.  load and importance carry none."""
+
+    @staticmethod
+    def forward(ctx, logits, ids, scoring, wide):
+        losses, load, importance = _moe_aux_loss_call(logits, ids, scoring, wide)
+        ctx.save_for_backward(logits, load)
+        ctx.scoring = scoring
+        ctx.mark_non_differentiable(load, importance)
+        return losses[0], losses[1], load, importance
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_balance, d_z, d_load, d_importance):
+        logits, load = ctx.saved_tensors
+        zero = torch.zeros((), dtype=torch.float32, device=logits.device)
+        grads = torch.stack([zero if g is None else g.to(torch.float32).reshape(()) for g in (d_balance, d_z)])
+        return moe_aux_loss_grad(logits, load, grads, ctx.scoring), None, None, None
+
+
+def moe_aux_loss(logits: torch.Tensor, ids: torch.Tensor, scoring: str = "softmax", chunk_tokens=None):
+    """The router's auxiliary losses and the per-expert load in two launches: from the router's `logits` [T, E] (fp16 / bf16 /
+    fp32) and the gate's picks `ids` [T, k] int32, held fixed, to (balance, z, load, importance).  With p[t, e] the softmax over
+    all E as the gate computes it (`scoring="softmax"`) or s / sum_j s_j of s = 1 / (1 + exp(-x)) (`"sigmoid"`), and lse_t the
+    log-sum-exp of token t's logits (for either scoring):
+    load [E] int32 = the slots that name each expert (an id outside [0, E) counts nowhere: `diff(moe_route(ids).offsets)`; what
+    DeepSeek-V3's aux-loss-free balancing updates `moe_gate`'s `bias` from); importance [E] fp32 = sum_t p[t, e];
+    balance = E sum_e (load_e / T) (importance_e / T), a 0-dim fp32 tensor - the load-balance loss of Switch / Mixtral, Hugging
+    Face's `load_balancing_loss_func` without an attention mask; DeepSeek's is this divided by k; z = mean_t lse_t^2, 0-dim
+    fp32 - ST-MoE's router z-loss.  1 <= k <= min(E, 64), E <= 1024, T k < 2^27, T >= 1.
+    balance and z are differentiable with respect to `logits` (load is a constant): the backward is one `moe_aux_loss_grad`
+    launch, once-differentiable.  load and importance carry no gradient.  Use fp32 or bf16 logits where the losses train: in
+    fp16 their gradients, of order E / T^2, fall into the subnormal range.
+    Partial sums per chunk of `chunk_tokens` tokens (None: automatic, from T alone; an int >= 1 with at most 8192 chunks is for
+    tests and sweeps), then one workgroup that adds the chunks in ascending order in fp64 (moe_aux.hip; include/flute_amd.h,
+    flute_moe_aux_loss states the order): no float atomics, equal arguments give equal bits, load does not depend on
+    `chunk_tokens`.  The workspace is allocated per call; no host synchronise (capturable); native HIP kernels on the current
+    stream.  Out of scope: token masks and padding weights, sequence-wise losses per batch row, and the bias update rule
+    itself (two torch ops on `load`)."""
+    wide = _validate_moe_aux_loss(logits, ids, scoring, chunk_tokens)
+    if _records_grad(logits):
+        return _MoeAuxLossFunction.apply(logits, ids, scoring, wide)
+    losses, load, importance = _moe_aux_loss_call(logits, ids, scoring, wide)
+    return losses[0], losses[1], load, importance
+
+
+def moe_aux_loss_grad(logits: torch.Tensor, load: torch.Tensor, grads: torch.Tensor, scoring: str = "softmax") -> torch.Tensor:
+    """The backward of `moe_aux_loss` in one launch: d_logits [T, E] in logits.dtype from `logits` [T, E] (fp16 / bf16 / fp32),
+    `load` [E] int32 (the forward's, a constant) and `grads` [2] fp32 on the GPU = the incoming gradients (g_b, g_z) of balance
+    and z.  With a_e = g_b E load_e / T^2 and sm the softmax of the token: softmax scoring p_te (a_e - sum_j a_j p_tj) +
+    g_z (2 / T) lse_t p_te; sigmoid scoring s_te (1 - s_te) (a_e - sum_j a_j p_tj) / sum_j s_tj + g_z (2 / T) lse_t sm_te -
+    in fp32 in the order include/flute_amd.h states at flute_moe_aux_loss_grad, one rounding to the logits' type; every
+    element is written and a zero is +0.  Not differentiable.  One wave per token, no atomics, no host synchronise
+    (capturable); a native HIP kernel on the current stream (moe_aux.hip); equal arguments give equal bits, and a token's
+    result depends on its own logits, load, grads, T and E only.  Folding this into `moe_gate_grad`'s launch is out of scope."""
+    _validate_moe_aux_loss_grad(logits, load, grads, scoring)
+    _refuse_grad("moe_aux_loss_grad", logits, grads)
+    T, E = logits.shape
+    out = torch.empty((T, E), dtype=logits.dtype, device=logits.device)
+    _abi_call("moe_aux_loss_grad", _lib.get().flute_moe_aux_loss_grad,
+              (_ROUTE_WEIGHT_DTYPE_ID[logits.dtype], T, E, _GATE_SCORING_ID[scoring]), (logits, load, grads), (out,))
     return out

@@ -39,6 +39,7 @@ extern "C" {
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
  *    the routing over many workgroups: flute_moe_route_wide, flute_moe_gate_route_wide, flute_moe_route_wide_workspace, flute_moe_route_form
+ *    the router's auxiliary losses: flute_moe_aux_loss, flute_moe_aux_loss_grad, flute_moe_aux_loss_workspace
  *    (additive: no existing entry point changed its signature or its refusals, so the number stays)
  * 8 (round 6, late): same structs; family 8 = persistent MFMA decode kernel (qgemm_persistm.h) in flute_plan.family / flute_overrides.family -
  *    slabs_per_wave = column groups per set (1 .. 3), visits = sets per workgroup (override: m_tiles), k_chunks = activation requests per macro-step
@@ -904,6 +905,63 @@ int flute_moe_weight_grad(int dtype, int R, int K, int E, const void* dHp, const
 int flute_moe_gate_grad(int logit_dtype, int T, int E, int k, int scoring, int renormalize, float scale, const void* logits,
                         const int32_t* ids, const float* d_weights, const float* d_row_weight, const int32_t* pos, void* d_logits,
                         void* stream);
+
+/* The router's auxiliary losses and the per-expert load, natively (csrc/moe_aux.hip): what a trained router is regularised with.
+ * Inputs: logits [T, E] fp16 / bf16 / fp32; ids [T, k] int32, the forward's picks, held fixed; scoring FLUTE_GATE_SOFTMAX or
+ * FLUTE_GATE_SIGMOID.  Limits, the gating's own: 1 <= k <= min(E, FLUTE_MOE_GATE_MAX_TOPK), E <= FLUTE_MOE_ROUTE_MAX_EXPERTS,
+ * T k < FLUTE_MOE_ROUTE_MAX_PAIRS, and T >= 1 (the losses divide by T).
+ * Per token t, in fp32 by csrc/moe_gate_score.h (gate_scores and gate_score_sums; one wave per token, fixed reduction order):
+ *   m_t = max_e x_te;  u_te = exp(x_te - m_t);  S_t = sum_e u_te;  sm_te = u_te / S_t (the softmax);  lse_t = m_t + log(S_t)
+ *   FLUTE_GATE_SOFTMAX:  p_te = sm_te, bit for bit gate_scores(..., normalise = true)
+ *   FLUTE_GATE_SIGMOID:  s_te = 1 / (1 + exp(-x_te));  p_te = s_te / sum_j s_tj
+ * lse_t is over the logits for either scoring.
+ * Outputs of flute_moe_aux_loss:
+ *   load [E] int32        the number of slots (t, j) with ids[t, j] == e; an id outside [0, E) counts nowhere: exactly the differences
+ *                         of flute_moe_route's offsets on the same ids.  DeepSeek-V3's aux-loss-free balancing updates the gating's
+ *                         `bias` from it (the rule itself is two tensor operations and is not part of this library)
+ *   importance [E] fp32   sum_t p_te
+ *   losses[0] = balance   E * sum_e (load_e / T) * (importance_e / T): the load-balance loss of Switch / Mixtral - Hugging Face's
+ *                         load_balancing_loss_func without an attention mask.  DeepSeek's is this divided by k
+ *   losses[1] = z         (1 / T) * sum_t lse_t^2: the router z-loss of ST-MoE
+ * Two launches.  (1) grid C = ceil(T / chunk_tokens): workgroup c of 4 waves owns the tokens [c chunk_tokens, (c + 1) chunk_tokens)
+ * cut at T; wave w takes its tokens w, w + 4, ... in ascending order and keeps the running sums of p in registers (lane l: experts
+ * l, l + 64, ...) and of lse^2; the four waves combine in wave order through LDS, ((w0 + w1) + w2) + w3; the chunk's slots are
+ * counted with integer atomics in LDS; the chunk writes its whole row of the workspace - E fp32 sums, E int32 counts (zeros
+ * included), one fp32 sum of lse^2 - with plain stores.  (2) one workgroup: per expert the chunks' sums are added in ascending chunk
+ * order in fp64 and rounded once (importance), the counts as integers (load); balance = E * (sum over e ascending of
+ * (double) load_e * importance_e's fp64 sum) / T^2 and z = (sum over c ascending of the chunks' lse^2) / T in fp64, each rounded
+ * once.  Every output word is written.  No float atomics, no workgroup waits on another, the host reads nothing (stream-ordered,
+ * hipGraph-capturable); equal arguments give equal bits; the workspace need not be cleared.  load does not depend on chunk_tokens.
+ * chunk_tokens: 0 = automatic, max(FLUTE_MOE_AUX_CHUNK_TOKENS, ceil(T / FLUTE_MOE_AUX_AUTO_CHUNKS)), from T alone; a positive value
+ * is honoured where C <= FLUTE_MOE_ROUTE_MAX_CHUNKS (for tests and sweeps).  workspace: flute_moe_aux_loss_workspace(T, E,
+ * chunk_tokens) = C (2 E + 1) 4 bytes - psum [C][E] fp32, pcnt [C][E] int32, pz [C] fp32; 0 for arguments the call refuses.
+ * Non-finite logits: a NaN in token t makes importance, balance and z NaN and leaves load alone; a logit of -infinity is a masked
+ * expert, p = +0.
+ * Refusals of flute_moe_aux_loss in this order, before anything is enqueued: FLUTE_ERR_DTYPE (logit_dtype, then scoring);
+ * FLUTE_ERR_SHAPE (T < 1, the gating's conditions on k and E, T k, chunk_tokens < 0, C > FLUTE_MOE_ROUTE_MAX_CHUNKS); then
+ * FLUTE_ERR_NULL (logits, ids, workspace, load, importance, losses).
+ *
+ * flute_moe_aux_loss_grad: the backward with respect to the logits - load is a constant - in ONE launch, one wave per token:
+ * d_logits [T, E] in the logits' type from logits, load [E] int32 and grads [2] fp32 ON THE DEVICE = (g_b, g_z), the incoming
+ * gradients of balance and z (no host synchronise).  In fp32, every operation rounded once, no fma; sums over e: lane l adds its
+ * experts in ascending order from +0, then the exchange tree:
+ *   a_e = (g_b * (E / (T * T))) * load_e;   D_t = sum_e a_e * p_te;   zc_t = (g_z * (2 / T)) * lse_t
+ *   FLUTE_GATE_SOFTMAX:  dx_te = p_te * (a_e - D_t) + zc_t * p_te
+ *   FLUTE_GATE_SIGMOID:  dx_te = (s_te * (1 - s_te)) * ((a_e - D_t) / sum_j s_tj) + zc_t * sm_te
+ *   d_logits[t, e] = round to the logits' type (dx_te + 0): every element is written, and a zero is +0
+ * A token's result depends on its own logits, load, grads, T and E only; a NaN row touches no other token.  In fp16 the loss
+ * gradients, of order E / T^2, fall into the subnormal range: use fp32 or bf16 logits where the losses train.
+ * Refusals in this order: FLUTE_ERR_DTYPE (logit_dtype, then scoring); FLUTE_ERR_SHAPE (T < 1, E < 1, E > FLUTE_MOE_ROUTE_MAX_EXPERTS,
+ * T >= FLUTE_MOE_ROUTE_MAX_PAIRS); then FLUTE_ERR_NULL (logits, load, grads, d_logits).
+ * Out of scope: token masks and padding weights, sequence-wise losses per batch row, folding this backward into
+ * flute_moe_gate_grad's launch, and the bias update rule. */
+#define FLUTE_MOE_AUX_CHUNK_TOKENS 32
+#define FLUTE_MOE_AUX_AUTO_CHUNKS 2048
+size_t flute_moe_aux_loss_workspace(int T, int E, int chunk_tokens);
+int flute_moe_aux_loss(int logit_dtype, int T, int E, int k, int scoring, int chunk_tokens, const void* logits, const int32_t* ids,
+                       void* workspace, int32_t* load, float* importance, float* losses /* [2]: balance, z */, void* stream);
+int flute_moe_aux_loss_grad(int logit_dtype, int T, int E, int scoring, const void* logits, const int32_t* load, const float* grads,
+                            void* d_logits, void* stream);
 
 /* Template table (replaces data/qgemm_kernel_raw_generated_configs.pth +
  * the generated switch, qgemm_kernel_raw_generated.cu:92-767). */

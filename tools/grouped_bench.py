@@ -94,6 +94,13 @@ and 4096 tokens - 16 .. 256 tokens for (c), the tokens of 512 .. 4096 pairs for 
 FluteSparseMoeBlock(fused=True, native_routing=True) at Mixtral's shapes, 512 and 4096 tokens, wide_routing off against "auto".
 Every row carries each contender's own spread over its ten replays.
 
+--mode aux_loss times the router's auxiliary losses (flute_amd.moe_aux_loss: load-balance loss, z-loss, load, importance; moe_aux.hip)
+at 512, 4096 and 16384 tokens of bf16 logits for an E = 8 top-2 softmax router and an E = 256 top-8 sigmoid router, by --mode router_grad's
+method in one process, contenders alternating: the forward alone and forward + backward to the logits, each against the torch fp32
+chain of tests/moe_aux_cases.py (Hugging Face's load_balancing_loss_func restated, plus the z-loss), which runs no kernel of
+moe_aux.hip; and one training step of FluteSparseMoeBlock at Mixtral's shapes, 512 and 4096 tokens, with aux_loss on against the
+same step with the torch chain bolted on (the router GEMM and a top-k again, as a user without the block's ids writes it).
+
 --mode prefill times the grouped FORWARD at prefill and training row counts, where the block form (qgemm_grouped_blocks.h) meets
 the row form (qgemm_grouped.h): W4G64 fp16 at Mixtral's two projections with 512, 4096 and 8192 routed rows (the counts of
 --mode projection at rows / 2 tokens, so its grouped figure from a build of the parent is the row form's here), the many-expert
@@ -1466,6 +1473,119 @@ def main_router_grad(args, device):
     print("wrote", args.out)
 
 
+# ---- --mode aux_loss --------------------------------------------------------------------------------------------------
+AUX_ROUTERS = {"E8 top2 softmax": (8, 2, "softmax"), "E256 top8 sigmoid": (256, 8, "sigmoid")}
+AUX_TOKENS = (512, 4096, 16384)
+AUX_DTYPE = torch.bfloat16                          # what a training router's GEMM hands on (fp16 loses the gradients to subnormals)
+AUX_ALPHA, AUX_BETA = 0.01, 0.001
+
+
+class AuxLoss:
+    """The auxiliary losses of `tokens` tokens: flute_amd.moe_aux_loss, or the torch fp32 chain of tests/moe_aux_cases.py; with
+    `backward` also the gradient of alpha balance + beta z to the logits."""
+
+    def __init__(self, tokens, shape, device, native, backward):
+        import flute_amd
+        from tests import moe_aux_cases
+        self.fa, self.chain, self.native, self.backward = flute_amd, moe_aux_cases.torch_chain, native, backward
+        E_, k, self.scoring = shape
+        gen = torch.Generator(device=device).manual_seed(tokens + E_)
+        self.logits = (torch.randn(tokens, E_, device=device, generator=gen) * 2).to(AUX_DTYPE)
+        self.ids, _ = flute_amd.moe_gate(self.logits, k, self.scoring, True)
+        if backward:
+            self.logits.requires_grad_()
+
+    def losses(self):
+        if self.native:
+            return self.fa.moe_aux_loss(self.logits, self.ids, self.scoring)[:2]
+        return self.chain(self.logits, self.ids, self.scoring)
+
+    def step(self, i):
+        if not self.backward:
+            with torch.no_grad():
+                return self.losses()
+        balance, z = self.losses()
+        return torch.autograd.grad(AUX_ALPHA * balance + AUX_BETA * z, self.logits)
+
+
+class AuxBlock:
+    """One training step of FluteSparseMoeBlock (softmax top-2, renormalised) on copy i of step_stacks with the router training and
+    alpha balance + beta z in the loss: the block's own aux_loss, or the torch chain bolted on."""
+
+    def __init__(self, stacks, tokens, device, native):
+        from flute_amd.integrations import moe
+        from tests import moe_aux_cases
+        self.chain, self.native = moe_aux_cases.torch_chain, native
+        gen = torch.Generator(device=device).manual_seed(tokens)
+        router = (torch.randn(E, 4096, device=device, generator=gen) * 0.02).to(DTYPE)
+        self.blocks = [moe.FluteSparseMoeBlock(router.clone(), moe.FluteExperts(g, u, d, fused=True, native_routing=True), TOPK,
+                                               renormalize=True) for g, u, d in stacks]
+        for b in self.blocks:
+            b.router_weight.requires_grad_()
+            b.aux_loss = native
+        self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE).requires_grad_()
+        self.dOut = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE)
+        self.one = torch.ones((), device=device)
+
+    def step(self, i):
+        block = self.blocks[i % len(self.blocks)]
+        out = block(self.hidden)
+        if self.native:
+            balance, z = block.aux.balance, block.aux.z
+            del block.aux       # it holds this step's autograd graph, as a kept loss does: let go of it before the next step, which
+            #                     may run on another stream (a capture) than the one the graph's leaf accumulators were made on
+        else:
+            logits = torch.nn.functional.linear(self.hidden, block.router_weight)
+            balance, z = self.chain(logits, logits.topk(TOPK, dim=1).indices, "softmax")
+        loss = AUX_ALPHA * balance + AUX_BETA * z
+        del balance, z
+        return torch.autograd.grad((out, loss), (self.hidden, block.router_weight), (self.dOut, self.one))
+
+
+def main_aux_loss(args, device):
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"what": "the router's auxiliary losses (load-balance loss, z-loss) on bf16 logits: flute_amd.moe_aux_loss against "
+                               "the torch fp32 chain of tests/moe_aux_cases.py (Hugging Face's load_balancing_loss_func restated, plus "
+                               "the z-loss), forward alone and forward + backward to the logits; one training step of "
+                               "FluteSparseMoeBlock(fused=True, native_routing=True) at Mixtral's shapes with aux_loss on against the "
+                               "same step with the torch chain bolted on.  hipGraph replays of `steps` calls between device-clock "
+                               "stamps, cold caches, median of `replays`, every contender timed twice, alternating, one process; "
+                               "spread: (max - min) / median over a contender's replays",
+                       "config": {"steps": args.steps, "warmup": args.warmup, "replays": args.replays, "logits": "bfloat16",
+                                  "alpha": AUX_ALPHA, "beta": AUX_BETA, "device": torch.cuda.get_device_name(device)}, "rows": rows},
+                      f, indent=1)
+
+    for name, shape in AUX_ROUTERS.items():
+        for tokens in AUX_TOKENS:
+            layers = {"%s %s" % (what, who): AuxLoss(tokens, shape, device, who == "native", what == "forward+backward")
+                      for what in ("forward", "forward+backward") for who in ("torch", "native")}
+            us, spread, replays = time_each(layers, args)
+            emit({"what": "aux losses", "router": name, "tokens": tokens, "us": us, "spread": spread,
+                  "forward_torch_over_native": round(us["forward torch"] / us["forward native"], 3),
+                  "forward_backward_torch_over_native": round(us["forward+backward torch"] / us["forward+backward native"], 3),
+                  "replays_us": replays})
+            del layers
+    copies = prefill_copies(E, 14336, 4096, BITS, stacks=3)
+    stacks = step_stacks(copies, device)
+    for tokens in (512, 4096):
+        layers = {"block step, torch chain": AuxBlock(stacks, tokens, device, False), "block step, aux_loss": AuxBlock(stacks, tokens, device, True)}
+        us, spread, replays = time_each(layers, args)
+        emit({"what": "FluteSparseMoeBlock training step with the auxiliary losses, Mixtral shapes", "tokens": tokens, "experts": E,
+              "top_k": TOPK, "us": us, "spread": spread, "weight_copies": copies,
+              "aux_loss_over_torch_chain": round(us["block step, aux_loss"] / us["block step, torch chain"], 4),
+              "torch_chain_minus_aux_loss_us": round(us["block step, torch chain"] - us["block step, aux_loss"], 3),
+              "replays_us": replays})
+        del layers
+        torch.cuda.empty_cache()
+    print("wrote", args.out)
+
+
 # ---- --mode route_wide ------------------------------------------------------------------------------------------------
 WIDE_ROUTERS = {"E8 top2 softmax": dict(E=8, k=2, scoring="softmax", bias=False, scale=1.0, groups=None),
                 "E64 top8 softmax": dict(E=64, k=8, scoring="softmax", bias=False, scale=1.0, groups=None),
@@ -1666,7 +1786,7 @@ def main():
     ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64])
     ap.add_argument("--bits", type=int, choices=[2, 3, 4], default=BITS, help="--mode projection: the bit width")
     ap.add_argument("--mode", choices=["projection", "mlp", "step", "gate", "gate_limited", "input_grad", "scale_grad", "table_grad",
-                                       "prefill", "router_grad", "route_wide"],
+                                       "prefill", "router_grad", "route_wide", "aux_loss"],
                     default="projection")
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
@@ -1686,7 +1806,8 @@ def main():
                                                    "table_grad": "grouped_moe_table_grad.json",
                                                    "prefill": "grouped_moe_prefill.json",
                                                    "router_grad": "grouped_moe_router_grad.json",
-                                                   "route_wide": "grouped_moe_route_wide.json"}[args.mode])
+                                                   "route_wide": "grouped_moe_route_wide.json",
+                                                   "aux_loss": "grouped_moe_aux_loss.json"}[args.mode])
     if args.mode in ("scale_grad", "table_grad"):
         if not args.child:
             return main_input_grad(args)             # the parent never opens the GPU
@@ -1712,6 +1833,8 @@ def main():
         return main_router_grad(args, device)
     if args.mode == "route_wide":
         return main_route_wide(args, device)
+    if args.mode == "aux_loss":
+        return main_aux_loss(args, device)
     if args.mode == "input_grad":
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
