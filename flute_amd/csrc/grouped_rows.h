@@ -28,7 +28,7 @@ inline long long grouped_blocks_row_blocks(int E, int T) {
     return ((long long)T + (long long)(kGroupedBlockRows - 1) * E) / kGroupedBlockRows;
 }
 
-// What the block form of the forward serves (api.hip's form rule and refusal read this, nothing else decides it): plain (0) and
+// What the block form of the forward serves (api_train.hip's form rule and refusal read this, nothing else decides it): plain (0) and
 // weighted (2), 4 / 2 bits, scale rows in whole 8-group blocks, whole 256-column blocks, and the 32-bit descriptor limits of
 // choose_block - activation byte offsets (a block reaches up to 127 rows past its expert's end), one expert's scale bytes - and
 // a 31-bit grid.
@@ -41,7 +41,7 @@ inline bool grouped_blocks_eligible(int mode, int num_bits, int lg, int E, int T
     return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
 }
 
-// What the block form of the fused SwiGLU launch serves (flute_qgemm_grouped_glu_blocks; api.hip's refusal and query read this,
+// What the block form of the fused SwiGLU launch serves (flute_qgemm_grouped_glu_blocks; api_train.hip's refusal and query read this,
 // nothing else decides it): the plain mode's conditions with F in N's place, but for the activations - the descriptor spans Xsrc
 // and no block reaches past its expert, so Tsrc * K * 2 is what must stay below 2^32 - 16 - and a sorted-row index plus a block
 // that stays an int (R is not bounded by Tsrc).
@@ -54,7 +54,7 @@ inline bool grouped_glu_blocks_eligible(int num_bits, int lg, int E, int R, int 
     return grouped_blocks_row_blocks(E, R) * (F / 256) <= 0x7fffffffLL;
 }
 
-// What the block form of the input gradient serves (qgemm_grouped_input_grad_blocks.h; api.hip's form rule and refusal read
+// What the block form of the input gradient serves (qgemm_grouped_input_grad_blocks.h; api_train.hip's form rule and refusal read
 // this, nothing else decides it): 4 / 2 bits, whole 256-k blocks, a row index plus a block that stays an int, and a 31-bit
 // grid.  (N, TileP and the group size are the slab form's, which the caller has checked with the layer; every base in the kernel
 // is 64-bit and it builds no descriptor, so no operand size is refused.)

@@ -1,5 +1,5 @@
 // Explicit instantiations of the lean decode kernel (qgemm_fast.h), num_bits = 4: dtype x TileP x (waves per workgroup,
-// waves per unit row, pieces per wave) x rows per pass - the shapes api.hip's plan_fast hands out.  Built with
+// waves per unit row, pieces per wave) x rows per pass - the shapes planner_decode.hip's plan_fast hands out.  Built with
 // -mllvm -amdgpu-kernarg-preload-count=14 (Makefile): the kernel's arguments arrive in SGPRs.
 #include "kernels.h"
 #include "qgemm_fast.h"

@@ -1,5 +1,5 @@
 // Kernel lookups defined by the instantiation units (inst_*.hip), one row list per family and unit: the entry point of a
-// shape, nullptr where that shape is not built.  api.hip asks them while it plans (which shapes exist) and once more when
+// shape, nullptr where that shape is not built.  planner_decode.hip asks them while it plans (which shapes exist) and once more when
 // the plan is made (resolve_kernel: a plan without a built kernel is refused there, FLUTE_ERR_TEMPLATE_ID); a launch looks nothing up.
 #pragma once
 #include "common.h"
@@ -86,7 +86,7 @@ int param_grad_dispatch(const ParamGrad& a, hipStream_t stream);
 size_t table_grad_scratch_bytes(int num_bits, int lg, int M, int N, int K, int want_dS, int num_sms);
 size_t table_grad_grouped_scratch_bytes(int num_bits, int E, int N, int K);
 // One grouped forward launch over E stacked layers and rows sorted by expert (what every grouped kernel reads out of offsets [E + 1],
-// int32, device only: grouped_rows.h).  api.hip fills it by name; a unit fills its kernel's argument struct from it.
+// int32, device only: grouped_rows.h).  api_train.hip fills it by name; a unit fills its kernel's argument struct from it.
 struct GroupedForward {
     int mode;                                         // FLUTE_GROUPED_PLAIN / _GLU / _WEIGHTED
     int form;                                         // resolved: FLUTE_GROUPED_FORM_ROWS (qgemm_grouped.h) / _BLOCKS (qgemm_grouped_blocks.h)

@@ -394,7 +394,7 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
             // 128-row blocks x 2 / 4 K slices combined INSIDE the launch (round 5, xwg.h, E form): the reference's Stream-K fix-up
             // for any bit width (tile_scheduler_utils.hpp:58-211, :460-481).  Until round 4: [M][N] fp32 slabs and a reduce launch
             // - kept (a.state == nullptr) for the 256-row blocks and for the skinny blocks, whose 4 - 8 slices of 16 .. 64 rows
-            // the reduce pass sums faster than their last arrivers would (measured, api.hip).
+            // the reduce pass sums faster than their last arrivers would (measured, planner.hip: plan_block).
             if (a.splitk > 1 && a.state != nullptr) {
                 const uint32_t col0 = (uint32_t)unit_col0<BITS, TILEP>(unit0 + 4 * q4);
                 auto store_d = [&](int i, int t, const f32x4_t o4) {

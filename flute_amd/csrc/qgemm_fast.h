@@ -35,7 +35,7 @@
 // (flute/csrc/qgemm_kernel.hpp:546-557, :617-712), Stream-K fix-up replaced by the in-workgroup K split
 // (tile_scheduler_utils.hpp:58-211).
 //
-// Host contract (api.hip: plan_fast): num_bits = 4, 1 <= M <= MB in {1, 2, 4}, K == 512 * D * KW (D = 1 .. 8: K = 3584 is D = 7), units = N / 4 a
+// Host contract (planner_decode.hip: plan_fast): num_bits = 4, 1 <= M <= MB in {1, 2, 4}, K == 512 * D * KW (D = 1 .. 8: K = 3584 is D = 7), units = N / 4 a
 // multiple of W / KW, group size in {64, 128, 256}, MB * K * 2 <= 32768, N * (K / g) * 2 < 4 GiB.
 // LDS: [table image 64 KB][activations MB x K][W scale images of 4 columns x D * (512 / g) groups][arrival counters +
 // K-split partials].

@@ -41,7 +41,7 @@
 // staged activation set - a step's fragment read feeds NG MFMAs, the 128 KB of activations cross the CU's texture addresser once
 // for NG x the work.  11008-, 8192- and 6144-wide layers become ONE round of workgroups (230 / 256 / 192) where the NG = 1 form
 // needed 2.7 / 2 / 1.5 and lost to the skinny kernel (8192 x 4096: 10.2 against 8.9 us).
-// Host contract (api.hip: plan_fastm): num_bits = 4, M <= 16, K == 128 * NM * W, units = N / 4 a multiple of 4 (the last workgroup
+// Host contract (planner_decode.hip: plan_fastm): num_bits = 4, M <= 16, K == 128 * NM * W, units = N / 4 a multiple of 4 (the last workgroup
 // may hold fewer than NG groups: its missing unit rows read as zero and store nothing), group size 2^LG in {64, 128, 256},
 // LDS = 32 KB + 32 K bytes <= 160 KB (K <= 4096).
 #pragma once

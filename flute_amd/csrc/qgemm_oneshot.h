@@ -642,7 +642,7 @@ __global__ __launch_bounds__(oneshot_max_threads(BITS, MB)) void qgemv_oneshot_k
 
     if constexpr (PIPE) {
         // Software-pipelined loop over groups of 8 lookups (pipelined_pieces).  The host launches this variant only when
-        // EVERY wave of the grid holds exactly D pieces (api.hip: plan_oneshot; a run-time fallback to the plain loop
+        // EVERY wave of the grid holds exactly D pieces (planner_decode.hip: plan_oneshot; a run-time fallback to the plain loop
         // would put two sets of counted waits on the same in-flight registers behind a branch, the arrangement hipcc
         // mis-schedules - measured: wrong results).
         pipelined_pieces<T, BITS, MB, D, 0, (BITS != 2) ? 1 : 0>(q, x_lane, x_pshift, x_row, s_lane, (uint32_t)(gpp * J) * 2u, lane_off, acc);

@@ -8,7 +8,7 @@
 // Same arithmetic, table / lookup scheme and wire format as qgemm_oneshot.h; decode loop = pipelined_pieces().
 // Replaces, like the ring kernel (qgemm_stream.h), the reference's Stream-K main loop for M <= 2
 // (flute/csrc/qgemm_kernel.hpp:617-712, tile_scheduler_utils.hpp:460-481).
-// Host contract (api.hip: plan_persist): M <= MB in {1, 2} rows whose staged activations fit LDS beside
+// Host contract (planner_decode.hip: plan_persist): M <= MB in {1, 2} rows whose staged activations fit LDS beside
 // the table image, K a whole number of chunks of D pieces (K % (512 D) == 0), G even,
 // group size >= 64, at most 8 waves (two register sets of D pieces: the 256-register budget of two waves per SIMD).
 #pragma once

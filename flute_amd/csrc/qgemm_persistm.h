@@ -37,7 +37,7 @@
 // (tile_scheduler_utils.hpp:460-481) is the flat (set, macro-step) stream here, its fix-up the in-workgroup reduction.
 // Round 6, last: a 2-bit member (BITS = 2: a group = two unit rows of eight columns; the lookup address is v_bfe + v_lshl_or on a 16-entry image) and the
 // activations RESIDENT in LDS where 4 XR rows x K fit in 64 KB (XRES: staged once per workgroup, no activation request in the loop).
-// Host contract (api.hip: plan_persistm): num_bits = 4 or 2, M <= 16, K % 128 == 0, K >= 1024, group size 64 or 128 (128: K % 256 == 0 - a
+// Host contract (planner_decode.hip: plan_persistm): num_bits = 4 or 2, M <= 16, K % 128 == 0, K >= 1024, group size 64 or 128 (128: K % 256 == 0 - a
 // column's scale row is a whole number of dwords), N % 16 == 0, N * K / 2, N * (K / g) * 2 and M * K * 2 below 2^32 bytes, grid <= sets,
 // XR = 1 / 2 / 4 for M <= 4 / 8 / 16, LDS = persistm_lds_bytes(NG, XR): 32 KB table + rings + 8 NG KB of partial tiles.
 #pragma once

@@ -29,7 +29,7 @@
 // k-steps grow from 520 to 850 cycles).  With the requests interleaved as above: 12.6 us.
 // Arithmetic: fp16 w^ = round_T(lut * s) (packbits_utils.hpp:139), fp32 accumulation in the matrix core; bf16 (no packed
 // multiply on gfx950) applies the group scale to the fp32 MFMA result of each group run, as qgemm_tile.h.
-// Host contract (api.hip: plan_skinny): 4 bits, M <= 16, K = 32 D KW with D in {4, 8, 16} and KW in {4, 8}, G even, group
+// Host contract (planner_decode.hip: plan_skinny): 4 bits, M <= 16, K = 32 D KW with D in {4, 8, 16} and KW in {4, 8}, G even, group
 // size >= 32 and D * 32 / g <= 8, N % 64 == 0 (always: TileP >= 32).
 #pragma once
 #include "qgemm_oneshot.h"

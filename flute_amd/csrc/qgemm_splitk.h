@@ -38,7 +38,7 @@
 // RT = 8, KP = 2; slice s owns row tiles s, s + nsh, ... of every wave), the L form otherwise; sums are taken in a fixed order (K
 // parts ascending; owner first, then the other slices ascending; L: all slices ascending), so the result does not depend on arrival order.
 // Arithmetic contract as qgemm_block2.h: w^ = round_T(lut * s) (packbits_utils.hpp:139), fp32 accumulation, one rounding.
-// Host contract (api.hip, plan_splitk): 2 or 4 bits, G % 8 == 0, K % k_per_split == 0, k_per_split % (KP * max(64, g)) == 0,
+// Host contract (planner_decode.hip, plan_splitk): 2 or 4 bits, G % 8 == 0, K % k_per_split == 0, k_per_split % (KP * max(64, g)) == 0,
 // at most 64 scale groups (+ alignment slack: eight 8-group blocks) per workgroup K range, splitk * tiles * RT / KP * 16 KB of slabs < 2^31.
 #pragma once
 #include <utility>

@@ -327,7 +327,7 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
  * The block form serves: num_bits 4 / 2, (K / group_size) % 8 == 0, N a multiple of 256, (T + 256) * K * 2 and one expert's
  * scale bytes N * (K / group_size) * 2 below 2^32 - 16, the plain and weighted launches.  The automatic rule takes it where
  * it is eligible and the mean rows per expert, T / E, is at least FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS - or
- * FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms - (measured: csrc/api.hip);
+ * FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms - (measured: csrc/api_train.hip);
  * below that the launch is the row form's, grid included.  flute_qgemm_grouped_glu has no block form: it runs the row form at every count
  * (the block form of that launch is an entry of its own, flute_qgemm_grouped_glu_blocks).
  * Refusals, before anything is enqueued: FLUTE_ERR_DTYPE, then the layer checks of flute_dequantize (num_bits 2 / 3 / 4,
@@ -432,7 +432,7 @@ int flute_qgemm_grouped_glu_blocks(int dtype, int num_bits, int group_size, int 
  * FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS - or FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (F / 256) is below
  * num_sms (< 1: 256) -, else FLUTE_GROUPED_FORM_ROWS (flute_qgemm_grouped_glu; E == 0 and R == 0 included), or the negative
  * error either launch would refuse the layer with.  Host only: no pointers, nothing is enqueued; P is taken as
- * num_bits * F / 16.  The two constants are measured on the GLU launches (csrc/api.hip): each is the smallest
+ * num_bits * F / 16.  The two constants are measured on the GLU launches (csrc/api_train.hip): each is the smallest
  * swept mean from which the block launch is not slower on any swept stack of its kind. */
 #define FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS 16            /* E * (F / 256) >= num_sms: the experts' column blocks fill the chip */
 #define FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL 48    /* fewer workgroups than compute units */

@@ -221,7 +221,7 @@ def test_every_key_of_the_shipped_table_resolves_to_a_legal_plan():
     """flute_amd/data/gfx950_tuned.json is what the product serves (FluteLinear, tune_and_pack, bench.py): every key's template id
     exists for its bit width, honours the key's TileP constraint, passes is_template_supported and gives flute_qgemm_plan a legal
     plan for the key's shape at the bucket's batch size (the reference's tuner checks every id it stores: tune.py:294-392).  A plan
-    is resolved to its kernel when it is made (api.hip, resolve_kernel), so a key that plans has a built kernel as well: a table id
+    is resolved to its kernel when it is made (planner.hip, resolve_kernel), so a key that plans has a built kernel as well: a table id
     or a planner rule that picks a shape nobody instantiated fails here, without a GPU."""
     from flute_amd import _lib
     table = tune.load_tuned_table()

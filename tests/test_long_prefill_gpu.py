@@ -4,7 +4,7 @@ pins the same guards on the host).
 A long-context prefill is one call with M = batch x prompt length: on a K = 28672 layer 37 450 rows of activations pass
 2 GiB and 74 899 rows pass 4 GiB.  The block kernels read the activations through a descriptor with 32-bit byte offsets
 (qgemm_block2.h:97,111, qgemm_block3.h:96,109) and the planner admits them only while (M + 256) K 2 < 0xfffffff0
-(api.hip:831, x32_ok); past it the per-wave kernel takes over.  The outputs, the Hadamard scratch and the binding's
+(planner.hip choose_block: x32_ok); past it the per-wave kernel takes over.  The outputs, the Hadamard scratch and the binding's
 flattening of batch dimensions use 64-bit offsets.  A wrap anywhere would corrupt only the rows beyond 2 or 4 GiB.
 
 The data are exact by construction (tests/exact_cases.py): integer activations in [-4, 4], integer tables, +-2^e scales.

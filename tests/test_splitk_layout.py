@@ -169,7 +169,7 @@ def test_xcd_group_order_is_a_bijection():
     (block b -> XCD b % 8) so that the E row tiles that share a column tile's weights run on ONE XCD (round 4: pairs; round 6: up to
     eight - the four 64-row tiles of M = 256); every tile is produced exactly once for any tile grid, the incomplete last group of
     eight keeps the natural order."""
-    def group_of(tiles_m, ovr=0):                                   # api.hip, plan_splitk: the largest of 8, 4, 2 that divides into a power of two
+    def group_of(tiles_m, ovr=0):                                   # planner_decode.hip, plan_splitk: the largest of 8, 4, 2 that divides into a power of two
         E = 8
         while E > 1 and (tiles_m % E or ((tiles_m // E) & (tiles_m // E - 1))):
             E >>= 1
