@@ -32,6 +32,8 @@ qgemm_grouped = ops.qgemm_grouped
 qgemm_grouped_glu = ops.qgemm_grouped_glu
 qgemm_grouped_glu_blocks = ops.qgemm_grouped_glu_blocks     # the same launch on 128-row blocks, for prefill / training row counts
 qgemm_grouped_weighted = ops.qgemm_grouped_weighted
+qgemm_grouped_w3_blocks = ops.qgemm_grouped_w3_blocks       # stacks of 3-bit experts on 128-row blocks (plain and weighted)
+qgemm_grouped_weighted_w3_blocks = ops.qgemm_grouped_weighted_w3_blocks
 # their input gradient, one launch over the packed stacks (contracts over N); the grouped and mixture-of-experts functions
 # here backpropagate through it to activations, routing weights and router logits
 qgemm_grouped_input_grad = ops.qgemm_grouped_input_grad

@@ -1,5 +1,5 @@
 // Host side of the C ABI, the training and grouped entry points: the dense and grouped parameter gradients with their scratch
-// queries, the grouped forward launches (rows, blocks, GLU blocks) with their form queries, and the grouped input gradient.  Of the
+// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient.  Of the
 // planner they need the layer check alone (host.h).  No device code.
 #include <algorithm>
 
@@ -140,6 +140,35 @@ static GroupedForward glu_operands(int dtype, int num_bits, int E, int R, int Ts
 // 252 / 125, 329 / 128 - the routed draws say the same (at 32 on the last stack 121 / 121, a tie).
 static bool grouped_glu_blocks_serves(int num_bits, int lg, int E, int R, int Tsrc, int F, int K) {
     return grouped_glu_blocks_eligible(num_bits, lg, std::max(E, 1), std::max(R, 1), std::max(Tsrc, 1), F, K);
+}
+
+// The 3-bit block form behind its own entries (include/flute_amd.h; qgemm_block3.h GM = 1 / 2), flute_qgemm_grouped_w3_blocks (row_weight
+// null, mode plain) and _weighted_w3_blocks behind their signatures: check_grouped, then what the form serves - 3 bits and
+// grouped_w3_blocks_eligible, nothing else -, the empty launch, the null pointers, the unit.  The query's thresholds are the plain
+// form's rule (min_mean_rows: the split by E * (N / 256) against num_sms) on constants of their own,
+// FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS / _PARTIAL = 24 / 24: each the smallest swept mean from which the block launch is not slower on
+// any swept stack of its kind (the policy of 3.3m / 3.3p).  The sweep (profiles/grouped_moe_prefill_w3.json, "w3 threshold sweep":
+// W3G64 fp16, us of row form / block launch at even counts, rows / E = 8, 16, 24, 32, 48, 64, 96, 128; the 3-bit row form passes 16
+// rows at a time, so its time steps up at 17 rows per expert on every stack): Mixtral gate / up (448 workgroups per row block)
+// 125 / 142, 126 / 143, 227 / 145, 230 / 146, 329 / 150, 431 / 155, 636 / 164, 838 / 173; E 64 2048 x 2048 (512) 73 / 72, 74 / 73,
+// 128 / 74, 128 / 75, 184 / 79, 235 / 82, 344 / 89, 453 / 96; Mixtral down (E 8, N 4096, K 14336: 128 workgroups, does not fill the
+// chip) 172 / 244, 173 / 244, 327 / 246, 328 / 247, 473 / 249, 618 / 252, 910 / 259, 1201 / 268.  On the routed draws the block launch
+// wins from 16 on (some expert then has more than 16 rows); at 8 it loses on both E = 8 stacks.
+static int grouped_w3_blocks(int mode, int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                             const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                             const float* row_weight, void* Y, int num_sms, void* stream) {
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, T, N, K, P, &l);
+    if (rc) return rc;
+    if (num_bits != 3 || !grouped_w3_blocks_eligible(mode, l.lg, E, T, N, K)) return FLUTE_ERR_SHAPE;
+    if (E == 0 || T == 0) return FLUTE_OK;
+    if (!X || !offsets || !Q || !S || !QM2 || !Y || (mode == FLUTE_GROUPED_WEIGHTED && !row_weight)) return FLUTE_ERR_NULL;
+    GroupedForward g{};
+    g.mode = mode; g.dtype = dtype; g.num_bits = num_bits; g.form = FLUTE_GROUPED_FORM_BLOCKS; g.tile_p = l.t.tile_p; g.lg = l.lg;
+    g.E = E; g.R = T; g.Tsrc = T; g.N = N; g.K = K; g.P = P;
+    g.X = X; g.offsets = offsets; g.row_weight = row_weight; g.Y = Y; g.num_sms = num_sms;
+    g.Q[0] = g.Q[1] = Q; g.S[0] = g.S[1] = S; g.QM2[0] = g.QM2[1] = QM2;
+    return qgemm_grouped_blocks_unit_b3(g, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The two forms of the grouped input gradient (include/flute_amd.h): slabs = qgemm_grouped_input_grad.h, blocks =
@@ -304,6 +333,32 @@ int flute_qgemm_grouped_weighted_ex(int dtype, int num_bits, int group_size, int
     g.X = X; g.offsets = offsets; g.row_weight = row_weight; g.Y = Y; g.num_sms = num_sms;
     g.Q[0] = g.Q[1] = Q; g.S[0] = g.S[1] = S; g.QM2[0] = g.QM2[1] = QM2;
     return grouped_forward(g, group_size, template_id, form, stream);
+}
+
+int flute_qgemm_grouped_w3_blocks(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                                  const void* X, const void* offsets, const void* Q, const void* S, const void* QM2, void* Y,
+                                  int num_sms, void* stream) {
+    return grouped_w3_blocks(FLUTE_GROUPED_PLAIN, dtype, num_bits, group_size, E, T, N, K, P, template_id, X, offsets, Q, S, QM2,
+                             nullptr, Y, num_sms, stream);
+}
+
+int flute_qgemm_grouped_weighted_w3_blocks(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                           int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                           const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream) {
+    return grouped_w3_blocks(FLUTE_GROUPED_WEIGHTED, dtype, num_bits, group_size, E, T, N, K, P, template_id, X, offsets, Q, S, QM2,
+                             row_weight, Y, num_sms, stream);
+}
+
+int flute_qgemm_grouped_w3_blocks_form(int mode, int dtype, int group_size, int E, int rows, int N, int K, int template_id,
+                                       int num_sms) {
+    if (mode != FLUTE_GROUPED_PLAIN && mode != FLUTE_GROUPED_WEIGHTED) return FLUTE_ERR_SHAPE;
+    Layer l;
+    const int rc = check_grouped(dtype, 3, group_size, template_id, E, rows, N, K, 3 * (N / 16), &l);
+    if (rc) return rc;
+    if (E < 1 || rows < 1 || !grouped_w3_blocks_eligible(mode, l.lg, E, rows, N, K)) return FLUTE_GROUPED_FORM_ROWS;
+    const int thr = min_mean_rows(N / 256, E, num_sms, FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS,
+                                  FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL);
+    return (long long)rows >= (long long)thr * E ? FLUTE_GROUPED_FORM_BLOCKS : FLUTE_GROUPED_FORM_ROWS;
 }
 
 int flute_qgemm_grouped_input_grad_row_block(void) { return FLUTE_GROUPED_INPUT_GRAD_ROW_BLOCK; }

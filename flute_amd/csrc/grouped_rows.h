@@ -12,9 +12,9 @@
 //     row then holds either expert's result - or own more 128-row blocks than the grid holds - the surplus is dropped and its
 //     rows are left unwritten.
 //
-// The block forms (qgemm_block2.h's grouped front end, qgemm_grouped_input_grad_blocks.h) count the 128-row blocks of all
+// The block forms (qgemm_block2.h's and qgemm_block3.h's grouped front end, qgemm_grouped_input_grad_blocks.h) count the 128-row blocks of all
 // experts in expert order, expert e owning ceil(max(re - rb, 0) / 128) of them; their grid holds grouped_blocks_row_blocks(E, R),
-// the most a monotone table can own, and what they serve is decided by the two *_eligible rules below and nothing else.
+// the most a monotone table can own, and what they serve is decided by the *_eligible rules below and nothing else.
 #pragma once
 #include "common.h"
 
@@ -38,6 +38,19 @@ inline bool grouped_blocks_eligible(int mode, int num_bits, int lg, int E, int T
     if (E < 1 || T < 1 || N < 256 || N % 256 || K < 64 || (K >> lg) % 8) return false;
     if ((size_t)(T + 256) * K * 2 >= (size_t)0xfffffff0u) return false;
     if ((size_t)N * (K >> lg) * 2 >= (size_t)0xfffffff0u) return false;
+    return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
+}
+
+// What the 3-bit block form of the forward serves (flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks; qgemm_block3.h GM = 1 / 2;
+// api_train.hip's refusal and query read this, nothing else decides it): plain (0) and weighted (2), the shape conditions and the
+// activation, scale and grid limits of grouped_blocks_eligible, and one more descriptor - the kernel's weight descriptor spans one
+// expert's three planes, 3 (N / 16) unit rows of K 2 bytes, which must stay below 2^32 - 16.  E == 0 and T == 0 are inside the rule.
+inline bool grouped_w3_blocks_eligible(int mode, int lg, int E, int T, int N, int K) {
+    if (mode != 0 && mode != 2) return false;
+    if (E < 0 || T < 0 || N < 256 || N % 256 || K < 64 || (K >> lg) % 8) return false;
+    if (((size_t)T + 256) * K * 2 >= (size_t)0xfffffff0u) return false;
+    if ((size_t)N * (K >> lg) * 2 >= (size_t)0xfffffff0u) return false;
+    if ((size_t)(3 * (N / 16)) * K * 2 >= (size_t)0xfffffff0u) return false;
     return grouped_blocks_row_blocks(E, T) * (N / 256) <= 0x7fffffffLL;
 }
 

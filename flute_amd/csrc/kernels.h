@@ -107,6 +107,10 @@ int qgemm_grouped_weighted_unit(const GroupedForward& g, hipStream_t stream);
 // inst_grouped_blocks_b*.hip, one unit per bit width); the grid follows from (E, R, N) alone
 int qgemm_grouped_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);
 int qgemm_grouped_blocks_unit_b2(const GroupedForward& g, hipStream_t stream);
+// the 3-bit block form of the plain and weighted modes (qgemm_block3.h behind the same front end; what it serves:
+// grouped_w3_blocks_eligible; inst_grouped_blocks_b3.hip).  Its own entries (flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks):
+// qgemm_grouped_dispatch never takes it, and through the old entries 3 bits stay on the row form.
+int qgemm_grouped_blocks_unit_b3(const GroupedForward& g, hipStream_t stream);
 // the block form of the Glu mode (flute_qgemm_grouped_glu_blocks; what it serves: grouped_glu_blocks_eligible, grouped_rows.h;
 // inst_grouped_glu_blocks_b*.hip): the same grid from (E, R, F) alone.  Its own entry: qgemm_grouped_dispatch never takes it.
 int qgemm_grouped_glu_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);

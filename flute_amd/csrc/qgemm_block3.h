@@ -32,10 +32,26 @@
 // M = 1024 on 28672 x 8192 473 against 467 - the extra VALU (16 .. 44 per step) cost what the halved line count saved.
 namespace flute_amd {
 
-template <typename T, int RT>
-__global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args) {
+//
+// GM != 0: the grouped front end for stacks of 3-bit experts with many rows per expert (GM = 1: plain, 2: weighted; host side and
+// entry points: qgemm_grouped_blocks.h), the one qgemm_block2.h has for 4 and 2 bits, on this kernel's RT = 8 form.  The body below -
+// the three KIND instantiations, the plane ring, the barriers - is untouched: what changes is where a workgroup's operands come from
+// and which rows it stores.  A workgroup is (column block, row block b), b mapped to (expert e, block of e, rows [rb, re)) by
+// grouped_rows.h's block map; the map is wave-uniform, so a workgroup whose b is past the table's blocks leaves as a whole, ahead of
+// the branch on `wave`, before it requests a weight, scale or table word and before any barrier.  Q / S / QM2 move to expert e and the
+// plane-row arithmetic stays relative to that base: the weight descriptor spans ONE expert's 3 (N / 16) unit rows (a 32-bit limit of
+// its own: grouped_w3_blocks_eligible).  The activation descriptor starts at row rb and is (re - rb) rows long, so the block's rows at
+// or past re read as zero by the idiom of the dense rows past M, and no row outside [rb, re) forms an address; the epilogue stores the
+// rows < re, in the weighted mode round_T(row_weight[row] * acc32) - one rounding - and the weighted launch zeroes the rows no expert
+// serves.  No K split, no atomics, nothing shared between workgroups: equal arguments give equal bits.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / SGPRs / scratch bytes per lane / LDS): GM 1 f16 201 / 0 / 62 / 0 / 80 KB, bf16 205 / 0 / 62 / 0 / 80 KB; GM 2 f16 201 / 0 / 64 / 0 / 80 KB, bf16 205 / 0 / 64 / 0 / 80 KB -
+// two waves per SIMD, as the dense RT = 8 form; the new state (rb, re, the three bases) is scalar.
+template <typename T, int RT, int GM = 0>
+__global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs> args) {
     using NT = Num<T>;
     constexpr int BITS = 3, TILEP = 32;
+    static_assert(GM == 0 || RT == 8, "the grouped front end is built for 128-row blocks");
+    static_assert(GM >= 0 && GM <= 2, "0: dense, 1: grouped plain, 2: grouped weighted");
     // RT = 8: 128-row blocks (the weight ring leaves no registers for 16 row tiles).  RT = 1, 2, 4: "skinny" blocks of
     // 16 / 32 / 64 rows for small batches, launched with a grid-level K split (fp32 slabs + splitk_reduce_kernel): a
     // 3-bit wave of the per-wave kernel is 256 columns wide, so a 4096-wide layer gives it 16 column slabs; here the
@@ -53,7 +69,7 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
     constexpr int LUT_BYTES = 64 * 128;
     constexpr int STAGE_BYTES = PIECES * 1024;
 
-    BlockArgs a = args;
+    auto a = args;
     {
 #define FLUTE_OPAQUE(x) asm volatile("" : "+s"(x))
         FLUTE_OPAQUE(a.A); FLUTE_OPAQUE(a.Q); FLUTE_OPAQUE(a.D); FLUTE_OPAQUE(a.S); FLUTE_OPAQUE(a.QM2);
@@ -74,7 +90,23 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
     int bid = blockIdx.x, split = 0;
     if (a.splitk > 1) { split = bid % a.splitk; bid /= a.splitk; }
     int tm_idx, tn_idx;
-    if (a.order == 1) {
+    int row_lo = 0, row_hi = 0;                                    // grouped: the expert's rows [rb, re)
+    if constexpr (GM != 0) {
+        static_assert(GM == 0 || BM == kGroupedBlockRows, "the host's grid counts these blocks");
+        if constexpr (GM == 2) grouped_zero_unserved<NW * 64>(reinterpret_cast<uint16_t*>(a.D), a.offsets, a.E, a.M, a.N);
+        int b;
+        if (a.order == 1) { tn_idx = bid % a.tiles_n; b = bid / a.tiles_n; }
+        else { b = bid % a.tiles_m; tn_idx = bid / a.tiles_m; }
+        const GroupedBlock gb = grouped_block_map<kGroupedBlockRows>(a.offsets, a.E, a.M, b);
+        const int e = gb.e;
+        if (e < 0) return;                                         // b is past the table's blocks: nothing is requested, no barrier is met
+        tm_idx = gb.blk;
+        row_lo = gb.rb;
+        row_hi = gb.re;
+        a.Q += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);      // P = 3 (N / 16) unit rows of K / 2 words
+        a.S = reinterpret_cast<const uint16_t*>(a.S) + (size_t)e * (size_t)a.N * (size_t)a.G;
+        a.QM2 += (size_t)e << (2 * BITS);
+    } else if (a.order == 1) {
         const int per = a.tiles_m >> 3, x = bid & 7, i = bid >> 3;
         tm_idx = x * per + i % per;
         tn_idx = i / per;
@@ -93,7 +125,11 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
     const int nsteps = (kend - kbeg) >> 6;
     const uint32_t row_bytes = (uint32_t)a.K * 2u;
 
-    const srd_t x_srd = make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
+    // (grouped: rows count from the expert's first, the descriptor ends at its last; the weight and scale descriptors are one expert's)
+    const srd_t x_srd = GM != 0
+        ? make_srd(reinterpret_cast<const uint16_t*>(a.A) + (size_t)row_lo * a.K,
+                   (uint32_t)min((size_t)(row_hi - row_lo) * a.K * 2, (size_t)0xfffffff0u))
+        : make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
     const srd_t w_srd = make_srd(a.Q, (uint32_t)min((size_t)(3 * (a.N >> 4)) * row_bytes, (size_t)0xfffffff0u));
     const srd_t s_srd = make_srd(a.S, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
     // Activations (round 4, as qgemm_block2.h: WHOLE cache lines - a request is priced per line it touches; before: 16 rows
@@ -390,7 +426,7 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
 
         // ---- epilogue: accumulator register i of lane (r16, q4) = unit 4 q4 + i of the workgroup, i.e. four
         // consecutive columns of field f_t; the lane's output row is r16 ----
-        if constexpr (RT == 8) {
+        if constexpr (RT == 8 && GM == 0) {
             // 128-row blocks x 2 / 4 K slices combined INSIDE the launch (round 5, xwg.h, E form): the reference's Stream-K fix-up
             // for any bit width (tile_scheduler_utils.hpp:58-211, :460-481).  Until round 4: [M][N] fp32 slabs and a reduce launch
             // - kept (a.state == nullptr) for the 256-row blocks and for the skinny blocks, whose 4 - 8 slices of 16 .. 64 rows
@@ -412,13 +448,16 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const BlockArgs args)
         }
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
-            const int orow = m0 + r * 16 + r16;
-            if (orow < a.M) {
+            const int orow = (GM != 0 ? row_lo : 0) + m0 + r * 16 + r16;
+            if (orow < (GM != 0 ? row_hi : a.M)) {
+                float rw = 1.0f;
+                if constexpr (GM == 2) rw = a.row_weight[orow];     // once per lane and row tile, stored rows only
 #pragma unroll
                 for (int t = 0; t < NT2; ++t) {
                     const int col = unit_col0<BITS, TILEP>(unit0 + 4 * q4) + (t ? f1 : f0) * TILEP;
-                    const f32x4_t o4 = acc[r][t];
-                    if (a.splitk == 1) {
+                    f32x4_t o4 = acc[r][t];
+                    if constexpr (GM == 2) { o4[0] *= rw; o4[1] *= rw; o4[2] *= rw; o4[3] *= rw; }
+                    if (GM != 0 || a.splitk == 1) {
                         uint2 o;
                         o.x = (uint32_t)NT::from_float(o4[0]) | ((uint32_t)NT::from_float(o4[1]) << 16);
                         o.y = (uint32_t)NT::from_float(o4[2]) | ((uint32_t)NT::from_float(o4[3]) << 16);

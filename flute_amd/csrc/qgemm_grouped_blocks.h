@@ -1,11 +1,14 @@
 // Host side of the block form of the grouped qgemm: qgemm_block2.h's 128-row blocks behind a grouped front end (the kernel text and
 // the block map are described there), for experts with many rows - prefill and training - where the row form of qgemm_grouped.h
 // streams an expert's weights once per 32 rows.  Plain and weighted modes (flute_qgemm_grouped_ex / _weighted_ex with the block form)
-// and the SwiGLU mode behind its own entry (flute_qgemm_grouped_glu_blocks), 4 and 2 bits; 3 bits stay on the row form.
+// and the SwiGLU mode behind its own entry (flute_qgemm_grouped_glu_blocks), 4 and 2 bits.  3 bits: qgemm_block3.h's 128-row blocks
+// behind the same front end, plain and weighted, through entries of their own (flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks:
+// the old entries keep 3 bits on the row form); the fused SwiGLU launch has no 3-bit block form.
 #pragma once
 #include "../../include/flute_amd.h"
 #include "kernels.h"
 #include "qgemm_block2.h"
+#include "qgemm_block3.h"
 
 // The order of the block map: 1 - the column block is the fast index of blockIdx, so the workgroups in flight share a row block's
 // activations and spread over the column blocks of one expert; 0 (development builds, EXTRA=-DFLUTE_GROUPED_BLOCKS_ORDER=0) - the row
@@ -68,6 +71,19 @@ int qgemm_grouped_blocks_launch(const GroupedForward& g, hipStream_t stream) {
     if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, GM>;
     else if (tile_p == 64) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 64, 8, BITS, GM> : (Kernel)qgemm_block2_kernel<BF16, 64, 8, BITS, GM>;
     return grouped_blocks_enqueue<BITS>(k, a, stream);
+}
+
+// The 3-bit launch (qgemm_block3.h, RT = 8; TileP 32 only, like every 3-bit template): the same arguments, grid and LDS rule -
+// grouped_blocks_lds_bytes<3>() is the dense launch's 80 KB: the 8-KB pair table, 3 x 16-KB stages, 8 x 3-KB scale images.
+template <int GM>
+int qgemm_grouped_w3_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    GroupedBlockArgs a{};
+    grouped_block_args(a, g);
+    a.row_weight = GM == 2 ? g.row_weight : nullptr;
+    typedef void (*Kernel)(const GroupedBlockArgs);
+    Kernel k = nullptr;
+    if (g.tile_p == 32) k = g.dtype == 0 ? (Kernel)qgemm_block3_kernel<F16, 8, GM> : (Kernel)qgemm_block3_kernel<BF16, 8, GM>;
+    return grouped_blocks_enqueue<3>(k, a, stream);
 }
 
 // The SwiGLU launch (GM = 3): both stacks, the row index and the rows of Xsrc beside the shared arguments; the same grid.

@@ -74,6 +74,19 @@ def grouped_glu_blocks_form(E: int, rows: int, Tsrc: int, F: int, K: int, num_bi
     return {1: "rows", 2: "blocks"}[rc]
 
 
+def grouped_w3_blocks_form(mode: str, E: int, rows: int, N: int, K: int, group_size: int, template_id: int,
+                           num_sms: Optional[int] = None, dtype: torch.dtype = torch.float16) -> str:
+    """Which launch to take for `rows` rows over a stack of E 3-bit experts with [N, K] layers (`mode`: "plain", "weighted"):
+    "blocks" - `flute_amd.qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` - where the layer is eligible for them
+    and rows / E reaches the threshold, else "rows" - `flute_amd.qgemm_grouped` / `qgemm_grouped_weighted`; host only
+    (flute_qgemm_grouped_w3_blocks_form).  A layer both launches refuse raises."""
+    rc = _lib.get().flute_qgemm_grouped_w3_blocks_form({"plain": 0, "weighted": 2}[mode], _DTYPE_ID[dtype], group_size, E, rows,
+                                                       N, K, template_id, num_sms or 0)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "rows", 2: "blocks"}[rc]
+
+
 def grouped_input_grad_form(E: int, rows: int, N: int, K: int, num_bits: int, group_size: int, template_id: int,
                             num_sms: int = 0, dtype: torch.dtype = torch.float16, pair: bool = False) -> str:
     """The form - "slabs" or "blocks" - the automatic rule takes for a grouped input-gradient launch of `rows` rows over

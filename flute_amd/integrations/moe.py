@@ -10,7 +10,12 @@ for (`flute_amd.dev.grouped_form` tells which) - so the modules here need no swi
 backward's recompute of gate and up take the block form by themselves.  The fused GLU launch has its block form behind an
 entry of its own, `flute_amd.qgemm_grouped_glu_blocks`, and `FluteExperts(fused=True, glu_blocks=...)` opts in: `True` always
 (raises where the stacks are not eligible), `"auto"` where `flute_amd.dev.grouped_glu_blocks_form` says it pays for the step's
-T k rows (shapes only: no host synchronise), `False` - the default - never: the forward is then bit for bit what it was.  The
+T k rows (shapes only: no host synchronise), `False` - the default - never: the forward is then bit for bit what it was.
+Stacks of 3-bit experts have a block form too (qgemm_block3.h's 128-row blocks), behind ops of their own,
+`flute_amd.qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` - through `qgemm_grouped*` 3 bits are the row form at
+every count - and `FluteExperts(w3_blocks=...)` opts in the same three ways (`flute_amd.dev.grouped_w3_blocks_form` is its "auto")
+for the unfused gate, up and down launches and the fused path's weighted down launch; the fused GLU launch has no 3-bit block
+form and stays on its row form.  The
 backward's two input-gradient launches have their own pair of forms - slabs and, for 4- / 2-bit stacks with K % 256 == 0 from a
 mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input_grad_blocks.h;
 `flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.
@@ -268,6 +273,11 @@ class FluteExperts(torch.nn.Module):
     `glu_blocks` (with `fused=True`): which kernel runs the fused GLU launch - False: `qgemm_grouped_glu`'s row form at every
     row count (the default, today's forward bit for bit); True: `qgemm_grouped_glu_blocks` (raises where the stacks are not
     eligible); "auto": the block launch where `flute_amd.dev.grouped_glu_blocks_form` takes it for the step's T k rows.
+    `w3_blocks` (stacks of 3-bit experts): which kernel runs the plain launches of the unfused forward (gate, up, down) and the
+    fused forward's weighted down launch - False: `qgemm_grouped` / `qgemm_grouped_weighted`, the row form at 3 bits (the default,
+    today's forward bit for bit); True: `qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` (raises where a stack is not
+    3-bit, not eligible or learnable); "auto": those where `flute_amd.dev.grouped_w3_blocks_form` takes them for the step's T k
+    rows.  The fused GLU launch stays on its row form at 3 bits.
     `native_glu_grad` (with `fused=True`): the ops' keyword of that name - the backward of the fused GLU launch gathers its rows
     with `moe_gather` and forms dg, du with `swiglu_grad` (two HIP launches) where the default runs torch ops; the forward's bits
     are the same either way, the backward's differ within `flute_swiglu_grad`'s error account.
@@ -283,9 +293,12 @@ class FluteExperts(torch.nn.Module):
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
                  fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
                  native_glu_grad: bool = False, native_router_grad: bool = False,
-                 wide_routing: Union[bool, str] = False) -> None:
+                 wide_routing: Union[bool, str] = False, w3_blocks: Union[bool, str] = False) -> None:
         super().__init__()
         _check_tristate("glu_blocks", glu_blocks)
+        _check_tristate("w3_blocks", w3_blocks)
+        if w3_blocks is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
+            raise ValueError("FluteExperts: w3_blocks selects the kernels of 3-bit stacks; gate, up and down must be 3-bit")
         if glu_blocks is not False and not fused:
             raise ValueError("FluteExperts: glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
         _check_tristate("wide_routing", wide_routing)
@@ -312,15 +325,18 @@ class FluteExperts(torch.nn.Module):
         self.native_glu_grad = bool(native_glu_grad)
         self.native_router_grad = bool(native_router_grad)
         self.wide_routing = wide_routing
+        self.w3_blocks = w3_blocks
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
                      glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
-                     native_router_grad: bool = False, wide_routing: Union[bool, str] = False) -> "FluteExperts":
+                     native_router_grad: bool = False, wide_routing: Union[bool, str] = False,
+                     w3_blocks: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
-                   native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing)
+                   native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing,
+                   w3_blocks=w3_blocks)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -331,8 +347,8 @@ class FluteExperts(torch.nn.Module):
         if self.fused:
             return self._forward_fused(hidden, topk_weights, perm, offsets, token)
         x = hidden[token]
-        h = torch.nn.functional.silu(self.gate(x, offsets)) * self.up(x, offsets)
-        y = self.down(h, offsets) * topk_weights.reshape(-1)[perm].to(hidden.dtype)[:, None]
+        h = torch.nn.functional.silu(self._plain(self.gate, x, offsets)) * self._plain(self.up, x, offsets)
+        y = self._plain(self.down, h, offsets) * topk_weights.reshape(-1)[perm].to(hidden.dtype)[:, None]
         # rows past offsets[E] (ids outside [0, E)) were written by no expert: they contribute nothing
         served = torch.arange(y.shape[0], device=y.device) < offsets[-1]
         y = torch.where(served[:, None], y, torch.zeros_like(y))
@@ -409,7 +425,8 @@ class FluteExperts(torch.nn.Module):
         the rows past offsets[E] (ids outside [0, E)) as zeros.  `pos` is read by the GLU launch's backward only."""
         gate, up, down = self.gate, self.up, self.down
         num_sms = _stack_num_sms(gate, hidden.device)
-        glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms))
+        glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms),
+                                        self._takes_w3_blocks(down, "weighted", rows.shape[0], num_sms, hidden.dtype))
         h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales, _table_of(up),
                 gate.num_bits, gate.group_size, gate.template_id, num_sms, rows=rows, pos=pos)
         return weighted(h, offsets, down.weight, down.scales, _table_of(down), row_weight, down.num_bits, down.group_size,
@@ -430,11 +447,34 @@ class FluteExperts(torch.nn.Module):
                                                      gate.in_features, gate.num_bits, gate.group_size, gate.template_id,
                                                      num_sms, hidden.dtype) == "blocks"
 
-    def _fused_ops(self, glu_blocks: bool = False):
+    def _takes_w3_blocks(self, stack, mode: str, rows: int, num_sms, dtype) -> bool:
+        """Whether this step's plain / weighted launch of `stack` is the 3-bit block one: `w3_blocks`, "auto" resolved from the shapes
+        alone.  The learnable stacks' entries have no such form: True raises on them, "auto" leaves them as they are."""
+        if self.w3_blocks is False:
+            return False
+        if isinstance(stack, LearnableGroupedFluteLinear):
+            if self.w3_blocks is True:
+                raise ValueError("FluteExperts: w3_blocks=True, but a stack is learnable (freeze_experts first, or w3_blocks='auto')")
+            return False
+        if self.w3_blocks is True:
+            return True
+        return flute_amd.dev.grouped_w3_blocks_form(mode, self.num_experts, rows, stack.out_features, stack.in_features,
+                                                    stack.group_size, stack.template_id, num_sms, dtype) == "blocks"
+
+    def _plain(self, stack, x_sorted, offsets):
+        """One plain launch of the unfused forward: the stack's own forward, or with `w3_blocks` taken its 3-bit block op."""
+        num_sms = _stack_num_sms(stack, x_sorted.device)
+        if not self._takes_w3_blocks(stack, "plain", x_sorted.shape[0], num_sms, x_sorted.dtype):
+            return stack(x_sorted, offsets)
+        return flute_amd.qgemm_grouped_w3_blocks(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits,
+                                                 stack.group_size, stack.template_id, num_sms)
+
+    def _fused_ops(self, glu_blocks: bool = False, w3_down: bool = False):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
         scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
         `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
         `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`).
+        `w3_down`: the weighted launch on the 3-bit block form (`qgemm_grouped_weighted_w3_blocks`).
         The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
@@ -449,6 +489,8 @@ class FluteExperts(torch.nn.Module):
             glu = functools.partial(glu, native_glu_grad=True)
         weighted = qgemm_grouped_weighted_learnable if has[2] else \
             qgemm_grouped_weighted_learnable_scales if learnable else flute_amd.qgemm_grouped_weighted
+        if w3_down:                                             # (`_takes_w3_blocks`: the down stack is not learnable)
+            weighted = flute_amd.qgemm_grouped_weighted_w3_blocks
         if self.native_router_grad:
             weighted = functools.partial(weighted, native_router_grad=True)
         return glu, weighted
@@ -467,8 +509,8 @@ class FluteExperts(torch.nn.Module):
             y = self._fused_mlp(hidden, offsets, rows, row_weight, pos)
         else:
             x = hidden[rows]
-            h = torch.nn.functional.silu(self.gate(x, offsets)) * self.up(x, offsets)
-            y = self.down(h, offsets) * row_weight.to(hidden.dtype)[:, None]
+            h = torch.nn.functional.silu(self._plain(self.gate, x, offsets)) * self._plain(self.up, x, offsets)
+            y = self._plain(self.down, h, offsets) * row_weight.to(hidden.dtype)[:, None]
         return flute_amd.moe_combine(y, pos, offsets, rows if self.native_router_grad else None)
 
 

@@ -441,9 +441,15 @@ def _launch_grouped(name, tensors, weight, rows, N, out_shape, layer, row_limit=
     return out
 
 
+# `_launch_plain`'s and `_launch_weighted`'s form for the 3-bit block launches behind their own entries (flute_qgemm_grouped_w3_blocks /
+# _weighted_w3_blocks): not one of `_GROUPED_FORMS`, which keep their meaning on the old ops ("blocks" raises there at 3 bits)
+_W3_BLOCKS = "w3_blocks"
+
+
 def _launch_plain(input, offsets, weight, scales, table2, layer, form=None):
-    return _launch_grouped("qgemm_grouped_ex", (input, offsets, weight, scales, table2), weight, (input.shape[0],),
-                           scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=(form,))
+    name, form = ("qgemm_grouped_w3_blocks", ()) if form == _W3_BLOCKS else ("qgemm_grouped_ex", (form,))
+    return _launch_grouped(name, (input, offsets, weight, scales, table2), weight, (input.shape[0],),
+                           scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=form)
 
 
 # `_launch_glu`'s form for the block launch behind its own entry (flute_qgemm_grouped_glu_blocks): not one of `_GROUPED_FORMS`,
@@ -481,8 +487,27 @@ def _require_glu_blocks(name, input, rows, gate_weight, gate_scales, layer):
 
 
 def _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form=None):
-    return _launch_grouped("qgemm_grouped_weighted_ex", (input, offsets, weight, scales, table2, row_weight), weight,
-                           (input.shape[0],), scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=(form,))
+    name, form = ("qgemm_grouped_weighted_w3_blocks", ()) if form == _W3_BLOCKS else ("qgemm_grouped_weighted_ex", (form,))
+    return _launch_grouped(name, (input, offsets, weight, scales, table2, row_weight), weight,
+                           (input.shape[0],), scales.shape[1], (input.shape[0], scales.shape[1]), layer, form=form)
+
+
+def _require_w3_blocks(name, input, weight, scales, layer):
+    """Raise ValueError where flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks (one rule) do not serve the shape.  Host only,
+    before anything is launched: the entry refuses a shape before it looks at a pointer, so it is asked with null pointers."""
+    num_bits, group_size, template_id, _ = layer
+    E, P, K = weight.shape
+    if input.shape[0] >= 2 ** 31:
+        raise ValueError
+    rc = _lib.get().flute_qgemm_grouped_w3_blocks(
+        _DTYPE_ID[input.dtype], num_bits, group_size, E, input.shape[0], scales.shape[1], K, P, template_id,
+        *(None,) * 6, 0, None)
+    if rc == _FLUTE_ERR_SHAPE:
+        raise ValueError(f"flute_amd.{name}: the 3-bit block form is not eligible for this layer (include/flute_amd.h, "
+                         "flute_qgemm_grouped_w3_blocks: 3 bits, (K / group_size) % 8 == 0, N % 256 == 0, (T + 256) * K * 2 and "
+                         "one expert's scale and packed bytes below 2^32 - 16)")
+    if rc not in (0, _FLUTE_ERR_NULL):
+        _lib.check(rc)
 
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
@@ -509,8 +534,26 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     return _launch_plain(input, offsets, weight, scales, table2, layer, form)
 
 
+def qgemm_grouped_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                            table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+    """`qgemm_grouped` for stacks of 3-bit experts on the block form, for prefill and training row counts: the same operands,
+    formula and rounding (include/flute_amd.h, flute_qgemm_grouped_w3_blocks) on 128-row x 256-column blocks of the dense 3-bit
+    prefill kernel - all of K in one fp32 accumulator of the matrix core, a weight dequantised once per 128 rows (qgemm_block3.h,
+    GM = 1).  Same validation, same autograd (the backward's kernels do not depend on which kernel ran the forward; the 3-bit
+    input gradient stays on the slab form).  Equal arguments give equal bits; the bits equal `qgemm_grouped`'s on exactly
+    representable inputs and may differ elsewhere.  A layer the form does not serve raises ValueError before anything is launched;
+    `flute_amd.dev.grouped_w3_blocks_form` tells where the form pays."""
+    _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_w3_blocks("qgemm_grouped_w3_blocks", input, weight, scales, layer)
+    if _records_grad(input, scales, table2):
+        _refuse_stack_grads("qgemm_grouped_w3_blocks", scales, table2)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, _W3_BLOCKS)
+    return _launch_plain(input, offsets, weight, scales, table2, layer, _W3_BLOCKS)
+
+
 class _GroupedFunction(torch.autograd.Function):
-    """`qgemm_grouped` under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)
+    """`qgemm_grouped` (and, with form `_W3_BLOCKS`, `qgemm_grouped_w3_blocks`) under autograd: the same launch (rows no expert serves then zeroed), dX = qgemm_grouped_input_grad(dY)
     and - for `integrations.learnable`; the op itself refuses scales that require grad -
     dS = qgemm_grouped_scale_grad(dY, x), the only reader of the saved `input`.  With `codebook` - a stack's fp32 master,
     which `integrations.learnable` passes next to the `table2` it built from it (`_grouped_codebook_table2`) - the
@@ -707,8 +750,25 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
+def qgemm_grouped_weighted_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
+                                     table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
+                                     template_id: int, num_sms=None, native_router_grad: bool = False) -> torch.Tensor:
+    """`qgemm_grouped_weighted` for stacks of 3-bit experts on the block form (`qgemm_grouped_w3_blocks`'s kernel with the routing
+    weight in its epilogue, qgemm_block3.h GM = 2): out[r] = round_T(row_weight[r] * acc32), the rows from offsets[E] on zeros.
+    Same validation and autograd as `qgemm_grouped_weighted` (`native_router_grad` as there); a layer the form does not serve
+    raises ValueError before anything is launched."""
+    _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_w3_blocks("qgemm_grouped_weighted_w3_blocks", input, weight, scales, layer)
+    if _records_grad(input, row_weight, scales, table2):
+        _refuse_stack_grads("qgemm_grouped_weighted_w3_blocks", scales, table2)
+        return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, _W3_BLOCKS,
+                                              bool(native_router_grad))
+    return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, _W3_BLOCKS)
+
+
 class _GroupedWeightedFunction(torch.autograd.Function):
-    """`qgemm_grouped_weighted` under autograd.  A row weight that needs no gradient rides in the input-gradient kernel's
+    """`qgemm_grouped_weighted` (and, with form `_W3_BLOCKS`, `qgemm_grouped_weighted_w3_blocks`) under autograd.  A row weight that needs no gradient rides in the input-gradient kernel's
     epilogue (one launch); one that does takes dH' = input_grad(dY), d row_weight[r] = sum_k dH'[r, k] h[r, k] in fp32
     (zero from offsets[E] on) and dH = round_T(row_weight dH').  For `integrations.learnable` (the op itself refuses
     scales that require grad) dS = qgemm_grouped_scale_grad(dY, h, row_weight=row_weight): the routing weight multiplies

@@ -36,6 +36,8 @@ extern "C" {
  *    the block form of the grouped input gradient: flute_qgemm_grouped_input_grad_ex (the old entry with a trailing `form`),
  *    flute_qgemm_grouped_input_grad_form, flute_grouped_input_grad_form_t;
  *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
+ *    the block form for 3-bit stacks behind its own entries: flute_qgemm_grouped_w3_blocks, flute_qgemm_grouped_weighted_w3_blocks,
+ *    flute_qgemm_grouped_w3_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
  *    the routing over many workgroups: flute_moe_route_wide, flute_moe_gate_route_wide, flute_moe_route_wide_workspace, flute_moe_route_form
@@ -324,7 +326,7 @@ size_t flute_qgemm_table_grad_scratch_bytes(int num_bits, int group_size, int M,
  * hold: a NaN or Inf in row r still reaches row r of Y only.  A malformed table stays memory-safe in both forms; in the
  * block form a table whose clamped ranges own more blocks than the grid holds (decreasing entries can) leaves the rows of
  * the blocks past the grid unwritten, and rows that overlapping ranges name twice have unspecified contents.
- * The block form serves: num_bits 4 / 2, (K / group_size) % 8 == 0, N a multiple of 256, (T + 256) * K * 2 and one expert's
+ * The block form serves (3 bits have one behind entries of their own, flute_qgemm_grouped_w3_blocks below): num_bits 4 / 2, (K / group_size) % 8 == 0, N a multiple of 256, (T + 256) * K * 2 and one expert's
  * scale bytes N * (K / group_size) * 2 below 2^32 - 16, the plain and weighted launches.  The automatic rule takes it where
  * it is eligible and the mean rows per expert, T / E, is at least FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS - or
  * FLUTE_GROUPED_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms - (measured: csrc/api_train.hip);
@@ -451,6 +453,40 @@ int flute_qgemm_grouped_glu_blocks_form(int dtype, int num_bits, int group_size,
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream);
+
+/* The block form for stacks of 3-bit experts, behind entries of their own: flute_qgemm_grouped and flute_qgemm_grouped_weighted on
+ * the 128-row x 256-column blocks of the dense 3-bit prefill kernel (three-plane layout), for prefill and training row counts.  The
+ * operands, the formula, the zero fill of the weighted launch, the propagation of non-finite rows, the grid rule, hipGraph capture
+ * and the malformed-table contract are the block form's as flute_qgemm_grouped describes them (csrc/grouped_rows.h states the row
+ * map once): all of K in one fp32 accumulator of the matrix core, one rounding, nothing shared between workgroups, equal arguments
+ * give equal bits; bits may differ from the row form's except on exactly representable inputs.  flute_qgemm_grouped*, their _ex
+ * forms and flute_qgemm_grouped_form keep their behaviour - 3 bits there are the row form at every count, and forcing blocks is
+ * refused -; a caller opts in by calling these.
+ * They serve: num_bits 3 (TileP 32), (K / group_size) % 8 == 0, N a multiple of 256, and (T + 256) * K * 2, one expert's scale
+ * bytes N * (K / group_size) * 2 and one expert's packed bytes 3 * (N / 16) * K * 2 each below 2^32 - 16.
+ * Refusals, before anything is enqueued or dereferenced, in this order: the old entry's (dtype, the layer checks, FLUTE_ERR_SHAPE
+ * for P or a negative E / T); FLUTE_ERR_SHAPE for num_bits != 3 or a shape outside the list above (E == 0 and T == 0 are inside
+ * it); E == 0 or T == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL for a null pointer.  num_sms is accepted for
+ * symmetry and not used. */
+int flute_qgemm_grouped_w3_blocks(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P, int template_id,
+                                  const void* X, const void* offsets, const void* Q, const void* S, const void* QM2,
+                                  void* Y, int num_sms, void* stream);
+int flute_qgemm_grouped_weighted_w3_blocks(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
+                                           int template_id, const void* X, const void* offsets, const void* Q, const void* S,
+                                           const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream);
+
+/* Which launch a caller should take for a stack of 3-bit experts (mode: FLUTE_GROUPED_PLAIN or _WEIGHTED): FLUTE_GROUPED_FORM_BLOCKS
+ * (the entries above) where the shape is in their list, E >= 1 and the mean rows per expert, rows / E, is at least
+ * FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS - or FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (N / 256) is below num_sms
+ * (< 1: 256) -, else FLUTE_GROUPED_FORM_ROWS (the old entries), or the negative error the block launch would refuse the layer with
+ * (mode outside the two, num_bits != 3: FLUTE_ERR_SHAPE).  Host only: no pointers, nothing is enqueued; P is taken as 3 * N / 16.
+ * The two constants are measured on the 3-bit launches (csrc/api_train.hip): each is the smallest swept mean from
+ * which the block launch is not slower than the row form on any swept stack of its kind.  (Both are 24: the 3-bit row form
+ * streams an expert's weights once per 16 rows, so from 17 rows per expert on it pays a second pass whether the chip is full or not.) */
+#define FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS 24            /* E * (N / 256) >= num_sms: the experts' column blocks fill the chip */
+#define FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL 24    /* fewer workgroups than compute units */
+int flute_qgemm_grouped_w3_blocks_form(int mode, int dtype, int group_size, int E, int rows, int N, int K, int template_id,
+                                       int num_sms);
 
 /* The input gradient of flute_qgemm_grouped and of the fused forms built on it, in ONE launch: a grouped GEMM over the
  * packed stacks that contracts over N where the forward contracts over K.

@@ -115,7 +115,10 @@ step of FluteExperts(fused=True, native_routing=True) with glu_blocks False agai
 tool's method: form="rows", form="blocks", the automatic rule, and a per-expert loop of flute_amd.qgemm on row ranges the host
 knows (the stack's template; the planner picks each call's kernel).  Then the threshold sweep - rows / E in 16 .. 256 on two E = 8 stacks and
 an E = 64 stack, rows against blocks - and the backward step of --mode input_grad at 512 and 4096 tokens with the recompute of
-gate and up on the row form (the code before the block form) and on the automatic rule.
+gate and up on the row form (the code before the block form) and on the automatic rule.  Sections `w3` and `w3_sweep`
+(profiles/grouped_moe_prefill_w3.json: --only w3 w3_sweep): stacks of 3-bit experts, W3G64 fp16 and bf16 - the row form, the block
+launch behind flute_amd.qgemm_grouped_w3_blocks and the per-expert loop at Mixtral's two projections with 512, 4096 and 8192 rows
+and an E = 64 2048 x 2048 stack at 4096 - and the sweep of rows / E in 8 .. 128 that FLUTE_GROUPED_W3_BLOCKS_MIN_MEAN_ROWS* are read from.
 """
 import argparse
 import copy
@@ -839,7 +842,8 @@ def child_table_grad(args, device):
 
 class Forward:
     """`copies` stacks of `experts` packed layers [N, K]; step(i) is one forward over all routed rows on copy i, by `how`:
-    "rows" / "blocks" / "auto" - one grouped launch of that form (mode "plain" or "weighted") -, "loop" - flute_amd.qgemm per expert
+    "rows" / "blocks" / "auto" - one grouped launch of that form (mode "plain" or "weighted") -, "w3_blocks" - the 3-bit block launch
+    (flute_amd.qgemm_grouped_w3_blocks / _weighted_w3_blocks) -, "loop" - flute_amd.qgemm per expert
     on row ranges the host knows.  (The GLU contenders: GluForward.)"""
 
     def __init__(self, experts, N, K, counts, copies, device, how, mode="plain", bits=BITS, dtype=DTYPE):
@@ -876,6 +880,10 @@ class Forward:
                     r0, r1 = self.off_host[e], self.off_host[e + 1]
                     ys.append(fa.qgemm(self.X[r0:r1], Q[e], S[e], self.table, self.table2, self.ws, *a))
             return ys
+        if self.how == "w3_blocks":                   # the 3-bit block launches behind their own ops
+            if self.mode == "weighted":
+                return fa.qgemm_grouped_weighted_w3_blocks(self.X, self.offsets, Q, S, t2, self.w, *a)
+            return fa.qgemm_grouped_w3_blocks(self.X, self.offsets, Q, S, t2, *a)
         form = None if self.how == "auto" else self.how
         if self.mode == "weighted":
             return fa.qgemm_grouped_weighted(self.X, self.offsets, Q, S, t2, self.w, *a, form=form)
@@ -975,7 +983,15 @@ GLU_LINES = [("mixtral gate_up pair", 8, 14336, 4096, r, 4, "float16") for r in 
 GLU_SWEEP_MEANS = (16, 32, 48, 64, 96, 128)
 GLU_SWEEP_STACKS = [("mixtral gate_up pair", 8, 14336, 4096), ("many-expert 2048 x 2048 pair", 64, 2048, 2048),   # fill the chip
                     ("E 8 4096 x 4096 pair", 8, 4096, 4096)]                                                       # 128 workgroups: does not
-PREFILL_SECTIONS = ("forward", "glu", "sweep", "backward", "glu_sweep", "glu_module")
+PREFILL_SECTIONS = ("forward", "glu", "sweep", "backward", "glu_sweep", "glu_module", "w3", "w3_sweep")
+# 3-bit stacks (W3G64): the row form - what flute_amd.qgemm_grouped runs at every count -, the block launch behind its own op and the
+# per-expert loop; then the threshold sweep of the block launch against the row form (profiles/grouped_moe_prefill_w3.json:
+# --only w3 w3_sweep)
+W3_LINES = [(name, experts, N, K, r, dt, mode) for dt in ("float16", "bfloat16") for name, experts, N, K, r, mode in
+            [("mixtral gate_up", 8, 14336, 4096, r, "plain") for r in (512, 4096, 8192)] +
+            [("mixtral down", 8, 4096, 14336, r, "plain") for r in (512, 4096, 8192)] +
+            [("many-expert 2048 x 2048", 64, 2048, 2048, 4096, "plain"), ("mixtral down", 8, 4096, 14336, 4096, "weighted")]]
+W3_SWEEP_MEANS = (8, 16, 24, 32, 48, 64, 96, 128)
 SWEEP_STACKS = [("mixtral gate_up", 8, 14336, 4096), ("mixtral down", 8, 4096, 14336), ("many-expert 2048 x 2048", 64, 2048, 2048)]
 
 
@@ -1105,6 +1121,44 @@ def main_prefill(args, device):
             del layers
         del stacks
         torch.cuda.empty_cache()
+    # 3-bit stacks: the row form, the block launch and the per-expert loop; the dense 3-bit kernel's own time per block round beside it
+    for name, experts, N, K, nrows, dt, mode in (W3_LINES if want("w3") else ()):
+        dtype = getattr(torch, dt)
+        counts = routing(nrows // 2, seed=nrows // 2) if experts == E else ig_counts(nrows, experts, seed=nrows + experts)
+        copies = prefill_copies(experts, N, K, 3)
+        layers = {how: Forward(experts, N, K, counts, copies, device, how, mode, 3, dtype)
+                  for how in ("rows", "w3_blocks") + (("loop",) if mode == "plain" else ())}
+        first = layers["rows"]
+        a, b = layers["w3_blocks"].step(0).float(), first.step(0).float()
+        diff, ref = float((a - b).abs().max()), float(b.abs().max())
+        us, spread, replays = time_forms(layers, args)
+        flop, nblk = first.flops(), sum(-(-c // 128) for c in counts) * (N // 256)
+        emit({"what": "w3 forward", "shape": name, "mode": mode, "bits": 3, "dtype": dt, "experts": experts, "N": N, "K": K,
+              "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+              "auto_form": dev.grouped_w3_blocks_form(mode, experts, sum(counts), N, K, G, first.tid, first.num_sms, dtype),
+              "us": us, "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()}, "spread": spread, "flop": flop,
+              "blocks_over_rows": round(us["w3_blocks"] / us["rows"], 4), "workgroups_with_rows": nblk,
+              "rounds_of_256_CUs": round(nblk / first.num_sms, 2),
+              "us_per_block_round_at_K4096": round(us["w3_blocks"] / max(1.0, nblk / first.num_sms) * 4096 / K, 2),
+              "max_abs_diff_blocks_vs_rows": diff, "max_abs_rows": ref, "replays_us": replays})
+        del layers, first, a, b
+        torch.cuda.empty_cache()
+    for name, experts, N, K in (SWEEP_STACKS if want("w3_sweep") else ()):
+        copies = prefill_copies(experts, N, K, 3)
+        for mean in W3_SWEEP_MEANS:
+            for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                        ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                layers = {how: Forward(experts, N, K, counts, copies, device, how, "plain", 3) for how in ("rows", "w3_blocks")}
+                first = layers["rows"]
+                us, spread, replays = time_forms(layers, args)
+                emit({"what": "w3 threshold sweep", "shape": name, "experts": experts, "N": N, "K": K, "mean_rows_per_expert": mean,
+                      "counts": spread_name, "counts_min_max": [min(counts), max(counts)], "rows": sum(counts), "us": us,
+                      "fills_the_chip": bool(experts * (N // 256) >= first.num_sms),
+                      "blocks_over_rows": round(us["w3_blocks"] / us["rows"], 4), "spread": spread,
+                      "auto_form": dev.grouped_w3_blocks_form("plain", experts, sum(counts), N, K, G, first.tid, first.num_sms),
+                      "replays_us": replays})
+                del layers, first
+                torch.cuda.empty_cache()
     # the threshold sweep: rows / E on both sides of the rule, rows against blocks, even counts and a routed draw
     for name, experts, N, K in (SWEEP_STACKS if want("sweep") else ()):
         copies = prefill_copies(experts, N, K, BITS)
