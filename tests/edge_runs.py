@@ -119,14 +119,25 @@ def offsets_tensor(counts):
     return torch.tensor(OE.offsets_list(counts), dtype=torch.int32)
 
 
+# the block forms behind entries of their own (separate symbols, no trailing `form`): flute_qgemm_grouped_w3_blocks,
+# flute_qgemm_grouped_weighted_w3_blocks, flute_qgemm_grouped_glu_blocks
+FORWARD_FORM_W3_BLOCKS, FORWARD_FORM_GLU_BLOCKS = "w3_blocks", "glu_blocks"
+OWN_ENTRIES = {("qgemm_grouped", FORWARD_FORM_W3_BLOCKS): "qgemm_grouped_w3_blocks",
+               ("qgemm_grouped_weighted", FORWARD_FORM_W3_BLOCKS): "qgemm_grouped_weighted_w3_blocks",
+               ("qgemm_grouped_glu", FORWARD_FORM_GLU_BLOCKS): "qgemm_grouped_glu_blocks"}
+
+
 def _entry(name, form):
-    """form None: the old entry (the automatic rule); otherwise the _ex entry with the form named."""
+    """form None: the old entry (the automatic rule); a number: the _ex entry with the form named; a name: the form's own
+    entry, which refuses what it does not serve itself.  A launch that has no entry of that name is an error here."""
+    if isinstance(form, str):
+        return OWN_ENTRIES[name, form], ()
     return (name, ()) if form is None else (name + "_ex", (form,))
 
 
 def run_forward(env, c, X, nan_expected=False, form=None, counts=None):
-    """A forward case of op_edge_cases (plain, weighted or glu) on the activations X; counts: another table over the same
-    rows (one that ends early leaves rows no expert serves)."""
+    """A forward case of op_edge_cases (plain, weighted or glu) on the activations X; form: see _entry; counts: another table
+    over the same rows (one that ends early leaves rows no expert serves)."""
     st = dev_stack(env, c.layers)
     off = offsets_tensor(c.counts if counts is None else counts)
     R = sum(c.counts)

@@ -223,7 +223,7 @@ def device_row_weights(T, seed):
 
 
 class ExactStack:
-    """E exact layers [N, K = 7168] (4 / 2 bits, g = 64, TileP 32) on the device, each with its dense exact weight in fp64 and
+    """E exact layers [N, K = 7168] (4 / 3 / 2 bits, g = 64, TileP 32) on the device, each with its dense exact weight in fp64 and
     fp32, and the premise of exactness asserted for both contractions: K 4 max|w| < 2^21 (the forward, over K) and
     N 4 max|w| < 2^21 (the input gradient, over N) bound every sum of |x w|."""
 

@@ -1,8 +1,8 @@
 """Hostile operands for the MoE and training ops: the constructions and the by-rule expectations.
 
 A test helper module (not a conftest).  `tests/test_op_edge_cases.py` checks every construction and every rule on the CPU,
-`tests/test_grouped_edges_gpu.py`, `tests/test_block_edges_gpu.py` (the block variants) and `tests/test_grad_edges_gpu.py`
-run them against the kernels.  Each builder asserts the premises of its case while it builds it, so a premise holds
+`tests/test_grouped_edges_gpu.py`, `tests/test_block_edges_gpu.py` (the block variants), `tests/test_block_edges_own_entries_gpu.py`
+(the 3-bit and the SwiGLU block variants) and `tests/test_grad_edges_gpu.py` run them against the kernels.  Each builder asserts the premises of its case while it builds it, so a premise holds
 wherever the case is used.
 
 Range edges (fp16): an exact case outside the exact tests' operating region - subnormal weights (`Layer(**SUBW)`),
@@ -41,6 +41,12 @@ BLOCK_CONFIGS = tuple(c for c in CONFIGS if c[0] != 3)
 BLOCK_G_CASES = tuple(c for c in G_CASES if c[0] != 3)
 BLOCK_K_GRAD = 512
 BLOCK_OVERFLOW_K_GRAD = 256
+# The block forms behind entries of their own.  3 bits (qgemm_block3.h; flute_qgemm_grouped_w3_blocks and _weighted_w3_blocks): the
+# forward builders with block=True at (3, 32) - N = 512, one column block of the layout -, listed by the w3_block_* parameter lists.
+# The fused SwiGLU launch (qgemm_block2.h, GM = 3; flute_qgemm_grouped_glu_blocks): glu_saturation_case and the "glu" branch of
+# forward_nonfinite_case with block=True over BLOCK_CONFIGS, F = max(256, column block), K = 8 groups.
+W3_BLOCK_G_CASES = ((3, 32, 64), (3, 32, 32))
+W3_PUSHED_TRIES = 20
 
 
 def grad_counts(rb=ROW_BLOCK):
@@ -141,11 +147,22 @@ def grad_blocks_eligible(bits, K):
     return bits in (4, 2) and K % 256 == 0
 
 
+def w3_blocks_eligible(bits, g, K, N):
+    """include/flute_amd.h, flute_qgemm_grouped_w3_blocks "They serve" (the byte limits are far away): the 3-bit stacks' own
+    entries, with a rule of their own."""
+    return bits == 3 and K % g == 0 and (K // g) % 8 == 0 and N % 256 == 0
+
+
+def glu_blocks_eligible(bits, g, K, F):
+    """include/flute_amd.h, flute_qgemm_grouped_glu_blocks "It serves"."""
+    return bits in (4, 2) and K % g == 0 and (K // g) % 8 == 0 and F % 256 == 0
+
+
 def _forward_shape(bits, tile_p, g, block, overflow=False):
     """(counts, K, N) of a forward case."""
     if block:
         counts, K, N = grad_counts(), (XC.OVERFLOW_K if overflow else 8 * g), block_n(bits, tile_p)
-        assert forward_blocks_eligible(bits, g, K, N)
+        assert forward_blocks_eligible(bits, g, K, N) or w3_blocks_eligible(bits, g, K, N)
         return counts, K, N
     return FWD_COUNTS, (XC.OVERFLOW_K if overflow else K_EDGE), 3 * XC.cols_per_block(bits, tile_p)
 
@@ -231,10 +248,23 @@ def forward_range_case(op, kind, bits, tile_p, g=64, block=False):
 
 def weighted_pushed_case(bits, tile_p, g=64, block=False):
     """The unweighted result is finite; a power-of-two row weight alone pushes row a past 65520 (+inf), and the same
-    weight negated on a copy of the row, b, gives -inf at the same place."""
+    weight negated on a copy of the row, b, gives -inf at the same place.  The 3-bit block variant has a seed key of its own:
+    under the key of the other cases the pushed row's largest element is negative and nothing of row a reaches +inf, so it
+    takes the first of W3_PUSHED_TRIES keys under which every premise below holds (searched_stack's way; the premises are
+    asserted as for every other case)."""
+    if not (block and bits == 3):
+        return _weighted_pushed_case(bits, tile_p, g, block, XC.seed_of("pushed", bits, tile_p, g, *_block_key(block)))
+    for j in range(W3_PUSHED_TRIES):
+        try:
+            return _weighted_pushed_case(bits, tile_p, g, block, XC.seed_of("pushed", bits, tile_p, g, "w3 blocks", j))
+        except AssertionError as err:
+            last = err
+    raise AssertionError("no seed key meets the premises") from last
+
+
+def _weighted_pushed_case(bits, tile_p, g, block, seed):
     dtype = F16
     counts, K, N = _forward_shape(bits, tile_p, g, block)
-    seed = XC.seed_of("pushed", bits, tile_p, g, *_block_key(block))
     layers = stack(bits, tile_p, g, dtype, K, N, len(counts), seed)
     off = offsets_list(counts)
     T = off[-1]
@@ -275,24 +305,28 @@ def glu_exact(gate, up, counts, X, rows=None):
     return G, U
 
 
-def glu_saturation_case(bits, tile_p, g, dtype, use_rows):
+def glu_saturation_case(bits, tile_p, g, dtype, use_rows, block=False):
     """Integer activations at p = 0.  In every expert with two rows or more, row 0 = sign(w_gate[:, n0]) over the first
     sign_k k and row 1 = -row 0: |g| of several hundred in column n0, ordinary values elsewhere; the other rows are
     integers in [-1, 1].  The classes per element (c.hi, c.lo, c.mid) and their premises are asserted here; sign_k is the
     first of GLU_SIGN_KS with which they hold (the tables differ in size: a stack of large entries needs fewer k to reach
-    several hundred, and with more its products g u would leave the range in which they are exact in fp32)."""
+    several hundred, and with more its products g u would leave the range in which they are exact in fp32).
+    block: the same at a shape flute_qgemm_grouped_glu_blocks serves - grad_counts(), F = max(256, column block), K = 8 g."""
     for sign_k in GLU_SIGN_KS:
         try:
-            return _glu_saturation_case(bits, tile_p, g, dtype, use_rows, sign_k)
+            return _glu_saturation_case(bits, tile_p, g, dtype, use_rows, sign_k, block)
         except AssertionError as err:
             last = err
     raise AssertionError("no sign_k meets the premises; change the seed") from last
 
 
-def _glu_saturation_case(bits, tile_p, g, dtype, use_rows, sign_k):
+def _glu_saturation_case(bits, tile_p, g, dtype, use_rows, sign_k, block=False):
     counts, K = FWD_COUNTS, K_EDGE
     N = 3 * XC.cols_per_block(bits, tile_p)
-    seed = XC.seed_of("glu sat", bits, tile_p, g, dtype)
+    if block:
+        counts, K, N = grad_counts(), 8 * g, block_n(bits, tile_p)
+        assert glu_blocks_eligible(bits, g, K, N) and sign_k <= K
+    seed = XC.seed_of("glu sat", bits, tile_p, g, dtype, *_block_key(block))
     E = len(counts)
     gate = stack(bits, tile_p, g, dtype, K, N, E, seed)
     up = stack(bits, tile_p, g, dtype, K, N, E, seed + 500)
@@ -328,7 +362,7 @@ def _glu_saturation_case(bits, tile_p, g, dtype, use_rows, sign_k):
         assert torch.isinf(P.to(F16)[hi]).any(), "some round_T(g u) are +-inf: a store that saturates at 65504 fails"
     return types.SimpleNamespace(op="glu", kind="saturation", bits=bits, tile_p=tile_p, g=g, dtype=dtype, K=K, N=N,
                                  counts=counts, layers=gate, up=up, X=X, rows=rows, G=G, U=U, hi=hi, lo=lo, mid=mid,
-                                 P=P, Eref=Eref, rw=None, sign_k=sign_k)
+                                 P=P, Eref=Eref, rw=None, sign_k=sign_k, block=block, out=out)
 
 
 # --- non-finite rows ----------------------------------------------------------------------------------------------------
@@ -377,9 +411,11 @@ def _block_row_weights(rw):
 
 def forward_nonfinite_case(op, bits, tile_p, g, dtype, use_rows=False, block=False):
     """One NaN and one +Inf per launch, on both sides of a seam between two experts that have rows (c.launches); glu
-    through `rows`: each poisoned token has two slots in two different experts."""
-    assert not (block and (op == "glu" or use_rows)), "the GLU launch has no block form"
+    through `rows`: each poisoned token has two slots in two different experts.  block with "glu": the shapes of
+    flute_qgemm_grouped_glu_blocks (the same counts, F and K as the plain block variant of the configuration)."""
+    assert op == "glu" or not use_rows
     counts, K, N = _forward_shape(bits, tile_p, g, block)
+    assert not (block and op == "glu") or glu_blocks_eligible(bits, g, K, N)
     seed = XC.seed_of("forward nonfinite", op, bits, tile_p, g, dtype, use_rows, *_block_key(block))
     lseed = XC.seed_of("forward nonfinite layers", bits, tile_p, g, dtype, *_block_key(block))      # one stack for every op
     E = len(counts)
@@ -412,14 +448,19 @@ def forward_nonfinite_case(op, bits, tile_p, g, dtype, use_rows=False, block=Fal
         rows = torch.randint(0, Tsrc, (R,), generator=torch.Generator().manual_seed(seed + 2))
         rows[rows == t_nan] = 0
         rows[rows == t_inf] = 1
-        rows[15], rows[33] = t_nan, t_nan                   # the last row of expert 2, the first row of expert 5
-        rows[16], rows[65] = t_inf, t_inf                   # the first row of expert 3, the second row pass of expert 5
+        # token t_nan: the last row of expert 2 and the first row of the largest expert (across the empty one); token t_inf: the
+        # first row of expert 3 and a later row pass (block variant: the third row block) of the largest expert
+        a_rows, b_rows = ((127, 385), (128, 642)) if block else ((15, 33), (16, 65))
+        rows[list(a_rows)], rows[list(b_rows)] = t_nan, t_inf
         c.rows = rows
         c.X = (XC.make_x(Tsrc, K, seed + 1, dtype).double() * scale).to(dtype)
         c.launches = []
-        for name, (k_nan, k_inf) in (("first k-step", first), ("last group", last)):
-            poisons = [(r, None) for r in (15, 33)] + [(r, forward_inf_sign(c, r, k_inf)) for r in (16, 65)]
-            c.launches.append(types.SimpleNamespace(name=name, X=XC.poison_x(c.X, t_nan, t_inf, k_nan, k_inf), poisons=poisons))
+        # the block variant once more the other way round: the Inf in token t_nan reaches the last valid row of a ragged block
+        ways = ((t_nan, a_rows, t_inf, b_rows, ""),) + (((t_inf, b_rows, t_nan, a_rows, ", Inf in the last row"),) if block else ())
+        for tn, nan_rows, ti, inf_rows, tag in ways:
+            for name, (k_nan, k_inf) in (("first k-step", first), ("last group", last)):
+                poisons = [(r, None) for r in nan_rows] + [(r, forward_inf_sign(c, r, k_inf)) for r in inf_rows]
+                c.launches.append(types.SimpleNamespace(name=name + tag, X=XC.poison_x(c.X, tn, ti, k_nan, k_inf), poisons=poisons))
     else:
         c.X = (XC.make_x(R, K, seed + 1, dtype).double() * scale).to(dtype)
         c.launches = [types.SimpleNamespace(name=name, X=XC.poison_x(c.X, r_nan, r_inf, k_nan, k_inf),
@@ -1121,6 +1162,28 @@ def block_pushed_params():
 
 def block_forward_nonfinite_params():
     return [(op, b, p, g, dtype) for op, b, p, g, dtype, _ in forward_nonfinite_params() if b != 3 and op != "glu"]
+
+
+def w3_block_forward_range_params():
+    return [(op, kind, b, p, g) for op in ("plain", "weighted") for kind in RANGE_KINDS for b, p, g in W3_BLOCK_G_CASES
+            if g == 64 or kind == "subw"]
+
+
+def w3_block_pushed_params():
+    return [(b, p) for b, p, g in W3_BLOCK_G_CASES if g == 64]
+
+
+def w3_block_forward_nonfinite_params():
+    return [(op, b, p, g, dtype) for b, p, g in W3_BLOCK_G_CASES for dtype in (F16, BF16) for op in ("plain", "weighted")
+            if g == 64 or dtype == F16]
+
+
+def glu_block_saturation_params():
+    return [(b, p, 64, F16, use_rows) for b, p in BLOCK_CONFIGS for use_rows in (True, False)] + [(4, 32, 32, BF16, True)]
+
+
+def glu_block_nonfinite_params():
+    return [(b, p, g, dtype, use_rows) for op, b, p, g, dtype, use_rows in forward_nonfinite_params() if b != 3 and op == "glu"]
 
 
 def block_grad_range_params():

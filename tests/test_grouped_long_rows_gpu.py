@@ -10,9 +10,10 @@ expert), the GLU launch against the fp64 formula within grouped_cases.assert_glu
 launch on a compact copy of the rows it reads.  Every launch goes through the C ABI into a buffer guarded on both sides with
 the type's NaN bits and must leave the guards and its inputs as they were and every element it owes written.
 
-The second dimension is the smallest a layer of the layout has: N = F = 256 in the forward, and in the input gradient one
-column block of the layout (128 columns at 4 bits, 256 at 2 bits; a packed layer has no fewer).  4 bits, g = 64, TileP 32,
-fp16 unless a case says otherwise."""
+The second dimension is the smallest a layer of the layout has: N = F = 256 in the forward (3 bits: 512), and in the input
+gradient one column block of the layout (128 columns at 4 bits, 256 at 2 bits; a packed layer has no fewer).  4 bits, g = 64,
+TileP 32, fp16 unless a case says otherwise.  3 bits run the block form behind its own entries
+(flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks) at the same last T, and the row form of the old entries past it."""
 import pytest
 import torch
 
@@ -31,6 +32,8 @@ ERR_SHAPE = -4
 AUTO, ROWS, BLOCKS = 0, 1, 2                 # flute_grouped_form_t
 IG_AUTO, IG_SLABS, IG_BLOCKS = 0, 1, 2       # flute_grouped_input_grad_form_t
 N_FWD = 256
+N_W3 = 512                                   # 3 bits: one column block of the layout, a 3-bit layer has no narrower one
+W3_BLOCKS = "w3_blocks"                      # forward_launch: the 3-bit stacks' own entries (no trailing form)
 
 
 @pytest.fixture(scope="module")
@@ -90,13 +93,17 @@ def witnessed(env, st, X, T, off):
 # ---- 1 and 2: plain and weighted -------------------------------------------------------------------------------------------
 
 def forward_launch(env, st, X, T, off, rw, form, out):
-    """flute_qgemm_grouped_ex / _weighted_ex on X[:T] into `out`; returns the code."""
+    """flute_qgemm_grouped_ex / _weighted_ex on X[:T] into `out`, or (form W3_BLOCKS) flute_qgemm_grouped_w3_blocks /
+    _weighted_w3_blocks; returns the code."""
     offd = off_tensor(env, off)
     head = (dtype_id(st.dtype), st.bits, st.g, st.E, T, st.N, K, st.Q.shape[1], st.tid, X.data_ptr(), offd.data_ptr(),
             st.Q.data_ptr(), st.S.data_ptr(), st.t2.data_ptr())
     tail = (out.out.data_ptr(), env.num_sms, env.stream_ptr(env.dev), form)
     with torch.cuda.device(env.dev):
-        if rw is None:
+        if form == W3_BLOCKS:
+            rc = env.lib.flute_qgemm_grouped_w3_blocks(*head, *tail[:3]) if rw is None else \
+                env.lib.flute_qgemm_grouped_weighted_w3_blocks(*head, rw.data_ptr(), *tail[:3])
+        elif rw is None:
             rc = env.lib.flute_qgemm_grouped_ex(*head, *tail)
         else:
             rc = env.lib.flute_qgemm_grouped_weighted_ex(*head, rw.data_ptr(), *tail)
@@ -124,10 +131,10 @@ def forward_check(env, st, X, snap, T, off, rw, form, R, what):
     print("%s: exact" % (what,))
 
 
-def forward_case(env, bits, dtype, table, T, weighted):
+def forward_case(env, bits, dtype, table, T, weighted, N=N_FWD):
     counts = LC.TABLES[table](T)
     off = LC.served_offsets(counts)
-    st = stack(env, bits, N_FWD, dtype, len(counts))
+    st = stack(env, bits, N, dtype, len(counts))
     X, snap = activations(env, dtype)
     witnessed(env, st, X, T, off)
     rw = LC.device_row_weights(T, XC.seed_of("long rows rw", table, T)) if weighted else None
@@ -182,6 +189,70 @@ def test_row_form_past_the_edge(env, dtype, table, T):
         if weighted:
             short = LC.served_offsets(counts, T - 300)
             forward_check(env, st, X, snap, T, short, rw, ROWS, R, (mode, table, T, "offsets[E] = T - 300"))
+        del R
+
+
+# ---- 1 and 2 at 3 bits: the block form behind its own entries, the row form past its edge ------------------------------------------
+
+def w3_form(env, st, mode, T):
+    return env.dev_mod.grouped_w3_blocks_form(mode, st.E, T, st.N, K, st.g, st.tid, env.num_sms, st.dtype)
+
+
+@pytest.mark.parametrize("dtype,table", [(F16, "fat"), (F16, "spread"), (BF16, "spread")])
+def test_w3_block_form_at_the_last_t_it_admits(env, dtype, table):
+    """flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks at T = T_EDGE, N = 512: the activation rule of the 3-bit entries is the
+    4- / 2-bit block form's inequality, and their descriptor over an expert's rows is built from the same row range.  The old
+    entries' automatic rule says "rows" for 3 bits at every count; the 3-bit query says "blocks".  Weighted also with
+    offsets[E] = T - 300.  The stack's default scales keep the exactness premise (ExactStack asserts it: K 4 max|w| < 2^21)."""
+    need(40)
+    T = LC.T_EDGE
+    for weighted in (False, True):
+        st, X, snap, off, counts, rw, R, mode, auto = forward_case(env, 3, dtype, table, T, weighted, N_W3)
+        assert auto == "rows" and w3_form(env, st, mode, T) == "blocks"
+        forward_check(env, st, X, snap, T, off, rw, W3_BLOCKS, R, (mode, table, 3, str(dtype), T, "w3 blocks"))
+        if weighted:
+            short = LC.served_offsets(counts, T - 300)
+            assert short[-1] == T - 300
+            forward_check(env, st, X, snap, T, short, rw, W3_BLOCKS, R, (mode, table, 3, T, "offsets[E] = T - 300", "w3 blocks"))
+        del R
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
+def test_w3_entries_refuse_one_row_later(env, weighted):
+    """T = T_EDGE + 1: the 3-bit entries return FLUTE_ERR_SHAPE and write nothing; the Python ops raise before a launch."""
+    need(40)
+    T, dtype = LC.T_EDGE + 1, F16
+    counts = LC.spread_counts(T)
+    off = LC.served_offsets(counts)
+    st = stack(env, 3, N_W3, dtype, len(counts))
+    X, _ = activations(env, dtype)
+    rw = LC.device_row_weights(T, XC.seed_of("long rows rw", "spread", T)) if weighted else None
+    assert w3_form(env, st, "weighted" if weighted else "plain", T) == "rows"
+    out = LC.Guarded((T, st.N), dtype, env.dev)
+    assert forward_launch(env, st, X, T, off, rw, W3_BLOCKS, out) == ERR_SHAPE
+    out.assert_untouched()
+    del out
+    op = env.fa.qgemm_grouped_weighted_w3_blocks if weighted else env.fa.qgemm_grouped_w3_blocks
+    args = (X[:T], off_tensor(env, off), st.Q, st.S, st.t2) + ((rw,) if weighted else ())
+    with pytest.raises(ValueError):
+        op(*args, 3, st.g, st.tid, env.num_sms)
+
+
+def test_w3_row_form_past_the_edge(env):
+    """3 bits at R_LONG on the spread table, plain and weighted: the old entries, form rows and automatic (which is the row form
+    at 3 bits), behind 64-bit row bases; the last expert starts past 2^32.  This is what serves a 3-bit stack past T_EDGE."""
+    need(40)
+    T, dtype, table = LC.R_LONG, F16, "spread"
+    for weighted in (False, True):
+        st, X, snap, off, counts, rw, R, mode, auto = forward_case(env, 3, dtype, table, T, weighted, N_W3)
+        assert auto == "rows" and w3_form(env, st, mode, T) == "rows"
+        out = LC.Guarded((T, st.N), dtype, env.dev)
+        assert forward_launch(env, st, X, T, off, rw, BLOCKS, out) == ERR_SHAPE       # (3 bits have no block form behind _ex)
+        assert forward_launch(env, st, X, T, off, rw, W3_BLOCKS, out) == ERR_SHAPE
+        out.assert_untouched()
+        del out
+        for form in (AUTO, ROWS):
+            forward_check(env, st, X, snap, T, off, rw, form, R, (mode, table, 3, str(dtype), T, "form", form))
         del R
 
 

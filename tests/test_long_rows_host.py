@@ -101,6 +101,35 @@ def test_forward_forms_on_both_sides_of_t_edge(bits, dtype, mode):
     assert dev.grouped_form(name, 8, LC.T_EDGE + 1, N, K, bits, 64, tid, 256, dt) == "rows"
 
 
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("mode", [PLAIN, WEIGHTED])
+def test_w3_block_entries_on_both_sides_of_t_edge(dtype, mode):
+    """3 bits, N = 512 (a 3-bit layer has no narrower one): the activation rule of grouped_w3_blocks_eligible is the inequality of
+    the 4- / 2-bit block form, so T_EDGE is its last T too; the old entries serve every count on the row form and refuse blocks."""
+    lib, tid = _lib.get(), first_template(3, 32)
+    N = 512
+    P = 3 * N // 16
+    entry = lib.flute_qgemm_grouped_w3_blocks if mode == PLAIN else lib.flute_qgemm_grouped_weighted_w3_blocks
+    old = lib.flute_qgemm_grouped_ex if mode == PLAIN else lib.flute_qgemm_grouped_weighted_ex
+    nptr = 6 if mode == PLAIN else 7
+    name = {PLAIN: "plain", WEIGHTED: "weighted"}[mode]
+    dt = {0: LC.F16, 1: LC.BF16}[dtype]
+    for E in (3, 8):
+        asked = lambda T: entry(dtype, 3, 64, E, T, N, K, P, tid, *(None,) * nptr, 256, None)
+        forced = lambda T, f: old(dtype, 3, 64, E, T, N, K, P, tid, *(None,) * nptr, 256, None, f)
+        assert asked(LC.T_EDGE) == ERR_NULL
+        assert asked(LC.T_EDGE + 1) == ERR_SHAPE and asked(LC.R_LONG) == ERR_SHAPE
+        assert lib.flute_qgemm_grouped_w3_blocks_form(mode, dtype, 64, E, LC.T_EDGE, N, K, tid, 256) == BLOCKS
+        assert lib.flute_qgemm_grouped_w3_blocks_form(mode, dtype, 64, E, LC.T_EDGE + 1, N, K, tid, 256) == ROWS
+        assert dev.grouped_w3_blocks_form(name, E, LC.T_EDGE, N, K, 64, tid, 256, dt) == "blocks"
+        assert dev.grouped_w3_blocks_form(name, E, LC.T_EDGE + 1, N, K, 64, tid, 256, dt) == "rows"
+        assert dev.grouped_w3_blocks_form(name, E, LC.R_LONG, N, K, 64, tid, 256, dt) == "rows"
+        for T in (LC.T_EDGE, LC.T_EDGE + 1, LC.R_LONG):
+            assert lib.flute_qgemm_grouped_form(mode, dtype, 3, 64, E, T, N, K, tid, 256) == ROWS
+            assert forced(T, ROWS) == ERR_NULL and forced(T, AUTO) == ERR_NULL and forced(T, BLOCKS) == ERR_SHAPE
+            assert dev.grouped_form(name, E, T, N, K, 3, 64, tid, 256, dt) == "rows"
+
+
 @pytest.mark.parametrize("bits,dtype", SHAPES)
 def test_glu_blocks_on_both_sides_of_tsrc_edge(bits, dtype):
     lib, tid = _lib.get(), first_template(bits, 32)

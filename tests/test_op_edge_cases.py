@@ -190,6 +190,148 @@ def test_block_forward_nonfinite_rule(op, bits, tile_p, g, dtype):
             assert torch.isinf(exp[r_inf]).any(), "the Inf row shows infinities"
 
 
+# ---- the block forms behind entries of their own: 3 bits, the fused SwiGLU launch ---------------------------------------------
+
+def served_by_the_w3_entries(c):
+    """include/flute_amd.h, flute_qgemm_grouped_w3_blocks: 3 bits (TileP 32), (K / group_size) % 8 == 0, N a multiple of 256;
+    and the layer itself is legal - N whole column blocks of the 3-bit layout, 512 columns."""
+    assert (c.bits, c.tile_p) == (3, 32) and c.N % XC.cols_per_block(3, 32) == 0 and c.K % max(64, c.g) == 0
+    assert c.counts == OE.grad_counts() and c.block and c.N == 512
+    assert c.N % 256 == 0 and c.K % c.g == 0 and (c.K // c.g) % 8 == 0, (c.K, c.N, c.g)
+    assert OE.w3_blocks_eligible(c.bits, c.g, c.K, c.N) and not OE.forward_blocks_eligible(c.bits, c.g, c.K, c.N)
+    return True
+
+
+def test_w3_and_glu_block_shapes_are_what_their_entries_serve():
+    assert sum(OE.grad_counts()) == 649
+    for op, kind, b, p, g in OE.w3_block_forward_range_params():
+        c = OE.forward_range_case(op, kind, b, p, g, block=True)
+        assert served_by_the_w3_entries(c) and c.K == (XC.OVERFLOW_K if kind == "overflow" else 8 * g)
+    for b, p in OE.w3_block_pushed_params():
+        assert served_by_the_w3_entries(OE.weighted_pushed_case(b, p, block=True))
+    for op, b, p, g, dtype in OE.w3_block_forward_nonfinite_params():
+        c = OE.forward_nonfinite_case(op, b, p, g, dtype, block=True)
+        assert served_by_the_w3_entries(c) and c.K == 8 * g
+    assert {p[:2] + p[4:] for p in OE.w3_block_forward_range_params()} == \
+        {(op, kind, g) for op in ("plain", "weighted") for kind in OE.RANGE_KINDS for g in (64, 32) if g == 64 or kind == "subw"}
+    assert OE.w3_block_pushed_params() == [(3, 32)]
+    assert {(p[0],) + p[3:] for p in OE.w3_block_forward_nonfinite_params()} == \
+        {(op, g, dtype) for op in ("plain", "weighted") for g, dtype in ((64, F16), (64, BF16), (32, F16))}
+    # the SwiGLU block launch: 4 / 2 bits, F a multiple of 256 and whole column blocks, eight groups; the BLOCK_CONFIGS, with a row
+    # index and without
+    want = {(4, 32, 64), (2, 32, 64), (4, 64, 64), (2, 64, 64)}
+    for b, p, g, dtype, use_rows in OE.glu_block_saturation_params():
+        c = OE.glu_saturation_case(b, p, g, dtype, use_rows, block=True)
+        assert c.block and c.counts == OE.grad_counts() and (c.K, c.N) == (8 * g, max(256, XC.cols_per_block(b, p)))
+        assert OE.glu_blocks_eligible(b, g, c.K, c.N) and c.N % XC.cols_per_block(b, p) == 0 and (c.rows is not None) == use_rows
+    assert {p[:3] for p in OE.glu_block_saturation_params() if p[3] == F16} == want
+    assert {(p[:2], p[4]) for p in OE.glu_block_saturation_params()} >= {(c, u) for c in OE.BLOCK_CONFIGS for u in (True, False)}
+    for b, p, g, dtype, use_rows in OE.glu_block_nonfinite_params():
+        c = OE.forward_nonfinite_case("glu", b, p, g, dtype, use_rows, block=True)
+        assert c.block and c.counts == OE.grad_counts() and (c.K, c.N) == (8 * g, max(256, XC.cols_per_block(b, p)))
+        assert OE.glu_blocks_eligible(b, g, c.K, c.N) and (c.rows is not None) == use_rows
+    assert {p[:3] for p in OE.glu_block_nonfinite_params() if p[3] == BF16} == want
+    assert {p[:3] for p in OE.glu_block_nonfinite_params() if p[3] == F16} == want | {(4, 32, 32)}
+    assert {p[4] for p in OE.glu_block_nonfinite_params()} == {True, False}
+    # the row-form cases stay off these entries
+    assert not OE.w3_blocks_eligible(3, 64, OE.K_EDGE, 3 * 512) and not OE.glu_blocks_eligible(4, 64, OE.K_EDGE, 3 * 128)
+
+
+@pytest.mark.parametrize("op,kind,bits,tile_p,g", OE.w3_block_forward_range_params())
+def test_w3_block_forward_range_premises(op, kind, bits, tile_p, g):
+    c = OE.forward_range_case(op, kind, bits, tile_p, g, block=True)
+    check_forward_range_premises(c, kind)
+    off = OE.offsets_list(c.counts)
+    if op == "weighted":                                     # the zero weight sits on a row of the largest expert
+        assert float(c.rw[off[6] + 3]) == 0 and not c.R[off[6] + 3].any()
+    if kind == "overflow":                                   # every expert with three rows or more overflows both ways
+        for e, n in enumerate(c.counts):
+            if n >= 3 and op == "plain":
+                assert OE.has_both_infs(c.R[off[e]:off[e + 1]], c.dtype), e
+
+
+@pytest.mark.parametrize("bits,tile_p", OE.w3_block_pushed_params())
+def test_w3_block_weighted_pushed_premises(bits, tile_p):
+    c = OE.weighted_pushed_case(bits, tile_p, block=True)
+    Rt = c.R.to(c.dtype)
+    assert (Rt[c.a] == OE.INF).any() and torch.isfinite(Rt[c.a]).any() and float(c.rw[c.a]) == -float(c.rw[c.b])
+    assert OE.expert_of_row(c.counts, c.a) == OE.expert_of_row(c.counts, c.b) == 6
+    rest = torch.ones(Rt.shape[0], dtype=torch.bool)
+    rest[[c.a, c.b]] = False
+    assert torch.isfinite(Rt[rest]).all() and not XC.exact_equal(Rt, c.R.clamp(-XC.FP16_MAX, XC.FP16_MAX), c.dtype)
+    # the key the other cases share does not give the case: that is why this one has its own
+    with pytest.raises(AssertionError):
+        OE._weighted_pushed_case(bits, tile_p, 64, True, XC.seed_of("pushed", bits, tile_p, 64, *OE._block_key(True)))
+
+
+def check_block_forward_nonfinite_rule(c, op):
+    clean = OE.forward_ieee(c, c.X)
+    assert torch.isfinite(clean).all()
+    if op == "weighted":
+        assert not clean[OE.BLOCK_ZERO_WEIGHT_ROW].any()
+    check_block_places(c, [(la.name, la.poisons[0][0], la.poisons[1][0]) for la in c.launches])
+    for la in c.launches:
+        exp = OE.rowwise_expected(clean, la.poisons)
+        assert XC.nonfinite_equal(OE.forward_ieee(c, la.X), exp), la.name
+        (r_nan, s_nan), (r_inf, s_inf) = la.poisons
+        assert s_nan is None and torch.isnan(exp[r_nan]).all()
+        if op == "weighted" and float(c.rw[r_inf]) == 0:
+            assert torch.isnan(exp[r_inf]).all()             # zero times Inf
+        else:
+            assert torch.isinf(exp[r_inf]).any(), "the Inf row shows infinities"
+    return clean
+
+
+@pytest.mark.parametrize("op,bits,tile_p,g,dtype", OE.w3_block_forward_nonfinite_params())
+def test_w3_block_forward_nonfinite_rule(op, bits, tile_p, g, dtype):
+    c = OE.forward_nonfinite_case(op, bits, tile_p, g, dtype, block=True)
+    check_block_forward_nonfinite_rule(c, op)
+    if op == "weighted":                                     # an Inf row meets a negative, a zero and a small positive row weight
+        signs = {float(torch.sign(c.rw[la.poisons[1][0]])) for la in c.launches}
+        assert signs == {-1.0, 0.0, 1.0}
+
+
+@pytest.mark.parametrize("bits,tile_p,g,dtype,use_rows", OE.glu_block_saturation_params())
+def test_glu_block_saturation_premises(bits, tile_p, g, dtype, use_rows):
+    c = OE.glu_saturation_case(bits, tile_p, g, dtype, use_rows, block=True)
+    assert c.sign_k in OE.GLU_SIGN_KS
+    # the band -90 < g < -88 that the GPU test leaves out: at most 2 % of the reference's own g, and nothing else is left out
+    band = (c.G > OE.GLU_LO) & (c.G < OE.GLU_MID_LO)
+    assert torch.equal(band, c.out) and torch.equal(~band, c.hi | c.lo | c.mid) and float(band.double().mean()) <= 0.02
+    assert int((c.G > 89).sum()) >= 64
+    E = c.Eref
+    assert float(((E - c.P)[c.hi].abs() / c.P[c.hi].abs().clamp(min=1)).max()) < 2.0 ** -24
+    assert float(E[c.lo].abs().max()) < 2.0 ** -100
+    # every class on both sides of a 128-row block edge of the largest expert, and the sign rows at the seams
+    off = OE.offsets_list(c.counts)
+    for r0, r1 in ((off[6], off[6] + 128), (off[6] + 128, off[7])):
+        assert c.hi[r0:r1].any() and c.lo[r0:r1].any() and c.mid[r0:r1].any()
+    assert float(c.G[off[3]].abs().max()) >= 200 and float(c.G[off[6]].abs().max()) >= 200
+
+
+@pytest.mark.parametrize("bits,tile_p,g,dtype,use_rows", OE.glu_block_nonfinite_params())
+def test_glu_block_nonfinite_rule(bits, tile_p, g, dtype, use_rows):
+    c = OE.forward_nonfinite_case("glu", bits, tile_p, g, dtype, use_rows, block=True)
+    if not use_rows:
+        check_block_forward_nonfinite_rule(c, "glu")
+        return
+    clean = OE.forward_ieee(c, c.X)
+    assert torch.isfinite(clean).all()
+    off = OE.offsets_list(c.counts)
+    for t in (7, 22):                                        # each poisoned token: two slots in two different experts
+        assert len({OE.expert_of_row(c.counts, r) for r in (c.rows == t).nonzero().reshape(-1).tolist()}) == 2
+    assert sorted((c.rows == 7).nonzero().reshape(-1).tolist()) == [off[3] - 1, off[6]]
+    assert sorted((c.rows == 22).nonzero().reshape(-1).tolist()) == [off[3], off[6] + 2 * OE.ROW_BLOCK + 1]
+    assert len(c.launches) == 4
+    for i, la in enumerate(c.launches):
+        exp = OE.rowwise_expected(clean, la.poisons)
+        assert XC.nonfinite_equal(OE.forward_ieee(c, la.X), exp), la.name
+        inf_rows = [r for r, s in la.poisons if s is not None]
+        assert (off[3] - 1 in inf_rows) == (i >= 2)          # the last two launches: the Inf in the last valid row of a ragged block
+        for r in inf_rows:
+            assert torch.isinf(exp[r]).any() and torch.isnan(exp[r]).any(), "g = +inf: +-inf by u; g = -inf: NaN"
+
+
 @pytest.mark.parametrize("form,kind,bits,tile_p,g", OE.grad_range_params())
 def test_grad_range_premises(form, kind, bits, tile_p, g):
     c = OE.grad_range_case(form, kind, bits, tile_p, g)

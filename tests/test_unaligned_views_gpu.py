@@ -170,6 +170,38 @@ def test_grouped_glu_and_weighted(case):
         input, offsets, weight, scales, table2, row_weight, *lay), weighted, tuple(weighted))
 
 
+W3_K, W3_N, W3_COUNTS = 512, 512, (5, 0, 140)      # a small 3-bit stack: eight groups of 64, one column block, a second row block
+
+
+def test_grouped_w3_blocks(case):
+    """The 3-bit block form behind its own ops: `input` and `row_weight` misaligned."""
+    from flute_amd import utils
+    c, fa, d = case, case["fa"], case["d"]
+    tid = min(t for (b, t), cfg in fa.TEMPLATE_CONFIGS.items() if b == 3 and cfg["TileP"] == 32)
+    lays = [E.Layer(3, W3_K, W3_N, G, c["T"], 190 + e) for e in range(len(W3_COUNTS))]
+    Q = torch.stack([utils.pack(l.W.to(d), 3, [tid], c["num_sms"]) for l in lays])
+    S, t2 = torch.stack([l.S for l in lays]).to(d), torch.stack([l.table2 for l in lays]).to(d)
+    R = sum(W3_COUNTS)
+    gen = torch.Generator().manual_seed(17)
+    X = torch.randint(-4, 5, (R, W3_K), generator=gen).to(c["T"]).to(d)
+    off = torch.tensor([0, 5, 5, R], dtype=torch.int32, device=d)
+    check(lambda input: fa.qgemm_grouped_w3_blocks(input, off, Q, S, t2, 3, G, tid), dict(input=X), ("input",))
+    weighted = dict(input=X, row_weight=torch.rand(R, generator=gen).to(d))
+    check(lambda input, row_weight: fa.qgemm_grouped_weighted_w3_blocks(input, off, Q, S, t2, row_weight, 3, G, tid),
+          weighted, tuple(weighted))
+
+
+def test_grouped_glu_blocks(case):
+    """The block form of the fused SwiGLU launch (4 bits): `input` and `rows` misaligned."""
+    c = case
+    fa, lay = c["fa"], (BITS, G, c["tid"])
+    R = sum(COUNTS)
+    glu = dict(input=c["X"], rows=torch.randint(0, R, (R,), generator=torch.Generator().manual_seed(19)).to(torch.int32).to(c["d"]))
+    up = (c["Q"].flip(0).contiguous(), c["S"].flip(0).contiguous(), c["t2"].flip(0).contiguous())
+    check(lambda input, rows: fa.qgemm_grouped_glu_blocks(input, c["off"], c["Q"], c["S"], c["t2"], *up, *lay, rows=rows),
+          glu, tuple(glu))
+
+
 @pytest.mark.parametrize("id_dtype", [torch.int32, torch.int64], ids=["i32", "i64"])
 def test_moe_route_and_wide(case, routed, id_dtype):
     fa = case["fa"]
