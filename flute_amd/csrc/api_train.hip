@@ -1,5 +1,5 @@
 // Host side of the C ABI, the training and grouped entry points: the dense and grouped parameter gradients with their scratch
-// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient.  Of the
+// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient (slabs, blocks, 3-bit blocks).  Of the
 // planner they need the layer check alone (host.h).  No device code.
 #include <algorithm>
 
@@ -191,6 +191,51 @@ static int grouped_input_grad_form_auto(int num_bits, int E, int R, int N, int K
     return (long long)R >= mean * E ? FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS : FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
 }
 
+// flute_qgemm_grouped_input_grad_ex (w3_blocks false: `form` resolved through the two-form rule, the unit by the dispatch) and
+// flute_qgemm_grouped_input_grad_w3_blocks (true: `form` ignored; 3 bits and grouped_input_grad_w3_blocks_eligible, the 3-bit block unit)
+// behind their signatures: one sequence of refusals, the empty launches, the null pointers, the operands by name.  The 3-bit query's
+// thresholds are grouped_input_grad_form_auto's rule (min_mean_rows: the split by E * (K / 256) against num_sms) on constants of their
+// own, FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS / _PARTIAL = 8 / 128: each the smallest swept mean from which the block launch
+// is faster than the slab form in every alternation on every swept stack of its kind.  The sweep
+// (profiles/grouped_moe_input_grad_blocks_w3.json, "w3 threshold sweep": W3G64 fp16, us of slabs / block launch at even counts,
+// R / E = 8, 16, 32, 48, 64, 96, 128, 192, 256): Mixtral down (E 8, N 4096, K 14336: 448 workgroups per row block) 263 / 172,
+// 266 / 180, 298 / 190, 360 / 209, 407 / 224, 503 / 274, 692 / 278, 1064 / 451, 1300 / 542; E 64 2048 x 2048 (512) 135 / 90, 137 / 92,
+// 155 / 101, 188 / 109, 215 / 124, 263 / 159, 358 / 221, 547 / 286, 712 / 376; Mixtral gate / up (E 8, N 14336, K 4096: 128
+// workgroups, does not fill the chip) 224 / 290, 227 / 299, 256 / 311, 322 / 341, 356 / 371, 439 / 464, 607 / 465, 939 / 424,
+// 1166 / 468.  (8 is the sweep's lowest mean: where the chip is full the 3-bit slab form never led.)
+static int grouped_input_grad(bool w3_blocks, int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                              int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                              const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                              const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form) {
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
+    if (rc) return rc;
+    const bool pair = dY2 || Q2 || S2 || QM22;
+    if (pair && row_weight) return FLUTE_ERR_SHAPE;               // the pair form takes no row weight
+    int f = form;
+    if (w3_blocks) {
+        if (num_bits != 3) return FLUTE_ERR_NUM_BITS;
+        if (!grouped_input_grad_w3_blocks_eligible(E, R, N, K)) return FLUTE_ERR_SHAPE;
+        f = FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS;
+    } else if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_AUTO) f = grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
+    else if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS ? !grouped_input_grad_blocks_eligible(num_bits, E, R, N, K)
+                                                       : f != FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS)
+        return FLUTE_ERR_SHAPE;                                    // an unknown form, or blocks forced where they do not serve
+    if (R == 0) return FLUTE_OK;
+    if (!dX) return FLUTE_ERR_NULL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (E == 0)                                                    // no expert serves any row: zeros, as the kernel writes them
+        return hipMemsetAsync(dX, 0, (size_t)R * (size_t)K * 2, st) == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
+    if (!dY || !offsets || !Q || !S || !QM2 || (pair && (!dY2 || !Q2 || !S2 || !QM22))) return FLUTE_ERR_NULL;
+    GroupedInputGrad g{};                                          // (either grid follows from the shapes alone)
+    g.form = f; g.dtype = dtype; g.num_bits = num_bits; g.tile_p = l.t.tile_p; g.lg = l.lg;
+    g.E = E; g.R = R; g.N = N; g.K = K; g.P = P; g.pair = pair;
+    g.dY[0] = dY; g.Q[0] = Q; g.S[0] = S; g.QM2[0] = QM2;
+    g.dY[1] = pair ? dY2 : dY; g.Q[1] = pair ? Q2 : Q; g.S[1] = pair ? S2 : S; g.QM2[1] = pair ? QM22 : QM2;
+    g.offsets = offsets; g.row_weight = row_weight; g.dX = dX;
+    return w3_blocks ? qgemm_grouped_input_grad_blocks_unit_b3(g, st) : qgemm_grouped_input_grad_dispatch(g, st);
+}
+
 // flute_qgemm_grouped_scale_grad (table false: S, dT2 and the scratch null) and _table_grad behind their signatures.  The refusals after
 // check_grouped: the layout, and the kernel's limits - the workgroup's block is 128 n, the grid's z (the reduce's y) is the expert, a row
 // index plus one 32-row step stays an int.  (num_sms plays no part: the grid is (N / 128, ceil(K / 256), E), from the shapes alone.)
@@ -376,29 +421,28 @@ int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, i
                                       int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
                                       const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
                                       const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form) {
+    return grouped_input_grad(false, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
+                              Q2, S2, QM22, dX, num_sms, stream, form);
+}
+
+int flute_qgemm_grouped_input_grad_w3_blocks(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                             int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                             const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                             const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+    return grouped_input_grad(true, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
+                              Q2, S2, QM22, dX, num_sms, stream, FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS);
+}
+
+int flute_qgemm_grouped_input_grad_w3_blocks_form(int pair, int dtype, int group_size, int E, int R, int N, int K, int template_id,
+                                                  int num_sms) {
+    (void)pair;                                                    // the pair form is eligible where the single form is
     Layer l;
-    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, P, &l);
+    const int rc = check_grouped(dtype, 3, group_size, template_id, E, R, N, K, 3 * (N / 16), &l);
     if (rc) return rc;
-    const bool pair = dY2 || Q2 || S2 || QM22;
-    if (pair && row_weight) return FLUTE_ERR_SHAPE;               // the pair form takes no row weight
-    int f = form;
-    if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_AUTO) f = grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
-    else if (f == FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS ? !grouped_input_grad_blocks_eligible(num_bits, E, R, N, K)
-                                                       : f != FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS)
-        return FLUTE_ERR_SHAPE;                                    // an unknown form, or blocks forced where they do not serve
-    if (R == 0) return FLUTE_OK;
-    if (!dX) return FLUTE_ERR_NULL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (E == 0)                                                    // no expert serves any row: zeros, as the kernel writes them
-        return hipMemsetAsync(dX, 0, (size_t)R * (size_t)K * 2, st) == hipSuccess ? FLUTE_OK : FLUTE_ERR_LAUNCH;
-    if (!dY || !offsets || !Q || !S || !QM2 || (pair && (!dY2 || !Q2 || !S2 || !QM22))) return FLUTE_ERR_NULL;
-    GroupedInputGrad g{};                                          // (either grid follows from the shapes alone)
-    g.form = f; g.dtype = dtype; g.num_bits = num_bits; g.tile_p = l.t.tile_p; g.lg = l.lg;
-    g.E = E; g.R = R; g.N = N; g.K = K; g.P = P; g.pair = pair;
-    g.dY[0] = dY; g.Q[0] = Q; g.S[0] = S; g.QM2[0] = QM2;
-    g.dY[1] = pair ? dY2 : dY; g.Q[1] = pair ? Q2 : Q; g.S[1] = pair ? S2 : S; g.QM2[1] = pair ? QM22 : QM2;
-    g.offsets = offsets; g.row_weight = row_weight; g.dX = dX;
-    return qgemm_grouped_input_grad_dispatch(g, st);
+    if (E < 1 || R < 1 || !grouped_input_grad_w3_blocks_eligible(E, R, N, K)) return FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
+    const long long mean = min_mean_rows(K / kGroupedIgBlockK, E, num_sms, FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS,
+                                         FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL);
+    return (long long)R >= mean * E ? FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS : FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
 }
 
 int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,

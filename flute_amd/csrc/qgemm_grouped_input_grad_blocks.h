@@ -1,7 +1,7 @@
 // The block form of the grouped input gradient: what qgemm_grouped_input_grad.h (the slab form) computes - same operands,
 // same arithmetic, same bits - for experts with hundreds of rows, where the slab form's (expert, 128 k) workgroups read the
-// expert's dY once per slab as 8-byte per-lane requests and feed 8 MFMAs from 8 transposed reads.  4 and 2 bits; 3 bits stay
-// on the slab form (the decoder below would hold three planes of two octets in registers, and nothing asks for it).
+// expert's dY once per slab as 8-byte per-lane requests and feed 8 MFMAs from 8 transposed reads.  4 and 2 bits; 3 bits have
+// a kernel of their own on this work split (qgemm_grouped_input_grad_w3_blocks.h: the decoder below would hold three planes of two octets).
 //
 // Work split.  A workgroup of 8 waves owns one 128-row block of one expert x one block of 256 k and walks all of N once, in
 // the slab form's chunks of 64 columns (pair form: the first stack, then the second, into the same fp32 accumulators).  The
@@ -59,7 +59,7 @@ static_assert(kIgbKB == kGroupedIgBlockK, "grouped_input_grad_blocks_eligible (g
 template <typename T, int BITS, int TILEP, bool PAIR>
 __global__ __launch_bounds__(kIgThreads) void qgemm_grouped_input_grad_blocks_kernel(const GroupedIgArgs a) {
     using L = Layout<BITS>;
-    static_assert(BITS == 4 || BITS == 2, "3 bits stay on the slab form");
+    static_assert(BITS == 4 || BITS == 2, "3 bits: qgemm_grouped_input_grad_w3_blocks.h");
     constexpr int J = L::J;
     constexpr int NP = L::NPLANES;                                 // 1
     constexpr int UC = kIgNC / J;                                  // units per chunk: 16 / 8

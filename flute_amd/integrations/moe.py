@@ -18,7 +18,9 @@ for the unfused gate, up and down launches and the fused path's weighted down la
 form and stays on its row form.  The
 backward's two input-gradient launches have their own pair of forms - slabs and, for 4- / 2-bit stacks with K % 256 == 0 from a
 mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input_grad_blocks.h;
-`flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.
+`flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.  At 3 bits the block form of the
+input gradient is again an op of its own, `flute_amd.qgemm_grouped_input_grad_w3_blocks` (the same bits as the slab form), and
+`FluteExperts(w3_grad_blocks=...)` opts the backward in (`flute_amd.dev.grouped_input_grad_w3_blocks_form` is its "auto").
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
 its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
 `native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`
@@ -278,6 +280,10 @@ class FluteExperts(torch.nn.Module):
     today's forward bit for bit); True: `qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` (raises where a stack is not
     3-bit, not eligible or learnable); "auto": those where `flute_amd.dev.grouped_w3_blocks_form` takes them for the step's T k
     rows.  The fused GLU launch stays on its row form at 3 bits.
+    `w3_grad_blocks` (stacks of 3-bit experts): the ops' keyword of that name - which kernel runs the input-gradient launches of the
+    backward - False: `qgemm_grouped_input_grad`, the slab form at 3 bits (the default); True: `qgemm_grouped_input_grad_w3_blocks`
+    (raises where a stack is not 3-bit, has K % 256 != 0 or is learnable); "auto": that launch where
+    `flute_amd.dev.grouped_input_grad_w3_blocks_form` takes it for the step's T k rows.  Every gradient has the same bits either way.
     `native_glu_grad` (with `fused=True`): the ops' keyword of that name - the backward of the fused GLU launch gathers its rows
     with `moe_gather` and forms dg, du with `swiglu_grad` (two HIP launches) where the default runs torch ops; the forward's bits
     are the same either way, the backward's differ within `flute_swiglu_grad`'s error account.
@@ -293,12 +299,16 @@ class FluteExperts(torch.nn.Module):
     def __init__(self, gate: GroupedFluteLinear, up: GroupedFluteLinear, down: GroupedFluteLinear,
                  fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
                  native_glu_grad: bool = False, native_router_grad: bool = False,
-                 wide_routing: Union[bool, str] = False, w3_blocks: Union[bool, str] = False) -> None:
+                 wide_routing: Union[bool, str] = False, w3_blocks: Union[bool, str] = False,
+                 w3_grad_blocks: Union[bool, str] = False) -> None:
         super().__init__()
         _check_tristate("glu_blocks", glu_blocks)
         _check_tristate("w3_blocks", w3_blocks)
+        _check_tristate("w3_grad_blocks", w3_grad_blocks)
         if w3_blocks is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
             raise ValueError("FluteExperts: w3_blocks selects the kernels of 3-bit stacks; gate, up and down must be 3-bit")
+        if w3_grad_blocks is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
+            raise ValueError("FluteExperts: w3_grad_blocks selects the backward's kernels of 3-bit stacks; gate, up and down must be 3-bit")
         if glu_blocks is not False and not fused:
             raise ValueError("FluteExperts: glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
         _check_tristate("wide_routing", wide_routing)
@@ -326,17 +336,18 @@ class FluteExperts(torch.nn.Module):
         self.native_router_grad = bool(native_router_grad)
         self.wide_routing = wide_routing
         self.w3_blocks = w3_blocks
+        self.w3_grad_blocks = w3_grad_blocks
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
                      glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
                      native_router_grad: bool = False, wide_routing: Union[bool, str] = False,
-                     w3_blocks: Union[bool, str] = False) -> "FluteExperts":
+                     w3_blocks: Union[bool, str] = False, w3_grad_blocks: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
                    native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing,
-                   w3_blocks=w3_blocks)
+                   w3_blocks=w3_blocks, w3_grad_blocks=w3_grad_blocks)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -461,13 +472,27 @@ class FluteExperts(torch.nn.Module):
         return flute_amd.dev.grouped_w3_blocks_form(mode, self.num_experts, rows, stack.out_features, stack.in_features,
                                                     stack.group_size, stack.template_id, num_sms, dtype) == "blocks"
 
+    def _w3_grad_blocks(self, *stacks):
+        """The ops' `w3_grad_blocks` for a launch over `stacks`: the module's.  The learnable stacks' entries have no such keyword: True
+        raises on them, "auto" leaves their backward as it is."""
+        if self.w3_grad_blocks is not False and any(isinstance(m, LearnableGroupedFluteLinear) for m in stacks):
+            if self.w3_grad_blocks is True:
+                raise ValueError("FluteExperts: w3_grad_blocks=True, but a stack is learnable (freeze_experts first, or "
+                                 "w3_grad_blocks='auto')")
+            return False
+        return self.w3_grad_blocks
+
     def _plain(self, stack, x_sorted, offsets):
-        """One plain launch of the unfused forward: the stack's own forward, or with `w3_blocks` taken its 3-bit block op."""
+        """One plain launch of the unfused forward: the stack's own forward, or with `w3_blocks` taken its 3-bit block op; with
+        `w3_grad_blocks` the public op of either with that keyword."""
         num_sms = _stack_num_sms(stack, x_sorted.device)
-        if not self._takes_w3_blocks(stack, "plain", x_sorted.shape[0], num_sms, x_sorted.dtype):
+        grad_blocks = self._w3_grad_blocks(stack)
+        w3 = self._takes_w3_blocks(stack, "plain", x_sorted.shape[0], num_sms, x_sorted.dtype)
+        if not w3 and grad_blocks is False:
             return stack(x_sorted, offsets)
-        return flute_amd.qgemm_grouped_w3_blocks(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits,
-                                                 stack.group_size, stack.template_id, num_sms)
+        op = flute_amd.qgemm_grouped_w3_blocks if w3 else flute_amd.qgemm_grouped
+        return op(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits, stack.group_size,
+                  stack.template_id, num_sms, w3_grad_blocks=grad_blocks)
 
     def _fused_ops(self, glu_blocks: bool = False, w3_down: bool = False):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
@@ -475,7 +500,8 @@ class FluteExperts(torch.nn.Module):
         `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
         `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`).
         `w3_down`: the weighted launch on the 3-bit block form (`qgemm_grouped_weighted_w3_blocks`).
-        The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one."""
+        The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one, its
+        `w3_grad_blocks` on the public ops of both (the learnable entries have no such keyword)."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
         if has[0] != has[1]:
@@ -493,6 +519,9 @@ class FluteExperts(torch.nn.Module):
             weighted = flute_amd.qgemm_grouped_weighted_w3_blocks
         if self.native_router_grad:
             weighted = functools.partial(weighted, native_router_grad=True)
+        if self._w3_grad_blocks(gate, up, down) is not False:   # (no stack is learnable: both are public ops)
+            glu = functools.partial(glu, w3_grad_blocks=self.w3_grad_blocks)
+            weighted = functools.partial(weighted, w3_grad_blocks=self.w3_grad_blocks)
         return glu, weighted
 
     def _forward_native(self, hidden, topk_ids, topk_weights):

@@ -455,7 +455,7 @@ def _launch_plain(input, offsets, weight, scales, table2, layer, form=None):
 # `_launch_glu`'s form for the block launch behind its own entry (flute_qgemm_grouped_glu_blocks): not one of `_GROUPED_FORMS`,
 # which keep their meaning on `qgemm_grouped_glu` ("blocks" raises there)
 _GLU_BLOCKS = "glu_blocks"
-_FLUTE_ERR_SHAPE, _FLUTE_ERR_NULL = -4, -9       # include/flute_amd.h
+_FLUTE_ERR_NUM_BITS, _FLUTE_ERR_SHAPE, _FLUTE_ERR_NULL = -1, -4, -9       # include/flute_amd.h
 
 
 def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form=None):
@@ -512,7 +512,7 @@ def _require_w3_blocks(name, input, weight, scales, layer):
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                   table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                  form=None) -> torch.Tensor:
+                  form=None, w3_grad_blocks=False) -> torch.Tensor:
     """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
     r in [offsets[e], offsets[e + 1]).  `input` [T, K] holds the rows sorted by expert, `offsets` is an int32 CUDA tensor
     of E + 1 elements (0, non-decreasing, T last), `weight` [E, P, K], `scales` [E, N, K / g] and `table2`
@@ -524,31 +524,37 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     `form`: None - the library chooses from the shapes alone (`flute_amd.dev.grouped_form`): the row form (qgemm_grouped.h) for
     decode-sized row counts, the block form (qgemm_grouped_blocks.h: 128-row blocks of the dense prefill kernel) from a mean of
     32 rows per expert on (64 where the experts' column blocks do not fill the chip) where the layer is eligible for it;
-    "rows" / "blocks" force one (forcing blocks on a layer that is not eligible raises).  In the block form a malformed table may also leave rows it does name unwritten."""
+    "rows" / "blocks" force one (forcing blocks on a layer that is not eligible raises).  In the block form a malformed table may also leave rows it does name unwritten.
+    `w3_grad_blocks` (3-bit stacks only) is read by the backward only: False (the default) - dX is `qgemm_grouped_input_grad`, the slab
+    form at 3 bits; True - `qgemm_grouped_input_grad_w3_blocks` (raises where K % 256 != 0); "auto" - that launch where
+    `flute_amd.dev.grouped_input_grad_w3_blocks_form` says "blocks".  The bits of dX are the same in all three."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
     _grouped_form_id(form)
+    _check_w3_grad_blocks("qgemm_grouped", w3_grad_blocks, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form, w3_grad_blocks)
     return _launch_plain(input, offsets, weight, scales, table2, layer, form)
 
 
 def qgemm_grouped_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
-                            table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None) -> torch.Tensor:
+                            table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                            w3_grad_blocks=False) -> torch.Tensor:
     """`qgemm_grouped` for stacks of 3-bit experts on the block form, for prefill and training row counts: the same operands,
     formula and rounding (include/flute_amd.h, flute_qgemm_grouped_w3_blocks) on 128-row x 256-column blocks of the dense 3-bit
     prefill kernel - all of K in one fp32 accumulator of the matrix core, a weight dequantised once per 128 rows (qgemm_block3.h,
     GM = 1).  Same validation, same autograd (the backward's kernels do not depend on which kernel ran the forward; the 3-bit
-    input gradient stays on the slab form).  Equal arguments give equal bits; the bits equal `qgemm_grouped`'s on exactly
+    input gradient is the slab form unless `w3_grad_blocks`, as `qgemm_grouped`'s, says otherwise).  Equal arguments give equal bits; the bits equal `qgemm_grouped`'s on exactly
     representable inputs and may differ elsewhere.  A layer the form does not serve raises ValueError before anything is launched;
     `flute_amd.dev.grouped_w3_blocks_form` tells where the form pays."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
     layer = (num_bits, group_size, template_id, num_sms)
     _require_w3_blocks("qgemm_grouped_w3_blocks", input, weight, scales, layer)
+    _check_w3_grad_blocks("qgemm_grouped_w3_blocks", w3_grad_blocks, num_bits)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped_w3_blocks", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, _W3_BLOCKS)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, _W3_BLOCKS, w3_grad_blocks)
     return _launch_plain(input, offsets, weight, scales, table2, layer, _W3_BLOCKS)
 
 
@@ -560,7 +566,8 @@ class _GroupedFunction(torch.autograd.Function):
     backward's parameter gradients are `_grouped_table_grads`: one qgemm_grouped_table_grad launch for both."""
 
     @staticmethod
-    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer, form=None):
+    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer, form=None, w3_grad_blocks=False):
+        ctx.w3_grad_blocks = w3_grad_blocks
         out = _launch_plain(input, offsets, weight, scales, table2, layer, form)
         ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if any(ctx.needs_input_grad[1:3]) else ()))
         ctx.layer = layer
@@ -573,11 +580,11 @@ class _GroupedFunction(torch.autograd.Function):
         offsets, weight, scales, table2, *saved_input = ctx.saved_tensors
         d_input = d_scales = d_codebook = None
         if ctx.needs_input_grad[0]:
-            d_input = qgemm_grouped_input_grad(grad_output, offsets, weight, scales, table2, *ctx.layer)
+            d_input = _backward_input_grad(ctx.w3_grad_blocks, grad_output, offsets, weight, scales, table2, ctx.layer)
         if any(ctx.needs_input_grad[1:3]):
             d_scales, d_codebook = _grouped_table_grads(grad_output, saved_input[0], offsets, weight, scales, table2,
                                                         ctx.layer, *ctx.needs_input_grad[1:3], ctx.scalar)
-        return (d_input, d_scales, d_codebook) + (None,) * 5
+        return (d_input, d_scales, d_codebook) + (None,) * 6
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -606,7 +613,7 @@ def _validate_grouped_glu_pos(input, rows, pos):
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                      rows=None, pos=None, form=None, native_glu_grad: bool = False) -> torch.Tensor:
+                      rows=None, pos=None, form=None, native_glu_grad: bool = False, w3_grad_blocks=False) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
@@ -620,16 +627,18 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     form of the launch is an op of its own, `qgemm_grouped_glu_blocks`.  (The backward's recompute of gate and up is two plain grouped launches, which do choose automatically.)
     `native_glu_grad` is read by the backward only: False (the default) forms the gather and dg, du with torch ops, bit for bit
     as before; True runs `moe_gather` and `swiglu_grad` in their place (two launches, g and u never widened to fp32 tensors),
-    whose bits differ from the torch chain's within `flute_swiglu_grad`'s error account.  The forward's bits do not depend on it."""
+    whose bits differ from the torch chain's within `flute_swiglu_grad`'s error account.  The forward's bits do not depend on it.
+    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's pair-form input-gradient launch on 3-bit stacks."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
     _grouped_form_id(form)
+    _check_w3_grad_blocks("qgemm_grouped_glu", w3_grad_blocks, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad))
+                                         gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad), w3_grad_blocks)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        form)
 
@@ -668,7 +677,9 @@ class _GroupedGluFunction(torch.autograd.Function):
     `_grouped_table_grads` on the same operands."""
 
     @staticmethod
-    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None, native=False):
+    def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None, native=False,
+                w3_grad_blocks=False):
+        ctx.w3_grad_blocks = w3_grad_blocks
         ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
         ctx.native = native
         out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form)
@@ -684,15 +695,16 @@ class _GroupedGluFunction(torch.autograd.Function):
         rows = index[0] if ctx.has[0] else None
         pos = index[1] if ctx.has[1] else None
         dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
-                                              want_input_grad=ctx.needs_input_grad[0], native=ctx.native)
+                                              want_input_grad=ctx.needs_input_grad[0], native=ctx.native,
+                                              w3_grad_blocks=ctx.w3_grad_blocks)
         want = ctx.needs_input_grad
         d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
         d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
-        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 10
+        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 11
 
 
 def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad,
-                          native=False):
+                          native=False, w3_grad_blocks=False):
     """The backward of the fused GLU launch: (d input, x_sorted, dg, du) - the gathered rows and the two gradients in T
     that the pair-form launch reads, which the scale gradients read too.  `want_input_grad` false skips the pair-form
     launch and the sum over a token's slots (d input: None).  `native` (the ops' `native_glu_grad`): the gather is
@@ -714,7 +726,7 @@ def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw
         du = (dh * (g * sig)).to(input.dtype)
     if not want_input_grad:
         return None, x, dg, du
-    dx = qgemm_grouped_input_grad(dg, offsets, gw, gs, gt, *layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
+    dx = _backward_input_grad(w3_grad_blocks, dg, offsets, gw, gs, gt, layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
     if rows is not None:
         if pos is not None:
             dx = moe_combine(dx, pos, offsets)
@@ -730,7 +742,8 @@ def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weigh
 
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                            table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
-                           template_id: int, num_sms=None, form=None, native_router_grad: bool = False) -> torch.Tensor:
+                           template_id: int, num_sms=None, form=None, native_router_grad: bool = False,
+                           w3_grad_blocks=False) -> torch.Tensor:
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
@@ -739,31 +752,35 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     `native_router_grad` is read by the backward only, and only when `row_weight` requires grad: False (the default) forms
     d row_weight and d input from the unweighted input gradient with torch ops, bit for bit as before; True runs one
     `moe_weight_grad` launch in their place - d input has the same bits, d row_weight is summed in `flute_moe_weight_grad`'s
-    fixed order, not torch's.  The forward's bits do not depend on it."""
+    fixed order, not torch's.  The forward's bits do not depend on it.
+    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's input-gradient launch on 3-bit stacks."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     _grouped_form_id(form)
+    _check_w3_grad_blocks("qgemm_grouped_weighted", w3_grad_blocks, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
         return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form,
-                                              bool(native_router_grad))
+                                              bool(native_router_grad), w3_grad_blocks)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
 def qgemm_grouped_weighted_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                                      table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
-                                     template_id: int, num_sms=None, native_router_grad: bool = False) -> torch.Tensor:
+                                     template_id: int, num_sms=None, native_router_grad: bool = False,
+                                     w3_grad_blocks=False) -> torch.Tensor:
     """`qgemm_grouped_weighted` for stacks of 3-bit experts on the block form (`qgemm_grouped_w3_blocks`'s kernel with the routing
     weight in its epilogue, qgemm_block3.h GM = 2): out[r] = round_T(row_weight[r] * acc32), the rows from offsets[E] on zeros.
-    Same validation and autograd as `qgemm_grouped_weighted` (`native_router_grad` as there); a layer the form does not serve
+    Same validation and autograd as `qgemm_grouped_weighted` (`native_router_grad` and `w3_grad_blocks` as there); a layer the form does not serve
     raises ValueError before anything is launched."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     layer = (num_bits, group_size, template_id, num_sms)
     _require_w3_blocks("qgemm_grouped_weighted_w3_blocks", input, weight, scales, layer)
+    _check_w3_grad_blocks("qgemm_grouped_weighted_w3_blocks", w3_grad_blocks, num_bits)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted_w3_blocks", scales, table2)
         return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, _W3_BLOCKS,
-                                              bool(native_router_grad))
+                                              bool(native_router_grad), w3_grad_blocks)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, _W3_BLOCKS)
 
 
@@ -777,7 +794,9 @@ class _GroupedWeightedFunction(torch.autograd.Function):
     the two results of a row weight that needs a gradient come from one `moe_weight_grad` launch."""
 
     @staticmethod
-    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None, native=False):
+    def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None, native=False,
+                w3_grad_blocks=False):
+        ctx.w3_grad_blocks = w3_grad_blocks
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
         ctx.layer = layer
         ctx.native = native
@@ -792,25 +811,25 @@ class _GroupedWeightedFunction(torch.autograd.Function):
         d_input = d_weight = None
         if want_input or want_weight:
             d_input, d_weight = _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, want_input,
-                                                           want_weight, native=ctx.native)
+                                                           want_weight, native=ctx.native, w3_grad_blocks=ctx.w3_grad_blocks)
         d_scales, d_codebook = _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, ctx.layer,
                                                     want_scales, want_codebook, ctx.scalar, row_weight=row_weight)
-        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 6
+        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 7
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
-                               want_weight, native=False):
+                               want_weight, native=False, w3_grad_blocks=False):
     """(d input, d row_weight) of the weighted launch.  `native` (the ops' `native_router_grad`): with `want_weight` the
     unweighted input-gradient launch is followed by one `moe_weight_grad` launch in place of the torch lines below."""
     stack = (offsets, weight, scales, table2)
     if not want_weight:
-        return qgemm_grouped_input_grad(grad_output, *stack, *layer, row_weight=row_weight), None
+        return _backward_input_grad(w3_grad_blocks, grad_output, *stack, layer, row_weight=row_weight), None
     if native:
-        d_weight, d_input = moe_weight_grad(qgemm_grouped_input_grad(grad_output, *stack, *layer), input, row_weight, offsets,
-                                            want_input_grad=want_input)
+        d_weight, d_input = moe_weight_grad(_backward_input_grad(w3_grad_blocks, grad_output, *stack, layer), input, row_weight,
+                                            offsets, want_input_grad=want_input)
         return d_input, d_weight
     R = input.shape[0]
-    dh = qgemm_grouped_input_grad(grad_output, *stack, *layer).float()
+    dh = _backward_input_grad(w3_grad_blocks, grad_output, *stack, layer).float()
     served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
     # (a row no expert serves may hold anything in `input`: its dH' is zero, and the where keeps 0 x NaN out)
     d_weight = torch.where(served, (dh * input.float()).sum(dim=1), torch.zeros((), device=input.device))
@@ -878,6 +897,70 @@ def qgemm_grouped_input_grad(grad_output: torch.Tensor, offsets: torch.Tensor, w
     R, N = grad_output.shape
     return _launch_grouped("qgemm_grouped_input_grad_ex", tensors, weight, (R,), N, (R, weight.shape[2]),
                            (num_bits, group_size, template_id, num_sms), form=(form,), form_id=_grouped_input_grad_form_id)
+
+
+def _require_input_grad_w3_blocks(grad_output, weight, layer):
+    """Raise ValueError where flute_qgemm_grouped_input_grad_w3_blocks does not serve the shape.  Host only, before anything is
+    launched: the entry refuses a shape before it looks at a pointer, so it is asked with null pointers."""
+    num_bits, group_size, template_id, _ = layer
+    E, P, K = weight.shape
+    R, N = grad_output.shape
+    if R >= 2 ** 31:
+        raise ValueError
+    rc = _lib.get().flute_qgemm_grouped_input_grad_w3_blocks(_DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P,
+                                                             template_id, *(None,) * 11, 0, None)
+    if rc in (_FLUTE_ERR_SHAPE, _FLUTE_ERR_NUM_BITS):
+        raise ValueError("flute_amd.qgemm_grouped_input_grad_w3_blocks: the 3-bit block form of the input gradient is not eligible "
+                         "for this layer (include/flute_amd.h, flute_qgemm_grouped_input_grad_w3_blocks: 3 bits, K % 256 == 0)")
+    if rc not in (0, _FLUTE_ERR_NULL):
+        _lib.check(rc)
+
+
+def qgemm_grouped_input_grad_w3_blocks(grad_output: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                                       scales: torch.Tensor, table2: torch.Tensor, num_bits: int, group_size: int,
+                                       template_id: int, num_sms=None, row_weight=None, grad_output2=None, weight2=None,
+                                       scales2=None, table22=None) -> torch.Tensor:
+    """`qgemm_grouped_input_grad` for stacks of 3-bit experts on the block form, for training row counts: the same operands (single,
+    row-weighted and pair forms), formula and rounding on one 128-row block of an expert x 256 k per workgroup
+    (qgemm_grouped_input_grad_w3_blocks.h), with the same bits as `qgemm_grouped_input_grad` on all inputs - through that op 3 bits
+    are the slab form at every row count.  Same validation; a layer the form does not serve (not 3-bit, K % 256 != 0) raises
+    ValueError before anything is launched; `flute_amd.dev.grouped_input_grad_w3_blocks_form` tells where the form pays.  Not
+    differentiable itself."""
+    _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
+                                 grad_output2, weight2, scales2, table22)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_input_grad_w3_blocks(grad_output, weight, layer)
+    tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
+    if _records_grad(*tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_input_grad_w3_blocks: the backward is once-differentiable (no double backward)")
+    R, N = grad_output.shape
+    return _launch_grouped("qgemm_grouped_input_grad_w3_blocks", tensors, weight, (R,), N, (R, weight.shape[2]), layer)
+
+
+def _check_w3_grad_blocks(name, w3_grad_blocks, num_bits):
+    """The `w3_grad_blocks` keyword of the grouped forward ops: False, True or "auto", and anything but False on 3-bit stacks only."""
+    if not (w3_grad_blocks is False or w3_grad_blocks is True or (isinstance(w3_grad_blocks, str) and w3_grad_blocks == "auto")):
+        raise ValueError(f"flute_amd.{name}: w3_grad_blocks is False, True or 'auto', not {w3_grad_blocks!r}")
+    if w3_grad_blocks is not False and num_bits != 3:
+        raise ValueError(f"flute_amd.{name}: w3_grad_blocks selects the input-gradient kernel of 3-bit stacks; num_bits is {num_bits}")
+    return w3_grad_blocks
+
+
+def _backward_input_grad(w3_grad_blocks, grad_output, offsets, weight, scales, table2, layer, **operands):
+    """The input-gradient launch of the plain, GLU (pair form) and weighted backward: `qgemm_grouped_input_grad`, or - the forward
+    ops' `w3_grad_blocks` True, or "auto" where flute_qgemm_grouped_input_grad_w3_blocks_form says blocks for these shapes (host
+    only) - `qgemm_grouped_input_grad_w3_blocks`.  The bits are the same either way."""
+    take = w3_grad_blocks is True
+    if w3_grad_blocks == "auto":
+        (E, _, K), (R, N) = weight.shape, grad_output.shape
+        rc = _lib.get().flute_qgemm_grouped_input_grad_w3_blocks_form(
+            int("grad_output2" in operands), _DTYPE_ID[grad_output.dtype], layer[1], E, R, N, K, layer[2],
+            _num_sms(layer[3], grad_output.device))
+        if rc < 0:
+            _lib.check(rc)
+        take = rc == _GROUPED_INPUT_GRAD_FORMS["blocks"]
+    op = qgemm_grouped_input_grad_w3_blocks if take else qgemm_grouped_input_grad
+    return op(grad_output, offsets, weight, scales, table2, *layer, **operands)
 
 
 def _validate_grouped_scale_grad(grad_output, input, offsets, weight, table2, num_bits, group_size, row_weight):

@@ -38,6 +38,8 @@ extern "C" {
  *    the block form of the fused SwiGLU launch behind its own entry: flute_qgemm_grouped_glu_blocks, flute_qgemm_grouped_glu_blocks_form
  *    the block form for 3-bit stacks behind its own entries: flute_qgemm_grouped_w3_blocks, flute_qgemm_grouped_weighted_w3_blocks,
  *    flute_qgemm_grouped_w3_blocks_form
+ *    the block form of the grouped input gradient for 3-bit stacks behind its own entries: flute_qgemm_grouped_input_grad_w3_blocks,
+ *    flute_qgemm_grouped_input_grad_w3_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
  *    the routing over many workgroups: flute_moe_route_wide, flute_moe_gate_route_wide, flute_moe_route_wide_workspace, flute_moe_route_form
@@ -557,6 +559,39 @@ int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, i
  * rule); P is taken as num_bits * N / 16; num_sms < 1: 256. */
 int flute_qgemm_grouped_input_grad_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
                                         int template_id, int num_sms);
+
+/* The block form of the grouped input gradient for stacks of 3-bit experts, behind entries of their own:
+ * flute_qgemm_grouped_input_grad on the block form's work split - one 128-row block of one expert x 256 k per workgroup, the grid
+ * floor((R + 127 E) / 128) x K / 256 from (E, R, K) alone - with a decoder of the three-plane layout and a dY stager of its own
+ * (csrc/qgemm_grouped_input_grad_w3_blocks.h).  The arguments, the single, row-weighted and pair forms, the formula, clamping, the zero
+ * rows from offsets[E] on, determinism, capture and the block form's malformed-table contract are as described above, and so is the
+ * order in which every output sums over N: the launch gives EQUAL BITS to flute_qgemm_grouped_input_grad on all inputs.
+ * flute_qgemm_grouped_input_grad, its _ex form and flute_qgemm_grouped_input_grad_form keep their behaviour - 3 bits there are the
+ * slab form at every count, and forcing blocks is refused -; a caller opts in by calling this.
+ * It serves: num_bits 3 (TileP 32), K a positive multiple of 256, N a multiple of 64 (a 3-bit layer's is one of 512),
+ * R <= 2^31 - 257 and a 31-bit grid.
+ * Refusals, before anything is enqueued or dereferenced, in this order: flute_qgemm_grouped_input_grad's (dtype, the layer checks,
+ * FLUTE_ERR_SHAPE for P or a negative E / R, FLUTE_ERR_SHAPE for a row_weight together with any pointer of the pair form);
+ * FLUTE_ERR_NUM_BITS for num_bits != 3; FLUTE_ERR_SHAPE for a shape outside the list above (E == 0 and R == 0 are inside it);
+ * R == 0 returns FLUTE_OK and enqueues nothing; then FLUTE_ERR_NULL as the old entry gives it.  E == 0 with R > 0 writes dX as zeros
+ * (a memset node).  num_sms is accepted for symmetry and not used. */
+int flute_qgemm_grouped_input_grad_w3_blocks(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                             int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                             const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                             const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
+
+/* Which launch a caller should take for the input gradient of a stack of 3-bit experts: FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS (the
+ * entry above) where the shape is in its list, E >= 1 and the mean rows per expert, R / E, is at least
+ * FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS - where one row block per expert already fills the chip, E * (K / 256) >= num_sms
+ * (< 1: 256) - or FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL where it does not, else
+ * FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS (the old entries), or the negative error the old entries would refuse the layer with.  Host
+ * only: no pointers, nothing is enqueued; pair != 0: the pair form (the same rule); P is taken as 3 * N / 16.  The two constants are
+ * measured on the 3-bit launches (csrc/api_train.hip): each is the smallest swept mean from which the block launch
+ * is faster than the slab form on every swept stack of its kind. */
+#define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS 8             /* E * (K / 256) >= num_sms: the experts' k blocks fill the chip */
+#define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL 128   /* fewer workgroups per row block than compute units */
+int flute_qgemm_grouped_input_grad_w3_blocks_form(int pair, int dtype, int group_size, int E, int R, int N, int K, int template_id,
+                                                  int num_sms);
 
 /* The gradient of the scales of a stack flute_qgemm_grouped multiplies by, in ONE launch: flute_qgemm_scale_grad for every
  * expert over the rows the device-side table gives it.  With b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):

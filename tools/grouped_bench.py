@@ -6,6 +6,7 @@
     python tools/grouped_bench.py --mode gate [--processes 3] [--out profiles/grouped_moe_gate.json]
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
     python tools/grouped_bench.py --mode input_grad [--only-swiglu-grad] [--out profiles/grouped_moe_input_grad_blocks.json]
+    python tools/grouped_bench.py --mode input_grad --only w3        (profiles/grouped_moe_input_grad_blocks_w3.json)
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
@@ -301,7 +302,7 @@ class Step:
         return self.experts[i % len(self.experts)](self.hidden, self.ids, self.weights)
 
 
-def step_stacks(copies, device):
+def step_stacks(copies, device, BITS=BITS):
     """`copies` sets of gate / up [F, K] and down [K, F] GroupedFluteLinear with random packed bits, shared by both forms."""
     import flute_amd
     from flute_amd import utils
@@ -593,7 +594,7 @@ def ig_counts(rows, experts, seed):
 
 class InputGrad:
     """`copies` stacks of `experts` packed layers [N, K] (`pair`: two of them, and two dY); step(i) is dX [R, K] = dY [R, N] @ W_e on
-    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto" - or, "loop", the per-expert loop of dequantize + mm on row
+    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto", or "w3_blocks", the 3-bit block launch - or, "loop", the per-expert loop of dequantize + mm on row
     ranges the host knows.  `weights`: another InputGrad of the same stack whose weight copies are shared."""
 
     def __init__(self, experts, N, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, pair=False, weights=None):
@@ -626,6 +627,9 @@ class InputGrad:
         c = i % self.Q[0].shape[0]
         if self.how != "loop":
             second = dict(grad_output2=self.dY[1], weight2=self.Q[1][c], scales2=self.S[1][c], table22=self.tables2) if self.pair else {}
+            if self.how == "w3_blocks":                   # the 3-bit block launch behind its own op
+                return self.fa.qgemm_grouped_input_grad_w3_blocks(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2,
+                                                                  self.bits, G, self.tid, self.num_sms, **second)
             return self.fa.qgemm_grouped_input_grad(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G,
                                                     self.tid, self.num_sms, form=None if self.how == "auto" else self.how, **second)
         out = []
@@ -941,9 +945,9 @@ class ModuleStep:
     """One forward and one backward step of FluteExperts(fused=True, native_routing=True, glu_blocks=...) at `tokens` tokens (top-2)
     on copy i of step_stacks: the gradient reaches the hidden states (the experts' parameters are frozen)."""
 
-    def __init__(self, stacks, tokens, device, glu_blocks, backward):
+    def __init__(self, stacks, tokens, device, glu_blocks, backward, **kw):
         from flute_amd.integrations import moe
-        self.experts = [moe.FluteExperts(g, u, d, fused=True, native_routing=True, glu_blocks=glu_blocks) for g, u, d in stacks]
+        self.experts = [moe.FluteExperts(g, u, d, fused=True, native_routing=True, glu_blocks=glu_blocks, **kw) for g, u, d in stacks]
         self.backward = backward
         gen = torch.Generator(device=device).manual_seed(tokens)
         self.hidden = torch.randn(tokens, 4096, device=device, generator=gen).to(DTYPE).requires_grad_(backward)
@@ -1203,6 +1207,98 @@ IG_LINES = [("mixtral gate_up", 8, 14336, 4096, r, 4, "float16", False) for r in
             ("mixtral gate_up pair", 8, 14336, 4096, 512, 4, "float16", True),
             ("mixtral gate_up pair", 8, 14336, 4096, 4096, 4, "float16", True)]
 IG_FORMS = ("slabs", "blocks", "auto")
+
+
+# 3-bit stacks (W3G64, --mode input_grad --only w3; profiles/grouped_moe_input_grad_blocks_w3.json): the slab form - what
+# flute_amd.qgemm_grouped_input_grad runs at every count -, the block launch behind its own op and the per-expert loop
+W3_IG_LINES = [(name, experts, N, K, r, dt, pair) for dt in ("float16", "bfloat16") for name, experts, N, K, r, pair in
+               [("mixtral gate_up", 8, 14336, 4096, r, False) for r in (512, 4096, 8192)] +
+               [("mixtral down", 8, 4096, 14336, r, False) for r in (512, 4096, 8192)] +
+               [("many-expert 2048 x 2048", 64, 2048, 2048, 4096, False), ("mixtral gate_up pair", 8, 14336, 4096, 4096, True)]]
+W3_IG_SWEEP_MEANS = (8, 16, 32, 48, 64, 96, 128, 192, 256)
+
+
+def main_input_grad_w3(args, device):
+    """--mode input_grad --only w3: the 3-bit slab form, block launch and per-expert loop; the threshold sweep; the backward step of
+    FluteExperts(w3_blocks="auto") with w3_grad_blocks False against "auto" - all alternating in one process."""
+    from flute_amd import dev
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        with open(args.out, "w") as f:                # (rewritten after every line: a long run that is cut short keeps its lines)
+            json.dump({"what": "grouped input gradient of 3-bit stacks (W3G64) at training row counts: slab form, the block launch "
+                               "(flute_amd.qgemm_grouped_input_grad_w3_blocks) and a per-expert loop of flute_amd.dequantize + "
+                               "torch.mm; hipGraph replays, device-clock stamps, cold caches, median of the replays, two alternating "
+                               "passes of each contender in one process; then the threshold sweep and the forward + backward step of "
+                               "FluteExperts(fused=True, native_routing=True, w3_blocks='auto') with w3_grad_blocks False and 'auto'",
+                       "thresholds": {"FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS": W3_IG_THRESHOLDS[0],
+                                      "FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL": W3_IG_THRESHOLDS[1]},
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name, experts, N, K, nrows, dt, pair in W3_IG_LINES:
+        dtype = getattr(torch, dt)
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        copies = prefill_copies(experts, N, K, 3, stacks=2 if pair else 1)
+        first = InputGrad(experts, N, K, counts, copies, device, "slabs", 3, dtype, pair)
+        layers = {"slabs": first}
+        for how in ("w3_blocks", "loop"):
+            layers[how] = InputGrad(experts, N, K, counts, copies, device, how, 3, dtype, pair, weights=first)
+        a, b = layers["w3_blocks"].step(0), torch.cat(layers["loop"].step(0))
+        torch.cuda.synchronize()
+        equal = bool(torch.equal(a.view(torch.int16), first.step(0).view(torch.int16)))
+        diff, ref = float((a.float() - b.float()).abs().max()), float(b.float().abs().max())
+        us, spread, replays = time_forms(layers, args)
+        flop = first.flops()
+        emit({"what": "input_grad w3", "shape": name, "dtype": dt, "pair": pair, "experts": experts, "N": N, "K": K,
+              "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+              "auto_form": dev.grouped_input_grad_w3_blocks_form(experts, sum(counts), N, K, G, first.tid, first.num_sms, dtype, pair),
+              "us": us, "blocks_over_slabs": round(us["w3_blocks"] / us["slabs"], 4),
+              "blocks_over_loop": round(us["w3_blocks"] / us["loop"], 4),
+              "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()},
+              "workgroups_with_rows": sum(-(-c // 128) for c in counts) * (K // 256), "spread": spread, "flop": flop,
+              "blocks_bits_equal_slabs": equal, "max_abs_diff_blocks_vs_loop": diff, "max_abs_loop": ref, "replays_us": replays})
+        del layers, first, a, b
+        torch.cuda.empty_cache()
+    for name, experts, N, K in SWEEP_STACKS:
+        copies = prefill_copies(experts, N, K, 3)
+        first = None
+        for mean in W3_IG_SWEEP_MEANS:
+            counts = even_counts(mean * experts, experts)
+            layers = {}
+            for how in ("slabs", "w3_blocks"):
+                layers[how] = InputGrad(experts, N, K, counts, copies, device, how, 3, weights=first)
+                first = first or layers[how]
+            us, spread, replays = time_forms(layers, args)
+            emit({"what": "w3 threshold sweep", "shape": name, "experts": experts, "N": N, "K": K, "mean_rows_per_expert": mean,
+                  "rows": sum(counts), "us": us, "blocks_over_slabs": round(us["w3_blocks"] / us["slabs"], 4), "spread": spread,
+                  "blocks_faster_in_every_alternation": max(replays["w3_blocks"]) < min(replays["slabs"]),
+                  "auto_form": dev.grouped_input_grad_w3_blocks_form(experts, sum(counts), N, K, G, first.tid, first.num_sms),
+                  "replays_us": replays})
+            del layers
+        del first
+        torch.cuda.empty_cache()
+    copies = prefill_copies(E, 14336, 4096, 3, stacks=3)
+    stacks = step_stacks(copies, device, 3)
+    for tokens in (512, 4096):
+        layers = {str(v): ModuleStep(stacks, tokens, device, False, True, w3_blocks="auto", w3_grad_blocks=v) for v in (False, "auto")}
+        us, spread, replays = time_forms(layers, args)
+        emit({"what": "w3 module step (forward + backward to hidden)", "tokens": tokens, "rows": tokens * TOPK, "experts": E,
+              "top_k": TOPK, "weight_copies": copies, "us": us, "auto_over_false": round(us["auto"] / us["False"], 4),
+              "spread": spread, "replays_us": replays})
+    print("wrote", args.out)
+
+
+def _w3_ig_thresholds():
+    with open(os.path.join(ROOT, "include", "flute_amd.h")) as f:
+        d = dict(l.split()[1:3] for l in f if l.startswith("#define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS"))
+    return int(d["FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS"]), int(d["FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL"])
+
+
+W3_IG_THRESHOLDS = _w3_ig_thresholds()
 
 
 def main_input_grad_forms(args, device):
@@ -1890,6 +1986,9 @@ def main():
     if args.mode == "aux_loss":
         return main_aux_loss(args, device)
     if args.mode == "input_grad":
+        if args.only == ["w3"]:
+            args.out = os.path.join(os.path.dirname(args.out), "grouped_moe_input_grad_blocks_w3.json")
+            return main_input_grad_w3(args, device)
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
     bits = args.bits
