@@ -34,6 +34,7 @@ qgemm_grouped_glu_blocks = ops.qgemm_grouped_glu_blocks     # the same launch on
 qgemm_grouped_weighted = ops.qgemm_grouped_weighted
 qgemm_grouped_w3_blocks = ops.qgemm_grouped_w3_blocks       # stacks of 3-bit experts on 128-row blocks (plain and weighted)
 qgemm_grouped_weighted_w3_blocks = ops.qgemm_grouped_weighted_w3_blocks
+qgemm_grouped_glu_w3_blocks = ops.qgemm_grouped_glu_w3_blocks   # the fused SwiGLU launch of 3-bit stacks on 128-row blocks
 # their input gradient, one launch over the packed stacks (contracts over N); the grouped and mixture-of-experts functions
 # here backpropagate through it to activations, routing weights and router logits
 qgemm_grouped_input_grad = ops.qgemm_grouped_input_grad

@@ -70,6 +70,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_form": (c_int, [c_int] * 10),
     "flute_qgemm_grouped_glu_blocks": (c_int, [c_int] * 10 + [c_void_p] * 10 + [c_int, c_void_p]),
     "flute_qgemm_grouped_glu_blocks_form": (c_int, [c_int] * 10),
+    "flute_qgemm_grouped_glu_w3_blocks": (c_int, [c_int] * 10 + [c_void_p] * 10 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_glu_w3_blocks_form": (c_int, [c_int] * 10),
     "flute_qgemm_grouped_w3_blocks": (c_int, [c_int] * 9 + [c_void_p] * 6 + [c_int, c_void_p]),
     "flute_qgemm_grouped_weighted_w3_blocks": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
     "flute_qgemm_grouped_w3_blocks_form": (c_int, [c_int] * 9),

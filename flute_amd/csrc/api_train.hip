@@ -362,6 +362,48 @@ int flute_qgemm_grouped_glu_blocks(int dtype, int num_bits, int group_size, int 
     return num_bits == 4 ? qgemm_grouped_glu_blocks_unit_b4(g, st) : qgemm_grouped_glu_blocks_unit_b2(g, st);
 }
 
+// The 3-bit block form of the GLU launch behind its own pair of entries (include/flute_amd.h; qgemm_block3.h GM = 3): the sequence of
+// flute_qgemm_grouped_glu_blocks with 3 bits and grouped_glu_w3_blocks_eligible in the place of its rule (an empty launch asked with
+// E / R / Tsrc raised to 1, as there).  The query's thresholds are the plain form's rule on constants of their own,
+// FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS / _PARTIAL = 24 / 24: each the smallest swept mean from which the block launch is not slower
+// on any swept stack of its kind (the policy of 3.3m / 3.3u).  The sweep (profiles/grouped_moe_glu_blocks_w3.json, "w3 glu threshold
+// sweep": W3G64 fp16, us of row form qgemm_grouped_glu / block launch at even counts, rows / E = 8, 16, 24, 32, 48, 64, 96, 128; the row
+// form passes 16 rows at a time, so its time steps up at 17 rows per expert): Mixtral gate / up pair (448 workgroups per row block)
+// 257 / 280, 258 / 281, 480 / 286, 482 / 288, 704 / 294, 919 / 303, 1351 / 320, 1784 / 338; E 64 2048 x 2048 pair (512) 147 / 143,
+// 148 / 143, 265 / 148, 265 / 150, 382 / 154, 496 / 161, 722 / 176, 950 / 195; E 8 4096 x 4096 pair (128 workgroups: does not fill the
+// chip) 127 / 141, 128 / 141, 238 / 143, 239 / 144, 347 / 148, 455 / 150, 672 / 157, 889 / 162.  On the routed draws the block launch
+// wins from 16 on (some expert then has more than 16 rows: 459 / 283, 257 / 146, 230 / 142); at 8 it loses by 9 - 10 % on both E = 8 stacks.
+int flute_qgemm_grouped_glu_w3_blocks_form(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K,
+                                           int template_id, int num_sms) {
+    Layer l;
+    int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, num_bits * (F / 16), &l);
+    if (rc) return rc;
+    if (Tsrc < 0 || num_bits != 3) return FLUTE_ERR_SHAPE;
+    if (E < 1 || R < 1 || !grouped_glu_w3_blocks_eligible(l.lg, E, R, Tsrc, F, K)) return FLUTE_GROUPED_FORM_ROWS;
+    const int thr = min_mean_rows(F / 256, E, num_sms, FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS,
+                                  FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL);
+    return (long long)R >= (long long)thr * E ? FLUTE_GROUPED_FORM_BLOCKS : FLUTE_GROUPED_FORM_ROWS;
+}
+
+int flute_qgemm_grouped_glu_w3_blocks(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                                      int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                                      const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                                      void* H, int num_sms, void* stream) {
+    Layer l;
+    int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, F, K, P, &l);
+    if (rc) return rc;
+    rc = check_glu_rows(R, Tsrc, rows != nullptr);
+    if (rc) return rc;
+    if (num_bits != 3 || !grouped_glu_w3_blocks_eligible(l.lg, std::max(E, 1), std::max(R, 1), std::max(Tsrc, 1), F, K))
+        return FLUTE_ERR_SHAPE;
+    if (E == 0 || R == 0) return FLUTE_OK;
+    if (!Xsrc || !offsets || !Qgate || !Sgate || !QM2gate || !Qup || !Sup || !QM2up || !H) return FLUTE_ERR_NULL;
+    GroupedForward g = glu_operands(dtype, num_bits, E, R, Tsrc, F, K, P, Xsrc, rows, offsets, Qgate, Sgate, QM2gate, Qup, Sup, QM2up,
+                                    H, num_sms);
+    g.form = FLUTE_GROUPED_FORM_BLOCKS; g.tile_p = l.t.tile_p; g.lg = l.lg;
+    return qgemm_grouped_glu_blocks_unit_b3(g, reinterpret_cast<hipStream_t>(stream));
+}
+
 int flute_qgemm_grouped_weighted(int dtype, int num_bits, int group_size, int E, int T, int N, int K, int P,
                                  int template_id, const void* X, const void* offsets, const void* Q, const void* S,
                                  const void* QM2, const float* row_weight, void* Y, int num_sms, void* stream) {

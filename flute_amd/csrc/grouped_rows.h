@@ -67,6 +67,18 @@ inline bool grouped_glu_blocks_eligible(int num_bits, int lg, int E, int R, int 
     return grouped_blocks_row_blocks(E, R) * (F / 256) <= 0x7fffffffLL;
 }
 
+// What the 3-bit block form of the fused SwiGLU launch serves (flute_qgemm_grouped_glu_w3_blocks; qgemm_block3.h GM = 3; api_train.hip's
+// refusal and query read this, nothing else decides it): grouped_glu_blocks_eligible's conditions on a 3-bit pair of stacks, and the
+// three-plane weight descriptor of grouped_w3_blocks_eligible - 3 (F / 16) unit rows of K 2 bytes below 2^32 - 16.
+inline bool grouped_glu_w3_blocks_eligible(int lg, int E, int R, int Tsrc, int F, int K) {
+    if (E < 1 || R < 1 || Tsrc < 1 || F < 256 || F % 256 || K < 64 || (K >> lg) % 8) return false;
+    if (R > 0x7fffffff - 2 * kGroupedBlockRows) return false;
+    if ((size_t)Tsrc * K * 2 >= (size_t)0xfffffff0u) return false;
+    if ((size_t)F * (K >> lg) * 2 >= (size_t)0xfffffff0u) return false;
+    if ((size_t)(3 * (F / 16)) * K * 2 >= (size_t)0xfffffff0u) return false;
+    return grouped_blocks_row_blocks(E, R) * (F / 256) <= 0x7fffffffLL;
+}
+
 // What the block form of the input gradient serves (qgemm_grouped_input_grad_blocks.h; api_train.hip's form rule and refusal read
 // this, nothing else decides it): 4 / 2 bits, whole 256-k blocks, a row index plus a block that stays an int, and a 31-bit
 // grid.  (N, TileP and the group size are the slab form's, which the caller has checked with the layer; every base in the kernel

@@ -115,6 +115,9 @@ int qgemm_grouped_blocks_unit_b3(const GroupedForward& g, hipStream_t stream);
 // inst_grouped_glu_blocks_b*.hip): the same grid from (E, R, F) alone.  Its own entry: qgemm_grouped_dispatch never takes it.
 int qgemm_grouped_glu_blocks_unit_b4(const GroupedForward& g, hipStream_t stream);
 int qgemm_grouped_glu_blocks_unit_b2(const GroupedForward& g, hipStream_t stream);
+// the 3-bit block form of the Glu mode (flute_qgemm_grouped_glu_w3_blocks; qgemm_block3.h GM = 3; what it serves:
+// grouped_glu_w3_blocks_eligible; inst_grouped_glu_blocks_b3.hip).  Its own entry: the entries above keep refusing 3 bits.
+int qgemm_grouped_glu_blocks_unit_b3(const GroupedForward& g, hipStream_t stream);
 // the unit of a launch: the one ladder over form, bit width and mode
 inline int qgemm_grouped_dispatch(const GroupedForward& g, hipStream_t stream) {
     if (g.form == FLUTE_GROUPED_FORM_BLOCKS)

@@ -46,12 +46,25 @@ namespace flute_amd {
 // serves.  No K split, no atomics, nothing shared between workgroups: equal arguments give equal bits.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / SGPRs / scratch bytes per lane / LDS): GM 1 f16 201 / 0 / 62 / 0 / 80 KB, bf16 205 / 0 / 62 / 0 / 80 KB; GM 2 f16 201 / 0 / 64 / 0 / 80 KB, bf16 205 / 0 / 64 / 0 / 80 KB -
 // two waves per SIMD, as the dense RT = 8 form; the new state (rb, re, the three bases) is scalar.
+//
+// GM = 3: the fused SwiGLU member, H[r, :] = round_T(silu32(g) * u) over a gate and an up stack of 3-bit experts
+// (flute_qgemm_grouped_glu_w3_blocks; arithmetic, row index and contract: qgemm_block2.h's GM = 3).  The K pass of a body - prologue, ring,
+// drain: one program text, `k_pass` - runs twice over the same rows: for the gate stack, whose 64 fp32 accumulators per lane are then set
+// aside, and after one barrier for the up stack, with the pair table restaged from the up stack's QM2, the weight and scale descriptors
+// moved to the up stack of the same expert (the plane-row offsets are relative to the descriptor's base and stay) and the activations staged
+// again (L2-hot); the epilogue combines and rounds once.  The activation descriptor spans Xsrc and a lane's row is rows[r] (clamped to
+// [0, Tsrc), read once per workgroup); a block row at or past re reads no index and gets kRowOut.  Registers: 64 more accumulators do not
+// fit beside wave 7's ring of 72, so the member takes the RT = 16 form's XLDS path - planes 1 .. NPL - 1 of waves 6 / 7 through wave-private
+// LDS (18 KB; the launch's LDS is 98 KB: grouped_glu_w3_blocks_lds_bytes) - and every wave's ring is one plane.
+// Resources (as above): GM 3 f16 247 / 0 / 106 / 0 / 98 KB, bf16 247 / 0 / 106 / 0 / 98 KB - two waves per SIMD; 15 of the SGPRs are spilled
+// to lanes of v246 (v_writelane / v_readlane, outside the ring loops), no scratch.
 template <typename T, int RT, int GM = 0>
-__global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs> args) {
+__global__ __launch_bounds__(512) void qgemm_block3_kernel(
+    const std::conditional_t<GM == 3, GroupedGluBlockArgs, std::conditional_t<GM != 0, GroupedBlockArgs, BlockArgs>> args) {
     using NT = Num<T>;
     constexpr int BITS = 3, TILEP = 32;
     static_assert(GM == 0 || RT == 8, "the grouped front end is built for 128-row blocks");
-    static_assert(GM >= 0 && GM <= 2, "0: dense, 1: grouped plain, 2: grouped weighted");
+    static_assert(GM >= 0 && GM <= 3, "0: dense, 1: grouped plain, 2: grouped weighted, 3: grouped SwiGLU");
     // RT = 8: 128-row blocks (the weight ring leaves no registers for 16 row tiles).  RT = 1, 2, 4: "skinny" blocks of
     // 16 / 32 / 64 rows for small batches, launched with a grid-level K split (fp32 slabs + splitk_reduce_kernel): a
     // 3-bit wave of the per-wave kernel is 256 columns wide, so a 4096-wide layer gives it 16 column slabs; here the
@@ -91,6 +104,9 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
     if (a.splitk > 1) { split = bid % a.splitk; bid /= a.splitk; }
     int tm_idx, tn_idx;
     int row_lo = 0, row_hi = 0;                                    // grouped: the expert's rows [rb, re)
+    const int* glu_rows = nullptr;                                 // GM = 3: the row index (or null) and the rows of Xsrc
+    int glu_tsrc = 0;
+    if constexpr (GM == 3) { glu_rows = a.rows; glu_tsrc = a.Tsrc; }
     if constexpr (GM != 0) {
         static_assert(GM == 0 || BM == kGroupedBlockRows, "the host's grid counts these blocks");
         if constexpr (GM == 2) grouped_zero_unserved<NW * 64>(reinterpret_cast<uint16_t*>(a.D), a.offsets, a.E, a.M, a.N);
@@ -106,6 +122,11 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
         a.Q += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);      // P = 3 (N / 16) unit rows of K / 2 words
         a.S = reinterpret_cast<const uint16_t*>(a.S) + (size_t)e * (size_t)a.N * (size_t)a.G;
         a.QM2 += (size_t)e << (2 * BITS);
+        if constexpr (GM == 3) {
+            a.Q_up += (size_t)e * (size_t)a.P * (size_t)(a.K >> 1);
+            a.S_up = reinterpret_cast<const uint16_t*>(a.S_up) + (size_t)e * (size_t)a.N * (size_t)a.G;
+            a.QM2_up += (size_t)e << (2 * BITS);
+        }
     } else if (a.order == 1) {
         const int per = a.tiles_m >> 3, x = bid & 7, i = bid >> 3;
         tm_idx = x * per + i % per;
@@ -126,7 +147,9 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
     const uint32_t row_bytes = (uint32_t)a.K * 2u;
 
     // (grouped: rows count from the expert's first, the descriptor ends at its last; the weight and scale descriptors are one expert's)
-    const srd_t x_srd = GM != 0
+    const srd_t x_srd = GM == 3
+        ? make_srd(a.A, (uint32_t)min((size_t)glu_tsrc * a.K * 2, (size_t)0xfffffff0u))       // the whole of Xsrc: rows come through the index
+        : GM != 0
         ? make_srd(reinterpret_cast<const uint16_t*>(a.A) + (size_t)row_lo * a.K,
                    (uint32_t)min((size_t)(row_hi - row_lo) * a.K * 2, (size_t)0xfffffff0u))
         : make_srd(a.A, (uint32_t)min((size_t)a.M * a.K * 2, (size_t)0xfffffff0u));
@@ -142,7 +165,20 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
         const int rt = (p0 + i) >> 1, rh = (p0 + i) & 1, row8 = lane >> 3;
-        x_vo[i] = x_mine ? (uint32_t)(((size_t)(m0 + rt * 16 + rh * 8 + row8) * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2) : 0x80000000u;
+        if constexpr (GM == 3) {
+            // the lane's row through the index: r in [rb, re) reads rows[r] (null: r itself) clamped to [0, Tsrc); any other row of the
+            // block reads no index and forms no address.  kRowOut: Tsrc K 2 is a multiple of 128 below 2^32 - 16, so at most 2^32 - 128
+            // - out of range whether the check adds the 16 bytes of the request or not, and adding them does not wrap
+            constexpr uint32_t kRowOut = 0xffffffe0u;
+            const int r = row_lo + m0 + rt * 16 + rh * 8 + row8;
+            x_vo[i] = kRowOut;
+            if (r < row_hi) {
+                const int src = min(max(glu_rows ? glu_rows[r] : r, 0), glu_tsrc - 1);
+                x_vo[i] = (uint32_t)(((size_t)src * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2);
+            }
+        } else {
+            x_vo[i] = x_mine ? (uint32_t)(((size_t)(m0 + rt * 16 + rh * 8 + row8) * a.K + (((lane & 7) ^ blk_swz8(row8, rh)) * 8)) * 2) : 0x80000000u;
+        }
     }
     // plane rows of this lane's unit (common.h unit_row<3>): plane 0 = row u, planes 1 / 2 = 32 rows apart
     const int u = unit0 + r16;
@@ -190,7 +226,13 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
             ? (uint32_t)(((size_t)(unit_col0<BITS, TILEP>(unit0 + (lane & 15)) + ((lane >> 4) ? f1 : f0) * TILEP) * a.G) * 2) : 0x80000000u;
 
         static_assert((NST - 2) * BATCH <= 63, "vmcnt is six bits");
-        constexpr bool XLDS = RT == 16 && NPL > 1;                 // planes 1 .. NPL-1 through LDS
+        // GM = 3: one K pass over the stack that (w_cur, s_cur, the staged table) name, from k_pass to the drain: all of K into acc.  The
+        // member comes back once, for the up stack (a jump, so that the pass stays one program text and GM 0 / 1 / 2 compile as before)
+        std::conditional_t<GM == 3, srd_t, const srd_t&> w_cur = w_srd, s_cur = s_srd;
+        f32x4_t acc_gate[GM == 3 ? RT : 1][NT2];                   // GM = 3: g, set aside after the first pass
+        int pass = 0;
+    k_pass: __attribute__((unused));
+        constexpr bool XLDS = (RT == 16 || GM == 3) && NPL > 1;    // planes 1 .. NPL-1 through LDS (GM = 3: 64 more accumulators, as RT = 16)
         constexpr int NREG = XLDS ? 1 : NPL;                       // planes in the register ring
         constexpr int NX = NPL - NREG;
         u32x4_t w[NST][2][NREG];
@@ -210,13 +252,13 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
                 else vo = (c == 0) ? wv0 : wv1;
                 const uint32_t so = k0 * 2u + (uint32_t)h * 64u;
                 if constexpr (XLDS && c >= 1)
-                    dma16_buf(vo, w_srd, so, pl_base + (uint32_t)(((slot * 2 + h) * NX + (c - 1)) * 1024));
+                    dma16_buf(vo, w_cur, so, pl_base + (uint32_t)(((slot * 2 + h) * NX + (c - 1)) * 1024));
                 else
-                    w[slot][h][c] = buf_load16(vo, w_srd, so);
+                    w[slot][h][c] = buf_load16(vo, w_cur, so);
             } else {
                 const int g = (int)(k0 >> a.lg);
                 const bool blk_start = (ustep < nsteps) && ((g & 7) == 0 || ustep == 0) && ((k0 & ((1u << a.lg) - 1u)) == 0);
-                dma16_buf(s_voff, s_srd, (uint32_t)((g >> 3) * 16),
+                dma16_buf(s_voff, s_cur, (uint32_t)((g >> 3) * 16),
                           blk_start ? sc_base + (uint32_t)((g >> 3) & 1) * 1024u : sc_sink);
             }
         };
@@ -378,6 +420,14 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
                     frag(slot_tag, h_tag, std::integral_constant<int, R + 8>{});
                 } else {
                     frag(std::integral_constant<int, nslot>{}, std::integral_constant<int, nh>{}, std::integral_constant<int, R & 7>{});
+                    if constexpr (XLDS && RT == 8 && R == 0) {
+                        // (128-row blocks) the LDS planes were read before the barrier; LDS returns in order and only row tile 0's
+                        // fragment is younger: they are here before the first lookup forms its index
+                        u32x4_t& p0 = pw[0];
+                        u32x4_t& p1 = pw[NX > 1 ? 1 : 0];
+                        if constexpr (NX == 2) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(p0), "+v"(p1) : : "memory");
+                        else asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(p0) : : "memory");
+                    }
                     [&]<int... L>(std::integer_sequence<int, L...>) {
                         (lookup(std::integral_constant<int, nslot>{}, std::integral_constant<int, nh>{}, std::integral_constant<int, (R & 7) * LPR + L>{}), ...);
                     }(std::make_integer_sequence<int, LPR>{});
@@ -423,6 +473,26 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
         [&]<int... I>(std::integer_sequence<int, I...>) {
             (wait_batch(std::integral_constant<int, I>{}, std::integral_constant<int, 0>{}), ...);
         }(std::make_integer_sequence<int, NST>{});
+        if constexpr (GM == 3) {
+            if (pass == 0) {
+                // g is whole: set it aside and run the same pass for the up stack (acc starts from zero again there).  The barrier: every
+                // wave has drained its requests and finished its lookups, fragment and plane reads, so the pair table, the stages and
+                // the scale images may be overwritten; the table is restaged behind it and met by the pass's own first barrier.
+                pass = 1;
+#pragma unroll
+                for (int r = 0; r < RT; ++r)
+#pragma unroll
+                    for (int t = 0; t < NT2; ++t) acc_gate[r][t] = acc[r][t];
+                __builtin_amdgcn_s_barrier();
+                for (int p = tid; p < 64 * 8; p += NW * 64) {      // the up stack's pair table in the gate stack's place
+                    const uint32_t v = a.QM2_up[p >> 3];
+                    *reinterpret_cast<uint4*>(smem + (size_t)(p >> 3) * 128 + (p & 7) * 16) = make_uint4(v, v, v, v);
+                }
+                w_cur = make_srd(a.Q_up, (uint32_t)min((size_t)(3 * (a.N >> 4)) * row_bytes, (size_t)0xfffffff0u));
+                s_cur = make_srd(a.S_up, (uint32_t)min((size_t)a.N * a.G * 2, (size_t)0xfffffff0u));
+                goto k_pass;
+            }
+        }
 
         // ---- epilogue: accumulator register i of lane (r16, q4) = unit 4 q4 + i of the workgroup, i.e. four
         // consecutive columns of field f_t; the lane's output row is r16 ----
@@ -446,6 +516,9 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
                 return;
             }
         }
+        int ep_n = GM == 3 ? a.N : 0;
+        // (GM = 3: two sets of accumulators are live through the K passes; the 16 store addresses are formed here, not ahead of them)
+        if constexpr (GM == 3) asm volatile("" : "+s"(ep_n));
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
             const int orow = (GM != 0 ? row_lo : 0) + m0 + r * 16 + r16;
@@ -456,12 +529,19 @@ __global__ __launch_bounds__(512) void qgemm_block3_kernel(const std::conditiona
                 for (int t = 0; t < NT2; ++t) {
                     const int col = unit_col0<BITS, TILEP>(unit0 + 4 * q4) + (t ? f1 : f0) * TILEP;
                     f32x4_t o4 = acc[r][t];
+                    if constexpr (GM == 3) {
+                        const f32x4_t g4 = acc_gate[r][t];
+                        o4 = f32x4_t{silu32(g4[0]) * o4[0], silu32(g4[1]) * o4[1], silu32(g4[2]) * o4[2], silu32(g4[3]) * o4[3]};
+                        // the product is rounded to fp32 and then to T, as the row form's: without this hipcc contracts the multiply
+                        // and the fp16 conversion into one v_fma_mixlo_f16 (one rounding, -0 becomes +0)
+                        asm volatile("" : "+v"(o4));
+                    }
                     if constexpr (GM == 2) { o4[0] *= rw; o4[1] *= rw; o4[2] *= rw; o4[3] *= rw; }
                     if (GM != 0 || a.splitk == 1) {
                         uint2 o;
                         o.x = (uint32_t)NT::from_float(o4[0]) | ((uint32_t)NT::from_float(o4[1]) << 16);
                         o.y = (uint32_t)NT::from_float(o4[2]) | ((uint32_t)NT::from_float(o4[3]) << 16);
-                        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.D) + (size_t)orow * a.N + col) = o;
+                        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.D) + (size_t)orow * (GM == 3 ? ep_n : a.N) + col) = o;
                     } else {
                         *reinterpret_cast<f32x4_t*>(a.partial + ((size_t)split * a.M + orow) * a.N + col) = o4;
                     }

@@ -3,7 +3,8 @@
 // streams an expert's weights once per 32 rows.  Plain and weighted modes (flute_qgemm_grouped_ex / _weighted_ex with the block form)
 // and the SwiGLU mode behind its own entry (flute_qgemm_grouped_glu_blocks), 4 and 2 bits.  3 bits: qgemm_block3.h's 128-row blocks
 // behind the same front end, plain and weighted, through entries of their own (flute_qgemm_grouped_w3_blocks / _weighted_w3_blocks:
-// the old entries keep 3 bits on the row form); the fused SwiGLU launch has no 3-bit block form.
+// the old entries keep 3 bits on the row form), and the fused SwiGLU launch through one more (flute_qgemm_grouped_glu_w3_blocks:
+// qgemm_block3.h GM = 3, with an LDS size of its own).
 #pragma once
 #include "../../include/flute_amd.h"
 #include "kernels.h"
@@ -41,11 +42,16 @@ inline void grouped_block_args(GroupedBlockArgs& a, const GroupedForward& g) {
     a.E = g.E; a.P = g.P;
 }
 
+// The LDS of the 3-bit SwiGLU launch (qgemm_block3.h GM = 3): the 80 KB above and the plane slots of waves 6 / 7 - three stages x two
+// half steps x 1 KB for wave 6's second plane, x 2 KB for wave 7's second and third: 98 KB, one workgroup per compute unit as before.
+constexpr size_t grouped_glu_w3_blocks_lds_bytes() {
+    return grouped_blocks_lds_bytes<3>() + (size_t)(BLK_STAGES * 2 * (1 + 2) * 1024);
+}
+
 // The launch of one resolved kernel: the grid follows from (E, R, N) alone.
 template <int BITS, typename Args>
-int grouped_blocks_enqueue(void (*k)(const Args), Args& a, hipStream_t stream) {
+int grouped_blocks_enqueue(void (*k)(const Args), Args& a, hipStream_t stream, size_t lds = grouped_blocks_lds_bytes<BITS>()) {
     if (!k) return FLUTE_ERR_SHAPE;
-    const size_t lds = grouped_blocks_lds_bytes<BITS>();
     // (above 64 KB; the attribute is per device and setting it is no stream operation: asked for at every launch, as moe_route.hip does)
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
@@ -86,16 +92,29 @@ int qgemm_grouped_w3_blocks_launch(const GroupedForward& g, hipStream_t stream) 
     return grouped_blocks_enqueue<3>(k, a, stream);
 }
 
-// The SwiGLU launch (GM = 3): both stacks, the row index and the rows of Xsrc beside the shared arguments; the same grid.
-template <int BITS>
-int qgemm_grouped_glu_blocks_launch(const GroupedForward& g, hipStream_t stream) {
-    const int dtype = g.dtype, tile_p = g.tile_p;
-    GroupedGluBlockArgs a{};
+// What the SwiGLU launches (GM = 3) add to the shared arguments: the up stack, the row index and the rows of Xsrc.
+inline void grouped_glu_block_args(GroupedGluBlockArgs& a, const GroupedForward& g) {
     grouped_block_args(a, g);
     a.Q_up = reinterpret_cast<const uint32_t*>(g.Q[1]); a.S_up = g.S[1];
     a.QM2_up = reinterpret_cast<const uint32_t*>(g.QM2[1]);
     a.rows = reinterpret_cast<const int*>(g.rows);
     a.Tsrc = g.Tsrc;
+}
+
+// The 3-bit SwiGLU launch (qgemm_block3.h, RT = 8, GM = 3; TileP 32) of one type T: the same grid, an LDS size of its own.
+template <typename T>
+int qgemm_grouped_glu_w3_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    GroupedGluBlockArgs a{};
+    grouped_glu_block_args(a, g);
+    return grouped_blocks_enqueue<3>(g.tile_p == 32 ? qgemm_block3_kernel<T, 8, 3> : nullptr, a, stream, grouped_glu_w3_blocks_lds_bytes());
+}
+
+// The SwiGLU launch (GM = 3): both stacks, the row index and the rows of Xsrc beside the shared arguments; the same grid.
+template <int BITS>
+int qgemm_grouped_glu_blocks_launch(const GroupedForward& g, hipStream_t stream) {
+    const int dtype = g.dtype, tile_p = g.tile_p;
+    GroupedGluBlockArgs a{};
+    grouped_glu_block_args(a, g);
     typedef void (*Kernel)(const GroupedGluBlockArgs);
     Kernel k = nullptr;
     if (tile_p == 32) k = dtype == 0 ? (Kernel)qgemm_block2_kernel<F16, 32, 8, BITS, 3> : (Kernel)qgemm_block2_kernel<BF16, 32, 8, BITS, 3>;

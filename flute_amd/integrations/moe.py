@@ -14,8 +14,9 @@ T k rows (shapes only: no host synchronise), `False` - the default - never: the 
 Stacks of 3-bit experts have a block form too (qgemm_block3.h's 128-row blocks), behind ops of their own,
 `flute_amd.qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` - through `qgemm_grouped*` 3 bits are the row form at
 every count - and `FluteExperts(w3_blocks=...)` opts in the same three ways (`flute_amd.dev.grouped_w3_blocks_form` is its "auto")
-for the unfused gate, up and down launches and the fused path's weighted down launch; the fused GLU launch has no 3-bit block
-form and stays on its row form.  The
+for the unfused gate, up and down launches and the fused path's weighted down launch; the fused GLU launch of 3-bit stacks has its
+block form behind `flute_amd.qgemm_grouped_glu_w3_blocks`, and `FluteExperts(fused=True, w3_glu_blocks=...)` opts in likewise
+(`flute_amd.dev.grouped_glu_w3_blocks_form` is its "auto").  The
 backward's two input-gradient launches have their own pair of forms - slabs and, for 4- / 2-bit stacks with K % 256 == 0 from a
 mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input_grad_blocks.h;
 `flute_amd.dev.grouped_input_grad_form` tells which) - with equal bits, picked the same way.  At 3 bits the block form of the
@@ -279,7 +280,11 @@ class FluteExperts(torch.nn.Module):
     fused forward's weighted down launch - False: `qgemm_grouped` / `qgemm_grouped_weighted`, the row form at 3 bits (the default,
     today's forward bit for bit); True: `qgemm_grouped_w3_blocks` / `qgemm_grouped_weighted_w3_blocks` (raises where a stack is not
     3-bit, not eligible or learnable); "auto": those where `flute_amd.dev.grouped_w3_blocks_form` takes them for the step's T k
-    rows.  The fused GLU launch stays on its row form at 3 bits.
+    rows.  The fused GLU launch is not theirs: `w3_glu_blocks`.
+    `w3_glu_blocks` (with `fused=True`, 3-bit gate and up): which kernel runs the fused GLU launch - False: `qgemm_grouped_glu`'s row
+    form (the default, today's forward bit for bit); True: `qgemm_grouped_glu_w3_blocks` (raises where the stacks are not eligible or
+    learnable); "auto": that launch where `flute_amd.dev.grouped_glu_w3_blocks_form` takes it for the step's T k rows (learnable
+    stacks stay as they are).
     `w3_grad_blocks` (stacks of 3-bit experts): the ops' keyword of that name - which kernel runs the input-gradient launches of the
     backward - False: `qgemm_grouped_input_grad`, the slab form at 3 bits (the default); True: `qgemm_grouped_input_grad_w3_blocks`
     (raises where a stack is not 3-bit, has K % 256 != 0 or is learnable); "auto": that launch where
@@ -300,11 +305,19 @@ class FluteExperts(torch.nn.Module):
                  fused: bool = False, native_routing: bool = False, glu_blocks: Union[bool, str] = False,
                  native_glu_grad: bool = False, native_router_grad: bool = False,
                  wide_routing: Union[bool, str] = False, w3_blocks: Union[bool, str] = False,
-                 w3_grad_blocks: Union[bool, str] = False) -> None:
+                 w3_grad_blocks: Union[bool, str] = False, w3_glu_blocks: Union[bool, str] = False) -> None:
         super().__init__()
         _check_tristate("glu_blocks", glu_blocks)
         _check_tristate("w3_blocks", w3_blocks)
         _check_tristate("w3_grad_blocks", w3_grad_blocks)
+        _check_tristate("w3_glu_blocks", w3_glu_blocks)
+        if w3_glu_blocks is not False and not fused:
+            raise ValueError("FluteExperts: w3_glu_blocks selects the kernel of the fused GLU launch and needs fused=True")
+        if w3_glu_blocks is not False and glu_blocks is not False:
+            raise ValueError("FluteExperts: glu_blocks (4- / 2-bit stacks) and w3_glu_blocks (3-bit stacks) both select the kernel "
+                             "of the fused GLU launch; set one of them")
+        if w3_glu_blocks is not False and not (gate.num_bits == up.num_bits == 3):
+            raise ValueError("FluteExperts: w3_glu_blocks selects the fused GLU kernel of 3-bit stacks; gate and up must be 3-bit")
         if w3_blocks is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
             raise ValueError("FluteExperts: w3_blocks selects the kernels of 3-bit stacks; gate, up and down must be 3-bit")
         if w3_grad_blocks is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
@@ -337,17 +350,19 @@ class FluteExperts(torch.nn.Module):
         self.wide_routing = wide_routing
         self.w3_blocks = w3_blocks
         self.w3_grad_blocks = w3_grad_blocks
+        self.w3_glu_blocks = w3_glu_blocks
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
                      downs: Sequence[FluteLinear], fused: bool = False, native_routing: bool = False,
                      glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
                      native_router_grad: bool = False, wide_routing: Union[bool, str] = False,
-                     w3_blocks: Union[bool, str] = False, w3_grad_blocks: Union[bool, str] = False) -> "FluteExperts":
+                     w3_blocks: Union[bool, str] = False, w3_grad_blocks: Union[bool, str] = False,
+                     w3_glu_blocks: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
                    native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing,
-                   w3_blocks=w3_blocks, w3_grad_blocks=w3_grad_blocks)
+                   w3_blocks=w3_blocks, w3_grad_blocks=w3_grad_blocks, w3_glu_blocks=w3_glu_blocks)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -437,7 +452,8 @@ class FluteExperts(torch.nn.Module):
         gate, up, down = self.gate, self.up, self.down
         num_sms = _stack_num_sms(gate, hidden.device)
         glu, weighted = self._fused_ops(self._takes_glu_blocks(hidden, rows.shape[0], num_sms),
-                                        self._takes_w3_blocks(down, "weighted", rows.shape[0], num_sms, hidden.dtype))
+                                        self._takes_w3_blocks(down, "weighted", rows.shape[0], num_sms, hidden.dtype),
+                                        self._takes_w3_glu_blocks(hidden, rows.shape[0], num_sms))
         h = glu(hidden, offsets, gate.weight, gate.scales, _table_of(gate), up.weight, up.scales, _table_of(up),
                 gate.num_bits, gate.group_size, gate.template_id, num_sms, rows=rows, pos=pos)
         return weighted(h, offsets, down.weight, down.scales, _table_of(down), row_weight, down.num_bits, down.group_size,
@@ -457,6 +473,23 @@ class FluteExperts(torch.nn.Module):
         return flute_amd.dev.grouped_glu_blocks_form(self.num_experts, rows, hidden.shape[0], gate.out_features,
                                                      gate.in_features, gate.num_bits, gate.group_size, gate.template_id,
                                                      num_sms, hidden.dtype) == "blocks"
+
+    def _takes_w3_glu_blocks(self, hidden, rows: int, num_sms: int) -> bool:
+        """Whether this step's fused GLU launch is the 3-bit block one: `w3_glu_blocks`, "auto" resolved from the shapes alone.  The
+        learnable stacks' GLU entries have no such form: True raises on them, "auto" leaves them as they are."""
+        if self.w3_glu_blocks is False:
+            return False
+        gate = self.gate
+        if any(isinstance(m, LearnableGroupedFluteLinear) for m in (gate, self.up, self.down)):
+            if self.w3_glu_blocks is True:
+                raise ValueError("FluteExperts: w3_glu_blocks=True, but a stack is learnable (freeze_experts first, or "
+                                 "w3_glu_blocks='auto')")
+            return False
+        if self.w3_glu_blocks is True:
+            return True
+        return flute_amd.dev.grouped_glu_w3_blocks_form(self.num_experts, rows, hidden.shape[0], gate.out_features,
+                                                        gate.in_features, gate.group_size, gate.template_id, num_sms,
+                                                        hidden.dtype) == "blocks"
 
     def _takes_w3_blocks(self, stack, mode: str, rows: int, num_sms, dtype) -> bool:
         """Whether this step's plain / weighted launch of `stack` is the 3-bit block one: `w3_blocks`, "auto" resolved from the shapes
@@ -494,12 +527,13 @@ class FluteExperts(torch.nn.Module):
         return op(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits, stack.group_size,
                   stack.template_id, num_sms, w3_grad_blocks=grad_blocks)
 
-    def _fused_ops(self, glu_blocks: bool = False, w3_down: bool = False):
+    def _fused_ops(self, glu_blocks: bool = False, w3_down: bool = False, w3_glu: bool = False):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
         scales their gradient, or - when it has a codebook - those that take `_table_of(stack)`, the codebook, in
         `tables2`'s place and give it its gradient too (with grad mode off all of them are the public ops).
         `glu_blocks`: the GLU launch on its block form (`qgemm_grouped_glu_blocks`, the learnable entries' `blocks=True`).
         `w3_down`: the weighted launch on the 3-bit block form (`qgemm_grouped_weighted_w3_blocks`).
+        `w3_glu`: the GLU launch on the 3-bit block form (`qgemm_grouped_glu_w3_blocks`; `_takes_w3_glu_blocks`: no stack is learnable).
         The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one, its
         `w3_grad_blocks` on the public ops of both (the learnable entries have no such keyword)."""
         gate, up, down = self.gate, self.up, self.down
@@ -511,6 +545,8 @@ class FluteExperts(torch.nn.Module):
             qgemm_grouped_glu_learnable_scales if learnable else flute_amd.qgemm_grouped_glu
         if glu_blocks:
             glu = flute_amd.qgemm_grouped_glu_blocks if glu is flute_amd.qgemm_grouped_glu else functools.partial(glu, blocks=True)
+        if w3_glu:
+            glu = flute_amd.qgemm_grouped_glu_w3_blocks
         if self.native_glu_grad:
             glu = functools.partial(glu, native_glu_grad=True)
         weighted = qgemm_grouped_weighted_learnable if has[2] else \

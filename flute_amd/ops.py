@@ -455,19 +455,23 @@ def _launch_plain(input, offsets, weight, scales, table2, layer, form=None):
 # `_launch_glu`'s form for the block launch behind its own entry (flute_qgemm_grouped_glu_blocks): not one of `_GROUPED_FORMS`,
 # which keep their meaning on `qgemm_grouped_glu` ("blocks" raises there)
 _GLU_BLOCKS = "glu_blocks"
+# ... and for the 3-bit block launch behind its entry (flute_qgemm_grouped_glu_w3_blocks)
+_GLU_W3_BLOCKS = "glu_w3_blocks"
+_GLU_ENTRIES = {_GLU_BLOCKS: "qgemm_grouped_glu_blocks", _GLU_W3_BLOCKS: "qgemm_grouped_glu_w3_blocks"}
 _FLUTE_ERR_NUM_BITS, _FLUTE_ERR_SHAPE, _FLUTE_ERR_NULL = -1, -4, -9       # include/flute_amd.h
 
 
 def _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form=None):
     Tsrc = input.shape[0]
     R = Tsrc if rows is None else rows.shape[0]
-    name, form = ("qgemm_grouped_glu_blocks", ()) if form == _GLU_BLOCKS else ("qgemm_grouped_glu_ex", (form,))
+    name, form = (_GLU_ENTRIES[form], ()) if form in _GLU_ENTRIES else ("qgemm_grouped_glu_ex", (form,))
     return _launch_grouped(name, (input, rows, offsets, gw, gs, gt, uw, us, ut), gw, (R, Tsrc),
                            gs.shape[1], (R, gs.shape[1]), layer, form=form)
 
 
-def _require_glu_blocks(name, input, rows, gate_weight, gate_scales, layer):
-    """Raise ValueError where flute_qgemm_grouped_glu_blocks does not serve the shape.  Host only, before anything is launched:
+def _require_glu_blocks(name, input, rows, gate_weight, gate_scales, layer, form=_GLU_BLOCKS):
+    """Raise ValueError where the entry of `form` (flute_qgemm_grouped_glu_blocks, or with `_GLU_W3_BLOCKS` _glu_w3_blocks) does not
+    serve the shape.  Host only, before anything is launched:
     the entry refuses a shape before it looks at a pointer, so it is asked with null pointers (FLUTE_ERR_SHAPE: not served)."""
     num_bits, group_size, template_id, _ = layer
     Tsrc = input.shape[0]
@@ -475,12 +479,14 @@ def _require_glu_blocks(name, input, rows, gate_weight, gate_scales, layer):
     E, P, K = gate_weight.shape
     if max(R, Tsrc) >= 2 ** 31:
         raise ValueError
-    rc = _lib.get().flute_qgemm_grouped_glu_blocks(
+    entry = "flute_" + _GLU_ENTRIES[form]
+    rc = getattr(_lib.get(), entry)(
         _DTYPE_ID[input.dtype], num_bits, group_size, E, R, Tsrc, gate_scales.shape[1], K, P, template_id,
         None, None if rows is None else 1, *(None,) * 8, 0, None)          # (`rows` is compared with null only)
     if rc == _FLUTE_ERR_SHAPE:
+        bits = "3 bits" if form == _GLU_W3_BLOCKS else "4 / 2 bits"
         raise ValueError(f"flute_amd.{name}: the block form of the fused GLU launch is not eligible for this shape "
-                         "(include/flute_amd.h, flute_qgemm_grouped_glu_blocks: 4 / 2 bits, (K / group_size) % 8 == 0, "
+                         f"(include/flute_amd.h, {entry}: {bits}, (K / group_size) % 8 == 0, "
                          "F % 256 == 0, Tsrc * K * 2 below 2^32 - 16)")
     if rc not in (0, _FLUTE_ERR_NULL):
         _lib.check(rc)
@@ -667,8 +673,36 @@ def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_we
                        _GLU_BLOCKS)
 
 
+def qgemm_grouped_glu_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
+                                gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
+                                up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
+                                rows=None, pos=None, native_glu_grad: bool = False, w3_grad_blocks=False) -> torch.Tensor:
+    """`qgemm_grouped_glu` for stacks of 3-bit experts on the block form, for prefill and training row counts: the same operands,
+    formula and rounding (include/flute_amd.h, flute_qgemm_grouped_glu_w3_blocks) on 128-row x 256-column blocks of the dense 3-bit
+    prefill kernel - all of K for gate, then all of K for up, in two fp32 accumulators of the matrix core, a weight dequantised
+    once per 128 rows (qgemm_block3.h, GM = 3).  Same validation and autograd as `qgemm_grouped_glu_blocks` (`native_glu_grad`,
+    and `w3_grad_blocks` as on the sibling 3-bit ops); the backward's recompute of gate and up runs on the 3-bit block launches
+    (`qgemm_grouped_w3_blocks`'s kernel) where they serve the gathered rows - they do unless R * K * 2 nears 2^32 - else as
+    `qgemm_grouped` chooses.  Equal arguments give equal bits; the bits equal `qgemm_grouped_glu`'s on exactly representable inputs
+    and may differ elsewhere.  A shape the form does not serve raises ValueError before anything is launched;
+    `flute_amd.dev.grouped_glu_w3_blocks_form` tells where the form pays."""
+    _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
+                          num_bits, group_size, rows)
+    _validate_grouped_glu_pos(input, rows, pos)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_glu_blocks("qgemm_grouped_glu_w3_blocks", input, rows, gate_weight, gate_scales, layer, _GLU_W3_BLOCKS)
+    _check_w3_grad_blocks("qgemm_grouped_glu_w3_blocks", w3_grad_blocks, num_bits)
+    if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
+        _refuse_stack_grads("qgemm_grouped_glu_w3_blocks", gate_scales, gate_table2, up_scales, up_table2)
+        return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
+                                         gate_table2, up_weight, up_table2, layer, _GLU_W3_BLOCKS, bool(native_glu_grad),
+                                         w3_grad_blocks)
+    return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
+                       _GLU_W3_BLOCKS)
+
+
 class _GroupedGluFunction(torch.autograd.Function):
-    """`qgemm_grouped_glu` (and, with form `_GLU_BLOCKS`, `qgemm_grouped_glu_blocks`) under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
+    """`qgemm_grouped_glu` (and, with form `_GLU_BLOCKS` / `_GLU_W3_BLOCKS`, `qgemm_grouped_glu_blocks` / `_glu_w3_blocks`) under autograd.  The fused forward keeps nothing intermediate, so the backward recomputes
     g and u with two plain grouped launches on the gathered rows, forms dg = dh u sigma(g) (1 + g (1 - sigma(g))) and
     du = dh silu(g) in fp32, and gets dx_sorted from ONE pair-form launch of the input-gradient kernel.  For
     `integrations.learnable` (the op itself refuses scales that require grad) dS_gate = qgemm_grouped_scale_grad(dg,
@@ -682,6 +716,7 @@ class _GroupedGluFunction(torch.autograd.Function):
         ctx.w3_grad_blocks = w3_grad_blocks
         ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
         ctx.native = native
+        ctx.w3_recompute = form == _GLU_W3_BLOCKS
         out = _launch_glu(input, rows, offsets, gw, gs, gt, uw, us, ut, layer, form)
         ctx.save_for_backward(input, offsets, gw, gs, gt, uw, us, ut, *[t for t in (rows, pos) if t is not None])
         ctx.has = (rows is not None, pos is not None)
@@ -696,7 +731,7 @@ class _GroupedGluFunction(torch.autograd.Function):
         pos = index[1] if ctx.has[1] else None
         dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
                                               want_input_grad=ctx.needs_input_grad[0], native=ctx.native,
-                                              w3_grad_blocks=ctx.w3_grad_blocks)
+                                              w3_grad_blocks=ctx.w3_grad_blocks, w3_recompute=ctx.w3_recompute)
         want = ctx.needs_input_grad
         d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
         d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
@@ -704,22 +739,30 @@ class _GroupedGluFunction(torch.autograd.Function):
 
 
 def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad,
-                          native=False, w3_grad_blocks=False):
+                          native=False, w3_grad_blocks=False, w3_recompute=False):
     """The backward of the fused GLU launch: (d input, x_sorted, dg, du) - the gathered rows and the two gradients in T
     that the pair-form launch reads, which the scale gradients read too.  `want_input_grad` false skips the pair-form
     launch and the sum over a token's slots (d input: None).  `native` (the ops' `native_glu_grad`): the gather is
     `moe_gather` and dg, du are `swiglu_grad` on g and u as the plain launches wrote them, in T - two launches in place of
-    the torch chains, whose bits (torch's sigmoid) they do not promise; rows no expert serves are zeros in x, dg and du."""
+    the torch chains, whose bits (torch's sigmoid) they do not promise; rows no expert serves are zeros in x, dg and du.
+    `w3_recompute` (the forward was `qgemm_grouped_glu_w3_blocks`): g and u come from the 3-bit block launch where it serves the
+    gathered rows (a host rule on the shapes), else from the form `qgemm_grouped` chooses."""
     Tsrc = input.shape[0]
+    form = None
+    if w3_recompute:
+        R = Tsrc if rows is None else rows.shape[0]
+        rc = _lib.get().flute_qgemm_grouped_w3_blocks(_DTYPE_ID[input.dtype], layer[0], layer[1], gw.shape[0], R, gs.shape[1],
+                                                      gw.shape[2], gw.shape[1], layer[2], *(None,) * 6, 0, None)
+        form = _W3_BLOCKS if rc in (0, _FLUTE_ERR_NULL) else None
     if native:
         x = input if rows is None else moe_gather(input, rows, offsets)
-        g = _launch_plain(x, offsets, gw, gs, gt, layer)
-        u = _launch_plain(x, offsets, uw, us, ut, layer)
+        g = _launch_plain(x, offsets, gw, gs, gt, layer, form)
+        u = _launch_plain(x, offsets, uw, us, ut, layer, form)
         dg, du = swiglu_grad(g, u, grad_output, offsets)
     else:
         x = input if rows is None else input.index_select(0, rows.clamp(0, Tsrc - 1).long())
-        g = _launch_plain(x, offsets, gw, gs, gt, layer).float()
-        u = _launch_plain(x, offsets, uw, us, ut, layer).float()
+        g = _launch_plain(x, offsets, gw, gs, gt, layer, form).float()
+        u = _launch_plain(x, offsets, uw, us, ut, layer, form).float()
         dh = grad_output.float()
         sig = torch.sigmoid(g)
         dg = (dh * u * sig * (1 + g * (1 - sig))).to(input.dtype)

@@ -40,6 +40,8 @@ extern "C" {
  *    flute_qgemm_grouped_w3_blocks_form
  *    the block form of the grouped input gradient for 3-bit stacks behind its own entries: flute_qgemm_grouped_input_grad_w3_blocks,
  *    flute_qgemm_grouped_input_grad_w3_blocks_form
+ *    the block form of the fused SwiGLU launch for 3-bit stacks behind its own entries: flute_qgemm_grouped_glu_w3_blocks,
+ *    flute_qgemm_grouped_glu_w3_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
  *    the router's backward: flute_moe_weight_grad, flute_moe_gate_grad
  *    the routing over many workgroups: flute_moe_route_wide, flute_moe_gate_route_wide, flute_moe_route_wide_workspace, flute_moe_route_form
@@ -442,6 +444,34 @@ int flute_qgemm_grouped_glu_blocks(int dtype, int num_bits, int group_size, int 
 #define FLUTE_GROUPED_GLU_BLOCKS_MIN_MEAN_ROWS_PARTIAL 48    /* fewer workgroups than compute units */
 int flute_qgemm_grouped_glu_blocks_form(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K,
                                         int template_id, int num_sms);
+
+/* flute_qgemm_grouped_glu_blocks for stacks of 3-bit experts, behind an entry of its own: the same operands, formula, row index,
+ * grid rule, hipGraph capture and malformed-table / non-finite-row contract, on the 128-row x 256-column blocks of the dense 3-bit
+ * prefill kernel (three-plane layout; csrc/qgemm_block3.h GM = 3) - all of K for the gate stack, then all of K for the up stack, two
+ * fp32 accumulators, one rounding.  Equal arguments give equal bits; bits may differ from flute_qgemm_grouped_glu's except on exactly
+ * representable inputs.  The entries above keep their behaviour at 3 bits (flute_qgemm_grouped_glu_blocks refuses them, the row form
+ * serves every count); a caller opts in by calling this one.
+ * It serves: num_bits 3 (TileP 32), (K / group_size) % 8 == 0, F a multiple of 256, Tsrc * K * 2, one expert's scale bytes
+ * F * (K / group_size) * 2 and one expert's packed bytes 3 * (F / 16) * K * 2 each below 2^32 - 16, R at most 2^31 - 257.
+ * Refusals, in flute_qgemm_grouped_glu_blocks's order: flute_qgemm_grouped_glu's; FLUTE_ERR_SHAPE for num_bits != 3 or a shape
+ * outside the list (E == 0 or R == 0 are inside it); E == 0 or R == 0 returns FLUTE_OK without a launch; then FLUTE_ERR_NULL for a
+ * null pointer other than rows.  num_sms is accepted for symmetry and not used. */
+int flute_qgemm_grouped_glu_w3_blocks(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K, int P,
+                                      int template_id, const void* Xsrc, const void* rows, const void* offsets, const void* Qgate,
+                                      const void* Sgate, const void* QM2gate, const void* Qup, const void* Sup, const void* QM2up,
+                                      void* H, int num_sms, void* stream);
+
+/* Which GLU launch a caller should take for a pair of 3-bit stacks: FLUTE_GROUPED_FORM_BLOCKS (flute_qgemm_grouped_glu_w3_blocks)
+ * where the shape is in its list, E >= 1 and the mean rows per expert, R / E, is at least FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS -
+ * or FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL where E * (F / 256) is below num_sms (< 1: 256) -, else
+ * FLUTE_GROUPED_FORM_ROWS (flute_qgemm_grouped_glu), or the negative error the block launch would refuse the layer with (num_bits
+ * != 3: FLUTE_ERR_SHAPE).  Host only; P is taken as 3 * F / 16.  The two constants are measured on the 3-bit GLU launches
+ * (csrc/api_train.hip): each is the smallest swept mean from which the block launch is not slower than the row form
+ * on any swept stack of its kind.  (Both are 24: the row form's time steps up at 17 rows per expert on every stack.) */
+#define FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS 24            /* E * (F / 256) >= num_sms: the experts' column blocks fill the chip */
+#define FLUTE_GROUPED_GLU_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL 24    /* fewer workgroups than compute units */
+int flute_qgemm_grouped_glu_w3_blocks_form(int dtype, int num_bits, int group_size, int E, int R, int Tsrc, int F, int K,
+                                           int template_id, int num_sms);
 
 /* flute_qgemm_grouped with a per-row weight in the epilogue, for the down projection of a mixture-of-experts MLP:
  *   Y[r, :] = round_T( row_weight[r] * acc32 ),   acc32 = the fp32 sum of X[r, :] @ W_e^T,

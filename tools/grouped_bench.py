@@ -901,7 +901,9 @@ class GluForward:
     """`copies` pairs of gate / up stacks of `experts` packed layers [F, K] and `rows` sorted rows read out of rows / 2 source rows
     through an index (top-2 routing); step(i) is silu(gate) * up on copy i, by `how`: "rows" - the fused launch, flute_amd.qgemm_grouped_glu
     (the row form at every count) -, "blocks" - flute_amd.qgemm_grouped_glu_blocks -, "unfused" - the gather, two plain grouped
-    launches on the automatic form, silu and the product.  `weights`: another GluForward whose stacks and activations are shared."""
+    launches on the automatic form, silu and the product; at 3 bits "w3_blocks" - flute_amd.qgemm_grouped_glu_w3_blocks - and
+    "unfused_w3" - moe_gather, two qgemm_grouped_w3_blocks, silu and the product.  `weights`: another GluForward whose stacks and
+    activations are shared."""
 
     def __init__(self, experts, F, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, weights=None):
         import flute_amd
@@ -934,7 +936,11 @@ class GluForward:
             x = self.hidden[self.rows.long()]
             return torch.nn.functional.silu(fa.qgemm_grouped(x, off, self.Q[0][c], self.S[0][c], t2, *a)) * \
                 fa.qgemm_grouped(x, off, self.Q[1][c], self.S[1][c], t2, *a)
-        op = fa.qgemm_grouped_glu_blocks if self.how == "blocks" else fa.qgemm_grouped_glu
+        if self.how == "unfused_w3":
+            x = fa.moe_gather(self.hidden, self.rows, off)
+            return torch.nn.functional.silu(fa.qgemm_grouped_w3_blocks(x, off, self.Q[0][c], self.S[0][c], t2, *a)) * \
+                fa.qgemm_grouped_w3_blocks(x, off, self.Q[1][c], self.S[1][c], t2, *a)
+        op = {"blocks": fa.qgemm_grouped_glu_blocks, "w3_blocks": fa.qgemm_grouped_glu_w3_blocks}.get(self.how, fa.qgemm_grouped_glu)
         return op(self.hidden, off, self.Q[0][c], self.S[0][c], t2, self.Q[1][c], self.S[1][c], t2, *a, rows=self.rows)
 
     def flops(self):
@@ -987,7 +993,15 @@ GLU_LINES = [("mixtral gate_up pair", 8, 14336, 4096, r, 4, "float16") for r in 
 GLU_SWEEP_MEANS = (16, 32, 48, 64, 96, 128)
 GLU_SWEEP_STACKS = [("mixtral gate_up pair", 8, 14336, 4096), ("many-expert 2048 x 2048 pair", 64, 2048, 2048),   # fill the chip
                     ("E 8 4096 x 4096 pair", 8, 4096, 4096)]                                                       # 128 workgroups: does not
-PREFILL_SECTIONS = ("forward", "glu", "sweep", "backward", "glu_sweep", "glu_module", "w3", "w3_sweep")
+PREFILL_SECTIONS = ("forward", "glu", "sweep", "backward", "glu_sweep", "glu_module", "w3", "w3_sweep", "w3_glu", "w3_glu_sweep",
+                    "w3_glu_module")
+# the fused GLU launch of 3-bit stacks (W3G64; profiles/grouped_moe_glu_blocks_w3.json: --only w3_glu w3_glu_sweep w3_glu_module): its
+# row form, the unfused sequence on the 3-bit block launches and flute_amd.qgemm_grouped_glu_w3_blocks; the threshold sweep of the new
+# launch against the row form; the forward of FluteExperts(fused=True, native_routing=True, w3_blocks="auto") with w3_glu_blocks
+# False against "auto"
+W3_GLU_LINES = [(name, experts, F, K, r, dt) for dt in ("float16", "bfloat16") for name, experts, F, K, r in
+                [("mixtral gate_up pair", 8, 14336, 4096, r) for r in (512, 4096, 8192)] +
+                [("many-expert 2048 x 2048 pair", 64, 2048, 2048, 4096)]]
 # 3-bit stacks (W3G64): the row form - what flute_amd.qgemm_grouped runs at every count -, the block launch behind its own op and the
 # per-expert loop; then the threshold sweep of the block launch against the row form (profiles/grouped_moe_prefill_w3.json:
 # --only w3 w3_sweep)
@@ -1146,6 +1160,63 @@ def main_prefill(args, device):
               "us_per_block_round_at_K4096": round(us["w3_blocks"] / max(1.0, nblk / first.num_sms) * 4096 / K, 2),
               "max_abs_diff_blocks_vs_rows": diff, "max_abs_rows": ref, "replays_us": replays})
         del layers, first, a, b
+        torch.cuda.empty_cache()
+    def w3_glu_layers(experts, F, K, counts, dtype, hows):
+        copies = prefill_copies(experts, F, K, 3, stacks=2)
+        first = GluForward(experts, F, K, counts, copies, device, "rows", 3, dtype)
+        layers = {"rows": first}
+        for how in hows:
+            layers[how] = GluForward(experts, F, K, counts, copies, device, how, 3, dtype, weights=first)
+        return layers, copies
+
+    for name, experts, F, K, nrows, dt in (W3_GLU_LINES if want("w3_glu") else ()):
+        dtype = getattr(torch, dt)
+        counts = routing(nrows // 2, seed=nrows // 2) if experts == E else ig_counts(nrows, experts, seed=nrows + experts)
+        layers, copies = w3_glu_layers(experts, F, K, counts, dtype, ("unfused_w3", "w3_blocks"))
+        first = layers["rows"]
+        a, b = layers["w3_blocks"].step(0).float(), first.step(0).float()
+        diff, ref = float((a - b).abs().max()), float(b.abs().max())
+        us, spread, replays = time_forms(layers, args)
+        flop, nblk = first.flops(), sum(-(-c // 128) for c in counts) * (F // 256)
+        emit({"what": "w3 glu", "shape": name, "bits": 3, "dtype": dt, "experts": experts, "F": F, "K": K, "rows": sum(counts),
+              "source_rows": first.hidden.shape[0], "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+              "auto_form": dev.grouped_glu_w3_blocks_form(experts, sum(counts), first.hidden.shape[0], F, K, G, first.tid,
+                                                          first.num_sms, dtype),
+              "us": us, "blocks_over_rows": round(us["w3_blocks"] / us["rows"], 4),
+              "blocks_over_unfused": round(us["w3_blocks"] / us["unfused_w3"], 4),
+              "TFLOPs": {n: round(flop / v * 1e-6, 1) for n, v in us.items()}, "spread": spread, "flop": flop,
+              "rounds_of_256_CUs": round(nblk / first.num_sms, 2),
+              "us_per_block_round_at_K4096": round(us["w3_blocks"] / max(1.0, nblk / first.num_sms) * 4096 / K, 2),
+              "max_abs_diff_blocks_vs_rows": diff, "max_abs_rows": ref, "replays_us": replays})
+        del layers, first, a, b
+        torch.cuda.empty_cache()
+    for name, experts, F, K in (GLU_SWEEP_STACKS if want("w3_glu_sweep") else ()):
+        for mean in W3_SWEEP_MEANS:
+            for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                        ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                layers, copies = w3_glu_layers(experts, F, K, counts, DTYPE, ("w3_blocks",))
+                first = layers["rows"]
+                us, spread, replays = time_forms(layers, args)
+                emit({"what": "w3 glu threshold sweep", "shape": name, "experts": experts, "F": F, "K": K,
+                      "mean_rows_per_expert": mean, "counts": spread_name, "counts_min_max": [min(counts), max(counts)],
+                      "rows": sum(counts), "us": us, "fills_the_chip": bool(experts * (F // 256) >= first.num_sms),
+                      "blocks_over_rows": round(us["w3_blocks"] / us["rows"], 4), "spread": spread,
+                      "auto_form": dev.grouped_glu_w3_blocks_form(experts, sum(counts), first.hidden.shape[0], F, K, G, first.tid,
+                                                                  first.num_sms), "replays_us": replays})
+                del layers, first
+                torch.cuda.empty_cache()
+    if want("w3_glu_module"):
+        copies = prefill_copies(E, 14336, 4096, 3, stacks=3)
+        stacks = step_stacks(copies, device, 3)
+        for tokens in (512, 4096):
+            layers = {"forward " + ("auto" if v else "rows"): ModuleStep(stacks, tokens, device, False, False, w3_blocks="auto",
+                                                                         w3_glu_blocks=v) for v in (False, "auto")}
+            us, spread, replays = time_forms(layers, args)
+            emit({"what": "w3 glu module step", "tokens": tokens, "rows": tokens * TOPK, "experts": E, "top_k": TOPK,
+                  "weight_copies": copies, "us": us, "forward_auto_over_rows": round(us["forward auto"] / us["forward rows"], 4),
+                  "spread": spread, "replays_us": replays})
+            del layers
+        del stacks
         torch.cuda.empty_cache()
     for name, experts, N, K in (SWEEP_STACKS if want("w3_sweep") else ()):
         copies = prefill_copies(experts, N, K, 3)
