@@ -1,5 +1,5 @@
 // Host side of the C ABI, the training and grouped entry points: the dense and grouped parameter gradients with their scratch
-// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient (slabs, blocks, 3-bit blocks).  Of the
+// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient (slabs, blocks, 3-bit blocks, 256-row blocks).  Of the
 // planner they need the layer check alone (host.h).  No device code.
 #include <algorithm>
 
@@ -203,7 +203,10 @@ static int grouped_input_grad_form_auto(int num_bits, int E, int R, int N, int K
 // 155 / 101, 188 / 109, 215 / 124, 263 / 159, 358 / 221, 547 / 286, 712 / 376; Mixtral gate / up (E 8, N 14336, K 4096: 128
 // workgroups, does not fill the chip) 224 / 290, 227 / 299, 256 / 311, 322 / 341, 356 / 371, 439 / 464, 607 / 465, 939 / 424,
 // 1166 / 468.  (8 is the sweep's lowest mean: where the chip is full the 3-bit slab form never led.)
-static int grouped_input_grad(bool w3_blocks, int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+// flute_qgemm_grouped_input_grad_blocks256 (IG_BLOCKS256: `form` ignored; 4 / 2 bits and grouped_input_grad_blocks256_eligible, the 256-row
+// block units) is the third entry behind the same sequence.
+enum IgEntry { IG_EX, IG_W3_BLOCKS, IG_BLOCKS256 };
+static int grouped_input_grad(IgEntry entry, int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
                               int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
                               const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
                               const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form) {
@@ -213,7 +216,11 @@ static int grouped_input_grad(bool w3_blocks, int dtype, int num_bits, int group
     const bool pair = dY2 || Q2 || S2 || QM22;
     if (pair && row_weight) return FLUTE_ERR_SHAPE;               // the pair form takes no row weight
     int f = form;
-    if (w3_blocks) {
+    if (entry == IG_BLOCKS256) {
+        if (num_bits != 4 && num_bits != 2) return FLUTE_ERR_NUM_BITS;
+        if (!grouped_input_grad_blocks256_eligible(num_bits, E, R, N, K)) return FLUTE_ERR_SHAPE;
+        f = FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS;
+    } else if (entry == IG_W3_BLOCKS) {
         if (num_bits != 3) return FLUTE_ERR_NUM_BITS;
         if (!grouped_input_grad_w3_blocks_eligible(E, R, N, K)) return FLUTE_ERR_SHAPE;
         f = FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS;
@@ -233,7 +240,9 @@ static int grouped_input_grad(bool w3_blocks, int dtype, int num_bits, int group
     g.dY[0] = dY; g.Q[0] = Q; g.S[0] = S; g.QM2[0] = QM2;
     g.dY[1] = pair ? dY2 : dY; g.Q[1] = pair ? Q2 : Q; g.S[1] = pair ? S2 : S; g.QM2[1] = pair ? QM22 : QM2;
     g.offsets = offsets; g.row_weight = row_weight; g.dX = dX;
-    return w3_blocks ? qgemm_grouped_input_grad_blocks_unit_b3(g, st) : qgemm_grouped_input_grad_dispatch(g, st);
+    if (entry == IG_BLOCKS256)
+        return num_bits == 4 ? qgemm_grouped_input_grad_blocks256_unit_b4(g, st) : qgemm_grouped_input_grad_blocks256_unit_b2(g, st);
+    return entry == IG_W3_BLOCKS ? qgemm_grouped_input_grad_blocks_unit_b3(g, st) : qgemm_grouped_input_grad_dispatch(g, st);
 }
 
 // flute_qgemm_grouped_scale_grad (table false: S, dT2 and the scratch null) and _table_grad behind their signatures.  The refusals after
@@ -463,7 +472,7 @@ int flute_qgemm_grouped_input_grad_ex(int dtype, int num_bits, int group_size, i
                                       int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
                                       const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
                                       const void* S2, const void* QM22, void* dX, int num_sms, void* stream, int form) {
-    return grouped_input_grad(false, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
+    return grouped_input_grad(IG_EX, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
                               Q2, S2, QM22, dX, num_sms, stream, form);
 }
 
@@ -471,7 +480,7 @@ int flute_qgemm_grouped_input_grad_w3_blocks(int dtype, int num_bits, int group_
                                              int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
                                              const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
                                              const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
-    return grouped_input_grad(true, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
+    return grouped_input_grad(IG_W3_BLOCKS, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight, dY2,
                               Q2, S2, QM22, dX, num_sms, stream, FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS);
 }
 
@@ -485,6 +494,34 @@ int flute_qgemm_grouped_input_grad_w3_blocks_form(int pair, int dtype, int group
     const long long mean = min_mean_rows(K / kGroupedIgBlockK, E, num_sms, FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS,
                                          FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL);
     return (long long)R >= mean * E ? FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS : FLUTE_GROUPED_INPUT_GRAD_FORM_SLABS;
+}
+
+int flute_qgemm_grouped_input_grad_blocks256(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                             int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                             const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                             const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+    return grouped_input_grad(IG_BLOCKS256, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight,
+                              dY2, Q2, S2, QM22, dX, num_sms, stream, FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS);
+}
+
+// The thresholds are grouped_input_grad_form_auto's rule (min_mean_rows: the split by E * (K / 256) against num_sms) on constants of
+// their own, FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS / _PARTIAL and, at 2 bits, _B2 (include/flute_amd.h holds the sweep next to them; 0: never): below them
+// the answer is whatever flute_qgemm_grouped_input_grad_form gives - the 128-row blocks or the slabs.
+int flute_qgemm_grouped_input_grad_blocks256_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
+                                                  int template_id, int num_sms) {
+    (void)pair;                                                    // the pair form is eligible where the single form is
+    Layer l;
+    const int rc = check_grouped(dtype, num_bits, group_size, template_id, E, R, N, K, num_bits * (N / 16), &l);
+    if (rc) return rc;
+    if (grouped_input_grad_blocks256_eligible(num_bits, E, R, N, K)) {
+        const bool b2 = num_bits == 2;                             // the 2-bit launches gain less: constants of their own
+        const long long mean = min_mean_rows(K / kGroupedIgBlockK, E, num_sms,
+                                             b2 ? FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_B2 : FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS,
+                                             b2 ? FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL_B2
+                                                : FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL);
+        if (mean > 0 && (long long)R >= mean * E) return FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256;
+    }
+    return grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
 }
 
 int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,

@@ -100,6 +100,23 @@ inline bool grouped_input_grad_w3_blocks_eligible(int E, int R, int N, int K) {
     return grouped_blocks_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
 }
 
+// The 256-row block form of the input gradient (qgemm_grouped_input_grad_blocks256.h) counts 256-row blocks the same way: expert e
+// owns ceil(max(re - rb, 0) / 256) of them, and its grid holds the most a monotone table can own, floor((T + 255 E) / 256).
+constexpr int kGroupedBlock256Rows = 256;
+inline long long grouped_blocks256_row_blocks(int E, int T) {
+    return ((long long)T + (long long)(kGroupedBlock256Rows - 1) * E) / kGroupedBlock256Rows;
+}
+
+// What the 256-row block form of the input gradient serves (flute_qgemm_grouped_input_grad_blocks256; api_train.hip's refusal and
+// query read this, nothing else decides it): the conditions of grouped_input_grad_blocks_eligible with the 256-row blocks' grid
+// bound and a row index plus a 256-row block that stays an int.
+inline bool grouped_input_grad_blocks256_eligible(int num_bits, int E, int R, int N, int K) {
+    if (num_bits != 4 && num_bits != 2) return false;
+    if (E < 1 || R < 1 || N < 64 || N % 64 || K < kGroupedIgBlockK || K % kGroupedIgBlockK) return false;
+    if (R > 0x7fffffff - 2 * kGroupedBlock256Rows) return false;
+    return grouped_blocks256_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
+}
+
 // The rows [rb, re) of expert e, both ends clamped to [0, R].
 struct GroupedRows {
     int rb, re;

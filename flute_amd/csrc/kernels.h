@@ -155,6 +155,11 @@ inline int qgemm_grouped_input_grad_dispatch(const GroupedInputGrad& g, hipStrea
 // same work split; what it serves: grouped_input_grad_w3_blocks_eligible; inst_grouped_input_grad_blocks_b3.hip).  Its own entry
 // (flute_qgemm_grouped_input_grad_w3_blocks): the dispatch above never takes it, and through the old entries 3 bits stay on the slabs.
 int qgemm_grouped_input_grad_blocks_unit_b3(const GroupedInputGrad& g, hipStream_t stream);
+// the 256-row block form for 4- / 2-bit stacks (qgemm_grouped_input_grad_blocks256.h: one workgroup per 256-row block of an expert x 256 k,
+// a decoded weight fragment feeds twice the MFMAs; what it serves: grouped_input_grad_blocks256_eligible;
+// inst_grouped_input_grad_blocks256_b*.hip).  Its own entry (flute_qgemm_grouped_input_grad_blocks256): the dispatch above never takes it.
+int qgemm_grouped_input_grad_blocks256_unit_b4(const GroupedInputGrad& g, hipStream_t stream);
+int qgemm_grouped_input_grad_blocks256_unit_b2(const GroupedInputGrad& g, hipStream_t stream);
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

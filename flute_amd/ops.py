@@ -518,7 +518,7 @@ def _require_w3_blocks(name, input, weight, scales, layer):
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                   table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                  form=None, w3_grad_blocks=False) -> torch.Tensor:
+                  form=None, w3_grad_blocks=False, grad_blocks256=False) -> torch.Tensor:
     """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
     r in [offsets[e], offsets[e + 1]).  `input` [T, K] holds the rows sorted by expert, `offsets` is an int32 CUDA tensor
     of E + 1 elements (0, non-decreasing, T last), `weight` [E, P, K], `scales` [E, N, K / g] and `table2`
@@ -533,14 +533,18 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     "rows" / "blocks" force one (forcing blocks on a layer that is not eligible raises).  In the block form a malformed table may also leave rows it does name unwritten.
     `w3_grad_blocks` (3-bit stacks only) is read by the backward only: False (the default) - dX is `qgemm_grouped_input_grad`, the slab
     form at 3 bits; True - `qgemm_grouped_input_grad_w3_blocks` (raises where K % 256 != 0); "auto" - that launch where
-    `flute_amd.dev.grouped_input_grad_w3_blocks_form` says "blocks".  The bits of dX are the same in all three."""
+    `flute_amd.dev.grouped_input_grad_w3_blocks_form` says "blocks".  The bits of dX are the same in all three.
+    `grad_blocks256` (4- / 2-bit stacks only) is read by the backward only: False (the default) - dX is `qgemm_grouped_input_grad`;
+    True - `qgemm_grouped_input_grad_blocks256`, the 256-row block form (raises where K % 256 != 0); "auto" - that launch where
+    `flute_amd.dev.grouped_input_grad_blocks256_form` says "blocks256".  The bits of dX are the same in all three."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped", w3_grad_blocks, num_bits)
+    _check_grad_blocks256("qgemm_grouped", grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form, w3_grad_blocks)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form, w3_grad_blocks, grad_blocks256)
     return _launch_plain(input, offsets, weight, scales, table2, layer, form)
 
 
@@ -572,8 +576,8 @@ class _GroupedFunction(torch.autograd.Function):
     backward's parameter gradients are `_grouped_table_grads`: one qgemm_grouped_table_grad launch for both."""
 
     @staticmethod
-    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer, form=None, w3_grad_blocks=False):
-        ctx.w3_grad_blocks = w3_grad_blocks
+    def forward(ctx, input, scales, codebook, offsets, weight, table2, layer, form=None, w3_grad_blocks=False, grad_blocks256=False):
+        ctx.w3_grad_blocks, ctx.grad_blocks256 = w3_grad_blocks, grad_blocks256
         out = _launch_plain(input, offsets, weight, scales, table2, layer, form)
         ctx.save_for_backward(offsets, weight, scales, table2, *((input,) if any(ctx.needs_input_grad[1:3]) else ()))
         ctx.layer = layer
@@ -586,11 +590,11 @@ class _GroupedFunction(torch.autograd.Function):
         offsets, weight, scales, table2, *saved_input = ctx.saved_tensors
         d_input = d_scales = d_codebook = None
         if ctx.needs_input_grad[0]:
-            d_input = _backward_input_grad(ctx.w3_grad_blocks, grad_output, offsets, weight, scales, table2, ctx.layer)
+            d_input = _backward_input_grad(ctx.w3_grad_blocks, ctx.grad_blocks256, grad_output, offsets, weight, scales, table2, ctx.layer)
         if any(ctx.needs_input_grad[1:3]):
             d_scales, d_codebook = _grouped_table_grads(grad_output, saved_input[0], offsets, weight, scales, table2,
                                                         ctx.layer, *ctx.needs_input_grad[1:3], ctx.scalar)
-        return (d_input, d_scales, d_codebook) + (None,) * 6
+        return (d_input, d_scales, d_codebook) + (None,) * 7
 
 
 def _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
@@ -619,7 +623,8 @@ def _validate_grouped_glu_pos(input, rows, pos):
 def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                      rows=None, pos=None, form=None, native_glu_grad: bool = False, w3_grad_blocks=False) -> torch.Tensor:
+                      rows=None, pos=None, form=None, native_glu_grad: bool = False, w3_grad_blocks=False,
+                      grad_blocks256=False) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
@@ -634,17 +639,20 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     `native_glu_grad` is read by the backward only: False (the default) forms the gather and dg, du with torch ops, bit for bit
     as before; True runs `moe_gather` and `swiglu_grad` in their place (two launches, g and u never widened to fp32 tensors),
     whose bits differ from the torch chain's within `flute_swiglu_grad`'s error account.  The forward's bits do not depend on it.
-    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's pair-form input-gradient launch on 3-bit stacks."""
+    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's pair-form input-gradient launch on 3-bit stacks;
+    `grad_blocks256` as `qgemm_grouped`'s: the same on 4- / 2-bit stacks."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped_glu", w3_grad_blocks, num_bits)
+    _check_grad_blocks256("qgemm_grouped_glu", grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad), w3_grad_blocks)
+                                         gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad), w3_grad_blocks,
+                                         grad_blocks256)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        form)
 
@@ -652,23 +660,25 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
 def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                              gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                              up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                             rows=None, pos=None, native_glu_grad: bool = False) -> torch.Tensor:
+                             rows=None, pos=None, native_glu_grad: bool = False, grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped_glu` on the block form, for prefill and training row counts: the same operands, formula and rounding
     (include/flute_amd.h, flute_qgemm_grouped_glu_blocks) on 128-row x 256-column blocks of the dense prefill kernel - all of K
     for gate, then all of K for up, in two fp32 accumulators of the matrix core, a weight dequantised once per 128 rows
     (qgemm_block2.h, GM = 3).  Same validation, same autograd (the backward recomputes gate and up and never depends on which
     kernel ran the forward).  Equal arguments give equal bits; the bits equal `qgemm_grouped_glu`'s on exactly representable
     inputs and may differ elsewhere (another summation order).  A shape the form does not serve raises ValueError before
-    anything is launched; `flute_amd.dev.grouped_glu_blocks_form` tells where the form pays.  `native_glu_grad` as there."""
+    anything is launched; `flute_amd.dev.grouped_glu_blocks_form` tells where the form pays.  `native_glu_grad` and `grad_blocks256` as there."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
     layer = (num_bits, group_size, template_id, num_sms)
     _require_glu_blocks("qgemm_grouped_glu_blocks", input, rows, gate_weight, gate_scales, layer)
+    _check_grad_blocks256("qgemm_grouped_glu_blocks", grad_blocks256, num_bits)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu_blocks", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
-                                         gate_table2, up_weight, up_table2, layer, _GLU_BLOCKS, bool(native_glu_grad))
+                                         gate_table2, up_weight, up_table2, layer, _GLU_BLOCKS, bool(native_glu_grad), False,
+                                         grad_blocks256)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        _GLU_BLOCKS)
 
@@ -712,8 +722,8 @@ class _GroupedGluFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, gs, us, gc, uc, rows, pos, offsets, gw, gt, uw, ut, layer, form=None, native=False,
-                w3_grad_blocks=False):
-        ctx.w3_grad_blocks = w3_grad_blocks
+                w3_grad_blocks=False, grad_blocks256=False):
+        ctx.w3_grad_blocks, ctx.grad_blocks256 = w3_grad_blocks, grad_blocks256
         ctx.scalar = (gc is not None and gc.ndim == 2, uc is not None and uc.ndim == 2)
         ctx.native = native
         ctx.w3_recompute = form == _GLU_W3_BLOCKS
@@ -731,15 +741,16 @@ class _GroupedGluFunction(torch.autograd.Function):
         pos = index[1] if ctx.has[1] else None
         dx, x, dg, du = _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, ctx.layer,
                                               want_input_grad=ctx.needs_input_grad[0], native=ctx.native,
-                                              w3_grad_blocks=ctx.w3_grad_blocks, w3_recompute=ctx.w3_recompute)
+                                              w3_grad_blocks=ctx.w3_grad_blocks, w3_recompute=ctx.w3_recompute,
+                                              grad_blocks256=ctx.grad_blocks256)
         want = ctx.needs_input_grad
         d_gs, d_gc = _grouped_table_grads(dg, x, offsets, gw, gs, gt, ctx.layer, want[1], want[3], ctx.scalar[0])
         d_us, d_uc = _grouped_table_grads(du, x, offsets, uw, us, ut, ctx.layer, want[2], want[4], ctx.scalar[1])
-        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 11
+        return (dx, d_gs, d_us, d_gc, d_uc) + (None,) * 12
 
 
 def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw, us, ut, layer, want_input_grad,
-                          native=False, w3_grad_blocks=False, w3_recompute=False):
+                          native=False, w3_grad_blocks=False, w3_recompute=False, grad_blocks256=False):
     """The backward of the fused GLU launch: (d input, x_sorted, dg, du) - the gathered rows and the two gradients in T
     that the pair-form launch reads, which the scale gradients read too.  `want_input_grad` false skips the pair-form
     launch and the sum over a token's slots (d input: None).  `native` (the ops' `native_glu_grad`): the gather is
@@ -769,7 +780,7 @@ def _grouped_glu_backward(grad_output, input, rows, pos, offsets, gw, gs, gt, uw
         du = (dh * (g * sig)).to(input.dtype)
     if not want_input_grad:
         return None, x, dg, du
-    dx = _backward_input_grad(w3_grad_blocks, dg, offsets, gw, gs, gt, layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
+    dx = _backward_input_grad(w3_grad_blocks, grad_blocks256, dg, offsets, gw, gs, gt, layer, grad_output2=du, weight2=uw, scales2=us, table22=ut)
     if rows is not None:
         if pos is not None:
             dx = moe_combine(dx, pos, offsets)
@@ -786,7 +797,7 @@ def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weigh
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                            table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
                            template_id: int, num_sms=None, form=None, native_router_grad: bool = False,
-                           w3_grad_blocks=False) -> torch.Tensor:
+                           w3_grad_blocks=False, grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
@@ -796,15 +807,17 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     d row_weight and d input from the unweighted input gradient with torch ops, bit for bit as before; True runs one
     `moe_weight_grad` launch in their place - d input has the same bits, d row_weight is summed in `flute_moe_weight_grad`'s
     fixed order, not torch's.  The forward's bits do not depend on it.
-    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's input-gradient launch on 3-bit stacks."""
+    `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's input-gradient launch on 3-bit stacks; `grad_blocks256`
+    as `qgemm_grouped`'s: the same on 4- / 2-bit stacks."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped_weighted", w3_grad_blocks, num_bits)
+    _check_grad_blocks256("qgemm_grouped_weighted", grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
         return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form,
-                                              bool(native_router_grad), w3_grad_blocks)
+                                              bool(native_router_grad), w3_grad_blocks, grad_blocks256)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
@@ -838,8 +851,8 @@ class _GroupedWeightedFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, row_weight, scales, codebook, offsets, weight, table2, layer, form=None, native=False,
-                w3_grad_blocks=False):
-        ctx.w3_grad_blocks = w3_grad_blocks
+                w3_grad_blocks=False, grad_blocks256=False):
+        ctx.w3_grad_blocks, ctx.grad_blocks256 = w3_grad_blocks, grad_blocks256
         ctx.save_for_backward(input, row_weight, offsets, weight, scales, table2)
         ctx.layer = layer
         ctx.native = native
@@ -854,25 +867,26 @@ class _GroupedWeightedFunction(torch.autograd.Function):
         d_input = d_weight = None
         if want_input or want_weight:
             d_input, d_weight = _grouped_weighted_backward(grad_output, *ctx.saved_tensors, ctx.layer, want_input,
-                                                           want_weight, native=ctx.native, w3_grad_blocks=ctx.w3_grad_blocks)
+                                                           want_weight, native=ctx.native, w3_grad_blocks=ctx.w3_grad_blocks,
+                                                           grad_blocks256=ctx.grad_blocks256)
         d_scales, d_codebook = _grouped_table_grads(grad_output, input, offsets, weight, scales, table2, ctx.layer,
                                                     want_scales, want_codebook, ctx.scalar, row_weight=row_weight)
-        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 7
+        return (d_input, d_weight, d_scales, d_codebook) + (None,) * 8
 
 
 def _grouped_weighted_backward(grad_output, input, row_weight, offsets, weight, scales, table2, layer, want_input,
-                               want_weight, native=False, w3_grad_blocks=False):
+                               want_weight, native=False, w3_grad_blocks=False, grad_blocks256=False):
     """(d input, d row_weight) of the weighted launch.  `native` (the ops' `native_router_grad`): with `want_weight` the
     unweighted input-gradient launch is followed by one `moe_weight_grad` launch in place of the torch lines below."""
     stack = (offsets, weight, scales, table2)
     if not want_weight:
-        return _backward_input_grad(w3_grad_blocks, grad_output, *stack, layer, row_weight=row_weight), None
+        return _backward_input_grad(w3_grad_blocks, grad_blocks256, grad_output, *stack, layer, row_weight=row_weight), None
     if native:
-        d_weight, d_input = moe_weight_grad(_backward_input_grad(w3_grad_blocks, grad_output, *stack, layer), input, row_weight,
+        d_weight, d_input = moe_weight_grad(_backward_input_grad(w3_grad_blocks, grad_blocks256, grad_output, *stack, layer), input, row_weight,
                                             offsets, want_input_grad=want_input)
         return d_input, d_weight
     R = input.shape[0]
-    dh = _backward_input_grad(w3_grad_blocks, grad_output, *stack, layer).float()
+    dh = _backward_input_grad(w3_grad_blocks, grad_blocks256, grad_output, *stack, layer).float()
     served = torch.arange(R, device=input.device) < offsets[-1].clamp(0, R)
     # (a row no expert serves may hold anything in `input`: its dH' is zero, and the where keeps 0 x NaN out)
     d_weight = torch.where(served, (dh * input.float()).sum(dim=1), torch.zeros((), device=input.device))
@@ -989,10 +1003,74 @@ def _check_w3_grad_blocks(name, w3_grad_blocks, num_bits):
     return w3_grad_blocks
 
 
-def _backward_input_grad(w3_grad_blocks, grad_output, offsets, weight, scales, table2, layer, **operands):
+def _require_input_grad_blocks256(grad_output, weight, layer):
+    """Raise ValueError where flute_qgemm_grouped_input_grad_blocks256 does not serve the shape.  Host only, before anything is
+    launched: the entry refuses a shape before it looks at a pointer, so it is asked with null pointers."""
+    num_bits, group_size, template_id, _ = layer
+    E, P, K = weight.shape
+    R, N = grad_output.shape
+    if R >= 2 ** 31:
+        raise ValueError
+    rc = _lib.get().flute_qgemm_grouped_input_grad_blocks256(_DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P,
+                                                             template_id, *(None,) * 11, 0, None)
+    if rc in (_FLUTE_ERR_SHAPE, _FLUTE_ERR_NUM_BITS):
+        raise ValueError("flute_amd.qgemm_grouped_input_grad_blocks256: the 256-row block form of the input gradient is not eligible "
+                         "for this layer (include/flute_amd.h, flute_qgemm_grouped_input_grad_blocks256: 4 / 2 bits, K % 256 == 0, "
+                         "at least one expert and one row)")
+    if rc not in (0, _FLUTE_ERR_NULL):
+        _lib.check(rc)
+
+
+def qgemm_grouped_input_grad_blocks256(grad_output: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                                       scales: torch.Tensor, table2: torch.Tensor, num_bits: int, group_size: int,
+                                       template_id: int, num_sms=None, row_weight=None, grad_output2=None, weight2=None,
+                                       scales2=None, table22=None) -> torch.Tensor:
+    """`qgemm_grouped_input_grad` on the 256-row block form, for training row counts of 4- and 2-bit stacks: the same operands
+    (single, row-weighted and pair forms), formula and rounding on one 256-row block of an expert x 256 k per workgroup
+    (qgemm_grouped_input_grad_blocks256.h: a decoded weight fragment feeds twice the MFMAs of the 128-row block form), with the same
+    bits as `qgemm_grouped_input_grad` on all inputs.  Same validation; a layer the form does not serve (3-bit, K % 256 != 0, no
+    rows) raises ValueError before anything is launched; `flute_amd.dev.grouped_input_grad_blocks256_form` tells where the form
+    pays.  Not differentiable itself."""
+    _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
+                                 grad_output2, weight2, scales2, table22)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_input_grad_blocks256(grad_output, weight, layer)
+    tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
+    if _records_grad(*tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_input_grad_blocks256: the backward is once-differentiable (no double backward)")
+    R, N = grad_output.shape
+    return _launch_grouped("qgemm_grouped_input_grad_blocks256", tensors, weight, (R,), N, (R, weight.shape[2]), layer)
+
+
+_GROUPED_INPUT_GRAD_FORM_BLOCKS256 = 3           # include/flute_amd.h: an answer of flute_qgemm_grouped_input_grad_blocks256_form only
+
+
+def _check_grad_blocks256(name, grad_blocks256, num_bits):
+    """The `grad_blocks256` keyword of the grouped forward ops: False, True or "auto", and anything but False on 4- / 2-bit stacks only."""
+    if not (grad_blocks256 is False or grad_blocks256 is True or (isinstance(grad_blocks256, str) and grad_blocks256 == "auto")):
+        raise ValueError(f"flute_amd.{name}: grad_blocks256 is False, True or 'auto', not {grad_blocks256!r}")
+    if grad_blocks256 is not False and num_bits not in (4, 2):
+        raise ValueError(f"flute_amd.{name}: grad_blocks256 selects the input-gradient kernel of 4- / 2-bit stacks; num_bits is {num_bits}")
+    return grad_blocks256
+
+
+def _backward_input_grad(w3_grad_blocks, grad_blocks256, grad_output, offsets, weight, scales, table2, layer, **operands):
     """The input-gradient launch of the plain, GLU (pair form) and weighted backward: `qgemm_grouped_input_grad`, or - the forward
     ops' `w3_grad_blocks` True, or "auto" where flute_qgemm_grouped_input_grad_w3_blocks_form says blocks for these shapes (host
-    only) - `qgemm_grouped_input_grad_w3_blocks`.  The bits are the same either way."""
+    only) - `qgemm_grouped_input_grad_w3_blocks`, or - `grad_blocks256` True (and a row to serve), or "auto" where
+    flute_qgemm_grouped_input_grad_blocks256_form says so - `qgemm_grouped_input_grad_blocks256`.  The bits are the same whichever runs."""
+    if grad_blocks256 is not False and grad_output.shape[0] > 0:
+        take256 = grad_blocks256 is True
+        if not take256:
+            (E, _, K), (R, N) = weight.shape, grad_output.shape
+            rc = _lib.get().flute_qgemm_grouped_input_grad_blocks256_form(
+                int("grad_output2" in operands), _DTYPE_ID[grad_output.dtype], layer[0], layer[1], E, R, N, K, layer[2],
+                _num_sms(layer[3], grad_output.device))
+            if rc < 0:
+                _lib.check(rc)
+            take256 = rc == _GROUPED_INPUT_GRAD_FORM_BLOCKS256
+        if take256:
+            return qgemm_grouped_input_grad_blocks256(grad_output, offsets, weight, scales, table2, *layer, **operands)
     take = w3_grad_blocks is True
     if w3_grad_blocks == "auto":
         (E, _, K), (R, N) = weight.shape, grad_output.shape

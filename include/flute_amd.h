@@ -40,6 +40,8 @@ extern "C" {
  *    flute_qgemm_grouped_w3_blocks_form
  *    the block form of the grouped input gradient for 3-bit stacks behind its own entries: flute_qgemm_grouped_input_grad_w3_blocks,
  *    flute_qgemm_grouped_input_grad_w3_blocks_form
+ *    the 256-row block form of the grouped input gradient behind its own entries: flute_qgemm_grouped_input_grad_blocks256,
+ *    flute_qgemm_grouped_input_grad_blocks256_form
  *    the block form of the fused SwiGLU launch for 3-bit stacks behind its own entries: flute_qgemm_grouped_glu_w3_blocks,
  *    flute_qgemm_grouped_glu_w3_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
@@ -622,6 +624,52 @@ int flute_qgemm_grouped_input_grad_w3_blocks(int dtype, int num_bits, int group_
 #define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS_MIN_MEAN_ROWS_PARTIAL 128   /* fewer workgroups per row block than compute units */
 int flute_qgemm_grouped_input_grad_w3_blocks_form(int pair, int dtype, int group_size, int E, int R, int N, int K, int template_id,
                                                   int num_sms);
+
+/* The 256-row block form of the grouped input gradient for stacks of 4- and 2-bit experts, behind entries of their own:
+ * flute_qgemm_grouped_input_grad with one 256-row block of one expert x 256 k per workgroup, the grid
+ * floor((R + 255 E) / 256) x K / 256 from (E, R, K) alone (csrc/qgemm_grouped_input_grad_blocks256.h): a decoded weight fragment
+ * feeds twice the MFMAs of the 128-row block form.  The arguments, the single, row-weighted and pair forms, the formula, clamping,
+ * the zero rows from offsets[E] on, determinism, capture and the block form's malformed-table contract (256-row blocks in place of
+ * 128-row ones) are as described above, and so is the order in which every output sums over N: the launch gives EQUAL BITS to
+ * flute_qgemm_grouped_input_grad on all inputs.  flute_qgemm_grouped_input_grad, its _ex form (whose `form` still takes 0, 1, 2 and
+ * nothing else) and flute_qgemm_grouped_input_grad_form keep their behaviour; a caller opts in by calling this.
+ * It serves: num_bits 4 or 2, E >= 1, R >= 1, K a positive multiple of 256, N a multiple of 64, R <= 2^31 - 513 and a 31-bit grid.
+ * Refusals, before anything is enqueued or dereferenced, in this order: flute_qgemm_grouped_input_grad's (dtype, the layer checks,
+ * FLUTE_ERR_SHAPE for P or a negative E / R, FLUTE_ERR_SHAPE for a row_weight together with any pointer of the pair form);
+ * FLUTE_ERR_NUM_BITS for num_bits 3; FLUTE_ERR_SHAPE for a shape outside the list above; then FLUTE_ERR_NULL as the old entry gives
+ * it.  num_sms is accepted for symmetry and not used. */
+int flute_qgemm_grouped_input_grad_blocks256(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                             int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                             const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                             const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
+
+/* Which launch a caller should take for the input gradient of a stack of 4- or 2-bit experts:
+ * FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256 (the entry above) where the shape is in its list and the mean rows per expert, R / E, is at
+ * least FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS - where one row block per expert already fills the chip,
+ * E * (K / 256) >= num_sms (< 1: 256) - or FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL where it does not (at 2 bits the
+ * constants of those names with _B2; a constant of 0: never on that kind of shape); else what flute_qgemm_grouped_input_grad_form answers (_SLABS or _BLOCKS, the old entries), or the
+ * negative error the old entries would refuse the layer with.  Host only: no pointers, nothing is enqueued; pair != 0: the pair form
+ * (the same rule); P is taken as num_bits * N / 16.  FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256 is an answer of this query only:
+ * flute_qgemm_grouped_input_grad_ex refuses it as a `form`. */
+#define FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256 3
+/* Measured (profiles/grouped_moe_input_grad_blocks256.json, "b256 threshold sweep": G64, us of the 128-row block form / this launch,
+ * two alternating passes each, R / E = 128, 256, 512, 1024, 2048, even counts; the routed draws, bf16 and the spreads - below 3 % -
+ * are in the file).  Each constant is the smallest swept mean from which this launch is not slower on any swept stack of its kind
+ * at that bit width, on even and routed counts, fp16 and bf16; 0: there is no such mean and the query never answers _BLOCKS256.
+ *   4 bits, fp16, the chip full: Mixtral down (E 8, N 4096, K 14336) 211 / 211, 404 / 366, 698 / 720, 1359 / 1222, 2689 / 2376;
+ *                 E 64 2048 x 2048 115 / 116, 220 / 204, 437 / 410, 868 / 807, 1720 / 1619
+ *   4 bits, fp16, not full: Mixtral gate / up (E 8, N 14336, K 4096) 339 / 338, 347 / 606, 678 / 620, 1331 / 1231, 2640 / 2473;
+ *                 its pair form 687 / 681, 710 / 1227, 1381 / 1228, 2694 / 2437, 5376 / 4906
+ *     (routed counts at a mean of 512 - 490 to 532 rows: a third, nearly empty 256-row block per expert - 901 / 1061 and 1889 / 2173)
+ *   2 bits, fp16, the chip full: Mixtral down 214 / 218, 414 / 389, 695 / 763, 1347 / 1289, 2650 / 2501;
+ *                 E 64 2048 x 2048 123 / 123, 235 / 257, 457 / 473, 903 / 921, 1829 / 1809 (2048 is the sweep's last mean)
+ *   2 bits, fp16, not full: Mixtral gate / up 346 / 351, 350 / 644, 687 / 660, 1375 / 1345, 2773 / 2810 - slower again at 2048: never. */
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS 1024          /* 4 bits, E * (K / 256) >= num_sms: the experts' k blocks fill the chip */
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL 1024  /* 4 bits, fewer workgroups per row block than compute units */
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_B2 2048       /* 2 bits, the chip full */
+#define FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL_B2 0  /* 2 bits, not full: the launch wins at no swept mean */
+int flute_qgemm_grouped_input_grad_blocks256_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
+                                                  int template_id, int num_sms);
 
 /* The gradient of the scales of a stack flute_qgemm_grouped multiplies by, in ONE launch: flute_qgemm_scale_grad for every
  * expert over the rows the device-side table gives it.  With b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):

@@ -7,6 +7,7 @@
     python tools/grouped_bench.py --mode gate_limited [--out profiles/grouped_moe_gate_limited.json]
     python tools/grouped_bench.py --mode input_grad [--only-swiglu-grad] [--out profiles/grouped_moe_input_grad_blocks.json]
     python tools/grouped_bench.py --mode input_grad --only w3        (profiles/grouped_moe_input_grad_blocks_w3.json)
+    python tools/grouped_bench.py --mode input_grad --only b256      (profiles/grouped_moe_input_grad_blocks256.json)
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
@@ -594,7 +595,7 @@ def ig_counts(rows, experts, seed):
 
 class InputGrad:
     """`copies` stacks of `experts` packed layers [N, K] (`pair`: two of them, and two dY); step(i) is dX [R, K] = dY [R, N] @ W_e on
-    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto", or "w3_blocks", the 3-bit block launch - or, "loop", the per-expert loop of dequantize + mm on row
+    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto", or "w3_blocks", the 3-bit block launch, or "b256", the 256-row block launch - or, "loop", the per-expert loop of dequantize + mm on row
     ranges the host knows.  `weights`: another InputGrad of the same stack whose weight copies are shared."""
 
     def __init__(self, experts, N, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, pair=False, weights=None):
@@ -627,9 +628,10 @@ class InputGrad:
         c = i % self.Q[0].shape[0]
         if self.how != "loop":
             second = dict(grad_output2=self.dY[1], weight2=self.Q[1][c], scales2=self.S[1][c], table22=self.tables2) if self.pair else {}
-            if self.how == "w3_blocks":                   # the 3-bit block launch behind its own op
-                return self.fa.qgemm_grouped_input_grad_w3_blocks(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2,
-                                                                  self.bits, G, self.tid, self.num_sms, **second)
+            if self.how in ("w3_blocks", "b256"):         # the 3-bit and the 256-row block launch behind their own ops
+                op = self.fa.qgemm_grouped_input_grad_w3_blocks if self.how == "w3_blocks" else self.fa.qgemm_grouped_input_grad_blocks256
+                return op(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G, self.tid, self.num_sms,
+                          **second)
             return self.fa.qgemm_grouped_input_grad(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G,
                                                     self.tid, self.num_sms, form=None if self.how == "auto" else self.how, **second)
         out = []
@@ -1372,6 +1374,76 @@ def _w3_ig_thresholds():
 W3_IG_THRESHOLDS = _w3_ig_thresholds()
 
 
+# the 256-row block form (--mode input_grad --only b256; profiles/grouped_moe_input_grad_blocks256.json): the sweep behind
+# FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS[_PARTIAL] - the new launch against the 128-row block form - and the lines on which
+# the per-expert loop leads the 128-row form.  The fp16 4-bit sweep runs first: a run cut short keeps what the rule rests on.
+B256_SWEEP_MEANS = (128, 256, 512, 1024, 2048)
+B256_SWEEP_STACKS = [("mixtral gate_up", 8, 14336, 4096, False), ("mixtral down", 8, 4096, 14336, False),
+                     ("mixtral gate_up pair", 8, 14336, 4096, True), ("many-expert 2048 x 2048", 64, 2048, 2048, False)]
+B256_LOOP_LINES = [("mixtral down", 8, 4096, 14336, 4096), ("mixtral down", 8, 4096, 14336, 8192), ("mixtral gate_up", 8, 14336, 4096, 8192)]
+
+
+def main_input_grad_b256(args, device):
+    """--mode input_grad --only b256: the 256-row block launch against the 128-row block form (and, on B256_LOOP_LINES, the per-expert
+    loop), alternating in one process."""
+    from flute_amd import dev
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        with open(args.out, "w") as f:                # (rewritten after every line: a long run that is cut short keeps its lines)
+            json.dump({"what": "grouped input gradient of 4- / 2-bit stacks (G64) at training row counts: the 128-row block form "
+                               "(flute_amd.qgemm_grouped_input_grad, form='blocks'), the 256-row block launch "
+                               "(flute_amd.qgemm_grouped_input_grad_blocks256) and, on the loop lines, a per-expert loop of "
+                               "flute_amd.dequantize + torch.mm; hipGraph replays, device-clock stamps, cold caches, median of the "
+                               "replays, two alternating passes of each contender in one process",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name, experts, N, K, nrows in B256_LOOP_LINES:
+        counts = ig_counts(nrows, experts, seed=nrows + experts)
+        copies = prefill_copies(experts, N, K, BITS)
+        first = InputGrad(experts, N, K, counts, copies, device, "blocks")
+        layers = {"blocks": first}
+        for how in ("b256", "loop"):
+            layers[how] = InputGrad(experts, N, K, counts, copies, device, how, weights=first)
+        equal = bool(torch.equal(layers["b256"].step(0).view(torch.int16), first.step(0).view(torch.int16)))
+        us, spread, replays = time_forms(layers, args)
+        emit({"what": "b256 against the loop", "shape": name, "bits": BITS, "dtype": "float16", "experts": experts, "N": N, "K": K,
+              "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies, "us": us,
+              "b256_over_blocks": round(us["b256"] / us["blocks"], 4), "b256_over_loop": round(us["b256"] / us["loop"], 4),
+              "blocks_over_loop": round(us["blocks"] / us["loop"], 4), "spread": spread, "b256_bits_equal_blocks": equal,
+              "replays_us": replays})
+        del layers, first
+        torch.cuda.empty_cache()
+    for dt, bits in (("float16", 4), ("bfloat16", 4), ("float16", 2), ("bfloat16", 2)):
+        dtype = getattr(torch, dt)
+        for name, experts, N, K, pair in B256_SWEEP_STACKS:
+            copies = prefill_copies(experts, N, K, bits, stacks=2 if pair else 1)
+            first = None
+            for mean in B256_SWEEP_MEANS:
+                for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                            ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                    layers = {}
+                    for how in ("blocks", "b256"):
+                        layers[how] = InputGrad(experts, N, K, counts, copies, device, how, bits, dtype, pair, weights=first)
+                        first = first or layers[how]
+                    us, spread, replays = time_forms(layers, args)
+                    emit({"what": "b256 threshold sweep", "shape": name, "bits": bits, "dtype": dt, "pair": pair, "experts": experts,
+                          "N": N, "K": K, "mean_rows_per_expert": mean, "counts": spread_name, "counts_min_max": [min(counts), max(counts)],
+                          "rows": sum(counts), "fills_the_chip": experts * (K // 256) >= first.num_sms, "us": us,
+                          "b256_over_blocks": round(us["b256"] / us["blocks"], 4), "spread": spread,
+                          "auto_form": dev.grouped_input_grad_blocks256_form(experts, sum(counts), N, K, bits, G, first.tid,
+                                                                             first.num_sms, dtype, pair),
+                          "replays_us": replays})
+                    del layers
+            del first
+            torch.cuda.empty_cache()
+    print("wrote", args.out)
+
+
 def main_input_grad_forms(args, device):
     """--mode input_grad: the two forms of the grouped input gradient, the automatic rule and the per-expert loop, in one process."""
     from flute_amd import dev
@@ -2012,8 +2084,9 @@ def main():
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
-    ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS, default=None,
-                    help="--mode prefill: the sections to run (default: all) - " + ", ".join(PREFILL_SECTIONS))
+    ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS + ("b256",), default=None,
+                    help="--mode prefill: the sections to run (default: all) - " + ", ".join(PREFILL_SECTIONS) +
+                         "; --mode input_grad: w3 or b256, that section alone")
     ap.add_argument("--only-swiglu-grad", action="store_true",
                     help="--mode input_grad: its last section alone, the backward step with native_glu_grad off and on")
     ap.add_argument("--out", default=None)
@@ -2060,6 +2133,9 @@ def main():
         if args.only == ["w3"]:
             args.out = os.path.join(os.path.dirname(args.out), "grouped_moe_input_grad_blocks_w3.json")
             return main_input_grad_w3(args, device)
+        if args.only == ["b256"]:
+            args.out = os.path.join(os.path.dirname(args.out), "grouped_moe_input_grad_blocks256.json")
+            return main_input_grad_b256(args, device)
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
     bits = args.bits
