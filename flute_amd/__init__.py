@@ -40,6 +40,7 @@ qgemm_grouped_glu_w3_blocks = ops.qgemm_grouped_glu_w3_blocks   # the fused SwiG
 qgemm_grouped_input_grad = ops.qgemm_grouped_input_grad
 qgemm_grouped_input_grad_w3_blocks = ops.qgemm_grouped_input_grad_w3_blocks   # 3-bit stacks on 128-row x 256-k blocks, the same bits
 qgemm_grouped_input_grad_blocks256 = ops.qgemm_grouped_input_grad_blocks256   # 4- / 2-bit stacks on 256-row x 256-k blocks, the same bits
+qgemm_grouped_input_grad_w3_blocks256 = ops.qgemm_grouped_input_grad_w3_blocks256   # 3-bit stacks on 256-row x 256-k blocks, the same bits
 # the gradient of a stack's scales [E, N, K / g], one launch over the same device-side row table; the entry points that train
 # the experts' scales through it: flute_amd.integrations.learnable.qgemm_grouped*_learnable_scales, make_experts_learnable
 qgemm_grouped_scale_grad = ops.qgemm_grouped_scale_grad

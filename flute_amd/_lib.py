@@ -83,6 +83,8 @@ SYMBOLS = {
     "flute_qgemm_grouped_input_grad_w3_blocks_form": (c_int, [c_int] * 9),
     "flute_qgemm_grouped_input_grad_blocks256": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p]),
     "flute_qgemm_grouped_input_grad_blocks256_form": (c_int, [c_int] * 10),
+    "flute_qgemm_grouped_input_grad_w3_blocks256": (c_int, [c_int] * 9 + [c_void_p] * 11 + [c_int, c_void_p]),
+    "flute_qgemm_grouped_input_grad_w3_blocks256_form": (c_int, [c_int] * 9),
     "flute_qgemm_grouped_scale_grad": (c_int, [c_int] * 9 + [c_void_p] * 7 + [c_int, c_void_p]),
     "flute_qgemm_grouped_table_grad": (c_int, [c_int] * 9 + [c_void_p] * 10 + [c_size_t, c_int, c_void_p]),
     "flute_qgemm_grouped_table_grad_scratch_bytes": (c_size_t, [c_int] * 5),

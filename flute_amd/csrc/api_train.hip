@@ -1,5 +1,5 @@
 // Host side of the C ABI, the training and grouped entry points: the dense and grouped parameter gradients with their scratch
-// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient (slabs, blocks, 3-bit blocks, 256-row blocks).  Of the
+// queries, the grouped forward launches (rows, blocks, GLU blocks, 3-bit blocks) with their form queries, and the grouped input gradient (slabs, blocks, 3-bit blocks, 256-row blocks, 3-bit 256-row blocks).  Of the
 // planner they need the layer check alone (host.h).  No device code.
 #include <algorithm>
 
@@ -204,8 +204,9 @@ static int grouped_input_grad_form_auto(int num_bits, int E, int R, int N, int K
 // workgroups, does not fill the chip) 224 / 290, 227 / 299, 256 / 311, 322 / 341, 356 / 371, 439 / 464, 607 / 465, 939 / 424,
 // 1166 / 468.  (8 is the sweep's lowest mean: where the chip is full the 3-bit slab form never led.)
 // flute_qgemm_grouped_input_grad_blocks256 (IG_BLOCKS256: `form` ignored; 4 / 2 bits and grouped_input_grad_blocks256_eligible, the 256-row
-// block units) is the third entry behind the same sequence.
-enum IgEntry { IG_EX, IG_W3_BLOCKS, IG_BLOCKS256 };
+// block units) is the third entry behind the same sequence, flute_qgemm_grouped_input_grad_w3_blocks256 (IG_W3_BLOCKS256: `form` ignored;
+// 3 bits and grouped_input_grad_w3_blocks256_eligible, the 3-bit 256-row block unit) the fourth.
+enum IgEntry { IG_EX, IG_W3_BLOCKS, IG_BLOCKS256, IG_W3_BLOCKS256 };
 static int grouped_input_grad(IgEntry entry, int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
                               int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
                               const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
@@ -219,6 +220,10 @@ static int grouped_input_grad(IgEntry entry, int dtype, int num_bits, int group_
     if (entry == IG_BLOCKS256) {
         if (num_bits != 4 && num_bits != 2) return FLUTE_ERR_NUM_BITS;
         if (!grouped_input_grad_blocks256_eligible(num_bits, E, R, N, K)) return FLUTE_ERR_SHAPE;
+        f = FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS;
+    } else if (entry == IG_W3_BLOCKS256) {
+        if (num_bits != 3) return FLUTE_ERR_NUM_BITS;
+        if (!grouped_input_grad_w3_blocks256_eligible(E, R, N, K)) return FLUTE_ERR_SHAPE;
         f = FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS;
     } else if (entry == IG_W3_BLOCKS) {
         if (num_bits != 3) return FLUTE_ERR_NUM_BITS;
@@ -242,6 +247,7 @@ static int grouped_input_grad(IgEntry entry, int dtype, int num_bits, int group_
     g.offsets = offsets; g.row_weight = row_weight; g.dX = dX;
     if (entry == IG_BLOCKS256)
         return num_bits == 4 ? qgemm_grouped_input_grad_blocks256_unit_b4(g, st) : qgemm_grouped_input_grad_blocks256_unit_b2(g, st);
+    if (entry == IG_W3_BLOCKS256) return qgemm_grouped_input_grad_blocks256_unit_b3(g, st);
     return entry == IG_W3_BLOCKS ? qgemm_grouped_input_grad_blocks_unit_b3(g, st) : qgemm_grouped_input_grad_dispatch(g, st);
 }
 
@@ -522,6 +528,29 @@ int flute_qgemm_grouped_input_grad_blocks256_form(int pair, int dtype, int num_b
         if (mean > 0 && (long long)R >= mean * E) return FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256;
     }
     return grouped_input_grad_form_auto(num_bits, E, R, N, K, num_sms);
+}
+
+int flute_qgemm_grouped_input_grad_w3_blocks256(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                                int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                                const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                                const void* S2, const void* QM22, void* dX, int num_sms, void* stream) {
+    return grouped_input_grad(IG_W3_BLOCKS256, dtype, num_bits, group_size, E, R, N, K, P, template_id, dY, offsets, Q, S, QM2, row_weight,
+                              dY2, Q2, S2, QM22, dX, num_sms, stream, FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS);
+}
+
+// min_mean_rows on FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS / _PARTIAL (include/flute_amd.h holds the sweep next to them;
+// 0: never): below them the answer is flute_qgemm_grouped_input_grad_w3_blocks_form's - the 3-bit 128-row blocks or the slabs.
+int flute_qgemm_grouped_input_grad_w3_blocks256_form(int pair, int dtype, int group_size, int E, int R, int N, int K, int template_id,
+                                                     int num_sms) {
+    Layer l;
+    const int rc = check_grouped(dtype, 3, group_size, template_id, E, R, N, K, 3 * (N / 16), &l);
+    if (rc) return rc;
+    if (grouped_input_grad_w3_blocks256_eligible(E, R, N, K)) {
+        const long long mean = min_mean_rows(K / kGroupedIgBlockK, E, num_sms, FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS,
+                                             FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS_PARTIAL);
+        if (mean > 0 && (long long)R >= mean * E) return FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256;
+    }
+    return flute_qgemm_grouped_input_grad_w3_blocks_form(pair, dtype, group_size, E, R, N, K, template_id, num_sms);
 }
 
 int flute_qgemm_grouped_input_grad(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,

@@ -117,6 +117,15 @@ inline bool grouped_input_grad_blocks256_eligible(int num_bits, int E, int R, in
     return grouped_blocks256_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
 }
 
+// What the 3-bit 256-row block form of the input gradient serves (flute_qgemm_grouped_input_grad_w3_blocks256;
+// qgemm_grouped_input_grad_w3_blocks256.h; api_train.hip's refusal and query read this, nothing else decides it): the conditions of
+// grouped_input_grad_blocks256_eligible on a 3-bit stack (the layer check has already demanded N % 512 == 0).
+inline bool grouped_input_grad_w3_blocks256_eligible(int E, int R, int N, int K) {
+    if (E < 1 || R < 1 || N < 64 || N % 64 || K < kGroupedIgBlockK || K % kGroupedIgBlockK) return false;
+    if (R > 0x7fffffff - 2 * kGroupedBlock256Rows) return false;
+    return grouped_blocks256_row_blocks(E, R) * (K / kGroupedIgBlockK) <= 0x7fffffffLL;
+}
+
 // The rows [rb, re) of expert e, both ends clamped to [0, R].
 struct GroupedRows {
     int rb, re;

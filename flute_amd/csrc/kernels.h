@@ -160,6 +160,10 @@ int qgemm_grouped_input_grad_blocks_unit_b3(const GroupedInputGrad& g, hipStream
 // inst_grouped_input_grad_blocks256_b*.hip).  Its own entry (flute_qgemm_grouped_input_grad_blocks256): the dispatch above never takes it.
 int qgemm_grouped_input_grad_blocks256_unit_b4(const GroupedInputGrad& g, hipStream_t stream);
 int qgemm_grouped_input_grad_blocks256_unit_b2(const GroupedInputGrad& g, hipStream_t stream);
+// the 256-row block form for 3-bit stacks (qgemm_grouped_input_grad_w3_blocks256.h: that work split with the 3-bit block form's three-plane
+// decoder; what it serves: grouped_input_grad_w3_blocks256_eligible; inst_grouped_input_grad_blocks256_b3.hip).  Its own entry
+// (flute_qgemm_grouped_input_grad_w3_blocks256): the dispatch above never takes it.
+int qgemm_grouped_input_grad_blocks256_unit_b3(const GroupedInputGrad& g, hipStream_t stream);
 // the routing of a mixture-of-experts step (moe_route.hip): a stable counting sort of the P = T k (token, slot) pairs by expert in one
 // workgroup, which holds (16 + 1) (E + 1) ints of LDS; ids int32 / int64, weights T / fp32 or null, everything read on the device only
 int moe_route_dispatch(int id_dtype, int weight_dtype, int P, int k, int E, const void* ids, const void* weights,

@@ -138,6 +138,19 @@ def grouped_input_grad_blocks256_form(E: int, rows: int, N: int, K: int, num_bit
     return {1: "slabs", 2: "blocks", 3: "blocks256"}[rc]
 
 
+def grouped_input_grad_w3_blocks256_form(E: int, rows: int, N: int, K: int, group_size: int, template_id: int,
+                                         num_sms: int = 0, dtype: torch.dtype = torch.float16, pair: bool = False) -> str:
+    """Which launch to take for the input gradient of `rows` rows over a stack of E 3-bit experts with [N, K] layers (`pair`: the
+    pair form): "blocks256" - `flute_amd.qgemm_grouped_input_grad_w3_blocks256` - where the layer is eligible for it and rows / E
+    reaches its threshold, else what `grouped_input_grad_w3_blocks_form` answers, "slabs" or "blocks"; host only
+    (flute_qgemm_grouped_input_grad_w3_blocks256_form).  A layer every launch refuses raises."""
+    rc = _lib.get().flute_qgemm_grouped_input_grad_w3_blocks256_form(int(bool(pair)), _DTYPE_ID[dtype], group_size, E, rows, N, K,
+                                                                     template_id, num_sms or 0)
+    if rc < 0:
+        _lib.check(rc)
+    return {1: "slabs", 2: "blocks", 3: "blocks256"}[rc]
+
+
 def moe_route_form(T: int, k: int, E: int, gated: bool = True, num_sms: int = 0) -> str:
     """The routing the automatic rule takes for T tokens, top-k, E experts - "one": `moe_gate_route[_limited]` (`gated`) or
     `moe_route`, one workgroup; "wide": `moe_gate_route_wide` or `moe_route_wide`; host only, shapes alone, monotone in T

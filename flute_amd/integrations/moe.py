@@ -23,7 +23,9 @@ mean of 32 - 128 rows per expert on, 128-row x 256-k blocks (qgemm_grouped_input
 input gradient is again an op of its own, `flute_amd.qgemm_grouped_input_grad_w3_blocks` (the same bits as the slab form), and
 `FluteExperts(w3_grad_blocks=...)` opts the backward in (`flute_amd.dev.grouped_input_grad_w3_blocks_form` is its "auto").  For 4- /
 2-bit stacks a third form of the input gradient, 256-row x 256-k blocks, is the op `flute_amd.qgemm_grouped_input_grad_blocks256` (the
-same bits again); `FluteExperts(grad_blocks256=...)` opts in (`flute_amd.dev.grouped_input_grad_blocks256_form` is its "auto").
+same bits again); `FluteExperts(grad_blocks256=...)` opts in (`flute_amd.dev.grouped_input_grad_blocks256_form` is its "auto").  For
+3-bit stacks that form is `flute_amd.qgemm_grouped_input_grad_w3_blocks256` and `FluteExperts(w3_grad_blocks256=...)`
+(`flute_amd.dev.grouped_input_grad_w3_blocks256_form`).
 `FluteExperts` is the gated MLP of Mixtral / Qwen-MoE / DeepSeek-style blocks on three of them; with `fused=True`
 its forward is two launches (`qgemm_grouped_glu`, `qgemm_grouped_weighted`) instead of three and seven torch ops; with
 `native_routing=True` the torch ops around them - `sort_by_expert` and its glue before, `zeros_like` and `index_add_`
@@ -295,6 +297,11 @@ class FluteExperts(torch.nn.Module):
     the backward - False: `qgemm_grouped_input_grad`, slabs or 128-row blocks as it chooses (the default); True:
     `qgemm_grouped_input_grad_blocks256` (raises where a stack is 3-bit, has K % 256 != 0 or is learnable); "auto": that launch where
     `flute_amd.dev.grouped_input_grad_blocks256_form` takes it for the step's T k rows.  Every gradient has the same bits either way.
+    `w3_grad_blocks256` (stacks of 3-bit experts): the ops' keyword of that name - the 256-row block form of those launches - False:
+    `w3_grad_blocks` decides (the default); True: `qgemm_grouped_input_grad_w3_blocks256`, whatever `w3_grad_blocks` says (raises where
+    a stack is not 3-bit, has K % 256 != 0 or is learnable); "auto": that launch where
+    `flute_amd.dev.grouped_input_grad_w3_blocks256_form` takes it for the step's T k rows, else as `w3_grad_blocks` decides.  The same
+    bits again.
     `native_glu_grad` (with `fused=True`): the ops' keyword of that name - the backward of the fused GLU launch gathers its rows
     with `moe_gather` and forms dg, du with `swiglu_grad` (two HIP launches) where the default runs torch ops; the forward's bits
     are the same either way, the backward's differ within `flute_swiglu_grad`'s error account.
@@ -312,8 +319,12 @@ class FluteExperts(torch.nn.Module):
                  native_glu_grad: bool = False, native_router_grad: bool = False,
                  wide_routing: Union[bool, str] = False, w3_blocks: Union[bool, str] = False,
                  w3_grad_blocks: Union[bool, str] = False, w3_glu_blocks: Union[bool, str] = False,
-                 grad_blocks256: Union[bool, str] = False) -> None:
+                 grad_blocks256: Union[bool, str] = False, w3_grad_blocks256: Union[bool, str] = False) -> None:
         super().__init__()
+        _check_tristate("w3_grad_blocks256", w3_grad_blocks256)
+        if w3_grad_blocks256 is not False and not (gate.num_bits == up.num_bits == down.num_bits == 3):
+            raise ValueError("FluteExperts: w3_grad_blocks256 selects the backward's kernels of 3-bit stacks; gate, up and down must "
+                             "be 3-bit")
         _check_tristate("grad_blocks256", grad_blocks256)
         if grad_blocks256 is not False and not all(m.num_bits in (4, 2) for m in (gate, up, down)):
             raise ValueError("FluteExperts: grad_blocks256 selects the backward's kernels of 4- / 2-bit stacks; gate, up and down "
@@ -363,6 +374,7 @@ class FluteExperts(torch.nn.Module):
         self.w3_grad_blocks = w3_grad_blocks
         self.w3_glu_blocks = w3_glu_blocks
         self.grad_blocks256 = grad_blocks256
+        self.w3_grad_blocks256 = w3_grad_blocks256
 
     @classmethod
     def from_linears(cls, gates: Sequence[FluteLinear], ups: Sequence[FluteLinear],
@@ -370,12 +382,13 @@ class FluteExperts(torch.nn.Module):
                      glu_blocks: Union[bool, str] = False, native_glu_grad: bool = False,
                      native_router_grad: bool = False, wide_routing: Union[bool, str] = False,
                      w3_blocks: Union[bool, str] = False, w3_grad_blocks: Union[bool, str] = False,
-                     w3_glu_blocks: Union[bool, str] = False, grad_blocks256: Union[bool, str] = False) -> "FluteExperts":
+                     w3_glu_blocks: Union[bool, str] = False, grad_blocks256: Union[bool, str] = False,
+                     w3_grad_blocks256: Union[bool, str] = False) -> "FluteExperts":
         return cls(GroupedFluteLinear.from_linears(gates), GroupedFluteLinear.from_linears(ups),
                    GroupedFluteLinear.from_linears(downs), fused=fused, native_routing=native_routing, glu_blocks=glu_blocks,
                    native_glu_grad=native_glu_grad, native_router_grad=native_router_grad, wide_routing=wide_routing,
                    w3_blocks=w3_blocks, w3_grad_blocks=w3_grad_blocks, w3_glu_blocks=w3_glu_blocks,
-                   grad_blocks256=grad_blocks256)
+                   grad_blocks256=grad_blocks256, w3_grad_blocks256=w3_grad_blocks256)
 
     def forward(self, hidden: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor) -> torch.Tensor:
         if self.native_routing:
@@ -537,21 +550,31 @@ class FluteExperts(torch.nn.Module):
             return False
         return self.grad_blocks256
 
+    def _w3_grad_blocks256(self, *stacks):
+        """The ops' `w3_grad_blocks256` for a launch over `stacks`: the module's, under `_w3_grad_blocks`' rule for learnable stacks."""
+        if self.w3_grad_blocks256 is not False and any(isinstance(m, LearnableGroupedFluteLinear) for m in stacks):
+            if self.w3_grad_blocks256 is True:
+                raise ValueError("FluteExperts: w3_grad_blocks256=True, but a stack is learnable (freeze_experts first, or "
+                                 "w3_grad_blocks256='auto')")
+            return False
+        return self.w3_grad_blocks256
+
     def _plain(self, stack, x_sorted, offsets):
         """One plain launch of the unfused forward: the stack's own forward, or with `w3_blocks` taken its 3-bit block op; with
-        `w3_grad_blocks` the public op of either with that keyword, with `grad_blocks256` `qgemm_grouped` with that one."""
+        `w3_grad_blocks` or `w3_grad_blocks256` the public op of either with those keywords, with `grad_blocks256` `qgemm_grouped`
+        with that one."""
         num_sms = _stack_num_sms(stack, x_sorted.device)
         blocks256 = self._grad_blocks256(stack)
         if blocks256 is not False:                              # (4- / 2-bit stacks: none of the 3-bit keywords is set)
             return flute_amd.qgemm_grouped(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits,
                                            stack.group_size, stack.template_id, num_sms, grad_blocks256=blocks256)
-        grad_blocks = self._w3_grad_blocks(stack)
+        grad_blocks, grad_blocks256 = self._w3_grad_blocks(stack), self._w3_grad_blocks256(stack)
         w3 = self._takes_w3_blocks(stack, "plain", x_sorted.shape[0], num_sms, x_sorted.dtype)
-        if not w3 and grad_blocks is False:
+        if not w3 and grad_blocks is False and grad_blocks256 is False:
             return stack(x_sorted, offsets)
         op = flute_amd.qgemm_grouped_w3_blocks if w3 else flute_amd.qgemm_grouped
         return op(x_sorted, offsets, stack.weight, stack.scales, stack.tables2, stack.num_bits, stack.group_size,
-                  stack.template_id, num_sms, w3_grad_blocks=grad_blocks)
+                  stack.template_id, num_sms, w3_grad_blocks=grad_blocks, w3_grad_blocks256=grad_blocks256)
 
     def _fused_ops(self, glu_blocks: bool = False, w3_down: bool = False, w3_glu: bool = False):
         """The two fused launches: the public ops, or - when a stack is learnable - the entry points that also give the
@@ -561,7 +584,7 @@ class FluteExperts(torch.nn.Module):
         `w3_down`: the weighted launch on the 3-bit block form (`qgemm_grouped_weighted_w3_blocks`).
         `w3_glu`: the GLU launch on the 3-bit block form (`qgemm_grouped_glu_w3_blocks`; `_takes_w3_glu_blocks`: no stack is learnable).
         The module's `native_glu_grad` rides on whichever GLU entry that is, its `native_router_grad` on the weighted one, its
-        `w3_grad_blocks` and `grad_blocks256` on the public ops of both (the learnable entries have no such keywords)."""
+        `w3_grad_blocks`, `grad_blocks256` and `w3_grad_blocks256` on the public ops of both (the learnable entries have no such keywords)."""
         gate, up, down = self.gate, self.up, self.down
         has = [_has_codebook(m) for m in (gate, up, down)]
         if has[0] != has[1]:
@@ -587,6 +610,9 @@ class FluteExperts(torch.nn.Module):
         if self._grad_blocks256(gate, up, down) is not False:   # (likewise)
             glu = functools.partial(glu, grad_blocks256=self.grad_blocks256)
             weighted = functools.partial(weighted, grad_blocks256=self.grad_blocks256)
+        if self._w3_grad_blocks256(gate, up, down) is not False:
+            glu = functools.partial(glu, w3_grad_blocks256=self.w3_grad_blocks256)
+            weighted = functools.partial(weighted, w3_grad_blocks256=self.w3_grad_blocks256)
         return glu, weighted
 
     def _forward_native(self, hidden, topk_ids, topk_weights):

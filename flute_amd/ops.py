@@ -518,7 +518,7 @@ def _require_w3_blocks(name, input, weight, scales, layer):
 
 def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                   table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                  form=None, w3_grad_blocks=False, grad_blocks256=False) -> torch.Tensor:
+                  form=None, w3_grad_blocks=False, grad_blocks256=False, w3_grad_blocks256=False) -> torch.Tensor:
     """`qgemm` for the E experts of a mixture-of-experts layer in one launch: out[r] = input[r] @ W_e^T for the rows
     r in [offsets[e], offsets[e + 1]).  `input` [T, K] holds the rows sorted by expert, `offsets` is an int32 CUDA tensor
     of E + 1 elements (0, non-decreasing, T last), `weight` [E, P, K], `scales` [E, N, K / g] and `table2`
@@ -536,35 +536,43 @@ def qgemm_grouped(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tens
     `flute_amd.dev.grouped_input_grad_w3_blocks_form` says "blocks".  The bits of dX are the same in all three.
     `grad_blocks256` (4- / 2-bit stacks only) is read by the backward only: False (the default) - dX is `qgemm_grouped_input_grad`;
     True - `qgemm_grouped_input_grad_blocks256`, the 256-row block form (raises where K % 256 != 0); "auto" - that launch where
-    `flute_amd.dev.grouped_input_grad_blocks256_form` says "blocks256".  The bits of dX are the same in all three."""
+    `flute_amd.dev.grouped_input_grad_blocks256_form` says "blocks256".  The bits of dX are the same in all three.
+    `w3_grad_blocks256` (3-bit stacks only) is read by the backward only: False (the default) - `w3_grad_blocks` decides; True -
+    `qgemm_grouped_input_grad_w3_blocks256`, the 3-bit 256-row block form (raises where K % 256 != 0), whatever `w3_grad_blocks`
+    says; "auto" - that launch where `flute_amd.dev.grouped_input_grad_w3_blocks256_form` says "blocks256", else as `w3_grad_blocks`
+    decides.  The bits of dX are the same again."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped", w3_grad_blocks, num_bits)
     _check_grad_blocks256("qgemm_grouped", grad_blocks256, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped", w3_grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form, w3_grad_blocks, grad_blocks256)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, form, w3_grad_blocks,
+                                      grad_blocks256 or w3_grad_blocks256)
     return _launch_plain(input, offsets, weight, scales, table2, layer, form)
 
 
 def qgemm_grouped_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                             table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                            w3_grad_blocks=False) -> torch.Tensor:
+                            w3_grad_blocks=False, w3_grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped` for stacks of 3-bit experts on the block form, for prefill and training row counts: the same operands,
     formula and rounding (include/flute_amd.h, flute_qgemm_grouped_w3_blocks) on 128-row x 256-column blocks of the dense 3-bit
     prefill kernel - all of K in one fp32 accumulator of the matrix core, a weight dequantised once per 128 rows (qgemm_block3.h,
     GM = 1).  Same validation, same autograd (the backward's kernels do not depend on which kernel ran the forward; the 3-bit
-    input gradient is the slab form unless `w3_grad_blocks`, as `qgemm_grouped`'s, says otherwise).  Equal arguments give equal bits; the bits equal `qgemm_grouped`'s on exactly
+    input gradient is the slab form unless `w3_grad_blocks` or `w3_grad_blocks256`, as `qgemm_grouped`'s, say otherwise).  Equal arguments give equal bits; the bits equal `qgemm_grouped`'s on exactly
     representable inputs and may differ elsewhere.  A layer the form does not serve raises ValueError before anything is launched;
     `flute_amd.dev.grouped_w3_blocks_form` tells where the form pays."""
     _validate_grouped(input, offsets, weight, scales, table2, num_bits, group_size)
     layer = (num_bits, group_size, template_id, num_sms)
     _require_w3_blocks("qgemm_grouped_w3_blocks", input, weight, scales, layer)
     _check_w3_grad_blocks("qgemm_grouped_w3_blocks", w3_grad_blocks, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped_w3_blocks", w3_grad_blocks256, num_bits)
     if _records_grad(input, scales, table2):
         _refuse_stack_grads("qgemm_grouped_w3_blocks", scales, table2)
-        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, _W3_BLOCKS, w3_grad_blocks)
+        return _GroupedFunction.apply(input, scales, None, offsets, weight, table2, layer, _W3_BLOCKS, w3_grad_blocks,
+                                      w3_grad_blocks256)
     return _launch_plain(input, offsets, weight, scales, table2, layer, _W3_BLOCKS)
 
 
@@ -624,7 +632,7 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
                       gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                       up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
                       rows=None, pos=None, form=None, native_glu_grad: bool = False, w3_grad_blocks=False,
-                      grad_blocks256=False) -> torch.Tensor:
+                      grad_blocks256=False, w3_grad_blocks256=False) -> torch.Tensor:
     """The gated half of a mixture-of-experts MLP in one launch: out[r] = silu(x_r @ Wgate_e^T) * (x_r @ Wup_e^T) for
     the rows r in [offsets[e], offsets[e + 1]), x_r = input[rows[r]] (`rows`: an int32 CUDA tensor of R entries, each
     clamped to input's rows by the kernel; None: x_r = input[r]).  Gate and up are two stacks as `qgemm_grouped` takes
@@ -640,19 +648,20 @@ def qgemm_grouped_glu(input: torch.Tensor, offsets: torch.Tensor, gate_weight: t
     as before; True runs `moe_gather` and `swiglu_grad` in their place (two launches, g and u never widened to fp32 tensors),
     whose bits differ from the torch chain's within `flute_swiglu_grad`'s error account.  The forward's bits do not depend on it.
     `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's pair-form input-gradient launch on 3-bit stacks;
-    `grad_blocks256` as `qgemm_grouped`'s: the same on 4- / 2-bit stacks."""
+    `grad_blocks256` as `qgemm_grouped`'s: the same on 4- / 2-bit stacks; `w3_grad_blocks256` as `qgemm_grouped`'s."""
     _validate_grouped_glu(input, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2,
                           num_bits, group_size, rows)
     _validate_grouped_glu_pos(input, rows, pos)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped_glu", w3_grad_blocks, num_bits)
     _check_grad_blocks256("qgemm_grouped_glu", grad_blocks256, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped_glu", w3_grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
                                          gate_table2, up_weight, up_table2, layer, form, bool(native_glu_grad), w3_grad_blocks,
-                                         grad_blocks256)
+                                         grad_blocks256 or w3_grad_blocks256)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        form)
 
@@ -686,12 +695,13 @@ def qgemm_grouped_glu_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_we
 def qgemm_grouped_glu_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, gate_weight: torch.Tensor, gate_scales: torch.Tensor,
                                 gate_table2: torch.Tensor, up_weight: torch.Tensor, up_scales: torch.Tensor,
                                 up_table2: torch.Tensor, num_bits: int, group_size: int, template_id: int, num_sms=None,
-                                rows=None, pos=None, native_glu_grad: bool = False, w3_grad_blocks=False) -> torch.Tensor:
+                                rows=None, pos=None, native_glu_grad: bool = False, w3_grad_blocks=False,
+                                w3_grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped_glu` for stacks of 3-bit experts on the block form, for prefill and training row counts: the same operands,
     formula and rounding (include/flute_amd.h, flute_qgemm_grouped_glu_w3_blocks) on 128-row x 256-column blocks of the dense 3-bit
     prefill kernel - all of K for gate, then all of K for up, in two fp32 accumulators of the matrix core, a weight dequantised
     once per 128 rows (qgemm_block3.h, GM = 3).  Same validation and autograd as `qgemm_grouped_glu_blocks` (`native_glu_grad`,
-    and `w3_grad_blocks` as on the sibling 3-bit ops); the backward's recompute of gate and up runs on the 3-bit block launches
+    and `w3_grad_blocks`, `w3_grad_blocks256` as on the sibling 3-bit ops); the backward's recompute of gate and up runs on the 3-bit block launches
     (`qgemm_grouped_w3_blocks`'s kernel) where they serve the gathered rows - they do unless R * K * 2 nears 2^32 - else as
     `qgemm_grouped` chooses.  Equal arguments give equal bits; the bits equal `qgemm_grouped_glu`'s on exactly representable inputs
     and may differ elsewhere.  A shape the form does not serve raises ValueError before anything is launched;
@@ -702,11 +712,12 @@ def qgemm_grouped_glu_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, gate
     layer = (num_bits, group_size, template_id, num_sms)
     _require_glu_blocks("qgemm_grouped_glu_w3_blocks", input, rows, gate_weight, gate_scales, layer, _GLU_W3_BLOCKS)
     _check_w3_grad_blocks("qgemm_grouped_glu_w3_blocks", w3_grad_blocks, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped_glu_w3_blocks", w3_grad_blocks256, num_bits)
     if _records_grad(input, gate_scales, gate_table2, up_scales, up_table2):
         _refuse_stack_grads("qgemm_grouped_glu_w3_blocks", gate_scales, gate_table2, up_scales, up_table2)
         return _GroupedGluFunction.apply(input, gate_scales, up_scales, None, None, rows, pos, offsets, gate_weight,
                                          gate_table2, up_weight, up_table2, layer, _GLU_W3_BLOCKS, bool(native_glu_grad),
-                                         w3_grad_blocks)
+                                         w3_grad_blocks, w3_grad_blocks256)
     return _launch_glu(input, rows, offsets, gate_weight, gate_scales, gate_table2, up_weight, up_scales, up_table2, layer,
                        _GLU_W3_BLOCKS)
 
@@ -797,7 +808,7 @@ def _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weigh
 def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                            table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
                            template_id: int, num_sms=None, form=None, native_router_grad: bool = False,
-                           w3_grad_blocks=False, grad_blocks256=False) -> torch.Tensor:
+                           w3_grad_blocks=False, grad_blocks256=False, w3_grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped` with the routing weight in its epilogue: out[r] = row_weight[r] * (input[r] @ W_e^T), the
     product in fp32 before the one rounding (`row_weight`: an fp32 CUDA tensor of T entries), and the rows from
     offsets[E] on - rows no expert serves - returned as zeros whatever the routing.  No host synchronise; a native
@@ -808,35 +819,38 @@ def qgemm_grouped_weighted(input: torch.Tensor, offsets: torch.Tensor, weight: t
     `moe_weight_grad` launch in their place - d input has the same bits, d row_weight is summed in `flute_moe_weight_grad`'s
     fixed order, not torch's.  The forward's bits do not depend on it.
     `w3_grad_blocks` as `qgemm_grouped`'s: the kernel of the backward's input-gradient launch on 3-bit stacks; `grad_blocks256`
-    as `qgemm_grouped`'s: the same on 4- / 2-bit stacks."""
+    as `qgemm_grouped`'s: the same on 4- / 2-bit stacks; `w3_grad_blocks256` as `qgemm_grouped`'s."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     _grouped_form_id(form)
     _check_w3_grad_blocks("qgemm_grouped_weighted", w3_grad_blocks, num_bits)
     _check_grad_blocks256("qgemm_grouped_weighted", grad_blocks256, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped_weighted", w3_grad_blocks256, num_bits)
     layer = (num_bits, group_size, template_id, num_sms)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted", scales, table2)
         return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, form,
-                                              bool(native_router_grad), w3_grad_blocks, grad_blocks256)
+                                              bool(native_router_grad), w3_grad_blocks,
+                                              grad_blocks256 or w3_grad_blocks256)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, form)
 
 
 def qgemm_grouped_weighted_w3_blocks(input: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, scales: torch.Tensor,
                                      table2: torch.Tensor, row_weight: torch.Tensor, num_bits: int, group_size: int,
                                      template_id: int, num_sms=None, native_router_grad: bool = False,
-                                     w3_grad_blocks=False) -> torch.Tensor:
+                                     w3_grad_blocks=False, w3_grad_blocks256=False) -> torch.Tensor:
     """`qgemm_grouped_weighted` for stacks of 3-bit experts on the block form (`qgemm_grouped_w3_blocks`'s kernel with the routing
     weight in its epilogue, qgemm_block3.h GM = 2): out[r] = round_T(row_weight[r] * acc32), the rows from offsets[E] on zeros.
-    Same validation and autograd as `qgemm_grouped_weighted` (`native_router_grad` and `w3_grad_blocks` as there); a layer the form does not serve
+    Same validation and autograd as `qgemm_grouped_weighted` (`native_router_grad`, `w3_grad_blocks` and `w3_grad_blocks256` as there); a layer the form does not serve
     raises ValueError before anything is launched."""
     _validate_grouped_weighted(input, offsets, weight, scales, table2, row_weight, num_bits, group_size)
     layer = (num_bits, group_size, template_id, num_sms)
     _require_w3_blocks("qgemm_grouped_weighted_w3_blocks", input, weight, scales, layer)
     _check_w3_grad_blocks("qgemm_grouped_weighted_w3_blocks", w3_grad_blocks, num_bits)
+    _check_w3_grad_blocks256("qgemm_grouped_weighted_w3_blocks", w3_grad_blocks256, num_bits)
     if _records_grad(input, row_weight, scales, table2):
         _refuse_stack_grads("qgemm_grouped_weighted_w3_blocks", scales, table2)
         return _GroupedWeightedFunction.apply(input, row_weight, scales, None, offsets, weight, table2, layer, _W3_BLOCKS,
-                                              bool(native_router_grad), w3_grad_blocks)
+                                              bool(native_router_grad), w3_grad_blocks, w3_grad_blocks256)
     return _launch_weighted(input, offsets, weight, scales, table2, row_weight, layer, _W3_BLOCKS)
 
 
@@ -1042,7 +1056,7 @@ def qgemm_grouped_input_grad_blocks256(grad_output: torch.Tensor, offsets: torch
     return _launch_grouped("qgemm_grouped_input_grad_blocks256", tensors, weight, (R,), N, (R, weight.shape[2]), layer)
 
 
-_GROUPED_INPUT_GRAD_FORM_BLOCKS256 = 3           # include/flute_amd.h: an answer of flute_qgemm_grouped_input_grad_blocks256_form only
+_GROUPED_INPUT_GRAD_FORM_BLOCKS256 = 3           # include/flute_amd.h: an answer of the two _blocks256_form queries only
 
 
 def _check_grad_blocks256(name, grad_blocks256, num_bits):
@@ -1054,23 +1068,76 @@ def _check_grad_blocks256(name, grad_blocks256, num_bits):
     return grad_blocks256
 
 
+def _require_input_grad_w3_blocks256(grad_output, weight, layer):
+    """Raise ValueError where flute_qgemm_grouped_input_grad_w3_blocks256 does not serve the shape.  Host only, before anything is
+    launched: the entry refuses a shape before it looks at a pointer, so it is asked with null pointers."""
+    num_bits, group_size, template_id, _ = layer
+    E, P, K = weight.shape
+    R, N = grad_output.shape
+    if R >= 2 ** 31:
+        raise ValueError
+    rc = _lib.get().flute_qgemm_grouped_input_grad_w3_blocks256(_DTYPE_ID[grad_output.dtype], num_bits, group_size, E, R, N, K, P,
+                                                                template_id, *(None,) * 11, 0, None)
+    if rc in (_FLUTE_ERR_SHAPE, _FLUTE_ERR_NUM_BITS):
+        raise ValueError("flute_amd.qgemm_grouped_input_grad_w3_blocks256: the 3-bit 256-row block form of the input gradient is not "
+                         "eligible for this layer (include/flute_amd.h, flute_qgemm_grouped_input_grad_w3_blocks256: 3 bits, "
+                         "K % 256 == 0, at least one expert and one row)")
+    if rc not in (0, _FLUTE_ERR_NULL):
+        _lib.check(rc)
+
+
+def qgemm_grouped_input_grad_w3_blocks256(grad_output: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                                          scales: torch.Tensor, table2: torch.Tensor, num_bits: int, group_size: int,
+                                          template_id: int, num_sms=None, row_weight=None, grad_output2=None, weight2=None,
+                                          scales2=None, table22=None) -> torch.Tensor:
+    """`qgemm_grouped_input_grad` for stacks of 3-bit experts on the 256-row block form, for training row counts: the same operands
+    (single, row-weighted and pair forms), formula and rounding on one 256-row block of an expert x 256 k per workgroup
+    (qgemm_grouped_input_grad_w3_blocks256.h: a decoded weight fragment feeds twice the MFMAs of `qgemm_grouped_input_grad_w3_blocks`),
+    with the same bits as `qgemm_grouped_input_grad` on all inputs.  Same validation; a layer the form does not serve (not 3-bit,
+    K % 256 != 0, no rows) raises ValueError before anything is launched; `flute_amd.dev.grouped_input_grad_w3_blocks256_form` tells
+    where the form pays.  Not differentiable itself."""
+    _validate_grouped_input_grad(grad_output, offsets, weight, scales, table2, num_bits, group_size, row_weight,
+                                 grad_output2, weight2, scales2, table22)
+    layer = (num_bits, group_size, template_id, num_sms)
+    _require_input_grad_w3_blocks256(grad_output, weight, layer)
+    tensors = (grad_output, offsets, weight, scales, table2, row_weight, grad_output2, weight2, scales2, table22)
+    if _records_grad(*tensors):
+        raise RuntimeError("flute_amd.qgemm_grouped_input_grad_w3_blocks256: the backward is once-differentiable (no double backward)")
+    R, N = grad_output.shape
+    return _launch_grouped("qgemm_grouped_input_grad_w3_blocks256", tensors, weight, (R,), N, (R, weight.shape[2]), layer)
+
+
+def _check_w3_grad_blocks256(name, w3_grad_blocks256, num_bits):
+    """The `w3_grad_blocks256` keyword of the grouped forward ops: False, True or "auto", and anything but False on 3-bit stacks only."""
+    if not (w3_grad_blocks256 is False or w3_grad_blocks256 is True
+            or (isinstance(w3_grad_blocks256, str) and w3_grad_blocks256 == "auto")):
+        raise ValueError(f"flute_amd.{name}: w3_grad_blocks256 is False, True or 'auto', not {w3_grad_blocks256!r}")
+    if w3_grad_blocks256 is not False and num_bits != 3:
+        raise ValueError(f"flute_amd.{name}: w3_grad_blocks256 selects the input-gradient kernel of 3-bit stacks; num_bits is {num_bits}")
+    return w3_grad_blocks256
+
+
 def _backward_input_grad(w3_grad_blocks, grad_blocks256, grad_output, offsets, weight, scales, table2, layer, **operands):
     """The input-gradient launch of the plain, GLU (pair form) and weighted backward: `qgemm_grouped_input_grad`, or - the forward
     ops' `w3_grad_blocks` True, or "auto" where flute_qgemm_grouped_input_grad_w3_blocks_form says blocks for these shapes (host
-    only) - `qgemm_grouped_input_grad_w3_blocks`, or - `grad_blocks256` True (and a row to serve), or "auto" where
-    flute_qgemm_grouped_input_grad_blocks256_form says so - `qgemm_grouped_input_grad_blocks256`.  The bits are the same whichever runs."""
+    only) - `qgemm_grouped_input_grad_w3_blocks`, or - `grad_blocks256`, the forward ops' keyword of that name on 4- / 2-bit stacks
+    and their `w3_grad_blocks256` on 3-bit ones (at most one of the two is set), True (and a row to serve), or "auto" where the
+    width's query, flute_qgemm_grouped_input_grad_blocks256_form / _w3_blocks256_form, says so - the width's 256-row launch,
+    `qgemm_grouped_input_grad_blocks256` / `_w3_blocks256`, ahead of `w3_grad_blocks`.  The bits are the same whichever runs."""
     if grad_blocks256 is not False and grad_output.shape[0] > 0:
+        w3 = layer[0] == 3
         take256 = grad_blocks256 is True
         if not take256:
             (E, _, K), (R, N) = weight.shape, grad_output.shape
-            rc = _lib.get().flute_qgemm_grouped_input_grad_blocks256_form(
-                int("grad_output2" in operands), _DTYPE_ID[grad_output.dtype], layer[0], layer[1], E, R, N, K, layer[2],
-                _num_sms(layer[3], grad_output.device))
+            query = _lib.get().flute_qgemm_grouped_input_grad_w3_blocks256_form if w3 else _lib.get().flute_qgemm_grouped_input_grad_blocks256_form
+            rc = query(int("grad_output2" in operands), _DTYPE_ID[grad_output.dtype], *(() if w3 else (layer[0],)), layer[1], E, R, N, K,
+                       layer[2], _num_sms(layer[3], grad_output.device))
             if rc < 0:
                 _lib.check(rc)
             take256 = rc == _GROUPED_INPUT_GRAD_FORM_BLOCKS256
         if take256:
-            return qgemm_grouped_input_grad_blocks256(grad_output, offsets, weight, scales, table2, *layer, **operands)
+            op256 = qgemm_grouped_input_grad_w3_blocks256 if w3 else qgemm_grouped_input_grad_blocks256
+            return op256(grad_output, offsets, weight, scales, table2, *layer, **operands)
     take = w3_grad_blocks is True
     if w3_grad_blocks == "auto":
         (E, _, K), (R, N) = weight.shape, grad_output.shape

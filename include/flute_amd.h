@@ -42,6 +42,8 @@ extern "C" {
  *    flute_qgemm_grouped_input_grad_w3_blocks_form
  *    the 256-row block form of the grouped input gradient behind its own entries: flute_qgemm_grouped_input_grad_blocks256,
  *    flute_qgemm_grouped_input_grad_blocks256_form
+ *    the same for 3-bit stacks behind their own entries: flute_qgemm_grouped_input_grad_w3_blocks256,
+ *    flute_qgemm_grouped_input_grad_w3_blocks256_form
  *    the block form of the fused SwiGLU launch for 3-bit stacks behind its own entries: flute_qgemm_grouped_glu_w3_blocks,
  *    flute_qgemm_grouped_glu_w3_blocks_form
  *    the two streams of the fused SwiGLU launch's backward: flute_swiglu_grad, flute_moe_gather
@@ -670,6 +672,48 @@ int flute_qgemm_grouped_input_grad_blocks256(int dtype, int num_bits, int group_
 #define FLUTE_GROUPED_INPUT_GRAD_BLOCKS256_MIN_MEAN_ROWS_PARTIAL_B2 0  /* 2 bits, not full: the launch wins at no swept mean */
 int flute_qgemm_grouped_input_grad_blocks256_form(int pair, int dtype, int num_bits, int group_size, int E, int R, int N, int K,
                                                   int template_id, int num_sms);
+
+/* The 256-row block form of the grouped input gradient for stacks of 3-bit experts, behind entries of their own:
+ * flute_qgemm_grouped_input_grad_w3_blocks with one 256-row block of one expert x 256 k per workgroup, the grid
+ * floor((R + 255 E) / 256) x K / 256 from (E, R, K) alone (csrc/qgemm_grouped_input_grad_w3_blocks256.h): a decoded weight fragment
+ * feeds twice the MFMAs of the 3-bit 128-row block form.  The arguments, the single, row-weighted and pair forms, the formula,
+ * clamping, the zero rows from offsets[E] on, determinism, capture and the block form's malformed-table contract (256-row blocks in
+ * place of 128-row ones) are as described above, and so is the order in which every output sums over N: the launch gives EQUAL BITS
+ * to flute_qgemm_grouped_input_grad on all inputs.  flute_qgemm_grouped_input_grad_w3_blocks, flute_qgemm_grouped_input_grad_blocks256
+ * (which still refuses 3 bits) and the older entries keep their behaviour; a caller opts in by calling this.
+ * It serves: num_bits 3, E >= 1, R >= 1, K a positive multiple of 256, R <= 2^31 - 513 and a 31-bit grid.
+ * Refusals, before anything is enqueued or dereferenced, in this order: flute_qgemm_grouped_input_grad's (dtype, the layer checks,
+ * FLUTE_ERR_SHAPE for P or a negative E / R, FLUTE_ERR_SHAPE for a row_weight together with any pointer of the pair form);
+ * FLUTE_ERR_NUM_BITS for num_bits 4 or 2; FLUTE_ERR_SHAPE for a shape outside the list above; then FLUTE_ERR_NULL as the old entry
+ * gives it.  num_sms is accepted for symmetry and not used. */
+int flute_qgemm_grouped_input_grad_w3_blocks256(int dtype, int num_bits, int group_size, int E, int R, int N, int K, int P,
+                                                int template_id, const void* dY, const void* offsets, const void* Q, const void* S,
+                                                const void* QM2, const float* row_weight, const void* dY2, const void* Q2,
+                                                const void* S2, const void* QM22, void* dX, int num_sms, void* stream);
+
+/* Which launch a caller should take for the input gradient of a stack of 3-bit experts: FLUTE_GROUPED_INPUT_GRAD_FORM_BLOCKS256 (the
+ * entry above) where the shape is in its list and the mean rows per expert, R / E, is at least
+ * FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS - where one row block per expert already fills the chip,
+ * E * (K / 256) >= num_sms (< 1: 256) - or FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS_PARTIAL where it does not (a constant
+ * of 0: never on that kind of shape); else what flute_qgemm_grouped_input_grad_w3_blocks_form answers (_SLABS, or _BLOCKS for
+ * flute_qgemm_grouped_input_grad_w3_blocks), or the negative error the old entries would refuse the layer with.  Host only: no
+ * pointers, nothing is enqueued; pair != 0: the pair form (the same rule); P is taken as 3 * N / 16. */
+/* Measured (profiles/grouped_moe_input_grad_blocks256_w3.json, "w3 b256 threshold sweep": W3G64, us of the 3-bit 128-row block launch /
+ * this launch, two alternating passes each, R / E = 128, 256, 512, 1024, 2048, even counts, fp16; the routed draws and bf16 are in
+ * the file, spreads below 1.5 %).  Each constant is the smallest swept mean from which this launch is faster in every alternation on
+ * every swept stack of its kind, on even and routed counts, fp16 and bf16; 0: there is no such mean and the query never answers
+ * _BLOCKS256.
+ *   the chip full: Mixtral down (E 8, N 4096, K 14336) 280 / 294, 542 / 501, 918 / 984, 1783 / 1691, 3548 / 3317 - faster by 5 - 7 %
+ *                 from 1024 on, even and routed, fp16 and bf16;
+ *                 E 64 2048 x 2048 222 / 221, 376 / 628, 692 / 1209, 1314 / 2345, 2654 / 4585 - 1.6 - 1.8 x slower from 256 on: never
+ *   not full: Mixtral gate / up (E 8, N 14336, K 4096) 466 / 478, 469 / 834, 924 / 1015, 1873 / 1964, 3853 / 3867;
+ *                 its pair form 954 / 973, 960 / 1687, 1904 / 2013, 3827 / 3901, 7880 / 7695 - ahead on one even line, behind on the
+ *                 routed draw of the same mean: never
+ * A caller whose stack is shaped like Mixtral's down projection opts in with the entry above. */
+#define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS 0          /* E * (K / 256) >= num_sms: slower at every swept mean on E 64 2048 x 2048 */
+#define FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS_PARTIAL 0  /* fewer workgroups per row block than compute units: not faster on gate / up */
+int flute_qgemm_grouped_input_grad_w3_blocks256_form(int pair, int dtype, int group_size, int E, int R, int N, int K, int template_id,
+                                                     int num_sms);
 
 /* The gradient of the scales of a stack flute_qgemm_grouped multiplies by, in ONE launch: flute_qgemm_scale_grad for every
  * expert over the rows the device-side table gives it.  With b_e = clamp(offsets[e], 0, R), e_e = clamp(offsets[e + 1], 0, R):

@@ -8,6 +8,7 @@
     python tools/grouped_bench.py --mode input_grad [--only-swiglu-grad] [--out profiles/grouped_moe_input_grad_blocks.json]
     python tools/grouped_bench.py --mode input_grad --only w3        (profiles/grouped_moe_input_grad_blocks_w3.json)
     python tools/grouped_bench.py --mode input_grad --only b256      (profiles/grouped_moe_input_grad_blocks256.json)
+    python tools/grouped_bench.py --mode input_grad --only w3_b256   (profiles/grouped_moe_input_grad_blocks256_w3.json)
     python tools/grouped_bench.py --mode scale_grad [--processes 3] [--out profiles/grouped_moe_scale_grad.json]
     python tools/grouped_bench.py --mode table_grad [--processes 3] [--out profiles/grouped_moe_table_grad.json]
     python tools/grouped_bench.py --mode prefill [--out profiles/grouped_moe_prefill.json]
@@ -593,9 +594,13 @@ def ig_counts(rows, experts, seed):
     return torch.bincount(ids.reshape(-1), minlength=experts).tolist()
 
 
+OWN_IG_OPS = {"w3_blocks": "qgemm_grouped_input_grad_w3_blocks", "b256": "qgemm_grouped_input_grad_blocks256",
+              "w3_b256": "qgemm_grouped_input_grad_w3_blocks256"}
+
+
 class InputGrad:
     """`copies` stacks of `experts` packed layers [N, K] (`pair`: two of them, and two dY); step(i) is dX [R, K] = dY [R, N] @ W_e on
-    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto", or "w3_blocks", the 3-bit block launch, or "b256", the 256-row block launch - or, "loop", the per-expert loop of dequantize + mm on row
+    copy i: one grouped launch - `how` = "slabs" / "blocks" / "auto", or "w3_blocks", the 3-bit block launch, or "b256" / "w3_b256", the 256-row block launches - or, "loop", the per-expert loop of dequantize + mm on row
     ranges the host knows.  `weights`: another InputGrad of the same stack whose weight copies are shared."""
 
     def __init__(self, experts, N, K, counts, copies, device, how, bits=BITS, dtype=DTYPE, pair=False, weights=None):
@@ -628,8 +633,8 @@ class InputGrad:
         c = i % self.Q[0].shape[0]
         if self.how != "loop":
             second = dict(grad_output2=self.dY[1], weight2=self.Q[1][c], scales2=self.S[1][c], table22=self.tables2) if self.pair else {}
-            if self.how in ("w3_blocks", "b256"):         # the 3-bit and the 256-row block launch behind their own ops
-                op = self.fa.qgemm_grouped_input_grad_w3_blocks if self.how == "w3_blocks" else self.fa.qgemm_grouped_input_grad_blocks256
+            if self.how in OWN_IG_OPS:                    # the 3-bit and the 256-row block launches behind their own ops
+                op = getattr(self.fa, OWN_IG_OPS[self.how])
                 return op(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G, self.tid, self.num_sms,
                           **second)
             return self.fa.qgemm_grouped_input_grad(self.dY[0], self.offsets, self.Q[0][c], self.S[0][c], self.tables2, self.bits, G,
@@ -1444,6 +1449,68 @@ def main_input_grad_b256(args, device):
     print("wrote", args.out)
 
 
+def main_input_grad_w3_b256(args, device):
+    """--mode input_grad --only w3_b256 (profiles/grouped_moe_input_grad_blocks256_w3.json): the 3-bit 256-row block launch against
+    the 3-bit 128-row block launch - on B256_LOOP_LINES against the per-expert loop too -, alternating in one process; the sweep
+    behind FLUTE_GROUPED_INPUT_GRAD_W3_BLOCKS256_MIN_MEAN_ROWS[_PARTIAL].  Every line checks the new launch's bits against the slab
+    form's.  fp16 runs first: a run cut short keeps what the rule rests on."""
+    from statistics import median
+    from flute_amd import dev
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "replays_us"}), flush=True)
+        with open(args.out, "w") as f:                # (rewritten after every line: a long run that is cut short keeps its lines)
+            json.dump({"what": "grouped input gradient of 3-bit stacks (W3G64) at training row counts: the 128-row block launch "
+                               "(flute_amd.qgemm_grouped_input_grad_w3_blocks), the 256-row block launch "
+                               "(flute_amd.qgemm_grouped_input_grad_w3_blocks256) and, on the loop lines, a per-expert loop of "
+                               "flute_amd.dequantize + torch.mm; hipGraph replays, device-clock stamps, cold caches, median of the "
+                               "replays, two alternating passes of each contender in one process",
+                       "config": {"group_size": G, "steps": args.steps, "warmup": args.warmup, "replays": args.replays,
+                                  "device": torch.cuda.get_device_name(device)}, "rows": rows}, f, indent=1)
+
+    def line(what, name, experts, N, K, pair, dt, counts, copies, first, loop):
+        dtype = getattr(torch, dt)
+        layers = {}
+        for how in ("w3_blocks", "w3_b256") + (("loop",) if loop else ()):
+            layers[how] = InputGrad(experts, N, K, counts, copies, device, how, 3, dtype, pair, weights=first)
+            first = first or layers[how]
+        slabs = InputGrad(experts, N, K, counts, copies, device, "slabs", 3, dtype, pair, weights=first).step(0)
+        equal = bool(torch.equal(layers["w3_b256"].step(0).view(torch.int16), slabs.view(torch.int16)))
+        del slabs
+        us, spread, replays = time_forms(layers, args)
+        row = {"what": what, "shape": name, "bits": 3, "dtype": dt, "pair": pair, "experts": experts, "N": N, "K": K,
+               "rows": sum(counts), "counts_min_max": [min(counts), max(counts)], "weight_copies": copies,
+               "fills_the_chip": experts * (K // 256) >= first.num_sms, "us": us,
+               "b256_over_blocks": round(us["w3_b256"] / us["w3_blocks"], 4),
+               "b256_faster_in_every_alternation": all(median(a) < median(b) for a, b in zip(replays["w3_b256"], replays["w3_blocks"])),
+               "spread": spread, "b256_bits_equal_slabs": equal,
+               "auto_form": dev.grouped_input_grad_w3_blocks256_form(experts, sum(counts), N, K, G, first.tid, first.num_sms, dtype, pair)}
+        if loop:
+            row.update(b256_over_loop=round(us["w3_b256"] / us["loop"], 4), blocks_over_loop=round(us["w3_blocks"] / us["loop"], 4))
+        emit(dict(row, replays_us=replays))
+        return first
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name, experts, N, K, nrows in B256_LOOP_LINES:
+        line("w3 b256 against the loop", name, experts, N, K, False, "float16", ig_counts(nrows, experts, seed=nrows + experts),
+             prefill_copies(experts, N, K, 3), None, True)
+        torch.cuda.empty_cache()
+    for dt in ("float16", "bfloat16"):
+        for name, experts, N, K, pair in B256_SWEEP_STACKS:
+            copies = prefill_copies(experts, N, K, 3, stacks=2 if pair else 1)
+            first = None
+            for mean in B256_SWEEP_MEANS:
+                for spread_name, counts in (("even", even_counts(mean * experts, experts)),
+                                            ("routed", ig_counts(mean * experts, experts, seed=mean + experts))):
+                    first = line("w3 b256 threshold sweep, %s counts, mean %d" % (spread_name, mean), name, experts, N, K, pair, dt,
+                                 counts, copies, first, False)
+            del first
+            torch.cuda.empty_cache()
+    print("wrote", args.out)
+
+
 def main_input_grad_forms(args, device):
     """--mode input_grad: the two forms of the grouped input gradient, the automatic rule and the per-expert loop, in one process."""
     from flute_amd import dev
@@ -2084,9 +2151,9 @@ def main():
     ap.add_argument("--routing-tokens", type=int, nargs="*", default=[1, 16, 64], help="--mode step / gate: the rows without the GEMMs")
     ap.add_argument("--processes", type=int, default=3, help="--mode step / gate: fresh processes, one after the other")
     ap.add_argument("--child", action="store_true", help="--mode step / gate: one of those processes (internal)")
-    ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS + ("b256",), default=None,
+    ap.add_argument("--only", nargs="*", choices=PREFILL_SECTIONS + ("b256", "w3_b256"), default=None,
                     help="--mode prefill: the sections to run (default: all) - " + ", ".join(PREFILL_SECTIONS) +
-                         "; --mode input_grad: w3 or b256, that section alone")
+                         "; --mode input_grad: w3, b256 or w3_b256, that section alone")
     ap.add_argument("--only-swiglu-grad", action="store_true",
                     help="--mode input_grad: its last section alone, the backward step with native_glu_grad off and on")
     ap.add_argument("--out", default=None)
@@ -2136,6 +2203,10 @@ def main():
         if args.only == ["b256"]:
             args.out = os.path.join(os.path.dirname(args.out), "grouped_moe_input_grad_blocks256.json")
             return main_input_grad_b256(args, device)
+        if args.only == ["w3_b256"]:
+            if args.out.endswith("grouped_moe_input_grad_blocks.json"):
+                args.out = os.path.join(os.path.dirname(args.out), "grouped_moe_input_grad_blocks256_w3.json")
+            return main_input_grad_w3_b256(args, device)
         return main_swiglu_grad(args, device) if args.only_swiglu_grad else main_input_grad_forms(args, device)
     rows = []
     bits = args.bits
